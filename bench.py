@@ -15,15 +15,26 @@ GPU each) -- the parent never touches a GPU -- and relays rank 0's one line.  Un
 (WORLD_SIZE set) the process is one of the ranks.  WORLD_SIZE != --gpus is an error, never a
 silent one-GPU run.
 
-Rank 0 prints ONE JSON line.  `roofline` prices the dominant kernel against the 8 TB/s HBM
-peak with algorithmic bytes from the per-frame counters (DESIGN.md "Measurement");
-`cpu_baseline` is the CPU oracle (oracle/, a scalar restatement of the reference's passes)
-timed on this host over the same frames, 1 thread.  One rank also reports, in the same line:
-`steady_leg` (100 frames after 10), `fuse_leg` (frames that actually fuse), `reference_path_leg`
-(preprocess = 1, host buffers: what the drop-in's SurfelMapping::processFrame executes) and
-`hd_leg` (BASELINE configs[2]: 1920x1080, 20 M seeded surfels).  N ranks report the rig
-aggregate as `value` (configs[4]: one camera per GPU), the consolidation into a single
-GlobalModel, and `sharded_leg` (configs[3]: ONE stream over the N GPUs).
+Rank 0 prints ONE JSON line.  A plain one-rank run sets up, warms up, times the K steps and prints
+it (`value`, `ms_per_step` = milliseconds of one timed step); the figures below that take runs of
+their own (roofline, kernels, CPU baselines, legs) come with `--full` only -- without it they are null
+or absent.  The N-rank line is unaffected by `--full`.  `roofline` prices the
+dominant kernel against the 8 TB/s HBM peak with algorithmic bytes from the per-frame counters
+(DESIGN.md "Measurement"); `cpu_baseline` is the CPU oracle (oracle/, a scalar restatement of the
+reference's passes) timed on this host over the same frames, 1 thread.  One rank also reports, in
+the same line: `steady_leg` (100 frames after 10), `fuse_leg` (frames that actually fuse),
+`reference_path_leg` (preprocess = 1, host buffers: what the drop-in's
+SurfelMapping::processFrame executes) and `hd_leg` (BASELINE configs[2]: 1920x1080, 20 M seeded
+surfels).  N ranks report the rig aggregate as `value` (configs[4]: one camera per GPU), the
+consolidation into a single GlobalModel, and `sharded_leg` (configs[3]: ONE stream over the N GPUs).
+
+`--dump-outputs DIR` (one rank) writes, after the timed steps, what the timed context holds after its last
+step (see dump_outputs); the frames are generated from --seed, so the same arguments give the same
+inputs and two builds can be compared output for output.
+
+The one-rank stream is a drive of DRIVE_FRAMES frames along the street; a run with more frames than
+that (warm-up + steps) empties the map with SurfelMapping::reset and drives the same frames again,
+so that any --steps fits the model's capacity (`config.drive` counts the resets in the timed steps).
 """
 from __future__ import annotations
 
@@ -49,6 +60,19 @@ from surfelmapping_amd import synth  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0   # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 METRIC = "frames/sec per GPU, 1242x375 KITTI-shaped RGB-D+semantic, full associate+fuse+merge"
+DUMP_MAX_ROWS = 1_000_000     # --dump-outputs: model rows written at most (48 MB of float32 + 8 MB of row indices)
+# One drive of the synthetic street: the model grows by ~55 k surfels a frame and after 410 frames holds 22 M of the 25 M
+# slots of max_sqrt_vertices = 5000.  A longer run drives the same frames again on an emptied map (SurfelMapping::reset
+# before every DRIVE_FRAMES-th frame), so any --steps fits the model and at most one drive of frames is generated.
+DRIVE_FRAMES = 410
+
+
+def drive_frame(k, restart):
+    """Index into the drive of frame k of the stream; the map is restarted first at the start of every drive but the first."""
+    i = k % DRIVE_FRAMES
+    if k and not i:
+        restart()
+    return i
 
 
 # ------------------------------------------------------------------------------------------------
@@ -273,14 +297,34 @@ def stage_frames(sm, frames, P):
     return out
 
 
-def run_leg(capi, cam, frames, K, Wm, cfg_kw, *, events=True, mode="device", seed_model=None, seed_tick=None, keep=False):
+def dump_outputs(sm, out_dir):
+    """--dump-outputs: what a caller of the timed path receives after its last frame, as .npy files in `out_dir`:
+      model.npy       float32 [m][12]  GlobalModel::downloadMap rows (sm_download_model_aos); all of them when there are at
+                                       most DUMP_MAX_ROWS, otherwise a fixed sample (seed 0, in slot order)
+      model_rows.npy  float64 [m]      the slot index of every row of model.npy
+      counts.npy      float64 [8]      count, offset, data_count, conflict_count, unstable_count, fused_count, visible_count, tick"""
+    os.makedirs(out_dir, exist_ok=True)
+    model = sm.download_model()
+    counts = sm.counts()
+    n = model.shape[0]
+    rows = np.arange(n) if n <= DUMP_MAX_ROWS else np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_ROWS, replace=False))
+    np.save(os.path.join(out_dir, "model.npy"), np.ascontiguousarray(model[rows], np.float32))
+    np.save(os.path.join(out_dir, "model_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "counts.npy"), np.array([counts[k] for k in ("count", "offset", "data_count", "conflict_count",
+                                                                               "unstable_count", "fused_count", "visible_count", "tick")],
+                                                          np.float64))
+
+
+def run_leg(capi, cam, frames, K, Wm, cfg_kw, *, events=True, mode="device", seed_model=None, seed_tick=None, keep=False,
+            dump=None):
     """K frames after Wm on an un-instrumented context (this is the leg's frames/s), then -- events=True -- the same frames
     again on a context that records a HIP event after every kernel (per-kernel durations for the roofline).
     mode: "device"     frames staged in HBM, sm_process_frame_device, no host wait inside the K frames (the metric's form);
           "host_sync"  sm_process_frame on host buffers: 2.8 MB H2D + a host wait per frame = the reference's processFrame;
           "host_async" sm_process_frame_async on host buffers: pinned staging, the copy of frame f+1 overlaps frame f;
           "device_sync" device-resident frames, host waits for the counters after every frame.
-    Returns a dict; with keep=True the timed context stays open under "sm"."""
+    Returns a dict; with keep=True the timed context stays open under "sm".  dump: a directory for dump_outputs of the timed
+    context after its last frame."""
     P = cam["width"] * cam["height"]
 
     def prime(sm):
@@ -312,21 +356,28 @@ def run_leg(capi, cam, frames, K, Wm, cfg_kw, *, events=True, mode="device", see
             pinned.append((a, b, c, pose))
         frames = pinned
     step = step_fn(sm, dptr)
+
+    def restart(ctx):
+        ctx.reset()
+        prime(ctx)
+    again = lambda: restart(sm)      # noqa: E731
     # no collector pause inside the timed region: with torch imported a full collection takes ~45 ms.  Collect BEFORE the
     # warm-up: a pause between warm-up and t0 lets the GPU clock down (+130 us on the first frames)
     gc.collect(); gc.disable()
     for k in range(Wm):
-        step(k)
+        step(drive_frame(k, again))
     sm.sync()
     t0 = time.perf_counter()
     for k in range(Wm, Wm + K):
-        step(k)
+        step(drive_frame(k, again))
     t_enq = time.perf_counter() - t0
     sm.sync()
     el = time.perf_counter() - t0
     gc.enable()
     res = {"fps": K / el, "ms": el / K * 1e3, "log": sm.read_frame_log(K), "counts": sm.counts(), "tim": None,
            "host_enqueue_ms": t_enq / K * 1e3}
+    if dump:
+        dump_outputs(sm, dump)
     if keep:
         res["sm"], res["dptr"] = sm, dptr
     else:
@@ -335,11 +386,12 @@ def run_leg(capi, cam, frames, K, Wm, cfg_kw, *, events=True, mode="device", see
         ev = capi.SurfelMap(capi.make_config(**cam, **cfg_kw, enable_timing=1))
         prime(ev)
         dp = stage_frames(ev, frames, P)
+        again_ev = lambda: restart(ev)      # noqa: E731
         for k in range(Wm):
-            ev.process_frame_device(*dp[k])
+            ev.process_frame_device(*dp[drive_frame(k, again_ev)])
         ev.sync(); ev.timings()                       # drop the warm-up samples
         for k in range(Wm, Wm + K):
-            ev.process_frame_device(*dp[k])
+            ev.process_frame_device(*dp[drive_frame(k, again_ev)])
         ev.sync()
         res["tim"] = ev.timings()
         assert ev.counts()["count"] == res["counts"]["count"], "instrumented pass diverged from the timed pass"
@@ -358,17 +410,25 @@ def leg_summary(res, K):
 
 
 def oracle_run(ol, cam, frames, Wm, Kc, cfg_kw, libpath=None, seed_model=None, seed_tick=None, per_frame=False):
-    """the CPU oracle over frames [0, Wm + Kc); returns (frames/s over the last Kc, final counts, per-frame counts)"""
+    """the CPU oracle over the stream's frames [0, Wm + Kc) (drives as in run_leg); returns (frames/s over the last Kc, final
+    counts, per-frame counts)"""
     o = ol.Oracle(ol.make_config(**cam, **cfg_kw), **({"libpath": libpath} if libpath else {}))
-    if seed_model is not None:
-        o.upload_model(seed_model); o.set_tick(seed_tick)
+
+    def prime():
+        if seed_model is not None:
+            o.upload_model(seed_model); o.set_tick(seed_tick)
+
+    def again():
+        o.reset()
+        prime()
+    prime()
     for k in range(Wm):
-        o.process_frame(*frames[k])
+        o.process_frame(*frames[drive_frame(k, again)])
     seq = []
     o.stage_seconds(reset=True)
     c0 = time.perf_counter()
     for k in range(Wm, Wm + Kc):
-        o.process_frame(*frames[k])
+        o.process_frame(*frames[drive_frame(k, again)])
         if per_frame:
             seq.append(o.counts())
     el = time.perf_counter() - c0
@@ -486,7 +546,7 @@ def bench_ranks(args, cam, rank, world, local_rank, K, Wm, workers, emit):
     gc.enable()
     elapsed = max_over_ranks(own)
     log = sm.read_frame_log(K)
-    fu = torch.tensor([float(log["fused_count"].sum()), float(log["unstable_count"].sum())], dtype=torch.float64, device=tdev)
+    fu =torch.tensor([float(log["fused_count"].sum()), float(log["unstable_count"].sum())], dtype=torch.float64, device=tdev)
     dist.all_reduce(fu, op=dist.ReduceOp.SUM)
     F_total, U_total = float(fu[0]), float(fu[1])
     own_t = torch.tensor([own], dtype=torch.float64, device=tdev)
@@ -596,7 +656,7 @@ def bench_single(args, cam, K, Wm, workers, emit):
     P = cam["width"] * cam["height"]
     t0 = time.time()
     n_steady = 0 if (hd or args.no_steady_leg) else args.steady_warmup + args.steady_steps
-    frames = make_frames(cam, max(Wm + K, n_steady), args.seed, args.noise_mm, workers)
+    frames = make_frames(cam, min(max(Wm + K, n_steady), DRIVE_FRAMES), args.seed, args.noise_mm, workers)
     t_gen = time.time() - t0
     from surfelmapping_amd import capi
     # this process creates several contexts one after the other; they never run at the same time: keep the default
@@ -606,7 +666,7 @@ def bench_single(args, cam, K, Wm, workers, emit):
                 compact_period=args.compact_period)
     seed_model = synth.seeded_model(args.seed_surfels, tick=300, seed=args.seed) if hd else None
     head = run_leg(capi, cam, frames, K, Wm, base, events=not args.no_events, seed_model=seed_model, seed_tick=300,
-                   mode="device_sync" if args.sync_every_frame else "device")
+                   mode="device_sync" if args.sync_every_frame else "device", dump=args.dump_outputs)
     log, counts, tim = head["log"], head["counts"], head["tim"]
     kern, roofline = None, None
     if tim is not None:
@@ -617,6 +677,7 @@ def bench_single(args, cam, K, Wm, workers, emit):
     elapsed = K / head["fps"]
 
     legs = {}
+    Kl = min(K, DRIVE_FRAMES)          # the fuse and reference-path legs time at most one drive
     if not hd and not args.no_steady_leg:
         # the fair steady-state figure: the driver's 20-frame window holds one compaction, 100 frames hold six
         r = run_leg(capi, cam, frames, args.steady_steps, args.steady_warmup, base, events=False)
@@ -624,12 +685,12 @@ def bench_single(args, cam, K, Wm, workers, emit):
                                   steps=args.steady_steps, warmup=args.steady_warmup)
     if not hd and not args.no_fuse_leg:
         # frames that actually fuse: 4 mm depth noise and fuse_thresh 0.05 (data.vert:177-208 carries the frame)
-        ff = make_frames(cam, Wm + K, args.seed, 4.0, workers)
-        r = run_leg(capi, cam, ff, K, Wm, dict(base, fuse_thresh=0.05), events=not args.no_events)
-        fl = dict(leg_summary(r, K), config="same KITTI trajectory and scene, depth noise 4 mm, fuse_thresh 0.05 (Config::surfelFuseDistanceThreshFactor)",
-                  fused_F_per_sec=float(r["log"]["fused_count"].sum()) / (r["ms"] * 1e-3 * K))
+        ff = make_frames(cam, min(Wm + Kl, DRIVE_FRAMES), args.seed, 4.0, workers)
+        r = run_leg(capi, cam, ff, Kl, Wm, dict(base, fuse_thresh=0.05), events=not args.no_events)
+        fl = dict(leg_summary(r, Kl), config="same KITTI trajectory and scene, depth noise 4 mm, fuse_thresh 0.05 (Config::surfelFuseDistanceThreshFactor)",
+                  fused_F_per_sec=float(r["log"]["fused_count"].sum()) / (r["ms"] * 1e-3 * Kl))
         if r["tim"] is not None:
-            fk, _, froof = kernel_table(r["log"], r["tim"], P, K, Wm, args.compact_period, "kitti_fuse")
+            fk, _, froof = kernel_table(r["log"], r["tim"], P, Kl, Wm, args.compact_period, "kitti_fuse")
             fl["kernels"] = fk
             fl["roofline"] = {k: froof[k] for k in ("kernel", "achieved", "frac", "ms_per_launch", "alg_bytes_per_launch")}
         legs["fuse_leg"] = fl
@@ -638,13 +699,13 @@ def bench_single(args, cam, K, Wm, workers, emit):
         # /root/reference/src/SurfelMapping.cpp:122-156): three host images uploaded, p0a..p0e, the caller waits for the frame
         pre = dict(base, preprocess=1)
         rp = {"config": "preprocess = 1 (p0a..p0e), KITTI 1242x375, the same stream"}
-        r = run_leg(capi, cam, frames, K, Wm, pre, events=False, mode="host_sync")
-        rp["host_buffers_sync"] = dict(leg_summary(r, K), what="sm_process_frame: 2.8 MB H2D + one host wait per frame (the reference's semantics)")
+        r = run_leg(capi, cam, frames, Kl, Wm, pre, events=False, mode="host_sync")
+        rp["host_buffers_sync"] = dict(leg_summary(r, Kl), what="sm_process_frame: 2.8 MB H2D + one host wait per frame (the reference's semantics)")
         if hasattr(capi.SurfelMap, "process_frame_async"):
-            r = run_leg(capi, cam, frames, K, Wm, pre, events=False, mode="host_async")
-            rp["host_buffers_async"] = dict(leg_summary(r, K), what="sm_process_frame_async: pinned staging, the H2D copy of frame f+1 overlaps frame f, no host wait")
-        r = run_leg(capi, cam, frames, K, Wm, pre, events=False, mode="device")
-        rp["device_resident_async"] = dict(leg_summary(r, K), what="sm_process_frame_device, frames staged in HBM, no host wait")
+            r = run_leg(capi, cam, frames, Kl, Wm, pre, events=False, mode="host_async")
+            rp["host_buffers_async"] = dict(leg_summary(r, Kl), what="sm_process_frame_async: pinned staging, the H2D copy of frame f+1 overlaps frame f, no host wait")
+        r = run_leg(capi, cam, frames, Kl, Wm, pre, events=False, mode="device")
+        rp["device_resident_async"] = dict(leg_summary(r, Kl), what="sm_process_frame_device, frames staged in HBM, no host wait")
         if "host_buffers_async" in rp:
             rp["host_over_device"] = rp["host_buffers_async"]["ms_per_step"] / rp["device_resident_async"]["ms_per_step"]
         legs["reference_path_leg"] = rp
@@ -690,6 +751,7 @@ def bench_single(args, cam, K, Wm, workers, emit):
                                + f"depth noise {args.noise_mm} mm, metricise+conflict+cull+splat+associate+fuse+append per frame"
                                + (" + depth pre-processing p0b..p0e" if args.preprocess else ""),
                    "frames": f"{Wm}..{Wm + K - 1}", "multi_gpu": "single stream",
+                   "drive": {"frames": DRIVE_FRAMES, "map_resets_in_timed_frames": (Wm + K - 1) // DRIVE_FRAMES - (Wm - 1) // DRIVE_FRAMES},
                    "host_sync": "per frame" if args.sync_every_frame else "none inside the timed region",
                    "compaction": (f"deferred: culled surfels keep their slots, every {ordinal(args.compact_period)} cull compacts "
                                   f"({int((log['n_static'] < log['n_slots']).sum()) if len(log) else 0} of {K} timed frames moved surfels)")
@@ -723,7 +785,7 @@ def hd_leg(args, capi, workers):
     P = cam["width"] * cam["height"]
     K, Wm = args.hd_steps, args.hd_warmup
     t0 = time.time()
-    frames = make_frames(cam, Wm + K, args.seed, args.noise_mm, workers)
+    frames = make_frames(cam, min(Wm + K, DRIVE_FRAMES), args.seed, args.noise_mm, workers)
     seed_model = synth.seeded_model(args.seed_surfels, tick=300, seed=args.seed)
     t_gen = time.time() - t0
     cfg = dict(preprocess=0, conflict_cap=0, max_sqrt_vertices=10000, compact_period=args.compact_period)
@@ -795,7 +857,17 @@ def main():
                     help="reference semantics: host waits for the counters after every frame")
     ap.add_argument("--launch-dry-run", action="store_true", help="start the ranks, rendezvous over gloo, print who is who; no GPU work")
     ap.add_argument("--launch-timeout", type=float, default=1500.0)
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beyond the headline: the instrumented pass (per-kernel table, roofline), the CPU "
+                         "baselines and the steady / fuse / reference-path / hd legs (the --no-* options still drop single ones)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the timed context's model and counters to DIR/*.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus > 1 or args.force_dist):
+        ap.error("--dump-outputs is for the one-rank line (--gpus 1)")
+    if not args.full:
+        args.no_fuse_leg = args.no_steady_leg = args.no_reference_path_leg = args.no_hd_leg = True
+        args.no_cpu_baseline = args.no_events = True
     if args.only_headline:
         args.no_fuse_leg = args.no_steady_leg = args.no_reference_path_leg = args.no_hd_leg = True
 

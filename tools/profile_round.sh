@@ -1,10 +1,11 @@
 #!/bin/bash
-# Profile one bench.py command with rocprofv3 (run on the MI355X box through gpurun): kernel trace + the three PMC passes,
-# each in its own run (profiles/README.md).  usage: tools/profile_round.sh <outdir under gpurun_out> <steps> <warmup> [extra bench args]
+# Profile one bench.py command with rocprofv3 (run on the MI355X box): kernel trace + the three PMC passes,
+# each in its own run (profiles/README.md).  usage: OUT_DIR=<folder> tools/profile_round.sh <outdir under $OUT_DIR> <steps> <warmup> [extra bench args]
 set -e
+: "${OUT_DIR:?set OUT_DIR to the folder the results go to}"
 export TMPDIR=/tmp
-out=gpurun_out/$1; steps=$2; warm=$3; shift 3
-args="--steps $steps --warmup $warm --workers 1 --no-cpu-baseline --only-headline $*"
+out=$OUT_DIR/$1; steps=$2; warm=$3; shift 3
+args="--steps $steps --warmup $warm --workers 1 --no-cpu-baseline --only-headline --full $*"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py $args > $out.bench_under_profiler.json 2> $out.trace.err
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/pmc_fetch -- python3 bench.py $args > /dev/null 2> $out.fetch.err
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/pmc_write -- python3 bench.py $args > /dev/null 2> $out.write.err

@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define SM_API_VERSION 4   /* bumped whenever a struct or an entry point changes (3, 4: round 3 -- asynchronous host path, rig step, sm_timings::k_scan_own, sm_host_alloc_frame; the staged shard entry points are gone) */
+#define SM_API_VERSION 4   /* bumped whenever a struct or an entry point changes (3, 4: round 3 -- asynchronous host path, rig step, sm_timings::k_scan_own, sm_host_alloc_frame; the staged shard entry points are gone).  Purely additive changes keep it: sm_model_view / sm_render_model* were added at 4, no existing struct or entry point changed. */
 
 /* error codes (reference: void returns + CheckGlDieOnError(); bool for map IO) */
 enum {
@@ -220,6 +220,29 @@ int sm_download_depth(sm_ctx *s, int which, float *dst);
  * pose `view16`; bgr_out h*w*3 u8 (B,G,R as FragColor = srgb.wzy), sem_out h*w u8 = class + 1, 0 = empty. */
 int sm_render_image(sm_ctx *s, const float *view16, int w, int h, float fx, float fy, float cx, float cy,
                     uint8_t *bgr_out, uint8_t *sem_out);
+
+/* The model view: GlobalModel::renderModel's uniforms (src/GlobalModel.cpp:683-758) plus a viewport. */
+typedef struct sm_model_view {
+    float mvp[16];        /* column-major, pangolin::OpenGlMatrix converted to float (the MVP uniform) */
+    float mv_inv[16];     /* column-major, mv.Inverse() as the reference uploads it (the MVINV uniform) */
+    float threshold;
+    int32_t color_type;   /* 0 shaded, 1 normals, 2 colours, 3 semantic: renderModel's drawNormals ? 1 : drawColors ? 2 : drawSemantic ? 3 : 0 */
+    int32_t draw_unstable, draw_points, draw_window, time, time_delta;
+    int32_t width, height;
+    uint8_t clear_rgba[4];
+} sm_model_view;
+
+/* GlobalModel::renderModel (src/GlobalModel.cpp:683-758) into an image instead of the bound framebuffer: surfels as
+ * oriented discs (draw_surface.vert / draw_surface_adaptive.geom / draw_surface.frag) or points (draw_feedback.vert/.frag),
+ * GL_LESS into a 24-bit depth buffer cleared to 1.0, ties to the lower id (DESIGN.md "Model view").
+ * rgba: w*h*4 host bytes (alpha 255 where a surfel is drawn, clear_rgba elsewhere), GL row order (row 0 = bottom, as
+ * glReadPixels); depth (w*h float window z, 1.0 = empty) and id (w*h int32, AoS row of sm_download_model_aos, -1 = empty) are
+ * optional (NULL).  Waits for the copies.  Changes neither the model nor the frame state; frames in flight are waited for.
+ * SM_E_ARG: NULL ctx / view / rgba, w or h <= 0, w*h > 2^28, color_type outside 0..3, or a call between sm_stage_conflict
+ * and sm_stage_cull.  SM_E_UNSUPPORTED in a sharded context (a rank holds only its own surfels). */
+int sm_render_model(sm_ctx *s, const sm_model_view *v, uint8_t *rgba, float *depth, int32_t *id);
+/* the same into device memory (4-byte aligned), enqueued on the context's stream; returns without waiting for the render */
+int sm_render_model_device(sm_ctx *s, const sm_model_view *v, uint8_t *d_rgba, float *d_depth, int32_t *d_id);
 
 /* ---- per-pass entry points (GlobalModel / IndexMap methods), synchronous ---- */
 /* Upload RGB / metric depth / semantic textures directly (bypasses p0). */

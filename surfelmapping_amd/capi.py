@@ -23,7 +23,8 @@ SYMBOLS = (
     "sm_process_frame", "sm_process_frame_device", "sm_process_frame_async",
     "sm_inputs_consumed", "sm_host_alloc", "sm_host_alloc_frame", "sm_host_free", "sm_debug_slow_frames", "sm_sync", "sm_clean_points", "sm_clean_points_ex", "sm_clean_points_cb", "sm_reset",
     "sm_get_counts", "sm_download_model_aos", "sm_upload_model_aos", "sm_save_map", "sm_load_map",
-    "sm_download_index_map", "sm_download_raw_cloud", "sm_download_depth", "sm_render_image", "sm_set_frame", "sm_set_tick",
+    "sm_download_index_map", "sm_download_raw_cloud", "sm_download_depth", "sm_render_image", "sm_render_model",
+    "sm_render_model_device", "sm_set_frame", "sm_set_tick",
     "sm_stage_conflict", "sm_stage_cull", "sm_stage_splat", "sm_stage_associate_fuse",
     "sm_stage_timings", "sm_read_frame_log", "sm_device_alloc", "sm_device_free", "sm_device_upload",
     "sm_export_model_device", "sm_append_model_aos_device", "sm_device_download",
@@ -80,6 +81,35 @@ FRAME_LOG_LEN = 1024
 FRAME_LOG_DTYPE = np.dtype([(n, np.uint32) for n in (
     "tick", "n_before", "n_after_cull", "n_kill", "conflict_count", "visible_count",
     "fused_count", "unstable_count", "n_static", "n_conf_skipped", "n_splat_skipped", "n_slots")])
+
+
+class SmModelView(C.Structure):
+    _fields_ = [
+        ("mvp", C.c_float * 16), ("mv_inv", C.c_float * 16), ("threshold", C.c_float), ("color_type", C.c_int32),
+        ("draw_unstable", C.c_int32), ("draw_points", C.c_int32), ("draw_window", C.c_int32), ("time", C.c_int32),
+        ("time_delta", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("clear_rgba", C.c_uint8 * 4),
+    ]
+
+
+def _mat16(m):
+    """float32[16] column-major; a 4x4 matrix (numpy row/col indexing) is converted"""
+    a = np.asarray(m, np.float32)
+    if a.shape == (4, 4):
+        a = a.T
+    a = np.ascontiguousarray(a.reshape(16))
+    return a
+
+
+def model_view(mvp, mv_inv, w, h, threshold=0.0, color_type=0, unstable=True, points=False, window=False, time=0,
+               time_delta=0, clear=(0, 0, 0, 0)) -> SmModelView:
+    v = SmModelView()
+    v.mvp[:] = [float(x) for x in _mat16(mvp)]
+    v.mv_inv[:] = [float(x) for x in _mat16(mv_inv)]
+    v.threshold = threshold
+    v.color_type, v.draw_unstable, v.draw_points, v.draw_window = int(color_type), int(bool(unstable)), int(bool(points)), int(bool(window))
+    v.time, v.time_delta, v.width, v.height = int(time), int(time_delta), int(w), int(h)
+    v.clear_rgba[:] = [int(c) for c in clear]
+    return v
 
 
 class SurfelMapError(RuntimeError):
@@ -190,6 +220,8 @@ def load():
     L.sm_download_raw_cloud.argtypes = [vp, vp, C.c_uint32, u32p]
     L.sm_download_depth.argtypes = [vp, C.c_int, vp]
     L.sm_render_image.argtypes = [vp, vp, C.c_int, C.c_int] + [C.c_float] * 4 + [vp, vp]
+    L.sm_render_model.argtypes = [vp, C.POINTER(SmModelView), vp, vp, vp]
+    L.sm_render_model_device.argtypes = [vp, C.POINTER(SmModelView), vp, vp, vp]
     L.sm_set_frame.argtypes = [vp, vp, vp, vp]
     L.sm_set_tick.argtypes = [vp, C.c_int32]
     L.sm_stage_conflict.argtypes = [vp, vp, C.c_float, C.c_float, C.c_float, C.c_int]
@@ -412,6 +444,37 @@ class SurfelMap:
         sem = np.zeros((h, w), np.uint8)
         self._chk(self._L.sm_render_image(self._h, _ptr(view), w, h, fx, fy, cx, cy, _ptr(bgr), _ptr(sem)), "sm_render_image")
         return bgr, sem
+
+    def render_model(self, mvp, mv_inv, w, h, threshold=0.0, color_type=0, unstable=True, points=False, window=False,
+                     time=0, time_delta=0, clear=(0, 0, 0, 0), depth=False, ids=False):
+        """The model view (GlobalModel::renderModel, sm_render_model): mvp / mv_inv column-major float32[16] (or 4x4).
+        Returns rgba uint8[h][w][4] in GL row order (row 0 = bottom) and, if asked, depth float32[h][w] (1.0 = empty) and
+        ids int32[h][w] (AoS row of download_model(), -1 = empty): rgba, or a tuple (rgba, depth?, ids?)."""
+        v = model_view(mvp, mv_inv, w, h, threshold, color_type, unstable, points, window, time, time_delta, clear)
+        rgba = np.zeros((h, w, 4), np.uint8)
+        d = np.zeros((h, w), np.float32) if depth else None
+        i = np.zeros((h, w), np.int32) if ids else None
+        self._chk(self._L.sm_render_model(self._h, C.byref(v), _ptr(rgba), _ptr(d), _ptr(i)), "sm_render_model")
+        if not depth and not ids:
+            return rgba
+        return (rgba,) + ((d,) if depth else ()) + ((i,) if ids else ())
+
+    def render_model_device(self, mvp, mv_inv, w, h, d_rgba, d_depth=0, d_id=0, threshold=0.0, color_type=0, unstable=True,
+                            points=False, window=False, time=0, time_delta=0, clear=(0, 0, 0, 0)):
+        """render_model into device memory (raw pointers, e.g. torch tensors' data_ptr(); 0 = not wanted), enqueued on the
+        context's stream without waiting (sm_render_model_device)"""
+        v = model_view(mvp, mv_inv, w, h, threshold, color_type, unstable, points, window, time, time_delta, clear)
+        self._chk(self._L.sm_render_model_device(self._h, C.byref(v), d_rgba or None, d_depth or None, d_id or None),
+                  "sm_render_model_device")
+
+    def render_model_stats(self):
+        """diagnostic of the last render_model* call (sm_debug_render_model_stats, not part of the C-ABI header): (surfels on the
+        overflow path, [splat, overflow, resolve] ms or None unless SM_RENDER_MODEL_TIMING=1 was set for that call)"""
+        f = self._L.sm_debug_render_model_stats
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
+        n, ms = C.c_uint32(), (C.c_float * 3)()
+        self._chk(f(self._h, C.byref(n), ms), "sm_debug_render_model_stats")
+        return int(n.value), (None if ms[0] < 0 else [float(x) for x in ms])
 
     # -- per-pass entry points
     def set_frame(self, rgb=None, depth_metric=None, sem=None):

@@ -2,6 +2,7 @@
 // keep the reference's names and call order (src/SurfelMapping.cpp:178-239); passes that the
 // HIP core fuses into a neighbour are no-ops here (noted per method).
 #pragma once
+#include <cmath>
 #include <cstdio>
 #include <string>
 #include <utility>
@@ -127,6 +128,36 @@ public:
     }
     size_t lastDrawnCount() const { return drawn_.size() / 3; }
 
+    // renderModel's arguments plus a viewport: the model view rendered by the HIP core (sm_render_model) into a host image --
+    // the five colour modes, the confidence gate, the unstable switch, discs or points, as the reference's shaders draw them.
+    // `clear` is the glClearColor of the view.  The image is RGBA8, w*h*4 bytes, GL row order (row 0 = bottom).
+    bool renderModelImage(pangolin::OpenGlMatrix mvp, pangolin::OpenGlMatrix mv, float threshold, bool drawUnstable, bool drawNormals,
+                          bool drawColors, bool drawPoints, bool drawWindow, bool drawSemantic, int time, int timeDelta, int w, int h,
+                          const float clear[4])
+    {
+        sm_model_view v{};
+        double inv[16];
+        invert4d(mv.m, inv);                                             // mv.Inverse() in double, as pangolin computes it
+        for (int i = 0; i < 16; ++i) { v.mvp[i] = (float)mvp.m[i]; v.mv_inv[i] = (float)inv[i]; }
+        v.threshold = threshold;
+        v.color_type = drawNormals ? 1 : drawColors ? 2 : drawSemantic ? 3 : 0;    // src/GlobalModel.cpp:702
+        v.draw_unstable = drawUnstable; v.draw_points = drawPoints; v.draw_window = drawWindow;
+        v.time = time; v.time_delta = timeDelta;
+        v.width = w; v.height = h;
+        for (int c = 0; c < 4; ++c) {
+            const float x = clear ? clear[c] : 0.0f;
+            v.clear_rgba[c] = (uint8_t)std::floor((x < 0.0f ? 0.0f : x > 1.0f ? 1.0f : x) * 255.0f + 0.5f);
+        }
+        modelImage_.resize((size_t)(w > 0 ? w : 0) * (size_t)(h > 0 ? h : 0) * 4);
+        (void)sm_sync(ctx_);                                             // (SM_FACADE_ASYNC: frames may still be in flight)
+        if (sm_render_model(ctx_, &v, modelImage_.data(), nullptr, nullptr) != SM_OK) {
+            std::printf("renderModelImage: %s\n", sm_last_error());
+            return false;
+        }
+        return true;
+    }
+    const std::vector<unsigned char> &modelImageRGBA() const { return modelImage_; }
+
     // The model-aligned mirror textures (src/GlobalModel.cpp:639-681) do not exist in the compute core.  GUI::drawCapacity
     // (build_map.cpp:204) shows the fill level of the TEXTURE_DIMENSION^2 normal/radius mirror: the handle is filled lazily --
     // size TEXTURE_DIMENSION x TEXTURE_DIMENSION, and (without GL) the host copy of the plane for whoever wants to look.
@@ -136,6 +167,29 @@ public:
     const std::vector<float> &mirrorHost(int which) const { return mirror_[which]; }      // 0 VC, 1 CT, 2 NR: count x 4 floats
 
 private:
+    // general 4x4 inverse by cofactors (column-major, double)
+    static void invert4d(const double *m, double *o)
+    {
+        double c[16];
+        c[0] = m[5] * m[10] * m[15] - m[5] * m[11] * m[14] - m[9] * m[6] * m[15] + m[9] * m[7] * m[14] + m[13] * m[6] * m[11] - m[13] * m[7] * m[10];
+        c[4] = -m[4] * m[10] * m[15] + m[4] * m[11] * m[14] + m[8] * m[6] * m[15] - m[8] * m[7] * m[14] - m[12] * m[6] * m[11] + m[12] * m[7] * m[10];
+        c[8] = m[4] * m[9] * m[15] - m[4] * m[11] * m[13] - m[8] * m[5] * m[15] + m[8] * m[7] * m[13] + m[12] * m[5] * m[11] - m[12] * m[7] * m[9];
+        c[12] = -m[4] * m[9] * m[14] + m[4] * m[10] * m[13] + m[8] * m[5] * m[14] - m[8] * m[6] * m[13] - m[12] * m[5] * m[10] + m[12] * m[6] * m[9];
+        c[1] = -m[1] * m[10] * m[15] + m[1] * m[11] * m[14] + m[9] * m[2] * m[15] - m[9] * m[3] * m[14] - m[13] * m[2] * m[11] + m[13] * m[3] * m[10];
+        c[5] = m[0] * m[10] * m[15] - m[0] * m[11] * m[14] - m[8] * m[2] * m[15] + m[8] * m[3] * m[14] + m[12] * m[2] * m[11] - m[12] * m[3] * m[10];
+        c[9] = -m[0] * m[9] * m[15] + m[0] * m[11] * m[13] + m[8] * m[1] * m[15] - m[8] * m[3] * m[13] - m[12] * m[1] * m[11] + m[12] * m[3] * m[9];
+        c[13] = m[0] * m[9] * m[14] - m[0] * m[10] * m[13] - m[8] * m[1] * m[14] + m[8] * m[2] * m[13] + m[12] * m[1] * m[10] - m[12] * m[2] * m[9];
+        c[2] = m[1] * m[6] * m[15] - m[1] * m[7] * m[14] - m[5] * m[2] * m[15] + m[5] * m[3] * m[14] + m[13] * m[2] * m[7] - m[13] * m[3] * m[6];
+        c[6] = -m[0] * m[6] * m[15] + m[0] * m[7] * m[14] + m[4] * m[2] * m[15] - m[4] * m[3] * m[14] - m[12] * m[2] * m[7] + m[12] * m[3] * m[6];
+        c[10] = m[0] * m[5] * m[15] - m[0] * m[7] * m[13] - m[4] * m[1] * m[15] + m[4] * m[3] * m[13] + m[12] * m[1] * m[7] - m[12] * m[3] * m[5];
+        c[14] = -m[0] * m[5] * m[14] + m[0] * m[6] * m[13] + m[4] * m[1] * m[14] - m[4] * m[2] * m[13] - m[12] * m[1] * m[6] + m[12] * m[2] * m[5];
+        c[3] = -m[1] * m[6] * m[11] + m[1] * m[7] * m[10] + m[5] * m[2] * m[11] - m[5] * m[3] * m[10] - m[9] * m[2] * m[7] + m[9] * m[3] * m[6];
+        c[7] = m[0] * m[6] * m[11] - m[0] * m[7] * m[10] - m[4] * m[2] * m[11] + m[4] * m[3] * m[10] + m[8] * m[2] * m[7] - m[8] * m[3] * m[6];
+        c[11] = -m[0] * m[5] * m[11] + m[0] * m[7] * m[9] + m[4] * m[1] * m[11] - m[4] * m[3] * m[9] - m[8] * m[1] * m[7] + m[8] * m[3] * m[5];
+        c[15] = m[0] * m[5] * m[10] - m[0] * m[6] * m[9] - m[4] * m[1] * m[10] + m[4] * m[2] * m[9] + m[8] * m[1] * m[6] - m[8] * m[2] * m[5];
+        const double det = m[0] * c[0] + m[1] * c[4] + m[2] * c[8] + m[3] * c[12];
+        for (int i = 0; i < 16; ++i) o[i] = c[i] / det;
+    }
     void refreshHostModel() { hostModel_ = downloadModel(); }
     pangolin::GlTexture *fillMirror(GPUTexture &t, int off)
     {
@@ -163,5 +217,5 @@ private:
     GPUTexture mapVC_, mapCT_, mapNR_, imageTex_, semTex_;
     int iw_ = 0, ih_ = 0;
     float ifx_ = 0, ify_ = 0, icx_ = 0, icy_ = 0;
-    std::vector<unsigned char> imageBgr_, imageSem_;
+    std::vector<unsigned char> imageBgr_, imageSem_, modelImage_;
 };

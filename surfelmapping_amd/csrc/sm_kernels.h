@@ -17,5 +17,6 @@ namespace sm {
 #include "sm_k_assoc.h"
 #include "sm_k_shard.h"
 #include "sm_k_aux.h"
+#include "sm_k_view.h"
 
 }  // namespace sm

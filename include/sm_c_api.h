@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define SM_API_VERSION 4   /* bumped whenever a struct or an entry point changes (3, 4: round 3 -- asynchronous host path, rig step, sm_timings::k_scan_own, sm_host_alloc_frame; the staged shard entry points are gone).  Purely additive changes keep it: sm_model_view / sm_render_model* were added at 4, no existing struct or entry point changed. */
+#define SM_API_VERSION 4   /* bumped whenever a struct or an entry point changes (3, 4: round 3 -- asynchronous host path, rig step, sm_timings::k_scan_own, sm_host_alloc_frame; the staged shard entry points are gone).  Purely additive changes keep it: sm_model_view / sm_render_model* and sm_track_* were added at 4, no existing struct or entry point changed. */
 
 /* error codes (reference: void returns + CheckGlDieOnError(); bool for map IO) */
 enum {
@@ -243,6 +243,62 @@ typedef struct sm_model_view {
 int sm_render_model(sm_ctx *s, const sm_model_view *v, uint8_t *rgba, float *depth, int32_t *id);
 /* the same into device memory (4-byte aligned), enqueued on the context's stream; returns without waiting for the render */
 int sm_render_model_device(sm_ctx *s, const sm_model_view *v, uint8_t *d_rgba, float *d_depth, int32_t *d_id);
+
+/* ---- camera tracking (DESIGN.md "4d. Tracking") ----
+ * The reference documents processFrame's gtPose as optional ("if provided, we don't attempt to perform tracking",
+ * src/SurfelMapping.h:31-34) but has no tracker.  This one is projective frame-to-model point-to-plane ICP against the map:
+ *  - Poses are camera->world, column-major float[16], as everywhere in this header.
+ *  - Prediction: ONE per tracked frame, at T_prev = the pose of the last processed frame, of the model as it stands after that
+ *    frame.  Pixel (u, v) holds the nearest live surfel (alive under the deferred compaction; nothing is compacted) whose centre
+ *    has camera z in (near_clip, far_clip) and projects to u = floor(fx*x/z + cx + 0.5), v likewise (ties: lower slot).
+ *  - Current frame: metric depth by the metricise rule of the fused frame (mm -> m inside the clip range, 0 left of
+ *    stereo_border; no moving-object filter), vertex and normal of every pixel of the pixel_stride grid by the frame's own rule;
+ *    a pixel counts if its depth and its four neighbours' are non-zero.
+ *  - Association: T*v projected into the prediction camera; a pair is kept iff a surfel is at that pixel, |T*v - p_m| <= dist_thresh
+ *    and dot(R*n, n_m) >= cos(angle_thresh).  Residual r = n_m . (T*v - p_m); left-multiplied world twist xi = (rho, phi),
+ *    T <- exp(xi) T, Jacobian row [n_m, (T*v) x n_m].  Per-pixel terms fp32, sums fp64 in a fixed order: bit-reproducible.
+ *  - Solve: LDLT in double on the device; stop when |phi| < 1e-6 rad and |rho| < 1e-6 m, else after max_iters.  One host
+ *    synchronisation per tracked frame.
+ *  - Failure returns the guess with a status: SM_TRACK_LOST (fewer than min_inliers inliers in any iteration),
+ *    SM_TRACK_DEGENERATE (in the system of the converged or the last iteration, the smallest / largest LDLT pivot is below
+ *    SM_TRACK_DEGENERATE_BOUND, the system taken with the rotation about the prediction camera's centre and the rotation columns
+ *    scaled so that both 3x3 diagonal blocks have the same trace), SM_TRACK_NO_MODEL (no processed frame, an empty model, or no
+ *    surfel in view).
+ *  - Guess when none is given: constant velocity T_prev * (T_prev2^-1 * T_prev) from the last two processed poses (in double,
+ *    their rotations orthonormalised first, rounded to float); with one processed pose that pose; with none the identity.  The
+ *    iterations start from the guess with its rotation orthonormalised (in double). */
+enum { SM_TRACK_OK = 0, SM_TRACK_LOST = 1, SM_TRACK_DEGENERATE = 2, SM_TRACK_NO_MODEL = 3 };
+#define SM_TRACK_DEGENERATE_BOUND 1e-4
+#define SM_TRACK_MAX_ITERS 100        /* max_iters above this is SM_E_ARG */
+
+typedef struct sm_track_params {
+    int32_t max_iters;        /* 15 */
+    float dist_thresh;        /* 0.3 m */
+    float angle_thresh;       /* 30 degrees */
+    int32_t min_inliers;      /* 1000 */
+    int32_t pixel_stride;     /* 1: every pixel; s: every s-th column of every s-th row */
+} sm_track_params;
+
+typedef struct sm_track_info {
+    int32_t status;           /* SM_TRACK_* */
+    int32_t iterations;       /* Gauss-Newton systems solved (0: none was built) */
+    uint32_t inliers;         /* of the last system */
+    float rmse;               /* sqrt(sum r^2 / inliers) of the last system, metres */
+    float guess[16];          /* the guess the tracker started from */
+} sm_track_info;
+
+int sm_default_track_params(sm_track_params *p);
+/* Track one depth image (H*W u16 millimetres, host memory) against the model: pose16_out receives the pose (the guess on failure),
+ * info (may be NULL) the statistics.  guess16 NULL = constant velocity; params NULL = defaults.  Waits for frames in flight; changes
+ * nothing in the model, its counters, the frame log or the compaction schedule.  The tracked frame is NOT fused: pass the pose to
+ * sm_process_frame* (which still requires one).  SM_E_ARG: a NULL ctx / depth / output, a parameter out of range, or a call
+ * between sm_stage_conflict and sm_stage_cull.  SM_E_UNSUPPORTED in a sharded context (a rank holds only its own surfels). */
+int sm_track_frame(sm_ctx *s, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params, float *pose16_out,
+                   sm_track_info *info);
+/* For tests: the prediction the next sm_track_frame would draw (pred_slot, W*H int32 row-major, model slot or -1; slots equal the
+ * rows of sm_download_model_aos once the model is compacted) and the 29-value system of ONE iteration at pose16_eval with the default
+ * parameters (sys29: J^T J upper triangle row-major (21), J^T r (6), sum r^2, inliers; double).  Either output may be NULL. */
+int sm_track_debug(sm_ctx *s, const uint16_t *depth_mm, const float *pose16_eval, int32_t *pred_slot, double *sys29);
 
 /* ---- per-pass entry points (GlobalModel / IndexMap methods), synchronous ---- */
 /* Upload RGB / metric depth / semantic textures directly (bypasses p0). */

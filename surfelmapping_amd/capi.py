@@ -31,6 +31,7 @@ SYMBOLS = (
     "sm_shard_stream_configure", "sm_shard_set_collective", "sm_shard_rccl_unique_id", "sm_shard_rccl_init",
     "sm_shard_rccl_finalize", "sm_shard_rccl_nranks", "sm_shard_frame_device", "sm_shard_frame", "sm_shard_compact", "sm_shard_export_dense_device",
     "sm_gpu_process_count", "sm_rig_configure", "sm_rig_consolidate", "sm_rig_consolidate_step",
+    "sm_default_track_params", "sm_track_frame", "sm_track_debug",
 )
 
 SM_COLL_SUM, SM_COLL_MIN, SM_COLL_GATHER = 0, 1, 2
@@ -89,6 +90,31 @@ class SmModelView(C.Structure):
         ("draw_unstable", C.c_int32), ("draw_points", C.c_int32), ("draw_window", C.c_int32), ("time", C.c_int32),
         ("time_delta", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("clear_rgba", C.c_uint8 * 4),
     ]
+
+
+SM_TRACK_OK, SM_TRACK_LOST, SM_TRACK_DEGENERATE, SM_TRACK_NO_MODEL = 0, 1, 2, 3
+TRACK_STATUS = {SM_TRACK_OK: "OK", SM_TRACK_LOST: "LOST", SM_TRACK_DEGENERATE: "DEGENERATE", SM_TRACK_NO_MODEL: "NO_MODEL"}
+
+
+class SmTrackParams(C.Structure):
+    _fields_ = [("max_iters", C.c_int32), ("dist_thresh", C.c_float), ("angle_thresh", C.c_float), ("min_inliers", C.c_int32),
+                ("pixel_stride", C.c_int32)]
+
+
+class SmTrackInfo(C.Structure):
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("inliers", C.c_uint32), ("rmse", C.c_float),
+                ("guess", C.c_float * 16)]
+
+
+def track_params(**over) -> SmTrackParams:
+    """sm_default_track_params with fields overridden (max_iters, dist_thresh, angle_thresh, min_inliers, pixel_stride)"""
+    p = SmTrackParams()
+    load().sm_default_track_params(C.byref(p))
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
 
 
 def _mat16(m):
@@ -251,6 +277,9 @@ def load():
     L.sm_rig_configure.argtypes = [vp, C.c_int, C.c_int]
     L.sm_rig_consolidate.argtypes = [vp, vp, vp, vp, vp, u32p, u32p]
     L.sm_rig_consolidate_step.argtypes = [vp, vp, vp, vp, vp, u32p, u32p]
+    L.sm_default_track_params.argtypes = [C.POINTER(SmTrackParams)]
+    L.sm_track_frame.argtypes = [vp, vp, vp, C.POINTER(SmTrackParams), vp, C.POINTER(SmTrackInfo)]
+    L.sm_track_debug.argtypes = [vp, vp, vp, vp, vp]
     for name in SYMBOLS:
         getattr(L, name)          # AttributeError here = the library does not match the header
     _lib = L
@@ -386,6 +415,52 @@ class SurfelMap:
 
     def reset(self):
         self._chk(self._L.sm_reset(self._h), "sm_reset")
+
+    # -- tracking (sm_track_frame)
+    def track(self, depth, guess=None, **params):
+        """Track one depth image (uint16[H][W] mm) against the model (sm_track_frame); the model is not changed.  guess: a 4x4
+        camera->world matrix (numpy row/col indexing) or float32[16] column-major; None = constant velocity.  params override
+        sm_default_track_params.  Returns (pose 4x4 float32, numpy row/col indexing; the guess unless status is "OK",
+        info dict: status (name), status_code, iterations, inliers, rmse, guess 4x4)."""
+        depth = np.ascontiguousarray(depth, np.uint16)
+        assert depth.size == self.P, depth.shape
+        g = None if guess is None else _mat16(guess)
+        p = track_params(**params) if params else None
+        out = np.zeros(16, np.float32)
+        info = SmTrackInfo()
+        self._chk(self._L.sm_track_frame(self._h, _ptr(depth), _ptr(g), C.byref(p) if p is not None else None, _ptr(out),
+                                         C.byref(info)), "sm_track_frame")
+        d = dict(status=TRACK_STATUS.get(info.status, str(info.status)), status_code=int(info.status),
+                 iterations=int(info.iterations), inliers=int(info.inliers), rmse=float(info.rmse),
+                 guess=np.array(info.guess[:], np.float32).reshape(4, 4).T.copy())
+        return out.reshape(4, 4).T.copy(), d
+
+    def track_debug(self, depth, pose_eval):
+        """sm_track_debug: (pred_slot int32[H][W], model slot or -1, sys float64[29]) -- the prediction of the next track() and one
+        iteration's system at pose_eval (4x4 or float32[16] column-major) with the default parameters"""
+        depth = np.ascontiguousarray(depth, np.uint16)
+        assert depth.size == self.P, depth.shape
+        pe = _mat16(pose_eval)
+        pred = np.zeros((self.H, self.W), np.int32)
+        sys29 = np.zeros(29, np.float64)
+        self._chk(self._L.sm_track_debug(self._h, _ptr(depth), _ptr(pe), _ptr(pred), _ptr(sys29)), "sm_track_debug")
+        return pred, sys29
+
+    def track_stats(self):
+        """device times in ms of the last track()/track_debug() call made with SM_TRACK_TIMING=1 (sm_debug_track_stats, not part
+        of the C-ABI header): [prediction, vertex stage, reduce_0, solve_0, reduce_1, solve_1, ...], or [] if it was not timed"""
+        f = self._L.sm_debug_track_stats
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int)]
+        ms, n = (C.c_float * 256)(), C.c_int()
+        self._chk(f(self._h, ms, 256, C.byref(n)), "sm_debug_track_stats")
+        return [float(x) for x in ms[:n.value]]
+
+    def process_frame_tracked(self, rgb, depth, sem, guess=None, **params):
+        """track() the frame, then process_frame() it with the tracked pose (the guess when tracking failed).
+        Returns (pose 4x4 float32, info dict) as track()."""
+        pose, info = self.track(depth, guess, **params)
+        self.process_frame(rgb, depth, sem, _mat16(pose))
+        return pose, info
 
     # -- GlobalModel
     def counts(self) -> dict:

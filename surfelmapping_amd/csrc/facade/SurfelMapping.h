@@ -60,12 +60,30 @@ public:
     SurfelMapping(const SurfelMapping &) = delete;
     SurfelMapping &operator=(const SurfelMapping &) = delete;
 
-    // src/SurfelMapping.h:31-34.  A null gtPose is an error here (the reference dereferences it:
-    // src/SurfelMapping.cpp:130).
+    // src/SurfelMapping.h:31-34.  A null gtPose means "track" as the reference's header documents (the reference itself
+    // dereferences it: src/SurfelMapping.cpp:130): the depth image is tracked against the model (sm_track_frame, constant-velocity
+    // guess, default parameters) and the frame is then fused with the tracked pose.  A failed track (LOST, DEGENERATE,
+    // NO_MODEL) prints one line and fuses with the guess.  With SM_FACADE_ASYNC=1 the track waits for the frames in flight; the
+    // frame itself is enqueued as usual.
     void processFrame(const unsigned char *rgb, const unsigned short *depth = nullptr, const unsigned char *semantic = nullptr,
                       const Eigen::Matrix4f *gtPose = 0)
     {
-        if (!gtPose) { std::printf("processFrame: gtPose is required\n"); return; }
+        Eigen::Matrix4f tracked;
+        if (!gtPose) {
+            const unsigned short *d = depth ? depth : (textures[GPUTexture::DEPTH_RAW]->host_u16.empty()
+                                                           ? nullptr : textures[GPUTexture::DEPTH_RAW]->host_u16.data());
+            if (!d) { std::printf("processFrame: no gtPose and no depth image to track\n"); return; }
+            if (sm_track_frame(ctx_, d, nullptr, nullptr, tracked.data(), &lastTrackInfo) != SM_OK) {
+                std::printf("processFrame: %s\n", sm_last_error());
+                return;
+            }
+            static const char *const names[] = {"OK", "LOST", "DEGENERATE", "NO_MODEL"};
+            if (lastTrackInfo.status != SM_TRACK_OK)
+                std::printf("processFrame: tracking %s (%u inliers); using the guess\n",
+                            lastTrackInfo.status >= 0 && lastTrackInfo.status <= 3 ? names[lastTrackInfo.status] : "failed",
+                            lastTrackInfo.inliers);
+            gtPose = &tracked;
+        }
         currPose = *gtPose;
         // the reference uploads the three images into its RGB / DEPTH / SEMANTIC textures (src/SurfelMapping.cpp:122-128; a null
         // depth / semantic keeps the old one): kept here as host copies for getTexture()
@@ -90,6 +108,8 @@ public:
     bool getBeginCleanPoints() { return beginCleanPoints; }
     const Eigen::Matrix4f &getCurrPose() { return currPose; }
     const std::vector<Eigen::Matrix4f> &getHistoryPoses() { return historyPoses; }
+    // statistics of the last processFrame that tracked (gtPose null); zero before the first
+    const sm_track_info &getLastTrackInfo() { return lastTrackInfo; }
     IndexMap &getIndexMap() { return indexMap; }
     GlobalModel &getGlobalModel() { return globalModel; }
 
@@ -179,6 +199,7 @@ private:
     FeedbackBuffer rawFeedback;
     std::map<std::string, GPUTexture *> textures;
     std::vector<Eigen::Matrix4f> historyPoses;
+    sm_track_info lastTrackInfo{};
     bool beginCleanPoints = false;
     bool async_ = false;
 };

@@ -1,0 +1,366 @@
+// sm_k_track.h -- camera tracking: projective frame-to-model point-to-plane ICP (DESIGN.md "4d. Tracking").
+// Part of sm_kernels.h (included there, in order, inside namespace sm).  The reference has no tracker (its header promises one:
+// src/SurfelMapping.h:31-34); the vertex / normal rule is the frame's own (geometry.glsl:5-24 as local_surfel restates it).
+//
+// One tracked frame:
+//   k_track_splat    one pass over the occupied slots: every live surfel (alive bit set) whose centre lies in front of the
+//                    prediction camera T_prev with near < z < far lands on pixel (floor(fx*x/z + cx + 0.5), floor(fy*y/z + cy + 0.5))
+//                    by a 64-bit atomicMin of (float bits of z) << 32 | slot: the nearest surfel, ties to the lower slot.
+//   k_track_resolve  key -> slot (-1 = empty), row-major W*H int32.
+//   k_track_vertex   the current frame's metric depth (p0a's rule), vertex and normal of every pixel of the strided grid.
+//   then max_iters times:
+//   k_track_reduce   associate + residual + the 29 values of the normal equations per inlier, fp32 terms accumulated in fp64,
+//                    wave shuffle + LDS reduction to one fp64 partial per workgroup (fixed order: bit-reproducible).
+//   k_track_solve    one workgroup: fixed-order sum of the partials, LDLT in double, T <- exp(xi) T, convergence / failure
+//                    (LOST at any iteration; DEGENERATE when the system of the converged or last iteration is).
+// A device-side `done` word makes every launch after convergence or failure a no-op, so the host waits once per frame.
+
+constexpr int TRACK_BLOCK = 256;
+constexpr int TRACK_MAX_PARTS = 1024;    // workgroups of k_track_reduce at most (each leaves 29 partial sums)
+constexpr int TRACK_NSYS = 29;           // JtJ upper triangle (21, row-major), Jtr (6), r^2, inliers
+
+enum { TRACK_OK = 0, TRACK_LOST = 1, TRACK_DEGENERATE = 2, TRACK_NO_MODEL = 3 };
+
+struct TrackParams {
+    float tinv_prev[16];      // world -> prediction camera, column-major: [R^T | -R^T t] of T_prev in double, rounded to float
+    float fx, fy, cx, cy, inv_fx, inv_fy;
+    float near_clip, far_clip, stereo_border;
+    int W, H;
+    int stride, ni, nj, n;    // the strided pixel grid: columns 0, s, 2s, ... (ni of them) x rows 0, s, ... (nj); n = ni * nj
+    float dist, cos_angle;    // association gates
+    uint32_t min_inliers;
+    double degenerate_bound;  // smallest / largest LDLT pivot of the scaled, camera-centred system
+    double c[3];              // prediction camera centre (the translation of T_prev)
+    int nb;                   // workgroups of k_track_reduce
+    int max_iters;
+};
+
+struct TrackState {
+    double T[16];             // the estimate, camera -> world, column-major
+    double guess[16];
+    double sys[32];           // the last system summed by k_track_solve (TRACK_NSYS used)
+    double rmse, pivot_ratio, step_rot, step_trans;
+    int32_t status, iterations, done, pad;
+    uint32_t in_view, inliers;
+};
+
+// ---- the prediction ----
+
+__global__ __launch_bounds__(256) void k_track_splat(Model M, const DevState *__restrict__ st, const uint64_t *__restrict__ alive,
+                                                     TrackParams tp, uint64_t *__restrict__ key, TrackState *__restrict__ ts)
+{
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    bool in_view = false;
+    if (k < st->count && ((alive[k >> 6] >> (k & 63u)) & 1ull)) {
+        const float4 pc = M.s[st->cur].pos_conf[k];
+        const float3 c = xform3(tp.tinv_prev, pc.x, pc.y, pc.z);
+        if (c.z > tp.near_clip && c.z < tp.far_clip) {
+            const float fu = floorf(((tp.fx * c.x) / c.z + tp.cx) + 0.5f);
+            const float fv = floorf(((tp.fy * c.y) / c.z + tp.cy) + 0.5f);
+            if (fu >= 0.0f && fu < (float)tp.W && fv >= 0.0f && fv < (float)tp.H) {
+                in_view = true;
+                const size_t p = (size_t)(int)fv * tp.W + (int)fu;
+                atomicMin((unsigned long long *)&key[p], (unsigned long long)(((uint64_t)__float_as_uint(c.z) << 32) | k));
+            }
+        }
+    }
+    const uint64_t m = __ballot(in_view);                     // one atomic per wave
+    if (m && (threadIdx.x & 63u) == (uint32_t)(__ffsll((unsigned long long)m) - 1))
+        atomicAdd(&ts->in_view, (uint32_t)__popcll(m));
+}
+
+__global__ void k_track_resolve(const uint64_t *__restrict__ key, int npix, int32_t *__restrict__ slot)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npix) return;
+    const uint64_t kk = key[p];
+    slot[p] = kk == KEY_EMPTY ? -1 : (int32_t)(uint32_t)(kk & 0xFFFFFFFFull);
+}
+
+// ---- the current frame: vertex (xyz, 1 = valid) and normal per grid point ----
+
+// metriciseDepth (p0a: sm_k_prep.h, prep_image_block) of pixel (i, j) of the row-major millimetre image
+__device__ __forceinline__ float track_depth(const uint16_t *__restrict__ mm, int i, int j, const TrackParams &tp)
+{
+    const uint32_t lo = (uint32_t)(tp.near_clip * 1000.0f);
+    const uint32_t hi = (uint32_t)((tp.far_clip - 0.001f) * 1000.0f);
+    const uint32_t v = mm[(size_t)j * tp.W + i];
+    if ((float)i + 0.5f < tp.stereo_border) return 0.0f;
+    return (v > lo && v < hi) ? (float)v / 1000.0f : 0.0f;
+}
+
+__global__ __launch_bounds__(256) void k_track_vertex(const uint16_t *__restrict__ mm, const float *__restrict__ xs,
+                                                      const float *__restrict__ ys, TrackParams tp, float4 *__restrict__ vmap,
+                                                      float4 *__restrict__ nmap)
+{
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= tp.n) return;
+    const int gj = idx / tp.ni;
+    const int i = (idx - gj * tp.ni) * tp.stride, j = gj * tp.stride;
+    const int W = tp.W, H = tp.H;
+    // clamp-to-edge neighbours, as the frame's surfels (local_surfel)
+    const float z = track_depth(mm, i, j, tp);
+    const float zl = track_depth(mm, i > 0 ? i - 1 : i, j, tp), zr = track_depth(mm, i < W - 1 ? i + 1 : i, j, tp);
+    const float zu = track_depth(mm, i, j > 0 ? j - 1 : j, tp), zd = track_depth(mm, i, j < H - 1 ? j + 1 : j, tp);
+    float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f), nn = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    // checkNeighbours + range (data.vert:33-52,87); no checkerboard: every grid pixel is a measurement
+    if (z > 0.0f && zl != 0.0f && zu != 0.0f && zr != 0.0f && zd != 0.0f) {
+        FrameParams fp;                                       // (get_vertex reads cx, cy only)
+        fp.cx = tp.cx; fp.cy = tp.cy;
+        const float x = xs[i], y = ys[j];
+        const float3 p = get_vertex(z, x, y, fp, tp.inv_fx, tp.inv_fy);
+        const float3 xf = get_vertex(zr, x + 1.0f, y, fp, tp.inv_fx, tp.inv_fy);
+        const float3 xb = get_vertex(zl, x - 1.0f, y, fp, tp.inv_fx, tp.inv_fy);
+        const float3 yf = get_vertex(zd, x, y + 1.0f, fp, tp.inv_fx, tp.inv_fy);
+        const float3 yb = get_vertex(zu, x, y - 1.0f, fp, tp.inv_fx, tp.inv_fy);
+        const float3 del_x = make_float3(xb.x - xf.x, xb.y - xf.y, xb.z - xf.z);
+        const float3 del_y = make_float3(yb.x - yf.x, yb.y - yf.y, yb.z - yf.z);
+        const float3 n = normalize3(cross3(del_x, del_y));
+        if (isfinite(n.x) && isfinite(n.y) && isfinite(n.z)) {
+            v = make_float4(p.x, p.y, p.z, 1.0f);
+            nn = make_float4(n.x, n.y, n.z, 0.0f);
+        }
+    }
+    vmap[idx] = v;
+    nmap[idx] = nn;
+}
+
+// ---- one Gauss-Newton iteration ----
+
+// the estimate in float, column-major (rounded from the double state)
+__device__ __forceinline__ void track_pose_f(const TrackState *__restrict__ ts, float *m)
+{
+#pragma unroll
+    for (int e = 0; e < 16; ++e) m[e] = (float)ts->T[e];
+}
+
+// association and residual of grid point idx under the pose `m`: false if not an inlier
+__device__ __forceinline__ bool track_pair(int idx, const float *m, const TrackParams &tp, const float4 *__restrict__ vmap,
+                                           const float4 *__restrict__ nmap, const int32_t *__restrict__ pred, const SurfelSet &cur,
+                                           float *J, float &r)
+{
+    const float4 v = vmap[idx];
+    if (v.w == 0.0f) return false;
+    const float4 n = nmap[idx];
+    const float3 w = xform3(m, v.x, v.y, v.z);                // T v
+    const float3 nw = rot3(m, n.x, n.y, n.z);                 // R n
+    const float3 c = xform3(tp.tinv_prev, w.x, w.y, w.z);     // into the prediction camera
+    if (!(c.z > 0.0f)) return false;
+    const float fu = floorf(((tp.fx * c.x) / c.z + tp.cx) + 0.5f);
+    const float fv = floorf(((tp.fy * c.y) / c.z + tp.cy) + 0.5f);
+    if (!(fu >= 0.0f && fu < (float)tp.W && fv >= 0.0f && fv < (float)tp.H)) return false;
+    const int32_t s = pred[(size_t)(int)fv * tp.W + (int)fu];
+    if (s < 0) return false;
+    const float4 pm = cur.pos_conf[s];
+    const float4 nm = cur.norm_rad[s];
+    const float3 d = make_float3(w.x - pm.x, w.y - pm.y, w.z - pm.z);
+    if (!(sqrtf(dot3(d, d)) <= tp.dist)) return false;
+    const float3 nm3 = make_float3(nm.x, nm.y, nm.z);
+    if (!(dot3(nw, nm3) >= tp.cos_angle)) return false;
+    r = dot3(nm3, d);
+    const float3 wn = cross3(w, nm3);
+    J[0] = nm.x; J[1] = nm.y; J[2] = nm.z; J[3] = wn.x; J[4] = wn.y; J[5] = wn.z;
+    return true;
+}
+
+__device__ __forceinline__ double track_wave_sum(double x)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) x += __shfl_xor(x, o, 64);
+    return x;
+}
+
+// every workgroup: its lanes take grid points idx = blockIdx*256 + tid + k * nb*256 (fixed), so partials do not depend on timing
+__global__ __launch_bounds__(TRACK_BLOCK) void k_track_reduce(Model M, const DevState *__restrict__ st, TrackParams tp,
+                                                              const float4 *__restrict__ vmap, const float4 *__restrict__ nmap,
+                                                              const int32_t *__restrict__ pred, const TrackState *__restrict__ ts,
+                                                              double *__restrict__ part)
+{
+    if (ts->done) return;                                     // converged or failed: the remaining launches are no-ops
+    __shared__ double s_w[TRACK_BLOCK / 64][TRACK_NSYS];
+    float m[16];
+    track_pose_f(ts, m);
+    const SurfelSet cur = M.s[st->cur];
+    double acc[TRACK_NSYS];
+#pragma unroll
+    for (int e = 0; e < TRACK_NSYS; ++e) acc[e] = 0.0;
+    const int step = tp.nb * TRACK_BLOCK;
+    for (int idx = blockIdx.x * TRACK_BLOCK + threadIdx.x; idx < tp.n; idx += step) {
+        float J[6], r;
+        if (!track_pair(idx, m, tp, vmap, nmap, pred, cur, J, r)) continue;
+        int e = 0;
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int b = a; b < 6; ++b) acc[e++] += (double)(J[a] * J[b]);
+#pragma unroll
+        for (int a = 0; a < 6; ++a) acc[21 + a] += (double)(J[a] * r);
+        acc[27] += (double)(r * r);
+        acc[28] += 1.0;
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int e = 0; e < TRACK_NSYS; ++e) {
+        const double x = track_wave_sum(acc[e]);
+        if (lane == 0) s_w[wave][e] = x;
+    }
+    __syncthreads();
+    if (threadIdx.x < TRACK_NSYS) {
+        double x = s_w[0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < TRACK_BLOCK / 64; ++w) x += s_w[w][threadIdx.x];
+        part[(size_t)threadIdx.x * tp.nb + blockIdx.x] = x;
+    }
+}
+
+// exp of the twist (rho, phi) as R (row-major 3x3) and t, double
+__device__ inline void track_exp(const double *xi, double R[3][3], double t[3])
+{
+    const double px = xi[3], py = xi[4], pz = xi[5];
+    const double th2 = px * px + py * py + pz * pz, th = sqrt(th2);
+    double A, B, C;                                           // sin(th)/th, (1-cos)/th^2, (th-sin)/th^3
+    if (th < 1e-4) {
+        A = 1.0 - th2 / 6.0; B = 0.5 - th2 / 24.0; C = 1.0 / 6.0 - th2 / 120.0;
+    } else {
+        A = sin(th) / th; B = (1.0 - cos(th)) / th2; C = (th - sin(th)) / (th2 * th);
+    }
+    const double K[3][3] = {{0.0, -pz, py}, {pz, 0.0, -px}, {-py, px, 0.0}};
+    double K2[3][3];
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) K2[a][b] = K[a][0] * K[0][b] + K[a][1] * K[1][b] + K[a][2] * K[2][b];
+    double V[3][3];
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) {
+            const double I = a == b ? 1.0 : 0.0;
+            R[a][b] = I + A * K[a][b] + B * K2[a][b];
+            V[a][b] = I + B * K[a][b] + C * K2[a][b];
+        }
+    for (int a = 0; a < 3; ++a) t[a] = V[a][0] * xi[0] + V[a][1] * xi[1] + V[a][2] * xi[2];
+}
+
+// LDLT of the symmetric 6x6 A (no pivoting): d[] the pivots, L unit lower; false if a pivot is not positive
+__device__ inline bool track_ldlt(const double A[6][6], double L[6][6], double d[6])
+{
+    for (int j = 0; j < 6; ++j) {
+        double s = A[j][j];
+        for (int k = 0; k < j; ++k) s -= L[j][k] * L[j][k] * d[k];
+        d[j] = s;
+        if (!(s > 0.0)) return false;
+        L[j][j] = 1.0;
+        for (int i = j + 1; i < 6; ++i) {
+            double u = A[i][j];
+            for (int k = 0; k < j; ++k) u -= L[i][k] * L[j][k] * d[k];
+            L[i][j] = u / s;
+        }
+    }
+    return true;
+}
+
+// one workgroup.  sum_only: only the fixed-order sum into ts->sys (sm_track_debug)
+__global__ __launch_bounds__(256) void k_track_solve(TrackParams tp, const double *__restrict__ part, TrackState *__restrict__ ts,
+                                                     int sum_only)
+{
+    if (ts->done) return;
+    __shared__ double s_p[TRACK_NSYS][8];
+    const int t = threadIdx.x;
+    if (t < TRACK_NSYS * 8) {
+        // thread (e, sub) sums partials sub, sub + 8, ... of value e into four interleaved accumulators (independent loads in
+        // flight), then adds them in a fixed order
+        const int e = t >> 3, sub = t & 7;
+        const double *pe = part + (size_t)e * tp.nb;
+        double x0 = 0.0, x1 = 0.0, x2 = 0.0, x3 = 0.0;
+        int b = sub;
+        for (; b + 24 < tp.nb; b += 32) { x0 += pe[b]; x1 += pe[b + 8]; x2 += pe[b + 16]; x3 += pe[b + 24]; }
+        for (; b < tp.nb; b += 8) x0 += pe[b];
+        s_p[e][sub] = (x0 + x1) + (x2 + x3);
+    }
+    __syncthreads();
+    if (t != 0) return;
+    double sys[TRACK_NSYS];
+    for (int e = 0; e < TRACK_NSYS; ++e) {
+        double x = s_p[e][0];
+        for (int k = 1; k < 8; ++k) x += s_p[e][k];
+        sys[e] = x;
+        ts->sys[e] = x;
+    }
+    if (sum_only) return;
+    const double cnt = sys[28];
+    ts->iterations += 1;
+    ts->inliers = (uint32_t)cnt;
+    ts->rmse = cnt > 0.0 ? sqrt(sys[27] / cnt) : 0.0;
+    auto fail = [&](int status) {
+        for (int e = 0; e < 16; ++e) ts->T[e] = ts->guess[e];
+        ts->status = status;
+        ts->done = 1;
+    };
+    if (ts->iterations == 1 && ts->in_view == 0u) { fail(TRACK_NO_MODEL); return; }
+    if (cnt < (double)tp.min_inliers || cnt < 6.0) { fail(TRACK_LOST); return; }
+    double A[6][6], b[6];
+    int e = 0;
+    for (int a = 0; a < 6; ++a)
+        for (int c = a; c < 6; ++c) { A[a][c] = sys[e]; A[c][a] = sys[e]; ++e; }
+    for (int a = 0; a < 6; ++a) b[a] = sys[21 + a];
+    // degeneracy: the same system with the rotation taken about the prediction camera centre c (rows [n, (Tv - c) x n]: B = M^T A M,
+    // M = [[I, [c]x], [0, I]]) and the rotation columns scaled by 1/s, s^2 = (trace of its rotation block) / (trace of its
+    // translation block): unit-free and independent of where the world origin lies
+    {
+        const double cx = tp.c[0], cy = tp.c[1], cz = tp.c[2];
+        const double Mx[6][6] = {{1, 0, 0, 0, -cz, cy}, {0, 1, 0, cz, 0, -cx}, {0, 0, 1, -cy, cx, 0},
+                                 {0, 0, 0, 1, 0, 0}, {0, 0, 0, 0, 1, 0}, {0, 0, 0, 0, 0, 1}};
+        double AM[6][6], B[6][6];
+        for (int i = 0; i < 6; ++i)
+            for (int j = 0; j < 6; ++j) {
+                double x = 0.0;
+                for (int k = 0; k < 6; ++k) x += A[i][k] * Mx[k][j];
+                AM[i][j] = x;
+            }
+        for (int i = 0; i < 6; ++i)
+            for (int j = 0; j < 6; ++j) {
+                double x = 0.0;
+                for (int k = 0; k < 6; ++k) x += Mx[k][i] * AM[k][j];
+                B[i][j] = x;
+            }
+        const double tr_t = B[0][0] + B[1][1] + B[2][2], tr_r = B[3][3] + B[4][4] + B[5][5];
+        const double sc = tr_r > 0.0 && tr_t > 0.0 ? sqrt(tr_t / tr_r) : 1.0;
+        for (int i = 0; i < 6; ++i)
+            for (int j = 0; j < 6; ++j) B[i][j] *= (i >= 3 ? sc : 1.0) * (j >= 3 ? sc : 1.0);
+        double L[6][6], d[6];
+        double ratio = 0.0;
+        if (track_ldlt(B, L, d)) {
+            double lo = d[0], hi = d[0];
+            for (int k = 1; k < 6; ++k) { lo = fmin(lo, d[k]); hi = fmax(hi, d[k]); }
+            ratio = lo / hi;
+        }
+        ts->pivot_ratio = ratio;
+    }
+    // (judged on the system of the last iteration: a poor guess can pair mostly ground and walls in the first ones)
+    const bool degenerate = !(ts->pivot_ratio >= tp.degenerate_bound);
+    // Gauss-Newton step: (J^T J) xi = -J^T r
+    double L[6][6], d[6], xi[6], y[6];
+    if (!track_ldlt(A, L, d)) { fail(TRACK_DEGENERATE); return; }
+    for (int i = 0; i < 6; ++i) {
+        double x = -b[i];
+        for (int k = 0; k < i; ++k) x -= L[i][k] * y[k];
+        y[i] = x;
+    }
+    for (int i = 5; i >= 0; --i) {
+        double x = y[i] / d[i];
+        for (int k = i + 1; k < 6; ++k) x -= L[k][i] * xi[k];
+        xi[i] = x;
+    }
+    double R[3][3], tt[3];
+    track_exp(xi, R, tt);
+    const double *T = ts->T;                                  // column-major: T[c * 4 + r]
+    double Tn[16];
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) Tn[c * 4 + r] = R[r][0] * T[c * 4 + 0] + R[r][1] * T[c * 4 + 1] + R[r][2] * T[c * 4 + 2];
+        Tn[12 + r] = R[r][0] * T[12] + R[r][1] * T[13] + R[r][2] * T[14] + tt[r];
+    }
+    Tn[3] = 0.0; Tn[7] = 0.0; Tn[11] = 0.0; Tn[15] = 1.0;
+    for (int k = 0; k < 16; ++k) ts->T[k] = Tn[k];
+    ts->step_rot = sqrt(xi[3] * xi[3] + xi[4] * xi[4] + xi[5] * xi[5]);
+    ts->step_trans = sqrt(xi[0] * xi[0] + xi[1] * xi[1] + xi[2] * xi[2]);
+    const bool converged = ts->step_rot < 1e-6 && ts->step_trans < 1e-6;
+    if ((converged || ts->iterations >= tp.max_iters) && degenerate) { fail(TRACK_DEGENERATE); return; }
+    if (converged) ts->done = 1;
+}

@@ -18,5 +18,6 @@ namespace sm {
 #include "sm_k_shard.h"
 #include "sm_k_aux.h"
 #include "sm_k_view.h"
+#include "sm_k_track.h"
 
 }  // namespace sm

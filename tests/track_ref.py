@@ -1,0 +1,233 @@
+"""numpy restatement of the tracker (sm_track_frame, surfelmapping_amd/csrc/sm_k_track.h) -- the checker of tests/test_track.py.
+Every float32 step below is one IEEE float32 operation of the kernels, in their order (no contraction), so the prediction is
+equal slot for slot; the 29 sums are float32 terms added in float64 (in another order than the GPU's: equal to rounding).
+`solve` restates one Gauss-Newton step of k_track_solve in float64."""
+import math
+
+import numpy as np
+
+f32 = np.float32
+EMPTY = np.uint64(0x7FFFFFFFFFFFFFFF)
+NSYS = 29
+
+
+def pixel_tables(W, H):
+    """xs[i], ys[j]: the pixel-centre coordinates data.vert sees (sm_create: float((i + 0.5) / (double)(float)W) * W)"""
+    cols, rows = f32(W), f32(H)
+    xs = (np.array([(i + 0.5) / float(cols) for i in range(W)], np.float64).astype(f32) * cols).astype(f32)
+    ys = (np.array([(j + 0.5) / float(rows) for j in range(H)], np.float64).astype(f32) * rows).astype(f32)
+    return xs, ys
+
+
+def colmajor(m):
+    a = np.asarray(m, f32)
+    return np.ascontiguousarray((a.T if a.shape == (4, 4) else a).reshape(16))
+
+
+def rigid_inv_d(m16):
+    """[R^T | -R^T t] of a column-major pose in double (sm_api.hip rigid_inv_d)"""
+    m = np.asarray(m16, np.float64)
+    o = np.zeros(16)
+    for r in range(3):
+        for c in range(3):
+            o[c * 4 + r] = m[r * 4 + c]
+        o[12 + r] = -((m[r * 4 + 0] * m[12] + m[r * 4 + 1] * m[13]) + m[r * 4 + 2] * m[14])
+    o[15] = 1.0
+    return o
+
+
+def _xform(m, x, y, z):
+    return [((m[r] * x + m[r + 4] * y) + m[r + 8] * z) + m[r + 12] for r in range(3)]
+
+
+def _rot(m, x, y, z):
+    return [(m[r] * x + m[r + 4] * y) + m[r + 8] * z for r in range(3)]
+
+
+def _dot(a, b):
+    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
+
+
+def _cross(a, b):
+    return [a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]]
+
+
+def _project(cam, c):
+    with np.errstate(all="ignore"):
+        fu = np.floor(((f32(cam["fx"]) * c[0]) / c[2] + f32(cam["cx"])) + f32(0.5))
+        fv = np.floor(((f32(cam["fy"]) * c[1]) / c[2] + f32(cam["cy"])) + f32(0.5))
+    inb = (fu >= 0) & (fu < f32(cam["width"])) & (fv >= 0) & (fv < f32(cam["height"]))
+    return fu, fv, inb
+
+
+def predict(model, t_prev16, cam, near=1.0, far=30.0, live=None):
+    """k_track_splat + k_track_resolve: model AoS float32[n][12] whose row = slot, `live` an optional bool mask of the slots.
+    Returns int32[H][W] (slot or -1)."""
+    W, H = cam["width"], cam["height"]
+    tinv = rigid_inv_d(colmajor(t_prev16)).astype(f32)
+    p = np.asarray(model, f32)
+    c = _xform(tinv, p[:, 0], p[:, 1], p[:, 2])
+    ok = (c[2] > f32(near)) & (c[2] < f32(far))
+    if live is not None:
+        ok &= live
+    fu, fv, inb = _project(cam, c)
+    ok &= inb
+    slots = np.nonzero(ok)[0].astype(np.uint64)
+    pix = fv[ok].astype(np.int64) * W + fu[ok].astype(np.int64)
+    key = (c[2][ok].view(np.uint32).astype(np.uint64) << np.uint64(32)) | slots
+    keys = np.full(W * H, EMPTY, np.uint64)
+    np.minimum.at(keys, pix, key)
+    out = np.where(keys == EMPTY, -1, (keys & np.uint64(0xFFFFFFFF)).astype(np.int64)).astype(np.int32)
+    return out.reshape(H, W)
+
+
+def metric_depth(depth_mm, near=1.0, far=30.0, stereo_border=80.0):
+    """p0a's metricise rule (sm_k_prep.h prep_image_block): mm -> m inside the clip range, 0 left of stereo_border"""
+    lo = np.uint32(f32(near) * f32(1000.0))
+    hi = np.uint32((f32(far) - f32(0.001)) * f32(1000.0))
+    v = np.asarray(depth_mm, np.uint16).astype(np.uint32)
+    H, W = v.shape
+    i = np.arange(W, dtype=f32)[None, :]
+    keep = ~((i + f32(0.5)) < f32(stereo_border)) & (v > lo) & (v < hi)
+    return np.where(keep, v.astype(f32) / f32(1000.0), f32(0.0)).astype(f32)
+
+
+def vertex_normal(depth_mm, cam, near=1.0, far=30.0, stereo_border=80.0, stride=1):
+    """k_track_vertex on the strided grid (row-major over it): (vmap float32[n][4] (xyz, 1 = valid), nmap float32[n][4])"""
+    W, H = cam["width"], cam["height"]
+    z = metric_depth(depth_mm, near, far, stereo_border)
+    xs, ys = pixel_tables(W, H)
+    inv_fx, inv_fy = f32(1.0 / float(f32(cam["fx"]))), f32(1.0 / float(f32(cam["fy"])))
+    cx, cy = f32(cam["cx"]), f32(cam["cy"])
+    ii = np.arange(0, W, stride)
+    jj = np.arange(0, H, stride)
+    J, I = np.meshgrid(jj, ii, indexing="ij")
+    zc = z[J, I]
+    zl, zr = z[J, np.maximum(I - 1, 0)], z[J, np.minimum(I + 1, W - 1)]
+    zu, zd = z[np.maximum(J - 1, 0), I], z[np.minimum(J + 1, H - 1), I]
+    x, y = xs[I], ys[J]
+    one = f32(1.0)
+
+    def vert(zz, xx, yy):
+        return [((xx - cx) * zz) * inv_fx, ((yy - cy) * zz) * inv_fy, zz]
+
+    with np.errstate(all="ignore"):
+        p = vert(zc, x, y)
+        xf, xb = vert(zr, x + one, y), vert(zl, x - one, y)
+        yf, yb = vert(zd, x, y + one), vert(zu, x, y - one)
+        dx = [xb[k] - xf[k] for k in range(3)]
+        dy = [yb[k] - yf[k] for k in range(3)]
+        cr = _cross(dx, dy)
+        l = np.sqrt(_dot(cr, cr))
+        n = [cr[k] / l for k in range(3)]
+    valid = (zc > 0) & (zl != 0) & (zu != 0) & (zr != 0) & (zd != 0)
+    valid &= np.isfinite(n[0]) & np.isfinite(n[1]) & np.isfinite(n[2])
+    vmap = np.zeros(zc.shape + (4,), f32)
+    nmap = np.zeros(zc.shape + (4,), f32)
+    for k in range(3):
+        vmap[..., k] = np.where(valid, p[k], 0)
+        nmap[..., k] = np.where(valid, n[k], 0)
+    vmap[..., 3] = valid.astype(f32)
+    return vmap.reshape(-1, 4), nmap.reshape(-1, 4)
+
+
+def system(vmap, nmap, pred, model, pose16, t_prev16, cam, dist=0.3, angle_deg=30.0):
+    """k_track_reduce + the fixed-order sum of k_track_solve at pose16: float64[29] (JtJ upper triangle row-major, Jtr, r^2, n)"""
+    W = cam["width"]
+    m = colmajor(pose16)
+    tinv = rigid_inv_d(colmajor(t_prev16)).astype(f32)
+    cosa = f32(math.cos(angle_deg * (math.pi / 180.0)))
+    v = vmap[vmap[:, 3] != 0]
+    n = nmap[vmap[:, 3] != 0]
+    with np.errstate(all="ignore"):
+        w = _xform(m, v[:, 0], v[:, 1], v[:, 2])
+        nw = _rot(m, n[:, 0], n[:, 1], n[:, 2])
+        c = _xform(tinv, w[0], w[1], w[2])
+        fu, fv, inb = _project(cam, c)
+        ok = (c[2] > 0) & inb
+        slot = np.full(len(v), -1, np.int64)
+        slot[ok] = pred.reshape(-1)[fv[ok].astype(np.int64) * W + fu[ok].astype(np.int64)]
+        ok &= slot >= 0
+        mdl = np.asarray(model, f32)[np.where(ok, slot, 0)]
+        pm, nm = [mdl[:, k] for k in range(3)], [mdl[:, 8 + k] for k in range(3)]
+        d = [w[k] - pm[k] for k in range(3)]
+        ok &= np.sqrt(_dot(d, d)) <= f32(dist)
+        ok &= _dot(nw, nm) >= cosa
+        r = _dot(nm, d)
+        wn = _cross(w, nm)
+    Jc = [nm[0], nm[1], nm[2], wn[0], wn[1], wn[2]]
+    out = np.zeros(NSYS)
+    e = 0
+    for a in range(6):
+        for b in range(a, 6):
+            out[e] = (Jc[a][ok] * Jc[b][ok]).astype(np.float64).sum()
+            e += 1
+    for a in range(6):
+        out[21 + a] = (Jc[a][ok] * r[ok]).astype(np.float64).sum()
+    out[27] = (r[ok] * r[ok]).astype(np.float64).sum()
+    out[28] = float(ok.sum())
+    return out
+
+
+def _ldlt(A):
+    L, d = np.eye(6), np.zeros(6)
+    for j in range(6):
+        d[j] = A[j, j] - sum(L[j, k] ** 2 * d[k] for k in range(j))
+        if not d[j] > 0:
+            return None, None
+        for i in range(j + 1, 6):
+            L[i, j] = (A[i, j] - sum(L[i, k] * L[j, k] * d[k] for k in range(j))) / d[j]
+    return L, d
+
+
+def unpack(sys29):
+    A = np.zeros((6, 6))
+    e = 0
+    for a in range(6):
+        for b in range(a, 6):
+            A[a, b] = A[b, a] = sys29[e]
+            e += 1
+    return A, np.asarray(sys29[21:27], np.float64)
+
+
+def pivot_ratio(sys29, centre):
+    """k_track_solve's degeneracy measure: smallest / largest LDLT pivot of the camera-centred, block-scaled system"""
+    A, _ = unpack(sys29)
+    cx, cy, cz = centre
+    M = np.eye(6)
+    M[:3, 3:] = [[0, -cz, cy], [cz, 0, -cx], [-cy, cx, 0]]
+    B = M.T @ A @ M
+    s = math.sqrt(np.trace(B[:3, :3]) / np.trace(B[3:, 3:]))
+    S = np.diag([1, 1, 1, s, s, s])
+    _, d = _ldlt(S @ B @ S)
+    return 0.0 if d is None else d.min() / d.max()
+
+
+def se3_exp(xi):
+    rho, phi = np.asarray(xi[:3]), np.asarray(xi[3:])
+    th = np.linalg.norm(phi)
+    K = np.array([[0, -phi[2], phi[1]], [phi[2], 0, -phi[0]], [-phi[1], phi[0], 0]])
+    if th < 1e-4:
+        A, B, C = 1 - th * th / 6, 0.5 - th * th / 24, 1 / 6 - th * th / 120
+    else:
+        A, B, C = math.sin(th) / th, (1 - math.cos(th)) / th ** 2, (th - math.sin(th)) / th ** 3
+    R = np.eye(3) + A * K + B * K @ K
+    V = np.eye(3) + B * K + C * K @ K
+    T = np.eye(4)
+    T[:3, :3], T[:3, 3] = R, V @ rho
+    return T
+
+
+def solve(sys29, T):
+    """one Gauss-Newton step: (JtJ) xi = -Jtr, T <- exp(xi) T (4x4 float64, numpy row/col indexing); returns (T', xi)"""
+    A, b = unpack(sys29)
+    xi = np.linalg.solve(A, -b)
+    return se3_exp(xi) @ np.asarray(T, np.float64), xi
+
+
+def pose_error(a, b):
+    """(translation error m, rotation error deg) between two 4x4 poses"""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    d = np.linalg.inv(b) @ a
+    c = np.clip((np.trace(d[:3, :3]) - 1) / 2, -1.0, 1.0)
+    return float(np.linalg.norm(a[:3, 3] - b[:3, 3])), math.degrees(math.acos(c))

@@ -20,6 +20,7 @@
 #include <cstring>
 #include <atomic>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -47,6 +48,36 @@ void set_err(const char *what, hipError_t e, const char *file, int line)
         }                                                        \
     } while (0)
 
+// Owner of one HIP handle (device or pinned host memory, an event, a stream): move-only, released by its destructor on the
+// current device (sm_destroy makes the context's device current).  It reads as the raw handle, so kernel arguments and argument
+// structs take it unchanged.  put() releases what it holds and hands out the slot for a create call, filled only on success.
+template <typename H, auto Release>
+class Own {
+public:
+    Own() = default;
+    Own(Own &&o) noexcept : h_(o.release()) {}
+    Own &operator=(Own o) noexcept { std::swap(h_, o.h_); return *this; }
+    ~Own() { if (h_) (void)Release(h_); }
+    operator H() const { return h_; }
+    H operator->() const { return h_; }
+    H get() const { return h_; }
+    H *put() { *this = Own(); return &h_; }
+    H release() { H h = h_; h_ = nullptr; return h; }
+private:
+    H h_ = nullptr;
+};
+template <typename T> using Dev = Own<T *, hipFree>;
+template <typename T> using Host = Own<T *, hipHostFree>;
+using Event = Own<hipEvent_t, hipEventDestroy>;
+using Stream = Own<hipStream_t, hipStreamDestroy>;
+
+// the buffers behind one SurfelSet (Model is passed to kernels by value and stays a set of views)
+struct SetBufs {
+    Dev<float4> pos_conf, norm_rad;
+    Dev<uint32_t> color;
+    Dev<float> init_time, time;
+    SurfelSet view() const { return {pos_conf, norm_rad, color, init_time, time}; }
+};
 constexpr int EV_RING = 256;
 constexpr int N_EV = 9;           // start, prep, conflict, scan_cull, compact, associate, scan_new, append, + calibration
 constexpr int MAX_GRID = 2048;   // 256 CUs x 8 workgroups
@@ -253,70 +284,71 @@ bool compaction_needs_tickets(int dev)
 }  // namespace
 
 struct sm_ctx {
+    // the streams come first: members die in reverse order, so everything used on them is released before they are
+    Stream stream;
+    Stream stream_in;                  // ONE copy stream.  (Two -- colour on one engine, depth + class on another -- were 80 instead of 89 us per frame on
+                                       // one box of the pool and stalled for 10-16 ms every few dozen frames on others; tools/h2d_probe.hip: per frame, three
+                                       // copies on two streams 68 us + stalls, on one stream 87, ONE copy of the whole frame 58 = the PCIe rate.)
     sm_config cfg{};
     int W = 0, H = 0, P = 0;
     uint32_t cap = 0;                 // MAX_VERTICES
-    hipStream_t stream = nullptr;
     // The four frame planes exist twice (the *_nx pointers are the set of the other frame): a frame's association is held back
     // and runs in the NEXT frame's preparation launch, which writes the other set.  (Rounds 1-2 ran the depth filter chain of
     // frame f+1 on a second stream instead; since round 3 the chain is a stage of the preparation launch itself.)
     int plane_set = 0;                 // which plane set the current frame uses
     Model M{};
-    DevState *d_state = nullptr;
-    DevState *h_state = nullptr;      // pinned mirror
+    SetBufs m_bufs[2];                 // the buffers behind M.s[0] and M.s[1]
+    Dev<DevState> d_state;
+    Host<DevState> h_state;           // pinned mirror
     // column-major frame images
-    float *d_depthT = nullptr, *d_filteredT = nullptr, *d_lastT = nullptr;
-    uint32_t *d_rgbsT = nullptr;
-    uint2 *d_dcT = nullptr;            // (depth bits, rgbs) of the frame the conflict test sees
-    float *d_depthT_nx = nullptr; uint32_t *d_rgbsT_nx = nullptr; uint64_t *d_keyT_nx = nullptr; uint2 *d_dcT_nx = nullptr;
-    uint64_t *d_keyT = nullptr;
+    Dev<float> d_depthT, d_filteredT, d_lastT;
+    Dev<uint32_t> d_rgbsT;
+    Dev<uint2> d_dcT;                  // (depth bits, rgbs) of the frame the conflict test sees
+    Dev<float> d_depthT_nx; Dev<uint32_t> d_rgbsT_nx; Dev<uint64_t> d_keyT_nx; Dev<uint2> d_dcT_nx;
+    Dev<uint64_t> d_keyT;
     // row-major staging of the caller's inputs
-    uint8_t *d_rgb = nullptr, *d_sem = nullptr;
-    uint16_t *d_depth_raw = nullptr;
+    Dev<uint8_t> d_rgb, d_sem;
+    Dev<uint16_t> d_depth_raw;
     // sm_process_frame_async: a ring of device input sets filled on a copy stream, so that the H2D copy of frame f+1 runs while
     // frame f computes; images in buffers of sm_host_alloc are copied from in place, others through pinned staging
     static constexpr int IN_RING = 3;
-    struct InSlot { uint8_t *rgb = nullptr, *sem = nullptr; uint16_t *depth = nullptr; unsigned char *h_stage = nullptr;
-                    hipEvent_t ev_in = nullptr, ev_free = nullptr; bool used = false; };
+    struct InSlot { Dev<uint8_t> rgb; uint8_t *sem = nullptr; uint16_t *depth = nullptr;   // one block: depth and class follow the colour image
+                    Host<unsigned char> h_stage; Event ev_in, ev_free; bool used = false; };
     InSlot in[IN_RING];
-    hipStream_t stream_in = nullptr;   // ONE copy stream.  (Two -- colour on one engine, depth + class on another -- were 80 instead of 89 us per frame on
-                                       // one box of the pool and stalled for 10-16 ms every few dozen frames on others; tools/h2d_probe.hip: per frame, three
-                                       // copies on two streams 68 us + stalls, on one stream 87, ONE copy of the whole frame 58 = the PCIe rate.)
     size_t in_off_depth = 0, in_off_sem = 0, in_bytes = 0;   // a frame's images as ONE block: colour | depth | class, 16-byte aligned (sm_host_alloc_frame)
     uint32_t in_next = 0;
     const uint16_t *in_last_depth = nullptr; const uint8_t *in_last_sem = nullptr;     // device copies of the last depth / semantic image given
     int in_depth_slot = -1, in_sem_slot = -1;                                          // ... and the input sets that hold them
-    // Pinned host buffers handed out by sm_host_alloc (their ranges in `pinned`): the sources sm_process_frame_async copies from in
+    // Pinned host buffers handed out by sm_host_alloc, with their sizes: the sources sm_process_frame_async copies from in
     // place.  Caller memory is never registered: hipHostRegister / hipHostUnregister of heap ranges left the runtime treating
     // later, unrelated host arrays at the same addresses as pinned -- a GPU memory fault in whatever copied to or from them next.
-    std::vector<std::pair<const unsigned char *, size_t>> pinned;
-    std::vector<void *> host_allocs;
-    float *d_depth_f32 = nullptr;
-    float *d_xs = nullptr, *d_ys = nullptr;
+    std::vector<std::pair<Host<unsigned char>, size_t>> pinned;
+    Dev<float> d_depth_f32;
+    Dev<float> d_xs, d_ys;
     float h_wtab[169];                 // depth_smooth.frag's 13 x 13 weights (host-computed, handed to the chain stage as kernel arguments)
     // cull scratch
-    uint64_t *d_cm = nullptr, *d_dm = nullptr, *d_zm = nullptr;
-    uint32_t *d_tile_cnt = nullptr, *d_tile_allow = nullptr, *d_tile_keep = nullptr, *d_tile_flag = nullptr;
-    uint32_t *d_group_tot = nullptr, *d_group_base = nullptr;
-    uint64_t *d_alive = nullptr;       // 1 bit per slot: 0 = killed since the last physical compaction (free slots are 1)
-    uint32_t *d_tile_dead = nullptr;   // dead slots per tile
+    Dev<uint64_t> d_cm, d_dm, d_zm;
+    Dev<uint32_t> d_tile_cnt, d_tile_allow, d_tile_keep, d_tile_flag;
+    Dev<uint32_t> d_group_tot, d_group_base;
+    Dev<uint64_t> d_alive;             // 1 bit per slot: 0 = killed since the last physical compaction (free slots are 1)
+    Dev<uint32_t> d_tile_dead;         // dead slots per tile
     size_t alive_words = 0, dead_tiles = 0;
     bool maybe_garbage = false;        // a deferred-compaction cull ran since the last physical compaction
     bool keys_are_slots = false;       // the key map was drawn by a cull that did not compact: its ids are slot numbers
     int culls_since_compact = 0;       // deferred-compaction schedule (host side: it picks the kernels)
     uint32_t frames_enq = 0;           // appends enqueued so far (compared with the tag of *h_stat)
-    unsigned long long *h_stat = nullptr, *d_stat = nullptr;   // pinned, device-written: frames<<32 | occupied slots
-    uint32_t *d_tb = nullptr;          // per-tile bounds (8 words per tile)
-    uint8_t *d_tile_flags = nullptr;   // per-tile skip flags of the current frame
-    uint8_t *d_tile_flags_nx = nullptr; uint4 *d_wave_cnt_nx = nullptr; uint2 *d_prep_part_nx = nullptr;   // the other frame's (two-launch frame: its publisher runs next to this frame's flag workgroups)
-    uint32_t *d_conf_part = nullptr;   // per-workgroup partial counters (instead of same-address atomics)
-    uint2 *d_compact_part = nullptr;
-    uint4 *d_lazy_part = nullptr;      // partials of k_surfel_pass (visible, splat-skipped, killed, conflict-skipped)
+    Host<unsigned long long> h_stat; unsigned long long *d_stat = nullptr;   // pinned, device-written: frames<<32 | occupied slots
+    Dev<uint32_t> d_tb;                // per-tile bounds (8 words per tile)
+    Dev<uint8_t> d_tile_flags;         // per-tile skip flags of the current frame
+    Dev<uint8_t> d_tile_flags_nx; Dev<uint4> d_wave_cnt_nx; Dev<uint2> d_prep_part_nx;   // the other frame's (two-launch frame: its publisher runs next to this frame's flag workgroups)
+    Dev<uint32_t> d_conf_part;         // per-workgroup partial counters (instead of same-address atomics)
+    Dev<uint2> d_compact_part;
+    Dev<uint4> d_lazy_part;            // partials of k_surfel_pass (visible, splat-skipped, killed, conflict-skipped)
     bool lazy_part_live = false;       // the next append folds d_lazy_part (not d_compact_part) into the counters
     // one pass over the surfels per frame (k_surfel_pass + k_pass_fixup) on the frames whose cull only marks the dead
-    uint4 *d_wave_cnt = nullptr;       // conflicts per quarter tile (one word per wave)
-    float *d_undo = nullptr;           // confidence before this frame's decrement, per slot (read only if the conflict cap binds)
-    uint2 *d_fix_part = nullptr;       // partials of k_pass_fixup (visible added, resurrected)
+    Dev<uint4> d_wave_cnt;             // conflicts per quarter tile (one word per wave)
+    Dev<float> d_undo;                 // confidence before this frame's decrement, per slot (read only if the conflict cap binds)
+    Dev<uint2> d_fix_part;             // partials of k_pass_fixup (visible added, resurrected)
     bool fix_part_live = false;        // the next append also folds d_fix_part in (when the cap bound)
     uint32_t n_fix_part = 0;           // worker workgroups of the last k_pass_fixup
     bool ev_one_pass[EV_RING] = {};    // which frames of the event ring ran the one-pass kernels
@@ -324,23 +356,23 @@ struct sm_ctx {
     bool ev_merged[EV_RING] = {};      // the frame's preparation launch was k_assoc_prep (it carried the previous frame's association)
     bool ev_deferred[EV_RING] = {};    // the frame's own association was held back (no kernel between its marks 4 and 5)
     // tile skip flags of the frame, evaluated by extra workgroups of the preparation launch
-    uint2 *d_prep_part = nullptr;
+    Dev<uint2> d_prep_part;
     uint32_t n_prep_blocks = 0;        // flag workgroups the frame's k_prep ran (0: the pass kernel evaluates the flags itself)
     bool want_list = false;            // set by enqueue_frame before begin_frame launches k_prep
     int fix_grid = 128;
     // direct append (k_associate_direct): candidate counts per association block / per group, group prefixes
-    uint32_t *d_blk_cand = nullptr, *d_grp_cand = nullptr;
-    uint32_t *d_frame_sub = nullptr;   // 2 x 64 sub-counters: visible, killed (k_surfel_pass)
+    Dev<uint32_t> d_blk_cand, d_grp_cand;
+    Dev<uint32_t> d_frame_sub;         // 2 x 64 sub-counters: visible, killed (k_surfel_pass)
     uint32_t *d_nf_sub = nullptr, *d_nf_sub_nx = nullptr;   // 2 x 64 each: new, fused (k_associate_direct) of this / the other frame
     uint32_t *nf_last = nullptr;       // the set the last direct association counted into (its statistics may still be pending)
     uint32_t n_grp = 0, cand_group = 16;
     bool pend_finalize = false;        // the last frame's statistics are completed by the next k_pass_fixup or by k_frame_finalize
     int fix_set = 0;                   // k_pass_fixup's partials alternate between two sets (the previous frame's are read one frame later)
-    unsigned long long *d_pass_trace = nullptr;   // SM_PASS_TRACE=<file prefix>: per-workgroup time stamps of the last k_surfel_pass launch, dumped by sm_destroy
+    Dev<unsigned long long> d_pass_trace;         // SM_PASS_TRACE=<file prefix>: per-workgroup time stamps of the last k_surfel_pass launch, dumped by sm_destroy
     int pass_trace_grid = 0;
-    unsigned long long *d_ap_trace = nullptr;     // the same for the last k_assoc_prep launch: (entry, exit) per workgroup
+    Dev<unsigned long long> d_ap_trace;           // the same for the last k_assoc_prep launch: (entry, exit) per workgroup
     int ap_trace_n[4] = {0, 0, 0, 0};             // its association / tile-flag / image workgroups (dispatch order); fixup workgroups ahead of them
-    uint32_t *d_conf_sub = nullptr;    // 2 x 64 conflict sub-counters (one set per frame parity: zeroed by that frame's k_prep)
+    Dev<uint32_t> d_conf_sub;          // 2 x 64 conflict sub-counters (one set per frame parity: zeroed by that frame's k_prep)
     int conf_sub_set = 0;
     uint32_t n_conf_part = 0, n_compact_part = 0;
     uint32_t tb_tiles = 0;
@@ -348,8 +380,8 @@ struct sm_ctx {
     int compact_grid = COMPACT_GRID;
     int pass_grid = MAX_GRID;          // workgroups of k_surfel_pass that are resident at once (a larger grid runs its tail as a second, thin wave)
     // association scratch
-    uint64_t *d_validmask = nullptr, *d_fusedmask = nullptr;
-    uint2 *d_blk_cnt = nullptr;
+    Dev<uint64_t> d_validmask, d_fusedmask;
+    Dev<uint2> d_blk_cnt;
     // slot-addressed sharding of one stream, in-stream form (sm_shard_stream_*)
     bool ss_on = false;
     bool rig_on = false;               // sm_rig_configure: rank / world / collective are used by sm_rig_consolidate only
@@ -359,10 +391,10 @@ struct sm_ctx {
     sm_collective_fn ss_coll = nullptr;
     void *ss_user = nullptr;
     void *ss_comm = nullptr;           // ncclComm_t when the built-in RCCL binding is used
-    uint64_t *d_galive = nullptr, *d_new_alive = nullptr, *d_gmask = nullptr;
-    uint32_t *d_chk = nullptr;         // SM_CHECK_ALIVE=1: result words of k_check_alive
-    uint64_t *d_capx = nullptr;        // the conflict-cap exchange of a sharded frame: total | quarter-tile counts | conflict masks (k_shard_cap_pack)
-    uint32_t *d_ss_info = nullptr;
+    Dev<uint64_t> d_galive, d_new_alive, d_gmask;
+    Dev<uint32_t> d_chk;               // SM_CHECK_ALIVE=1: result words of k_check_alive
+    Dev<uint64_t> d_capx;              // the conflict-cap exchange of a sharded frame: total | quarter-tile counts | conflict masks (k_shard_cap_pack)
+    Dev<uint32_t> d_ss_info;
     // deferred association (k_assoc_prep): the association of an asynchronous frame is held back until the next frame's images
     // arrive and then shares that frame's k_prep launch (three launches per frame instead of four)
     bool defer_ok = false;             // this context may defer (plain stream, no depth filter chain, no per-kernel timing)
@@ -381,26 +413,27 @@ struct sm_ctx {
     int n_pix_blocks = 0;
     uint32_t n_odd_pixels = 0;
     // export staging
-    void *d_export = nullptr;
+    Dev<void> d_export;
     size_t export_bytes = 0;
     // model view (sm_render_model): where the last render left its overflow-list length in the export scratch (valid until the
     // scratch is reused), and the diagnostic timing events (SM_RENDER_MODEL_TIMING=1)
     size_t rm_ovf_off = 0;
     bool rm_ovf_valid = false;
     bool rm_timed = false;
-    hipEvent_t rm_ev[4] = {};
+    Event rm_ev[4];
     // tracking (sm_track_frame / sm_track_debug, sm_k_track.h): scratch allocated by the first call, the last two processed poses
-    uint16_t *d_trk_depth = nullptr;
-    float4 *d_trk_v = nullptr, *d_trk_n = nullptr;
-    uint64_t *d_trk_key = nullptr;
-    int32_t *d_trk_pred = nullptr;
-    double *d_trk_part = nullptr;
-    TrackState *d_trk = nullptr, *h_trk = nullptr;
+    Dev<uint16_t> d_trk_depth;
+    Dev<float4> d_trk_v, d_trk_n;
+    Dev<uint64_t> d_trk_key;
+    Dev<int32_t> d_trk_pred;
+    Dev<double> d_trk_part;
+    Dev<TrackState> d_trk;
+    Host<TrackState> h_trk;
     float trk_hist[2][16];             // [0] the last processed pose (T_prev), [1] the one before (T_prev2)
     int trk_n_hist = 0;                // poses processed so far (capped at 2)
     bool trk_timed = false;            // SM_TRACK_TIMING=1 at the last call: events around every kernel
     int trk_ev_iters = 0;              // iterations the events of the last timed call cover
-    std::vector<hipEvent_t> trk_ev;
+    std::vector<Event> trk_ev;
     // host frame state (src/SurfelMapping.h:100-103)
     int tick = 0;
     bool ref_set = false;
@@ -411,39 +444,27 @@ struct sm_ctx {
     bool pending_cull = false;
     uint32_t count_before_cull = 0, offset_before_cull = 0;
     sm_counts counts{};
-    std::vector<void *> user_allocs;
+    std::vector<Dev<void>> user_allocs;
     // timing
-    hipEvent_t ev[N_EV][EV_RING];     // per-frame timeline: before prep, then after each kernel
+    std::unique_ptr<Event[][EV_RING]> ev;   // enable_timing: per-frame timeline (before prep, then after each kernel), [N_EV][EV_RING]; whole or absent
     bool ev_compacted[EV_RING] = {};  // which cull kernel the frame of that slot ran
-    FrameLog *d_log = nullptr;
-    bool ev_ok = false;
+    Dev<FrameLog> d_log;
     uint64_t ev_frames = 0, ev_read = 0;
 };
 
 namespace {
 
 template <typename T>
-int dalloc(T **p, size_t n)
+int dalloc(Dev<T> &p, size_t n)
 {
-    HIPCK(hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T)));
+    HIPCK(hipMalloc(p.put(), std::max<size_t>(n, 1) * sizeof(T)));
     return SM_OK;
 }
 
-int alloc_set(SurfelSet &s, size_t cap)
+int alloc_set(SetBufs &b, size_t cap)
 {
-    int rc;
-    if ((rc = dalloc(&s.pos_conf, cap))) return rc;
-    if ((rc = dalloc(&s.norm_rad, cap))) return rc;
-    if ((rc = dalloc(&s.color, cap))) return rc;
-    if ((rc = dalloc(&s.init_time, cap))) return rc;
-    if ((rc = dalloc(&s.time, cap))) return rc;
-    return SM_OK;
-}
-
-void free_set(SurfelSet &s)
-{
-    (void)hipFree(s.pos_conf); (void)hipFree(s.norm_rad); (void)hipFree(s.color);
-    (void)hipFree(s.init_time); (void)hipFree(s.time);
+    return dalloc(b.pos_conf, cap) || dalloc(b.norm_rad, cap) || dalloc(b.color, cap) || dalloc(b.init_time, cap) ||
+           dalloc(b.time, cap) ? SM_E_HIP : SM_OK;
 }
 
 FrameParams make_params(const sm_ctx *s, const float *pose)
@@ -580,7 +601,7 @@ int launch_prep(sm_ctx *s, const uint8_t *rgb, const uint16_t *raw, const uint8_
         tp.st = s->d_state; tp.tb = s->d_tb; tp.tile_flags = s->d_tile_flags; tp.wave_cnt = s->d_wave_cnt; tp.prep_part = s->d_prep_part;
         s->n_prep_blocks = tp.nfb;
     }
-    if (s->ev_ok) s->ev_merged[s->ev_frames % EV_RING] = s->merge_assoc || chain != nullptr;
+    if (s->ev) s->ev_merged[s->ev_frames % EV_RING] = s->merge_assoc || chain != nullptr;
     if (s->merge_assoc || chain) {
         // the held-back association of the previous frame (if any) + this frame's tile flags + its image / chain tiles in one launch
         const bool carry = s->merge_assoc;
@@ -639,7 +660,7 @@ int launch_prep(sm_ctx *s, const uint8_t *rgb, const uint16_t *raw, const uint8_
 
 int mark(sm_ctx *s, int which, bool timed)
 {
-    if (timed && s->ev_ok) HIPCK(hipEventRecord(s->ev[which][s->ev_frames % EV_RING], s->stream));
+    if (timed && s->ev) HIPCK(hipEventRecord(s->ev[which][s->ev_frames % EV_RING], s->stream));
     return SM_OK;
 }
 
@@ -699,7 +720,7 @@ int launch_surfel_pass(sm_ctx *s, const FrameParams &fp, bool timed, bool direct
     //  every append enqueued since -- not from count_bound, which after a hundred unsynchronised frames is the capacity)
     uint64_t slots_est = s->count_bound;
     {
-        const unsigned long long v = __atomic_load_n(s->h_stat, __ATOMIC_RELAXED);
+        const unsigned long long v = __atomic_load_n(s->h_stat.get(), __ATOMIC_RELAXED);
         const uint32_t fr = (uint32_t)(v >> 32), slots = (uint32_t)v;
         // growth per frame as the device has reported it (between two reports at least 8 frames apart), at most a frame's candidates
         if (fr < s->est_fr0 || slots < s->est_slots0) { s->est_fr0 = fr; s->est_slots0 = slots; }      // (a compaction, a reset: the rate stands)
@@ -804,7 +825,7 @@ int launch_associate_direct(sm_ctx *s, const FrameParams &fp, bool timed)
     memset(&sh, 0, sizeof sh);
     AssocArgs a;
     fill_assoc_args(s, fp, a);
-    if (s->ev_ok && timed) s->ev_deferred[s->ev_frames % EV_RING] = s->defer_ok;
+    if (s->ev && timed) s->ev_deferred[s->ev_frames % EV_RING] = s->defer_ok;
     s->nf_last = s->d_nf_sub;
     if (s->defer_ok && timed) {
         // asynchronous plain stream: hold the association back; the next frame's k_prep launch carries it (k_assoc_prep),
@@ -894,7 +915,7 @@ bool decide_compact(sm_ctx *s)
     static const long wait_us = std::getenv("SM_CAPACITY_WAIT_US") ? std::atol(std::getenv("SM_CAPACITY_WAIT_US")) : 2000;
     const auto t_start = std::chrono::steady_clock::now();
     for (uint32_t spins = 0;; ++spins) {
-        const unsigned long long v = __atomic_load_n(s->h_stat, __ATOMIC_RELAXED);
+        const unsigned long long v = __atomic_load_n(s->h_stat.get(), __ATOMIC_RELAXED);
         const uint32_t fr = (uint32_t)(v >> 32), slots = (uint32_t)v;
         uint64_t bound = s->count_bound;
         const uint32_t ahead = s->frames_enq >= fr ? s->frames_enq - fr : 0u;
@@ -919,7 +940,7 @@ void note_cull(sm_ctx *s, bool compacted)
 // refresh the pinned slot statistic after the host changed the model (device idle)
 void publish_stat(sm_ctx *s)
 {
-    __atomic_store_n(s->h_stat, ((unsigned long long)s->h_state->stat_frames << 32) | (unsigned long long)s->h_state->count, __ATOMIC_RELAXED);
+    __atomic_store_n(s->h_stat.get(), ((unsigned long long)s->h_state->stat_frames << 32) | (unsigned long long)s->h_state->count, __ATOMIC_RELAXED);
     s->frames_enq = s->h_state->stat_frames;
 }
 
@@ -1126,7 +1147,7 @@ void end_frame(sm_ctx *s, bool timed)
 {
     if (s->cfg.preprocess) std::swap(s->d_lastT, s->d_filteredT);   // :244 LAST <- DEPTH_FILTERED without a copy
     memcpy(s->last_pose, s->curr_pose, 64);               // :245 (LAST aliases the metric depth when preprocess == 0)
-    if (s->ev_ok && timed) s->ev_frames++;
+    if (s->ev && timed) s->ev_frames++;
     s->tick++;
 }
 
@@ -1154,11 +1175,11 @@ int enqueue_frame(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_raw, const 
     fp.compact_now = compact_now ? 1u : 0u;
     note_cull(s, fp.compact_now != 0u);
     s->keys_are_slots = fp.compact_now == 0u;      // this frame's splat writes slot numbers iff nothing moves
-    if (s->ev_ok) s->ev_compacted[s->ev_frames % EV_RING] = fp.compact_now != 0u;
+    if (s->ev) s->ev_compacted[s->ev_frames % EV_RING] = fp.compact_now != 0u;
     // a cull that only marks the dead is ONE pass over the surfels (k_surfel_pass + k_pass_fixup: conflict test, decrement, cull,
     // splat), and the association appends the new surfels directly (no append kernel)
     const bool one_pass = !fp.compact_now;
-    if (s->ev_ok) { s->ev_one_pass[s->ev_frames % EV_RING] = one_pass; s->ev_direct[s->ev_frames % EV_RING] = one_pass; }
+    if (s->ev) { s->ev_one_pass[s->ev_frames % EV_RING] = one_pass; s->ev_direct[s->ev_frames % EV_RING] = one_pass; }
     if (one_pass) {
         if ((rc = launch_surfel_pass(s, fp, true, true))) return rc;        // :178-197
         if ((rc = launch_associate_direct(s, fp, true))) return rc;         // :212-239
@@ -1207,10 +1228,46 @@ int ensure_export(sm_ctx *s, size_t bytes)
 {
     s->rm_ovf_valid = false;                  // (every user of the scratch may overwrite the model view's overflow count)
     if (bytes <= s->export_bytes) return SM_OK;
-    if (s->d_export) (void)hipFree(s->d_export);
-    s->d_export = nullptr; s->export_bytes = 0;
-    HIPCK(hipMalloc(&s->d_export, bytes));
+    s->export_bytes = 0;
+    HIPCK(hipMalloc(s->d_export.put(), bytes));
     s->export_bytes = bytes;
+    return SM_OK;
+}
+
+// sm_create's buffers in order, up to the first failure (g_err is set only where dalloc failed)
+int alloc_ctx(sm_ctx *s)
+{
+    const size_t P = (size_t)s->P, cap = s->cap, nwords = s->alive_words, ntiles = s->dead_tiles, tb = s->tb_tiles;
+    if (hipStreamCreateWithFlags(s->stream.put(), hipStreamNonBlocking) != hipSuccess ||
+        alloc_set(s->m_bufs[0], cap) ||      // one SoA set: the compaction is in place
+        dalloc(s->d_state, 1) || dalloc(s->d_log, FRAME_LOG_LEN) || hipHostMalloc(s->h_state.put(), sizeof(DevState), hipHostMallocDefault) != hipSuccess ||
+        hipHostMalloc(s->h_stat.put(), 8, hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer((void **)&s->d_stat, s->h_stat, 0) != hipSuccess ||
+        dalloc(s->d_depthT, P) || dalloc(s->d_filteredT, P) || dalloc(s->d_lastT, P) || dalloc(s->d_rgbsT, P) || dalloc(s->d_keyT, P) ||
+        dalloc(s->d_dcT, P) || hipMemset(s->d_dcT, 0, P * 8) != hipSuccess ||
+        (s->defer_ok && (dalloc(s->d_depthT_nx, P) || dalloc(s->d_rgbsT_nx, P) || dalloc(s->d_keyT_nx, P) || dalloc(s->d_dcT_nx, P) ||
+                         hipMemset(s->d_depthT_nx, 0, P * 4) != hipSuccess || hipMemset(s->d_rgbsT_nx, 0, P * 4) != hipSuccess ||
+                         hipMemset(s->d_dcT_nx, 0, P * 8) != hipSuccess)) ||
+        dalloc(s->d_rgb, P * 3) || dalloc(s->d_sem, P) || dalloc(s->d_depth_raw, P) || dalloc(s->d_depth_f32, P) ||
+        dalloc(s->d_xs, (size_t)s->W * 2) || dalloc(s->d_ys, (size_t)s->H * 2) ||
+        dalloc(s->d_cm, nwords) || dalloc(s->d_dm, nwords) || dalloc(s->d_zm, nwords) ||
+        dalloc(s->d_alive, nwords) || hipMemset(s->d_alive, 0xFF, nwords * 8) != hipSuccess ||
+        dalloc(s->d_tile_dead, ntiles) || hipMemset(s->d_tile_dead, 0, ntiles * 4) != hipSuccess ||
+        dalloc(s->d_tile_cnt, ntiles * 3) || dalloc(s->d_tile_allow, ntiles) || dalloc(s->d_tile_keep, ntiles) || dalloc(s->d_tile_flag, ntiles) ||
+        hipMemset(s->d_tile_flag, 0, ntiles * 4) != hipSuccess ||
+        dalloc(s->d_group_tot, (ntiles / GROUP + 2) * 4) || dalloc(s->d_group_base, ntiles / GROUP + 2) ||
+        dalloc(s->d_conf_part, (size_t)MAX_GRID * 4) || dalloc(s->d_compact_part, (size_t)MAX_GRID) || dalloc(s->d_lazy_part, (size_t)MAX_GRID) ||
+        dalloc(s->d_fix_part, (size_t)MAX_GRID * 2 + 2) || dalloc(s->d_wave_cnt, ntiles) || dalloc(s->d_undo, cap + TILE) ||
+        dalloc(s->d_conf_sub, (size_t)2 * SUB_SET) || dalloc(s->d_prep_part, (size_t)256) || hipMemset(s->d_conf_sub, 0, (size_t)2 * SUB_SET * 4) != hipSuccess ||
+        dalloc(s->d_tb, tb * 8) || dalloc(s->d_tile_flags, tb) || hipMemset(s->d_tile_flags, 0, tb) != hipSuccess ||
+        dalloc(s->d_validmask, (P + 63) / 64 + 4) || dalloc(s->d_fusedmask, (P + 63) / 64 + 4) || dalloc(s->d_blk_cnt, (size_t)s->n_pix_blocks) ||
+        dalloc(s->d_blk_cand, (size_t)s->n_grp * CAND_GROUP_MAX) || dalloc(s->d_grp_cand, (size_t)s->n_grp) ||
+        dalloc(s->d_frame_sub, (size_t)6 * SUB_SET) || hipMemset(s->d_frame_sub, 0, (size_t)6 * SUB_SET * 4) != hipSuccess ||
+        (s->defer_ok && (dalloc(s->d_tile_flags_nx, tb) || hipMemset(s->d_tile_flags_nx, 0, tb) != hipSuccess ||
+                         dalloc(s->d_wave_cnt_nx, ntiles) || dalloc(s->d_prep_part_nx, (size_t)256))))
+        return SM_E_HIP;
+    s->M.s[0] = s->m_bufs[0].view();
+    *s->h_stat = 0ull;
+    s->d_nf_sub = s->d_frame_sub + 2 * SUB_SET; s->d_nf_sub_nx = s->d_frame_sub + 4 * SUB_SET;
     return SM_OK;
 }
 
@@ -1257,9 +1314,8 @@ sm_ctx *sm_create(const sm_config *c)
         return nullptr;
     }
     if (hipSetDevice(c->device) != hipSuccess) { g_err = "hipSetDevice failed"; return nullptr; }
-    sm_ctx *s = new sm_ctx();
+    std::unique_ptr<sm_ctx> s(new sm_ctx());
     s->cfg = *c;
-    if (c->device >= 0 && c->device < MAX_DEV) { std::lock_guard<std::mutex> lk(g_compact_mu); g_ctx_on_dev[c->device]++; }
     s->W = c->width; s->H = c->height; s->P = c->width * c->height;
     s->in_off_depth = ((size_t)s->P * 3 + 15) & ~(size_t)15;
     s->in_off_sem = s->in_off_depth + (((size_t)s->P * 2 + 15) & ~(size_t)15);
@@ -1269,62 +1325,23 @@ sm_ctx *sm_create(const sm_config *c)
     const size_t P = (size_t)s->P, cap = s->cap;
     const size_t nwords = (cap + 63) / 64 + TILE_WORDS, ntiles = (cap + TILE - 1) / TILE + 1;
     s->n_pix_blocks = (s->P + PIX_BLOCK - 1) / PIX_BLOCK;
-    bool ok = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) == hipSuccess;
-    ok = ok && alloc_set(s->M.s[0], cap) == SM_OK;      // one SoA set: the compaction is in place
-    ok = ok && dalloc(&s->d_state, 1) == SM_OK && dalloc(&s->d_log, FRAME_LOG_LEN) == SM_OK;
-    ok = ok && hipHostMalloc((void **)&s->h_state, sizeof(DevState), hipHostMallocDefault) == hipSuccess;
-    ok = ok && hipHostMalloc((void **)&s->h_stat, 8, hipHostMallocMapped) == hipSuccess &&
-         hipHostGetDevicePointer((void **)&s->d_stat, s->h_stat, 0) == hipSuccess;
-    if (ok) *s->h_stat = 0ull;
-    ok = ok && dalloc(&s->d_depthT, P) == SM_OK && dalloc(&s->d_filteredT, P) == SM_OK && dalloc(&s->d_lastT, P) == SM_OK;
-    ok = ok && dalloc(&s->d_rgbsT, P) == SM_OK && dalloc(&s->d_keyT, P) == SM_OK && dalloc(&s->d_dcT, P) == SM_OK &&
-         hipMemset(s->d_dcT, 0, P * 8) == hipSuccess;
+    s->alive_words = nwords; s->dead_tiles = ntiles;
+    s->tb_tiles = (uint32_t)(ntiles + P / 2 / TILE + 8);
     // deferred association (three launches per frame; with or without the depth filter chain)
     {
         const char *e = std::getenv("SM_DEFER_ASSOC");                    // "0": every frame launches its own association
         s->defer_ok = !(e && e[0] == '0');
     }
-    if (s->defer_ok)
-        ok = ok && dalloc(&s->d_depthT_nx, P) == SM_OK && dalloc(&s->d_rgbsT_nx, P) == SM_OK && dalloc(&s->d_keyT_nx, P) == SM_OK &&
-             dalloc(&s->d_dcT_nx, P) == SM_OK && hipMemset(s->d_depthT_nx, 0, P * 4) == hipSuccess &&
-             hipMemset(s->d_rgbsT_nx, 0, P * 4) == hipSuccess && hipMemset(s->d_dcT_nx, 0, P * 8) == hipSuccess;
-    ok = ok && dalloc(&s->d_rgb, P * 3) == SM_OK && dalloc(&s->d_sem, P) == SM_OK && dalloc(&s->d_depth_raw, P) == SM_OK;
-    ok = ok && dalloc(&s->d_depth_f32, P) == SM_OK;
-    ok = ok && dalloc(&s->d_xs, (size_t)s->W * 2) == SM_OK && dalloc(&s->d_ys, (size_t)s->H * 2) == SM_OK;
-    ok = ok && dalloc(&s->d_cm, nwords) == SM_OK && dalloc(&s->d_dm, nwords) == SM_OK && dalloc(&s->d_zm, nwords) == SM_OK;
-    s->alive_words = nwords; s->dead_tiles = ntiles;
-    ok = ok && dalloc(&s->d_alive, nwords) == SM_OK && hipMemset(s->d_alive, 0xFF, nwords * 8) == hipSuccess &&
-         dalloc(&s->d_tile_dead, ntiles) == SM_OK && hipMemset(s->d_tile_dead, 0, ntiles * 4) == hipSuccess;
-    ok = ok && dalloc(&s->d_tile_cnt, ntiles * 3) == SM_OK && dalloc(&s->d_tile_allow, ntiles) == SM_OK &&
-         dalloc(&s->d_tile_keep, ntiles) == SM_OK && dalloc(&s->d_tile_flag, ntiles) == SM_OK &&
-         hipMemset(s->d_tile_flag, 0, ntiles * 4) == hipSuccess &&
-         dalloc(&s->d_group_tot, (ntiles / GROUP + 2) * 4) == SM_OK && dalloc(&s->d_group_base, ntiles / GROUP + 2) == SM_OK;
-    s->tb_tiles = (uint32_t)(ntiles + P / 2 / TILE + 8);
-    ok = ok && dalloc(&s->d_conf_part, (size_t)MAX_GRID * 4) == SM_OK && dalloc(&s->d_compact_part, (size_t)MAX_GRID) == SM_OK &&
-         dalloc(&s->d_lazy_part, (size_t)MAX_GRID) == SM_OK && dalloc(&s->d_fix_part, (size_t)MAX_GRID * 2 + 2) == SM_OK &&
-         dalloc(&s->d_wave_cnt, ntiles) == SM_OK && dalloc(&s->d_undo, cap + TILE) == SM_OK && dalloc(&s->d_conf_sub, (size_t)2 * SUB_SET) == SM_OK &&
-         dalloc(&s->d_prep_part, (size_t)256) == SM_OK &&
-         hipMemset(s->d_conf_sub, 0, (size_t)2 * SUB_SET * 4) == hipSuccess;
-    ok = ok && dalloc(&s->d_tb, (size_t)s->tb_tiles * 8) == SM_OK && dalloc(&s->d_tile_flags, (size_t)s->tb_tiles) == SM_OK &&
-         hipMemset(s->d_tile_flags, 0, s->tb_tiles) == hipSuccess;
-    ok = ok && dalloc(&s->d_validmask, (P + 63) / 64 + 4) == SM_OK && dalloc(&s->d_fusedmask, (P + 63) / 64 + 4) == SM_OK;
-    ok = ok && dalloc(&s->d_blk_cnt, (size_t)s->n_pix_blocks) == SM_OK;
     // candidate groups: small groups make the counting workgroups short (k_pass_fixup 3.5 -> 2.5 us at 1242x375 with 4
     // instead of 16 blocks per group) but every association wave sums all groups before its own: keep ~250-500 groups
     s->cand_group = s->n_pix_blocks <= 2048 ? 4u : s->n_pix_blocks <= 4096 ? 8u : 16u;
     if (const char *e = std::getenv("SM_CAND_GROUP")) { const int v = std::atoi(e); if (v == 4 || v == 8 || v == 16) s->cand_group = (uint32_t)v; }
     s->n_grp = (uint32_t)((s->n_pix_blocks + s->cand_group - 1) / s->cand_group);
-    ok = ok && dalloc(&s->d_blk_cand, (size_t)s->n_grp * CAND_GROUP_MAX) == SM_OK && dalloc(&s->d_grp_cand, (size_t)s->n_grp) == SM_OK &&
-         dalloc(&s->d_frame_sub, (size_t)6 * SUB_SET) == SM_OK && hipMemset(s->d_frame_sub, 0, (size_t)6 * SUB_SET * 4) == hipSuccess;
-    s->d_nf_sub = s->d_frame_sub + 2 * SUB_SET; s->d_nf_sub_nx = s->d_frame_sub + 4 * SUB_SET;
-    if (s->defer_ok)
-        ok = ok && dalloc(&s->d_tile_flags_nx, (size_t)s->tb_tiles) == SM_OK && hipMemset(s->d_tile_flags_nx, 0, s->tb_tiles) == hipSuccess &&
-             dalloc(&s->d_wave_cnt_nx, ntiles) == SM_OK && dalloc(&s->d_prep_part_nx, (size_t)256) == SM_OK;
     {
         const char *e = std::getenv("SM_TWO_LAUNCH");                     // "0": the fixup step keeps its own launch (three launches per frame)
         s->two_launch = s->defer_ok && !(e && e[0] == '0');
     }
-    if (!ok) { if (g_err.empty()) g_err = "sm_create: allocation failed"; sm_destroy(s); return nullptr; }
+    if (alloc_ctx(s.get())) { if (g_err.empty()) g_err = "sm_create: allocation failed"; return nullptr; }
 
     // pixel-centre coordinates exactly as data.vert sees them:
     // texcoord = float((i+0.5)/(double)(float)W) (src/GlobalModel.cpp:71-72), x = texcoord*cols (data.vert:62-63)
@@ -1352,7 +1369,6 @@ sm_ctx *sm_create(const sm_config *c)
     }
     if (!clamp_ok) {   // the kernels index neighbours as i+-1 / j+-1; refuse sizes where fp32 texcoords disagree
         g_err = "sm_create: texel addressing for this image size is not the simple clamp form";
-        sm_destroy(s);
         return nullptr;
     }
     for (int i = 0; i < s->W; ++i) odd += (uint32_t)((s->H + ((i & 1) ? 1 : 0)) / 2);
@@ -1367,27 +1383,27 @@ sm_ctx *sm_create(const sm_config *c)
                 wtab[(iy + 6) * 13 + (ix + 6)] = exp_spec(-((float)(ix * ix + iy * iy) * sigPix));
     }
     memset(s->h_state, 0, sizeof(DevState));
-    ok = hipMemcpy(s->d_xs, xs.data(), xs.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
+    bool ok = hipMemcpy(s->d_xs, xs.data(), xs.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
          hipMemcpy(s->d_ys, ys.data(), ys.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
          hipMemcpy(s->d_state, s->h_state, sizeof(DevState), hipMemcpyHostToDevice) == hipSuccess &&
          hipMemset(s->d_depthT, 0, P * 4) == hipSuccess && hipMemset(s->d_filteredT, 0, P * 4) == hipSuccess &&
          hipMemset(s->d_lastT, 0, P * 4) == hipSuccess && hipMemset(s->d_rgbsT, 0, P * 4) == hipSuccess &&
          hipMemset(s->d_rgb, 0, P * 3) == hipSuccess && hipMemset(s->d_sem, 0, P) == hipSuccess &&
-         hipMemset(s->d_depth_raw, 0, P * 2) == hipSuccess && hipMemset(s->d_depth_f32, 0, P * 4) == hipSuccess;
-    ok = ok && hipDeviceSynchronize() == hipSuccess;
+         hipMemset(s->d_depth_raw, 0, P * 2) == hipSuccess && hipMemset(s->d_depth_f32, 0, P * 4) == hipSuccess &&
+         hipDeviceSynchronize() == hipSuccess;
     if (ok) {
         hipLaunchKernelGGL(k_tile_bounds_reset, dim3((s->tb_tiles + 255) / 256), dim3(256), 0, s->stream, s->d_tb, 0u, s->tb_tiles);
         hipLaunchKernelGGL(k_fill_keys, dim3((s->P + 255) / 256), dim3(256), 0, s->stream, s->d_keyT, s->P);
         ok = hipStreamSynchronize(s->stream) == hipSuccess;
     }
-    if (!ok) { g_err = "sm_create: device initialisation failed"; sm_destroy(s); return nullptr; }
+    if (!ok) { g_err = "sm_create: device initialisation failed"; return nullptr; }
     {
         // the in-place compaction needs every workgroup of k_compact resident at once
         int cus = 0, per_cu = 0;
         (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
-        if (std::getenv("SM_CHECK_ALIVE") && (hipMalloc((void **)&s->d_chk, 32) != hipSuccess || hipMemset(s->d_chk, 0, 32) != hipSuccess)) s->d_chk = nullptr;
-        if (std::getenv("SM_PASS_TRACE") && hipMalloc((void **)&s->d_pass_trace, (size_t)MAX_GRID * 64) != hipSuccess) s->d_pass_trace = nullptr;
-        if (std::getenv("SM_PASS_TRACE") && hipMalloc((void **)&s->d_ap_trace, (size_t)65536 * 16) != hipSuccess) s->d_ap_trace = nullptr;
+        if (std::getenv("SM_CHECK_ALIVE") && (hipMalloc(s->d_chk.put(), 32) != hipSuccess || hipMemset(s->d_chk, 0, 32) != hipSuccess)) s->d_chk = {};
+        if (std::getenv("SM_PASS_TRACE")) (void)hipMalloc(s->d_pass_trace.put(), (size_t)MAX_GRID * 64);
+        if (std::getenv("SM_PASS_TRACE")) (void)hipMalloc(s->d_ap_trace.put(), (size_t)65536 * 16);
         {
             // k_surfel_pass: with more workgroups than the chip holds at once the surplus starts when the first ones are done --
             // on a model where every tile has work (20 M scattered surfels: ~10 tiles per workgroup) that is a second pass at an
@@ -1409,31 +1425,25 @@ sm_ctx *sm_create(const sm_config *c)
             s->compact_grid = std::max(1, cus * want);
         }
     }
-    if (c->enable_timing) {
-        s->ev_ok = true;
-        for (auto &row : s->ev)
-            for (auto &e : row)
-                if (hipEventCreate(&e) != hipSuccess) s->ev_ok = false;
+    if (c->enable_timing) {                                       // all or nothing: without the whole ring the context runs untimed
+        std::unique_ptr<Event[][EV_RING]> ev(new Event[N_EV][EV_RING]);
+        bool made = true;
+        for (int k = 0; k < N_EV && made; ++k)
+            for (int i = 0; i < EV_RING && made; ++i) made = hipEventCreate(ev[k][i].put()) == hipSuccess;
+        if (made) s->ev = std::move(ev);
     }
-    return s;
+    if (c->device >= 0 && c->device < MAX_DEV) { std::lock_guard<std::mutex> lk(g_compact_mu); g_ctx_on_dev[c->device]++; }
+    return s.release();
 }
 
 void sm_destroy(sm_ctx *s)
 {
     if (!s) return;
     if (s->cfg.device >= 0 && s->cfg.device < MAX_DEV) { std::lock_guard<std::mutex> lk(g_compact_mu); g_ctx_on_dev[s->cfg.device]--; }
-    (void)hipSetDevice(s->cfg.device);
+    (void)hipSetDevice(s->cfg.device);         // every owner releases on the context's device
     if (s->stream) (void)hipStreamSynchronize(s->stream);
     if (s->ss_comm) (void)sm_shard_rccl_finalize(s);         // a communicator the caller did not finalize
     if (s->stream_in) (void)hipStreamSynchronize(s->stream_in);
-    for (auto &sl : s->in) {
-        (void)hipFree(sl.rgb);          // (one block: depth and class follow the colour image)
-        if (sl.h_stage) (void)hipHostFree(sl.h_stage);
-        if (sl.ev_in) (void)hipEventDestroy(sl.ev_in);
-        if (sl.ev_free) (void)hipEventDestroy(sl.ev_free);
-    }
-    if (s->stream_in) (void)hipStreamDestroy(s->stream_in);
-    for (void *hp : s->host_allocs) (void)hipHostFree(hp);
     if (s->d_pass_trace) {
         // SM_PASS_TRACE=<prefix>: the last k_surfel_pass launch's per-workgroup record (wall_clock64 at entry / first tile /
         // after it / exit, that tile, its compacted entries, XCC | HW_ID, tiles) -> <prefix>.<n>.bin (tools/pass_trace.py)
@@ -1444,7 +1454,6 @@ void sm_destroy(sm_ctx *s)
             snprintf(path, sizeof path, "%s.%d.bin", std::getenv("SM_PASS_TRACE") ? std::getenv("SM_PASS_TRACE") : "pass_trace", n_dump++);
             if (FILE *f = fopen(path, "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
         }
-        (void)hipFree(s->d_pass_trace);
     }
     if (s->d_ap_trace) {
         const int n = s->ap_trace_n[0] + s->ap_trace_n[1] + s->ap_trace_n[2] + s->ap_trace_n[3];
@@ -1455,33 +1464,7 @@ void sm_destroy(sm_ctx *s)
             snprintf(path, sizeof path, "%s.assoc_prep.bin", std::getenv("SM_PASS_TRACE") ? std::getenv("SM_PASS_TRACE") : "pass_trace");
             if (FILE *f = fopen(path, "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
         }
-        (void)hipFree(s->d_ap_trace);
     }
-    (void)hipFree(s->d_depthT_nx); (void)hipFree(s->d_rgbsT_nx); (void)hipFree(s->d_keyT_nx); (void)hipFree(s->d_dcT_nx);
-    free_set(s->M.s[0]); free_set(s->M.s[1]);
-    (void)hipFree(s->d_state); (void)hipFree(s->d_log);
-    if (s->h_state) (void)hipHostFree(s->h_state);
-    if (s->h_stat) (void)hipHostFree(s->h_stat);
-    (void)hipFree(s->d_depthT); (void)hipFree(s->d_filteredT); (void)hipFree(s->d_lastT);
-    (void)hipFree(s->d_rgbsT); (void)hipFree(s->d_keyT); (void)hipFree(s->d_dcT);
-    (void)hipFree(s->d_rgb); (void)hipFree(s->d_sem); (void)hipFree(s->d_depth_raw); (void)hipFree(s->d_depth_f32);
-    (void)hipFree(s->d_xs); (void)hipFree(s->d_ys);
-    (void)hipFree(s->d_cm); (void)hipFree(s->d_dm); (void)hipFree(s->d_zm); (void)hipFree(s->d_alive); (void)hipFree(s->d_tile_dead);
-    (void)hipFree(s->d_tile_flags_nx); (void)hipFree(s->d_wave_cnt_nx); (void)hipFree(s->d_prep_part_nx);
-    (void)hipFree(s->d_tile_cnt); (void)hipFree(s->d_tile_allow); (void)hipFree(s->d_tile_keep); (void)hipFree(s->d_tile_flag); (void)hipFree(s->d_group_tot); (void)hipFree(s->d_group_base); (void)hipFree(s->d_tb); (void)hipFree(s->d_tile_flags); (void)hipFree(s->d_conf_part); (void)hipFree(s->d_compact_part); (void)hipFree(s->d_lazy_part); (void)hipFree(s->d_conf_sub); (void)hipFree(s->d_fix_part); (void)hipFree(s->d_blk_cand); (void)hipFree(s->d_grp_cand); (void)hipFree(s->d_frame_sub); (void)hipFree(s->d_wave_cnt); (void)hipFree(s->d_undo); (void)hipFree(s->d_prep_part);
-    (void)hipFree(s->d_validmask); (void)hipFree(s->d_fusedmask); (void)hipFree(s->d_blk_cnt);
-    (void)hipFree(s->d_chk); (void)hipFree(s->d_galive); (void)hipFree(s->d_new_alive); (void)hipFree(s->d_gmask); (void)hipFree(s->d_ss_info); (void)hipFree(s->d_capx);
-    if (s->d_export) (void)hipFree(s->d_export);
-    for (hipEvent_t e : s->rm_ev) if (e) (void)hipEventDestroy(e);
-    (void)hipFree(s->d_trk_depth); (void)hipFree(s->d_trk_v); (void)hipFree(s->d_trk_n); (void)hipFree(s->d_trk_key);
-    (void)hipFree(s->d_trk_pred); (void)hipFree(s->d_trk_part); (void)hipFree(s->d_trk);
-    if (s->h_trk) (void)hipHostFree(s->h_trk);
-    for (hipEvent_t e : s->trk_ev) if (e) (void)hipEventDestroy(e);
-    for (void *p : s->user_allocs) (void)hipFree(p);
-    if (s->ev_ok)
-        for (auto &row : s->ev)
-            for (auto &e : row) (void)hipEventDestroy(e);
-    if (s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
 }
 
@@ -1527,11 +1510,10 @@ void *sm_host_alloc(sm_ctx *s, size_t bytes)
 {
     if (!s || !bytes) return nullptr;
     if (hipSetDevice(s->cfg.device) != hipSuccess) return nullptr;
-    void *p = nullptr;
-    if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) { g_err = "sm_host_alloc: hipHostMalloc failed"; return nullptr; }
-    s->pinned.emplace_back(static_cast<const unsigned char *>(p), bytes);
-    s->host_allocs.push_back(p);
-    return p;
+    Host<unsigned char> p;
+    if (hipHostMalloc(p.put(), bytes, hipHostMallocDefault) != hipSuccess) { g_err = "sm_host_alloc: hipHostMalloc failed"; return nullptr; }
+    s->pinned.emplace_back(std::move(p), bytes);
+    return s->pinned.back().first;
 }
 
 int sm_host_alloc_frame(sm_ctx *s, uint8_t **rgb, uint16_t **depth_mm, uint8_t **semantic)
@@ -1546,13 +1528,12 @@ int sm_host_alloc_frame(sm_ctx *s, uint8_t **rgb, uint16_t **depth_mm, uint8_t *
 int sm_host_free(sm_ctx *s, void *p)
 {
     if (!s || !p) return SM_E_ARG;
-    auto it = std::find(s->host_allocs.begin(), s->host_allocs.end(), p);
-    if (it == s->host_allocs.end()) { g_err = "sm_host_free: not a buffer of sm_host_alloc"; return SM_E_ARG; }
+    auto it = std::find_if(s->pinned.begin(), s->pinned.end(), [p](const auto &b) { return b.first == p; });
+    if (it == s->pinned.end()) { g_err = "sm_host_free: not a buffer of sm_host_alloc"; return SM_E_ARG; }
     HIPCK(hipSetDevice(s->cfg.device));
     if (s->stream_in) HIPCK(hipStreamSynchronize(s->stream_in));
-    s->host_allocs.erase(it);
-    for (size_t i = 0; i < s->pinned.size(); ++i)
-        if (s->pinned[i].first == p) { s->pinned.erase(s->pinned.begin() + (long)i); break; }
+    (void)it->first.release();
+    s->pinned.erase(it);
     HIPCK(hipHostFree(p));
     return SM_OK;
 }
@@ -1562,15 +1543,18 @@ int sm_process_frame_async(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_
     if (!s || !rgb || !pose16) { g_err = "sm_process_frame_async: null argument (rgb and pose are required)"; return SM_E_ARG; }
     HIPCK(hipSetDevice(s->cfg.device));
     const size_t P = (size_t)s->P;
-    if (!s->stream_in) {
-        HIPCK(hipStreamCreateWithFlags(&s->stream_in, hipStreamNonBlocking));
-        for (auto &sl : s->in) {
-            unsigned char *blk = nullptr;
-            HIPCK(hipMalloc((void **)&blk, s->in_bytes));
-            sl.rgb = blk; sl.depth = reinterpret_cast<uint16_t *>(blk + s->in_off_depth); sl.sem = blk + s->in_off_sem;
-            HIPCK(hipEventCreateWithFlags(&sl.ev_in, hipEventDisableTiming));
-            HIPCK(hipEventCreateWithFlags(&sl.ev_free, hipEventDisableTiming));
+    if (!s->stream_in) {                  // the copy stream and the ring, built whole before the context takes them
+        Stream st;
+        sm_ctx::InSlot ring[sm_ctx::IN_RING];
+        HIPCK(hipStreamCreateWithFlags(st.put(), hipStreamNonBlocking));
+        for (auto &sl : ring) {
+            HIPCK(hipMalloc(sl.rgb.put(), s->in_bytes));
+            sl.depth = reinterpret_cast<uint16_t *>(sl.rgb + s->in_off_depth); sl.sem = sl.rgb + s->in_off_sem;
+            HIPCK(hipEventCreateWithFlags(sl.ev_in.put(), hipEventDisableTiming));
+            HIPCK(hipEventCreateWithFlags(sl.ev_free.put(), hipEventDisableTiming));
         }
+        std::move(std::begin(ring), std::end(ring), s->in);
+        s->stream_in = std::move(st);
     }
     const int slot = (int)(s->in_next++ % sm_ctx::IN_RING);
     sm_ctx::InSlot &sl = s->in[slot];
@@ -1592,7 +1576,7 @@ int sm_process_frame_async(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_
     } else if (!is_pinned(rgb, P * 3) || (depth_mm && !is_pinned(depth_mm, P * 2)) || (semantic && !is_pinned(semantic, P))) {
         // pageable caller memory: through this set's pinned staging in the frame-block layout (host memcpys; the previous copy out
         // of it -- three frames ago -- must have completed), then ONE copy of what was given
-        if (!sl.h_stage) HIPCK(hipHostMalloc((void **)&sl.h_stage, s->in_bytes, hipHostMallocDefault));
+        if (!sl.h_stage) HIPCK(hipHostMalloc(sl.h_stage.put(), s->in_bytes, hipHostMallocDefault));
         if (sl.used) HIPCK(hipEventSynchronize(sl.ev_in));
         memcpy(sl.h_stage, rgb, P * 3);
         if (depth_mm) memcpy(sl.h_stage + s->in_off_depth, depth_mm, P * 2);
@@ -1749,7 +1733,7 @@ int sm_download_model_aos(sm_ctx *s, float *dst12, uint32_t cap, uint32_t *n)
     if ((rc = ensure_export(s, (size_t)std::min(cnt, CH) * 48))) return rc;
     for (uint32_t first = 0; first < cnt; first += CH) {
         const uint32_t m = std::min(CH, cnt - first);
-        hipLaunchKernelGGL(k_export_aos, dim3((m + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, (float *)s->d_export, first, m);
+        hipLaunchKernelGGL(k_export_aos, dim3((m + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, (float *)s->d_export.get(), first, m);
         HIPCK(hipGetLastError());
         HIPCK(hipMemcpyAsync(dst12 + (size_t)first * 12, s->d_export, (size_t)m * 48, hipMemcpyDeviceToHost, s->stream));
         HIPCK(hipStreamSynchronize(s->stream));
@@ -1770,7 +1754,7 @@ int sm_upload_model_aos(sm_ctx *s, const float *src12, uint32_t n)
     for (uint32_t first = 0; first < n; first += CH) {
         const uint32_t m = std::min(CH, n - first);
         HIPCK(hipMemcpyAsync(s->d_export, src12 + (size_t)first * 12, (size_t)m * 48, hipMemcpyHostToDevice, s->stream));
-        hipLaunchKernelGGL(k_import_aos, dim3((m + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, (const float *)s->d_export, first, m);
+        hipLaunchKernelGGL(k_import_aos, dim3((m + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, (const float *)s->d_export.get(), first, m);
         HIPCK(hipGetLastError());
         HIPCK(hipStreamSynchronize(s->stream));
     }
@@ -1794,8 +1778,8 @@ int sm_save_map(sm_ctx *s, const char *path, int32_t start_id, int32_t end_id)
     FILE *f = fopen(path, "wb");
     if (!f) { g_err = std::string(path) + " is not open!"; return SM_E_ARG; }
     // u32 count | i32 startId | i32 endId | count*12 f32   (src/GlobalModel.cpp:927-932)
-    bool ok = fwrite(&n, 4, 1, f) == 1 && fwrite(&start_id, 4, 1, f) == 1 && fwrite(&end_id, 4, 1, f) == 1;
-    ok = ok && (n == 0 || fwrite(buf.data(), 48, n, f) == n);
+    bool ok = fwrite(&n, 4, 1, f) == 1 && fwrite(&start_id, 4, 1, f) == 1 && fwrite(&end_id, 4, 1, f) == 1 &&
+              (n == 0 || fwrite(buf.data(), 48, n, f) == n);
     ok = (fclose(f) == 0) && ok;
     if (!ok) { g_err = std::string(path) + " saved err!!"; return SM_E_ARG; }
     return SM_OK;
@@ -1826,7 +1810,7 @@ int sm_download_index_map(sm_ctx *s, int32_t *id, float *vert_conf4, float *colo
     int rc = ensure_compact(s);
     if (rc) return rc;
     if ((rc = ensure_export(s, P * 52))) return rc;
-    char *base = (char *)s->d_export;
+    char *base = (char *)s->d_export.get();
     int32_t *d_id = (int32_t *)(base + P * 48);
     float4 *d_vc = (float4 *)base, *d_ct = (float4 *)(base + P * 16), *d_nr = (float4 *)(base + P * 32);
     FrameParams fp = make_params(s, s->curr_pose);
@@ -1849,8 +1833,8 @@ int sm_download_raw_cloud(sm_ctx *s, float *dst12, uint32_t cap, uint32_t *n)
     const size_t P = (size_t)s->P;
     int rc = ensure_export(s, P * 49);
     if (rc) return rc;
-    float4 *d_rec = (float4 *)s->d_export;
-    uint8_t *d_flag = (uint8_t *)s->d_export + P * 48;
+    float4 *d_rec = (float4 *)s->d_export.get();
+    uint8_t *d_flag = (uint8_t *)s->d_export.get() + P * 48;
     FrameParams fp = make_params(s, s->curr_pose);
     fp.init_mode = 1;
     fp.time = s->raw_tick;
@@ -1885,7 +1869,7 @@ int sm_download_depth(sm_ctx *s, int which, float *dst)
     if (!src) return SM_E_ARG;
     int rc = ensure_export(s, (size_t)s->P * 4);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_untranspose_f32, dim3((s->P + 255) / 256), dim3(256), 0, s->stream, src, (float *)s->d_export, s->W, s->H);
+    hipLaunchKernelGGL(k_untranspose_f32, dim3((s->P + 255) / 256), dim3(256), 0, s->stream, src, (float *)s->d_export.get(), s->W, s->H);
     HIPCK(hipGetLastError());
     HIPCK(hipMemcpyAsync(dst, s->d_export, (size_t)s->P * 4, hipMemcpyDeviceToHost, s->stream));
     HIPCK(hipStreamSynchronize(s->stream));
@@ -1903,8 +1887,8 @@ int sm_render_image(sm_ctx *s, const float *view16, int w, int h, float fx, floa
     if ((rc = pull_state(s))) return rc;
     const size_t npix = (size_t)w * h;
     if ((rc = ensure_export(s, npix * 12))) return rc;            // [keys u64 | bgr | sem]
-    uint64_t *d_key = (uint64_t *)s->d_export;
-    uint8_t *d_bgr = (uint8_t *)s->d_export + npix * 8, *d_sem = d_bgr + npix * 3;
+    uint64_t *d_key = (uint64_t *)s->d_export.get();
+    uint8_t *d_bgr = (uint8_t *)s->d_export.get() + npix * 8, *d_sem = d_bgr + npix * 3;
     RenderParams rp;
     invert4(view16, rp.t_inv);
     rp.fx = fx; rp.fy = fy; rp.cx = cx; rp.cy = cy; rp.cols = (float)w; rp.rows = (float)h; rp.w = w; rp.h = h;
@@ -1951,7 +1935,7 @@ int render_model_enqueue(sm_ctx *s, const sm_model_view *v, const char *fn, uint
     const size_t npix = (size_t)v->width * v->height;
     const size_t ovf_off = npix * 8, list_off = ovf_off + 256, extra_off = list_off + (((size_t)cnt * 4 + 255) & ~(size_t)255);
     if ((rc = ensure_export(s, extra_off + (stage ? npix * 12 : 0)))) return rc;
-    uint8_t *base = (uint8_t *)s->d_export;
+    uint8_t *base = (uint8_t *)s->d_export.get();
     uint64_t *d_key = (uint64_t *)base;
     uint32_t *d_ovf_n = (uint32_t *)(base + ovf_off), *d_ovf = (uint32_t *)(base + list_off);
     if (stage) {
@@ -1977,8 +1961,11 @@ int render_model_enqueue(sm_ctx *s, const sm_model_view *v, const char *fn, uint
                ((uint32_t)v->clear_rgba[3] << 24);
     const char *te = std::getenv("SM_RENDER_MODEL_TIMING");
     s->rm_timed = te && te[0] == '1';
-    if (s->rm_timed && !s->rm_ev[0])
-        for (hipEvent_t &e : s->rm_ev) HIPCK(hipEventCreate(&e));
+    if (s->rm_timed && !s->rm_ev[0]) {
+        Event ev[4];
+        for (Event &e : ev) HIPCK(hipEventCreate(e.put()));
+        std::move(std::begin(ev), std::end(ev), s->rm_ev);
+    }
     const unsigned pblocks = (unsigned)((npix + 255) / 256);
     hipLaunchKernelGGL(k_fill_keys, dim3(pblocks), dim3(256), 0, s->stream, d_key, (int)npix);
     HIPCK(hipMemsetAsync(d_ovf_n, 0, 4, s->stream));
@@ -2029,7 +2016,7 @@ int sm_debug_render_model_stats(sm_ctx *s, uint32_t *overflow, float *ms3)
     HIPCK(hipSetDevice(s->cfg.device));
     HIPCK(hipStreamSynchronize(s->stream));
     if (!s->rm_ovf_valid) { g_err = "sm_debug_render_model_stats: no model view since the last reuse of the export scratch"; return SM_E_ARG; }
-    if (overflow) HIPCK(hipMemcpy(overflow, (uint8_t *)s->d_export + s->rm_ovf_off, 4, hipMemcpyDeviceToHost));
+    if (overflow) HIPCK(hipMemcpy(overflow, (uint8_t *)s->d_export.get() + s->rm_ovf_off, 4, hipMemcpyDeviceToHost));
     if (ms3)
         for (int i = 0; i < 3; ++i) {
             ms3[i] = -1.0f;
@@ -2100,13 +2087,17 @@ int track_alloc(sm_ctx *s)
 {
     if (s->d_trk) return SM_OK;
     const size_t P = (size_t)s->P;
+    Dev<uint16_t> depth; Dev<float4> v, n; Dev<uint64_t> key; Dev<int32_t> pred; Dev<double> part; Dev<TrackState> d;
+    Host<TrackState> h;
     int rc;
-    if ((rc = dalloc(&s->d_trk_depth, P)) || (rc = dalloc(&s->d_trk_v, P)) || (rc = dalloc(&s->d_trk_n, P)) ||
-        (rc = dalloc(&s->d_trk_key, P)) || (rc = dalloc(&s->d_trk_pred, P)) ||
-        (rc = dalloc(&s->d_trk_part, (size_t)TRACK_NSYS * TRACK_MAX_PARTS)))
+    if ((rc = dalloc(depth, P)) || (rc = dalloc(v, P)) || (rc = dalloc(n, P)) || (rc = dalloc(key, P)) || (rc = dalloc(pred, P)) ||
+        (rc = dalloc(part, (size_t)TRACK_NSYS * TRACK_MAX_PARTS)) || (rc = dalloc(d, 1)))
         return rc;
-    HIPCK(hipHostMalloc((void **)&s->h_trk, sizeof(TrackState)));
-    return dalloc(&s->d_trk, 1);
+    HIPCK(hipHostMalloc(h.put(), sizeof(TrackState)));
+    s->d_trk_depth = std::move(depth); s->d_trk_v = std::move(v); s->d_trk_n = std::move(n); s->d_trk_key = std::move(key);
+    s->d_trk_pred = std::move(pred); s->d_trk_part = std::move(part); s->h_trk = std::move(h);
+    s->d_trk = std::move(d);              // last: it marks the set complete
+    return SM_OK;
 }
 
 int track_check(sm_ctx *s, const char *fn)
@@ -2148,9 +2139,9 @@ int track_event(sm_ctx *s, size_t i)
 {
     if (!s->trk_timed) return SM_OK;
     while (s->trk_ev.size() <= i) {
-        hipEvent_t e;
-        HIPCK(hipEventCreate(&e));
-        s->trk_ev.push_back(e);
+        Event e;
+        HIPCK(hipEventCreate(e.put()));
+        s->trk_ev.push_back(std::move(e));
     }
     HIPCK(hipEventRecord(s->trk_ev[i], s->stream));
     return SM_OK;
@@ -2414,7 +2405,7 @@ int sm_stage_timings(sm_ctx *s, sm_timings *out)
 {
     if (!s || !out) return SM_E_ARG;
     memset(out, 0, sizeof *out);
-    if (!s->ev_ok) { g_err = "sm_stage_timings: create the context with enable_timing=1"; return SM_E_UNSUPPORTED; }
+    if (!s->ev) { g_err = "sm_stage_timings: create the context with enable_timing=1"; return SM_E_UNSUPPORTED; }
     HIPCK(hipSetDevice(s->cfg.device));
     HIPCK(hipStreamSynchronize(s->stream));
     uint64_t first = s->ev_read;
@@ -2433,10 +2424,10 @@ int sm_stage_timings(sm_ctx *s, sm_timings *out)
             ok = hipEventElapsedTime(&ms, s->ev[k][slot], s->ev[k + 1][slot]) == hipSuccess;
             loc[k] = ms;
         }
-        ok = ok && hipEventElapsedTime(&ms, s->ev[0][slot], s->ev[7][slot]) == hipSuccess;
         float o = 0;
-        ok = ok && hipEventElapsedTime(&o, s->ev[8][slot], s->ev[0][slot]) == hipSuccess;
-        if (!ok) continue;
+        if (!ok || hipEventElapsedTime(&ms, s->ev[0][slot], s->ev[7][slot]) != hipSuccess ||
+            hipEventElapsedTime(&o, s->ev[8][slot], s->ev[0][slot]) != hipSuccess)
+            continue;
         for (int k = 0; k < 7; ++k) seg[k] += loc[k];
         cull[s->ev_compacted[slot] ? 1 : 0] += loc[3];
         ncls[s->ev_compacted[slot] ? 1 : 0]++;
@@ -2504,10 +2495,10 @@ void *sm_device_alloc(sm_ctx *s, size_t bytes)
 {
     if (!s) return nullptr;
     if (hipSetDevice(s->cfg.device) != hipSuccess) return nullptr;
-    void *p = nullptr;
-    if (hipMalloc(&p, std::max<size_t>(bytes, 1)) != hipSuccess) { g_err = "sm_device_alloc: hipMalloc failed"; return nullptr; }
-    s->user_allocs.push_back(p);
-    return p;
+    Dev<void> p;
+    if (hipMalloc(p.put(), std::max<size_t>(bytes, 1)) != hipSuccess) { g_err = "sm_device_alloc: hipMalloc failed"; return nullptr; }
+    s->user_allocs.push_back(std::move(p));
+    return s->user_allocs.back();
 }
 
 int sm_device_free(sm_ctx *s, void *p)
@@ -2515,6 +2506,7 @@ int sm_device_free(sm_ctx *s, void *p)
     if (!s || !p) return SM_E_ARG;
     auto it = std::find(s->user_allocs.begin(), s->user_allocs.end(), p);
     if (it == s->user_allocs.end()) return SM_E_ARG;
+    (void)it->release();
     s->user_allocs.erase(it);
     HIPCK(hipSetDevice(s->cfg.device));
     HIPCK(hipStreamSynchronize(s->stream));
@@ -2543,7 +2535,7 @@ int sm_export_model_device(sm_ctx *s, void **d_aos, uint32_t *n)
     const uint32_t cnt = s->h_state->count;
     if ((rc = ensure_export(s, (size_t)std::max(cnt, 1u) * 48))) return rc;
     if (cnt) {
-        hipLaunchKernelGGL(k_export_aos, dim3((cnt + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, (float *)s->d_export, 0u, cnt);
+        hipLaunchKernelGGL(k_export_aos, dim3((cnt + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, (float *)s->d_export.get(), 0u, cnt);
         HIPCK(hipGetLastError());
         HIPCK(hipStreamSynchronize(s->stream));
     }
@@ -2734,12 +2726,18 @@ int sm_shard_stream_configure(sm_ctx *s, int rank, int world)
         g_err = "sm_shard_stream_configure: the context must be new (no frame, no model)";
         return SM_E_ARG;
     }
-    if ((rc = alloc_set(s->M.s[1], s->cap))) return rc;                        // staging set of the sharded compaction
-    if ((rc = dalloc(&s->d_galive, s->alive_words)) || (rc = dalloc(&s->d_new_alive, s->alive_words)) ||
-        (rc = dalloc(&s->d_gmask, (size_t)(s->P + 63) / 64 + 4)) || (rc = dalloc(&s->d_ss_info, 4)) ||
-        (rc = dalloc(&s->d_capx, (size_t)1 + (size_t)(2 + TILE_WORDS) * s->dead_tiles)))
+    SetBufs set1;                              // staging set of the sharded compaction
+    Dev<uint64_t> galive, new_alive, gmask, capx;
+    Dev<uint32_t> info;
+    if ((rc = alloc_set(set1, s->cap)) || (rc = dalloc(galive, s->alive_words)) || (rc = dalloc(new_alive, s->alive_words)) ||
+        (rc = dalloc(gmask, (size_t)(s->P + 63) / 64 + 4)) || (rc = dalloc(info, 4)) ||
+        (rc = dalloc(capx, (size_t)1 + (size_t)(2 + TILE_WORDS) * s->dead_tiles)))
         return rc;
-    HIPCK(hipMemset(s->d_ss_info, 0, 16));
+    HIPCK(hipMemset(info, 0, 16));
+    s->M.s[1] = set1.view();
+    s->m_bufs[1] = std::move(set1);
+    s->d_galive = std::move(galive); s->d_new_alive = std::move(new_alive); s->d_gmask = std::move(gmask);
+    s->d_ss_info = std::move(info); s->d_capx = std::move(capx);
     s->ss_on = true; s->ss_rank = rank; s->ss_world = world; s->ss_frames = 0;
     s->defer_ok = false;                       // the association of a sharded frame sits between two collectives
     return SM_OK;
@@ -2845,7 +2843,7 @@ int sm_shard_frame_device(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_dep
     fp.shard_slots = 1;
     note_cull(s, false);
     s->keys_are_slots = true;
-    if (s->ev_ok) { s->ev_compacted[s->ev_frames % EV_RING] = false; s->ev_one_pass[s->ev_frames % EV_RING] = true; s->ev_direct[s->ev_frames % EV_RING] = true; }
+    if (s->ev) { s->ev_compacted[s->ev_frames % EV_RING] = false; s->ev_one_pass[s->ev_frames % EV_RING] = true; s->ev_direct[s->ev_frames % EV_RING] = true; }
     if (s->n_prep_blocks == 0) { g_err = "internal: sharded frame without tile flags from k_prep"; return SM_E_ARG; }
     if ((rc = launch_surfel_pass(s, fp, true, true))) return rc;
     // The W*H conflict cap acts in surfel order over ALL ranks: exchange the conflict masks and take this rank's surplus back
@@ -2913,10 +2911,10 @@ int sm_shard_export_dense_device(sm_ctx *s, const float **d_out12, uint32_t *cou
     if ((rc = pull_state(s))) return rc;
     const uint32_t n = s->h_state->count;
     if ((rc = ensure_export(s, (size_t)std::max<uint32_t>(n, 1) * 48))) return rc;
-    if (n) hipLaunchKernelGGL(k_shard_export_aos, dim3((n + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, s->d_alive, (float *)s->d_export, n);
+    if (n) hipLaunchKernelGGL(k_shard_export_aos, dim3((n + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, s->d_alive, (float *)s->d_export.get(), n);
     HIPCK(hipGetLastError());
     HIPCK(hipStreamSynchronize(s->stream));
-    *d_out12 = (const float *)s->d_export;
+    *d_out12 = (const float *)s->d_export.get();
     *count = n;
     return SM_OK;
 }
@@ -2943,7 +2941,7 @@ namespace {
 // instead of one rank returning early and the rest blocking inside RCCL.
 struct RigXchg {
     sm_ctx *s; int W, r;
-    unsigned long long *d_cnt = nullptr;            // [W][4]
+    Dev<unsigned long long> d_cnt;                 // [W][4]
     std::vector<unsigned long long> h;
     RigXchg(sm_ctx *s_, int W_, int r_) : s(s_), W(W_), r(r_), h((size_t)W_ * 4) {}
     // returns 0, this rank's own failure code, or SM_E_HIP when another rank failed
@@ -2986,12 +2984,11 @@ int sm_rig_consolidate_step(sm_ctx *s, const uint16_t *depth_mm, const uint8_t *
     const int W = s->ss_world, r = s->ss_rank;
     const size_t P = (size_t)s->P;
     const size_t off_sem = 2 * P, off_pose = (3 * P + 7) / 8 * 8, row = off_pose + 64;
-    uint8_t *d_views = nullptr;
-    float *d_lists = nullptr;
-    uint32_t *d_first = nullptr;
+    Dev<uint8_t> d_views;
+    Dev<float> d_lists;
+    Dev<uint32_t> d_first;
     RigXchg x(s, W, r);
-    auto done = [&](int code) { (void)hipFree(d_views); (void)hipFree(d_lists); (void)hipFree(d_first); (void)hipFree(x.d_cnt); return code; };
-    HIPCK(hipMalloc((void **)&x.d_cnt, 32 * (size_t)W));
+    HIPCK(hipMalloc(x.d_cnt.put(), 32 * (size_t)W));
     // ---- local: compact (slots become positions), find the first surfel newer than the previous step, stage the view
     int st = ensure_compact(s);
     if (!st) st = pull_state(s);
@@ -2999,7 +2996,7 @@ int sm_rig_consolidate_step(sm_ctx *s, const uint16_t *depth_mm, const uint8_t *
     if (!st) {
         cnt = s->h_state->count;
         first = cnt;
-        if (hipMalloc((void **)&d_first, 4) != hipSuccess || hipMemsetAsync(d_first, 0xFF, 4, s->stream) != hipSuccess) st = SM_E_HIP;
+        if (hipMalloc(d_first.put(), 4) != hipSuccess || hipMemsetAsync(d_first, 0xFF, 4, s->stream) != hipSuccess) st = SM_E_HIP;
         if (!st && cnt) {
             hipLaunchKernelGGL(k_first_newer, dim3(std::min<uint32_t>((cnt + 255u) / 256u, 1024u)), dim3(256), 0, s->stream, s->M, s->d_state, s->rig_last_time, d_first);
             uint32_t f = 0xFFFFFFFFu;
@@ -3009,40 +3006,40 @@ int sm_rig_consolidate_step(sm_ctx *s, const uint16_t *depth_mm, const uint8_t *
         }
     }
     const uint32_t n_new = st ? 0u : cnt - first;
-    if (!st && hipMalloc((void **)&d_views, row * (size_t)W) != hipSuccess) { g_err = "sm_rig_consolidate_step: out of device memory for the views"; st = SM_E_HIP; }
+    if (!st && hipMalloc(d_views.put(), row * (size_t)W) != hipSuccess) { g_err = "sm_rig_consolidate_step: out of device memory for the views"; st = SM_E_HIP; }
     if (!st && (hipMemsetAsync(d_views + row * r, 0, row, s->stream) != hipSuccess ||
                 hipMemcpyAsync(d_views + row * r, depth_mm, 2 * P, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
                 hipMemcpyAsync(d_views + row * r + off_sem, semantic, P, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
                 hipMemcpyAsync(d_views + row * r + off_pose, pose16, 64, hipMemcpyHostToDevice, s->stream) != hipSuccess)) st = SM_E_HIP;
     int rc = x.run(n_new, 0ull, st);
-    if (rc) return done(rc);
+    if (rc) return rc;
     // ---- 1. the new-surfel lists, all-gathered (padded to the longest) and appended to `global` in rank order
     unsigned long long T = 0, maxn = 0;
     std::vector<unsigned long long> nn((size_t)W);
     for (int q = 0; q < W; ++q) { nn[(size_t)q] = x.count(q); T += nn[(size_t)q]; maxn = std::max(maxn, nn[(size_t)q]); }
     if (new_surfels) *new_surfels = (uint32_t)T;
     st = SM_OK;
-    if (T && hipMalloc((void **)&d_lists, (size_t)maxn * 48 * (size_t)W) != hipSuccess) { g_err = "sm_rig_consolidate_step: out of device memory for the lists"; st = SM_E_HIP; }
-    if ((rc = x.run(n_new, 0ull, st))) return done(rc);
+    if (T && hipMalloc(d_lists.put(), (size_t)maxn * 48 * (size_t)W) != hipSuccess) { g_err = "sm_rig_consolidate_step: out of device memory for the lists"; st = SM_E_HIP; }
+    if ((rc = x.run(n_new, 0ull, st))) return rc;
     if (T) {
         if (n_new) hipLaunchKernelGGL(k_export_aos, dim3((n_new + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, d_lists + (size_t)r * maxn * 12, first, n_new);
-        if (hipGetLastError() != hipSuccess) return done(SM_E_HIP);
-        if ((rc = ss_collective(s, d_lists + (size_t)r * maxn * 12, d_lists, (size_t)maxn * 6, SM_COLL_GATHER))) return done(rc);
+        if (hipGetLastError() != hipSuccess) return SM_E_HIP;
+        if ((rc = ss_collective(s, d_lists + (size_t)r * maxn * 12, d_lists, (size_t)maxn * 6, SM_COLL_GATHER))) return rc;
     }
-    if ((rc = ss_collective(s, d_views + row * r, d_views, row / 8, SM_COLL_GATHER))) return done(rc);
+    if ((rc = ss_collective(s, d_views + row * r, d_views, row / 8, SM_COLL_GATHER))) return rc;
     std::vector<float> poses((size_t)W * 16);
     for (int v = 0; v < W; ++v)
-        if (hipMemcpyAsync(&poses[(size_t)v * 16], d_views + row * v + off_pose, 64, hipMemcpyDeviceToHost, s->stream) != hipSuccess) return done(SM_E_HIP);
-    if (hipStreamSynchronize(s->stream) != hipSuccess) return done(SM_E_HIP);
+        if (hipMemcpyAsync(&poses[(size_t)v * 16], d_views + row * v + off_pose, 64, hipMemcpyDeviceToHost, s->stream) != hipSuccess) return SM_E_HIP;
+    if (hipStreamSynchronize(s->stream) != hipSuccess) return SM_E_HIP;
     for (int q = 0; q < W; ++q)
-        if (nn[(size_t)q] && (rc = sm_append_model_aos_device(global, d_lists + (size_t)q * maxn * 12, (uint32_t)nn[(size_t)q]))) return done(rc);
+        if (nn[(size_t)q] && (rc = sm_append_model_aos_device(global, d_lists + (size_t)q * maxn * 12, (uint32_t)nn[(size_t)q]))) return rc;
     // ---- 2. the union cleaned against every camera's latest view, in rank order (the same work on every rank)
     for (int v = 0; v < W; ++v)
         if ((rc = clean_points_device(global, reinterpret_cast<const uint16_t *>(d_views + row * v), d_views + row * v + off_sem,
-                                      &poses[(size_t)v * 16], 1))) return done(rc);
+                                      &poses[(size_t)v * 16], 1))) return rc;
     if (global_count) *global_count = global->counts.count;
     s->rig_last_time = (float)(s->tick - 1);           // every surfel created so far carries a time stamp <= tick - 1
-    return done(SM_OK);
+    return SM_OK;
 }
 
 int sm_rig_consolidate(sm_ctx *s, const uint16_t *depth_mm, const uint8_t *semantic, const float *pose16, sm_ctx *global,
@@ -3054,16 +3051,15 @@ int sm_rig_consolidate(sm_ctx *s, const uint16_t *depth_mm, const uint8_t *seman
     const int W = s->ss_world, r = s->ss_rank;
     const size_t P = (size_t)s->P;
     const size_t off_sem = 2 * P, off_pose = (3 * P + 7) / 8 * 8, row = off_pose + 64;        // bytes of one view (a multiple of 8)
-    uint8_t *d_views = nullptr;
-    float *d_union = nullptr;
+    Dev<uint8_t> d_views;
+    Dev<float> d_union;
     RigXchg x(s, W, r);
-    auto done = [&](int code) { (void)hipFree(d_views); (void)hipFree(d_union); (void)hipFree(x.d_cnt); return code; };
     // the exchange buffer first: without it this rank cannot even tell the others that it failed
-    HIPCK(hipMalloc((void **)&x.d_cnt, 32 * (size_t)W));
+    HIPCK(hipMalloc(x.d_cnt.put(), 32 * (size_t)W));
     // ---- local, fallible: settle the stream's pending work, stage this camera's latest view
     int st = finalize_if_pending(s);
     if (!st) st = pull_state(s);
-    if (!st && hipMalloc((void **)&d_views, row * (size_t)W) != hipSuccess) { g_err = "sm_rig_consolidate: out of device memory for the views"; st = SM_E_HIP; }
+    if (!st && hipMalloc(d_views.put(), row * (size_t)W) != hipSuccess) { g_err = "sm_rig_consolidate: out of device memory for the views"; st = SM_E_HIP; }
     if (!st && (hipMemsetAsync(d_views + row * r, 0, row, s->stream) != hipSuccess ||
                 hipMemcpyAsync(d_views + row * r, depth_mm, 2 * P, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
                 hipMemcpyAsync(d_views + row * r + off_sem, semantic, P, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
@@ -3071,9 +3067,9 @@ int sm_rig_consolidate(sm_ctx *s, const uint16_t *depth_mm, const uint8_t *seman
         g_err = "sm_rig_consolidate: staging the view failed"; st = SM_E_HIP;
     }
     int rc = x.run(st ? 0ull : s->counts.count, 0ull, st);
-    if (rc) return done(rc);
+    if (rc) return rc;
     // ---- 1. every rank learns every camera's latest view: all-gather, in place (3 bytes per pixel and camera)
-    if ((rc = ss_collective(s, d_views + row * r, d_views, row / 8, SM_COLL_GATHER))) return done(rc);
+    if ((rc = ss_collective(s, d_views + row * r, d_views, row / 8, SM_COLL_GATHER))) return rc;
     std::vector<float> poses((size_t)W * 16);
     st = SM_OK;
     for (int v = 0; v < W && !st; ++v)
@@ -3103,7 +3099,7 @@ int sm_rig_consolidate(sm_ctx *s, const uint16_t *depth_mm, const uint8_t *seman
                                                      &poses[(size_t)v * 16], first == r ? 1 : 0, &hook);
         // every rank makes both exchanges of a view whatever happened to it locally: a failure travels in the status word
         if (!hook_ran) (void)x.run(0ull, 0ull, cl ? cl : SM_E_HIP);
-        if ((rc = x.run(s->counts.count, 0ull, cl))) return done(rc);              // the slices' sizes after this view
+        if ((rc = x.run(s->counts.count, 0ull, cl))) return rc;              // the slices' sizes after this view
         if (view_conflicts) view_conflicts[v] = (uint32_t)(s->cfg.conflict_cap ? std::min<unsigned long long>(view_total, (unsigned long long)s->P) : view_total);
     }
     // ---- 3. the cleaned slices, all-gathered (padded to the largest) and appended in rank order to `global` on every rank
@@ -3111,21 +3107,21 @@ int sm_rig_consolidate(sm_ctx *s, const uint16_t *depth_mm, const uint8_t *seman
     std::vector<unsigned long long> cnt((size_t)W);
     for (int q = 0; q < W; ++q) { cnt[(size_t)q] = x.count(q); T += cnt[(size_t)q]; maxcnt = std::max(maxcnt, cnt[(size_t)q]); }
     if (total_out) *total_out = (uint32_t)T;
-    (void)hipFree(d_views); d_views = nullptr;
+    d_views = {};
     st = SM_OK;
-    if (T && hipMalloc((void **)&d_union, (size_t)maxcnt * 48 * (size_t)W) != hipSuccess) { g_err = "sm_rig_consolidate: out of device memory for the union"; st = SM_E_HIP; }
+    if (T && hipMalloc(d_union.put(), (size_t)maxcnt * 48 * (size_t)W) != hipSuccess) { g_err = "sm_rig_consolidate: out of device memory for the union"; st = SM_E_HIP; }
     if (!st) st = ensure_compact(s);
     if (!st) st = pull_state(s);
-    if ((rc = x.run(cnt[(size_t)r], 0ull, st))) return done(rc);
-    if (T == 0) return done(SM_OK);
+    if ((rc = x.run(cnt[(size_t)r], 0ull, st))) return rc;
+    if (T == 0) return SM_OK;
     const uint32_t own = s->h_state->count;
     if (own) hipLaunchKernelGGL(k_export_aos, dim3((own + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, d_union + (size_t)r * maxcnt * 12, 0u, own);
-    if (hipGetLastError() != hipSuccess) { g_err = "sm_rig_consolidate: export kernel launch failed"; return done(SM_E_HIP); }   // (the others' all-gather then fails or stalls: a launch failure is not recoverable)
-    if ((rc = ss_collective(s, d_union + (size_t)r * maxcnt * 12, d_union, (size_t)maxcnt * 6, SM_COLL_GATHER))) return done(rc);
-    if (hipStreamSynchronize(s->stream) != hipSuccess) return done(SM_E_HIP);
+    if (hipGetLastError() != hipSuccess) { g_err = "sm_rig_consolidate: export kernel launch failed"; return SM_E_HIP; }   // (the others' all-gather then fails or stalls: a launch failure is not recoverable)
+    if ((rc = ss_collective(s, d_union + (size_t)r * maxcnt * 12, d_union, (size_t)maxcnt * 6, SM_COLL_GATHER))) return rc;
+    if (hipStreamSynchronize(s->stream) != hipSuccess) return SM_E_HIP;
     for (int q = 0; q < W; ++q)
-        if (cnt[(size_t)q] && (rc = sm_append_model_aos_device(global, d_union + (size_t)q * maxcnt * 12, (uint32_t)cnt[(size_t)q]))) return done(rc);
-    return done(SM_OK);
+        if (cnt[(size_t)q] && (rc = sm_append_model_aos_device(global, d_union + (size_t)q * maxcnt * 12, (uint32_t)cnt[(size_t)q]))) return rc;
+    return SM_OK;
 }
 
 }  // extern "C"

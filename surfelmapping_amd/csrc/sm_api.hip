@@ -1,16 +1,14 @@
-// sm_api.hip -- C-ABI (include/sm_c_api.h) of the gfx950 surfel-fusion core: context, buffers,
-// frame sequencing (SurfelMapping::processFrame, /root/reference/src/SurfelMapping.cpp:115-251)
-// and launches of the kernels in sm_kernels.h.  No CPU fallback: without a HIP device
-// sm_create() fails with SM_E_NO_DEVICE.
-#include "../../include/sm_c_api.h"
+// sm_api.hip -- C-ABI (include/sm_c_api.h) of the gfx950 surfel-fusion core: context lifecycle, buffers, frame sequencing
+// (SurfelMapping::processFrame, /root/reference/src/SurfelMapping.cpp:115-251), the per-pass stage API, the sharded stream,
+// and launches of the kernels in sm_kernels.h.  The other features live in their own sources (sm_ctx.h lists them).  No CPU
+// fallback: without a HIP device sm_create() fails with SM_E_NO_DEVICE.
+#include "sm_ctx.h"
 #include "sm_kernels.h"
 
 #include <hip/hip_runtime.h>
 
 #include <dirent.h>
-#include <dlfcn.h>
 #include <link.h>
-#include <rccl/rccl.h>      // types and enums only: the library is bound at run time (sm_shard_rccl_*), never linked
 
 #include <algorithm>
 #include <chrono>
@@ -29,102 +27,6 @@
 using namespace sm;
 
 namespace {
-
-thread_local std::string g_err;
-
-void set_err(const char *what, hipError_t e, const char *file, int line)
-{
-    char buf[512];
-    snprintf(buf, sizeof buf, "%s: %s (%s:%d)", what, hipGetErrorString(e), file, line);
-    g_err = buf;
-}
-
-#define HIPCK(expr)                                              \
-    do {                                                         \
-        hipError_t e_ = (expr);                                  \
-        if (e_ != hipSuccess) {                                  \
-            set_err(#expr, e_, __FILE__, __LINE__);              \
-            return SM_E_HIP;                                     \
-        }                                                        \
-    } while (0)
-
-// Owner of one HIP handle (device or pinned host memory, an event, a stream): move-only, released by its destructor on the
-// current device (sm_destroy makes the context's device current).  It reads as the raw handle, so kernel arguments and argument
-// structs take it unchanged.  put() releases what it holds and hands out the slot for a create call, filled only on success.
-template <typename H, auto Release>
-class Own {
-public:
-    Own() = default;
-    Own(Own &&o) noexcept : h_(o.release()) {}
-    Own &operator=(Own o) noexcept { std::swap(h_, o.h_); return *this; }
-    ~Own() { if (h_) (void)Release(h_); }
-    operator H() const { return h_; }
-    H operator->() const { return h_; }
-    H get() const { return h_; }
-    H *put() { *this = Own(); return &h_; }
-    H release() { H h = h_; h_ = nullptr; return h; }
-private:
-    H h_ = nullptr;
-};
-template <typename T> using Dev = Own<T *, hipFree>;
-template <typename T> using Host = Own<T *, hipHostFree>;
-using Event = Own<hipEvent_t, hipEventDestroy>;
-using Stream = Own<hipStream_t, hipStreamDestroy>;
-
-// the buffers behind one SurfelSet (Model is passed to kernels by value and stays a set of views)
-struct SetBufs {
-    Dev<float4> pos_conf, norm_rad;
-    Dev<uint32_t> color;
-    Dev<float> init_time, time;
-    SurfelSet view() const { return {pos_conf, norm_rad, color, init_time, time}; }
-};
-constexpr int EV_RING = 256;
-constexpr int N_EV = 9;           // start, prep, conflict, scan_cull, compact, associate, scan_new, append, + calibration
-constexpr int MAX_GRID = 2048;   // 256 CUs x 8 workgroups
-constexpr int COMPACT_GRID = 1024;  // k_compact: 256 CUs x 4 workgroups, must be fully co-resident (in-place hand-off)
-
-// general 4x4 inverse, column-major, cofactor expansion, inv = adj * (1/det), fp32
-// (the role of Eigen::Matrix4f::inverse() at src/GlobalModel.cpp:419, src/IndexMap.cpp:157)
-void invert4(const float *m, float *out)
-{
-    float a[16];
-    a[0] = m[5] * m[10] * m[15] - m[5] * m[11] * m[14] - m[9] * m[6] * m[15] + m[9] * m[7] * m[14] +
-           m[13] * m[6] * m[11] - m[13] * m[7] * m[10];
-    a[4] = -m[4] * m[10] * m[15] + m[4] * m[11] * m[14] + m[8] * m[6] * m[15] - m[8] * m[7] * m[14] -
-           m[12] * m[6] * m[11] + m[12] * m[7] * m[10];
-    a[8] = m[4] * m[9] * m[15] - m[4] * m[11] * m[13] - m[8] * m[5] * m[15] + m[8] * m[7] * m[13] +
-           m[12] * m[5] * m[11] - m[12] * m[7] * m[9];
-    a[12] = -m[4] * m[9] * m[14] + m[4] * m[10] * m[13] + m[8] * m[5] * m[14] - m[8] * m[6] * m[13] -
-            m[12] * m[5] * m[10] + m[12] * m[6] * m[9];
-    a[1] = -m[1] * m[10] * m[15] + m[1] * m[11] * m[14] + m[9] * m[2] * m[15] - m[9] * m[3] * m[14] -
-           m[13] * m[2] * m[11] + m[13] * m[3] * m[10];
-    a[5] = m[0] * m[10] * m[15] - m[0] * m[11] * m[14] - m[8] * m[2] * m[15] + m[8] * m[3] * m[14] +
-           m[12] * m[2] * m[11] - m[12] * m[3] * m[10];
-    a[9] = -m[0] * m[9] * m[15] + m[0] * m[11] * m[13] + m[8] * m[1] * m[15] - m[8] * m[3] * m[13] -
-           m[12] * m[1] * m[11] + m[12] * m[3] * m[9];
-    a[13] = m[0] * m[9] * m[14] - m[0] * m[10] * m[13] - m[8] * m[1] * m[14] + m[8] * m[2] * m[13] +
-            m[12] * m[1] * m[10] - m[12] * m[2] * m[9];
-    a[2] = m[1] * m[6] * m[15] - m[1] * m[7] * m[14] - m[5] * m[2] * m[15] + m[5] * m[3] * m[14] +
-           m[13] * m[2] * m[7] - m[13] * m[3] * m[6];
-    a[6] = -m[0] * m[6] * m[15] + m[0] * m[7] * m[14] + m[4] * m[2] * m[15] - m[4] * m[3] * m[14] -
-           m[12] * m[2] * m[7] + m[12] * m[3] * m[6];
-    a[10] = m[0] * m[5] * m[15] - m[0] * m[7] * m[13] - m[4] * m[1] * m[15] + m[4] * m[3] * m[13] +
-            m[12] * m[1] * m[7] - m[12] * m[3] * m[5];
-    a[14] = -m[0] * m[5] * m[14] + m[0] * m[6] * m[13] + m[4] * m[1] * m[14] - m[4] * m[2] * m[13] -
-            m[12] * m[1] * m[6] + m[12] * m[2] * m[5];
-    a[3] = -m[1] * m[6] * m[11] + m[1] * m[7] * m[10] + m[5] * m[2] * m[11] - m[5] * m[3] * m[10] -
-           m[9] * m[2] * m[7] + m[9] * m[3] * m[6];
-    a[7] = m[0] * m[6] * m[11] - m[0] * m[7] * m[10] - m[4] * m[2] * m[11] + m[4] * m[3] * m[10] +
-           m[8] * m[2] * m[7] - m[8] * m[3] * m[6];
-    a[11] = -m[0] * m[5] * m[11] + m[0] * m[7] * m[9] + m[4] * m[1] * m[11] - m[4] * m[3] * m[9] -
-            m[8] * m[1] * m[7] + m[8] * m[3] * m[5];
-    a[15] = m[0] * m[5] * m[10] - m[0] * m[6] * m[9] - m[4] * m[1] * m[10] + m[4] * m[2] * m[9] +
-            m[8] * m[1] * m[6] - m[8] * m[2] * m[5];
-    const float det = m[0] * a[0] + m[1] * a[4] + m[2] * a[8] + m[3] * a[12];
-    const float rdet = 1.0f / det;
-    for (int i = 0; i < 16; ++i) out[i] = a[i] * rdet;
-}
-
 
 // column-major 4x4 product, c_ij = ((a_i0 b_0j + a_i1 b_1j) + a_i2 b_2j) + a_i3 b_3j
 void mul4(const float *a, const float *b, float *out)
@@ -170,8 +72,9 @@ int collect_hip_runtime(struct dl_phdr_info *info, size_t, void *data)
     if (info->dlpi_name && std::strstr(info->dlpi_name, "libamdhip64")) v->push_back(info->dlpi_name);
     return 0;
 }
-// true (and g_err set) if more than one libamdhip64 is mapped into this process
-bool hip_runtime_conflict(const char *where)
+}  // namespace
+
+bool sm_impl::hip_runtime_conflict(const char *where)
 {
     std::vector<std::string> libs;
     dl_iterate_phdr(collect_hip_runtime, &libs);
@@ -183,7 +86,6 @@ bool hip_runtime_conflict(const char *where)
             "surfelmapping_amd.capi, before anything that loads ROCm's libamdhip64; C++: link RCCL and this library against the same ROCm)";
     return true;
 }
-}  // namespace
 
 // Contexts of one process that share a GPU: the in-place compaction kernel waits on tile hand-off flags and, in its
 // default form, needs its whole grid resident -- two of them running at the same time can starve each other
@@ -281,185 +183,6 @@ bool compaction_needs_tickets(int dev)
     }
     return gpu_shared_with_other_process(dev);
 }
-}  // namespace
-
-struct sm_ctx {
-    // the streams come first: members die in reverse order, so everything used on them is released before they are
-    Stream stream;
-    Stream stream_in;                  // ONE copy stream.  (Two -- colour on one engine, depth + class on another -- were 80 instead of 89 us per frame on
-                                       // one box of the pool and stalled for 10-16 ms every few dozen frames on others; tools/h2d_probe.hip: per frame, three
-                                       // copies on two streams 68 us + stalls, on one stream 87, ONE copy of the whole frame 58 = the PCIe rate.)
-    sm_config cfg{};
-    int W = 0, H = 0, P = 0;
-    uint32_t cap = 0;                 // MAX_VERTICES
-    // The four frame planes exist twice (the *_nx pointers are the set of the other frame): a frame's association is held back
-    // and runs in the NEXT frame's preparation launch, which writes the other set.  (Rounds 1-2 ran the depth filter chain of
-    // frame f+1 on a second stream instead; since round 3 the chain is a stage of the preparation launch itself.)
-    int plane_set = 0;                 // which plane set the current frame uses
-    Model M{};
-    SetBufs m_bufs[2];                 // the buffers behind M.s[0] and M.s[1]
-    Dev<DevState> d_state;
-    Host<DevState> h_state;           // pinned mirror
-    // column-major frame images
-    Dev<float> d_depthT, d_filteredT, d_lastT;
-    Dev<uint32_t> d_rgbsT;
-    Dev<uint2> d_dcT;                  // (depth bits, rgbs) of the frame the conflict test sees
-    Dev<float> d_depthT_nx; Dev<uint32_t> d_rgbsT_nx; Dev<uint64_t> d_keyT_nx; Dev<uint2> d_dcT_nx;
-    Dev<uint64_t> d_keyT;
-    // row-major staging of the caller's inputs
-    Dev<uint8_t> d_rgb, d_sem;
-    Dev<uint16_t> d_depth_raw;
-    // sm_process_frame_async: a ring of device input sets filled on a copy stream, so that the H2D copy of frame f+1 runs while
-    // frame f computes; images in buffers of sm_host_alloc are copied from in place, others through pinned staging
-    static constexpr int IN_RING = 3;
-    struct InSlot { Dev<uint8_t> rgb; uint8_t *sem = nullptr; uint16_t *depth = nullptr;   // one block: depth and class follow the colour image
-                    Host<unsigned char> h_stage; Event ev_in, ev_free; bool used = false; };
-    InSlot in[IN_RING];
-    size_t in_off_depth = 0, in_off_sem = 0, in_bytes = 0;   // a frame's images as ONE block: colour | depth | class, 16-byte aligned (sm_host_alloc_frame)
-    uint32_t in_next = 0;
-    const uint16_t *in_last_depth = nullptr; const uint8_t *in_last_sem = nullptr;     // device copies of the last depth / semantic image given
-    int in_depth_slot = -1, in_sem_slot = -1;                                          // ... and the input sets that hold them
-    // Pinned host buffers handed out by sm_host_alloc, with their sizes: the sources sm_process_frame_async copies from in
-    // place.  Caller memory is never registered: hipHostRegister / hipHostUnregister of heap ranges left the runtime treating
-    // later, unrelated host arrays at the same addresses as pinned -- a GPU memory fault in whatever copied to or from them next.
-    std::vector<std::pair<Host<unsigned char>, size_t>> pinned;
-    Dev<float> d_depth_f32;
-    Dev<float> d_xs, d_ys;
-    float h_wtab[169];                 // depth_smooth.frag's 13 x 13 weights (host-computed, handed to the chain stage as kernel arguments)
-    // cull scratch
-    Dev<uint64_t> d_cm, d_dm, d_zm;
-    Dev<uint32_t> d_tile_cnt, d_tile_allow, d_tile_keep, d_tile_flag;
-    Dev<uint32_t> d_group_tot, d_group_base;
-    Dev<uint64_t> d_alive;             // 1 bit per slot: 0 = killed since the last physical compaction (free slots are 1)
-    Dev<uint32_t> d_tile_dead;         // dead slots per tile
-    size_t alive_words = 0, dead_tiles = 0;
-    bool maybe_garbage = false;        // a deferred-compaction cull ran since the last physical compaction
-    bool keys_are_slots = false;       // the key map was drawn by a cull that did not compact: its ids are slot numbers
-    int culls_since_compact = 0;       // deferred-compaction schedule (host side: it picks the kernels)
-    uint32_t frames_enq = 0;           // appends enqueued so far (compared with the tag of *h_stat)
-    Host<unsigned long long> h_stat; unsigned long long *d_stat = nullptr;   // pinned, device-written: frames<<32 | occupied slots
-    Dev<uint32_t> d_tb;                // per-tile bounds (8 words per tile)
-    Dev<uint8_t> d_tile_flags;         // per-tile skip flags of the current frame
-    Dev<uint8_t> d_tile_flags_nx; Dev<uint4> d_wave_cnt_nx; Dev<uint2> d_prep_part_nx;   // the other frame's (two-launch frame: its publisher runs next to this frame's flag workgroups)
-    Dev<uint32_t> d_conf_part;         // per-workgroup partial counters (instead of same-address atomics)
-    Dev<uint2> d_compact_part;
-    Dev<uint4> d_lazy_part;            // partials of k_surfel_pass (visible, splat-skipped, killed, conflict-skipped)
-    bool lazy_part_live = false;       // the next append folds d_lazy_part (not d_compact_part) into the counters
-    // one pass over the surfels per frame (k_surfel_pass + k_pass_fixup) on the frames whose cull only marks the dead
-    Dev<uint4> d_wave_cnt;             // conflicts per quarter tile (one word per wave)
-    Dev<float> d_undo;                 // confidence before this frame's decrement, per slot (read only if the conflict cap binds)
-    Dev<uint2> d_fix_part;             // partials of k_pass_fixup (visible added, resurrected)
-    bool fix_part_live = false;        // the next append also folds d_fix_part in (when the cap bound)
-    uint32_t n_fix_part = 0;           // worker workgroups of the last k_pass_fixup
-    bool ev_one_pass[EV_RING] = {};    // which frames of the event ring ran the one-pass kernels
-    bool ev_direct[EV_RING] = {};      // ... and appended directly
-    bool ev_merged[EV_RING] = {};      // the frame's preparation launch was k_assoc_prep (it carried the previous frame's association)
-    bool ev_deferred[EV_RING] = {};    // the frame's own association was held back (no kernel between its marks 4 and 5)
-    // tile skip flags of the frame, evaluated by extra workgroups of the preparation launch
-    Dev<uint2> d_prep_part;
-    uint32_t n_prep_blocks = 0;        // flag workgroups the frame's k_prep ran (0: the pass kernel evaluates the flags itself)
-    bool want_list = false;            // set by enqueue_frame before begin_frame launches k_prep
-    int fix_grid = 128;
-    // direct append (k_associate_direct): candidate counts per association block / per group, group prefixes
-    Dev<uint32_t> d_blk_cand, d_grp_cand;
-    Dev<uint32_t> d_frame_sub;         // 2 x 64 sub-counters: visible, killed (k_surfel_pass)
-    uint32_t *d_nf_sub = nullptr, *d_nf_sub_nx = nullptr;   // 2 x 64 each: new, fused (k_associate_direct) of this / the other frame
-    uint32_t *nf_last = nullptr;       // the set the last direct association counted into (its statistics may still be pending)
-    uint32_t n_grp = 0, cand_group = 16;
-    bool pend_finalize = false;        // the last frame's statistics are completed by the next k_pass_fixup or by k_frame_finalize
-    int fix_set = 0;                   // k_pass_fixup's partials alternate between two sets (the previous frame's are read one frame later)
-    Dev<unsigned long long> d_pass_trace;         // SM_PASS_TRACE=<file prefix>: per-workgroup time stamps of the last k_surfel_pass launch, dumped by sm_destroy
-    int pass_trace_grid = 0;
-    Dev<unsigned long long> d_ap_trace;           // the same for the last k_assoc_prep launch: (entry, exit) per workgroup
-    int ap_trace_n[4] = {0, 0, 0, 0};             // its association / tile-flag / image workgroups (dispatch order); fixup workgroups ahead of them
-    Dev<uint32_t> d_conf_sub;          // 2 x 64 conflict sub-counters (one set per frame parity: zeroed by that frame's k_prep)
-    int conf_sub_set = 0;
-    uint32_t n_conf_part = 0, n_compact_part = 0;
-    uint32_t tb_tiles = 0;
-    uint32_t cull_epoch = 0;
-    int compact_grid = COMPACT_GRID;
-    int pass_grid = MAX_GRID;          // workgroups of k_surfel_pass that are resident at once (a larger grid runs its tail as a second, thin wave)
-    // association scratch
-    Dev<uint64_t> d_validmask, d_fusedmask;
-    Dev<uint2> d_blk_cnt;
-    // slot-addressed sharding of one stream, in-stream form (sm_shard_stream_*)
-    bool ss_on = false;
-    bool rig_on = false;               // sm_rig_configure: rank / world / collective are used by sm_rig_consolidate only
-    float rig_last_time = -1.0e30f;    // creation time stamp up to which this rank's surfels are in the incremental GlobalModel (sm_rig_consolidate_step)
-    int ss_rank = 0, ss_world = 1;
-    uint32_t ss_frames = 0;            // fusing frames so far = index of the next segment (its owner: index % world)
-    sm_collective_fn ss_coll = nullptr;
-    void *ss_user = nullptr;
-    void *ss_comm = nullptr;           // ncclComm_t when the built-in RCCL binding is used
-    Dev<uint64_t> d_galive, d_new_alive, d_gmask;
-    Dev<uint32_t> d_chk;               // SM_CHECK_ALIVE=1: result words of k_check_alive
-    Dev<uint64_t> d_capx;              // the conflict-cap exchange of a sharded frame: total | quarter-tile counts | conflict masks (k_shard_cap_pack)
-    Dev<uint32_t> d_ss_info;
-    // deferred association (k_assoc_prep): the association of an asynchronous frame is held back until the next frame's images
-    // arrive and then shares that frame's k_prep launch (three launches per frame instead of four)
-    bool defer_ok = false;             // this context may defer (plain stream, no depth filter chain, no per-kernel timing)
-    bool assoc_pending = false;
-    AssocArgs assoc_args{};            // the held-back association (its FrameParams and that frame's planes)
-    bool merge_assoc = false;          // set by enqueue_frame: the k_prep launch of this call carries assoc_args
-    // two-launch frame: the fixup step (publisher, cap repair) of a frame whose association is held back rides on the same
-    // launch as that association; the candidate count moved into the pass's launch
-    bool two_launch = false;           // this context uses it (defer_ok, SM_TWO_LAUNCH != 0)
-    uint32_t est_fr0 = 0, est_slots0 = 0, est_rate = 0xFFFFFFFFu;   // launch_surfel_pass's estimate of the slots per frame (from the pinned statistic)
-    bool fix_pending = false;          // the last frame's fixup has not run yet
-    FixArgs fix_args{};
-    static constexpr uint32_t N_CREW = 32;
-    bool ss_settle_pending = false;    // the last sharded frame's k_shard_settle work rides on the next k_prep (or runs stand-alone first)
-    ShardSettle ss_settle{};
-    int n_pix_blocks = 0;
-    uint32_t n_odd_pixels = 0;
-    // export staging
-    Dev<void> d_export;
-    size_t export_bytes = 0;
-    // model view (sm_render_model): where the last render left its overflow-list length in the export scratch (valid until the
-    // scratch is reused), and the diagnostic timing events (SM_RENDER_MODEL_TIMING=1)
-    size_t rm_ovf_off = 0;
-    bool rm_ovf_valid = false;
-    bool rm_timed = false;
-    Event rm_ev[4];
-    // tracking (sm_track_frame / sm_track_debug, sm_k_track.h): scratch allocated by the first call, the last two processed poses
-    Dev<uint16_t> d_trk_depth;
-    Dev<float4> d_trk_v, d_trk_n;
-    Dev<uint64_t> d_trk_key;
-    Dev<int32_t> d_trk_pred;
-    Dev<double> d_trk_part;
-    Dev<TrackState> d_trk;
-    Host<TrackState> h_trk;
-    float trk_hist[2][16];             // [0] the last processed pose (T_prev), [1] the one before (T_prev2)
-    int trk_n_hist = 0;                // poses processed so far (capped at 2)
-    bool trk_timed = false;            // SM_TRACK_TIMING=1 at the last call: events around every kernel
-    int trk_ev_iters = 0;              // iterations the events of the last timed call cover
-    std::vector<Event> trk_ev;
-    // host frame state (src/SurfelMapping.h:100-103)
-    int tick = 0;
-    bool ref_set = false;
-    bool raw_valid = false;            // a frame that computes the raw feedback cloud has run (every call but the reference frame)
-    int raw_tick = 0;                  // its time stamp
-    float curr_pose[16], last_pose[16];
-    uint32_t count_bound = 0;         // host upper bound of the device-side count (grid sizing)
-    bool pending_cull = false;
-    uint32_t count_before_cull = 0, offset_before_cull = 0;
-    sm_counts counts{};
-    std::vector<Dev<void>> user_allocs;
-    // timing
-    std::unique_ptr<Event[][EV_RING]> ev;   // enable_timing: per-frame timeline (before prep, then after each kernel), [N_EV][EV_RING]; whole or absent
-    bool ev_compacted[EV_RING] = {};  // which cull kernel the frame of that slot ran
-    Dev<FrameLog> d_log;
-    uint64_t ev_frames = 0, ev_read = 0;
-};
-
-namespace {
-
-template <typename T>
-int dalloc(Dev<T> &p, size_t n)
-{
-    HIPCK(hipMalloc(p.put(), std::max<size_t>(n, 1) * sizeof(T)));
-    return SM_OK;
-}
 
 int alloc_set(SetBufs &b, size_t cap)
 {
@@ -467,52 +190,10 @@ int alloc_set(SetBufs &b, size_t cap)
            dalloc(b.time, cap) ? SM_E_HIP : SM_OK;
 }
 
-FrameParams make_params(const sm_ctx *s, const float *pose)
-{
-    FrameParams fp;
-    memset(&fp, 0, sizeof fp);
-    memcpy(fp.pose, pose, 64);
-    invert4(pose, fp.t_inv);
-    const sm_config &c = s->cfg;
-    fp.fx = c.fx; fp.fy = c.fy; fp.cx = c.cx; fp.cy = c.cy;
-    fp.inv_fx = (float)(1.0 / (double)c.fx);
-    fp.inv_fy = (float)(1.0 / (double)c.fy);
-    fp.cols = (float)c.width; fp.rows = (float)c.height;
-    fp.W = c.width; fp.H = c.height; fp.P = s->P;
-    fp.min_depth = c.near_clip; fp.max_depth = c.far_clip;
-    fp.conflict_thresh = c.fuse_thresh;
-    fp.fuse_thresh = c.fuse_thresh;
-    fp.stereo_border = c.stereo_border;
-    fp.is_clean = 0;
-    fp.time = s->tick;
-    fp.time_delta = c.time_delta;
-    fp.depth_cutoff = c.far_clip;
-    fp.conflict_cap = c.conflict_cap ? (uint32_t)s->P : 0xFFFFFFFFu;
-    fp.max_vertices = s->cap;
-    fp.init_mode = 0;
-    fp.inv_fx_fb = 1.0f / c.fx;
-    fp.inv_fy_fb = 1.0f / c.fy;
-    fp.use_bounds = c.disable_tile_bounds ? 0 : 1;
-    fp.compact_now = 1;                     // the per-pass entry points compact at every cull
-    fp.maintenance = 0;
-    fp.par = s->plane_set;
-    return fp;
-}
-
 int grid_surfels(const sm_ctx *s)
 {
     const uint64_t tiles = ((uint64_t)s->count_bound + TILE - 1) / TILE;
     return (int)std::min<uint64_t>(std::max<uint64_t>(tiles, 1), MAX_GRID);
-}
-
-void publish_stat(sm_ctx *s);
-
-int push_state(sm_ctx *s)
-{
-    HIPCK(hipMemcpyAsync(s->d_state, s->h_state, sizeof(DevState), hipMemcpyHostToDevice, s->stream));
-    HIPCK(hipStreamSynchronize(s->stream));
-    publish_stat(s);
-    return SM_OK;
 }
 
 // a direct-append frame leaves its new / fused totals, the dead-slot total and its log entry to be completed by the next
@@ -524,41 +205,6 @@ void check_alive(sm_ctx *s, uint32_t stage)
 {
     if (!s->d_chk) return;
     hipLaunchKernelGGL(k_check_alive, dim3(64), dim3(256), 0, s->stream, s->d_state, s->d_alive, s->d_tile_dead, s->d_chk, stage);
-}
-
-int finalize_if_pending(sm_ctx *s)
-{
-    if (flush_assoc(s)) return SM_E_HIP;      // a held-back association comes first: everything below reads its results
-    if (s->ss_settle_pending) {          // a sharded frame whose settle step has not run yet: stand-alone, before anything reads its results
-        s->ss_settle_pending = false;
-        hipLaunchKernelGGL(k_shard_settle, dim3(s->ss_settle.n), dim3(PIX_BLOCK), 0, s->stream, s->ss_settle);
-        HIPCK(hipGetLastError());
-    }
-    if (!s->pend_finalize) return SM_OK;
-    s->pend_finalize = false;
-    hipLaunchKernelGGL(k_frame_finalize, dim3(1), dim3(256), 0, s->stream, s->d_state, s->nf_last ? s->nf_last : s->d_nf_sub,
-                       s->d_fix_part + (size_t)s->fix_set * MAX_GRID, s->n_fix_part, s->d_log);
-    HIPCK(hipGetLastError());
-    return SM_OK;
-}
-
-int pull_state(sm_ctx *s)
-{
-    int rcf = finalize_if_pending(s);
-    if (rcf) return rcf;
-    HIPCK(hipMemcpyAsync(s->h_state, s->d_state, sizeof(DevState), hipMemcpyDeviceToHost, s->stream));
-    HIPCK(hipStreamSynchronize(s->stream));
-    const DevState &d = *s->h_state;
-    s->counts.count = s->pending_cull ? s->count_before_cull : d.count - d.garbage;   // dead slots are not surfels
-    s->counts.offset = d.offset - (d.garbage - d.holes_last);   // (empty slots of fused candidates lie above `offset`)
-    s->counts.data_count = d.data_count;
-    s->counts.conflict_count = d.conflict_count;
-    s->counts.unstable_count = d.unstable_count;
-    s->counts.fused_count = d.fused_count;
-    s->counts.visible_count = d.visible_count;
-    s->counts.tick = s->tick;
-    s->count_bound = std::max(d.count, d.cull_n * (s->pending_cull ? 1u : 0u));
-    return SM_OK;
 }
 
 int take_error(sm_ctx *s)
@@ -953,55 +599,7 @@ int launch_post_fill(sm_ctx *s)
     return SM_OK;
 }
 
-// Physical compaction outside a frame: every entry point that exposes slots as surfel ids (downloads, the per-pass
-// API, rendering, sharding, uploads) first squeezes out the slots that deferred culls left dead.  Nothing is killed:
-// empty conflict masks, then the regular scan + in-place compaction, with the key map's ids translated on the way.
 int ss_compact(sm_ctx *s);
-
-int ensure_compact(sm_ctx *s)
-{
-    if (finalize_if_pending(s)) return SM_E_HIP;
-    if (s->ss_on) {
-        // slot-addressed sharding: a rank's arrays always hold the (dead) slots of the other ranks' surfels; the compaction is
-        // a collective step, so every rank must be making this same call
-        int rc = ss_compact(s);
-        if (rc) return rc;
-        HIPCK(hipStreamSynchronize(s->stream));
-        return SM_OK;
-    }
-    if (!s->maybe_garbage) return SM_OK;
-    if (s->pending_cull) { g_err = "internal: deferred compaction with a pending per-pass cull"; return SM_E_ARG; }
-    FrameParams fp = make_params(s, s->curr_pose);
-    fp.maintenance = 1;
-    fp.compact_now = 1;
-    fp.conflict_cap = 0xFFFFFFFFu;
-    const uint64_t tiles = ((uint64_t)s->count_bound + TILE - 1) / TILE + 1;
-    const size_t words = std::min<size_t>(tiles * TILE_WORDS, s->alive_words);
-    HIPCK(hipMemsetAsync(s->d_cm, 0, words * 8, s->stream));
-    HIPCK(hipMemsetAsync(s->d_dm, 0, words * 8, s->stream));
-    HIPCK(hipMemsetAsync(s->d_zm, 0, words * 8, s->stream));
-    HIPCK(hipMemsetAsync(s->d_tile_cnt, 0, std::min<size_t>(tiles, s->dead_tiles) * 12, s->stream));
-    const int ngroups = std::max<int>(1, (int)((tiles + GROUP - 1) / GROUP));
-    hipLaunchKernelGGL(k_scan_cull, dim3(ngroups), dim3(1024), 0, s->stream, s->d_state, s->d_tile_cnt, s->d_tile_allow,
-                       s->d_tile_keep, s->d_group_tot, s->d_tile_dead);
-    hipLaunchKernelGGL(k_cull_finalize, dim3(1), dim3(1024), 0, s->stream, s->d_state, fp, s->d_cm, s->d_dm, s->d_zm,
-                       s->d_tile_cnt, s->d_tile_allow, s->d_tile_keep, s->d_group_tot, s->d_group_base, s->d_conf_part, 0u,
-                       s->d_alive, s->d_tile_dead, s->d_stat);
-    if (s->keys_are_slots)     // ids of the index map: slot -> position among the live surfels, as the API hands them out
-        hipLaunchKernelGGL(k_remap_keys, dim3((s->P + 255) / 256), dim3(256), 0, s->stream, s->d_state, s->d_keyT, s->P, s->d_alive,
-                           s->d_tile_keep, s->d_group_base);
-    s->keys_are_slots = false;
-    HIPCK(hipGetLastError());
-    const uint32_t keep_part = s->n_compact_part;
-    int rc = launch_compact(s, fp, false, false);
-    s->n_compact_part = keep_part;
-    if (rc) return rc;
-    if ((rc = launch_post_fill(s))) return rc;
-    s->maybe_garbage = false;
-    s->culls_since_compact = 0;
-    HIPCK(hipStreamSynchronize(s->stream));
-    return SM_OK;
-}
 
 int launch_associate_only(sm_ctx *s, const FrameParams &fp)
 {
@@ -1030,8 +628,6 @@ int launch_associate(sm_ctx *s, const FrameParams &fp, bool timed)
     check_alive(s, 5u + 16u * (uint32_t)(s->tick & 0xFFFF));
     return SM_OK;
 }
-
-int rebuild_bounds(sm_ctx *s, uint32_t first_surfel, uint32_t count);
 
 // empty the model on the device (reset path; synchronises)
 int discard_model(sm_ctx *s)
@@ -1068,9 +664,7 @@ int begin_frame(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_raw, const ui
 {
     if (s->pending_cull) { g_err = "sm_stage_conflict without sm_stage_cull"; return SM_E_ARG; }
     memcpy(s->curr_pose, pose, 64);
-    memcpy(s->trk_hist[1], s->trk_hist[0], 64);          // the tracker's constant-velocity history (sm_track_frame)
-    memcpy(s->trk_hist[0], pose, 64);
-    s->trk_n_hist = std::min(s->trk_n_hist + 1, 2);
+    s->trk.note_pose(pose);                               // the tracker's constant-velocity history (sm_track_frame)
     FrameParams fp = make_params(s, pose);
     const bool fusing = s->ref_set && s->tick != 0;
     int rc;
@@ -1205,35 +799,6 @@ int upload_inputs(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth, const ui
     return SM_OK;
 }
 
-// rebuild the bounds of every tile that holds a surfel with index >= first_surfel (after the model was written
-// from outside the frame pipeline); the state on the device must already carry the new count
-int rebuild_bounds(sm_ctx *s, uint32_t first_surfel, uint32_t count)
-{
-    const uint32_t t0 = first_surfel / TILE;
-    if (t0 < s->tb_tiles) {
-        const uint32_t n = s->tb_tiles - t0;
-        hipLaunchKernelGGL(k_tile_bounds_reset, dim3((n + 255) / 256), dim3(256), 0, s->stream, s->d_tb, t0, n);
-        HIPCK(hipGetLastError());
-    }
-    const uint32_t k0 = t0 * TILE;
-    if (count > k0) {
-        hipLaunchKernelGGL(k_tile_bounds_build, dim3((count - k0 + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, s->d_tb, k0);
-        HIPCK(hipGetLastError());
-    }
-    HIPCK(hipStreamSynchronize(s->stream));
-    return SM_OK;
-}
-
-int ensure_export(sm_ctx *s, size_t bytes)
-{
-    s->rm_ovf_valid = false;                  // (every user of the scratch may overwrite the model view's overflow count)
-    if (bytes <= s->export_bytes) return SM_OK;
-    s->export_bytes = 0;
-    HIPCK(hipMalloc(s->d_export.put(), bytes));
-    s->export_bytes = bytes;
-    return SM_OK;
-}
-
 // sm_create's buffers in order, up to the first failure (g_err is set only where dalloc failed)
 int alloc_ctx(sm_ctx *s)
 {
@@ -1272,6 +837,246 @@ int alloc_ctx(sm_ctx *s)
 }
 
 }  // namespace
+
+// ---- helpers the other sources call (declared in sm_ctx.h) ----
+
+// general 4x4 inverse, column-major, cofactor expansion, inv = adj * (1/det), fp32
+// (the role of Eigen::Matrix4f::inverse() at src/GlobalModel.cpp:419, src/IndexMap.cpp:157)
+void sm_impl::invert4(const float *m, float *out)
+{
+    float a[16];
+    a[0] = m[5] * m[10] * m[15] - m[5] * m[11] * m[14] - m[9] * m[6] * m[15] + m[9] * m[7] * m[14] +
+           m[13] * m[6] * m[11] - m[13] * m[7] * m[10];
+    a[4] = -m[4] * m[10] * m[15] + m[4] * m[11] * m[14] + m[8] * m[6] * m[15] - m[8] * m[7] * m[14] -
+           m[12] * m[6] * m[11] + m[12] * m[7] * m[10];
+    a[8] = m[4] * m[9] * m[15] - m[4] * m[11] * m[13] - m[8] * m[5] * m[15] + m[8] * m[7] * m[13] +
+           m[12] * m[5] * m[11] - m[12] * m[7] * m[9];
+    a[12] = -m[4] * m[9] * m[14] + m[4] * m[10] * m[13] + m[8] * m[5] * m[14] - m[8] * m[6] * m[13] -
+            m[12] * m[5] * m[10] + m[12] * m[6] * m[9];
+    a[1] = -m[1] * m[10] * m[15] + m[1] * m[11] * m[14] + m[9] * m[2] * m[15] - m[9] * m[3] * m[14] -
+           m[13] * m[2] * m[11] + m[13] * m[3] * m[10];
+    a[5] = m[0] * m[10] * m[15] - m[0] * m[11] * m[14] - m[8] * m[2] * m[15] + m[8] * m[3] * m[14] +
+           m[12] * m[2] * m[11] - m[12] * m[3] * m[10];
+    a[9] = -m[0] * m[9] * m[15] + m[0] * m[11] * m[13] + m[8] * m[1] * m[15] - m[8] * m[3] * m[13] -
+           m[12] * m[1] * m[11] + m[12] * m[3] * m[9];
+    a[13] = m[0] * m[9] * m[14] - m[0] * m[10] * m[13] - m[8] * m[1] * m[14] + m[8] * m[2] * m[13] +
+            m[12] * m[1] * m[10] - m[12] * m[2] * m[9];
+    a[2] = m[1] * m[6] * m[15] - m[1] * m[7] * m[14] - m[5] * m[2] * m[15] + m[5] * m[3] * m[14] +
+           m[13] * m[2] * m[7] - m[13] * m[3] * m[6];
+    a[6] = -m[0] * m[6] * m[15] + m[0] * m[7] * m[14] + m[4] * m[2] * m[15] - m[4] * m[3] * m[14] -
+           m[12] * m[2] * m[7] + m[12] * m[3] * m[6];
+    a[10] = m[0] * m[5] * m[15] - m[0] * m[7] * m[13] - m[4] * m[1] * m[15] + m[4] * m[3] * m[13] +
+            m[12] * m[1] * m[7] - m[12] * m[3] * m[5];
+    a[14] = -m[0] * m[5] * m[14] + m[0] * m[6] * m[13] + m[4] * m[1] * m[14] - m[4] * m[2] * m[13] -
+            m[12] * m[1] * m[6] + m[12] * m[2] * m[5];
+    a[3] = -m[1] * m[6] * m[11] + m[1] * m[7] * m[10] + m[5] * m[2] * m[11] - m[5] * m[3] * m[10] -
+           m[9] * m[2] * m[7] + m[9] * m[3] * m[6];
+    a[7] = m[0] * m[6] * m[11] - m[0] * m[7] * m[10] - m[4] * m[2] * m[11] + m[4] * m[3] * m[10] +
+           m[8] * m[2] * m[7] - m[8] * m[3] * m[6];
+    a[11] = -m[0] * m[5] * m[11] + m[0] * m[7] * m[9] + m[4] * m[1] * m[11] - m[4] * m[3] * m[9] -
+            m[8] * m[1] * m[7] + m[8] * m[3] * m[5];
+    a[15] = m[0] * m[5] * m[10] - m[0] * m[6] * m[9] - m[4] * m[1] * m[10] + m[4] * m[2] * m[9] +
+            m[8] * m[1] * m[6] - m[8] * m[2] * m[5];
+    const float det = m[0] * a[0] + m[1] * a[4] + m[2] * a[8] + m[3] * a[12];
+    const float rdet = 1.0f / det;
+    for (int i = 0; i < 16; ++i) out[i] = a[i] * rdet;
+}
+
+FrameParams sm_impl::make_params(const sm_ctx *s, const float *pose)
+{
+    FrameParams fp;
+    memset(&fp, 0, sizeof fp);
+    memcpy(fp.pose, pose, 64);
+    invert4(pose, fp.t_inv);
+    const sm_config &c = s->cfg;
+    fp.fx = c.fx; fp.fy = c.fy; fp.cx = c.cx; fp.cy = c.cy;
+    fp.inv_fx = (float)(1.0 / (double)c.fx);
+    fp.inv_fy = (float)(1.0 / (double)c.fy);
+    fp.cols = (float)c.width; fp.rows = (float)c.height;
+    fp.W = c.width; fp.H = c.height; fp.P = s->P;
+    fp.min_depth = c.near_clip; fp.max_depth = c.far_clip;
+    fp.conflict_thresh = c.fuse_thresh;
+    fp.fuse_thresh = c.fuse_thresh;
+    fp.stereo_border = c.stereo_border;
+    fp.is_clean = 0;
+    fp.time = s->tick;
+    fp.time_delta = c.time_delta;
+    fp.depth_cutoff = c.far_clip;
+    fp.conflict_cap = c.conflict_cap ? (uint32_t)s->P : 0xFFFFFFFFu;
+    fp.max_vertices = s->cap;
+    fp.init_mode = 0;
+    fp.inv_fx_fb = 1.0f / c.fx;
+    fp.inv_fy_fb = 1.0f / c.fy;
+    fp.use_bounds = c.disable_tile_bounds ? 0 : 1;
+    fp.compact_now = 1;                     // the per-pass entry points compact at every cull
+    fp.maintenance = 0;
+    fp.par = s->plane_set;
+    return fp;
+}
+
+int sm_impl::push_state(sm_ctx *s)
+{
+    HIPCK(hipMemcpyAsync(s->d_state, s->h_state, sizeof(DevState), hipMemcpyHostToDevice, s->stream));
+    HIPCK(hipStreamSynchronize(s->stream));
+    publish_stat(s);
+    return SM_OK;
+}
+
+int sm_impl::finalize_if_pending(sm_ctx *s)
+{
+    if (flush_assoc(s)) return SM_E_HIP;      // a held-back association comes first: everything below reads its results
+    if (s->ss_settle_pending) {          // a sharded frame whose settle step has not run yet: stand-alone, before anything reads its results
+        s->ss_settle_pending = false;
+        hipLaunchKernelGGL(k_shard_settle, dim3(s->ss_settle.n), dim3(PIX_BLOCK), 0, s->stream, s->ss_settle);
+        HIPCK(hipGetLastError());
+    }
+    if (!s->pend_finalize) return SM_OK;
+    s->pend_finalize = false;
+    hipLaunchKernelGGL(k_frame_finalize, dim3(1), dim3(256), 0, s->stream, s->d_state, s->nf_last ? s->nf_last : s->d_nf_sub,
+                       s->d_fix_part + (size_t)s->fix_set * MAX_GRID, s->n_fix_part, s->d_log);
+    HIPCK(hipGetLastError());
+    return SM_OK;
+}
+
+int sm_impl::pull_state(sm_ctx *s)
+{
+    int rcf = finalize_if_pending(s);
+    if (rcf) return rcf;
+    HIPCK(hipMemcpyAsync(s->h_state, s->d_state, sizeof(DevState), hipMemcpyDeviceToHost, s->stream));
+    HIPCK(hipStreamSynchronize(s->stream));
+    const DevState &d = *s->h_state;
+    s->counts.count = s->pending_cull ? s->count_before_cull : d.count - d.garbage;   // dead slots are not surfels
+    s->counts.offset = d.offset - (d.garbage - d.holes_last);   // (empty slots of fused candidates lie above `offset`)
+    s->counts.data_count = d.data_count;
+    s->counts.conflict_count = d.conflict_count;
+    s->counts.unstable_count = d.unstable_count;
+    s->counts.fused_count = d.fused_count;
+    s->counts.visible_count = d.visible_count;
+    s->counts.tick = s->tick;
+    s->count_bound = std::max(d.count, d.cull_n * (s->pending_cull ? 1u : 0u));
+    return SM_OK;
+}
+
+// Physical compaction outside a frame: every entry point that exposes slots as surfel ids (downloads, the per-pass
+// API, rendering, sharding, uploads) first squeezes out the slots that deferred culls left dead.  Nothing is killed:
+// empty conflict masks, then the regular scan + in-place compaction, with the key map's ids translated on the way.
+int sm_impl::ensure_compact(sm_ctx *s)
+{
+    if (finalize_if_pending(s)) return SM_E_HIP;
+    if (s->ss_on) {
+        // slot-addressed sharding: a rank's arrays always hold the (dead) slots of the other ranks' surfels; the compaction is
+        // a collective step, so every rank must be making this same call
+        int rc = ss_compact(s);
+        if (rc) return rc;
+        HIPCK(hipStreamSynchronize(s->stream));
+        return SM_OK;
+    }
+    if (!s->maybe_garbage) return SM_OK;
+    if (s->pending_cull) { g_err = "internal: deferred compaction with a pending per-pass cull"; return SM_E_ARG; }
+    FrameParams fp = make_params(s, s->curr_pose);
+    fp.maintenance = 1;
+    fp.compact_now = 1;
+    fp.conflict_cap = 0xFFFFFFFFu;
+    const uint64_t tiles = ((uint64_t)s->count_bound + TILE - 1) / TILE + 1;
+    const size_t words = std::min<size_t>(tiles * TILE_WORDS, s->alive_words);
+    HIPCK(hipMemsetAsync(s->d_cm, 0, words * 8, s->stream));
+    HIPCK(hipMemsetAsync(s->d_dm, 0, words * 8, s->stream));
+    HIPCK(hipMemsetAsync(s->d_zm, 0, words * 8, s->stream));
+    HIPCK(hipMemsetAsync(s->d_tile_cnt, 0, std::min<size_t>(tiles, s->dead_tiles) * 12, s->stream));
+    const int ngroups = std::max<int>(1, (int)((tiles + GROUP - 1) / GROUP));
+    hipLaunchKernelGGL(k_scan_cull, dim3(ngroups), dim3(1024), 0, s->stream, s->d_state, s->d_tile_cnt, s->d_tile_allow,
+                       s->d_tile_keep, s->d_group_tot, s->d_tile_dead);
+    hipLaunchKernelGGL(k_cull_finalize, dim3(1), dim3(1024), 0, s->stream, s->d_state, fp, s->d_cm, s->d_dm, s->d_zm,
+                       s->d_tile_cnt, s->d_tile_allow, s->d_tile_keep, s->d_group_tot, s->d_group_base, s->d_conf_part, 0u,
+                       s->d_alive, s->d_tile_dead, s->d_stat);
+    if (s->keys_are_slots)     // ids of the index map: slot -> position among the live surfels, as the API hands them out
+        hipLaunchKernelGGL(k_remap_keys, dim3((s->P + 255) / 256), dim3(256), 0, s->stream, s->d_state, s->d_keyT, s->P, s->d_alive,
+                           s->d_tile_keep, s->d_group_base);
+    s->keys_are_slots = false;
+    HIPCK(hipGetLastError());
+    const uint32_t keep_part = s->n_compact_part;
+    int rc = launch_compact(s, fp, false, false);
+    s->n_compact_part = keep_part;
+    if (rc) return rc;
+    if ((rc = launch_post_fill(s))) return rc;
+    s->maybe_garbage = false;
+    s->culls_since_compact = 0;
+    HIPCK(hipStreamSynchronize(s->stream));
+    return SM_OK;
+}
+
+// rebuild the bounds of every tile that holds a surfel with index >= first_surfel (after the model was written
+// from outside the frame pipeline); the state on the device must already carry the new count
+int sm_impl::rebuild_bounds(sm_ctx *s, uint32_t first_surfel, uint32_t count)
+{
+    const uint32_t t0 = first_surfel / TILE;
+    if (t0 < s->tb_tiles) {
+        const uint32_t n = s->tb_tiles - t0;
+        hipLaunchKernelGGL(k_tile_bounds_reset, dim3((n + 255) / 256), dim3(256), 0, s->stream, s->d_tb, t0, n);
+        HIPCK(hipGetLastError());
+    }
+    const uint32_t k0 = t0 * TILE;
+    if (count > k0) {
+        hipLaunchKernelGGL(k_tile_bounds_build, dim3((count - k0 + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, s->d_tb, k0);
+        HIPCK(hipGetLastError());
+    }
+    HIPCK(hipStreamSynchronize(s->stream));
+    return SM_OK;
+}
+
+int sm_impl::ensure_export(sm_ctx *s, size_t bytes)
+{
+    s->rm.scratch_reused();
+    if (bytes <= s->export_bytes) return SM_OK;
+    s->export_bytes = 0;
+    HIPCK(hipMalloc(s->d_export.put(), bytes));
+    s->export_bytes = bytes;
+    return SM_OK;
+}
+
+void sm_impl::fill_keys(sm_ctx *s, uint64_t *key, size_t n)
+{
+    hipLaunchKernelGGL(k_fill_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, key, (int)n);
+}
+
+// SurfelMapping::cleanPoints with the view already in device memory (sm_clean_points_ex uploads it; sm_rig_consolidate
+// takes it from the gathered views of the rig).  `cap_hook`, if given, runs between the conflict test (which changes nothing)
+// and the cull: it receives this model's conflict count and returns the number of them that may take effect, in surfel order
+// (src/GlobalModel.cpp:54-57: conflictVbo holds W*H records) -- a rig slice learns its share of the union's W*H there -- or a
+// negative error code, which abandons the cull with the model untouched.
+int sm_impl::clean_points_device(sm_ctx *s, const uint16_t *d_depth_mm, const uint8_t *d_semantic, const float *pose16, int exempt_first,
+                                 const std::function<long long(uint32_t)> *cap_hook)
+{
+    if (s->pending_cull) { g_err = "sm_stage_conflict without sm_stage_cull"; return SM_E_ARG; }
+    // cleanPoints culls without redrawing the index map (src/SurfelMapping.cpp:496-532): the map keeps ids of the model
+    // as it was, so they are settled (slot -> position) before this cull changes the positions
+    int rc = ensure_compact(s);
+    if (rc) return rc;
+    memcpy(s->curr_pose, pose16, 64);
+    FrameParams fp = make_params(s, pose16);
+    if ((rc = launch_prep(s, s->d_rgb, d_depth_mm, d_semantic, nullptr, fp, false))) return rc;   // metriciseDepth only
+    fp.max_depth = s->cfg.far_clip - 15.0f;     // src/SurfelMapping.cpp:515
+    fp.conflict_thresh = 0.1f;                  // :516
+    fp.is_clean = 1;                            // :517
+    fp.no_exempt = exempt_first ? 0 : 1;
+    fp.compact_now = decide_compact(s) ? 1u : 0u;
+    if ((rc = launch_conflict_test(s, fp))) return rc;
+    if (cap_hook) {
+        std::vector<uint32_t> part((size_t)s->n_conf_part * 4);
+        HIPCK(hipMemcpyAsync(part.data(), s->d_conf_part, part.size() * 4, hipMemcpyDeviceToHost, s->stream));
+        HIPCK(hipStreamSynchronize(s->stream));
+        uint64_t local = 0;
+        for (uint32_t b = 0; b < s->n_conf_part; ++b) local += part[(size_t)b * 4 + 1];
+        const long long allow = (*cap_hook)((uint32_t)local);
+        if (allow < 0) return (int)allow;
+        fp.conflict_cap = (uint32_t)std::min<long long>(allow, 0xFFFFFFFFll);
+    }
+    note_cull(s, fp.compact_now != 0u);
+    if ((rc = launch_conflict_finalize(s, fp))) return rc;
+    if ((rc = launch_compact(s, fp, false, false))) return rc;
+    if ((rc = launch_post_fill(s))) return rc;
+    return sm_sync(s);
+}
 
 // =============================================================================================
 extern "C" {
@@ -1393,7 +1198,7 @@ sm_ctx *sm_create(const sm_config *c)
          hipDeviceSynchronize() == hipSuccess;
     if (ok) {
         hipLaunchKernelGGL(k_tile_bounds_reset, dim3((s->tb_tiles + 255) / 256), dim3(256), 0, s->stream, s->d_tb, 0u, s->tb_tiles);
-        hipLaunchKernelGGL(k_fill_keys, dim3((s->P + 255) / 256), dim3(256), 0, s->stream, s->d_keyT, s->P);
+        fill_keys(s.get(), s->d_keyT, s->P);
         ok = hipStreamSynchronize(s->stream) == hipSuccess;
     }
     if (!ok) { g_err = "sm_create: device initialisation failed"; return nullptr; }
@@ -1620,51 +1425,6 @@ int sm_clean_points(sm_ctx *s, const uint16_t *depth_mm, const uint8_t *semantic
     return sm_clean_points_ex(s, depth_mm, semantic, pose16, 1);
 }
 
-}  // extern "C"
-
-namespace {
-// SurfelMapping::cleanPoints with the view already in device memory (sm_clean_points_ex uploads it; sm_rig_consolidate
-// takes it from the gathered views of the rig).  `cap_hook`, if given, runs between the conflict test (which changes nothing)
-// and the cull: it receives this model's conflict count and returns the number of them that may take effect, in surfel order
-// (src/GlobalModel.cpp:54-57: conflictVbo holds W*H records) -- a rig slice learns its share of the union's W*H there -- or a
-// negative error code, which abandons the cull with the model untouched.
-int clean_points_device(sm_ctx *s, const uint16_t *d_depth_mm, const uint8_t *d_semantic, const float *pose16, int exempt_first,
-                        const std::function<long long(uint32_t)> *cap_hook = nullptr)
-{
-    if (s->pending_cull) { g_err = "sm_stage_conflict without sm_stage_cull"; return SM_E_ARG; }
-    // cleanPoints culls without redrawing the index map (src/SurfelMapping.cpp:496-532): the map keeps ids of the model
-    // as it was, so they are settled (slot -> position) before this cull changes the positions
-    int rc = ensure_compact(s);
-    if (rc) return rc;
-    memcpy(s->curr_pose, pose16, 64);
-    FrameParams fp = make_params(s, pose16);
-    if ((rc = launch_prep(s, s->d_rgb, d_depth_mm, d_semantic, nullptr, fp, false))) return rc;   // metriciseDepth only
-    fp.max_depth = s->cfg.far_clip - 15.0f;     // src/SurfelMapping.cpp:515
-    fp.conflict_thresh = 0.1f;                  // :516
-    fp.is_clean = 1;                            // :517
-    fp.no_exempt = exempt_first ? 0 : 1;
-    fp.compact_now = decide_compact(s) ? 1u : 0u;
-    if ((rc = launch_conflict_test(s, fp))) return rc;
-    if (cap_hook) {
-        std::vector<uint32_t> part((size_t)s->n_conf_part * 4);
-        HIPCK(hipMemcpyAsync(part.data(), s->d_conf_part, part.size() * 4, hipMemcpyDeviceToHost, s->stream));
-        HIPCK(hipStreamSynchronize(s->stream));
-        uint64_t local = 0;
-        for (uint32_t b = 0; b < s->n_conf_part; ++b) local += part[(size_t)b * 4 + 1];
-        const long long allow = (*cap_hook)((uint32_t)local);
-        if (allow < 0) return (int)allow;
-        fp.conflict_cap = (uint32_t)std::min<long long>(allow, 0xFFFFFFFFll);
-    }
-    note_cull(s, fp.compact_now != 0u);
-    if ((rc = launch_conflict_finalize(s, fp))) return rc;
-    if ((rc = launch_compact(s, fp, false, false))) return rc;
-    if ((rc = launch_post_fill(s))) return rc;
-    return sm_sync(s);
-}
-}  // namespace
-
-extern "C" {
-
 int sm_clean_points_ex(sm_ctx *s, const uint16_t *depth_mm, const uint8_t *semantic, const float *pose16, int exempt_first)
 {
     if (!s || !depth_mm || !semantic || !pose16) { g_err = "sm_clean_points: null argument"; return SM_E_ARG; }
@@ -1714,579 +1474,6 @@ int sm_get_counts(sm_ctx *s, sm_counts *out)
     if (!s || !out) return SM_E_ARG;
     *out = s->counts;
     out->tick = s->tick;
-    return SM_OK;
-}
-
-int sm_download_model_aos(sm_ctx *s, float *dst12, uint32_t cap, uint32_t *n)
-{
-    if (!s || !n) return SM_E_ARG;
-    HIPCK(hipSetDevice(s->cfg.device));
-    int rc = ensure_compact(s);
-    if (rc) return rc;
-    if ((rc = pull_state(s))) return rc;
-    const uint32_t cnt = s->pending_cull ? s->count_before_cull : s->h_state->count;
-    *n = cnt;
-    if (!dst12) return SM_OK;
-    if (cap < cnt) { g_err = "sm_download_model_aos: destination too small"; return SM_E_CAPACITY; }
-    if (s->pending_cull) { g_err = "sm_download_model_aos between sm_stage_conflict and sm_stage_cull"; return SM_E_ARG; }
-    const uint32_t CH = 1u << 22;                // 4 Mi surfels (192 MiB) per staging chunk
-    if ((rc = ensure_export(s, (size_t)std::min(cnt, CH) * 48))) return rc;
-    for (uint32_t first = 0; first < cnt; first += CH) {
-        const uint32_t m = std::min(CH, cnt - first);
-        hipLaunchKernelGGL(k_export_aos, dim3((m + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, (float *)s->d_export.get(), first, m);
-        HIPCK(hipGetLastError());
-        HIPCK(hipMemcpyAsync(dst12 + (size_t)first * 12, s->d_export, (size_t)m * 48, hipMemcpyDeviceToHost, s->stream));
-        HIPCK(hipStreamSynchronize(s->stream));
-    }
-    return SM_OK;
-}
-
-int sm_upload_model_aos(sm_ctx *s, const float *src12, uint32_t n)
-{
-    if (!s || (!src12 && n)) return SM_E_ARG;
-    HIPCK(hipSetDevice(s->cfg.device));
-    if (n > s->cap) { g_err = "sm_upload_model_aos: exceeds MAX_VERTICES"; return SM_E_CAPACITY; }
-    int rc = ensure_compact(s);
-    if (rc) return rc;
-    if ((rc = pull_state(s))) return rc;
-    const uint32_t CH = 1u << 22;
-    if (n && (rc = ensure_export(s, (size_t)std::min(n, CH) * 48))) return rc;
-    for (uint32_t first = 0; first < n; first += CH) {
-        const uint32_t m = std::min(CH, n - first);
-        HIPCK(hipMemcpyAsync(s->d_export, src12 + (size_t)first * 12, (size_t)m * 48, hipMemcpyHostToDevice, s->stream));
-        hipLaunchKernelGGL(k_import_aos, dim3((m + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, (const float *)s->d_export.get(), first, m);
-        HIPCK(hipGetLastError());
-        HIPCK(hipStreamSynchronize(s->stream));
-    }
-    s->h_state->count = n;                       // src/GlobalModel.cpp:995
-    s->h_state->offset = n;
-    s->h_state->garbage = 0; s->h_state->garbage_prev = 0; s->h_state->first_live = 0; s->h_state->do_compact = 0;
-    s->pending_cull = false;
-    if ((rc = push_state(s))) return rc;
-    if ((rc = rebuild_bounds(s, 0, n))) return rc;
-    return pull_state(s);
-}
-
-int sm_save_map(sm_ctx *s, const char *path, int32_t start_id, int32_t end_id)
-{
-    if (!s || !path) return SM_E_ARG;
-    uint32_t n = 0;
-    int rc = sm_download_model_aos(s, nullptr, 0, &n);
-    if (rc) return rc;
-    std::vector<float> buf((size_t)n * 12);
-    if ((rc = sm_download_model_aos(s, buf.data(), n, &n))) return rc;
-    FILE *f = fopen(path, "wb");
-    if (!f) { g_err = std::string(path) + " is not open!"; return SM_E_ARG; }
-    // u32 count | i32 startId | i32 endId | count*12 f32   (src/GlobalModel.cpp:927-932)
-    bool ok = fwrite(&n, 4, 1, f) == 1 && fwrite(&start_id, 4, 1, f) == 1 && fwrite(&end_id, 4, 1, f) == 1 &&
-              (n == 0 || fwrite(buf.data(), 48, n, f) == n);
-    ok = (fclose(f) == 0) && ok;
-    if (!ok) { g_err = std::string(path) + " saved err!!"; return SM_E_ARG; }
-    return SM_OK;
-}
-
-int sm_load_map(sm_ctx *s, const char *path, int32_t *start_id, int32_t *end_id)
-{
-    if (!s || !path) return SM_E_ARG;
-    FILE *f = fopen(path, "rb");
-    if (!f) { g_err = std::string(path) + " is not open!"; return SM_E_ARG; }
-    uint32_t n = 0; int32_t a = 0, b = 0;
-    bool ok = fread(&n, 4, 1, f) == 1 && fread(&a, 4, 1, f) == 1 && fread(&b, 4, 1, f) == 1;
-    std::vector<float> buf;
-    if (ok && n <= s->cap) { buf.resize((size_t)n * 12); ok = n == 0 || fread(buf.data(), 48, n, f) == n; }
-    fclose(f);
-    if (!ok) { g_err = std::string(path) + " read err!!"; return SM_E_ARG; }
-    if (n > s->cap) { g_err = "map larger than MAX_VERTICES"; return SM_E_CAPACITY; }
-    if (start_id) *start_id = a;
-    if (end_id) *end_id = b;
-    return sm_upload_model_aos(s, buf.data(), n);
-}
-
-int sm_download_index_map(sm_ctx *s, int32_t *id, float *vert_conf4, float *color_time4, float *norm_rad4)
-{
-    if (!s) return SM_E_ARG;
-    HIPCK(hipSetDevice(s->cfg.device));
-    const size_t P = (size_t)s->P;
-    int rc = ensure_compact(s);
-    if (rc) return rc;
-    if ((rc = ensure_export(s, P * 52))) return rc;
-    char *base = (char *)s->d_export.get();
-    int32_t *d_id = (int32_t *)(base + P * 48);
-    float4 *d_vc = (float4 *)base, *d_ct = (float4 *)(base + P * 16), *d_nr = (float4 *)(base + P * 32);
-    FrameParams fp = make_params(s, s->curr_pose);
-    hipLaunchKernelGGL(k_export_index, dim3((s->P + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, fp, s->d_keyT, d_id, d_vc, d_ct, d_nr);
-    HIPCK(hipGetLastError());
-    if (id) HIPCK(hipMemcpyAsync(id, d_id, P * 4, hipMemcpyDeviceToHost, s->stream));
-    if (vert_conf4) HIPCK(hipMemcpyAsync(vert_conf4, d_vc, P * 16, hipMemcpyDeviceToHost, s->stream));
-    if (color_time4) HIPCK(hipMemcpyAsync(color_time4, d_ct, P * 16, hipMemcpyDeviceToHost, s->stream));
-    if (norm_rad4) HIPCK(hipMemcpyAsync(norm_rad4, d_nr, P * 16, hipMemcpyDeviceToHost, s->stream));
-    HIPCK(hipStreamSynchronize(s->stream));
-    return SM_OK;
-}
-
-int sm_download_raw_cloud(sm_ctx *s, float *dst12, uint32_t cap, uint32_t *n)
-{
-    if (!s || !n) return SM_E_ARG;
-    HIPCK(hipSetDevice(s->cfg.device));
-    *n = 0;
-    if (!s->raw_valid) return SM_OK;                     // nothing computed yet (the reference's buffer is empty before the 2nd frame)
-    const size_t P = (size_t)s->P;
-    int rc = ensure_export(s, P * 49);
-    if (rc) return rc;
-    float4 *d_rec = (float4 *)s->d_export.get();
-    uint8_t *d_flag = (uint8_t *)s->d_export.get() + P * 48;
-    FrameParams fp = make_params(s, s->curr_pose);
-    fp.init_mode = 1;
-    fp.time = s->raw_tick;
-    hipLaunchKernelGGL(k_raw_cloud, dim3((s->P + 255) / 256), dim3(256), 0, s->stream, fp, s->d_depthT, s->d_rgbsT, s->d_xs, s->d_ys, d_rec, d_flag);
-    HIPCK(hipGetLastError());
-    std::vector<uint8_t> flag(P);
-    HIPCK(hipMemcpyAsync(flag.data(), d_flag, P, hipMemcpyDeviceToHost, s->stream));
-    HIPCK(hipStreamSynchronize(s->stream));
-    uint32_t cnt = 0;
-    for (size_t q = 0; q < P; ++q) cnt += flag[q];
-    *n = cnt;
-    if (!dst12) return SM_OK;
-    if (cap < cnt) { g_err = "sm_download_raw_cloud: destination too small"; return SM_E_CAPACITY; }
-    std::vector<float> rec(P * 12);
-    HIPCK(hipMemcpyAsync(rec.data(), d_rec, P * 48, hipMemcpyDeviceToHost, s->stream));
-    HIPCK(hipStreamSynchronize(s->stream));
-    uint32_t w = 0;
-    for (size_t q = 0; q < P; ++q)                       // q = i * H + j: the feedback buffer's vertex order
-        if (flag[q]) { memcpy(dst12 + (size_t)w * 12, rec.data() + q * 12, 48); ++w; }
-    return SM_OK;
-}
-
-int sm_download_depth(sm_ctx *s, int which, float *dst)
-{
-    if (!s || !dst) return SM_E_ARG;
-    HIPCK(hipSetDevice(s->cfg.device));
-    const bool alias = s->cfg.preprocess == 0;
-    // preprocess == 1: after every processFrame LAST == DEPTH_FILTERED (src/SurfelMapping.cpp:244); the two
-    // buffers are swapped instead of copied, so both names read d_lastT.
-    const float *src = which == SM_TEX_DEPTH_METRIC ? s->d_depthT : which == SM_TEX_DEPTH_FILTERED ? (alias ? s->d_depthT : s->d_lastT)
-                     : which == SM_TEX_LAST ? (alias ? s->d_depthT : s->d_lastT) : nullptr;
-    if (!src) return SM_E_ARG;
-    int rc = ensure_export(s, (size_t)s->P * 4);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_untranspose_f32, dim3((s->P + 255) / 256), dim3(256), 0, s->stream, src, (float *)s->d_export.get(), s->W, s->H);
-    HIPCK(hipGetLastError());
-    HIPCK(hipMemcpyAsync(dst, s->d_export, (size_t)s->P * 4, hipMemcpyDeviceToHost, s->stream));
-    HIPCK(hipStreamSynchronize(s->stream));
-    return SM_OK;
-}
-
-int sm_render_image(sm_ctx *s, const float *view16, int w, int h, float fx, float fy, float cx, float cy, uint8_t *bgr_out,
-                    uint8_t *sem_out)
-{
-    if (!s || !view16 || w <= 0 || h <= 0 || (uint64_t)w * h > (1u << 28) || !bgr_out || !sem_out) return SM_E_ARG;
-    HIPCK(hipSetDevice(s->cfg.device));
-    if (s->pending_cull) { g_err = "sm_render_image between sm_stage_conflict and sm_stage_cull"; return SM_E_ARG; }
-    int rc = ensure_compact(s);
-    if (rc) return rc;
-    if ((rc = pull_state(s))) return rc;
-    const size_t npix = (size_t)w * h;
-    if ((rc = ensure_export(s, npix * 12))) return rc;            // [keys u64 | bgr | sem]
-    uint64_t *d_key = (uint64_t *)s->d_export.get();
-    uint8_t *d_bgr = (uint8_t *)s->d_export.get() + npix * 8, *d_sem = d_bgr + npix * 3;
-    RenderParams rp;
-    invert4(view16, rp.t_inv);
-    rp.fx = fx; rp.fy = fy; rp.cx = cx; rp.cy = cy; rp.cols = (float)w; rp.rows = (float)h; rp.w = w; rp.h = h;
-    hipLaunchKernelGGL(k_fill_keys, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s->stream, d_key, (int)npix);
-    const uint32_t cnt = s->h_state->count;
-    if (cnt) hipLaunchKernelGGL(k_render_splat, dim3((cnt + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, rp, d_key);
-    hipLaunchKernelGGL(k_render_resolve, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s->stream, s->M, s->d_state, d_key,
-                       (int)npix, d_bgr, d_sem);
-    HIPCK(hipGetLastError());
-    HIPCK(hipMemcpyAsync(bgr_out, d_bgr, npix * 3, hipMemcpyDeviceToHost, s->stream));
-    HIPCK(hipMemcpyAsync(sem_out, d_sem, npix, hipMemcpyDeviceToHost, s->stream));
-    HIPCK(hipStreamSynchronize(s->stream));
-    return SM_OK;
-}
-
-}  // extern "C"
-
-namespace {
-// GlobalModel::renderModel (src/GlobalModel.cpp:683-758) into device memory (sm_k_view.h): keys [8 w h] | overflow length
-// [256] | overflow list [4 count] in the export scratch; with `stage` (the host path) the images follow there too -- rgba,
-// depth, id, w*h*4 bytes each -- and *stage points at them.  Changes neither the model nor the frame state; the forced
-// compaction of ensure_compact is the one every read-back does.
-int render_model_enqueue(sm_ctx *s, const sm_model_view *v, const char *fn, uint8_t **stage, uint8_t *d_rgba, float *d_depth,
-                         int32_t *d_id)
-{
-    // (the view is checked before the context, so that each rule can be exercised without a device)
-    if (!v) { g_err = std::string(fn) + ": null view"; return SM_E_ARG; }
-    if (v->width <= 0 || v->height <= 0 || (uint64_t)v->width * (uint64_t)v->height > (1u << 28)) {
-        g_err = std::string(fn) + ": width and height must be positive, w*h at most 2^28"; return SM_E_ARG;
-    }
-    if (v->color_type < 0 || v->color_type > 3) { g_err = std::string(fn) + ": color_type is 0..3"; return SM_E_ARG; }
-    if (!d_rgba && !stage) { g_err = std::string(fn) + ": null rgba"; return SM_E_ARG; }
-    if (!s) { g_err = std::string(fn) + ": null context"; return SM_E_ARG; }
-    if (!stage && (((uintptr_t)d_rgba | (uintptr_t)d_depth | (uintptr_t)d_id) & 3u)) {
-        g_err = std::string(fn) + ": outputs must be 4-byte aligned"; return SM_E_ARG;
-    }
-    if (s->ss_on) { g_err = std::string(fn) + ": a sharded context holds only its rank's surfels; rendering the union is not supported"; return SM_E_UNSUPPORTED; }
-    if (s->pending_cull) { g_err = std::string(fn) + " between sm_stage_conflict and sm_stage_cull"; return SM_E_ARG; }
-    HIPCK(hipSetDevice(s->cfg.device));
-    int rc = ensure_compact(s);
-    if (rc) return rc;
-    if ((rc = pull_state(s))) return rc;                          // (waits for frames in flight; count is the live surfels)
-    const uint32_t cnt = s->h_state->count;
-    const size_t npix = (size_t)v->width * v->height;
-    const size_t ovf_off = npix * 8, list_off = ovf_off + 256, extra_off = list_off + (((size_t)cnt * 4 + 255) & ~(size_t)255);
-    if ((rc = ensure_export(s, extra_off + (stage ? npix * 12 : 0)))) return rc;
-    uint8_t *base = (uint8_t *)s->d_export.get();
-    uint64_t *d_key = (uint64_t *)base;
-    uint32_t *d_ovf_n = (uint32_t *)(base + ovf_off), *d_ovf = (uint32_t *)(base + list_off);
-    if (stage) {
-        *stage = base + extra_off;
-        d_rgba = *stage;
-        if (d_depth) d_depth = (float *)(*stage + npix * 4);
-        if (d_id) d_id = (int32_t *)(*stage + npix * 8);
-    }
-    ViewParams vp;
-    memcpy(vp.mvp, v->mvp, 64);
-    memcpy(vp.mvinv, v->mv_inv, 64);
-    vp.threshold = v->threshold;
-    vp.unstable = v->draw_unstable ? 1 : 0;
-    vp.points = v->draw_points ? 1 : 0;
-    vp.w = v->width; vp.h = v->height;
-    vp.fp_lane = 64;                                              // tuning constant: DESIGN.md "Model view" has the sweep
-    if (const char *e = std::getenv("SM_RENDER_MODEL_LANE_PX")) vp.fp_lane = (uint32_t)std::max(0, std::atoi(e));
-    ViewShade vs;
-    vs.color_type = v->color_type;
-    vs.window = (v->draw_window && !v->draw_points) ? 1 : 0;      // draw_feedback.vert has no window
-    vs.time = v->time; vs.time_delta = v->time_delta;
-    vs.clear = (uint32_t)v->clear_rgba[0] | ((uint32_t)v->clear_rgba[1] << 8) | ((uint32_t)v->clear_rgba[2] << 16) |
-               ((uint32_t)v->clear_rgba[3] << 24);
-    const char *te = std::getenv("SM_RENDER_MODEL_TIMING");
-    s->rm_timed = te && te[0] == '1';
-    if (s->rm_timed && !s->rm_ev[0]) {
-        Event ev[4];
-        for (Event &e : ev) HIPCK(hipEventCreate(e.put()));
-        std::move(std::begin(ev), std::end(ev), s->rm_ev);
-    }
-    const unsigned pblocks = (unsigned)((npix + 255) / 256);
-    hipLaunchKernelGGL(k_fill_keys, dim3(pblocks), dim3(256), 0, s->stream, d_key, (int)npix);
-    HIPCK(hipMemsetAsync(d_ovf_n, 0, 4, s->stream));
-    if (s->rm_timed) HIPCK(hipEventRecord(s->rm_ev[0], s->stream));
-    if (cnt) hipLaunchKernelGGL(k_view_splat, dim3((cnt + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, vp, d_key, d_ovf_n, d_ovf);
-    if (s->rm_timed) HIPCK(hipEventRecord(s->rm_ev[1], s->stream));
-    if (cnt && !vp.points)
-        hipLaunchKernelGGL(k_view_overflow, dim3(VIEW_OVF_BLOCKS), dim3(256), 0, s->stream, s->M, s->d_state, vp, d_key, d_ovf_n, d_ovf);
-    if (s->rm_timed) HIPCK(hipEventRecord(s->rm_ev[2], s->stream));
-    hipLaunchKernelGGL(k_view_resolve, dim3(pblocks), dim3(256), 0, s->stream, s->M, s->d_state, vs, d_key, (int)npix,
-                       (uint32_t *)d_rgba, d_depth, d_id);
-    if (s->rm_timed) HIPCK(hipEventRecord(s->rm_ev[3], s->stream));
-    HIPCK(hipGetLastError());
-    s->rm_ovf_off = ovf_off;
-    s->rm_ovf_valid = true;
-    return SM_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int sm_render_model(sm_ctx *s, const sm_model_view *v, uint8_t *rgba, float *depth, int32_t *id)
-{
-    uint8_t *stage = nullptr;
-    // (rgba / depth / id only say which images are wanted: the staging area receives them)
-    int rc = render_model_enqueue(s, v, "sm_render_model", rgba ? &stage : nullptr, nullptr, depth, id);
-    if (rc) return rc;
-    const size_t npix = (size_t)v->width * v->height;
-    HIPCK(hipMemcpyAsync(rgba, stage, npix * 4, hipMemcpyDeviceToHost, s->stream));
-    if (depth) HIPCK(hipMemcpyAsync(depth, stage + npix * 4, npix * 4, hipMemcpyDeviceToHost, s->stream));
-    if (id) HIPCK(hipMemcpyAsync(id, stage + npix * 8, npix * 4, hipMemcpyDeviceToHost, s->stream));
-    HIPCK(hipStreamSynchronize(s->stream));
-    return SM_OK;
-}
-
-int sm_render_model_device(sm_ctx *s, const sm_model_view *v, uint8_t *d_rgba, float *d_depth, int32_t *d_id)
-{
-    return render_model_enqueue(s, v, "sm_render_model_device", nullptr, d_rgba, d_depth, d_id);
-}
-
-// Diagnostic, deliberately not part of include/sm_c_api.h (tools/render_model_probe.py, tests/test_render_model.py): waits
-// for the context's stream; `overflow` = surfels the last sm_render_model* call rasterised on the overflow path (the count
-// lives in the export scratch: SM_E_ARG if another read-back has reused it since), `ms3` = its splat / overflow / resolve
-// kernel times when SM_RENDER_MODEL_TIMING=1 was set for that call, else -1.
-int sm_debug_render_model_stats(sm_ctx *s, uint32_t *overflow, float *ms3)
-{
-    if (!s) return SM_E_ARG;
-    HIPCK(hipSetDevice(s->cfg.device));
-    HIPCK(hipStreamSynchronize(s->stream));
-    if (!s->rm_ovf_valid) { g_err = "sm_debug_render_model_stats: no model view since the last reuse of the export scratch"; return SM_E_ARG; }
-    if (overflow) HIPCK(hipMemcpy(overflow, (uint8_t *)s->d_export.get() + s->rm_ovf_off, 4, hipMemcpyDeviceToHost));
-    if (ms3)
-        for (int i = 0; i < 3; ++i) {
-            ms3[i] = -1.0f;
-            if (s->rm_timed) HIPCK(hipEventElapsedTime(&ms3[i], s->rm_ev[i], s->rm_ev[i + 1]));
-        }
-    return SM_OK;
-}
-
-}  // extern "C"
-
-namespace {
-// ---- tracking (sm_k_track.h) ----
-
-// [R^T | -R^T t] of a column-major rigid pose, double
-void rigid_inv_d(const double *m, double *o)
-{
-    for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) o[c * 4 + r] = m[r * 4 + c];
-        o[12 + r] = -((m[r * 4 + 0] * m[12] + m[r * 4 + 1] * m[13]) + m[r * 4 + 2] * m[14]);
-    }
-    o[3] = 0.0; o[7] = 0.0; o[11] = 0.0; o[15] = 1.0;
-}
-
-// column-major rigid product a * b, double
-void mul_rigid_d(const double *a, const double *b, double *o)
-{
-    for (int c = 0; c < 4; ++c)
-        for (int r = 0; r < 3; ++r)
-            o[c * 4 + r] = ((a[r] * b[c * 4] + a[4 + r] * b[c * 4 + 1]) + a[8 + r] * b[c * 4 + 2]) + (c == 3 ? a[12 + r] : 0.0);
-    o[3] = 0.0; o[7] = 0.0; o[11] = 0.0; o[15] = 1.0;
-}
-
-// the rotation of a column-major pose made orthonormal (Gram-Schmidt on columns 0 and 1, column 2 = 0 x 1), double.  Float
-// poses are orthonormal to ~1e-7 only; products of them (the constant-velocity guess, exp(xi) * guess) would carry and, frame
-// after frame, multiply that error, so every product starts from orthonormal factors.
-void orthonormalize_d(double *m)
-{
-    double *a = m, *b = m + 4, *c = m + 8;
-    const double na = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
-    for (int k = 0; k < 3; ++k) a[k] /= na;
-    const double ab = a[0] * b[0] + a[1] * b[1] + a[2] * b[2];
-    for (int k = 0; k < 3; ++k) b[k] -= ab * a[k];
-    const double nb = std::sqrt(b[0] * b[0] + b[1] * b[1] + b[2] * b[2]);
-    for (int k = 0; k < 3; ++k) b[k] /= nb;
-    c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
-    m[3] = 0.0; m[7] = 0.0; m[11] = 0.0; m[15] = 1.0;
-}
-
-// constant velocity T_prev * (T_prev2^-1 * T_prev) of the orthonormalised poses; one processed pose: that pose; none: the identity
-void track_guess(const sm_ctx *s, float *g)
-{
-    if (s->trk_n_hist == 0) {
-        for (int e = 0; e < 16; ++e) g[e] = (e % 5 == 0) ? 1.0f : 0.0f;
-        return;
-    }
-    if (s->trk_n_hist == 1) { memcpy(g, s->trk_hist[0], 64); return; }
-    double p[16], p2[16], p2i[16], rel[16], out[16];
-    for (int e = 0; e < 16; ++e) { p[e] = s->trk_hist[0][e]; p2[e] = s->trk_hist[1][e]; }
-    orthonormalize_d(p);
-    orthonormalize_d(p2);
-    rigid_inv_d(p2, p2i);
-    mul_rigid_d(p2i, p, rel);
-    mul_rigid_d(p, rel, out);
-    for (int e = 0; e < 16; ++e) g[e] = (float)out[e];
-}
-
-int track_alloc(sm_ctx *s)
-{
-    if (s->d_trk) return SM_OK;
-    const size_t P = (size_t)s->P;
-    Dev<uint16_t> depth; Dev<float4> v, n; Dev<uint64_t> key; Dev<int32_t> pred; Dev<double> part; Dev<TrackState> d;
-    Host<TrackState> h;
-    int rc;
-    if ((rc = dalloc(depth, P)) || (rc = dalloc(v, P)) || (rc = dalloc(n, P)) || (rc = dalloc(key, P)) || (rc = dalloc(pred, P)) ||
-        (rc = dalloc(part, (size_t)TRACK_NSYS * TRACK_MAX_PARTS)) || (rc = dalloc(d, 1)))
-        return rc;
-    HIPCK(hipHostMalloc(h.put(), sizeof(TrackState)));
-    s->d_trk_depth = std::move(depth); s->d_trk_v = std::move(v); s->d_trk_n = std::move(n); s->d_trk_key = std::move(key);
-    s->d_trk_pred = std::move(pred); s->d_trk_part = std::move(part); s->h_trk = std::move(h);
-    s->d_trk = std::move(d);              // last: it marks the set complete
-    return SM_OK;
-}
-
-int track_check(sm_ctx *s, const char *fn)
-{
-    if (s->ss_on) { g_err = std::string(fn) + ": a sharded context holds only its rank's surfels; tracking is not supported"; return SM_E_UNSUPPORTED; }
-    if (s->pending_cull) { g_err = std::string(fn) + " between sm_stage_conflict and sm_stage_cull"; return SM_E_ARG; }
-    return SM_OK;
-}
-
-TrackParams track_params(const sm_ctx *s, const sm_track_params &p)
-{
-    TrackParams tp;
-    memset(&tp, 0, sizeof tp);
-    double prev[16], inv[16];
-    for (int e = 0; e < 16; ++e) prev[e] = s->trk_n_hist ? (double)s->trk_hist[0][e] : ((e % 5 == 0) ? 1.0 : 0.0);
-    rigid_inv_d(prev, inv);
-    for (int e = 0; e < 16; ++e) tp.tinv_prev[e] = (float)inv[e];
-    for (int k = 0; k < 3; ++k) tp.c[k] = prev[12 + k];
-    const sm_config &c = s->cfg;
-    tp.fx = c.fx; tp.fy = c.fy; tp.cx = c.cx; tp.cy = c.cy;
-    tp.inv_fx = (float)(1.0 / (double)c.fx);
-    tp.inv_fy = (float)(1.0 / (double)c.fy);
-    tp.near_clip = c.near_clip; tp.far_clip = c.far_clip; tp.stereo_border = c.stereo_border;
-    tp.W = s->W; tp.H = s->H;
-    tp.stride = p.pixel_stride;
-    tp.ni = (s->W + p.pixel_stride - 1) / p.pixel_stride;
-    tp.nj = (s->H + p.pixel_stride - 1) / p.pixel_stride;
-    tp.n = tp.ni * tp.nj;
-    tp.dist = p.dist_thresh;
-    tp.cos_angle = (float)std::cos((double)p.angle_thresh * (3.14159265358979323846 / 180.0));
-    tp.min_inliers = (uint32_t)p.min_inliers;
-    tp.degenerate_bound = SM_TRACK_DEGENERATE_BOUND;
-    tp.max_iters = p.max_iters;
-    tp.nb = (int)std::min<long>(TRACK_MAX_PARTS, std::max<long>(1, ((long)tp.n + TRACK_BLOCK * 4 - 1) / (TRACK_BLOCK * 4)));
-    return tp;
-}
-
-int track_event(sm_ctx *s, size_t i)
-{
-    if (!s->trk_timed) return SM_OK;
-    while (s->trk_ev.size() <= i) {
-        Event e;
-        HIPCK(hipEventCreate(e.put()));
-        s->trk_ev.push_back(std::move(e));
-    }
-    HIPCK(hipEventRecord(s->trk_ev[i], s->stream));
-    return SM_OK;
-}
-
-// the state, the prediction at T_prev and the vertex / normal stage, enqueued (the model's state has been pulled)
-int track_prepare(sm_ctx *s, const uint16_t *depth_mm, const TrackParams &tp, const float *T0, const float *guess, bool ortho)
-{
-    const size_t P = (size_t)s->P;
-    TrackState &h = *s->h_trk;
-    memset(&h, 0, sizeof h);
-    for (int e = 0; e < 16; ++e) { h.T[e] = T0[e]; h.guess[e] = guess[e]; }
-    if (ortho) orthonormalize_d(h.T);
-    h.status = TRACK_OK;
-    HIPCK(hipMemcpyAsync(s->d_trk, &h, sizeof h, hipMemcpyHostToDevice, s->stream));
-    HIPCK(hipMemcpyAsync(s->d_trk_depth, depth_mm, P * 2, hipMemcpyHostToDevice, s->stream));
-    const char *te = std::getenv("SM_TRACK_TIMING");
-    s->trk_timed = te && te[0] == '1';
-    s->trk_ev_iters = 0;
-    int rc;
-    if ((rc = track_event(s, 0))) return rc;
-    const unsigned pblocks = (unsigned)((P + 255) / 256);
-    hipLaunchKernelGGL(k_fill_keys, dim3(pblocks), dim3(256), 0, s->stream, s->d_trk_key, (int)P);
-    const uint32_t slots = s->h_state->count;
-    if (slots)
-        hipLaunchKernelGGL(k_track_splat, dim3((slots + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, s->d_alive, tp,
-                           s->d_trk_key, s->d_trk);
-    hipLaunchKernelGGL(k_track_resolve, dim3(pblocks), dim3(256), 0, s->stream, s->d_trk_key, (int)P, s->d_trk_pred);
-    if ((rc = track_event(s, 1))) return rc;
-    hipLaunchKernelGGL(k_track_vertex, dim3((tp.n + 255) / 256), dim3(256), 0, s->stream, s->d_trk_depth, s->d_xs, s->d_ys, tp,
-                       s->d_trk_v, s->d_trk_n);
-    HIPCK(hipGetLastError());
-    return track_event(s, 2);
-}
-
-int track_iteration(sm_ctx *s, const TrackParams &tp, int sum_only)
-{
-    hipLaunchKernelGGL(k_track_reduce, dim3(tp.nb), dim3(TRACK_BLOCK), 0, s->stream, s->M, s->d_state, tp, s->d_trk_v, s->d_trk_n,
-                       s->d_trk_pred, s->d_trk, s->d_trk_part);
-    int rc;
-    if ((rc = track_event(s, 3 + 2 * (size_t)s->trk_ev_iters))) return rc;
-    hipLaunchKernelGGL(k_track_solve, dim3(1), dim3(256), 0, s->stream, tp, s->d_trk_part, s->d_trk, sum_only);
-    HIPCK(hipGetLastError());
-    if ((rc = track_event(s, 4 + 2 * (size_t)s->trk_ev_iters))) return rc;
-    s->trk_ev_iters++;
-    return SM_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int sm_default_track_params(sm_track_params *p)
-{
-    if (!p) return SM_E_ARG;
-    p->max_iters = 15;
-    p->dist_thresh = 0.3f;
-    p->angle_thresh = 30.0f;
-    p->min_inliers = 1000;
-    p->pixel_stride = 1;
-    return SM_OK;
-}
-
-int sm_track_frame(sm_ctx *s, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params, float *pose16_out,
-                   sm_track_info *info)
-{
-    if (!s || !depth_mm || !pose16_out) { g_err = "sm_track_frame: null argument"; return SM_E_ARG; }
-    sm_track_params p;
-    if (params) p = *params;
-    else sm_default_track_params(&p);
-    if (p.max_iters < 1 || p.max_iters > SM_TRACK_MAX_ITERS || !(p.dist_thresh > 0.0f) || !std::isfinite(p.dist_thresh) ||
-        !(p.angle_thresh > 0.0f && p.angle_thresh <= 180.0f) || p.min_inliers < 0 || p.pixel_stride < 1 ||
-        p.pixel_stride > std::min(s->W, s->H)) {
-        g_err = "sm_track_frame: parameter out of range (max_iters 1..100, dist_thresh > 0, angle_thresh in (0, 180], "
-                "min_inliers >= 0, pixel_stride 1..min(W, H))";
-        return SM_E_ARG;
-    }
-    int rc = track_check(s, "sm_track_frame");
-    if (rc) return rc;
-    HIPCK(hipSetDevice(s->cfg.device));
-    if ((rc = pull_state(s))) return rc;                      // waits for frames in flight: the model after the last frame
-    float g[16];
-    if (guess16) memcpy(g, guess16, 64);
-    else track_guess(s, g);
-    sm_track_info inf;
-    memset(&inf, 0, sizeof inf);
-    memcpy(inf.guess, g, 64);
-    const uint32_t live = s->h_state->count - s->h_state->garbage;
-    if (s->trk_n_hist == 0 || live == 0) {
-        inf.status = SM_TRACK_NO_MODEL;
-        memcpy(pose16_out, g, 64);
-        if (info) *info = inf;
-        return SM_OK;
-    }
-    if ((rc = track_alloc(s))) return rc;
-    const TrackParams tp = track_params(s, p);
-    if ((rc = track_prepare(s, depth_mm, tp, g, g, true))) return rc;    // (iterates from the orthonormalised guess)
-    for (int it = 0; it < p.max_iters; ++it)
-        if ((rc = track_iteration(s, tp, 0))) return rc;
-    HIPCK(hipMemcpyAsync(s->h_trk, s->d_trk, sizeof(TrackState), hipMemcpyDeviceToHost, s->stream));
-    HIPCK(hipStreamSynchronize(s->stream));                   // the one wait of a tracked frame
-    const TrackState &h = *s->h_trk;
-    for (int e = 0; e < 16; ++e) pose16_out[e] = (float)h.T[e];
-    inf.status = h.status;
-    inf.iterations = h.iterations;
-    inf.inliers = h.inliers;
-    inf.rmse = (float)h.rmse;
-    if (info) *info = inf;
-    return SM_OK;
-}
-
-int sm_track_debug(sm_ctx *s, const uint16_t *depth_mm, const float *pose16_eval, int32_t *pred_slot, double *sys29)
-{
-    if (!s || !depth_mm || !pose16_eval) { g_err = "sm_track_debug: null argument"; return SM_E_ARG; }
-    int rc = track_check(s, "sm_track_debug");
-    if (rc) return rc;
-    HIPCK(hipSetDevice(s->cfg.device));
-    if ((rc = pull_state(s))) return rc;
-    if ((rc = track_alloc(s))) return rc;
-    sm_track_params p;
-    sm_default_track_params(&p);
-    const TrackParams tp = track_params(s, p);
-    if ((rc = track_prepare(s, depth_mm, tp, pose16_eval, pose16_eval, false))) return rc;   // (the pose as given)
-    if ((rc = track_iteration(s, tp, 1))) return rc;
-    if (pred_slot) HIPCK(hipMemcpyAsync(pred_slot, s->d_trk_pred, (size_t)s->P * 4, hipMemcpyDeviceToHost, s->stream));
-    HIPCK(hipMemcpyAsync(s->h_trk, s->d_trk, sizeof(TrackState), hipMemcpyDeviceToHost, s->stream));
-    HIPCK(hipStreamSynchronize(s->stream));
-    if (sys29) memcpy(sys29, s->h_trk->sys, TRACK_NSYS * sizeof(double));
-    return SM_OK;
-}
-
-// Diagnostic, deliberately not part of include/sm_c_api.h (tools/track_probe.py): device times of the last sm_track_frame /
-// sm_track_debug call made with SM_TRACK_TIMING=1, in ms: ms[0] prediction (key fill, splat, resolve), ms[1] vertex stage, then per
-// launched iteration its reduction and its solve (a no-op once converged); *n = values written (0 if that call was not timed).
-int sm_debug_track_stats(sm_ctx *s, float *ms, int cap, int *n)
-{
-    if (!s || !ms || !n) return SM_E_ARG;
-    HIPCK(hipSetDevice(s->cfg.device));
-    HIPCK(hipStreamSynchronize(s->stream));
-    *n = 0;
-    if (!s->trk_timed) return SM_OK;
-    const int total = 2 + 2 * s->trk_ev_iters;
-    for (int i = 0; i < total && i < cap; ++i) {
-        HIPCK(hipEventElapsedTime(&ms[i], s->trk_ev[i], s->trk_ev[i + 1]));
-        *n = i + 1;
-    }
     return SM_OK;
 }
 
@@ -2379,7 +1566,7 @@ int sm_stage_splat(sm_ctx *s, const float *pose16, int32_t time, float depth_cut
     HIPCK(hipMemsetAsync(&s->d_state->visible_count, 0, 4, s->stream));
     s->n_compact_part = 0;                       // k_splat counts with an atomic; no k_compact partials to fold in
     s->lazy_part_live = false;
-    hipLaunchKernelGGL(k_fill_keys, dim3((s->P + 255) / 256), dim3(256), 0, s->stream, s->d_keyT, s->P);
+    fill_keys(s, s->d_keyT, s->P);
     HIPCK(hipGetLastError());
     const int grid = (int)std::min<uint64_t>(std::max<uint64_t>(((uint64_t)s->h_state->count + 255) / 256, 1), MAX_GRID);
     hipLaunchKernelGGL(k_splat, dim3(grid), dim3(256), 0, s->stream, s->M, s->d_state, fp, s->d_keyT);
@@ -2491,89 +1678,20 @@ int sm_read_frame_log(sm_ctx *s, sm_frame_log *out, uint32_t n, uint32_t *writte
     return SM_OK;
 }
 
-void *sm_device_alloc(sm_ctx *s, size_t bytes)
+int sm_debug_slow_frames(sm_ctx *s, uint32_t *n)
 {
-    if (!s) return nullptr;
-    if (hipSetDevice(s->cfg.device) != hipSuccess) return nullptr;
-    Dev<void> p;
-    if (hipMalloc(p.put(), std::max<size_t>(bytes, 1)) != hipSuccess) { g_err = "sm_device_alloc: hipMalloc failed"; return nullptr; }
-    s->user_allocs.push_back(std::move(p));
-    return s->user_allocs.back();
-}
-
-int sm_device_free(sm_ctx *s, void *p)
-{
-    if (!s || !p) return SM_E_ARG;
-    auto it = std::find(s->user_allocs.begin(), s->user_allocs.end(), p);
-    if (it == s->user_allocs.end()) return SM_E_ARG;
-    (void)it->release();
-    s->user_allocs.erase(it);
+    if (!s || !n) return SM_E_ARG;
     HIPCK(hipSetDevice(s->cfg.device));
-    HIPCK(hipStreamSynchronize(s->stream));
-    HIPCK(hipFree(p));
-    return SM_OK;
-}
-
-int sm_device_upload(sm_ctx *s, void *dst_device, const void *src_host, size_t bytes)
-{
-    if (!s || !dst_device || !src_host) return SM_E_ARG;
-    HIPCK(hipSetDevice(s->cfg.device));
-    HIPCK(hipMemcpyAsync(dst_device, src_host, bytes, hipMemcpyHostToDevice, s->stream));
-    HIPCK(hipStreamSynchronize(s->stream));
-    return SM_OK;
-}
-
-int sm_export_model_device(sm_ctx *s, void **d_aos, uint32_t *n)
-{
-    if (!s || !d_aos || !n) return SM_E_ARG;
-    if (hip_runtime_conflict("sm_export_model_device")) return SM_E_HIP;     // the pointer goes to foreign code (RCCL)
-    HIPCK(hipSetDevice(s->cfg.device));
-    if (s->pending_cull) { g_err = "sm_export_model_device between sm_stage_conflict and sm_stage_cull"; return SM_E_ARG; }
-    int rc = ensure_compact(s);
+    int rc = pull_state(s);
     if (rc) return rc;
-    if ((rc = pull_state(s))) return rc;
-    const uint32_t cnt = s->h_state->count;
-    if ((rc = ensure_export(s, (size_t)std::max(cnt, 1u) * 48))) return rc;
-    if (cnt) {
-        hipLaunchKernelGGL(k_export_aos, dim3((cnt + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, (float *)s->d_export.get(), 0u, cnt);
-        HIPCK(hipGetLastError());
-        HIPCK(hipStreamSynchronize(s->stream));
-    }
-    *d_aos = s->d_export;
-    *n = cnt;
+    *n = s->h_state->slow_frames;
     return SM_OK;
 }
 
-int sm_append_model_aos_device(sm_ctx *s, const float *d_src12, uint32_t n)
+int sm_gpu_process_count(sm_ctx *s)
 {
-    if (!s || (!d_src12 && n)) return SM_E_ARG;
-    if (hip_runtime_conflict("sm_append_model_aos_device")) return SM_E_HIP;
-    HIPCK(hipSetDevice(s->cfg.device));
-    if (s->pending_cull) { g_err = "sm_append_model_aos_device between sm_stage_conflict and sm_stage_cull"; return SM_E_ARG; }
-    int rc = ensure_compact(s);
-    if (rc) return rc;
-    if ((rc = pull_state(s))) return rc;
-    const uint32_t cnt = s->h_state->count;
-    if ((uint64_t)cnt + n > s->cap) { g_err = "sm_append_model_aos_device: exceeds MAX_VERTICES"; return SM_E_CAPACITY; }
-    if (n) {
-        hipLaunchKernelGGL(k_import_aos, dim3((n + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, d_src12, cnt, n);
-        HIPCK(hipGetLastError());
-        HIPCK(hipStreamSynchronize(s->stream));
-    }
-    s->h_state->count = cnt + n;
-    s->h_state->offset = cnt;
-    if ((rc = push_state(s))) return rc;
-    if ((rc = rebuild_bounds(s, cnt, cnt + n))) return rc;
-    return pull_state(s);
-}
-
-int sm_device_download(sm_ctx *s, void *dst_host, const void *src_device, size_t bytes)
-{
-    if (!s || !dst_host || !src_device) return SM_E_ARG;
-    HIPCK(hipSetDevice(s->cfg.device));
-    HIPCK(hipMemcpyAsync(dst_host, src_device, bytes, hipMemcpyDeviceToHost, s->stream));
-    HIPCK(hipStreamSynchronize(s->stream));
-    return SM_OK;
+    if (!s) return SM_E_ARG;
+    return kfd_processes_on_gpu(s->cfg.device);
 }
 
 }  // extern "C"
@@ -2587,74 +1705,7 @@ int sm_device_download(sm_ctx *s, void *dst_host, const void *src_device, size_t
 // all ranks publish the same counts.  A frame is  k_prep | k_surfel_pass | k_pass_fixup | all-reduce(min) key map |
 // k_associate_direct<shard> | all-reduce(sum) fused mask + 3 counters | k_shard_settle, all on the context's stream.
 
-namespace {
-
-struct RcclApi {
-    void *lib = nullptr;
-    ncclResult_t (*GetUniqueId)(ncclUniqueId *) = nullptr;
-    ncclResult_t (*CommInitRank)(ncclComm_t *, int, ncclUniqueId, int) = nullptr;
-    ncclResult_t (*AllReduce)(const void *, void *, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*AllGather)(const void *, void *, size_t, ncclDataType_t, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*CommCount)(const ncclComm_t, int *) = nullptr;
-    ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-    const char *(*GetErrorString)(ncclResult_t) = nullptr;
-};
-RcclApi g_rccl;
-std::mutex g_rccl_mu;
-
-int find_rccl(struct dl_phdr_info *info, size_t, void *data)
-{
-    auto *v = static_cast<std::string *>(data);
-    if (v->empty() && info->dlpi_name && std::strstr(info->dlpi_name, "librccl")) *v = info->dlpi_name;
-    return 0;
-}
-
-// RCCL is bound at run time: the copy already mapped into the process if there is one (a PyTorch process has its own
-// bundled librccl; two RCCLs would work but the one that is there already shares the HIP runtime for certain), else ROCm's.
-int load_rccl()
-{
-    std::lock_guard<std::mutex> lk(g_rccl_mu);
-    if (g_rccl.lib) return SM_OK;
-    std::string loaded;
-    dl_iterate_phdr(find_rccl, &loaded);
-    void *h = nullptr;
-    // SM_RCCL_LIB: an explicit copy (surfelmapping_amd.capi names PyTorch's bundled one when it pre-loaded PyTorch's HIP
-    // runtime: RCCL and the runtime then come from the same build)
-    if (const char *e = std::getenv("SM_RCCL_LIB")) { if (e[0]) { h = dlopen(e, RTLD_NOW | RTLD_LOCAL); if (h) loaded = e; } }
-    if (!h && !loaded.empty()) h = dlopen(loaded.c_str(), RTLD_NOW | RTLD_NOLOAD);
-    if (!h) h = dlopen("librccl.so.1", RTLD_NOW | RTLD_LOCAL);
-    if (!h) h = dlopen("librccl.so", RTLD_NOW | RTLD_LOCAL);
-    if (!h) { g_err = std::string("RCCL not found: ") + (dlerror() ? dlerror() : "dlopen failed"); return SM_E_UNSUPPORTED; }
-    g_rccl.GetUniqueId = reinterpret_cast<decltype(g_rccl.GetUniqueId)>(dlsym(h, "ncclGetUniqueId"));
-    g_rccl.CommInitRank = reinterpret_cast<decltype(g_rccl.CommInitRank)>(dlsym(h, "ncclCommInitRank"));
-    g_rccl.AllReduce = reinterpret_cast<decltype(g_rccl.AllReduce)>(dlsym(h, "ncclAllReduce"));
-    g_rccl.AllGather = reinterpret_cast<decltype(g_rccl.AllGather)>(dlsym(h, "ncclAllGather"));
-    g_rccl.CommCount = reinterpret_cast<decltype(g_rccl.CommCount)>(dlsym(h, "ncclCommCount"));
-    g_rccl.CommDestroy = reinterpret_cast<decltype(g_rccl.CommDestroy)>(dlsym(h, "ncclCommDestroy"));
-    g_rccl.GetErrorString = reinterpret_cast<decltype(g_rccl.GetErrorString)>(dlsym(h, "ncclGetErrorString"));
-    if (!g_rccl.GetUniqueId || !g_rccl.CommInitRank || !g_rccl.AllReduce || !g_rccl.AllGather || !g_rccl.CommCount || !g_rccl.CommDestroy) {
-        g_err = "RCCL: missing symbols in " + (loaded.empty() ? std::string("librccl.so") : loaded);
-        return SM_E_UNSUPPORTED;
-    }
-    g_rccl.lib = h;
-    return SM_OK;
-}
-
-int rccl_collective(void *user, const void *send, void *recv, size_t count, int op, void *stream)
-{
-    sm_ctx *s = static_cast<sm_ctx *>(user);
-    const ncclResult_t r = op == SM_COLL_GATHER
-        ? g_rccl.AllGather(send, recv, count, ncclUint64, static_cast<ncclComm_t>(s->ss_comm), static_cast<hipStream_t>(stream))
-        : g_rccl.AllReduce(send, recv, count, ncclUint64, op == SM_COLL_MIN ? ncclMin : ncclSum,
-                           static_cast<ncclComm_t>(s->ss_comm), static_cast<hipStream_t>(stream));
-    if (r != ncclSuccess) {
-        g_err = std::string(op == SM_COLL_GATHER ? "ncclAllGather: " : "ncclAllReduce: ") + (g_rccl.GetErrorString ? g_rccl.GetErrorString(r) : "failed");
-        return SM_E_HIP;
-    }
-    return SM_OK;
-}
-
-int ss_collective(sm_ctx *s, const void *send, void *recv, size_t count, int op)
+int sm_impl::ss_collective(sm_ctx *s, const void *send, void *recv, size_t count, int op)
 {
     if (!s->ss_coll) {
         if (s->ss_world == 1) {          // one rank and no communicator: reduction and gather are the identity
@@ -2668,6 +1719,8 @@ int ss_collective(sm_ctx *s, const void *send, void *recv, size_t count, int op)
     if (rc && g_err.empty()) g_err = "sharded stream: the collective callback failed";
     return rc;
 }
+
+namespace {
 
 // Physical compaction between two frames of a sharded stream (k_shard_* in sm_kernels.h); enqueue only.
 int ss_compact(sm_ctx *s)
@@ -2698,22 +1751,6 @@ int ss_compact(sm_ctx *s)
 }  // namespace
 
 extern "C" {
-
-int sm_debug_slow_frames(sm_ctx *s, uint32_t *n)
-{
-    if (!s || !n) return SM_E_ARG;
-    HIPCK(hipSetDevice(s->cfg.device));
-    int rc = pull_state(s);
-    if (rc) return rc;
-    *n = s->h_state->slow_frames;
-    return SM_OK;
-}
-
-int sm_gpu_process_count(sm_ctx *s)
-{
-    if (!s) return SM_E_ARG;
-    return kfd_processes_on_gpu(s->cfg.device);
-}
 
 int sm_shard_stream_configure(sm_ctx *s, int rank, int world)
 {
@@ -2747,59 +1784,6 @@ int sm_shard_set_collective(sm_ctx *s, sm_collective_fn fn, void *user)
 {
     if (!s || !(s->ss_on || s->rig_on)) { g_err = "sm_shard_set_collective: call sm_shard_stream_configure or sm_rig_configure first"; return SM_E_ARG; }
     s->ss_coll = fn; s->ss_user = user;
-    return SM_OK;
-}
-
-int sm_shard_rccl_unique_id(void *out128)
-{
-    if (!out128) return SM_E_ARG;
-    int rc = load_rccl();
-    if (rc) return rc;
-    ncclUniqueId id;
-    static_assert(sizeof(ncclUniqueId) == 128, "ncclUniqueId is 128 bytes");
-    const ncclResult_t r = g_rccl.GetUniqueId(&id);
-    if (r != ncclSuccess) { g_err = "ncclGetUniqueId failed"; return SM_E_HIP; }
-    memcpy(out128, &id, 128);
-    return SM_OK;
-}
-
-int sm_shard_rccl_init(sm_ctx *s, const void *id128)
-{
-    if (!s || !id128 || !(s->ss_on || s->rig_on)) { g_err = "sm_shard_rccl_init: call sm_shard_stream_configure or sm_rig_configure first"; return SM_E_ARG; }
-    HIPCK(hipSetDevice(s->cfg.device));
-    if (hip_runtime_conflict("sm_shard_rccl_init")) return SM_E_HIP;
-    int rc = load_rccl();
-    if (rc) return rc;
-    ncclUniqueId id;
-    memcpy(&id, id128, 128);
-    ncclComm_t comm = nullptr;
-    const ncclResult_t r = g_rccl.CommInitRank(&comm, s->ss_world, id, s->ss_rank);
-    if (r != ncclSuccess) { g_err = std::string("ncclCommInitRank: ") + (g_rccl.GetErrorString ? g_rccl.GetErrorString(r) : "failed"); return SM_E_HIP; }
-    s->ss_comm = comm;
-    s->ss_coll = rccl_collective; s->ss_user = s;
-    return SM_OK;
-}
-
-int sm_shard_rccl_nranks(sm_ctx *s)
-{
-    if (!s) return SM_E_ARG;
-    if (!s->ss_comm || !g_rccl.CommCount) { g_err = "sm_shard_rccl_nranks: no RCCL communicator on this context"; return SM_E_ARG; }
-    int n = 0;
-    const ncclResult_t r = g_rccl.CommCount(static_cast<ncclComm_t>(s->ss_comm), &n);
-    if (r != ncclSuccess) { g_err = "ncclCommCount failed"; return SM_E_HIP; }
-    return n;
-}
-
-int sm_shard_rccl_finalize(sm_ctx *s)
-{
-    if (!s) return SM_E_ARG;
-    if (s->ss_comm && g_rccl.CommDestroy) {
-        HIPCK(hipSetDevice(s->cfg.device));
-        HIPCK(hipStreamSynchronize(s->stream));
-        (void)g_rccl.CommDestroy(static_cast<ncclComm_t>(s->ss_comm));
-    }
-    s->ss_comm = nullptr;
-    if (s->ss_coll == rccl_collective) { s->ss_coll = nullptr; s->ss_user = nullptr; }
     return SM_OK;
 }
 
@@ -2916,211 +1900,6 @@ int sm_shard_export_dense_device(sm_ctx *s, const float **d_out12, uint32_t *cou
     HIPCK(hipStreamSynchronize(s->stream));
     *d_out12 = (const float *)s->d_export.get();
     *count = n;
-    return SM_OK;
-}
-
-
-// ---- BASELINE configs[4]: a rig of `world` cameras, one per rank, consolidated into a single GlobalModel ----
-// Frames go through the ordinary entry points (no collective).  sm_rig_consolidate is the definition of DESIGN.md 6 --
-// union in rank order, cleanPoints against every camera's latest view in rank order -- entirely on the device: the views,
-// the slice sizes, the per-view conflict totals and the cleaned slices cross the ranks through the installed collective
-// (RCCL's all-reduce, or a callback); an all-gather is the sum of buffers that are zero outside the sender's part.
-
-int sm_rig_configure(sm_ctx *s, int rank, int world)
-{
-    if (!s || world < 1 || rank < 0 || rank >= world) return SM_E_ARG;
-    if (s->ss_on) { g_err = "sm_rig_configure: the context is configured for sharding"; return SM_E_ARG; }
-    s->rig_on = true; s->ss_rank = rank; s->ss_world = world;
-    return SM_OK;
-}
-
-namespace {
-// The exchanges of a rig consolidation.  Every rank contributes a row of four words -- live surfels of its slice, conflicts of
-// the view at hand, a status word, a spare -- through an all-gather, so that (a) all ranks see all counts and (b) a rank whose
-// LOCAL step failed says so in the very exchange the others are waiting in: everybody then leaves together with an error
-// instead of one rank returning early and the rest blocking inside RCCL.
-struct RigXchg {
-    sm_ctx *s; int W, r;
-    Dev<unsigned long long> d_cnt;                 // [W][4]
-    std::vector<unsigned long long> h;
-    RigXchg(sm_ctx *s_, int W_, int r_) : s(s_), W(W_), r(r_), h((size_t)W_ * 4) {}
-    // returns 0, this rank's own failure code, or SM_E_HIP when another rank failed
-    int run(unsigned long long count, unsigned long long conflicts, int status)
-    {
-        unsigned long long row[4] = {count, conflicts, (unsigned long long)(long long)status, 0ull};
-        if (hipMemcpyAsync(d_cnt + (size_t)r * 4, row, 32, hipMemcpyHostToDevice, s->stream) != hipSuccess) return SM_E_HIP;
-        int rc = ss_collective(s, d_cnt + (size_t)r * 4, d_cnt, 4, SM_COLL_GATHER);
-        if (rc) return rc;
-        if (hipMemcpyAsync(h.data(), d_cnt, 32 * (size_t)W, hipMemcpyDeviceToHost, s->stream) != hipSuccess) return SM_E_HIP;
-        if (hipStreamSynchronize(s->stream) != hipSuccess) return SM_E_HIP;
-        if (status) return status;
-        for (int q = 0; q < W; ++q)
-            if (h[(size_t)q * 4 + 2]) { g_err = "sm_rig_consolidate: rank " + std::to_string(q) + " failed (code " + std::to_string((long long)h[(size_t)q * 4 + 2]) + "); all ranks abandon the consolidation"; return SM_E_HIP; }
-        return SM_OK;
-    }
-    unsigned long long count(int q) const { return h[(size_t)q * 4]; }
-    unsigned long long conflicts(int q) const { return h[(size_t)q * 4 + 1]; }
-};
-}  // namespace
-
-// The single GlobalModel DURING a run ("all-gather of per-GPU new-surfel lists into the single GlobalModel, followed by
-// one conflict pass of every camera's depth against the union").  One step, collective:
-//   1. every rank's NEW surfels -- created since its previous step, still alive, in creation order (the model is kept in creation
-//      order, so they are a suffix of the compacted model) -- are all-gathered and appended to `global` in rank order
-//      (GlobalModel::concatenate's order for W append lists), on every rank;
-//   2. the cameras' latest views are all-gathered and `global` is cleaned against each of them in rank order with
-//      SurfelMapping::cleanPoints (src/SurfelMapping.cpp:496-532) -- replicated: every rank holds the same GlobalModel, so the W*H
-//      conflict cap and the id-0 rule need no exchange, and the work runs on `global`'s own stream, next to the camera's frames.
-// The camera's own slice is not touched (its fusion goes on as if alone); what an older surfel of it becomes later -- fused
-// updates, its own culls -- reaches `global` only through the views' conflict tests.  sm_rig_consolidate above is the exact
-// end-of-run union; this is the incremental model, defined by the same reference operations (tests/test_rig.py states it on
-// oracles).
-int sm_rig_consolidate_step(sm_ctx *s, const uint16_t *depth_mm, const uint8_t *semantic, const float *pose16, sm_ctx *global,
-                            uint32_t *new_surfels, uint32_t *global_count)
-{
-    if (!s || !depth_mm || !semantic || !pose16 || !global || !s->rig_on) { g_err = "sm_rig_consolidate_step: bad argument (sm_rig_configure first)"; return SM_E_ARG; }
-    HIPCK(hipSetDevice(s->cfg.device));
-    if (hip_runtime_conflict("sm_rig_consolidate_step")) return SM_E_HIP;
-    const int W = s->ss_world, r = s->ss_rank;
-    const size_t P = (size_t)s->P;
-    const size_t off_sem = 2 * P, off_pose = (3 * P + 7) / 8 * 8, row = off_pose + 64;
-    Dev<uint8_t> d_views;
-    Dev<float> d_lists;
-    Dev<uint32_t> d_first;
-    RigXchg x(s, W, r);
-    HIPCK(hipMalloc(x.d_cnt.put(), 32 * (size_t)W));
-    // ---- local: compact (slots become positions), find the first surfel newer than the previous step, stage the view
-    int st = ensure_compact(s);
-    if (!st) st = pull_state(s);
-    uint32_t cnt = 0, first = 0;
-    if (!st) {
-        cnt = s->h_state->count;
-        first = cnt;
-        if (hipMalloc(d_first.put(), 4) != hipSuccess || hipMemsetAsync(d_first, 0xFF, 4, s->stream) != hipSuccess) st = SM_E_HIP;
-        if (!st && cnt) {
-            hipLaunchKernelGGL(k_first_newer, dim3(std::min<uint32_t>((cnt + 255u) / 256u, 1024u)), dim3(256), 0, s->stream, s->M, s->d_state, s->rig_last_time, d_first);
-            uint32_t f = 0xFFFFFFFFu;
-            if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&f, d_first, 4, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
-                hipStreamSynchronize(s->stream) != hipSuccess) st = SM_E_HIP;
-            else first = std::min(f, cnt);
-        }
-    }
-    const uint32_t n_new = st ? 0u : cnt - first;
-    if (!st && hipMalloc(d_views.put(), row * (size_t)W) != hipSuccess) { g_err = "sm_rig_consolidate_step: out of device memory for the views"; st = SM_E_HIP; }
-    if (!st && (hipMemsetAsync(d_views + row * r, 0, row, s->stream) != hipSuccess ||
-                hipMemcpyAsync(d_views + row * r, depth_mm, 2 * P, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
-                hipMemcpyAsync(d_views + row * r + off_sem, semantic, P, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
-                hipMemcpyAsync(d_views + row * r + off_pose, pose16, 64, hipMemcpyHostToDevice, s->stream) != hipSuccess)) st = SM_E_HIP;
-    int rc = x.run(n_new, 0ull, st);
-    if (rc) return rc;
-    // ---- 1. the new-surfel lists, all-gathered (padded to the longest) and appended to `global` in rank order
-    unsigned long long T = 0, maxn = 0;
-    std::vector<unsigned long long> nn((size_t)W);
-    for (int q = 0; q < W; ++q) { nn[(size_t)q] = x.count(q); T += nn[(size_t)q]; maxn = std::max(maxn, nn[(size_t)q]); }
-    if (new_surfels) *new_surfels = (uint32_t)T;
-    st = SM_OK;
-    if (T && hipMalloc(d_lists.put(), (size_t)maxn * 48 * (size_t)W) != hipSuccess) { g_err = "sm_rig_consolidate_step: out of device memory for the lists"; st = SM_E_HIP; }
-    if ((rc = x.run(n_new, 0ull, st))) return rc;
-    if (T) {
-        if (n_new) hipLaunchKernelGGL(k_export_aos, dim3((n_new + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, d_lists + (size_t)r * maxn * 12, first, n_new);
-        if (hipGetLastError() != hipSuccess) return SM_E_HIP;
-        if ((rc = ss_collective(s, d_lists + (size_t)r * maxn * 12, d_lists, (size_t)maxn * 6, SM_COLL_GATHER))) return rc;
-    }
-    if ((rc = ss_collective(s, d_views + row * r, d_views, row / 8, SM_COLL_GATHER))) return rc;
-    std::vector<float> poses((size_t)W * 16);
-    for (int v = 0; v < W; ++v)
-        if (hipMemcpyAsync(&poses[(size_t)v * 16], d_views + row * v + off_pose, 64, hipMemcpyDeviceToHost, s->stream) != hipSuccess) return SM_E_HIP;
-    if (hipStreamSynchronize(s->stream) != hipSuccess) return SM_E_HIP;
-    for (int q = 0; q < W; ++q)
-        if (nn[(size_t)q] && (rc = sm_append_model_aos_device(global, d_lists + (size_t)q * maxn * 12, (uint32_t)nn[(size_t)q]))) return rc;
-    // ---- 2. the union cleaned against every camera's latest view, in rank order (the same work on every rank)
-    for (int v = 0; v < W; ++v)
-        if ((rc = clean_points_device(global, reinterpret_cast<const uint16_t *>(d_views + row * v), d_views + row * v + off_sem,
-                                      &poses[(size_t)v * 16], 1))) return rc;
-    if (global_count) *global_count = global->counts.count;
-    s->rig_last_time = (float)(s->tick - 1);           // every surfel created so far carries a time stamp <= tick - 1
-    return SM_OK;
-}
-
-int sm_rig_consolidate(sm_ctx *s, const uint16_t *depth_mm, const uint8_t *semantic, const float *pose16, sm_ctx *global,
-                       uint32_t *view_conflicts, uint32_t *total_out)
-{
-    if (!s || !depth_mm || !semantic || !pose16 || !global || !s->rig_on) { g_err = "sm_rig_consolidate: bad argument (sm_rig_configure first)"; return SM_E_ARG; }
-    HIPCK(hipSetDevice(s->cfg.device));
-    if (hip_runtime_conflict("sm_rig_consolidate")) return SM_E_HIP;
-    const int W = s->ss_world, r = s->ss_rank;
-    const size_t P = (size_t)s->P;
-    const size_t off_sem = 2 * P, off_pose = (3 * P + 7) / 8 * 8, row = off_pose + 64;        // bytes of one view (a multiple of 8)
-    Dev<uint8_t> d_views;
-    Dev<float> d_union;
-    RigXchg x(s, W, r);
-    // the exchange buffer first: without it this rank cannot even tell the others that it failed
-    HIPCK(hipMalloc(x.d_cnt.put(), 32 * (size_t)W));
-    // ---- local, fallible: settle the stream's pending work, stage this camera's latest view
-    int st = finalize_if_pending(s);
-    if (!st) st = pull_state(s);
-    if (!st && hipMalloc(d_views.put(), row * (size_t)W) != hipSuccess) { g_err = "sm_rig_consolidate: out of device memory for the views"; st = SM_E_HIP; }
-    if (!st && (hipMemsetAsync(d_views + row * r, 0, row, s->stream) != hipSuccess ||
-                hipMemcpyAsync(d_views + row * r, depth_mm, 2 * P, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
-                hipMemcpyAsync(d_views + row * r + off_sem, semantic, P, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
-                hipMemcpyAsync(d_views + row * r + off_pose, pose16, 64, hipMemcpyHostToDevice, s->stream) != hipSuccess)) {
-        g_err = "sm_rig_consolidate: staging the view failed"; st = SM_E_HIP;
-    }
-    int rc = x.run(st ? 0ull : s->counts.count, 0ull, st);
-    if (rc) return rc;
-    // ---- 1. every rank learns every camera's latest view: all-gather, in place (3 bytes per pixel and camera)
-    if ((rc = ss_collective(s, d_views + row * r, d_views, row / 8, SM_COLL_GATHER))) return rc;
-    std::vector<float> poses((size_t)W * 16);
-    st = SM_OK;
-    for (int v = 0; v < W && !st; ++v)
-        if (hipMemcpyAsync(&poses[(size_t)v * 16], d_views + row * v + off_pose, 64, hipMemcpyDeviceToHost, s->stream) != hipSuccess) st = SM_E_HIP;
-    if (!st && hipStreamSynchronize(s->stream) != hipSuccess) st = SM_E_HIP;
-    // ---- 2. the union cleaned against every view, in rank order: each rank cleans ITS slice (the test is per surfel and view)
-    for (int v = 0; v < W; ++v) {
-        int first = -1;
-        for (int q = 0; q < W && first < 0; ++q) if (x.count(q) > 0) first = q;
-        unsigned long long view_total = 0;
-        bool hook_ran = false;
-        // Between the conflict test and the cull the ranks exchange their conflict counts: at most W*H conflicts take effect per
-        // view, in the surfel order of the UNION (src/GlobalModel.cpp:54-57) -- slices are concatenated in rank order, so this
-        // rank's share is what the lower ranks left of the W*H, and "the first `share` conflicts of my slice" is exactly the rule
-        // the single-model cull applies with that cap.
-        const std::function<long long(uint32_t)> hook = [&](uint32_t local) -> long long {
-            hook_ran = true;
-            const int e = x.run(s->counts.count, local, SM_OK);
-            if (e) return e;
-            unsigned long long before = 0;
-            for (int q = 0; q < W; ++q) { if (q < r) before += x.conflicts(q); view_total += x.conflicts(q); }
-            if (!s->cfg.conflict_cap) return 0xFFFFFFFFll;
-            return before >= (unsigned long long)s->P ? 0ll : (long long)std::min<unsigned long long>(local, (unsigned long long)s->P - before);
-        };
-        // surfel id 0 never conflicts (conflict.geom:15): the exemption belongs to the rank that holds the union's first surfel
-        const int cl = st ? st : clean_points_device(s, reinterpret_cast<const uint16_t *>(d_views + row * v), d_views + row * v + off_sem,
-                                                     &poses[(size_t)v * 16], first == r ? 1 : 0, &hook);
-        // every rank makes both exchanges of a view whatever happened to it locally: a failure travels in the status word
-        if (!hook_ran) (void)x.run(0ull, 0ull, cl ? cl : SM_E_HIP);
-        if ((rc = x.run(s->counts.count, 0ull, cl))) return rc;              // the slices' sizes after this view
-        if (view_conflicts) view_conflicts[v] = (uint32_t)(s->cfg.conflict_cap ? std::min<unsigned long long>(view_total, (unsigned long long)s->P) : view_total);
-    }
-    // ---- 3. the cleaned slices, all-gathered (padded to the largest) and appended in rank order to `global` on every rank
-    unsigned long long T = 0, maxcnt = 0;
-    std::vector<unsigned long long> cnt((size_t)W);
-    for (int q = 0; q < W; ++q) { cnt[(size_t)q] = x.count(q); T += cnt[(size_t)q]; maxcnt = std::max(maxcnt, cnt[(size_t)q]); }
-    if (total_out) *total_out = (uint32_t)T;
-    d_views = {};
-    st = SM_OK;
-    if (T && hipMalloc(d_union.put(), (size_t)maxcnt * 48 * (size_t)W) != hipSuccess) { g_err = "sm_rig_consolidate: out of device memory for the union"; st = SM_E_HIP; }
-    if (!st) st = ensure_compact(s);
-    if (!st) st = pull_state(s);
-    if ((rc = x.run(cnt[(size_t)r], 0ull, st))) return rc;
-    if (T == 0) return SM_OK;
-    const uint32_t own = s->h_state->count;
-    if (own) hipLaunchKernelGGL(k_export_aos, dim3((own + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, d_union + (size_t)r * maxcnt * 12, 0u, own);
-    if (hipGetLastError() != hipSuccess) { g_err = "sm_rig_consolidate: export kernel launch failed"; return SM_E_HIP; }   // (the others' all-gather then fails or stalls: a launch failure is not recoverable)
-    if ((rc = ss_collective(s, d_union + (size_t)r * maxcnt * 12, d_union, (size_t)maxcnt * 6, SM_COLL_GATHER))) return rc;
-    if (hipStreamSynchronize(s->stream) != hipSuccess) return SM_E_HIP;
-    for (int q = 0; q < W; ++q)
-        if (cnt[(size_t)q] && (rc = sm_append_model_aos_device(global, d_union + (size_t)q * maxcnt * 12, (uint32_t)cnt[(size_t)q]))) return rc;
     return SM_OK;
 }
 

@@ -1,0 +1,304 @@
+// sm_ctx.h -- private to the core's sources, never installed: the context (struct sm_ctx), the owners of its HIP resources,
+// the error channel, the constants, and the helpers that more than one source calls.  It includes no kernels: every kernel
+// is defined and launched in exactly one source, and another source reaches it through a host helper declared below.
+//
+//   sm_api.hip       context lifecycle, the frame pipeline, the per-pass stage API, the sharded stream
+//   sm_model_io.hip  model download / upload, map files, index map, raw cloud, depth, sm_render_image, device buffers
+//   sm_view.hip      the model view (sm_render_model*)
+//   sm_track.hip     tracking (sm_track_*)
+//   sm_rccl.hip      the RCCL binding (sm_shard_rccl_*)
+//   sm_rig.hip       rig consolidation (sm_rig_*)
+#pragma once
+
+#include "../../include/sm_c_api.h"
+#include "sm_device.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <functional>
+#include <memory>
+#include <string>
+#include <utility>
+#include <vector>
+
+namespace sm { struct TrackState; }
+
+// Hidden: libsurfelmapping_hip.so exports the C ABI and the kernels' host stubs, nothing of this namespace.  Its functions are
+// defined qualified (sm_impl::name) so that the definitions keep the visibility.
+namespace sm_impl __attribute__((visibility("hidden"))) {
+
+using namespace sm;
+
+inline thread_local std::string g_err;
+
+inline void set_err(const char *what, hipError_t e, const char *file, int line)
+{
+    char buf[512];
+    snprintf(buf, sizeof buf, "%s: %s (%s:%d)", what, hipGetErrorString(e), file, line);
+    g_err = buf;
+}
+
+#define HIPCK(expr)                                              \
+    do {                                                         \
+        hipError_t e_ = (expr);                                  \
+        if (e_ != hipSuccess) {                                  \
+            set_err(#expr, e_, __FILE__, __LINE__);              \
+            return SM_E_HIP;                                     \
+        }                                                        \
+    } while (0)
+
+// Owner of one HIP handle (device or pinned host memory, an event, a stream): move-only, released by its destructor on the
+// current device (sm_destroy makes the context's device current).  It reads as the raw handle, so kernel arguments and argument
+// structs take it unchanged.  put() releases what it holds and hands out the slot for a create call, filled only on success.
+template <typename H, auto Release>
+class Own {
+public:
+    Own() = default;
+    Own(Own &&o) noexcept : h_(o.release()) {}
+    Own &operator=(Own o) noexcept { std::swap(h_, o.h_); return *this; }
+    ~Own() { if (h_) (void)Release(h_); }
+    operator H() const { return h_; }
+    H operator->() const { return h_; }
+    H get() const { return h_; }
+    H *put() { *this = Own(); return &h_; }
+    H release() { H h = h_; h_ = nullptr; return h; }
+private:
+    H h_ = nullptr;
+};
+template <typename T> using Dev = Own<T *, hipFree>;
+template <typename T> using Host = Own<T *, hipHostFree>;
+using Event = Own<hipEvent_t, hipEventDestroy>;
+using Stream = Own<hipStream_t, hipStreamDestroy>;
+
+// the buffers behind one SurfelSet (Model is passed to kernels by value and stays a set of views)
+struct SetBufs {
+    Dev<float4> pos_conf, norm_rad;
+    Dev<uint32_t> color;
+    Dev<float> init_time, time;
+    SurfelSet view() const { return {pos_conf, norm_rad, color, init_time, time}; }
+};
+constexpr int EV_RING = 256;
+constexpr int N_EV = 9;           // start, prep, conflict, scan_cull, compact, associate, scan_new, append, + calibration
+constexpr int MAX_GRID = 2048;   // 256 CUs x 8 workgroups
+constexpr int COMPACT_GRID = 1024;  // k_compact: 256 CUs x 4 workgroups, must be fully co-resident (in-place hand-off)
+
+// tracking (sm_track.hip, sm_k_track.h): scratch allocated by the first call, the last two processed poses
+struct Tracker {
+    Dev<uint16_t> d_depth;
+    Dev<float4> d_v, d_n;
+    Dev<uint64_t> d_key;
+    Dev<int32_t> d_pred;
+    Dev<double> d_part;
+    Dev<TrackState> d_state;
+    Host<TrackState> h_state;
+    float hist[2][16];                 // [0] the last processed pose (T_prev), [1] the one before (T_prev2)
+    int n_hist = 0;                    // poses processed so far (capped at 2)
+    bool timed = false;                // SM_TRACK_TIMING=1 at the last call: events around every kernel
+    int ev_iters = 0;                  // iterations the events of the last timed call cover
+    std::vector<Event> ev;
+    // every processed frame's pose (begin_frame): the constant-velocity history of sm_track_frame
+    void note_pose(const float *pose)
+    {
+        memcpy(hist[1], hist[0], 64);
+        memcpy(hist[0], pose, 64);
+        n_hist = std::min(n_hist + 1, 2);
+    }
+};
+
+// model view (sm_view.hip): where the last render left its overflow-list length in the export scratch, and the diagnostic
+// timing events (SM_RENDER_MODEL_TIMING=1)
+struct ModelView {
+    size_t ovf_off = 0;
+    bool ovf_valid = false;
+    bool timed = false;
+    Event ev[4];
+    // every user of the export scratch (ensure_export) may overwrite the overflow count
+    void scratch_reused() { ovf_valid = false; }
+};
+
+}  // namespace sm_impl
+
+using namespace sm_impl;
+
+struct sm_ctx {
+    // the streams come first: members die in reverse order, so everything used on them is released before they are
+    Stream stream;
+    Stream stream_in;                  // ONE copy stream.  (Two -- colour on one engine, depth + class on another -- were 80 instead of 89 us per frame on
+                                       // one box of the pool and stalled for 10-16 ms every few dozen frames on others; tools/h2d_probe.hip: per frame, three
+                                       // copies on two streams 68 us + stalls, on one stream 87, ONE copy of the whole frame 58 = the PCIe rate.)
+    sm_config cfg{};
+    int W = 0, H = 0, P = 0;
+    uint32_t cap = 0;                 // MAX_VERTICES
+    // The four frame planes exist twice (the *_nx pointers are the set of the other frame): a frame's association is held back
+    // and runs in the NEXT frame's preparation launch, which writes the other set.  (Rounds 1-2 ran the depth filter chain of
+    // frame f+1 on a second stream instead; since round 3 the chain is a stage of the preparation launch itself.)
+    int plane_set = 0;                 // which plane set the current frame uses
+    Model M{};
+    SetBufs m_bufs[2];                 // the buffers behind M.s[0] and M.s[1]
+    Dev<DevState> d_state;
+    Host<DevState> h_state;           // pinned mirror
+    // column-major frame images
+    Dev<float> d_depthT, d_filteredT, d_lastT;
+    Dev<uint32_t> d_rgbsT;
+    Dev<uint2> d_dcT;                  // (depth bits, rgbs) of the frame the conflict test sees
+    Dev<float> d_depthT_nx; Dev<uint32_t> d_rgbsT_nx; Dev<uint64_t> d_keyT_nx; Dev<uint2> d_dcT_nx;
+    Dev<uint64_t> d_keyT;
+    // row-major staging of the caller's inputs
+    Dev<uint8_t> d_rgb, d_sem;
+    Dev<uint16_t> d_depth_raw;
+    // sm_process_frame_async: a ring of device input sets filled on a copy stream, so that the H2D copy of frame f+1 runs while
+    // frame f computes; images in buffers of sm_host_alloc are copied from in place, others through pinned staging
+    static constexpr int IN_RING = 3;
+    struct InSlot { Dev<uint8_t> rgb; uint8_t *sem = nullptr; uint16_t *depth = nullptr;   // one block: depth and class follow the colour image
+                    Host<unsigned char> h_stage; Event ev_in, ev_free; bool used = false; };
+    InSlot in[IN_RING];
+    size_t in_off_depth = 0, in_off_sem = 0, in_bytes = 0;   // a frame's images as ONE block: colour | depth | class, 16-byte aligned (sm_host_alloc_frame)
+    uint32_t in_next = 0;
+    const uint16_t *in_last_depth = nullptr; const uint8_t *in_last_sem = nullptr;     // device copies of the last depth / semantic image given
+    int in_depth_slot = -1, in_sem_slot = -1;                                          // ... and the input sets that hold them
+    // Pinned host buffers handed out by sm_host_alloc, with their sizes: the sources sm_process_frame_async copies from in
+    // place.  Caller memory is never registered: hipHostRegister / hipHostUnregister of heap ranges left the runtime treating
+    // later, unrelated host arrays at the same addresses as pinned -- a GPU memory fault in whatever copied to or from them next.
+    std::vector<std::pair<Host<unsigned char>, size_t>> pinned;
+    Dev<float> d_depth_f32;
+    Dev<float> d_xs, d_ys;
+    float h_wtab[169];                 // depth_smooth.frag's 13 x 13 weights (host-computed, handed to the chain stage as kernel arguments)
+    // cull scratch
+    Dev<uint64_t> d_cm, d_dm, d_zm;
+    Dev<uint32_t> d_tile_cnt, d_tile_allow, d_tile_keep, d_tile_flag;
+    Dev<uint32_t> d_group_tot, d_group_base;
+    Dev<uint64_t> d_alive;             // 1 bit per slot: 0 = killed since the last physical compaction (free slots are 1)
+    Dev<uint32_t> d_tile_dead;         // dead slots per tile
+    size_t alive_words = 0, dead_tiles = 0;
+    bool maybe_garbage = false;        // a deferred-compaction cull ran since the last physical compaction
+    bool keys_are_slots = false;       // the key map was drawn by a cull that did not compact: its ids are slot numbers
+    int culls_since_compact = 0;       // deferred-compaction schedule (host side: it picks the kernels)
+    uint32_t frames_enq = 0;           // appends enqueued so far (compared with the tag of *h_stat)
+    Host<unsigned long long> h_stat; unsigned long long *d_stat = nullptr;   // pinned, device-written: frames<<32 | occupied slots
+    Dev<uint32_t> d_tb;                // per-tile bounds (8 words per tile)
+    Dev<uint8_t> d_tile_flags;         // per-tile skip flags of the current frame
+    Dev<uint8_t> d_tile_flags_nx; Dev<uint4> d_wave_cnt_nx; Dev<uint2> d_prep_part_nx;   // the other frame's (two-launch frame: its publisher runs next to this frame's flag workgroups)
+    Dev<uint32_t> d_conf_part;         // per-workgroup partial counters (instead of same-address atomics)
+    Dev<uint2> d_compact_part;
+    Dev<uint4> d_lazy_part;            // partials of k_surfel_pass (visible, splat-skipped, killed, conflict-skipped)
+    bool lazy_part_live = false;       // the next append folds d_lazy_part (not d_compact_part) into the counters
+    // one pass over the surfels per frame (k_surfel_pass + k_pass_fixup) on the frames whose cull only marks the dead
+    Dev<uint4> d_wave_cnt;             // conflicts per quarter tile (one word per wave)
+    Dev<float> d_undo;                 // confidence before this frame's decrement, per slot (read only if the conflict cap binds)
+    Dev<uint2> d_fix_part;             // partials of k_pass_fixup (visible added, resurrected)
+    bool fix_part_live = false;        // the next append also folds d_fix_part in (when the cap bound)
+    uint32_t n_fix_part = 0;           // worker workgroups of the last k_pass_fixup
+    bool ev_one_pass[EV_RING] = {};    // which frames of the event ring ran the one-pass kernels
+    bool ev_direct[EV_RING] = {};      // ... and appended directly
+    bool ev_merged[EV_RING] = {};      // the frame's preparation launch was k_assoc_prep (it carried the previous frame's association)
+    bool ev_deferred[EV_RING] = {};    // the frame's own association was held back (no kernel between its marks 4 and 5)
+    // tile skip flags of the frame, evaluated by extra workgroups of the preparation launch
+    Dev<uint2> d_prep_part;
+    uint32_t n_prep_blocks = 0;        // flag workgroups the frame's k_prep ran (0: the pass kernel evaluates the flags itself)
+    bool want_list = false;            // set by enqueue_frame before begin_frame launches k_prep
+    int fix_grid = 128;
+    // direct append (k_associate_direct): candidate counts per association block / per group, group prefixes
+    Dev<uint32_t> d_blk_cand, d_grp_cand;
+    Dev<uint32_t> d_frame_sub;         // 2 x 64 sub-counters: visible, killed (k_surfel_pass)
+    uint32_t *d_nf_sub = nullptr, *d_nf_sub_nx = nullptr;   // 2 x 64 each: new, fused (k_associate_direct) of this / the other frame
+    uint32_t *nf_last = nullptr;       // the set the last direct association counted into (its statistics may still be pending)
+    uint32_t n_grp = 0, cand_group = 16;
+    bool pend_finalize = false;        // the last frame's statistics are completed by the next k_pass_fixup or by k_frame_finalize
+    int fix_set = 0;                   // k_pass_fixup's partials alternate between two sets (the previous frame's are read one frame later)
+    Dev<unsigned long long> d_pass_trace;         // SM_PASS_TRACE=<file prefix>: per-workgroup time stamps of the last k_surfel_pass launch, dumped by sm_destroy
+    int pass_trace_grid = 0;
+    Dev<unsigned long long> d_ap_trace;           // the same for the last k_assoc_prep launch: (entry, exit) per workgroup
+    int ap_trace_n[4] = {0, 0, 0, 0};             // its association / tile-flag / image workgroups (dispatch order); fixup workgroups ahead of them
+    Dev<uint32_t> d_conf_sub;          // 2 x 64 conflict sub-counters (one set per frame parity: zeroed by that frame's k_prep)
+    int conf_sub_set = 0;
+    uint32_t n_conf_part = 0, n_compact_part = 0;
+    uint32_t tb_tiles = 0;
+    uint32_t cull_epoch = 0;
+    int compact_grid = COMPACT_GRID;
+    int pass_grid = MAX_GRID;          // workgroups of k_surfel_pass that are resident at once (a larger grid runs its tail as a second, thin wave)
+    // association scratch
+    Dev<uint64_t> d_validmask, d_fusedmask;
+    Dev<uint2> d_blk_cnt;
+    // slot-addressed sharding of one stream, in-stream form (sm_shard_stream_*)
+    bool ss_on = false;
+    bool rig_on = false;               // sm_rig_configure: rank / world / collective are used by sm_rig_consolidate only
+    float rig_last_time = -1.0e30f;    // creation time stamp up to which this rank's surfels are in the incremental GlobalModel (sm_rig_consolidate_step)
+    int ss_rank = 0, ss_world = 1;
+    uint32_t ss_frames = 0;            // fusing frames so far = index of the next segment (its owner: index % world)
+    sm_collective_fn ss_coll = nullptr;
+    void *ss_user = nullptr;
+    void *ss_comm = nullptr;           // ncclComm_t when the built-in RCCL binding is used
+    Dev<uint64_t> d_galive, d_new_alive, d_gmask;
+    Dev<uint32_t> d_chk;               // SM_CHECK_ALIVE=1: result words of k_check_alive
+    Dev<uint64_t> d_capx;              // the conflict-cap exchange of a sharded frame: total | quarter-tile counts | conflict masks (k_shard_cap_pack)
+    Dev<uint32_t> d_ss_info;
+    // deferred association (k_assoc_prep): the association of an asynchronous frame is held back until the next frame's images
+    // arrive and then shares that frame's k_prep launch (three launches per frame instead of four)
+    bool defer_ok = false;             // this context may defer (plain stream, no depth filter chain, no per-kernel timing)
+    bool assoc_pending = false;
+    AssocArgs assoc_args{};            // the held-back association (its FrameParams and that frame's planes)
+    bool merge_assoc = false;          // set by enqueue_frame: the k_prep launch of this call carries assoc_args
+    // two-launch frame: the fixup step (publisher, cap repair) of a frame whose association is held back rides on the same
+    // launch as that association; the candidate count moved into the pass's launch
+    bool two_launch = false;           // this context uses it (defer_ok, SM_TWO_LAUNCH != 0)
+    uint32_t est_fr0 = 0, est_slots0 = 0, est_rate = 0xFFFFFFFFu;   // launch_surfel_pass's estimate of the slots per frame (from the pinned statistic)
+    bool fix_pending = false;          // the last frame's fixup has not run yet
+    FixArgs fix_args{};
+    static constexpr uint32_t N_CREW = 32;
+    bool ss_settle_pending = false;    // the last sharded frame's k_shard_settle work rides on the next k_prep (or runs stand-alone first)
+    ShardSettle ss_settle{};
+    int n_pix_blocks = 0;
+    uint32_t n_odd_pixels = 0;
+    // export staging
+    Dev<void> d_export;
+    size_t export_bytes = 0;
+    ModelView rm;
+    Tracker trk;
+    // host frame state (src/SurfelMapping.h:100-103)
+    int tick = 0;
+    bool ref_set = false;
+    bool raw_valid = false;            // a frame that computes the raw feedback cloud has run (every call but the reference frame)
+    int raw_tick = 0;                  // its time stamp
+    float curr_pose[16], last_pose[16];
+    uint32_t count_bound = 0;         // host upper bound of the device-side count (grid sizing)
+    bool pending_cull = false;
+    uint32_t count_before_cull = 0, offset_before_cull = 0;
+    sm_counts counts{};
+    std::vector<Dev<void>> user_allocs;
+    // timing
+    std::unique_ptr<Event[][EV_RING]> ev;   // enable_timing: per-frame timeline (before prep, then after each kernel), [N_EV][EV_RING]; whole or absent
+    bool ev_compacted[EV_RING] = {};  // which cull kernel the frame of that slot ran
+    Dev<FrameLog> d_log;
+    uint64_t ev_frames = 0, ev_read = 0;
+};
+
+namespace sm_impl __attribute__((visibility("hidden"))) {
+
+template <typename T>
+int dalloc(Dev<T> &p, size_t n)
+{
+    HIPCK(hipMalloc(p.put(), std::max<size_t>(n, 1) * sizeof(T)));
+    return SM_OK;
+}
+
+// ---- sm_api.hip ----
+void invert4(const float *m, float *out);         // general 4x4 inverse, column-major, fp32
+FrameParams make_params(const sm_ctx *s, const float *pose);
+bool hip_runtime_conflict(const char *where);     // true (and g_err set) if more than one libamdhip64 is mapped into the process
+int push_state(sm_ctx *s);
+int pull_state(sm_ctx *s);
+int finalize_if_pending(sm_ctx *s);
+int ensure_compact(sm_ctx *s);
+int rebuild_bounds(sm_ctx *s, uint32_t first_surfel, uint32_t count);
+int ensure_export(sm_ctx *s, size_t bytes);
+void fill_keys(sm_ctx *s, uint64_t *key, size_t n);                  // k_fill_keys on the context's stream
+int clean_points_device(sm_ctx *s, const uint16_t *d_depth_mm, const uint8_t *d_semantic, const float *pose16, int exempt_first,
+                        const std::function<long long(uint32_t)> *cap_hook = nullptr);
+int ss_collective(sm_ctx *s, const void *send, void *recv, size_t count, int op);
+// ---- sm_model_io.hip ----
+void export_aos(sm_ctx *s, float *dst12, uint32_t first, uint32_t n);   // k_export_aos on the context's stream
+
+}  // namespace sm_impl

@@ -382,4 +382,139 @@ __device__ __forceinline__ uint64_t first_n_bits(uint64_t m, uint32_t n)
     return m ^ rest;
 }
 
+
+// ---------------------------------------------------------------------------------------------
+// The frame's surfel at pixel q (data.vert:59-234; surfel_feedback.vert with fp.init_mode): the association's and the raw
+// feedback cloud's rule, and the vertex rule the tracker shares.
+// ---------------------------------------------------------------------------------------------
+struct LocalSurfel {
+    float3 pos;       // vPosLocal
+    float3 nrm;       // vNormLocal
+    float radius;     // radii_n
+    float cr, cg, cb; // color_n
+    uint32_t sem;
+    float xl, yl, lambda;
+};
+
+__device__ __forceinline__ float3 get_vertex(float z, float x, float y, const FrameParams &fp, float inv_fx, float inv_fy)
+{
+    // geometry.glsl:5-9
+    float3 r;
+    r.x = (x - fp.cx) * z * inv_fx;
+    r.y = (y - fp.cy) * z * inv_fy;
+    r.z = z;
+    return r;
+}
+
+// What the association of pixel q reads from the frame's planes and the key map, loaded by the caller ahead of a decision it
+// has to take first (two-launch frame: associate_direct_block)
+struct PixelLoads { float z, zl, zu, zr, zd; uint32_t c; uint64_t key; };
+
+__device__ __forceinline__ bool local_surfel(int q, const FrameParams &fp, const float *__restrict__ depthT,
+                                             const uint32_t *__restrict__ rgbsT, const float *__restrict__ xs,
+                                             const float *__restrict__ ys, LocalSurfel &L, int qi = -1, int qj = 0,
+                                             const PixelLoads *pre = nullptr)
+{
+    const int H = fp.H, W = fp.W;
+    const int i = qi >= 0 ? qi : q / H, j = qi >= 0 ? qj : q - i * H;     // (qi, qj): the caller knows the column / row of q already
+    // init_mode: xs/ys hold the FeedbackBuffer's own pixel coordinates (src/FeedbackBuffer.cpp:47-53); they
+    // follow the association tables in the same arrays at offsets W and H
+    const float x = fp.init_mode ? xs[W + i] : xs[i], y = fp.init_mode ? ys[H + j] : ys[j];
+    const float inv_fx = fp.init_mode ? fp.inv_fx_fb : fp.inv_fx, inv_fy = fp.init_mode ? fp.inv_fy_fb : fp.inv_fy;
+    const float z = pre ? pre->z : depthT[q];
+    // clamp-to-edge neighbours: at the border the neighbour depth is the pixel's own (A1)
+    const float zl = pre ? pre->zl : depthT[i > 0 ? q - H : q];
+    const float zu = pre ? pre->zu : depthT[j > 0 ? q - 1 : q];
+    const float zr = pre ? pre->zr : depthT[i < W - 1 ? q + H : q];
+    const float zd = pre ? pre->zd : depthT[j < H - 1 ? q + 1 : q];
+    if (fp.init_mode) {
+        // surfel_feedback.vert:80-92: 0 < z < maxDepth and the checkerboard; no neighbour test
+        if (!(z > 0.0f && z < fp.max_depth)) return false;
+    } else {
+        // checkNeighbours data.vert:33-52 + range data.vert:87
+        if (zl == 0.0f || zu == 0.0f || zr == 0.0f || zd == 0.0f) return false;
+        if (!(z > fp.min_depth && z < fp.max_depth)) return false;
+    }
+    if ((((int)x + (int)y) % 2) != 1) return false;       // data.vert:88 / surfel_feedback.vert:81
+    L.xl = (x - fp.cx) * inv_fx;
+    L.yl = (y - fp.cy) * inv_fy;
+    L.lambda = sqrtf((L.xl * L.xl + L.yl * L.yl) + 1.0f);
+    L.pos = get_vertex(z, x, y, fp, inv_fx, inv_fy);
+    // getNormal geometry.glsl:12-24
+    const float3 xf = get_vertex(zr, x + 1.0f, y, fp, inv_fx, inv_fy);
+    const float3 xb = get_vertex(zl, x - 1.0f, y, fp, inv_fx, inv_fy);
+    const float3 yf = get_vertex(zd, x, y + 1.0f, fp, inv_fx, inv_fy);
+    const float3 yb = get_vertex(zu, x, y - 1.0f, fp, inv_fx, inv_fy);
+    const float3 del_x = make_float3(xb.x - xf.x, xb.y - xf.y, xb.z - xf.z);
+    const float3 del_y = make_float3(yb.x - yf.x, yb.y - yf.y, yb.z - yf.z);
+    L.nrm = normalize3(cross3(del_x, del_y));
+    const uint32_t c = pre ? pre->c : rgbsT[q];
+    L.cr = (float)((c >> 16) & 0xFFu) / 255.0f;     // GL_RGB32F upload of u8 (A1)
+    L.cg = (float)((c >> 8) & 0xFFu) / 255.0f;
+    L.cb = (float)(c & 0xFFu) / 255.0f;
+    L.sem = c >> 24;
+    L.radius = get_radius(L.pos.z, L.nrm.z, inv_fx, inv_fy);
+    return true;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Kernel arguments the host keeps between launches (struct sm_ctx holds them)
+// ---------------------------------------------------------------------------------------------
+struct AssocArgs {
+    Model M; DevState *st; FrameParams fp;
+    const float *depthT; const uint32_t *rgbsT; const uint64_t *keyT; const float *xs, *ys;
+    const uint32_t *blk_cand /* candidate pixels per block ... */, *grp_cand /* ... and per group of CAND_GROUP blocks */;
+    uint32_t *nf /* new, fused: 64 sub-counters each */, *tb;
+    uint64_t *alive; uint32_t *tile_dead; uint32_t n_grp, cg; unsigned long long *host_stat;
+    // two-launch frame: the frame's publisher / repair crew run in the SAME launch (fixup_merged_block); on the rare frames where
+    // they change anything the association waits for them first
+    const uint32_t *slow_conf_sub;   // the frame's conflict sub-counters, or null: the fixup ran in a launch of its own
+    uint32_t slow_need;              // workgroups to wait for (publisher + crew)
+};
+
+// Arguments of the direct-append frame form (k_associate_direct), handed to k_pass_fixup's publisher
+struct DirectArgs {
+    int on;                              // 1: this frame appends directly (k_associate_direct follows; no k_append_scan); 2: ... and its candidate pixels were counted by the pass's launch
+    uint32_t *blk_cand, *grp_cand;       // out: candidate pixels per association block / per group of CAND_GROUP blocks (this frame)
+    uint32_t n_grp, cg;                  // groups; association blocks per group (4, 8 or 16)
+    int n_pix_blocks;
+    const float *depthT, *xs, *ys;
+    uint32_t *frame_sub;                 // 2 x 64 sub-counters: visible, killed (this frame's pass)
+    uint32_t *nf_prev;                   // 2 x 64 sub-counters: new, fused of the PREVIOUS frame's association (the sets alternate where that association runs next to this publisher)
+    const uint2 *fix_prev;               // the previous frame's k_pass_fixup partials (read if its conflict cap bound)
+    uint32_t n_fix_prev;
+    FrameLog *log;
+};
+
+struct FixArgs {
+    const uint64_t *cm, *km;
+    const uint4 *wave_cnt;
+    const uint8_t *tile_flags;
+    const uint4 *part; uint32_t n_part;
+    uint2 *fix_part;                     // [workers] (visible added, resurrected)
+    uint64_t *alive; uint32_t *tile_dead;
+    const uint32_t *conf_sub;            // the frame's 64 conflict sub-counters
+    uint64_t *keyT;
+    const float *undo;
+    unsigned long long *host_stat;
+    const uint2 *prep_part; uint32_t n_prep;     // the preparation launch's skip statistics (it evaluated the tile flags), or 0
+    DirectArgs da;
+    uint32_t *tb;                        // tile bounds: a tile drawn only through a resurrected surfel gets the frame's time stamp too
+    uint32_t n_crew;                     // MERGED: workgroups behind the publisher that repair (0: the launch carries no fixup)
+};
+
+struct ShardSettle {
+    uint32_t n;                       // pixel blocks to settle (0: nothing pending) -- as extra workgroups of the next frame's k_prep, or k_shard_settle
+    DevState *st;
+    const uint64_t *validmask, *ownmask, *gmask;
+    uint32_t nwords;
+    const uint32_t *blk_cand, *grp_cand;
+    uint32_t *nf;                     // new / fused sub-counter sets
+    uint64_t *alive;
+    uint32_t *tile_dead;
+    int owner;
+    uint32_t cap_pixels, max_vertices;
+    uint32_t cg;                      // association blocks per candidate group
+};
+
 }  // namespace sm

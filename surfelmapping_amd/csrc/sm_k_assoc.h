@@ -1,33 +1,10 @@
-// sm_k_assoc.h -- data association + fuse + append (p8..p11): k_associate_direct / k_assoc_prep (direct append), k_associate + k_append_scan (dense append on compacting frames), the raw feedback cloud.
+// sm_k_assoc.h -- data association + fuse + append (p8..p11): k_associate_direct / k_assoc_prep (direct append), k_associate + k_append_scan (dense append on compacting frames).
 // Part of sm_kernels.h (included there, in order, inside namespace sm); shader citations: /root/reference/src/Shaders/<file>:<line>.
 #pragma once
 
 // ---------------------------------------------------------------------------------------------
-// p8 data association (data.vert:59-234) for pixel q = i*H + j.
+// p8 data association (data.vert:59-234) for pixel q = i*H + j (the pixel's own surfel: local_surfel, sm_device.h).
 // ---------------------------------------------------------------------------------------------
-struct LocalSurfel {
-    float3 pos;       // vPosLocal
-    float3 nrm;       // vNormLocal
-    float radius;     // radii_n
-    float cr, cg, cb; // color_n
-    uint32_t sem;
-    float xl, yl, lambda;
-};
-
-__device__ __forceinline__ float3 get_vertex(float z, float x, float y, const FrameParams &fp, float inv_fx, float inv_fy)
-{
-    // geometry.glsl:5-9
-    float3 r;
-    r.x = (x - fp.cx) * z * inv_fx;
-    r.y = (y - fp.cy) * z * inv_fy;
-    r.z = z;
-    return r;
-}
-
-// What the association of pixel q reads from the frame's planes and the key map, loaded by the caller ahead of a decision it
-// has to take first (two-launch frame: associate_direct_block)
-struct PixelLoads { float z, zl, zu, zr, zd; uint32_t c; uint64_t key; };
-
 __device__ __forceinline__ PixelLoads load_pixel(int q, int i, int j, const FrameParams &fp, const float *__restrict__ depthT,
                                                  const uint32_t *__restrict__ rgbsT, const uint64_t *__restrict__ keyT)
 {
@@ -42,53 +19,6 @@ __device__ __forceinline__ PixelLoads load_pixel(int q, int i, int j, const Fram
     r.zd = depthT[j < H - 1 && q + 1 < fp.P ? q + 1 : q];
     r.c = rgbsT[q];
     return r;
-}
-
-__device__ __forceinline__ bool local_surfel(int q, const FrameParams &fp, const float *__restrict__ depthT,
-                                             const uint32_t *__restrict__ rgbsT, const float *__restrict__ xs,
-                                             const float *__restrict__ ys, LocalSurfel &L, int qi = -1, int qj = 0,
-                                             const PixelLoads *pre = nullptr)
-{
-    const int H = fp.H, W = fp.W;
-    const int i = qi >= 0 ? qi : q / H, j = qi >= 0 ? qj : q - i * H;     // (qi, qj): the caller knows the column / row of q already
-    // init_mode: xs/ys hold the FeedbackBuffer's own pixel coordinates (src/FeedbackBuffer.cpp:47-53); they
-    // follow the association tables in the same arrays at offsets W and H
-    const float x = fp.init_mode ? xs[W + i] : xs[i], y = fp.init_mode ? ys[H + j] : ys[j];
-    const float inv_fx = fp.init_mode ? fp.inv_fx_fb : fp.inv_fx, inv_fy = fp.init_mode ? fp.inv_fy_fb : fp.inv_fy;
-    const float z = pre ? pre->z : depthT[q];
-    // clamp-to-edge neighbours: at the border the neighbour depth is the pixel's own (A1)
-    const float zl = pre ? pre->zl : depthT[i > 0 ? q - H : q];
-    const float zu = pre ? pre->zu : depthT[j > 0 ? q - 1 : q];
-    const float zr = pre ? pre->zr : depthT[i < W - 1 ? q + H : q];
-    const float zd = pre ? pre->zd : depthT[j < H - 1 ? q + 1 : q];
-    if (fp.init_mode) {
-        // surfel_feedback.vert:80-92: 0 < z < maxDepth and the checkerboard; no neighbour test
-        if (!(z > 0.0f && z < fp.max_depth)) return false;
-    } else {
-        // checkNeighbours data.vert:33-52 + range data.vert:87
-        if (zl == 0.0f || zu == 0.0f || zr == 0.0f || zd == 0.0f) return false;
-        if (!(z > fp.min_depth && z < fp.max_depth)) return false;
-    }
-    if ((((int)x + (int)y) % 2) != 1) return false;       // data.vert:88 / surfel_feedback.vert:81
-    L.xl = (x - fp.cx) * inv_fx;
-    L.yl = (y - fp.cy) * inv_fy;
-    L.lambda = sqrtf((L.xl * L.xl + L.yl * L.yl) + 1.0f);
-    L.pos = get_vertex(z, x, y, fp, inv_fx, inv_fy);
-    // getNormal geometry.glsl:12-24
-    const float3 xf = get_vertex(zr, x + 1.0f, y, fp, inv_fx, inv_fy);
-    const float3 xb = get_vertex(zl, x - 1.0f, y, fp, inv_fx, inv_fy);
-    const float3 yf = get_vertex(zd, x, y + 1.0f, fp, inv_fx, inv_fy);
-    const float3 yb = get_vertex(zu, x, y - 1.0f, fp, inv_fx, inv_fy);
-    const float3 del_x = make_float3(xb.x - xf.x, xb.y - xf.y, xb.z - xf.z);
-    const float3 del_y = make_float3(yb.x - yf.x, yb.y - yf.y, yb.z - yf.z);
-    L.nrm = normalize3(cross3(del_x, del_y));
-    const uint32_t c = pre ? pre->c : rgbsT[q];
-    L.cr = (float)((c >> 16) & 0xFFu) / 255.0f;     // GL_RGB32F upload of u8 (A1)
-    L.cg = (float)((c >> 8) & 0xFFu) / 255.0f;
-    L.cb = (float)(c & 0xFFu) / 255.0f;
-    L.sem = c >> 24;
-    L.radius = get_radius(L.pos.z, L.nrm.z, inv_fx, inv_fy);
-    return true;
 }
 
 // Where a fused surfel went (for the tile-bounds update)
@@ -333,18 +263,6 @@ struct ShardArgs {
                               //   4 more words follow: [nw + 0..2] this rank's conflicts / surfels drawn into the index map / surfels killed
     uint32_t nwords;          // ceil(P / 64)
     int owner;                // 1: this rank owns the frame's new surfels (frame's segment index % world == rank)
-};
-
-struct AssocArgs {
-    Model M; DevState *st; FrameParams fp;
-    const float *depthT; const uint32_t *rgbsT; const uint64_t *keyT; const float *xs, *ys;
-    const uint32_t *blk_cand /* candidate pixels per block ... */, *grp_cand /* ... and per group of CAND_GROUP blocks */;
-    uint32_t *nf /* new, fused: 64 sub-counters each */, *tb;
-    uint64_t *alive; uint32_t *tile_dead; uint32_t n_grp, cg; unsigned long long *host_stat;
-    // two-launch frame: the frame's publisher / repair crew run in the SAME launch (fixup_merged_block); on the rare frames where
-    // they change anything the association waits for them first
-    const uint32_t *slow_conf_sub;   // the frame's conflict sub-counters, or null: the fixup ran in a launch of its own
-    uint32_t slow_need;              // workgroups to wait for (publisher + crew)
 };
 
 // bit i of x -> bit 2 i (Morton spread)
@@ -684,24 +602,4 @@ __global__ __launch_bounds__(PIX_BLOCK) void k_append_scan(Model M, DevState *__
     float3 pw = make_float3(0.f, 0.f, 0.f);
     if (wr) pw = write_new_surfel(cur, slot, L, fp);
     bounds_expand_wave(tb, wr, slot / (uint32_t)TILE, pw.x, pw.y, pw.z, (float)fp.time, false);
-}
-
-// The raw per-frame surfel cloud of FeedbackBuffer::compute (src/FeedbackBuffer.cpp:85-145, surfel_feedback.vert:25-63,
-// surfel_feedback.geom:17-26): every checkerboard pixel with 0 < z < maxDepth as a CAMERA-frame surfel
-// (pos, 0.9 | colour, 0, time, time | normal, radius), no neighbour test.  One record slot per pixel + a flag; the host
-// keeps the flagged ones in vertex order (x-outer / y-inner, src/FeedbackBuffer.cpp:47-54).  Not on the hot path: the
-// reference fills this buffer every frame for the GUI's "Draw raw" view only (src/SurfelMapping.cpp:172).
-__global__ __launch_bounds__(256) void k_raw_cloud(FrameParams fp, const float *__restrict__ depthT, const uint32_t *__restrict__ rgbsT,
-                                                   const float *__restrict__ xs, const float *__restrict__ ys,
-                                                   float4 *__restrict__ rec /* [P][3] */, uint8_t *__restrict__ flag)
-{
-    const int q = blockIdx.x * 256 + threadIdx.x;
-    if (q >= fp.P) return;
-    LocalSurfel L;
-    const bool ok = local_surfel(q, fp, depthT, rgbsT, xs, ys, L);       // fp.init_mode = 1: the feedback buffer's rules
-    flag[q] = ok ? 1 : 0;
-    if (!ok) return;
-    rec[(size_t)q * 3 + 0] = make_float4(L.pos.x, L.pos.y, L.pos.z, 0.9f);                             // surfel_feedback.vert:96
-    rec[(size_t)q * 3 + 1] = make_float4(__uint_as_float(encode_color(L.cr, L.cg, L.cb, L.sem)), 0.0f, (float)fp.time, (float)fp.time);
-    rec[(size_t)q * 3 + 2] = make_float4(L.nrm.x, L.nrm.y, L.nrm.z, L.radius);
 }

@@ -1,4 +1,4 @@
-// sm_k_cull.h -- the cull of the frames that compact: conflict test (p2), scans, finalize, in-place stable compaction + splat (p3..p6); the index-map splat of one surfel.
+// sm_k_cull.h -- the cull of the frames that compact: conflict test (p2), scans, finalize, in-place stable compaction + splat (p3..p6); the index-map splat of one surfel; the tile-bounds rebuild and the alive-bits check.
 // Part of sm_kernels.h (included there, in order, inside namespace sm); shader citations: /root/reference/src/Shaders/<file>:<line>.
 #pragma once
 
@@ -769,4 +769,47 @@ __global__ __launch_bounds__(256) void k_cull_lazy(Model M, const DevState *__re
         }
         if (killed && lane == 0) atomicAdd(&tile_dead[tile], killed);
     }
+}
+
+// SM_CHECK_ALIVE=1 (diagnostic): the invariant every compaction relies on -- per tile, occupied slots - dead count == live bits --
+// checked after a stage; out[0] counts the tiles that violate it, out[1..4] describe the first one seen
+__global__ __launch_bounds__(256) void k_check_alive(const DevState *__restrict__ st, const uint64_t *__restrict__ alive,
+                                                     const uint32_t *__restrict__ tile_dead, uint32_t *__restrict__ out, uint32_t stage)
+{
+    const uint32_t N = st->count;
+    const uint32_t ntiles = (N + TILE - 1) / TILE;
+    for (uint32_t t = blockIdx.x * 256u + threadIdx.x; t < ntiles; t += gridDim.x * 256u) {
+        uint32_t live = 0;
+        for (int w = 0; w < TILE_WORDS; ++w) {
+            const uint64_t base = ((uint64_t)t * TILE_WORDS + w) * 64u;
+            if (base >= N) break;
+            const uint64_t rem = (uint64_t)N - base;
+            live += (uint32_t)__popcll(alive[(size_t)t * TILE_WORDS + w] & (rem >= 64 ? ~0ull : ((1ull << rem) - 1ull)));
+        }
+        const uint32_t occ = min((uint32_t)TILE, N - t * (uint32_t)TILE);
+        if (occ - tile_dead[t] != live && atomicAdd(&out[0], 1u) == 0u) { out[1] = stage; out[2] = t; out[3] = live; out[4] = occ - tile_dead[t]; out[5] = N; }
+    }
+}
+
+// rebuild of the tile bounds from the stored model (upload / import / device append)
+__global__ void k_tile_bounds_reset(uint32_t *__restrict__ tb, uint32_t first, uint32_t n)
+{
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    uint4 *b = reinterpret_cast<uint4 *>(tb + (size_t)(first + t) * 8);
+    b[0] = make_uint4(0u, 0u, 0u, 0u);
+    b[1] = make_uint4(0u, 0u, 0u, 0u);
+}
+
+__global__ __launch_bounds__(256) void k_tile_bounds_build(Model M, const DevState *__restrict__ st, uint32_t *__restrict__ tb,
+                                                           uint32_t first_surfel)
+{
+    const SurfelSet cur = M.s[st->cur];
+    const uint32_t N = st->count;
+    const uint32_t k = first_surfel + blockIdx.x * 256u + threadIdx.x;
+    const bool a = k < N;
+    float4 v = make_float4(0.f, 0.f, 0.f, 1.f);
+    float t = 0.f;
+    if (a) { v = cur.pos_conf[k]; t = cur.time[k]; }
+    bounds_expand_wave(tb, a, k / (uint32_t)TILE, v.x, v.y, v.z, t, !(v.w > 0.0f));
 }

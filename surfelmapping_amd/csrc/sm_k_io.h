@@ -1,62 +1,10 @@
-// sm_k_aux.h -- off the hot path: tile-bounds rebuild, AoS export / import, index-map textures, the novel-view renderer.
-// Part of sm_kernels.h (included there, in order, inside namespace sm); shader citations: /root/reference/src/Shaders/<file>:<line>.
+// sm_k_io.h -- off the hot path: AoS export / import, index-map textures, the raw feedback cloud, depth read-back, the
+// novel-view renderer.  Included by sm_model_io.hip only; shader citations: /root/reference/src/Shaders/<file>:<line>.
 #pragma once
 
-// first surfel (position in the compacted model) created after time stamp t0: the model is kept in creation order, so the
-// surfels a rig rank has not yet contributed to the single GlobalModel are the suffix from there on (sm_rig_consolidate_step)
-__global__ __launch_bounds__(256) void k_first_newer(Model M, const DevState *__restrict__ st, float t0, uint32_t *__restrict__ out)
-{
-    const uint32_t N = st->count;
-    const float *__restrict__ it = M.s[st->cur].init_time;
-    uint32_t best = 0xFFFFFFFFu;
-    for (uint32_t k = blockIdx.x * 256u + threadIdx.x; k < N; k += gridDim.x * 256u)
-        if (it[k] > t0) { best = k; break; }               // (k ascending per thread: its first hit is its smallest)
-    best = 0xFFFFFFFFu - wave_max_u32(0xFFFFFFFFu - best);
-    if ((threadIdx.x & 63) == 0 && best != 0xFFFFFFFFu) atomicMin(out, best);
-}
+#include "sm_device.h"
 
-// SM_CHECK_ALIVE=1 (diagnostic): the invariant every compaction relies on -- per tile, occupied slots - dead count == live bits --
-// checked after a stage; out[0] counts the tiles that violate it, out[1..4] describe the first one seen
-__global__ __launch_bounds__(256) void k_check_alive(const DevState *__restrict__ st, const uint64_t *__restrict__ alive,
-                                                     const uint32_t *__restrict__ tile_dead, uint32_t *__restrict__ out, uint32_t stage)
-{
-    const uint32_t N = st->count;
-    const uint32_t ntiles = (N + TILE - 1) / TILE;
-    for (uint32_t t = blockIdx.x * 256u + threadIdx.x; t < ntiles; t += gridDim.x * 256u) {
-        uint32_t live = 0;
-        for (int w = 0; w < TILE_WORDS; ++w) {
-            const uint64_t base = ((uint64_t)t * TILE_WORDS + w) * 64u;
-            if (base >= N) break;
-            const uint64_t rem = (uint64_t)N - base;
-            live += (uint32_t)__popcll(alive[(size_t)t * TILE_WORDS + w] & (rem >= 64 ? ~0ull : ((1ull << rem) - 1ull)));
-        }
-        const uint32_t occ = min((uint32_t)TILE, N - t * (uint32_t)TILE);
-        if (occ - tile_dead[t] != live && atomicAdd(&out[0], 1u) == 0u) { out[1] = stage; out[2] = t; out[3] = live; out[4] = occ - tile_dead[t]; out[5] = N; }
-    }
-}
-
-// rebuild of the tile bounds from the stored model (upload / import / device append)
-__global__ void k_tile_bounds_reset(uint32_t *__restrict__ tb, uint32_t first, uint32_t n)
-{
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n) return;
-    uint4 *b = reinterpret_cast<uint4 *>(tb + (size_t)(first + t) * 8);
-    b[0] = make_uint4(0u, 0u, 0u, 0u);
-    b[1] = make_uint4(0u, 0u, 0u, 0u);
-}
-
-__global__ __launch_bounds__(256) void k_tile_bounds_build(Model M, const DevState *__restrict__ st, uint32_t *__restrict__ tb,
-                                                           uint32_t first_surfel)
-{
-    const SurfelSet cur = M.s[st->cur];
-    const uint32_t N = st->count;
-    const uint32_t k = first_surfel + blockIdx.x * 256u + threadIdx.x;
-    const bool a = k < N;
-    float4 v = make_float4(0.f, 0.f, 0.f, 1.f);
-    float t = 0.f;
-    if (a) { v = cur.pos_conf[k]; t = cur.time[k]; }
-    bounds_expand_wave(tb, a, k / (uint32_t)TILE, v.x, v.y, v.z, t, !(v.w > 0.0f));
-}
+namespace sm {
 
 // ---------------------------------------------------------------------------------------------
 // export helpers (not on the hot path)
@@ -116,6 +64,34 @@ __global__ void k_export_index(Model M, const DevState *__restrict__ st, FramePa
     if (nr) nr[p] = c;
 }
 
+// The raw per-frame surfel cloud of FeedbackBuffer::compute (src/FeedbackBuffer.cpp:85-145, surfel_feedback.vert:25-63,
+// surfel_feedback.geom:17-26): every checkerboard pixel with 0 < z < maxDepth as a CAMERA-frame surfel
+// (pos, 0.9 | colour, 0, time, time | normal, radius), no neighbour test.  One record slot per pixel + a flag; the host
+// keeps the flagged ones in vertex order (x-outer / y-inner, src/FeedbackBuffer.cpp:47-54).  Not on the hot path: the
+// reference fills this buffer every frame for the GUI's "Draw raw" view only (src/SurfelMapping.cpp:172).
+__global__ __launch_bounds__(256) void k_raw_cloud(FrameParams fp, const float *__restrict__ depthT, const uint32_t *__restrict__ rgbsT,
+                                                   const float *__restrict__ xs, const float *__restrict__ ys,
+                                                   float4 *__restrict__ rec /* [P][3] */, uint8_t *__restrict__ flag)
+{
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= fp.P) return;
+    LocalSurfel L;
+    const bool ok = local_surfel(q, fp, depthT, rgbsT, xs, ys, L);       // fp.init_mode = 1: the feedback buffer's rules
+    flag[q] = ok ? 1 : 0;
+    if (!ok) return;
+    rec[(size_t)q * 3 + 0] = make_float4(L.pos.x, L.pos.y, L.pos.z, 0.9f);                             // surfel_feedback.vert:96
+    rec[(size_t)q * 3 + 1] = make_float4(__uint_as_float(encode_color(L.cr, L.cg, L.cb, L.sem)), 0.0f, (float)fp.time, (float)fp.time);
+    rec[(size_t)q * 3 + 2] = make_float4(L.nrm.x, L.nrm.y, L.nrm.z, L.radius);
+}
+
+// column-major -> row-major read-back helper (tests / GUI textures)
+__global__ void k_untranspose_f32(const float *__restrict__ srcT, float *__restrict__ dst, int W, int H)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= W * H) return;
+    const int j = p / W, i = p - j * W;
+    dst[p] = srcT[(size_t)i * H + j];
+}
 
 // ---------------------------------------------------------------------------------------------
 // Novel-view renderer: GlobalModel::renderImage (src/GlobalModel.cpp:772-833),
@@ -234,3 +210,5 @@ __global__ void k_render_resolve(Model M, const DevState *__restrict__ st, const
     bgr[(size_t)p * 3] = b; bgr[(size_t)p * 3 + 1] = g; bgr[(size_t)p * 3 + 2] = r;
     sem[p] = s;
 }
+
+}  // namespace sm

@@ -616,20 +616,6 @@ __device__ __forceinline__ uint64_t ineffective_conflicts(uint64_t c, uint32_t b
     return c & ~first_n_bits(c, cap - before);
 }
 
-// Arguments of the direct-append frame form (k_associate_direct), handed to k_pass_fixup's publisher
-struct DirectArgs {
-    int on;                              // 1: this frame appends directly (k_associate_direct follows; no k_append_scan); 2: ... and its candidate pixels were counted by the pass's launch
-    uint32_t *blk_cand, *grp_cand;       // out: candidate pixels per association block / per group of CAND_GROUP blocks (this frame)
-    uint32_t n_grp, cg;                  // groups; association blocks per group (4, 8 or 16)
-    int n_pix_blocks;
-    const float *depthT, *xs, *ys;
-    uint32_t *frame_sub;                 // 2 x 64 sub-counters: visible, killed (this frame's pass)
-    uint32_t *nf_prev;                   // 2 x 64 sub-counters: new, fused of the PREVIOUS frame's association (the sets alternate where that association runs next to this publisher)
-    const uint2 *fix_prev;               // the previous frame's k_pass_fixup partials (read if its conflict cap bound)
-    uint32_t n_fix_prev;
-    FrameLog *log;
-};
-
 // DevState fields of the pending frame, loaded before the reductions so that completing it costs no further round trip
 struct PendFields { uint32_t cull_n, garbage_prev, n_kill, visible, conflict, n_static, conf_skipped, splat_skipped, tick, frames_logged; };
 
@@ -716,25 +702,8 @@ __global__ __launch_bounds__(256) void k_frame_finalize(DevState *__restrict__ s
 // tells the two cases apart for itself (slow_frame) and waits for the publisher and the repair crew only then (wait_slow_frame).
 // What a MERGED publisher must not touch, because workgroups of its own launch read or write it: count (the association's first
 // workgroup publishes the new one; N is taken from `offset`, which the pass's launch set), offset, first_live unless it changes,
-// the dirty word (cleared one launch later), the host statistic.
+// the dirty word (cleared one launch later), the host statistic.  (FixArgs: sm_device.h)
 // ---------------------------------------------------------------------------------------------
-struct FixArgs {
-    const uint64_t *cm, *km;
-    const uint4 *wave_cnt;
-    const uint8_t *tile_flags;
-    const uint4 *part; uint32_t n_part;
-    uint2 *fix_part;                     // [workers] (visible added, resurrected)
-    uint64_t *alive; uint32_t *tile_dead;
-    const uint32_t *conf_sub;            // the frame's 64 conflict sub-counters
-    uint64_t *keyT;
-    const float *undo;
-    unsigned long long *host_stat;
-    const uint2 *prep_part; uint32_t n_prep;     // the preparation launch's skip statistics (it evaluated the tile flags), or 0
-    DirectArgs da;
-    uint32_t *tb;                        // tile bounds: a tile drawn only through a resurrected surfel gets the frame's time stamp too
-    uint32_t n_crew;                     // MERGED: workgroups behind the publisher that repair (0: the launch carries no fixup)
-};
-
 template <bool MERGED>
 __device__ __forceinline__ void fixup_publisher(DevState *__restrict__ st, const FrameParams &fp, const FixArgs &x, uint32_t ctotal)
 {

@@ -185,19 +185,6 @@ constexpr int CAND_GROUP_MAX = 16;  // association blocks per candidate-counting
 // Nothing but the NEXT frame's surfel pass needs this done, so it normally runs as extra workgroups of that frame's
 // k_prep (one launch less per frame); k_shard_settle is the stand-alone form for everything that reads the counters first.
 // ---------------------------------------------------------------------------------------------
-struct ShardSettle {
-    uint32_t n;                       // pixel blocks to settle (0: nothing pending) -- as extra workgroups of the next frame's k_prep, or k_shard_settle
-    DevState *st;
-    const uint64_t *validmask, *ownmask, *gmask;
-    uint32_t nwords;
-    const uint32_t *blk_cand, *grp_cand;
-    uint32_t *nf;                     // new / fused sub-counter sets
-    uint64_t *alive;
-    uint32_t *tile_dead;
-    int owner;
-    uint32_t cap_pixels, max_vertices;
-    uint32_t cg;                      // association blocks per candidate group
-};
 
 // NSUB pixel blocks per workgroup (blockDim.x == NSUB * 256): sub-block = threadIdx.x / 256.  No early exit: every thread
 // reaches every barrier.
@@ -265,7 +252,6 @@ __device__ __forceinline__ void shard_settle_body(const ShardSettle &a, uint32_t
         }
     }
 }
-
 
 // ---------------------------------------------------------------------------------------------
 // p0a metricise (depth_metric.frag:15-35) + u8 RGB/semantic pack + LDS-tiled transpose to the
@@ -590,15 +576,6 @@ __device__ __forceinline__ void prep_chain_block(const PrepArgs &a, const ChainA
         a.dcT[q] = make_uint2(__float_as_uint(out), rgbs);
         if (a.keyT) a.keyT[q] = KEY_EMPTY;
     }
-}
-
-// column-major -> row-major read-back helper (tests / GUI textures)
-__global__ void k_untranspose_f32(const float *__restrict__ srcT, float *__restrict__ dst, int W, int H)
-{
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= W * H) return;
-    const int j = p / W, i = p - j * W;
-    dst[p] = srcT[(size_t)i * H + j];
 }
 
 __global__ void k_fill_keys(uint64_t *keyT, int P)

@@ -1,5 +1,5 @@
 // sm_k_track.h -- camera tracking: projective frame-to-model point-to-plane ICP (DESIGN.md "4d. Tracking").
-// Part of sm_kernels.h (included there, in order, inside namespace sm).  The reference has no tracker (its header promises one:
+// Included by sm_track.hip only.  The reference has no tracker (its header promises one:
 // src/SurfelMapping.h:31-34); the vertex / normal rule is the frame's own (geometry.glsl:5-24 as local_surfel restates it).
 //
 // One tracked frame:
@@ -14,6 +14,12 @@
 //   k_track_solve    one workgroup: fixed-order sum of the partials, LDLT in double, T <- exp(xi) T, convergence / failure
 //                    (LOST at any iteration; DEGENERATE when the system of the converged or last iteration is).
 // A device-side `done` word makes every launch after convergence or failure a no-op, so the host waits once per frame.
+
+#pragma once
+
+#include "sm_device.h"
+
+namespace sm {
 
 constexpr int TRACK_BLOCK = 256;
 constexpr int TRACK_MAX_PARTS = 1024;    // workgroups of k_track_reduce at most (each leaves 29 partial sums)
@@ -364,3 +370,5 @@ __global__ __launch_bounds__(256) void k_track_solve(TrackParams tp, const doubl
     if ((converged || ts->iterations >= tp.max_iters) && degenerate) { fail(TRACK_DEGENERATE); return; }
     if (converged) ts->done = 1;
 }
+
+}  // namespace sm

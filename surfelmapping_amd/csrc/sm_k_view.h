@@ -1,5 +1,5 @@
 // sm_k_view.h -- the model view: GlobalModel::renderModel (src/GlobalModel.cpp:683-758) into an image.
-// Part of sm_kernels.h (included there, in order, inside namespace sm); shader citations: /root/reference/src/Shaders/<file>:<line>.
+// Included by sm_view.hip only; shader citations: /root/reference/src/Shaders/<file>:<line>.
 //
 // Surfel mode is draw_surface.vert + draw_surface_adaptive.geom + draw_surface.frag (the program renderModel binds,
 // src/GlobalModel.cpp:23-24); points mode is draw_feedback.vert/.frag (:22).  The `pose` uniform is the identity
@@ -20,7 +20,7 @@
 // Vertex: c = MVP*(v,1), each row ((m[r]*x + m[r+4]*y) + m[r+8]*z) + m[r+12]; xw = ((c.x/c.w)*0.5 + 0.5)*W,
 //   yw likewise with H, zw = (c.z/c.w)*0.5 + 0.5, iw = 1/c.w.  Not drawn (DESIGN.md "Model view"): any vertex with c.w <= 0
 //   (GL would clip the polygon), |xw| or |yw| >= 1e6, or a non-finite zw / iw.
-// Raster: the novel-view renderer's rules (raster_tri, sm_k_aux.h): 24.8 fixed point X = floor(xw*256 + 0.5) (double),
+// Raster: the novel-view renderer's rules (raster_tri, sm_k_io.h): 24.8 fixed point X = floor(xw*256 + 0.5) (double),
 //   64-bit edge functions, top-left fill rule, pixel centres at +0.5, l_i = (float)((double)e_i / (double)area).
 //   Texcoords perspective-correct: wl_i = l_i*iw_i, s = (wl0 + wl1) + wl2, t = ((wl0*t0 + wl1*t1) + wl2*t2) / s;
 //   discarded if tx*tx + ty*ty > 1 (draw_surface.frag:30-31).  Depth screen-linear: zw = (l0*z0 + l1*z1) + l2*z2, kept iff
@@ -40,6 +40,12 @@
 // box covers at most `fp_lane` pixels is rasterised by its own lane, a larger one is appended (one atomic per wave) to an
 // overflow list that k_view_overflow rasterises with one wave per (surfel, slice of its 64-pixel chunks), lanes over pixels.
 // Both paths call view_px_tri, so which path drew a pixel cannot change the image.
+
+#pragma once
+
+#include "sm_device.h"
+
+namespace sm {
 
 struct VVert { long long X, Y; float zw, iw, tx, ty; };
 struct VTri { VVert a, b, c; long long area; int ba, bb, bc; };
@@ -288,3 +294,5 @@ __global__ void k_view_resolve(Model M, const DevState *__restrict__ st, ViewSha
     if (depth) depth[p] = d;
     if (ids) ids[p] = id;
 }
+
+}  // namespace sm

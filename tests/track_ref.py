@@ -25,7 +25,7 @@ def colmajor(m):
 
 
 def rigid_inv_d(m16):
-    """[R^T | -R^T t] of a column-major pose in double (sm_api.hip rigid_inv_d)"""
+    """[R^T | -R^T t] of a column-major pose in double (sm_track.hip rigid_inv_d)"""
     m = np.asarray(m16, np.float64)
     o = np.zeros(16)
     for r in range(3):

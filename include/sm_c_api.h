@@ -300,6 +300,50 @@ int sm_track_frame(sm_ctx *s, const uint16_t *depth_mm, const float *guess16, co
  * parameters (sys29: J^T J upper triangle row-major (21), J^T r (6), sum r^2, inliers; double).  Either output may be NULL. */
 int sm_track_debug(sm_ctx *s, const uint16_t *depth_mm, const float *pose16_eval, int32_t *pred_slot, double *sys29);
 
+/* ---- retirement (DESIGN.md "4e. Retirement") ----
+ * The model grows with the distance driven and MAX_VERTICES is fixed; the reference leaves that to a person (build_map.cpp:204
+ * draws the capacity bar, :235-254 saves the map, :258-263 resets it, the part under the camera included).  Retirement moves out
+ * of the model, in model order, exactly the surfels fusion can no longer reach, and closes the gaps on the GPU.
+ * With the context's tick (sm_counts.tick: the time stamp the NEXT frame will carry), the camera centre c = pose16[12..14] and the
+ * rows m of sm_download_model_aos, surfel i is retired iff, in fp32 without fused multiply-add and in this order,
+ *     age = float(tick) - m[i][7];                      old = age > float(min_age)
+ *     dx, dy, dz = m[i][0..2] - c[0..2];                d2  = (dx*dx + dy*dy) + dz*dz
+ *     far = min_distance <= 0  ||  d2 > min_distance*min_distance        (the product rounded to fp32 once)
+ *     retired = old && far                              (a comparison with a NaN is false; with min_distance <= 0 the
+ *                                                        position is not looked at)
+ * The records written are m[retired], the model afterwards is m[!retired], both in the old order and bit for bit, whatever
+ * compact_period is (slots a deferred-compaction cull has killed are neither).  count = offset = kept; tick, the other counters,
+ * the frame log, the tracker's pose history, the frame planes and the depth filter's "last depth" are untouched; the index map is
+ * not redrawn (as after sm_clean_points / sm_upload_model_aos); the compaction schedule restarts as after an upload.
+ * index_map.vert:45 never draws a surfel whose last update is more than time_delta frames old, so with min_age >= time_delta a
+ * retired surfel could never have been associated or fused again; beyond 1.5 * far_clip no pass reaches it at all.  Smaller
+ * values are allowed. */
+typedef struct sm_retire_params {
+    int32_t min_age;          /* frames since the last update, exclusive */
+    float min_distance;       /* metres from the camera centre, exclusive; <= 0: the age gate alone */
+} sm_retire_params;
+/* min_age = c->time_delta; min_distance = 1.5f * c->far_clip (index_map.vert:45 draws nothing beyond maxDepth * 1.5) */
+int sm_default_retire_params(const sm_config *c, sm_retire_params *p);
+/* pose16 NULL = pose of the last processed frame; params NULL = defaults.  dst12 NULL: *n = how many WOULD be retired, nothing
+ * changes.  cap < that number: SM_E_CAPACITY, nothing changes.  Synchronous (waits for frames in flight, flushes a held-back
+ * association like every entry point that reads the model).
+ * SM_E_ARG: NULL ctx / n, min_age < 0, non-finite min_distance or pose, a call between sm_stage_conflict and sm_stage_cull.
+ * SM_E_UNSUPPORTED: a sharded context or a rig context (a rank holds only its own surfels; the rig indexes them by creation
+ * time) -- for sm_retire, sm_retire_device and sm_set_auto_retire. */
+int sm_retire(sm_ctx *s, const float *pose16, const sm_retire_params *params, float *dst12, uint32_t cap, uint32_t *n);
+/* the same into device memory of this context's GPU (48-byte records, 16-byte aligned); *n is still returned, so one wait */
+int sm_retire_device(sm_ctx *s, const float *pose16, const sm_retire_params *params, float *d_dst12, uint32_t cap, uint32_t *n);
+/* Periodic policy for sm_process_frame / _device / _async: after every frame whose new tick is a multiple of `every`, retire at
+ * that frame's pose and write the records as one map file "<prefix>_%06u.bin" in GlobalModel::downloadMap's format
+ * (u32 count | i32 startId | i32 endId | count*12 f32, src/GlobalModel.cpp:927-932; startId = tick at the previous retirement that
+ * wrote a file or 0, endId = tick - 1), which sm_load_map reads.  An empty retirement writes no file; files are numbered 0,1,2..
+ * in writing order.  The file is written BEFORE the model is changed: if it cannot be written the frame call returns SM_E_ARG
+ * (sm_last_error names the path) and the model is as the frame left it.  That one frame call in `every` waits for the device; all
+ * others are exactly what they are without the policy (no extra launch, copy or wait).  every <= 0 or prefix NULL switches the
+ * policy off (the default). */
+int sm_set_auto_retire(sm_ctx *s, const sm_retire_params *params, int32_t every, const char *path_prefix);
+int sm_auto_retire_stats(sm_ctx *s, uint32_t *files, uint64_t *surfels);     /* written so far */
+
 /* ---- per-pass entry points (GlobalModel / IndexMap methods), synchronous ---- */
 /* Upload RGB / metric depth / semantic textures directly (bypasses p0). */
 int sm_set_frame(sm_ctx *s, const uint8_t *rgb, const float *depth_metric,

@@ -32,6 +32,7 @@ SYMBOLS = (
     "sm_shard_rccl_finalize", "sm_shard_rccl_nranks", "sm_shard_frame_device", "sm_shard_frame", "sm_shard_compact", "sm_shard_export_dense_device",
     "sm_gpu_process_count", "sm_rig_configure", "sm_rig_consolidate", "sm_rig_consolidate_step",
     "sm_default_track_params", "sm_track_frame", "sm_track_debug",
+    "sm_default_retire_params", "sm_retire", "sm_retire_device", "sm_set_auto_retire", "sm_auto_retire_stats",
 )
 
 SM_COLL_SUM, SM_COLL_MIN, SM_COLL_GATHER = 0, 1, 2
@@ -110,6 +111,21 @@ def track_params(**over) -> SmTrackParams:
     """sm_default_track_params with fields overridden (max_iters, dist_thresh, angle_thresh, min_inliers, pixel_stride)"""
     p = SmTrackParams()
     load().sm_default_track_params(C.byref(p))
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+class SmRetireParams(C.Structure):
+    _fields_ = [("min_age", C.c_int32), ("min_distance", C.c_float)]
+
+
+def retire_params(cfg, **over) -> SmRetireParams:
+    """sm_default_retire_params of a config (min_age = time_delta, min_distance = 1.5 * far_clip) with fields overridden"""
+    p = SmRetireParams()
+    load().sm_default_retire_params(C.byref(cfg), C.byref(p))
     for k, v in over.items():
         if not hasattr(p, k):
             raise KeyError(k)
@@ -280,6 +296,11 @@ def load():
     L.sm_default_track_params.argtypes = [C.POINTER(SmTrackParams)]
     L.sm_track_frame.argtypes = [vp, vp, vp, C.POINTER(SmTrackParams), vp, C.POINTER(SmTrackInfo)]
     L.sm_track_debug.argtypes = [vp, vp, vp, vp, vp]
+    L.sm_default_retire_params.argtypes = [C.POINTER(SmConfig), C.POINTER(SmRetireParams)]
+    L.sm_retire.argtypes = [vp, vp, C.POINTER(SmRetireParams), vp, C.c_uint32, u32p]
+    L.sm_retire_device.argtypes = [vp, vp, C.POINTER(SmRetireParams), vp, C.c_uint32, u32p]
+    L.sm_set_auto_retire.argtypes = [vp, C.POINTER(SmRetireParams), C.c_int32, C.c_char_p]
+    L.sm_auto_retire_stats.argtypes = [vp, u32p, C.POINTER(C.c_uint64)]
     for name in SYMBOLS:
         getattr(L, name)          # AttributeError here = the library does not match the header
     _lib = L
@@ -486,6 +507,47 @@ class SurfelMap:
         a, b = C.c_int32(), C.c_int32()
         self._chk(self._L.sm_load_map(self._h, os.fsencode(path), C.byref(a), C.byref(b)), "sm_load_map")
         return a.value, b.value
+
+    # -- retirement (sm_retire, sm_set_auto_retire)
+    def retire(self, pose=None, dry_run=False, **params):
+        """Move the surfels that are older than min_age frames and farther than min_distance from the camera centre out of
+        the model (sm_retire).  pose: a 4x4 camera->world matrix (numpy row/col indexing) or float32[16] column-major; None =
+        the pose of the last processed frame.  params override sm_default_retire_params.  Returns the retired records,
+        float32[n][12] in model order -- or, with dry_run, only how many there would be (nothing changes)."""
+        g = None if pose is None else _mat16(pose)
+        p = retire_params(self.cfg, **params) if params else None
+        pp = C.byref(p) if p is not None else None
+        n = C.c_uint32()
+        self._chk(self._L.sm_retire(self._h, _ptr(g), pp, None, 0, C.byref(n)), "sm_retire")
+        if dry_run:
+            return int(n.value)
+        out = np.zeros((n.value, 12), np.float32)
+        # (a destination is always given, also for n = 0: a NULL one would be another dry run)
+        dst = out if n.value else np.zeros((1, 12), np.float32)
+        self._chk(self._L.sm_retire(self._h, _ptr(g), pp, _ptr(dst), n.value, C.byref(n)), "sm_retire")
+        return out
+
+    def set_auto_retire(self, every, prefix, **params):
+        """After every frame whose new tick is a multiple of `every`, retire at that frame's pose into the map file
+        "<prefix>_%06u.bin" (sm_set_auto_retire; load_map reads such a file).  every <= 0 or prefix None: off."""
+        p = retire_params(self.cfg, **params) if params else None
+        self._chk(self._L.sm_set_auto_retire(self._h, C.byref(p) if p is not None else None, int(every),
+                                             None if prefix is None else os.fsencode(prefix)), "sm_set_auto_retire")
+
+    def auto_retire_stats(self):
+        """(map files, surfels) the periodic policy has written so far"""
+        f, n = C.c_uint32(), C.c_uint64()
+        self._chk(self._L.sm_auto_retire_stats(self._h, C.byref(f), C.byref(n)), "sm_auto_retire_stats")
+        return int(f.value), int(n.value)
+
+    def retire_stats(self):
+        """device times in ms of the last retirement made with SM_RETIRE_TIMING=1 (sm_debug_retire_stats, not part of the C-ABI
+        header): dict(mark, scan, gather, compact, bounds), or None if it was not timed"""
+        f = self._L.sm_debug_retire_stats
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        ms = (C.c_float * 5)()
+        self._chk(f(self._h, ms), "sm_debug_retire_stats")
+        return None if ms[0] < 0 else dict(zip(("mark", "scan", "gather", "compact", "bounds"), [float(x) for x in ms]))
 
     # -- IndexMap
     def download_index_map(self):

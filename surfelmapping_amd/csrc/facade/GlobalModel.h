@@ -68,6 +68,21 @@ public:
     }
     void resetBuffer() { sm_reset(ctx_); }
 
+    // Not in the reference, whose operator saves the whole map and resets it when the capacity bar fills (build_map.cpp:204,
+    // 235-263): moves the surfels last updated more than minAge frames ago and farther than minDistance metres from the
+    // camera centre of `pose` out of the model into `out` (12 floats each, model order), the rest stays (sm_retire).
+    bool retire(const Eigen::Matrix4f &pose, int minAge, float minDistance, std::vector<float> &out)
+    {
+        const sm_retire_params p = {minAge, minDistance};
+        uint32_t n = 0;
+        out.clear();
+        if (sm_retire(ctx_, pose.data(), &p, nullptr, 0, &n) != SM_OK) { std::printf("retire: %s\n", sm_last_error()); return false; }
+        out.resize((size_t)n * 12 + 12);             // never empty: a null destination would be a dry run
+        if (sm_retire(ctx_, pose.data(), &p, out.data(), n, &n) != SM_OK) { std::printf("retire: %s\n", sm_last_error()); out.clear(); return false; }
+        out.resize((size_t)n * 12);
+        return true;
+    }
+
     // model read-back in the reference's AoS layout (12 floats / surfel, src/Config.cpp:17-32)
     std::vector<float> downloadModel()
     {

@@ -186,6 +186,30 @@ public:
 
     // extras of the HIP core
     sm_ctx *context() { return ctx_; }
+    // The replacement of the operator's save / reset buttons (build_map.cpp:235-263) for a headless run: after every `every`-th
+    // frame the surfels that fusion can no longer reach (older than Config's time delta, farther than 1.5 farClip from the
+    // camera) leave the model for the map file "<prefix>_%06u.bin", which uploadMap reads (sm_set_auto_retire).  every <= 0: off.
+    // minAge / minDistance, if not negative, replace those two defaults.
+    bool setAutoRetire(int every, const std::string &prefix, int minAge = -1, float minDistance = -1.0f)
+    {
+        sm_config c;
+        sm_default_config(&c, Config::W(), Config::H(), Config::fx(), Config::fy(), Config::cx(), Config::cy());
+        c.far_clip = Config::farClip();
+        sm_retire_params p;
+        sm_default_retire_params(&c, &p);
+        if (minAge >= 0) p.min_age = minAge;
+        if (minDistance >= 0.0f) p.min_distance = minDistance;
+        if (sm_set_auto_retire(ctx_, &p, every, prefix.c_str()) == SM_OK) return true;
+        std::printf("setAutoRetire: %s\n", sm_last_error());
+        return false;
+    }
+    // map files written so far and the surfels in them
+    std::pair<unsigned, unsigned long long> autoRetireStats()
+    {
+        uint32_t f = 0; uint64_t n = 0;
+        sm_auto_retire_stats(ctx_, &f, &n);
+        return {f, (unsigned long long)n};
+    }
     // (sm_sync first: with SM_FACADE_ASYNC frames may still be in flight, and sm_get_counts returns the counters of the last wait)
     sm_counts counts() { sm_counts c{}; (void)sm_sync(ctx_); sm_get_counts(ctx_, &c); return c; }
 

@@ -1297,7 +1297,8 @@ int sm_process_frame_device(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_d
     if (!s || !d_rgb || !pose16) { g_err = "sm_process_frame_device: null argument"; return SM_E_ARG; }
     HIPCK(hipSetDevice(s->cfg.device));
     // a null depth / semantic keeps the previous texture (src/SurfelMapping.cpp:124-128)
-    return enqueue_frame(s, d_rgb, d_depth_mm ? d_depth_mm : s->d_depth_raw, d_semantic ? d_semantic : s->d_sem, pose16);
+    const int rc = enqueue_frame(s, d_rgb, d_depth_mm ? d_depth_mm : s->d_depth_raw, d_semantic ? d_semantic : s->d_sem, pose16);
+    return rc ? rc : auto_retire_after_frame(s);
 }
 
 int sm_process_frame(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const uint8_t *semantic, const float *pose16)
@@ -1308,7 +1309,9 @@ int sm_process_frame(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, co
     if (rc) return rc;
     rc = enqueue_frame(s, s->d_rgb, s->d_depth_raw, s->d_sem, pose16);
     if (rc) return rc;
-    return sm_sync(s);
+    rc = sm_sync(s);                     // (a sticky SM_E_CAPACITY of this frame is still reported when the policy retires after it)
+    const int rr = auto_retire_after_frame(s);
+    return rc ? rc : rr;
 }
 
 void *sm_host_alloc(sm_ctx *s, size_t bytes)
@@ -1409,7 +1412,7 @@ int sm_process_frame_async(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_
     // a frame without its own depth / semantic image read another set's: that set is busy until this frame has prepared too
     for (int o : {s->in_depth_slot, s->in_sem_slot})
         if (o >= 0 && o != slot) { HIPCK(hipEventRecord(s->in[o].ev_free, s->stream)); s->in[o].used = true; }
-    return rc;
+    return rc ? rc : auto_retire_after_frame(s);
 }
 
 int sm_inputs_consumed(sm_ctx *s)

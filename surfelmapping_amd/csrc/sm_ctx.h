@@ -8,6 +8,7 @@
 //   sm_track.hip     tracking (sm_track_*)
 //   sm_rccl.hip      the RCCL binding (sm_shard_rccl_*)
 //   sm_rig.hip       rig consolidation (sm_rig_*)
+//   sm_retire.hip    retirement (sm_retire*, sm_set_auto_retire)
 #pragma once
 
 #include "../../include/sm_c_api.h"
@@ -117,6 +118,21 @@ struct ModelView {
     Event ev[4];
     // every user of the export scratch (ensure_export) may overwrite the overflow count
     void scratch_reused() { ovf_valid = false; }
+};
+
+// retirement (sm_retire.hip, sm_k_retire.h): scratch allocated by the first call, the periodic policy and its tally
+struct Retire {
+    Dev<uint64_t> d_mask;              // 1 bit per slot: retired by the last mark
+    Dev<uint32_t> d_tile_ret, d_tile_base, d_total;   // retired per tile, their exclusive prefix, (total, slots marked)
+    int32_t every = 0;                 // sm_set_auto_retire: 0 = off
+    sm_retire_params params{};
+    std::string prefix;
+    Host<float> h_stage;               // pinned: one chunk of records on its way into a map file
+    uint32_t files = 0;                // map files written so far
+    uint64_t surfels = 0;              // ... and the surfels in them
+    int32_t last_tick = 0;             // tick at the last retirement that wrote a file (the next file's startId)
+    bool timed = false, stats_valid = false;   // SM_RETIRE_TIMING=1: events around every step of the last call
+    Event ev[8];
 };
 
 }  // namespace sm_impl
@@ -257,6 +273,7 @@ struct sm_ctx {
     size_t export_bytes = 0;
     ModelView rm;
     Tracker trk;
+    Retire ret;
     // host frame state (src/SurfelMapping.h:100-103)
     int tick = 0;
     bool ref_set = false;
@@ -300,5 +317,7 @@ int clean_points_device(sm_ctx *s, const uint16_t *d_depth_mm, const uint8_t *d_
 int ss_collective(sm_ctx *s, const void *send, void *recv, size_t count, int op);
 // ---- sm_model_io.hip ----
 void export_aos(sm_ctx *s, float *dst12, uint32_t first, uint32_t n);   // k_export_aos on the context's stream
+// ---- sm_retire.hip ----
+int auto_retire_after_frame(sm_ctx *s);           // the periodic policy: called once a frame is enqueued (one test unless it is due)
 
 }  // namespace sm_impl

@@ -1,0 +1,271 @@
+// sm_retire.hip -- retirement (sm_retire*, the periodic policy of sm_set_auto_retire): surfels that fusion can no longer reach
+// leave the model for a caller's buffer or a map file, and the existing compaction closes the gaps.  Kernels: sm_k_retire.h.
+#include "sm_ctx.h"
+#include "sm_k_retire.h"
+
+#include <cmath>
+#include <cstdlib>
+
+using namespace sm;
+
+namespace {
+
+constexpr uint32_t CHUNK = 1u << 22;             // surfels per staging chunk, as sm_download_model_aos
+constexpr uint32_t FILE_CHUNK = 1u << 20;        // ... and per write of the periodic policy's map file (48 MiB of pinned staging)
+
+int grid_tiles(uint32_t slots)
+{
+    const uint64_t tiles = ((uint64_t)slots + TILE - 1) / TILE;
+    return (int)std::min<uint64_t>(std::max<uint64_t>(tiles, 1), MAX_GRID);
+}
+
+int tic(sm_ctx *s, int i)
+{
+    if (s->ret.timed) HIPCK(hipEventRecord(s->ret.ev[i], s->stream));
+    return SM_OK;
+}
+
+int check_args(sm_ctx *s, const float *pose16, const sm_retire_params *p, const char *who)
+{
+    if (s->ss_on || s->rig_on) {
+        g_err = std::string(who) + ": a sharded or rig context holds only its own surfels";
+        return SM_E_UNSUPPORTED;
+    }
+    if (p && (p->min_age < 0 || !std::isfinite(p->min_distance))) { g_err = std::string(who) + ": bad parameters"; return SM_E_ARG; }
+    if (pose16)
+        for (int i = 0; i < 16; ++i)
+            if (!std::isfinite(pose16[i])) { g_err = std::string(who) + ": non-finite pose"; return SM_E_ARG; }
+    if (s->pending_cull) { g_err = std::string(who) + " between sm_stage_conflict and sm_stage_cull"; return SM_E_ARG; }
+    return SM_OK;
+}
+
+int ensure_scratch(sm_ctx *s)
+{
+    if (s->ret.d_mask) return SM_OK;
+    Dev<uint64_t> mask;
+    Dev<uint32_t> tile_ret, tile_base, total;
+    int rc;
+    if ((rc = dalloc(mask, s->alive_words)) || (rc = dalloc(tile_ret, s->dead_tiles)) || (rc = dalloc(tile_base, s->dead_tiles)) ||
+        (rc = dalloc(total, 2)))
+        return rc;
+    const char *e = std::getenv("SM_RETIRE_TIMING");
+    if (e && e[0] == '1')
+        for (auto &ev : s->ret.ev) HIPCK(hipEventCreate(ev.put()));
+    s->ret.d_mask = std::move(mask); s->ret.d_tile_ret = std::move(tile_ret); s->ret.d_tile_base = std::move(tile_base);
+    s->ret.d_total = std::move(total);
+    return SM_OK;
+}
+
+// Steps 1-2: the retired masks, per-tile counts and bases of the model as it stands; *n = how many would be retired.  Waits for
+// the frames in flight; changes nothing in the model.
+int retire_mark(sm_ctx *s, const float *pose16, const sm_retire_params *params, uint32_t *n)
+{
+    sm_retire_params p;
+    if (params) p = *params;
+    else sm_default_retire_params(&s->cfg, &p);
+    const float *pose = pose16 ? pose16 : s->last_pose;
+    int rc = ensure_scratch(s);
+    if (rc) return rc;
+    if ((rc = pull_state(s))) return rc;         // flushes a held-back association, completes the last frame's statistics
+    s->ret.timed = (bool)s->ret.ev[0];
+    s->ret.stats_valid = false;
+    RetireArgs ra;
+    ra.tick = (float)s->tick;
+    ra.min_age = (float)p.min_age;
+    ra.cx = pose[12]; ra.cy = pose[13]; ra.cz = pose[14];
+    ra.md2 = p.min_distance * p.min_distance;
+    ra.use_dist = p.min_distance <= 0.0f ? 0 : 1;
+    if ((rc = tic(s, 0))) return rc;
+    hipLaunchKernelGGL(k_retire_mark, dim3(grid_tiles(s->h_state->count)), dim3(256), 0, s->stream, s->M, s->d_state, ra, s->d_alive,
+                       s->ret.d_mask, s->ret.d_tile_ret);
+    if ((rc = tic(s, 1))) return rc;
+    hipLaunchKernelGGL(k_retire_scan, dim3(1), dim3(1024), 0, s->stream, s->d_state, s->ret.d_tile_ret, s->ret.d_tile_base, s->ret.d_total);
+    HIPCK(hipGetLastError());
+    if ((rc = tic(s, 2))) return rc;
+    uint32_t tot[2] = {0, 0};
+    HIPCK(hipMemcpyAsync(tot, s->ret.d_total, sizeof tot, hipMemcpyDeviceToHost, s->stream));
+    HIPCK(hipStreamSynchronize(s->stream));
+    *n = tot[0];
+    return SM_OK;
+}
+
+void launch_gather(sm_ctx *s, float *d_dst, uint32_t r0, uint32_t r1)
+{
+    hipLaunchKernelGGL(k_retire_gather, dim3(grid_tiles(s->h_state->count)), dim3(256), 0, s->stream, s->M, s->d_state, s->ret.d_mask,
+                       s->ret.d_tile_ret, s->ret.d_tile_base, s->ret.d_total, (float4 *)d_dst, r0, r1);
+}
+
+// Step 3 into host memory, one staging chunk at a time
+int retire_gather_host(sm_ctx *s, float *dst12, uint32_t n)
+{
+    int rc = tic(s, 3);
+    if (rc) return rc;
+    if (n && (rc = ensure_export(s, (size_t)std::min(n, CHUNK) * 48))) return rc;
+    for (uint32_t first = 0; first < n; first += CHUNK) {
+        const uint32_t m = std::min(CHUNK, n - first);
+        launch_gather(s, (float *)s->d_export.get(), first, first + m);
+        HIPCK(hipGetLastError());
+        HIPCK(hipMemcpyAsync(dst12 + (size_t)first * 12, s->d_export, (size_t)m * 48, hipMemcpyDeviceToHost, s->stream));
+        HIPCK(hipStreamSynchronize(s->stream));
+    }
+    return tic(s, 4);
+}
+
+// Step 4: the retired become dead slots, the compaction that exists squeezes them out, the state is what an upload of the
+// kept surfels would leave (sm_upload_model_aos), the tile boxes are rebuilt
+int retire_commit(sm_ctx *s, uint32_t n)
+{
+    int rc = tic(s, 5);
+    if (rc) return rc;
+    if (n) {
+        const uint32_t words = (uint32_t)(((uint64_t)s->h_state->count + TILE - 1) / TILE) * TILE_WORDS;
+        hipLaunchKernelGGL(k_retire_clear, dim3(std::min<uint32_t>((words + 255) / 256, MAX_GRID)), dim3(256), 0, s->stream, s->d_state,
+                           s->ret.d_mask, s->ret.d_tile_ret, s->ret.d_total, s->d_alive, s->d_tile_dead);
+        HIPCK(hipGetLastError());
+        s->maybe_garbage = true;
+    }
+    if ((rc = ensure_compact(s))) return rc;
+    if ((rc = pull_state(s))) return rc;
+    DevState &d = *s->h_state;
+    d.offset = d.count;
+    d.garbage = 0; d.garbage_prev = 0; d.first_live = 0; d.do_compact = 0;
+    s->culls_since_compact = 0;                  // the compaction schedule restarts, as after an upload
+    if ((rc = push_state(s))) return rc;
+    if ((rc = tic(s, 6))) return rc;
+    if ((rc = rebuild_bounds(s, 0, d.count))) return rc;
+    if ((rc = tic(s, 7))) return rc;
+    if (s->ret.timed) { HIPCK(hipStreamSynchronize(s->stream)); s->ret.stats_valid = true; }
+    return pull_state(s);
+}
+
+int retire_common(sm_ctx *s, const float *pose16, const sm_retire_params *params, float *dst, bool device, uint32_t cap, uint32_t *n,
+                  const char *who)
+{
+    if (!s || !n) return SM_E_ARG;
+    int rc = check_args(s, pose16, params, who);
+    if (rc) return rc;
+    if (device && hip_runtime_conflict(who)) return SM_E_HIP;
+    HIPCK(hipSetDevice(s->cfg.device));
+    if ((rc = retire_mark(s, pose16, params, n))) return rc;
+    if (!dst) return SM_OK;                      // dry run
+    if (cap < *n) { g_err = std::string(who) + ": destination too small"; return SM_E_CAPACITY; }
+    if (device) {
+        if ((rc = tic(s, 3))) return rc;
+        if (*n) launch_gather(s, dst, 0u, *n);
+        HIPCK(hipGetLastError());
+        if ((rc = tic(s, 4))) return rc;
+    } else if ((rc = retire_gather_host(s, dst, *n))) return rc;
+    return retire_commit(s, *n);
+}
+
+}  // namespace
+
+// The periodic policy, called by the frame entry points after a frame has been enqueued: nothing but this test on the
+// frames that do not retire.
+int sm_impl::auto_retire_after_frame(sm_ctx *s)
+{
+    Retire &r = s->ret;
+    if (r.every <= 0 || s->tick <= 0 || s->tick % r.every != 0) return SM_OK;
+    uint32_t n = 0;
+    int rc = retire_mark(s, nullptr, &r.params, &n);       // at that frame's pose
+    if (rc) return rc;
+    if ((rc = tic(s, 3))) return rc;
+    if (n) {
+        // u32 count | i32 startId | i32 endId | count*12 f32   (src/GlobalModel.cpp:927-932), on disk BEFORE the model changes;
+        // one chunk at a time through pinned staging, so that a large retirement needs neither a host copy of its own nor
+        // gigabytes of staging
+        if (!r.h_stage) HIPCK(hipHostMalloc(r.h_stage.put(), (size_t)FILE_CHUNK * 48, hipHostMallocDefault));
+        if ((rc = ensure_export(s, (size_t)std::min(n, FILE_CHUNK) * 48))) return rc;
+        char name[32];
+        snprintf(name, sizeof name, "_%06u.bin", r.files);
+        const std::string path = r.prefix + name;
+        const int32_t start_id = r.last_tick, end_id = s->tick - 1;
+        FILE *f = fopen(path.c_str(), "wb");
+        if (!f) { g_err = path + " is not open!"; return SM_E_ARG; }
+        bool ok = fwrite(&n, 4, 1, f) == 1 && fwrite(&start_id, 4, 1, f) == 1 && fwrite(&end_id, 4, 1, f) == 1;
+        hipError_t he = hipSuccess;
+        for (uint32_t first = 0; ok && he == hipSuccess && first < n; first += FILE_CHUNK) {
+            const uint32_t m = std::min(FILE_CHUNK, n - first);
+            launch_gather(s, (float *)s->d_export.get(), first, first + m);
+            if ((he = hipGetLastError()) == hipSuccess)
+                he = hipMemcpyAsync(r.h_stage, s->d_export, (size_t)m * 48, hipMemcpyDeviceToHost, s->stream);
+            if (he == hipSuccess) he = hipStreamSynchronize(s->stream);
+            if (he == hipSuccess) ok = fwrite(r.h_stage, 48, m, f) == m;
+        }
+        ok = (fclose(f) == 0) && ok;
+        if (he != hipSuccess || !ok) {
+            std::remove(path.c_str());           // no half-written map file is left behind
+            if (he != hipSuccess) { set_err("retirement into a map file", he, __FILE__, __LINE__); return SM_E_HIP; }
+            g_err = path + " saved err!!";
+            return SM_E_ARG;
+        }
+        r.files++;
+        r.surfels += n;
+        r.last_tick = s->tick;
+    }
+    if ((rc = tic(s, 4))) return rc;
+    return retire_commit(s, n);
+}
+
+extern "C" {
+
+int sm_default_retire_params(const sm_config *c, sm_retire_params *p)
+{
+    if (!c || !p) return SM_E_ARG;
+    p->min_age = c->time_delta;
+    p->min_distance = 1.5f * c->far_clip;
+    return SM_OK;
+}
+
+int sm_retire(sm_ctx *s, const float *pose16, const sm_retire_params *params, float *dst12, uint32_t cap, uint32_t *n)
+{
+    return retire_common(s, pose16, params, dst12, false, cap, n, "sm_retire");
+}
+
+int sm_retire_device(sm_ctx *s, const float *pose16, const sm_retire_params *params, float *d_dst12, uint32_t cap, uint32_t *n)
+{
+    if (d_dst12 && ((uintptr_t)d_dst12 & 15u)) { g_err = "sm_retire_device: destination not 16-byte aligned"; return SM_E_ARG; }
+    return retire_common(s, pose16, params, d_dst12, true, cap, n, "sm_retire_device");
+}
+
+int sm_set_auto_retire(sm_ctx *s, const sm_retire_params *params, int32_t every, const char *path_prefix)
+{
+    if (!s) return SM_E_ARG;
+    sm_retire_params p;
+    if (params) p = *params;
+    else sm_default_retire_params(&s->cfg, &p);
+    int rc = check_args(s, nullptr, &p, "sm_set_auto_retire");
+    if (rc) return rc;
+    Retire &r = s->ret;
+    if (every <= 0 || !path_prefix) { r.every = 0; r.prefix.clear(); return SM_OK; }
+    HIPCK(hipSetDevice(s->cfg.device));
+    if ((rc = ensure_scratch(s))) return rc;     // so that the frame that retires first allocates nothing
+    r.params = p;
+    r.every = every;
+    r.prefix = path_prefix;
+    return SM_OK;
+}
+
+int sm_auto_retire_stats(sm_ctx *s, uint32_t *files, uint64_t *surfels)
+{
+    if (!s) return SM_E_ARG;
+    if (files) *files = s->ret.files;
+    if (surfels) *surfels = s->ret.surfels;
+    return SM_OK;
+}
+
+// diagnostic, not part of the C-ABI header: device times in ms of the last retirement made with SM_RETIRE_TIMING=1 in the
+// environment when the context retired first -- mark, scan, gather (with the copies of its chunks when the destination is host
+// memory), clear + compaction, tile bounds; -1 each if that call was not timed or ended before the model changed
+int sm_debug_retire_stats(sm_ctx *s, float *ms5)
+{
+    if (!s || !ms5) return SM_E_ARG;
+    for (int i = 0; i < 5; ++i) ms5[i] = -1.0f;
+    if (!s->ret.timed || !s->ret.stats_valid) return SM_OK;
+    HIPCK(hipSetDevice(s->cfg.device));
+    const int a[5] = {0, 1, 3, 5, 6}, b[5] = {1, 2, 4, 6, 7};
+    for (int i = 0; i < 5; ++i) HIPCK(hipEventElapsedTime(&ms5[i], s->ret.ev[a[i]], s->ret.ev[b[i]]));
+    return SM_OK;
+}
+
+}  // extern "C"

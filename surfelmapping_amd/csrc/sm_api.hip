@@ -172,16 +172,57 @@ bool gpu_shared_with_other_process(int dev)
     return cached[dev] > 1;
 }
 
-bool compaction_needs_tickets(int dev)
+bool compaction_needs_tickets(const sm_ctx *s)
 {
-    static const char *env = std::getenv("SM_COMPACT_TICKETS");      // "1": always, "0": never (contexts known not to overlap)
-    if (env) return env[0] != '0';
+    const int dev = s->cfg.device;
+    if (s->sw.compact_tickets >= 0) return s->sw.compact_tickets != 0;
     if (dev < 0 || dev >= MAX_DEV) return true;
     {
         std::lock_guard<std::mutex> lk(g_compact_mu);
         if (g_ctx_on_dev[dev] > 1) return true;
     }
     return gpu_shared_with_other_process(dev);
+}
+
+// every SM_* switch of this source, once per context (sm_create); Switches explains them
+Switches read_switches()
+{
+    Switches sw;
+    auto off = [](const char *name) { const char *e = std::getenv(name); return e && e[0] == '0'; };
+    auto num = [](const char *name, long unset) { const char *e = std::getenv(name); return e ? std::atol(e) : unset; };
+    sw.defer_assoc = !off("SM_DEFER_ASSOC");
+    sw.two_launch = !off("SM_TWO_LAUNCH");
+    sw.pass_split = (int)num("SM_PASS_SPLIT", 0);
+    if (const char *e = std::getenv("SM_PASS_TRACE")) { sw.trace = true; sw.trace_prefix = e; }
+    if (std::getenv("SM_COMPACT_TICKETS")) sw.compact_tickets = off("SM_COMPACT_TICKETS") ? 0 : 1;
+    sw.capacity_wait_us = num("SM_CAPACITY_WAIT_US", 2000);
+    sw.check_alive = std::getenv("SM_CHECK_ALIVE") != nullptr;
+    if (std::getenv("SM_PASS_WG_PER_CU")) sw.pass_wg_per_cu = (int)std::max(1l, num("SM_PASS_WG_PER_CU", 1));
+    if (std::getenv("SM_COMPACT_WG_PER_CU")) sw.compact_wg_per_cu = (int)std::max(1l, num("SM_COMPACT_WG_PER_CU", 1));
+    return sw;
+}
+
+// Workgroups of k_surfel_pass and of k_compact that are resident at once on `device`; left as they are where the device cannot be asked.
+void resident_grids(const Switches &sw, int device, int *pass_grid, int *compact_grid)
+{
+    int cus = 0, per_cu = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) return;
+    // k_surfel_pass: with more workgroups than the chip holds at once the surplus starts when the first ones are done --
+    // on a model where every tile has work (20 M scattered surfels: ~10 tiles per workgroup) that is a second pass at an
+    // eighth of the occupancy.  Grid = what is resident; tiles go round-robin.  (sw.pass_wg_per_cu overrides.)
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_surfel_pass<1>, 256, 0) == hipSuccess && per_cu > 0) {
+        // the occupancy API over-reports by one block per CU here (measured; MI355X_MICROARCH.md)
+        const int want = sw.pass_wg_per_cu ? sw.pass_wg_per_cu : std::max(1, per_cu - 1);
+        *pass_grid = std::max(256, std::min(cus * want, MAX_GRID));
+    }
+    // the in-place compaction needs every workgroup of k_compact resident at once
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_compact<true>, 256, 0) == hipSuccess && per_cu > 0) {
+        // the occupancy API can over-report by one block per CU (MI355X_MICROARCH.md): stay at <= 4 and below it
+        // <= 4 per CU: in that range the limit is VGPR/LDS-bound and the API is exact; above it keep a margin
+        // (sw.compact_wg_per_cu overrides the margin for experiments)
+        const int want = sw.compact_wg_per_cu ? std::min(per_cu, sw.compact_wg_per_cu) : std::min(per_cu, 4);
+        *compact_grid = std::max(1, cus * want);
+    }
 }
 
 int alloc_set(SetBufs &b, size_t cap)
@@ -195,10 +236,6 @@ int grid_surfels(const sm_ctx *s)
     const uint64_t tiles = ((uint64_t)s->count_bound + TILE - 1) / TILE;
     return (int)std::min<uint64_t>(std::max<uint64_t>(tiles, 1), MAX_GRID);
 }
-
-// a direct-append frame leaves its new / fused totals, the dead-slot total and its log entry to be completed by the next
-// frame's k_pass_fixup; everything else that reads them asks for the completion first
-int flush_assoc(sm_ctx *s);
 
 // SM_CHECK_ALIVE=1 (diagnostic): check the alive-bits / dead-count invariant after a stage; reported by sm_sync
 void check_alive(sm_ctx *s, uint32_t stage)
@@ -231,83 +268,110 @@ static inline uint32_t assoc_wgs(const sm_ctx *s)
     return (uint32_t)(s->n_pix_blocks + 1) / 2u;
 }
 
-// `chain`: the frame runs the depth pre-processing chain p0a..p0e (preprocess = 1): the launch is k_assoc_prep<., true>, whose
-// image workgroups are chain tiles (prep_chain_block) -- with or without a held-back association to carry
-int launch_prep(sm_ctx *s, const uint8_t *rgb, const uint16_t *raw, const uint8_t *sem, const float *dm,
-                const FrameParams &fp, bool clear_keys, hipStream_t st = nullptr, const ChainArgs *chain = nullptr)
+// the one launch site of each held-back step (HeldBack: who holds them back, who takes them)
+int launch_fixup(sm_ctx *s, const FrameParams &fp, const FixArgs &x)
 {
-    const int tiles = ((s->W + 31) / 32) * ((s->H + 31) / 32);
-    // the frame's tile skip flags for the one-pass surfel kernel: a few extra workgroups (128 tiles each per round)
-    TilePrep tp;
-    memset(&tp, 0, sizeof tp);
-    s->n_prep_blocks = 0;
-    if (clear_keys && s->want_list) {
-        const uint64_t ntl = ((uint64_t)s->count_bound + TILE - 1) / TILE;
-        tp.nfb = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((ntl + 1023) / 1024, 1), 64);     // one tile per thread (k_prep: 1 024 threads)
-        tp.st = s->d_state; tp.tb = s->d_tb; tp.tile_flags = s->d_tile_flags; tp.wave_cnt = s->d_wave_cnt; tp.prep_part = s->d_prep_part;
-        s->n_prep_blocks = tp.nfb;
-    }
-    if (s->ev) s->ev_merged[s->ev_frames % EV_RING] = s->merge_assoc || chain != nullptr;
-    if (s->merge_assoc || chain) {
-        // the held-back association of the previous frame (if any) + this frame's tile flags + its image / chain tiles in one launch
-        const bool carry = s->merge_assoc;
-        s->merge_assoc = false;
-        if (carry) s->assoc_pending = false;
-        if (chain && s->ss_settle_pending) {          // (a sharded stream's settle step rides on k_prep only: stand-alone here)
-            s->ss_settle_pending = false;
-            hipLaunchKernelGGL(k_shard_settle, dim3(s->ss_settle.n), dim3(PIX_BLOCK), 0, s->stream, s->ss_settle);
-            HIPCK(hipGetLastError());
-        }
-        if (tp.nfb) {
-            const uint64_t ntl = ((uint64_t)s->count_bound + TILE - 1) / TILE;
-            tp.nfb = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((ntl + 255) / 256, 1), 128);     // one tile per thread
-            if (carry) { tp.grp_cand = s->assoc_args.grp_cand; tp.n_grp = s->assoc_args.n_grp; tp.prev_time = s->assoc_args.fp.time; }
-            s->n_prep_blocks = tp.nfb;
-        }
-        // two-launch frame: the held-back association's frame has not had its fixup step yet -- its publisher and repair crew
-        // open this launch, the association and the flag workgroups check for themselves whether they have to wait for them
-        FixArgs fx;
-        memset(&fx, 0, sizeof fx);
-        uint32_t n_fix = 0;
-        s->assoc_args.slow_conf_sub = nullptr; s->assoc_args.slow_need = 0u;
-        if (carry && s->fix_pending) {
-            s->fix_pending = false;
-            fx = s->fix_args;
-            n_fix = 1u + fx.n_crew;
-            s->assoc_args.slow_conf_sub = fx.conf_sub; s->assoc_args.slow_need = n_fix;
-            if (tp.nfb) { tp.slow_conf_sub = fx.conf_sub; tp.slow_cap = s->assoc_args.fp.conflict_cap; tp.slow_need = n_fix; tp.slow_par = s->assoc_args.fp.par; }
-        }
-        PrepArgs pa;
-        pa.rgb = rgb; pa.depth_raw = raw; pa.sem = sem; pa.depth_f32 = dm; pa.depthT = s->d_depthT; pa.rgbsT = s->d_rgbsT;
-        pa.keyT = clear_keys ? s->d_keyT : nullptr; pa.dcT = s->d_dcT;
-        pa.conf_sub = clear_keys ? s->d_conf_sub + SUB_SET * s->conf_sub_set : nullptr;
-        const uint32_t n_assoc = carry ? assoc_wgs(s) : 0u;
-        ChainArgs ca;
-        memset(&ca, 0, sizeof ca);
-        uint32_t n_img = (uint32_t)tiles;
-        if (chain) { ca = *chain; n_img = (uint32_t)(((s->W + CH_TX - 1) / CH_TX) * ((s->H + CH_TY - 1) / CH_TY)); }
-        if (s->d_ap_trace) { s->ap_trace_n[0] = (int)n_assoc; s->ap_trace_n[1] = (int)tp.nfb; s->ap_trace_n[2] = (int)n_img; s->ap_trace_n[3] = (int)n_fix; }    // (chain: dispatched image | association | flags; the fixup workgroups before them)
-        const dim3 grid(n_fix + tp.nfb + n_assoc + n_img);
-        if (chain) hipLaunchKernelGGL((k_assoc_prep<true>), grid, dim3(PIX_BLOCK), 0, s->stream, s->assoc_args, pa, fp, tp, n_assoc, n_img, ca, fx, n_fix, s->d_ap_trace);
-        else hipLaunchKernelGGL((k_assoc_prep<false>), grid, dim3(PIX_BLOCK), 0, s->stream, s->assoc_args, pa, fp, tp, n_assoc, n_img, ca, fx, n_fix, s->d_ap_trace);
-        HIPCK(hipGetLastError());
-        return SM_OK;
-    }
-    // the previous frame of a sharded stream is finished by extra workgroups of this launch (on the main stream only)
-    ShardSettle ss;
-    memset(&ss, 0, sizeof ss);
-    if (s->ss_settle_pending && (!st || st == s->stream)) { ss = s->ss_settle; s->ss_settle_pending = false; }
-    // a frame's k_prep (clear_keys) also zeroes the conflict sub-counters of that frame (set chosen by begin_frame)
-    hipLaunchKernelGGL(k_prep, dim3(tiles + tp.nfb + (ss.n + 3u) / 4u), dim3(1024), 0, st ? st : s->stream, rgb, raw, sem, dm, s->d_depthT, s->d_rgbsT,
-                       clear_keys ? s->d_keyT : nullptr, fp, s->d_dcT, clear_keys ? s->d_conf_sub + SUB_SET * s->conf_sub_set : nullptr, tp, ss);
+    hipLaunchKernelGGL(k_pass_fixup, dim3(x.n_crew + 1), dim3(256), 0, s->stream, s->M, s->d_state, fp, x);
     HIPCK(hipGetLastError());
     return SM_OK;
 }
 
-int mark(sm_ctx *s, int which, bool timed)
+int launch_assoc(sm_ctx *s, const AssocArgs &a, uint32_t stage)
 {
-    if (timed && s->ev) HIPCK(hipEventRecord(s->ev[which][s->ev_frames % EV_RING], s->stream));
+    hipLaunchKernelGGL((k_associate_direct<false>), dim3(assoc_wgs(s)), dim3(PIX_BLOCK), 0, s->stream, a, ShardArgs{});
+    HIPCK(hipGetLastError());
+    check_alive(s, stage + 16u * (uint32_t)(s->tick & 0xFFFF));
     return SM_OK;
+}
+
+int launch_settle(sm_ctx *s, const ShardSettle &ss)
+{
+    hipLaunchKernelGGL(k_shard_settle, dim3(ss.n), dim3(PIX_BLOCK), 0, s->stream, ss);
+    HIPCK(hipGetLastError());
+    return SM_OK;
+}
+
+// The held-back work in the order it must complete.  `all` = false stops after the association: what a frame that cannot carry
+// the previous frame's association needs (its statistics are still completed by this frame's fixup publisher).
+int complete_held(sm_ctx *s, bool all)
+{
+    FixArgs *fx;
+    if (const AssocArgs *a = s->held.take_assoc(fx)) {
+        // two-launch frame: that frame's fixup step has not run either -- in a launch of its own, first (the association's
+        // slow_conf_sub is null as fill_assoc_args left it: nothing to wait for)
+        if (fx && launch_fixup(s, a->fp, *fx)) return SM_E_HIP;
+        if (launch_assoc(s, *a, 3u)) return SM_E_HIP;
+    }
+    if (!all) return SM_OK;
+    // a sharded frame whose settle step has not run yet: stand-alone, before anything reads its results
+    if (const ShardSettle *ss = s->held.take_settle()) if (launch_settle(s, *ss)) return SM_E_HIP;
+    if (uint32_t *nf = s->held.take_stats()) {
+        hipLaunchKernelGGL(k_frame_finalize, dim3(1), dim3(256), 0, s->stream, s->d_state, nf, s->part.fix_cur(), s->part.n_fix, s->d_log);
+        HIPCK(hipGetLastError());
+    }
+    return SM_OK;
+}
+
+// The preparation launch: the image planes, and besides them
+//   tile_flags: the frame's tile skip flags for the one-pass surfel kernel (a frame whose cull only marks the dead)
+//   carry:      the held-back association (and fixup) of the previous frame, if there is one
+//   chain:      the frame runs the depth pre-processing chain p0a..p0e (preprocess = 1): the launch is k_assoc_prep<true>, whose
+//               image workgroups are chain tiles (prep_chain_block) -- with or without an association to carry
+// Returns the number of flag workgroups the launch ran (0: none asked for), < 0 on error.
+int launch_prep(sm_ctx *s, const uint8_t *rgb, const uint16_t *raw, const uint8_t *sem, const FrameParams &fp, bool clear_keys,
+                bool tile_flags = false, bool carry = false, const ChainArgs *chain = nullptr)
+{
+    const int tiles = ((s->W + 31) / 32) * ((s->H + 31) / 32);
+    // the frame's tile skip flags for the one-pass surfel kernel: a few extra workgroups (128 tiles each per round)
+    TilePrep tp{};
+    const uint64_t ntl = ((uint64_t)s->count_bound + TILE - 1) / TILE;
+    if (clear_keys && tile_flags) {
+        tp.nfb = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((ntl + 1023) / 1024, 1), 64);     // one tile per thread (k_prep: 1 024 threads)
+        tp.st = s->d_state; tp.tb = s->d_tb; tp.tile_flags = s->d_tile_flags; tp.wave_cnt = s->d_wave_cnt; tp.prep_part = s->d_prep_part;
+    }
+    FixArgs *fxp = nullptr;
+    AssocArgs *carried = carry ? s->held.take_assoc(fxp) : nullptr;
+    s->tl.frame().merged = carried || chain;
+    uint32_t *conf_sub = clear_keys ? s->conf_sub() : nullptr;      // a frame's preparation (clear_keys) also zeroes that frame's conflict sub-counters
+    if (carried || chain) {
+        // the held-back association of the previous frame (if any) + this frame's tile flags + its image / chain tiles in one launch
+        // (a sharded stream's settle step rides on k_prep only: stand-alone here)
+        if (const ShardSettle *ss = chain ? s->held.take_settle() : nullptr) if (launch_settle(s, *ss)) return SM_E_HIP;
+        static const AssocArgs none{};          // nothing carried: the launch has no association workgroups
+        const AssocArgs &a = carried ? *carried : none;
+        if (tp.nfb) {
+            tp.nfb = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((ntl + 255) / 256, 1), 128);     // one tile per thread
+            if (carried) { tp.grp_cand = a.grp_cand; tp.n_grp = a.n_grp; tp.prev_time = a.fp.time; }
+        }
+        // two-launch frame: the held-back association's frame has not had its fixup step yet -- its publisher and repair crew
+        // open this launch, the association and the flag workgroups check for themselves whether they have to wait for them
+        const FixArgs fx = fxp ? *fxp : FixArgs{};
+        const uint32_t n_fix = fxp ? 1u + fx.n_crew : 0u;
+        if (fxp) {
+            carried->slow_conf_sub = fx.conf_sub; carried->slow_need = n_fix;
+            if (tp.nfb) { tp.slow_conf_sub = fx.conf_sub; tp.slow_cap = a.fp.conflict_cap; tp.slow_need = n_fix; tp.slow_par = a.fp.par; }
+        }
+        PrepArgs pa;
+        pa.rgb = rgb; pa.depth_raw = raw; pa.sem = sem; pa.depth_f32 = nullptr; pa.depthT = s->d_depthT; pa.rgbsT = s->d_rgbsT;
+        pa.keyT = clear_keys ? s->d_keyT : nullptr; pa.dcT = s->d_dcT;
+        pa.conf_sub = conf_sub;
+        const uint32_t n_assoc = carried ? assoc_wgs(s) : 0u;
+        const ChainArgs ca = chain ? *chain : ChainArgs{};
+        const uint32_t n_img = chain ? (uint32_t)(((s->W + CH_TX - 1) / CH_TX) * ((s->H + CH_TY - 1) / CH_TY)) : (uint32_t)tiles;
+        if (s->d_ap_trace) { s->ap_trace_n[0] = (int)n_assoc; s->ap_trace_n[1] = (int)tp.nfb; s->ap_trace_n[2] = (int)n_img; s->ap_trace_n[3] = (int)n_fix; }    // (chain: dispatched image | association | flags; the fixup workgroups before them)
+        const dim3 grid(n_fix + tp.nfb + n_assoc + n_img);
+        const auto assoc_prep = chain ? k_assoc_prep<true> : k_assoc_prep<false>;
+        hipLaunchKernelGGL(assoc_prep, grid, dim3(PIX_BLOCK), 0, s->stream, a, pa, fp, tp, n_assoc, n_img, ca, fx, n_fix, s->d_ap_trace);
+        HIPCK(hipGetLastError());
+        return (int)tp.nfb;
+    }
+    // the previous frame of a sharded stream is finished by extra workgroups of this launch
+    const ShardSettle *held = s->held.take_settle();
+    const ShardSettle ss = held ? *held : ShardSettle{};
+    hipLaunchKernelGGL(k_prep, dim3(tiles + tp.nfb + (ss.n + 3u) / 4u), dim3(1024), 0, s->stream, rgb, raw, sem, (const float *)nullptr, s->d_depthT, s->d_rgbsT,
+                       clear_keys ? s->d_keyT : nullptr, fp, s->d_dcT, conf_sub, tp, ss);
+    HIPCK(hipGetLastError());
+    return (int)tp.nfb;
 }
 
 // p2: the conflict test alone (masks, per-tile counts, per-workgroup partial sums); nothing of the model changes
@@ -317,9 +381,9 @@ int launch_conflict_test(sm_ctx *s, const FrameParams &fp, bool timed = false)
     s->n_conf_part = (uint32_t)grid_surfels(s);
     hipLaunchKernelGGL(k_conflict, dim3(s->n_conf_part), dim3(256), 0, s->stream, s->M, s->d_state, fp, s->d_dcT,
                        s->d_cm, s->d_dm, s->d_zm, s->d_tile_cnt, s->d_tb, s->d_tile_flags, s->d_conf_part, s->d_alive,
-                       s->d_conf_sub + SUB_SET * s->conf_sub_set);
+                       s->conf_sub());
     HIPCK(hipGetLastError());
-    if (mark(s, 2, timed)) return SM_E_HIP;
+    if (s->tl.mark(s->stream, 2, timed)) return SM_E_HIP;
     return SM_OK;
 }
 
@@ -338,7 +402,7 @@ int launch_conflict_finalize(sm_ctx *s, const FrameParams &fp, bool timed = fals
                        s->d_tile_cnt, s->d_tile_allow, s->d_tile_keep, s->d_group_tot, s->d_group_base, s->d_conf_part, s->n_conf_part,
                        s->d_alive, s->d_tile_dead, s->d_stat);
     HIPCK(hipGetLastError());
-    if (mark(s, 3, timed)) return SM_E_HIP;
+    if (s->tl.mark(s->stream, 3, timed)) return SM_E_HIP;
     return SM_OK;
 }
 
@@ -349,86 +413,97 @@ int launch_conflict(sm_ctx *s, const FrameParams &fp, bool timed = false)
     return launch_conflict_finalize(s, fp, timed);
 }
 
-// conflict test + cull (marks only) + splat in ONE pass over the surfels, then the publisher / cap fixup kernel.
-// direct: the frame appends directly (k_associate_direct follows): the pass also counts the candidate pixels, the fixup
-// publishes their group prefixes and the new count.
-int launch_surfel_pass(sm_ctx *s, const FrameParams &fp, bool timed, bool direct)
+// The pinned slot statistic (device-written after every cull and append: frames << 32 | occupied slots) against the appends
+// enqueued so far
+// fr, slots: frame tag and occupied slots at the device's last report; ahead: appends enqueued since that report -- known
+// only while the tag is not ahead of the host's count (0 otherwise)
+struct SlotStat { uint32_t fr, slots; bool ahead_known; uint32_t ahead; };
+
+SlotStat read_slot_stat(const sm_ctx *s)
 {
-    if (s->n_prep_blocks == 0) { g_err = "internal: one-pass frame without tile flags from the preparation launch"; return SM_E_ARG; }
-    // two-launch frame: the association will be held back, and the fixup step with it (launch_prep carries both); the candidate
-    // pixels are counted by extra workgroups of the pass's own launch
-    const bool two = s->two_launch && s->defer_ok && timed && direct;
+    const unsigned long long v = __atomic_load_n(s->h_stat.get(), __ATOMIC_RELAXED);
+    const uint32_t fr = (uint32_t)(v >> 32);
+    return {fr, (uint32_t)v, s->frames_enq >= fr, s->frames_enq >= fr ? s->frames_enq - fr : 0u};
+}
+
+struct PassGrid { int split, grid, fix_workers; };
+
+// Grid policy of k_surfel_pass and its fixup step, from an ESTIMATE of the occupied slots -- the pinned statistic plus the measured
+// growth for every append enqueued since -- not from count_bound, which after a hundred unsynchronised frames is the capacity.
+// `two`: two-launch frame, `direct`: the frame appends directly.
+PassGrid pass_grid_policy(sm_ctx *s, bool two, bool direct)
+{
     // Grid: up to 2 048 workgroups while the model is small (most tiles are skipped by their flags; a wide grid spreads the few
     // hundred tiles with work), but no more than are RESIDENT once every workgroup has many tiles with work (>= 4 per
     // workgroup: beyond ~8 M slots) -- the surplus would start when the first ones finish and run a second, thin wave
     // (20 M scattered surfels: 160 us with 2 048 workgroups, 140 with 1 536 = 6 per CU, 152 with 5, 172 with 7)
-    // (the regime is picked from an ESTIMATE of the occupied slots -- the pinned statistic plus a frame's worth of candidates for
-    //  every append enqueued since -- not from count_bound, which after a hundred unsynchronised frames is the capacity)
     uint64_t slots_est = s->count_bound;
-    {
-        const unsigned long long v = __atomic_load_n(s->h_stat.get(), __ATOMIC_RELAXED);
-        const uint32_t fr = (uint32_t)(v >> 32), slots = (uint32_t)v;
-        // growth per frame as the device has reported it (between two reports at least 8 frames apart), at most a frame's candidates
-        if (fr < s->est_fr0 || slots < s->est_slots0) { s->est_fr0 = fr; s->est_slots0 = slots; }      // (a compaction, a reset: the rate stands)
-        else if (fr >= s->est_fr0 + 8u) {
-            s->est_rate = std::min<uint32_t>((slots - s->est_slots0) / (fr - s->est_fr0) + 1u, s->n_odd_pixels);
-            s->est_fr0 = fr; s->est_slots0 = slots;
-        }
-        // (a compaction comes at least every `compact_period` frames: the slots do not grow for longer than that)
-        const uint32_t ahead = std::min<uint32_t>(s->frames_enq - fr, (uint32_t)std::max(s->cfg.compact_period, 1));
-        if (s->frames_enq >= fr) slots_est = std::min<uint64_t>(slots_est, (uint64_t)slots + (uint64_t)ahead * s->est_rate);
+    const SlotStat st = read_slot_stat(s);
+    // growth per frame as the device has reported it (between two reports at least 8 frames apart), at most a frame's candidates
+    if (st.fr < s->est_fr0 || st.slots < s->est_slots0) { s->est_fr0 = st.fr; s->est_slots0 = st.slots; }      // (a compaction, a reset: the rate stands)
+    else if (st.fr >= s->est_fr0 + 8u) {
+        s->est_rate = std::min<uint32_t>((st.slots - s->est_slots0) / (st.fr - s->est_fr0) + 1u, s->n_odd_pixels);
+        s->est_fr0 = st.fr; s->est_slots0 = st.slots;
     }
+    // (a compaction comes at least every `compact_period` frames: the slots do not grow for longer than that)
+    const uint32_t ahead = std::min<uint32_t>(st.ahead, (uint32_t)std::max(s->cfg.compact_period, 1));
+    if (st.ahead_known) slots_est = std::min<uint64_t>(slots_est, (uint64_t)st.slots + (uint64_t)ahead * s->est_rate);
     const uint64_t tiles_b = (slots_est + TILE - 1) / TILE;
-    static const int pers_env = std::getenv("SM_PASS_PERSIST_TILES") ? std::atoi(std::getenv("SM_PASS_PERSIST_TILES")) : 0;
     // (8 192 / 16 384 / never on 100 and 200 KITTI frames: 38.7 / 38.4 / 38.5 us per frame -- the two forms are level there, and a
     //  scattered model pays 1.5x for quarter tiles at 20 M surfels: the lower threshold stays)
-    const bool persistent = tiles_b > (uint64_t)(pers_env > 0 ? pers_env : 4 * MAX_GRID);
+    const bool persistent = tiles_b > (uint64_t)(4 * MAX_GRID);
     // Quarter-tile units (k_surfel_pass<4>: four workgroups per tile sequence) while tiles are few and some of them dense; whole
     // tiles once every workgroup owns many (the scattered 20 M-surfel model: ~50 listed slots per tile, batches of 8 tiles)
-    static const int split_env = std::getenv("SM_PASS_SPLIT") ? std::atoi(std::getenv("SM_PASS_SPLIT")) : 0;
-    const int split = split_env == 1 || split_env == 4 ? split_env : persistent ? 1 : 4;
-    int grid = persistent ? std::min(grid_surfels(s), s->pass_grid) : grid_surfels(s);
-    if (split == 4) {
-        static const int seq_env = std::getenv("SM_PASS_SEQ") ? std::atoi(std::getenv("SM_PASS_SEQ")) : 0;
+    PassGrid g;
+    g.split = s->sw.pass_split == 1 || s->sw.pass_split == 4 ? s->sw.pass_split : persistent ? 1 : 4;
+    g.grid = persistent ? std::min(grid_surfels(s), s->pass_grid) : grid_surfels(s);
+    if (g.split == 4) {
         // (all of them resident: 2 048 workgroups were 17.5 us where 1 536 are 14.1 -- the last quarter started when the first left)
-        const int max_seq = seq_env > 0 ? std::min(seq_env, MAX_GRID / 4) : 3 * MAX_GRID / 16;       // 384 sequences = 1 536 workgroups, six per CU
+        const int max_seq = 3 * MAX_GRID / 16;       // 384 sequences = 1 536 workgroups, six per CU
         const uint64_t tiles_all = ((uint64_t)s->count_bound + TILE - 1) / TILE;
-        grid = 4 * (int)std::min<uint64_t>(std::max<uint64_t>(tiles_all, 1), (uint64_t)max_seq);
+        g.grid = 4 * (int)std::min<uint64_t>(std::max<uint64_t>(tiles_all, 1), (uint64_t)max_seq);
     }
     // fixup workers: the cap repair strides over the tiles; with direct append they first count the frame's candidate pixels, one group each
-    const int fgrid = two ? (int)sm_ctx::N_CREW
-                    : direct ? std::max(std::min(grid, s->fix_grid), (int)std::min<uint32_t>(s->n_grp, MAX_GRID)) : std::min(grid, s->fix_grid);
-    const uint32_t n_fix_prev = s->n_fix_part;
-    const uint2 *fix_prev = s->d_fix_part + (size_t)s->fix_set * MAX_GRID;
-    s->fix_set ^= 1;
-    uint2 *fix_cur = s->d_fix_part + (size_t)s->fix_set * MAX_GRID;
+    g.fix_workers = two ? (int)sm_ctx::N_CREW
+                  : direct ? std::max(std::min(g.grid, s->fix_grid), (int)std::min<uint32_t>(s->n_grp, MAX_GRID)) : std::min(g.grid, s->fix_grid);
+    return g;
+}
+
+// conflict test + cull (marks only) + splat in ONE pass over the surfels, then the publisher / cap fixup kernel.
+// direct: the frame appends directly (k_associate_direct follows): the pass also counts the candidate pixels, the fixup
+// publishes their group prefixes and the new count.  n_prep: the flag workgroups the frame's preparation launch ran.
+int launch_surfel_pass(sm_ctx *s, const FrameParams &fp, bool timed, bool direct, uint32_t n_prep)
+{
+    if (n_prep == 0) { g_err = "internal: one-pass frame without tile flags from the preparation launch"; return SM_E_ARG; }
+    // two-launch frame: the association will be held back, and the fixup step with it (launch_prep carries both); the candidate
+    // pixels are counted by extra workgroups of the pass's own launch
+    const bool two = s->sw.two_launch && s->defer_ok && timed && direct;
+    const PassGrid g = pass_grid_policy(s, two, direct);
+    const int grid = g.grid;
+    PassPartials &pp = s->part;
+    const uint32_t n_fix_prev = pp.n_fix;
+    const uint2 *fix_prev = pp.fix_cur();
+    pp.fix_set ^= 1;
     s->n_conf_part = (uint32_t)grid;
-    s->n_compact_part = (uint32_t)grid;
-    s->lazy_part_live = true;
-    s->fix_part_live = true;
-    s->n_fix_part = (uint32_t)fgrid;
-    uint32_t *sub = s->d_conf_sub + SUB_SET * s->conf_sub_set;
+    pp.n_compact = (uint32_t)grid;
+    pp.pass_live = true;
+    pp.n_fix = (uint32_t)g.fix_workers;
+    uint32_t *sub = s->conf_sub();
     const uint32_t tile_bound = (uint32_t)std::max<uint64_t>(((uint64_t)s->count_bound + TILE - 1) / TILE, 1);
     if (s->d_pass_trace) s->pass_trace_grid = grid;
-    CandArgs ca;
-    memset(&ca, 0, sizeof ca);
+    CandArgs ca{};
     ca.n_pass = (uint32_t)grid;
     if (two) {
         ca.n_grp = s->n_grp; ca.cg = s->cand_group; ca.n_pix_blocks = s->n_pix_blocks;
         ca.depthT = s->d_depthT; ca.xs = s->d_xs; ca.ys = s->d_ys; ca.blk_cand = s->d_blk_cand; ca.grp_cand = s->d_grp_cand;
     }
-    if (split == 4)
-        hipLaunchKernelGGL(k_surfel_pass<4>, dim3(grid + (two ? (int)s->n_grp : 0)), dim3(256), 0, s->stream, s->M, s->d_state, fp, s->d_dcT, s->d_cm, s->d_dm /* km */,
-                           s->d_wave_cnt, s->d_tb, s->d_tile_flags, s->d_lazy_part, s->d_alive, s->d_tile_dead, sub, s->d_keyT, s->d_undo, tile_bound,
-                           s->d_frame_sub, ca, s->d_pass_trace);
-    else
-        hipLaunchKernelGGL(k_surfel_pass<1>, dim3(grid + (two ? (int)s->n_grp : 0)), dim3(256), 0, s->stream, s->M, s->d_state, fp, s->d_dcT, s->d_cm, s->d_dm /* km */,
-                           s->d_wave_cnt, s->d_tb, s->d_tile_flags, s->d_lazy_part, s->d_alive, s->d_tile_dead, sub, s->d_keyT, s->d_undo, tile_bound,
-                           s->d_frame_sub, ca, s->d_pass_trace);
+    const auto pass = g.split == 4 ? k_surfel_pass<4> : k_surfel_pass<1>;
+    hipLaunchKernelGGL(pass, dim3(grid + (two ? (int)s->n_grp : 0)), dim3(256), 0, s->stream, s->M, s->d_state, fp, s->d_dcT, s->d_cm, s->d_dm /* km */,
+                       s->d_wave_cnt, s->d_tb, s->d_tile_flags, pp.d_lazy, s->d_alive, s->d_tile_dead, sub, s->d_keyT, s->d_undo, tile_bound,
+                       s->d_frame_sub, ca, s->d_pass_trace);
     HIPCK(hipGetLastError());
-    if (mark(s, 2, timed) || mark(s, 3, timed)) return SM_E_HIP;
-    FixArgs x;
-    memset(&x, 0, sizeof x);
+    if (s->tl.mark(s->stream, 2, timed) || s->tl.mark(s->stream, 3, timed)) return SM_E_HIP;
+    FixArgs x{};
     DirectArgs &da = x.da;
     da.on = direct ? (two ? 2 : 1) : 0;
     da.blk_cand = s->d_blk_cand; da.grp_cand = s->d_grp_cand; da.n_grp = s->n_grp; da.cg = s->cand_group; da.n_pix_blocks = s->n_pix_blocks;
@@ -436,21 +511,16 @@ int launch_surfel_pass(sm_ctx *s, const FrameParams &fp, bool timed, bool direct
     da.frame_sub = s->d_frame_sub;
     // the previous frame's new / fused counters: the other set where the sets alternate (its association may run next to this publisher)
     da.nf_prev = s->defer_ok ? s->d_nf_sub_nx : s->d_nf_sub;
-    // (the previous frame's fixup partials: only if it appended directly and nothing has completed its statistics since)
-    da.fix_prev = fix_prev; da.n_fix_prev = s->pend_finalize ? n_fix_prev : 0u;
+    // (the previous frame's fixup partials: only if it appended directly and nothing has completed its statistics since;
+    //  the fixup's publisher completes the previous frame's statistics first)
+    da.fix_prev = fix_prev; da.n_fix_prev = s->held.take_stats() ? n_fix_prev : 0u;
     da.log = s->d_log;
-    s->pend_finalize = false;            // the fixup's publisher completes the previous frame's statistics first
-    x.cm = s->d_cm; x.km = s->d_dm; x.wave_cnt = s->d_wave_cnt; x.tile_flags = s->d_tile_flags; x.part = s->d_lazy_part; x.n_part = (uint32_t)grid;
-    x.fix_part = fix_cur; x.alive = s->d_alive; x.tile_dead = s->d_tile_dead; x.conf_sub = sub; x.keyT = s->d_keyT; x.undo = s->d_undo;
-    x.host_stat = s->d_stat; x.prep_part = s->d_prep_part; x.n_prep = s->n_prep_blocks; x.tb = s->d_tb; x.n_crew = (uint32_t)fgrid;
-    if (two) {
-        s->fix_args = x;
-        s->fix_pending = true;
-    } else {
-        hipLaunchKernelGGL(k_pass_fixup, dim3(fgrid + 1), dim3(256), 0, s->stream, s->M, s->d_state, fp, x);
-        HIPCK(hipGetLastError());
-    }
-    if (mark(s, 4, timed)) return SM_E_HIP;
+    x.cm = s->d_cm; x.km = s->d_dm; x.wave_cnt = s->d_wave_cnt; x.tile_flags = s->d_tile_flags; x.part = pp.d_lazy; x.n_part = (uint32_t)grid;
+    x.fix_part = pp.fix_cur(); x.alive = s->d_alive; x.tile_dead = s->d_tile_dead; x.conf_sub = sub; x.keyT = s->d_keyT; x.undo = s->d_undo;
+    x.host_stat = s->d_stat; x.prep_part = s->d_prep_part; x.n_prep = n_prep; x.tb = s->d_tb; x.n_crew = (uint32_t)g.fix_workers;
+    if (two) s->held.hold_fixup(x);
+    else if (launch_fixup(s, fp, x)) return SM_E_HIP;
+    if (s->tl.mark(s->stream, 4, timed)) return SM_E_HIP;
     check_alive(s, 1u + 16u * (uint32_t)(s->tick & 0xFFFF));
     return SM_OK;
 }
@@ -467,80 +537,46 @@ void fill_assoc_args(const sm_ctx *s, const FrameParams &fp, AssocArgs &a)
 // association + in-place fuse + direct append (the frame's last kernel; its statistics are completed later)
 int launch_associate_direct(sm_ctx *s, const FrameParams &fp, bool timed)
 {
-    ShardArgs sh;
-    memset(&sh, 0, sizeof sh);
     AssocArgs a;
     fill_assoc_args(s, fp, a);
-    if (s->ev && timed) s->ev_deferred[s->ev_frames % EV_RING] = s->defer_ok;
-    s->nf_last = s->d_nf_sub;
-    if (s->defer_ok && timed) {
-        // asynchronous plain stream: hold the association back; the next frame's k_prep launch carries it (k_assoc_prep),
-        // anything else that needs its results launches it first (flush_assoc, reached through finalize_if_pending)
-        s->assoc_args = a;
-        s->assoc_pending = true;
-    } else {
-        hipLaunchKernelGGL((k_associate_direct<false>), dim3(assoc_wgs(s)), dim3(PIX_BLOCK), 0, s->stream, a, sh);
-        HIPCK(hipGetLastError());
-        check_alive(s, 2u + 16u * (uint32_t)(s->tick & 0xFFFF));
-    }
-    s->lazy_part_live = false;
-    s->fix_part_live = false;
-    s->pend_finalize = true;
+    s->tl.frame().deferred = s->defer_ok;
+    // asynchronous plain stream: hold the association back; the next frame's preparation launch carries it (k_assoc_prep),
+    // anything else that needs its results launches it first (finalize_if_pending)
+    if (s->defer_ok && timed) s->held.hold_assoc(a);
+    else if (launch_assoc(s, a, 2u)) return SM_E_HIP;
+    s->part.clear();
+    s->held.hold_stats(s->d_nf_sub);
     s->frames_enq++;
-    if (mark(s, 5, timed) || mark(s, 6, timed) || mark(s, 7, timed)) return SM_E_HIP;
-    return SM_OK;
-}
-
-int flush_assoc(sm_ctx *s)
-{
-    if (!s->assoc_pending) return SM_OK;
-    s->assoc_pending = false;
-    if (s->fix_pending) {                 // two-launch frame: that frame's fixup step has not run either -- in a launch of its own, first
-        s->fix_pending = false;
-        hipLaunchKernelGGL(k_pass_fixup, dim3(s->fix_args.n_crew + 1), dim3(256), 0, s->stream, s->M, s->d_state, s->assoc_args.fp, s->fix_args);
-        HIPCK(hipGetLastError());
-    }
-    s->assoc_args.slow_conf_sub = nullptr; s->assoc_args.slow_need = 0u;
-    ShardArgs sh;
-    memset(&sh, 0, sizeof sh);
-    hipLaunchKernelGGL((k_associate_direct<false>), dim3(assoc_wgs(s)), dim3(PIX_BLOCK), 0, s->stream, s->assoc_args, sh);
-    HIPCK(hipGetLastError());
-    check_alive(s, 3u + 16u * (uint32_t)(s->tick & 0xFFFF));
+    if (s->tl.mark(s->stream, 5, timed) || s->tl.mark(s->stream, 6, timed) || s->tl.mark(s->stream, 7, timed)) return SM_E_HIP;
     return SM_OK;
 }
 
 int launch_compact(sm_ctx *s, const FrameParams &fp, bool splat, bool timed)
 {
-    s->lazy_part_live = false;
-    s->fix_part_live = false;
+    s->part.clear();
     if (!fp.compact_now) {
         // deferred compaction: the cull only marks the dead -- lean kernel, no co-residency requirement
         if (splat) { g_err = "internal: a frame's cull that only marks the dead is k_surfel_pass"; return SM_E_ARG; }
         const int grid = grid_surfels(s);
-        s->n_compact_part = 0u;
+        s->part.n_compact = 0u;
         hipLaunchKernelGGL(k_cull_lazy, dim3(grid), dim3(256), 0, s->stream, s->M, s->d_state, fp, s->d_cm, s->d_dm, s->d_zm,
                            s->d_tile_cnt, s->d_tile_allow, s->d_alive, s->d_tile_dead);
         HIPCK(hipGetLastError());
-        if (mark(s, 4, timed)) return SM_E_HIP;
+        if (s->tl.mark(s->stream, 4, timed)) return SM_E_HIP;
         return SM_OK;
     }
     const int grid = std::min(grid_surfels(s), s->compact_grid);
     const uint32_t epoch = ++s->cull_epoch;
-    s->n_compact_part = splat ? (uint32_t)grid : 0u;
+    // (a maintenance compaction -- ensure_compact -- kills nothing and draws nothing: what the next append folds stays as it is)
+    if (!fp.maintenance) s->part.n_compact = splat ? (uint32_t)grid : 0u;
     FrameParams fpc = fp;
-    fpc.compact_tickets = compaction_needs_tickets(s->cfg.device) ? 1 : 0;
-    if (splat)
-        hipLaunchKernelGGL(k_compact<true>, dim3(grid), dim3(256), 0, s->stream, s->M, s->d_state, fpc, s->d_cm,
-                           s->d_dm, s->d_zm, s->d_tile_cnt, s->d_tile_allow, s->d_tile_keep, s->d_keyT, s->d_tile_flag, epoch,
-                           s->d_group_base, s->d_tb, s->d_tile_flags, s->d_compact_part, s->d_alive,
-                           s->d_tile_dead);
-    else
-        hipLaunchKernelGGL(k_compact<false>, dim3(grid), dim3(256), 0, s->stream, s->M, s->d_state, fpc, s->d_cm,
-                           s->d_dm, s->d_zm, s->d_tile_cnt, s->d_tile_allow, s->d_tile_keep, s->d_keyT, s->d_tile_flag, epoch,
-                           s->d_group_base, s->d_tb, s->d_tile_flags, s->d_compact_part, s->d_alive,
-                           s->d_tile_dead);
+    fpc.compact_tickets = compaction_needs_tickets(s) ? 1 : 0;
+    const auto compact = splat ? k_compact<true> : k_compact<false>;
+    hipLaunchKernelGGL(compact, dim3(grid), dim3(256), 0, s->stream, s->M, s->d_state, fpc, s->d_cm,
+                       s->d_dm, s->d_zm, s->d_tile_cnt, s->d_tile_allow, s->d_tile_keep, s->d_keyT, s->d_tile_flag, epoch,
+                       s->d_group_base, s->d_tb, s->d_tile_flags, s->part.d_compact, s->d_alive, s->d_tile_dead);
     HIPCK(hipGetLastError());
-    if (mark(s, 4, timed)) return SM_E_HIP;
+    if (s->tl.mark(s->stream, 4, timed)) return SM_E_HIP;
     return SM_OK;
 }
 
@@ -557,20 +593,17 @@ bool decide_compact(sm_ctx *s)
     // When the host has run far ahead of the device the bound is loose; rather than compacting for nothing it then
     // lets the device catch up (the queue still holds every frame in between, so the GPU stays busy).
     // (This is the one place where an "enqueue only" call may wait, and only within one frame's worth of the capacity:
-    //  at most SM_CAPACITY_WAIT_US, default 2000 us, then it compacts instead.)
-    static const long wait_us = std::getenv("SM_CAPACITY_WAIT_US") ? std::atol(std::getenv("SM_CAPACITY_WAIT_US")) : 2000;
+    //  at most sw.capacity_wait_us, default 2000 us, then it compacts instead.)
     const auto t_start = std::chrono::steady_clock::now();
     for (uint32_t spins = 0;; ++spins) {
-        const unsigned long long v = __atomic_load_n(s->h_stat.get(), __ATOMIC_RELAXED);
-        const uint32_t fr = (uint32_t)(v >> 32), slots = (uint32_t)v;
+        const SlotStat st = read_slot_stat(s);
         uint64_t bound = s->count_bound;
-        const uint32_t ahead = s->frames_enq >= fr ? s->frames_enq - fr : 0u;
-        if (s->frames_enq >= fr) bound = std::min<uint64_t>(bound, (uint64_t)slots + (uint64_t)ahead * s->n_odd_pixels);
+        if (st.ahead_known) bound = std::min<uint64_t>(bound, (uint64_t)st.slots + (uint64_t)st.ahead * s->n_odd_pixels);
         if (bound + s->n_odd_pixels <= s->cap) break;                  // fits even if every candidate pixel is new
-        if (ahead <= 1u) return true;                                  // the bound is (nearly) exact: compact
-        if ((uint64_t)slots + 2ull * s->n_odd_pixels > s->cap) return true;   // would not fit with the device caught up either
+        if (st.ahead <= 1u) return true;                               // the bound is (nearly) exact: compact
+        if ((uint64_t)st.slots + 2ull * s->n_odd_pixels > s->cap) return true;   // would not fit with the device caught up either
         if ((spins & 63u) == 63u &&
-            std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_start).count() > wait_us)
+            std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_start).count() > s->sw.capacity_wait_us)
             return true;                                               // the device is further behind than we are willing to wait for
         std::this_thread::yield();
     }
@@ -614,17 +647,16 @@ int launch_associate(sm_ctx *s, const FrameParams &fp, bool timed)
 {
     int rc = launch_associate_only(s, fp);
     if (rc) return rc;
-    if (mark(s, 5, timed) || mark(s, 6, timed)) return SM_E_HIP;
+    if (s->tl.mark(s->stream, 5, timed) || s->tl.mark(s->stream, 6, timed)) return SM_E_HIP;
     // the append derives its own prefix from the per-block counts (no scan kernel)
+    const PassPartials::Fold f = s->part.fold();
     hipLaunchKernelGGL(k_append_scan, dim3(s->n_pix_blocks), dim3(PIX_BLOCK), 0, s->stream, s->M, s->d_state, fp, s->d_depthT,
-                       s->d_rgbsT, s->d_xs, s->d_ys, s->d_validmask, s->d_fusedmask, s->d_blk_cnt, s->d_log, s->d_tb, s->d_compact_part,
-                       s->n_compact_part, s->d_alive, s->d_tile_dead, s->d_stat, s->lazy_part_live ? s->d_lazy_part : nullptr,
-                       (s->lazy_part_live && s->fix_part_live) ? s->d_fix_part + (size_t)s->fix_set * MAX_GRID : nullptr, s->n_fix_part);
-    s->lazy_part_live = false;
-    s->fix_part_live = false;
+                       s->d_rgbsT, s->d_xs, s->d_ys, s->d_validmask, s->d_fusedmask, s->d_blk_cnt, s->d_log, s->d_tb, f.compact,
+                       f.n_compact, s->d_alive, s->d_tile_dead, s->d_stat, f.lazy, f.fix, f.n_fix);
+    s->part.clear();
     s->frames_enq++;
     HIPCK(hipGetLastError());
-    if (mark(s, 7, timed)) return SM_E_HIP;
+    if (s->tl.mark(s->stream, 7, timed)) return SM_E_HIP;
     check_alive(s, 5u + 16u * (uint32_t)(s->tick & 0xFFFF));
     return SM_OK;
 }
@@ -654,13 +686,21 @@ void bump_bound(sm_ctx *s)
     s->count_bound = (uint32_t)std::min<uint64_t>((uint64_t)s->count_bound + s->n_odd_pixels, s->cap);
 }
 
-void end_frame(sm_ctx *s, bool timed = true);
+// tail of processFrame (src/SurfelMapping.cpp:244-248)
+void end_frame(sm_ctx *s, bool timed = true)
+{
+    if (s->cfg.preprocess) std::swap(s->d_lastT, s->d_filteredT);   // :244 LAST <- DEPTH_FILTERED without a copy
+    memcpy(s->last_pose, s->curr_pose, 64);               // :245 (LAST aliases the metric depth when preprocess == 0)
+    s->tl.end_frame(timed);
+    s->tick++;
+}
 
 // First half of SurfelMapping::processFrame once the textures are on the device
 // (src/SurfelMapping.cpp:130-169): pre-processing and the reference-frame early-out.
+// `tile_flags`, `carry`: as launch_prep takes them; *n_prep: the flag workgroups it ran.
 // Returns 1 when the fusing passes must follow, 0 when the call ends here, <0 on error.
-int begin_frame(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_raw, const uint8_t *d_sem, const float *pose,
-                FrameParams *fp_out)
+int begin_frame(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_raw, const uint8_t *d_sem, const float *pose, bool tile_flags, bool carry,
+                FrameParams *fp_out, uint32_t *n_prep)
 {
     if (s->pending_cull) { g_err = "sm_stage_conflict without sm_stage_cull"; return SM_E_ARG; }
     memcpy(s->curr_pose, pose, 64);
@@ -668,15 +708,14 @@ int begin_frame(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_raw, const ui
     FrameParams fp = make_params(s, pose);
     const bool fusing = s->ref_set && s->tick != 0;
     int rc;
-    if ((rc = mark(s, 8, fusing))) return rc;    // back-to-back pair 8 -> 0: the cost of an event record itself
-    if ((rc = mark(s, 0, fusing))) return rc;
+    if ((rc = s->tl.mark(s->stream, 8, fusing))) return rc;    // back-to-back pair 8 -> 0: the cost of an event record itself
+    if ((rc = s->tl.mark(s->stream, 0, fusing))) return rc;
     // The reference frame and the frame after reset() do not draw the index map: its textures keep what the last
     // predictIndices left (src/SurfelMapping.cpp:142-169), so the key map is neither cleared nor exchanged then.
     const bool will_splat = fusing;
     // frame parity: the conflict sub-counters, the frame planes and the per-frame scratch of the fixup step alternate between two
     // sets, so that the pre-processing of frame f+1 never touches what frame f still reads
     s->plane_set ^= 1;
-    s->conf_sub_set = s->plane_set;
     fp.par = s->plane_set;
     if (s->defer_ok) {
         std::swap(s->d_depthT, s->d_depthT_nx); std::swap(s->d_rgbsT, s->d_rgbsT_nx);
@@ -689,8 +728,7 @@ int begin_frame(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_raw, const ui
     }
     // metriciseDepth + filterDepth + removeMovings (src/SurfelMapping.cpp:136-139,156,254-365): with preprocess = 1 the whole
     // chain is one stage of the preparation launch (prep_chain_block); the reference frame stops before removeMovings
-    ChainArgs ca;
-    memset(&ca, 0, sizeof ca);
+    ChainArgs ca{};
     if (s->cfg.preprocess) {
         ca.lastT = s->d_lastT; ca.filteredT = s->d_filteredT; memcpy(ca.w, s->h_wtab, sizeof ca.w);
         ca.border = (int)std::ceil(s->cfg.stereo_border - 0.5f);
@@ -701,7 +739,8 @@ int begin_frame(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_raw, const ui
             mul4(linv, s->curr_pose, ca.t_c2l.m);
         }
     }
-    if ((rc = launch_prep(s, d_rgb, d_raw, d_sem, nullptr, fp, will_splat, nullptr, s->cfg.preprocess ? &ca : nullptr))) return rc;
+    if ((rc = launch_prep(s, d_rgb, d_raw, d_sem, fp, will_splat, tile_flags, carry, s->cfg.preprocess ? &ca : nullptr)) < 0) return rc;
+    *n_prep = (uint32_t)rc;
     // preprocess == 0: DEPTH_FILTERED and LAST are the metric depth itself (nothing reads them on the
     // hot path); they alias d_depthT in sm_download_depth instead of being copied every frame.
     if (!s->ref_set) {                                    // src/SurfelMapping.cpp:142-154
@@ -711,7 +750,7 @@ int begin_frame(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_raw, const ui
         s->tick++;
         return 0;
     }
-    if ((rc = mark(s, 1, fusing))) return rc;
+    if ((rc = s->tl.mark(s->stream, 1, fusing))) return rc;
     s->raw_valid = true;                                  // computeFeedbackBuffers (src/SurfelMapping.cpp:164,172): on demand here
     s->raw_tick = s->tick;
     if (s->tick == 0) {
@@ -723,8 +762,8 @@ int begin_frame(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_raw, const ui
         // (src/GlobalModel.cpp:211-228): a map that was
         // uploaded after reset() is discarded, not extended
         if ((rc = discard_model(s))) return rc;
-        s->n_compact_part = 0;                            // no cull / splat ran: nothing to fold into visible_count
-        s->lazy_part_live = false;
+        s->part.clear();
+        s->part.n_compact = 0;                            // no cull / splat ran: nothing to fold into visible_count
         if ((rc = launch_associate(s, fp, false))) return rc;
         bump_bound(s);
         end_frame(s, false);
@@ -736,15 +775,6 @@ int begin_frame(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_raw, const ui
     return 1;
 }
 
-// tail of processFrame (src/SurfelMapping.cpp:244-248)
-void end_frame(sm_ctx *s, bool timed)
-{
-    if (s->cfg.preprocess) std::swap(s->d_lastT, s->d_filteredT);   // :244 LAST <- DEPTH_FILTERED without a copy
-    memcpy(s->last_pose, s->curr_pose, 64);               // :245 (LAST aliases the metric depth when preprocess == 0)
-    if (s->ev && timed) s->ev_frames++;
-    s->tick++;
-}
-
 // SurfelMapping::processFrame body (src/SurfelMapping.cpp:130-251); enqueue only.
 int enqueue_frame(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_raw, const uint8_t *d_sem, const float *pose)
 {
@@ -754,28 +784,26 @@ int enqueue_frame(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_raw, const 
     // the one-pass surfel kernel
     const bool fusing = s->ref_set && s->tick != 0 && !s->pending_cull;
     const bool compact_now = fusing ? decide_compact(s) : true;
-    s->want_list = fusing && !compact_now;
     // a held-back association rides on this frame's k_prep launch if this is again a fusing frame; anything else (the frame
     // after reset, ...) needs its results first
     // (a compacting frame too: its k_prep launch has no tile flags to make; the doubled words of DevState a merged publisher
     //  leaves set are cleared by k_cull_finalize there, by the next pass's launch otherwise)
-    s->merge_assoc = s->assoc_pending && fusing && s->defer_ok;
+    const bool carry = fusing && s->defer_ok;
     int rc = SM_OK;
-    if (s->assoc_pending && !s->merge_assoc && (rc = flush_assoc(s))) return rc;
-    rc = begin_frame(s, d_rgb, d_raw, d_sem, pose, &fp);
-    s->want_list = false;
-    s->merge_assoc = false;
+    uint32_t n_prep = 0;
+    if (!carry && (rc = complete_held(s, false))) return rc;
+    rc = begin_frame(s, d_rgb, d_raw, d_sem, pose, fusing && !compact_now, carry, &fp, &n_prep);
     if (rc <= 0) return rc;
     fp.compact_now = compact_now ? 1u : 0u;
     note_cull(s, fp.compact_now != 0u);
     s->keys_are_slots = fp.compact_now == 0u;      // this frame's splat writes slot numbers iff nothing moves
-    if (s->ev) s->ev_compacted[s->ev_frames % EV_RING] = fp.compact_now != 0u;
     // a cull that only marks the dead is ONE pass over the surfels (k_surfel_pass + k_pass_fixup: conflict test, decrement, cull,
     // splat), and the association appends the new surfels directly (no append kernel)
     const bool one_pass = !fp.compact_now;
-    if (s->ev) { s->ev_one_pass[s->ev_frames % EV_RING] = one_pass; s->ev_direct[s->ev_frames % EV_RING] = one_pass; }
+    Timeline::Flags &fl = s->tl.frame();
+    fl.compacted = !one_pass; fl.one_pass = fl.direct = one_pass;
     if (one_pass) {
-        if ((rc = launch_surfel_pass(s, fp, true, true))) return rc;        // :178-197
+        if ((rc = launch_surfel_pass(s, fp, true, true, n_prep))) return rc;        // :178-197
         if ((rc = launch_associate_direct(s, fp, true))) return rc;         // :212-239
         bump_bound(s);
         end_frame(s);
@@ -820,8 +848,8 @@ int alloc_ctx(sm_ctx *s)
         dalloc(s->d_tile_cnt, ntiles * 3) || dalloc(s->d_tile_allow, ntiles) || dalloc(s->d_tile_keep, ntiles) || dalloc(s->d_tile_flag, ntiles) ||
         hipMemset(s->d_tile_flag, 0, ntiles * 4) != hipSuccess ||
         dalloc(s->d_group_tot, (ntiles / GROUP + 2) * 4) || dalloc(s->d_group_base, ntiles / GROUP + 2) ||
-        dalloc(s->d_conf_part, (size_t)MAX_GRID * 4) || dalloc(s->d_compact_part, (size_t)MAX_GRID) || dalloc(s->d_lazy_part, (size_t)MAX_GRID) ||
-        dalloc(s->d_fix_part, (size_t)MAX_GRID * 2 + 2) || dalloc(s->d_wave_cnt, ntiles) || dalloc(s->d_undo, cap + TILE) ||
+        dalloc(s->d_conf_part, (size_t)MAX_GRID * 4) || dalloc(s->part.d_compact, (size_t)MAX_GRID) || dalloc(s->part.d_lazy, (size_t)MAX_GRID) ||
+        dalloc(s->part.d_fix, (size_t)MAX_GRID * 2 + 2) || dalloc(s->d_wave_cnt, ntiles) || dalloc(s->d_undo, cap + TILE) ||
         dalloc(s->d_conf_sub, (size_t)2 * SUB_SET) || dalloc(s->d_prep_part, (size_t)256) || hipMemset(s->d_conf_sub, 0, (size_t)2 * SUB_SET * 4) != hipSuccess ||
         dalloc(s->d_tb, tb * 8) || dalloc(s->d_tile_flags, tb) || hipMemset(s->d_tile_flags, 0, tb) != hipSuccess ||
         dalloc(s->d_validmask, (P + 63) / 64 + 4) || dalloc(s->d_fusedmask, (P + 63) / 64 + 4) || dalloc(s->d_blk_cnt, (size_t)s->n_pix_blocks) ||
@@ -922,20 +950,12 @@ int sm_impl::push_state(sm_ctx *s)
     return SM_OK;
 }
 
+// a direct-append frame leaves its new / fused totals, the dead-slot total and its log entry to be completed by the next
+// frame's fixup publisher, and a deferring context its association (and fixup) to the next frame's preparation launch:
+// everything else that reads their results asks for the completion first
 int sm_impl::finalize_if_pending(sm_ctx *s)
 {
-    if (flush_assoc(s)) return SM_E_HIP;      // a held-back association comes first: everything below reads its results
-    if (s->ss_settle_pending) {          // a sharded frame whose settle step has not run yet: stand-alone, before anything reads its results
-        s->ss_settle_pending = false;
-        hipLaunchKernelGGL(k_shard_settle, dim3(s->ss_settle.n), dim3(PIX_BLOCK), 0, s->stream, s->ss_settle);
-        HIPCK(hipGetLastError());
-    }
-    if (!s->pend_finalize) return SM_OK;
-    s->pend_finalize = false;
-    hipLaunchKernelGGL(k_frame_finalize, dim3(1), dim3(256), 0, s->stream, s->d_state, s->nf_last ? s->nf_last : s->d_nf_sub,
-                       s->d_fix_part + (size_t)s->fix_set * MAX_GRID, s->n_fix_part, s->d_log);
-    HIPCK(hipGetLastError());
-    return SM_OK;
+    return complete_held(s, true);
 }
 
 int sm_impl::pull_state(sm_ctx *s)
@@ -994,9 +1014,7 @@ int sm_impl::ensure_compact(sm_ctx *s)
                            s->d_tile_keep, s->d_group_base);
     s->keys_are_slots = false;
     HIPCK(hipGetLastError());
-    const uint32_t keep_part = s->n_compact_part;
     int rc = launch_compact(s, fp, false, false);
-    s->n_compact_part = keep_part;
     if (rc) return rc;
     if ((rc = launch_post_fill(s))) return rc;
     s->maybe_garbage = false;
@@ -1054,7 +1072,7 @@ int sm_impl::clean_points_device(sm_ctx *s, const uint16_t *d_depth_mm, const ui
     if (rc) return rc;
     memcpy(s->curr_pose, pose16, 64);
     FrameParams fp = make_params(s, pose16);
-    if ((rc = launch_prep(s, s->d_rgb, d_depth_mm, d_semantic, nullptr, fp, false))) return rc;   // metriciseDepth only
+    if ((rc = launch_prep(s, s->d_rgb, d_depth_mm, d_semantic, fp, false)) < 0) return rc;   // metriciseDepth only
     fp.max_depth = s->cfg.far_clip - 15.0f;     // src/SurfelMapping.cpp:515
     fp.conflict_thresh = 0.1f;                  // :516
     fp.is_clean = 1;                            // :517
@@ -1132,20 +1150,12 @@ sm_ctx *sm_create(const sm_config *c)
     s->n_pix_blocks = (s->P + PIX_BLOCK - 1) / PIX_BLOCK;
     s->alive_words = nwords; s->dead_tiles = ntiles;
     s->tb_tiles = (uint32_t)(ntiles + P / 2 / TILE + 8);
-    // deferred association (three launches per frame; with or without the depth filter chain)
-    {
-        const char *e = std::getenv("SM_DEFER_ASSOC");                    // "0": every frame launches its own association
-        s->defer_ok = !(e && e[0] == '0');
-    }
+    s->sw = read_switches();
+    s->defer_ok = s->sw.defer_assoc;       // deferred association (three launches per frame; with or without the depth filter chain)
     // candidate groups: small groups make the counting workgroups short (k_pass_fixup 3.5 -> 2.5 us at 1242x375 with 4
     // instead of 16 blocks per group) but every association wave sums all groups before its own: keep ~250-500 groups
     s->cand_group = s->n_pix_blocks <= 2048 ? 4u : s->n_pix_blocks <= 4096 ? 8u : 16u;
-    if (const char *e = std::getenv("SM_CAND_GROUP")) { const int v = std::atoi(e); if (v == 4 || v == 8 || v == 16) s->cand_group = (uint32_t)v; }
     s->n_grp = (uint32_t)((s->n_pix_blocks + s->cand_group - 1) / s->cand_group);
-    {
-        const char *e = std::getenv("SM_TWO_LAUNCH");                     // "0": the fixup step keeps its own launch (three launches per frame)
-        s->two_launch = s->defer_ok && !(e && e[0] == '0');
-    }
     if (alloc_ctx(s.get())) { if (g_err.empty()) g_err = "sm_create: allocation failed"; return nullptr; }
 
     // pixel-centre coordinates exactly as data.vert sees them:
@@ -1202,40 +1212,15 @@ sm_ctx *sm_create(const sm_config *c)
         ok = hipStreamSynchronize(s->stream) == hipSuccess;
     }
     if (!ok) { g_err = "sm_create: device initialisation failed"; return nullptr; }
-    {
-        // the in-place compaction needs every workgroup of k_compact resident at once
-        int cus = 0, per_cu = 0;
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
-        if (std::getenv("SM_CHECK_ALIVE") && (hipMalloc(s->d_chk.put(), 32) != hipSuccess || hipMemset(s->d_chk, 0, 32) != hipSuccess)) s->d_chk = {};
-        if (std::getenv("SM_PASS_TRACE")) (void)hipMalloc(s->d_pass_trace.put(), (size_t)MAX_GRID * 64);
-        if (std::getenv("SM_PASS_TRACE")) (void)hipMalloc(s->d_ap_trace.put(), (size_t)65536 * 16);
-        {
-            // k_surfel_pass: with more workgroups than the chip holds at once the surplus starts when the first ones are done --
-            // on a model where every tile has work (20 M scattered surfels: ~10 tiles per workgroup) that is a second pass at an
-            // eighth of the occupancy.  Grid = what is resident; tiles go round-robin.  (SM_PASS_WG_PER_CU overrides.)
-            int pc = 0;
-            if (cus > 0 && hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, k_surfel_pass<1>, 256, 0) == hipSuccess && pc > 0) {
-                int want = std::max(1, pc - 1);      // the occupancy API over-reports by one block per CU here (measured; MI355X_MICROARCH.md)
-                if (const char *e = std::getenv("SM_PASS_WG_PER_CU")) want = std::max(1, std::atoi(e));
-                s->pass_grid = std::max(256, std::min(cus * want, MAX_GRID));
-            }
-        }
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess && cus > 0 &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_compact<true>, 256, 0) == hipSuccess && per_cu > 0) {
-            // the occupancy API can over-report by one block per CU (MI355X_MICROARCH.md): stay at <= 4 and below it
-            // (SM_COMPACT_WG_PER_CU overrides the margin for experiments)
-            // <= 4 per CU: in that range the limit is VGPR/LDS-bound and the API is exact; above it keep a margin
-            int want = per_cu <= 4 ? per_cu : 4;
-            if (const char *e = std::getenv("SM_COMPACT_WG_PER_CU")) want = std::max(1, std::min(per_cu, std::atoi(e)));
-            s->compact_grid = std::max(1, cus * want);
-        }
-    }
+    if (s->sw.check_alive && (hipMalloc(s->d_chk.put(), 32) != hipSuccess || hipMemset(s->d_chk, 0, 32) != hipSuccess)) s->d_chk = {};
+    if (s->sw.trace) { (void)hipMalloc(s->d_pass_trace.put(), (size_t)MAX_GRID * 64); (void)hipMalloc(s->d_ap_trace.put(), (size_t)65536 * 16); }
+    resident_grids(s->sw, c->device, &s->pass_grid, &s->compact_grid);
     if (c->enable_timing) {                                       // all or nothing: without the whole ring the context runs untimed
         std::unique_ptr<Event[][EV_RING]> ev(new Event[N_EV][EV_RING]);
         bool made = true;
         for (int k = 0; k < N_EV && made; ++k)
             for (int i = 0; i < EV_RING && made; ++i) made = hipEventCreate(ev[k][i].put()) == hipSuccess;
-        if (made) s->ev = std::move(ev);
+        if (made) s->tl.ev = std::move(ev);
     }
     if (c->device >= 0 && c->device < MAX_DEV) { std::lock_guard<std::mutex> lk(g_compact_mu); g_ctx_on_dev[c->device]++; }
     return s.release();
@@ -1256,7 +1241,7 @@ void sm_destroy(sm_ctx *s)
         std::vector<unsigned long long> h((size_t)std::max(s->pass_trace_grid, 0) * 8);
         if (!h.empty() && hipMemcpy(h.data(), s->d_pass_trace, h.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
             char path[512];
-            snprintf(path, sizeof path, "%s.%d.bin", std::getenv("SM_PASS_TRACE") ? std::getenv("SM_PASS_TRACE") : "pass_trace", n_dump++);
+            snprintf(path, sizeof path, "%s.%d.bin", s->sw.trace_prefix.c_str(), n_dump++);
             if (FILE *f = fopen(path, "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
         }
     }
@@ -1266,7 +1251,7 @@ void sm_destroy(sm_ctx *s)
         if (n > 0 && hipMemcpy(h.data() + 3, s->d_ap_trace, (h.size() - 3) * 8, hipMemcpyDeviceToHost) == hipSuccess) {
             h[0] = (unsigned long long)s->ap_trace_n[0] | ((unsigned long long)s->ap_trace_n[3] << 32); h[1] = (unsigned long long)s->ap_trace_n[1]; h[2] = (unsigned long long)s->ap_trace_n[2];
             char path[512];
-            snprintf(path, sizeof path, "%s.assoc_prep.bin", std::getenv("SM_PASS_TRACE") ? std::getenv("SM_PASS_TRACE") : "pass_trace");
+            snprintf(path, sizeof path, "%s.assoc_prep.bin", s->sw.trace_prefix.c_str());
             if (FILE *f = fopen(path, "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
         }
     }
@@ -1567,8 +1552,8 @@ int sm_stage_splat(sm_ctx *s, const float *pose16, int32_t time, float depth_cut
     FrameParams fp = make_params(s, pose16);
     fp.time = time; fp.depth_cutoff = depth_cutoff; fp.time_delta = time_delta;
     HIPCK(hipMemsetAsync(&s->d_state->visible_count, 0, 4, s->stream));
-    s->n_compact_part = 0;                       // k_splat counts with an atomic; no k_compact partials to fold in
-    s->lazy_part_live = false;
+    s->part.clear();
+    s->part.n_compact = 0;                       // k_splat counts with an atomic; no k_compact partials to fold in
     fill_keys(s, s->d_keyT, s->P);
     HIPCK(hipGetLastError());
     const int grid = (int)std::min<uint64_t>(std::max<uint64_t>(((uint64_t)s->h_state->count + 255) / 256, 1), MAX_GRID);
@@ -1595,41 +1580,43 @@ int sm_stage_timings(sm_ctx *s, sm_timings *out)
 {
     if (!s || !out) return SM_E_ARG;
     memset(out, 0, sizeof *out);
-    if (!s->ev) { g_err = "sm_stage_timings: create the context with enable_timing=1"; return SM_E_UNSUPPORTED; }
+    if (!s->tl.ev) { g_err = "sm_stage_timings: create the context with enable_timing=1"; return SM_E_UNSUPPORTED; }
     HIPCK(hipSetDevice(s->cfg.device));
     HIPCK(hipStreamSynchronize(s->stream));
-    uint64_t first = s->ev_read;
-    if (s->ev_frames - first > EV_RING) first = s->ev_frames - EV_RING;
+    Timeline &tl = s->tl;
+    uint64_t first = tl.read;
+    if (tl.frames - first > EV_RING) first = tl.frames - EV_RING;
     double seg[7] = {0}, run = 0, ovh = 0, cull[2] = {0, 0};
     double own[6] = {0};          // pass, fixup (one-pass frames) | conflict (others) | associate (direct) | associate, append (others)
     double prep2[2] = {0, 0};     // k_prep alone | k_assoc_prep
     double scan_own = 0;          // k_scan_cull + k_cull_finalize on the frames that ran k_conflict
     uint32_t nfr = 0, ncls[2] = {0, 0}, n_op = 0, n_dir = 0, n_merged = 0, n_alone = 0;
-    for (uint64_t f = first; f < s->ev_frames; ++f) {
+    for (uint64_t f = first; f < tl.frames; ++f) {
         const int slot = (int)(f % EV_RING);
+        const Timeline::Flags &fl = tl.flags[slot];
         float ms = 0;
         bool ok = true;
         double loc[7];
         for (int k = 0; k < 7 && ok; ++k) {
-            ok = hipEventElapsedTime(&ms, s->ev[k][slot], s->ev[k + 1][slot]) == hipSuccess;
+            ok = hipEventElapsedTime(&ms, tl.ev[k][slot], tl.ev[k + 1][slot]) == hipSuccess;
             loc[k] = ms;
         }
         float o = 0;
-        if (!ok || hipEventElapsedTime(&ms, s->ev[0][slot], s->ev[7][slot]) != hipSuccess ||
-            hipEventElapsedTime(&o, s->ev[8][slot], s->ev[0][slot]) != hipSuccess)
+        if (!ok || hipEventElapsedTime(&ms, tl.ev[0][slot], tl.ev[7][slot]) != hipSuccess ||
+            hipEventElapsedTime(&o, tl.ev[8][slot], tl.ev[0][slot]) != hipSuccess)
             continue;
         for (int k = 0; k < 7; ++k) seg[k] += loc[k];
-        cull[s->ev_compacted[slot] ? 1 : 0] += loc[3];
-        ncls[s->ev_compacted[slot] ? 1 : 0]++;
-        if (s->ev_one_pass[slot]) { own[0] += loc[1]; own[1] += loc[3]; n_op++; } else { own[2] += loc[1]; scan_own += loc[2]; }
-        if (s->ev_direct[slot]) { n_dir++; if (!s->ev_deferred[slot]) { own[3] += loc[4]; n_alone++; } } else { own[4] += loc[4]; own[5] += loc[6]; }
-        prep2[s->ev_merged[slot] ? 1 : 0] += loc[0];
-        if (s->ev_merged[slot]) n_merged++;
+        cull[fl.compacted ? 1 : 0] += loc[3];
+        ncls[fl.compacted ? 1 : 0]++;
+        if (fl.one_pass) { own[0] += loc[1]; own[1] += loc[3]; n_op++; } else { own[2] += loc[1]; scan_own += loc[2]; }
+        if (fl.direct) { n_dir++; if (!fl.deferred) { own[3] += loc[4]; n_alone++; } } else { own[4] += loc[4]; own[5] += loc[6]; }
+        prep2[fl.merged ? 1 : 0] += loc[0];
+        if (fl.merged) n_merged++;
         run += ms;
         ovh += o;
         nfr++;
     }
-    s->ev_read = s->ev_frames;
+    tl.read = tl.frames;
     out->frames = nfr;
     if (nfr) {
         const double inv = 1.0 / nfr;
@@ -1746,8 +1733,7 @@ int ss_compact(sm_ctx *s)
     HIPCK(hipGetLastError());
     s->culls_since_compact = 0;
     s->keys_are_slots = false;
-    s->lazy_part_live = false;
-    s->fix_part_live = false;
+    s->part.clear();
     return SM_OK;
 }
 
@@ -1820,19 +1806,18 @@ int sm_shard_frame_device(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_dep
             if ((uint64_t)s->count_bound + s->n_odd_pixels > s->cap && (rc = pull_state(s))) return rc;
         }
     }
-    s->want_list = fusing;
     FrameParams fp;
-    rc = begin_frame(s, d_rgb, d_depth_mm ? d_depth_mm : s->d_depth_raw, d_semantic ? d_semantic : s->d_sem, pose16, &fp);
-    s->want_list = false;
+    uint32_t n_prep = 0;
+    rc = begin_frame(s, d_rgb, d_depth_mm ? d_depth_mm : s->d_depth_raw, d_semantic ? d_semantic : s->d_sem, pose16, fusing, false, &fp, &n_prep);
     if (rc <= 0) return rc;
     fp.compact_now = 0u;
     fp.conflict_cap = 0xFFFFFFFFu;            // applied over all ranks below (k_shard_cap_pack / k_shard_cap_repair), not per shard
     fp.shard_slots = 1;
     note_cull(s, false);
     s->keys_are_slots = true;
-    if (s->ev) { s->ev_compacted[s->ev_frames % EV_RING] = false; s->ev_one_pass[s->ev_frames % EV_RING] = true; s->ev_direct[s->ev_frames % EV_RING] = true; }
-    if (s->n_prep_blocks == 0) { g_err = "internal: sharded frame without tile flags from k_prep"; return SM_E_ARG; }
-    if ((rc = launch_surfel_pass(s, fp, true, true))) return rc;
+    Timeline::Flags &fl = s->tl.frame();
+    fl.compacted = false; fl.one_pass = fl.direct = true;
+    if ((rc = launch_surfel_pass(s, fp, true, true, n_prep))) return rc;
     // The W*H conflict cap acts in surfel order over ALL ranks: exchange the conflict masks and take this rank's surplus back
     // before anything reads the key map (k_shard_cap_pack / k_shard_cap_repair).  Conflicts <= surfels, so a model with no
     // more slots than pixels cannot reach the cap; the bound is the host's, the same on every rank.
@@ -1840,7 +1825,7 @@ int sm_shard_frame_device(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_dep
         const uint32_t tbnd = (uint32_t)std::min<uint64_t>(((uint64_t)s->count_bound + TILE - 1) / TILE, s->dead_tiles);
         const int gp = (int)std::min<uint32_t>(std::max<uint32_t>((tbnd * (uint32_t)TILE_WORDS + 255u) / 256u, 1u), 1024u);
         hipLaunchKernelGGL(k_shard_cap_pack, dim3(gp), dim3(256), 0, s->stream, s->d_state, s->d_wave_cnt, s->d_cm,
-                           s->d_conf_sub + SUB_SET * s->conf_sub_set, s->d_capx, tbnd);
+                           s->conf_sub(), s->d_capx, tbnd);
         HIPCK(hipGetLastError());
         if ((rc = ss_collective(s, s->d_capx, s->d_capx, (size_t)1 + (size_t)(2 + TILE_WORDS) * tbnd, SM_COLL_SUM))) return rc;
         hipLaunchKernelGGL(k_shard_cap_repair, dim3(std::min<uint32_t>(std::max<uint32_t>(tbnd, 1u), (uint32_t)MAX_GRID)), dim3(256), 0, s->stream, s->M,
@@ -1856,19 +1841,18 @@ int sm_shard_frame_device(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_dep
     fill_assoc_args(s, fp, aa);
     hipLaunchKernelGGL((k_associate_direct<true>), dim3(assoc_wgs(s)), dim3(PIX_BLOCK), 0, s->stream, aa, sh);
     HIPCK(hipGetLastError());
-    if ((rc = mark(s, 5, true))) return rc;
+    if ((rc = s->tl.mark(s->stream, 5, true))) return rc;
     if ((rc = ss_collective(s, s->d_gmask, s->d_gmask, (size_t)sh.nwords + 4, SM_COLL_SUM))) return rc;   // in place, like the key map
     // the frame's last step (counts from the reduced mask, the owner's foreign-fused slots, the totals over the ranks) is
     // only needed by the next frame's surfel pass: it rides on that frame's k_prep (finalize_if_pending runs it earlier if asked)
-    ShardSettle &ss = s->ss_settle;
+    ShardSettle ss;
     ss.n = (uint32_t)s->n_pix_blocks; ss.st = s->d_state; ss.validmask = s->d_validmask; ss.ownmask = s->d_fusedmask; ss.gmask = s->d_gmask;
     ss.nwords = sh.nwords; ss.blk_cand = s->d_blk_cand; ss.grp_cand = s->d_grp_cand; ss.nf = s->d_nf_sub; ss.alive = s->d_alive;
     ss.tile_dead = s->d_tile_dead; ss.owner = sh.owner; ss.cap_pixels = s->cfg.conflict_cap ? (uint32_t)s->P : 0xFFFFFFFFu; ss.max_vertices = s->cap; ss.cg = s->cand_group;
-    s->ss_settle_pending = true;
-    if ((rc = mark(s, 6, true)) || (rc = mark(s, 7, true))) return rc;
-    s->lazy_part_live = false;
-    s->fix_part_live = false;
-    s->pend_finalize = true;
+    s->held.hold_settle(ss);
+    if ((rc = s->tl.mark(s->stream, 6, true)) || (rc = s->tl.mark(s->stream, 7, true))) return rc;
+    s->part.clear();
+    s->held.hold_stats(s->d_nf_sub);
     s->frames_enq++;
     s->ss_frames++;
     bump_bound(s);

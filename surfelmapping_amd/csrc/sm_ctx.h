@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cassert>
 #include <cstdio>
 #include <cstring>
 #include <functional>
@@ -135,6 +136,91 @@ struct Retire {
     Event ev[8];
 };
 
+// The SM_* switches of the frame pipeline (sm_api.hip), read once by sm_create (read_switches): nothing on the per-frame path
+// reads the environment.
+struct Switches {
+    bool defer_assoc = true;           // SM_DEFER_ASSOC=0: every frame launches its own association
+    bool two_launch = true;            // SM_TWO_LAUNCH=0: the fixup step keeps its own launch (three launches per frame)
+    int pass_split = 0;                // SM_PASS_SPLIT=1|4: k_surfel_pass on whole / quarter tiles whatever the model's size (else: the grid policy picks)
+    bool trace = false;                // SM_PASS_TRACE=<file prefix>: per-workgroup time stamps of the last k_surfel_pass and k_assoc_prep launches,
+    std::string trace_prefix;          //   dumped by sm_destroy (tools/pass_trace.py)
+    int compact_tickets = -1;          // SM_COMPACT_TICKETS=1: compactions always use the ticket-ordered kernel (several PROCESSES share a GPU);
+                                       //   =0: never (contexts known not to run at the same time); unset: decided per compaction
+    long capacity_wait_us = 2000;      // SM_CAPACITY_WAIT_US: how long an enqueue may let the device catch up before it compacts instead (decide_compact)
+    bool check_alive = false;          // SM_CHECK_ALIVE (diagnostic): check the alive-bits / dead-count invariant after every stage; reported by sm_sync
+    int pass_wg_per_cu = 0;            // SM_PASS_WG_PER_CU: workgroups of k_surfel_pass per CU taken as resident (0: what the occupancy query says)
+    int compact_wg_per_cu = 0;         // SM_COMPACT_WG_PER_CU: the same for k_compact, within what the occupancy query allows (experiments)
+};
+
+// Work of the last frame that the host has not launched yet.  Each step is held back by the frame that produces it and taken
+// exactly once -- by the next frame's preparation launch where it can ride on it (launch_prep), by finalize_if_pending before
+// anything else reads its results.  The steps complete in this order: fixup, association, settle, statistics.
+// take_*: the arguments (valid until the next hold) with the slot cleared, or null when nothing is held.
+class HeldBack {
+public:
+    // two-launch frame: the fixup step (publisher, cap repair) of a frame whose association is held back too
+    void hold_fixup(const FixArgs &x) { assert(!has_fix_ && !has_assoc_); fix_ = x; has_fix_ = true; }
+    // the association of an asynchronous frame: held back until the next frame's images arrive, then it shares that frame's
+    // preparation launch (k_assoc_prep)
+    void hold_assoc(const AssocArgs &a) { assoc_ = a; has_assoc_ = true; }
+    // A held-back fixup exists only with the held-back association of its frame and runs ahead of it: the two are taken together.
+    // `fix`: that frame's fixup, or null -- it ran in a launch of its own.
+    AssocArgs *take_assoc(FixArgs *&fix)
+    {
+        assert(has_assoc_ || !has_fix_);
+        fix = std::exchange(has_fix_, false) ? &fix_ : nullptr;
+        return std::exchange(has_assoc_, false) ? &assoc_ : nullptr;
+    }
+    // the last sharded frame's settle step: rides on the next k_prep, or runs stand-alone (k_shard_settle)
+    void hold_settle(const ShardSettle &ss) { settle_ = ss; has_settle_ = true; }
+    ShardSettle *take_settle() { return std::exchange(has_settle_, false) ? &settle_ : nullptr; }
+    // the statistics of a direct-append frame (`nf`: the set its association counts into): completed by the next frame's fixup
+    // publisher, or by k_frame_finalize
+    void hold_stats(uint32_t *nf) { nf_ = nf; }
+    uint32_t *take_stats() { return std::exchange(nf_, nullptr); }
+private:
+    bool has_fix_ = false, has_assoc_ = false, has_settle_ = false;
+    FixArgs fix_{};
+    AssocArgs assoc_{};
+    ShardSettle settle_{};
+    uint32_t *nf_ = nullptr;
+};
+
+// Per-workgroup partial sums a frame's cull / pass leaves for the append that follows it (instead of same-address atomics)
+struct PassPartials {
+    Dev<uint2> d_compact;              // k_compact<true>: (visible, splat-skipped)
+    Dev<uint4> d_lazy;                 // k_surfel_pass: (visible, splat-skipped, killed, conflict-skipped)
+    Dev<uint2> d_fix;                  // k_pass_fixup: (visible added, resurrected), read when the cap bound; two sets of MAX_GRID
+    int fix_set = 0;                   // ... which alternate: the previous frame's are read one frame later
+    uint32_t n_compact = 0;            // workgroups whose partials the next append folds (0: the counters are complete)
+    uint32_t n_fix = 0;                // worker workgroups of the last k_pass_fixup
+    bool pass_live = false;            // the next append folds d_lazy and d_fix (not d_compact): only between a pass and the append after it
+    void clear() { pass_live = false; }
+    uint2 *fix_cur() const { return d_fix + (size_t)fix_set * MAX_GRID; }
+    // what k_append_scan folds into the counters
+    struct Fold { const uint2 *compact; uint32_t n_compact; const uint4 *lazy; const uint2 *fix; uint32_t n_fix; };
+    Fold fold() const { return {d_compact, n_compact, pass_live ? d_lazy.get() : nullptr, pass_live ? fix_cur() : nullptr, n_fix}; }
+};
+
+// enable_timing: the per-frame time line (an event before the preparation launch, then one after each kernel) over a ring of
+// frames, and which kernels the frame of each slot ran (sm_stage_timings)
+struct Timeline {
+    // compacted: the frame's cull was k_compact (not one that only marks the dead); one_pass: it ran the one-pass kernels
+    // (k_surfel_pass + fixup); direct: ... and appended directly; merged: its preparation launch was k_assoc_prep (it carried the
+    // previous frame's association, or the chain); deferred: its own association was held back (no kernel between its marks 4 and 5)
+    struct Flags { bool compacted, one_pass, direct, merged, deferred; };
+    std::unique_ptr<Event[][EV_RING]> ev;   // [N_EV][EV_RING]; whole or absent
+    Flags flags[EV_RING] = {};
+    uint64_t frames = 0, read = 0;     // frames recorded / read by sm_stage_timings so far
+    int mark(hipStream_t st, int which, bool timed)
+    {
+        if (timed && ev) HIPCK(hipEventRecord(ev[which][frames % EV_RING], st));
+        return SM_OK;
+    }
+    Flags &frame() { return flags[frames % EV_RING]; }      // this frame's (without the ring `frames` stays 0: the writes land in a slot nobody reads)
+    void end_frame(bool timed) { if (timed && ev) frames++; }
+};
+
 }  // namespace sm_impl
 
 using namespace sm_impl;
@@ -197,40 +283,26 @@ struct sm_ctx {
     Dev<uint32_t> d_tb;                // per-tile bounds (8 words per tile)
     Dev<uint8_t> d_tile_flags;         // per-tile skip flags of the current frame
     Dev<uint8_t> d_tile_flags_nx; Dev<uint4> d_wave_cnt_nx; Dev<uint2> d_prep_part_nx;   // the other frame's (two-launch frame: its publisher runs next to this frame's flag workgroups)
-    Dev<uint32_t> d_conf_part;         // per-workgroup partial counters (instead of same-address atomics)
-    Dev<uint2> d_compact_part;
-    Dev<uint4> d_lazy_part;            // partials of k_surfel_pass (visible, splat-skipped, killed, conflict-skipped)
-    bool lazy_part_live = false;       // the next append folds d_lazy_part (not d_compact_part) into the counters
+    Dev<uint32_t> d_conf_part;         // per-workgroup partial counters of k_conflict (instead of same-address atomics)
+    PassPartials part;
     // one pass over the surfels per frame (k_surfel_pass + k_pass_fixup) on the frames whose cull only marks the dead
     Dev<uint4> d_wave_cnt;             // conflicts per quarter tile (one word per wave)
     Dev<float> d_undo;                 // confidence before this frame's decrement, per slot (read only if the conflict cap binds)
-    Dev<uint2> d_fix_part;             // partials of k_pass_fixup (visible added, resurrected)
-    bool fix_part_live = false;        // the next append also folds d_fix_part in (when the cap bound)
-    uint32_t n_fix_part = 0;           // worker workgroups of the last k_pass_fixup
-    bool ev_one_pass[EV_RING] = {};    // which frames of the event ring ran the one-pass kernels
-    bool ev_direct[EV_RING] = {};      // ... and appended directly
-    bool ev_merged[EV_RING] = {};      // the frame's preparation launch was k_assoc_prep (it carried the previous frame's association)
-    bool ev_deferred[EV_RING] = {};    // the frame's own association was held back (no kernel between its marks 4 and 5)
     // tile skip flags of the frame, evaluated by extra workgroups of the preparation launch
     Dev<uint2> d_prep_part;
-    uint32_t n_prep_blocks = 0;        // flag workgroups the frame's k_prep ran (0: the pass kernel evaluates the flags itself)
-    bool want_list = false;            // set by enqueue_frame before begin_frame launches k_prep
     int fix_grid = 128;
     // direct append (k_associate_direct): candidate counts per association block / per group, group prefixes
     Dev<uint32_t> d_blk_cand, d_grp_cand;
     Dev<uint32_t> d_frame_sub;         // 2 x 64 sub-counters: visible, killed (k_surfel_pass)
     uint32_t *d_nf_sub = nullptr, *d_nf_sub_nx = nullptr;   // 2 x 64 each: new, fused (k_associate_direct) of this / the other frame
-    uint32_t *nf_last = nullptr;       // the set the last direct association counted into (its statistics may still be pending)
     uint32_t n_grp = 0, cand_group = 16;
-    bool pend_finalize = false;        // the last frame's statistics are completed by the next k_pass_fixup or by k_frame_finalize
-    int fix_set = 0;                   // k_pass_fixup's partials alternate between two sets (the previous frame's are read one frame later)
-    Dev<unsigned long long> d_pass_trace;         // SM_PASS_TRACE=<file prefix>: per-workgroup time stamps of the last k_surfel_pass launch, dumped by sm_destroy
+    Dev<unsigned long long> d_pass_trace;         // Switches::trace: per-workgroup time stamps of the last k_surfel_pass launch, dumped by sm_destroy
     int pass_trace_grid = 0;
     Dev<unsigned long long> d_ap_trace;           // the same for the last k_assoc_prep launch: (entry, exit) per workgroup
     int ap_trace_n[4] = {0, 0, 0, 0};             // its association / tile-flag / image workgroups (dispatch order); fixup workgroups ahead of them
     Dev<uint32_t> d_conf_sub;          // 2 x 64 conflict sub-counters (one set per frame parity: zeroed by that frame's k_prep)
-    int conf_sub_set = 0;
-    uint32_t n_conf_part = 0, n_compact_part = 0;
+    uint32_t *conf_sub() const { return d_conf_sub + SUB_SET * plane_set; }   // the current frame's set
+    uint32_t n_conf_part = 0;
     uint32_t tb_tiles = 0;
     uint32_t cull_epoch = 0;
     int compact_grid = COMPACT_GRID;
@@ -248,24 +320,18 @@ struct sm_ctx {
     void *ss_user = nullptr;
     void *ss_comm = nullptr;           // ncclComm_t when the built-in RCCL binding is used
     Dev<uint64_t> d_galive, d_new_alive, d_gmask;
-    Dev<uint32_t> d_chk;               // SM_CHECK_ALIVE=1: result words of k_check_alive
+    Dev<uint32_t> d_chk;               // Switches::check_alive: result words of k_check_alive
     Dev<uint64_t> d_capx;              // the conflict-cap exchange of a sharded frame: total | quarter-tile counts | conflict masks (k_shard_cap_pack)
     Dev<uint32_t> d_ss_info;
+    Switches sw;
     // deferred association (k_assoc_prep): the association of an asynchronous frame is held back until the next frame's images
-    // arrive and then shares that frame's k_prep launch (three launches per frame instead of four)
-    bool defer_ok = false;             // this context may defer (plain stream, no depth filter chain, no per-kernel timing)
-    bool assoc_pending = false;
-    AssocArgs assoc_args{};            // the held-back association (its FrameParams and that frame's planes)
-    bool merge_assoc = false;          // set by enqueue_frame: the k_prep launch of this call carries assoc_args
-    // two-launch frame: the fixup step (publisher, cap repair) of a frame whose association is held back rides on the same
-    // launch as that association; the candidate count moved into the pass's launch
-    bool two_launch = false;           // this context uses it (defer_ok, SM_TWO_LAUNCH != 0)
-    uint32_t est_fr0 = 0, est_slots0 = 0, est_rate = 0xFFFFFFFFu;   // launch_surfel_pass's estimate of the slots per frame (from the pinned statistic)
-    bool fix_pending = false;          // the last frame's fixup has not run yet
-    FixArgs fix_args{};
+    // arrive and then shares that frame's k_prep launch (three launches per frame instead of four).  Two-launch frame
+    // (sw.two_launch): the frame's fixup step is held back with it and rides on the same launch; the candidate count moved into
+    // the pass's launch
+    bool defer_ok = false;             // this context may defer (sw.defer_assoc, not a sharded stream)
+    HeldBack held;
+    uint32_t est_fr0 = 0, est_slots0 = 0, est_rate = 0xFFFFFFFFu;   // pass_grid_policy's estimate of the slots per frame (from the pinned statistic)
     static constexpr uint32_t N_CREW = 32;
-    bool ss_settle_pending = false;    // the last sharded frame's k_shard_settle work rides on the next k_prep (or runs stand-alone first)
-    ShardSettle ss_settle{};
     int n_pix_blocks = 0;
     uint32_t n_odd_pixels = 0;
     // export staging
@@ -285,11 +351,8 @@ struct sm_ctx {
     uint32_t count_before_cull = 0, offset_before_cull = 0;
     sm_counts counts{};
     std::vector<Dev<void>> user_allocs;
-    // timing
-    std::unique_ptr<Event[][EV_RING]> ev;   // enable_timing: per-frame timeline (before prep, then after each kernel), [N_EV][EV_RING]; whole or absent
-    bool ev_compacted[EV_RING] = {};  // which cull kernel the frame of that slot ran
+    Timeline tl;
     Dev<FrameLog> d_log;
-    uint64_t ev_frames = 0, ev_read = 0;
 };
 
 namespace sm_impl __attribute__((visibility("hidden"))) {

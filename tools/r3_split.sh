@@ -18,7 +18,7 @@ print(sys.argv[2], "value", round(d["value"]), round(d["ms_per_step"]*1e3,2), "u
 PY
 }
 for cfg in "20 5" "100 10"; do set -- $cfg; BARGS="--steps $1 --warmup $2"
-  run s1_$1 SM_PASS_SPLIT=1 && run s4_$1 SM_PASS_SPLIT=4 && run s4q384_$1 SM_PASS_SPLIT=4 SM_PASS_SEQ=384 && run s4q256_$1 SM_PASS_SPLIT=4 SM_PASS_SEQ=256 || exit 1
+  run s1_$1 SM_PASS_SPLIT=1 && run s4_$1 SM_PASS_SPLIT=4 || exit 1
 done
 BARGS="--workload hd20m --steps 40 --warmup 5"
 run hd_s1 SM_PASS_SPLIT=1 && run hd_s4 SM_PASS_SPLIT=4

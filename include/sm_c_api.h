@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define SM_API_VERSION 4   /* bumped whenever a struct or an entry point changes (3, 4: round 3 -- asynchronous host path, rig step, sm_timings::k_scan_own, sm_host_alloc_frame; the staged shard entry points are gone).  Purely additive changes keep it: sm_model_view / sm_render_model* and sm_track_* were added at 4, no existing struct or entry point changed. */
+#define SM_API_VERSION 4   /* bumped whenever a struct or an entry point changes (3, 4: round 3 -- asynchronous host path, rig step, sm_timings::k_scan_own, sm_host_alloc_frame; the staged shard entry points are gone).  Purely additive changes keep it: sm_model_view / sm_render_model*, sm_track_* and sm_track_*rgb* were added at 4, no existing struct or entry point changed. */
 
 /* error codes (reference: void returns + CheckGlDieOnError(); bool for map IO) */
 enum {
@@ -299,6 +299,60 @@ int sm_track_frame(sm_ctx *s, const uint16_t *depth_mm, const float *guess16, co
  * rows of sm_download_model_aos once the model is compacted) and the 29-value system of ONE iteration at pose16_eval with the default
  * parameters (sys29: J^T J upper triangle row-major (21), J^T r (6), sum r^2, inliers; double).  Either output may be NULL. */
 int sm_track_debug(sm_ctx *s, const uint16_t *depth_mm, const float *pose16_eval, int32_t *pred_slot, double *sys29);
+
+/* ---- camera tracking with the colour term (DESIGN.md "4d. Tracking", "colour term") ----
+ * Depth alone cannot see motion along flat ground between flat walls (sm_track_frame reports SM_TRACK_DEGENERATE there).
+ * sm_track_frame_rgb adds a photometric term -- the surfels' stored colours against the frame's rgb image -- solved jointly with the
+ * geometric one over an image pyramid, coarse to fine.  Everything not restated here is sm_track_frame's rule: the guess, the
+ * orthonormalisation, the prediction at T_prev, the frame's depth / vertex / normal rule, the left-multiplied world twist, fp32
+ * per-sample terms with fp64 sums in a fixed order (bit-reproducible), the device LDLT, one host synchronisation per frame.
+ *  - Luminance: Y = ((0.299f*R + 0.587f*G) + 0.114f*B) / 255.0f; a surfel's from its colour word (sem<<24 | r<<16 | g<<8 | b).
+ *  - Pyramid: level 0 is the frame's luminance, level l+1 the mean ((a+b)+(c+d))*0.25f of each 2x2 block (a b the upper row), of size
+ *    floor(w/2) x floor(h/2).  Pixel k of level l spans [k*2^l, (k+1)*2^l) in full-resolution coordinates.  No validity mask.
+ *  - Levels run from levels-1 down to 0, at most iters[l] Gauss-Newton systems at level l; a level ends early when the step is below
+ *    sm_track_frame's stop thresholds; ending level 0 ends the frame.  sum(iters[0..levels-1]) <= SM_TRACK_MAX_ITERS.
+ *  - The sample stride at level l is pixel_stride * 2^l for both terms; the geometric term at level l is exactly sm_track_frame's on
+ *    that strided grid.
+ *  - Photometric samples: one per prediction pixel of the strided grid that holds a surfel, p its world centre, Y_m its luminance.
+ *    Under the estimate T = [R|t]: c = R^T (p - t), x = fx*c.x/c.z + cx, y = fy*c.y/c.z + cy (pixel i is centred at i + 0.5).  Kept
+ *    iff c.z > 0; 0 <= x < W and 0 <= y < H; the frame's metric depth D at pixel (floor x, floor y) is non-zero and
+ *    |D - c.z| <= dist_thresh (occlusion; drops the stereo border too); the four texels of the bilinear sample of level l at
+ *    (x/2^l - 0.5, y/2^l - 0.5) lie inside the level image; |r| < rgb_max_residual, r = I_l(bilinear) - Y_m.  (gx, gy) = the
+ *    derivative of that interpolant / 2^l; g_c = (gx*fx/c.z, gy*fy/c.z, -(gx*fx*c.x + gy*fy*c.y)/c.z^2), g_w = R g_c; the Jacobian
+ *    row is -[g_w, p x g_w].
+ *  - System: A = A_icp + rgb_weight * A_rgb, b likewise, added in double after each term's own fixed-order sum.
+ *  - Status: SM_TRACK_LOST if in any iteration (geometric inliers) * 4^l < min_inliers; SM_TRACK_DEGENERATE judged on the joint
+ *    system of the last level-0 iteration with sm_track_frame's measure and bound; SM_TRACK_NO_MODEL as there.  Failure returns the
+ *    guess.
+ *  - With levels = 1, iters[0] = max_iters and rgb_weight = 0 the call equals sm_track_frame bit for bit, pose and info.
+ *    (sm_track_params::max_iters is range-checked as there and otherwise unused: iters[] is the schedule.) */
+typedef struct sm_track_rgb_params {
+    int32_t levels;           /* 3 (1..6) */
+    int32_t iters[6];         /* index = level: 10, 5, 4, 4, 4, 4 */
+    float rgb_weight;         /* 0.01: lambda of the joint system */
+    float rgb_max_residual;   /* 0.25 (luminance in 0..1) */
+} sm_track_rgb_params;
+
+typedef struct sm_track_rgb_info {
+    uint32_t rgb_inliers;     /* photometric samples of the last system */
+    float rgb_rmse;           /* sqrt(sum r^2 / rgb_inliers) of the last system, luminance units */
+    double pivot_ratio;       /* the degeneracy measure of the last system that was solved (joint) */
+    int32_t level_iterations[6];  /* systems solved per level */
+} sm_track_rgb_info;
+
+int sm_default_track_rgb_params(sm_track_rgb_params *p);
+/* sm_track_frame with the colour term: rgb is the frame's H*W*3 u8 image (host memory), as sm_process_frame takes it.  info and
+ * rgb_info may be NULL; sm_track_info's inliers and rmse are the geometric term's.  Synchronous; changes nothing in the model, its
+ * counters, the frame log, the pose history or the compaction schedule.  SM_E_ARG / SM_E_UNSUPPORTED as sm_track_frame, and
+ * SM_E_ARG for a NULL rgb, levels outside 1..6, iters[l] < 1 for a used level, sum of iters > SM_TRACK_MAX_ITERS, rgb_weight < 0
+ * or not finite, rgb_max_residual <= 0, a coarsest level smaller than 8x8, pixel_stride * 2^(levels-1) > min(W, H). */
+int sm_track_frame_rgb(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params,
+                       const sm_track_rgb_params *rgb_params, float *pose16_out, sm_track_info *info, sm_track_rgb_info *rgb_info);
+/* For tests: the 29-value system (layout as sm_track_debug) of ONE iteration at pose16_eval and `level` (0..5) with the default
+ * parameters.  which: 0 = joint (values 0..27 = geometric + rgb_weight * photometric, value 28 the geometric inliers), 1 = the
+ * geometric term only, 2 = the photometric term only, unweighted (sum r^2 and count are that term's). */
+int sm_track_rgb_debug(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *pose16_eval, int level, int which,
+                       double *sys29);
 
 /* ---- retirement (DESIGN.md "4e. Retirement") ----
  * The model grows with the distance driven and MAX_VERTICES is fixed; the reference leaves that to a person (build_map.cpp:204

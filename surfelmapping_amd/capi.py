@@ -32,6 +32,7 @@ SYMBOLS = (
     "sm_shard_rccl_finalize", "sm_shard_rccl_nranks", "sm_shard_frame_device", "sm_shard_frame", "sm_shard_compact", "sm_shard_export_dense_device",
     "sm_gpu_process_count", "sm_rig_configure", "sm_rig_consolidate", "sm_rig_consolidate_step",
     "sm_default_track_params", "sm_track_frame", "sm_track_debug",
+    "sm_default_track_rgb_params", "sm_track_frame_rgb", "sm_track_rgb_debug",
     "sm_default_retire_params", "sm_retire", "sm_retire_device", "sm_set_auto_retire", "sm_auto_retire_stats",
 )
 
@@ -115,6 +116,31 @@ def track_params(**over) -> SmTrackParams:
         if not hasattr(p, k):
             raise KeyError(k)
         setattr(p, k, v)
+    return p
+
+
+class SmTrackRgbParams(C.Structure):
+    _fields_ = [("levels", C.c_int32), ("iters", C.c_int32 * 6), ("rgb_weight", C.c_float), ("rgb_max_residual", C.c_float)]
+
+
+class SmTrackRgbInfo(C.Structure):
+    _fields_ = [("rgb_inliers", C.c_uint32), ("rgb_rmse", C.c_float), ("pivot_ratio", C.c_double),
+                ("level_iterations", C.c_int32 * 6)]
+
+
+def track_rgb_params(**over) -> SmTrackRgbParams:
+    """sm_default_track_rgb_params with fields overridden (levels, iters: a sequence whose index is the level, the levels it
+    does not name keep their default; rgb_weight, rgb_max_residual)"""
+    p = SmTrackRgbParams()
+    load().sm_default_track_rgb_params(C.byref(p))
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise KeyError(k)
+        if k == "iters":
+            for l, n in enumerate(v):
+                p.iters[l] = int(n)
+        else:
+            setattr(p, k, v)
     return p
 
 
@@ -296,6 +322,10 @@ def load():
     L.sm_default_track_params.argtypes = [C.POINTER(SmTrackParams)]
     L.sm_track_frame.argtypes = [vp, vp, vp, C.POINTER(SmTrackParams), vp, C.POINTER(SmTrackInfo)]
     L.sm_track_debug.argtypes = [vp, vp, vp, vp, vp]
+    L.sm_default_track_rgb_params.argtypes = [C.POINTER(SmTrackRgbParams)]
+    L.sm_track_frame_rgb.argtypes = [vp, vp, vp, vp, C.POINTER(SmTrackParams), C.POINTER(SmTrackRgbParams), vp,
+                                     C.POINTER(SmTrackInfo), C.POINTER(SmTrackRgbInfo)]
+    L.sm_track_rgb_debug.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp]
     L.sm_default_retire_params.argtypes = [C.POINTER(SmConfig), C.POINTER(SmRetireParams)]
     L.sm_retire.argtypes = [vp, vp, C.POINTER(SmRetireParams), vp, C.c_uint32, u32p]
     L.sm_retire_device.argtypes = [vp, vp, C.POINTER(SmRetireParams), vp, C.c_uint32, u32p]
@@ -480,6 +510,63 @@ class SurfelMap:
         """track() the frame, then process_frame() it with the tracked pose (the guess when tracking failed).
         Returns (pose 4x4 float32, info dict) as track()."""
         pose, info = self.track(depth, guess, **params)
+        self.process_frame(rgb, depth, sem, _mat16(pose))
+        return pose, info
+
+    # -- tracking with the colour term (sm_track_frame_rgb)
+    _RGB_KEYS = ("levels", "iters", "rgb_weight", "rgb_max_residual")
+
+    def track_rgb(self, rgb, depth, guess=None, **params):
+        """track() with the photometric term, coarse to fine (sm_track_frame_rgb): rgb uint8[H][W][3] as process_frame takes it.
+        params override sm_default_track_params and sm_default_track_rgb_params (levels, iters, rgb_weight, rgb_max_residual).
+        Returns (pose, info) as track(), info with rgb_inliers, rgb_rmse, pivot_ratio and level_iterations (list of 6) added."""
+        rgb = np.ascontiguousarray(rgb, np.uint8)
+        depth = np.ascontiguousarray(depth, np.uint16)
+        assert depth.size == self.P and rgb.size == self.P * 3, (depth.shape, rgb.shape)
+        g = None if guess is None else _mat16(guess)
+        icp = {k: v for k, v in params.items() if k not in self._RGB_KEYS}
+        col = {k: v for k, v in params.items() if k in self._RGB_KEYS}
+        p = track_params(**icp) if icp else None
+        q = track_rgb_params(**col) if col else None
+        out = np.zeros(16, np.float32)
+        info, rinfo = SmTrackInfo(), SmTrackRgbInfo()
+        self._chk(self._L.sm_track_frame_rgb(self._h, _ptr(rgb), _ptr(depth), _ptr(g), C.byref(p) if p is not None else None,
+                                             C.byref(q) if q is not None else None, _ptr(out), C.byref(info), C.byref(rinfo)),
+                  "sm_track_frame_rgb")
+        d = dict(status=TRACK_STATUS.get(info.status, str(info.status)), status_code=int(info.status),
+                 iterations=int(info.iterations), inliers=int(info.inliers), rmse=float(info.rmse),
+                 guess=np.array(info.guess[:], np.float32).reshape(4, 4).T.copy(),
+                 rgb_inliers=int(rinfo.rgb_inliers), rgb_rmse=float(rinfo.rgb_rmse), pivot_ratio=float(rinfo.pivot_ratio),
+                 level_iterations=[int(x) for x in rinfo.level_iterations])
+        return out.reshape(4, 4).T.copy(), d
+
+    def track_rgb_debug(self, rgb, depth, pose_eval, level=0, which=0):
+        """sm_track_rgb_debug: the system float64[29] of one iteration at pose_eval and `level` with the default parameters;
+        which 0 = joint, 1 = the geometric term, 2 = the photometric term (unweighted)"""
+        rgb = np.ascontiguousarray(rgb, np.uint8)
+        depth = np.ascontiguousarray(depth, np.uint16)
+        assert depth.size == self.P and rgb.size == self.P * 3, (depth.shape, rgb.shape)
+        pe = _mat16(pose_eval)
+        sys29 = np.zeros(29, np.float64)
+        self._chk(self._L.sm_track_rgb_debug(self._h, _ptr(rgb), _ptr(depth), _ptr(pe), int(level), int(which), _ptr(sys29)),
+                  "sm_track_rgb_debug")
+        return sys29
+
+    def track_rgb_stats(self):
+        """device times of the last track_rgb()/track_rgb_debug() call made with SM_TRACK_TIMING=1 (sm_debug_track_rgb_stats, not
+        part of the C-ABI header): a list of (kind, level, ms), kind one of "prediction", "vertex", "pyramid", "gather",
+        "level_vertex", "icp", "photo", "solve"; [] if it was not timed"""
+        f = self._L.sm_debug_track_rgb_stats
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]
+        ms, kind, n = (C.c_float * 512)(), (C.c_int * 512)(), C.c_int()
+        self._chk(f(self._h, ms, kind, 512, C.byref(n)), "sm_debug_track_rgb_stats")
+        names = ("prediction", "vertex", "pyramid", "gather", "level_vertex", "icp", "photo", "solve")
+        return [(names[kind[i] & 15], kind[i] >> 4, float(ms[i])) for i in range(n.value)]
+
+    def process_frame_tracked_rgb(self, rgb, depth, sem, guess=None, **params):
+        """track_rgb() the frame, then process_frame() it with the tracked pose (the guess when tracking failed).
+        Returns (pose 4x4 float32, info dict) as track_rgb()."""
+        pose, info = self.track_rgb(rgb, depth, guess, **params)
         self.process_frame(rgb, depth, sem, _mat16(pose))
         return pose, info
 

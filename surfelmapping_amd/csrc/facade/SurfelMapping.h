@@ -64,7 +64,8 @@ public:
     // dereferences it: src/SurfelMapping.cpp:130): the depth image is tracked against the model (sm_track_frame, constant-velocity
     // guess, default parameters) and the frame is then fused with the tracked pose.  A failed track (LOST, DEGENERATE,
     // NO_MODEL) prints one line and fuses with the guess.  With SM_FACADE_ASYNC=1 the track waits for the frames in flight; the
-    // frame itself is enqueued as usual.
+    // frame itself is enqueued as usual.  After setTrackColour(true) the track is sm_track_frame_rgb with the frame's own rgb
+    // (default parameters): the colour term sees motion along flat ground and walls, where depth alone is DEGENERATE.
     void processFrame(const unsigned char *rgb, const unsigned short *depth = nullptr, const unsigned char *semantic = nullptr,
                       const Eigen::Matrix4f *gtPose = 0)
     {
@@ -73,7 +74,10 @@ public:
             const unsigned short *d = depth ? depth : (textures[GPUTexture::DEPTH_RAW]->host_u16.empty()
                                                            ? nullptr : textures[GPUTexture::DEPTH_RAW]->host_u16.data());
             if (!d) { std::printf("processFrame: no gtPose and no depth image to track\n"); return; }
-            if (sm_track_frame(ctx_, d, nullptr, nullptr, tracked.data(), &lastTrackInfo) != SM_OK) {
+            const int rc = trackColour_ ? sm_track_frame_rgb(ctx_, rgb, d, nullptr, nullptr, nullptr, tracked.data(), &lastTrackInfo,
+                                                             &lastTrackRgbInfo)
+                                        : sm_track_frame(ctx_, d, nullptr, nullptr, tracked.data(), &lastTrackInfo);
+            if (rc != SM_OK) {
                 std::printf("processFrame: %s\n", sm_last_error());
                 return;
             }
@@ -110,6 +114,9 @@ public:
     const std::vector<Eigen::Matrix4f> &getHistoryPoses() { return historyPoses; }
     // statistics of the last processFrame that tracked (gtPose null); zero before the first
     const sm_track_info &getLastTrackInfo() { return lastTrackInfo; }
+    // track with the colour term as well (off by default); its statistics of the last processFrame that tracked with it
+    void setTrackColour(bool on) { trackColour_ = on; }
+    const sm_track_rgb_info &getLastTrackRgbInfo() { return lastTrackRgbInfo; }
     IndexMap &getIndexMap() { return indexMap; }
     GlobalModel &getGlobalModel() { return globalModel; }
 
@@ -224,6 +231,8 @@ private:
     std::map<std::string, GPUTexture *> textures;
     std::vector<Eigen::Matrix4f> historyPoses;
     sm_track_info lastTrackInfo{};
+    sm_track_rgb_info lastTrackRgbInfo{};
+    bool trackColour_ = false;
     bool beginCleanPoints = false;
     bool async_ = false;
 };

@@ -26,7 +26,7 @@
 #include <utility>
 #include <vector>
 
-namespace sm { struct TrackState; }
+namespace sm { struct TrackState; struct TrackRgbState; }
 
 // Hidden: libsurfelmapping_hip.so exports the C ABI and the kernels' host stubs, nothing of this namespace.  Its functions are
 // defined qualified (sm_impl::name) so that the definitions keep the visibility.
@@ -101,6 +101,14 @@ struct Tracker {
     bool timed = false;                // SM_TRACK_TIMING=1 at the last call: events around every kernel
     int ev_iters = 0;                  // iterations the events of the last timed call cover
     std::vector<Event> ev;
+    // the colour term (sm_track_frame_rgb): scratch allocated by its first call
+    Dev<uint8_t> d_rgb;
+    Dev<float> d_pyr;                  // the luminance pyramid, level after level
+    Dev<float4> d_plane;               // the prediction as (surfel centre, luminance) per pixel
+    Dev<double> d_part_rgb;
+    Dev<TrackRgbState> d_rstate;
+    Host<TrackRgbState> h_rstate;
+    std::vector<int> ev_kind;          // of the last timed rgb call: what the interval after event 2 + k covers (kind | level << 4)
     // every processed frame's pose (begin_frame): the constant-velocity history of sm_track_frame
     void note_pose(const float *pose)
     {

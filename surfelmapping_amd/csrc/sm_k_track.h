@@ -176,14 +176,30 @@ __device__ __forceinline__ double track_wave_sum(double x)
     return x;
 }
 
-// every workgroup: its lanes take grid points idx = blockIdx*256 + tid + k * nb*256 (fixed), so partials do not depend on timing
-__global__ __launch_bounds__(TRACK_BLOCK) void k_track_reduce(Model M, const DevState *__restrict__ st, TrackParams tp,
-                                                              const float4 *__restrict__ vmap, const float4 *__restrict__ nmap,
-                                                              const int32_t *__restrict__ pred, const TrackState *__restrict__ ts,
-                                                              double *__restrict__ part)
+// the workgroup's 29 wave-reduced sums -> one partial per value (fixed order: waves 0, 1, 2, 3)
+__device__ __forceinline__ void track_block_sum(const double *acc, double (*s_w)[TRACK_NSYS], int nb, double *__restrict__ part)
 {
-    if (ts->done) return;                                     // converged or failed: the remaining launches are no-ops
-    __shared__ double s_w[TRACK_BLOCK / 64][TRACK_NSYS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int e = 0; e < TRACK_NSYS; ++e) {
+        const double x = track_wave_sum(acc[e]);
+        if (lane == 0) s_w[wave][e] = x;
+    }
+    __syncthreads();
+    if (threadIdx.x < TRACK_NSYS) {
+        double x = s_w[0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < TRACK_BLOCK / 64; ++w) x += s_w[w][threadIdx.x];
+        part[(size_t)threadIdx.x * nb + blockIdx.x] = x;
+    }
+}
+
+// every workgroup: its lanes take grid points idx = blockIdx*256 + tid + k * nb*256 (fixed), so partials do not depend on timing
+__device__ __forceinline__ void track_reduce_body(const Model &M, const DevState *__restrict__ st, const TrackParams &tp,
+                                                  const float4 *__restrict__ vmap, const float4 *__restrict__ nmap,
+                                                  const int32_t *__restrict__ pred, const TrackState *__restrict__ ts,
+                                                  double *__restrict__ part, double (*s_w)[TRACK_NSYS])
+{
     float m[16];
     track_pose_f(ts, m);
     const SurfelSet cur = M.s[st->cur];
@@ -204,19 +220,17 @@ __global__ __launch_bounds__(TRACK_BLOCK) void k_track_reduce(Model M, const Dev
         acc[27] += (double)(r * r);
         acc[28] += 1.0;
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int e = 0; e < TRACK_NSYS; ++e) {
-        const double x = track_wave_sum(acc[e]);
-        if (lane == 0) s_w[wave][e] = x;
-    }
-    __syncthreads();
-    if (threadIdx.x < TRACK_NSYS) {
-        double x = s_w[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < TRACK_BLOCK / 64; ++w) x += s_w[w][threadIdx.x];
-        part[(size_t)threadIdx.x * tp.nb + blockIdx.x] = x;
-    }
+    track_block_sum(acc, s_w, tp.nb, part);
+}
+
+__global__ __launch_bounds__(TRACK_BLOCK) void k_track_reduce(Model M, const DevState *__restrict__ st, TrackParams tp,
+                                                              const float4 *__restrict__ vmap, const float4 *__restrict__ nmap,
+                                                              const int32_t *__restrict__ pred, const TrackState *__restrict__ ts,
+                                                              double *__restrict__ part)
+{
+    if (ts->done) return;                                     // converged or failed: the remaining launches are no-ops
+    __shared__ double s_w[TRACK_BLOCK / 64][TRACK_NSYS];
+    track_reduce_body(M, st, tp, vmap, nmap, pred, ts, part, s_w);
 }
 
 // exp of the twist (rho, phi) as R (row-major 3x3) and t, double
@@ -262,88 +276,78 @@ __device__ inline bool track_ldlt(const double A[6][6], double L[6][6], double d
     return true;
 }
 
-// one workgroup.  sum_only: only the fixed-order sum into ts->sys (sm_track_debug)
-__global__ __launch_bounds__(256) void k_track_solve(TrackParams tp, const double *__restrict__ part, TrackState *__restrict__ ts,
-                                                     int sum_only)
+// the fixed-order sum of the nb partials of each of the 29 values (all 256 threads; sys is valid in thread 0).  Thread (e, sub)
+// sums partials sub, sub + 8, ... of value e into four interleaved accumulators (independent loads in flight) and adds them in a
+// fixed order; thread 0 then adds the eight sub-sums of every value
+__device__ __forceinline__ void track_sum_parts(const double *__restrict__ part, int nb, double (*s_p)[8], double *sys)
 {
-    if (ts->done) return;
-    __shared__ double s_p[TRACK_NSYS][8];
     const int t = threadIdx.x;
     if (t < TRACK_NSYS * 8) {
-        // thread (e, sub) sums partials sub, sub + 8, ... of value e into four interleaved accumulators (independent loads in
-        // flight), then adds them in a fixed order
         const int e = t >> 3, sub = t & 7;
-        const double *pe = part + (size_t)e * tp.nb;
+        const double *pe = part + (size_t)e * nb;
         double x0 = 0.0, x1 = 0.0, x2 = 0.0, x3 = 0.0;
         int b = sub;
-        for (; b + 24 < tp.nb; b += 32) { x0 += pe[b]; x1 += pe[b + 8]; x2 += pe[b + 16]; x3 += pe[b + 24]; }
-        for (; b < tp.nb; b += 8) x0 += pe[b];
+        for (; b + 24 < nb; b += 32) { x0 += pe[b]; x1 += pe[b + 8]; x2 += pe[b + 16]; x3 += pe[b + 24]; }
+        for (; b < nb; b += 8) x0 += pe[b];
         s_p[e][sub] = (x0 + x1) + (x2 + x3);
     }
     __syncthreads();
     if (t != 0) return;
-    double sys[TRACK_NSYS];
     for (int e = 0; e < TRACK_NSYS; ++e) {
         double x = s_p[e][0];
         for (int k = 1; k < 8; ++k) x += s_p[e][k];
         sys[e] = x;
-        ts->sys[e] = x;
     }
-    if (sum_only) return;
-    const double cnt = sys[28];
-    ts->iterations += 1;
-    ts->inliers = (uint32_t)cnt;
-    ts->rmse = cnt > 0.0 ? sqrt(sys[27] / cnt) : 0.0;
-    auto fail = [&](int status) {
-        for (int e = 0; e < 16; ++e) ts->T[e] = ts->guess[e];
-        ts->status = status;
-        ts->done = 1;
-    };
-    if (ts->iterations == 1 && ts->in_view == 0u) { fail(TRACK_NO_MODEL); return; }
-    if (cnt < (double)tp.min_inliers || cnt < 6.0) { fail(TRACK_LOST); return; }
-    double A[6][6], b[6];
+}
+
+__device__ inline void track_unpack(const double *sys, double A[6][6], double b[6])
+{
     int e = 0;
     for (int a = 0; a < 6; ++a)
         for (int c = a; c < 6; ++c) { A[a][c] = sys[e]; A[c][a] = sys[e]; ++e; }
     for (int a = 0; a < 6; ++a) b[a] = sys[21 + a];
-    // degeneracy: the same system with the rotation taken about the prediction camera centre c (rows [n, (Tv - c) x n]: B = M^T A M,
-    // M = [[I, [c]x], [0, I]]) and the rotation columns scaled by 1/s, s^2 = (trace of its rotation block) / (trace of its
-    // translation block): unit-free and independent of where the world origin lies
-    {
-        const double cx = tp.c[0], cy = tp.c[1], cz = tp.c[2];
-        const double Mx[6][6] = {{1, 0, 0, 0, -cz, cy}, {0, 1, 0, cz, 0, -cx}, {0, 0, 1, -cy, cx, 0},
-                                 {0, 0, 0, 1, 0, 0}, {0, 0, 0, 0, 1, 0}, {0, 0, 0, 0, 0, 1}};
-        double AM[6][6], B[6][6];
-        for (int i = 0; i < 6; ++i)
-            for (int j = 0; j < 6; ++j) {
-                double x = 0.0;
-                for (int k = 0; k < 6; ++k) x += A[i][k] * Mx[k][j];
-                AM[i][j] = x;
-            }
-        for (int i = 0; i < 6; ++i)
-            for (int j = 0; j < 6; ++j) {
-                double x = 0.0;
-                for (int k = 0; k < 6; ++k) x += Mx[k][i] * AM[k][j];
-                B[i][j] = x;
-            }
-        const double tr_t = B[0][0] + B[1][1] + B[2][2], tr_r = B[3][3] + B[4][4] + B[5][5];
-        const double sc = tr_r > 0.0 && tr_t > 0.0 ? sqrt(tr_t / tr_r) : 1.0;
-        for (int i = 0; i < 6; ++i)
-            for (int j = 0; j < 6; ++j) B[i][j] *= (i >= 3 ? sc : 1.0) * (j >= 3 ? sc : 1.0);
-        double L[6][6], d[6];
-        double ratio = 0.0;
-        if (track_ldlt(B, L, d)) {
-            double lo = d[0], hi = d[0];
-            for (int k = 1; k < 6; ++k) { lo = fmin(lo, d[k]); hi = fmax(hi, d[k]); }
-            ratio = lo / hi;
+}
+
+// degeneracy: the same system with the rotation taken about the prediction camera centre c (rows [n, (Tv - c) x n]: B = M^T A M,
+// M = [[I, [c]x], [0, I]]) and the rotation columns scaled by 1/s, s^2 = (trace of its rotation block) / (trace of its
+// translation block): unit-free and independent of where the world origin lies.  Smallest / largest LDLT pivot (0: not positive)
+__device__ inline double track_pivot_ratio(const double A[6][6], const double *c)
+{
+    const double cx = c[0], cy = c[1], cz = c[2];
+    const double Mx[6][6] = {{1, 0, 0, 0, -cz, cy}, {0, 1, 0, cz, 0, -cx}, {0, 0, 1, -cy, cx, 0},
+                             {0, 0, 0, 1, 0, 0}, {0, 0, 0, 0, 1, 0}, {0, 0, 0, 0, 0, 1}};
+    double AM[6][6], B[6][6];
+    for (int i = 0; i < 6; ++i)
+        for (int j = 0; j < 6; ++j) {
+            double x = 0.0;
+            for (int k = 0; k < 6; ++k) x += A[i][k] * Mx[k][j];
+            AM[i][j] = x;
         }
-        ts->pivot_ratio = ratio;
+    for (int i = 0; i < 6; ++i)
+        for (int j = 0; j < 6; ++j) {
+            double x = 0.0;
+            for (int k = 0; k < 6; ++k) x += Mx[k][i] * AM[k][j];
+            B[i][j] = x;
+        }
+    const double tr_t = B[0][0] + B[1][1] + B[2][2], tr_r = B[3][3] + B[4][4] + B[5][5];
+    const double sc = tr_r > 0.0 && tr_t > 0.0 ? sqrt(tr_t / tr_r) : 1.0;
+    for (int i = 0; i < 6; ++i)
+        for (int j = 0; j < 6; ++j) B[i][j] *= (i >= 3 ? sc : 1.0) * (j >= 3 ? sc : 1.0);
+    double L[6][6], d[6];
+    double ratio = 0.0;
+    if (track_ldlt(B, L, d)) {
+        double lo = d[0], hi = d[0];
+        for (int k = 1; k < 6; ++k) { lo = fmin(lo, d[k]); hi = fmax(hi, d[k]); }
+        ratio = lo / hi;
     }
-    // (judged on the system of the last iteration: a poor guess can pair mostly ground and walls in the first ones)
-    const bool degenerate = !(ts->pivot_ratio >= tp.degenerate_bound);
-    // Gauss-Newton step: (J^T J) xi = -J^T r
+    return ratio;
+}
+
+// Gauss-Newton step: (J^T J) xi = -J^T r, T <- exp(xi) T, the step's norms into ts; false if A is not positive definite
+__device__ inline bool track_step(const double A[6][6], const double *b, TrackState *__restrict__ ts)
+{
     double L[6][6], d[6], xi[6], y[6];
-    if (!track_ldlt(A, L, d)) { fail(TRACK_DEGENERATE); return; }
+    if (!track_ldlt(A, L, d)) return false;
     for (int i = 0; i < 6; ++i) {
         double x = -b[i];
         for (int k = 0; k < i; ++k) x -= L[i][k] * y[k];
@@ -366,8 +370,41 @@ __global__ __launch_bounds__(256) void k_track_solve(TrackParams tp, const doubl
     for (int k = 0; k < 16; ++k) ts->T[k] = Tn[k];
     ts->step_rot = sqrt(xi[3] * xi[3] + xi[4] * xi[4] + xi[5] * xi[5]);
     ts->step_trans = sqrt(xi[0] * xi[0] + xi[1] * xi[1] + xi[2] * xi[2]);
+    return true;
+}
+
+__device__ inline void track_fail(TrackState *__restrict__ ts, int status)
+{
+    for (int e = 0; e < 16; ++e) ts->T[e] = ts->guess[e];
+    ts->status = status;
+    ts->done = 1;
+}
+
+// one workgroup.  sum_only: only the fixed-order sum into ts->sys (sm_track_debug)
+__global__ __launch_bounds__(256) void k_track_solve(TrackParams tp, const double *__restrict__ part, TrackState *__restrict__ ts,
+                                                     int sum_only)
+{
+    if (ts->done) return;
+    __shared__ double s_p[TRACK_NSYS][8];
+    double sys[TRACK_NSYS];
+    track_sum_parts(part, tp.nb, s_p, sys);
+    if (threadIdx.x != 0) return;
+    for (int e = 0; e < TRACK_NSYS; ++e) ts->sys[e] = sys[e];
+    if (sum_only) return;
+    const double cnt = sys[28];
+    ts->iterations += 1;
+    ts->inliers = (uint32_t)cnt;
+    ts->rmse = cnt > 0.0 ? sqrt(sys[27] / cnt) : 0.0;
+    if (ts->iterations == 1 && ts->in_view == 0u) { track_fail(ts, TRACK_NO_MODEL); return; }
+    if (cnt < (double)tp.min_inliers || cnt < 6.0) { track_fail(ts, TRACK_LOST); return; }
+    double A[6][6], b[6];
+    track_unpack(sys, A, b);
+    ts->pivot_ratio = track_pivot_ratio(A, tp.c);
+    // (judged on the system of the last iteration: a poor guess can pair mostly ground and walls in the first ones)
+    const bool degenerate = !(ts->pivot_ratio >= tp.degenerate_bound);
+    if (!track_step(A, b, ts)) { track_fail(ts, TRACK_DEGENERATE); return; }
     const bool converged = ts->step_rot < 1e-6 && ts->step_trans < 1e-6;
-    if ((converged || ts->iterations >= tp.max_iters) && degenerate) { fail(TRACK_DEGENERATE); return; }
+    if ((converged || ts->iterations >= tp.max_iters) && degenerate) { track_fail(ts, TRACK_DEGENERATE); return; }
     if (converged) ts->done = 1;
 }
 

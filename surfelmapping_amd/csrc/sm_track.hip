@@ -1,7 +1,8 @@
 // sm_track.hip -- camera tracking: projective frame-to-model point-to-plane ICP (sm_track_*; DESIGN.md "4d. Tracking").
-// Kernels: sm_k_track.h.
+// Kernels: sm_k_track.h; the colour term (sm_track_frame_rgb): sm_k_track_rgb.h.
 #include "sm_ctx.h"
 #include "sm_k_track.h"
+#include "sm_k_track_rgb.h"
 
 #include <cmath>
 
@@ -82,6 +83,18 @@ int track_check(sm_ctx *s, const char *fn)
 {
     if (s->ss_on) { g_err = std::string(fn) + ": a sharded context holds only its rank's surfels; tracking is not supported"; return SM_E_UNSUPPORTED; }
     if (s->pending_cull) { g_err = std::string(fn) + " between sm_stage_conflict and sm_stage_cull"; return SM_E_ARG; }
+    return SM_OK;
+}
+
+int track_params_check(const sm_ctx *s, const sm_track_params &p, const char *fn)
+{
+    if (p.max_iters < 1 || p.max_iters > SM_TRACK_MAX_ITERS || !(p.dist_thresh > 0.0f) || !std::isfinite(p.dist_thresh) ||
+        !(p.angle_thresh > 0.0f && p.angle_thresh <= 180.0f) || p.min_inliers < 0 || p.pixel_stride < 1 ||
+        p.pixel_stride > std::min(s->W, s->H)) {
+        g_err = std::string(fn) + ": parameter out of range (max_iters 1..100, dist_thresh > 0, angle_thresh in (0, 180], "
+                                  "min_inliers >= 0, pixel_stride 1..min(W, H))";
+        return SM_E_ARG;
+    }
     return SM_OK;
 }
 
@@ -167,6 +180,121 @@ int track_iteration(sm_ctx *s, const TrackParams &tp, int sum_only)
     s->trk.ev_iters++;
     return SM_OK;
 }
+
+// ---- the colour term ----
+
+enum { RGB_EV_PYRAMID = 2, RGB_EV_GATHER = 3, RGB_EV_VERTEX = 4, RGB_EV_ICP = 5, RGB_EV_PHOTO = 6, RGB_EV_SOLVE = 7 };
+
+int track_rgb_alloc(sm_ctx *s)
+{
+    if (s->trk.d_rstate) return SM_OK;
+    const size_t P = (size_t)s->P;
+    Dev<uint8_t> rgb; Dev<float> pyr; Dev<float4> plane; Dev<double> part; Dev<TrackRgbState> d;
+    Host<TrackRgbState> h;
+    int rc;
+    // (levels 1.. hold at most P / 3 pixels together)
+    if ((rc = dalloc(rgb, P * 3)) || (rc = dalloc(pyr, P + P / 3 + 1)) || (rc = dalloc(plane, P)) ||
+        (rc = dalloc(part, (size_t)TRACK_NSYS * TRACK_MAX_PARTS)) || (rc = dalloc(d, 1)))
+        return rc;
+    HIPCK(hipHostMalloc(h.put(), sizeof(TrackRgbState)));
+    s->trk.d_rgb = std::move(rgb); s->trk.d_pyr = std::move(pyr); s->trk.d_plane = std::move(plane);
+    s->trk.d_part_rgb = std::move(part); s->trk.h_rstate = std::move(h);
+    s->trk.d_rstate = std::move(d);             // last: it marks the set complete
+    return SM_OK;
+}
+
+// the event that closes an interval of kind `kind` at `level` (after track_prepare's events 0..2)
+int track_rgb_event(sm_ctx *s, int kind, int level)
+{
+    if (!s->trk.timed) return SM_OK;
+    s->trk.ev_kind.push_back(kind | (level << 4));
+    return track_event(s, 2 + s->trk.ev_kind.size());
+}
+
+const char *track_rgb_check(const sm_ctx *s, const sm_track_params &p, const sm_track_rgb_params &q)
+{
+    if (q.levels < 1 || q.levels > TRACK_RGB_LEVELS) return "levels outside 1..6";
+    long sum = 0;
+    for (int l = 0; l < q.levels; ++l) {
+        if (q.iters[l] < 1) return "iters[l] < 1 for a used level";
+        sum += q.iters[l];
+    }
+    if (sum > SM_TRACK_MAX_ITERS) return "the sum of iters exceeds SM_TRACK_MAX_ITERS";
+    if (!(q.rgb_weight >= 0.0f) || !std::isfinite(q.rgb_weight)) return "rgb_weight negative or not finite";
+    if (!(q.rgb_max_residual > 0.0f)) return "rgb_max_residual <= 0";
+    if ((s->W >> (q.levels - 1)) < 8 || (s->H >> (q.levels - 1)) < 8) return "the coarsest level is smaller than 8 x 8";
+    if ((long)p.pixel_stride << (q.levels - 1) > std::min(s->W, s->H)) return "pixel_stride * 2^(levels-1) exceeds min(W, H)";
+    return nullptr;
+}
+
+TrackRgbParams track_rgb_params(const sm_ctx *s, const sm_track_rgb_params &q)
+{
+    TrackRgbParams rp;
+    memset(&rp, 0, sizeof rp);
+    rp.levels = q.levels;
+    int off = 0;
+    for (int l = 0; l < TRACK_RGB_LEVELS; ++l) {
+        rp.iters[l] = q.iters[l];
+        rp.lw[l] = s->W >> l; rp.lh[l] = s->H >> l;
+        rp.off[l] = off;
+        off += rp.lw[l] * rp.lh[l];
+    }
+    rp.max_residual = q.rgb_max_residual;
+    rp.lambda = (double)q.rgb_weight;
+    return rp;
+}
+
+TrackParams track_level_params(const sm_ctx *s, sm_track_params p, int level)
+{
+    p.pixel_stride <<= level;
+    return track_params(s, p);
+}
+
+// sm_track_frame's preparation on the coarsest level's grid, then the pyramid and the gathered prediction (the rgb upload precedes event 0, as the depth's)
+int track_rgb_prepare(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const TrackParams &tpc, const TrackRgbParams &rp,
+                      const float *T0, const float *guess, bool ortho, int first_level)
+{
+    const size_t P = (size_t)s->P;
+    TrackRgbState &h = *s->trk.h_rstate;
+    memset(&h, 0, sizeof h);
+    h.level = first_level;
+    HIPCK(hipMemcpyAsync(s->trk.d_rstate, &h, sizeof h, hipMemcpyHostToDevice, s->stream));
+    HIPCK(hipMemcpyAsync(s->trk.d_rgb, rgb, P * 3, hipMemcpyHostToDevice, s->stream));
+    s->trk.ev_kind.clear();
+    int rc;
+    if ((rc = track_prepare(s, depth_mm, tpc, T0, guess, ortho))) return rc;
+    hipLaunchKernelGGL(k_track_luma_pyr, dim3((s->W + TRACK_RGB_TILE - 1) / TRACK_RGB_TILE, (s->H + TRACK_RGB_TILE - 1) / TRACK_RGB_TILE),
+                       dim3(256), 0, s->stream, s->trk.d_rgb, s->W, s->H, rp, s->trk.d_pyr);
+    if ((rc = track_rgb_event(s, RGB_EV_PYRAMID, 0))) return rc;
+    hipLaunchKernelGGL(k_track_gather, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s->stream, s->M, s->d_state, s->trk.d_pred,
+                       (int)P, s->trk.d_plane);
+    HIPCK(hipGetLastError());
+    return track_rgb_event(s, RGB_EV_GATHER, 0);
+}
+
+// the vertex stage of a level's grid (the coarsest level's is track_prepare's own)
+int track_rgb_level(sm_ctx *s, const TrackParams &tpl, int level)
+{
+    hipLaunchKernelGGL(k_track_vertex, dim3((tpl.n + 255) / 256), dim3(256), 0, s->stream, s->trk.d_depth, s->d_xs, s->d_ys, tpl,
+                       s->trk.d_v, s->trk.d_n);
+    HIPCK(hipGetLastError());
+    return track_rgb_event(s, RGB_EV_VERTEX, level);
+}
+
+int track_rgb_iteration(sm_ctx *s, const TrackParams &tpl, const TrackRgbParams &rp, int level, int sum_only)
+{
+    int rc;
+    hipLaunchKernelGGL(k_track_rgb_icp, dim3(tpl.nb), dim3(TRACK_BLOCK), 0, s->stream, s->M, s->d_state, tpl, level, s->trk.d_v,
+                       s->trk.d_n, s->trk.d_pred, s->trk.d_state, s->trk.d_rstate, s->trk.d_part);
+    if ((rc = track_rgb_event(s, RGB_EV_ICP, level))) return rc;
+    hipLaunchKernelGGL(k_track_rgb_photo, dim3(tpl.nb), dim3(TRACK_BLOCK), 0, s->stream, tpl, rp, level, s->trk.d_depth,
+                       s->trk.d_plane, s->trk.d_pyr, s->trk.d_state, s->trk.d_rstate, s->trk.d_part_rgb);
+    if ((rc = track_rgb_event(s, RGB_EV_PHOTO, level))) return rc;
+    hipLaunchKernelGGL(k_track_rgb_solve, dim3(1), dim3(256), 0, s->stream, tpl, rp, level, s->trk.d_part, s->trk.d_part_rgb,
+                       s->trk.d_state, s->trk.d_rstate, sum_only);
+    HIPCK(hipGetLastError());
+    return track_rgb_event(s, RGB_EV_SOLVE, level);
+}
 }  // namespace
 
 extern "C" {
@@ -189,15 +317,8 @@ int sm_track_frame(sm_ctx *s, const uint16_t *depth_mm, const float *guess16, co
     sm_track_params p;
     if (params) p = *params;
     else sm_default_track_params(&p);
-    if (p.max_iters < 1 || p.max_iters > SM_TRACK_MAX_ITERS || !(p.dist_thresh > 0.0f) || !std::isfinite(p.dist_thresh) ||
-        !(p.angle_thresh > 0.0f && p.angle_thresh <= 180.0f) || p.min_inliers < 0 || p.pixel_stride < 1 ||
-        p.pixel_stride > std::min(s->W, s->H)) {
-        g_err = "sm_track_frame: parameter out of range (max_iters 1..100, dist_thresh > 0, angle_thresh in (0, 180], "
-                "min_inliers >= 0, pixel_stride 1..min(W, H))";
-        return SM_E_ARG;
-    }
-    int rc = track_check(s, "sm_track_frame");
-    if (rc) return rc;
+    int rc;
+    if ((rc = track_params_check(s, p, "sm_track_frame")) || (rc = track_check(s, "sm_track_frame"))) return rc;
     HIPCK(hipSetDevice(s->cfg.device));
     if ((rc = pull_state(s))) return rc;                      // waits for frames in flight: the model after the last frame
     float g[16];
@@ -263,6 +384,131 @@ int sm_debug_track_stats(sm_ctx *s, float *ms, int cap, int *n)
     const int total = 2 + 2 * s->trk.ev_iters;
     for (int i = 0; i < total && i < cap; ++i) {
         HIPCK(hipEventElapsedTime(&ms[i], s->trk.ev[i], s->trk.ev[i + 1]));
+        *n = i + 1;
+    }
+    return SM_OK;
+}
+
+int sm_default_track_rgb_params(sm_track_rgb_params *p)
+{
+    if (!p) return SM_E_ARG;
+    static const int32_t iters[TRACK_RGB_LEVELS] = {10, 5, 4, 4, 4, 4};
+    p->levels = 3;
+    memcpy(p->iters, iters, sizeof iters);
+    p->rgb_weight = 0.01f;
+    p->rgb_max_residual = 0.25f;
+    return SM_OK;
+}
+
+int sm_track_frame_rgb(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params,
+                       const sm_track_rgb_params *rgb_params, float *pose16_out, sm_track_info *info, sm_track_rgb_info *rgb_info)
+{
+    if (!s || !rgb || !depth_mm || !pose16_out) { g_err = "sm_track_frame_rgb: null argument"; return SM_E_ARG; }
+    sm_track_params p;
+    if (params) p = *params;
+    else sm_default_track_params(&p);
+    sm_track_rgb_params q;
+    if (rgb_params) q = *rgb_params;
+    else sm_default_track_rgb_params(&q);
+    int rc;
+    // (max_iters is sm_track_frame's: checked as there; the level schedule is iters[])
+    if ((rc = track_params_check(s, p, "sm_track_frame_rgb"))) return rc;
+    if (const char *why = track_rgb_check(s, p, q)) { g_err = std::string("sm_track_frame_rgb: ") + why; return SM_E_ARG; }
+    if ((rc = track_check(s, "sm_track_frame_rgb"))) return rc;
+    HIPCK(hipSetDevice(s->cfg.device));
+    if ((rc = pull_state(s))) return rc;                      // waits for frames in flight: the model after the last frame
+    float g[16];
+    if (guess16) memcpy(g, guess16, 64);
+    else track_guess(s, g);
+    sm_track_info inf;
+    sm_track_rgb_info rinf;
+    memset(&inf, 0, sizeof inf);
+    memset(&rinf, 0, sizeof rinf);
+    memcpy(inf.guess, g, 64);
+    const uint32_t live = s->h_state->count - s->h_state->garbage;
+    if (s->trk.n_hist == 0 || live == 0) {
+        inf.status = SM_TRACK_NO_MODEL;
+        memcpy(pose16_out, g, 64);
+        if (info) *info = inf;
+        if (rgb_info) *rgb_info = rinf;
+        return SM_OK;
+    }
+    if ((rc = track_alloc(s)) || (rc = track_rgb_alloc(s))) return rc;
+    const TrackRgbParams rp = track_rgb_params(s, q);
+    // (the preparation's vertex stage is the coarsest level's; the prediction does not depend on the stride)
+    const TrackParams tpc = track_level_params(s, p, q.levels - 1);
+    if ((rc = track_rgb_prepare(s, rgb, depth_mm, tpc, rp, g, g, true, q.levels - 1))) return rc;
+    for (int l = q.levels - 1; l >= 0; --l) {
+        const TrackParams tpl = track_level_params(s, p, l);
+        if (l < q.levels - 1 && (rc = track_rgb_level(s, tpl, l))) return rc;
+        for (int it = 0; it < q.iters[l]; ++it)
+            if ((rc = track_rgb_iteration(s, tpl, rp, l, 0))) return rc;
+    }
+    HIPCK(hipMemcpyAsync(s->trk.h_state, s->trk.d_state, sizeof(TrackState), hipMemcpyDeviceToHost, s->stream));
+    HIPCK(hipMemcpyAsync(s->trk.h_rstate, s->trk.d_rstate, sizeof(TrackRgbState), hipMemcpyDeviceToHost, s->stream));
+    HIPCK(hipStreamSynchronize(s->stream));                   // the one wait of a tracked frame
+    const TrackState &h = *s->trk.h_state;
+    const TrackRgbState &hr = *s->trk.h_rstate;
+    for (int e = 0; e < 16; ++e) pose16_out[e] = (float)h.T[e];
+    inf.status = h.status;
+    inf.iterations = h.iterations;
+    inf.inliers = h.inliers;
+    inf.rmse = (float)h.rmse;
+    rinf.rgb_inliers = hr.rgb_inliers;
+    rinf.rgb_rmse = (float)hr.rgb_rmse;
+    rinf.pivot_ratio = h.pivot_ratio;
+    for (int l = 0; l < TRACK_RGB_LEVELS; ++l) rinf.level_iterations[l] = hr.level_iterations[l];
+    if (info) *info = inf;
+    if (rgb_info) *rgb_info = rinf;
+    return SM_OK;
+}
+
+int sm_track_rgb_debug(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *pose16_eval, int level, int which,
+                       double *sys29)
+{
+    if (!s || !rgb || !depth_mm || !pose16_eval) { g_err = "sm_track_rgb_debug: null argument"; return SM_E_ARG; }
+    sm_track_params p;
+    sm_default_track_params(&p);
+    sm_track_rgb_params q;
+    sm_default_track_rgb_params(&q);
+    q.levels = level + 1;                                     // (the pyramid up to that level; its size is checked below)
+    if (level < 0 || level >= TRACK_RGB_LEVELS || which < 0 || which > 2) {
+        g_err = "sm_track_rgb_debug: level outside 0..5 or which outside 0..2";
+        return SM_E_ARG;
+    }
+    if (const char *why = track_rgb_check(s, p, q)) { g_err = std::string("sm_track_rgb_debug: ") + why; return SM_E_ARG; }
+    int rc = track_check(s, "sm_track_rgb_debug");
+    if (rc) return rc;
+    HIPCK(hipSetDevice(s->cfg.device));
+    if ((rc = pull_state(s))) return rc;
+    if ((rc = track_alloc(s)) || (rc = track_rgb_alloc(s))) return rc;
+    const TrackRgbParams rp = track_rgb_params(s, q);
+    const TrackParams tpl = track_level_params(s, p, level);
+    if ((rc = track_rgb_prepare(s, rgb, depth_mm, tpl, rp, pose16_eval, pose16_eval, false, level))) return rc;   // (the pose as given)
+    if ((rc = track_rgb_iteration(s, tpl, rp, level, 1))) return rc;
+    HIPCK(hipMemcpyAsync(s->trk.h_state, s->trk.d_state, sizeof(TrackState), hipMemcpyDeviceToHost, s->stream));
+    HIPCK(hipMemcpyAsync(s->trk.h_rstate, s->trk.d_rstate, sizeof(TrackRgbState), hipMemcpyDeviceToHost, s->stream));
+    HIPCK(hipStreamSynchronize(s->stream));
+    const double *src = which == 0 ? s->trk.h_state->sys : which == 1 ? s->trk.h_rstate->sys_icp : s->trk.h_rstate->sys_rgb;
+    if (sys29) memcpy(sys29, src, TRACK_NSYS * sizeof(double));
+    return SM_OK;
+}
+
+// Diagnostic, deliberately not part of include/sm_c_api.h (tools/track_rgb_probe.py): device times of the last sm_track_frame_rgb /
+// sm_track_rgb_debug call made with SM_TRACK_TIMING=1, in ms, with what each covers: kind[i] & 15 = 0 prediction, 1 vertex stage of
+// the coarsest level, 2 luminance pyramid, 3 gather, 4 a finer level's vertex stage, 5 geometric reduction, 6 photometric reduction,
+// 7 solve (5..7 are no-ops once their level has ended); kind[i] >> 4 = the level.  *n = values written (0 if not timed).
+int sm_debug_track_rgb_stats(sm_ctx *s, float *ms, int *kind, int cap, int *n)
+{
+    if (!s || !ms || !kind || !n) return SM_E_ARG;
+    HIPCK(hipSetDevice(s->cfg.device));
+    HIPCK(hipStreamSynchronize(s->stream));
+    *n = 0;
+    if (!s->trk.timed || s->trk.ev_kind.empty()) return SM_OK;
+    const int total = 2 + (int)s->trk.ev_kind.size();
+    for (int i = 0; i < total && i < cap; ++i) {
+        HIPCK(hipEventElapsedTime(&ms[i], s->trk.ev[i], s->trk.ev[i + 1]));
+        kind[i] = i < 2 ? i : s->trk.ev_kind[i - 2];
         *n = i + 1;
     }
     return SM_OK;

@@ -1,0 +1,165 @@
+"""numpy restatement of the tracker's colour term (sm_track_frame_rgb, surfelmapping_amd/csrc/sm_k_track_rgb.h) -- the checker of
+tests/test_track_rgb.py.  As in tests/track_ref.py, every float32 step is one IEEE float32 operation of the kernels, in their
+order, so the sample sets are equal sample for sample; the 29 sums are float32 terms added in float64 (in another order than the
+GPU's: equal to rounding).  `track` restates the level schedule and the solve of k_track_rgb_solve in float64."""
+import numpy as np
+
+import track_ref as tr
+
+f32 = np.float32
+MAX_LEVELS = 6
+DEFAULT_ITERS = (10, 5, 4, 4, 4, 4)
+
+
+def luminance(r, g, b):
+    """Y = ((0.299 R + 0.587 G) + 0.114 B) / 255 of 8-bit channels (track_luma)"""
+    r, g, b = (np.asarray(x).astype(f32) for x in (r, g, b))
+    return ((f32(0.299) * r + f32(0.587) * g) + f32(0.114) * b) / f32(255.0)
+
+
+def colour_luminance(word):
+    """luminance of colour words sem<<24 | r<<16 | g<<8 | b (uint32)"""
+    w = np.asarray(word, np.uint32)
+    return luminance((w >> 16) & 0xFF, (w >> 8) & 0xFF, w & 0xFF)
+
+
+def half(img):
+    """the next pyramid level: mean ((a + b) + (c + d)) * 0.25 of each 2x2 block, floor(w/2) x floor(h/2)"""
+    h, w = img.shape[0] // 2, img.shape[1] // 2
+    a, b = img[0:2 * h:2, 0:2 * w:2], img[0:2 * h:2, 1:2 * w:2]
+    c, d = img[1:2 * h:2, 0:2 * w:2], img[1:2 * h:2, 1:2 * w:2]
+    return (((a + b) + (c + d)) * f32(0.25)).astype(f32)
+
+
+def pyramid(rgb, levels):
+    """k_track_luma_pyr: [level 0 luminance float32[H][W], level 1, ...]"""
+    rgb = np.asarray(rgb, np.uint8)
+    out = [luminance(rgb[..., 0], rgb[..., 1], rgb[..., 2])]
+    for _ in range(1, levels):
+        out.append(half(out[-1]))
+    return out
+
+
+def gather(pred, model):
+    """k_track_gather: float32[H][W][4] (surfel centre, luminance of its colour word; w = -1: no surfel)"""
+    m = np.asarray(model, f32)
+    ok = pred >= 0
+    row = m[np.where(ok, pred, 0)]
+    out = np.zeros(pred.shape + (4,), f32)
+    out[..., :3] = row[..., :3]
+    out[..., 3] = colour_luminance(np.ascontiguousarray(row[..., 4]).view(np.uint32))
+    out[~ok] = (0, 0, 0, -1)
+    return out
+
+
+def bilinear(img, u, v):
+    """the bilinear interpolant of img at texel coordinates (u, v) (texel k at k) and its derivative per texel:
+    (value, d/du, d/dv, inside) -- inside iff the four texels exist"""
+    lh, lw = img.shape
+    with np.errstate(all="ignore"):
+        fu, fv = np.floor(u), np.floor(v)
+        ok = (fu >= 0) & (fu < f32(lw - 1)) & (fv >= 0) & (fv < f32(lh - 1))
+        iu, iv = np.where(ok, fu, 0).astype(np.int64), np.where(ok, fv, 0).astype(np.int64)
+        a, b = (u - fu).astype(f32), (v - fv).astype(f32)
+        i00, i10, i01, i11 = img[iv, iu], img[iv, iu + 1], img[iv + 1, iu], img[iv + 1, iu + 1]
+        d0, d1 = i10 - i00, i11 - i01
+        top, bot = i00 + a * d0, i01 + a * d1
+        dv = bot - top
+        return top + b * dv, d0 + b * (d1 - d0), dv, ok
+
+
+def photo_terms(plane, depth_mm, img, pose16, cam, level=0, stride=1, dist=0.3, max_residual=0.25, near=1.0, far=30.0,
+                stereo_border=80.0):
+    """track_rgb_sample on the grid of `stride` (the caller passes pixel_stride * 2^level): (J float32[n][6], r float32[n],
+    kept bool[n]) over the grid's pixels, row-major"""
+    W, H = cam["width"], cam["height"]
+    m = tr.colmajor(pose16)
+    z = tr.metric_depth(depth_mm, near, far, stereo_border)
+    pl = plane[0:H:stride, 0:W:stride].reshape(-1, 4)
+    p = [pl[:, k] for k in range(3)]
+    ym = pl[:, 3]
+    fx, fy, cx0, cy0 = f32(cam["fx"]), f32(cam["fy"]), f32(cam["cx"]), f32(cam["cy"])
+    inv_s = f32(1.0) / f32(1 << level)
+    with np.errstate(all="ignore"):
+        d = [p[0] - m[12], p[1] - m[13], p[2] - m[14]]
+        c = [(m[4 * k] * d[0] + m[4 * k + 1] * d[1]) + m[4 * k + 2] * d[2] for k in range(3)]
+        ok = (ym >= 0) & (c[2] > 0)
+        x = (fx * c[0]) / c[2] + cx0
+        y = (fy * c[1]) / c[2] + cy0
+        ok &= (x >= 0) & (x < f32(W)) & (y >= 0) & (y < f32(H))
+        D = z[np.where(ok, y, 0).astype(np.int64), np.where(ok, x, 0).astype(np.int64)]
+        ok &= (D != 0) & (np.abs(D - c[2]) <= f32(dist))
+        u, v = x * inv_s - f32(0.5), y * inv_s - f32(0.5)
+        val, du, dv, inside = bilinear(img, u, v)
+        ok &= inside
+        r = val - ym
+        ok &= np.abs(r) < f32(max_residual)
+        gx, gy = du * inv_s, dv * inv_s
+        ga, gb = (gx * fx) / c[2], (gy * fy) / c[2]
+        gc = -((ga * c[0] + gb * c[1]) / c[2])
+        gw = tr._rot(m, ga, gb, gc)
+        pg = tr._cross(p, gw)
+    J = np.stack([-gw[0], -gw[1], -gw[2], -pg[0], -pg[1], -pg[2]], axis=1).astype(f32)
+    return J, r.astype(f32), ok
+
+
+def photo_system(plane, depth_mm, img, pose16, cam, **kw):
+    """k_track_rgb_photo + its fixed-order sum: float64[29], unweighted"""
+    J, r, ok = photo_terms(plane, depth_mm, img, pose16, cam, **kw)
+    J, r = J[ok], r[ok]
+    out = np.zeros(tr.NSYS)
+    e = 0
+    for a in range(6):
+        for b in range(a, 6):
+            out[e] = (J[:, a] * J[:, b]).astype(np.float64).sum()
+            e += 1
+    for a in range(6):
+        out[21 + a] = (J[:, a] * r).astype(np.float64).sum()
+    out[27] = (r * r).astype(np.float64).sum()
+    out[28] = float(ok.sum())
+    return out
+
+
+def joint(sys_icp, sys_rgb, weight):
+    """k_track_rgb_solve's system: values 0..27 icp + weight * rgb, value 28 the geometric inliers"""
+    out = np.asarray(sys_icp, np.float64) + float(f32(weight)) * np.asarray(sys_rgb, np.float64)
+    out[28] = sys_icp[28]
+    return out
+
+
+def track(rgb, depth_mm, model, t_prev16, guess, cam, levels=3, iters=DEFAULT_ITERS, rgb_weight=0.01, rgb_max_residual=0.25,
+          dist=0.3, angle_deg=30.0, pixel_stride=1, min_inliers=1000, bound=1e-4, stereo_border=80.0):
+    """sm_track_frame_rgb from `guess` (4x4) against `model` (AoS, row = slot) predicted at t_prev16: returns (pose 4x4 float64,
+    info) with info = status, iterations, level_iterations, pivot_ratio (joint, last system), pivot_ratio_icp (geometric term
+    of that system alone), inliers, rgb_inliers"""
+    pred = tr.predict(model, t_prev16, cam)
+    plane = gather(pred, model)
+    pyr = pyramid(rgb, levels)
+    centre = np.asarray(t_prev16, np.float64).reshape(-1)[12:15]
+    T = np.asarray(guess, np.float64).copy()
+    info = dict(status="OK", iterations=0, level_iterations=[0] * MAX_LEVELS, pivot_ratio=0.0, pivot_ratio_icp=0.0, inliers=0,
+                rgb_inliers=0)
+    for level in range(levels - 1, -1, -1):
+        stride = pixel_stride << level
+        vm, nm = tr.vertex_normal(depth_mm, cam, stereo_border=stereo_border, stride=stride)
+        for _ in range(iters[level]):
+            pose = T.astype(f32)
+            si = tr.system(vm, nm, pred, model, pose, t_prev16, cam, dist=dist, angle_deg=angle_deg)
+            sr = photo_system(plane, depth_mm, pyr[level], pose, cam, level=level, stride=stride, dist=dist,
+                              max_residual=rgb_max_residual, stereo_border=stereo_border)
+            sys = joint(si, sr, rgb_weight)
+            info["iterations"] += 1
+            info["level_iterations"][level] += 1
+            info["inliers"], info["rgb_inliers"] = int(si[28]), int(sr[28])
+            if si[28] * 4 ** level < min_inliers or si[28] < 6:
+                info["status"] = "LOST"
+                return np.asarray(guess, np.float64), info
+            info["pivot_ratio"] = tr.pivot_ratio(sys, centre)
+            info["pivot_ratio_icp"] = tr.pivot_ratio(si, centre)
+            T, xi = tr.solve(sys, T)
+            if np.linalg.norm(xi[3:]) < 1e-6 and np.linalg.norm(xi[:3]) < 1e-6:
+                break
+    if not info["pivot_ratio"] >= bound:
+        info["status"] = "DEGENERATE"
+        return np.asarray(guess, np.float64), info
+    return T, info

@@ -244,6 +244,58 @@ int sm_render_model(sm_ctx *s, const sm_model_view *v, uint8_t *rgba, float *dep
 /* the same into device memory (4-byte aligned), enqueued on the context's stream; returns without waiting for the render */
 int sm_render_model_device(sm_ctx *s, const sm_model_view *v, uint8_t *d_rgba, float *d_depth, int32_t *d_id);
 
+/* ---- views of a map set (DESIGN.md "4f. Views of a map set") ----
+ * A map set is a list of map files (GlobalModel::downloadMap's format: sm_save_map, the files of sm_set_auto_retire), drawn in
+ * the given order, optionally followed by the context's live model.  The two calls below draw it without loading it: the
+ * files are streamed through the device in chunks, so the set may be larger than the context, larger than device memory, and
+ * include what retirement has moved out of the model.
+ *   Global id.  A surfel's id is its position in the concatenation of the set: the files in order, each file's records in
+ *     file order, then the live model in sm_download_model_aos order.  The id planes carry it.
+ *   Output equality.  Per view, every output equals sm_render_image / sm_render_model of a context whose model is that
+ *     concatenation, bit for bit (whether or not such a context could exist) -- the clear colour, sem 0, depth 1.0 and id -1 of
+ *     an empty pixel included; a depth tie goes to the lower id, so to the source that comes first.  The result depends
+ *     neither on the chunking nor on how many views are drawn per pass over the files.
+ *   Size limit.  A set of more than 2^31 - 1 surfels: SM_E_CAPACITY, before anything is drawn.
+ *   Degenerate sets.  n_paths == 0 with include_model == 1 equals the existing entry point; an empty set gives the cleared images.
+ *   Side effects.  The model, the counters, the tick, the frame log and the tracker state are untouched; the forced compaction
+ *     that every read-back does is the only side effect, as in sm_render_model.  Frames in flight are waited for.
+ *   Files.  The headers of ALL files are read and checked before anything else is done: the record count against the file's
+ *     length (12 + 48 * count bytes exactly), the total against the size limit.  A file that is missing, shorter or longer
+ *     than its header says: SM_E_ARG, sm_last_error() names it, and the outputs are not written.  That guarantee is
+ *     the header check's: a file that shrinks or disappears after it (between the check and a later pass) also gives
+ *     SM_E_ARG, but views of earlier passes may already have been written; treat the outputs as undefined then.  Every file
+ *     is read once per pass; a pass draws as many views as fit the key budget (1 GiB of 8-byte keys; SM_RENDER_MAPS_KEY_MB overrides it).
+ *   Other errors.  SM_E_UNSUPPORTED in a sharded context.  SM_E_ARG: a NULL ctx or source, a call between sm_stage_conflict and
+ *     sm_stage_cull, NULL paths with n_paths > 0, NULL views or outputs (bgr_out, sem_out; rgba) with n_views > 0, a view
+ *     sm_render_image / sm_render_model would refuse, views of different width x height.  n_views == 0 checks the set and
+ *     draws nothing.
+ * SM_RENDER_MAPS_NO_CULL=1 turns the per-block view test off (an A/B switch: the images are the same either way). */
+typedef struct sm_map_source {
+    const char *const *paths; uint32_t n_paths;  /* GlobalModel::downloadMap files, drawn in this order */
+    int32_t include_model;                        /* 1: the live model follows the files */
+} sm_map_source;
+
+/* what the last sm_render_image_maps / sm_render_model_maps call of the context did */
+typedef struct sm_maps_stats {
+    uint64_t surfels_read;        /* records read from the files, all passes together */
+    uint32_t chunks, passes;      /* chunks (at most 2^20 records) copied to the device; passes over the files */
+    uint64_t pairs_tested;        /* (block of 256 records, view) pairs the view test ran on (0 with SM_RENDER_MAPS_NO_CULL=1) */
+    uint64_t pairs_skipped;       /* ... of them, found outside the view and not drawn */
+    float read_ms, copy_ms;       /* in fread; in the host-to-device copies (events) */
+    float device_ms;              /* in the kernels (events around each chunk's and the live model's) */
+    float total_ms;               /* the whole call (host clock) */
+} sm_maps_stats;   /* (not named after the call: a typedef and a function share C's name space) */
+
+/* sm_render_image of a map set from n_views camera->world poses (16 floats each): bgr_out n_views*h*w*3, sem_out n_views*h*w */
+int sm_render_image_maps(sm_ctx *s, const sm_map_source *src, const float *views16, uint32_t n_views, int w, int h, float fx,
+                         float fy, float cx, float cy, uint8_t *bgr_out, uint8_t *sem_out);
+/* sm_render_model of a map set from n_views views of one width x height: rgba n_views*w*h*4; depth and id (n_views*w*h each)
+ * are optional (NULL) */
+int sm_render_model_maps(sm_ctx *s, const sm_map_source *src, const sm_model_view *views, uint32_t n_views, uint8_t *rgba,
+                         float *depth, int32_t *id);
+/* SM_E_ARG if the context has made no such call yet */
+int sm_render_maps_stats(sm_ctx *s, sm_maps_stats *out);
+
 /* ---- camera tracking (DESIGN.md "4d. Tracking") ----
  * The reference documents processFrame's gtPose as optional ("if provided, we don't attempt to perform tracking",
  * src/SurfelMapping.h:31-34) but has no tracker.  This one is projective frame-to-model point-to-plane ICP against the map:

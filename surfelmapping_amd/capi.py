@@ -24,7 +24,7 @@ SYMBOLS = (
     "sm_inputs_consumed", "sm_host_alloc", "sm_host_alloc_frame", "sm_host_free", "sm_debug_slow_frames", "sm_sync", "sm_clean_points", "sm_clean_points_ex", "sm_clean_points_cb", "sm_reset",
     "sm_get_counts", "sm_download_model_aos", "sm_upload_model_aos", "sm_save_map", "sm_load_map",
     "sm_download_index_map", "sm_download_raw_cloud", "sm_download_depth", "sm_render_image", "sm_render_model",
-    "sm_render_model_device", "sm_set_frame", "sm_set_tick",
+    "sm_render_model_device", "sm_render_image_maps", "sm_render_model_maps", "sm_render_maps_stats", "sm_set_frame", "sm_set_tick",
     "sm_stage_conflict", "sm_stage_cull", "sm_stage_splat", "sm_stage_associate_fuse",
     "sm_stage_timings", "sm_read_frame_log", "sm_device_alloc", "sm_device_free", "sm_device_upload",
     "sm_export_model_device", "sm_append_model_aos_device", "sm_device_download",
@@ -92,6 +92,25 @@ class SmModelView(C.Structure):
         ("draw_unstable", C.c_int32), ("draw_points", C.c_int32), ("draw_window", C.c_int32), ("time", C.c_int32),
         ("time_delta", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("clear_rgba", C.c_uint8 * 4),
     ]
+
+
+class SmMapSource(C.Structure):
+    _fields_ = [("paths", C.POINTER(C.c_char_p)), ("n_paths", C.c_uint32), ("include_model", C.c_int32)]
+
+
+class SmMapsStats(C.Structure):
+    _fields_ = [("surfels_read", C.c_uint64), ("chunks", C.c_uint32), ("passes", C.c_uint32), ("pairs_tested", C.c_uint64),
+                ("pairs_skipped", C.c_uint64), ("read_ms", C.c_float), ("copy_ms", C.c_float), ("device_ms", C.c_float),
+                ("total_ms", C.c_float)]
+
+
+def map_source(paths, include_model=True) -> SmMapSource:
+    """a map set: the files in drawing order, then (include_model) the live model; keeps the path strings alive"""
+    enc = [os.fsencode(p) for p in paths]
+    arr = (C.c_char_p * max(len(enc), 1))(*enc)
+    src = SmMapSource(C.cast(arr, C.POINTER(C.c_char_p)), len(enc), int(bool(include_model)))
+    src._keep = (enc, arr)
+    return src
 
 
 SM_TRACK_OK, SM_TRACK_LOST, SM_TRACK_DEGENERATE, SM_TRACK_NO_MODEL = 0, 1, 2, 3
@@ -290,6 +309,9 @@ def load():
     L.sm_render_image.argtypes = [vp, vp, C.c_int, C.c_int] + [C.c_float] * 4 + [vp, vp]
     L.sm_render_model.argtypes = [vp, C.POINTER(SmModelView), vp, vp, vp]
     L.sm_render_model_device.argtypes = [vp, C.POINTER(SmModelView), vp, vp, vp]
+    L.sm_render_image_maps.argtypes = [vp, C.POINTER(SmMapSource), vp, C.c_uint32, C.c_int, C.c_int] + [C.c_float] * 4 + [vp, vp]
+    L.sm_render_model_maps.argtypes = [vp, C.POINTER(SmMapSource), C.POINTER(SmModelView), C.c_uint32, vp, vp, vp]
+    L.sm_render_maps_stats.argtypes = [vp, C.POINTER(SmMapsStats)]
     L.sm_set_frame.argtypes = [vp, vp, vp, vp]
     L.sm_set_tick.argtypes = [vp, C.c_int32]
     L.sm_stage_conflict.argtypes = [vp, vp, C.c_float, C.c_float, C.c_float, C.c_int]
@@ -699,6 +721,46 @@ class SurfelMap:
         n, ms = C.c_uint32(), (C.c_float * 3)()
         self._chk(f(self._h, C.byref(n), ms), "sm_debug_render_model_stats")
         return int(n.value), (None if ms[0] < 0 else [float(x) for x in ms])
+
+    # -- views of a map set (sm_render_image_maps, sm_render_model_maps)
+    def render_image_maps(self, paths, views, w, h, fx, fy, cx, cy, include_model=True):
+        """Novel views of a map set -- the map files `paths` in that order, then (include_model) the live model -- streamed
+        through the device without loading it: every view equals render_image() of a model that is their concatenation.
+        views: float32[V][16] camera->world poses (column-major, as render_image takes them).  Returns (bgr uint8[V][h][w][3],
+        semantic uint8[V][h][w]).  One call reads every file once per batch of views (render_maps_stats()['passes'])."""
+        views = np.ascontiguousarray(views, np.float32).reshape(-1, 16)
+        V = views.shape[0]
+        bgr = np.zeros((V, h, w, 3), np.uint8)
+        sem = np.zeros((V, h, w), np.uint8)
+        src = map_source(paths, include_model)
+        self._chk(self._L.sm_render_image_maps(self._h, C.byref(src), _ptr(views), V, w, h, fx, fy, cx, cy, _ptr(bgr), _ptr(sem)),
+                  "sm_render_image_maps")
+        return bgr, sem
+
+    def render_model_maps(self, paths, views, include_model=True, depth=False, ids=False):
+        """Model views of a map set (see render_image_maps): `views` is a list of model_view(...) structs -- the arguments of
+        render_model per view -- or of dicts of those arguments; all of one width x height.  Returns rgba uint8[V][h][w][4] in
+        GL row order and, if asked, depth float32[V][h][w] and ids int32[V][h][w] (position in the concatenation, -1 = empty):
+        rgba, or a tuple (rgba, depth?, ids?)."""
+        vs = [v if isinstance(v, SmModelView) else model_view(**v) for v in views]
+        V = len(vs)
+        arr = (SmModelView * max(V, 1))(*vs)
+        w, h = (vs[0].width, vs[0].height) if V else (1, 1)
+        rgba = np.zeros((V, h, w, 4), np.uint8)
+        d = np.zeros((V, h, w), np.float32) if depth else None
+        i = np.zeros((V, h, w), np.int32) if ids else None
+        src = map_source(paths, include_model)
+        self._chk(self._L.sm_render_model_maps(self._h, C.byref(src), arr, V, _ptr(rgba), _ptr(d), _ptr(i)), "sm_render_model_maps")
+        if not depth and not ids:
+            return rgba
+        return (rgba,) + ((d,) if depth else ()) + ((i,) if ids else ())
+
+    def render_maps_stats(self) -> dict:
+        """of the last render_*_maps call: surfels_read, chunks, passes, pairs_tested, pairs_skipped ((block of 256 records,
+        view) pairs the view test ran on / found outside), read_ms, copy_ms, device_ms, total_ms"""
+        st = SmMapsStats()
+        self._chk(self._L.sm_render_maps_stats(self._h, C.byref(st)), "sm_render_maps_stats")
+        return {k: getattr(st, k) for k, _ in SmMapsStats._fields_}
 
     # -- per-pass entry points
     def set_frame(self, rgb=None, depth_metric=None, sem=None):

@@ -151,21 +151,30 @@ public:
                           const float clear[4])
     {
         sm_model_view v{};
-        double inv[16];
-        invert4d(mv.m, inv);                                             // mv.Inverse() in double, as pangolin computes it
-        for (int i = 0; i < 16; ++i) { v.mvp[i] = (float)mvp.m[i]; v.mv_inv[i] = (float)inv[i]; }
-        v.threshold = threshold;
-        v.color_type = drawNormals ? 1 : drawColors ? 2 : drawSemantic ? 3 : 0;    // src/GlobalModel.cpp:702
-        v.draw_unstable = drawUnstable; v.draw_points = drawPoints; v.draw_window = drawWindow;
-        v.time = time; v.time_delta = timeDelta;
-        v.width = w; v.height = h;
-        for (int c = 0; c < 4; ++c) {
-            const float x = clear ? clear[c] : 0.0f;
-            v.clear_rgba[c] = (uint8_t)std::floor((x < 0.0f ? 0.0f : x > 1.0f ? 1.0f : x) * 255.0f + 0.5f);
-        }
+        fillModelView(v, mvp, mv, threshold, drawUnstable, drawNormals, drawColors, drawPoints, drawWindow, drawSemantic, time, timeDelta, w, h, clear);
         modelImage_.resize((size_t)(w > 0 ? w : 0) * (size_t)(h > 0 ? h : 0) * 4);
         (void)sm_sync(ctx_);                                             // (SM_FACADE_ASYNC: frames may still be in flight)
         if (sm_render_model(ctx_, &v, modelImage_.data(), nullptr, nullptr) != SM_OK) {
+            std::printf("renderModelImage: %s\n", sm_last_error());
+            return false;
+        }
+        return true;
+    }
+    // The same view of a map set: the map files `mapFiles` (downloadMap's format, the files of SurfelMapping::setAutoRetire) in
+    // that order, then -- includeModel -- the live model, streamed through the core without loading them
+    // (sm_render_model_maps): the image equals renderModelImage of a model that is their concatenation.
+    bool renderModelImage(pangolin::OpenGlMatrix mvp, pangolin::OpenGlMatrix mv, float threshold, bool drawUnstable, bool drawNormals,
+                          bool drawColors, bool drawPoints, bool drawWindow, bool drawSemantic, int time, int timeDelta, int w, int h,
+                          const float clear[4], const std::vector<std::string> &mapFiles, bool includeModel = true)
+    {
+        sm_model_view v{};
+        fillModelView(v, mvp, mv, threshold, drawUnstable, drawNormals, drawColors, drawPoints, drawWindow, drawSemantic, time, timeDelta, w, h, clear);
+        modelImage_.resize((size_t)(w > 0 ? w : 0) * (size_t)(h > 0 ? h : 0) * 4);
+        std::vector<const char *> paths;
+        for (const std::string &f : mapFiles) paths.push_back(f.c_str());
+        const sm_map_source src{paths.data(), (uint32_t)paths.size(), includeModel ? 1 : 0};
+        (void)sm_sync(ctx_);                                             // (SM_FACADE_ASYNC: frames may still be in flight)
+        if (sm_render_model_maps(ctx_, &src, &v, 1, modelImage_.data(), nullptr, nullptr) != SM_OK) {
             std::printf("renderModelImage: %s\n", sm_last_error());
             return false;
         }
@@ -182,6 +191,24 @@ public:
     const std::vector<float> &mirrorHost(int which) const { return mirror_[which]; }      // 0 VC, 1 CT, 2 NR: count x 4 floats
 
 private:
+    // renderModel's arguments plus a viewport as the core takes them
+    static void fillModelView(sm_model_view &v, const pangolin::OpenGlMatrix &mvp, const pangolin::OpenGlMatrix &mv, float threshold,
+                              bool drawUnstable, bool drawNormals, bool drawColors, bool drawPoints, bool drawWindow, bool drawSemantic,
+                              int time, int timeDelta, int w, int h, const float clear[4])
+    {
+        double inv[16];
+        invert4d(mv.m, inv);                                             // mv.Inverse() in double, as pangolin computes it
+        for (int i = 0; i < 16; ++i) { v.mvp[i] = (float)mvp.m[i]; v.mv_inv[i] = (float)inv[i]; }
+        v.threshold = threshold;
+        v.color_type = drawNormals ? 1 : drawColors ? 2 : drawSemantic ? 3 : 0;    // src/GlobalModel.cpp:702
+        v.draw_unstable = drawUnstable; v.draw_points = drawPoints; v.draw_window = drawWindow;
+        v.time = time; v.time_delta = timeDelta;
+        v.width = w; v.height = h;
+        for (int c = 0; c < 4; ++c) {
+            const float x = clear ? clear[c] : 0.0f;
+            v.clear_rgba[c] = (uint8_t)std::floor((x < 0.0f ? 0.0f : x > 1.0f ? 1.0f : x) * 255.0f + 0.5f);
+        }
+    }
     // general 4x4 inverse by cofactors (column-major, double)
     static void invert4d(const double *m, double *o)
     {

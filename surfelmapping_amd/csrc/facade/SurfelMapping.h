@@ -3,6 +3,7 @@
 #pragma once
 #include <cassert>
 #include <cstdio>
+#include <cstring>
 #include <map>
 #include <stdexcept>
 #include <string>
@@ -189,6 +190,43 @@ public:
             if (!(r1 && r2)) std::printf("%s is NOT saved!\n", name);
             startId++;
         }
+    }
+
+    // The same dump of a map set: the map files `mapFiles` (downloadMap's format, the files of setAutoRetire) in that order,
+    // then -- includeModel -- the live model.  One streamed call draws all views (sm_render_image_maps: every file is read once
+    // per batch of views, nothing is loaded into the model); the pictures and their names are those of the overload above for a
+    // model that is the concatenation of the set.
+    bool acquireImages(std::string path, const std::vector<std::string> &mapFiles, const std::vector<Eigen::Matrix4f> &views, int w,
+                       int h, float fx, float fy, float cx, float cy, int startId = 0, bool includeModel = true)
+    {
+        if (path.empty() || path.back() != '/') path += "/";
+        const std::string image_path = path + "image/", semantic_path = path + "semantic/";
+        ::mkdir(image_path.c_str(), 0755);
+        ::mkdir(semantic_path.c_str(), 0755);
+        if (w <= 0 || h <= 0) return false;
+        const size_t npix = (size_t)w * h;
+        std::vector<float> v16(views.size() * 16);
+        for (size_t i = 0; i < views.size(); ++i) std::memcpy(&v16[i * 16], views[i].data(), 64);
+        std::vector<const char *> paths;
+        for (const std::string &f : mapFiles) paths.push_back(f.c_str());
+        const sm_map_source src{paths.data(), (uint32_t)paths.size(), includeModel ? 1 : 0};
+        std::vector<unsigned char> bgr(views.size() * npix * 3), sem(views.size() * npix), rgb(npix * 3);
+        (void)sm_sync(ctx_);                                             // (SM_FACADE_ASYNC: frames may still be in flight)
+        if (sm_render_image_maps(ctx_, &src, v16.data(), (uint32_t)views.size(), w, h, fx, fy, cx, cy, bgr.data(), sem.data()) != SM_OK) {
+            std::printf("acquireImages: %s\n", sm_last_error());
+            return false;
+        }
+        bool ok = true;
+        for (size_t i = 0; i < views.size(); ++i, ++startId) {
+            char name[32];
+            std::snprintf(name, sizeof name, "%06d.png", startId);
+            const unsigned char *b = &bgr[i * npix * 3];
+            for (size_t p = 0; p < npix; ++p) { rgb[p * 3] = b[p * 3 + 2]; rgb[p * 3 + 1] = b[p * 3 + 1]; rgb[p * 3 + 2] = b[p * 3]; }
+            const bool r1 = sm_png::write((image_path + name).c_str(), rgb.data(), w, h, 3);
+            const bool r2 = sm_png::write((semantic_path + name).c_str(), &sem[i * npix], w, h, 1);
+            if (!(r1 && r2)) { std::printf("%s is NOT saved!\n", name); ok = false; }
+        }
+        return ok;
     }
 
     // extras of the HIP core

@@ -9,6 +9,7 @@
 //   sm_rccl.hip      the RCCL binding (sm_shard_rccl_*)
 //   sm_rig.hip       rig consolidation (sm_rig_*)
 //   sm_retire.hip    retirement (sm_retire*, sm_set_auto_retire)
+//   sm_render_maps.hip  views of a map set (sm_render_*_maps): map files streamed through the renderers
 #pragma once
 
 #include "../../include/sm_c_api.h"
@@ -26,7 +27,7 @@
 #include <utility>
 #include <vector>
 
-namespace sm { struct TrackState; struct TrackRgbState; }
+namespace sm { struct TrackState; struct TrackRgbState; struct RenderParams; struct ViewParams; struct ViewShade; }
 
 // Hidden: libsurfelmapping_hip.so exports the C ABI and the kernels' host stubs, nothing of this namespace.  Its functions are
 // defined qualified (sm_impl::name) so that the definitions keep the visibility.
@@ -142,6 +143,27 @@ struct Retire {
     int32_t last_tick = 0;             // tick at the last retirement that wrote a file (the next file's startId)
     bool timed = false, stats_valid = false;   // SM_RETIRE_TIMING=1: events around every step of the last call
     Event ev[8];
+};
+
+// views of a map set (sm_render_maps.hip, sm_k_render_maps.h): the staging of the file stream, allocated by the first call, and
+// the last call's tally.  Chunk c of a pass goes through buffer c & 1: fread into h_rec, copied on `copy` into d_rec, unpacked
+// into the one set of SoA planes by the intake kernel on the context's stream.
+struct RenderMaps {
+    static constexpr uint32_t CHUNK = 1u << 20;          // records per chunk (48 MiB), the chunk sm_retire writes files in
+    Stream copy;                       // first: what follows is used on it
+    Host<float4> h_rec[2];             // pinned
+    Dev<float4> d_rec[2];
+    Event ev_copy0[2], ev_copied[2];   // on `copy`: around the chunk's copy
+    Event ev_free[2];                  // on the context's stream: the intake has read d_rec
+    Event ev_k0[2], ev_k1[2];          // ... around the chunk's kernels
+    bool in_flight[2] = {false, false};   // the buffer's events have been recorded and not yet folded into the tally
+    Dev<float4> d_pos_conf, d_norm_rad, d_box;
+    Dev<uint32_t> d_color;
+    Dev<float> d_time;
+    Dev<uint8_t> d_par;                // per-view parameters | shading | skipped counters | hit flags
+    size_t par_bytes = 0;
+    sm_maps_stats stats{};
+    bool stats_valid = false;
 };
 
 // The SM_* switches of the frame pipeline (sm_api.hip), read once by sm_create (read_switches): nothing on the per-frame path
@@ -348,6 +370,7 @@ struct sm_ctx {
     ModelView rm;
     Tracker trk;
     Retire ret;
+    RenderMaps maps;
     // host frame state (src/SurfelMapping.h:100-103)
     int tick = 0;
     bool ref_set = false;
@@ -388,6 +411,17 @@ int clean_points_device(sm_ctx *s, const uint16_t *d_depth_mm, const uint8_t *d_
 int ss_collective(sm_ctx *s, const void *send, void *recv, size_t count, int op);
 // ---- sm_model_io.hip ----
 void export_aos(sm_ctx *s, float *dst12, uint32_t first, uint32_t n);   // k_export_aos on the context's stream
+// the novel view's splat of the live model into `key` with ids id_base + slot (k_render_splat on the context's stream)
+void render_splat_model(sm_ctx *s, const RenderParams &rp, uint64_t *key, uint32_t id_base);
+// ---- sm_view.hip ----
+// a model view's rules that need no context (SM_E_ARG with g_err set), and its kernel arguments
+int check_model_view(const sm_model_view *v, const char *fn);
+void model_view_params(const sm_model_view *v, ViewParams &vp, ViewShade &vs);
+// the model view's splat (+ overflow) of the live model into `key` with ids id_base + slot, on the context's stream;
+// d_ovf_n: 4 bytes, d_ovf: 4 bytes per live surfel.  `timing` (optional): three events recorded before the splat, between
+// the two kernels and after the overflow (SM_RENDER_MODEL_TIMING).
+int view_splat_model(sm_ctx *s, const ViewParams &vp, uint64_t *key, uint32_t *d_ovf_n, uint32_t *d_ovf, uint32_t id_base,
+                     const Event *timing = nullptr);
 // ---- sm_retire.hip ----
 int auto_retire_after_frame(sm_ctx *s);           // the periodic policy: called once a frame is enqueued (one test unless it is due)
 

@@ -11,6 +11,12 @@ void sm_impl::export_aos(sm_ctx *s, float *dst12, uint32_t first, uint32_t n)
     hipLaunchKernelGGL(k_export_aos, dim3((n + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, dst12, first, n);
 }
 
+void sm_impl::render_splat_model(sm_ctx *s, const RenderParams &rp, uint64_t *key, uint32_t id_base)
+{
+    const uint32_t cnt = s->h_state->count;
+    if (cnt) hipLaunchKernelGGL(k_render_splat, dim3((cnt + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, rp, key, id_base);
+}
+
 extern "C" {
 
 int sm_download_model_aos(sm_ctx *s, float *dst12, uint32_t cap, uint32_t *n)
@@ -189,8 +195,7 @@ int sm_render_image(sm_ctx *s, const float *view16, int w, int h, float fx, floa
     invert4(view16, rp.t_inv);
     rp.fx = fx; rp.fy = fy; rp.cx = cx; rp.cy = cy; rp.cols = (float)w; rp.rows = (float)h; rp.w = w; rp.h = h;
     fill_keys(s, d_key, npix);
-    const uint32_t cnt = s->h_state->count;
-    if (cnt) hipLaunchKernelGGL(k_render_splat, dim3((cnt + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, rp, d_key);
+    render_splat_model(s, rp, d_key, 0u);
     hipLaunchKernelGGL(k_render_resolve, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s->stream, s->M, s->d_state, d_key,
                        (int)npix, d_bgr, d_sem);
     HIPCK(hipGetLastError());

@@ -1,0 +1,316 @@
+// sm_render_maps.hip -- views of a map set (sm_render_image_maps, sm_render_model_maps; DESIGN.md "4f. Views of a map set"):
+// map files streamed through the two renderers in chunks, the live model last.  Kernels: sm_k_render_maps.h.
+#include "sm_ctx.h"
+#include "sm_k_render_maps.h"
+
+#include <chrono>
+#include <sys/stat.h>
+
+using namespace sm;
+
+namespace {
+
+struct MapFile { const char *path; uint32_t n; };
+struct FileCloser { void operator()(FILE *f) const { if (f) fclose(f); } };
+using File = std::unique_ptr<FILE, FileCloser>;
+
+double now_ms()
+{
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// the headers of all files: u32 count | i32 startId | i32 endId | count * 48 bytes (src/GlobalModel.cpp:927-932)
+int scan_files(const sm_map_source *src, const char *fn, std::vector<MapFile> &files, uint64_t &total)
+{
+    for (uint32_t i = 0; i < src->n_paths; ++i) {
+        const char *path = src->paths[i];
+        if (!path) { g_err = std::string(fn) + ": null path"; return SM_E_ARG; }
+        File f(fopen(path, "rb"));
+        if (!f) { g_err = std::string(fn) + ": " + path + " is not open!"; return SM_E_ARG; }
+        uint32_t hdr[3];
+        struct stat st;
+        if (fread(hdr, 4, 3, f.get()) != 3 || fstat(fileno(f.get()), &st) != 0) {
+            g_err = std::string(fn) + ": " + path + " read err!! (no header)"; return SM_E_ARG;
+        }
+        const uint64_t want = 12ull + 48ull * hdr[0];
+        if ((uint64_t)st.st_size != want) {
+            g_err = std::string(fn) + ": " + path + " holds " + std::to_string((uint64_t)st.st_size) + " bytes, its header's " +
+                    std::to_string(hdr[0]) + " records need " + std::to_string(want);
+            return SM_E_ARG;
+        }
+        files.push_back({path, hdr[0]});
+        total += hdr[0];
+    }
+    return SM_OK;
+}
+
+// what differs between the two renderers
+struct Mode {
+    bool image;
+    int w, h;
+    uint32_t n_views;
+    const void *params; size_t param_size;               // RenderParams / ViewParams per view
+    const ViewShade *shade;                              // model view only
+    // host outputs, per view npix * 3 | npix (image) or npix * 4 each (view: depth and id may be null)
+    uint8_t *out0; uint8_t *out1; uint8_t *out2;
+};
+
+int ensure_staging(sm_ctx *s)
+{
+    RenderMaps &rm = s->maps;
+    if (rm.copy) return SM_OK;
+    Stream copy;
+    HIPCK(hipStreamCreateWithFlags(copy.put(), hipStreamNonBlocking));
+    const size_t N = RenderMaps::CHUNK;
+    for (int b = 0; b < 2; ++b) {
+        HIPCK(hipHostMalloc((void **)rm.h_rec[b].put(), N * 48, hipHostMallocDefault));
+        HIPCK(hipMalloc(rm.d_rec[b].put(), N * 48));
+        for (Event *e : {&rm.ev_copy0[b], &rm.ev_copied[b], &rm.ev_free[b], &rm.ev_k0[b], &rm.ev_k1[b]}) HIPCK(hipEventCreate(e->put()));
+    }
+    int rc;
+    if ((rc = dalloc(rm.d_pos_conf, N)) || (rc = dalloc(rm.d_norm_rad, N)) || (rc = dalloc(rm.d_color, N)) || (rc = dalloc(rm.d_time, N)) ||
+        (rc = dalloc(rm.d_box, 2 * (N / MAPS_BLOCK))))
+        return rc;
+    rm.copy = std::move(copy);                           // last: the staging is whole or absent
+    return SM_OK;
+}
+
+// fold the finished events of buffer b into the tally (waits for them)
+int fold_events(sm_ctx *s, int b)
+{
+    RenderMaps &rm = s->maps;
+    if (!rm.in_flight[b]) return SM_OK;
+    float ms = 0.0f;
+    HIPCK(hipEventSynchronize(rm.ev_k1[b]));
+    HIPCK(hipEventElapsedTime(&ms, rm.ev_copy0[b], rm.ev_copied[b]));
+    rm.stats.copy_ms += ms;
+    HIPCK(hipEventElapsedTime(&ms, rm.ev_k0[b], rm.ev_k1[b]));
+    rm.stats.device_ms += ms;
+    rm.in_flight[b] = false;
+    return SM_OK;
+}
+
+int render_maps(sm_ctx *s, const sm_map_source *src, const char *fn, const Mode &md)
+{
+    const double t_begin = now_ms();
+    if (s->ss_on) { g_err = std::string(fn) + ": a sharded context holds only its rank's surfels; rendering the union is not supported"; return SM_E_UNSUPPORTED; }
+    if (s->pending_cull) { g_err = std::string(fn) + " between sm_stage_conflict and sm_stage_cull"; return SM_E_ARG; }
+    if (src->n_paths && !src->paths) { g_err = std::string(fn) + ": null paths"; return SM_E_ARG; }
+    std::vector<MapFile> files;
+    uint64_t total = 0;
+    int rc = scan_files(src, fn, files, total);
+    if (rc) return rc;
+    HIPCK(hipSetDevice(s->cfg.device));
+    if ((rc = ensure_compact(s))) return rc;
+    if ((rc = pull_state(s))) return rc;                          // (waits for frames in flight; count is the live surfels)
+    const uint32_t cnt = src->include_model ? s->h_state->count : 0u;
+    const uint64_t file_total = total;
+    total += cnt;
+    if (total > 0x7FFFFFFFull) { g_err = std::string(fn) + ": the map set holds " + std::to_string(total) + " surfels, ids end at 2^31 - 1"; return SM_E_CAPACITY; }
+    RenderMaps &rm = s->maps;
+    rm.stats = sm_maps_stats{};
+    rm.stats_valid = true;
+    if (md.n_views == 0) { rm.stats.total_ms = (float)(now_ms() - t_begin); return SM_OK; }
+    if (file_total && (rc = ensure_staging(s))) return rc;
+
+    const char *e = std::getenv("SM_RENDER_MAPS_NO_CULL");
+    const int cull = (e && e[0] == '1') ? 0 : 1;
+    size_t key_mb = 1024;
+    if (const char *k = std::getenv("SM_RENDER_MAPS_KEY_MB")) key_mb = (size_t)std::min(8192L, std::max(1L, std::atol(k)));   // (at most 2^30 keys per batch)
+    const size_t npix = (size_t)md.w * md.h;
+    const uint32_t B = (uint32_t)std::min<uint64_t>(std::min<uint32_t>(md.n_views, 4096u), std::max<uint64_t>(1, (key_mb << 20) / (npix * 8)));
+    const unsigned pblocks = (unsigned)((npix + 255) / 256);
+
+    // per-view parameters | shading | skipped counters | hit flags
+    const size_t V = md.n_views;
+    const size_t off_shade = (V * md.param_size + 15) & ~(size_t)15, off_skip = off_shade + V * sizeof(ViewShade), off_hit = off_skip + V * 4,
+                 par_bytes = off_hit + V;
+    if (par_bytes > rm.par_bytes) {
+        rm.par_bytes = 0;
+        HIPCK(hipMalloc((void **)rm.d_par.put(), par_bytes));
+        rm.par_bytes = par_bytes;
+    }
+    uint8_t *d_par = rm.d_par;
+    uint32_t *d_skip = (uint32_t *)(d_par + off_skip);
+    uint8_t *d_hit = d_par + off_hit;
+    HIPCK(hipMemcpyAsync(d_par, md.params, V * md.param_size, hipMemcpyHostToDevice, s->stream));
+    if (!md.image) HIPCK(hipMemcpyAsync(d_par + off_shade, md.shade, V * sizeof(ViewShade), hipMemcpyHostToDevice, s->stream));
+    HIPCK(hipMemsetAsync(d_skip, 0, V * 4, s->stream));
+
+    // export scratch: keys | output planes of one batch | (model view + live model) overflow length and list
+    const size_t out_px = md.image ? 4 : 12;
+    const size_t off_out = (size_t)B * npix * 8, off_ovf = off_out + (((size_t)B * npix * out_px + 255) & ~(size_t)255);
+    if ((rc = ensure_export(s, off_ovf + ((!md.image && cnt) ? 256 + (size_t)cnt * 4 : 0)))) return rc;
+    uint8_t *base = (uint8_t *)s->d_export.get();
+    uint64_t *d_key = (uint64_t *)base;
+    uint8_t *d_out = base + off_out;
+    uint32_t *d_ovf_n = (uint32_t *)(base + off_ovf), *d_ovf = (uint32_t *)(base + off_ovf + 256);
+
+    const MapsSoA chunk{rm.d_pos_conf, rm.d_norm_rad, rm.d_color, rm.d_time};
+    const SurfelSet cur = s->M.s[s->h_state->cur];
+    const MapsSoA live{cur.pos_conf, cur.norm_rad, cur.color, cur.time};
+
+    for (uint32_t v0 = 0; v0 < md.n_views; v0 += B) {
+        const uint32_t b = std::min(B, md.n_views - v0);
+        const size_t bp = (size_t)b * npix;
+        rm.stats.passes++;
+        // this batch's planes
+        uint8_t *d_bgr = d_out, *d_sem = d_out + bp * 3;
+        uint32_t *d_rgba = (uint32_t *)d_out;
+        float *d_depth = (float *)(d_out + bp * 4);
+        int32_t *d_id = (int32_t *)(d_out + bp * 8);
+        const RenderParams *d_rp = (const RenderParams *)d_par + v0;
+        const ViewParams *d_vp = (const ViewParams *)d_par + v0;
+        const ViewShade *d_vs = (const ViewShade *)(d_par + off_shade) + v0;
+        auto resolve = [&](const MapsSoA &from, uint32_t id_base, uint32_t n) {
+            if (md.image)
+                hipLaunchKernelGGL(k_maps_resolve_image, dim3(pblocks, b), dim3(256), 0, s->stream, from, id_base, n, d_key, npix, d_hit + v0, d_bgr, d_sem);
+            else
+                hipLaunchKernelGGL(k_maps_resolve_view, dim3(pblocks, b), dim3(256), 0, s->stream, from, id_base, n, d_vs, d_key, npix, d_hit + v0,
+                                   d_rgba, d_depth, d_id);
+        };
+        fill_keys(s, d_key, bp);
+
+        // ---- the files, chunk by chunk: the host reads chunk c + 1 while the copy and the kernels of chunk c run
+        uint32_t c = 0;                                  // chunk index within the pass
+        uint64_t id_base = 0;
+        for (const MapFile &mf : files) {
+            if (!mf.n) continue;
+            File f(fopen(mf.path, "rb"));
+            if (!f || fseek(f.get(), 12, SEEK_SET) != 0) { (void)hipDeviceSynchronize(); g_err = std::string(fn) + ": " + mf.path + " is not open!"; return SM_E_ARG; }
+            for (uint32_t first = 0; first < mf.n; first += RenderMaps::CHUNK, ++c) {
+                const uint32_t n = std::min(RenderMaps::CHUNK, mf.n - first);
+                const int q = (int)(c & 1u);
+                if ((rc = fold_events(s, q))) return rc;              // (the copy out of h_rec[q] two chunks ago is over as well)
+                const double t0 = now_ms();
+                const size_t got = fread(rm.h_rec[q].get(), 48, n, f.get());
+                rm.stats.read_ms += (float)(now_ms() - t0);
+                if (got != n) { (void)hipDeviceSynchronize(); g_err = std::string(fn) + ": " + mf.path + " read err!!"; return SM_E_ARG; }
+                HIPCK(hipStreamWaitEvent(rm.copy, rm.ev_free[q], 0));     // (never recorded: no wait)
+                HIPCK(hipEventRecord(rm.ev_copy0[q], rm.copy));
+                HIPCK(hipMemcpyAsync(rm.d_rec[q], rm.h_rec[q], (size_t)n * 48, hipMemcpyHostToDevice, rm.copy));
+                HIPCK(hipEventRecord(rm.ev_copied[q], rm.copy));
+                HIPCK(hipStreamWaitEvent(s->stream, rm.ev_copied[q], 0));
+                HIPCK(hipEventRecord(rm.ev_k0[q], s->stream));
+                const unsigned nblk = (n + MAPS_BLOCK - 1) / MAPS_BLOCK;
+                hipLaunchKernelGGL(k_maps_intake, dim3(nblk), dim3(256), 0, s->stream, (const float4 *)rm.d_rec[q].get(), n, chunk, rm.d_box.get());
+                HIPCK(hipEventRecord(rm.ev_free[q], s->stream));
+                HIPCK(hipMemsetAsync(d_hit + v0, 0, b, s->stream));
+                const uint32_t gid = (uint32_t)(id_base + first);
+                if (md.image)
+                    hipLaunchKernelGGL(k_maps_splat_image, dim3(nblk, b), dim3(256), 0, s->stream, chunk, n, gid, (const float4 *)rm.d_box.get(), d_rp,
+                                       d_key, npix, cull, d_skip + v0, d_hit + v0);
+                else
+                    hipLaunchKernelGGL(k_maps_splat_view, dim3(nblk, b), dim3(256), 0, s->stream, chunk, n, gid, (const float4 *)rm.d_box.get(), d_vp,
+                                       d_key, npix, cull, d_skip + v0, d_hit + v0);
+                resolve(chunk, gid, n);
+                HIPCK(hipEventRecord(rm.ev_k1[q], s->stream));
+                HIPCK(hipGetLastError());
+                rm.in_flight[q] = true;
+                rm.stats.surfels_read += n;
+                rm.stats.chunks++;
+                if (cull) rm.stats.pairs_tested += (uint64_t)nblk * b;
+            }
+            id_base += mf.n;
+        }
+        if ((rc = fold_events(s, 0)) || (rc = fold_events(s, 1))) return rc;
+
+        // ---- the live model, by the resident kernels with an id base
+        if (cnt) {
+            Event &k0 = rm.ev_k0[0], &k1 = rm.ev_k1[0];          // (free: both buffers have been folded)
+            if (!k0) { HIPCK(hipEventCreate(k0.put())); HIPCK(hipEventCreate(k1.put())); }
+            HIPCK(hipEventRecord(k0, s->stream));
+            for (uint32_t i = 0; i < b; ++i) {
+                uint64_t *kv = d_key + (size_t)i * npix;
+                if (md.image) render_splat_model(s, ((const RenderParams *)md.params)[v0 + i], kv, (uint32_t)file_total);
+                else if ((rc = view_splat_model(s, ((const ViewParams *)md.params)[v0 + i], kv, d_ovf_n, d_ovf, (uint32_t)file_total))) return rc;
+            }
+            HIPCK(hipMemsetAsync(d_hit + v0, 1, b, s->stream));
+            resolve(live, (uint32_t)file_total, cnt);
+            HIPCK(hipEventRecord(k1, s->stream));
+            HIPCK(hipGetLastError());
+            float ms = 0.0f;
+            HIPCK(hipEventSynchronize(k1));
+            HIPCK(hipEventElapsedTime(&ms, k0, k1));
+            rm.stats.device_ms += ms;
+        }
+
+        // ---- pixels nobody won, then the batch's planes to the caller
+        if (md.image) hipLaunchKernelGGL(k_maps_finish_image, dim3((unsigned)((bp + 255) / 256)), dim3(256), 0, s->stream, d_key, bp, d_bgr, d_sem);
+        else hipLaunchKernelGGL(k_maps_finish_view, dim3(pblocks, b), dim3(256), 0, s->stream, d_vs, d_key, npix, d_rgba, d_depth, d_id);
+        HIPCK(hipGetLastError());
+        const size_t vp0 = (size_t)v0 * npix;
+        if (md.image) {
+            HIPCK(hipMemcpyAsync(md.out0 + vp0 * 3, d_bgr, bp * 3, hipMemcpyDeviceToHost, s->stream));
+            HIPCK(hipMemcpyAsync(md.out1 + vp0, d_sem, bp, hipMemcpyDeviceToHost, s->stream));
+        } else {
+            HIPCK(hipMemcpyAsync(md.out0 + vp0 * 4, d_rgba, bp * 4, hipMemcpyDeviceToHost, s->stream));
+            if (md.out1) HIPCK(hipMemcpyAsync(md.out1 + vp0 * 4, d_depth, bp * 4, hipMemcpyDeviceToHost, s->stream));
+            if (md.out2) HIPCK(hipMemcpyAsync(md.out2 + vp0 * 4, d_id, bp * 4, hipMemcpyDeviceToHost, s->stream));
+        }
+        HIPCK(hipStreamSynchronize(s->stream));
+    }
+    std::vector<uint32_t> skipped(V);
+    HIPCK(hipMemcpy(skipped.data(), d_skip, V * 4, hipMemcpyDeviceToHost));
+    for (uint32_t x : skipped) rm.stats.pairs_skipped += x;
+    rm.stats.total_ms = (float)(now_ms() - t_begin);
+    return SM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sm_render_image_maps(sm_ctx *s, const sm_map_source *src, const float *views16, uint32_t n_views, int w, int h, float fx, float fy,
+                         float cx, float cy, uint8_t *bgr_out, uint8_t *sem_out)
+{
+    const char *fn = "sm_render_image_maps";
+    if (!s || !src) { g_err = std::string(fn) + ": null context or source"; return SM_E_ARG; }
+    if (n_views && (!views16 || !bgr_out || !sem_out)) { g_err = std::string(fn) + ": null views or outputs"; return SM_E_ARG; }
+    if (w <= 0 || h <= 0 || (uint64_t)w * h > (1u << 28)) { g_err = std::string(fn) + ": width and height must be positive, w*h at most 2^28"; return SM_E_ARG; }
+    std::vector<RenderParams> rps(n_views);
+    for (uint32_t i = 0; i < n_views; ++i) {
+        RenderParams &rp = rps[i];
+        invert4(views16 + (size_t)i * 16, rp.t_inv);
+        rp.fx = fx; rp.fy = fy; rp.cx = cx; rp.cy = cy; rp.cols = (float)w; rp.rows = (float)h; rp.w = w; rp.h = h;
+    }
+    Mode md{};
+    md.image = true; md.w = w; md.h = h; md.n_views = n_views;
+    md.params = rps.data(); md.param_size = sizeof(RenderParams);
+    md.out0 = bgr_out; md.out1 = sem_out;
+    return render_maps(s, src, fn, md);
+}
+
+int sm_render_model_maps(sm_ctx *s, const sm_map_source *src, const sm_model_view *views, uint32_t n_views, uint8_t *rgba, float *depth,
+                         int32_t *id)
+{
+    const char *fn = "sm_render_model_maps";
+    if (!s || !src) { g_err = std::string(fn) + ": null context or source"; return SM_E_ARG; }
+    if (n_views && (!views || !rgba)) { g_err = std::string(fn) + ": null views or rgba"; return SM_E_ARG; }
+    std::vector<ViewParams> vps(n_views);
+    std::vector<ViewShade> vss(n_views);
+    for (uint32_t i = 0; i < n_views; ++i) {
+        if (int rc = check_model_view(&views[i], fn)) return rc;
+        if (views[i].width != views[0].width || views[i].height != views[0].height) {
+            g_err = std::string(fn) + ": all views of a call have one width x height"; return SM_E_ARG;
+        }
+        model_view_params(&views[i], vps[i], vss[i]);
+    }
+    Mode md{};
+    md.image = false; md.n_views = n_views;
+    md.w = n_views ? views[0].width : 1; md.h = n_views ? views[0].height : 1;
+    md.params = vps.data(); md.param_size = sizeof(ViewParams);
+    md.shade = vss.data();
+    md.out0 = rgba; md.out1 = (uint8_t *)depth; md.out2 = (uint8_t *)id;
+    return render_maps(s, src, fn, md);
+}
+
+int sm_render_maps_stats(sm_ctx *s, sm_maps_stats *out)
+{
+    if (!s || !out) return SM_E_ARG;
+    if (!s->maps.stats_valid) { g_err = "sm_render_maps_stats: no sm_render_image_maps / sm_render_model_maps call yet"; return SM_E_ARG; }
+    *out = s->maps.stats;
+    return SM_OK;
+}
+
+}  // extern "C"

@@ -5,6 +5,47 @@
 
 using namespace sm;
 
+int sm_impl::check_model_view(const sm_model_view *v, const char *fn)
+{
+    if (!v) { g_err = std::string(fn) + ": null view"; return SM_E_ARG; }
+    if (v->width <= 0 || v->height <= 0 || (uint64_t)v->width * (uint64_t)v->height > (1u << 28)) {
+        g_err = std::string(fn) + ": width and height must be positive, w*h at most 2^28"; return SM_E_ARG;
+    }
+    if (v->color_type < 0 || v->color_type > 3) { g_err = std::string(fn) + ": color_type is 0..3"; return SM_E_ARG; }
+    return SM_OK;
+}
+
+void sm_impl::model_view_params(const sm_model_view *v, ViewParams &vp, ViewShade &vs)
+{
+    memcpy(vp.mvp, v->mvp, 64);
+    memcpy(vp.mvinv, v->mv_inv, 64);
+    vp.threshold = v->threshold;
+    vp.unstable = v->draw_unstable ? 1 : 0;
+    vp.points = v->draw_points ? 1 : 0;
+    vp.w = v->width; vp.h = v->height;
+    vp.fp_lane = 64;                                              // tuning constant: DESIGN.md "Model view" has the sweep
+    if (const char *e = std::getenv("SM_RENDER_MODEL_LANE_PX")) vp.fp_lane = (uint32_t)std::max(0, std::atoi(e));
+    vs.color_type = v->color_type;
+    vs.window = (v->draw_window && !v->draw_points) ? 1 : 0;      // draw_feedback.vert has no window
+    vs.time = v->time; vs.time_delta = v->time_delta;
+    vs.clear = (uint32_t)v->clear_rgba[0] | ((uint32_t)v->clear_rgba[1] << 8) | ((uint32_t)v->clear_rgba[2] << 16) |
+               ((uint32_t)v->clear_rgba[3] << 24);
+}
+
+int sm_impl::view_splat_model(sm_ctx *s, const ViewParams &vp, uint64_t *key, uint32_t *d_ovf_n, uint32_t *d_ovf, uint32_t id_base,
+                              const Event *timing)
+{
+    const uint32_t cnt = s->h_state->count;
+    HIPCK(hipMemsetAsync(d_ovf_n, 0, 4, s->stream));
+    if (timing) HIPCK(hipEventRecord(timing[0], s->stream));
+    if (cnt) hipLaunchKernelGGL(k_view_splat, dim3((cnt + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, vp, key, d_ovf_n, d_ovf, id_base);
+    if (timing) HIPCK(hipEventRecord(timing[1], s->stream));
+    if (cnt && !vp.points)
+        hipLaunchKernelGGL(k_view_overflow, dim3(VIEW_OVF_BLOCKS), dim3(256), 0, s->stream, s->M, s->d_state, vp, key, d_ovf_n, d_ovf, id_base);
+    if (timing) HIPCK(hipEventRecord(timing[2], s->stream));
+    return SM_OK;
+}
+
 namespace {
 // GlobalModel::renderModel (src/GlobalModel.cpp:683-758) into device memory (sm_k_view.h): keys [8 w h] | overflow length
 // [256] | overflow list [4 count] in the export scratch; with `stage` (the host path) the images follow there too -- rgba,
@@ -14,11 +55,7 @@ int render_model_enqueue(sm_ctx *s, const sm_model_view *v, const char *fn, uint
                          int32_t *d_id)
 {
     // (the view is checked before the context, so that each rule can be exercised without a device)
-    if (!v) { g_err = std::string(fn) + ": null view"; return SM_E_ARG; }
-    if (v->width <= 0 || v->height <= 0 || (uint64_t)v->width * (uint64_t)v->height > (1u << 28)) {
-        g_err = std::string(fn) + ": width and height must be positive, w*h at most 2^28"; return SM_E_ARG;
-    }
-    if (v->color_type < 0 || v->color_type > 3) { g_err = std::string(fn) + ": color_type is 0..3"; return SM_E_ARG; }
+    if (int rc = check_model_view(v, fn)) return rc;
     if (!d_rgba && !stage) { g_err = std::string(fn) + ": null rgba"; return SM_E_ARG; }
     if (!s) { g_err = std::string(fn) + ": null context"; return SM_E_ARG; }
     if (!stage && (((uintptr_t)d_rgba | (uintptr_t)d_depth | (uintptr_t)d_id) & 3u)) {
@@ -44,20 +81,8 @@ int render_model_enqueue(sm_ctx *s, const sm_model_view *v, const char *fn, uint
         if (d_id) d_id = (int32_t *)(*stage + npix * 8);
     }
     ViewParams vp;
-    memcpy(vp.mvp, v->mvp, 64);
-    memcpy(vp.mvinv, v->mv_inv, 64);
-    vp.threshold = v->threshold;
-    vp.unstable = v->draw_unstable ? 1 : 0;
-    vp.points = v->draw_points ? 1 : 0;
-    vp.w = v->width; vp.h = v->height;
-    vp.fp_lane = 64;                                              // tuning constant: DESIGN.md "Model view" has the sweep
-    if (const char *e = std::getenv("SM_RENDER_MODEL_LANE_PX")) vp.fp_lane = (uint32_t)std::max(0, std::atoi(e));
     ViewShade vs;
-    vs.color_type = v->color_type;
-    vs.window = (v->draw_window && !v->draw_points) ? 1 : 0;      // draw_feedback.vert has no window
-    vs.time = v->time; vs.time_delta = v->time_delta;
-    vs.clear = (uint32_t)v->clear_rgba[0] | ((uint32_t)v->clear_rgba[1] << 8) | ((uint32_t)v->clear_rgba[2] << 16) |
-               ((uint32_t)v->clear_rgba[3] << 24);
+    model_view_params(v, vp, vs);
     const char *te = std::getenv("SM_RENDER_MODEL_TIMING");
     s->rm.timed = te && te[0] == '1';
     if (s->rm.timed && !s->rm.ev[0]) {
@@ -67,13 +92,7 @@ int render_model_enqueue(sm_ctx *s, const sm_model_view *v, const char *fn, uint
     }
     const unsigned pblocks = (unsigned)((npix + 255) / 256);
     fill_keys(s, d_key, npix);
-    HIPCK(hipMemsetAsync(d_ovf_n, 0, 4, s->stream));
-    if (s->rm.timed) HIPCK(hipEventRecord(s->rm.ev[0], s->stream));
-    if (cnt) hipLaunchKernelGGL(k_view_splat, dim3((cnt + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, vp, d_key, d_ovf_n, d_ovf);
-    if (s->rm.timed) HIPCK(hipEventRecord(s->rm.ev[1], s->stream));
-    if (cnt && !vp.points)
-        hipLaunchKernelGGL(k_view_overflow, dim3(VIEW_OVF_BLOCKS), dim3(256), 0, s->stream, s->M, s->d_state, vp, d_key, d_ovf_n, d_ovf);
-    if (s->rm.timed) HIPCK(hipEventRecord(s->rm.ev[2], s->stream));
+    if ((rc = view_splat_model(s, vp, d_key, d_ovf_n, d_ovf, 0u, s->rm.timed ? s->rm.ev : nullptr))) return rc;
     hipLaunchKernelGGL(k_view_resolve, dim3(pblocks), dim3(256), 0, s->stream, s->M, s->d_state, vs, d_key, (int)npix,
                        (uint32_t *)d_rgba, d_depth, d_id);
     if (s->rm.timed) HIPCK(hipEventRecord(s->rm.ev[3], s->stream));

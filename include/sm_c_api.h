@@ -450,6 +450,73 @@ int sm_retire_device(sm_ctx *s, const float *pose16, const sm_retire_params *par
 int sm_set_auto_retire(sm_ctx *s, const sm_retire_params *params, int32_t every, const char *path_prefix);
 int sm_auto_retire_stats(sm_ctx *s, uint32_t *files, uint64_t *surfels);     /* written so far */
 
+/* ---- paging in (DESIGN.md "4g. Paging in") ----
+ * The reverse of retirement: the records of map files (GlobalModel::downloadMap's format: the files of sm_set_auto_retire,
+ * sm_save_map) that lie within `radius` of the camera centre come back into the model, so that a camera that returns finds
+ * the surfels it left, and a second drive can localise and work inside a saved map set.
+ * With c = pose16[12..14] (camera->world, column-major; NULL = the pose of the last processed frame), row q of a file is near
+ * iff, in fp32 without fused multiply-add and in this order,
+ *     dx, dy, dz = q[0..2] - c[0..2];                   d2 = (dx*dx + dy*dy) + dz*dz
+ *     near = d2 <= radius*radius                        (the product rounded to fp32 once; a comparison with a NaN is false,
+ *                                                        an infinite d2 is not near)
+ * For finite rows and the same c and distance this is exactly the complement of sm_retire's `far`: a surfel retired because it
+ * is far is never recalled in the same round.  R = the concatenation of rows[near]: the files in the given order, each file's
+ * rows in file order.  m = the rows sm_download_model_aos would return (slots a deferred-compaction cull has killed are not
+ * among them, so nothing below depends on compact_period).
+ *   SM_RECALL_COUNT  *n = |R|; nothing changes, nothing is written anywhere.
+ *   SM_RECALL_COPY   the model becomes concat(m, R), bit for bit; the files are untouched.
+ *   SM_RECALL_MOVE   the model as in COPY; every file that lost a row holds rows[!near] in order afterwards, with its startId
+ *                    and endId unchanged and its count updated.  A file that lost nothing is not rewritten (bytes and mtime
+ *                    unchanged); a file that lost every row stays as a 12-byte file with count 0, so path lists and the
+ *                    retirement policy's numbering stay valid (sm_render_*_maps accept such a file).
+ * State afterwards (COPY, MOVE): as after sm_upload_model_aos(concat(m, R)) with the exceptions retirement makes:
+ * count = offset = |m| + |R|; the tick, the other counters, the frame log, the tracker's pose history, the frame planes and the
+ * depth filter's "last depth" are untouched; the index map is not redrawn; the compaction schedule restarts.  Synchronous.
+ * Errors.  |m| + |R| > MAX_VERTICES (COPY, MOVE): SM_E_CAPACITY with *n = |R|, model and files unchanged.  SM_E_ARG: NULL
+ * ctx / src / n, include_model != 0, NULL paths with n_paths > 0, a NULL path, a path listed twice in MOVE, a radius that is
+ * not finite or <= 0, a non-finite pose, an unknown mode, a call between sm_stage_conflict and sm_stage_cull.
+ * SM_E_UNSUPPORTED: a sharded or rig context.  Every file's length is checked against its header (12 + 48 * count bytes
+ * exactly) before anything changes: a file that fails gives SM_E_ARG, sm_last_error() names it, nothing has changed.
+ * Durability of MOVE.  A file's new contents go to "<path>.recall.tmp" in the same directory; all temporaries are complete
+ * before the model changes; then the model is appended; then each temporary is renamed over its file.  A temporary that cannot
+ * be written: all temporaries are removed, SM_E_ARG, nothing has changed.  A rename that fails AFTER the append: SM_E_ARG names
+ * the file, the other files are still renamed, and that file still holds the rows that are now in the model as well -- the
+ * outcome of a failure is duplicates, never loss.
+ * File index.  The context remembers size, mtime and the box of the finite centres of every file a recall has read; a listed
+ * file whose stat() still matches and whose box lies farther than radius from c is neither opened nor read.  Nothing is written
+ * next to the files.  SM_RECALL_NO_INDEX=1 turns the index off (an A/B switch: the results are the same either way). */
+enum { SM_RECALL_MOVE = 0, SM_RECALL_COPY = 1, SM_RECALL_COUNT = 2 };
+typedef struct sm_recall_params { float radius; } sm_recall_params;   /* metres, > 0, finite */
+/* radius = 1.5f * c->far_clip: sm_retire's default distance */
+int sm_default_recall_params(const sm_config *c, sm_recall_params *p);
+/* params NULL = defaults; src->include_model must be 0 */
+int sm_recall(sm_ctx *s, const sm_map_source *src, const float *pose16, const sm_recall_params *params, int32_t mode, uint32_t *n);
+
+/* what the last sm_recall of the context (the policy's included) did */
+typedef struct sm_recall_stats_t {
+    uint32_t files_listed, files_skipped;   /* paths given; of them, left unopened by the file index */
+    uint32_t files_read, files_rewritten;   /* opened and streamed through the device; renamed over (MOVE) */
+    uint64_t records_read, recalled;        /* records of the files read; |R| */
+    uint32_t chunks;                        /* chunks (at most 2^20 records) copied to the device */
+    float read_ms, copy_ms;                 /* in fread; in the host-to-device copies (events) */
+    float device_ms, write_ms;              /* in the kernels (events); in writing the temporaries (with their device-to-host copies) and renaming */
+    float total_ms;                         /* the whole call (host clock) */
+} sm_recall_stats_t;   /* (a typedef and a function share C's name space) */
+/* SM_E_ARG if the context has made no such call yet */
+int sm_recall_stats(sm_ctx *s, sm_recall_stats_t *out);
+
+/* Periodic policy.  It acts only while sm_set_auto_retire is on: on the one frame in `every` that retires, after the retirement
+ * has written its file and changed the model, it does a MOVE recall at that frame's pose from all files the retirement policy
+ * has written so far ("<prefix>_%06u.bin", 0 .. files - 1, in number order; the file this round has just written is known to hold
+ * no near row, because radius <= min_distance at the same pose, and is not read; the file index learns its box from the
+ * retirement itself).  It requires 0 < radius <= min_distance of the
+ * retirement parameters and min_distance > 0 (so that what a round retires it does not recall): whichever of the two setters is
+ * called second checks this, returns SM_E_ARG and leaves the earlier setting alone.  SM_E_CAPACITY of the recall is returned by
+ * the frame call: that frame's retirement stands and nothing is recalled.  Frames that do not retire do exactly what they do
+ * without the policy.  params NULL or radius <= 0: off (the default). */
+int sm_set_auto_recall(sm_ctx *s, const sm_recall_params *params);
+int sm_auto_recall_stats(sm_ctx *s, uint32_t *rounds, uint64_t *surfels);    /* recalls made by the policy; surfels they brought back */
+
 /* ---- per-pass entry points (GlobalModel / IndexMap methods), synchronous ---- */
 /* Upload RGB / metric depth / semantic textures directly (bypasses p0). */
 int sm_set_frame(sm_ctx *s, const uint8_t *rgb, const float *depth_metric,

@@ -34,6 +34,7 @@ SYMBOLS = (
     "sm_default_track_params", "sm_track_frame", "sm_track_debug",
     "sm_default_track_rgb_params", "sm_track_frame_rgb", "sm_track_rgb_debug",
     "sm_default_retire_params", "sm_retire", "sm_retire_device", "sm_set_auto_retire", "sm_auto_retire_stats",
+    "sm_default_recall_params", "sm_recall", "sm_recall_stats", "sm_set_auto_recall", "sm_auto_recall_stats",
 )
 
 SM_COLL_SUM, SM_COLL_MIN, SM_COLL_GATHER = 0, 1, 2
@@ -171,6 +172,31 @@ def retire_params(cfg, **over) -> SmRetireParams:
     """sm_default_retire_params of a config (min_age = time_delta, min_distance = 1.5 * far_clip) with fields overridden"""
     p = SmRetireParams()
     load().sm_default_retire_params(C.byref(cfg), C.byref(p))
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+SM_RECALL_MOVE, SM_RECALL_COPY, SM_RECALL_COUNT = 0, 1, 2
+RECALL_MODE = {"move": SM_RECALL_MOVE, "copy": SM_RECALL_COPY, "count": SM_RECALL_COUNT}
+
+
+class SmRecallParams(C.Structure):
+    _fields_ = [("radius", C.c_float)]
+
+
+class SmRecallStats(C.Structure):
+    _fields_ = [("files_listed", C.c_uint32), ("files_skipped", C.c_uint32), ("files_read", C.c_uint32), ("files_rewritten", C.c_uint32),
+                ("records_read", C.c_uint64), ("recalled", C.c_uint64), ("chunks", C.c_uint32), ("read_ms", C.c_float),
+                ("copy_ms", C.c_float), ("device_ms", C.c_float), ("write_ms", C.c_float), ("total_ms", C.c_float)]
+
+
+def recall_params(cfg, **over) -> SmRecallParams:
+    """sm_default_recall_params of a config (radius = 1.5 * far_clip) with fields overridden"""
+    p = SmRecallParams()
+    load().sm_default_recall_params(C.byref(cfg), C.byref(p))
     for k, v in over.items():
         if not hasattr(p, k):
             raise KeyError(k)
@@ -353,6 +379,11 @@ def load():
     L.sm_retire_device.argtypes = [vp, vp, C.POINTER(SmRetireParams), vp, C.c_uint32, u32p]
     L.sm_set_auto_retire.argtypes = [vp, C.POINTER(SmRetireParams), C.c_int32, C.c_char_p]
     L.sm_auto_retire_stats.argtypes = [vp, u32p, C.POINTER(C.c_uint64)]
+    L.sm_default_recall_params.argtypes = [C.POINTER(SmConfig), C.POINTER(SmRecallParams)]
+    L.sm_recall.argtypes = [vp, C.POINTER(SmMapSource), vp, C.POINTER(SmRecallParams), C.c_int32, u32p]
+    L.sm_recall_stats.argtypes = [vp, C.POINTER(SmRecallStats)]
+    L.sm_set_auto_recall.argtypes = [vp, C.POINTER(SmRecallParams)]
+    L.sm_auto_recall_stats.argtypes = [vp, u32p, C.POINTER(C.c_uint64)]
     for name in SYMBOLS:
         getattr(L, name)          # AttributeError here = the library does not match the header
     _lib = L
@@ -657,6 +688,42 @@ class SurfelMap:
         ms = (C.c_float * 5)()
         self._chk(f(self._h, ms), "sm_debug_retire_stats")
         return None if ms[0] < 0 else dict(zip(("mark", "scan", "gather", "compact", "bounds"), [float(x) for x in ms]))
+
+    # -- paging in (sm_recall, sm_set_auto_recall)
+    def recall(self, paths, pose=None, mode="move", **params) -> int:
+        """Bring the records of the map files `paths` that lie within `radius` of the camera centre back into the model
+        (sm_recall): the model becomes concat(download_model(), near rows of the files in the given order).  mode "move" takes
+        them out of the files, "copy" leaves the files alone, "count" only counts.  pose: a 4x4 camera->world matrix or
+        float32[16] column-major; None = the pose of the last processed frame.  params override sm_default_recall_params.
+        Returns how many rows came back (or would)."""
+        g = None if pose is None else _mat16(pose)
+        p = recall_params(self.cfg, **params) if params else None
+        src = map_source(paths, include_model=False)
+        n = C.c_uint32()
+        self._chk(self._L.sm_recall(self._h, C.byref(src), _ptr(g), C.byref(p) if p is not None else None, RECALL_MODE[mode], C.byref(n)),
+                  "sm_recall")
+        return int(n.value)
+
+    def recall_stats(self) -> dict:
+        """of the last recall (the policy's included): files_listed, files_skipped (by the file index), files_read,
+        files_rewritten, records_read, recalled, chunks, read_ms, copy_ms, device_ms, write_ms, total_ms"""
+        st = SmRecallStats()
+        self._chk(self._L.sm_recall_stats(self._h, C.byref(st)), "sm_recall_stats")
+        return {k: getattr(st, k) for k, _ in SmRecallStats._fields_}
+
+    def set_auto_recall(self, **params):
+        """While set_auto_retire is on: after every retirement, move back the records of its files within `radius` of that
+        frame's pose (sm_set_auto_recall; 0 < radius <= min_distance).  No params or radius <= 0: off."""
+        p = SmRecallParams(float(params["radius"])) if params else None
+        if params and set(params) != {"radius"}:
+            raise KeyError(sorted(set(params) - {"radius"}))
+        self._chk(self._L.sm_set_auto_recall(self._h, C.byref(p) if p is not None else None), "sm_set_auto_recall")
+
+    def auto_recall_stats(self):
+        """(recalls the policy has made, surfels they brought back)"""
+        r, n = C.c_uint32(), C.c_uint64()
+        self._chk(self._L.sm_auto_recall_stats(self._h, C.byref(r), C.byref(n)), "sm_auto_recall_stats")
+        return int(r.value), int(n.value)
 
     # -- IndexMap
     def download_index_map(self):

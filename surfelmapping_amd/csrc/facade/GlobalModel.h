@@ -83,6 +83,25 @@ public:
         return true;
     }
 
+    // The reverse: the records of the map files `mapFiles` (downloadMap's format, the files of SurfelMapping::setAutoRetire) that
+    // lie within `radius` metres of the camera centre of `pose` are appended to the model, in the order of the files and of their
+    // records, and -- unless keepFiles -- taken out of the files (sm_recall).  Returns how many came back, or -1 with the error
+    // printed (then neither the model nor the files have changed, but for a failed rename: see sm_c_api.h).
+    long recall(const std::vector<std::string> &mapFiles, const Eigen::Matrix4f &pose, float radius, bool keepFiles = false)
+    {
+        std::vector<const char *> paths;
+        for (const std::string &f : mapFiles) paths.push_back(f.c_str());
+        const sm_map_source src{paths.data(), (uint32_t)paths.size(), 0};
+        const sm_recall_params p = {radius};
+        uint32_t n = 0;
+        (void)sm_sync(ctx_);                                             // (SM_FACADE_ASYNC: frames may still be in flight)
+        if (sm_recall(ctx_, &src, pose.data(), &p, keepFiles ? SM_RECALL_COPY : SM_RECALL_MOVE, &n) != SM_OK) {
+            std::printf("recall: %s\n", sm_last_error());
+            return -1;
+        }
+        return (long)n;
+    }
+
     // model read-back in the reference's AoS layout (12 floats / surfel, src/Config.cpp:17-32)
     std::vector<float> downloadModel()
     {

@@ -255,6 +255,23 @@ public:
         sm_auto_retire_stats(ctx_, &f, &n);
         return {f, (unsigned long long)n};
     }
+    // With setAutoRetire on: after every retirement, the records of its map files within `radius` metres of that frame's camera
+    // come back into the model and leave the files, so that a camera that returns finds what it left (sm_set_auto_recall;
+    // 0 < radius <= the retirement's minDistance).  radius <= 0: off.
+    bool setAutoRecall(float radius = -1.0f)
+    {
+        const sm_recall_params p = {radius};
+        if (sm_set_auto_recall(ctx_, radius > 0.0f ? &p : nullptr) == SM_OK) return true;
+        std::printf("setAutoRecall: %s\n", sm_last_error());
+        return false;
+    }
+    // recalls the policy has made and the surfels they brought back
+    std::pair<unsigned, unsigned long long> autoRecallStats()
+    {
+        uint32_t r = 0; uint64_t n = 0;
+        sm_auto_recall_stats(ctx_, &r, &n);
+        return {r, (unsigned long long)n};
+    }
     // (sm_sync first: with SM_FACADE_ASYNC frames may still be in flight, and sm_get_counts returns the counters of the last wait)
     sm_counts counts() { sm_counts c{}; (void)sm_sync(ctx_); sm_get_counts(ctx_, &c); return c; }
 

@@ -10,6 +10,7 @@
 //   sm_rig.hip       rig consolidation (sm_rig_*)
 //   sm_retire.hip    retirement (sm_retire*, sm_set_auto_retire)
 //   sm_render_maps.hip  views of a map set (sm_render_*_maps): map files streamed through the renderers
+//   sm_recall.hip    paging in (sm_recall*, sm_set_auto_recall): records of map files near the camera back into the model
 #pragma once
 
 #include "../../include/sm_c_api.h"
@@ -22,12 +23,13 @@
 #include <cstdio>
 #include <cstring>
 #include <functional>
+#include <map>
 #include <memory>
 #include <string>
 #include <utility>
 #include <vector>
 
-namespace sm { struct TrackState; struct TrackRgbState; struct RenderParams; struct ViewParams; struct ViewShade; }
+namespace sm { struct TrackState; struct TrackRgbState; struct RenderParams; struct ViewParams; struct ViewShade; struct RecallChunk; }
 
 // Hidden: libsurfelmapping_hip.so exports the C ABI and the kernels' host stubs, nothing of this namespace.  Its functions are
 // defined qualified (sm_impl::name) so that the definitions keep the visibility.
@@ -164,6 +166,23 @@ struct RenderMaps {
     size_t par_bytes = 0;
     sm_maps_stats stats{};
     bool stats_valid = false;
+};
+
+// paging in (sm_recall.hip, sm_k_recall.h): scratch allocated by the first call that reads a file, the file index, the last
+// call's tally, the periodic policy and its tally.  The records stream through RenderMaps' staging.
+struct Recall {
+    // what the context knows of a map file it has read: valid while the file's size and mtime are these
+    struct Entry { uint64_t size; int64_t mtime_ns; float lo[3], hi[3]; };   // box of the rows' finite centres (lo > hi: none)
+    std::map<std::string, Entry> index;
+    Dev<uint64_t> d_mask;              // 4 words per block of 256 records: near
+    Dev<uint32_t> d_blk_cnt, d_blk_base, d_run;   // near per block, their exclusive prefix, the call's running total
+    Dev<RecallChunk> d_chunk;          // [2]: the scan's tally of the chunk in buffer c & 1
+    Host<RecallChunk> h_chunk;         // pinned, [2]
+    sm_recall_stats_t stats{};
+    bool stats_valid = false;
+    float radius = 0.0f;               // sm_set_auto_recall: <= 0 = off
+    uint32_t rounds = 0;               // recalls the policy has made
+    uint64_t surfels = 0;              // ... and the surfels they brought back
 };
 
 // The SM_* switches of the frame pipeline (sm_api.hip), read once by sm_create (read_switches): nothing on the per-frame path
@@ -371,6 +390,7 @@ struct sm_ctx {
     Tracker trk;
     Retire ret;
     RenderMaps maps;
+    Recall rec;
     // host frame state (src/SurfelMapping.h:100-103)
     int tick = 0;
     bool ref_set = false;
@@ -424,5 +444,18 @@ int view_splat_model(sm_ctx *s, const ViewParams &vp, uint64_t *key, uint32_t *d
                      const Event *timing = nullptr);
 // ---- sm_retire.hip ----
 int auto_retire_after_frame(sm_ctx *s);           // the periodic policy: called once a frame is enqueued (one test unless it is due)
+// ---- sm_render_maps.hip ----
+int maps_ensure_staging(sm_ctx *s);               // RenderMaps' copy stream, record buffers and events: whole or absent
+// ---- sm_recall.hip ----
+// the periodic policy: called by a frame that has just retired (one test unless it is on).  wrote_file: this round's retirement
+// wrote the policy's newest file, at this pose -- every row of it is far, so the recall does not read it
+int auto_recall_after_retire(sm_ctx *s, bool wrote_file);
+// For the file index, while the recall policy is on (its setter has allocated the scratch): the box of the finite centres of n
+// AoS records in device memory folded into lo / hi (k_recall_mark + k_recall_scan on the context's stream; waits), and the entry
+// of a map file the context has just written itself with that box
+int recall_box_of(sm_ctx *s, const float *d_rec12, uint32_t n, float lo[3], float hi[3]);
+void recall_note_written(sm_ctx *s, const std::string &path, const float lo[3], const float hi[3]);
+// what the two policies require of each other when both are on (SM_E_ARG with g_err set otherwise)
+int check_recall_policy(float radius, const sm_retire_params &rp, const char *who);
 
 }  // namespace sm_impl

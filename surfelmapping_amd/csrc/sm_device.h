@@ -211,6 +211,17 @@ __device__ __forceinline__ float get_radius(float depth, float norm_z, float inv
     return min_glsl(2.0f * radius, radius_n);
 }
 
+// one 48-byte AoS record (pos_conf | colour, standby, init_time, time | norm_rad) into slot k of a set: what every import of
+// records from outside the frame pipeline writes (k_import_aos, k_recall_place); the standby word is not stored
+__device__ __forceinline__ void store_record(const SurfelSet &cur, uint32_t k, const float4 &pc, const float4 &ct, const float4 &nr)
+{
+    cur.pos_conf[k] = pc;
+    cur.color[k] = __float_as_uint(ct.x);
+    cur.init_time[k] = ct.z;
+    cur.time[k] = ct.w;
+    cur.norm_rad[k] = nr;
+}
+
 // exclusive scan of one value per thread over a 1024-thread block; lds needs 17 words
 __device__ __forceinline__ uint32_t block_scan_1024(uint32_t v, uint32_t *total, uint32_t *lds)
 {

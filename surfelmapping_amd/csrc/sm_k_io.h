@@ -27,14 +27,9 @@ __global__ void k_import_aos(Model M, const DevState *__restrict__ st, const flo
 {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) return;
-    const SurfelSet cur = M.s[st->cur];
-    const uint32_t k = first + t;
     const float *o = src + (size_t)t * 12;
-    cur.pos_conf[k] = make_float4(o[0], o[1], o[2], o[3]);
-    cur.color[k] = __float_as_uint(o[4]);
-    cur.init_time[k] = o[6];
-    cur.time[k] = o[7];
-    cur.norm_rad[k] = make_float4(o[8], o[9], o[10], o[11]);
+    store_record(M.s[st->cur], first + t, make_float4(o[0], o[1], o[2], o[3]), make_float4(o[4], o[5], o[6], o[7]),
+                 make_float4(o[8], o[9], o[10], o[11]));
 }
 
 // index-map textures (index_map.vert:61-63) materialised from the key map, row-major output

@@ -55,26 +55,6 @@ struct Mode {
     uint8_t *out0; uint8_t *out1; uint8_t *out2;
 };
 
-int ensure_staging(sm_ctx *s)
-{
-    RenderMaps &rm = s->maps;
-    if (rm.copy) return SM_OK;
-    Stream copy;
-    HIPCK(hipStreamCreateWithFlags(copy.put(), hipStreamNonBlocking));
-    const size_t N = RenderMaps::CHUNK;
-    for (int b = 0; b < 2; ++b) {
-        HIPCK(hipHostMalloc((void **)rm.h_rec[b].put(), N * 48, hipHostMallocDefault));
-        HIPCK(hipMalloc(rm.d_rec[b].put(), N * 48));
-        for (Event *e : {&rm.ev_copy0[b], &rm.ev_copied[b], &rm.ev_free[b], &rm.ev_k0[b], &rm.ev_k1[b]}) HIPCK(hipEventCreate(e->put()));
-    }
-    int rc;
-    if ((rc = dalloc(rm.d_pos_conf, N)) || (rc = dalloc(rm.d_norm_rad, N)) || (rc = dalloc(rm.d_color, N)) || (rc = dalloc(rm.d_time, N)) ||
-        (rc = dalloc(rm.d_box, 2 * (N / MAPS_BLOCK))))
-        return rc;
-    rm.copy = std::move(copy);                           // last: the staging is whole or absent
-    return SM_OK;
-}
-
 // fold the finished events of buffer b into the tally (waits for them)
 int fold_events(sm_ctx *s, int b)
 {
@@ -111,7 +91,7 @@ int render_maps(sm_ctx *s, const sm_map_source *src, const char *fn, const Mode 
     rm.stats = sm_maps_stats{};
     rm.stats_valid = true;
     if (md.n_views == 0) { rm.stats.total_ms = (float)(now_ms() - t_begin); return SM_OK; }
-    if (file_total && (rc = ensure_staging(s))) return rc;
+    if (file_total && (rc = maps_ensure_staging(s))) return rc;
 
     const char *e = std::getenv("SM_RENDER_MAPS_NO_CULL");
     const int cull = (e && e[0] == '1') ? 0 : 1;
@@ -258,6 +238,26 @@ int render_maps(sm_ctx *s, const sm_map_source *src, const char *fn, const Mode 
 }
 
 }  // namespace
+
+int sm_impl::maps_ensure_staging(sm_ctx *s)
+{
+    RenderMaps &rm = s->maps;
+    if (rm.copy) return SM_OK;
+    Stream copy;
+    HIPCK(hipStreamCreateWithFlags(copy.put(), hipStreamNonBlocking));
+    const size_t N = RenderMaps::CHUNK;
+    for (int b = 0; b < 2; ++b) {
+        HIPCK(hipHostMalloc((void **)rm.h_rec[b].put(), N * 48, hipHostMallocDefault));
+        HIPCK(hipMalloc(rm.d_rec[b].put(), N * 48));
+        for (Event *e : {&rm.ev_copy0[b], &rm.ev_copied[b], &rm.ev_free[b], &rm.ev_k0[b], &rm.ev_k1[b]}) HIPCK(hipEventCreate(e->put()));
+    }
+    int rc;
+    if ((rc = dalloc(rm.d_pos_conf, N)) || (rc = dalloc(rm.d_norm_rad, N)) || (rc = dalloc(rm.d_color, N)) || (rc = dalloc(rm.d_time, N)) ||
+        (rc = dalloc(rm.d_box, 2 * (N / MAPS_BLOCK))))
+        return rc;
+    rm.copy = std::move(copy);                           // last: the staging is whole or absent
+    return SM_OK;
+}
 
 extern "C" {
 

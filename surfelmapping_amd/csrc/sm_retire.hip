@@ -180,6 +180,11 @@ int sm_impl::auto_retire_after_frame(sm_ctx *s)
         snprintf(name, sizeof name, "_%06u.bin", r.files);
         const std::string path = r.prefix + name;
         const int32_t start_id = r.last_tick, end_id = s->tick - 1;
+        // sm_set_auto_recall: the file index learns the file's box now, from the records on the device, so that no recall has
+        // to read the file only to find out where it lies
+        const bool want_box = s->rec.radius > 0.0f;
+        const float INF = __builtin_inff();
+        float lo[3] = {INF, INF, INF}, hi[3] = {-INF, -INF, -INF};
         FILE *f = fopen(path.c_str(), "wb");
         if (!f) { g_err = path + " is not open!"; return SM_E_ARG; }
         bool ok = fwrite(&n, 4, 1, f) == 1 && fwrite(&start_id, 4, 1, f) == 1 && fwrite(&end_id, 4, 1, f) == 1;
@@ -190,21 +195,25 @@ int sm_impl::auto_retire_after_frame(sm_ctx *s)
             if ((he = hipGetLastError()) == hipSuccess)
                 he = hipMemcpyAsync(r.h_stage, s->d_export, (size_t)m * 48, hipMemcpyDeviceToHost, s->stream);
             if (he == hipSuccess) he = hipStreamSynchronize(s->stream);
+            if (he == hipSuccess && want_box && (rc = recall_box_of(s, (const float *)s->d_export.get(), m, lo, hi))) { ok = false; break; }
             if (he == hipSuccess) ok = fwrite(r.h_stage, 48, m, f) == m;
         }
         ok = (fclose(f) == 0) && ok;
         if (he != hipSuccess || !ok) {
             std::remove(path.c_str());           // no half-written map file is left behind
+            if (rc) return rc;                   // (recall_box_of: a device error, g_err is set)
             if (he != hipSuccess) { set_err("retirement into a map file", he, __FILE__, __LINE__); return SM_E_HIP; }
             g_err = path + " saved err!!";
             return SM_E_ARG;
         }
+        if (want_box) recall_note_written(s, path, lo, hi);
         r.files++;
         r.surfels += n;
         r.last_tick = s->tick;
     }
     if ((rc = tic(s, 4))) return rc;
-    return retire_commit(s, n);
+    if ((rc = retire_commit(s, n))) return rc;
+    return auto_recall_after_retire(s, n != 0);          // sm_set_auto_recall: pages in around the same pose (one test unless it is on)
 }
 
 extern "C" {
@@ -238,6 +247,7 @@ int sm_set_auto_retire(sm_ctx *s, const sm_retire_params *params, int32_t every,
     if (rc) return rc;
     Retire &r = s->ret;
     if (every <= 0 || !path_prefix) { r.every = 0; r.prefix.clear(); return SM_OK; }
+    if (s->rec.radius > 0.0f && (rc = check_recall_policy(s->rec.radius, p, "sm_set_auto_retire"))) return rc;
     HIPCK(hipSetDevice(s->cfg.device));
     if ((rc = ensure_scratch(s))) return rc;     // so that the frame that retires first allocates nothing
     r.params = p;

@@ -672,13 +672,8 @@ int discard_model(sm_ctx *s)
         HIPCK(hipMemsetAsync(s->d_tile_dead, 0, s->dead_tiles * 4, s->stream));
         s->maybe_garbage = false;
     }
-    s->culls_since_compact = 0;
-    DevState &d = *s->h_state;
-    d.count = 0; d.offset = 0; d.garbage = 0; d.garbage_prev = 0; d.first_live = 0; d.do_compact = 0;
-    d.conflict_count = 0; d.visible_count = 0;      // no conflict pass, no index map in the initialising frame
-    if ((rc = push_state(s))) return rc;
-    if ((rc = rebuild_bounds(s, 0, 0))) return rc;
-    return pull_state(s);
+    s->h_state->conflict_count = 0; s->h_state->visible_count = 0;      // no conflict pass, no index map in the initialising frame
+    return publish_dense(s, 0, 0);
 }
 
 void bump_bound(sm_ctx *s)
@@ -1040,6 +1035,19 @@ int sm_impl::rebuild_bounds(sm_ctx *s, uint32_t first_surfel, uint32_t count)
     }
     HIPCK(hipStreamSynchronize(s->stream));
     return SM_OK;
+}
+
+int sm_impl::publish_dense(sm_ctx *s, uint32_t count, uint32_t first_new)
+{
+    DevState &d = *s->h_state;
+    d.count = count;                             // src/GlobalModel.cpp:995
+    d.offset = count;
+    d.garbage = 0; d.garbage_prev = 0; d.first_live = 0; d.do_compact = 0;
+    s->culls_since_compact = 0;
+    int rc = push_state(s);
+    if (rc) return rc;
+    if ((rc = rebuild_bounds(s, first_new, count))) return rc;
+    return pull_state(s);
 }
 
 int sm_impl::ensure_export(sm_ctx *s, size_t bytes)

@@ -11,6 +11,8 @@
 //   sm_retire.hip    retirement (sm_retire*, sm_set_auto_retire)
 //   sm_render_maps.hip  views of a map set (sm_render_*_maps): map files streamed through the renderers
 //   sm_recall.hip    paging in (sm_recall*, sm_set_auto_recall): records of map files near the camera back into the model
+// and, beside it, for everything that touches a map file: sm_mapfile.h (the format: checked open, writer, chunk plan; host only)
+// and sm_map_stream.h (the double-buffered chunk stream of sm_render_maps.hip and sm_recall.hip).
 #pragma once
 
 #include "../../include/sm_c_api.h"
@@ -20,6 +22,7 @@
 
 #include <algorithm>
 #include <cassert>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <functional>
@@ -148,17 +151,16 @@ struct Retire {
 };
 
 // views of a map set (sm_render_maps.hip, sm_k_render_maps.h): the staging of the file stream, allocated by the first call, and
-// the last call's tally.  Chunk c of a pass goes through buffer c & 1: fread into h_rec, copied on `copy` into d_rec, unpacked
-// into the one set of SoA planes by the intake kernel on the context's stream.
+// the last call's tally.  Chunk c of a pass goes through buffer c & 1 (MapStream, sm_map_stream.h, which sm_recall.hip uses as
+// well): read into h_rec, copied on `copy` into d_rec, unpacked into the one set of SoA planes by the intake kernel on the
+// context's stream.
 struct RenderMaps {
     static constexpr uint32_t CHUNK = 1u << 20;          // records per chunk (48 MiB), the chunk sm_retire writes files in
     Stream copy;                       // first: what follows is used on it
     Host<float4> h_rec[2];             // pinned
     Dev<float4> d_rec[2];
     Event ev_copy0[2], ev_copied[2];   // on `copy`: around the chunk's copy
-    Event ev_free[2];                  // on the context's stream: the intake has read d_rec
-    Event ev_k0[2], ev_k1[2];          // ... around the chunk's kernels
-    bool in_flight[2] = {false, false};   // the buffer's events have been recorded and not yet folded into the tally
+    Event ev_k0[2], ev_k1[2];          // on the context's stream: around the chunk's kernels
     Dev<float4> d_pos_conf, d_norm_rad, d_box;
     Dev<uint32_t> d_color;
     Dev<float> d_time;
@@ -424,6 +426,10 @@ int pull_state(sm_ctx *s);
 int finalize_if_pending(sm_ctx *s);
 int ensure_compact(sm_ctx *s);
 int rebuild_bounds(sm_ctx *s, uint32_t first_surfel, uint32_t count);
+// The model has been written from outside the frame pipeline and is now the dense rows [0, count), of which [first_new, count)
+// are new: count and offset, no dead slots, the compaction schedule restarted, the tile boxes from first_new's tile on rebuilt,
+// the host's mirror and counts refreshed.  What an upload leaves; a retirement, a recall and the reset path leave the same.
+int publish_dense(sm_ctx *s, uint32_t count, uint32_t first_new);
 int ensure_export(sm_ctx *s, size_t bytes);
 void fill_keys(sm_ctx *s, uint64_t *key, size_t n);                  // k_fill_keys on the context's stream
 int clean_points_device(sm_ctx *s, const uint16_t *d_depth_mm, const uint8_t *d_semantic, const float *pose16, int exempt_first,
@@ -457,5 +463,40 @@ int recall_box_of(sm_ctx *s, const float *d_rec12, uint32_t n, float lo[3], floa
 void recall_note_written(sm_ctx *s, const std::string &path, const float lo[3], const float hi[3]);
 // what the two policies require of each other when both are on (SM_E_ARG with g_err set otherwise)
 int check_recall_policy(float radius, const sm_retire_params &rp, const char *who);
+
+// ---- what several sources ask of their arguments (SM_E_ARG with g_err set) ----
+inline int check_pose(const float *pose16, const char *who)          // null: the entry point's default
+{
+    if (pose16)
+        for (int i = 0; i < 16; ++i)
+            if (!std::isfinite(pose16[i])) { g_err = std::string(who) + ": non-finite pose"; return SM_E_ARG; }
+    return SM_OK;
+}
+
+inline int check_map_source(const sm_map_source *src, const char *who)
+{
+    if (src->n_paths && !src->paths) { g_err = std::string(who) + ": null paths"; return SM_E_ARG; }
+    for (uint32_t i = 0; i < src->n_paths; ++i)
+        if (!src->paths[i]) { g_err = std::string(who) + ": null path"; return SM_E_ARG; }
+    return SM_OK;
+}
+
+// n records out of the model into host memory, `chunk` at a time through the export scratch (which holds a chunk: ensure_export):
+// produce(d_dst, first, m) launches what fills the scratch with records [first, first + m), they are copied to
+// dst + first * dst_stride floats (0: a staging buffer that each(first, m) empties), the stream is waited for, each() runs.
+template <typename Produce, typename Each>
+int drain_export(sm_ctx *s, uint32_t n, uint32_t chunk, float *dst, size_t dst_stride, Produce produce, Each each)
+{
+    for (uint32_t first = 0; first < n; first += chunk) {
+        const uint32_t m = std::min(chunk, n - first);
+        produce((float *)s->d_export.get(), first, m);
+        HIPCK(hipGetLastError());
+        HIPCK(hipMemcpyAsync(dst + (size_t)first * dst_stride, s->d_export, (size_t)m * 48, hipMemcpyDeviceToHost, s->stream));
+        HIPCK(hipStreamSynchronize(s->stream));
+        if (int rc = each(first, m)) return rc;
+    }
+    return SM_OK;
+}
+inline int no_hook(uint32_t, uint32_t) { return SM_OK; }
 
 }  // namespace sm_impl

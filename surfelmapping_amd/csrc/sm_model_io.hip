@@ -3,6 +3,7 @@
 // device-side export / append of sharded and rig runs.  Kernels: sm_k_io.h.
 #include "sm_ctx.h"
 #include "sm_k_io.h"
+#include "sm_mapfile.h"
 
 using namespace sm;
 
@@ -33,14 +34,7 @@ int sm_download_model_aos(sm_ctx *s, float *dst12, uint32_t cap, uint32_t *n)
     if (s->pending_cull) { g_err = "sm_download_model_aos between sm_stage_conflict and sm_stage_cull"; return SM_E_ARG; }
     const uint32_t CH = 1u << 22;                // 4 Mi surfels (192 MiB) per staging chunk
     if ((rc = ensure_export(s, (size_t)std::min(cnt, CH) * 48))) return rc;
-    for (uint32_t first = 0; first < cnt; first += CH) {
-        const uint32_t m = std::min(CH, cnt - first);
-        export_aos(s, (float *)s->d_export.get(), first, m);
-        HIPCK(hipGetLastError());
-        HIPCK(hipMemcpyAsync(dst12 + (size_t)first * 12, s->d_export, (size_t)m * 48, hipMemcpyDeviceToHost, s->stream));
-        HIPCK(hipStreamSynchronize(s->stream));
-    }
-    return SM_OK;
+    return drain_export(s, cnt, CH, dst12, 12, [s](float *d, uint32_t first, uint32_t m) { export_aos(s, d, first, m); }, no_hook);
 }
 
 int sm_upload_model_aos(sm_ctx *s, const float *src12, uint32_t n)
@@ -60,15 +54,11 @@ int sm_upload_model_aos(sm_ctx *s, const float *src12, uint32_t n)
         HIPCK(hipGetLastError());
         HIPCK(hipStreamSynchronize(s->stream));
     }
-    s->h_state->count = n;                       // src/GlobalModel.cpp:995
-    s->h_state->offset = n;
-    s->h_state->garbage = 0; s->h_state->garbage_prev = 0; s->h_state->first_live = 0; s->h_state->do_compact = 0;
     s->pending_cull = false;
-    if ((rc = push_state(s))) return rc;
-    if ((rc = rebuild_bounds(s, 0, n))) return rc;
-    return pull_state(s);
+    return publish_dense(s, n, 0);
 }
 
+// (a call that fails leaves no file at `path`, not a truncated one)
 int sm_save_map(sm_ctx *s, const char *path, int32_t start_id, int32_t end_id)
 {
     if (!s || !path) return SM_E_ARG;
@@ -77,31 +67,22 @@ int sm_save_map(sm_ctx *s, const char *path, int32_t start_id, int32_t end_id)
     if (rc) return rc;
     std::vector<float> buf((size_t)n * 12);
     if ((rc = sm_download_model_aos(s, buf.data(), n, &n))) return rc;
-    FILE *f = fopen(path, "wb");
-    if (!f) { g_err = std::string(path) + " is not open!"; return SM_E_ARG; }
-    // u32 count | i32 startId | i32 endId | count*12 f32   (src/GlobalModel.cpp:927-932)
-    bool ok = fwrite(&n, 4, 1, f) == 1 && fwrite(&start_id, 4, 1, f) == 1 && fwrite(&end_id, 4, 1, f) == 1 &&
-              (n == 0 || fwrite(buf.data(), 48, n, f) == n);
-    ok = (fclose(f) == 0) && ok;
-    if (!ok) { g_err = std::string(path) + " saved err!!"; return SM_E_ARG; }
-    return SM_OK;
+    sm_mapfile::Writer w;
+    return w.open(path, n, start_id, end_id, nullptr, g_err) && w.append(buf.data(), n, g_err) && w.commit(g_err) ? SM_OK : SM_E_ARG;
 }
 
 int sm_load_map(sm_ctx *s, const char *path, int32_t *start_id, int32_t *end_id)
 {
     if (!s || !path) return SM_E_ARG;
-    FILE *f = fopen(path, "rb");
-    if (!f) { g_err = std::string(path) + " is not open!"; return SM_E_ARG; }
-    uint32_t n = 0; int32_t a = 0, b = 0;
-    bool ok = fread(&n, 4, 1, f) == 1 && fread(&a, 4, 1, f) == 1 && fread(&b, 4, 1, f) == 1;
-    std::vector<float> buf;
-    if (ok && n <= s->cap) { buf.resize((size_t)n * 12); ok = n == 0 || fread(buf.data(), 48, n, f) == n; }
-    fclose(f);
-    if (!ok) { g_err = std::string(path) + " read err!!"; return SM_E_ARG; }
-    if (n > s->cap) { g_err = "map larger than MAX_VERTICES"; return SM_E_CAPACITY; }
-    if (start_id) *start_id = a;
-    if (end_id) *end_id = b;
-    return sm_upload_model_aos(s, buf.data(), n);
+    sm_mapfile::Header h;
+    sm_mapfile::File f = sm_mapfile::open_checked(path, nullptr, h, g_err, true);
+    if (!f) return SM_E_ARG;
+    if (h.count > s->cap) { g_err = "map larger than MAX_VERTICES"; return SM_E_CAPACITY; }
+    std::vector<float> buf((size_t)h.count * 12);
+    if (!sm_mapfile::read_rows(f.get(), buf.data(), h.count)) { g_err = std::string(path) + " read err!!"; return SM_E_ARG; }
+    if (start_id) *start_id = h.start_id;
+    if (end_id) *end_id = h.end_id;
+    return sm_upload_model_aos(s, buf.data(), h.count);
 }
 
 int sm_download_index_map(sm_ctx *s, int32_t *id, float *vert_conf4, float *color_time4, float *norm_rad4)

@@ -6,28 +6,19 @@
 // (never at or above MAX_VERTICES); the count is published only when every file has been read and every temporary of a MOVE is
 // complete, so a call that fails -- a file that cannot be read, a temporary that cannot be written, SM_E_CAPACITY -- leaves the
 // model as it was: slots above `count` are nobody's.
-#include "sm_ctx.h"
+#include "sm_map_stream.h"
 #include "sm_k_recall.h"
 
-#include <chrono>
-#include <cmath>
 #include <cstdlib>
-#include <sys/stat.h>
 
 using namespace sm;
+using sm_mapfile::Job;
+using sm_mapfile::now_ms;
 
 namespace {
 
 constexpr uint32_t CHUNK = RenderMaps::CHUNK;
 static_assert(CHUNK / RECALL_BLOCK == RECALL_MAX_BLOCKS, "a chunk's blocks are scanned by one workgroup");
-
-struct FileCloser { void operator()(FILE *f) const { if (f) fclose(f); } };
-using File = std::unique_ptr<FILE, FileCloser>;
-
-double now_ms()
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 // ---------------------------------------------------------------------------------------------
 // The file index's test.  True = no row of the file can be near, the file need not be opened.  Conservative by construction:
@@ -66,23 +57,15 @@ bool box_out_of_reach(const Recall::Entry &e, const float *c, float r2)
 // one listed file through the call
 struct MapFile {
     std::string path;
-    uint64_t size = 0;                 // from stat(), as the index keeps it
-    int64_t mtime_ns = 0;
     bool skipped = false;              // by the index: not opened
-    uint32_t n = 0;                    // records (header)
-    int32_t start_id = 0, end_id = 0;
+    sm_mapfile::Header h;              // count 0 unless the file is read
     float lo[3], hi[3];                // box of this read
     uint32_t chunks_left = 0;
-    // MOVE: the temporary, opened by the first chunk that loses a row
-    FILE *tmp = nullptr;
-    std::string tmp_path;
-    bool tmp_made = false, tmp_done = false;
-    uint32_t kept = 0;
+    // MOVE: the temporary, opened by the first chunk that loses a row; a call that ends before the file is replaced removes it
+    sm_mapfile::Writer tmp;
+    bool tmp_done = false;             // complete and closed, not yet renamed
+    ~MapFile() { if (tmp_done) std::remove(tmp.path().c_str()); }
 };
-
-struct Job { uint32_t file, first, n; };
-
-int64_t mtime_of(const struct stat &st) { return (int64_t)st.st_mtim.tv_sec * 1000000000ll + (int64_t)st.st_mtim.tv_nsec; }
 
 int ensure_scratch(sm_ctx *s)
 {
@@ -101,31 +84,6 @@ int ensure_scratch(sm_ctx *s)
     return SM_OK;
 }
 
-// the temporary of a file that is about to lose its first row: header (completed at the end), then the rows of the chunks
-// before `first`, which lost nothing, from the file itself
-int open_tmp(MapFile &mf, uint32_t first, const char *who)
-{
-    mf.tmp_path = mf.path + ".recall.tmp";
-    mf.tmp = fopen(mf.tmp_path.c_str(), "wb");
-    if (!mf.tmp) { g_err = std::string(who) + ": " + mf.tmp_path + " is not open!"; return SM_E_ARG; }
-    mf.tmp_made = true;
-    const uint32_t hdr[3] = {0u, (uint32_t)mf.start_id, (uint32_t)mf.end_id};
-    bool ok = fwrite(hdr, 4, 3, mf.tmp) == 3;
-    if (ok && first) {
-        File f(fopen(mf.path.c_str(), "rb"));
-        ok = f && fseek(f.get(), 12, SEEK_SET) == 0;
-        std::vector<char> buf((size_t)48 << 14);
-        for (uint64_t left = (uint64_t)first; ok && left;) {
-            const size_t m = (size_t)std::min<uint64_t>(left, (uint64_t)1 << 14);
-            ok = fread(buf.data(), 48, m, f.get()) == m && fwrite(buf.data(), 48, m, mf.tmp) == m;
-            left -= m;
-        }
-        mf.kept = first;
-    }
-    if (!ok) { g_err = std::string(who) + ": " + mf.tmp_path + " saved err!!"; return SM_E_ARG; }
-    return SM_OK;
-}
-
 struct Run {
     sm_ctx *s;
     const char *who;
@@ -135,116 +93,84 @@ struct Run {
     std::vector<MapFile> &files;
     std::vector<Job> jobs;
     uint64_t total = 0;                // |R| so far
-    File in;                           // the file being read
-    uint32_t in_file = 0xFFFFFFFFu;
 };
 
-// chunk c: the host's read, the copy, the kernels and the read-back of the chunk's tally, all asynchronous but the read
-int enqueue(Run &R, uint32_t c)
+// the next chunk of the stream: the kernels and the read-back of the chunk's tally, all asynchronous
+int enqueue(Run &R, MapStream &in, MapStream::Chunk &ck)
 {
     sm_ctx *s = R.s;
     RenderMaps &rm = s->maps;
     Recall &r = s->rec;
-    const Job &j = R.jobs[c];
-    MapFile &mf = R.files[j.file];
-    const int q = (int)(c & 1u);
-    if (R.in_file != j.file) {
-        R.in.reset(fopen(mf.path.c_str(), "rb"));
-        R.in_file = j.file;
-        if (!R.in || fseek(R.in.get(), 12, SEEK_SET) != 0) { g_err = std::string(R.who) + ": " + mf.path + " is not open!"; return SM_E_ARG; }
-    }
-    const double t0 = now_ms();
-    const size_t got = fread(rm.h_rec[q].get(), 48, j.n, R.in.get());
-    r.stats.read_ms += (float)(now_ms() - t0);
-    if (got != j.n) { g_err = std::string(R.who) + ": " + mf.path + " read err!!"; return SM_E_ARG; }
-    // (buffer q is free on both sides: chunk c - 2 was finished, which waits for its kernels)
-    HIPCK(hipEventRecord(rm.ev_copy0[q], rm.copy));
-    HIPCK(hipMemcpyAsync(rm.d_rec[q], rm.h_rec[q], (size_t)j.n * 48, hipMemcpyHostToDevice, rm.copy));
-    HIPCK(hipEventRecord(rm.ev_copied[q], rm.copy));
-    HIPCK(hipStreamWaitEvent(s->stream, rm.ev_copied[q], 0));
-    HIPCK(hipEventRecord(rm.ev_k0[q], s->stream));
-    const unsigned nblk = (j.n + RECALL_BLOCK - 1) / RECALL_BLOCK;
-    const float4 *rec = (const float4 *)rm.d_rec[q].get();
-    hipLaunchKernelGGL(k_recall_mark, dim3(nblk), dim3(256), 0, s->stream, rec, j.n, R.ra, r.d_mask.get(), r.d_blk_cnt.get(), rm.d_box.get());
+    int rc = in.next(ck);
+    if (rc) return rc;
+    const int q = ck.q;
+    const uint32_t n = ck.job->n;
+    const unsigned nblk = (n + RECALL_BLOCK - 1) / RECALL_BLOCK;
+    const float4 *rec = ck.d_rec;
+    hipLaunchKernelGGL(k_recall_mark, dim3(nblk), dim3(256), 0, s->stream, rec, n, R.ra, r.d_mask.get(), r.d_blk_cnt.get(), rm.d_box.get());
     hipLaunchKernelGGL(k_recall_scan, dim3(1), dim3(1024), 0, s->stream, nblk, (const uint32_t *)r.d_blk_cnt.get(), (const float4 *)rm.d_box.get(),
                        r.d_blk_base.get(), r.d_run.get(), r.d_chunk.get() + q);
     if (R.mode != SM_RECALL_COUNT) {
         float4 *keep = R.mode == SM_RECALL_MOVE ? (float4 *)s->d_export.get() + (size_t)q * CHUNK * 3 : nullptr;
-        hipLaunchKernelGGL(k_recall_place, dim3(nblk), dim3(256), 0, s->stream, rec, j.n, s->M, (const DevState *)s->d_state.get(),
+        hipLaunchKernelGGL(k_recall_place, dim3(nblk), dim3(256), 0, s->stream, rec, n, s->M, (const DevState *)s->d_state.get(),
                            (const uint64_t *)r.d_mask.get(), (const uint32_t *)r.d_blk_cnt.get(), (const uint32_t *)r.d_blk_base.get(),
                            (const RecallChunk *)(r.d_chunk.get() + q), R.base0, s->cap, keep);
     }
     HIPCK(hipGetLastError());
     HIPCK(hipMemcpyAsync(r.h_chunk.get() + q, r.d_chunk.get() + q, sizeof(RecallChunk), hipMemcpyDeviceToHost, s->stream));
-    HIPCK(hipEventRecord(rm.ev_k1[q], s->stream));
+    if ((rc = in.done(q))) return rc;
     r.stats.chunks++;
-    r.stats.records_read += j.n;
+    r.stats.records_read += n;
     return SM_OK;
 }
 
-// chunk c is through the device: its tally, its box, and (MOVE) its rows that stay into the file's temporary
-int finish(Run &R, uint32_t c)
+// the chunk is through the device: its tally, its box, and (MOVE) its rows that stay into the file's temporary
+int finish(Run &R, MapStream &in, const MapStream::Chunk &ck)
 {
     sm_ctx *s = R.s;
     RenderMaps &rm = s->maps;
     Recall &r = s->rec;
-    const Job &j = R.jobs[c];
+    const Job &j = *ck.job;
     MapFile &mf = R.files[j.file];
-    const int q = (int)(c & 1u);
-    float ms = 0.0f;
-    HIPCK(hipEventSynchronize(rm.ev_k1[q]));
-    HIPCK(hipEventElapsedTime(&ms, rm.ev_copy0[q], rm.ev_copied[q]));
-    r.stats.copy_ms += ms;
-    HIPCK(hipEventElapsedTime(&ms, rm.ev_k0[q], rm.ev_k1[q]));
-    r.stats.device_ms += ms;
-    const RecallChunk ck = r.h_chunk.get()[q];
-    R.total += ck.total;
-    mf.lo[0] = std::min(mf.lo[0], ck.lx); mf.lo[1] = std::min(mf.lo[1], ck.ly); mf.lo[2] = std::min(mf.lo[2], ck.lz);
-    mf.hi[0] = std::max(mf.hi[0], ck.hx); mf.hi[1] = std::max(mf.hi[1], ck.hy); mf.hi[2] = std::max(mf.hi[2], ck.hz);
+    const int q = ck.q;
+    int rc = in.fold(q);
+    if (rc) return rc;
+    const RecallChunk rc_q = r.h_chunk.get()[q];
+    R.total += rc_q.total;
+    mf.lo[0] = std::min(mf.lo[0], rc_q.lx); mf.lo[1] = std::min(mf.lo[1], rc_q.ly); mf.lo[2] = std::min(mf.lo[2], rc_q.lz);
+    mf.hi[0] = std::max(mf.hi[0], rc_q.hx); mf.hi[1] = std::max(mf.hi[1], rc_q.hy); mf.hi[2] = std::max(mf.hi[2], rc_q.hz);
     mf.chunks_left--;
     if (R.mode != SM_RECALL_MOVE) return SM_OK;
     const double t0 = now_ms();
-    int rc = SM_OK;
-    if (ck.total && !mf.tmp_made) rc = open_tmp(mf, j.first, R.who);
-    if (!rc && mf.tmp) {
-        const uint32_t kept = j.n - ck.total;
-        if (ck.total && kept) {
+    bool ok = true;
+    // the temporary of a file that is about to lose its first row: the chunks before this one lost nothing and come from the
+    // file itself
+    if (rc_q.total && !mf.tmp.is_open())
+        ok = mf.tmp.open(mf.path + ".recall.tmp", sm_mapfile::Writer::UNKNOWN, mf.h.start_id, mf.h.end_id, R.who, g_err) &&
+             mf.tmp.append_head_of(mf.path, j.first, g_err);
+    if (ok && mf.tmp.is_open()) {
+        const uint32_t kept = j.n - rc_q.total;
+        if (rc_q.total && kept) {
             // (the copy stream is idle or copying the next chunk in; the kernels that wrote the staging are over)
-            HIPCK(hipMemcpyAsync(rm.h_rec[q], (const float4 *)s->d_export.get() + (size_t)q * CHUNK * 3, (size_t)kept * 48, hipMemcpyDeviceToHost, rm.copy));
+            HIPCK(hipMemcpyAsync(rm.h_rec[q], (const float4 *)s->d_export.get() + (size_t)q * CHUNK * 3, (size_t)kept * sm_mapfile::RECORD_BYTES, hipMemcpyDeviceToHost, rm.copy));
             HIPCK(hipStreamSynchronize(rm.copy));
         }
-        bool ok = kept == 0 || fwrite(rm.h_rec[q].get(), 48, kept, mf.tmp) == kept;   // (a chunk that lost nothing: as it was read)
-        mf.kept += kept;
-        if (ok && mf.chunks_left == 0) {
-            ok = fseek(mf.tmp, 0, SEEK_SET) == 0 && fwrite(&mf.kept, 4, 1, mf.tmp) == 1;
-            ok = (fclose(mf.tmp) == 0) && ok;
-            mf.tmp = nullptr;
-            mf.tmp_done = ok;
-        }
-        if (!ok) { g_err = std::string(R.who) + ": " + mf.tmp_path + " saved err!!"; rc = SM_E_ARG; }
+        ok = mf.tmp.append(rm.h_rec[q].get(), kept, g_err);      // (a chunk that lost nothing: as it was read)
+        if (ok && mf.chunks_left == 0) mf.tmp_done = ok = mf.tmp.commit(g_err);
     }
     r.stats.write_ms += (float)(now_ms() - t0);
-    return rc;
+    return ok ? SM_OK : SM_E_ARG;
 }
 
-int stream_files(Run &R)
+int stream_files(Run &R, MapStream &in)
 {
     int rc;
-    const uint32_t nj = (uint32_t)R.jobs.size();
-    for (uint32_t c = 0; c < nj; ++c) {
-        if ((rc = enqueue(R, c))) return rc;             // the host reads chunk c while the device works on chunk c - 1
-        if (c && (rc = finish(R, c - 1))) return rc;     // ... and writes what stays of chunk c - 1 while it works on chunk c
+    MapStream::Chunk cur{}, prev{};
+    for (in.begin(R.jobs); in.more(); prev = cur) {
+        if ((rc = enqueue(R, in, cur))) return rc;               // the host reads chunk c while the device works on chunk c - 1
+        if (prev.job && (rc = finish(R, in, prev))) return rc;   // ... and writes what stays of chunk c - 1 while it works on chunk c
     }
-    if (nj && (rc = finish(R, nj - 1))) return rc;
-    return SM_OK;
-}
-
-void drop_temporaries(std::vector<MapFile> &files)
-{
-    for (MapFile &mf : files) {
-        if (mf.tmp) { fclose(mf.tmp); mf.tmp = nullptr; }
-        if (mf.tmp_made) { std::remove(mf.tmp_path.c_str()); mf.tmp_made = false; }
-    }
+    return prev.job ? finish(R, in, prev) : SM_OK;
 }
 
 int check_args(sm_ctx *s, const sm_map_source *src, const float *pose16, const sm_recall_params *p, int32_t mode, const uint32_t *n,
@@ -253,14 +179,10 @@ int check_args(sm_ctx *s, const sm_map_source *src, const float *pose16, const s
     if (!s || !src || !n) { g_err = std::string(who) + ": null context, source or count"; return SM_E_ARG; }
     if (s->ss_on || s->rig_on) { g_err = std::string(who) + ": a sharded or rig context holds only its own surfels"; return SM_E_UNSUPPORTED; }
     if (src->include_model) { g_err = std::string(who) + ": include_model must be 0"; return SM_E_ARG; }
-    if (src->n_paths && !src->paths) { g_err = std::string(who) + ": null paths"; return SM_E_ARG; }
-    for (uint32_t i = 0; i < src->n_paths; ++i)
-        if (!src->paths[i]) { g_err = std::string(who) + ": null path"; return SM_E_ARG; }
+    if (int rc = check_map_source(src, who)) return rc;
     if (mode != SM_RECALL_MOVE && mode != SM_RECALL_COPY && mode != SM_RECALL_COUNT) { g_err = std::string(who) + ": unknown mode"; return SM_E_ARG; }
     if (p && !(std::isfinite(p->radius) && p->radius > 0.0f)) { g_err = std::string(who) + ": radius must be finite and > 0"; return SM_E_ARG; }
-    if (pose16)
-        for (int i = 0; i < 16; ++i)
-            if (!std::isfinite(pose16[i])) { g_err = std::string(who) + ": non-finite pose"; return SM_E_ARG; }
+    if (int rc = check_pose(pose16, who)) return rc;
     if (s->pending_cull) { g_err = std::string(who) + " between sm_stage_conflict and sm_stage_cull"; return SM_E_ARG; }
     if (mode == SM_RECALL_MOVE)
         for (uint32_t i = 0; i < src->n_paths; ++i)
@@ -293,43 +215,25 @@ int recall(sm_ctx *s, const sm_map_source *src, const float *pose16, const sm_re
     sm_recall_stats_t st{};
     st.files_listed = src->n_paths;
     std::vector<MapFile> files(src->n_paths);
-    Run R{s, who, mode, ra, 0u, files, {}, 0, nullptr, 0xFFFFFFFFu};
+    Run R{s, who, mode, ra, 0u, files, {}, 0};
+    std::vector<sm_mapfile::Header> headers(src->n_paths);   // (count 0: a file that is not read)
     const float INF = __builtin_inff();
     for (uint32_t i = 0; i < src->n_paths; ++i) {
         MapFile &mf = files[i];
         mf.path = src->paths[i];
         for (int a = 0; a < 3; ++a) { mf.lo[a] = INF; mf.hi[a] = -INF; }
-        struct stat sb;
-        if ((int64_t)i == known_far) { mf.skipped = true; st.files_skipped++; continue; }
-        if (use_index && stat(mf.path.c_str(), &sb) == 0) {
+        bool skip = (int64_t)i == known_far;
+        if (!skip && use_index && sm_mapfile::stat_of(mf.path, mf.h)) {
             auto it = r.index.find(mf.path);
-            if (it != r.index.end() && it->second.size == (uint64_t)sb.st_size && it->second.mtime_ns == mtime_of(sb) &&
-                box_out_of_reach(it->second, c3, ra.r2)) {
-                mf.skipped = true;
-                st.files_skipped++;
-                continue;
-            }
+            skip = it != r.index.end() && it->second.size == mf.h.size && it->second.mtime_ns == mf.h.mtime_ns && box_out_of_reach(it->second, c3, ra.r2);
         }
-        File f(fopen(mf.path.c_str(), "rb"));
-        if (!f) { g_err = std::string(who) + ": " + mf.path + " is not open!"; return SM_E_ARG; }
-        uint32_t hdr[3];
-        if (fread(hdr, 4, 3, f.get()) != 3 || fstat(fileno(f.get()), &sb) != 0) {
-            g_err = std::string(who) + ": " + mf.path + " read err!! (no header)"; return SM_E_ARG;
-        }
-        const uint64_t want = 12ull + 48ull * hdr[0];
-        if ((uint64_t)sb.st_size != want) {
-            g_err = std::string(who) + ": " + mf.path + " holds " + std::to_string((uint64_t)sb.st_size) + " bytes, its header's " +
-                    std::to_string(hdr[0]) + " records need " + std::to_string(want);
-            return SM_E_ARG;
-        }
-        mf.size = (uint64_t)sb.st_size; mf.mtime_ns = mtime_of(sb);
-        mf.n = hdr[0]; mf.start_id = (int32_t)hdr[1]; mf.end_id = (int32_t)hdr[2];
+        if (skip) { mf.skipped = true; st.files_skipped++; continue; }
+        if (!sm_mapfile::open_checked(mf.path, who, mf.h, g_err)) return SM_E_ARG;
+        headers[i] = mf.h;
         st.files_read++;
-        for (uint32_t first = 0; first < mf.n; first += CHUNK) {
-            R.jobs.push_back({i, first, std::min(CHUNK, mf.n - first)});
-            mf.chunks_left++;
-        }
     }
+    R.jobs = sm_mapfile::chunk_plan(headers, CHUNK);
+    for (const Job &j : R.jobs) files[j.file].chunks_left++;
 
     HIPCK(hipSetDevice(s->cfg.device));
     // COUNT leaves the model alone altogether; the others append to the rows a download would return
@@ -343,60 +247,46 @@ int recall(sm_ctx *s, const sm_map_source *src, const float *pose16, const sm_re
         if ((rc = maps_ensure_staging(s)) || (rc = ensure_scratch(s))) return rc;
         uint32_t largest = 0;
         for (const Job &j : R.jobs) largest = std::max(largest, j.n);
-        if (mode == SM_RECALL_MOVE && (rc = ensure_export(s, (size_t)CHUNK * 48 + (size_t)largest * 48))) return rc;   // two chunks of rows that stay
+        if (mode == SM_RECALL_MOVE && (rc = ensure_export(s, ((size_t)CHUNK + largest) * sm_mapfile::RECORD_BYTES))) return rc;   // two chunks of rows that stay
         HIPCK(hipMemsetAsync(r.d_run, 0, 4, s->stream));
-        rc = stream_files(R);
-        R.in.reset();                                    // (before the renames: an open handle would keep a replaced file's pages alive)
-        if (rc) {
-            (void)hipStreamSynchronize(s->maps.copy);
-            (void)hipStreamSynchronize(s->stream);
-            drop_temporaries(files);
-            return rc;
-        }
+        // (gone before the renames: an open handle would keep a replaced file's pages alive.  If the call fails, the stream drains
+        // what is in flight and the temporaries go with `files`.)
+        MapStream in(s, who, src->paths, {&r.stats.read_ms, &r.stats.copy_ms, &r.stats.device_ms});
+        if ((rc = stream_files(R, in))) return rc;
     }
     r.stats.recalled = R.total;
     *n = (uint32_t)std::min<uint64_t>(R.total, 0xFFFFFFFFull);
     // what this read has learnt goes into the index, whatever becomes of the call: the files are as they were
     auto note = [&](const MapFile &mf) {
-        Recall::Entry en{mf.size, mf.mtime_ns, {mf.lo[0], mf.lo[1], mf.lo[2]}, {mf.hi[0], mf.hi[1], mf.hi[2]}};
+        Recall::Entry en{mf.h.size, mf.h.mtime_ns, {mf.lo[0], mf.lo[1], mf.lo[2]}, {mf.hi[0], mf.hi[1], mf.hi[2]}};
         r.index[mf.path] = en;
     };
     for (const MapFile &mf : files)
         if (!mf.skipped) note(mf);
     if (mode == SM_RECALL_COUNT) { r.stats.total_ms = (float)(now_ms() - t_begin); return SM_OK; }
     if ((uint64_t)cnt + R.total > s->cap) {
-        drop_temporaries(files);
         g_err = std::string(who) + ": " + std::to_string(cnt) + " surfels + " + std::to_string(R.total) + " recalled exceed MAX_VERTICES";
         r.stats.total_ms = (float)(now_ms() - t_begin);
         return SM_E_CAPACITY;
     }
 
-    // ---- publish: the state an upload of concat(m, R) leaves, with retirement's exceptions (retire_commit)
-    DevState &d = *s->h_state;
-    d.count = cnt + (uint32_t)R.total;
-    d.offset = d.count;
-    d.garbage = 0; d.garbage_prev = 0; d.first_live = 0; d.do_compact = 0;
-    s->culls_since_compact = 0;
-    if ((rc = push_state(s)) == SM_OK && R.total) rc = rebuild_bounds(s, cnt, d.count);
-    if (rc == SM_OK) rc = pull_state(s);
-    if (rc) { drop_temporaries(files); return rc; }      // (a device error: the context is lost anyway)
+    // ---- publish: the state an upload of concat(m, R) leaves; only the tiles that hold a recalled row get new boxes
+    if ((rc = publish_dense(s, cnt + (uint32_t)R.total, cnt))) return rc;   // (a device error: the context is lost anyway)
 
     // ---- the files, last: a failure from here on leaves rows twice, never nowhere
     const double t0 = now_ms();
     for (MapFile &mf : files) {
         if (!mf.tmp_done) continue;
-        if (std::rename(mf.tmp_path.c_str(), mf.path.c_str()) != 0) {
+        if (std::rename(mf.tmp.path().c_str(), mf.path.c_str()) != 0) {
             if (rc == SM_OK) g_err = std::string(who) + ": " + mf.path + " could not be replaced; its recalled rows are in the model AND still in the file";
             rc = SM_E_ARG;
-            continue;                                    // (drop_temporaries below removes its temporary)
+            continue;                                    // (its temporary goes with `files`)
         }
-        mf.tmp_made = false;
+        mf.tmp_done = false;
         r.stats.files_rewritten++;
-        struct stat sb;
-        if (stat(mf.path.c_str(), &sb) == 0) { mf.size = (uint64_t)sb.st_size; mf.mtime_ns = mtime_of(sb); note(mf); }   // (the old box: a superset)
+        if (sm_mapfile::stat_of(mf.path, mf.h)) note(mf);   // (the old box: a superset)
         else r.index.erase(mf.path);
     }
-    drop_temporaries(files);
     r.stats.write_ms += (float)(now_ms() - t0);
     r.stats.total_ms = (float)(now_ms() - t_begin);
     return rc;
@@ -432,9 +322,9 @@ int sm_impl::recall_box_of(sm_ctx *s, const float *d_rec12, uint32_t n, float lo
 
 void sm_impl::recall_note_written(sm_ctx *s, const std::string &path, const float lo[3], const float hi[3])
 {
-    struct stat sb;
-    if (stat(path.c_str(), &sb) != 0) { s->rec.index.erase(path); return; }
-    s->rec.index[path] = Recall::Entry{(uint64_t)sb.st_size, mtime_of(sb), {lo[0], lo[1], lo[2]}, {hi[0], hi[1], hi[2]}};
+    sm_mapfile::Header h;
+    if (!sm_mapfile::stat_of(path, h)) { s->rec.index.erase(path); return; }
+    s->rec.index[path] = Recall::Entry{h.size, h.mtime_ns, {lo[0], lo[1], lo[2]}, {hi[0], hi[1], hi[2]}};
 }
 
 // The periodic policy, called by auto_retire_after_frame once that frame's retirement is complete: a MOVE recall at the frame's
@@ -448,9 +338,7 @@ int sm_impl::auto_recall_after_retire(sm_ctx *s, bool wrote_file)
     std::vector<std::string> paths(s->ret.files);
     std::vector<const char *> ptrs(s->ret.files);
     for (uint32_t i = 0; i < s->ret.files; ++i) {
-        char name[32];
-        snprintf(name, sizeof name, "_%06u.bin", i);
-        paths[i] = s->ret.prefix + name;
+        paths[i] = sm_mapfile::policy_file(s->ret.prefix, i);
         ptrs[i] = paths[i].c_str();
     }
     const sm_map_source src{ptrs.data(), s->ret.files, 0};
@@ -496,7 +384,7 @@ int sm_set_auto_recall(sm_ctx *s, const sm_recall_params *params)
     // so that the frame that recalls first allocates nothing: the staging of the stream, the scratch, two chunks of rows that stay
     HIPCK(hipSetDevice(s->cfg.device));
     int rc;
-    if ((rc = maps_ensure_staging(s)) || (rc = ensure_scratch(s)) || (rc = ensure_export(s, (size_t)CHUNK * 96))) return rc;
+    if ((rc = maps_ensure_staging(s)) || (rc = ensure_scratch(s)) || (rc = ensure_export(s, (size_t)CHUNK * 2 * sm_mapfile::RECORD_BYTES))) return rc;
     s->rec.radius = params->radius;
     return SM_OK;
 }

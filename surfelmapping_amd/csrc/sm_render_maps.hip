@@ -1,48 +1,12 @@
 // sm_render_maps.hip -- views of a map set (sm_render_image_maps, sm_render_model_maps; DESIGN.md "4f. Views of a map set"):
 // map files streamed through the two renderers in chunks, the live model last.  Kernels: sm_k_render_maps.h.
-#include "sm_ctx.h"
+#include "sm_map_stream.h"
 #include "sm_k_render_maps.h"
 
-#include <chrono>
-#include <sys/stat.h>
-
 using namespace sm;
+using sm_mapfile::now_ms;
 
 namespace {
-
-struct MapFile { const char *path; uint32_t n; };
-struct FileCloser { void operator()(FILE *f) const { if (f) fclose(f); } };
-using File = std::unique_ptr<FILE, FileCloser>;
-
-double now_ms()
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-// the headers of all files: u32 count | i32 startId | i32 endId | count * 48 bytes (src/GlobalModel.cpp:927-932)
-int scan_files(const sm_map_source *src, const char *fn, std::vector<MapFile> &files, uint64_t &total)
-{
-    for (uint32_t i = 0; i < src->n_paths; ++i) {
-        const char *path = src->paths[i];
-        if (!path) { g_err = std::string(fn) + ": null path"; return SM_E_ARG; }
-        File f(fopen(path, "rb"));
-        if (!f) { g_err = std::string(fn) + ": " + path + " is not open!"; return SM_E_ARG; }
-        uint32_t hdr[3];
-        struct stat st;
-        if (fread(hdr, 4, 3, f.get()) != 3 || fstat(fileno(f.get()), &st) != 0) {
-            g_err = std::string(fn) + ": " + path + " read err!! (no header)"; return SM_E_ARG;
-        }
-        const uint64_t want = 12ull + 48ull * hdr[0];
-        if ((uint64_t)st.st_size != want) {
-            g_err = std::string(fn) + ": " + path + " holds " + std::to_string((uint64_t)st.st_size) + " bytes, its header's " +
-                    std::to_string(hdr[0]) + " records need " + std::to_string(want);
-            return SM_E_ARG;
-        }
-        files.push_back({path, hdr[0]});
-        total += hdr[0];
-    }
-    return SM_OK;
-}
 
 // what differs between the two renderers
 struct Mode {
@@ -55,31 +19,23 @@ struct Mode {
     uint8_t *out0; uint8_t *out1; uint8_t *out2;
 };
 
-// fold the finished events of buffer b into the tally (waits for them)
-int fold_events(sm_ctx *s, int b)
-{
-    RenderMaps &rm = s->maps;
-    if (!rm.in_flight[b]) return SM_OK;
-    float ms = 0.0f;
-    HIPCK(hipEventSynchronize(rm.ev_k1[b]));
-    HIPCK(hipEventElapsedTime(&ms, rm.ev_copy0[b], rm.ev_copied[b]));
-    rm.stats.copy_ms += ms;
-    HIPCK(hipEventElapsedTime(&ms, rm.ev_k0[b], rm.ev_k1[b]));
-    rm.stats.device_ms += ms;
-    rm.in_flight[b] = false;
-    return SM_OK;
-}
-
 int render_maps(sm_ctx *s, const sm_map_source *src, const char *fn, const Mode &md)
 {
     const double t_begin = now_ms();
     if (s->ss_on) { g_err = std::string(fn) + ": a sharded context holds only its rank's surfels; rendering the union is not supported"; return SM_E_UNSUPPORTED; }
     if (s->pending_cull) { g_err = std::string(fn) + " between sm_stage_conflict and sm_stage_cull"; return SM_E_ARG; }
-    if (src->n_paths && !src->paths) { g_err = std::string(fn) + ": null paths"; return SM_E_ARG; }
-    std::vector<MapFile> files;
-    uint64_t total = 0;
-    int rc = scan_files(src, fn, files, total);
+    int rc = check_map_source(src, fn);
     if (rc) return rc;
+    // the headers of all files, each against its length, before anything else
+    std::vector<sm_mapfile::Header> files(src->n_paths);
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < src->n_paths; ++i) {
+        if (!sm_mapfile::open_checked(src->paths[i], fn, files[i], g_err)) return SM_E_ARG;
+        total += files[i].count;
+    }
+    const std::vector<sm_mapfile::Job> jobs = sm_mapfile::chunk_plan(files, RenderMaps::CHUNK);
+    std::vector<uint64_t> id_base(files.size());         // of each file's first record in the set
+    for (size_t i = 1; i < files.size(); ++i) id_base[i] = id_base[i - 1] + files[i - 1].count;
     HIPCK(hipSetDevice(s->cfg.device));
     if ((rc = ensure_compact(s))) return rc;
     if ((rc = pull_state(s))) return rc;                          // (waits for frames in flight; count is the live surfels)
@@ -129,6 +85,7 @@ int render_maps(sm_ctx *s, const sm_map_source *src, const char *fn, const Mode 
     const MapsSoA chunk{rm.d_pos_conf, rm.d_norm_rad, rm.d_color, rm.d_time};
     const SurfelSet cur = s->M.s[s->h_state->cur];
     const MapsSoA live{cur.pos_conf, cur.norm_rad, cur.color, cur.time};
+    MapStream in(s, fn, src->paths, {&rm.stats.read_ms, &rm.stats.copy_ms, &rm.stats.device_ms});
 
     for (uint32_t v0 = 0; v0 < md.n_views; v0 += B) {
         const uint32_t b = std::min(B, md.n_views - v0);
@@ -152,48 +109,28 @@ int render_maps(sm_ctx *s, const sm_map_source *src, const char *fn, const Mode 
         fill_keys(s, d_key, bp);
 
         // ---- the files, chunk by chunk: the host reads chunk c + 1 while the copy and the kernels of chunk c run
-        uint32_t c = 0;                                  // chunk index within the pass
-        uint64_t id_base = 0;
-        for (const MapFile &mf : files) {
-            if (!mf.n) continue;
-            File f(fopen(mf.path, "rb"));
-            if (!f || fseek(f.get(), 12, SEEK_SET) != 0) { (void)hipDeviceSynchronize(); g_err = std::string(fn) + ": " + mf.path + " is not open!"; return SM_E_ARG; }
-            for (uint32_t first = 0; first < mf.n; first += RenderMaps::CHUNK, ++c) {
-                const uint32_t n = std::min(RenderMaps::CHUNK, mf.n - first);
-                const int q = (int)(c & 1u);
-                if ((rc = fold_events(s, q))) return rc;              // (the copy out of h_rec[q] two chunks ago is over as well)
-                const double t0 = now_ms();
-                const size_t got = fread(rm.h_rec[q].get(), 48, n, f.get());
-                rm.stats.read_ms += (float)(now_ms() - t0);
-                if (got != n) { (void)hipDeviceSynchronize(); g_err = std::string(fn) + ": " + mf.path + " read err!!"; return SM_E_ARG; }
-                HIPCK(hipStreamWaitEvent(rm.copy, rm.ev_free[q], 0));     // (never recorded: no wait)
-                HIPCK(hipEventRecord(rm.ev_copy0[q], rm.copy));
-                HIPCK(hipMemcpyAsync(rm.d_rec[q], rm.h_rec[q], (size_t)n * 48, hipMemcpyHostToDevice, rm.copy));
-                HIPCK(hipEventRecord(rm.ev_copied[q], rm.copy));
-                HIPCK(hipStreamWaitEvent(s->stream, rm.ev_copied[q], 0));
-                HIPCK(hipEventRecord(rm.ev_k0[q], s->stream));
-                const unsigned nblk = (n + MAPS_BLOCK - 1) / MAPS_BLOCK;
-                hipLaunchKernelGGL(k_maps_intake, dim3(nblk), dim3(256), 0, s->stream, (const float4 *)rm.d_rec[q].get(), n, chunk, rm.d_box.get());
-                HIPCK(hipEventRecord(rm.ev_free[q], s->stream));
-                HIPCK(hipMemsetAsync(d_hit + v0, 0, b, s->stream));
-                const uint32_t gid = (uint32_t)(id_base + first);
-                if (md.image)
-                    hipLaunchKernelGGL(k_maps_splat_image, dim3(nblk, b), dim3(256), 0, s->stream, chunk, n, gid, (const float4 *)rm.d_box.get(), d_rp,
-                                       d_key, npix, cull, d_skip + v0, d_hit + v0);
-                else
-                    hipLaunchKernelGGL(k_maps_splat_view, dim3(nblk, b), dim3(256), 0, s->stream, chunk, n, gid, (const float4 *)rm.d_box.get(), d_vp,
-                                       d_key, npix, cull, d_skip + v0, d_hit + v0);
-                resolve(chunk, gid, n);
-                HIPCK(hipEventRecord(rm.ev_k1[q], s->stream));
-                HIPCK(hipGetLastError());
-                rm.in_flight[q] = true;
-                rm.stats.surfels_read += n;
-                rm.stats.chunks++;
-                if (cull) rm.stats.pairs_tested += (uint64_t)nblk * b;
-            }
-            id_base += mf.n;
+        for (in.begin(jobs); in.more();) {
+            MapStream::Chunk ck;
+            if ((rc = in.next(ck))) return rc;
+            const uint32_t n = ck.job->n;
+            const unsigned nblk = (n + MAPS_BLOCK - 1) / MAPS_BLOCK;
+            hipLaunchKernelGGL(k_maps_intake, dim3(nblk), dim3(256), 0, s->stream, ck.d_rec, n, chunk, rm.d_box.get());
+            HIPCK(hipMemsetAsync(d_hit + v0, 0, b, s->stream));
+            const uint32_t gid = (uint32_t)(id_base[ck.job->file] + ck.job->first);
+            if (md.image)
+                hipLaunchKernelGGL(k_maps_splat_image, dim3(nblk, b), dim3(256), 0, s->stream, chunk, n, gid, (const float4 *)rm.d_box.get(), d_rp,
+                                   d_key, npix, cull, d_skip + v0, d_hit + v0);
+            else
+                hipLaunchKernelGGL(k_maps_splat_view, dim3(nblk, b), dim3(256), 0, s->stream, chunk, n, gid, (const float4 *)rm.d_box.get(), d_vp,
+                                   d_key, npix, cull, d_skip + v0, d_hit + v0);
+            resolve(chunk, gid, n);
+            if ((rc = in.done(ck.q))) return rc;
+            HIPCK(hipGetLastError());
+            rm.stats.surfels_read += n;
+            rm.stats.chunks++;
+            if (cull) rm.stats.pairs_tested += (uint64_t)nblk * b;
         }
-        if ((rc = fold_events(s, 0)) || (rc = fold_events(s, 1))) return rc;
+        if ((rc = in.fold(0)) || (rc = in.fold(1))) return rc;
 
         // ---- the live model, by the resident kernels with an id base
         if (cnt) {
@@ -247,9 +184,9 @@ int sm_impl::maps_ensure_staging(sm_ctx *s)
     HIPCK(hipStreamCreateWithFlags(copy.put(), hipStreamNonBlocking));
     const size_t N = RenderMaps::CHUNK;
     for (int b = 0; b < 2; ++b) {
-        HIPCK(hipHostMalloc((void **)rm.h_rec[b].put(), N * 48, hipHostMallocDefault));
-        HIPCK(hipMalloc(rm.d_rec[b].put(), N * 48));
-        for (Event *e : {&rm.ev_copy0[b], &rm.ev_copied[b], &rm.ev_free[b], &rm.ev_k0[b], &rm.ev_k1[b]}) HIPCK(hipEventCreate(e->put()));
+        HIPCK(hipHostMalloc((void **)rm.h_rec[b].put(), N * sm_mapfile::RECORD_BYTES, hipHostMallocDefault));
+        HIPCK(hipMalloc(rm.d_rec[b].put(), N * sm_mapfile::RECORD_BYTES));
+        for (Event *e : {&rm.ev_copy0[b], &rm.ev_copied[b], &rm.ev_k0[b], &rm.ev_k1[b]}) HIPCK(hipEventCreate(e->put()));
     }
     int rc;
     if ((rc = dalloc(rm.d_pos_conf, N)) || (rc = dalloc(rm.d_norm_rad, N)) || (rc = dalloc(rm.d_color, N)) || (rc = dalloc(rm.d_time, N)) ||

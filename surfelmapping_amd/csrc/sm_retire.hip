@@ -2,8 +2,8 @@
 // leave the model for a caller's buffer or a map file, and the existing compaction closes the gaps.  Kernels: sm_k_retire.h.
 #include "sm_ctx.h"
 #include "sm_k_retire.h"
+#include "sm_mapfile.h"
 
-#include <cmath>
 #include <cstdlib>
 
 using namespace sm;
@@ -32,11 +32,17 @@ int check_args(sm_ctx *s, const float *pose16, const sm_retire_params *p, const 
         return SM_E_UNSUPPORTED;
     }
     if (p && (p->min_age < 0 || !std::isfinite(p->min_distance))) { g_err = std::string(who) + ": bad parameters"; return SM_E_ARG; }
-    if (pose16)
-        for (int i = 0; i < 16; ++i)
-            if (!std::isfinite(pose16[i])) { g_err = std::string(who) + ": non-finite pose"; return SM_E_ARG; }
+    if (int rc = check_pose(pose16, who)) return rc;
     if (s->pending_cull) { g_err = std::string(who) + " between sm_stage_conflict and sm_stage_cull"; return SM_E_ARG; }
     return SM_OK;
+}
+
+sm_retire_params params_or_default(sm_ctx *s, const sm_retire_params *params)
+{
+    sm_retire_params p;
+    if (params) p = *params;
+    else sm_default_retire_params(&s->cfg, &p);
+    return p;
 }
 
 int ensure_scratch(sm_ctx *s)
@@ -60,9 +66,7 @@ int ensure_scratch(sm_ctx *s)
 // the frames in flight; changes nothing in the model.
 int retire_mark(sm_ctx *s, const float *pose16, const sm_retire_params *params, uint32_t *n)
 {
-    sm_retire_params p;
-    if (params) p = *params;
-    else sm_default_retire_params(&s->cfg, &p);
+    const sm_retire_params p = params_or_default(s, params);
     const float *pose = pose16 ? pose16 : s->last_pose;
     int rc = ensure_scratch(s);
     if (rc) return rc;
@@ -101,18 +105,13 @@ int retire_gather_host(sm_ctx *s, float *dst12, uint32_t n)
     int rc = tic(s, 3);
     if (rc) return rc;
     if (n && (rc = ensure_export(s, (size_t)std::min(n, CHUNK) * 48))) return rc;
-    for (uint32_t first = 0; first < n; first += CHUNK) {
-        const uint32_t m = std::min(CHUNK, n - first);
-        launch_gather(s, (float *)s->d_export.get(), first, first + m);
-        HIPCK(hipGetLastError());
-        HIPCK(hipMemcpyAsync(dst12 + (size_t)first * 12, s->d_export, (size_t)m * 48, hipMemcpyDeviceToHost, s->stream));
-        HIPCK(hipStreamSynchronize(s->stream));
-    }
+    if ((rc = drain_export(s, n, CHUNK, dst12, 12, [s](float *d, uint32_t first, uint32_t m) { launch_gather(s, d, first, first + m); }, no_hook)))
+        return rc;
     return tic(s, 4);
 }
 
-// Step 4: the retired become dead slots, the compaction that exists squeezes them out, the state is what an upload of the
-// kept surfels would leave (sm_upload_model_aos), the tile boxes are rebuilt
+// Step 4: the retired become dead slots, the compaction that exists squeezes them out, and the kept surfels are published as
+// an upload of them would be (publish_dense: the state, the compaction schedule, the tile boxes)
 int retire_commit(sm_ctx *s, uint32_t n)
 {
     int rc = tic(s, 5);
@@ -126,16 +125,11 @@ int retire_commit(sm_ctx *s, uint32_t n)
     }
     if ((rc = ensure_compact(s))) return rc;
     if ((rc = pull_state(s))) return rc;
-    DevState &d = *s->h_state;
-    d.offset = d.count;
-    d.garbage = 0; d.garbage_prev = 0; d.first_live = 0; d.do_compact = 0;
-    s->culls_since_compact = 0;                  // the compaction schedule restarts, as after an upload
-    if ((rc = push_state(s))) return rc;
     if ((rc = tic(s, 6))) return rc;
-    if ((rc = rebuild_bounds(s, 0, d.count))) return rc;
+    if ((rc = publish_dense(s, s->h_state->count, 0))) return rc;
     if ((rc = tic(s, 7))) return rc;
     if (s->ret.timed) { HIPCK(hipStreamSynchronize(s->stream)); s->ret.stats_valid = true; }
-    return pull_state(s);
+    return SM_OK;
 }
 
 int retire_common(sm_ctx *s, const float *pose16, const sm_retire_params *params, float *dst, bool device, uint32_t cap, uint32_t *n,
@@ -171,41 +165,26 @@ int sm_impl::auto_retire_after_frame(sm_ctx *s)
     if (rc) return rc;
     if ((rc = tic(s, 3))) return rc;
     if (n) {
-        // u32 count | i32 startId | i32 endId | count*12 f32   (src/GlobalModel.cpp:927-932), on disk BEFORE the model changes;
-        // one chunk at a time through pinned staging, so that a large retirement needs neither a host copy of its own nor
-        // gigabytes of staging
-        if (!r.h_stage) HIPCK(hipHostMalloc(r.h_stage.put(), (size_t)FILE_CHUNK * 48, hipHostMallocDefault));
-        if ((rc = ensure_export(s, (size_t)std::min(n, FILE_CHUNK) * 48))) return rc;
-        char name[32];
-        snprintf(name, sizeof name, "_%06u.bin", r.files);
-        const std::string path = r.prefix + name;
-        const int32_t start_id = r.last_tick, end_id = s->tick - 1;
+        // the map file (sm_mapfile.h) is on disk BEFORE the model changes; one chunk at a time through pinned staging, so that a
+        // large retirement needs neither a host copy of its own nor gigabytes of staging
+        if (!r.h_stage) HIPCK(hipHostMalloc(r.h_stage.put(), (size_t)FILE_CHUNK * sm_mapfile::RECORD_BYTES, hipHostMallocDefault));
+        if ((rc = ensure_export(s, (size_t)std::min(n, FILE_CHUNK) * sm_mapfile::RECORD_BYTES))) return rc;
+        const std::string path = sm_mapfile::policy_file(r.prefix, r.files);
         // sm_set_auto_recall: the file index learns the file's box now, from the records on the device, so that no recall has
         // to read the file only to find out where it lies
         const bool want_box = s->rec.radius > 0.0f;
         const float INF = __builtin_inff();
         float lo[3] = {INF, INF, INF}, hi[3] = {-INF, -INF, -INF};
-        FILE *f = fopen(path.c_str(), "wb");
-        if (!f) { g_err = path + " is not open!"; return SM_E_ARG; }
-        bool ok = fwrite(&n, 4, 1, f) == 1 && fwrite(&start_id, 4, 1, f) == 1 && fwrite(&end_id, 4, 1, f) == 1;
-        hipError_t he = hipSuccess;
-        for (uint32_t first = 0; ok && he == hipSuccess && first < n; first += FILE_CHUNK) {
-            const uint32_t m = std::min(FILE_CHUNK, n - first);
-            launch_gather(s, (float *)s->d_export.get(), first, first + m);
-            if ((he = hipGetLastError()) == hipSuccess)
-                he = hipMemcpyAsync(r.h_stage, s->d_export, (size_t)m * 48, hipMemcpyDeviceToHost, s->stream);
-            if (he == hipSuccess) he = hipStreamSynchronize(s->stream);
-            if (he == hipSuccess && want_box && (rc = recall_box_of(s, (const float *)s->d_export.get(), m, lo, hi))) { ok = false; break; }
-            if (he == hipSuccess) ok = fwrite(r.h_stage, 48, m, f) == m;
-        }
-        ok = (fclose(f) == 0) && ok;
-        if (he != hipSuccess || !ok) {
-            std::remove(path.c_str());           // no half-written map file is left behind
-            if (rc) return rc;                   // (recall_box_of: a device error, g_err is set)
-            if (he != hipSuccess) { set_err("retirement into a map file", he, __FILE__, __LINE__); return SM_E_HIP; }
-            g_err = path + " saved err!!";
-            return SM_E_ARG;
-        }
+        sm_mapfile::Writer w;                    // (no half-written map file is left behind: a return below removes it)
+        if (!w.open(path, n, r.last_tick, s->tick - 1, nullptr, g_err)) return SM_E_ARG;
+        rc = drain_export(s, n, FILE_CHUNK, r.h_stage, 0, [s](float *d, uint32_t first, uint32_t m) { launch_gather(s, d, first, first + m); },
+                          [&](uint32_t, uint32_t m) -> int {
+                              if (want_box)
+                                  if (int rb = recall_box_of(s, (const float *)s->d_export.get(), m, lo, hi)) return rb;
+                              return w.append(r.h_stage, m, g_err) ? SM_OK : SM_E_ARG;
+                          });
+        if (rc) return rc;
+        if (!w.commit(g_err)) return SM_E_ARG;
         if (want_box) recall_note_written(s, path, lo, hi);
         r.files++;
         r.surfels += n;
@@ -240,9 +219,7 @@ int sm_retire_device(sm_ctx *s, const float *pose16, const sm_retire_params *par
 int sm_set_auto_retire(sm_ctx *s, const sm_retire_params *params, int32_t every, const char *path_prefix)
 {
     if (!s) return SM_E_ARG;
-    sm_retire_params p;
-    if (params) p = *params;
-    else sm_default_retire_params(&s->cfg, &p);
+    const sm_retire_params p = params_or_default(s, params);
     int rc = check_args(s, nullptr, &p, "sm_set_auto_retire");
     if (rc) return rc;
     Retire &r = s->ret;
@@ -266,7 +243,7 @@ int sm_auto_retire_stats(sm_ctx *s, uint32_t *files, uint64_t *surfels)
 
 // diagnostic, not part of the C-ABI header: device times in ms of the last retirement made with SM_RETIRE_TIMING=1 in the
 // environment when the context retired first -- mark, scan, gather (with the copies of its chunks when the destination is host
-// memory), clear + compaction, tile bounds; -1 each if that call was not timed or ended before the model changed
+// memory), clear + compaction, the publication of the kept surfels (state and tile bounds); -1 each if that call was not timed or ended before the model changed
 int sm_debug_retire_stats(sm_ctx *s, float *ms5)
 {
     if (!s || !ms5) return SM_E_ARG;

@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define SM_API_VERSION 4   /* bumped whenever a struct or an entry point changes (3, 4: round 3 -- asynchronous host path, rig step, sm_timings::k_scan_own, sm_host_alloc_frame; the staged shard entry points are gone).  Purely additive changes keep it: sm_model_view / sm_render_model*, sm_track_* and sm_track_*rgb* were added at 4, no existing struct or entry point changed. */
+#define SM_API_VERSION 4   /* bumped whenever a struct or an entry point changes (3, 4: round 3 -- asynchronous host path, rig step, sm_timings::k_scan_own, sm_host_alloc_frame; the staged shard entry points are gone).  Purely additive changes keep it: sm_model_view / sm_render_model*, sm_track_* and sm_track_*rgb* were added at 4, as were sm_warp_by_time / sm_loop_spread / sm_track_*_old / sm_close_loop: no existing struct or entry point changed. */
 
 /* error codes (reference: void returns + CheckGlDieOnError(); bool for map IO) */
 enum {
@@ -516,6 +516,92 @@ int sm_recall_stats(sm_ctx *s, sm_recall_stats_t *out);
  * without the policy.  params NULL or radius <= 0: off (the default). */
 int sm_set_auto_recall(sm_ctx *s, const sm_recall_params *params);
 int sm_auto_recall_stats(sm_ctx *s, uint32_t *rounds, uint64_t *surfels);    /* recalls made by the policy; surfels they brought back */
+
+/* ---- closing loops: the map warped by surfel time (DESIGN.md "4h. Closing loops") ----
+ * A camera that tracks its own pose drifts; when it returns to a place it has mapped, the error it has gathered since is a
+ * world->world correction that is fully due now and not at all when it left.  Every surfel record carries its last-update time
+ * (m[7]), so a correction that is a function of that time can be applied to the live model and to map files alike.
+ * corr12 is n rows of 12 floats: row k is the ROW-major 3x4 world->world transform [R|t] for tick t0 + k (C[0..3] = the first row
+ * of R, then t.x) -- the one exception to "column-major float[16]" in this header.
+ * Row rule.  For a record m (a row of sm_download_model_aos, or of a map file), in fp32 without fused multiply-add, in this order:
+ *     tau = m[7];  sel = tau >= float(t0)                                  (false on a NaN)
+ *     d   = tau - float(t0);  k = d >= float(n-1) ? n-1 : (uint32)d         (truncation; +inf -> n-1)
+ *     C   = corr12[k]
+ *     m'[0] = ((C[0]*m[0] + C[1]*m[1]) + C[2]*m[2]) + C[3]                  (m'[1] from C[4..7], m'[2] from C[8..11])
+ *     m'[8] = ( C[0]*m[8] + C[1]*m[9]) + C[2]*m[10]                         (m'[9], m'[10] likewise: no translation, no renormalisation)
+ * Every other field of a selected row and every field of an unselected row is bit-identical afterwards; the order is unchanged.
+ * The transform is applied as given: rigidity is the caller's business (sm_loop_spread makes rigid tables).
+ * Model (src->include_model == 1).  Warped in place, live surfels only: the result is defined on the rows of sm_download_model_aos
+ *   and is the same for every compact_period.  The tile boxes are rebuilt for the whole model; the index map is not redrawn; count,
+ *   offset, tick, the other counters, the frame log and the compaction schedule are untouched.  Synchronous: waits for frames in
+ *   flight and flushes a held-back association, like sm_retire.  The context's stored poses move with the model: the pose of the
+ *   last processed frame (both copies: the one sm_retire / sm_recall default to and the moving-object filter's "last pose") and the
+ *   tracker's history (tick - 1 and tick - 2).  A stored pose P of tick T is selected by the row rule with tau = float(T) and becomes
+ *   C * P, the product computed in double from the widened floats and rounded to float once -- so the next constant-velocity guess
+ *   and the filter's relative pose live in the corrected world.
+ * Files.  Each listed file is streamed through the device in chunks, its rows warped there and copied back.  A file with at least
+ *   one selected row is rewritten through "<path>.warp.tmp" in the same directory, header (count, startId, endId) unchanged; a
+ *   file with none is not rewritten (bytes and mtime unchanged).  Durability, in sm_recall MOVE's order: all temporaries are
+ *   complete; then the model is warped; then each temporary is renamed over its file.  A temporary that cannot be written: all
+ *   temporaries are removed, SM_E_ARG, nothing has changed.  A rename that fails AFTER the model was warped: SM_E_ARG names the
+ *   file, the other files are still renamed, and that file's temporary is LEFT IN PLACE -- it holds the warped rows the model now
+ *   agrees with, so an operator finishes the job with one mv "<path>.warp.tmp" "<path>"; until then the file holds the unwarped world.
+ * File index.  sm_recall's index also remembers the largest non-NaN m[7] of every file a recall or a warp has read or the
+ *   retirement policy has written: a listed file whose stat() still matches and whose largest time is below t0 is neither opened
+ *   nor read, so a loop closed late in a long drive touches only the recent files.  A rewritten file's entry is refreshed (size,
+ *   mtime, the box of the warped rows).  SM_RECALL_NO_INDEX=1 turns this off too (the results are the same either way).
+ * Errors.  SM_E_ARG: NULL ctx / src / corr12, n == 0, a non-finite table entry, NULL paths with n_paths > 0, a NULL path, a path
+ *   listed twice, a file whose length disagrees with its header (all files are checked before anything changes), a call between
+ *   sm_stage_conflict and sm_stage_cull.  SM_E_UNSUPPORTED: a sharded or rig context.  An empty source is a valid no-op. */
+typedef struct sm_warp_stats_t {
+    uint32_t files_listed, files_skipped, files_read, files_rewritten;   /* paths given; left unopened by the index; streamed; renamed over */
+    uint64_t records_read, records_moved;   /* records of the files read; of them, selected */
+    uint32_t model_moved, chunks;           /* live surfels selected; chunks (at most 2^20 records) copied to the device */
+    float read_ms, copy_ms, device_ms, write_ms, total_ms;   /* fread; host-to-device copies; kernels (files and model); temporaries and renames; the call */
+} sm_warp_stats_t;
+int sm_warp_by_time(sm_ctx *s, const sm_map_source *src, int32_t t0, uint32_t n, const float *corr12);
+/* of the context's last sm_warp_by_time; SM_E_ARG before the first */
+int sm_warp_stats(sm_ctx *s, sm_warp_stats_t *out);
+
+/* The table for a loop closure.  D16 (column-major 4x4, world->world) is the correction that is fully due at tick t_b and not at
+ * all at t_a; corr12 receives t_b - t_a + 1 rows.  All in double: phi = log(R_D) (axis-angle), w_k = k / (t_b - t_a),
+ * R_k = exp(w_k * phi) by Rodrigues' formula, t_k = w_k * t_D; row k = [R_k | t_k] rounded to float once; row 0 is exactly the
+ * identity.  (Rotation and translation are interpolated separately, on purpose: the simplest rule a restatement can pin.)  Host
+ * only, no device call.  SM_E_ARG: a NULL argument, t_b <= t_a, a non-finite D, a rotation part farther than 1e-3 from
+ * orthonormal (max |R^T R - I|, or det < 0), a rotation angle above pi - 1e-3. */
+int sm_loop_spread(const float *D16, int32_t t_a, int32_t t_b, float *corr12);
+
+/* The loop measurement: sm_track_frame in every rule, except that the prediction holds only surfels with m[7] <= float(max_time)
+ * (false on a NaN) -- the map as it was before the drift, which index_map.vert:45 no longer draws for fusion but a recall has
+ * brought back.  With max_time = INT32_MAX there is no window: pose and info equal sm_track_frame's bit for bit.  anchor_time
+ * (may be NULL) receives the largest m[7] among the surfels the prediction holds, or -1 with none.  No surfel of the window in
+ * view: SM_TRACK_NO_MODEL.  sm_track_debug_old is sm_track_debug with the same window.  (sm_track_frame_rgb has no such form.) */
+int sm_track_frame_old(sm_ctx *s, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params, int32_t max_time,
+                       float *pose16_out, sm_track_info *info, float *anchor_time);
+int sm_track_debug_old(sm_ctx *s, const uint16_t *depth_mm, const float *pose16_eval, int32_t max_time, int32_t *pred_slot, double *sys29);
+
+/* The policy: notice that the camera is back, measure the error, pull the map straight.  pose16 is where the caller believes the
+ * camera is (sm_track_frame's answer, say); src lists the map files that are to move with the model (include_model is taken as 1).
+ *   1. max_time = tick - 1 - min_age;  T_old = sm_track_frame_old(depth, guess = pose16, tp, max_time).  SM_TRACK_NO_MODEL gives
+ *      SM_LOOP_NO_OLD_MAP, any other failure SM_LOOP_TRACK_FAILED.
+ *   2. D = T_old * pose16^-1 (the rigid inverse [R^T | -R^T t]), in double, rounded to float once: info->D.  Its size is judged
+ *      at the camera: trans = |centre of T_old - centre of pose16|, rot = the angle of D's rotation.  trans < min_trans and
+ *      rot < min_rot_deg: SM_LOOP_NONE.  trans > max_trans or rot > max_rot_deg: SM_LOOP_REJECTED.
+ *   3. In every case so far nothing has changed and pose16_out = pose16.  Otherwise t_a = int(anchor_time), t_b = tick - 1, the
+ *      table is sm_loop_spread(info->D, t_a, t_b), sm_warp_by_time(src, t_a + 1, t_b - t_a, table + 12) moves model, poses and files
+ *      (the table without its identity row: the same row for every surfel newer than the anchor, while the surfels OF the anchor
+ *      time keep their bits -- an identity row would still turn a -0.0 into +0.0), and pose16_out = D * pose16 (in double from the
+ *      widened floats, rounded once): SM_LOOP_CLOSED.
+ * Everything last touched up to the anchor time is the old world and stays put, bit for bit; everything after slides along the ramp.
+ * Returns SM_OK with the outcome in info->status (info may not be NULL); SM_E_ARG / SM_E_UNSUPPORTED as sm_track_frame_old and
+ * sm_warp_by_time, and SM_E_ARG for min_age < 1 or a negative or non-finite bound.  tp, lp NULL = defaults. */
+typedef struct sm_loop_params { int32_t min_age; float min_trans, min_rot_deg, max_trans, max_rot_deg; } sm_loop_params;
+     /* defaults: time_delta; 0.02 m, 0.05 deg; 2 m, 10 deg */
+typedef struct sm_loop_info { int32_t status; sm_track_info track; float D[16]; int32_t t_a, t_b; } sm_loop_info;
+enum { SM_LOOP_CLOSED = 0, SM_LOOP_NONE = 1, SM_LOOP_NO_OLD_MAP = 2, SM_LOOP_TRACK_FAILED = 3, SM_LOOP_REJECTED = 4 };
+int sm_default_loop_params(const sm_config *c, sm_loop_params *p);
+int sm_close_loop(sm_ctx *s, const uint16_t *depth_mm, const float *pose16, const sm_map_source *src, const sm_track_params *tp,
+                  const sm_loop_params *lp, float *pose16_out, sm_loop_info *info);
 
 /* ---- per-pass entry points (GlobalModel / IndexMap methods), synchronous ---- */
 /* Upload RGB / metric depth / semantic textures directly (bypasses p0). */

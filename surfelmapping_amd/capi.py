@@ -35,6 +35,8 @@ SYMBOLS = (
     "sm_default_track_rgb_params", "sm_track_frame_rgb", "sm_track_rgb_debug",
     "sm_default_retire_params", "sm_retire", "sm_retire_device", "sm_set_auto_retire", "sm_auto_retire_stats",
     "sm_default_recall_params", "sm_recall", "sm_recall_stats", "sm_set_auto_recall", "sm_auto_recall_stats",
+    "sm_warp_by_time", "sm_warp_stats", "sm_loop_spread", "sm_track_frame_old", "sm_track_debug_old",
+    "sm_default_loop_params", "sm_close_loop",
 )
 
 SM_COLL_SUM, SM_COLL_MIN, SM_COLL_GATHER = 0, 1, 2
@@ -202,6 +204,55 @@ def recall_params(cfg, **over) -> SmRecallParams:
             raise KeyError(k)
         setattr(p, k, v)
     return p
+
+
+class SmWarpStats(C.Structure):
+    _fields_ = [("files_listed", C.c_uint32), ("files_skipped", C.c_uint32), ("files_read", C.c_uint32), ("files_rewritten", C.c_uint32),
+                ("records_read", C.c_uint64), ("records_moved", C.c_uint64), ("model_moved", C.c_uint32), ("chunks", C.c_uint32),
+                ("read_ms", C.c_float), ("copy_ms", C.c_float), ("device_ms", C.c_float), ("write_ms", C.c_float), ("total_ms", C.c_float)]
+
+
+SM_LOOP_CLOSED, SM_LOOP_NONE, SM_LOOP_NO_OLD_MAP, SM_LOOP_TRACK_FAILED, SM_LOOP_REJECTED = 0, 1, 2, 3, 4
+LOOP_STATUS = {SM_LOOP_CLOSED: "CLOSED", SM_LOOP_NONE: "NONE", SM_LOOP_NO_OLD_MAP: "NO_OLD_MAP", SM_LOOP_TRACK_FAILED: "TRACK_FAILED",
+               SM_LOOP_REJECTED: "REJECTED"}
+
+
+class SmLoopParams(C.Structure):
+    _fields_ = [("min_age", C.c_int32), ("min_trans", C.c_float), ("min_rot_deg", C.c_float), ("max_trans", C.c_float),
+                ("max_rot_deg", C.c_float)]
+
+
+class SmLoopInfo(C.Structure):
+    _fields_ = [("status", C.c_int32), ("track", SmTrackInfo), ("D", C.c_float * 16), ("t_a", C.c_int32), ("t_b", C.c_int32)]
+
+
+def loop_params(cfg, **over) -> SmLoopParams:
+    """sm_default_loop_params of a config (min_age = time_delta; 0.02 m, 0.05 deg; 2 m, 10 deg) with fields overridden"""
+    p = SmLoopParams()
+    load().sm_default_loop_params(C.byref(cfg), C.byref(p))
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+def _track_info_dict(info) -> dict:
+    return dict(status=TRACK_STATUS.get(info.status, str(info.status)), status_code=int(info.status), iterations=int(info.iterations),
+                inliers=int(info.inliers), rmse=float(info.rmse), guess=np.array(info.guess[:], np.float32).reshape(4, 4).T.copy())
+
+
+def loop_spread(D, t_a, t_b) -> np.ndarray:
+    """sm_loop_spread: the table float32[t_b - t_a + 1][12] (row-major 3x4 [R|t] per tick) that ramps the world->world correction D
+    (4x4, numpy row/col indexing, or float32[16] column-major) from nothing at tick t_a to all of it at t_b.  Host only."""
+    L = load()
+    d = _mat16(D)
+    t_a, t_b = int(t_a), int(t_b)
+    out = np.zeros((max(t_b - t_a + 1, 1), 12), np.float32)
+    rc = L.sm_loop_spread(_ptr(d), t_a, t_b, _ptr(out))
+    if rc != SM_OK:
+        raise SurfelMapError("sm_loop_spread", rc, L.sm_last_error().decode())
+    return out
 
 
 def _mat16(m):
@@ -384,6 +435,14 @@ def load():
     L.sm_recall_stats.argtypes = [vp, C.POINTER(SmRecallStats)]
     L.sm_set_auto_recall.argtypes = [vp, C.POINTER(SmRecallParams)]
     L.sm_auto_recall_stats.argtypes = [vp, u32p, C.POINTER(C.c_uint64)]
+    L.sm_warp_by_time.argtypes = [vp, C.POINTER(SmMapSource), C.c_int32, C.c_uint32, vp]
+    L.sm_warp_stats.argtypes = [vp, C.POINTER(SmWarpStats)]
+    L.sm_loop_spread.argtypes = [vp, C.c_int32, C.c_int32, vp]
+    L.sm_track_frame_old.argtypes = [vp, vp, vp, C.POINTER(SmTrackParams), C.c_int32, vp, C.POINTER(SmTrackInfo), C.POINTER(C.c_float)]
+    L.sm_track_debug_old.argtypes = [vp, vp, vp, C.c_int32, vp, vp]
+    L.sm_default_loop_params.argtypes = [C.POINTER(SmConfig), C.POINTER(SmLoopParams)]
+    L.sm_close_loop.argtypes = [vp, vp, vp, C.POINTER(SmMapSource), C.POINTER(SmTrackParams), C.POINTER(SmLoopParams), vp,
+                                C.POINTER(SmLoopInfo)]
     for name in SYMBOLS:
         getattr(L, name)          # AttributeError here = the library does not match the header
     _lib = L
@@ -724,6 +783,70 @@ class SurfelMap:
         r, n = C.c_uint32(), C.c_uint64()
         self._chk(self._L.sm_auto_recall_stats(self._h, C.byref(r), C.byref(n)), "sm_auto_recall_stats")
         return int(r.value), int(n.value)
+
+    # -- closing loops (sm_warp_by_time)
+    def warp_by_time(self, paths, t0, corr, include_model=True):
+        """Move every surfel whose last-update time tau is >= t0 by row min(int(tau - t0), n - 1) of `corr` (float32[n][12], each
+        row a row-major 3x4 world->world [R|t]): the records of the map files `paths` (rewritten in place where a row moved)
+        and, with include_model, the live model and the context's stored poses (sm_warp_by_time)."""
+        corr = np.ascontiguousarray(corr, np.float32).reshape(-1, 12)
+        src = map_source(paths, include_model=include_model)
+        self._chk(self._L.sm_warp_by_time(self._h, C.byref(src), int(t0), len(corr), _ptr(corr)), "sm_warp_by_time")
+
+    def warp_stats(self) -> dict:
+        """of the last warp_by_time: files_listed, files_skipped (by the file index), files_read, files_rewritten, records_read,
+        records_moved, model_moved, chunks, read_ms, copy_ms, device_ms, write_ms, total_ms"""
+        st = SmWarpStats()
+        self._chk(self._L.sm_warp_stats(self._h, C.byref(st)), "sm_warp_stats")
+        return {k: getattr(st, k) for k, _ in SmWarpStats._fields_}
+
+    def track_old(self, depth, max_time, guess=None, **params):
+        """track() against the map as it was: the prediction holds only surfels last updated at or before max_time
+        (sm_track_frame_old).  Returns (pose, info) as track(), with info["anchor_time"] = the newest time the prediction holds
+        (-1: none)."""
+        depth = np.ascontiguousarray(depth, np.uint16)
+        assert depth.size == self.P, depth.shape
+        g = None if guess is None else _mat16(guess)
+        p = track_params(**params) if params else None
+        out = np.zeros(16, np.float32)
+        info, anchor = SmTrackInfo(), C.c_float()
+        self._chk(self._L.sm_track_frame_old(self._h, _ptr(depth), _ptr(g), C.byref(p) if p is not None else None, int(max_time), _ptr(out),
+                                             C.byref(info), C.byref(anchor)), "sm_track_frame_old")
+        d = _track_info_dict(info)
+        d["anchor_time"] = float(anchor.value)
+        return out.reshape(4, 4).T.copy(), d
+
+    def track_debug_old(self, depth, pose_eval, max_time):
+        """track_debug() with track_old()'s window (sm_track_debug_old)"""
+        depth = np.ascontiguousarray(depth, np.uint16)
+        assert depth.size == self.P, depth.shape
+        pe = _mat16(pose_eval)
+        pred = np.zeros((self.H, self.W), np.int32)
+        sys29 = np.zeros(29, np.float64)
+        self._chk(self._L.sm_track_debug_old(self._h, _ptr(depth), _ptr(pe), int(max_time), _ptr(pred), _ptr(sys29)), "sm_track_debug_old")
+        return pred, sys29
+
+    def close_loop(self, depth, pose, paths=(), **params):
+        """Notice that the camera is back in mapped territory and pull the map straight (sm_close_loop).  pose: where the caller
+        believes the camera is (4x4 camera->world or float32[16] column-major); paths: the map files that move with the model.
+        params: fields of sm_loop_params (min_age, min_trans, min_rot_deg, max_trans, max_rot_deg) and of sm_track_params.
+        Returns (pose 4x4: corrected if status is "CLOSED", else as given; info dict: status (name), status_code, track (as
+        track()'s info), D 4x4, t_a, t_b)."""
+        depth = np.ascontiguousarray(depth, np.uint16)
+        assert depth.size == self.P, depth.shape
+        loop_keys = {n for n, _ in SmLoopParams._fields_}
+        lp = loop_params(self.cfg, **{k: v for k, v in params.items() if k in loop_keys})
+        tk = {k: v for k, v in params.items() if k not in loop_keys}
+        tp = track_params(**tk) if tk else None
+        src = map_source(paths, include_model=True)
+        g = _mat16(pose)
+        out = np.zeros(16, np.float32)
+        info = SmLoopInfo()
+        self._chk(self._L.sm_close_loop(self._h, _ptr(depth), _ptr(g), C.byref(src), C.byref(tp) if tp is not None else None, C.byref(lp),
+                                        _ptr(out), C.byref(info)), "sm_close_loop")
+        d = dict(status=LOOP_STATUS.get(info.status, str(info.status)), status_code=int(info.status), track=_track_info_dict(info.track),
+                 D=np.array(info.D[:], np.float32).reshape(4, 4).T.copy(), t_a=int(info.t_a), t_b=int(info.t_b))
+        return out.reshape(4, 4).T.copy(), d
 
     # -- IndexMap
     def download_index_map(self):

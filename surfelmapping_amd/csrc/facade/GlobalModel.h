@@ -83,6 +83,24 @@ public:
         return true;
     }
 
+    // A correction that is a function of a surfel's last-update time (sm_warp_by_time): every surfel of the model and of the map
+    // files `mapFiles` whose time tau is >= t0 is moved by row min(int(tau - t0), rows - 1) of `corr12` (12 floats per row: a
+    // row-major 3x4 world->world [R|t]); files that hold such a surfel are rewritten in place.  Returns how many surfels moved
+    // (model and files together), or -1 with the error printed.
+    long warpByTime(const std::vector<std::string> &mapFiles, int t0, const std::vector<float> &corr12, bool includeModel = true)
+    {
+        std::vector<const char *> paths;
+        for (const std::string &f : mapFiles) paths.push_back(f.c_str());
+        const sm_map_source src{paths.data(), (uint32_t)paths.size(), includeModel ? 1 : 0};
+        (void)sm_sync(ctx_);                                             // (SM_FACADE_ASYNC: frames may still be in flight)
+        sm_warp_stats_t st;
+        if (sm_warp_by_time(ctx_, &src, t0, (uint32_t)(corr12.size() / 12), corr12.data()) != SM_OK || sm_warp_stats(ctx_, &st) != SM_OK) {
+            std::printf("warpByTime: %s\n", sm_last_error());
+            return -1;
+        }
+        return (long)(st.records_moved + st.model_moved);
+    }
+
     // The reverse: the records of the map files `mapFiles` (downloadMap's format, the files of SurfelMapping::setAutoRetire) that
     // lie within `radius` metres of the camera centre of `pose` are appended to the model, in the order of the files and of their
     // records, and -- unless keepFiles -- taken out of the files (sm_recall).  Returns how many came back, or -1 with the error

@@ -255,6 +255,26 @@ public:
         sm_auto_retire_stats(ctx_, &f, &n);
         return {f, (unsigned long long)n};
     }
+    // Close a loop (sm_close_loop, default parameters): `depth` is tracked against the surfels that are older than time_delta
+    // frames -- what a recall has brought back -- starting from `pose`, where the caller believes the camera is; if the two
+    // disagree by a plausible amount, the model, the stored poses and the map files `mapFiles` are pulled straight along a ramp
+    // over the surfels' times.  Returns the corrected pose, or `pose` itself when no loop was closed; getLastLoopInfo().status
+    // (SM_LOOP_*) says which, and its D is the correction that was measured.
+    Eigen::Matrix4f closeLoop(const unsigned short *depth, const Eigen::Matrix4f &pose, const std::vector<std::string> &mapFiles = {})
+    {
+        std::vector<const char *> paths;
+        for (const std::string &f : mapFiles) paths.push_back(f.c_str());
+        const sm_map_source src{paths.data(), (uint32_t)paths.size(), 1};
+        Eigen::Matrix4f out = pose;
+        (void)sm_sync(ctx_);                                             // (SM_FACADE_ASYNC: frames may still be in flight)
+        if (sm_close_loop(ctx_, depth, pose.data(), &src, nullptr, nullptr, out.data(), &lastLoopInfo) != SM_OK) {
+            std::printf("closeLoop: %s\n", sm_last_error());
+            return pose;
+        }
+        return out;
+    }
+    const sm_loop_info &getLastLoopInfo() { return lastLoopInfo; }
+
     // With setAutoRetire on: after every retirement, the records of its map files within `radius` metres of that frame's camera
     // come back into the model and leave the files, so that a camera that returns finds what it left (sm_set_auto_recall;
     // 0 < radius <= the retirement's minDistance).  radius <= 0: off.
@@ -288,6 +308,7 @@ private:
     sm_track_info lastTrackInfo{};
     sm_track_rgb_info lastTrackRgbInfo{};
     bool trackColour_ = false;
+    sm_loop_info lastLoopInfo{};
     bool beginCleanPoints = false;
     bool async_ = false;
 };

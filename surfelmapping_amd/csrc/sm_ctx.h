@@ -11,6 +11,7 @@
 //   sm_retire.hip    retirement (sm_retire*, sm_set_auto_retire)
 //   sm_render_maps.hip  views of a map set (sm_render_*_maps): map files streamed through the renderers
 //   sm_recall.hip    paging in (sm_recall*, sm_set_auto_recall): records of map files near the camera back into the model
+//   sm_warp.hip      closing loops (sm_warp_by_time, sm_loop_spread): the model and map files warped by surfel time
 // and, beside it, for everything that touches a map file: sm_mapfile.h (the format: checked open, writer, chunk plan; host only)
 // and sm_map_stream.h (the double-buffered chunk stream of sm_render_maps.hip and sm_recall.hip).
 #pragma once
@@ -32,7 +33,7 @@
 #include <utility>
 #include <vector>
 
-namespace sm { struct TrackState; struct TrackRgbState; struct RenderParams; struct ViewParams; struct ViewShade; struct RecallChunk; }
+namespace sm { struct TrackState; struct TrackRgbState; struct RenderParams; struct ViewParams; struct ViewShade; struct RecallChunk; struct WarpChunk; }
 
 // Hidden: libsurfelmapping_hip.so exports the C ABI and the kernels' host stubs, nothing of this namespace.  Its functions are
 // defined qualified (sm_impl::name) so that the definitions keep the visibility.
@@ -102,6 +103,7 @@ struct Tracker {
     Dev<double> d_part;
     Dev<TrackState> d_state;
     Host<TrackState> h_state;
+    Dev<uint32_t> d_anchor;            // sm_track_frame_old: the newest time in the windowed prediction (order-preserving code, 0 = none)
     float hist[2][16];                 // [0] the last processed pose (T_prev), [1] the one before (T_prev2)
     int n_hist = 0;                    // poses processed so far (capped at 2)
     bool timed = false;                // SM_TRACK_TIMING=1 at the last call: events around every kernel
@@ -174,10 +176,11 @@ struct RenderMaps {
 // call's tally, the periodic policy and its tally.  The records stream through RenderMaps' staging.
 struct Recall {
     // what the context knows of a map file it has read: valid while the file's size and mtime are these
-    struct Entry { uint64_t size; int64_t mtime_ns; float lo[3], hi[3]; };   // box of the rows' finite centres (lo > hi: none)
+    struct Entry { uint64_t size; int64_t mtime_ns; float lo[3], hi[3]; float max_time; };   // box of the rows' finite centres (lo > hi: none); largest non-NaN m[7] (-inf: none)
     std::map<std::string, Entry> index;
     Dev<uint64_t> d_mask;              // 4 words per block of 256 records: near
     Dev<uint32_t> d_blk_cnt, d_blk_base, d_run;   // near per block, their exclusive prefix, the call's running total
+    Dev<float4> d_box;                 // recall_box_of's own block boxes (the retirement policy has no stream staging)
     Dev<RecallChunk> d_chunk;          // [2]: the scan's tally of the chunk in buffer c & 1
     Host<RecallChunk> h_chunk;         // pinned, [2]
     sm_recall_stats_t stats{};
@@ -185,6 +188,20 @@ struct Recall {
     float radius = 0.0f;               // sm_set_auto_recall: <= 0 = off
     uint32_t rounds = 0;               // recalls the policy has made
     uint64_t surfels = 0;              // ... and the surfels they brought back
+};
+
+// the warp by surfel time (sm_warp.hip, sm_k_warp.h): scratch allocated by the first call, the last call's tally.  The files
+// stream through RenderMaps' staging and are warped in it; the file index is Recall's.
+struct Warp {
+    Dev<float4> d_corr;                // the table, 3 float4 per row
+    size_t corr_rows = 0;
+    Dev<float4> d_box;                 // per block of 256 records: (min xyz | largest time), (max xyz | 0)
+    Dev<uint32_t> d_sel;               // selected rows: [0], [1] of the chunk in buffer c & 1, [2] of the live model
+    Dev<WarpChunk> d_chunk;            // [2]
+    Host<WarpChunk> h_chunk;           // pinned, [2]
+    Event ev[2];                       // around the live model's kernel
+    sm_warp_stats_t stats{};
+    bool stats_valid = false;
 };
 
 // The SM_* switches of the frame pipeline (sm_api.hip), read once by sm_create (read_switches): nothing on the per-frame path
@@ -393,6 +410,7 @@ struct sm_ctx {
     Retire ret;
     RenderMaps maps;
     Recall rec;
+    Warp warp;
     // host frame state (src/SurfelMapping.h:100-103)
     int tick = 0;
     bool ref_set = false;
@@ -456,11 +474,12 @@ int maps_ensure_staging(sm_ctx *s);               // RenderMaps' copy stream, re
 // the periodic policy: called by a frame that has just retired (one test unless it is on).  wrote_file: this round's retirement
 // wrote the policy's newest file, at this pose -- every row of it is far, so the recall does not read it
 int auto_recall_after_retire(sm_ctx *s, bool wrote_file);
-// For the file index, while the recall policy is on (its setter has allocated the scratch): the box of the finite centres of n
-// AoS records in device memory folded into lo / hi (k_recall_mark + k_recall_scan on the context's stream; waits), and the entry
-// of a map file the context has just written itself with that box
-int recall_box_of(sm_ctx *s, const float *d_rec12, uint32_t n, float lo[3], float hi[3]);
-void recall_note_written(sm_ctx *s, const std::string &path, const float lo[3], const float hi[3]);
+// For the file index, when the retirement policy writes a file (its setter has allocated the scratch): the box of the finite
+// centres and the largest non-NaN time of n AoS records in device memory folded into lo / hi / *max_time (k_recall_mark +
+// k_recall_scan on the context's stream; waits), and the entry of a map file the context has just written itself with them
+int recall_box_of(sm_ctx *s, const float *d_rec12, uint32_t n, float lo[3], float hi[3], float *max_time);
+void recall_note_written(sm_ctx *s, const std::string &path, const float lo[3], const float hi[3], float max_time);
+int recall_ensure_scratch(sm_ctx *s);             // what recall_box_of needs (sm_set_auto_retire allocates it with its own)
 // what the two policies require of each other when both are on (SM_E_ARG with g_err set otherwise)
 int check_recall_policy(float radius, const sm_retire_params &rp, const char *who);
 

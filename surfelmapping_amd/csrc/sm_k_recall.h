@@ -34,8 +34,9 @@ __device__ __forceinline__ bool recall_test(const RecallArgs &ra, const float4 &
 }
 
 // what the scan leaves per chunk (read back by the host): total near records, the running total BEFORE this chunk, and the
-// box of the chunk's finite centres (lo = +inf, hi = -inf if it has none)
-struct RecallChunk { uint32_t total, run_before; float lx, ly, lz, hx, hy, hz; };
+// box of the chunk's finite centres (lo = +inf, hi = -inf if it has none), and the largest non-NaN last-update time of its records
+// (-inf if it has none: what sm_warp_by_time's file skip asks the index)
+struct RecallChunk { uint32_t total, run_before; float lx, ly, lz, hx, hy, hz, tmax; };
 
 __device__ __forceinline__ float recall_wave_min(float v)
 {
@@ -59,12 +60,12 @@ __device__ __forceinline__ void recall_load_block(const float4 *__restrict__ rec
 }
 
 // mask[4 * b + w]: near bits of records 256 b + 64 w ...; blk_cnt[b]: their number; box[2 b], box[2 b + 1]: min / max of the
-// finite centres of the block
+// finite centres of the block; box[2 b + 1].w: the largest non-NaN time of the block
 __global__ __launch_bounds__(256) void k_recall_mark(const float4 *__restrict__ rec, uint32_t n, RecallArgs ra, uint64_t *__restrict__ mask,
                                                      uint32_t *__restrict__ blk_cnt, float4 *__restrict__ box)
 {
     __shared__ float4 s_rec[RECALL_BLOCK * 3];           // 12 KiB
-    __shared__ float s_red[4][6];
+    __shared__ float s_red[4][7];
     __shared__ uint32_t s_cnt[4];
     const uint32_t first = blockIdx.x * (uint32_t)RECALL_BLOCK;
     const uint32_t m = min((uint32_t)RECALL_BLOCK, n - first);              // >= 1: the grid is ceil(n / 256)
@@ -79,11 +80,13 @@ __global__ __launch_bounds__(256) void k_recall_mark(const float4 *__restrict__ 
     const bool fin = have && (pc.x - pc.x == 0.0f) && (pc.y - pc.y == 0.0f) && (pc.z - pc.z == 0.0f);
     const float lx = recall_wave_min(fin ? pc.x : INF), ly = recall_wave_min(fin ? pc.y : INF), lz = recall_wave_min(fin ? pc.z : INF);
     const float hx = recall_wave_max(fin ? pc.x : -INF), hy = recall_wave_max(fin ? pc.y : -INF), hz = recall_wave_max(fin ? pc.z : -INF);
+    const float tau = have ? s_rec[threadIdx.x * 3 + 1].w : -INF;
+    const float tm = recall_wave_max(tau == tau ? tau : -INF);
     if (lane == 0) {
         mask[(size_t)blockIdx.x * 4 + wave] = near;
         s_cnt[wave] = (uint32_t)__popcll(near);
         s_red[wave][0] = lx; s_red[wave][1] = ly; s_red[wave][2] = lz;
-        s_red[wave][3] = hx; s_red[wave][4] = hy; s_red[wave][5] = hz;
+        s_red[wave][3] = hx; s_red[wave][4] = hy; s_red[wave][5] = hz; s_red[wave][6] = tm;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -96,7 +99,7 @@ __global__ __launch_bounds__(256) void k_recall_mark(const float4 *__restrict__ 
         hi.x = fmaxf(fmaxf(s_red[0][3], s_red[1][3]), fmaxf(s_red[2][3], s_red[3][3]));
         hi.y = fmaxf(fmaxf(s_red[0][4], s_red[1][4]), fmaxf(s_red[2][4], s_red[3][4]));
         hi.z = fmaxf(fmaxf(s_red[0][5], s_red[1][5]), fmaxf(s_red[2][5], s_red[3][5]));
-        hi.w = 0.0f;
+        hi.w = fmaxf(fmaxf(s_red[0][6], s_red[1][6]), fmaxf(s_red[2][6], s_red[3][6]));
         box[2 * (size_t)blockIdx.x] = lo;
         box[2 * (size_t)blockIdx.x + 1] = hi;
     }
@@ -107,9 +110,9 @@ __global__ __launch_bounds__(1024) void k_recall_scan(uint32_t nblk, const uint3
                                                       uint32_t *__restrict__ blk_base, uint32_t *__restrict__ run, RecallChunk *__restrict__ out)
 {
     __shared__ uint32_t s_scan[17];
-    __shared__ float s_red[16][6];
+    __shared__ float s_red[16][7];
     const float INF = __uint_as_float(0x7F800000u);
-    float lx = INF, ly = INF, lz = INF, hx = -INF, hy = -INF, hz = -INF;
+    float lx = INF, ly = INF, lz = INF, hx = -INF, hy = -INF, hz = -INF, tm = -INF;
     uint32_t sum = 0;
     for (uint32_t b0 = 0; b0 < nblk; b0 += 1024u) {      // at most four rounds
         const uint32_t b = b0 + threadIdx.x;
@@ -120,26 +123,26 @@ __global__ __launch_bounds__(1024) void k_recall_scan(uint32_t nblk, const uint3
             blk_base[b] = sum + excl;
             const float4 lo = box[2 * (size_t)b], hi = box[2 * (size_t)b + 1];
             lx = fminf(lx, lo.x); ly = fminf(ly, lo.y); lz = fminf(lz, lo.z);
-            hx = fmaxf(hx, hi.x); hy = fmaxf(hy, hi.y); hz = fmaxf(hz, hi.z);
+            hx = fmaxf(hx, hi.x); hy = fmaxf(hy, hi.y); hz = fmaxf(hz, hi.z); tm = fmaxf(tm, hi.w);
         }
         sum += tot;
     }
     lx = recall_wave_min(lx); ly = recall_wave_min(ly); lz = recall_wave_min(lz);
-    hx = recall_wave_max(hx); hy = recall_wave_max(hy); hz = recall_wave_max(hz);
+    hx = recall_wave_max(hx); hy = recall_wave_max(hy); hz = recall_wave_max(hz); tm = recall_wave_max(tm);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) {
         s_red[wave][0] = lx; s_red[wave][1] = ly; s_red[wave][2] = lz;
-        s_red[wave][3] = hx; s_red[wave][4] = hy; s_red[wave][5] = hz;
+        s_red[wave][3] = hx; s_red[wave][4] = hy; s_red[wave][5] = hz; s_red[wave][6] = tm;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int w = 1; w < 16; ++w) {
             lx = fminf(lx, s_red[w][0]); ly = fminf(ly, s_red[w][1]); lz = fminf(lz, s_red[w][2]);
-            hx = fmaxf(hx, s_red[w][3]); hy = fmaxf(hy, s_red[w][4]); hz = fmaxf(hz, s_red[w][5]);
+            hx = fmaxf(hx, s_red[w][3]); hy = fmaxf(hy, s_red[w][4]); hz = fmaxf(hz, s_red[w][5]); tm = fmaxf(tm, s_red[w][6]);
         }
         const uint32_t before = *run;
         *run = before + sum;
-        *out = RecallChunk{sum, before, lx, ly, lz, hx, hy, hz};
+        *out = RecallChunk{sum, before, lx, ly, lz, hx, hy, hz, tm};
     }
 }
 

@@ -7,6 +7,7 @@
 //                    prediction camera T_prev with near < z < far lands on pixel (floor(fx*x/z + cx + 0.5), floor(fy*y/z + cy + 0.5))
 //                    by a 64-bit atomicMin of (float bits of z) << 32 | slot: the nearest surfel, ties to the lower slot.
 //   k_track_resolve  key -> slot (-1 = empty), row-major W*H int32.
+//   (sm_track_frame_old: k_track_splat_old instead, which also gates on the surfel's time, and k_track_anchor after the resolve)
 //   k_track_vertex   the current frame's metric depth (p0a's rule), vertex and normal of every pixel of the strided grid.
 //   then max_iters times:
 //   k_track_reduce   associate + residual + the 29 values of the normal equations per inlier, fp32 terms accumulated in fp64,
@@ -81,6 +82,47 @@ __global__ void k_track_resolve(const uint64_t *__restrict__ key, int npix, int3
     if (p >= npix) return;
     const uint64_t kk = key[p];
     slot[p] = kk == KEY_EMPTY ? -1 : (int32_t)(uint32_t)(kk & 0xFFFFFFFFull);
+}
+
+// ---- the windowed prediction (sm_track_frame_old: the loop measurement, DESIGN.md "4h. Closing loops") ----
+// k_track_splat with one more gate: only surfels last updated at or before max_time (one extra time-plane load; false on a NaN).
+// A kernel of its own, so that k_track_splat stays what it is.
+__global__ __launch_bounds__(256) void k_track_splat_old(Model M, const DevState *__restrict__ st, const uint64_t *__restrict__ alive,
+                                                         TrackParams tp, float max_time, uint64_t *__restrict__ key, TrackState *__restrict__ ts)
+{
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    bool in_view = false;
+    if (k < st->count && ((alive[k >> 6] >> (k & 63u)) & 1ull) && M.s[st->cur].time[k] <= max_time) {
+        const float4 pc = M.s[st->cur].pos_conf[k];
+        const float3 c = xform3(tp.tinv_prev, pc.x, pc.y, pc.z);
+        if (c.z > tp.near_clip && c.z < tp.far_clip) {
+            const float fu = floorf(((tp.fx * c.x) / c.z + tp.cx) + 0.5f);
+            const float fv = floorf(((tp.fy * c.y) / c.z + tp.cy) + 0.5f);
+            if (fu >= 0.0f && fu < (float)tp.W && fv >= 0.0f && fv < (float)tp.H) {
+                in_view = true;
+                const size_t p = (size_t)(int)fv * tp.W + (int)fu;
+                atomicMin((unsigned long long *)&key[p], (unsigned long long)(((uint64_t)__float_as_uint(c.z) << 32) | k));
+            }
+        }
+    }
+    const uint64_t m = __ballot(in_view);                     // one atomic per wave
+    if (m && (threadIdx.x & 63u) == (uint32_t)(__ffsll((unsigned long long)m) - 1))
+        atomicAdd(&ts->in_view, (uint32_t)__popcll(m));
+}
+
+// *anchor = max over the resolved slots of f2ord(last-update time); 0 (no float's code but a NaN's) stays where the prediction is
+// empty.  One wave reduction and at most one atomic per wave.
+__global__ __launch_bounds__(256) void k_track_anchor(Model M, const DevState *__restrict__ st, const int32_t *__restrict__ slot, int npix,
+                                                      uint32_t *__restrict__ anchor)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    uint32_t v = 0u;
+    if (p < npix) {
+        const int32_t k = slot[p];
+        if (k >= 0) v = f2ord(M.s[st->cur].time[k]);
+    }
+    v = wave_max_u32(v);                                      // (all 64 lanes active: nobody has returned)
+    if ((threadIdx.x & 63u) == 0u && v) atomicMax(anchor, v);
 }
 
 // ---- the current frame: vertex (xyz, 1 = valid) and normal per grid point ----

@@ -1,4 +1,4 @@
-// sm_map_stream.h -- private to sm_render_maps.hip and sm_recall.hip: the double-buffered stream of map-file chunks through
+// sm_map_stream.h -- private to sm_render_maps.hip, sm_recall.hip and sm_warp.hip: the double-buffered stream of map-file chunks through
 // RenderMaps' staging, one object per call.  Chunk c of a pass goes through buffer q = c & 1: read into h_rec[q] (timed into
 // read_ms), copied on `copy` into d_rec[q], and the context's stream waits for the copy; the caller then launches its kernels on
 // d_rec[q] and says done(q).  fold(q) waits for them and adds the buffer's event times to the caller's tally.  The host reads

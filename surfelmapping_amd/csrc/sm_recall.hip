@@ -60,6 +60,7 @@ struct MapFile {
     bool skipped = false;              // by the index: not opened
     sm_mapfile::Header h;              // count 0 unless the file is read
     float lo[3], hi[3];                // box of this read
+    float tmax = -__builtin_inff();    // largest non-NaN time of this read
     uint32_t chunks_left = 0;
     // MOVE: the temporary, opened by the first chunk that loses a row; a call that ends before the file is replaced removes it
     sm_mapfile::Writer tmp;
@@ -74,13 +75,14 @@ int ensure_scratch(sm_ctx *s)
     Dev<uint64_t> mask;
     Dev<uint32_t> cnt, base, run;
     Dev<RecallChunk> chunk;
+    Dev<float4> box;
     int rc;
-    if ((rc = dalloc(mask, (size_t)RECALL_MAX_BLOCKS * 4)) || (rc = dalloc(cnt, RECALL_MAX_BLOCKS)) || (rc = dalloc(base, RECALL_MAX_BLOCKS)) ||
+    if ((rc = dalloc(box, (size_t)RECALL_MAX_BLOCKS * 2)) || (rc = dalloc(mask, (size_t)RECALL_MAX_BLOCKS * 4)) || (rc = dalloc(cnt, RECALL_MAX_BLOCKS)) || (rc = dalloc(base, RECALL_MAX_BLOCKS)) ||
         (rc = dalloc(run, 1)) || (rc = dalloc(chunk, 2)))
         return rc;
     HIPCK(hipHostMalloc((void **)r.h_chunk.put(), 2 * sizeof(RecallChunk), hipHostMallocDefault));
     r.d_mask = std::move(mask); r.d_blk_cnt = std::move(cnt); r.d_blk_base = std::move(base); r.d_run = std::move(run);
-    r.d_chunk = std::move(chunk);
+    r.d_chunk = std::move(chunk); r.d_box = std::move(box);
     return SM_OK;
 }
 
@@ -139,6 +141,7 @@ int finish(Run &R, MapStream &in, const MapStream::Chunk &ck)
     R.total += rc_q.total;
     mf.lo[0] = std::min(mf.lo[0], rc_q.lx); mf.lo[1] = std::min(mf.lo[1], rc_q.ly); mf.lo[2] = std::min(mf.lo[2], rc_q.lz);
     mf.hi[0] = std::max(mf.hi[0], rc_q.hx); mf.hi[1] = std::max(mf.hi[1], rc_q.hy); mf.hi[2] = std::max(mf.hi[2], rc_q.hz);
+    mf.tmax = std::max(mf.tmax, rc_q.tmax);
     mf.chunks_left--;
     if (R.mode != SM_RECALL_MOVE) return SM_OK;
     const double t0 = now_ms();
@@ -258,7 +261,7 @@ int recall(sm_ctx *s, const sm_map_source *src, const float *pose16, const sm_re
     *n = (uint32_t)std::min<uint64_t>(R.total, 0xFFFFFFFFull);
     // what this read has learnt goes into the index, whatever becomes of the call: the files are as they were
     auto note = [&](const MapFile &mf) {
-        Recall::Entry en{mf.h.size, mf.h.mtime_ns, {mf.lo[0], mf.lo[1], mf.lo[2]}, {mf.hi[0], mf.hi[1], mf.hi[2]}};
+        Recall::Entry en{mf.h.size, mf.h.mtime_ns, {mf.lo[0], mf.lo[1], mf.lo[2]}, {mf.hi[0], mf.hi[1], mf.hi[2]}, mf.tmax};   // (a MOVE only takes rows away: tmax stays an upper bound)
         r.index[mf.path] = en;
     };
     for (const MapFile &mf : files)
@@ -301,15 +304,15 @@ int sm_impl::check_recall_policy(float radius, const sm_retire_params &rp, const
     return SM_E_ARG;
 }
 
-int sm_impl::recall_box_of(sm_ctx *s, const float *d_rec12, uint32_t n, float lo[3], float hi[3])
+int sm_impl::recall_box_of(sm_ctx *s, const float *d_rec12, uint32_t n, float lo[3], float hi[3], float *max_time)
 {
     Recall &r = s->rec;
     if (!n) return SM_OK;
     const unsigned nblk = (n + RECALL_BLOCK - 1) / RECALL_BLOCK;         // n <= a chunk: the caller's staging holds no more
     const RecallArgs none{0.0f, 0.0f, 0.0f, -1.0f};                       // (no d2 is <= -1: the masks stay empty)
     hipLaunchKernelGGL(k_recall_mark, dim3(nblk), dim3(256), 0, s->stream, (const float4 *)d_rec12, n, none, r.d_mask.get(), r.d_blk_cnt.get(),
-                       s->maps.d_box.get());
-    hipLaunchKernelGGL(k_recall_scan, dim3(1), dim3(1024), 0, s->stream, nblk, (const uint32_t *)r.d_blk_cnt.get(), (const float4 *)s->maps.d_box.get(),
+                       r.d_box.get());
+    hipLaunchKernelGGL(k_recall_scan, dim3(1), dim3(1024), 0, s->stream, nblk, (const uint32_t *)r.d_blk_cnt.get(), (const float4 *)r.d_box.get(),
                        r.d_blk_base.get(), r.d_run.get(), r.d_chunk.get());
     HIPCK(hipGetLastError());
     HIPCK(hipMemcpyAsync(r.h_chunk.get(), r.d_chunk.get(), sizeof(RecallChunk), hipMemcpyDeviceToHost, s->stream));
@@ -317,15 +320,18 @@ int sm_impl::recall_box_of(sm_ctx *s, const float *d_rec12, uint32_t n, float lo
     const RecallChunk ck = r.h_chunk.get()[0];
     lo[0] = std::min(lo[0], ck.lx); lo[1] = std::min(lo[1], ck.ly); lo[2] = std::min(lo[2], ck.lz);
     hi[0] = std::max(hi[0], ck.hx); hi[1] = std::max(hi[1], ck.hy); hi[2] = std::max(hi[2], ck.hz);
+    *max_time = std::max(*max_time, ck.tmax);
     return SM_OK;
 }
 
-void sm_impl::recall_note_written(sm_ctx *s, const std::string &path, const float lo[3], const float hi[3])
+void sm_impl::recall_note_written(sm_ctx *s, const std::string &path, const float lo[3], const float hi[3], float max_time)
 {
     sm_mapfile::Header h;
     if (!sm_mapfile::stat_of(path, h)) { s->rec.index.erase(path); return; }
-    s->rec.index[path] = Recall::Entry{h.size, h.mtime_ns, {lo[0], lo[1], lo[2]}, {hi[0], hi[1], hi[2]}};
+    s->rec.index[path] = Recall::Entry{h.size, h.mtime_ns, {lo[0], lo[1], lo[2]}, {hi[0], hi[1], hi[2]}, max_time};
 }
+
+int sm_impl::recall_ensure_scratch(sm_ctx *s) { return ensure_scratch(s); }
 
 // The periodic policy, called by auto_retire_after_frame once that frame's retirement is complete: a MOVE recall at the frame's
 // pose from every file the retirement policy has written.  The file this round has written is listed and not read: each of its

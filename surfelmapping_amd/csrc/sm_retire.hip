@@ -170,22 +170,20 @@ int sm_impl::auto_retire_after_frame(sm_ctx *s)
         if (!r.h_stage) HIPCK(hipHostMalloc(r.h_stage.put(), (size_t)FILE_CHUNK * sm_mapfile::RECORD_BYTES, hipHostMallocDefault));
         if ((rc = ensure_export(s, (size_t)std::min(n, FILE_CHUNK) * sm_mapfile::RECORD_BYTES))) return rc;
         const std::string path = sm_mapfile::policy_file(r.prefix, r.files);
-        // sm_set_auto_recall: the file index learns the file's box now, from the records on the device, so that no recall has
-        // to read the file only to find out where it lies
-        const bool want_box = s->rec.radius > 0.0f;
+        // the file index learns the file's box and its largest time now, from the records on the device, so that neither a recall
+        // nor a warp has to read the file only to find out where and when it lies
         const float INF = __builtin_inff();
-        float lo[3] = {INF, INF, INF}, hi[3] = {-INF, -INF, -INF};
+        float lo[3] = {INF, INF, INF}, hi[3] = {-INF, -INF, -INF}, tmax = -INF;
         sm_mapfile::Writer w;                    // (no half-written map file is left behind: a return below removes it)
         if (!w.open(path, n, r.last_tick, s->tick - 1, nullptr, g_err)) return SM_E_ARG;
         rc = drain_export(s, n, FILE_CHUNK, r.h_stage, 0, [s](float *d, uint32_t first, uint32_t m) { launch_gather(s, d, first, first + m); },
                           [&](uint32_t, uint32_t m) -> int {
-                              if (want_box)
-                                  if (int rb = recall_box_of(s, (const float *)s->d_export.get(), m, lo, hi)) return rb;
+                              if (int rb = recall_box_of(s, (const float *)s->d_export.get(), m, lo, hi, &tmax)) return rb;
                               return w.append(r.h_stage, m, g_err) ? SM_OK : SM_E_ARG;
                           });
         if (rc) return rc;
         if (!w.commit(g_err)) return SM_E_ARG;
-        if (want_box) recall_note_written(s, path, lo, hi);
+        recall_note_written(s, path, lo, hi, tmax);
         r.files++;
         r.surfels += n;
         r.last_tick = s->tick;
@@ -226,7 +224,7 @@ int sm_set_auto_retire(sm_ctx *s, const sm_retire_params *params, int32_t every,
     if (every <= 0 || !path_prefix) { r.every = 0; r.prefix.clear(); return SM_OK; }
     if (s->rec.radius > 0.0f && (rc = check_recall_policy(s->rec.radius, p, "sm_set_auto_retire"))) return rc;
     HIPCK(hipSetDevice(s->cfg.device));
-    if ((rc = ensure_scratch(s))) return rc;     // so that the frame that retires first allocates nothing
+    if ((rc = ensure_scratch(s)) || (rc = recall_ensure_scratch(s))) return rc;     // so that the frame that retires first allocates nothing (the file index's box pass included)
     r.params = p;
     r.every = every;
     r.prefix = path_prefix;

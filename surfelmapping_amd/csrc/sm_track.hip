@@ -67,14 +67,16 @@ int track_alloc(sm_ctx *s)
     if (s->trk.d_state) return SM_OK;
     const size_t P = (size_t)s->P;
     Dev<uint16_t> depth; Dev<float4> v, n; Dev<uint64_t> key; Dev<int32_t> pred; Dev<double> part; Dev<TrackState> d;
+    Dev<uint32_t> anchor;
     Host<TrackState> h;
     int rc;
-    if ((rc = dalloc(depth, P)) || (rc = dalloc(v, P)) || (rc = dalloc(n, P)) || (rc = dalloc(key, P)) || (rc = dalloc(pred, P)) ||
+    if ((rc = dalloc(anchor, 1)) || (rc = dalloc(depth, P)) || (rc = dalloc(v, P)) || (rc = dalloc(n, P)) || (rc = dalloc(key, P)) || (rc = dalloc(pred, P)) ||
         (rc = dalloc(part, (size_t)TRACK_NSYS * TRACK_MAX_PARTS)) || (rc = dalloc(d, 1)))
         return rc;
     HIPCK(hipHostMalloc(h.put(), sizeof(TrackState)));
     s->trk.d_depth = std::move(depth); s->trk.d_v = std::move(v); s->trk.d_n = std::move(n); s->trk.d_key = std::move(key);
     s->trk.d_pred = std::move(pred); s->trk.d_part = std::move(part); s->trk.h_state = std::move(h);
+    s->trk.d_anchor = std::move(anchor);
     s->trk.d_state = std::move(d);              // last: it marks the set complete
     return SM_OK;
 }
@@ -138,8 +140,11 @@ int track_event(sm_ctx *s, size_t i)
     return SM_OK;
 }
 
-// the state, the prediction at T_prev and the vertex / normal stage, enqueued (the model's state has been pulled)
-int track_prepare(sm_ctx *s, const uint16_t *depth_mm, const TrackParams &tp, const float *T0, const float *guess, bool ortho)
+// the state, the prediction at T_prev and the vertex / normal stage, enqueued (the model's state has been pulled).
+// max_time (sm_track_*_old; null otherwise): the prediction holds only surfels last updated at or before it, and the newest time
+// it holds is left in d_anchor
+int track_prepare(sm_ctx *s, const uint16_t *depth_mm, const TrackParams &tp, const float *T0, const float *guess, bool ortho,
+                  const int32_t *max_time = nullptr)
 {
     const size_t P = (size_t)s->P;
     TrackState &h = *s->trk.h_state;
@@ -157,10 +162,18 @@ int track_prepare(sm_ctx *s, const uint16_t *depth_mm, const TrackParams &tp, co
     const unsigned pblocks = (unsigned)((P + 255) / 256);
     fill_keys(s, s->trk.d_key, P);
     const uint32_t slots = s->h_state->count;
-    if (slots)
+    // (max_time == INT32_MAX is "no window": exactly sm_track_frame's prediction, whatever the times are)
+    if (slots && max_time && *max_time != INT32_MAX)
+        hipLaunchKernelGGL(k_track_splat_old, dim3((slots + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, s->d_alive, tp,
+                           (float)*max_time, s->trk.d_key, s->trk.d_state);
+    else if (slots)
         hipLaunchKernelGGL(k_track_splat, dim3((slots + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, s->d_alive, tp,
                            s->trk.d_key, s->trk.d_state);
     hipLaunchKernelGGL(k_track_resolve, dim3(pblocks), dim3(256), 0, s->stream, s->trk.d_key, (int)P, s->trk.d_pred);
+    if (max_time) {
+        HIPCK(hipMemsetAsync(s->trk.d_anchor, 0, 4, s->stream));
+        hipLaunchKernelGGL(k_track_anchor, dim3(pblocks), dim3(256), 0, s->stream, s->M, s->d_state, s->trk.d_pred, (int)P, s->trk.d_anchor);
+    }
     if ((rc = track_event(s, 1))) return rc;
     hipLaunchKernelGGL(k_track_vertex, dim3((tp.n + 255) / 256), dim3(256), 0, s->stream, s->trk.d_depth, s->d_xs, s->d_ys, tp,
                        s->trk.d_v, s->trk.d_n);
@@ -310,15 +323,30 @@ int sm_default_track_params(sm_track_params *p)
     return SM_OK;
 }
 
-int sm_track_frame(sm_ctx *s, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params, float *pose16_out,
-                   sm_track_info *info)
+}  // extern "C"
+
+namespace {
+// a prediction slot code of k_track_anchor as the time it stands for (-1: the prediction is empty)
+float anchor_of(uint32_t code)
 {
-    if (!s || !depth_mm || !pose16_out) { g_err = "sm_track_frame: null argument"; return SM_E_ARG; }
+    if (!code) return -1.0f;
+    const uint32_t b = (code & 0x80000000u) ? (code & 0x7FFFFFFFu) : ~code;
+    float f;
+    memcpy(&f, &b, 4);
+    return f;
+}
+
+// sm_track_frame, and with max_time sm_track_frame_old (anchor_time may be null)
+int track_frame(sm_ctx *s, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params, const int32_t *max_time,
+                float *pose16_out, sm_track_info *info, float *anchor_time, const char *fn)
+{
+    if (!s || !depth_mm || !pose16_out) { g_err = std::string(fn) + ": null argument"; return SM_E_ARG; }
     sm_track_params p;
     if (params) p = *params;
     else sm_default_track_params(&p);
     int rc;
-    if ((rc = track_params_check(s, p, "sm_track_frame")) || (rc = track_check(s, "sm_track_frame"))) return rc;
+    if ((rc = track_params_check(s, p, fn)) || (rc = track_check(s, fn))) return rc;
+    if (anchor_time) *anchor_time = -1.0f;
     HIPCK(hipSetDevice(s->cfg.device));
     if ((rc = pull_state(s))) return rc;                      // waits for frames in flight: the model after the last frame
     float g[16];
@@ -336,9 +364,11 @@ int sm_track_frame(sm_ctx *s, const uint16_t *depth_mm, const float *guess16, co
     }
     if ((rc = track_alloc(s))) return rc;
     const TrackParams tp = track_params(s, p);
-    if ((rc = track_prepare(s, depth_mm, tp, g, g, true))) return rc;    // (iterates from the orthonormalised guess)
+    if ((rc = track_prepare(s, depth_mm, tp, g, g, true, max_time))) return rc;    // (iterates from the orthonormalised guess)
     for (int it = 0; it < p.max_iters; ++it)
         if ((rc = track_iteration(s, tp, 0))) return rc;
+    uint32_t anchor = 0;
+    if (max_time) HIPCK(hipMemcpyAsync(&anchor, s->trk.d_anchor, 4, hipMemcpyDeviceToHost, s->stream));
     HIPCK(hipMemcpyAsync(s->trk.h_state, s->trk.d_state, sizeof(TrackState), hipMemcpyDeviceToHost, s->stream));
     HIPCK(hipStreamSynchronize(s->stream));                   // the one wait of a tracked frame
     const TrackState &h = *s->trk.h_state;
@@ -348,13 +378,15 @@ int sm_track_frame(sm_ctx *s, const uint16_t *depth_mm, const float *guess16, co
     inf.inliers = h.inliers;
     inf.rmse = (float)h.rmse;
     if (info) *info = inf;
+    if (anchor_time) *anchor_time = anchor_of(anchor);
     return SM_OK;
 }
 
-int sm_track_debug(sm_ctx *s, const uint16_t *depth_mm, const float *pose16_eval, int32_t *pred_slot, double *sys29)
+int track_debug(sm_ctx *s, const uint16_t *depth_mm, const float *pose16_eval, const int32_t *max_time, int32_t *pred_slot, double *sys29,
+                const char *fn)
 {
-    if (!s || !depth_mm || !pose16_eval) { g_err = "sm_track_debug: null argument"; return SM_E_ARG; }
-    int rc = track_check(s, "sm_track_debug");
+    if (!s || !depth_mm || !pose16_eval) { g_err = std::string(fn) + ": null argument"; return SM_E_ARG; }
+    int rc = track_check(s, fn);
     if (rc) return rc;
     HIPCK(hipSetDevice(s->cfg.device));
     if ((rc = pull_state(s))) return rc;
@@ -362,13 +394,38 @@ int sm_track_debug(sm_ctx *s, const uint16_t *depth_mm, const float *pose16_eval
     sm_track_params p;
     sm_default_track_params(&p);
     const TrackParams tp = track_params(s, p);
-    if ((rc = track_prepare(s, depth_mm, tp, pose16_eval, pose16_eval, false))) return rc;   // (the pose as given)
+    if ((rc = track_prepare(s, depth_mm, tp, pose16_eval, pose16_eval, false, max_time))) return rc;   // (the pose as given)
     if ((rc = track_iteration(s, tp, 1))) return rc;
     if (pred_slot) HIPCK(hipMemcpyAsync(pred_slot, s->trk.d_pred, (size_t)s->P * 4, hipMemcpyDeviceToHost, s->stream));
     HIPCK(hipMemcpyAsync(s->trk.h_state, s->trk.d_state, sizeof(TrackState), hipMemcpyDeviceToHost, s->stream));
     HIPCK(hipStreamSynchronize(s->stream));
     if (sys29) memcpy(sys29, s->trk.h_state->sys, TRACK_NSYS * sizeof(double));
     return SM_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int sm_track_frame(sm_ctx *s, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params, float *pose16_out,
+                   sm_track_info *info)
+{
+    return track_frame(s, depth_mm, guess16, params, nullptr, pose16_out, info, nullptr, "sm_track_frame");
+}
+
+int sm_track_frame_old(sm_ctx *s, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params, int32_t max_time,
+                       float *pose16_out, sm_track_info *info, float *anchor_time)
+{
+    return track_frame(s, depth_mm, guess16, params, &max_time, pose16_out, info, anchor_time, "sm_track_frame_old");
+}
+
+int sm_track_debug(sm_ctx *s, const uint16_t *depth_mm, const float *pose16_eval, int32_t *pred_slot, double *sys29)
+{
+    return track_debug(s, depth_mm, pose16_eval, nullptr, pred_slot, sys29, "sm_track_debug");
+}
+
+int sm_track_debug_old(sm_ctx *s, const uint16_t *depth_mm, const float *pose16_eval, int32_t max_time, int32_t *pred_slot, double *sys29)
+{
+    return track_debug(s, depth_mm, pose16_eval, &max_time, pred_slot, sys29, "sm_track_debug_old");
 }
 
 // Diagnostic, deliberately not part of include/sm_c_api.h (tools/track_probe.py): device times of the last sm_track_frame /

@@ -233,8 +233,7 @@ int alloc_set(SetBufs &b, size_t cap)
 
 int grid_surfels(const sm_ctx *s)
 {
-    const uint64_t tiles = ((uint64_t)s->count_bound + TILE - 1) / TILE;
-    return (int)std::min<uint64_t>(std::max<uint64_t>(tiles, 1), MAX_GRID);
+    return (int)std::min<uint64_t>(std::max<uint64_t>(s->slots.tiles(), 1), MAX_GRID);
 }
 
 // SM_CHECK_ALIVE=1 (diagnostic): check the alive-bits / dead-count invariant after a stage; reported by sm_sync
@@ -324,15 +323,16 @@ int launch_prep(sm_ctx *s, const uint8_t *rgb, const uint16_t *raw, const uint8_
     const int tiles = ((s->W + 31) / 32) * ((s->H + 31) / 32);
     // the frame's tile skip flags for the one-pass surfel kernel: a few extra workgroups (128 tiles each per round)
     TilePrep tp{};
-    const uint64_t ntl = ((uint64_t)s->count_bound + TILE - 1) / TILE;
+    const uint64_t ntl = s->slots.tiles();
+    const FrameSet &f = s->cur();
     if (clear_keys && tile_flags) {
         tp.nfb = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((ntl + 1023) / 1024, 1), 64);     // one tile per thread (k_prep: 1 024 threads)
-        tp.st = s->d_state; tp.tb = s->d_tb; tp.tile_flags = s->d_tile_flags; tp.wave_cnt = s->d_wave_cnt; tp.prep_part = s->d_prep_part;
+        tp.st = s->d_state; tp.tb = s->d_tb; tp.tile_flags = f.tile_flags; tp.wave_cnt = f.wave_cnt; tp.prep_part = f.prep_part;
     }
     FixArgs *fxp = nullptr;
     AssocArgs *carried = carry ? s->held.take_assoc(fxp) : nullptr;
     s->tl.frame().merged = carried || chain;
-    uint32_t *conf_sub = clear_keys ? s->conf_sub() : nullptr;      // a frame's preparation (clear_keys) also zeroes that frame's conflict sub-counters
+    uint32_t *conf_sub = clear_keys ? f.conf_sub : nullptr;      // a frame's preparation (clear_keys) also zeroes that frame's conflict sub-counters
     if (carried || chain) {
         // the held-back association of the previous frame (if any) + this frame's tile flags + its image / chain tiles in one launch
         // (a sharded stream's settle step rides on k_prep only: stand-alone here)
@@ -352,8 +352,8 @@ int launch_prep(sm_ctx *s, const uint8_t *rgb, const uint16_t *raw, const uint8_
             if (tp.nfb) { tp.slow_conf_sub = fx.conf_sub; tp.slow_cap = a.fp.conflict_cap; tp.slow_need = n_fix; tp.slow_par = a.fp.par; }
         }
         PrepArgs pa;
-        pa.rgb = rgb; pa.depth_raw = raw; pa.sem = sem; pa.depth_f32 = nullptr; pa.depthT = s->d_depthT; pa.rgbsT = s->d_rgbsT;
-        pa.keyT = clear_keys ? s->d_keyT : nullptr; pa.dcT = s->d_dcT;
+        pa.rgb = rgb; pa.depth_raw = raw; pa.sem = sem; pa.depth_f32 = nullptr; pa.depthT = f.depthT; pa.rgbsT = f.rgbsT;
+        pa.keyT = clear_keys ? s->keyT() : nullptr; pa.dcT = f.dcT;
         pa.conf_sub = conf_sub;
         const uint32_t n_assoc = carried ? assoc_wgs(s) : 0u;
         const ChainArgs ca = chain ? *chain : ChainArgs{};
@@ -368,8 +368,8 @@ int launch_prep(sm_ctx *s, const uint8_t *rgb, const uint16_t *raw, const uint8_
     // the previous frame of a sharded stream is finished by extra workgroups of this launch
     const ShardSettle *held = s->held.take_settle();
     const ShardSettle ss = held ? *held : ShardSettle{};
-    hipLaunchKernelGGL(k_prep, dim3(tiles + tp.nfb + (ss.n + 3u) / 4u), dim3(1024), 0, s->stream, rgb, raw, sem, (const float *)nullptr, s->d_depthT, s->d_rgbsT,
-                       clear_keys ? s->d_keyT : nullptr, fp, s->d_dcT, conf_sub, tp, ss);
+    hipLaunchKernelGGL(k_prep, dim3(tiles + tp.nfb + (ss.n + 3u) / 4u), dim3(1024), 0, s->stream, rgb, raw, sem, (const float *)nullptr, f.depthT, f.rgbsT,
+                       clear_keys ? s->keyT() : nullptr, fp, f.dcT, conf_sub, tp, ss);
     HIPCK(hipGetLastError());
     return (int)tp.nfb;
 }
@@ -379,9 +379,9 @@ int launch_conflict_test(sm_ctx *s, const FrameParams &fp, bool timed = false)
 {
     if (finalize_if_pending(s)) return SM_E_HIP;
     s->n_conf_part = (uint32_t)grid_surfels(s);
-    hipLaunchKernelGGL(k_conflict, dim3(s->n_conf_part), dim3(256), 0, s->stream, s->M, s->d_state, fp, s->d_dcT,
-                       s->d_cm, s->d_dm, s->d_zm, s->d_tile_cnt, s->d_tb, s->d_tile_flags, s->d_conf_part, s->d_alive,
-                       s->conf_sub());
+    hipLaunchKernelGGL(k_conflict, dim3(s->n_conf_part), dim3(256), 0, s->stream, s->M, s->d_state, fp, s->cur().dcT,
+                       s->d_cm, s->d_dm, s->d_zm, s->d_tile_cnt, s->d_tb, s->cur().tile_flags, s->d_conf_part, s->d_alive,
+                       s->cur().conf_sub);
     HIPCK(hipGetLastError());
     if (s->tl.mark(s->stream, 2, timed)) return SM_E_HIP;
     return SM_OK;
@@ -393,7 +393,7 @@ int launch_conflict_finalize(sm_ctx *s, const FrameParams &fp, bool timed = fals
     if (fp.compact_now) {
         // this cull compacts: the survivor prefixes are needed, scan them with one workgroup per 1024 tiles.
         // A cull that only marks the dead gets its totals from k_conflict's partial sums in the finalize kernel.
-        const int ngroups = std::max<int>(1, (int)((((uint64_t)s->count_bound + TILE - 1) / TILE + GROUP - 1) / GROUP));
+        const int ngroups = std::max<int>(1, (int)((s->slots.tiles() + GROUP - 1) / GROUP));
         hipLaunchKernelGGL(k_scan_cull, dim3(ngroups), dim3(1024), 0, s->stream, s->d_state, s->d_tile_cnt, s->d_tile_allow,
                            s->d_tile_keep, s->d_group_tot, s->d_tile_dead);
         HIPCK(hipGetLastError());
@@ -413,23 +413,10 @@ int launch_conflict(sm_ctx *s, const FrameParams &fp, bool timed = false)
     return launch_conflict_finalize(s, fp, timed);
 }
 
-// The pinned slot statistic (device-written after every cull and append: frames << 32 | occupied slots) against the appends
-// enqueued so far
-// fr, slots: frame tag and occupied slots at the device's last report; ahead: appends enqueued since that report -- known
-// only while the tag is not ahead of the host's count (0 otherwise)
-struct SlotStat { uint32_t fr, slots; bool ahead_known; uint32_t ahead; };
-
-SlotStat read_slot_stat(const sm_ctx *s)
-{
-    const unsigned long long v = __atomic_load_n(s->h_stat.get(), __ATOMIC_RELAXED);
-    const uint32_t fr = (uint32_t)(v >> 32);
-    return {fr, (uint32_t)v, s->frames_enq >= fr, s->frames_enq >= fr ? s->frames_enq - fr : 0u};
-}
-
 struct PassGrid { int split, grid, fix_workers; };
 
-// Grid policy of k_surfel_pass and its fixup step, from an ESTIMATE of the occupied slots -- the pinned statistic plus the measured
-// growth for every append enqueued since -- not from count_bound, which after a hundred unsynchronised frames is the capacity.
+// Grid policy of k_surfel_pass and its fixup step, from an ESTIMATE of the occupied slots (SlotSchedule::estimate_slots), not from
+// the host's bound, which after a hundred unsynchronised frames is the capacity.
 // `two`: two-launch frame, `direct`: the frame appends directly.
 PassGrid pass_grid_policy(sm_ctx *s, bool two, bool direct)
 {
@@ -437,18 +424,7 @@ PassGrid pass_grid_policy(sm_ctx *s, bool two, bool direct)
     // hundred tiles with work), but no more than are RESIDENT once every workgroup has many tiles with work (>= 4 per
     // workgroup: beyond ~8 M slots) -- the surplus would start when the first ones finish and run a second, thin wave
     // (20 M scattered surfels: 160 us with 2 048 workgroups, 140 with 1 536 = 6 per CU, 152 with 5, 172 with 7)
-    uint64_t slots_est = s->count_bound;
-    const SlotStat st = read_slot_stat(s);
-    // growth per frame as the device has reported it (between two reports at least 8 frames apart), at most a frame's candidates
-    if (st.fr < s->est_fr0 || st.slots < s->est_slots0) { s->est_fr0 = st.fr; s->est_slots0 = st.slots; }      // (a compaction, a reset: the rate stands)
-    else if (st.fr >= s->est_fr0 + 8u) {
-        s->est_rate = std::min<uint32_t>((st.slots - s->est_slots0) / (st.fr - s->est_fr0) + 1u, s->n_odd_pixels);
-        s->est_fr0 = st.fr; s->est_slots0 = st.slots;
-    }
-    // (a compaction comes at least every `compact_period` frames: the slots do not grow for longer than that)
-    const uint32_t ahead = std::min<uint32_t>(st.ahead, (uint32_t)std::max(s->cfg.compact_period, 1));
-    if (st.ahead_known) slots_est = std::min<uint64_t>(slots_est, (uint64_t)st.slots + (uint64_t)ahead * s->est_rate);
-    const uint64_t tiles_b = (slots_est + TILE - 1) / TILE;
+    const uint64_t tiles_b = s->slots.tiles_of(s->slots.estimate_slots());
     // (8 192 / 16 384 / never on 100 and 200 KITTI frames: 38.7 / 38.4 / 38.5 us per frame -- the two forms are level there, and a
     //  scattered model pays 1.5x for quarter tiles at 20 M surfels: the lower threshold stays)
     const bool persistent = tiles_b > (uint64_t)(4 * MAX_GRID);
@@ -460,8 +436,7 @@ PassGrid pass_grid_policy(sm_ctx *s, bool two, bool direct)
     if (g.split == 4) {
         // (all of them resident: 2 048 workgroups were 17.5 us where 1 536 are 14.1 -- the last quarter started when the first left)
         const int max_seq = 3 * MAX_GRID / 16;       // 384 sequences = 1 536 workgroups, six per CU
-        const uint64_t tiles_all = ((uint64_t)s->count_bound + TILE - 1) / TILE;
-        g.grid = 4 * (int)std::min<uint64_t>(std::max<uint64_t>(tiles_all, 1), (uint64_t)max_seq);
+        g.grid = 4 * (int)std::min<uint64_t>(std::max<uint64_t>(s->slots.tiles(), 1), (uint64_t)max_seq);
     }
     // fixup workers: the cap repair strides over the tiles; with direct append they first count the frame's candidate pixels, one group each
     g.fix_workers = two ? (int)sm_ctx::N_CREW
@@ -488,18 +463,19 @@ int launch_surfel_pass(sm_ctx *s, const FrameParams &fp, bool timed, bool direct
     pp.n_compact = (uint32_t)grid;
     pp.pass_live = true;
     pp.n_fix = (uint32_t)g.fix_workers;
-    uint32_t *sub = s->conf_sub();
-    const uint32_t tile_bound = (uint32_t)std::max<uint64_t>(((uint64_t)s->count_bound + TILE - 1) / TILE, 1);
+    const FrameSet &f = s->cur();
+    uint32_t *sub = f.conf_sub;
+    const uint32_t tile_bound = (uint32_t)std::max<uint64_t>(s->slots.tiles(), 1);
     if (s->d_pass_trace) s->pass_trace_grid = grid;
     CandArgs ca{};
     ca.n_pass = (uint32_t)grid;
     if (two) {
         ca.n_grp = s->n_grp; ca.cg = s->cand_group; ca.n_pix_blocks = s->n_pix_blocks;
-        ca.depthT = s->d_depthT; ca.xs = s->d_xs; ca.ys = s->d_ys; ca.blk_cand = s->d_blk_cand; ca.grp_cand = s->d_grp_cand;
+        ca.depthT = f.depthT; ca.xs = s->d_xs; ca.ys = s->d_ys; ca.blk_cand = s->d_blk_cand; ca.grp_cand = s->d_grp_cand;
     }
     const auto pass = g.split == 4 ? k_surfel_pass<4> : k_surfel_pass<1>;
-    hipLaunchKernelGGL(pass, dim3(grid + (two ? (int)s->n_grp : 0)), dim3(256), 0, s->stream, s->M, s->d_state, fp, s->d_dcT, s->d_cm, s->d_dm /* km */,
-                       s->d_wave_cnt, s->d_tb, s->d_tile_flags, pp.d_lazy, s->d_alive, s->d_tile_dead, sub, s->d_keyT, s->d_undo, tile_bound,
+    hipLaunchKernelGGL(pass, dim3(grid + (two ? (int)s->n_grp : 0)), dim3(256), 0, s->stream, s->M, s->d_state, fp, f.dcT, s->d_cm, s->d_dm /* km */,
+                       f.wave_cnt, s->d_tb, f.tile_flags, pp.d_lazy, s->d_alive, s->d_tile_dead, sub, s->keyT(), s->d_undo, tile_bound,
                        s->d_frame_sub, ca, s->d_pass_trace);
     HIPCK(hipGetLastError());
     if (s->tl.mark(s->stream, 2, timed) || s->tl.mark(s->stream, 3, timed)) return SM_E_HIP;
@@ -507,17 +483,17 @@ int launch_surfel_pass(sm_ctx *s, const FrameParams &fp, bool timed, bool direct
     DirectArgs &da = x.da;
     da.on = direct ? (two ? 2 : 1) : 0;
     da.blk_cand = s->d_blk_cand; da.grp_cand = s->d_grp_cand; da.n_grp = s->n_grp; da.cg = s->cand_group; da.n_pix_blocks = s->n_pix_blocks;
-    da.depthT = s->d_depthT; da.xs = s->d_xs; da.ys = s->d_ys;
+    da.depthT = f.depthT; da.xs = s->d_xs; da.ys = s->d_ys;
     da.frame_sub = s->d_frame_sub;
-    // the previous frame's new / fused counters: the other set where the sets alternate (its association may run next to this publisher)
-    da.nf_prev = s->defer_ok ? s->d_nf_sub_nx : s->d_nf_sub;
+    // the previous frame's new / fused counters (its association may run next to this publisher)
+    da.nf_prev = s->prev().nf_sub;
     // (the previous frame's fixup partials: only if it appended directly and nothing has completed its statistics since;
     //  the fixup's publisher completes the previous frame's statistics first)
     da.fix_prev = fix_prev; da.n_fix_prev = s->held.take_stats() ? n_fix_prev : 0u;
     da.log = s->d_log;
-    x.cm = s->d_cm; x.km = s->d_dm; x.wave_cnt = s->d_wave_cnt; x.tile_flags = s->d_tile_flags; x.part = pp.d_lazy; x.n_part = (uint32_t)grid;
-    x.fix_part = pp.fix_cur(); x.alive = s->d_alive; x.tile_dead = s->d_tile_dead; x.conf_sub = sub; x.keyT = s->d_keyT; x.undo = s->d_undo;
-    x.host_stat = s->d_stat; x.prep_part = s->d_prep_part; x.n_prep = n_prep; x.tb = s->d_tb; x.n_crew = (uint32_t)g.fix_workers;
+    x.cm = s->d_cm; x.km = s->d_dm; x.wave_cnt = f.wave_cnt; x.tile_flags = f.tile_flags; x.part = pp.d_lazy; x.n_part = (uint32_t)grid;
+    x.fix_part = pp.fix_cur(); x.alive = s->d_alive; x.tile_dead = s->d_tile_dead; x.conf_sub = sub; x.keyT = s->keyT(); x.undo = s->d_undo;
+    x.host_stat = s->d_stat; x.prep_part = f.prep_part; x.n_prep = n_prep; x.tb = s->d_tb; x.n_crew = (uint32_t)g.fix_workers;
     if (two) s->held.hold_fixup(x);
     else if (launch_fixup(s, fp, x)) return SM_E_HIP;
     if (s->tl.mark(s->stream, 4, timed)) return SM_E_HIP;
@@ -528,8 +504,9 @@ int launch_surfel_pass(sm_ctx *s, const FrameParams &fp, bool timed, bool direct
 void fill_assoc_args(const sm_ctx *s, const FrameParams &fp, AssocArgs &a)
 {
     a.M = s->M; a.st = s->d_state; a.fp = fp;
-    a.depthT = s->d_depthT; a.rgbsT = s->d_rgbsT; a.keyT = s->d_keyT; a.xs = s->d_xs; a.ys = s->d_ys;
-    a.blk_cand = s->d_blk_cand; a.grp_cand = s->d_grp_cand; a.nf = s->d_nf_sub; a.tb = s->d_tb;
+    const FrameSet &f = s->cur();
+    a.depthT = f.depthT; a.rgbsT = f.rgbsT; a.keyT = s->keyT(); a.xs = s->d_xs; a.ys = s->d_ys;
+    a.blk_cand = s->d_blk_cand; a.grp_cand = s->d_grp_cand; a.nf = f.nf_sub; a.tb = s->d_tb;
     a.alive = s->d_alive; a.tile_dead = s->d_tile_dead; a.n_grp = s->n_grp; a.cg = s->cand_group; a.host_stat = s->d_stat;
     a.slow_conf_sub = nullptr; a.slow_need = 0u;
 }
@@ -545,8 +522,8 @@ int launch_associate_direct(sm_ctx *s, const FrameParams &fp, bool timed)
     if (s->defer_ok && timed) s->held.hold_assoc(a);
     else if (launch_assoc(s, a, 2u)) return SM_E_HIP;
     s->part.clear();
-    s->held.hold_stats(s->d_nf_sub);
-    s->frames_enq++;
+    s->held.hold_stats(s->cur().nf_sub);
+    s->slots.append_enqueued();
     if (s->tl.mark(s->stream, 5, timed) || s->tl.mark(s->stream, 6, timed) || s->tl.mark(s->stream, 7, timed)) return SM_E_HIP;
     return SM_OK;
 }
@@ -566,61 +543,18 @@ int launch_compact(sm_ctx *s, const FrameParams &fp, bool splat, bool timed)
         return SM_OK;
     }
     const int grid = std::min(grid_surfels(s), s->compact_grid);
-    const uint32_t epoch = ++s->cull_epoch;
+    const uint32_t epoch = s->slots.next_cull_epoch();
     // (a maintenance compaction -- ensure_compact -- kills nothing and draws nothing: what the next append folds stays as it is)
     if (!fp.maintenance) s->part.n_compact = splat ? (uint32_t)grid : 0u;
     FrameParams fpc = fp;
     fpc.compact_tickets = compaction_needs_tickets(s) ? 1 : 0;
     const auto compact = splat ? k_compact<true> : k_compact<false>;
     hipLaunchKernelGGL(compact, dim3(grid), dim3(256), 0, s->stream, s->M, s->d_state, fpc, s->d_cm,
-                       s->d_dm, s->d_zm, s->d_tile_cnt, s->d_tile_allow, s->d_tile_keep, s->d_keyT, s->d_tile_flag, epoch,
-                       s->d_group_base, s->d_tb, s->d_tile_flags, s->part.d_compact, s->d_alive, s->d_tile_dead);
+                       s->d_dm, s->d_zm, s->d_tile_cnt, s->d_tile_allow, s->d_tile_keep, s->keyT(), s->d_tile_flag, epoch,
+                       s->d_group_base, s->d_tb, s->cur().tile_flags, s->part.d_compact, s->d_alive, s->d_tile_dead);
     HIPCK(hipGetLastError());
     if (s->tl.mark(s->stream, 4, timed)) return SM_E_HIP;
     return SM_OK;
-}
-
-// Deferred-compaction schedule.  The HOST decides whether a cull compacts (it must launch the matching kernels, and it
-// must do so without waiting for the device): every `compact_period`-th cull, and whenever dead slots could make the
-// frame overflow the capacity (then the result would differ from the reference's).  The bound on the occupied slots
-// comes from a pinned word the device updates after every cull and append: slots then + one frame's worth of new
-// surfels for every append enqueued since.
-bool decide_compact(sm_ctx *s)
-{
-    if (s->cfg.compact_period <= 1) return true;
-    // Capacity: a cull that only marks the dead must not be able to make the frame overflow because of them.
-    // bound = slots at the last device update + one frame's worth of new surfels for every append enqueued since.
-    // When the host has run far ahead of the device the bound is loose; rather than compacting for nothing it then
-    // lets the device catch up (the queue still holds every frame in between, so the GPU stays busy).
-    // (This is the one place where an "enqueue only" call may wait, and only within one frame's worth of the capacity:
-    //  at most sw.capacity_wait_us, default 2000 us, then it compacts instead.)
-    const auto t_start = std::chrono::steady_clock::now();
-    for (uint32_t spins = 0;; ++spins) {
-        const SlotStat st = read_slot_stat(s);
-        uint64_t bound = s->count_bound;
-        if (st.ahead_known) bound = std::min<uint64_t>(bound, (uint64_t)st.slots + (uint64_t)st.ahead * s->n_odd_pixels);
-        if (bound + s->n_odd_pixels <= s->cap) break;                  // fits even if every candidate pixel is new
-        if (st.ahead <= 1u) return true;                               // the bound is (nearly) exact: compact
-        if ((uint64_t)st.slots + 2ull * s->n_odd_pixels > s->cap) return true;   // would not fit with the device caught up either
-        if ((spins & 63u) == 63u &&
-            std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_start).count() > s->sw.capacity_wait_us)
-            return true;                                               // the device is further behind than we are willing to wait for
-        std::this_thread::yield();
-    }
-    return s->culls_since_compact + 1 >= s->cfg.compact_period;
-}
-
-void note_cull(sm_ctx *s, bool compacted)
-{
-    if (compacted) { s->culls_since_compact = 0; }
-    else { s->culls_since_compact++; s->maybe_garbage = true; }
-}
-
-// refresh the pinned slot statistic after the host changed the model (device idle)
-void publish_stat(sm_ctx *s)
-{
-    __atomic_store_n(s->h_stat.get(), ((unsigned long long)s->h_state->stat_frames << 32) | (unsigned long long)s->h_state->count, __ATOMIC_RELAXED);
-    s->frames_enq = s->h_state->stat_frames;
 }
 
 // after a cull that is not followed by the append kernel (which does this itself): restore the alive mask
@@ -637,12 +571,13 @@ int ss_compact(sm_ctx *s);
 int launch_associate_only(sm_ctx *s, const FrameParams &fp)
 {
     hipLaunchKernelGGL(k_associate, dim3(s->n_pix_blocks), dim3(PIX_BLOCK), 0, s->stream, s->M, s->d_state, fp,
-                       s->d_depthT, s->d_rgbsT, s->d_keyT, s->d_xs, s->d_ys, s->d_validmask, s->d_fusedmask, s->d_blk_cnt, s->d_tb);
+                       s->cur().depthT, s->cur().rgbsT, s->keyT(), s->d_xs, s->d_ys, s->d_validmask, s->d_fusedmask, s->d_blk_cnt, s->d_tb);
     HIPCK(hipGetLastError());
     return SM_OK;
 }
 
-// association + in-place fuse, then the dense ordered append (frames that compact; the frame after reset(); the per-pass API)
+// association + in-place fuse, then the dense ordered append (frames that compact; the frame after reset(); the per-pass API,
+// whose sm_sync pulls the exact bound right after)
 int launch_associate(sm_ctx *s, const FrameParams &fp, bool timed)
 {
     int rc = launch_associate_only(s, fp);
@@ -650,11 +585,11 @@ int launch_associate(sm_ctx *s, const FrameParams &fp, bool timed)
     if (s->tl.mark(s->stream, 5, timed) || s->tl.mark(s->stream, 6, timed)) return SM_E_HIP;
     // the append derives its own prefix from the per-block counts (no scan kernel)
     const PassPartials::Fold f = s->part.fold();
-    hipLaunchKernelGGL(k_append_scan, dim3(s->n_pix_blocks), dim3(PIX_BLOCK), 0, s->stream, s->M, s->d_state, fp, s->d_depthT,
-                       s->d_rgbsT, s->d_xs, s->d_ys, s->d_validmask, s->d_fusedmask, s->d_blk_cnt, s->d_log, s->d_tb, f.compact,
+    hipLaunchKernelGGL(k_append_scan, dim3(s->n_pix_blocks), dim3(PIX_BLOCK), 0, s->stream, s->M, s->d_state, fp, s->cur().depthT,
+                       s->cur().rgbsT, s->d_xs, s->d_ys, s->d_validmask, s->d_fusedmask, s->d_blk_cnt, s->d_log, s->d_tb, f.compact,
                        f.n_compact, s->d_alive, s->d_tile_dead, s->d_stat, f.lazy, f.fix, f.n_fix);
     s->part.clear();
-    s->frames_enq++;
+    s->slots.append_enqueued();
     HIPCK(hipGetLastError());
     if (s->tl.mark(s->stream, 7, timed)) return SM_E_HIP;
     check_alive(s, 5u + 16u * (uint32_t)(s->tick & 0xFFFF));
@@ -666,19 +601,14 @@ int discard_model(sm_ctx *s)
 {
     int rc = pull_state(s);
     if (rc) return rc;
-    if (s->h_state->count == 0 && !s->maybe_garbage && s->h_state->conflict_count == 0 && s->h_state->visible_count == 0) return SM_OK;
-    if (s->maybe_garbage) {
+    if (s->h_state->count == 0 && !s->slots.maybe_garbage() && s->h_state->conflict_count == 0 && s->h_state->visible_count == 0) return SM_OK;
+    if (s->slots.maybe_garbage()) {
         HIPCK(hipMemsetAsync(s->d_alive, 0xFF, s->alive_words * 8, s->stream));
         HIPCK(hipMemsetAsync(s->d_tile_dead, 0, s->dead_tiles * 4, s->stream));
-        s->maybe_garbage = false;
+        s->slots.model_discarded();
     }
     s->h_state->conflict_count = 0; s->h_state->visible_count = 0;      // no conflict pass, no index map in the initialising frame
     return publish_dense(s, 0, 0);
-}
-
-void bump_bound(sm_ctx *s)
-{
-    s->count_bound = (uint32_t)std::min<uint64_t>((uint64_t)s->count_bound + s->n_odd_pixels, s->cap);
 }
 
 // tail of processFrame (src/SurfelMapping.cpp:244-248)
@@ -708,19 +638,11 @@ int begin_frame(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_raw, const ui
     // The reference frame and the frame after reset() do not draw the index map: its textures keep what the last
     // predictIndices left (src/SurfelMapping.cpp:142-169), so the key map is neither cleared nor exchanged then.
     const bool will_splat = fusing;
-    // frame parity: the conflict sub-counters, the frame planes and the per-frame scratch of the fixup step alternate between two
-    // sets, so that the pre-processing of frame f+1 never touches what frame f still reads
+    // frame parity: the frame takes the other FrameSet, so that the pre-processing of frame f+1 never touches what frame f still
+    // reads; the key map follows on the frames that draw it
     s->plane_set ^= 1;
     fp.par = s->plane_set;
-    if (s->defer_ok) {
-        std::swap(s->d_depthT, s->d_depthT_nx); std::swap(s->d_rgbsT, s->d_rgbsT_nx);
-        std::swap(s->d_dcT, s->d_dcT_nx);
-        if (will_splat) std::swap(s->d_keyT, s->d_keyT_nx);
-        // per-frame scratch the previous frame's publisher / repair crew may still read while this frame's flag workgroups and
-        // association write theirs (two-launch frame)
-        std::swap(s->d_tile_flags, s->d_tile_flags_nx); std::swap(s->d_wave_cnt, s->d_wave_cnt_nx);
-        std::swap(s->d_prep_part, s->d_prep_part_nx); std::swap(s->d_nf_sub, s->d_nf_sub_nx);
-    }
+    if (s->defer_ok && will_splat) s->key_set ^= 1;
     // metriciseDepth + filterDepth + removeMovings (src/SurfelMapping.cpp:136-139,156,254-365): with preprocess = 1 the whole
     // chain is one stage of the preparation launch (prep_chain_block); the reference frame stops before removeMovings
     ChainArgs ca{};
@@ -737,7 +659,7 @@ int begin_frame(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_raw, const ui
     if ((rc = launch_prep(s, d_rgb, d_raw, d_sem, fp, will_splat, tile_flags, carry, s->cfg.preprocess ? &ca : nullptr)) < 0) return rc;
     *n_prep = (uint32_t)rc;
     // preprocess == 0: DEPTH_FILTERED and LAST are the metric depth itself (nothing reads them on the
-    // hot path); they alias d_depthT in sm_download_depth instead of being copied every frame.
+    // hot path); they alias the frame's depthT in sm_download_depth instead of being copied every frame.
     if (!s->ref_set) {                                    // src/SurfelMapping.cpp:142-154
         if (s->cfg.preprocess) std::swap(s->d_lastT, s->d_filteredT);   // LAST <- DEPTH_FILTERED without a copy
         memcpy(s->last_pose, s->curr_pose, 64);
@@ -760,7 +682,6 @@ int begin_frame(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_raw, const ui
         s->part.clear();
         s->part.n_compact = 0;                            // no cull / splat ran: nothing to fold into visible_count
         if ((rc = launch_associate(s, fp, false))) return rc;
-        bump_bound(s);
         end_frame(s, false);
         return 0;
     }
@@ -778,7 +699,7 @@ int enqueue_frame(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_raw, const 
     // the cull's kind is decided first: a frame whose cull only marks the dead lets k_prep evaluate the tile skip flags for
     // the one-pass surfel kernel
     const bool fusing = s->ref_set && s->tick != 0 && !s->pending_cull;
-    const bool compact_now = fusing ? decide_compact(s) : true;
+    const bool compact_now = fusing ? s->slots.decide_compact() : true;
     // a held-back association rides on this frame's k_prep launch if this is again a fusing frame; anything else (the frame
     // after reset, ...) needs its results first
     // (a compacting frame too: its k_prep launch has no tile flags to make; the doubled words of DevState a merged publisher
@@ -790,8 +711,8 @@ int enqueue_frame(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_raw, const 
     rc = begin_frame(s, d_rgb, d_raw, d_sem, pose, fusing && !compact_now, carry, &fp, &n_prep);
     if (rc <= 0) return rc;
     fp.compact_now = compact_now ? 1u : 0u;
-    note_cull(s, fp.compact_now != 0u);
-    s->keys_are_slots = fp.compact_now == 0u;      // this frame's splat writes slot numbers iff nothing moves
+    s->slots.cull_noted(fp.compact_now != 0u);
+    s->slots.keys_drawn(fp.compact_now == 0u);      // this frame's splat writes slot numbers iff nothing moves
     // a cull that only marks the dead is ONE pass over the surfels (k_surfel_pass + k_pass_fixup: conflict test, decrement, cull,
     // splat), and the association appends the new surfels directly (no append kernel)
     const bool one_pass = !fp.compact_now;
@@ -800,14 +721,12 @@ int enqueue_frame(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_raw, const 
     if (one_pass) {
         if ((rc = launch_surfel_pass(s, fp, true, true, n_prep))) return rc;        // :178-197
         if ((rc = launch_associate_direct(s, fp, true))) return rc;         // :212-239
-        bump_bound(s);
         end_frame(s);
         return SM_OK;
     }
     if ((rc = launch_conflict(s, fp, true))) return rc;           // :178-187
     if ((rc = launch_compact(s, fp, true, true))) return rc;      // :189-197 (cull + mirror + index map)
     if ((rc = launch_associate(s, fp, true))) return rc;   // :212-239
-    bump_bound(s);
     end_frame(s);
     return SM_OK;
 }
@@ -822,6 +741,23 @@ int upload_inputs(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth, const ui
     return SM_OK;
 }
 
+// one FrameSet's buffers (s->frame_mem owns them): the planes and the skip flags zeroed
+int alloc_frame_set(sm_ctx *s, FrameSet &f)
+{
+    auto get = [s](auto *&p, size_t n, bool zero) -> int {
+        Dev<void> m;
+        const size_t bytes = std::max<size_t>(n, 1) * sizeof *p;
+        HIPCK(hipMalloc(m.put(), bytes));
+        if (zero) HIPCK(hipMemset(m, 0, bytes));
+        p = static_cast<std::remove_reference_t<decltype(p)>>(m.get());
+        s->frame_mem.push_back(std::move(m));
+        return SM_OK;
+    };
+    const size_t P = (size_t)s->P;
+    return get(f.depthT, P, true) || get(f.rgbsT, P, true) || get(f.dcT, P, true) || get(f.tile_flags, s->tb_tiles, true) ||
+           get(f.wave_cnt, s->dead_tiles, false) || get(f.prep_part, 256, false) ? SM_E_HIP : SM_OK;
+}
+
 // sm_create's buffers in order, up to the first failure (g_err is set only where dalloc failed)
 int alloc_ctx(sm_ctx *s)
 {
@@ -830,11 +766,10 @@ int alloc_ctx(sm_ctx *s)
         alloc_set(s->m_bufs[0], cap) ||      // one SoA set: the compaction is in place
         dalloc(s->d_state, 1) || dalloc(s->d_log, FRAME_LOG_LEN) || hipHostMalloc(s->h_state.put(), sizeof(DevState), hipHostMallocDefault) != hipSuccess ||
         hipHostMalloc(s->h_stat.put(), 8, hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer((void **)&s->d_stat, s->h_stat, 0) != hipSuccess ||
-        dalloc(s->d_depthT, P) || dalloc(s->d_filteredT, P) || dalloc(s->d_lastT, P) || dalloc(s->d_rgbsT, P) || dalloc(s->d_keyT, P) ||
-        dalloc(s->d_dcT, P) || hipMemset(s->d_dcT, 0, P * 8) != hipSuccess ||
-        (s->defer_ok && (dalloc(s->d_depthT_nx, P) || dalloc(s->d_rgbsT_nx, P) || dalloc(s->d_keyT_nx, P) || dalloc(s->d_dcT_nx, P) ||
-                         hipMemset(s->d_depthT_nx, 0, P * 4) != hipSuccess || hipMemset(s->d_rgbsT_nx, 0, P * 4) != hipSuccess ||
-                         hipMemset(s->d_dcT_nx, 0, P * 8) != hipSuccess)) ||
+        dalloc(s->d_filteredT, P) || dalloc(s->d_lastT, P) ||
+        // what alternates between frames: twice where a frame's association is held back, else both frames see the one set
+        alloc_frame_set(s, s->fset[0]) || dalloc(s->d_key[0], P) ||
+        (s->defer_ok && (alloc_frame_set(s, s->fset[1]) || dalloc(s->d_key[1], P))) ||
         dalloc(s->d_rgb, P * 3) || dalloc(s->d_sem, P) || dalloc(s->d_depth_raw, P) || dalloc(s->d_depth_f32, P) ||
         dalloc(s->d_xs, (size_t)s->W * 2) || dalloc(s->d_ys, (size_t)s->H * 2) ||
         dalloc(s->d_cm, nwords) || dalloc(s->d_dm, nwords) || dalloc(s->d_zm, nwords) ||
@@ -844,18 +779,17 @@ int alloc_ctx(sm_ctx *s)
         hipMemset(s->d_tile_flag, 0, ntiles * 4) != hipSuccess ||
         dalloc(s->d_group_tot, (ntiles / GROUP + 2) * 4) || dalloc(s->d_group_base, ntiles / GROUP + 2) ||
         dalloc(s->d_conf_part, (size_t)MAX_GRID * 4) || dalloc(s->part.d_compact, (size_t)MAX_GRID) || dalloc(s->part.d_lazy, (size_t)MAX_GRID) ||
-        dalloc(s->part.d_fix, (size_t)MAX_GRID * 2 + 2) || dalloc(s->d_wave_cnt, ntiles) || dalloc(s->d_undo, cap + TILE) ||
-        dalloc(s->d_conf_sub, (size_t)2 * SUB_SET) || dalloc(s->d_prep_part, (size_t)256) || hipMemset(s->d_conf_sub, 0, (size_t)2 * SUB_SET * 4) != hipSuccess ||
-        dalloc(s->d_tb, tb * 8) || dalloc(s->d_tile_flags, tb) || hipMemset(s->d_tile_flags, 0, tb) != hipSuccess ||
+        dalloc(s->part.d_fix, (size_t)MAX_GRID * 2 + 2) || dalloc(s->d_undo, cap + TILE) ||
+        dalloc(s->d_conf_sub, (size_t)2 * SUB_SET) || hipMemset(s->d_conf_sub, 0, (size_t)2 * SUB_SET * 4) != hipSuccess ||
+        dalloc(s->d_tb, tb * 8) ||
         dalloc(s->d_validmask, (P + 63) / 64 + 4) || dalloc(s->d_fusedmask, (P + 63) / 64 + 4) || dalloc(s->d_blk_cnt, (size_t)s->n_pix_blocks) ||
         dalloc(s->d_blk_cand, (size_t)s->n_grp * CAND_GROUP_MAX) || dalloc(s->d_grp_cand, (size_t)s->n_grp) ||
-        dalloc(s->d_frame_sub, (size_t)6 * SUB_SET) || hipMemset(s->d_frame_sub, 0, (size_t)6 * SUB_SET * 4) != hipSuccess ||
-        (s->defer_ok && (dalloc(s->d_tile_flags_nx, tb) || hipMemset(s->d_tile_flags_nx, 0, tb) != hipSuccess ||
-                         dalloc(s->d_wave_cnt_nx, ntiles) || dalloc(s->d_prep_part_nx, (size_t)256))))
+        dalloc(s->d_frame_sub, (size_t)6 * SUB_SET) || hipMemset(s->d_frame_sub, 0, (size_t)6 * SUB_SET * 4) != hipSuccess)
         return SM_E_HIP;
     s->M.s[0] = s->m_bufs[0].view();
     *s->h_stat = 0ull;
-    s->d_nf_sub = s->d_frame_sub + 2 * SUB_SET; s->d_nf_sub_nx = s->d_frame_sub + 4 * SUB_SET;
+    for (int i = 0; i < 2; ++i) { s->fset[i].nf_sub = s->d_frame_sub + (2 + 2 * i) * SUB_SET; s->fset[i].conf_sub = s->d_conf_sub + i * SUB_SET; }
+    if (!s->defer_ok) s->alias_frame_sets();
     return SM_OK;
 }
 
@@ -941,7 +875,7 @@ int sm_impl::push_state(sm_ctx *s)
 {
     HIPCK(hipMemcpyAsync(s->d_state, s->h_state, sizeof(DevState), hipMemcpyHostToDevice, s->stream));
     HIPCK(hipStreamSynchronize(s->stream));
-    publish_stat(s);
+    s->slots.state_pushed(s->h_state->stat_frames, s->h_state->count);      // the pinned statistic follows what the host wrote
     return SM_OK;
 }
 
@@ -968,7 +902,7 @@ int sm_impl::pull_state(sm_ctx *s)
     s->counts.fused_count = d.fused_count;
     s->counts.visible_count = d.visible_count;
     s->counts.tick = s->tick;
-    s->count_bound = std::max(d.count, d.cull_n * (s->pending_cull ? 1u : 0u));
+    s->slots.state_pulled(d.count, d.cull_n, s->pending_cull);
     return SM_OK;
 }
 
@@ -986,13 +920,13 @@ int sm_impl::ensure_compact(sm_ctx *s)
         HIPCK(hipStreamSynchronize(s->stream));
         return SM_OK;
     }
-    if (!s->maybe_garbage) return SM_OK;
+    if (!s->slots.maybe_garbage()) return SM_OK;
     if (s->pending_cull) { g_err = "internal: deferred compaction with a pending per-pass cull"; return SM_E_ARG; }
     FrameParams fp = make_params(s, s->curr_pose);
     fp.maintenance = 1;
     fp.compact_now = 1;
     fp.conflict_cap = 0xFFFFFFFFu;
-    const uint64_t tiles = ((uint64_t)s->count_bound + TILE - 1) / TILE + 1;
+    const uint64_t tiles = s->slots.tiles() + 1;
     const size_t words = std::min<size_t>(tiles * TILE_WORDS, s->alive_words);
     HIPCK(hipMemsetAsync(s->d_cm, 0, words * 8, s->stream));
     HIPCK(hipMemsetAsync(s->d_dm, 0, words * 8, s->stream));
@@ -1004,16 +938,14 @@ int sm_impl::ensure_compact(sm_ctx *s)
     hipLaunchKernelGGL(k_cull_finalize, dim3(1), dim3(1024), 0, s->stream, s->d_state, fp, s->d_cm, s->d_dm, s->d_zm,
                        s->d_tile_cnt, s->d_tile_allow, s->d_tile_keep, s->d_group_tot, s->d_group_base, s->d_conf_part, 0u,
                        s->d_alive, s->d_tile_dead, s->d_stat);
-    if (s->keys_are_slots)     // ids of the index map: slot -> position among the live surfels, as the API hands them out
-        hipLaunchKernelGGL(k_remap_keys, dim3((s->P + 255) / 256), dim3(256), 0, s->stream, s->d_state, s->d_keyT, s->P, s->d_alive,
+    if (s->slots.keys_are_slots())     // ids of the index map: slot -> position among the live surfels, as the API hands them out
+        hipLaunchKernelGGL(k_remap_keys, dim3((s->P + 255) / 256), dim3(256), 0, s->stream, s->d_state, s->keyT(), s->P, s->d_alive,
                            s->d_tile_keep, s->d_group_base);
-    s->keys_are_slots = false;
     HIPCK(hipGetLastError());
     int rc = launch_compact(s, fp, false, false);
     if (rc) return rc;
     if ((rc = launch_post_fill(s))) return rc;
-    s->maybe_garbage = false;
-    s->culls_since_compact = 0;
+    s->slots.compacted_outside_frame();
     HIPCK(hipStreamSynchronize(s->stream));
     return SM_OK;
 }
@@ -1043,7 +975,7 @@ int sm_impl::publish_dense(sm_ctx *s, uint32_t count, uint32_t first_new)
     d.count = count;                             // src/GlobalModel.cpp:995
     d.offset = count;
     d.garbage = 0; d.garbage_prev = 0; d.first_live = 0; d.do_compact = 0;
-    s->culls_since_compact = 0;
+    s->slots.published_dense();
     int rc = push_state(s);
     if (rc) return rc;
     if ((rc = rebuild_bounds(s, first_new, count))) return rc;
@@ -1085,7 +1017,7 @@ int sm_impl::clean_points_device(sm_ctx *s, const uint16_t *d_depth_mm, const ui
     fp.conflict_thresh = 0.1f;                  // :516
     fp.is_clean = 1;                            // :517
     fp.no_exempt = exempt_first ? 0 : 1;
-    fp.compact_now = decide_compact(s) ? 1u : 0u;
+    fp.compact_now = s->slots.decide_compact() ? 1u : 0u;
     if ((rc = launch_conflict_test(s, fp))) return rc;
     if (cap_hook) {
         std::vector<uint32_t> part((size_t)s->n_conf_part * 4);
@@ -1097,7 +1029,7 @@ int sm_impl::clean_points_device(sm_ctx *s, const uint16_t *d_depth_mm, const ui
         if (allow < 0) return (int)allow;
         fp.conflict_cap = (uint32_t)std::min<long long>(allow, 0xFFFFFFFFll);
     }
-    note_cull(s, fp.compact_now != 0u);
+    s->slots.cull_noted(fp.compact_now != 0u);
     if ((rc = launch_conflict_finalize(s, fp))) return rc;
     if ((rc = launch_compact(s, fp, false, false))) return rc;
     if ((rc = launch_post_fill(s))) return rc;
@@ -1195,7 +1127,7 @@ sm_ctx *sm_create(const sm_config *c)
         return nullptr;
     }
     for (int i = 0; i < s->W; ++i) odd += (uint32_t)((s->H + ((i & 1) ? 1 : 0)) / 2);
-    s->n_odd_pixels = odd;
+    s->slots = sm_slots::SlotSchedule(TILE, s->cap, odd, c->compact_period, s->sw.capacity_wait_us, s->h_stat.get());      // a frame's candidate pixels: the most it can append
     // depth_smooth.frag weights: the host passes 0.5/30^2 as "sigPix" (src/SurfelMapping.cpp:292-309)
     float *wtab = s->h_wtab;
     {
@@ -1209,14 +1141,13 @@ sm_ctx *sm_create(const sm_config *c)
     bool ok = hipMemcpy(s->d_xs, xs.data(), xs.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
          hipMemcpy(s->d_ys, ys.data(), ys.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
          hipMemcpy(s->d_state, s->h_state, sizeof(DevState), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemset(s->d_depthT, 0, P * 4) == hipSuccess && hipMemset(s->d_filteredT, 0, P * 4) == hipSuccess &&
-         hipMemset(s->d_lastT, 0, P * 4) == hipSuccess && hipMemset(s->d_rgbsT, 0, P * 4) == hipSuccess &&
+         hipMemset(s->d_filteredT, 0, P * 4) == hipSuccess && hipMemset(s->d_lastT, 0, P * 4) == hipSuccess &&
          hipMemset(s->d_rgb, 0, P * 3) == hipSuccess && hipMemset(s->d_sem, 0, P) == hipSuccess &&
          hipMemset(s->d_depth_raw, 0, P * 2) == hipSuccess && hipMemset(s->d_depth_f32, 0, P * 4) == hipSuccess &&
          hipDeviceSynchronize() == hipSuccess;
     if (ok) {
         hipLaunchKernelGGL(k_tile_bounds_reset, dim3((s->tb_tiles + 255) / 256), dim3(256), 0, s->stream, s->d_tb, 0u, s->tb_tiles);
-        fill_keys(s.get(), s->d_keyT, s->P);
+        fill_keys(s.get(), s->keyT(), s->P);
         ok = hipStreamSynchronize(s->stream) == hipSuccess;
     }
     if (!ok) { g_err = "sm_create: device initialisation failed"; return nullptr; }
@@ -1491,8 +1422,8 @@ int sm_set_frame(sm_ctx *s, const uint8_t *rgb, const float *depth_metric, const
     ShardSettle ss;
     memset(&ss, 0, sizeof ss);
     hipLaunchKernelGGL(k_prep, dim3(tiles), dim3(1024), 0, s->stream, s->d_rgb, (const uint16_t *)nullptr, s->d_sem,
-                       depth_metric ? s->d_depth_f32 : nullptr, depth_metric ? s->d_depthT : nullptr, s->d_rgbsT,
-                       (uint64_t *)nullptr, fp, s->d_dcT, (uint32_t *)nullptr, tp, ss);
+                       depth_metric ? s->d_depth_f32 : nullptr, depth_metric ? s->cur().depthT : nullptr, s->cur().rgbsT,
+                       (uint64_t *)nullptr, fp, s->cur().dcT, (uint32_t *)nullptr, tp, ss);
     HIPCK(hipGetLastError());
     HIPCK(hipStreamSynchronize(s->stream));
     return SM_OK;
@@ -1562,10 +1493,10 @@ int sm_stage_splat(sm_ctx *s, const float *pose16, int32_t time, float depth_cut
     HIPCK(hipMemsetAsync(&s->d_state->visible_count, 0, 4, s->stream));
     s->part.clear();
     s->part.n_compact = 0;                       // k_splat counts with an atomic; no k_compact partials to fold in
-    fill_keys(s, s->d_keyT, s->P);
+    fill_keys(s, s->keyT(), s->P);
     HIPCK(hipGetLastError());
     const int grid = (int)std::min<uint64_t>(std::max<uint64_t>(((uint64_t)s->h_state->count + 255) / 256, 1), MAX_GRID);
-    hipLaunchKernelGGL(k_splat, dim3(grid), dim3(256), 0, s->stream, s->M, s->d_state, fp, s->d_keyT);
+    hipLaunchKernelGGL(k_splat, dim3(grid), dim3(256), 0, s->stream, s->M, s->d_state, fp, s->keyT());
     HIPCK(hipGetLastError());
     return sm_sync(s);
 }
@@ -1724,8 +1655,8 @@ namespace {
 int ss_compact(sm_ctx *s)
 {
     if (finalize_if_pending(s)) return SM_E_HIP;
-    const uint64_t nw = ((uint64_t)s->count_bound + 63) / 64;
-    const uint64_t tiles = ((uint64_t)s->count_bound + TILE - 1) / TILE;
+    const uint64_t nw = ((uint64_t)s->slots.bound() + 63) / 64;
+    const uint64_t tiles = s->slots.tiles();
     const int g1 = (int)std::min<uint64_t>(std::max<uint64_t>((nw + 255) / 256, 1), 1024);
     const int gt = (int)std::min<uint64_t>(std::max<uint64_t>(tiles, 1), MAX_GRID);
     hipLaunchKernelGGL(k_shard_alive_copy, dim3(g1), dim3(256), 0, s->stream, s->d_state, s->d_alive, s->d_galive, s->d_new_alive, (uint32_t)nw);
@@ -1739,8 +1670,7 @@ int ss_compact(sm_ctx *s)
     hipLaunchKernelGGL(k_shard_unstage, dim3(gt), dim3(256), 0, s->stream, s->M, s->d_state, s->d_ss_info, s->d_new_alive, s->d_alive,
                        s->d_tile_dead, s->d_tb);
     HIPCK(hipGetLastError());
-    s->culls_since_compact = 0;
-    s->keys_are_slots = false;
+    s->slots.compacted_sharded();
     s->part.clear();
     return SM_OK;
 }
@@ -1756,7 +1686,7 @@ int sm_shard_stream_configure(sm_ctx *s, int rank, int world)
     if (s->ss_on) { g_err = "sm_shard_stream_configure: already configured"; return SM_E_ARG; }
     int rc = pull_state(s);
     if (rc) return rc;
-    if (s->h_state->count != 0 || s->maybe_garbage || s->tick != 0 || s->ref_set) {
+    if (s->h_state->count != 0 || s->slots.maybe_garbage() || s->tick != 0 || s->ref_set) {
         g_err = "sm_shard_stream_configure: the context must be new (no frame, no model)";
         return SM_E_ARG;
     }
@@ -1773,7 +1703,8 @@ int sm_shard_stream_configure(sm_ctx *s, int rank, int world)
     s->d_galive = std::move(galive); s->d_new_alive = std::move(new_alive); s->d_gmask = std::move(gmask);
     s->d_ss_info = std::move(info); s->d_capx = std::move(capx);
     s->ss_on = true; s->ss_rank = rank; s->ss_world = world; s->ss_frames = 0;
-    s->defer_ok = false;                       // the association of a sharded frame sits between two collectives
+    s->defer_ok = false;                       // the association of a sharded frame sits between two collectives:
+    s->alias_frame_sets();                     // one set of buffers from here on (no frame has run: the first)
     return SM_OK;
 }
 
@@ -1804,14 +1735,14 @@ int sm_shard_frame_device(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_dep
     if (fusing) {
         // The compaction schedule must be the same on every rank: the period counter, and a capacity bound that only uses
         // what all ranks know (after a synchronisation the host's bound is the device's count, identical everywhere).
-        bool compact = s->cfg.compact_period <= 1 || s->culls_since_compact + 1 >= s->cfg.compact_period;
-        if (!compact && (uint64_t)s->count_bound + s->n_odd_pixels > s->cap) {
+        bool compact = s->slots.period_due();
+        if (!compact && s->slots.bound_may_overflow()) {
             if ((rc = pull_state(s))) return rc;
-            compact = (uint64_t)s->count_bound + s->n_odd_pixels > s->cap;
+            compact = s->slots.bound_may_overflow();
         }
-        if (compact && s->culls_since_compact > 0) {
+        if (compact && s->slots.culls_since_compact() > 0) {
             if ((rc = ss_compact(s))) return rc;
-            if ((uint64_t)s->count_bound + s->n_odd_pixels > s->cap && (rc = pull_state(s))) return rc;
+            if (s->slots.bound_may_overflow() && (rc = pull_state(s))) return rc;
         }
     }
     FrameParams fp;
@@ -1821,27 +1752,27 @@ int sm_shard_frame_device(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_dep
     fp.compact_now = 0u;
     fp.conflict_cap = 0xFFFFFFFFu;            // applied over all ranks below (k_shard_cap_pack / k_shard_cap_repair), not per shard
     fp.shard_slots = 1;
-    note_cull(s, false);
-    s->keys_are_slots = true;
+    s->slots.cull_noted(false);
+    s->slots.keys_drawn(true);
     Timeline::Flags &fl = s->tl.frame();
     fl.compacted = false; fl.one_pass = fl.direct = true;
     if ((rc = launch_surfel_pass(s, fp, true, true, n_prep))) return rc;
     // The W*H conflict cap acts in surfel order over ALL ranks: exchange the conflict masks and take this rank's surplus back
     // before anything reads the key map (k_shard_cap_pack / k_shard_cap_repair).  Conflicts <= surfels, so a model with no
     // more slots than pixels cannot reach the cap; the bound is the host's, the same on every rank.
-    if (s->cfg.conflict_cap && (uint64_t)s->count_bound > (uint64_t)s->P) {
-        const uint32_t tbnd = (uint32_t)std::min<uint64_t>(((uint64_t)s->count_bound + TILE - 1) / TILE, s->dead_tiles);
+    if (s->cfg.conflict_cap && (uint64_t)s->slots.bound() > (uint64_t)s->P) {
+        const uint32_t tbnd = (uint32_t)std::min<uint64_t>(s->slots.tiles(), s->dead_tiles);
         const int gp = (int)std::min<uint32_t>(std::max<uint32_t>((tbnd * (uint32_t)TILE_WORDS + 255u) / 256u, 1u), 1024u);
-        hipLaunchKernelGGL(k_shard_cap_pack, dim3(gp), dim3(256), 0, s->stream, s->d_state, s->d_wave_cnt, s->d_cm,
-                           s->conf_sub(), s->d_capx, tbnd);
+        hipLaunchKernelGGL(k_shard_cap_pack, dim3(gp), dim3(256), 0, s->stream, s->d_state, s->cur().wave_cnt, s->d_cm,
+                           s->cur().conf_sub, s->d_capx, tbnd);
         HIPCK(hipGetLastError());
         if ((rc = ss_collective(s, s->d_capx, s->d_capx, (size_t)1 + (size_t)(2 + TILE_WORDS) * tbnd, SM_COLL_SUM))) return rc;
         hipLaunchKernelGGL(k_shard_cap_repair, dim3(std::min<uint32_t>(std::max<uint32_t>(tbnd, 1u), (uint32_t)MAX_GRID)), dim3(256), 0, s->stream, s->M,
-                           s->d_state, fp, s->d_capx, tbnd, (uint32_t)s->P, s->d_wave_cnt, s->d_dm /* km */, s->d_tile_flags, s->d_alive,
-                           s->d_tile_dead, s->d_keyT, s->d_undo, s->d_tb);
+                           s->d_state, fp, s->d_capx, tbnd, (uint32_t)s->P, s->cur().wave_cnt, s->d_dm /* km */, s->cur().tile_flags, s->d_alive,
+                           s->d_tile_dead, s->keyT(), s->d_undo, s->d_tb);
         HIPCK(hipGetLastError());
     }
-    if ((rc = ss_collective(s, s->d_keyT, s->d_keyT, (size_t)s->P, SM_COLL_MIN))) return rc;
+    if ((rc = ss_collective(s, s->keyT(), s->keyT(), (size_t)s->P, SM_COLL_MIN))) return rc;
     ShardArgs sh;
     sh.validmask = s->d_validmask; sh.ownmask = s->d_fusedmask; sh.gmask = s->d_gmask; sh.nwords = (uint32_t)((s->P + 63) / 64);
     sh.owner = (int)(s->ss_frames % (uint32_t)s->ss_world) == s->ss_rank ? 1 : 0;
@@ -1855,15 +1786,14 @@ int sm_shard_frame_device(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_dep
     // only needed by the next frame's surfel pass: it rides on that frame's k_prep (finalize_if_pending runs it earlier if asked)
     ShardSettle ss;
     ss.n = (uint32_t)s->n_pix_blocks; ss.st = s->d_state; ss.validmask = s->d_validmask; ss.ownmask = s->d_fusedmask; ss.gmask = s->d_gmask;
-    ss.nwords = sh.nwords; ss.blk_cand = s->d_blk_cand; ss.grp_cand = s->d_grp_cand; ss.nf = s->d_nf_sub; ss.alive = s->d_alive;
+    ss.nwords = sh.nwords; ss.blk_cand = s->d_blk_cand; ss.grp_cand = s->d_grp_cand; ss.nf = s->cur().nf_sub; ss.alive = s->d_alive;
     ss.tile_dead = s->d_tile_dead; ss.owner = sh.owner; ss.cap_pixels = s->cfg.conflict_cap ? (uint32_t)s->P : 0xFFFFFFFFu; ss.max_vertices = s->cap; ss.cg = s->cand_group;
     s->held.hold_settle(ss);
     if ((rc = s->tl.mark(s->stream, 6, true)) || (rc = s->tl.mark(s->stream, 7, true))) return rc;
     s->part.clear();
-    s->held.hold_stats(s->d_nf_sub);
-    s->frames_enq++;
+    s->held.hold_stats(s->cur().nf_sub);
+    s->slots.append_enqueued();
     s->ss_frames++;
-    bump_bound(s);
     end_frame(s);
     return SM_OK;
 }

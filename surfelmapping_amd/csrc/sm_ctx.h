@@ -13,11 +13,13 @@
 //   sm_recall.hip    paging in (sm_recall*, sm_set_auto_recall): records of map files near the camera back into the model
 //   sm_warp.hip      closing loops (sm_warp_by_time, sm_loop_spread): the model and map files warped by surfel time
 // and, beside it, for everything that touches a map file: sm_mapfile.h (the format: checked open, writer, chunk plan; host only)
-// and sm_map_stream.h (the double-buffered chunk stream of sm_render_maps.hip and sm_recall.hip).
+// and sm_map_stream.h (the double-buffered chunk stream of sm_render_maps.hip and sm_recall.hip); for the occupied slots and the
+// compaction schedule: sm_slots.h (SlotSchedule; host only).  What alternates between consecutive frames is FrameSet, below.
 #pragma once
 
 #include "../../include/sm_c_api.h"
 #include "sm_device.h"
+#include "sm_slots.h"
 
 #include <hip/hip_runtime.h>
 
@@ -214,7 +216,7 @@ struct Switches {
     std::string trace_prefix;          //   dumped by sm_destroy (tools/pass_trace.py)
     int compact_tickets = -1;          // SM_COMPACT_TICKETS=1: compactions always use the ticket-ordered kernel (several PROCESSES share a GPU);
                                        //   =0: never (contexts known not to run at the same time); unset: decided per compaction
-    long capacity_wait_us = 2000;      // SM_CAPACITY_WAIT_US: how long an enqueue may let the device catch up before it compacts instead (decide_compact)
+    long capacity_wait_us = 2000;      // SM_CAPACITY_WAIT_US: how long an enqueue may let the device catch up before it compacts instead (SlotSchedule::decide_compact)
     bool check_alive = false;          // SM_CHECK_ALIVE (diagnostic): check the alive-bits / dead-count invariant after every stage; reported by sm_sync
     int pass_wg_per_cu = 0;            // SM_PASS_WG_PER_CU: workgroups of k_surfel_pass per CU taken as resident (0: what the occupancy query says)
     int compact_wg_per_cu = 0;         // SM_COMPACT_WG_PER_CU: the same for k_compact, within what the occupancy query allows (experiments)
@@ -252,6 +254,21 @@ private:
     AssocArgs assoc_{};
     ShardSettle settle_{};
     uint32_t *nf_ = nullptr;
+};
+
+// What alternates between consecutive frames (views; sm_ctx::frame_mem owns the memory).  A frame's association is held back and
+// runs in the NEXT frame's preparation launch, which writes the other set; in a two-launch frame its fixup step rides on that
+// launch too, so the per-frame scratch its publisher and repair crew read while the next frame's flag workgroups and association
+// write theirs alternates as well.
+struct FrameSet {
+    float *depthT = nullptr;           // column-major frame images
+    uint32_t *rgbsT = nullptr;
+    uint2 *dcT = nullptr;              // (depth bits, rgbs) of the frame the conflict test sees
+    uint8_t *tile_flags = nullptr;     // per-tile skip flags, evaluated by extra workgroups of the preparation launch
+    uint4 *wave_cnt = nullptr;         // conflicts per quarter tile (one word per wave)
+    uint2 *prep_part = nullptr;        // the flag workgroups' skip statistics
+    uint32_t *nf_sub = nullptr;        // 2 x 64 sub-counters: new, fused (k_associate_direct)
+    uint32_t *conf_sub = nullptr;      // 64 conflict sub-counters (zeroed by the frame's k_prep)
 };
 
 // Per-workgroup partial sums a frame's cull / pass leaves for the append that follows it (instead of same-address atomics)
@@ -302,20 +319,25 @@ struct sm_ctx {
     sm_config cfg{};
     int W = 0, H = 0, P = 0;
     uint32_t cap = 0;                 // MAX_VERTICES
-    // The four frame planes exist twice (the *_nx pointers are the set of the other frame): a frame's association is held back
-    // and runs in the NEXT frame's preparation launch, which writes the other set.  (Rounds 1-2 ran the depth filter chain of
-    // frame f+1 on a second stream instead; since round 3 the chain is a stage of the preparation launch itself.)
-    int plane_set = 0;                 // which plane set the current frame uses
+    // Frame parity: begin_frame flips plane_set, and with it the FrameSet the frame uses.  A context that does not defer
+    // (SM_DEFER_ASSOC=0, a sharded stream) has ONE set of buffers -- fset[1] views fset[0]'s (alias_frame_sets) -- and the conflict
+    // sub-counters alternate all the same.  (Rounds 1-2 ran the depth filter chain of frame f+1 on a second stream instead; since
+    // round 3 the chain is a stage of the preparation launch itself.)
+    int plane_set = 0;                 // which set the current frame uses (FrameParams::par)
+    FrameSet fset[2];
+    const FrameSet &cur() const { return fset[plane_set]; }        // the current frame's
+    const FrameSet &prev() const { return fset[plane_set ^ 1]; }   // the previous frame's: what its held-back steps still read
+    void alias_frame_sets() { uint32_t *c = fset[1].conf_sub; fset[1] = fset[0]; fset[1].conf_sub = c; }
+    // the key map alternates on its own schedule: only on the frames that splat (and only where the sets alternate)
+    Dev<uint64_t> d_key[2];
+    int key_set = 0;
+    uint64_t *keyT() const { return d_key[key_set]; }
+    std::vector<Dev<void>> frame_mem;  // the buffers behind fset
     Model M{};
     SetBufs m_bufs[2];                 // the buffers behind M.s[0] and M.s[1]
     Dev<DevState> d_state;
     Host<DevState> h_state;           // pinned mirror
-    // column-major frame images
-    Dev<float> d_depthT, d_filteredT, d_lastT;
-    Dev<uint32_t> d_rgbsT;
-    Dev<uint2> d_dcT;                  // (depth bits, rgbs) of the frame the conflict test sees
-    Dev<float> d_depthT_nx; Dev<uint32_t> d_rgbsT_nx; Dev<uint64_t> d_keyT_nx; Dev<uint2> d_dcT_nx;
-    Dev<uint64_t> d_keyT;
+    Dev<float> d_filteredT, d_lastT;   // column-major, like the FrameSet's planes
     // row-major staging of the caller's inputs
     Dev<uint8_t> d_rgb, d_sem;
     Dev<uint16_t> d_depth_raw;
@@ -343,36 +365,25 @@ struct sm_ctx {
     Dev<uint64_t> d_alive;             // 1 bit per slot: 0 = killed since the last physical compaction (free slots are 1)
     Dev<uint32_t> d_tile_dead;         // dead slots per tile
     size_t alive_words = 0, dead_tiles = 0;
-    bool maybe_garbage = false;        // a deferred-compaction cull ran since the last physical compaction
-    bool keys_are_slots = false;       // the key map was drawn by a cull that did not compact: its ids are slot numbers
-    int culls_since_compact = 0;       // deferred-compaction schedule (host side: it picks the kernels)
-    uint32_t frames_enq = 0;           // appends enqueued so far (compared with the tag of *h_stat)
-    Host<unsigned long long> h_stat; unsigned long long *d_stat = nullptr;   // pinned, device-written: frames<<32 | occupied slots
+    sm_slots::SlotSchedule slots;      // the occupied slots as the host knows them, which culls compact, what the compaction leaves (sm_slots.h)
+    Host<unsigned long long> h_stat; unsigned long long *d_stat = nullptr;   // pinned, device-written: frames<<32 | occupied slots (read by `slots`)
     Dev<uint32_t> d_tb;                // per-tile bounds (8 words per tile)
-    Dev<uint8_t> d_tile_flags;         // per-tile skip flags of the current frame
-    Dev<uint8_t> d_tile_flags_nx; Dev<uint4> d_wave_cnt_nx; Dev<uint2> d_prep_part_nx;   // the other frame's (two-launch frame: its publisher runs next to this frame's flag workgroups)
     Dev<uint32_t> d_conf_part;         // per-workgroup partial counters of k_conflict (instead of same-address atomics)
     PassPartials part;
     // one pass over the surfels per frame (k_surfel_pass + k_pass_fixup) on the frames whose cull only marks the dead
-    Dev<uint4> d_wave_cnt;             // conflicts per quarter tile (one word per wave)
     Dev<float> d_undo;                 // confidence before this frame's decrement, per slot (read only if the conflict cap binds)
-    // tile skip flags of the frame, evaluated by extra workgroups of the preparation launch
-    Dev<uint2> d_prep_part;
     int fix_grid = 128;
     // direct append (k_associate_direct): candidate counts per association block / per group, group prefixes
     Dev<uint32_t> d_blk_cand, d_grp_cand;
-    Dev<uint32_t> d_frame_sub;         // 2 x 64 sub-counters: visible, killed (k_surfel_pass)
-    uint32_t *d_nf_sub = nullptr, *d_nf_sub_nx = nullptr;   // 2 x 64 each: new, fused (k_associate_direct) of this / the other frame
+    Dev<uint32_t> d_frame_sub;         // 2 x 64 sub-counters: visible, killed (k_surfel_pass); behind them the two FrameSets' nf_sub
     uint32_t n_grp = 0, cand_group = 16;
     Dev<unsigned long long> d_pass_trace;         // Switches::trace: per-workgroup time stamps of the last k_surfel_pass launch, dumped by sm_destroy
     int pass_trace_grid = 0;
     Dev<unsigned long long> d_ap_trace;           // the same for the last k_assoc_prep launch: (entry, exit) per workgroup
     int ap_trace_n[4] = {0, 0, 0, 0};             // its association / tile-flag / image workgroups (dispatch order); fixup workgroups ahead of them
-    Dev<uint32_t> d_conf_sub;          // 2 x 64 conflict sub-counters (one set per frame parity: zeroed by that frame's k_prep)
-    uint32_t *conf_sub() const { return d_conf_sub + SUB_SET * plane_set; }   // the current frame's set
+    Dev<uint32_t> d_conf_sub;          // 2 x 64 conflict sub-counters: the two FrameSets' conf_sub
     uint32_t n_conf_part = 0;
     uint32_t tb_tiles = 0;
-    uint32_t cull_epoch = 0;
     int compact_grid = COMPACT_GRID;
     int pass_grid = MAX_GRID;          // workgroups of k_surfel_pass that are resident at once (a larger grid runs its tail as a second, thin wave)
     // association scratch
@@ -398,10 +409,8 @@ struct sm_ctx {
     // the pass's launch
     bool defer_ok = false;             // this context may defer (sw.defer_assoc, not a sharded stream)
     HeldBack held;
-    uint32_t est_fr0 = 0, est_slots0 = 0, est_rate = 0xFFFFFFFFu;   // pass_grid_policy's estimate of the slots per frame (from the pinned statistic)
     static constexpr uint32_t N_CREW = 32;
     int n_pix_blocks = 0;
-    uint32_t n_odd_pixels = 0;
     // export staging
     Dev<void> d_export;
     size_t export_bytes = 0;
@@ -417,7 +426,6 @@ struct sm_ctx {
     bool raw_valid = false;            // a frame that computes the raw feedback cloud has run (every call but the reference frame)
     int raw_tick = 0;                  // its time stamp
     float curr_pose[16], last_pose[16];
-    uint32_t count_bound = 0;         // host upper bound of the device-side count (grid sizing)
     bool pending_cull = false;
     uint32_t count_before_cull = 0, offset_before_cull = 0;
     sm_counts counts{};

@@ -97,7 +97,7 @@ int sm_download_index_map(sm_ctx *s, int32_t *id, float *vert_conf4, float *colo
     int32_t *d_id = (int32_t *)(base + P * 48);
     float4 *d_vc = (float4 *)base, *d_ct = (float4 *)(base + P * 16), *d_nr = (float4 *)(base + P * 32);
     FrameParams fp = make_params(s, s->curr_pose);
-    hipLaunchKernelGGL(k_export_index, dim3((s->P + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, fp, s->d_keyT, d_id, d_vc, d_ct, d_nr);
+    hipLaunchKernelGGL(k_export_index, dim3((s->P + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, fp, s->keyT(), d_id, d_vc, d_ct, d_nr);
     HIPCK(hipGetLastError());
     if (id) HIPCK(hipMemcpyAsync(id, d_id, P * 4, hipMemcpyDeviceToHost, s->stream));
     if (vert_conf4) HIPCK(hipMemcpyAsync(vert_conf4, d_vc, P * 16, hipMemcpyDeviceToHost, s->stream));
@@ -121,7 +121,7 @@ int sm_download_raw_cloud(sm_ctx *s, float *dst12, uint32_t cap, uint32_t *n)
     FrameParams fp = make_params(s, s->curr_pose);
     fp.init_mode = 1;
     fp.time = s->raw_tick;
-    hipLaunchKernelGGL(k_raw_cloud, dim3((s->P + 255) / 256), dim3(256), 0, s->stream, fp, s->d_depthT, s->d_rgbsT, s->d_xs, s->d_ys, d_rec, d_flag);
+    hipLaunchKernelGGL(k_raw_cloud, dim3((s->P + 255) / 256), dim3(256), 0, s->stream, fp, s->cur().depthT, s->cur().rgbsT, s->d_xs, s->d_ys, d_rec, d_flag);
     HIPCK(hipGetLastError());
     std::vector<uint8_t> flag(P);
     HIPCK(hipMemcpyAsync(flag.data(), d_flag, P, hipMemcpyDeviceToHost, s->stream));
@@ -147,8 +147,9 @@ int sm_download_depth(sm_ctx *s, int which, float *dst)
     const bool alias = s->cfg.preprocess == 0;
     // preprocess == 1: after every processFrame LAST == DEPTH_FILTERED (src/SurfelMapping.cpp:244); the two
     // buffers are swapped instead of copied, so both names read d_lastT.
-    const float *src = which == SM_TEX_DEPTH_METRIC ? s->d_depthT : which == SM_TEX_DEPTH_FILTERED ? (alias ? s->d_depthT : s->d_lastT)
-                     : which == SM_TEX_LAST ? (alias ? s->d_depthT : s->d_lastT) : nullptr;
+    const float *depthT = s->cur().depthT;
+    const float *src = which == SM_TEX_DEPTH_METRIC ? depthT : which == SM_TEX_DEPTH_FILTERED ? (alias ? depthT : s->d_lastT)
+                     : which == SM_TEX_LAST ? (alias ? depthT : s->d_lastT) : nullptr;
     if (!src) return SM_E_ARG;
     int rc = ensure_export(s, (size_t)s->P * 4);
     if (rc) return rc;

@@ -121,7 +121,7 @@ int retire_commit(sm_ctx *s, uint32_t n)
         hipLaunchKernelGGL(k_retire_clear, dim3(std::min<uint32_t>((words + 255) / 256, MAX_GRID)), dim3(256), 0, s->stream, s->d_state,
                            s->ret.d_mask, s->ret.d_tile_ret, s->ret.d_total, s->d_alive, s->d_tile_dead);
         HIPCK(hipGetLastError());
-        s->maybe_garbage = true;
+        s->slots.dead_slots_made();
     }
     if ((rc = ensure_compact(s))) return rc;
     if ((rc = pull_state(s))) return rc;

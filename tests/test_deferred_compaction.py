@@ -60,6 +60,21 @@ def test_any_compaction_schedule_gives_the_oracle_model(period):
     assert_models_equal(o.download_model(), h.download_model(), f"period={period} continued")
 
 
+@pytest.mark.parametrize("period", [1, 3, 1000])
+def test_the_period_alone_schedules_the_compactions_of_synchronous_frames(period):
+    """After a synchronous frame the slot statistic is exact, and 490 000 slots hold this sequence many times over: the capacity
+    rule never asks, so of N fusing frames exactly floor(N / period) compact."""
+    n = 12
+    seq = synth.make_sequence(SMALL, wavy(n + 1), seed=27, noise_mm=6.0)           # the reference frame + n fusing ones
+    h = make("hip", *(SMALL[k] for k in ("width", "height", "fx", "fy", "cx", "cy")), preprocess=0, stereo_border=20.0,
+             max_sqrt_vertices=700, compact_period=period, enable_timing=1)
+    for fr in seq:
+        h.process_frame(*fr)
+    t = h.timings()
+    assert t["frames"] == n
+    assert t["frames_compact"] == n // period
+
+
 def test_index_map_ids_are_positions_among_live_surfels():
     seq = synth.make_sequence(SMALL, wavy(14), seed=23, noise_mm=6.0)
     o, h = pair(SMALL, stereo_border=20.0, max_sqrt_vertices=700, compact_period=1000)

@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define SM_API_VERSION 4   /* bumped whenever a struct or an entry point changes (3, 4: round 3 -- asynchronous host path, rig step, sm_timings::k_scan_own, sm_host_alloc_frame; the staged shard entry points are gone).  Purely additive changes keep it: sm_model_view / sm_render_model*, sm_track_* and sm_track_*rgb* were added at 4, as were sm_warp_by_time / sm_loop_spread / sm_track_*_old / sm_close_loop: no existing struct or entry point changed. */
+#define SM_API_VERSION 4   /* bumped whenever a struct or an entry point changes (3, 4: round 3 -- asynchronous host path, rig step, sm_timings::k_scan_own, sm_host_alloc_frame; the staged shard entry points are gone).  Purely additive changes keep it: sm_model_view / sm_render_model*, sm_track_* and sm_track_*rgb* were added at 4, as were sm_warp_by_time / sm_loop_spread / sm_track_*_old / sm_close_loop and sm_track_*_window / sm_close_loop_rgb / sm_old_in_view / sm_*auto_loop*: no existing struct or entry point changed. */
 
 /* error codes (reference: void returns + CheckGlDieOnError(); bool for map IO) */
 enum {
@@ -575,7 +575,7 @@ int sm_loop_spread(const float *D16, int32_t t_a, int32_t t_b, float *corr12);
  * (false on a NaN) -- the map as it was before the drift, which index_map.vert:45 no longer draws for fusion but a recall has
  * brought back.  With max_time = INT32_MAX there is no window: pose and info equal sm_track_frame's bit for bit.  anchor_time
  * (may be NULL) receives the largest m[7] among the surfels the prediction holds, or -1 with none.  No surfel of the window in
- * view: SM_TRACK_NO_MODEL.  sm_track_debug_old is sm_track_debug with the same window.  (sm_track_frame_rgb has no such form.) */
+ * view: SM_TRACK_NO_MODEL.  sm_track_debug_old is sm_track_debug with the same window.  (sm_track_frame_rgb's form: sm_track_frame_rgb_window.) */
 int sm_track_frame_old(sm_ctx *s, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params, int32_t max_time,
                        float *pose16_out, sm_track_info *info, float *anchor_time);
 int sm_track_debug_old(sm_ctx *s, const uint16_t *depth_mm, const float *pose16_eval, int32_t max_time, int32_t *pred_slot, double *sys29);
@@ -602,6 +602,74 @@ enum { SM_LOOP_CLOSED = 0, SM_LOOP_NONE = 1, SM_LOOP_NO_OLD_MAP = 2, SM_LOOP_TRA
 int sm_default_loop_params(const sm_config *c, sm_loop_params *p);
 int sm_close_loop(sm_ctx *s, const uint16_t *depth_mm, const float *pose16, const sm_map_source *src, const sm_track_params *tp,
                   const sm_loop_params *lp, float *pose16_out, sm_loop_info *info);
+
+/* ---- closing loops unasked (DESIGN.md "4i. Closing loops unasked") ----
+ * Every frame fused before a loop is closed fuses the drifted world into the old one and culls the old one where the two disagree,
+ * so a loop has to be noticed and closed BEFORE the frame that sees it is fused.  Four pieces, each usable by hand:
+ * The window.  sm_track_frame_window / sm_track_debug_window / sm_track_frame_rgb_window / sm_track_rgb_debug_window are
+ *   sm_track_frame / sm_track_debug / sm_track_frame_rgb / sm_track_rgb_debug in every rule, except that the prediction holds only
+ *   surfels with m[7] > float(min_time) && m[7] <= float(max_time) (both comparisons false on a NaN).  min_time = INT32_MIN and
+ *   max_time = INT32_MAX leave that end open: no comparison is made for an open end, so a NaN time passes exactly where it passes
+ *   in the plain form.  Both ends open equals the plain form bit for bit, pose and info; (INT32_MIN, max_time) equals
+ *   sm_track_frame_old / sm_track_debug_old bit for bit.  anchor_time (may be NULL) as sm_track_frame_old's.  The debug forms'
+ *   pred_slot (may be NULL) is the windowed prediction.  Arguments and errors as the plain forms'.
+ * The measurement with colour.  sm_close_loop_rgb is sm_close_loop in every rule, except that step 1 is
+ *   sm_track_frame_rgb_window(rgb, depth, guess = pose16, tp, rp, INT32_MIN, tick - 1 - min_age): a street of flat ground and flat
+ *   walls, SM_LOOP_TRACK_FAILED for depth alone, can close.  info->track is that call's sm_track_info; the colour tracker's extra
+ *   info is not reported.  rp NULL = defaults; a NULL rgb is SM_E_ARG.
+ * The census.  sm_old_in_view counts the slots k below the occupied count with the alive bit set, m[7] <= float(max_time) (false on
+ *   a NaN) and, with tinv = [R^T | -R^T t] of pose16 in double rounded to float and c = tinv * centre, sm_track_frame's own
+ *   prediction gates: near < c.z < far and the pixel (floor(((fx*c.x)/c.z + cx) + 0.5), floor(((fy*c.y)/c.z + cy) + 0.5)) inside the
+ *   image.  It is what sm_track_debug_old's prediction would be offered, before the nearest-per-pixel choice.  Synchronous (waits
+ *   for frames in flight); changes nothing.  SM_E_ARG: a NULL argument, a non-finite pose, a call between sm_stage_conflict and
+ *   sm_stage_cull.  SM_E_UNSUPPORTED: a sharded or rig context.
+ * The policy.  While sm_set_auto_loop is on, sm_track_frame and sm_track_frame_rgb (and so the callers that track first and fuse
+ *   second) do the following, with T = tick and split = T - 1 - loop.min_age:
+ *   1. The pose is tracked in the young window (split, INT32_MAX) -- while split < 0 in the plain prediction, bit for bit.  A status
+ *      other than SM_TRACK_OK returns as without the policy: no census, no attempt.
+ *   2. A census is due when split >= 0, T % every == 0 and T >= rest_until (0 at first).  n_old = sm_old_in_view(tracked pose, split);
+ *      `checked` counts the censuses.  n_old < min_old: nothing more happens, pose16_out is the tracked pose.
+ *   3. Otherwise one attempt: sm_close_loop (from sm_track_frame) or sm_close_loop_rgb (from sm_track_frame_rgb) with pose16 = the
+ *      tracked pose, this call's tracker parameters and the policy's `loop`.  The source is the model, the paths of `src` and every
+ *      file the retirement policy has written so far ("<prefix>_%06u.bin"), a path in both lists once.  On SM_LOOP_CLOSED
+ *      pose16_out is the corrected pose, so the caller fuses in the straightened map; on every other outcome the tracked pose.
+ *   4. After every attempt, whatever its outcome: rest_until = T + rest.
+ *   sm_track_info is sm_track_frame's own, of the young-window track; the loop's outcome is read from sm_auto_loop_stats.  An error
+ *   of the attempt (a map file that cannot be read, say) is returned by the tracker call and counted as `failed`.
+ *   With the policy off (the default; p NULL switches it off) every entry point is exactly what it is without it.  src may be NULL
+ *   (no files of the caller's); its paths are copied.  Setting the policy clears its tally and rest_until.
+ *   SM_E_ARG: a NULL ctx, every < 1, rest < 0, loop as sm_close_loop rejects it, a NULL path, a path listed twice.
+ *   SM_E_UNSUPPORTED: a sharded or rig context; sm_shard_stream_configure and sm_rig_configure switch the policy off.
+ *   "Bit for bit" above speaks of results: with the policy on and split < 0 the call also computes the anchor time it does not
+ *   report (one small kernel and a 4-byte read-back), and a parameter the tracker rejects is named in sm_last_error under
+ *   sm_track_frame_window / sm_track_frame_rgb_window, the entry points the policy tracks through. */
+int sm_track_frame_window(sm_ctx *s, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params, int32_t min_time,
+                          int32_t max_time, float *pose16_out, sm_track_info *info, float *anchor_time);
+int sm_track_debug_window(sm_ctx *s, const uint16_t *depth_mm, const float *pose16_eval, int32_t min_time, int32_t max_time,
+                          int32_t *pred_slot, double *sys29);
+int sm_track_frame_rgb_window(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params,
+                              const sm_track_rgb_params *rgb_params, int32_t min_time, int32_t max_time, float *pose16_out,
+                              sm_track_info *info, sm_track_rgb_info *rgb_info, float *anchor_time);
+int sm_track_rgb_debug_window(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *pose16_eval, int level, int which,
+                              int32_t min_time, int32_t max_time, int32_t *pred_slot, double *sys29);
+int sm_close_loop_rgb(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *pose16, const sm_map_source *src,
+                      const sm_track_params *tp, const sm_track_rgb_params *rp, const sm_loop_params *lp, float *pose16_out,
+                      sm_loop_info *info);
+int sm_old_in_view(sm_ctx *s, const float *pose16, int32_t max_time, uint32_t *n);
+typedef struct sm_auto_loop_params {
+    int32_t every, rest;      /* 1: a census on every tick that is a multiple of it; 10: ticks without a census after an attempt */
+    uint32_t min_old;         /* 1000 (sm_track_params::min_inliers): old surfels in view below which no attempt is made */
+    sm_loop_params loop;      /* sm_default_loop_params */
+} sm_auto_loop_params;
+typedef struct sm_auto_loop_stats_t {
+    uint32_t checked, attempts;                            /* censuses taken; of them, followed by an attempt */
+    uint32_t closed, none, rejected, failed, no_old_map;   /* the attempts by outcome (failed: SM_LOOP_TRACK_FAILED or an error) */
+    uint32_t last_census;                                  /* n_old of the last census */
+    sm_loop_info last;                                     /* of the last attempt that returned SM_OK */
+} sm_auto_loop_stats_t;
+int sm_default_auto_loop_params(const sm_config *c, sm_auto_loop_params *p);
+int sm_set_auto_loop(sm_ctx *s, const sm_auto_loop_params *p, const sm_map_source *src);
+int sm_auto_loop_stats(sm_ctx *s, sm_auto_loop_stats_t *out);
 
 /* ---- per-pass entry points (GlobalModel / IndexMap methods), synchronous ---- */
 /* Upload RGB / metric depth / semantic textures directly (bypasses p0). */

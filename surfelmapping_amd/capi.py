@@ -37,6 +37,8 @@ SYMBOLS = (
     "sm_default_recall_params", "sm_recall", "sm_recall_stats", "sm_set_auto_recall", "sm_auto_recall_stats",
     "sm_warp_by_time", "sm_warp_stats", "sm_loop_spread", "sm_track_frame_old", "sm_track_debug_old",
     "sm_default_loop_params", "sm_close_loop",
+    "sm_track_frame_window", "sm_track_debug_window", "sm_track_frame_rgb_window", "sm_track_rgb_debug_window", "sm_close_loop_rgb",
+    "sm_old_in_view", "sm_default_auto_loop_params", "sm_set_auto_loop", "sm_auto_loop_stats",
 )
 
 SM_COLL_SUM, SM_COLL_MIN, SM_COLL_GATHER = 0, 1, 2
@@ -237,9 +239,42 @@ def loop_params(cfg, **over) -> SmLoopParams:
     return p
 
 
+class SmAutoLoopParams(C.Structure):
+    _fields_ = [("every", C.c_int32), ("rest", C.c_int32), ("min_old", C.c_uint32), ("loop", SmLoopParams)]
+
+
+class SmAutoLoopStats(C.Structure):
+    _fields_ = [("checked", C.c_uint32), ("attempts", C.c_uint32), ("closed", C.c_uint32), ("none", C.c_uint32),
+                ("rejected", C.c_uint32), ("failed", C.c_uint32), ("no_old_map", C.c_uint32), ("last_census", C.c_uint32),
+                ("last", SmLoopInfo)]
+
+
+def auto_loop_params(cfg, **over) -> SmAutoLoopParams:
+    """sm_default_auto_loop_params of a config (every 1, rest 10, min_old 1000, loop = loop_params(cfg)) with fields overridden;
+    the fields of sm_loop_params are given by their own names (min_age, max_trans, ...)"""
+    p = SmAutoLoopParams()
+    load().sm_default_auto_loop_params(C.byref(cfg), C.byref(p))
+    for k, v in over.items():
+        if k != "loop" and hasattr(p, k):
+            setattr(p, k, v)
+        elif hasattr(p.loop, k):
+            setattr(p.loop, k, v)
+        else:
+            raise KeyError(k)
+    return p
+
+
+INT32_MIN, INT32_MAX = -2 ** 31, 2 ** 31 - 1
+
+
 def _track_info_dict(info) -> dict:
     return dict(status=TRACK_STATUS.get(info.status, str(info.status)), status_code=int(info.status), iterations=int(info.iterations),
                 inliers=int(info.inliers), rmse=float(info.rmse), guess=np.array(info.guess[:], np.float32).reshape(4, 4).T.copy())
+
+
+def _loop_info_dict(info) -> dict:
+    return dict(status=LOOP_STATUS.get(info.status, str(info.status)), status_code=int(info.status), track=_track_info_dict(info.track),
+                D=np.array(info.D[:], np.float32).reshape(4, 4).T.copy(), t_a=int(info.t_a), t_b=int(info.t_b))
 
 
 def loop_spread(D, t_a, t_b) -> np.ndarray:
@@ -443,6 +478,17 @@ def load():
     L.sm_default_loop_params.argtypes = [C.POINTER(SmConfig), C.POINTER(SmLoopParams)]
     L.sm_close_loop.argtypes = [vp, vp, vp, C.POINTER(SmMapSource), C.POINTER(SmTrackParams), C.POINTER(SmLoopParams), vp,
                                 C.POINTER(SmLoopInfo)]
+    i32, tpp, rpp, lpp = C.c_int32, C.POINTER(SmTrackParams), C.POINTER(SmTrackRgbParams), C.POINTER(SmLoopParams)
+    L.sm_track_frame_window.argtypes = [vp, vp, vp, tpp, i32, i32, vp, C.POINTER(SmTrackInfo), C.POINTER(C.c_float)]
+    L.sm_track_debug_window.argtypes = [vp, vp, vp, i32, i32, vp, vp]
+    L.sm_track_frame_rgb_window.argtypes = [vp, vp, vp, vp, tpp, rpp, i32, i32, vp, C.POINTER(SmTrackInfo), C.POINTER(SmTrackRgbInfo),
+                                            C.POINTER(C.c_float)]
+    L.sm_track_rgb_debug_window.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, i32, i32, vp, vp]
+    L.sm_close_loop_rgb.argtypes = [vp, vp, vp, vp, C.POINTER(SmMapSource), tpp, rpp, lpp, vp, C.POINTER(SmLoopInfo)]
+    L.sm_old_in_view.argtypes = [vp, vp, i32, u32p]
+    L.sm_default_auto_loop_params.argtypes = [C.POINTER(SmConfig), C.POINTER(SmAutoLoopParams)]
+    L.sm_set_auto_loop.argtypes = [vp, C.POINTER(SmAutoLoopParams), C.POINTER(SmMapSource)]
+    L.sm_auto_loop_stats.argtypes = [vp, C.POINTER(SmAutoLoopStats)]
     for name in SYMBOLS:
         getattr(L, name)          # AttributeError here = the library does not match the header
     _lib = L
@@ -844,9 +890,126 @@ class SurfelMap:
         info = SmLoopInfo()
         self._chk(self._L.sm_close_loop(self._h, _ptr(depth), _ptr(g), C.byref(src), C.byref(tp) if tp is not None else None, C.byref(lp),
                                         _ptr(out), C.byref(info)), "sm_close_loop")
-        d = dict(status=LOOP_STATUS.get(info.status, str(info.status)), status_code=int(info.status), track=_track_info_dict(info.track),
-                 D=np.array(info.D[:], np.float32).reshape(4, 4).T.copy(), t_a=int(info.t_a), t_b=int(info.t_b))
+        return out.reshape(4, 4).T.copy(), _loop_info_dict(info)
+
+    # -- closing loops unasked (sm_set_auto_loop)
+    def old_in_view(self, pose, max_time) -> int:
+        """how many live surfels last updated at or before max_time pass the tracker's prediction gates at `pose` (sm_old_in_view)"""
+        g = _mat16(pose)
+        n = C.c_uint32()
+        self._chk(self._L.sm_old_in_view(self._h, _ptr(g), int(max_time), C.byref(n)), "sm_old_in_view")
+        return int(n.value)
+
+    def census_ms(self):
+        """device time in ms of the census kernel of the last old_in_view() made with SM_TRACK_TIMING=1 (sm_debug_census_ms, not
+        part of the C-ABI header); None if it was not timed"""
+        f = self._L.sm_debug_census_ms
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        ms = C.c_float()
+        self._chk(f(self._h, C.byref(ms)), "sm_debug_census_ms")
+        return None if ms.value < 0 else float(ms.value)
+
+    def track_window(self, depth, min_time, max_time, guess=None, **params):
+        """track() with the prediction held to surfels with min_time < time <= max_time; INT32_MIN / INT32_MAX leave an end open
+        (sm_track_frame_window).  Returns (pose, info) as track_old()."""
+        depth = np.ascontiguousarray(depth, np.uint16)
+        assert depth.size == self.P, depth.shape
+        g = None if guess is None else _mat16(guess)
+        p = track_params(**params) if params else None
+        out = np.zeros(16, np.float32)
+        info, anchor = SmTrackInfo(), C.c_float()
+        self._chk(self._L.sm_track_frame_window(self._h, _ptr(depth), _ptr(g), C.byref(p) if p is not None else None, int(min_time),
+                                                int(max_time), _ptr(out), C.byref(info), C.byref(anchor)), "sm_track_frame_window")
+        d = _track_info_dict(info)
+        d["anchor_time"] = float(anchor.value)
         return out.reshape(4, 4).T.copy(), d
+
+    def track_debug_window(self, depth, pose_eval, min_time, max_time):
+        """track_debug() with track_window()'s window (sm_track_debug_window)"""
+        depth = np.ascontiguousarray(depth, np.uint16)
+        assert depth.size == self.P, depth.shape
+        pe = _mat16(pose_eval)
+        pred = np.zeros((self.H, self.W), np.int32)
+        sys29 = np.zeros(29, np.float64)
+        self._chk(self._L.sm_track_debug_window(self._h, _ptr(depth), _ptr(pe), int(min_time), int(max_time), _ptr(pred), _ptr(sys29)),
+                  "sm_track_debug_window")
+        return pred, sys29
+
+    def track_rgb_window(self, rgb, depth, min_time, max_time, guess=None, **params):
+        """track_rgb() with track_window()'s window (sm_track_frame_rgb_window); info with anchor_time added"""
+        rgb = np.ascontiguousarray(rgb, np.uint8)
+        depth = np.ascontiguousarray(depth, np.uint16)
+        assert depth.size == self.P and rgb.size == self.P * 3, (depth.shape, rgb.shape)
+        g = None if guess is None else _mat16(guess)
+        icp = {k: v for k, v in params.items() if k not in self._RGB_KEYS}
+        col = {k: v for k, v in params.items() if k in self._RGB_KEYS}
+        p = track_params(**icp) if icp else None
+        q = track_rgb_params(**col) if col else None
+        out = np.zeros(16, np.float32)
+        info, rinfo, anchor = SmTrackInfo(), SmTrackRgbInfo(), C.c_float()
+        self._chk(self._L.sm_track_frame_rgb_window(self._h, _ptr(rgb), _ptr(depth), _ptr(g), C.byref(p) if p is not None else None,
+                                                    C.byref(q) if q is not None else None, int(min_time), int(max_time), _ptr(out),
+                                                    C.byref(info), C.byref(rinfo), C.byref(anchor)), "sm_track_frame_rgb_window")
+        d = _track_info_dict(info)
+        d.update(rgb_inliers=int(rinfo.rgb_inliers), rgb_rmse=float(rinfo.rgb_rmse), pivot_ratio=float(rinfo.pivot_ratio),
+                 level_iterations=[int(x) for x in rinfo.level_iterations], anchor_time=float(anchor.value))
+        return out.reshape(4, 4).T.copy(), d
+
+    def track_rgb_debug_window(self, rgb, depth, pose_eval, min_time, max_time, level=0, which=0):
+        """track_rgb_debug() with track_window()'s window (sm_track_rgb_debug_window): (pred_slot int32[H][W], sys float64[29])"""
+        rgb = np.ascontiguousarray(rgb, np.uint8)
+        depth = np.ascontiguousarray(depth, np.uint16)
+        assert depth.size == self.P and rgb.size == self.P * 3, (depth.shape, rgb.shape)
+        pe = _mat16(pose_eval)
+        pred = np.zeros((self.H, self.W), np.int32)
+        sys29 = np.zeros(29, np.float64)
+        self._chk(self._L.sm_track_rgb_debug_window(self._h, _ptr(rgb), _ptr(depth), _ptr(pe), int(level), int(which), int(min_time),
+                                                    int(max_time), _ptr(pred), _ptr(sys29)), "sm_track_rgb_debug_window")
+        return pred, sys29
+
+    def close_loop_rgb(self, rgb, depth, pose, paths=(), **params):
+        """close_loop() with the loop measured by the colour tracker as well (sm_close_loop_rgb): params may also name the fields of
+        sm_track_rgb_params.  Returns (pose, info) as close_loop()."""
+        rgb = np.ascontiguousarray(rgb, np.uint8)
+        depth = np.ascontiguousarray(depth, np.uint16)
+        assert depth.size == self.P and rgb.size == self.P * 3, (depth.shape, rgb.shape)
+        loop_keys = {n for n, _ in SmLoopParams._fields_}
+        lp = loop_params(self.cfg, **{k: v for k, v in params.items() if k in loop_keys})
+        icp = {k: v for k, v in params.items() if k not in loop_keys and k not in self._RGB_KEYS}
+        col = {k: v for k, v in params.items() if k in self._RGB_KEYS}
+        tp = track_params(**icp) if icp else None
+        rp = track_rgb_params(**col) if col else None
+        src = map_source(paths, include_model=True)
+        g = _mat16(pose)
+        out = np.zeros(16, np.float32)
+        info = SmLoopInfo()
+        self._chk(self._L.sm_close_loop_rgb(self._h, _ptr(rgb), _ptr(depth), _ptr(g), C.byref(src), C.byref(tp) if tp is not None else None,
+                                            C.byref(rp) if rp is not None else None, C.byref(lp), _ptr(out), C.byref(info)),
+                  "sm_close_loop_rgb")
+        return out.reshape(4, 4).T.copy(), _loop_info_dict(info)
+
+    def set_auto_loop(self, paths=(), **params):
+        """Make track() / track_rgb() (and process_frame_tracked*) close loops by themselves (sm_set_auto_loop): they track in the
+        young map, count the old surfels in view and, with at least min_old of them, make one close_loop attempt before the
+        frame is fused.  paths: the map files that move with the model (those of set_auto_retire are added).  params override
+        auto_loop_params(cfg).  Neither paths nor params: off -- so to switch the policy on with every default and no file
+        of the caller's, name one default, e.g. set_auto_loop(every=1)."""
+        paths = list(paths)
+        if not params and not paths:
+            self._chk(self._L.sm_set_auto_loop(self._h, None, None), "sm_set_auto_loop")
+            return
+        p = auto_loop_params(self.cfg, **params)
+        src = map_source(paths, include_model=True)
+        self._chk(self._L.sm_set_auto_loop(self._h, C.byref(p), C.byref(src)), "sm_set_auto_loop")
+
+    def auto_loop_stats(self) -> dict:
+        """checked, attempts, closed, none, rejected, failed, no_old_map, last_census, and last = the last attempt's info as
+        close_loop() returns it (sm_auto_loop_stats)"""
+        st = SmAutoLoopStats()
+        self._chk(self._L.sm_auto_loop_stats(self._h, C.byref(st)), "sm_auto_loop_stats")
+        d = {k: int(getattr(st, k)) for k, _ in SmAutoLoopStats._fields_ if k != "last"}
+        d["last"] = _loop_info_dict(st.last)
+        return d
 
     # -- IndexMap
     def download_index_map(self):

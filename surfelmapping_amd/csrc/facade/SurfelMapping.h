@@ -273,7 +273,57 @@ public:
         }
         return out;
     }
+    // The same with the frame's rgb image: after setTrackColour(true) the loop is measured with the colour term as well
+    // (sm_close_loop_rgb, default parameters), which closes on a street of flat ground and flat walls, where depth alone cannot;
+    // without it this is the overload above.
+    Eigen::Matrix4f closeLoop(const unsigned char *rgb, const unsigned short *depth, const Eigen::Matrix4f &pose,
+                              const std::vector<std::string> &mapFiles = {})
+    {
+        if (!trackColour_) return closeLoop(depth, pose, mapFiles);
+        std::vector<const char *> paths;
+        for (const std::string &f : mapFiles) paths.push_back(f.c_str());
+        const sm_map_source src{paths.data(), (uint32_t)paths.size(), 1};
+        Eigen::Matrix4f out = pose;
+        (void)sm_sync(ctx_);
+        if (sm_close_loop_rgb(ctx_, rgb, depth, pose.data(), &src, nullptr, nullptr, nullptr, out.data(), &lastLoopInfo) != SM_OK) {
+            std::printf("closeLoop: %s\n", sm_last_error());
+            return pose;
+        }
+        return out;
+    }
     const sm_loop_info &getLastLoopInfo() { return lastLoopInfo; }
+    // Close loops unasked (sm_set_auto_loop): while on, every processFrame that tracks (null gtPose) tracks in the young map, counts
+    // the surfels older than time_delta frames the tracked pose sees and, with at least minOld of them, makes one closeLoop attempt
+    // before the frame is fused -- with the colour term after setTrackColour(true).  The map files `mapFiles` and those of
+    // setAutoRetire move with the model.  every / rest / minOld, if not negative, replace the defaults (1, 10, 1000).  on = false: off.
+    bool setAutoLoop(bool on, const std::vector<std::string> &mapFiles = {}, int every = -1, int rest = -1, long minOld = -1)
+    {
+        int rc;
+        if (!on) rc = sm_set_auto_loop(ctx_, nullptr, nullptr);
+        else {
+            sm_config c;
+            sm_default_config(&c, Config::W(), Config::H(), Config::fx(), Config::fy(), Config::cx(), Config::cy());
+            sm_auto_loop_params p;
+            sm_default_auto_loop_params(&c, &p);
+            if (every >= 0) p.every = every;
+            if (rest >= 0) p.rest = rest;
+            if (minOld >= 0) p.min_old = (uint32_t)minOld;
+            std::vector<const char *> paths;
+            for (const std::string &f : mapFiles) paths.push_back(f.c_str());
+            const sm_map_source src{paths.data(), (uint32_t)paths.size(), 1};
+            rc = sm_set_auto_loop(ctx_, &p, &src);
+        }
+        if (rc == SM_OK) return true;
+        std::printf("setAutoLoop: %s\n", sm_last_error());
+        return false;
+    }
+    // censuses, attempts and their outcomes so far; `last` is the last attempt's sm_loop_info
+    sm_auto_loop_stats_t autoLoopStats()
+    {
+        sm_auto_loop_stats_t st{};
+        sm_auto_loop_stats(ctx_, &st);
+        return st;
+    }
 
     // With setAutoRetire on: after every retirement, the records of its map files within `radius` metres of that frame's camera
     // come back into the model and leave the files, so that a camera that returns finds what it left (sm_set_auto_recall;

@@ -1703,6 +1703,7 @@ int sm_shard_stream_configure(sm_ctx *s, int rank, int world)
     s->d_galive = std::move(galive); s->d_new_alive = std::move(new_alive); s->d_gmask = std::move(gmask);
     s->d_ss_info = std::move(info); s->d_capx = std::move(capx);
     s->ss_on = true; s->ss_rank = rank; s->ss_world = world; s->ss_frames = 0;
+    s->aloop.on = false;                                  // (sm_set_auto_loop: a rank holds only its own surfels)
     s->defer_ok = false;                       // the association of a sharded frame sits between two collectives:
     s->alias_frame_sets();                     // one set of buffers from here on (no frame has run: the first)
     return SM_OK;

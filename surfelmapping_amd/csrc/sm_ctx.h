@@ -118,6 +118,9 @@ struct Tracker {
     Dev<double> d_part_rgb;
     Dev<TrackRgbState> d_rstate;
     Host<TrackRgbState> h_rstate;
+    Dev<uint32_t> d_census;            // sm_old_in_view: the count (allocated by its first call)
+    Event ev_census[2];                // SM_TRACK_TIMING=1: around k_loop_census
+    bool census_timed = false;
     std::vector<int> ev_kind;          // of the last timed rgb call: what the interval after event 2 + k covers (kind | level << 4)
     // every processed frame's pose (begin_frame): the constant-velocity history of sm_track_frame
     void note_pose(const float *pose)
@@ -204,6 +207,15 @@ struct Warp {
     Event ev[2];                       // around the live model's kernel
     sm_warp_stats_t stats{};
     bool stats_valid = false;
+};
+
+// closing loops unasked (sm_loop.hip): the policy of sm_set_auto_loop and its tally
+struct AutoLoop {
+    bool on = false;
+    sm_auto_loop_params p{};
+    std::vector<std::string> paths;    // the caller's map files; the retirement policy's are added per attempt
+    int64_t rest_until = 0;            // no census before this tick
+    sm_auto_loop_stats_t stats{};
 };
 
 // The SM_* switches of the frame pipeline (sm_api.hip), read once by sm_create (read_switches): nothing on the per-frame path
@@ -420,6 +432,7 @@ struct sm_ctx {
     RenderMaps maps;
     Recall rec;
     Warp warp;
+    AutoLoop aloop;
     // host frame state (src/SurfelMapping.h:100-103)
     int tick = 0;
     bool ref_set = false;
@@ -490,6 +503,14 @@ void recall_note_written(sm_ctx *s, const std::string &path, const float lo[3], 
 int recall_ensure_scratch(sm_ctx *s);             // what recall_box_of needs (sm_set_auto_retire allocates it with its own)
 // what the two policies require of each other when both are on (SM_E_ARG with g_err set otherwise)
 int check_recall_policy(float radius, const sm_retire_params &rp, const char *who);
+
+// ---- sm_loop.hip ----
+// sm_track_frame (rgb null) / sm_track_frame_rgb while sm_set_auto_loop is on: the young-window track, the census, one attempt
+int auto_loop_track(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params,
+                    const sm_track_rgb_params *rgb_params, float *pose16_out, sm_track_info *info, sm_track_rgb_info *rgb_info);
+// ---- sm_warp.hip ----
+// sm_close_loop's rules for its parameters (SM_E_ARG with g_err set)
+int check_loop_params(const sm_loop_params &p, const char *who);
 
 // ---- what several sources ask of their arguments (SM_E_ARG with g_err set) ----
 inline int check_pose(const float *pose16, const char *who)          // null: the entry point's default

@@ -33,6 +33,7 @@ int sm_rig_configure(sm_ctx *s, int rank, int world)
     if (!s || world < 1 || rank < 0 || rank >= world) return SM_E_ARG;
     if (s->ss_on) { g_err = "sm_rig_configure: the context is configured for sharding"; return SM_E_ARG; }
     s->rig_on = true; s->ss_rank = rank; s->ss_world = world;
+    s->aloop.on = false;                                  // (sm_set_auto_loop: a rank holds only its own surfels)
     return SM_OK;
 }
 

@@ -3,12 +3,16 @@
 #include "sm_ctx.h"
 #include "sm_k_track.h"
 #include "sm_k_track_rgb.h"
+#include "sm_k_loop.h"
 
 #include <cmath>
 
 using namespace sm;
 
 namespace {
+// the time window of a prediction: surfels with lo < m[7] <= hi; INT32_MIN / INT32_MAX leave that end open
+struct Window { int32_t lo, hi; };
+
 // [R^T | -R^T t] of a column-major rigid pose, double
 void rigid_inv_d(const double *m, double *o)
 {
@@ -141,10 +145,10 @@ int track_event(sm_ctx *s, size_t i)
 }
 
 // the state, the prediction at T_prev and the vertex / normal stage, enqueued (the model's state has been pulled).
-// max_time (sm_track_*_old; null otherwise): the prediction holds only surfels last updated at or before it, and the newest time
-// it holds is left in d_anchor
+// win (sm_track_*_old, sm_track_*_window; null otherwise): the prediction holds only surfels last updated inside it, and the
+// newest time it holds is left in d_anchor
 int track_prepare(sm_ctx *s, const uint16_t *depth_mm, const TrackParams &tp, const float *T0, const float *guess, bool ortho,
-                  const int32_t *max_time = nullptr)
+                  const Window *win = nullptr)
 {
     const size_t P = (size_t)s->P;
     TrackState &h = *s->trk.h_state;
@@ -162,15 +166,20 @@ int track_prepare(sm_ctx *s, const uint16_t *depth_mm, const TrackParams &tp, co
     const unsigned pblocks = (unsigned)((P + 255) / 256);
     fill_keys(s, s->trk.d_key, P);
     const uint32_t slots = s->h_state->count;
-    // (max_time == INT32_MAX is "no window": exactly sm_track_frame's prediction, whatever the times are)
-    if (slots && max_time && *max_time != INT32_MAX)
+    // (an open end is not compared: both open is exactly sm_track_frame's prediction, whatever the times are, and an open
+    // lower end exactly sm_track_frame_old's)
+    const bool use_min = win && win->lo != INT32_MIN, use_max = win && win->hi != INT32_MAX;
+    if (slots && use_min)
+        hipLaunchKernelGGL(k_track_splat_window, dim3((slots + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, s->d_alive, tp,
+                           (float)win->lo, (float)win->hi, 1, use_max ? 1 : 0, s->trk.d_key, s->trk.d_state);
+    else if (slots && use_max)
         hipLaunchKernelGGL(k_track_splat_old, dim3((slots + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, s->d_alive, tp,
-                           (float)*max_time, s->trk.d_key, s->trk.d_state);
+                           (float)win->hi, s->trk.d_key, s->trk.d_state);
     else if (slots)
         hipLaunchKernelGGL(k_track_splat, dim3((slots + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, s->d_alive, tp,
                            s->trk.d_key, s->trk.d_state);
     hipLaunchKernelGGL(k_track_resolve, dim3(pblocks), dim3(256), 0, s->stream, s->trk.d_key, (int)P, s->trk.d_pred);
-    if (max_time) {
+    if (win) {
         HIPCK(hipMemsetAsync(s->trk.d_anchor, 0, 4, s->stream));
         hipLaunchKernelGGL(k_track_anchor, dim3(pblocks), dim3(256), 0, s->stream, s->M, s->d_state, s->trk.d_pred, (int)P, s->trk.d_anchor);
     }
@@ -265,7 +274,7 @@ TrackParams track_level_params(const sm_ctx *s, sm_track_params p, int level)
 
 // sm_track_frame's preparation on the coarsest level's grid, then the pyramid and the gathered prediction (the rgb upload precedes event 0, as the depth's)
 int track_rgb_prepare(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const TrackParams &tpc, const TrackRgbParams &rp,
-                      const float *T0, const float *guess, bool ortho, int first_level)
+                      const float *T0, const float *guess, bool ortho, int first_level, const Window *win = nullptr)
 {
     const size_t P = (size_t)s->P;
     TrackRgbState &h = *s->trk.h_rstate;
@@ -275,7 +284,7 @@ int track_rgb_prepare(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, c
     HIPCK(hipMemcpyAsync(s->trk.d_rgb, rgb, P * 3, hipMemcpyHostToDevice, s->stream));
     s->trk.ev_kind.clear();
     int rc;
-    if ((rc = track_prepare(s, depth_mm, tpc, T0, guess, ortho))) return rc;
+    if ((rc = track_prepare(s, depth_mm, tpc, T0, guess, ortho, win))) return rc;
     hipLaunchKernelGGL(k_track_luma_pyr, dim3((s->W + TRACK_RGB_TILE - 1) / TRACK_RGB_TILE, (s->H + TRACK_RGB_TILE - 1) / TRACK_RGB_TILE),
                        dim3(256), 0, s->stream, s->trk.d_rgb, s->W, s->H, rp, s->trk.d_pyr);
     if ((rc = track_rgb_event(s, RGB_EV_PYRAMID, 0))) return rc;
@@ -336,8 +345,8 @@ float anchor_of(uint32_t code)
     return f;
 }
 
-// sm_track_frame, and with max_time sm_track_frame_old (anchor_time may be null)
-int track_frame(sm_ctx *s, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params, const int32_t *max_time,
+// sm_track_frame, and with a window sm_track_frame_old / sm_track_frame_window (anchor_time may be null)
+int track_frame(sm_ctx *s, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params, const Window *win,
                 float *pose16_out, sm_track_info *info, float *anchor_time, const char *fn)
 {
     if (!s || !depth_mm || !pose16_out) { g_err = std::string(fn) + ": null argument"; return SM_E_ARG; }
@@ -364,11 +373,11 @@ int track_frame(sm_ctx *s, const uint16_t *depth_mm, const float *guess16, const
     }
     if ((rc = track_alloc(s))) return rc;
     const TrackParams tp = track_params(s, p);
-    if ((rc = track_prepare(s, depth_mm, tp, g, g, true, max_time))) return rc;    // (iterates from the orthonormalised guess)
+    if ((rc = track_prepare(s, depth_mm, tp, g, g, true, win))) return rc;         // (iterates from the orthonormalised guess)
     for (int it = 0; it < p.max_iters; ++it)
         if ((rc = track_iteration(s, tp, 0))) return rc;
     uint32_t anchor = 0;
-    if (max_time) HIPCK(hipMemcpyAsync(&anchor, s->trk.d_anchor, 4, hipMemcpyDeviceToHost, s->stream));
+    if (win) HIPCK(hipMemcpyAsync(&anchor, s->trk.d_anchor, 4, hipMemcpyDeviceToHost, s->stream));
     HIPCK(hipMemcpyAsync(s->trk.h_state, s->trk.d_state, sizeof(TrackState), hipMemcpyDeviceToHost, s->stream));
     HIPCK(hipStreamSynchronize(s->stream));                   // the one wait of a tracked frame
     const TrackState &h = *s->trk.h_state;
@@ -382,7 +391,7 @@ int track_frame(sm_ctx *s, const uint16_t *depth_mm, const float *guess16, const
     return SM_OK;
 }
 
-int track_debug(sm_ctx *s, const uint16_t *depth_mm, const float *pose16_eval, const int32_t *max_time, int32_t *pred_slot, double *sys29,
+int track_debug(sm_ctx *s, const uint16_t *depth_mm, const float *pose16_eval, const Window *win, int32_t *pred_slot, double *sys29,
                 const char *fn)
 {
     if (!s || !depth_mm || !pose16_eval) { g_err = std::string(fn) + ": null argument"; return SM_E_ARG; }
@@ -394,7 +403,7 @@ int track_debug(sm_ctx *s, const uint16_t *depth_mm, const float *pose16_eval, c
     sm_track_params p;
     sm_default_track_params(&p);
     const TrackParams tp = track_params(s, p);
-    if ((rc = track_prepare(s, depth_mm, tp, pose16_eval, pose16_eval, false, max_time))) return rc;   // (the pose as given)
+    if ((rc = track_prepare(s, depth_mm, tp, pose16_eval, pose16_eval, false, win))) return rc;   // (the pose as given)
     if ((rc = track_iteration(s, tp, 1))) return rc;
     if (pred_slot) HIPCK(hipMemcpyAsync(pred_slot, s->trk.d_pred, (size_t)s->P * 4, hipMemcpyDeviceToHost, s->stream));
     HIPCK(hipMemcpyAsync(s->trk.h_state, s->trk.d_state, sizeof(TrackState), hipMemcpyDeviceToHost, s->stream));
@@ -409,13 +418,15 @@ extern "C" {
 int sm_track_frame(sm_ctx *s, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params, float *pose16_out,
                    sm_track_info *info)
 {
+    if (s && s->aloop.on) return auto_loop_track(s, nullptr, depth_mm, guess16, params, nullptr, pose16_out, info, nullptr);
     return track_frame(s, depth_mm, guess16, params, nullptr, pose16_out, info, nullptr, "sm_track_frame");
 }
 
 int sm_track_frame_old(sm_ctx *s, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params, int32_t max_time,
                        float *pose16_out, sm_track_info *info, float *anchor_time)
 {
-    return track_frame(s, depth_mm, guess16, params, &max_time, pose16_out, info, anchor_time, "sm_track_frame_old");
+    const Window win{INT32_MIN, max_time};
+    return track_frame(s, depth_mm, guess16, params, &win, pose16_out, info, anchor_time, "sm_track_frame_old");
 }
 
 int sm_track_debug(sm_ctx *s, const uint16_t *depth_mm, const float *pose16_eval, int32_t *pred_slot, double *sys29)
@@ -423,9 +434,24 @@ int sm_track_debug(sm_ctx *s, const uint16_t *depth_mm, const float *pose16_eval
     return track_debug(s, depth_mm, pose16_eval, nullptr, pred_slot, sys29, "sm_track_debug");
 }
 
+int sm_track_frame_window(sm_ctx *s, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params, int32_t min_time,
+                          int32_t max_time, float *pose16_out, sm_track_info *info, float *anchor_time)
+{
+    const Window win{min_time, max_time};
+    return track_frame(s, depth_mm, guess16, params, &win, pose16_out, info, anchor_time, "sm_track_frame_window");
+}
+
+int sm_track_debug_window(sm_ctx *s, const uint16_t *depth_mm, const float *pose16_eval, int32_t min_time, int32_t max_time,
+                          int32_t *pred_slot, double *sys29)
+{
+    const Window win{min_time, max_time};
+    return track_debug(s, depth_mm, pose16_eval, &win, pred_slot, sys29, "sm_track_debug_window");
+}
+
 int sm_track_debug_old(sm_ctx *s, const uint16_t *depth_mm, const float *pose16_eval, int32_t max_time, int32_t *pred_slot, double *sys29)
 {
-    return track_debug(s, depth_mm, pose16_eval, &max_time, pred_slot, sys29, "sm_track_debug_old");
+    const Window win{INT32_MIN, max_time};
+    return track_debug(s, depth_mm, pose16_eval, &win, pred_slot, sys29, "sm_track_debug_old");
 }
 
 // Diagnostic, deliberately not part of include/sm_c_api.h (tools/track_probe.py): device times of the last sm_track_frame /
@@ -457,10 +483,12 @@ int sm_default_track_rgb_params(sm_track_rgb_params *p)
     return SM_OK;
 }
 
-int sm_track_frame_rgb(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params,
-                       const sm_track_rgb_params *rgb_params, float *pose16_out, sm_track_info *info, sm_track_rgb_info *rgb_info)
+// sm_track_frame_rgb, and with a window sm_track_frame_rgb_window (anchor_time may be null)
+static int track_frame_rgb(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params,
+                           const sm_track_rgb_params *rgb_params, const Window *win, float *pose16_out, sm_track_info *info,
+                           sm_track_rgb_info *rgb_info, float *anchor_time, const char *fn)
 {
-    if (!s || !rgb || !depth_mm || !pose16_out) { g_err = "sm_track_frame_rgb: null argument"; return SM_E_ARG; }
+    if (!s || !rgb || !depth_mm || !pose16_out) { g_err = std::string(fn) + ": null argument"; return SM_E_ARG; }
     sm_track_params p;
     if (params) p = *params;
     else sm_default_track_params(&p);
@@ -469,9 +497,10 @@ int sm_track_frame_rgb(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, 
     else sm_default_track_rgb_params(&q);
     int rc;
     // (max_iters is sm_track_frame's: checked as there; the level schedule is iters[])
-    if ((rc = track_params_check(s, p, "sm_track_frame_rgb"))) return rc;
-    if (const char *why = track_rgb_check(s, p, q)) { g_err = std::string("sm_track_frame_rgb: ") + why; return SM_E_ARG; }
-    if ((rc = track_check(s, "sm_track_frame_rgb"))) return rc;
+    if ((rc = track_params_check(s, p, fn))) return rc;
+    if (const char *why = track_rgb_check(s, p, q)) { g_err = std::string(fn) + ": " + why; return SM_E_ARG; }
+    if ((rc = track_check(s, fn))) return rc;
+    if (anchor_time) *anchor_time = -1.0f;
     HIPCK(hipSetDevice(s->cfg.device));
     if ((rc = pull_state(s))) return rc;                      // waits for frames in flight: the model after the last frame
     float g[16];
@@ -494,13 +523,15 @@ int sm_track_frame_rgb(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, 
     const TrackRgbParams rp = track_rgb_params(s, q);
     // (the preparation's vertex stage is the coarsest level's; the prediction does not depend on the stride)
     const TrackParams tpc = track_level_params(s, p, q.levels - 1);
-    if ((rc = track_rgb_prepare(s, rgb, depth_mm, tpc, rp, g, g, true, q.levels - 1))) return rc;
+    if ((rc = track_rgb_prepare(s, rgb, depth_mm, tpc, rp, g, g, true, q.levels - 1, win))) return rc;
     for (int l = q.levels - 1; l >= 0; --l) {
         const TrackParams tpl = track_level_params(s, p, l);
         if (l < q.levels - 1 && (rc = track_rgb_level(s, tpl, l))) return rc;
         for (int it = 0; it < q.iters[l]; ++it)
             if ((rc = track_rgb_iteration(s, tpl, rp, l, 0))) return rc;
     }
+    uint32_t anchor = 0;
+    if (win) HIPCK(hipMemcpyAsync(&anchor, s->trk.d_anchor, 4, hipMemcpyDeviceToHost, s->stream));
     HIPCK(hipMemcpyAsync(s->trk.h_state, s->trk.d_state, sizeof(TrackState), hipMemcpyDeviceToHost, s->stream));
     HIPCK(hipMemcpyAsync(s->trk.h_rstate, s->trk.d_rstate, sizeof(TrackRgbState), hipMemcpyDeviceToHost, s->stream));
     HIPCK(hipStreamSynchronize(s->stream));                   // the one wait of a tracked frame
@@ -517,37 +548,127 @@ int sm_track_frame_rgb(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, 
     for (int l = 0; l < TRACK_RGB_LEVELS; ++l) rinf.level_iterations[l] = hr.level_iterations[l];
     if (info) *info = inf;
     if (rgb_info) *rgb_info = rinf;
+    if (anchor_time) *anchor_time = anchor_of(anchor);
     return SM_OK;
 }
 
-int sm_track_rgb_debug(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *pose16_eval, int level, int which,
-                       double *sys29)
+int sm_track_frame_rgb(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params,
+                       const sm_track_rgb_params *rgb_params, float *pose16_out, sm_track_info *info, sm_track_rgb_info *rgb_info)
 {
-    if (!s || !rgb || !depth_mm || !pose16_eval) { g_err = "sm_track_rgb_debug: null argument"; return SM_E_ARG; }
+    if (s && rgb && s->aloop.on) return auto_loop_track(s, rgb, depth_mm, guess16, params, rgb_params, pose16_out, info, rgb_info);
+    return track_frame_rgb(s, rgb, depth_mm, guess16, params, rgb_params, nullptr, pose16_out, info, rgb_info, nullptr, "sm_track_frame_rgb");
+}
+
+int sm_track_frame_rgb_window(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params,
+                              const sm_track_rgb_params *rgb_params, int32_t min_time, int32_t max_time, float *pose16_out,
+                              sm_track_info *info, sm_track_rgb_info *rgb_info, float *anchor_time)
+{
+    const Window win{min_time, max_time};
+    return track_frame_rgb(s, rgb, depth_mm, guess16, params, rgb_params, &win, pose16_out, info, rgb_info, anchor_time,
+                           "sm_track_frame_rgb_window");
+}
+
+// sm_track_rgb_debug, and with a window sm_track_rgb_debug_window (pred_slot may be null)
+static int track_rgb_debug(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *pose16_eval, int level, int which,
+                           const Window *win, int32_t *pred_slot, double *sys29, const char *fn)
+{
+    if (!s || !rgb || !depth_mm || !pose16_eval) { g_err = std::string(fn) + ": null argument"; return SM_E_ARG; }
     sm_track_params p;
     sm_default_track_params(&p);
     sm_track_rgb_params q;
     sm_default_track_rgb_params(&q);
     q.levels = level + 1;                                     // (the pyramid up to that level; its size is checked below)
     if (level < 0 || level >= TRACK_RGB_LEVELS || which < 0 || which > 2) {
-        g_err = "sm_track_rgb_debug: level outside 0..5 or which outside 0..2";
+        g_err = std::string(fn) + ": level outside 0..5 or which outside 0..2";
         return SM_E_ARG;
     }
-    if (const char *why = track_rgb_check(s, p, q)) { g_err = std::string("sm_track_rgb_debug: ") + why; return SM_E_ARG; }
-    int rc = track_check(s, "sm_track_rgb_debug");
+    if (const char *why = track_rgb_check(s, p, q)) { g_err = std::string(fn) + ": " + why; return SM_E_ARG; }
+    int rc = track_check(s, fn);
     if (rc) return rc;
     HIPCK(hipSetDevice(s->cfg.device));
     if ((rc = pull_state(s))) return rc;
     if ((rc = track_alloc(s)) || (rc = track_rgb_alloc(s))) return rc;
     const TrackRgbParams rp = track_rgb_params(s, q);
     const TrackParams tpl = track_level_params(s, p, level);
-    if ((rc = track_rgb_prepare(s, rgb, depth_mm, tpl, rp, pose16_eval, pose16_eval, false, level))) return rc;   // (the pose as given)
+    if ((rc = track_rgb_prepare(s, rgb, depth_mm, tpl, rp, pose16_eval, pose16_eval, false, level, win))) return rc;   // (the pose as given)
     if ((rc = track_rgb_iteration(s, tpl, rp, level, 1))) return rc;
+    if (pred_slot) HIPCK(hipMemcpyAsync(pred_slot, s->trk.d_pred, (size_t)s->P * 4, hipMemcpyDeviceToHost, s->stream));
     HIPCK(hipMemcpyAsync(s->trk.h_state, s->trk.d_state, sizeof(TrackState), hipMemcpyDeviceToHost, s->stream));
     HIPCK(hipMemcpyAsync(s->trk.h_rstate, s->trk.d_rstate, sizeof(TrackRgbState), hipMemcpyDeviceToHost, s->stream));
     HIPCK(hipStreamSynchronize(s->stream));
     const double *src = which == 0 ? s->trk.h_state->sys : which == 1 ? s->trk.h_rstate->sys_icp : s->trk.h_rstate->sys_rgb;
     if (sys29) memcpy(sys29, src, TRACK_NSYS * sizeof(double));
+    return SM_OK;
+}
+
+int sm_track_rgb_debug(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *pose16_eval, int level, int which,
+                       double *sys29)
+{
+    return track_rgb_debug(s, rgb, depth_mm, pose16_eval, level, which, nullptr, nullptr, sys29, "sm_track_rgb_debug");
+}
+
+int sm_track_rgb_debug_window(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *pose16_eval, int level, int which,
+                              int32_t min_time, int32_t max_time, int32_t *pred_slot, double *sys29)
+{
+    const Window win{min_time, max_time};
+    return track_rgb_debug(s, rgb, depth_mm, pose16_eval, level, which, &win, pred_slot, sys29, "sm_track_rgb_debug_window");
+}
+
+// ---- the census of old surfels in view (DESIGN.md "4i. Closing loops unasked") ----
+
+int sm_old_in_view(sm_ctx *s, const float *pose16, int32_t max_time, uint32_t *n)
+{
+    const char *fn = "sm_old_in_view";
+    if (!s || !pose16 || !n) { g_err = std::string(fn) + ": null argument"; return SM_E_ARG; }
+    int rc;
+    if ((rc = check_pose(pose16, fn)) || (rc = track_check(s, fn))) return rc;
+    if (s->rig_on) { g_err = std::string(fn) + ": a rig context holds only its own surfels"; return SM_E_UNSUPPORTED; }
+    *n = 0;
+    HIPCK(hipSetDevice(s->cfg.device));
+    if ((rc = pull_state(s))) return rc;                      // waits for frames in flight: the model after the last frame
+    const char *te = std::getenv("SM_TRACK_TIMING");
+    s->trk.census_timed = false;
+    const uint32_t slots = s->h_state->count;
+    if (!slots) return SM_OK;
+    if (!s->trk.d_census && (rc = dalloc(s->trk.d_census, 1))) return rc;
+    sm_track_params p;
+    sm_default_track_params(&p);
+    TrackParams tp = track_params(s, p);
+    double pose[16], inv[16];
+    for (int e = 0; e < 16; ++e) pose[e] = (double)pose16[e];
+    rigid_inv_d(pose, inv);
+    for (int e = 0; e < 16; ++e) tp.tinv_prev[e] = (float)inv[e];
+    const bool timed = te && te[0] == '1';
+    if (timed && !s->trk.ev_census[0]) {
+        Event e0, e1;
+        HIPCK(hipEventCreate(e0.put()));
+        HIPCK(hipEventCreate(e1.put()));
+        s->trk.ev_census[0] = std::move(e0); s->trk.ev_census[1] = std::move(e1);
+    }
+    HIPCK(hipMemsetAsync(s->trk.d_census, 0, 4, s->stream));
+    if (timed) HIPCK(hipEventRecord(s->trk.ev_census[0], s->stream));
+    const unsigned grid = (unsigned)std::min<uint32_t>((slots + 255u) / 256u, (uint32_t)LOOP_CENSUS_GRID);
+    hipLaunchKernelGGL(k_loop_census, dim3(grid), dim3(256), 0, s->stream, s->M, (const DevState *)s->d_state.get(),
+                       (const uint64_t *)s->d_alive.get(), tp, (float)max_time, s->trk.d_census.get());
+    HIPCK(hipGetLastError());
+    if (timed) HIPCK(hipEventRecord(s->trk.ev_census[1], s->stream));
+    uint32_t got = 0;
+    HIPCK(hipMemcpyAsync(&got, s->trk.d_census, 4, hipMemcpyDeviceToHost, s->stream));
+    HIPCK(hipStreamSynchronize(s->stream));
+    s->trk.census_timed = timed;
+    *n = got;
+    return SM_OK;
+}
+
+// Diagnostic, deliberately not part of include/sm_c_api.h (tools/auto_loop_probe.py): the device time in ms of k_loop_census in the
+// last sm_old_in_view made with SM_TRACK_TIMING=1 (-1 if that call was not timed or launched nothing)
+int sm_debug_census_ms(sm_ctx *s, float *ms)
+{
+    if (!s || !ms) return SM_E_ARG;
+    *ms = -1.0f;
+    if (!s->trk.census_timed) return SM_OK;
+    HIPCK(hipSetDevice(s->cfg.device));
+    HIPCK(hipEventElapsedTime(ms, s->trk.ev_census[0], s->trk.ev_census[1]));
     return SM_OK;
 }
 

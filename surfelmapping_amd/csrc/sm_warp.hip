@@ -341,21 +341,30 @@ int sm_default_loop_params(const sm_config *c, sm_loop_params *p)
     return SM_OK;
 }
 
-int sm_close_loop(sm_ctx *s, const uint16_t *depth_mm, const float *pose16, const sm_map_source *src, const sm_track_params *tp,
-                  const sm_loop_params *lp, float *pose16_out, sm_loop_info *info)
+}  // extern "C"
+
+int sm_impl::check_loop_params(const sm_loop_params &p, const char *who)
 {
-    const char *who = "sm_close_loop";
+    const float bounds[4] = {p.min_trans, p.min_rot_deg, p.max_trans, p.max_rot_deg};
+    for (float b : bounds)
+        if (!(b >= 0.0f) || !std::isfinite(b)) { g_err = std::string(who) + ": a bound is negative or not finite"; return SM_E_ARG; }
+    if (p.min_age < 1) { g_err = std::string(who) + ": min_age must be at least 1"; return SM_E_ARG; }
+    return SM_OK;
+}
+
+namespace {
+// sm_close_loop (rgb null: the depth-only measurement) and sm_close_loop_rgb
+int close_loop(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *pose16, const sm_map_source *src,
+               const sm_track_params *tp, const sm_track_rgb_params *rp, const sm_loop_params *lp, float *pose16_out, sm_loop_info *info,
+               const char *who)
+{
     if (!s || !depth_mm || !pose16 || !src || !pose16_out || !info) { g_err = std::string(who) + ": null argument"; return SM_E_ARG; }
     if (s->ss_on || s->rig_on) { g_err = std::string(who) + ": a sharded or rig context holds only its own surfels"; return SM_E_UNSUPPORTED; }
     sm_loop_params p;
     if (lp) p = *lp;
     else sm_default_loop_params(&s->cfg, &p);
-    const float bounds[4] = {p.min_trans, p.min_rot_deg, p.max_trans, p.max_rot_deg};
-    for (float b : bounds)
-        if (!(b >= 0.0f) || !std::isfinite(b)) { g_err = std::string(who) + ": a bound is negative or not finite"; return SM_E_ARG; }
-    if (p.min_age < 1) { g_err = std::string(who) + ": min_age must be at least 1"; return SM_E_ARG; }
     int rc;
-    if ((rc = check_pose(pose16, who)) || (rc = check_map_source(src, who))) return rc;
+    if ((rc = check_loop_params(p, who)) || (rc = check_pose(pose16, who)) || (rc = check_map_source(src, who))) return rc;
     memset(info, 0, sizeof *info);
     for (int e = 0; e < 16; ++e) info->D[e] = (e % 5 == 0) ? 1.0f : 0.0f;
     info->t_a = info->t_b = -1;
@@ -363,7 +372,9 @@ int sm_close_loop(sm_ctx *s, const uint16_t *depth_mm, const float *pose16, cons
     const int64_t mt = (int64_t)s->tick - 1 - p.min_age;
     const int32_t max_time = (int32_t)std::max<int64_t>(mt, INT32_MIN);
     float t_old[16], anchor = -1.0f;
-    if ((rc = sm_track_frame_old(s, depth_mm, pose16, tp, max_time, t_old, &info->track, &anchor))) return rc;
+    if (rgb) rc = sm_track_frame_rgb_window(s, rgb, depth_mm, pose16, tp, rp, INT32_MIN, max_time, t_old, &info->track, nullptr, &anchor);
+    else rc = sm_track_frame_old(s, depth_mm, pose16, tp, max_time, t_old, &info->track, &anchor);
+    if (rc) return rc;
     if (info->track.status == SM_TRACK_NO_MODEL) { info->status = SM_LOOP_NO_OLD_MAP; return SM_OK; }
     if (info->track.status != SM_TRACK_OK) { info->status = SM_LOOP_TRACK_FAILED; return SM_OK; }
     // D = T_old * pose16^-1, the inverse taken as a rigid pose's: each element ((a0*b0 + a1*b1) + a2*b2) (+ a3 in the last column)
@@ -405,6 +416,23 @@ int sm_close_loop(sm_ctx *s, const uint16_t *depth_mm, const float *pose16, cons
     info->t_a = t_a;
     info->t_b = t_b;
     return SM_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int sm_close_loop(sm_ctx *s, const uint16_t *depth_mm, const float *pose16, const sm_map_source *src, const sm_track_params *tp,
+                  const sm_loop_params *lp, float *pose16_out, sm_loop_info *info)
+{
+    return close_loop(s, nullptr, depth_mm, pose16, src, tp, nullptr, lp, pose16_out, info, "sm_close_loop");
+}
+
+int sm_close_loop_rgb(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *pose16, const sm_map_source *src,
+                      const sm_track_params *tp, const sm_track_rgb_params *rp, const sm_loop_params *lp, float *pose16_out,
+                      sm_loop_info *info)
+{
+    if (!rgb) { g_err = "sm_close_loop_rgb: null argument"; return SM_E_ARG; }
+    return close_loop(s, rgb, depth_mm, pose16, src, tp, rp, lp, pose16_out, info, "sm_close_loop_rgb");
 }
 
 int sm_loop_spread(const float *D16, int32_t t_a, int32_t t_b, float *corr12)

@@ -671,6 +671,84 @@ int sm_default_auto_loop_params(const sm_config *c, sm_auto_loop_params *p);
 int sm_set_auto_loop(sm_ctx *s, const sm_auto_loop_params *p, const sm_map_source *src);
 int sm_auto_loop_stats(sm_ctx *s, sm_auto_loop_stats_t *out);
 
+/* ---- pose search before the tracker (DESIGN.md "4j. Pose search") ----
+ * The trackers converge from a few decimetres; a drive that returns after retirement and recall has drifted by metres.  The search
+ * scores a grid of candidate poses against the windowed prediction, refines the best on a finer grid and hands the winners to the
+ * trackers.  Three layers, each usable by hand:
+ * The score.  sm_score_poses_window takes sm_track_frame_window's prediction (at T_prev, the same window rules and open ends) and
+ *   the grid points (0, stride, 2*stride, ...) x (0, stride, ...) of the depth image with the tracker's vertex and normal rule
+ *   (tp->pixel_stride is ignored).  scores[i] counts the grid points that pass, under candidate i (cand16 + 16*i, camera->world,
+ *   column-major), the tracker's own association tests in the same fp32 expressions: vertex valid, c.z > 0, the pixel inside the
+ *   image, a surfel at the pixel, |T v - p_m| <= dist_thresh, dot(R n, n_m) >= cos(angle_thresh) -- and, with rgb non-NULL,
+ *   fabsf(Y_f - Y_m) <= colour_thresh, Y_f the luminance of the grid point's own pixel and Y_m that of the surfel's colour word,
+ *   both by sm_track_frame_rgb's rule.  With rgb NULL, stride 1 and default tp, scores[i] is value 28 of sm_track_debug_window at the
+ *   same pose.  tp NULL = defaults.  Synchronous (waits for frames in flight); changes nothing.  No processed frame or an empty
+ *   model: every score is 0.  SM_E_ARG: a NULL argument (rgb aside), n == 0, n > 2^20, stride < 1 or > min(W, H), a non-finite
+ *   candidate, colour_thresh < 0 or NaN, tp as the trackers reject it, a call between sm_stage_conflict and sm_stage_cull.
+ * The search.  sm_search_pose, with sp NULL = sm_default_search_params:
+ *   Axes.  Six axes in the order rot x, rot y, rot z (rot_half_deg / rot_step_deg, about the camera's x right, y down, z forward),
+ *     trans x, trans y, trans z (trans_half / trans_step, metres).  An axis is active iff half > 0 and step > 0; it has
+ *     n = 2*floor(half/step) + 1 offsets (k - (n-1)/2) * step, k = 0..n-1, in double; an inactive axis the single offset 0.
+ *   Level 0.  Nested loops over the six axes in that order, the last fastest.  Delta = [Ry(b) * Rx(a) * Rz(c) | t] in double for
+ *     rotation offsets (a, b, c) in degrees and translation t; candidate = centre16 * Delta (column-major rigid product in double,
+ *     ((a0*b0 + a1*b1) + a2*b2) + a3), rounded to float once.  More than 2^20 candidates: SM_E_ARG.  Scored at stride0.
+ *   Ranking.  Score descending, then index ascending; a candidate is kept only if score * stride^2 >= tp->min_inliers (64-bit);
+ *     the first top_k kept go on.  None kept at any level: status SM_TRACK_LOST, pose16_out = centre16.
+ *   Level l+1 (levels - 1 of them).  For each kept candidate in rank order, the same nesting with offsets k * step / refine^(l+1),
+ *     k = -refine..refine, on the active axes, right-multiplied onto that candidate's float pose widened to double; all of them
+ *     scored in one call at stride max(1, stride0 >> (l+1)) and ranked as one list.
+ *   Refinement.  Each kept candidate of the last level, in rank order, is the guess of sm_track_frame_rgb_window (rgb given; rp
+ *     NULL = defaults) or sm_track_frame_window (rgb NULL) with the caller's tp and window.  The answer is the SM_TRACK_OK result
+ *     with the most inliers, ties to the earlier rank.  None OK: the status of rank 0's track, pose16_out = centre16.
+ *   No processed frame, an empty model or no surfel of the window in view: SM_TRACK_NO_MODEL, pose16_out = centre16.
+ *   info (may be NULL): status; levels_run; candidates[l] and best_score[l] (the largest score) of each level run; winner_rank
+ *   (-1: none); track, start (the guess the winner started from) and anchor_time of the winner -- of rank 0's track when none is
+ *   OK; score_ms (device time of the scoring kernels) and total_ms (host clock).  The candidates are ranked on the host.
+ *   SM_E_ARG: as the score's and the trackers', levels outside 1..4, refine < 1, top_k outside 1..16, stride0 < 1, a negative or
+ *   non-finite half, step or colour_thresh, a level with more than 2^20 candidates.
+ * The policies.  sm_close_loop_search is sm_close_loop (rgb NULL) / sm_close_loop_rgb in every rule, except that step 1 is
+ *   sm_search_pose(centre = pose16, window (INT32_MIN, tick - 1 - min_age)): T_old and the anchor are the winner's, info->track the
+ *   winner's sm_track_info.  SM_TRACK_NO_MODEL gives SM_LOOP_NO_OLD_MAP, any other failure SM_LOOP_TRACK_FAILED.  The default box
+ *   reaches sqrt(2^2 + 2^2) = 2.8 m, past sm_loop_params' default max_trans = 2: a caller who wants a wider loop raises lp.
+ *   sm_set_auto_loop_search(sp): while the auto-loop policy is on, its attempt (step 3) is sm_close_loop_search with these
+ *   parameters, with rgb when the call came from sm_track_frame_rgb.  NULL = off (the default): the attempt is what it was.  The
+ *   census, the rest and the statistics are unchanged.  May be set before or after sm_set_auto_loop, which leaves it alone.
+ * SM_E_UNSUPPORTED, all of them: a sharded or rig context. */
+typedef struct sm_search_params {
+    int32_t levels;           /* 2 (1..4) */
+    float trans_half[3];      /* camera x right, y down, z forward: 2, 0, 2 m */
+    float trans_step[3];      /* 0.25 m each */
+    float rot_half_deg[3];    /* about camera x, y, z: 0, 3, 0 */
+    float rot_step_deg[3];    /* 0.5 each */
+    int32_t refine;           /* 4: level l+1 has steps / refine and spans +-1 step of level l on every active axis */
+    int32_t stride0;          /* 8: level l scores at max(1, stride0 >> l) */
+    int32_t top_k;            /* 4 (1..16) */
+    float colour_thresh;      /* 0.1 */
+} sm_search_params;
+typedef struct sm_search_info {
+    int32_t status;           /* SM_TRACK_* */
+    int32_t levels_run;
+    uint32_t candidates[4];
+    uint32_t best_score[4];
+    int32_t winner_rank;      /* -1: none */
+    sm_track_info track;
+    float start[16];
+    float anchor_time;
+    float score_ms, total_ms;
+} sm_search_info;
+#define SM_SEARCH_MAX_CANDIDATES (1u << 20)
+int sm_default_search_params(sm_search_params *p);
+int sm_score_poses_window(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *cand16, uint32_t n,
+                          const sm_track_params *tp, int32_t stride, float colour_thresh, int32_t min_time, int32_t max_time,
+                          uint32_t *scores);
+int sm_search_pose(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *centre16, const sm_track_params *tp,
+                   const sm_track_rgb_params *rp, const sm_search_params *sp, int32_t min_time, int32_t max_time, float *pose16_out,
+                   sm_search_info *info);
+int sm_close_loop_search(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *pose16, const sm_map_source *src,
+                         const sm_track_params *tp, const sm_track_rgb_params *rp, const sm_loop_params *lp, const sm_search_params *sp,
+                         float *pose16_out, sm_loop_info *info);
+int sm_set_auto_loop_search(sm_ctx *s, const sm_search_params *sp);
+
 /* ---- per-pass entry points (GlobalModel / IndexMap methods), synchronous ---- */
 /* Upload RGB / metric depth / semantic textures directly (bypasses p0). */
 int sm_set_frame(sm_ctx *s, const uint8_t *rgb, const float *depth_metric,

@@ -39,6 +39,7 @@ SYMBOLS = (
     "sm_default_loop_params", "sm_close_loop",
     "sm_track_frame_window", "sm_track_debug_window", "sm_track_frame_rgb_window", "sm_track_rgb_debug_window", "sm_close_loop_rgb",
     "sm_old_in_view", "sm_default_auto_loop_params", "sm_set_auto_loop", "sm_auto_loop_stats",
+    "sm_default_search_params", "sm_score_poses_window", "sm_search_pose", "sm_close_loop_search", "sm_set_auto_loop_search",
 )
 
 SM_COLL_SUM, SM_COLL_MIN, SM_COLL_GATHER = 0, 1, 2
@@ -262,6 +263,44 @@ def auto_loop_params(cfg, **over) -> SmAutoLoopParams:
         else:
             raise KeyError(k)
     return p
+
+
+class SmSearchParams(C.Structure):
+    _fields_ = [("levels", C.c_int32), ("trans_half", C.c_float * 3), ("trans_step", C.c_float * 3), ("rot_half_deg", C.c_float * 3),
+                ("rot_step_deg", C.c_float * 3), ("refine", C.c_int32), ("stride0", C.c_int32), ("top_k", C.c_int32),
+                ("colour_thresh", C.c_float)]
+
+
+class SmSearchInfo(C.Structure):
+    _fields_ = [("status", C.c_int32), ("levels_run", C.c_int32), ("candidates", C.c_uint32 * 4), ("best_score", C.c_uint32 * 4),
+                ("winner_rank", C.c_int32), ("track", SmTrackInfo), ("start", C.c_float * 16), ("anchor_time", C.c_float),
+                ("score_ms", C.c_float), ("total_ms", C.c_float)]
+
+
+SEARCH_MAX_CANDIDATES = 1 << 20
+
+
+def search_params(**over) -> SmSearchParams:
+    """sm_default_search_params (2 levels; +-2 m in x and z at 0.25 m, +-3 deg about y at 0.5 deg; refine 4, stride0 8, top_k 4,
+    colour_thresh 0.1) with fields overridden; the four per-axis fields take a sequence of three"""
+    p = SmSearchParams()
+    load().sm_default_search_params(C.byref(p))
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise KeyError(k)
+        if k in ("trans_half", "trans_step", "rot_half_deg", "rot_step_deg"):
+            for a, x in enumerate(v):
+                getattr(p, k)[a] = float(x)
+        else:
+            setattr(p, k, v)
+    return p
+
+
+def _search_arg(search):
+    """close_loop(search=...) / set_auto_loop(search=...): None or False = no search, True = the defaults, a dict = overrides"""
+    if search is None or search is False:
+        return None
+    return search_params(**({} if search is True else dict(search)))
 
 
 INT32_MIN, INT32_MAX = -2 ** 31, 2 ** 31 - 1
@@ -489,6 +528,12 @@ def load():
     L.sm_default_auto_loop_params.argtypes = [C.POINTER(SmConfig), C.POINTER(SmAutoLoopParams)]
     L.sm_set_auto_loop.argtypes = [vp, C.POINTER(SmAutoLoopParams), C.POINTER(SmMapSource)]
     L.sm_auto_loop_stats.argtypes = [vp, C.POINTER(SmAutoLoopStats)]
+    spp = C.POINTER(SmSearchParams)
+    L.sm_default_search_params.argtypes = [spp]
+    L.sm_score_poses_window.argtypes = [vp, vp, vp, vp, C.c_uint32, tpp, i32, C.c_float, i32, i32, vp]
+    L.sm_search_pose.argtypes = [vp, vp, vp, vp, tpp, rpp, spp, i32, i32, vp, C.POINTER(SmSearchInfo)]
+    L.sm_close_loop_search.argtypes = [vp, vp, vp, vp, C.POINTER(SmMapSource), tpp, rpp, lpp, spp, vp, C.POINTER(SmLoopInfo)]
+    L.sm_set_auto_loop_search.argtypes = [vp, spp]
     for name in SYMBOLS:
         getattr(L, name)          # AttributeError here = the library does not match the header
     _lib = L
@@ -872,10 +917,12 @@ class SurfelMap:
         self._chk(self._L.sm_track_debug_old(self._h, _ptr(depth), _ptr(pe), int(max_time), _ptr(pred), _ptr(sys29)), "sm_track_debug_old")
         return pred, sys29
 
-    def close_loop(self, depth, pose, paths=(), **params):
+    def close_loop(self, depth, pose, paths=(), search=None, **params):
         """Notice that the camera is back in mapped territory and pull the map straight (sm_close_loop).  pose: where the caller
         believes the camera is (4x4 camera->world or float32[16] column-major); paths: the map files that move with the model.
         params: fields of sm_loop_params (min_age, min_trans, min_rot_deg, max_trans, max_rot_deg) and of sm_track_params.
+        search: True or a dict of search_params() overrides measures the loop by a pose search around `pose` instead of a single
+        track from it (sm_close_loop_search), which reaches metres of drift.
         Returns (pose 4x4: corrected if status is "CLOSED", else as given; info dict: status (name), status_code, track (as
         track()'s info), D 4x4, t_a, t_b)."""
         depth = np.ascontiguousarray(depth, np.uint16)
@@ -888,6 +935,11 @@ class SurfelMap:
         g = _mat16(pose)
         out = np.zeros(16, np.float32)
         info = SmLoopInfo()
+        sp = _search_arg(search)
+        if sp is not None:
+            self._chk(self._L.sm_close_loop_search(self._h, None, _ptr(depth), _ptr(g), C.byref(src), C.byref(tp) if tp is not None else None,
+                                                   None, C.byref(lp), C.byref(sp), _ptr(out), C.byref(info)), "sm_close_loop_search")
+            return out.reshape(4, 4).T.copy(), _loop_info_dict(info)
         self._chk(self._L.sm_close_loop(self._h, _ptr(depth), _ptr(g), C.byref(src), C.byref(tp) if tp is not None else None, C.byref(lp),
                                         _ptr(out), C.byref(info)), "sm_close_loop")
         return out.reshape(4, 4).T.copy(), _loop_info_dict(info)
@@ -967,9 +1019,10 @@ class SurfelMap:
                                                     int(max_time), _ptr(pred), _ptr(sys29)), "sm_track_rgb_debug_window")
         return pred, sys29
 
-    def close_loop_rgb(self, rgb, depth, pose, paths=(), **params):
+    def close_loop_rgb(self, rgb, depth, pose, paths=(), search=None, **params):
         """close_loop() with the loop measured by the colour tracker as well (sm_close_loop_rgb): params may also name the fields of
-        sm_track_rgb_params.  Returns (pose, info) as close_loop()."""
+        sm_track_rgb_params.  search as close_loop()'s: the search scores with the colour gate.  Returns (pose, info) as
+        close_loop()."""
         rgb = np.ascontiguousarray(rgb, np.uint8)
         depth = np.ascontiguousarray(depth, np.uint16)
         assert depth.size == self.P and rgb.size == self.P * 3, (depth.shape, rgb.shape)
@@ -983,24 +1036,84 @@ class SurfelMap:
         g = _mat16(pose)
         out = np.zeros(16, np.float32)
         info = SmLoopInfo()
+        sp = _search_arg(search)
+        if sp is not None:
+            self._chk(self._L.sm_close_loop_search(self._h, _ptr(rgb), _ptr(depth), _ptr(g), C.byref(src),
+                                                   C.byref(tp) if tp is not None else None, C.byref(rp) if rp is not None else None,
+                                                   C.byref(lp), C.byref(sp), _ptr(out), C.byref(info)), "sm_close_loop_search")
+            return out.reshape(4, 4).T.copy(), _loop_info_dict(info)
         self._chk(self._L.sm_close_loop_rgb(self._h, _ptr(rgb), _ptr(depth), _ptr(g), C.byref(src), C.byref(tp) if tp is not None else None,
                                             C.byref(rp) if rp is not None else None, C.byref(lp), _ptr(out), C.byref(info)),
                   "sm_close_loop_rgb")
         return out.reshape(4, 4).T.copy(), _loop_info_dict(info)
 
-    def set_auto_loop(self, paths=(), **params):
+    def set_auto_loop(self, paths=(), search=None, **params):
         """Make track() / track_rgb() (and process_frame_tracked*) close loops by themselves (sm_set_auto_loop): they track in the
         young map, count the old surfels in view and, with at least min_old of them, make one close_loop attempt before the
         frame is fused.  paths: the map files that move with the model (those of set_auto_retire are added).  params override
         auto_loop_params(cfg).  Neither paths nor params: off -- so to switch the policy on with every default and no file
-        of the caller's, name one default, e.g. set_auto_loop(every=1)."""
+        of the caller's, name one default, e.g. set_auto_loop(every=1).  search: True or a dict of search_params() overrides makes
+        the attempt a close_loop(search=...) (sm_set_auto_loop_search); every call without it switches the search off."""
         paths = list(paths)
-        if not params and not paths:
+        sp = _search_arg(search)
+        if not params and not paths and sp is None:
             self._chk(self._L.sm_set_auto_loop(self._h, None, None), "sm_set_auto_loop")
-            return
-        p = auto_loop_params(self.cfg, **params)
-        src = map_source(paths, include_model=True)
-        self._chk(self._L.sm_set_auto_loop(self._h, C.byref(p), C.byref(src)), "sm_set_auto_loop")
+        else:
+            p = auto_loop_params(self.cfg, **params)
+            src = map_source(paths, include_model=True)
+            self._chk(self._L.sm_set_auto_loop(self._h, C.byref(p), C.byref(src)), "sm_set_auto_loop")
+        self._chk(self._L.sm_set_auto_loop_search(self._h, C.byref(sp) if sp is not None else None), "sm_set_auto_loop_search")
+
+    # -- pose search before the tracker (sm_score_poses_window, sm_search_pose)
+    def score_poses(self, depth, cands, rgb=None, stride=1, colour_thresh=0.1, min_time=INT32_MIN, max_time=INT32_MAX, **params):
+        """How many grid points of `depth` at `stride` the tracker would call inliers under each candidate pose, against the
+        prediction of the window (sm_score_poses_window).  cands: float32[n][16] column-major poses, or [n][4][4] matrices (numpy
+        row/col indexing).  rgb given: the colour gate |Y_frame - Y_surfel| <= colour_thresh as well.  params: fields of
+        sm_track_params (pixel_stride is not used).  Returns uint32[n]."""
+        depth = np.ascontiguousarray(depth, np.uint16)
+        assert depth.size == self.P, depth.shape
+        if rgb is not None:
+            rgb = np.ascontiguousarray(rgb, np.uint8)
+            assert rgb.size == self.P * 3, rgb.shape
+        c = np.asarray(cands, np.float32)
+        if c.ndim == 3:
+            c = c.transpose(0, 2, 1)
+        c = np.ascontiguousarray(c.reshape(-1, 16))
+        p = track_params(**params) if params else None
+        scores = np.zeros(len(c), np.uint32)
+        self._chk(self._L.sm_score_poses_window(self._h, _ptr(rgb), _ptr(depth), _ptr(c), len(c), C.byref(p) if p is not None else None,
+                                                int(stride), float(colour_thresh), int(min_time), int(max_time), _ptr(scores)),
+                  "sm_score_poses_window")
+        return scores
+
+    def search_pose(self, depth, centre, rgb=None, min_time=INT32_MIN, max_time=INT32_MAX, search=None, **params):
+        """Find the camera within metres of `centre`: score a grid of poses around it, refine the best, track from the winners
+        (sm_search_pose).  search: a dict of search_params() overrides; params: fields of sm_track_params and, with rgb, of
+        sm_track_rgb_params.  Returns (pose 4x4: the centre unless status is "OK"; info dict: status, status_code, levels_run,
+        candidates, best_score, winner_rank, track (as track()'s info), start 4x4, anchor_time, score_ms, total_ms)."""
+        depth = np.ascontiguousarray(depth, np.uint16)
+        assert depth.size == self.P, depth.shape
+        if rgb is not None:
+            rgb = np.ascontiguousarray(rgb, np.uint8)
+            assert rgb.size == self.P * 3, rgb.shape
+        icp = {k: v for k, v in params.items() if k not in self._RGB_KEYS}
+        col = {k: v for k, v in params.items() if k in self._RGB_KEYS}
+        p = track_params(**icp) if icp else None
+        q = track_rgb_params(**col) if col else None
+        sp = search_params(**dict(search)) if search else None
+        g = _mat16(centre)
+        out = np.zeros(16, np.float32)
+        info = SmSearchInfo()
+        self._chk(self._L.sm_search_pose(self._h, _ptr(rgb), _ptr(depth), _ptr(g), C.byref(p) if p is not None else None,
+                                         C.byref(q) if q is not None else None, C.byref(sp) if sp is not None else None, int(min_time),
+                                         int(max_time), _ptr(out), C.byref(info)), "sm_search_pose")
+        n = int(info.levels_run)
+        d = dict(status=TRACK_STATUS.get(info.status, str(info.status)), status_code=int(info.status), levels_run=n,
+                 candidates=[int(x) for x in info.candidates[:n]], best_score=[int(x) for x in info.best_score[:n]],
+                 winner_rank=int(info.winner_rank), track=_track_info_dict(info.track),
+                 start=np.array(info.start[:], np.float32).reshape(4, 4).T.copy(), anchor_time=float(info.anchor_time),
+                 score_ms=float(info.score_ms), total_ms=float(info.total_ms))
+        return out.reshape(4, 4).T.copy(), d
 
     def auto_loop_stats(self) -> dict:
         """checked, attempts, closed, none, rejected, failed, no_old_map, last_census, and last = the last attempt's info as

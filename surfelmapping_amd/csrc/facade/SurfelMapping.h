@@ -267,7 +267,10 @@ public:
         const sm_map_source src{paths.data(), (uint32_t)paths.size(), 1};
         Eigen::Matrix4f out = pose;
         (void)sm_sync(ctx_);                                             // (SM_FACADE_ASYNC: frames may still be in flight)
-        if (sm_close_loop(ctx_, depth, pose.data(), &src, nullptr, nullptr, out.data(), &lastLoopInfo) != SM_OK) {
+        const int rc = loopSearch_ ? sm_close_loop_search(ctx_, nullptr, depth, pose.data(), &src, nullptr, nullptr, loopParams(), &loopSearchParams_,
+                                                          out.data(), &lastLoopInfo)
+                                   : sm_close_loop(ctx_, depth, pose.data(), &src, nullptr, nullptr, out.data(), &lastLoopInfo);
+        if (rc != SM_OK) {
             std::printf("closeLoop: %s\n", sm_last_error());
             return pose;
         }
@@ -285,13 +288,37 @@ public:
         const sm_map_source src{paths.data(), (uint32_t)paths.size(), 1};
         Eigen::Matrix4f out = pose;
         (void)sm_sync(ctx_);
-        if (sm_close_loop_rgb(ctx_, rgb, depth, pose.data(), &src, nullptr, nullptr, nullptr, out.data(), &lastLoopInfo) != SM_OK) {
+        const int rc = loopSearch_ ? sm_close_loop_search(ctx_, rgb, depth, pose.data(), &src, nullptr, nullptr, loopParams(), &loopSearchParams_,
+                                                          out.data(), &lastLoopInfo)
+                                   : sm_close_loop_rgb(ctx_, rgb, depth, pose.data(), &src, nullptr, nullptr, nullptr, out.data(), &lastLoopInfo);
+        if (rc != SM_OK) {
             std::printf("closeLoop: %s\n", sm_last_error());
             return pose;
         }
         return out;
     }
     const sm_loop_info &getLastLoopInfo() { return lastLoopInfo; }
+    // Measure loops by a pose search (sm_close_loop_search, sm_set_auto_loop_search): instead of one track from the believed pose,
+    // which converges from a few decimetres, a grid of poses +-transHalf metres sideways and forward and +-yawHalfDeg degrees about
+    // the vertical around it is scored against the old surfels, refined, and the best are tracked from -- metres of drift close.
+    // Honoured by both closeLoop overloads and by setAutoLoop, before or after this call.  Negative arguments keep the defaults
+    // (2 m, 3 degrees); maxTrans, if not negative, replaces the 2 m above which a measured loop is rejected (the default box
+    // reaches 2.8 m).  on = false: off, and the bound is the default again.
+    bool setLoopSearch(bool on, float transHalf = -1.0f, float yawHalfDeg = -1.0f, float maxTrans = -1.0f)
+    {
+        sm_search_params sp;
+        sm_default_search_params(&sp);
+        if (transHalf >= 0.0f) sp.trans_half[0] = sp.trans_half[2] = transHalf;
+        if (yawHalfDeg >= 0.0f) sp.rot_half_deg[1] = yawHalfDeg;
+        if (sm_set_auto_loop_search(ctx_, on ? &sp : nullptr) != SM_OK) {
+            std::printf("setLoopSearch: %s\n", sm_last_error());
+            return false;
+        }
+        loopSearch_ = on;
+        loopSearchParams_ = sp;
+        loopMaxTrans_ = on ? maxTrans : -1.0f;
+        return true;
+    }
     // Close loops unasked (sm_set_auto_loop): while on, every processFrame that tracks (null gtPose) tracks in the young map, counts
     // the surfels older than time_delta frames the tracked pose sees and, with at least minOld of them, makes one closeLoop attempt
     // before the frame is fused -- with the colour term after setTrackColour(true).  The map files `mapFiles` and those of
@@ -308,6 +335,7 @@ public:
             if (every >= 0) p.every = every;
             if (rest >= 0) p.rest = rest;
             if (minOld >= 0) p.min_old = (uint32_t)minOld;
+            if (loopSearch_ && loopMaxTrans_ >= 0.0f) p.loop.max_trans = loopMaxTrans_;
             std::vector<const char *> paths;
             for (const std::string &f : mapFiles) paths.push_back(f.c_str());
             const sm_map_source src{paths.data(), (uint32_t)paths.size(), 1};
@@ -359,6 +387,20 @@ private:
     sm_track_rgb_info lastTrackRgbInfo{};
     bool trackColour_ = false;
     sm_loop_info lastLoopInfo{};
+    bool loopSearch_ = false;
+    sm_search_params loopSearchParams_{};
+    float loopMaxTrans_ = -1.0f;
+    sm_loop_params loopParams_{};
+    // the loop bounds of a searched closeLoop: the defaults, with setLoopSearch's maxTrans (null: the defaults as they are)
+    const sm_loop_params *loopParams()
+    {
+        if (loopMaxTrans_ < 0.0f) return nullptr;
+        sm_config c;
+        sm_default_config(&c, Config::W(), Config::H(), Config::fx(), Config::fy(), Config::cx(), Config::cy());
+        sm_default_loop_params(&c, &loopParams_);
+        loopParams_.max_trans = loopMaxTrans_;
+        return &loopParams_;
+    }
     bool beginCleanPoints = false;
     bool async_ = false;
 };

@@ -12,6 +12,7 @@
 //   sm_render_maps.hip  views of a map set (sm_render_*_maps): map files streamed through the renderers
 //   sm_recall.hip    paging in (sm_recall*, sm_set_auto_recall): records of map files near the camera back into the model
 //   sm_warp.hip      closing loops (sm_warp_by_time, sm_loop_spread): the model and map files warped by surfel time
+//   sm_search.hip    pose search before the tracker (sm_score_poses_window, sm_search_pose)
 // and, beside it, for everything that touches a map file: sm_mapfile.h (the format: checked open, writer, chunk plan; host only)
 // and sm_map_stream.h (the double-buffered chunk stream of sm_render_maps.hip and sm_recall.hip); for the occupied slots and the
 // compaction schedule: sm_slots.h (SlotSchedule; host only).  What alternates between consecutive frames is FrameSet, below.
@@ -209,9 +210,24 @@ struct Warp {
     bool stats_valid = false;
 };
 
+// pose search (sm_search.hip, sm_k_search.h): scratch allocated by the first call, sized for the frame and grown with the
+// candidate list
+struct Search {
+    Dev<uint8_t> d_rgb;                // the frame's colour image, row-major
+    Dev<float4> d_samp;                // the packed grid points, two float4 each: (v, Y_f), (n, 0)
+    Dev<float4> d_plane;               // the prediction, two float4 per pixel: (p_m, Y_m), (n_m, valid)
+    Dev<uint32_t> d_nsamp;             // how many grid points were packed
+    Dev<float> d_cand;                 // 12 floats per candidate: columns 0..3 of its pose, rows 0..2
+    Dev<uint32_t> d_scores;
+    size_t cand_cap = 0;
+    Event ev[2];                       // around the scoring kernels
+};
+
 // closing loops unasked (sm_loop.hip): the policy of sm_set_auto_loop and its tally
 struct AutoLoop {
     bool on = false;
+    bool search = false;               // sm_set_auto_loop_search: the attempt is sm_close_loop_search with `sp`
+    sm_search_params sp{};
     sm_auto_loop_params p{};
     std::vector<std::string> paths;    // the caller's map files; the retirement policy's are added per attempt
     int64_t rest_until = 0;            // no census before this tick
@@ -433,6 +449,7 @@ struct sm_ctx {
     Recall rec;
     Warp warp;
     AutoLoop aloop;
+    Search srch;
     // host frame state (src/SurfelMapping.h:100-103)
     int tick = 0;
     bool ref_set = false;
@@ -504,6 +521,27 @@ int recall_ensure_scratch(sm_ctx *s);             // what recall_box_of needs (s
 // what the two policies require of each other when both are on (SM_E_ARG with g_err set otherwise)
 int check_recall_policy(float radius, const sm_retire_params &rp, const char *who);
 
+// ---- sm_track.hip ----
+// What sm_search.hip takes from a tracked frame's preparation.  The prediction's camera and image, the grid of `stride` and the
+// association gates, as the trackers' kernels get them:
+struct SearchFrame {
+    float tinv_prev[16];               // world -> prediction camera
+    float fx, fy, cx, cy;
+    int W, H;
+    int stride, ni, nj, n;             // the grid: ni columns x nj rows, n = ni * nj
+    float dist, cos_angle;
+};
+// the buffers the preparation leaves on the context's stream: vertex and normal per grid point (row-major over the grid), slot per
+// pixel (-1: none), and the surfels in view of the prediction (a device word)
+struct SearchBufs { const float4 *v, *n; const int32_t *pred; const uint32_t *in_view; };
+// sm_track_frame_window's checks and preparation for the grid of `stride` (tp's own pixel_stride is not used), enqueued:
+// *no_model when there is no processed frame or no live surfel (nothing is enqueued then).  fresh = false: the prediction of the
+// last call stands (same frame, same window, nothing ran in between) and only the grid's vertex stage runs again.
+int search_prepare(sm_ctx *s, const uint16_t *depth_mm, const sm_track_params &tp, int32_t stride, int32_t min_time, int32_t max_time,
+                   bool fresh, SearchFrame *f, SearchBufs *b, bool *no_model, const char *fn);
+// ---- sm_search.hip ----
+// sm_search_pose's rules for its parameters (SM_E_ARG with g_err set)
+int check_search_params(const sm_search_params &p, const char *who);
 // ---- sm_loop.hip ----
 // sm_track_frame (rgb null) / sm_track_frame_rgb while sm_set_auto_loop is on: the young-window track, the census, one attempt
 int auto_loop_track(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params,

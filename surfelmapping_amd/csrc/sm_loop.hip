@@ -1,6 +1,6 @@
 // sm_loop.hip -- closing loops unasked (DESIGN.md "4i. Closing loops unasked"): the per-frame policy of sm_set_auto_loop.  While it
 // is on, sm_track_frame / sm_track_frame_rgb track in the young map, count the old surfels the tracked pose sees (sm_old_in_view)
-// and, with enough of them, make one sm_close_loop / sm_close_loop_rgb attempt.  Host code only: the kernels are the trackers'
+// and, with enough of them, make one sm_close_loop / sm_close_loop_rgb attempt (sm_close_loop_search after sm_set_auto_loop_search).  Host code only: the kernels are the trackers'
 // (sm_k_track.h, sm_k_loop.h) and the warp's (sm_k_warp.h).
 #include "sm_ctx.h"
 #include "sm_mapfile.h"
@@ -44,7 +44,8 @@ int sm_impl::auto_loop_track(sm_ctx *s, const uint8_t *rgb, const uint16_t *dept
     sm_loop_info li;
     a.stats.attempts++;
     a.rest_until = T + a.p.rest;                          // whatever the outcome
-    if (rgb) rc = sm_close_loop_rgb(s, rgb, depth_mm, tracked, &src, params, rgb_params, &a.p.loop, corrected, &li);
+    if (a.search) rc = sm_close_loop_search(s, rgb, depth_mm, tracked, &src, params, rgb_params, &a.p.loop, &a.sp, corrected, &li);
+    else if (rgb) rc = sm_close_loop_rgb(s, rgb, depth_mm, tracked, &src, params, rgb_params, &a.p.loop, corrected, &li);
     else rc = sm_close_loop(s, depth_mm, tracked, &src, params, &a.p.loop, corrected, &li);
     if (rc) { a.stats.failed++; return rc; }
     a.stats.last = li;
@@ -95,6 +96,19 @@ int sm_set_auto_loop(sm_ctx *s, const sm_auto_loop_params *p, const sm_map_sourc
     a.paths = std::move(paths);
     a.rest_until = 0;
     a.stats = sm_auto_loop_stats_t{};
+    return SM_OK;
+}
+
+int sm_set_auto_loop_search(sm_ctx *s, const sm_search_params *sp)
+{
+    const char *who = "sm_set_auto_loop_search";
+    if (!s) { g_err = std::string(who) + ": null context"; return SM_E_ARG; }
+    if (s->ss_on || s->rig_on) { g_err = std::string(who) + ": a sharded or rig context holds only its own surfels"; return SM_E_UNSUPPORTED; }
+    AutoLoop &a = s->aloop;
+    if (!sp) { a.search = false; return SM_OK; }
+    if (int rc = check_search_params(*sp, who)) return rc;
+    a.search = true;
+    a.sp = *sp;
     return SM_OK;
 }
 

@@ -413,6 +413,40 @@ int track_debug(sm_ctx *s, const uint16_t *depth_mm, const float *pose16_eval, c
 }
 }  // namespace
 
+// ---- what the pose search takes from the preparation (sm_search.hip) ----
+int sm_impl::search_prepare(sm_ctx *s, const uint16_t *depth_mm, const sm_track_params &params, int32_t stride, int32_t min_time,
+                            int32_t max_time, bool fresh, SearchFrame *f, SearchBufs *b, bool *no_model, const char *fn)
+{
+    sm_track_params p = params;
+    p.pixel_stride = stride;
+    int rc;
+    if ((rc = track_params_check(s, p, fn)) || (rc = track_check(s, fn))) return rc;
+    HIPCK(hipSetDevice(s->cfg.device));
+    if ((rc = pull_state(s))) return rc;                      // waits for frames in flight: the model after the last frame
+    *no_model = s->trk.n_hist == 0 || s->h_state->count == s->h_state->garbage;
+    if (*no_model) return SM_OK;
+    if ((rc = track_alloc(s))) return rc;
+    const TrackParams tp = track_params(s, p);
+    if (fresh) {
+        float eye[16];
+        for (int e = 0; e < 16; ++e) eye[e] = (e % 5 == 0) ? 1.0f : 0.0f;
+        const Window win{min_time, max_time};
+        if ((rc = track_prepare(s, depth_mm, tp, eye, eye, false, &win))) return rc;   // (no estimate is iterated)
+    } else {
+        hipLaunchKernelGGL(k_track_vertex, dim3((tp.n + 255) / 256), dim3(256), 0, s->stream, s->trk.d_depth, s->d_xs, s->d_ys, tp,
+                           s->trk.d_v, s->trk.d_n);
+        HIPCK(hipGetLastError());
+    }
+    memcpy(f->tinv_prev, tp.tinv_prev, sizeof f->tinv_prev);
+    f->fx = tp.fx; f->fy = tp.fy; f->cx = tp.cx; f->cy = tp.cy;
+    f->W = tp.W; f->H = tp.H;
+    f->stride = tp.stride; f->ni = tp.ni; f->nj = tp.nj; f->n = tp.n;
+    f->dist = tp.dist; f->cos_angle = tp.cos_angle;
+    b->v = s->trk.d_v; b->n = s->trk.d_n; b->pred = s->trk.d_pred;
+    b->in_view = &s->trk.d_state.get()->in_view;
+    return SM_OK;
+}
+
 extern "C" {
 
 int sm_track_frame(sm_ctx *s, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params, float *pose16_out,

@@ -353,10 +353,11 @@ int sm_impl::check_loop_params(const sm_loop_params &p, const char *who)
 }
 
 namespace {
-// sm_close_loop (rgb null: the depth-only measurement) and sm_close_loop_rgb
+// sm_close_loop (rgb null: the depth-only measurement) and sm_close_loop_rgb; search: sm_close_loop_search, whose step 1 is
+// sm_search_pose with sp (null: its defaults)
 int close_loop(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *pose16, const sm_map_source *src,
-               const sm_track_params *tp, const sm_track_rgb_params *rp, const sm_loop_params *lp, float *pose16_out, sm_loop_info *info,
-               const char *who)
+               const sm_track_params *tp, const sm_track_rgb_params *rp, const sm_loop_params *lp, bool search, const sm_search_params *sp,
+               float *pose16_out, sm_loop_info *info, const char *who)
 {
     if (!s || !depth_mm || !pose16 || !src || !pose16_out || !info) { g_err = std::string(who) + ": null argument"; return SM_E_ARG; }
     if (s->ss_on || s->rig_on) { g_err = std::string(who) + ": a sharded or rig context holds only its own surfels"; return SM_E_UNSUPPORTED; }
@@ -372,7 +373,14 @@ int close_loop(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const fl
     const int64_t mt = (int64_t)s->tick - 1 - p.min_age;
     const int32_t max_time = (int32_t)std::max<int64_t>(mt, INT32_MIN);
     float t_old[16], anchor = -1.0f;
-    if (rgb) rc = sm_track_frame_rgb_window(s, rgb, depth_mm, pose16, tp, rp, INT32_MIN, max_time, t_old, &info->track, nullptr, &anchor);
+    if (search) {
+        sm_search_info si;
+        if ((rc = sm_search_pose(s, rgb, depth_mm, pose16, tp, rp, sp, INT32_MIN, max_time, t_old, &si))) return rc;
+        info->track = si.track;
+        info->track.status = si.status;
+        anchor = si.anchor_time;
+    }
+    else if (rgb) rc = sm_track_frame_rgb_window(s, rgb, depth_mm, pose16, tp, rp, INT32_MIN, max_time, t_old, &info->track, nullptr, &anchor);
     else rc = sm_track_frame_old(s, depth_mm, pose16, tp, max_time, t_old, &info->track, &anchor);
     if (rc) return rc;
     if (info->track.status == SM_TRACK_NO_MODEL) { info->status = SM_LOOP_NO_OLD_MAP; return SM_OK; }
@@ -424,7 +432,7 @@ extern "C" {
 int sm_close_loop(sm_ctx *s, const uint16_t *depth_mm, const float *pose16, const sm_map_source *src, const sm_track_params *tp,
                   const sm_loop_params *lp, float *pose16_out, sm_loop_info *info)
 {
-    return close_loop(s, nullptr, depth_mm, pose16, src, tp, nullptr, lp, pose16_out, info, "sm_close_loop");
+    return close_loop(s, nullptr, depth_mm, pose16, src, tp, nullptr, lp, false, nullptr, pose16_out, info, "sm_close_loop");
 }
 
 int sm_close_loop_rgb(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *pose16, const sm_map_source *src,
@@ -432,7 +440,14 @@ int sm_close_loop_rgb(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, c
                       sm_loop_info *info)
 {
     if (!rgb) { g_err = "sm_close_loop_rgb: null argument"; return SM_E_ARG; }
-    return close_loop(s, rgb, depth_mm, pose16, src, tp, rp, lp, pose16_out, info, "sm_close_loop_rgb");
+    return close_loop(s, rgb, depth_mm, pose16, src, tp, rp, lp, false, nullptr, pose16_out, info, "sm_close_loop_rgb");
+}
+
+int sm_close_loop_search(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *pose16, const sm_map_source *src,
+                         const sm_track_params *tp, const sm_track_rgb_params *rp, const sm_loop_params *lp, const sm_search_params *sp,
+                         float *pose16_out, sm_loop_info *info)
+{
+    return close_loop(s, rgb, depth_mm, pose16, src, tp, rp, lp, true, sp, pose16_out, info, "sm_close_loop_search");
 }
 
 int sm_loop_spread(const float *D16, int32_t t_a, int32_t t_b, float *corr12)

@@ -791,6 +791,9 @@ int sm_device_download(sm_ctx *s, void *dst_host, const void *src_device, size_t
 /* diagnostic: how many frames so far took the rare path of the two-launch frame (their association waited, inside its launch, for
  * the publisher and the cap repair: conflicts > W*H, or the "id 0" surfel died).  Synchronises. */
 int sm_debug_slow_frames(sm_ctx *s, uint32_t *n);
+/* diagnostic: squeezes between the two launches of a frame so far (DESIGN.md 4 "Tail squeeze") -- `tail`: those that started at a
+ * dense tile and left dead slots below it, `full`: those that started at the first dead slot.  Synchronises. */
+int sm_debug_squeezes(sm_ctx *s, uint32_t *tail, uint32_t *full);
 /* Diagnostic: processes that hold compute queues on this context's GPU according to the KFD driver's tables (>= 1: this
  * one included), or -1 if /sys/class/kfd is not readable.  The in-place compaction switches to its ticket-ordered form
  * (no co-residency assumption) whenever the value is > 1 or a second context of this process shares the GPU; the value is

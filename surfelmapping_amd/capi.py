@@ -21,7 +21,7 @@ TEX_DEPTH_METRIC, TEX_DEPTH_FILTERED, TEX_LAST = 0, 1, 2
 SYMBOLS = (
     "sm_api_version", "sm_last_error", "sm_default_config", "sm_create", "sm_destroy",
     "sm_process_frame", "sm_process_frame_device", "sm_process_frame_async",
-    "sm_inputs_consumed", "sm_host_alloc", "sm_host_alloc_frame", "sm_host_free", "sm_debug_slow_frames", "sm_sync", "sm_clean_points", "sm_clean_points_ex", "sm_clean_points_cb", "sm_reset",
+    "sm_inputs_consumed", "sm_host_alloc", "sm_host_alloc_frame", "sm_host_free", "sm_debug_slow_frames", "sm_debug_squeezes", "sm_sync", "sm_clean_points", "sm_clean_points_ex", "sm_clean_points_cb", "sm_reset",
     "sm_get_counts", "sm_download_model_aos", "sm_upload_model_aos", "sm_save_map", "sm_load_map",
     "sm_download_index_map", "sm_download_raw_cloud", "sm_download_depth", "sm_render_image", "sm_render_model",
     "sm_render_model_device", "sm_render_image_maps", "sm_render_model_maps", "sm_render_maps_stats", "sm_set_frame", "sm_set_tick",
@@ -444,6 +444,7 @@ def load():
     L.sm_host_free.argtypes = [vp, vp]
     L.sm_host_alloc_frame.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     L.sm_debug_slow_frames.argtypes = [vp, u32p]
+    L.sm_debug_squeezes.argtypes = [vp, u32p, u32p]
     L.sm_sync.argtypes = [vp]
     L.sm_clean_points.argtypes = [vp, vp, vp, vp]
     L.sm_clean_points_ex.argtypes = [vp, vp, vp, vp, C.c_int]
@@ -630,6 +631,13 @@ class SurfelMap:
         n = C.c_uint32()
         self._chk(self._L.sm_debug_slow_frames(self._h, C.byref(n)), "sm_debug_slow_frames")
         return int(n.value)
+
+    def debug_squeezes(self):
+        """(tail, full): the squeezes between a frame's two launches so far that left dead slots below their boundary / that
+        squeezed every dead slot (diagnostic; synchronises)"""
+        t, f = C.c_uint32(), C.c_uint32()
+        self._chk(self._L.sm_debug_squeezes(self._h, C.byref(t), C.byref(f)), "sm_debug_squeezes")
+        return int(t.value), int(f.value)
 
     def inputs_consumed(self):
         self._chk(self._L.sm_inputs_consumed(self._h), "sm_inputs_consumed")

@@ -192,6 +192,8 @@ Switches read_switches()
     auto num = [](const char *name, long unset) { const char *e = std::getenv(name); return e ? std::atol(e) : unset; };
     sw.defer_assoc = !off("SM_DEFER_ASSOC");
     sw.two_launch = !off("SM_TWO_LAUNCH");
+    sw.tail_squeeze = !off("SM_TAIL_SQUEEZE");
+    sw.tail_thresh = (uint32_t)std::max(1l, num("SM_TAIL_THRESH", (long)TAIL_DEAD_THRESH));
     sw.pass_split = (int)num("SM_PASS_SPLIT", 0);
     if (const char *e = std::getenv("SM_PASS_TRACE")) { sw.trace = true; sw.trace_prefix = e; }
     if (std::getenv("SM_COMPACT_TICKETS")) sw.compact_tickets = off("SM_COMPACT_TICKETS") ? 0 : 1;
@@ -395,7 +397,7 @@ int launch_conflict_finalize(sm_ctx *s, const FrameParams &fp, bool timed = fals
         // A cull that only marks the dead gets its totals from k_conflict's partial sums in the finalize kernel.
         const int ngroups = std::max<int>(1, (int)((s->slots.tiles() + GROUP - 1) / GROUP));
         hipLaunchKernelGGL(k_scan_cull, dim3(ngroups), dim3(1024), 0, s->stream, s->d_state, s->d_tile_cnt, s->d_tile_allow,
-                           s->d_tile_keep, s->d_group_tot, s->d_tile_dead);
+                           s->d_tile_keep, s->d_group_tot, s->d_tile_dead, 0u, 0u);
         HIPCK(hipGetLastError());
     }
     hipLaunchKernelGGL(k_cull_finalize, dim3(1), dim3(1024), 0, s->stream, s->d_state, fp, s->d_cm, s->d_dm, s->d_zm,
@@ -447,7 +449,8 @@ PassGrid pass_grid_policy(sm_ctx *s, bool two, bool direct)
 // conflict test + cull (marks only) + splat in ONE pass over the surfels, then the publisher / cap fixup kernel.
 // direct: the frame appends directly (k_associate_direct follows): the pass also counts the candidate pixels, the fixup
 // publishes their group prefixes and the new count.  n_prep: the flag workgroups the frame's preparation launch ran.
-int launch_surfel_pass(sm_ctx *s, const FrameParams &fp, bool timed, bool direct, uint32_t n_prep)
+// squeezed: a squeeze ran ahead of the pass and has taken the marks 2..4 (Timeline::Flags): the pass ends at the association's mark 5.
+int launch_surfel_pass(sm_ctx *s, const FrameParams &fp, bool timed, bool direct, uint32_t n_prep, bool squeezed = false)
 {
     if (n_prep == 0) { g_err = "internal: one-pass frame without tile flags from the preparation launch"; return SM_E_ARG; }
     // two-launch frame: the association will be held back, and the fixup step with it (launch_prep carries both); the candidate
@@ -478,7 +481,7 @@ int launch_surfel_pass(sm_ctx *s, const FrameParams &fp, bool timed, bool direct
                        f.wave_cnt, s->d_tb, f.tile_flags, pp.d_lazy, s->d_alive, s->d_tile_dead, sub, s->keyT(), s->d_undo, tile_bound,
                        s->d_frame_sub, ca, s->d_pass_trace);
     HIPCK(hipGetLastError());
-    if (s->tl.mark(s->stream, 2, timed) || s->tl.mark(s->stream, 3, timed)) return SM_E_HIP;
+    if (!squeezed && (s->tl.mark(s->stream, 2, timed) || s->tl.mark(s->stream, 3, timed))) return SM_E_HIP;
     FixArgs x{};
     DirectArgs &da = x.da;
     da.on = direct ? (two ? 2 : 1) : 0;
@@ -496,7 +499,7 @@ int launch_surfel_pass(sm_ctx *s, const FrameParams &fp, bool timed, bool direct
     x.host_stat = s->d_stat; x.prep_part = f.prep_part; x.n_prep = n_prep; x.tb = s->d_tb; x.n_crew = (uint32_t)g.fix_workers;
     if (two) s->held.hold_fixup(x);
     else if (launch_fixup(s, fp, x)) return SM_E_HIP;
-    if (s->tl.mark(s->stream, 4, timed)) return SM_E_HIP;
+    if (!squeezed && s->tl.mark(s->stream, 4, timed)) return SM_E_HIP;
     check_alive(s, 1u + 16u * (uint32_t)(s->tick & 0xFFFF));
     return SM_OK;
 }
@@ -594,6 +597,36 @@ int launch_associate(sm_ctx *s, const FrameParams &fp, bool timed)
     if (s->tl.mark(s->stream, 7, timed)) return SM_E_HIP;
     check_alive(s, 5u + 16u * (uint32_t)(s->tick & 0xFFFF));
     return SM_OK;
+}
+
+// The kill-nothing compaction (enqueue only): k_scan_cull -> k_cull_finalize -> k_compact<false> over the dead counts and alive words
+// alone -- no conflict masks exist and none are read.  Nothing of the last frame may be held back or pending (the caller completes it).
+//   in_frame: between the two launches of a frame -- k_compact itself restores the alive words and resets the skip flags of the
+//             tiles it rewrites; the key map has just been cleared, no id is outstanding.  Otherwise the caller launches k_post_fill,
+//             and the key map's slot numbers are translated here.
+//   tail:     the squeeze may start at the first dense tile and leave the few dead slots below it (TAIL_DEAD_THRESH); otherwise
+//             it starts at the first dead slot and leaves none.
+int launch_squeeze(sm_ctx *s, bool in_frame, bool tail, bool timed)
+{
+    FrameParams fp = make_params(s, s->curr_pose);
+    fp.maintenance = in_frame ? 2 : 1;
+    fp.compact_now = 1;
+    fp.conflict_cap = 0xFFFFFFFFu;
+    fp.no_masks = 1;
+    fp.tail_thresh = tail ? s->sw.tail_thresh : 0u;
+    const uint64_t tiles = s->slots.tiles() + 1;
+    const int ngroups = std::max<int>(1, (int)((tiles + GROUP - 1) / GROUP));
+    hipLaunchKernelGGL(k_scan_cull, dim3(ngroups), dim3(1024), 0, s->stream, s->d_state, s->d_tile_cnt, s->d_tile_allow,
+                       s->d_tile_keep, s->d_group_tot, s->d_tile_dead, 1u, fp.tail_thresh);
+    hipLaunchKernelGGL(k_cull_finalize, dim3(1), dim3(1024), 0, s->stream, s->d_state, fp, s->d_cm, s->d_dm, s->d_zm,
+                       s->d_tile_cnt, s->d_tile_allow, s->d_tile_keep, s->d_group_tot, s->d_group_base, s->d_conf_part, 0u,
+                       s->d_alive, s->d_tile_dead, s->d_stat);
+    if (!in_frame && s->slots.keys_are_slots())     // ids of the index map: slot -> position among the live surfels, as the API hands them out
+        hipLaunchKernelGGL(k_remap_keys, dim3((s->P + 255) / 256), dim3(256), 0, s->stream, s->d_state, s->keyT(), s->P, s->d_alive,
+                           s->d_tile_keep, s->d_group_base);
+    HIPCK(hipGetLastError());
+    if (s->tl.mark(s->stream, 2, timed) || s->tl.mark(s->stream, 3, timed)) return SM_E_HIP;
+    return launch_compact(s, fp, false, timed);
 }
 
 // empty the model on the device (reset path; synchronises)
@@ -699,7 +732,14 @@ int enqueue_frame(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_raw, const 
     // the cull's kind is decided first: a frame whose cull only marks the dead lets k_prep evaluate the tile skip flags for
     // the one-pass surfel kernel
     const bool fusing = s->ref_set && s->tick != 0 && !s->pending_cull;
-    const bool compact_now = fusing ? s->slots.decide_compact() : true;
+    using Due = sm_slots::SlotSchedule::Due;
+    const Due due = fusing ? s->slots.decide_due() : Due::forced;
+    const bool compact_now = due != Due::none;
+    // Tail squeeze: a compaction only the period asked for, on an asynchronous plain stream, keeps the frame's regular form --
+    // the slots that are dead ALREADY are squeezed out between the preparation launch and the pass; this frame's own victims
+    // wait for the next one like every other frame's.  (A forced compaction must leave no dead slot and append densely: the
+    // compacting frame.)
+    const bool squeeze = fusing && due == Due::period && s->sw.tail_squeeze && s->defer_ok;
     // a held-back association rides on this frame's k_prep launch if this is again a fusing frame; anything else (the frame
     // after reset, ...) needs its results first
     // (a compacting frame too: its k_prep launch has no tile flags to make; the doubled words of DevState a merged publisher
@@ -708,18 +748,25 @@ int enqueue_frame(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_raw, const 
     int rc = SM_OK;
     uint32_t n_prep = 0;
     if (!carry && (rc = complete_held(s, false))) return rc;
-    rc = begin_frame(s, d_rgb, d_raw, d_sem, pose, fusing && !compact_now, carry, &fp, &n_prep);
+    rc = begin_frame(s, d_rgb, d_raw, d_sem, pose, fusing && (!compact_now || squeeze), carry, &fp, &n_prep);
     if (rc <= 0) return rc;
-    fp.compact_now = compact_now ? 1u : 0u;
-    s->slots.cull_noted(fp.compact_now != 0u);
+    fp.compact_now = compact_now && !squeeze ? 1u : 0u;
+    if (squeeze) {
+        // the preparation launch carried the previous frame's fixup and association; its statistics (the dead-slot total the
+        // squeeze starts from) are completed now, not by this frame's publisher
+        if ((rc = complete_held(s, true))) return rc;
+        if ((rc = launch_squeeze(s, true, true, true))) return rc;
+        s->slots.squeezed_in_frame();
+    } else
+        s->slots.cull_noted(fp.compact_now != 0u);
     s->slots.keys_drawn(fp.compact_now == 0u);      // this frame's splat writes slot numbers iff nothing moves
     // a cull that only marks the dead is ONE pass over the surfels (k_surfel_pass + k_pass_fixup: conflict test, decrement, cull,
     // splat), and the association appends the new surfels directly (no append kernel)
     const bool one_pass = !fp.compact_now;
     Timeline::Flags &fl = s->tl.frame();
-    fl.compacted = !one_pass; fl.one_pass = fl.direct = one_pass;
+    fl.compacted = !one_pass || squeeze; fl.one_pass = fl.direct = one_pass; fl.squeezed = squeeze;
     if (one_pass) {
-        if ((rc = launch_surfel_pass(s, fp, true, true, n_prep))) return rc;        // :178-197
+        if ((rc = launch_surfel_pass(s, fp, true, true, n_prep, squeeze))) return rc;        // :178-197
         if ((rc = launch_associate_direct(s, fp, true))) return rc;         // :212-239
         end_frame(s);
         return SM_OK;
@@ -922,27 +969,7 @@ int sm_impl::ensure_compact(sm_ctx *s)
     }
     if (!s->slots.maybe_garbage()) return SM_OK;
     if (s->pending_cull) { g_err = "internal: deferred compaction with a pending per-pass cull"; return SM_E_ARG; }
-    FrameParams fp = make_params(s, s->curr_pose);
-    fp.maintenance = 1;
-    fp.compact_now = 1;
-    fp.conflict_cap = 0xFFFFFFFFu;
-    const uint64_t tiles = s->slots.tiles() + 1;
-    const size_t words = std::min<size_t>(tiles * TILE_WORDS, s->alive_words);
-    HIPCK(hipMemsetAsync(s->d_cm, 0, words * 8, s->stream));
-    HIPCK(hipMemsetAsync(s->d_dm, 0, words * 8, s->stream));
-    HIPCK(hipMemsetAsync(s->d_zm, 0, words * 8, s->stream));
-    HIPCK(hipMemsetAsync(s->d_tile_cnt, 0, std::min<size_t>(tiles, s->dead_tiles) * 12, s->stream));
-    const int ngroups = std::max<int>(1, (int)((tiles + GROUP - 1) / GROUP));
-    hipLaunchKernelGGL(k_scan_cull, dim3(ngroups), dim3(1024), 0, s->stream, s->d_state, s->d_tile_cnt, s->d_tile_allow,
-                       s->d_tile_keep, s->d_group_tot, s->d_tile_dead);
-    hipLaunchKernelGGL(k_cull_finalize, dim3(1), dim3(1024), 0, s->stream, s->d_state, fp, s->d_cm, s->d_dm, s->d_zm,
-                       s->d_tile_cnt, s->d_tile_allow, s->d_tile_keep, s->d_group_tot, s->d_group_base, s->d_conf_part, 0u,
-                       s->d_alive, s->d_tile_dead, s->d_stat);
-    if (s->slots.keys_are_slots())     // ids of the index map: slot -> position among the live surfels, as the API hands them out
-        hipLaunchKernelGGL(k_remap_keys, dim3((s->P + 255) / 256), dim3(256), 0, s->stream, s->d_state, s->keyT(), s->P, s->d_alive,
-                           s->d_tile_keep, s->d_group_base);
-    HIPCK(hipGetLastError());
-    int rc = launch_compact(s, fp, false, false);
+    int rc = launch_squeeze(s, false, false, false);     // always full and dense: ids are positions among the live surfels
     if (rc) return rc;
     if ((rc = launch_post_fill(s))) return rc;
     s->slots.compacted_outside_frame();
@@ -1529,7 +1556,7 @@ int sm_stage_timings(sm_ctx *s, sm_timings *out)
     double own[6] = {0};          // pass, fixup (one-pass frames) | conflict (others) | associate (direct) | associate, append (others)
     double prep2[2] = {0, 0};     // k_prep alone | k_assoc_prep
     double scan_own = 0;          // k_scan_cull + k_cull_finalize on the frames that ran k_conflict
-    uint32_t nfr = 0, ncls[2] = {0, 0}, n_op = 0, n_dir = 0, n_merged = 0, n_alone = 0;
+    uint32_t nfr = 0, ncls[2] = {0, 0}, n_op = 0, n_dir = 0, n_merged = 0, n_alone = 0, n_sq = 0;
     for (uint64_t f = first; f < tl.frames; ++f) {
         const int slot = (int)(f % EV_RING);
         const Timeline::Flags &fl = tl.flags[slot];
@@ -1547,7 +1574,10 @@ int sm_stage_timings(sm_ctx *s, sm_timings *out)
         for (int k = 0; k < 7; ++k) seg[k] += loc[k];
         cull[fl.compacted ? 1 : 0] += loc[3];
         ncls[fl.compacted ? 1 : 0]++;
-        if (fl.one_pass) { own[0] += loc[1]; own[1] += loc[3]; n_op++; } else { own[2] += loc[1]; scan_own += loc[2]; }
+        // (a squeezed frame: marks 1..2 k_frame_finalize + scan + finalize -- all three go to the scan figure --, 3..4 k_compact, 4..5
+        //  the pass; its fixup and association are held back: it has no fixup segment and stays out of that average)
+        if (fl.squeezed) { own[0] += loc[4]; scan_own += loc[1]; n_op++; n_sq++; }
+        else if (fl.one_pass) { own[0] += loc[1]; own[1] += loc[3]; n_op++; } else { own[2] += loc[1]; scan_own += loc[2]; }
         if (fl.direct) { n_dir++; if (!fl.deferred) { own[3] += loc[4]; n_alone++; } } else { own[4] += loc[4]; own[5] += loc[6]; }
         prep2[fl.merged ? 1 : 0] += loc[0];
         if (fl.merged) n_merged++;
@@ -1571,8 +1601,8 @@ int sm_stage_timings(sm_ctx *s, sm_timings *out)
         out->k_compact_own = ncls[1] ? (float)std::max(0.0, cull[1] / ncls[1] - oh) : 0.0f;
         out->frames_compact = ncls[1];
         auto avg = [&](double sum, uint32_t n) { return n ? (float)std::max(0.0, sum / n - oh) : 0.0f; };
-        out->k_surfel_pass = avg(own[0], n_op); out->k_pass_fixup = avg(own[1], n_op); out->k_conflict_own = avg(own[2], nfr - n_op);
-        out->k_scan_own = avg(scan_own, nfr - n_op);
+        out->k_surfel_pass = avg(own[0], n_op); out->k_pass_fixup = avg(own[1], n_op - n_sq); out->k_conflict_own = avg(own[2], nfr - n_op);
+        out->k_scan_own = avg(scan_own, nfr - n_op + n_sq);
         out->k_associate_direct = avg(own[3], n_alone); out->k_associate_own = avg(own[4], nfr - n_dir); out->k_append_own = avg(own[5], nfr - n_dir);
         out->frames_one_pass = n_op; out->frames_direct = n_dir;
         out->k_assoc_prep = avg(prep2[1], n_merged); out->k_prep_own = avg(prep2[0], nfr - n_merged);
@@ -1614,6 +1644,16 @@ int sm_debug_slow_frames(sm_ctx *s, uint32_t *n)
     int rc = pull_state(s);
     if (rc) return rc;
     *n = s->h_state->slow_frames;
+    return SM_OK;
+}
+
+int sm_debug_squeezes(sm_ctx *s, uint32_t *tail, uint32_t *full)
+{
+    if (!s || !tail || !full) return SM_E_ARG;
+    HIPCK(hipSetDevice(s->cfg.device));
+    int rc = pull_state(s);
+    if (rc) return rc;
+    *tail = s->h_state->sq_tail; *full = s->h_state->sq_full;
     return SM_OK;
 }
 
@@ -1756,7 +1796,7 @@ int sm_shard_frame_device(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_dep
     s->slots.cull_noted(false);
     s->slots.keys_drawn(true);
     Timeline::Flags &fl = s->tl.frame();
-    fl.compacted = false; fl.one_pass = fl.direct = true;
+    fl.compacted = false; fl.one_pass = fl.direct = true; fl.squeezed = false;
     if ((rc = launch_surfel_pass(s, fp, true, true, n_prep))) return rc;
     // The W*H conflict cap acts in surfel order over ALL ranks: exchange the conflict masks and take this rank's surplus back
     // before anything reads the key map (k_shard_cap_pack / k_shard_cap_repair).  Conflicts <= surfels, so a model with no

@@ -239,6 +239,8 @@ struct AutoLoop {
 struct Switches {
     bool defer_assoc = true;           // SM_DEFER_ASSOC=0: every frame launches its own association
     bool two_launch = true;            // SM_TWO_LAUNCH=0: the fixup step keeps its own launch (three launches per frame)
+    bool tail_squeeze = true;          // SM_TAIL_SQUEEZE=0: a periodic compaction is the seven-launch compacting frame and squeezes every dead slot
+    uint32_t tail_thresh = 0;          // SM_TAIL_THRESH (debug): dead slots that make a tile the tail squeeze's boundary (unset: TAIL_DEAD_THRESH)
     int pass_split = 0;                // SM_PASS_SPLIT=1|4: k_surfel_pass on whole / quarter tiles whatever the model's size (else: the grid policy picks)
     bool trace = false;                // SM_PASS_TRACE=<file prefix>: per-workgroup time stamps of the last k_surfel_pass and k_assoc_prep launches,
     std::string trace_prefix;          //   dumped by sm_destroy (tools/pass_trace.py)
@@ -320,8 +322,9 @@ struct PassPartials {
 struct Timeline {
     // compacted: the frame's cull was k_compact (not one that only marks the dead); one_pass: it ran the one-pass kernels
     // (k_surfel_pass + fixup); direct: ... and appended directly; merged: its preparation launch was k_assoc_prep (it carried the
-    // previous frame's association, or the chain); deferred: its own association was held back (no kernel between its marks 4 and 5)
-    struct Flags { bool compacted, one_pass, direct, merged, deferred; };
+    // previous frame's association, or the chain); deferred: its own association was held back (no kernel between its marks 4 and 5);
+    // squeezed: a one-pass frame with a squeeze ahead of its pass -- scan + finalize end at mark 2, k_compact at mark 4, the pass at mark 5
+    struct Flags { bool compacted, one_pass, direct, merged, deferred, squeezed; };
     std::unique_ptr<Event[][EV_RING]> ev;   // [N_EV][EV_RING]; whole or absent
     Flags flags[EV_RING] = {};
     uint64_t frames = 0, read = 0;     // frames recorded / read by sm_stage_timings so far

@@ -72,6 +72,9 @@ struct DevState {
                               //    (by the next frame's k_pass_fixup, or by k_frame_finalize before anything else reads them)
     uint32_t pend_tick;       // time stamp of that frame
     uint32_t holes_last;      // slots of the last frame's appended range that stayed empty (candidate pixels that fused instead)
+    // ---- tail squeeze (k_cull_finalize with FrameParams::maintenance == 2; DESIGN.md 4 "Tail squeeze") ----
+    uint32_t sq_static;       // 1 + the slots the squeeze of the frame at hand left in place (that frame's log entry: n_static); 0: no squeeze moved anything
+    uint32_t sq_tail, sq_full; // diagnostic: squeezes that kept a boundary > 0 with dead slots below it / that ran the full form (sm_debug_squeezes)
 };
 
 struct FrameLog { uint32_t tick, n_before, n_after_cull, n_kill, conflict_count, visible_count, fused_count, unstable_count, n_static, n_conf_skipped, n_splat_skipped, n_slots; };
@@ -103,7 +106,10 @@ struct FrameParams {
     // ---- deferred compaction ----
     uint32_t compact_now;     // 1: this cull moves the survivors (k_scan_cull + k_compact); 0: it only marks the dead (k_cull_lazy).
                               // Decided by the host (a fixed period + a capacity bound), so that it can launch the matching kernels
-    int maintenance;          // 1: compaction outside a frame (no kills): frame statistics are left alone
+    int maintenance;          // 1: compaction outside a frame (no kills): frame statistics are left alone; 2: the same between the two launches
+                              // of a frame (tail squeeze): k_compact restores the alive words and resets the tile skip flags of what it rewrites
+    int no_masks;             // 1: nothing is killed and cm / dm / zm / tile_cnt / tile_allow hold nothing: the cull kernels do not read them
+    uint32_t tail_thresh;     // > 0: tail rule -- the squeeze starts at the first tile with at least this many dead slots (0: at the first dead slot)
     int compact_tickets;      // 1: k_compact hands its moving tiles out in order from a ticket counter (no co-residency needed)
     int no_exempt;            // 1: no surfel is exempt from the conflict test (a rig slice that does not hold the global surfel 0)
     int shard_slots;          // 1: slot-addressed sharding of one stream: ids are global slot numbers on every rank

@@ -162,38 +162,52 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SM_CONFLICT
 // ---------------------------------------------------------------------------------------------
 constexpr int GROUP = 1024;   // tiles per scan group
 
+// Tail squeeze: a periodic squeeze of a plain asynchronous stream starts at the first tile that holds at least
+// this many dead slots instead of at the first dead slot -- 99.44 % of all deaths hit surfels at most 8 frames old
+// (tools/kill_age_study.py), so the dense holes lie in the newest tiles and the few old deaths below them are left as garbage.
+// SM_TAIL_THRESH overrides it per context (tests).
+constexpr uint32_t TAIL_DEAD_THRESH = TILE / 16;
+// ... unless more than 1 / TAIL_GARBAGE_DIV of the occupied slots would stay dead below that tile: then the squeeze is a full one
+constexpr uint32_t TAIL_GARBAGE_DIV = 32;
+
 __global__ __launch_bounds__(1024) void k_scan_cull(const DevState *__restrict__ st,
                                                     const uint32_t *__restrict__ tile_cnt,
                                                     uint32_t *__restrict__ tile_allow,
                                                     uint32_t *__restrict__ tile_keep_prefix,
-                                                    uint32_t *__restrict__ group_tot /* [g][4]: conf, keep, first killing tile, - */,
-                                                    const uint32_t *__restrict__ tile_dead)
+                                                    uint32_t *__restrict__ group_tot /* [g][4]: conf, keep, first killing tile, first dense tile */,
+                                                    const uint32_t *__restrict__ tile_dead,
+                                                    uint32_t no_masks /* nothing is killed: tile_cnt is not read */,
+                                                    uint32_t tail_thresh /* > 0: also report the first tile with that many dead slots */)
 {
     __shared__ uint32_t s_scan[17];
-    __shared__ uint32_t s_first;
+    __shared__ uint32_t s_first, s_dense;
     const uint32_t N = st->count;
     const uint32_t ntiles = (N + TILE - 1) / TILE;
     const uint32_t t = blockIdx.x * GROUP + threadIdx.x;
-    if (threadIdx.x == 0) s_first = 0xFFFFFFFFu;
+    if (threadIdx.x == 0) { s_first = 0xFFFFFFFFu; s_dense = 0xFFFFFFFFu; }
     uint32_t nconf = 0, keep = 0;
-    bool kills = false;
+    bool kills = false, dense = false;
     if (t < ntiles) {
-        nconf = tile_cnt[t * 3];
-        const uint32_t nkill = tile_cnt[t * 3 + 1];
-        keep = min((uint32_t)TILE, N - t * TILE) - tile_dead[t] - nkill;
-        kills = nkill != 0 || tile_dead[t] != 0;
-        tile_allow[t] = nconf;                  // every conflict takes effect unless the cap binds
+        uint32_t nkill = 0;
+        if (!no_masks) { nconf = tile_cnt[t * 3]; nkill = tile_cnt[t * 3 + 1]; }
+        const uint32_t dead = tile_dead[t];
+        keep = min((uint32_t)TILE, N - t * TILE) - dead - nkill;
+        kills = nkill != 0 || dead != 0;
+        dense = tail_thresh != 0u && dead >= tail_thresh;
+        if (!no_masks) tile_allow[t] = nconf;   // every conflict takes effect unless the cap binds
     }
     uint32_t ctot, ktot;
     block_scan_1024(nconf, &ctot, s_scan);
     const uint32_t kpre = block_scan_1024(keep, &ktot, s_scan);
     if (kills) atomicMin(&s_first, t);
+    if (dense) atomicMin(&s_dense, t);
     if (t < ntiles) tile_keep_prefix[t] = kpre;
     __syncthreads();
     if (threadIdx.x == 0) {
         group_tot[blockIdx.x * 4 + 0] = ctot;
         group_tot[blockIdx.x * 4 + 1] = ktot;
         group_tot[blockIdx.x * 4 + 2] = s_first;
+        group_tot[blockIdx.x * 4 + 3] = s_dense;
     }
 }
 
@@ -231,7 +245,7 @@ __global__ __launch_bounds__(1024) void k_cull_finalize(DevState *__restrict__ s
                                                         unsigned long long *__restrict__ host_stat)
 {
     __shared__ uint32_t s_scan[17];
-    __shared__ uint32_t s_first, s_ft, s_fl, s_keep_first;
+    __shared__ uint32_t s_first, s_ft, s_fl, s_keep_first, s_dense, s_left;
     const uint32_t N = st->count;                     // occupied slots
     const uint32_t g0 = st->garbage;                  // dead ones among them
     const uint32_t old_first = st->first_live, old_offset = st->offset;
@@ -242,11 +256,11 @@ __global__ __launch_bounds__(1024) void k_cull_finalize(DevState *__restrict__ s
     // k_scan_cull ran before this kernel exactly when this cull compacts (the host decides and launches accordingly);
     // a cull that only marks the dead needs no prefixes, its totals come from k_conflict's per-workgroup sums
     const bool have_scan = fp.compact_now != 0u || fp.maintenance != 0;
-    if (threadIdx.x == 0) { s_first = 0xFFFFFFFFu; s_ft = 0xFFFFFFFFu; s_fl = 0xFFFFFFFFu; }
+    if (threadIdx.x == 0) { s_first = 0xFFFFFFFFu; s_ft = 0xFFFFFFFFu; s_fl = 0xFFFFFFFFu; s_dense = 0xFFFFFFFFu; s_left = 0u; }
     if (threadIdx.x == 1023) {
         // does the surfel that is id 0 today survive this cull?  (almost always: then its slot stays "id 0")
-        uint32_t survive = 0;
-        if (old_first < N) {
+        uint32_t survive = fp.no_masks ? 1u : 0u;     // (nothing is killed)
+        if (old_first < N && !fp.no_masks) {
             const uint32_t w = old_first / 64u, bit = old_first % 64u;
             survive = (((zm[w] | (cm[w] & dm[w])) >> bit) & 1ull) ? 0u : 1u;     // all conflicts counted: conservative under the cap
         }
@@ -263,6 +277,8 @@ __global__ __launch_bounds__(1024) void k_cull_finalize(DevState *__restrict__ s
     block_scan_1024(ckill, &ckill_tot, s_scan);
     uint32_t ctotal = cconf_tot, ktotal = (N - g0) - ckill_tot, gkpre = 0;
     uint32_t nstatic = N;
+    // the first tile the compaction may touch, and the dead slots it leaves below that tile (tail rule only)
+    uint32_t bnd = ntiles, left = 0;
     if (have_scan) {
         // scan the group totals of k_scan_cull (ngroups <= 1024 covers 1 G surfels)
         uint32_t gc = 0, gk = 0;
@@ -270,14 +286,30 @@ __global__ __launch_bounds__(1024) void k_cull_finalize(DevState *__restrict__ s
             gc = group_tot[threadIdx.x * 4 + 0];
             gk = group_tot[threadIdx.x * 4 + 1];
             atomicMin(&s_first, group_tot[threadIdx.x * 4 + 2]);
+            if (fp.tail_thresh) atomicMin(&s_dense, group_tot[threadIdx.x * 4 + 3]);
         }
         block_scan_1024(gc, &ctotal, s_scan);
         gkpre = block_scan_1024(gk, &ktotal, s_scan);
         nstatic = (s_first == 0xFFFFFFFFu) ? N : min(N, s_first * (uint32_t)TILE);
+        bnd = (s_first == 0xFFFFFFFFu) ? ntiles : min(s_first, ntiles);
+        if (fp.tail_thresh) {                         // workgroup-uniform
+            // Tail rule: the first DENSE tile `bt` instead of the first dead slot.  Live surfels below it = the prefix k_scan_cull
+            // computed for it (group base + tile prefix); the rest of the slots below it are dead and stay.
+            const uint32_t bt = min(s_dense, ntiles);
+            if (bt < ntiles) { if (threadIdx.x == bt / (uint32_t)GROUP) s_left = bt * (uint32_t)TILE - (gkpre + tile_keep_prefix[bt]); }
+            else if (threadIdx.x == 0) s_left = N - ktotal;
+            __syncthreads();
+            left = s_left;
+            // sparse deaths everywhere (or nothing dead below the dense tile): the full form, from the first dead slot
+            if (left == 0u || left > N / TAIL_GARBAGE_DIV) left = 0u;
+            else { bnd = bt; nstatic = min(N, bt * (uint32_t)TILE); }
+        }
     }
+    const bool tail = left != 0u;
     const bool cap_binds = ctotal > cap;
     if (!cap_binds) {
-        if (have_scan && threadIdx.x < ngroups) group_keep_base[threadIdx.x] = gkpre;
+        // (tail rule: the tiles from `bnd` on land behind ALL the slots below it, dead ones included)
+        if (have_scan && threadIdx.x < ngroups) group_keep_base[threadIdx.x] = gkpre + ((tail && threadIdx.x >= bnd / (uint32_t)GROUP) ? left : 0u);
     } else {
         // ---- slow path: the cap binds; exact sequential-order scan with absolute prefixes
         if (threadIdx.x < ngroups) group_keep_base[threadIdx.x] = 0;
@@ -331,7 +363,9 @@ __global__ __launch_bounds__(1024) void k_cull_finalize(DevState *__restrict__ s
     const uint32_t g1 = N - kept;                     // dead slots if nothing moves
     const bool compact = have_scan;
     // slot of the first survivor (the surfel the reference addresses as id 0)
-    uint32_t first_live = compact ? 0u : N;
+    // (tail rule: it keeps its slot, which lies below the boundary -- a tile below the first dense one holds fewer than tail_thresh
+    //  <= TILE dead slots, i.e. a live one; with a threshold above TILE no tile is dense, the boundary is the end and nothing moves)
+    uint32_t first_live = compact ? (tail ? old_first : 0u) : N;
     if (!compact && kept != 0u) {
         __syncthreads();                              // s_keep_first; tile_keep_prefix of the slow path
         if (s_keep_first) {
@@ -374,16 +408,24 @@ __global__ __launch_bounds__(1024) void k_cull_finalize(DevState *__restrict__ s
         st->garbage_prev = g0;
         st->cap_binds = cap_binds ? 1u : 0u;
         st->do_compact = compact ? 1u : 0u;
-        st->first_moving = (compact && s_first != 0xFFFFFFFFu) ? min(s_first, ntiles) : ntiles;
+        st->first_moving = compact ? bnd : ntiles;
+        if (fp.maintenance == 2) {                        // the squeeze of a frame: what its log entry and the diagnostics say
+            st->sq_static = bnd < ntiles ? nstatic + 1u : 0u;
+            if (tail) st->sq_tail = st->sq_tail + 1u; else st->sq_full = st->sq_full + 1u;
+        }
         st->compact_ticket = 0u;
         st->first_live = first_live;
         st->fl_dirty2[0] = 0u; st->fl_dirty2[1] = 0u;    // (a two-launch frame's publisher, merged into this frame's preparation launch, left them to the next pass -- there is none here)
         st->slow_done[0] = 0u; st->slow_done[1] = 0u;
         st->holes_last = 0u;
         if (compact) {
-            st->count = kept;                             // src/GlobalModel.cpp:575
-            st->offset = fp.maintenance ? old_offset - (g0 - holes) : kept;
-            st->garbage = 0;
+            st->count = kept + left;                      // src/GlobalModel.cpp:575 (left: 0 unless the tail rule leaves dead slots behind)
+            // (tail rule: `+ left` takes every slot left behind to lie below old_offset.  A boundary inside the last appended range
+            //  would count some of `holes` twice and put `offset` too high: harmless between a frame's two launches, the only place
+            //  the tail rule runs -- the pass's launch sets offset = count before anything reads it (k_surfel_pass, first candidate
+            //  workgroup) -- and ensure_compact never uses the tail rule)
+            st->offset = fp.maintenance ? old_offset - (g0 - holes) + left : kept;
+            st->garbage = left;
         } else {
             st->count = N;                                // the dead keep their slots until the next compaction
             st->offset = N;
@@ -392,7 +434,7 @@ __global__ __launch_bounds__(1024) void k_cull_finalize(DevState *__restrict__ s
         // host-visible (pinned) statistic: occupied slots, tagged with the number of completed appends, so that the host
         // can bound the slot count of a frame it enqueues without waiting for the device
         if (host_stat)
-            __hip_atomic_store(host_stat, ((unsigned long long)st->stat_frames << 32) | (unsigned long long)(compact ? kept : N),
+            __hip_atomic_store(host_stat, ((unsigned long long)st->stat_frames << 32) | (unsigned long long)(compact ? kept + left : N),
                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
@@ -406,8 +448,10 @@ __device__ __forceinline__ void post_compact_fill(const DevState *__restrict__ s
     if (st->do_compact == 0u || st->garbage_prev == 0u) return;
     const uint32_t n = st->cull_n;
     const uint32_t nwords = (n + 63u) / 64u, ntiles = (n + TILE - 1) / TILE;
-    for (uint32_t w = tid; w < nwords; w += nthreads) alive[w] = ~0ull;
-    for (uint32_t t = tid; t < ntiles; t += nthreads) tile_dead[t] = 0u;
+    // (the tiles below the first one the compaction touched keep what they have: no dead slot at all, or -- tail rule -- theirs)
+    const uint32_t t0 = min(st->first_moving, ntiles);
+    for (uint32_t w = t0 * TILE_WORDS + tid; w < nwords; w += nthreads) alive[w] = ~0ull;
+    for (uint32_t t = t0 + tid; t < ntiles; t += nthreads) tile_dead[t] = 0u;
 }
 
 __global__ void k_post_fill(const DevState *__restrict__ st, uint64_t *__restrict__ alive, uint32_t *__restrict__ tile_dead)
@@ -485,7 +529,7 @@ __global__ __launch_bounds__(256) void k_compact(Model M, DevState *__restrict__
                                                  uint64_t *__restrict__ keyT,
                                                  uint32_t *__restrict__ tile_flag, uint32_t epoch,
                                                  const uint32_t *__restrict__ group_keep_base,
-                                                 uint32_t *__restrict__ tb, const uint8_t *__restrict__ tile_flags,
+                                                 uint32_t *__restrict__ tb, uint8_t *__restrict__ tile_flags,
                                                  uint2 *__restrict__ blk_part /* [grid] (visible, splat-skipped) */,
                                                  uint64_t *__restrict__ alive, uint32_t *__restrict__ tile_dead)
 {
@@ -503,6 +547,13 @@ __global__ __launch_bounds__(256) void k_compact(Model M, DevState *__restrict__
     // (k_cull_lazy) are squeezed out together with this cull's own victims.
     const bool had_dead = st->garbage_prev != 0u;
     const bool cap_binds = st->cap_binds != 0u;
+    // A squeeze (fp.no_masks): nothing is killed, the masks and per-tile counts hold nothing and are not read; the tiles below the
+    // boundary k_cull_finalize chose (first_moving) are not visited at all -- under the tail rule they keep their dead slots.
+    // Between the two launches of a frame (fp.maintenance == 2) every tile that is rewritten also gets its alive words and dead
+    // count back here (its own workgroup is their only reader in this launch) and its skip flags reset to "visit, both tests":
+    // the flags were evaluated before the squeeze, for the surfels that used to live in these slots.
+    const bool nomask = fp.no_masks != 0, in_frame = fp.maintenance == 2;
+    const uint32_t lo = (nomask && !SPLAT) ? min(st->first_moving, ntiles) : 0u;
     // Two ways to share out the tiles.  Round-robin over a grid that is known to be fully resident (the default: a tile
     // only waits for lower tiles, all of which are then running).  Or, when the GPU is shared and residency cannot be
     // counted on (fp.compact_tickets): the tiles below `fm` stay in place (nothing killed or dead in or before them) and
@@ -511,11 +562,11 @@ __global__ __launch_bounds__(256) void k_compact(Model M, DevState *__restrict__
     // anything, so progress never depends on how many workgroups the GPU keeps resident.  (+1 returning atomic per
     // moving tile on its critical path: k_compact 50 -> 66 us at KITTI size, hence not the default.)
     const bool use_tickets = fp.compact_tickets != 0;
-    const uint32_t fm = use_tickets ? min(st->first_moving, ntiles) : ntiles;
+    const uint32_t fm = use_tickets ? max(lo, min(st->first_moving, ntiles)) : ntiles;
     constexpr uint32_t TICKET = 1;                    // one tile per ticket: a tile must be able to publish without first finishing a lower one
     __shared__ uint32_t s_tk;
     bool ticketing = false;
-    uint32_t rr_tile = blockIdx.x, tk_tile = 0, tk_left = 0;
+    uint32_t rr_tile = lo + blockIdx.x, tk_tile = 0, tk_left = 0;
     for (;;) {
         uint32_t tile, allow, nconf, nkill_full, base_id, tdead;
         bool skipbit;
@@ -532,7 +583,7 @@ __global__ __launch_bounds__(256) void k_compact(Model M, DevState *__restrict__
                 const bool in = tl < fm;
                 const uint32_t tt = in ? (uint32_t)tl : 0u;
                 skipmask = __ballot(in && (tile_flags[tt] & 2u));
-                m_nconf = tile_cnt[tt * 3]; m_nkill = tile_cnt[tt * 3 + 1];
+                if (!nomask) { m_nconf = tile_cnt[tt * 3]; m_nkill = tile_cnt[tt * 3 + 1]; }
                 m_allow = cap_binds ? tile_allow[tt] : m_nconf;         // every conflict takes effect unless the cap binds
                 m_base = tile_keep_prefix[tt] + group_keep_base[tt / GROUP];
                 m_dead = had_dead ? tile_dead[tt] : 0u;
@@ -553,7 +604,7 @@ __global__ __launch_bounds__(256) void k_compact(Model M, DevState *__restrict__
             tile = tk_tile;
             if (tile >= ntiles) break;
             ++tk_tile; --tk_left;
-            nconf = tile_cnt[tile * 3]; nkill_full = tile_cnt[tile * 3 + 1];
+            nconf = nomask ? 0u : tile_cnt[tile * 3]; nkill_full = nomask ? 0u : tile_cnt[tile * 3 + 1];
             allow = cap_binds ? tile_allow[tile] : nconf;
             base_id = tile_keep_prefix[tile] + group_keep_base[tile / GROUP];
             tdead = had_dead ? tile_dead[tile] : 0u;
@@ -611,7 +662,7 @@ __global__ __launch_bounds__(256) void k_compact(Model M, DevState *__restrict__
             const uint32_t word = tile * TILE_WORDS + threadIdx.x;
             const uint64_t base = (uint64_t)word * 64u;
             if (base < N) {
-                c = cm[word]; d = dm[word]; z = zm[word];
+                if (!nomask) { c = cm[word]; d = dm[word]; z = zm[word]; }
                 const uint64_t rem = (uint64_t)N - base;
                 valid = rem >= 64 ? ~0ull : ((1ull << rem) - 1ull);
                 if (had_dead) valid &= alive[word];
@@ -672,6 +723,10 @@ __global__ __launch_bounds__(256) void k_compact(Model M, DevState *__restrict__
                 }
             }
             __syncthreads();
+            if (in_frame) {
+                if (threadIdx.x < TILE_WORDS && (uint64_t)(tile * TILE_WORDS + threadIdx.x) * 64u < N) alive[tile * TILE_WORDS + threadIdx.x] = ~0ull;
+                if (threadIdx.x == 0) { tile_dead[tile] = 0u; tile_flags[tile] = 0; }
+            }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 if (kept[r]) {

@@ -722,6 +722,7 @@ __device__ __forceinline__ void fixup_publisher(DevState *__restrict__ st, const
     // ---- every load the publisher needs, issued together (each dependent round trip costs ~1 us on this single workgroup)
     const uint32_t pend = st->pend, cap_prev = st->cap_binds, g_in = st->garbage, old_first = st->first_live;
     const bool dirty = st->fl_dirty2[fp.par] != 0u;
+    const uint32_t sq = st->sq_static;                  // a squeeze ran ahead of this frame's pass (tail squeeze): 1 + the slots it left in place
     PendFields pf;
     pf.cull_n = st->cull_n; pf.garbage_prev = st->garbage_prev; pf.n_kill = st->n_kill; pf.visible = st->visible_count;
     pf.conflict = st->conflict_count; pf.n_static = st->n_static; pf.conf_skipped = st->n_conf_skipped;
@@ -802,7 +803,8 @@ __device__ __forceinline__ void fixup_publisher(DevState *__restrict__ st, const
     if (threadIdx.x == 0) {
         st->n_conf_skipped = cskip_tot;
         st->n_splat_skipped = sskip_tot;
-        st->n_static = N;
+        st->n_static = sq ? min(N, sq - 1u) : N;
+        if (sq) st->sq_static = 0u;
         st->conflict_count = min(ctotal, cap);
         if (fp.splat_follows) st->visible_count = 0;
         st->cull_n = N;

@@ -49,9 +49,14 @@ public:
     bool period_due() const { return period_ <= 1 || culls_ + 1 >= period_; }
     // the host's bound alone (what every rank of a sharded stream knows) cannot rule out that the next frame overflows
     bool bound_may_overflow() const { return (uint64_t)bound_ + max_new_ > cap_; }
-    bool decide_compact() const
+    // Why: `period` -- the period alone asked, and dead slots could not make the frame overflow; `forced` -- the capacity rule
+    // asked (or every cull compacts: period <= 1).  A periodic compaction of a plain asynchronous stream may be a tail squeeze that
+    // leaves dead slots behind; a forced one squeezes everything and appends densely.
+    enum class Due { none, period, forced };
+    bool decide_compact() const { return decide_due() != Due::none; }
+    Due decide_due() const
     {
-        if (period_ <= 1) return true;
+        if (period_ <= 1) return Due::forced;
         // Capacity: a cull that only marks the dead must not be able to make the frame overflow because of them.
         // bound = slots at the last device update + one frame's worth of new surfels for every append enqueued since.
         // When the host has run far ahead of the device the bound is loose; rather than compacting for nothing it then
@@ -64,14 +69,14 @@ public:
             uint64_t bound = bound_;
             if (st.ahead_known) bound = std::min<uint64_t>(bound, (uint64_t)st.slots + (uint64_t)st.ahead * max_new_);
             if (bound + max_new_ <= cap_) break;                           // fits even if every candidate pixel is new
-            if (st.ahead <= 1u) return true;                               // the bound is (nearly) exact: compact
-            if ((uint64_t)st.slots + 2ull * max_new_ > cap_) return true;  // would not fit with the device caught up either
+            if (st.ahead <= 1u) return Due::forced;                        // the bound is (nearly) exact: compact
+            if ((uint64_t)st.slots + 2ull * max_new_ > cap_) return Due::forced;  // would not fit with the device caught up either
             if ((spins & 63u) == 63u &&
                 std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_start).count() > wait_us_)
-                return true;                                               // the device is further behind than we are willing to wait for
+                return Due::forced;                                        // the device is further behind than we are willing to wait for
             std::this_thread::yield();
         }
-        return period_due();
+        return period_due() ? Due::period : Due::none;
     }
 
     // An ESTIMATE of the occupied slots (the surfel pass's grid policy): the statistic plus the measured growth for every append
@@ -99,6 +104,9 @@ public:
         if (compacted) { culls_ = 0; }
         else { culls_++; garbage_ = true; }
     }
+    // a squeeze was enqueued between the two launches of a frame, ahead of its cull (tail squeeze): the period restarts; dead slots
+    // may remain below the squeeze's boundary and that frame's cull marks more, and its splat still draws slot numbers
+    void squeezed_in_frame() { culls_ = 0; garbage_ = true; }
     // an append was enqueued (the device bumps the statistic's frame tag with it): at most max_new more slots
     void append_enqueued()
     {

@@ -306,9 +306,16 @@ def _search_arg(search):
 INT32_MIN, INT32_MAX = -2 ** 31, 2 ** 31 - 1
 
 
-def _track_info_dict(info) -> dict:
-    return dict(status=TRACK_STATUS.get(info.status, str(info.status)), status_code=int(info.status), iterations=int(info.iterations),
-                inliers=int(info.inliers), rmse=float(info.rmse), guess=np.array(info.guess[:], np.float32).reshape(4, 4).T.copy())
+def _track_info_dict(info, rinfo=None, anchor=None) -> dict:
+    """SmTrackInfo as the trackers' info dict; rinfo (SmTrackRgbInfo) and anchor (c_float) add their keys when given"""
+    d = dict(status=TRACK_STATUS.get(info.status, str(info.status)), status_code=int(info.status), iterations=int(info.iterations),
+             inliers=int(info.inliers), rmse=float(info.rmse), guess=np.array(info.guess[:], np.float32).reshape(4, 4).T.copy())
+    if rinfo is not None:
+        d.update(rgb_inliers=int(rinfo.rgb_inliers), rgb_rmse=float(rinfo.rgb_rmse), pivot_ratio=float(rinfo.pivot_ratio),
+                 level_iterations=[int(x) for x in rinfo.level_iterations])
+    if anchor is not None:
+        d["anchor_time"] = float(anchor.value)
+    return d
 
 
 def _loop_info_dict(info) -> dict:
@@ -678,35 +685,65 @@ class SurfelMap:
     def reset(self):
         self._chk(self._L.sm_reset(self._h), "sm_reset")
 
-    # -- tracking (sm_track_frame)
+    # -- tracking (sm_track_frame): what every wrapper of a tracker shares
+    _RGB_KEYS = ("levels", "iters", "rgb_weight", "rgb_max_residual")
+
+    def _images(self, depth, rgb=None):
+        """depth uint16[H][W] (and rgb uint8[H][W][3], if given) contiguous and of the context's size"""
+        depth = np.ascontiguousarray(depth, np.uint16)
+        if rgb is None:
+            assert depth.size == self.P, depth.shape
+            return depth, None
+        rgb = np.ascontiguousarray(rgb, np.uint8)
+        assert depth.size == self.P and rgb.size == self.P * 3, (depth.shape, rgb.shape)
+        return depth, rgb
+
+    def _split_params(self, params, colour):
+        """**params as (SmTrackParams, SmTrackRgbParams), None where no field is named (the C side's defaults).  colour False:
+        every key must be sm_track_params' own."""
+        col = {k: v for k, v in params.items() if colour and k in self._RGB_KEYS}
+        icp = {k: v for k, v in params.items() if k not in col}
+        return track_params(**icp) if icp else None, track_rgb_params(**col) if col else None
+
+    def _track_frame(self, fn, depth, guess, params, rgb=None, window=()):
+        """One tracked frame through sm_track_frame* `fn`, whose arguments are (ctx, [rgb,] depth, guess, params, [rgb params,]
+        [window...,] pose out, info, [rgb info,] [anchor time]): rgb and window (a tuple of times) say which.  Returns
+        (pose 4x4, info dict)."""
+        depth, rgb = self._images(depth, rgb)
+        g = None if guess is None else _mat16(guess)
+        p, q = self._split_params(params, colour=rgb is not None)
+        out = np.zeros(16, np.float32)
+        info = SmTrackInfo()
+        rinfo = None if rgb is None else SmTrackRgbInfo()
+        anchor = C.c_float() if window else None
+        one = (lambda x: []) if rgb is None else (lambda x: [x])          # an argument of the colour forms only
+        args = ([self._h] + one(_ptr(rgb)) + [_ptr(depth), _ptr(g), p] + one(q) + [int(t) for t in window] + [_ptr(out), info] + one(rinfo)
+                + ([anchor] if window else []))
+        self._chk(getattr(self._L, fn)(*args), fn)
+        return out.reshape(4, 4).T.copy(), _track_info_dict(info, rinfo, anchor)
+
+    def _track_debug(self, fn, depth, pose_eval, *mid, rgb=None):
+        """One iteration's system through sm_track*_debug* `fn`(ctx, [rgb,] depth, pose_eval, *mid, pred out, sys29 out).
+        Returns (pred_slot int32[H][W], sys float64[29])."""
+        depth, rgb = self._images(depth, rgb)
+        pe = _mat16(pose_eval)
+        pred = np.zeros((self.H, self.W), np.int32)
+        sys29 = np.zeros(29, np.float64)
+        head = [self._h] if rgb is None else [self._h, _ptr(rgb)]
+        self._chk(getattr(self._L, fn)(*head, _ptr(depth), _ptr(pe), *[int(v) for v in mid], _ptr(pred), _ptr(sys29)), fn)
+        return pred, sys29
+
     def track(self, depth, guess=None, **params):
         """Track one depth image (uint16[H][W] mm) against the model (sm_track_frame); the model is not changed.  guess: a 4x4
         camera->world matrix (numpy row/col indexing) or float32[16] column-major; None = constant velocity.  params override
         sm_default_track_params.  Returns (pose 4x4 float32, numpy row/col indexing; the guess unless status is "OK",
         info dict: status (name), status_code, iterations, inliers, rmse, guess 4x4)."""
-        depth = np.ascontiguousarray(depth, np.uint16)
-        assert depth.size == self.P, depth.shape
-        g = None if guess is None else _mat16(guess)
-        p = track_params(**params) if params else None
-        out = np.zeros(16, np.float32)
-        info = SmTrackInfo()
-        self._chk(self._L.sm_track_frame(self._h, _ptr(depth), _ptr(g), C.byref(p) if p is not None else None, _ptr(out),
-                                         C.byref(info)), "sm_track_frame")
-        d = dict(status=TRACK_STATUS.get(info.status, str(info.status)), status_code=int(info.status),
-                 iterations=int(info.iterations), inliers=int(info.inliers), rmse=float(info.rmse),
-                 guess=np.array(info.guess[:], np.float32).reshape(4, 4).T.copy())
-        return out.reshape(4, 4).T.copy(), d
+        return self._track_frame("sm_track_frame", depth, guess, params)
 
     def track_debug(self, depth, pose_eval):
         """sm_track_debug: (pred_slot int32[H][W], model slot or -1, sys float64[29]) -- the prediction of the next track() and one
         iteration's system at pose_eval (4x4 or float32[16] column-major) with the default parameters"""
-        depth = np.ascontiguousarray(depth, np.uint16)
-        assert depth.size == self.P, depth.shape
-        pe = _mat16(pose_eval)
-        pred = np.zeros((self.H, self.W), np.int32)
-        sys29 = np.zeros(29, np.float64)
-        self._chk(self._L.sm_track_debug(self._h, _ptr(depth), _ptr(pe), _ptr(pred), _ptr(sys29)), "sm_track_debug")
-        return pred, sys29
+        return self._track_debug("sm_track_debug", depth, pose_eval)
 
     def track_stats(self):
         """device times in ms of the last track()/track_debug() call made with SM_TRACK_TIMING=1 (sm_debug_track_stats, not part
@@ -725,38 +762,16 @@ class SurfelMap:
         return pose, info
 
     # -- tracking with the colour term (sm_track_frame_rgb)
-    _RGB_KEYS = ("levels", "iters", "rgb_weight", "rgb_max_residual")
-
     def track_rgb(self, rgb, depth, guess=None, **params):
         """track() with the photometric term, coarse to fine (sm_track_frame_rgb): rgb uint8[H][W][3] as process_frame takes it.
         params override sm_default_track_params and sm_default_track_rgb_params (levels, iters, rgb_weight, rgb_max_residual).
         Returns (pose, info) as track(), info with rgb_inliers, rgb_rmse, pivot_ratio and level_iterations (list of 6) added."""
-        rgb = np.ascontiguousarray(rgb, np.uint8)
-        depth = np.ascontiguousarray(depth, np.uint16)
-        assert depth.size == self.P and rgb.size == self.P * 3, (depth.shape, rgb.shape)
-        g = None if guess is None else _mat16(guess)
-        icp = {k: v for k, v in params.items() if k not in self._RGB_KEYS}
-        col = {k: v for k, v in params.items() if k in self._RGB_KEYS}
-        p = track_params(**icp) if icp else None
-        q = track_rgb_params(**col) if col else None
-        out = np.zeros(16, np.float32)
-        info, rinfo = SmTrackInfo(), SmTrackRgbInfo()
-        self._chk(self._L.sm_track_frame_rgb(self._h, _ptr(rgb), _ptr(depth), _ptr(g), C.byref(p) if p is not None else None,
-                                             C.byref(q) if q is not None else None, _ptr(out), C.byref(info), C.byref(rinfo)),
-                  "sm_track_frame_rgb")
-        d = dict(status=TRACK_STATUS.get(info.status, str(info.status)), status_code=int(info.status),
-                 iterations=int(info.iterations), inliers=int(info.inliers), rmse=float(info.rmse),
-                 guess=np.array(info.guess[:], np.float32).reshape(4, 4).T.copy(),
-                 rgb_inliers=int(rinfo.rgb_inliers), rgb_rmse=float(rinfo.rgb_rmse), pivot_ratio=float(rinfo.pivot_ratio),
-                 level_iterations=[int(x) for x in rinfo.level_iterations])
-        return out.reshape(4, 4).T.copy(), d
+        return self._track_frame("sm_track_frame_rgb", depth, guess, params, rgb=np.asarray(rgb))
 
     def track_rgb_debug(self, rgb, depth, pose_eval, level=0, which=0):
         """sm_track_rgb_debug: the system float64[29] of one iteration at pose_eval and `level` with the default parameters;
         which 0 = joint, 1 = the geometric term, 2 = the photometric term (unweighted)"""
-        rgb = np.ascontiguousarray(rgb, np.uint8)
-        depth = np.ascontiguousarray(depth, np.uint16)
-        assert depth.size == self.P and rgb.size == self.P * 3, (depth.shape, rgb.shape)
+        depth, rgb = self._images(depth, np.asarray(rgb))
         pe = _mat16(pose_eval)
         sys29 = np.zeros(29, np.float64)
         self._chk(self._L.sm_track_rgb_debug(self._h, _ptr(rgb), _ptr(depth), _ptr(pe), int(level), int(which), _ptr(sys29)),
@@ -903,27 +918,31 @@ class SurfelMap:
         """track() against the map as it was: the prediction holds only surfels last updated at or before max_time
         (sm_track_frame_old).  Returns (pose, info) as track(), with info["anchor_time"] = the newest time the prediction holds
         (-1: none)."""
-        depth = np.ascontiguousarray(depth, np.uint16)
-        assert depth.size == self.P, depth.shape
-        g = None if guess is None else _mat16(guess)
-        p = track_params(**params) if params else None
-        out = np.zeros(16, np.float32)
-        info, anchor = SmTrackInfo(), C.c_float()
-        self._chk(self._L.sm_track_frame_old(self._h, _ptr(depth), _ptr(g), C.byref(p) if p is not None else None, int(max_time), _ptr(out),
-                                             C.byref(info), C.byref(anchor)), "sm_track_frame_old")
-        d = _track_info_dict(info)
-        d["anchor_time"] = float(anchor.value)
-        return out.reshape(4, 4).T.copy(), d
+        return self._track_frame("sm_track_frame_old", depth, guess, params, window=(max_time,))
 
     def track_debug_old(self, depth, pose_eval, max_time):
         """track_debug() with track_old()'s window (sm_track_debug_old)"""
-        depth = np.ascontiguousarray(depth, np.uint16)
-        assert depth.size == self.P, depth.shape
-        pe = _mat16(pose_eval)
-        pred = np.zeros((self.H, self.W), np.int32)
-        sys29 = np.zeros(29, np.float64)
-        self._chk(self._L.sm_track_debug_old(self._h, _ptr(depth), _ptr(pe), int(max_time), _ptr(pred), _ptr(sys29)), "sm_track_debug_old")
-        return pred, sys29
+        return self._track_debug("sm_track_debug_old", depth, pose_eval, max_time)
+
+    def _close_loop(self, rgb, depth, pose, paths, search, params):
+        """close_loop() (rgb None) and close_loop_rgb(): sm_close_loop_search with `search`, else sm_close_loop / sm_close_loop_rgb"""
+        depth, rgb = self._images(depth, rgb)
+        loop_keys = {n for n, _ in SmLoopParams._fields_}
+        lp = loop_params(self.cfg, **{k: v for k, v in params.items() if k in loop_keys})
+        tp, rp = self._split_params({k: v for k, v in params.items() if k not in loop_keys}, colour=rgb is not None)
+        src = map_source(paths, include_model=True)
+        g = _mat16(pose)
+        out = np.zeros(16, np.float32)
+        info = SmLoopInfo()
+        sp = _search_arg(search)
+        if sp is not None:
+            self._chk(self._L.sm_close_loop_search(self._h, _ptr(rgb), _ptr(depth), _ptr(g), src, tp, rp, lp, sp, _ptr(out), info),
+                      "sm_close_loop_search")
+        elif rgb is not None:
+            self._chk(self._L.sm_close_loop_rgb(self._h, _ptr(rgb), _ptr(depth), _ptr(g), src, tp, rp, lp, _ptr(out), info), "sm_close_loop_rgb")
+        else:
+            self._chk(self._L.sm_close_loop(self._h, _ptr(depth), _ptr(g), src, tp, lp, _ptr(out), info), "sm_close_loop")
+        return out.reshape(4, 4).T.copy(), _loop_info_dict(info)
 
     def close_loop(self, depth, pose, paths=(), search=None, **params):
         """Notice that the camera is back in mapped territory and pull the map straight (sm_close_loop).  pose: where the caller
@@ -933,24 +952,7 @@ class SurfelMap:
         track from it (sm_close_loop_search), which reaches metres of drift.
         Returns (pose 4x4: corrected if status is "CLOSED", else as given; info dict: status (name), status_code, track (as
         track()'s info), D 4x4, t_a, t_b)."""
-        depth = np.ascontiguousarray(depth, np.uint16)
-        assert depth.size == self.P, depth.shape
-        loop_keys = {n for n, _ in SmLoopParams._fields_}
-        lp = loop_params(self.cfg, **{k: v for k, v in params.items() if k in loop_keys})
-        tk = {k: v for k, v in params.items() if k not in loop_keys}
-        tp = track_params(**tk) if tk else None
-        src = map_source(paths, include_model=True)
-        g = _mat16(pose)
-        out = np.zeros(16, np.float32)
-        info = SmLoopInfo()
-        sp = _search_arg(search)
-        if sp is not None:
-            self._chk(self._L.sm_close_loop_search(self._h, None, _ptr(depth), _ptr(g), C.byref(src), C.byref(tp) if tp is not None else None,
-                                                   None, C.byref(lp), C.byref(sp), _ptr(out), C.byref(info)), "sm_close_loop_search")
-            return out.reshape(4, 4).T.copy(), _loop_info_dict(info)
-        self._chk(self._L.sm_close_loop(self._h, _ptr(depth), _ptr(g), C.byref(src), C.byref(tp) if tp is not None else None, C.byref(lp),
-                                        _ptr(out), C.byref(info)), "sm_close_loop")
-        return out.reshape(4, 4).T.copy(), _loop_info_dict(info)
+        return self._close_loop(None, depth, pose, paths, search, params)
 
     # -- closing loops unasked (sm_set_auto_loop)
     def old_in_view(self, pose, max_time) -> int:
@@ -972,88 +974,25 @@ class SurfelMap:
     def track_window(self, depth, min_time, max_time, guess=None, **params):
         """track() with the prediction held to surfels with min_time < time <= max_time; INT32_MIN / INT32_MAX leave an end open
         (sm_track_frame_window).  Returns (pose, info) as track_old()."""
-        depth = np.ascontiguousarray(depth, np.uint16)
-        assert depth.size == self.P, depth.shape
-        g = None if guess is None else _mat16(guess)
-        p = track_params(**params) if params else None
-        out = np.zeros(16, np.float32)
-        info, anchor = SmTrackInfo(), C.c_float()
-        self._chk(self._L.sm_track_frame_window(self._h, _ptr(depth), _ptr(g), C.byref(p) if p is not None else None, int(min_time),
-                                                int(max_time), _ptr(out), C.byref(info), C.byref(anchor)), "sm_track_frame_window")
-        d = _track_info_dict(info)
-        d["anchor_time"] = float(anchor.value)
-        return out.reshape(4, 4).T.copy(), d
+        return self._track_frame("sm_track_frame_window", depth, guess, params, window=(min_time, max_time))
 
     def track_debug_window(self, depth, pose_eval, min_time, max_time):
         """track_debug() with track_window()'s window (sm_track_debug_window)"""
-        depth = np.ascontiguousarray(depth, np.uint16)
-        assert depth.size == self.P, depth.shape
-        pe = _mat16(pose_eval)
-        pred = np.zeros((self.H, self.W), np.int32)
-        sys29 = np.zeros(29, np.float64)
-        self._chk(self._L.sm_track_debug_window(self._h, _ptr(depth), _ptr(pe), int(min_time), int(max_time), _ptr(pred), _ptr(sys29)),
-                  "sm_track_debug_window")
-        return pred, sys29
+        return self._track_debug("sm_track_debug_window", depth, pose_eval, min_time, max_time)
 
     def track_rgb_window(self, rgb, depth, min_time, max_time, guess=None, **params):
         """track_rgb() with track_window()'s window (sm_track_frame_rgb_window); info with anchor_time added"""
-        rgb = np.ascontiguousarray(rgb, np.uint8)
-        depth = np.ascontiguousarray(depth, np.uint16)
-        assert depth.size == self.P and rgb.size == self.P * 3, (depth.shape, rgb.shape)
-        g = None if guess is None else _mat16(guess)
-        icp = {k: v for k, v in params.items() if k not in self._RGB_KEYS}
-        col = {k: v for k, v in params.items() if k in self._RGB_KEYS}
-        p = track_params(**icp) if icp else None
-        q = track_rgb_params(**col) if col else None
-        out = np.zeros(16, np.float32)
-        info, rinfo, anchor = SmTrackInfo(), SmTrackRgbInfo(), C.c_float()
-        self._chk(self._L.sm_track_frame_rgb_window(self._h, _ptr(rgb), _ptr(depth), _ptr(g), C.byref(p) if p is not None else None,
-                                                    C.byref(q) if q is not None else None, int(min_time), int(max_time), _ptr(out),
-                                                    C.byref(info), C.byref(rinfo), C.byref(anchor)), "sm_track_frame_rgb_window")
-        d = _track_info_dict(info)
-        d.update(rgb_inliers=int(rinfo.rgb_inliers), rgb_rmse=float(rinfo.rgb_rmse), pivot_ratio=float(rinfo.pivot_ratio),
-                 level_iterations=[int(x) for x in rinfo.level_iterations], anchor_time=float(anchor.value))
-        return out.reshape(4, 4).T.copy(), d
+        return self._track_frame("sm_track_frame_rgb_window", depth, guess, params, rgb=np.asarray(rgb), window=(min_time, max_time))
 
     def track_rgb_debug_window(self, rgb, depth, pose_eval, min_time, max_time, level=0, which=0):
         """track_rgb_debug() with track_window()'s window (sm_track_rgb_debug_window): (pred_slot int32[H][W], sys float64[29])"""
-        rgb = np.ascontiguousarray(rgb, np.uint8)
-        depth = np.ascontiguousarray(depth, np.uint16)
-        assert depth.size == self.P and rgb.size == self.P * 3, (depth.shape, rgb.shape)
-        pe = _mat16(pose_eval)
-        pred = np.zeros((self.H, self.W), np.int32)
-        sys29 = np.zeros(29, np.float64)
-        self._chk(self._L.sm_track_rgb_debug_window(self._h, _ptr(rgb), _ptr(depth), _ptr(pe), int(level), int(which), int(min_time),
-                                                    int(max_time), _ptr(pred), _ptr(sys29)), "sm_track_rgb_debug_window")
-        return pred, sys29
+        return self._track_debug("sm_track_rgb_debug_window", depth, pose_eval, level, which, min_time, max_time, rgb=np.asarray(rgb))
 
     def close_loop_rgb(self, rgb, depth, pose, paths=(), search=None, **params):
         """close_loop() with the loop measured by the colour tracker as well (sm_close_loop_rgb): params may also name the fields of
         sm_track_rgb_params.  search as close_loop()'s: the search scores with the colour gate.  Returns (pose, info) as
         close_loop()."""
-        rgb = np.ascontiguousarray(rgb, np.uint8)
-        depth = np.ascontiguousarray(depth, np.uint16)
-        assert depth.size == self.P and rgb.size == self.P * 3, (depth.shape, rgb.shape)
-        loop_keys = {n for n, _ in SmLoopParams._fields_}
-        lp = loop_params(self.cfg, **{k: v for k, v in params.items() if k in loop_keys})
-        icp = {k: v for k, v in params.items() if k not in loop_keys and k not in self._RGB_KEYS}
-        col = {k: v for k, v in params.items() if k in self._RGB_KEYS}
-        tp = track_params(**icp) if icp else None
-        rp = track_rgb_params(**col) if col else None
-        src = map_source(paths, include_model=True)
-        g = _mat16(pose)
-        out = np.zeros(16, np.float32)
-        info = SmLoopInfo()
-        sp = _search_arg(search)
-        if sp is not None:
-            self._chk(self._L.sm_close_loop_search(self._h, _ptr(rgb), _ptr(depth), _ptr(g), C.byref(src),
-                                                   C.byref(tp) if tp is not None else None, C.byref(rp) if rp is not None else None,
-                                                   C.byref(lp), C.byref(sp), _ptr(out), C.byref(info)), "sm_close_loop_search")
-            return out.reshape(4, 4).T.copy(), _loop_info_dict(info)
-        self._chk(self._L.sm_close_loop_rgb(self._h, _ptr(rgb), _ptr(depth), _ptr(g), C.byref(src), C.byref(tp) if tp is not None else None,
-                                            C.byref(rp) if rp is not None else None, C.byref(lp), _ptr(out), C.byref(info)),
-                  "sm_close_loop_rgb")
-        return out.reshape(4, 4).T.copy(), _loop_info_dict(info)
+        return self._close_loop(np.asarray(rgb), depth, pose, paths, search, params)
 
     def set_auto_loop(self, paths=(), search=None, **params):
         """Make track() / track_rgb() (and process_frame_tracked*) close loops by themselves (sm_set_auto_loop): they track in the

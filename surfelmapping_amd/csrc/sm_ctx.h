@@ -15,7 +15,8 @@
 //   sm_search.hip    pose search before the tracker (sm_score_poses_window, sm_search_pose)
 // and, beside it, for everything that touches a map file: sm_mapfile.h (the format: checked open, writer, chunk plan; host only)
 // and sm_map_stream.h (the double-buffered chunk stream of sm_render_maps.hip and sm_recall.hip); for the occupied slots and the
-// compaction schedule: sm_slots.h (SlotSchedule; host only).  What alternates between consecutive frames is FrameSet, below.
+// compaction schedule: sm_slots.h (SlotSchedule; host only); for the arithmetic of rigid poses in double: sm_pose.h (host only,
+// included by sm_track.hip and sm_warp.hip).  What alternates between consecutive frames is FrameSet, below.
 #pragma once
 
 #include "../../include/sm_c_api.h"
@@ -525,6 +526,13 @@ int recall_ensure_scratch(sm_ctx *s);             // what recall_box_of needs (s
 int check_recall_policy(float radius, const sm_retire_params &rp, const char *who);
 
 // ---- sm_track.hip ----
+// the time window of a prediction: surfels with lo < m[7] <= hi; INT32_MIN / INT32_MAX leave that end open
+struct TrackWindow { int32_t lo, hi; };
+// One tracked frame, whichever public form it came through (fn names it in the error texts): rgb null = sm_track_frame's depth
+// schedule, otherwise sm_track_frame_rgb's; win null = the whole model.  It never consults the policy of sm_set_auto_loop.
+int track_windowed(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params,
+                   const sm_track_rgb_params *rgb_params, const TrackWindow *win, float *pose16_out, sm_track_info *info,
+                   sm_track_rgb_info *rgb_info, float *anchor_time, const char *fn);
 // What sm_search.hip takes from a tracked frame's preparation.  The prediction's camera and image, the grid of `stride` and the
 // association gates, as the trackers' kernels get them:
 struct SearchFrame {
@@ -552,8 +560,21 @@ int auto_loop_track(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, con
 // ---- sm_warp.hip ----
 // sm_close_loop's rules for its parameters (SM_E_ARG with g_err set)
 int check_loop_params(const sm_loop_params &p, const char *who);
+// sm_close_loop (rgb null: the depth-only measurement) and sm_close_loop_rgb; search: sm_close_loop_search, whose step 1 is
+// sm_search_pose with sp (null: its defaults).  who: the one of the three the call came through.
+int close_loop(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *pose16, const sm_map_source *src,
+               const sm_track_params *tp, const sm_track_rgb_params *rp, const sm_loop_params *lp, bool search, const sm_search_params *sp,
+               float *pose16_out, sm_loop_info *info, const char *who);
 
 // ---- what several sources ask of their arguments (SM_E_ARG with g_err set) ----
+// what works on the whole map (retirement, recall, warp, loop closure and its policy, pose search) refuses a context that holds a
+// part of it
+inline int check_whole_map(const sm_ctx *s, const char *who)
+{
+    if (s->ss_on || s->rig_on) { g_err = std::string(who) + ": a sharded or rig context holds only its own surfels"; return SM_E_UNSUPPORTED; }
+    return SM_OK;
+}
+
 inline int check_pose(const float *pose16, const char *who)          // null: the entry point's default
 {
     if (pose16)

@@ -1,9 +1,6 @@
-// sm_k_loop.h -- closing loops unasked (DESIGN.md "4i. Closing loops unasked"): the two-sided time window of the trackers'
-// prediction and the per-frame census of old surfels in view.  Included by sm_track.hip only, after sm_k_track.h.
+// sm_k_loop.h -- closing loops unasked (DESIGN.md "4i. Closing loops unasked"): the per-frame census of old surfels in view.
+// Included by sm_track.hip only, after sm_k_track.h.
 //
-//   k_track_splat_window  k_track_splat with one more gate: min_time < m[7] <= max_time, either end open.  A kernel of its own,
-//                         so that k_track_splat and k_track_splat_old stay what they are (the host picks those two where they
-//                         say the same: both ends open, or only the upper end closed).
 //   k_loop_census         how many live surfels with m[7] <= max_time pass k_track_splat's gates at a given pose: one alive word
 //                         per 64 slots, one time per slot, a position only where the lane is old; one ballot per 64 slots, the
 //                         count kept in a register, one atomic per wave at the end.
@@ -15,35 +12,6 @@
 namespace sm {
 
 constexpr int LOOP_CENSUS_GRID = 2048;   // 256 CUs x 8 workgroups of 256: every wave walks its share of the alive words
-
-// use_min / use_max: 0 = that end is open and no comparison is made (a NaN time passes as it does in k_track_splat); both
-// comparisons are false on a NaN
-__global__ __launch_bounds__(256) void k_track_splat_window(Model M, const DevState *__restrict__ st, const uint64_t *__restrict__ alive,
-                                                            TrackParams tp, float min_time, float max_time, int use_min, int use_max,
-                                                            uint64_t *__restrict__ key, TrackState *__restrict__ ts)
-{
-    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
-    bool in_view = false;
-    if (k < st->count && ((alive[k >> 6] >> (k & 63u)) & 1ull)) {
-        const float t = M.s[st->cur].time[k];
-        if ((!use_min || t > min_time) && (!use_max || t <= max_time)) {
-            const float4 pc = M.s[st->cur].pos_conf[k];
-            const float3 c = xform3(tp.tinv_prev, pc.x, pc.y, pc.z);
-            if (c.z > tp.near_clip && c.z < tp.far_clip) {
-                const float fu = floorf(((tp.fx * c.x) / c.z + tp.cx) + 0.5f);
-                const float fv = floorf(((tp.fy * c.y) / c.z + tp.cy) + 0.5f);
-                if (fu >= 0.0f && fu < (float)tp.W && fv >= 0.0f && fv < (float)tp.H) {
-                    in_view = true;
-                    const size_t p = (size_t)(int)fv * tp.W + (int)fu;
-                    atomicMin((unsigned long long *)&key[p], (unsigned long long)(((uint64_t)__float_as_uint(c.z) << 32) | k));
-                }
-            }
-        }
-    }
-    const uint64_t m = __ballot(in_view);                     // one atomic per wave
-    if (m && (threadIdx.x & 63u) == (uint32_t)(__ffsll((unsigned long long)m) - 1))
-        atomicAdd(&ts->in_view, (uint32_t)__popcll(m));
-}
 
 // tp.tinv_prev holds the inverse of the pose the census is taken at.  Wave w of the grid takes alive words 4w .. 4w + 3, then those
 // 4 * waves further on, ...: the loop bound is the same for all 64 lanes, so every ballot sees the whole wave.  The four times of

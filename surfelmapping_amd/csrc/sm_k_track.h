@@ -7,7 +7,8 @@
 //                    prediction camera T_prev with near < z < far lands on pixel (floor(fx*x/z + cx + 0.5), floor(fy*y/z + cy + 0.5))
 //                    by a 64-bit atomicMin of (float bits of z) << 32 | slot: the nearest surfel, ties to the lower slot.
 //   k_track_resolve  key -> slot (-1 = empty), row-major W*H int32.
-//   (sm_track_frame_old: k_track_splat_old instead, which also gates on the surfel's time, and k_track_anchor after the resolve)
+//   (with a time window -- sm_track_*_old, sm_track_*_window -- the splat's instantiation that also gates on the surfel's time,
+//   and k_track_anchor after the resolve)
 //   k_track_vertex   the current frame's metric depth (p0a's rule), vertex and normal of every pixel of the strided grid.
 //   then max_iters times:
 //   k_track_reduce   associate + residual + the 29 values of the normal equations per inlier, fp32 terms accumulated in fp64,
@@ -53,21 +54,34 @@ struct TrackState {
 
 // ---- the prediction ----
 
+// USE_MIN / USE_MAX: the surfel's last-update time is held to min_time < m[7] <= max_time (sm_track_*_old, sm_track_*_window).  The
+// gates are compile-time so that the open-ended forms are the plain kernel by construction: an open end makes no comparison (a NaN
+// time passes there; both comparisons are false on a NaN), and with both ends open the time plane is not loaded at all.
+template <bool USE_MIN, bool USE_MAX>
 __global__ __launch_bounds__(256) void k_track_splat(Model M, const DevState *__restrict__ st, const uint64_t *__restrict__ alive,
-                                                     TrackParams tp, uint64_t *__restrict__ key, TrackState *__restrict__ ts)
+                                                     TrackParams tp, float min_time, float max_time, uint64_t *__restrict__ key,
+                                                     TrackState *__restrict__ ts)
 {
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;
     bool in_view = false;
     if (k < st->count && ((alive[k >> 6] >> (k & 63u)) & 1ull)) {
-        const float4 pc = M.s[st->cur].pos_conf[k];
-        const float3 c = xform3(tp.tinv_prev, pc.x, pc.y, pc.z);
-        if (c.z > tp.near_clip && c.z < tp.far_clip) {
-            const float fu = floorf(((tp.fx * c.x) / c.z + tp.cx) + 0.5f);
-            const float fv = floorf(((tp.fy * c.y) / c.z + tp.cy) + 0.5f);
-            if (fu >= 0.0f && fu < (float)tp.W && fv >= 0.0f && fv < (float)tp.H) {
-                in_view = true;
-                const size_t p = (size_t)(int)fv * tp.W + (int)fu;
-                atomicMin((unsigned long long *)&key[p], (unsigned long long)(((uint64_t)__float_as_uint(c.z) << 32) | k));
+        bool inside = true;
+        if constexpr (USE_MIN || USE_MAX) {
+            const float t = M.s[st->cur].time[k];
+            if constexpr (USE_MIN) inside = t > min_time;
+            if constexpr (USE_MAX) inside = inside && t <= max_time;
+        }
+        if (inside) {
+            const float4 pc = M.s[st->cur].pos_conf[k];
+            const float3 c = xform3(tp.tinv_prev, pc.x, pc.y, pc.z);
+            if (c.z > tp.near_clip && c.z < tp.far_clip) {
+                const float fu = floorf(((tp.fx * c.x) / c.z + tp.cx) + 0.5f);
+                const float fv = floorf(((tp.fy * c.y) / c.z + tp.cy) + 0.5f);
+                if (fu >= 0.0f && fu < (float)tp.W && fv >= 0.0f && fv < (float)tp.H) {
+                    in_view = true;
+                    const size_t p = (size_t)(int)fv * tp.W + (int)fu;
+                    atomicMin((unsigned long long *)&key[p], (unsigned long long)(((uint64_t)__float_as_uint(c.z) << 32) | k));
+                }
             }
         }
     }
@@ -82,32 +96,6 @@ __global__ void k_track_resolve(const uint64_t *__restrict__ key, int npix, int3
     if (p >= npix) return;
     const uint64_t kk = key[p];
     slot[p] = kk == KEY_EMPTY ? -1 : (int32_t)(uint32_t)(kk & 0xFFFFFFFFull);
-}
-
-// ---- the windowed prediction (sm_track_frame_old: the loop measurement, DESIGN.md "4h. Closing loops") ----
-// k_track_splat with one more gate: only surfels last updated at or before max_time (one extra time-plane load; false on a NaN).
-// A kernel of its own, so that k_track_splat stays what it is.
-__global__ __launch_bounds__(256) void k_track_splat_old(Model M, const DevState *__restrict__ st, const uint64_t *__restrict__ alive,
-                                                         TrackParams tp, float max_time, uint64_t *__restrict__ key, TrackState *__restrict__ ts)
-{
-    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
-    bool in_view = false;
-    if (k < st->count && ((alive[k >> 6] >> (k & 63u)) & 1ull) && M.s[st->cur].time[k] <= max_time) {
-        const float4 pc = M.s[st->cur].pos_conf[k];
-        const float3 c = xform3(tp.tinv_prev, pc.x, pc.y, pc.z);
-        if (c.z > tp.near_clip && c.z < tp.far_clip) {
-            const float fu = floorf(((tp.fx * c.x) / c.z + tp.cx) + 0.5f);
-            const float fv = floorf(((tp.fy * c.y) / c.z + tp.cy) + 0.5f);
-            if (fu >= 0.0f && fu < (float)tp.W && fv >= 0.0f && fv < (float)tp.H) {
-                in_view = true;
-                const size_t p = (size_t)(int)fv * tp.W + (int)fu;
-                atomicMin((unsigned long long *)&key[p], (unsigned long long)(((uint64_t)__float_as_uint(c.z) << 32) | k));
-            }
-        }
-    }
-    const uint64_t m = __ballot(in_view);                     // one atomic per wave
-    if (m && (threadIdx.x & 63u) == (uint32_t)(__ffsll((unsigned long long)m) - 1))
-        atomicAdd(&ts->in_view, (uint32_t)__popcll(m));
 }
 
 // *anchor = max over the resolved slots of f2ord(last-update time); 0 (no float's code but a NaN's) stays where the prediction is

@@ -1,6 +1,7 @@
 // sm_loop.hip -- closing loops unasked (DESIGN.md "4i. Closing loops unasked"): the per-frame policy of sm_set_auto_loop.  While it
 // is on, sm_track_frame / sm_track_frame_rgb track in the young map, count the old surfels the tracked pose sees (sm_old_in_view)
-// and, with enough of them, make one sm_close_loop / sm_close_loop_rgb attempt (sm_close_loop_search after sm_set_auto_loop_search).  Host code only: the kernels are the trackers'
+// and, with enough of them, make one sm_close_loop / sm_close_loop_rgb attempt (sm_close_loop_search after sm_set_auto_loop_search).  Both go through the
+// internal bodies (track_windowed, close_loop), not the public entry points: the policy is not re-entered.  Host code only: the kernels are the trackers'
 // (sm_k_track.h, sm_k_loop.h) and the warp's (sm_k_warp.h).
 #include "sm_ctx.h"
 #include "sm_mapfile.h"
@@ -18,9 +19,10 @@ int sm_impl::auto_loop_track(sm_ctx *s, const uint8_t *rgb, const uint16_t *dept
     const int32_t split = split64 < 0 ? INT32_MIN : (int32_t)split64;
     sm_track_info inf;
     int rc;
-    if (rgb) rc = sm_track_frame_rgb_window(s, rgb, depth_mm, guess16, params, rgb_params, split, INT32_MAX, pose16_out, &inf, rgb_info, nullptr);
-    else rc = sm_track_frame_window(s, depth_mm, guess16, params, split, INT32_MAX, pose16_out, &inf, nullptr);
-    if (rc) return rc;
+    const TrackWindow young{split, INT32_MAX};
+    if ((rc = track_windowed(s, rgb, depth_mm, guess16, params, rgb_params, &young, pose16_out, &inf, rgb_info, nullptr,
+                             rgb ? "sm_track_frame_rgb_window" : "sm_track_frame_window")))
+        return rc;
     if (info) *info = inf;
     if (inf.status != SM_TRACK_OK || split64 < 0) return SM_OK;
     if (T % a.p.every != 0 || T < a.rest_until) return SM_OK;
@@ -44,9 +46,8 @@ int sm_impl::auto_loop_track(sm_ctx *s, const uint8_t *rgb, const uint16_t *dept
     sm_loop_info li;
     a.stats.attempts++;
     a.rest_until = T + a.p.rest;                          // whatever the outcome
-    if (a.search) rc = sm_close_loop_search(s, rgb, depth_mm, tracked, &src, params, rgb_params, &a.p.loop, &a.sp, corrected, &li);
-    else if (rgb) rc = sm_close_loop_rgb(s, rgb, depth_mm, tracked, &src, params, rgb_params, &a.p.loop, corrected, &li);
-    else rc = sm_close_loop(s, depth_mm, tracked, &src, params, &a.p.loop, corrected, &li);
+    rc = close_loop(s, rgb, depth_mm, tracked, &src, params, rgb_params, &a.p.loop, a.search, &a.sp, corrected, &li,
+                    a.search ? "sm_close_loop_search" : rgb ? "sm_close_loop_rgb" : "sm_close_loop");
     if (rc) { a.stats.failed++; return rc; }
     a.stats.last = li;
     switch (li.status) {
@@ -74,7 +75,7 @@ int sm_set_auto_loop(sm_ctx *s, const sm_auto_loop_params *p, const sm_map_sourc
 {
     const char *who = "sm_set_auto_loop";
     if (!s) { g_err = std::string(who) + ": null context"; return SM_E_ARG; }
-    if (s->ss_on || s->rig_on) { g_err = std::string(who) + ": a sharded or rig context holds only its own surfels"; return SM_E_UNSUPPORTED; }
+    if (int rc = check_whole_map(s, who)) return rc;
     AutoLoop &a = s->aloop;
     if (!p) { a.on = false; a.paths.clear(); return SM_OK; }
     if (p->every < 1 || p->rest < 0) { g_err = std::string(who) + ": every must be at least 1 and rest at least 0"; return SM_E_ARG; }
@@ -103,7 +104,7 @@ int sm_set_auto_loop_search(sm_ctx *s, const sm_search_params *sp)
 {
     const char *who = "sm_set_auto_loop_search";
     if (!s) { g_err = std::string(who) + ": null context"; return SM_E_ARG; }
-    if (s->ss_on || s->rig_on) { g_err = std::string(who) + ": a sharded or rig context holds only its own surfels"; return SM_E_UNSUPPORTED; }
+    if (int rc = check_whole_map(s, who)) return rc;
     AutoLoop &a = s->aloop;
     if (!sp) { a.search = false; return SM_OK; }
     if (int rc = check_search_params(*sp, who)) return rc;

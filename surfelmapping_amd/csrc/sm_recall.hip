@@ -180,7 +180,7 @@ int check_args(sm_ctx *s, const sm_map_source *src, const float *pose16, const s
                const char *who)
 {
     if (!s || !src || !n) { g_err = std::string(who) + ": null context, source or count"; return SM_E_ARG; }
-    if (s->ss_on || s->rig_on) { g_err = std::string(who) + ": a sharded or rig context holds only its own surfels"; return SM_E_UNSUPPORTED; }
+    if (int rc = check_whole_map(s, who)) return rc;
     if (src->include_model) { g_err = std::string(who) + ": include_model must be 0"; return SM_E_ARG; }
     if (int rc = check_map_source(src, who)) return rc;
     if (mode != SM_RECALL_MOVE && mode != SM_RECALL_COPY && mode != SM_RECALL_COUNT) { g_err = std::string(who) + ": unknown mode"; return SM_E_ARG; }
@@ -382,7 +382,7 @@ int sm_recall_stats(sm_ctx *s, sm_recall_stats_t *out)
 int sm_set_auto_recall(sm_ctx *s, const sm_recall_params *params)
 {
     if (!s) return SM_E_ARG;
-    if (s->ss_on || s->rig_on) { g_err = "sm_set_auto_recall: a sharded or rig context holds only its own surfels"; return SM_E_UNSUPPORTED; }
+    if (int rc = check_whole_map(s, "sm_set_auto_recall")) return rc;
     if (!params || params->radius <= 0.0f) { s->rec.radius = 0.0f; return SM_OK; }
     if (!std::isfinite(params->radius)) { g_err = "sm_set_auto_recall: radius must be finite"; return SM_E_ARG; }
     if (s->ret.every > 0)

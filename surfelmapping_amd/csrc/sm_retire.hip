@@ -27,10 +27,7 @@ int tic(sm_ctx *s, int i)
 
 int check_args(sm_ctx *s, const float *pose16, const sm_retire_params *p, const char *who)
 {
-    if (s->ss_on || s->rig_on) {
-        g_err = std::string(who) + ": a sharded or rig context holds only its own surfels";
-        return SM_E_UNSUPPORTED;
-    }
+    if (int rc = check_whole_map(s, who)) return rc;
     if (p && (p->min_age < 0 || !std::isfinite(p->min_distance))) { g_err = std::string(who) + ": bad parameters"; return SM_E_ARG; }
     if (int rc = check_pose(pose16, who)) return rc;
     if (s->pending_cull) { g_err = std::string(who) + " between sm_stage_conflict and sm_stage_cull"; return SM_E_ARG; }

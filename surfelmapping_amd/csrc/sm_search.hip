@@ -1,6 +1,6 @@
 // sm_search.hip -- pose search before the tracker (sm_score_poses_window, sm_search_pose; DESIGN.md "4j. Pose search").
 // Kernels: sm_k_search.h.  The prediction and the grid's vertex stage are the trackers' (sm_track.hip, search_prepare); the
-// refinement runs through the public windowed trackers.
+// refinement runs through the trackers' one frame body (track_windowed).
 #include "sm_ctx.h"
 #include "sm_k_search.h"
 
@@ -41,12 +41,6 @@ int check_candidates(const float *cand16, uint32_t n, const char *fn)
     if (n == 0 || n > SM_SEARCH_MAX_CANDIDATES) { g_err = std::string(fn) + ": the number of candidates is outside 1..2^20"; return SM_E_ARG; }
     for (size_t i = 0; i < (size_t)n * 16; ++i)
         if (!std::isfinite(cand16[i])) { g_err = std::string(fn) + ": non-finite candidate"; return SM_E_ARG; }
-    return SM_OK;
-}
-
-int check_context(const sm_ctx *s, const char *fn)
-{
-    if (s->ss_on || s->rig_on) { g_err = std::string(fn) + ": a sharded or rig context holds only its own surfels"; return SM_E_UNSUPPORTED; }
     return SM_OK;
 }
 
@@ -219,7 +213,7 @@ int sm_score_poses_window(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_m
     const char *fn = "sm_score_poses_window";
     if (!s || !depth_mm || !cand16 || !scores) { g_err = std::string(fn) + ": null argument"; return SM_E_ARG; }
     int rc;
-    if ((rc = check_context(s, fn)) || (rc = check_candidates(cand16, n, fn))) return rc;
+    if ((rc = check_whole_map(s, fn)) || (rc = check_candidates(cand16, n, fn))) return rc;
     if (stride < 1) { g_err = std::string(fn) + ": stride < 1"; return SM_E_ARG; }
     if (!(colour_thresh >= 0.0f)) { g_err = std::string(fn) + ": colour_thresh negative or not a number"; return SM_E_ARG; }
     sm_track_params p;
@@ -250,7 +244,7 @@ int sm_search_pose(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, cons
     const auto t_start = std::chrono::steady_clock::now();
     if (!s || !depth_mm || !centre16 || !pose16_out) { g_err = std::string(fn) + ": null argument"; return SM_E_ARG; }
     int rc;
-    if ((rc = check_context(s, fn)) || (rc = check_pose(centre16, fn))) return rc;
+    if ((rc = check_whole_map(s, fn)) || (rc = check_pose(centre16, fn))) return rc;
     sm_search_params q;
     if (sp) q = *sp;
     else sm_default_search_params(&q);
@@ -324,13 +318,14 @@ int sm_search_pose(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, cons
 
     // the refinement: every kept candidate of the last level through the tracker
     bool have_ok = false;
+    const TrackWindow win{min_time, max_time};
     for (size_t r = 0; r < kept.size(); ++r) {
         const float *g = kept_pose.data() + r * 16;
         float out[16], anchor = -1.0f;
         sm_track_info ti;
-        if (rgb) rc = sm_track_frame_rgb_window(s, rgb, depth_mm, g, &p, rp, min_time, max_time, out, &ti, nullptr, &anchor);
-        else rc = sm_track_frame_window(s, depth_mm, g, &p, min_time, max_time, out, &ti, &anchor);
-        if (rc) return rc;
+        if ((rc = track_windowed(s, rgb, depth_mm, g, &p, rp, &win, out, &ti, nullptr, &anchor,
+                                 rgb ? "sm_track_frame_rgb_window" : "sm_track_frame_window")))
+            return rc;
         const bool ok = ti.status == SM_TRACK_OK;
         if ((r == 0 && !ok) || (ok && (!have_ok || ti.inliers > inf.track.inliers))) {
             inf.track = ti;

@@ -4,65 +4,28 @@
 #include "sm_k_track.h"
 #include "sm_k_track_rgb.h"
 #include "sm_k_loop.h"
+#include "sm_pose.h"
 
 #include <cmath>
 
 using namespace sm;
+using sm_pose::orthonormalize_d;
+using sm_pose::rigid_inv_d;
 
 namespace {
-// the time window of a prediction: surfels with lo < m[7] <= hi; INT32_MIN / INT32_MAX leave that end open
-struct Window { int32_t lo, hi; };
-
-// [R^T | -R^T t] of a column-major rigid pose, double
-void rigid_inv_d(const double *m, double *o)
-{
-    for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) o[c * 4 + r] = m[r * 4 + c];
-        o[12 + r] = -((m[r * 4 + 0] * m[12] + m[r * 4 + 1] * m[13]) + m[r * 4 + 2] * m[14]);
-    }
-    o[3] = 0.0; o[7] = 0.0; o[11] = 0.0; o[15] = 1.0;
-}
-
-// column-major rigid product a * b, double
-void mul_rigid_d(const double *a, const double *b, double *o)
-{
-    for (int c = 0; c < 4; ++c)
-        for (int r = 0; r < 3; ++r)
-            o[c * 4 + r] = ((a[r] * b[c * 4] + a[4 + r] * b[c * 4 + 1]) + a[8 + r] * b[c * 4 + 2]) + (c == 3 ? a[12 + r] : 0.0);
-    o[3] = 0.0; o[7] = 0.0; o[11] = 0.0; o[15] = 1.0;
-}
-
-// the rotation of a column-major pose made orthonormal (Gram-Schmidt on columns 0 and 1, column 2 = 0 x 1), double.  Float
-// poses are orthonormal to ~1e-7 only; products of them (the constant-velocity guess, exp(xi) * guess) would carry and, frame
-// after frame, multiply that error, so every product starts from orthonormal factors.
-void orthonormalize_d(double *m)
-{
-    double *a = m, *b = m + 4, *c = m + 8;
-    const double na = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
-    for (int k = 0; k < 3; ++k) a[k] /= na;
-    const double ab = a[0] * b[0] + a[1] * b[1] + a[2] * b[2];
-    for (int k = 0; k < 3; ++k) b[k] -= ab * a[k];
-    const double nb = std::sqrt(b[0] * b[0] + b[1] * b[1] + b[2] * b[2]);
-    for (int k = 0; k < 3; ++k) b[k] /= nb;
-    c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
-    m[3] = 0.0; m[7] = 0.0; m[11] = 0.0; m[15] = 1.0;
-}
-
 // constant velocity T_prev * (T_prev2^-1 * T_prev) of the orthonormalised poses; one processed pose: that pose; none: the identity
 void track_guess(const sm_ctx *s, float *g)
 {
-    if (s->trk.n_hist == 0) {
-        for (int e = 0; e < 16; ++e) g[e] = (e % 5 == 0) ? 1.0f : 0.0f;
-        return;
-    }
+    if (s->trk.n_hist == 0) { sm_pose::identity(g); return; }
     if (s->trk.n_hist == 1) { memcpy(g, s->trk.hist[0], 64); return; }
     double p[16], p2[16], p2i[16], rel[16], out[16];
-    for (int e = 0; e < 16; ++e) { p[e] = s->trk.hist[0][e]; p2[e] = s->trk.hist[1][e]; }
+    sm_pose::widen(s->trk.hist[0], p);
+    sm_pose::widen(s->trk.hist[1], p2);
     orthonormalize_d(p);
     orthonormalize_d(p2);
     rigid_inv_d(p2, p2i);
-    mul_rigid_d(p2i, p, rel);
-    mul_rigid_d(p, rel, out);
+    sm_pose::mul_rigid_d(p2i, p, rel);
+    sm_pose::mul_rigid_d(p, rel, out);
     for (int e = 0; e < 16; ++e) g[e] = (float)out[e];
 }
 
@@ -109,7 +72,8 @@ TrackParams track_params(const sm_ctx *s, const sm_track_params &p)
     TrackParams tp;
     memset(&tp, 0, sizeof tp);
     double prev[16], inv[16];
-    for (int e = 0; e < 16; ++e) prev[e] = s->trk.n_hist ? (double)s->trk.hist[0][e] : ((e % 5 == 0) ? 1.0 : 0.0);
+    if (s->trk.n_hist) sm_pose::widen(s->trk.hist[0], prev);
+    else sm_pose::identity(prev);
     rigid_inv_d(prev, inv);
     for (int e = 0; e < 16; ++e) tp.tinv_prev[e] = (float)inv[e];
     for (int k = 0; k < 3; ++k) tp.c[k] = prev[12 + k];
@@ -148,7 +112,7 @@ int track_event(sm_ctx *s, size_t i)
 // win (sm_track_*_old, sm_track_*_window; null otherwise): the prediction holds only surfels last updated inside it, and the
 // newest time it holds is left in d_anchor
 int track_prepare(sm_ctx *s, const uint16_t *depth_mm, const TrackParams &tp, const float *T0, const float *guess, bool ortho,
-                  const Window *win = nullptr)
+                  const TrackWindow *win)
 {
     const size_t P = (size_t)s->P;
     TrackState &h = *s->trk.h_state;
@@ -169,15 +133,11 @@ int track_prepare(sm_ctx *s, const uint16_t *depth_mm, const TrackParams &tp, co
     // (an open end is not compared: both open is exactly sm_track_frame's prediction, whatever the times are, and an open
     // lower end exactly sm_track_frame_old's)
     const bool use_min = win && win->lo != INT32_MIN, use_max = win && win->hi != INT32_MAX;
-    if (slots && use_min)
-        hipLaunchKernelGGL(k_track_splat_window, dim3((slots + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, s->d_alive, tp,
-                           (float)win->lo, (float)win->hi, 1, use_max ? 1 : 0, s->trk.d_key, s->trk.d_state);
-    else if (slots && use_max)
-        hipLaunchKernelGGL(k_track_splat_old, dim3((slots + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, s->d_alive, tp,
-                           (float)win->hi, s->trk.d_key, s->trk.d_state);
-    else if (slots)
-        hipLaunchKernelGGL(k_track_splat, dim3((slots + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, s->d_alive, tp,
-                           s->trk.d_key, s->trk.d_state);
+    const auto splat = use_min ? (use_max ? k_track_splat<true, true> : k_track_splat<true, false>)
+                               : (use_max ? k_track_splat<false, true> : k_track_splat<false, false>);
+    if (slots)
+        hipLaunchKernelGGL(splat, dim3((slots + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, s->d_alive, tp,
+                           use_min ? (float)win->lo : 0.0f, use_max ? (float)win->hi : 0.0f, s->trk.d_key, s->trk.d_state);
     hipLaunchKernelGGL(k_track_resolve, dim3(pblocks), dim3(256), 0, s->stream, s->trk.d_key, (int)P, s->trk.d_pred);
     if (win) {
         HIPCK(hipMemsetAsync(s->trk.d_anchor, 0, 4, s->stream));
@@ -274,7 +234,7 @@ TrackParams track_level_params(const sm_ctx *s, sm_track_params p, int level)
 
 // sm_track_frame's preparation on the coarsest level's grid, then the pyramid and the gathered prediction (the rgb upload precedes event 0, as the depth's)
 int track_rgb_prepare(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const TrackParams &tpc, const TrackRgbParams &rp,
-                      const float *T0, const float *guess, bool ortho, int first_level, const Window *win = nullptr)
+                      const float *T0, const float *guess, bool ortho, int first_level, const TrackWindow *win)
 {
     const size_t P = (size_t)s->P;
     TrackRgbState &h = *s->trk.h_rstate;
@@ -345,16 +305,77 @@ float anchor_of(uint32_t code)
     return f;
 }
 
-// sm_track_frame, and with a window sm_track_frame_old / sm_track_frame_window (anchor_time may be null)
-int track_frame(sm_ctx *s, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params, const Window *win,
-                float *pose16_out, sm_track_info *info, float *anchor_time, const char *fn)
+// one iteration's system at the pose as given, with the default parameters: sm_track_debug* (rgb null; level and which are not
+// read) and sm_track_rgb_debug* (which 0 = joint, 1 = the geometric term, 2 = the photometric term).  pred_slot may be null.
+int track_debug(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *pose16_eval, int level, int which,
+                const TrackWindow *win, int32_t *pred_slot, double *sys29, const char *fn)
+{
+    if (!s || !depth_mm || !pose16_eval) { g_err = std::string(fn) + ": null argument"; return SM_E_ARG; }
+    sm_track_params p;
+    sm_default_track_params(&p);
+    sm_track_rgb_params q;
+    if (rgb) {
+        sm_default_track_rgb_params(&q);
+        q.levels = level + 1;                                 // (the pyramid up to that level; its size is checked below)
+        if (level < 0 || level >= TRACK_RGB_LEVELS || which < 0 || which > 2) {
+            g_err = std::string(fn) + ": level outside 0..5 or which outside 0..2";
+            return SM_E_ARG;
+        }
+        if (const char *why = track_rgb_check(s, p, q)) { g_err = std::string(fn) + ": " + why; return SM_E_ARG; }
+    }
+    int rc = track_check(s, fn);
+    if (rc) return rc;
+    HIPCK(hipSetDevice(s->cfg.device));
+    if ((rc = pull_state(s))) return rc;
+    if ((rc = track_alloc(s)) || (rgb && (rc = track_rgb_alloc(s)))) return rc;
+    const double *src = s->trk.h_state->sys;
+    if (rgb) {
+        const TrackRgbParams rp = track_rgb_params(s, q);
+        const TrackParams tpl = track_level_params(s, p, level);
+        if ((rc = track_rgb_prepare(s, rgb, depth_mm, tpl, rp, pose16_eval, pose16_eval, false, level, win))) return rc;   // (the pose as given)
+        if ((rc = track_rgb_iteration(s, tpl, rp, level, 1))) return rc;
+        if (which) src = which == 1 ? s->trk.h_rstate->sys_icp : s->trk.h_rstate->sys_rgb;
+    } else {
+        const TrackParams tp = track_params(s, p);
+        if ((rc = track_prepare(s, depth_mm, tp, pose16_eval, pose16_eval, false, win))) return rc;   // (the pose as given)
+        if ((rc = track_iteration(s, tp, 1))) return rc;
+    }
+    if (pred_slot) HIPCK(hipMemcpyAsync(pred_slot, s->trk.d_pred, (size_t)s->P * 4, hipMemcpyDeviceToHost, s->stream));
+    HIPCK(hipMemcpyAsync(s->trk.h_state, s->trk.d_state, sizeof(TrackState), hipMemcpyDeviceToHost, s->stream));
+    if (rgb) HIPCK(hipMemcpyAsync(s->trk.h_rstate, s->trk.d_rstate, sizeof(TrackRgbState), hipMemcpyDeviceToHost, s->stream));
+    HIPCK(hipStreamSynchronize(s->stream));
+    if (sys29) memcpy(sys29, src, TRACK_NSYS * sizeof(double));
+    return SM_OK;
+}
+
+// what an entry point of the colour forms says to a null image (rgb null selects the depth forms in the bodies)
+int null_argument(const char *fn)
+{
+    g_err = std::string(fn) + ": null argument";
+    return SM_E_ARG;
+}
+}  // namespace
+
+// ---- one tracked frame, every form: rgb null is the depth schedule (max_iters iterations on the pixel_stride grid; rgb_params and
+// rgb_info are not read), otherwise the colour term's pyramid schedule; win null is the whole model (anchor_time may be null).
+// fn: the public entry point the call came through -- it does not consult the policy of sm_set_auto_loop.
+int sm_impl::track_windowed(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params,
+                            const sm_track_rgb_params *rgb_params, const TrackWindow *win, float *pose16_out, sm_track_info *info,
+                            sm_track_rgb_info *rgb_info, float *anchor_time, const char *fn)
 {
     if (!s || !depth_mm || !pose16_out) { g_err = std::string(fn) + ": null argument"; return SM_E_ARG; }
     sm_track_params p;
     if (params) p = *params;
     else sm_default_track_params(&p);
+    sm_track_rgb_params q;
+    if (rgb_params) q = *rgb_params;
+    else sm_default_track_rgb_params(&q);
     int rc;
-    if ((rc = track_params_check(s, p, fn)) || (rc = track_check(s, fn))) return rc;
+    // (max_iters is sm_track_frame's: checked as there in the colour forms too, whose schedule is iters[])
+    if ((rc = track_params_check(s, p, fn))) return rc;
+    if (rgb)
+        if (const char *why = track_rgb_check(s, p, q)) { g_err = std::string(fn) + ": " + why; return SM_E_ARG; }
+    if ((rc = track_check(s, fn))) return rc;
     if (anchor_time) *anchor_time = -1.0f;
     HIPCK(hipSetDevice(s->cfg.device));
     if ((rc = pull_state(s))) return rc;                      // waits for frames in flight: the model after the last frame
@@ -362,23 +383,40 @@ int track_frame(sm_ctx *s, const uint16_t *depth_mm, const float *guess16, const
     if (guess16) memcpy(g, guess16, 64);
     else track_guess(s, g);
     sm_track_info inf;
+    sm_track_rgb_info rinf;
     memset(&inf, 0, sizeof inf);
+    memset(&rinf, 0, sizeof rinf);
     memcpy(inf.guess, g, 64);
     const uint32_t live = s->h_state->count - s->h_state->garbage;
     if (s->trk.n_hist == 0 || live == 0) {
         inf.status = SM_TRACK_NO_MODEL;
         memcpy(pose16_out, g, 64);
         if (info) *info = inf;
+        if (rgb && rgb_info) *rgb_info = rinf;
         return SM_OK;
     }
-    if ((rc = track_alloc(s))) return rc;
-    const TrackParams tp = track_params(s, p);
-    if ((rc = track_prepare(s, depth_mm, tp, g, g, true, win))) return rc;         // (iterates from the orthonormalised guess)
-    for (int it = 0; it < p.max_iters; ++it)
-        if ((rc = track_iteration(s, tp, 0))) return rc;
+    if ((rc = track_alloc(s)) || (rgb && (rc = track_rgb_alloc(s)))) return rc;
+    if (rgb) {
+        const TrackRgbParams rp = track_rgb_params(s, q);
+        // (the preparation's vertex stage is the coarsest level's; the prediction does not depend on the stride)
+        const TrackParams tpc = track_level_params(s, p, q.levels - 1);
+        if ((rc = track_rgb_prepare(s, rgb, depth_mm, tpc, rp, g, g, true, q.levels - 1, win))) return rc;
+        for (int l = q.levels - 1; l >= 0; --l) {
+            const TrackParams tpl = track_level_params(s, p, l);
+            if (l < q.levels - 1 && (rc = track_rgb_level(s, tpl, l))) return rc;
+            for (int it = 0; it < q.iters[l]; ++it)
+                if ((rc = track_rgb_iteration(s, tpl, rp, l, 0))) return rc;
+        }
+    } else {
+        const TrackParams tp = track_params(s, p);
+        if ((rc = track_prepare(s, depth_mm, tp, g, g, true, win))) return rc;     // (iterates from the orthonormalised guess)
+        for (int it = 0; it < p.max_iters; ++it)
+            if ((rc = track_iteration(s, tp, 0))) return rc;
+    }
     uint32_t anchor = 0;
     if (win) HIPCK(hipMemcpyAsync(&anchor, s->trk.d_anchor, 4, hipMemcpyDeviceToHost, s->stream));
     HIPCK(hipMemcpyAsync(s->trk.h_state, s->trk.d_state, sizeof(TrackState), hipMemcpyDeviceToHost, s->stream));
+    if (rgb) HIPCK(hipMemcpyAsync(s->trk.h_rstate, s->trk.d_rstate, sizeof(TrackRgbState), hipMemcpyDeviceToHost, s->stream));
     HIPCK(hipStreamSynchronize(s->stream));                   // the one wait of a tracked frame
     const TrackState &h = *s->trk.h_state;
     for (int e = 0; e < 16; ++e) pose16_out[e] = (float)h.T[e];
@@ -387,31 +425,17 @@ int track_frame(sm_ctx *s, const uint16_t *depth_mm, const float *guess16, const
     inf.inliers = h.inliers;
     inf.rmse = (float)h.rmse;
     if (info) *info = inf;
+    if (rgb && rgb_info) {
+        const TrackRgbState &hr = *s->trk.h_rstate;
+        rinf.rgb_inliers = hr.rgb_inliers;
+        rinf.rgb_rmse = (float)hr.rgb_rmse;
+        rinf.pivot_ratio = h.pivot_ratio;
+        for (int l = 0; l < TRACK_RGB_LEVELS; ++l) rinf.level_iterations[l] = hr.level_iterations[l];
+        *rgb_info = rinf;
+    }
     if (anchor_time) *anchor_time = anchor_of(anchor);
     return SM_OK;
 }
-
-int track_debug(sm_ctx *s, const uint16_t *depth_mm, const float *pose16_eval, const Window *win, int32_t *pred_slot, double *sys29,
-                const char *fn)
-{
-    if (!s || !depth_mm || !pose16_eval) { g_err = std::string(fn) + ": null argument"; return SM_E_ARG; }
-    int rc = track_check(s, fn);
-    if (rc) return rc;
-    HIPCK(hipSetDevice(s->cfg.device));
-    if ((rc = pull_state(s))) return rc;
-    if ((rc = track_alloc(s))) return rc;
-    sm_track_params p;
-    sm_default_track_params(&p);
-    const TrackParams tp = track_params(s, p);
-    if ((rc = track_prepare(s, depth_mm, tp, pose16_eval, pose16_eval, false, win))) return rc;   // (the pose as given)
-    if ((rc = track_iteration(s, tp, 1))) return rc;
-    if (pred_slot) HIPCK(hipMemcpyAsync(pred_slot, s->trk.d_pred, (size_t)s->P * 4, hipMemcpyDeviceToHost, s->stream));
-    HIPCK(hipMemcpyAsync(s->trk.h_state, s->trk.d_state, sizeof(TrackState), hipMemcpyDeviceToHost, s->stream));
-    HIPCK(hipStreamSynchronize(s->stream));
-    if (sys29) memcpy(sys29, s->trk.h_state->sys, TRACK_NSYS * sizeof(double));
-    return SM_OK;
-}
-}  // namespace
 
 // ---- what the pose search takes from the preparation (sm_search.hip) ----
 int sm_impl::search_prepare(sm_ctx *s, const uint16_t *depth_mm, const sm_track_params &params, int32_t stride, int32_t min_time,
@@ -429,8 +453,8 @@ int sm_impl::search_prepare(sm_ctx *s, const uint16_t *depth_mm, const sm_track_
     const TrackParams tp = track_params(s, p);
     if (fresh) {
         float eye[16];
-        for (int e = 0; e < 16; ++e) eye[e] = (e % 5 == 0) ? 1.0f : 0.0f;
-        const Window win{min_time, max_time};
+        sm_pose::identity(eye);
+        const TrackWindow win{min_time, max_time};
         if ((rc = track_prepare(s, depth_mm, tp, eye, eye, false, &win))) return rc;   // (no estimate is iterated)
     } else {
         hipLaunchKernelGGL(k_track_vertex, dim3((tp.n + 255) / 256), dim3(256), 0, s->stream, s->trk.d_depth, s->d_xs, s->d_ys, tp,
@@ -453,39 +477,72 @@ int sm_track_frame(sm_ctx *s, const uint16_t *depth_mm, const float *guess16, co
                    sm_track_info *info)
 {
     if (s && s->aloop.on) return auto_loop_track(s, nullptr, depth_mm, guess16, params, nullptr, pose16_out, info, nullptr);
-    return track_frame(s, depth_mm, guess16, params, nullptr, pose16_out, info, nullptr, "sm_track_frame");
+    return track_windowed(s, nullptr, depth_mm, guess16, params, nullptr, nullptr, pose16_out, info, nullptr, nullptr, "sm_track_frame");
 }
 
 int sm_track_frame_old(sm_ctx *s, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params, int32_t max_time,
                        float *pose16_out, sm_track_info *info, float *anchor_time)
 {
-    const Window win{INT32_MIN, max_time};
-    return track_frame(s, depth_mm, guess16, params, &win, pose16_out, info, anchor_time, "sm_track_frame_old");
-}
-
-int sm_track_debug(sm_ctx *s, const uint16_t *depth_mm, const float *pose16_eval, int32_t *pred_slot, double *sys29)
-{
-    return track_debug(s, depth_mm, pose16_eval, nullptr, pred_slot, sys29, "sm_track_debug");
+    const TrackWindow win{INT32_MIN, max_time};
+    return track_windowed(s, nullptr, depth_mm, guess16, params, nullptr, &win, pose16_out, info, nullptr, anchor_time, "sm_track_frame_old");
 }
 
 int sm_track_frame_window(sm_ctx *s, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params, int32_t min_time,
                           int32_t max_time, float *pose16_out, sm_track_info *info, float *anchor_time)
 {
-    const Window win{min_time, max_time};
-    return track_frame(s, depth_mm, guess16, params, &win, pose16_out, info, anchor_time, "sm_track_frame_window");
+    const TrackWindow win{min_time, max_time};
+    return track_windowed(s, nullptr, depth_mm, guess16, params, nullptr, &win, pose16_out, info, nullptr, anchor_time, "sm_track_frame_window");
+}
+
+int sm_track_frame_rgb(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params,
+                       const sm_track_rgb_params *rgb_params, float *pose16_out, sm_track_info *info, sm_track_rgb_info *rgb_info)
+{
+    if (!rgb) return null_argument("sm_track_frame_rgb");
+    if (s && s->aloop.on) return auto_loop_track(s, rgb, depth_mm, guess16, params, rgb_params, pose16_out, info, rgb_info);
+    return track_windowed(s, rgb, depth_mm, guess16, params, rgb_params, nullptr, pose16_out, info, rgb_info, nullptr, "sm_track_frame_rgb");
+}
+
+int sm_track_frame_rgb_window(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params,
+                              const sm_track_rgb_params *rgb_params, int32_t min_time, int32_t max_time, float *pose16_out,
+                              sm_track_info *info, sm_track_rgb_info *rgb_info, float *anchor_time)
+{
+    if (!rgb) return null_argument("sm_track_frame_rgb_window");
+    const TrackWindow win{min_time, max_time};
+    return track_windowed(s, rgb, depth_mm, guess16, params, rgb_params, &win, pose16_out, info, rgb_info, anchor_time,
+                          "sm_track_frame_rgb_window");
+}
+
+int sm_track_debug(sm_ctx *s, const uint16_t *depth_mm, const float *pose16_eval, int32_t *pred_slot, double *sys29)
+{
+    return track_debug(s, nullptr, depth_mm, pose16_eval, 0, 0, nullptr, pred_slot, sys29, "sm_track_debug");
+}
+
+int sm_track_debug_old(sm_ctx *s, const uint16_t *depth_mm, const float *pose16_eval, int32_t max_time, int32_t *pred_slot, double *sys29)
+{
+    const TrackWindow win{INT32_MIN, max_time};
+    return track_debug(s, nullptr, depth_mm, pose16_eval, 0, 0, &win, pred_slot, sys29, "sm_track_debug_old");
 }
 
 int sm_track_debug_window(sm_ctx *s, const uint16_t *depth_mm, const float *pose16_eval, int32_t min_time, int32_t max_time,
                           int32_t *pred_slot, double *sys29)
 {
-    const Window win{min_time, max_time};
-    return track_debug(s, depth_mm, pose16_eval, &win, pred_slot, sys29, "sm_track_debug_window");
+    const TrackWindow win{min_time, max_time};
+    return track_debug(s, nullptr, depth_mm, pose16_eval, 0, 0, &win, pred_slot, sys29, "sm_track_debug_window");
 }
 
-int sm_track_debug_old(sm_ctx *s, const uint16_t *depth_mm, const float *pose16_eval, int32_t max_time, int32_t *pred_slot, double *sys29)
+int sm_track_rgb_debug(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *pose16_eval, int level, int which,
+                       double *sys29)
 {
-    const Window win{INT32_MIN, max_time};
-    return track_debug(s, depth_mm, pose16_eval, &win, pred_slot, sys29, "sm_track_debug_old");
+    if (!rgb) return null_argument("sm_track_rgb_debug");
+    return track_debug(s, rgb, depth_mm, pose16_eval, level, which, nullptr, nullptr, sys29, "sm_track_rgb_debug");
+}
+
+int sm_track_rgb_debug_window(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *pose16_eval, int level, int which,
+                              int32_t min_time, int32_t max_time, int32_t *pred_slot, double *sys29)
+{
+    if (!rgb) return null_argument("sm_track_rgb_debug_window");
+    const TrackWindow win{min_time, max_time};
+    return track_debug(s, rgb, depth_mm, pose16_eval, level, which, &win, pred_slot, sys29, "sm_track_rgb_debug_window");
 }
 
 // Diagnostic, deliberately not part of include/sm_c_api.h (tools/track_probe.py): device times of the last sm_track_frame /
@@ -517,137 +574,6 @@ int sm_default_track_rgb_params(sm_track_rgb_params *p)
     return SM_OK;
 }
 
-// sm_track_frame_rgb, and with a window sm_track_frame_rgb_window (anchor_time may be null)
-static int track_frame_rgb(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params,
-                           const sm_track_rgb_params *rgb_params, const Window *win, float *pose16_out, sm_track_info *info,
-                           sm_track_rgb_info *rgb_info, float *anchor_time, const char *fn)
-{
-    if (!s || !rgb || !depth_mm || !pose16_out) { g_err = std::string(fn) + ": null argument"; return SM_E_ARG; }
-    sm_track_params p;
-    if (params) p = *params;
-    else sm_default_track_params(&p);
-    sm_track_rgb_params q;
-    if (rgb_params) q = *rgb_params;
-    else sm_default_track_rgb_params(&q);
-    int rc;
-    // (max_iters is sm_track_frame's: checked as there; the level schedule is iters[])
-    if ((rc = track_params_check(s, p, fn))) return rc;
-    if (const char *why = track_rgb_check(s, p, q)) { g_err = std::string(fn) + ": " + why; return SM_E_ARG; }
-    if ((rc = track_check(s, fn))) return rc;
-    if (anchor_time) *anchor_time = -1.0f;
-    HIPCK(hipSetDevice(s->cfg.device));
-    if ((rc = pull_state(s))) return rc;                      // waits for frames in flight: the model after the last frame
-    float g[16];
-    if (guess16) memcpy(g, guess16, 64);
-    else track_guess(s, g);
-    sm_track_info inf;
-    sm_track_rgb_info rinf;
-    memset(&inf, 0, sizeof inf);
-    memset(&rinf, 0, sizeof rinf);
-    memcpy(inf.guess, g, 64);
-    const uint32_t live = s->h_state->count - s->h_state->garbage;
-    if (s->trk.n_hist == 0 || live == 0) {
-        inf.status = SM_TRACK_NO_MODEL;
-        memcpy(pose16_out, g, 64);
-        if (info) *info = inf;
-        if (rgb_info) *rgb_info = rinf;
-        return SM_OK;
-    }
-    if ((rc = track_alloc(s)) || (rc = track_rgb_alloc(s))) return rc;
-    const TrackRgbParams rp = track_rgb_params(s, q);
-    // (the preparation's vertex stage is the coarsest level's; the prediction does not depend on the stride)
-    const TrackParams tpc = track_level_params(s, p, q.levels - 1);
-    if ((rc = track_rgb_prepare(s, rgb, depth_mm, tpc, rp, g, g, true, q.levels - 1, win))) return rc;
-    for (int l = q.levels - 1; l >= 0; --l) {
-        const TrackParams tpl = track_level_params(s, p, l);
-        if (l < q.levels - 1 && (rc = track_rgb_level(s, tpl, l))) return rc;
-        for (int it = 0; it < q.iters[l]; ++it)
-            if ((rc = track_rgb_iteration(s, tpl, rp, l, 0))) return rc;
-    }
-    uint32_t anchor = 0;
-    if (win) HIPCK(hipMemcpyAsync(&anchor, s->trk.d_anchor, 4, hipMemcpyDeviceToHost, s->stream));
-    HIPCK(hipMemcpyAsync(s->trk.h_state, s->trk.d_state, sizeof(TrackState), hipMemcpyDeviceToHost, s->stream));
-    HIPCK(hipMemcpyAsync(s->trk.h_rstate, s->trk.d_rstate, sizeof(TrackRgbState), hipMemcpyDeviceToHost, s->stream));
-    HIPCK(hipStreamSynchronize(s->stream));                   // the one wait of a tracked frame
-    const TrackState &h = *s->trk.h_state;
-    const TrackRgbState &hr = *s->trk.h_rstate;
-    for (int e = 0; e < 16; ++e) pose16_out[e] = (float)h.T[e];
-    inf.status = h.status;
-    inf.iterations = h.iterations;
-    inf.inliers = h.inliers;
-    inf.rmse = (float)h.rmse;
-    rinf.rgb_inliers = hr.rgb_inliers;
-    rinf.rgb_rmse = (float)hr.rgb_rmse;
-    rinf.pivot_ratio = h.pivot_ratio;
-    for (int l = 0; l < TRACK_RGB_LEVELS; ++l) rinf.level_iterations[l] = hr.level_iterations[l];
-    if (info) *info = inf;
-    if (rgb_info) *rgb_info = rinf;
-    if (anchor_time) *anchor_time = anchor_of(anchor);
-    return SM_OK;
-}
-
-int sm_track_frame_rgb(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params,
-                       const sm_track_rgb_params *rgb_params, float *pose16_out, sm_track_info *info, sm_track_rgb_info *rgb_info)
-{
-    if (s && rgb && s->aloop.on) return auto_loop_track(s, rgb, depth_mm, guess16, params, rgb_params, pose16_out, info, rgb_info);
-    return track_frame_rgb(s, rgb, depth_mm, guess16, params, rgb_params, nullptr, pose16_out, info, rgb_info, nullptr, "sm_track_frame_rgb");
-}
-
-int sm_track_frame_rgb_window(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params,
-                              const sm_track_rgb_params *rgb_params, int32_t min_time, int32_t max_time, float *pose16_out,
-                              sm_track_info *info, sm_track_rgb_info *rgb_info, float *anchor_time)
-{
-    const Window win{min_time, max_time};
-    return track_frame_rgb(s, rgb, depth_mm, guess16, params, rgb_params, &win, pose16_out, info, rgb_info, anchor_time,
-                           "sm_track_frame_rgb_window");
-}
-
-// sm_track_rgb_debug, and with a window sm_track_rgb_debug_window (pred_slot may be null)
-static int track_rgb_debug(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *pose16_eval, int level, int which,
-                           const Window *win, int32_t *pred_slot, double *sys29, const char *fn)
-{
-    if (!s || !rgb || !depth_mm || !pose16_eval) { g_err = std::string(fn) + ": null argument"; return SM_E_ARG; }
-    sm_track_params p;
-    sm_default_track_params(&p);
-    sm_track_rgb_params q;
-    sm_default_track_rgb_params(&q);
-    q.levels = level + 1;                                     // (the pyramid up to that level; its size is checked below)
-    if (level < 0 || level >= TRACK_RGB_LEVELS || which < 0 || which > 2) {
-        g_err = std::string(fn) + ": level outside 0..5 or which outside 0..2";
-        return SM_E_ARG;
-    }
-    if (const char *why = track_rgb_check(s, p, q)) { g_err = std::string(fn) + ": " + why; return SM_E_ARG; }
-    int rc = track_check(s, fn);
-    if (rc) return rc;
-    HIPCK(hipSetDevice(s->cfg.device));
-    if ((rc = pull_state(s))) return rc;
-    if ((rc = track_alloc(s)) || (rc = track_rgb_alloc(s))) return rc;
-    const TrackRgbParams rp = track_rgb_params(s, q);
-    const TrackParams tpl = track_level_params(s, p, level);
-    if ((rc = track_rgb_prepare(s, rgb, depth_mm, tpl, rp, pose16_eval, pose16_eval, false, level, win))) return rc;   // (the pose as given)
-    if ((rc = track_rgb_iteration(s, tpl, rp, level, 1))) return rc;
-    if (pred_slot) HIPCK(hipMemcpyAsync(pred_slot, s->trk.d_pred, (size_t)s->P * 4, hipMemcpyDeviceToHost, s->stream));
-    HIPCK(hipMemcpyAsync(s->trk.h_state, s->trk.d_state, sizeof(TrackState), hipMemcpyDeviceToHost, s->stream));
-    HIPCK(hipMemcpyAsync(s->trk.h_rstate, s->trk.d_rstate, sizeof(TrackRgbState), hipMemcpyDeviceToHost, s->stream));
-    HIPCK(hipStreamSynchronize(s->stream));
-    const double *src = which == 0 ? s->trk.h_state->sys : which == 1 ? s->trk.h_rstate->sys_icp : s->trk.h_rstate->sys_rgb;
-    if (sys29) memcpy(sys29, src, TRACK_NSYS * sizeof(double));
-    return SM_OK;
-}
-
-int sm_track_rgb_debug(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *pose16_eval, int level, int which,
-                       double *sys29)
-{
-    return track_rgb_debug(s, rgb, depth_mm, pose16_eval, level, which, nullptr, nullptr, sys29, "sm_track_rgb_debug");
-}
-
-int sm_track_rgb_debug_window(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *pose16_eval, int level, int which,
-                              int32_t min_time, int32_t max_time, int32_t *pred_slot, double *sys29)
-{
-    const Window win{min_time, max_time};
-    return track_rgb_debug(s, rgb, depth_mm, pose16_eval, level, which, &win, pred_slot, sys29, "sm_track_rgb_debug_window");
-}
-
 // ---- the census of old surfels in view (DESIGN.md "4i. Closing loops unasked") ----
 
 int sm_old_in_view(sm_ctx *s, const float *pose16, int32_t max_time, uint32_t *n)
@@ -669,7 +595,7 @@ int sm_old_in_view(sm_ctx *s, const float *pose16, int32_t max_time, uint32_t *n
     sm_default_track_params(&p);
     TrackParams tp = track_params(s, p);
     double pose[16], inv[16];
-    for (int e = 0; e < 16; ++e) pose[e] = (double)pose16[e];
+    sm_pose::widen(pose16, pose);
     rigid_inv_d(pose, inv);
     for (int e = 0; e < 16; ++e) tp.tinv_prev[e] = (float)inv[e];
     const bool timed = te && te[0] == '1';

@@ -10,6 +10,7 @@
 // with, the file still holds the unwarped world, and an operator finishes the job with one mv "<path>.warp.tmp" "<path>".
 #include "sm_map_stream.h"
 #include "sm_k_warp.h"
+#include "sm_pose.h"
 
 #include <cstdlib>
 
@@ -200,7 +201,7 @@ int warp_model(sm_ctx *s, const WarpArgs &wa, int32_t t0, uint32_t n, const floa
 int check_args(sm_ctx *s, const sm_map_source *src, uint32_t n, const float *corr12, const char *who)
 {
     if (!s || !src || !corr12) { g_err = std::string(who) + ": null context, source or table"; return SM_E_ARG; }
-    if (s->ss_on || s->rig_on) { g_err = std::string(who) + ": a sharded or rig context holds only its own surfels"; return SM_E_UNSUPPORTED; }
+    if (int rc = check_whole_map(s, who)) return rc;
     if (n == 0) { g_err = std::string(who) + ": an empty table"; return SM_E_ARG; }
     for (size_t i = 0; i < (size_t)n * 12; ++i)
         if (!std::isfinite(corr12[i])) { g_err = std::string(who) + ": non-finite table entry"; return SM_E_ARG; }
@@ -352,22 +353,19 @@ int sm_impl::check_loop_params(const sm_loop_params &p, const char *who)
     return SM_OK;
 }
 
-namespace {
-// sm_close_loop (rgb null: the depth-only measurement) and sm_close_loop_rgb; search: sm_close_loop_search, whose step 1 is
-// sm_search_pose with sp (null: its defaults)
-int close_loop(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *pose16, const sm_map_source *src,
-               const sm_track_params *tp, const sm_track_rgb_params *rp, const sm_loop_params *lp, bool search, const sm_search_params *sp,
-               float *pose16_out, sm_loop_info *info, const char *who)
+int sm_impl::close_loop(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *pose16, const sm_map_source *src,
+                        const sm_track_params *tp, const sm_track_rgb_params *rp, const sm_loop_params *lp, bool search,
+                        const sm_search_params *sp, float *pose16_out, sm_loop_info *info, const char *who)
 {
     if (!s || !depth_mm || !pose16 || !src || !pose16_out || !info) { g_err = std::string(who) + ": null argument"; return SM_E_ARG; }
-    if (s->ss_on || s->rig_on) { g_err = std::string(who) + ": a sharded or rig context holds only its own surfels"; return SM_E_UNSUPPORTED; }
+    int rc;
+    if ((rc = check_whole_map(s, who))) return rc;
     sm_loop_params p;
     if (lp) p = *lp;
     else sm_default_loop_params(&s->cfg, &p);
-    int rc;
     if ((rc = check_loop_params(p, who)) || (rc = check_pose(pose16, who)) || (rc = check_map_source(src, who))) return rc;
     memset(info, 0, sizeof *info);
-    for (int e = 0; e < 16; ++e) info->D[e] = (e % 5 == 0) ? 1.0f : 0.0f;
+    sm_pose::identity(info->D);
     info->t_a = info->t_b = -1;
     memcpy(pose16_out, pose16, 64);
     const int64_t mt = (int64_t)s->tick - 1 - p.min_age;
@@ -380,23 +378,20 @@ int close_loop(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const fl
         info->track.status = si.status;
         anchor = si.anchor_time;
     }
-    else if (rgb) rc = sm_track_frame_rgb_window(s, rgb, depth_mm, pose16, tp, rp, INT32_MIN, max_time, t_old, &info->track, nullptr, &anchor);
-    else rc = sm_track_frame_old(s, depth_mm, pose16, tp, max_time, t_old, &info->track, &anchor);
-    if (rc) return rc;
+    else {
+        const TrackWindow old{INT32_MIN, max_time};
+        if ((rc = track_windowed(s, rgb, depth_mm, pose16, tp, rp, &old, t_old, &info->track, nullptr, &anchor,
+                                 rgb ? "sm_track_frame_rgb_window" : "sm_track_frame_old")))
+            return rc;
+    }
     if (info->track.status == SM_TRACK_NO_MODEL) { info->status = SM_LOOP_NO_OLD_MAP; return SM_OK; }
     if (info->track.status != SM_TRACK_OK) { info->status = SM_LOOP_TRACK_FAILED; return SM_OK; }
-    // D = T_old * pose16^-1, the inverse taken as a rigid pose's: each element ((a0*b0 + a1*b1) + a2*b2) (+ a3 in the last column)
-    double inv[16], D[16];
-    for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) inv[c * 4 + r] = (double)pose16[r * 4 + c];
-        inv[12 + r] = -(((double)pose16[r * 4] * (double)pose16[12] + (double)pose16[r * 4 + 1] * (double)pose16[13]) + (double)pose16[r * 4 + 2] * (double)pose16[14]);
-    }
-    inv[3] = inv[7] = inv[11] = 0.0; inv[15] = 1.0;
-    for (int c = 0; c < 4; ++c) {
-        for (int r = 0; r < 3; ++r)
-            D[c * 4 + r] = (((double)t_old[r] * inv[c * 4] + (double)t_old[4 + r] * inv[c * 4 + 1]) + (double)t_old[8 + r] * inv[c * 4 + 2]) + (c == 3 ? (double)t_old[12 + r] : 0.0);
-        D[c * 4 + 3] = c == 3 ? 1.0 : 0.0;
-    }
+    // D = T_old * pose16^-1, the inverse taken as a rigid pose's
+    double pose[16], told[16], inv[16], D[16];
+    sm_pose::widen(pose16, pose);
+    sm_pose::widen(t_old, told);
+    sm_pose::rigid_inv_d(pose, inv);
+    sm_pose::mul_rigid_d(told, inv, D);
     for (int e = 0; e < 16; ++e) info->D[e] = (float)D[e];
     Rot R;
     for (int i = 0; i < 3; ++i)
@@ -416,6 +411,7 @@ int close_loop(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const fl
     // Row 0, the identity, is not applied: the warp starts at t_a + 1 with the table from row 1 on.  The rows are the same for every
     // surfel newer than the anchor, and the old world keeps its BITS (1*x + 0*y + 0*z turns a -0.0 into +0.0, and fused normals hold many).
     if ((rc = warp(s, &all, t_a + 1, n - 1u, table.data() + 12, who))) return rc;
+    // the corrected pose D * pose16, written out: it multiplies by the pose's own fourth row, which sm_pose.h's rigid product takes as (0, 0, 0, 1)
     for (int c = 0; c < 4; ++c)
         for (int r = 0; r < 3; ++r)
             pose16_out[c * 4 + r] = (float)((((double)info->D[r] * (double)pose16[c * 4] + (double)info->D[4 + r] * (double)pose16[c * 4 + 1]) +
@@ -425,7 +421,6 @@ int close_loop(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const fl
     info->t_b = t_b;
     return SM_OK;
 }
-}  // namespace
 
 extern "C" {
 

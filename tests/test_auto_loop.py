@@ -310,6 +310,37 @@ def test_window_equalities(frames, old_map):     # noqa: F811
     assert_models_equal(m.download_model(), model, "tracking changes nothing")
 
 
+@pytest.mark.gpu
+def test_every_instantiation_of_the_splat_matches_the_restatement():
+    """The prediction's splat is one kernel with a compile-time gate per end of the window.  Its four instantiations against the
+    restatement on the census test's hand-made rows (2500 of them: a tail block and a partial wave), whose times lie around 40
+    and hold NaNs: a NaN passes an open end and fails a closed one."""
+    pose = np.eye(4, dtype=f32)
+    model = _census_rows(2500, 40, np.eye(4))
+    times = model[:, 7]
+    frame = rr.sequence(1)[0]
+    g = _gpu(200)
+    g.process_frame(frame[0], frame[1], frame[2], pose)         # the prediction camera: the identity
+    g.upload_model(model)                                       # slots = rows
+    g.set_tick(60)
+    occupied, nans = [], []
+    for lo, hi in ((IMIN, IMAX), (IMIN, 40), (39, IMAX), (38, 40), (40, 40)):
+        want = tr.predict(model, pose, CAM, live=lar.in_window(times, lo, hi))
+        pred, _ = g.track_debug_window(frame[1], pose, lo, hi)
+        occupied.append(int((want >= 0).sum()))
+        nans.append(int(np.isnan(times[want[want >= 0]]).sum()))
+        print(f"window ({lo}, {hi}]: {int((pred >= 0).sum())} pixels occupied (restatement {occupied[-1]}, {nans[-1]} by NaN-time slots), "
+              f"{int((pred != want).sum())} differ")
+        assert np.array_equal(pred, want), (lo, hi)
+    assert np.all(pred == -1)                                   # (40, 40]: nothing
+    # the scene tells the five apart, and NaN times are in the prediction exactly where no end is compared (the figures: the
+    # restatement's, worked out without a GPU)
+    assert occupied == [1034, 415, 694, 210, 0] and nans[0] == 64
+    assert 0 == occupied[4] < occupied[3] < occupied[1] < occupied[2] < occupied[0]
+    assert nans[0] > 0 and nans[1:] == [0, 0, 0, 0]
+    assert_models_equal(g.download_model(), model, "tracking changes nothing")
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # 3. colour closes where depth cannot
 # ---------------------------------------------------------------------------------------------------------------------

@@ -25,7 +25,7 @@ def colmajor(m):
 
 
 def rigid_inv_d(m16):
-    """[R^T | -R^T t] of a column-major pose in double (sm_track.hip rigid_inv_d)"""
+    """[R^T | -R^T t] of a column-major pose in double (sm_pose.h rigid_inv_d)"""
     m = np.asarray(m16, np.float64)
     o = np.zeros(16)
     for r in range(3):
@@ -34,6 +34,33 @@ def rigid_inv_d(m16):
         o[12 + r] = -((m[r * 4 + 0] * m[12] + m[r * 4 + 1] * m[13]) + m[r * 4 + 2] * m[14])
     o[15] = 1.0
     return o
+
+
+def mul_rigid_d(a16, b16):
+    """the rigid product a * b of column-major poses in double (sm_pose.h mul_rigid_d): ((a0*b0 + a1*b1) + a2*b2), + a's
+    translation in the last column"""
+    a, b = np.asarray(a16, np.float64), np.asarray(b16, np.float64)
+    o = np.zeros(16)
+    for c in range(4):
+        for r in range(3):
+            o[c * 4 + r] = ((a[r] * b[c * 4] + a[4 + r] * b[c * 4 + 1]) + a[8 + r] * b[c * 4 + 2]) + (a[12 + r] if c == 3 else 0.0)
+    o[15] = 1.0
+    return o
+
+
+def orthonormalize_d(m16):
+    """the rotation of a column-major pose made orthonormal in double (sm_pose.h orthonormalize_d): Gram-Schmidt on columns 0
+    and 1, column 2 = 0 x 1; every sum left to right"""
+    m = np.array(m16, np.float64)
+    a, b = m[0:3].copy(), m[4:7].copy()
+    a = a / math.sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2])
+    ab = (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
+    b = b - ab * a
+    b = b / math.sqrt((b[0] * b[0] + b[1] * b[1]) + b[2] * b[2])
+    m[0:3], m[4:7], m[8:11] = a, b, _cross(a, b)
+    m[3] = m[7] = m[11] = 0.0
+    m[15] = 1.0
+    return m
 
 
 def _xform(m, x, y, z):

@@ -749,6 +749,68 @@ int sm_close_loop_search(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm
                          float *pose16_out, sm_loop_info *info);
 int sm_set_auto_loop_search(sm_ctx *s, const sm_search_params *sp);
 
+/* ---- lidar sweeps (DESIGN.md "4k. Lidar sweeps") ----
+ * What a spinning lidar at a pose would measure in the map: every beam of a spherical grid against every live surfel as an oriented
+ * disc, the nearest return per beam.  The renderers above are pinhole rasterisers and return no range; this is the second sensor.
+ * Sensor.  n_el rows x n_az columns.  The sensor frame is the camera's (x right, y down, z forward); pose16 is sensor->world,
+ *   column-major.  Azimuth runs from +z towards +x, elevation is positive upwards.
+ * Directions.  Beam (row i, column j): a = (az0_deg + j*az_step_deg) * pi/180, e = el_deg[i] * pi/180, pi = 3.14159265358979323846,
+ *   d = (sin a cos e, -sin e, cos a cos e), in double from the widened floats, each component rounded to float once.
+ *   sm_lidar_directions (host only, no context) writes the table, n_el * n_az * 3 floats, row-major; the sweep uses exactly it.
+ * Surfel in the sensor frame.  tinv = [R^T | -R^T t] of pose16 in double, rounded to float.  c = tinv * centre by sm_old_in_view's
+ *   rule, each row ((m[r]*x + m[r+4]*y) + m[r+8]*z) + m[r+12]; m = the rotation rows of tinv applied to the stored normal in the same
+ *   order, (m[r]*x + m[r+4]*y) + m[r+8]*z, not normalised; r = the stored radius.  Everything fp32, no contraction, as written.
+ * Hit.  For a beam d and a surfel (c, m, r):
+ *     den = (m.x*d.x + m.y*d.y) + m.z*d.z        num = (m.x*c.x + m.y*c.y) + m.z*c.z        t = num / den        q_i = t*d_i - c_i
+ *     hit = t >= min_range && t <= max_range && ((q.x*q.x + q.y*q.y) + q.z*q.z) <= r*r
+ *   Every comparison is false on a NaN; a grazing beam (den == 0) gives an infinity or a NaN and no hit: no epsilon.  Discs are
+ *   two-sided.  The beam's return is the hitting surfel with the smallest t, ties to the lower id (t > 0: its float bits order).
+ * Which surfels, which ids.  The live ones (alive bit set) with conf >= min_conf (false on a NaN).  Ids are the rows of
+ *   sm_download_model_aos, exactly as sm_render_model's id plane; the same forced compaction on read-back is the only side effect.
+ * Outputs, row-major n_el x n_az (per sweep); any but `range` may be NULL:
+ *     range  float   t                                                            empty: 0
+ *     id     int32   surfel id                                                    empty: -1
+ *     rgb    3 x u8  bytes >>16, >>8, >>0 of the surfel's colour word             empty: 0
+ *     sem    u8      class + 1, as sm_render_image's                              empty: 0
+ * The calls are synchronous and wait for frames in flight; the model, the counters, the tick, the frame log and the tracker
+ *   state are untouched.
+ * sm_lidar_sweep_maps is sm_render_image_maps rule for rule: the global id is the position in the concatenation (files in order,
+ *   then the live model); every output equals sm_lidar_sweep of a context holding that concatenation, bit for bit; the result
+ *   depends neither on the chunking nor on the sweeps per pass; all headers are checked first and a bad file gives SM_E_ARG with the
+ *   outputs unwritten; more than 2^31 - 1 surfels: SM_E_CAPACITY; n_sweeps == 0 checks the set only.  poses16: n_sweeps poses,
+ *   outputs n_sweeps planes each.  A pass sweeps as many poses as fit the key budget (1 GiB of 8-byte keys; SM_LIDAR_KEY_MB
+ *   overrides it).  SM_LIDAR_NO_CULL=1 turns the per-block range test off and SM_LIDAR_LANE_BEAMS sets the beams a lane tests by
+ *   itself (A/B switches: the outputs are the same either way).
+ * sm_lidar_stats: what the last sweep call of the context did (SM_E_ARG before the first).
+ * Errors.  SM_E_ARG: a NULL ctx, sensor, pose or range; a sensor outside the limits in the struct below (non-increasing elevations
+ *   included); a non-finite pose; a call between sm_stage_conflict and sm_stage_cull; the file errors of sm_render_image_maps.
+ *   SM_E_UNSUPPORTED: a sharded or rig context. */
+typedef struct sm_lidar_sensor {
+    int32_t n_az, n_el;            /* columns, rows; n_az * n_el <= 2^22 */
+    float az0_deg, az_step_deg;    /* column j looks at azimuth az0 + j*step; step > 0; n_az*step <= 360 */
+    const float *el_deg;           /* n_el elevations, strictly increasing, each inside (-90, 90) */
+    float min_range, max_range;    /* metres, 0 < min_range <= max_range, finite */
+    float min_conf;                /* a surfel takes part iff conf >= min_conf (false on a NaN); default 0 */
+} sm_lidar_sensor;
+typedef struct sm_lidar_stats_t {
+    uint64_t surfels;              /* offered: live slots and records read, once per pass and source */
+    uint64_t tests;                /* exact tests made */
+    uint64_t wide;                 /* (surfel, sweep) pairs whose footprint went to a whole wave */
+    uint64_t blocks_skipped;       /* (block of 256 records, sweep) pairs the range test skipped */
+    uint32_t chunks, passes;       /* chunks (at most 2^20 records) copied to the device; passes over the files */
+    float read_ms, copy_ms;        /* in fread; in the host-to-device copies (events) */
+    float device_ms;               /* in the kernels (events) */
+    float total_ms;                /* the whole call (host clock) */
+} sm_lidar_stats_t;
+#define SM_LIDAR_MAX_BEAMS (1u << 22)
+/* 360 x 16 at 1 deg from az0 = 0, el = -15..0 step 1 (a static table), 1..60 m, min_conf 0 */
+int sm_default_lidar_sensor(sm_lidar_sensor *p);
+int sm_lidar_directions(const sm_lidar_sensor *sn, float *dir3);
+int sm_lidar_sweep(sm_ctx *s, const sm_lidar_sensor *sn, const float *pose16, float *range, int32_t *id, uint8_t *rgb, uint8_t *sem);
+int sm_lidar_sweep_maps(sm_ctx *s, const sm_map_source *src, const sm_lidar_sensor *sn, const float *poses16, uint32_t n_sweeps,
+                        float *range, int32_t *id, uint8_t *rgb, uint8_t *sem);
+int sm_lidar_stats(sm_ctx *s, sm_lidar_stats_t *out);
+
 /* ---- per-pass entry points (GlobalModel / IndexMap methods), synchronous ---- */
 /* Upload RGB / metric depth / semantic textures directly (bypasses p0). */
 int sm_set_frame(sm_ctx *s, const uint8_t *rgb, const float *depth_metric,

@@ -40,6 +40,7 @@ SYMBOLS = (
     "sm_track_frame_window", "sm_track_debug_window", "sm_track_frame_rgb_window", "sm_track_rgb_debug_window", "sm_close_loop_rgb",
     "sm_old_in_view", "sm_default_auto_loop_params", "sm_set_auto_loop", "sm_auto_loop_stats",
     "sm_default_search_params", "sm_score_poses_window", "sm_search_pose", "sm_close_loop_search", "sm_set_auto_loop_search",
+    "sm_default_lidar_sensor", "sm_lidar_directions", "sm_lidar_sweep", "sm_lidar_sweep_maps", "sm_lidar_stats",
 )
 
 SM_COLL_SUM, SM_COLL_MIN, SM_COLL_GATHER = 0, 1, 2
@@ -117,6 +118,65 @@ def map_source(paths, include_model=True) -> SmMapSource:
     src = SmMapSource(C.cast(arr, C.POINTER(C.c_char_p)), len(enc), int(bool(include_model)))
     src._keep = (enc, arr)
     return src
+
+
+class SmLidarSensor(C.Structure):
+    _fields_ = [("n_az", C.c_int32), ("n_el", C.c_int32), ("az0_deg", C.c_float), ("az_step_deg", C.c_float),
+                ("el_deg", C.POINTER(C.c_float)), ("min_range", C.c_float), ("max_range", C.c_float), ("min_conf", C.c_float)]
+
+
+class SmLidarStats(C.Structure):
+    _fields_ = [("surfels", C.c_uint64), ("tests", C.c_uint64), ("wide", C.c_uint64), ("blocks_skipped", C.c_uint64),
+                ("chunks", C.c_uint32), ("passes", C.c_uint32), ("read_ms", C.c_float), ("copy_ms", C.c_float),
+                ("device_ms", C.c_float), ("total_ms", C.c_float)]
+
+
+LIDAR_MAX_BEAMS = 1 << 22
+
+
+def lidar_sensor(**over) -> SmLidarSensor:
+    """sm_default_lidar_sensor with fields replaced: n_az, n_el, az0_deg, az_step_deg, el_deg (a sequence of n_el elevations; giving
+    it sets n_el unless that is given too), min_range, max_range, min_conf.  Keeps the elevation array alive."""
+    p = SmLidarSensor()
+    load().sm_default_lidar_sensor(C.byref(p))
+    el = over.pop("el_deg", None)
+    if el is None:
+        el = np.array([p.el_deg[i] for i in range(p.n_el)], np.float32)
+    el = np.ascontiguousarray(el, np.float32).reshape(-1)
+    p.n_el = len(el)
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise KeyError(k)
+        setattr(p, k, v)
+    p.el_deg = el.ctypes.data_as(C.POINTER(C.c_float))
+    p._keep = el
+    return p
+
+
+def lidar_directions(sensor) -> np.ndarray:
+    """the sensor's beam directions in its own frame (sm_lidar_directions): float32[n_el][n_az][3]"""
+    d = np.zeros((max(sensor.n_el, 0), max(sensor.n_az, 0), 3), np.float32)
+    rc = load().sm_lidar_directions(C.byref(sensor), _ptr(d))
+    if rc:
+        raise SurfelMapError("sm_lidar_directions", rc, load().sm_last_error().decode())
+    return d
+
+
+def lidar_points(range, dirs, rgb=None) -> np.ndarray:
+    """the returns of a sweep as KITTI velodyne points: float32[N][4] = (z, -x, -y) of t*d in the sensor frame (x forward, y left,
+    z up) and the reflectance -- the luminance of rgb by the colour tracker's weights, ((0.299 r + 0.587 g) + 0.114 b) / 255 in
+    float32, or 0 without rgb.  Beams without a return (range 0) are left out; the order is the grid's, row-major."""
+    f32 = np.float32
+    t = np.ascontiguousarray(range, f32).reshape(-1)
+    d = np.ascontiguousarray(dirs, f32).reshape(-1, 3)
+    got = t > 0
+    p = t[got, None] * d[got]
+    out = np.zeros((int(got.sum()), 4), f32)
+    out[:, 0], out[:, 1], out[:, 2] = p[:, 2], -p[:, 0], -p[:, 1]
+    if rgb is not None:
+        c = np.ascontiguousarray(rgb, np.uint8).reshape(-1, 3)[got].astype(f32)
+        out[:, 3] = ((f32(0.299) * c[:, 0] + f32(0.587) * c[:, 1]) + f32(0.114) * c[:, 2]) / f32(255.0)
+    return out
 
 
 SM_TRACK_OK, SM_TRACK_LOST, SM_TRACK_DEGENERATE, SM_TRACK_NO_MODEL = 0, 1, 2, 3
@@ -357,6 +417,11 @@ def model_view(mvp, mv_inv, w, h, threshold=0.0, color_type=0, unstable=True, po
     return v
 
 
+def _lidar_planes(shape) -> dict:
+    return dict(range=np.zeros(shape, np.float32), id=np.zeros(shape, np.int32), rgb=np.zeros(tuple(shape) + (3,), np.uint8),
+                sem=np.zeros(shape, np.uint8))
+
+
 class SurfelMapError(RuntimeError):
     def __init__(self, what, rc, detail=""):
         super().__init__(f"{what} failed: rc={rc} {detail}".strip())
@@ -542,6 +607,12 @@ def load():
     L.sm_search_pose.argtypes = [vp, vp, vp, vp, tpp, rpp, spp, i32, i32, vp, C.POINTER(SmSearchInfo)]
     L.sm_close_loop_search.argtypes = [vp, vp, vp, vp, C.POINTER(SmMapSource), tpp, rpp, lpp, spp, vp, C.POINTER(SmLoopInfo)]
     L.sm_set_auto_loop_search.argtypes = [vp, spp]
+    lsp = C.POINTER(SmLidarSensor)
+    L.sm_default_lidar_sensor.argtypes = [lsp]
+    L.sm_lidar_directions.argtypes = [lsp, vp]
+    L.sm_lidar_sweep.argtypes = [vp, lsp, vp, vp, vp, vp, vp]
+    L.sm_lidar_sweep_maps.argtypes = [vp, C.POINTER(SmMapSource), lsp, vp, C.c_uint32, vp, vp, vp, vp]
+    L.sm_lidar_stats.argtypes = [vp, C.POINTER(SmLidarStats)]
     for name in SYMBOLS:
         getattr(L, name)          # AttributeError here = the library does not match the header
     _lib = L
@@ -1174,6 +1245,37 @@ class SurfelMap:
         st = SmMapsStats()
         self._chk(self._L.sm_render_maps_stats(self._h, C.byref(st)), "sm_render_maps_stats")
         return {k: getattr(st, k) for k, _ in SmMapsStats._fields_}
+
+    # -- lidar sweeps (sm_lidar_sweep, sm_lidar_sweep_maps)
+    def lidar_sweep(self, pose, sensor=None) -> dict:
+        """What a lidar at `pose` (sensor->world, float32[16] column-major or 4x4) measures in the live model: a dict of
+        range float32[n_el][n_az] (0 = no return), id int32 (row of download_model(), -1), rgb uint8[..][3], sem uint8 (class + 1,
+        0).  sensor: lidar_sensor(...); None = the default."""
+        sensor = lidar_sensor() if sensor is None else sensor
+        pose = _mat16(pose)
+        out = _lidar_planes((sensor.n_el, sensor.n_az))
+        self._chk(self._L.sm_lidar_sweep(self._h, C.byref(sensor), _ptr(pose), *[_ptr(out[k]) for k in ("range", "id", "rgb", "sem")]),
+                  "sm_lidar_sweep")
+        return out
+
+    def lidar_sweep_maps(self, paths, poses, sensor=None, include_model=True) -> dict:
+        """lidar_sweep of a map set (see render_image_maps) from every pose of `poses` (float32[V][16]): the same dict with a
+        leading axis V; ids are positions in the concatenation."""
+        sensor = lidar_sensor() if sensor is None else sensor
+        poses = np.ascontiguousarray(poses, np.float32).reshape(-1, 16)
+        V = poses.shape[0]
+        out = _lidar_planes((V, sensor.n_el, sensor.n_az))
+        src = map_source(paths, include_model)
+        self._chk(self._L.sm_lidar_sweep_maps(self._h, C.byref(src), C.byref(sensor), _ptr(poses), V,
+                                              *[_ptr(out[k]) for k in ("range", "id", "rgb", "sem")]), "sm_lidar_sweep_maps")
+        return out
+
+    def lidar_stats(self) -> dict:
+        """of the last lidar_sweep* call: surfels offered, exact tests, wide (surfel, sweep) pairs, blocks_skipped, chunks, passes,
+        read_ms, copy_ms, device_ms, total_ms"""
+        st = SmLidarStats()
+        self._chk(self._L.sm_lidar_stats(self._h, C.byref(st)), "sm_lidar_stats")
+        return {k: getattr(st, k) for k, _ in SmLidarStats._fields_}
 
     # -- per-pass entry points
     def set_frame(self, rgb=None, depth_metric=None, sem=None):

@@ -219,6 +219,21 @@ public:
     }
     const std::vector<unsigned char> &modelImageRGBA() const { return modelImage_; }
 
+    // What a lidar `sensor` at `pose` (sensor->world, the camera's axes) measures in the model (sm_lidar_sweep): per beam of the
+    // n_el x n_az grid, row-major, the range (0: no return), the surfel's id (-1), its colour bytes and its class + 1 (0).
+    struct LidarReturns { std::vector<float> range; std::vector<int32_t> id; std::vector<unsigned char> rgb, sem; };
+    bool lidarSweep(const Eigen::Matrix4f &pose, const sm_lidar_sensor &sensor, LidarReturns &out)
+    {
+        const size_t nb = (size_t)(sensor.n_az > 0 ? sensor.n_az : 0) * (size_t)(sensor.n_el > 0 ? sensor.n_el : 0);
+        out.range.assign(nb, 0.0f); out.id.assign(nb, -1); out.rgb.assign(nb * 3, 0); out.sem.assign(nb, 0);
+        (void)sm_sync(ctx_);                                             // (SM_FACADE_ASYNC: frames may still be in flight)
+        if (sm_lidar_sweep(ctx_, &sensor, pose.data(), out.range.data(), out.id.data(), out.rgb.data(), out.sem.data()) != SM_OK) {
+            std::printf("lidarSweep: %s\n", sm_last_error());
+            return false;
+        }
+        return true;
+    }
+
     // The model-aligned mirror textures (src/GlobalModel.cpp:639-681) do not exist in the compute core.  GUI::drawCapacity
     // (build_map.cpp:204) shows the fill level of the TEXTURE_DIMENSION^2 normal/radius mirror: the handle is filled lazily --
     // size TEXTURE_DIMENSION x TEXTURE_DIMENSION, and (without GL) the host copy of the plane for whoever wants to look.

@@ -229,6 +229,58 @@ public:
         return ok;
     }
 
+    // The second sensor's dump: what a lidar `sensor` (sm_lidar_sensor; sm_default_lidar_sensor) at each of `poses` (sensor->world,
+    // the camera's axes) measures in the live model, written as <path>/velodyne/%06d.bin next to acquireImages' folders, in KITTI's
+    // velodyne layout: per return four floats, (z, -x, -y) of t*d in the sensor frame -- x forward, y left, z up -- and the
+    // reflectance, the luminance ((0.299 r + 0.587 g) + 0.114 b) / 255 of the surfel's colour.  Beams without a return are left out.
+    bool acquireSweeps(std::string path, const std::vector<Eigen::Matrix4f> &poses, const sm_lidar_sensor &sensor, int startId = 0)
+    {
+        return acquireSweeps(path, {}, poses, sensor, startId, true);
+    }
+    // The same dump of a map set (sm_lidar_sweep_maps): the map files in that order, then -- includeModel -- the live model, streamed.
+    bool acquireSweeps(std::string path, const std::vector<std::string> &mapFiles, const std::vector<Eigen::Matrix4f> &poses,
+                       const sm_lidar_sensor &sensor, int startId = 0, bool includeModel = true)
+    {
+        if (path.empty() || path.back() != '/') path += "/";
+        const std::string velo_path = path + "velodyne/";
+        ::mkdir(velo_path.c_str(), 0755);
+        if (sensor.n_az <= 0 || sensor.n_el <= 0 || (unsigned long long)sensor.n_az * (unsigned long long)sensor.n_el > SM_LIDAR_MAX_BEAMS) return false;
+        const size_t nb = (size_t)sensor.n_az * sensor.n_el;
+        std::vector<float> p16(poses.size() * 16), dir(nb * 3), range(poses.size() * nb);
+        for (size_t i = 0; i < poses.size(); ++i) std::memcpy(&p16[i * 16], poses[i].data(), 64);
+        std::vector<unsigned char> rgb(poses.size() * nb * 3);
+        std::vector<const char *> paths;
+        for (const std::string &f : mapFiles) paths.push_back(f.c_str());
+        const sm_map_source src{paths.data(), (uint32_t)paths.size(), includeModel ? 1 : 0};
+        (void)sm_sync(ctx_);                                             // (SM_FACADE_ASYNC: frames may still be in flight)
+        if (sm_lidar_directions(&sensor, dir.data()) != SM_OK ||
+            sm_lidar_sweep_maps(ctx_, &src, &sensor, p16.data(), (uint32_t)poses.size(), range.data(), nullptr, rgb.data(), nullptr) != SM_OK) {
+            std::printf("acquireSweeps: %s\n", sm_last_error());
+            return false;
+        }
+        bool ok = true;
+        std::vector<float> pts;
+        for (size_t i = 0; i < poses.size(); ++i, ++startId) {
+            char name[32];
+            std::snprintf(name, sizeof name, "%06d.bin", startId);
+            pts.clear();
+            for (size_t b = 0; b < nb; ++b) {
+                const float t = range[i * nb + b];
+                if (!(t > 0.0f)) continue;
+                const unsigned char *c = &rgb[(i * nb + b) * 3];
+                const float x = t * dir[3 * b], y = t * dir[3 * b + 1], z = t * dir[3 * b + 2];
+                const float lum = 0.299f * (float)c[0] + 0.587f * (float)c[1];
+                pts.push_back(z); pts.push_back(-x); pts.push_back(-y);
+                pts.push_back((lum + 0.114f * (float)c[2]) / 255.0f);
+            }
+            FILE *f = std::fopen((velo_path + name).c_str(), "wb");
+            const bool w = f && std::fwrite(pts.data(), 4, pts.size(), f) == pts.size();
+            if (f && std::fclose(f) != 0) ok = false;
+            if (!w) { std::printf("%s is NOT saved!\n", name); ok = false; }
+        }
+        return ok;
+    }
+
     // extras of the HIP core
     sm_ctx *context() { return ctx_; }
     // The replacement of the operator's save / reset buttons (build_map.cpp:235-263) for a headless run: after every `every`-th

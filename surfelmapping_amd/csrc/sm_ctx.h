@@ -13,6 +13,7 @@
 //   sm_recall.hip    paging in (sm_recall*, sm_set_auto_recall): records of map files near the camera back into the model
 //   sm_warp.hip      closing loops (sm_warp_by_time, sm_loop_spread): the model and map files warped by surfel time
 //   sm_search.hip    pose search before the tracker (sm_score_poses_window, sm_search_pose)
+//   sm_lidar.hip     lidar sweeps (sm_lidar_*): beams against the live model and against streamed map files
 // and, beside it, for everything that touches a map file: sm_mapfile.h (the format: checked open, writer, chunk plan; host only)
 // and sm_map_stream.h (the double-buffered chunk stream of sm_render_maps.hip and sm_recall.hip); for the occupied slots and the
 // compaction schedule: sm_slots.h (SlotSchedule; host only); for the arithmetic of rigid poses in double: sm_pose.h (host only,
@@ -222,6 +223,19 @@ struct Search {
     Dev<uint32_t> d_scores;
     size_t cand_cap = 0;
     Event ev[2];                       // around the scoring kernels
+};
+
+// lidar sweeps (sm_lidar.hip, sm_k_lidar.h): the last sensor's tables on the device, the per-sweep poses, the device tally and
+// the last call's.  Keys and output planes live in the export scratch; the files stream through RenderMaps' staging.
+struct Lidar {
+    Dev<float> d_dir, d_el;            // the direction table (n_el * n_az * 3) and the elevations in radians
+    std::vector<float> key;            // what the tables on the device were made of: n_az, n_el, az0, step, the elevations
+    Dev<uint8_t> d_poses;              // LidarPose per sweep
+    size_t pose_cap = 0;
+    Dev<uint8_t> d_tally;              // LidarTally
+    Event ev[2];                       // around the live model's kernels
+    sm_lidar_stats_t stats{};
+    bool stats_valid = false;
 };
 
 // closing loops unasked (sm_loop.hip): the policy of sm_set_auto_loop and its tally
@@ -454,6 +468,7 @@ struct sm_ctx {
     Warp warp;
     AutoLoop aloop;
     Search srch;
+    Lidar lid;
     // host frame state (src/SurfelMapping.h:100-103)
     int tick = 0;
     bool ref_set = false;
@@ -512,6 +527,8 @@ int view_splat_model(sm_ctx *s, const ViewParams &vp, uint64_t *key, uint32_t *d
 int auto_retire_after_frame(sm_ctx *s);           // the periodic policy: called once a frame is enqueued (one test unless it is due)
 // ---- sm_render_maps.hip ----
 int maps_ensure_staging(sm_ctx *s);               // RenderMaps' copy stream, record buffers and events: whole or absent
+// k_maps_intake on the context's stream: n records at d_rec into RenderMaps' SoA planes and its one box per 256 records
+void maps_intake(sm_ctx *s, const float4 *d_rec, uint32_t n);
 // ---- sm_recall.hip ----
 // the periodic policy: called by a frame that has just retired (one test unless it is on).  wrote_file: this round's retirement
 // wrote the policy's newest file, at this pose -- every row of it is far, so the recall does not read it

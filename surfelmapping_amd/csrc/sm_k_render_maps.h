@@ -7,39 +7,14 @@
 //   k_maps_finish_*      after the last source: pixels nobody won take the clear values
 // Every per-surfel and per-pixel rule is sm_k_draw.h's, shared with the resident kernels: a record drawn here sets the key
 // bits it would set as slot `id` of a model holding the whole set, and the keys are merged by the same atomicMin.
+// The chunk's planes and the box layout are in sm_k_maps_box.h, shared with the lidar sweeps (sm_k_lidar.h).
 #pragma once
 
 #include "sm_device.h"
 #include "sm_k_draw.h"
+#include "sm_k_maps_box.h"
 
 namespace sm {
-
-// a chunk's planes (or the live model's: the resolve reads either)
-struct MapsSoA {
-    float4 *pos_conf, *norm_rad;
-    uint32_t *color;
-    float *time;
-};
-
-constexpr int MAPS_BLOCK = 256;          // records per box = per workgroup of the splat
-
-// One box per block of 256 records: box[2b] = (min x, min y, min z, rmax), box[2b + 1] = (max x, max y, max z, rnorm);
-// rmax = the largest |radius|, rnorm = the largest |radius| * max(1, |normal|) (the model view draws with the stored normal as
-// it is, see maps_reach_view).  A block with a record whose centre, radius or normal is not finite has rnorm = +inf -- a box
-// with a non-finite member is never skipped.
-struct MapsBox { float lx, ly, lz, rmax, hx, hy, hz, rnorm; };
-
-__device__ __forceinline__ MapsBox maps_box_load(const float4 *__restrict__ box, uint32_t b)
-{
-    const float4 lo = box[2 * (size_t)b], hi = box[2 * (size_t)b + 1];
-    return {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-}
-
-__device__ __forceinline__ bool maps_box_finite(const MapsBox &b)
-{
-    const float t = ((b.lx - b.lx) + (b.ly - b.ly)) + ((b.lz - b.lz) + (b.hx - b.hx)) + ((b.hy - b.hy) + (b.hz - b.hz)) + ((b.rmax - b.rmax) + (b.rnorm - b.rnorm));
-    return t == 0.0f;                                    // x - x is 0 for a finite x, NaN otherwise
-}
 
 // The disc's reach from its centre.  Its four vertices are c +- x, c +- y with |x| = |u| * r' * 1.41421356, |u| = 1 up to a few
 // ulps (u is normalised), r' <= |r|, and y = d x x, so |y| <= |d| |x| (1 + a few ulps); 1e-4 covers the roundings (those of

@@ -114,7 +114,7 @@ int render_maps(sm_ctx *s, const sm_map_source *src, const char *fn, const Mode 
             if ((rc = in.next(ck))) return rc;
             const uint32_t n = ck.job->n;
             const unsigned nblk = (n + MAPS_BLOCK - 1) / MAPS_BLOCK;
-            hipLaunchKernelGGL(k_maps_intake, dim3(nblk), dim3(256), 0, s->stream, ck.d_rec, n, chunk, rm.d_box.get());
+            maps_intake(s, ck.d_rec, n);
             HIPCK(hipMemsetAsync(d_hit + v0, 0, b, s->stream));
             const uint32_t gid = (uint32_t)(id_base[ck.job->file] + ck.job->first);
             if (md.image)
@@ -194,6 +194,13 @@ int sm_impl::maps_ensure_staging(sm_ctx *s)
         return rc;
     rm.copy = std::move(copy);                           // last: the staging is whole or absent
     return SM_OK;
+}
+
+void sm_impl::maps_intake(sm_ctx *s, const float4 *d_rec, uint32_t n)
+{
+    RenderMaps &rm = s->maps;
+    const MapsSoA chunk{rm.d_pos_conf, rm.d_norm_rad, rm.d_color, rm.d_time};
+    hipLaunchKernelGGL(k_maps_intake, dim3((n + MAPS_BLOCK - 1) / MAPS_BLOCK), dim3(256), 0, s->stream, d_rec, n, chunk, rm.d_box.get());
 }
 
 extern "C" {

@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define SM_API_VERSION 4   /* bumped whenever a struct or an entry point changes (3, 4: round 3 -- asynchronous host path, rig step, sm_timings::k_scan_own, sm_host_alloc_frame; the staged shard entry points are gone).  Purely additive changes keep it: sm_model_view / sm_render_model*, sm_track_* and sm_track_*rgb* were added at 4, as were sm_warp_by_time / sm_loop_spread / sm_track_*_old / sm_close_loop and sm_track_*_window / sm_close_loop_rgb / sm_old_in_view / sm_*auto_loop*: no existing struct or entry point changed. */
+#define SM_API_VERSION 4   /* bumped whenever a struct or an entry point changes (3, 4: round 3 -- asynchronous host path, rig step, sm_timings::k_scan_own, sm_host_alloc_frame; the staged shard entry points are gone).  Purely additive changes keep it: sm_model_view / sm_render_model*, sm_track_* and sm_track_*rgb* were added at 4, as were sm_warp_by_time / sm_loop_spread / sm_track_*_old / sm_close_loop and sm_track_*_window / sm_close_loop_rgb / sm_old_in_view / sm_*auto_loop*, and sm_fern_* / sm_search_pose_at / sm_close_loop_at / sm_*auto_place*: no existing struct or entry point changed. */
 
 /* error codes (reference: void returns + CheckGlDieOnError(); bool for map IO) */
 enum {
@@ -810,6 +810,124 @@ int sm_lidar_sweep(sm_ctx *s, const sm_lidar_sensor *sn, const float *pose16, fl
 int sm_lidar_sweep_maps(sm_ctx *s, const sm_map_source *src, const sm_lidar_sensor *sn, const float *poses16, uint32_t n_sweeps,
                         float *range, int32_t *id, uint8_t *rgb, uint8_t *sem);
 int sm_lidar_stats(sm_ctx *s, sm_lidar_stats_t *out);
+
+/* ---- place recognition (DESIGN.md "4l. Place recognition") ----
+ * Everything above starts from the believed pose; after more drift than the pose search's box reaches, none of it finds the place
+ * again.  A fern code (Glocker et al., the global loops of ElasticFusion) is a short binary code of a frame, computed from block
+ * means of colour and depth; the codes of keyframes live in a database on the device with their poses and times; a new frame is
+ * matched against all of them, and the matched keyframe's pose is handed to the geometric machinery, which verifies the match.
+ * The table (host only, no context).  sm_fern_params: n_ferns a multiple of 32 in 32..2048, cell one of 4, 8, 16, 32,
+ *   0 <= depth_lo_mm < depth_hi_mm <= 65535.  sm_default_fern_params: 512, 8, seed 1, the config's near and far clip in millimetres
+ *   ((int32)(clip * 1000.0f), clamped to 0..65535).  sm_fern_table writes n_ferns records.  gw = width / cell, gh = height / cell
+ *   (integer division; both must be >= 1; the remainder columns and rows belong to no cell).  The generator is splitmix64 on a
+ *   uint64 state that starts at `seed`; one draw is
+ *       state += 0x9E3779B97F4A7C15;  z = state;  z = (z ^ z>>30) * 0xBF58476D1CE4E5B9;  z = (z ^ z>>27) * 0x94D049BB133111EB;
+ *       z ^= z>>31;  draw(r) = ((z >> 32) * r) >> 32
+ *   and a fern takes six draws in this order: x = draw(gw), y = draw(gh), tr = draw(255), tg = draw(255), tb = draw(255),
+ *   td = depth_lo_mm + draw(depth_hi_mm - depth_lo_mm).
+ * The code.  sm_set_ferns builds the table for the context's image size and creates an empty database; p NULL frees both (the
+ *   default).  Setting it again replaces table and database and switches sm_set_auto_place off.  sm_reset empties the database: the map
+ *   it indexes is gone.
+ *   sm_fern_encode takes host images as sm_track_frame_rgb takes them (rgb H*W*3 u8, R first; depth_mm H*W u16); rgb may be NULL;
+ *   code receives n_ferns / 8 uint32.  sm_fern_encode_device takes images resident in this context's device memory (depth 2-byte
+ *   aligned) and is synchronous too.  The cell of fern f is columns [x*cell, (x+1)*cell) of rows [y*cell, (y+1)*cell).  Its means:
+ *       R, G, B = the sum of the cell^2 bytes of the channel / cell^2                       (integer division)
+ *       D       = the sum of the non-zero depth_mm of the cell / their count                 (integer division, 32 bits; 0 with none)
+ *   of the raw inputs: no stereo border, no clip, no filter.  The fern's nibble: bit 0 = R > tr, bit 1 = G > tg, bit 2 = B > tb,
+ *   bit 3 = D > td; with rgb NULL the three colour bits are 0.  Fern f occupies bits 4*(f&7) .. 4*(f&7)+3 of word f>>3.
+ * The database.  Codes are stored keyframe-major on the device, each with an int32 time; the poses (column-major float[16]) stay
+ *   on the host; the capacity grows geometrically up to SM_FERN_MAX_KEYFRAMES (beyond: SM_E_CAPACITY).  sm_fern_add appends one
+ *   keyframe (index, may be NULL, receives its number); sm_fern_count reports how many there are; sm_fern_download reads them back
+ *   in order (codes count * n_ferns/8 uint32, poses16 count * 16, times count; any pointer may be NULL).
+ *   sm_fern_save writes one file, little-endian, no padding:
+ *       offset 0 u32 magic 0x4E524653 | 4 u32 version 1 | 8 i32 n_ferns | 12 i32 cell | 16 u64 seed | 24 i32 depth_lo_mm |
+ *       28 i32 depth_hi_mm | 32 i32 width | 36 i32 height | 40 u32 count | 44 u32 0 | 48 count records, each
+ *       i32 time | 16 f32 pose | n_ferns/8 u32 code
+ *   through "<path>.tmp" in the same directory, renamed over `path` once complete.  sm_fern_load replaces the database by a file's;
+ *   a file that is missing, whose magic, version, parameters or image size differ from the context's, whose count exceeds
+ *   SM_FERN_MAX_KEYFRAMES or whose length is not exactly 48 + count * (68 + n_ferns/2): SM_E_ARG, sm_last_error() names it, and
+ *   nothing has changed.
+ * The match.  dis(k) = the number of ferns whose nibbles differ between `code` and keyframe k.  Among the keyframes with
+ *   time > min_time && time <= max_time (integer compares) the answer is the smallest dis, ties to the lower index; none in the
+ *   window: index = -1, dis = UINT32_MAX.  dis_all (may be NULL; count entries) receives dis(k) of every keyframe, whatever its time.
+ * A prediction somewhere else.  sm_search_pose_at is sm_search_pose in every rule, except that the prediction camera of the score
+ *   and of the refining trackers is pred16 (camera->world) instead of T_prev; the trackers' guess and history are untouched.  With
+ *   pred16 bit-equal to T_prev it equals sm_search_pose bit for bit, pose and info.  sm_close_loop_at is sm_close_loop_search in
+ *   every rule, except that step 1 is sm_search_pose_at(pred = place16, centre = place16, window (INT32_MIN, tick - 1 - min_age)):
+ *   D = T_old * pose16^-1, and the judgement against lp, the ramp, the warp and pose16_out are as there.  A matched keyframe's pose
+ *   is such a place.
+ * Keyframe poses move with the map.  sm_warp_by_time (with include_model) applies to every stored keyframe pose the rule it applies
+ *   to the context's other stored poses: a keyframe of time T is selected by the row rule with tau = float(T) and becomes C * P, in
+ *   double from the widened floats, rounded once; unselected keyframes keep their bits.
+ * All of these are synchronous, change nothing in the model, its counters, the tick, the frame log or the tracker state (the warp
+ *   aside), and wait for what they need of the stream only.
+ * SM_E_ARG: a NULL argument where none is allowed, parameters outside the rules above, a context without ferns (all but
+ *   sm_set_ferns), a non-finite pose, a call between sm_stage_conflict and sm_stage_cull.
+ *   SM_E_UNSUPPORTED: a sharded or rig context, checked right after the NULL context and before every other argument. */
+typedef struct sm_fern_params {
+    int32_t n_ferns;               /* 512 */
+    int32_t cell;                  /* 8 */
+    uint64_t seed;                 /* 1 */
+    int32_t depth_lo_mm, depth_hi_mm;   /* near_clip, far_clip in millimetres */
+} sm_fern_params;
+typedef struct sm_fern { uint16_t x, y, tr, tg, tb, td; } sm_fern;   /* cell column, cell row, the four thresholds */
+#define SM_FERN_MAX_KEYFRAMES (1u << 20)
+int sm_default_fern_params(const sm_config *c, sm_fern_params *p);
+int sm_fern_table(const sm_fern_params *p, int32_t width, int32_t height, sm_fern *out);
+int sm_set_ferns(sm_ctx *s, const sm_fern_params *p);
+int sm_fern_encode(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, uint32_t *code);
+int sm_fern_encode_device(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_depth_mm, uint32_t *code);
+int sm_fern_add(sm_ctx *s, const uint32_t *code, const float *pose16, int32_t time, uint32_t *index);
+int sm_fern_count(sm_ctx *s, uint32_t *n);
+int sm_fern_download(sm_ctx *s, uint32_t *codes, float *poses16, int32_t *times);
+int sm_fern_save(sm_ctx *s, const char *path);
+int sm_fern_load(sm_ctx *s, const char *path);
+int sm_fern_match(sm_ctx *s, const uint32_t *code, int32_t min_time, int32_t max_time, int32_t *index, uint32_t *dis, uint32_t *dis_all);
+int sm_search_pose_at(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *pred16, const float *centre16,
+                      const sm_track_params *tp, const sm_track_rgb_params *rp, const sm_search_params *sp, int32_t min_time,
+                      int32_t max_time, float *pose16_out, sm_search_info *info);
+int sm_close_loop_at(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *pose16, const float *place16,
+                     const sm_map_source *src, const sm_track_params *tp, const sm_track_rgb_params *rp, const sm_loop_params *lp,
+                     const sm_search_params *sp, float *pose16_out, sm_loop_info *info);
+/* The policy.  sm_set_auto_place needs sm_set_ferns first (SM_E_ARG otherwise; sm_set_ferns(NULL) switches it off with the ferns);
+ * p NULL switches it off (the default); setting it clears its tally and rest_until.  While it is on, sm_track_frame and
+ * sm_track_frame_rgb do the following after their existing work, the policy of sm_set_auto_loop included:
+ *   1. If the track's status is not SM_TRACK_OK, or the auto-loop policy closed a loop on this call: nothing.
+ *   2. The frame is encoded from the tracker's device copies of its images (rgb NULL from sm_track_frame): `encoded` counts.
+ *      T = tick, split = T - 1 - loop.min_age.
+ *   3. One match launch gives the best over all keyframes (dis_any) and the best with time <= split (k, dis_old), neither with a
+ *      lower end (a keyframe of time INT32_MIN, which sm_fern_match's strict min_time can never name, takes part): `matched` counts
+ *      the frames with k >= 0 and float(dis_old) <= match_below * float(n_ferns) (fp32).
+ *   4. An attempt is made if T % every == 0, T >= rest_until, the frame matched, and the centres of P_k and of the tracked pose are
+ *      more than min_jump apart (in double from the floats: sqrt((dx*dx + dy*dy) + dz*dz) > min_jump).  If the recall policy is on
+ *      and the retirement policy has written files, first one SM_RECALL_MOVE around P_k from those files with that policy's radius.
+ *      Then sm_close_loop_at(pose16 = the tracked pose, place16 = P_k, this call's tracker parameters, `loop`, `search`) over the
+ *      sources of the auto-loop policy's attempt (its caller's files while it is on, and the retirement policy's).  SM_LOOP_CLOSED
+ *      hands back the corrected pose, anything else the tracked pose; rest_until = T + rest whatever the outcome.  An error of the
+ *      recall or of the attempt is returned by the tracker call and counted as `failed`.
+ *   5. If the database is empty or float(dis_any) > add_above * float(n_ferns), the frame becomes a keyframe: its code, the pose
+ *      the call returns and time T -- after step 4, so a corrected pose is what is stored.
+ * With the policy off every entry point is exactly what it is without it.
+ * SM_E_ARG: a NULL ctx, every < 1, rest < 0, add_above or match_below outside [0, 1] or not finite, min_jump negative or not
+ * finite, loop as sm_close_loop rejects it, search as sm_search_pose rejects it.  SM_E_UNSUPPORTED: a sharded or rig context. */
+typedef struct sm_auto_place_params {
+    int32_t every, rest;           /* 1: a check on every tick that is a multiple of it; 10: ticks without an attempt after one */
+    float add_above;               /* 0.2: fraction of n_ferns above which a frame becomes a keyframe */
+    float match_below;             /* 0.3: fraction of n_ferns up to which an old keyframe counts as a match */
+    float min_jump;                /* 2 m: nearer than this the loop policy of 4i is left to handle it */
+    sm_loop_params loop;           /* sm_default_loop_params with max_trans 50 m, max_rot_deg 45 */
+    sm_search_params search;       /* sm_default_search_params: the search at the matched place */
+} sm_auto_place_params;
+typedef struct sm_auto_place_stats_t {
+    uint32_t encoded, added, matched, attempts;
+    uint32_t closed, none, rejected, failed, no_old_map;   /* the attempts by outcome (failed: SM_LOOP_TRACK_FAILED or an error) */
+    int32_t last_k;                /* of the last match: the old keyframe, -1 with none */
+    uint32_t last_dis;             /* ... and its dissimilarity (UINT32_MAX with none) */
+    sm_loop_info last;             /* of the last attempt that returned SM_OK */
+} sm_auto_place_stats_t;
+int sm_default_auto_place_params(const sm_config *c, sm_auto_place_params *p);
+int sm_set_auto_place(sm_ctx *s, const sm_auto_place_params *p);
+int sm_auto_place_stats(sm_ctx *s, sm_auto_place_stats_t *out);
 
 /* ---- per-pass entry points (GlobalModel / IndexMap methods), synchronous ---- */
 /* Upload RGB / metric depth / semantic textures directly (bypasses p0). */

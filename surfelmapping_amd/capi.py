@@ -41,6 +41,9 @@ SYMBOLS = (
     "sm_old_in_view", "sm_default_auto_loop_params", "sm_set_auto_loop", "sm_auto_loop_stats",
     "sm_default_search_params", "sm_score_poses_window", "sm_search_pose", "sm_close_loop_search", "sm_set_auto_loop_search",
     "sm_default_lidar_sensor", "sm_lidar_directions", "sm_lidar_sweep", "sm_lidar_sweep_maps", "sm_lidar_stats",
+    "sm_default_fern_params", "sm_fern_table", "sm_set_ferns", "sm_fern_encode", "sm_fern_encode_device", "sm_fern_add", "sm_fern_count",
+    "sm_fern_download", "sm_fern_save", "sm_fern_load", "sm_fern_match", "sm_search_pose_at", "sm_close_loop_at",
+    "sm_default_auto_place_params", "sm_set_auto_place", "sm_auto_place_stats",
 )
 
 SM_COLL_SUM, SM_COLL_MIN, SM_COLL_GATHER = 0, 1, 2
@@ -340,6 +343,39 @@ class SmSearchInfo(C.Structure):
 SEARCH_MAX_CANDIDATES = 1 << 20
 
 
+class SmFernParams(C.Structure):
+    _fields_ = [("n_ferns", C.c_int32), ("cell", C.c_int32), ("seed", C.c_uint64), ("depth_lo_mm", C.c_int32), ("depth_hi_mm", C.c_int32)]
+
+
+class SmFern(C.Structure):
+    _fields_ = [("x", C.c_uint16), ("y", C.c_uint16), ("tr", C.c_uint16), ("tg", C.c_uint16), ("tb", C.c_uint16), ("td", C.c_uint16)]
+
+
+FERN_MAX_KEYFRAMES = 1 << 20
+FERN_DTYPE = np.dtype([(n, np.uint16) for n, _ in SmFern._fields_])
+
+
+def fern_params(cfg, **over) -> SmFernParams:
+    """sm_default_fern_params (512 ferns, cell 8, seed 1, the config's near and far clip in millimetres) with fields overridden"""
+    p = SmFernParams()
+    load().sm_default_fern_params(C.byref(cfg), C.byref(p))
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+def fern_table(params, width, height) -> np.ndarray:
+    """sm_fern_table: the ferns of `params` for an image size, a structured array (x, y, tr, tg, tb, td; uint16).  Host only."""
+    L = load()
+    out = np.zeros(max(int(params.n_ferns), 0), FERN_DTYPE)
+    rc = L.sm_fern_table(C.byref(params), int(width), int(height), _ptr(out))
+    if rc != SM_OK:
+        raise SurfelMapError("sm_fern_table", rc, L.sm_last_error().decode())
+    return out
+
+
 def search_params(**over) -> SmSearchParams:
     """sm_default_search_params (2 levels; +-2 m in x and z at 0.25 m, +-3 deg about y at 0.5 deg; refine 4, stride0 8, top_k 4,
     colour_thresh 0.1) with fields overridden; the four per-axis fields take a sequence of three"""
@@ -353,6 +389,35 @@ def search_params(**over) -> SmSearchParams:
                 getattr(p, k)[a] = float(x)
         else:
             setattr(p, k, v)
+    return p
+
+
+class SmAutoPlaceParams(C.Structure):
+    _fields_ = [("every", C.c_int32), ("rest", C.c_int32), ("add_above", C.c_float), ("match_below", C.c_float), ("min_jump", C.c_float),
+                ("loop", SmLoopParams), ("search", SmSearchParams)]
+
+
+class SmAutoPlaceStats(C.Structure):
+    _fields_ = [("encoded", C.c_uint32), ("added", C.c_uint32), ("matched", C.c_uint32), ("attempts", C.c_uint32), ("closed", C.c_uint32),
+                ("none", C.c_uint32), ("rejected", C.c_uint32), ("failed", C.c_uint32), ("no_old_map", C.c_uint32), ("last_k", C.c_int32),
+                ("last_dis", C.c_uint32), ("last", SmLoopInfo)]
+
+
+def auto_place_params(cfg, **over) -> SmAutoPlaceParams:
+    """sm_default_auto_place_params (every 1, rest 10, add_above 0.2, match_below 0.3, min_jump 2 m, loop = loop_params(cfg) with
+    max_trans 50 and max_rot_deg 45, search = search_params()) with fields overridden: a field of sm_loop_params by its own name,
+    search as a dict of search_params() overrides"""
+    p = SmAutoPlaceParams()
+    load().sm_default_auto_place_params(C.byref(cfg), C.byref(p))
+    for k, v in over.items():
+        if k == "search":
+            p.search = search_params(**dict(v))
+        elif hasattr(p.loop, k):
+            setattr(p.loop, k, v)
+        elif hasattr(p, k) and k != "loop":
+            setattr(p, k, v)
+        else:
+            raise KeyError(k)
     return p
 
 
@@ -613,6 +678,24 @@ def load():
     L.sm_lidar_sweep.argtypes = [vp, lsp, vp, vp, vp, vp, vp]
     L.sm_lidar_sweep_maps.argtypes = [vp, C.POINTER(SmMapSource), lsp, vp, C.c_uint32, vp, vp, vp, vp]
     L.sm_lidar_stats.argtypes = [vp, C.POINTER(SmLidarStats)]
+    fpp = C.POINTER(SmFernParams)
+    L.sm_default_fern_params.argtypes = [C.POINTER(SmConfig), fpp]
+    L.sm_fern_table.argtypes = [fpp, i32, i32, vp]
+    L.sm_set_ferns.argtypes = [vp, fpp]
+    L.sm_fern_encode.argtypes = [vp, vp, vp, vp]
+    L.sm_fern_encode_device.argtypes = [vp, vp, vp, vp]
+    L.sm_fern_add.argtypes = [vp, vp, vp, i32, u32p]
+    L.sm_fern_count.argtypes = [vp, u32p]
+    L.sm_fern_download.argtypes = [vp, vp, vp, vp]
+    L.sm_fern_save.argtypes = [vp, C.c_char_p]
+    L.sm_fern_load.argtypes = [vp, C.c_char_p]
+    L.sm_fern_match.argtypes = [vp, vp, i32, i32, C.POINTER(i32), u32p, vp]
+    L.sm_search_pose_at.argtypes = [vp, vp, vp, vp, vp, tpp, rpp, spp, i32, i32, vp, C.POINTER(SmSearchInfo)]
+    L.sm_close_loop_at.argtypes = [vp, vp, vp, vp, vp, C.POINTER(SmMapSource), tpp, rpp, lpp, spp, vp, C.POINTER(SmLoopInfo)]
+    L.sm_default_auto_place_params.argtypes = [C.POINTER(SmConfig), C.POINTER(SmAutoPlaceParams)]
+    L.sm_set_auto_place.argtypes = [vp, C.POINTER(SmAutoPlaceParams)]
+    L.sm_auto_place_stats.argtypes = [vp, C.POINTER(SmAutoPlaceStats)]
+    L.sm_debug_place_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]     # (a diagnostic, not in the header)
     for name in SYMBOLS:
         getattr(L, name)          # AttributeError here = the library does not match the header
     _lib = L
@@ -995,8 +1078,9 @@ class SurfelMap:
         """track_debug() with track_old()'s window (sm_track_debug_old)"""
         return self._track_debug("sm_track_debug_old", depth, pose_eval, max_time)
 
-    def _close_loop(self, rgb, depth, pose, paths, search, params):
-        """close_loop() (rgb None) and close_loop_rgb(): sm_close_loop_search with `search`, else sm_close_loop / sm_close_loop_rgb"""
+    def _close_loop(self, rgb, depth, pose, paths, search, params, place=None):
+        """close_loop() (rgb None) and close_loop_rgb(): sm_close_loop_at with `place`, sm_close_loop_search with `search`, else
+        sm_close_loop / sm_close_loop_rgb"""
         depth, rgb = self._images(depth, rgb)
         loop_keys = {n for n, _ in SmLoopParams._fields_}
         lp = loop_params(self.cfg, **{k: v for k, v in params.items() if k in loop_keys})
@@ -1006,7 +1090,11 @@ class SurfelMap:
         out = np.zeros(16, np.float32)
         info = SmLoopInfo()
         sp = _search_arg(search)
-        if sp is not None:
+        if place is not None:
+            pl = _mat16(place)
+            self._chk(self._L.sm_close_loop_at(self._h, _ptr(rgb), _ptr(depth), _ptr(g), _ptr(pl), src, tp, rp, lp, sp, _ptr(out), info),
+                      "sm_close_loop_at")
+        elif sp is not None:
             self._chk(self._L.sm_close_loop_search(self._h, _ptr(rgb), _ptr(depth), _ptr(g), src, tp, rp, lp, sp, _ptr(out), info),
                       "sm_close_loop_search")
         elif rgb is not None:
@@ -1015,15 +1103,16 @@ class SurfelMap:
             self._chk(self._L.sm_close_loop(self._h, _ptr(depth), _ptr(g), src, tp, lp, _ptr(out), info), "sm_close_loop")
         return out.reshape(4, 4).T.copy(), _loop_info_dict(info)
 
-    def close_loop(self, depth, pose, paths=(), search=None, **params):
+    def close_loop(self, depth, pose, paths=(), search=None, place=None, **params):
         """Notice that the camera is back in mapped territory and pull the map straight (sm_close_loop).  pose: where the caller
         believes the camera is (4x4 camera->world or float32[16] column-major); paths: the map files that move with the model.
         params: fields of sm_loop_params (min_age, min_trans, min_rot_deg, max_trans, max_rot_deg) and of sm_track_params.
         search: True or a dict of search_params() overrides measures the loop by a pose search around `pose` instead of a single
-        track from it (sm_close_loop_search), which reaches metres of drift.
+        track from it (sm_close_loop_search), which reaches metres of drift.  place: a pose (a matched keyframe's, fern_match) at
+        which the search is centred and its prediction drawn instead (sm_close_loop_at; search then only sets its parameters).
         Returns (pose 4x4: corrected if status is "CLOSED", else as given; info dict: status (name), status_code, track (as
         track()'s info), D 4x4, t_a, t_b)."""
-        return self._close_loop(None, depth, pose, paths, search, params)
+        return self._close_loop(None, depth, pose, paths, search, params, place)
 
     # -- closing loops unasked (sm_set_auto_loop)
     def old_in_view(self, pose, max_time) -> int:
@@ -1059,11 +1148,11 @@ class SurfelMap:
         """track_rgb_debug() with track_window()'s window (sm_track_rgb_debug_window): (pred_slot int32[H][W], sys float64[29])"""
         return self._track_debug("sm_track_rgb_debug_window", depth, pose_eval, level, which, min_time, max_time, rgb=np.asarray(rgb))
 
-    def close_loop_rgb(self, rgb, depth, pose, paths=(), search=None, **params):
+    def close_loop_rgb(self, rgb, depth, pose, paths=(), search=None, place=None, **params):
         """close_loop() with the loop measured by the colour tracker as well (sm_close_loop_rgb): params may also name the fields of
         sm_track_rgb_params.  search as close_loop()'s: the search scores with the colour gate.  Returns (pose, info) as
         close_loop()."""
-        return self._close_loop(np.asarray(rgb), depth, pose, paths, search, params)
+        return self._close_loop(np.asarray(rgb), depth, pose, paths, search, params, place)
 
     def set_auto_loop(self, paths=(), search=None, **params):
         """Make track() / track_rgb() (and process_frame_tracked*) close loops by themselves (sm_set_auto_loop): they track in the
@@ -1104,10 +1193,11 @@ class SurfelMap:
                   "sm_score_poses_window")
         return scores
 
-    def search_pose(self, depth, centre, rgb=None, min_time=INT32_MIN, max_time=INT32_MAX, search=None, **params):
+    def search_pose(self, depth, centre, rgb=None, min_time=INT32_MIN, max_time=INT32_MAX, search=None, pred=None, **params):
         """Find the camera within metres of `centre`: score a grid of poses around it, refine the best, track from the winners
         (sm_search_pose).  search: a dict of search_params() overrides; params: fields of sm_track_params and, with rgb, of
-        sm_track_rgb_params.  Returns (pose 4x4: the centre unless status is "OK"; info dict: status, status_code, levels_run,
+        sm_track_rgb_params.  pred: the pose the prediction is drawn at instead of the last processed frame's (sm_search_pose_at).
+        Returns (pose 4x4: the centre unless status is "OK"; info dict: status, status_code, levels_run,
         candidates, best_score, winner_rank, track (as track()'s info), start 4x4, anchor_time, score_ms, total_ms)."""
         depth = np.ascontiguousarray(depth, np.uint16)
         assert depth.size == self.P, depth.shape
@@ -1122,9 +1212,13 @@ class SurfelMap:
         g = _mat16(centre)
         out = np.zeros(16, np.float32)
         info = SmSearchInfo()
-        self._chk(self._L.sm_search_pose(self._h, _ptr(rgb), _ptr(depth), _ptr(g), C.byref(p) if p is not None else None,
-                                         C.byref(q) if q is not None else None, C.byref(sp) if sp is not None else None, int(min_time),
-                                         int(max_time), _ptr(out), C.byref(info)), "sm_search_pose")
+        tail = (C.byref(p) if p is not None else None, C.byref(q) if q is not None else None, C.byref(sp) if sp is not None else None,
+                int(min_time), int(max_time), _ptr(out), C.byref(info))
+        if pred is not None:
+            at = _mat16(pred)
+            self._chk(self._L.sm_search_pose_at(self._h, _ptr(rgb), _ptr(depth), _ptr(at), _ptr(g), *tail), "sm_search_pose_at")
+        else:
+            self._chk(self._L.sm_search_pose(self._h, _ptr(rgb), _ptr(depth), _ptr(g), *tail), "sm_search_pose")
         n = int(info.levels_run)
         d = dict(status=TRACK_STATUS.get(info.status, str(info.status)), status_code=int(info.status), levels_run=n,
                  candidates=[int(x) for x in info.candidates[:n]], best_score=[int(x) for x in info.best_score[:n]],
@@ -1132,6 +1226,94 @@ class SurfelMap:
                  start=np.array(info.start[:], np.float32).reshape(4, 4).T.copy(), anchor_time=float(info.anchor_time),
                  score_ms=float(info.score_ms), total_ms=float(info.total_ms))
         return out.reshape(4, 4).T.copy(), d
+
+    # -- place recognition (sm_fern_*)
+    def set_ferns(self, on=True, **params):
+        """Give the context a fern table for its image size and an empty keyframe database (sm_set_ferns); params override
+        fern_params(cfg).  on False: free both."""
+        p = fern_params(self.cfg, **params) if on else None
+        self._chk(self._L.sm_set_ferns(self._h, C.byref(p) if on else None), "sm_set_ferns")
+        self._fern = p
+
+    def _fern_words(self):
+        if getattr(self, "_fern", None) is None:
+            raise SurfelMapError("fern", SM_E_ARG, "the context has no ferns (set_ferns)")
+        return self._fern.n_ferns // 8
+
+    def fern_encode(self, depth, rgb=None) -> np.ndarray:
+        """the fern code of a frame, uint32[n_ferns / 8] (sm_fern_encode): depth uint16[H][W] mm, rgb uint8[H][W][3] or None (the
+        colour bits are 0 then)"""
+        depth, rgb = self._images(depth, rgb)
+        code = np.zeros(self._fern_words(), np.uint32)
+        self._chk(self._L.sm_fern_encode(self._h, _ptr(rgb), _ptr(depth), _ptr(code)), "sm_fern_encode")
+        return code
+
+    def fern_encode_device(self, d_depth: int, d_rgb: int = 0) -> np.ndarray:
+        """fern_encode() of images in this context's device memory (sm_fern_encode_device)"""
+        code = np.zeros(self._fern_words(), np.uint32)
+        self._chk(self._L.sm_fern_encode_device(self._h, d_rgb or None, d_depth, _ptr(code)), "sm_fern_encode_device")
+        return code
+
+    def fern_add(self, code, pose, time) -> int:
+        """append a keyframe (sm_fern_add): its code, its pose (4x4 or float32[16] column-major) and its time; returns its index"""
+        code = np.ascontiguousarray(code, np.uint32)
+        assert code.size == self._fern_words(), code.shape
+        g = _mat16(pose)
+        k = C.c_uint32()
+        self._chk(self._L.sm_fern_add(self._h, _ptr(code), _ptr(g), int(time), C.byref(k)), "sm_fern_add")
+        return int(k.value)
+
+    def fern_count(self) -> int:
+        n = C.c_uint32()
+        self._chk(self._L.sm_fern_count(self._h, C.byref(n)), "sm_fern_count")
+        return int(n.value)
+
+    def fern_match(self, code, min_time=INT32_MIN, max_time=INT32_MAX, dis_all=False):
+        """The keyframe nearest to `code` among those with min_time < time <= max_time (sm_fern_match): (index or -1,
+        dissimilarity = ferns whose nibbles differ, 2^32 - 1 with none); with dis_all also uint32[count], every keyframe's."""
+        code = np.ascontiguousarray(code, np.uint32)
+        assert code.size == self._fern_words(), code.shape
+        k, d = C.c_int32(), C.c_uint32()
+        every = np.zeros(self.fern_count(), np.uint32) if dis_all else None
+        self._chk(self._L.sm_fern_match(self._h, _ptr(code), int(min_time), int(max_time), C.byref(k), C.byref(d), _ptr(every)), "sm_fern_match")
+        return (int(k.value), int(d.value), every) if dis_all else (int(k.value), int(d.value))
+
+    def fern_keyframes(self) -> dict:
+        """the database (sm_fern_download): codes uint32[n][n_ferns / 8], poses float32[n][16] column-major, times int32[n]"""
+        n, w = self.fern_count(), self._fern_words()
+        codes, poses, times = np.zeros((n, w), np.uint32), np.zeros((n, 16), np.float32), np.zeros(n, np.int32)
+        self._chk(self._L.sm_fern_download(self._h, _ptr(codes), _ptr(poses), _ptr(times)), "sm_fern_download")
+        return dict(codes=codes, poses=poses, times=times)
+
+    def fern_save(self, path):
+        self._chk(self._L.sm_fern_save(self._h, os.fsencode(path)), "sm_fern_save")
+
+    def fern_load(self, path):
+        self._chk(self._L.sm_fern_load(self._h, os.fsencode(path)), "sm_fern_load")
+
+    def place_ms(self):
+        """device times in ms of the last fern encode and the last fern match kernel of a context whose set_ferns() ran with
+        SM_PLACE_TIMING=1 (sm_debug_place_ms, not part of the C-ABI header); (None, None) if it was not timed"""
+        e, m = C.c_float(), C.c_float()
+        self._chk(self._L.sm_debug_place_ms(self._h, C.byref(e), C.byref(m)), "sm_debug_place_ms")
+        return (None, None) if e.value < 0 else (float(e.value), float(m.value))
+
+    def set_auto_place(self, on=True, **params):
+        """Make track() / track_rgb() (and process_frame_tracked*) recognise revisited places by themselves (sm_set_auto_place; needs
+        set_ferns first): every tracked frame is encoded and matched against the keyframes, a match with an old keyframe far from
+        the tracked pose is verified and closed by close_loop(place=) before the frame is fused, and frames unlike every keyframe
+        become keyframes.  params override auto_place_params(cfg).  on False: off."""
+        p = auto_place_params(self.cfg, **params) if on else None
+        self._chk(self._L.sm_set_auto_place(self._h, C.byref(p) if on else None), "sm_set_auto_place")
+
+    def auto_place_stats(self) -> dict:
+        """encoded, added, matched, attempts, closed, none, rejected, failed, no_old_map, last_k, last_dis, and last = the last
+        attempt's info as close_loop() returns it (sm_auto_place_stats)"""
+        st = SmAutoPlaceStats()
+        self._chk(self._L.sm_auto_place_stats(self._h, C.byref(st)), "sm_auto_place_stats")
+        d = {k: int(getattr(st, k)) for k, _ in SmAutoPlaceStats._fields_ if k != "last"}
+        d["last"] = _loop_info_dict(st.last)
+        return d
 
     def auto_loop_stats(self) -> dict:
         """checked, attempts, closed, none, rejected, failed, no_old_map, last_census, and last = the last attempt's info as

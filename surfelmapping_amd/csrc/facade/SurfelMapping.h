@@ -405,6 +405,56 @@ public:
         return st;
     }
 
+    // Recognise revisited places without a pose prior (sm_set_ferns, sm_set_auto_place): while on, every processFrame that tracks
+    // (null gtPose) encodes the frame as a fern code, matches it against the keyframes, and where an old keyframe far from the
+    // tracked pose matches, searches and tracks at that keyframe's pose and closes the loop before the frame is fused; frames unlike
+    // every keyframe become keyframes.  Turning it on makes a fresh, empty database (loadKeyframes fills it from a file).  nFerns /
+    // matchBelow, if not negative, replace the defaults (512, 0.3).  on = false: off, and the database is freed.
+    bool setAutoPlace(bool on, int nFerns = -1, float matchBelow = -1.0f)
+    {
+        int rc;
+        if (!on) {
+            rc = sm_set_auto_place(ctx_, nullptr);
+            if (rc == SM_OK) rc = sm_set_ferns(ctx_, nullptr);
+        } else {
+            sm_config c;
+            sm_default_config(&c, Config::W(), Config::H(), Config::fx(), Config::fy(), Config::cx(), Config::cy());
+            c.near_clip = Config::nearClip();              // (the context's own clips: the ferns' depth thresholds span them)
+            c.far_clip = Config::farClip();
+            sm_fern_params fp;
+            sm_default_fern_params(&c, &fp);
+            if (nFerns >= 0) fp.n_ferns = nFerns;
+            sm_auto_place_params ap;
+            sm_default_auto_place_params(&c, &ap);
+            if (matchBelow >= 0.0f) ap.match_below = matchBelow;
+            rc = sm_set_ferns(ctx_, &fp);
+            if (rc == SM_OK) rc = sm_set_auto_place(ctx_, &ap);
+        }
+        if (rc == SM_OK) return true;
+        std::printf("setAutoPlace: %s\n", sm_last_error());
+        return false;
+    }
+    // the keyframes (codes, poses, times) as one file, and back: of a context whose setAutoPlace used the same number of ferns
+    bool saveKeyframes(const std::string &path)
+    {
+        if (sm_fern_save(ctx_, path.c_str()) == SM_OK) return true;
+        std::printf("saveKeyframes: %s\n", sm_last_error());
+        return false;
+    }
+    bool loadKeyframes(const std::string &path)
+    {
+        if (sm_fern_load(ctx_, path.c_str()) == SM_OK) return true;
+        std::printf("loadKeyframes: %s\n", sm_last_error());
+        return false;
+    }
+    // frames encoded, keyframes added, matches, attempts and their outcomes so far; `last` is the last attempt's sm_loop_info
+    sm_auto_place_stats_t autoPlaceStats()
+    {
+        sm_auto_place_stats_t st{};
+        sm_auto_place_stats(ctx_, &st);
+        return st;
+    }
+
     // With setAutoRetire on: after every retirement, the records of its map files within `radius` metres of that frame's camera
     // come back into the model and leave the files, so that a camera that returns finds what it left (sm_set_auto_recall;
     // 0 < radius <= the retirement's minDistance).  radius <= 0: off.

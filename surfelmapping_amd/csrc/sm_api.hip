@@ -1418,6 +1418,7 @@ int sm_reset(sm_ctx *s)
     s->h_state->cur = cur;
     s->tick = 0;                                 // refFrameIsSet stays (src/SurfelMapping.cpp:436-441)
     s->pending_cull = false;
+    place_reset(s);                              // the keyframes index a map that is gone
     if ((rc = push_state(s))) return rc;
     if ((rc = rebuild_bounds(s, 0, 0))) return rc;
     return pull_state(s);

@@ -14,6 +14,7 @@
 //   sm_warp.hip      closing loops (sm_warp_by_time, sm_loop_spread): the model and map files warped by surfel time
 //   sm_search.hip    pose search before the tracker (sm_score_poses_window, sm_search_pose)
 //   sm_lidar.hip     lidar sweeps (sm_lidar_*): beams against the live model and against streamed map files
+//   sm_place.hip     place recognition (sm_fern_*, sm_search_pose_at, sm_close_loop_at): fern codes, the keyframe database, the match
 // and, beside it, for everything that touches a map file: sm_mapfile.h (the format: checked open, writer, chunk plan; host only)
 // and sm_map_stream.h (the double-buffered chunk stream of sm_render_maps.hip and sm_recall.hip); for the occupied slots and the
 // compaction schedule: sm_slots.h (SlotSchedule; host only); for the arithmetic of rigid poses in double: sm_pose.h (host only,
@@ -236,6 +237,33 @@ struct Lidar {
     Event ev[2];                       // around the live model's kernels
     sm_lidar_stats_t stats{};
     bool stats_valid = false;
+};
+
+// place recognition (sm_place.hip, sm_k_place.h): the fern table, the staging of a frame to encode, the keyframe database (codes
+// and times on the device, poses and times on the host) and the match's scratch.  on = false: none of it exists.
+struct Place {
+    bool on = false;
+    sm_fern_params p{};
+    Dev<uint4> d_table;                // per fern: x | y << 16, tr | tg << 16, tb | td << 16, 0
+    Dev<uint8_t> d_rgb;                // sm_fern_encode's copies of the host images
+    Dev<uint16_t> d_depth;
+    Dev<uint32_t> d_code;              // the code of the last encode, and the query of a match
+    Dev<uint32_t> d_codes;             // keyframe-major, n_ferns / 8 words each
+    Dev<int32_t> d_times;
+    size_t cap = 0;                    // keyframes the two hold
+    std::vector<float> poses;          // 16 per keyframe
+    std::vector<int32_t> times;
+    Dev<unsigned long long> d_keys;    // [2]: the match's answers
+    Dev<uint32_t> d_dis;               // dis_all, `cap` entries, allocated by the first match that asks
+    size_t dis_cap = 0;
+    uint32_t count() const { return (uint32_t)times.size(); }
+    bool timed = false;                // SM_PLACE_TIMING=1 at sm_set_ferns: events around the two kernels (tools/place_probe.py)
+    Event ev[4];                       // before / after k_fern_encode, before / after k_fern_match, of the last launches
+    // the policy of sm_set_auto_place and its tally
+    bool auto_on = false;
+    sm_auto_place_params ap{};
+    int64_t rest_until = 0;            // no attempt before this tick
+    sm_auto_place_stats_t stats{};
 };
 
 // closing loops unasked (sm_loop.hip): the policy of sm_set_auto_loop and its tally
@@ -469,6 +497,7 @@ struct sm_ctx {
     AutoLoop aloop;
     Search srch;
     Lidar lid;
+    Place place;
     // host frame state (src/SurfelMapping.h:100-103)
     int tick = 0;
     bool ref_set = false;
@@ -547,9 +576,10 @@ int check_recall_policy(float radius, const sm_retire_params &rp, const char *wh
 struct TrackWindow { int32_t lo, hi; };
 // One tracked frame, whichever public form it came through (fn names it in the error texts): rgb null = sm_track_frame's depth
 // schedule, otherwise sm_track_frame_rgb's; win null = the whole model.  It never consults the policy of sm_set_auto_loop.
+// pred16 (null: T_prev, the pose of the last processed frame) is the camera the prediction is drawn at (sm_search_pose_at).
 int track_windowed(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params,
                    const sm_track_rgb_params *rgb_params, const TrackWindow *win, float *pose16_out, sm_track_info *info,
-                   sm_track_rgb_info *rgb_info, float *anchor_time, const char *fn);
+                   sm_track_rgb_info *rgb_info, float *anchor_time, const char *fn, const float *pred16 = nullptr);
 // What sm_search.hip takes from a tracked frame's preparation.  The prediction's camera and image, the grid of `stride` and the
 // association gates, as the trackers' kernels get them:
 struct SearchFrame {
@@ -564,12 +594,25 @@ struct SearchFrame {
 struct SearchBufs { const float4 *v, *n; const int32_t *pred; const uint32_t *in_view; };
 // sm_track_frame_window's checks and preparation for the grid of `stride` (tp's own pixel_stride is not used), enqueued:
 // *no_model when there is no processed frame or no live surfel (nothing is enqueued then).  fresh = false: the prediction of the
-// last call stands (same frame, same window, nothing ran in between) and only the grid's vertex stage runs again.
+// last call stands (same frame, same window, same pred16, nothing ran in between) and only the grid's vertex stage runs again.
+// pred16 as track_windowed's.
 int search_prepare(sm_ctx *s, const uint16_t *depth_mm, const sm_track_params &tp, int32_t stride, int32_t min_time, int32_t max_time,
-                   bool fresh, SearchFrame *f, SearchBufs *b, bool *no_model, const char *fn);
+                   bool fresh, SearchFrame *f, SearchBufs *b, bool *no_model, const char *fn, const float *pred16 = nullptr);
 // ---- sm_search.hip ----
 // sm_search_pose's rules for its parameters (SM_E_ARG with g_err set)
 int check_search_params(const sm_search_params &p, const char *who);
+// sm_search_pose (pred16 null: the prediction at T_prev) and sm_search_pose_at; fn: the one the call came through
+int search_pose(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *pred16, const float *centre16, const sm_track_params *tp,
+                const sm_track_rgb_params *rp, const sm_search_params *sp, int32_t min_time, int32_t max_time, float *pose16_out,
+                sm_search_info *info, const char *fn);
+// ---- sm_place.hip ----
+void place_reset(sm_ctx *s);                      // sm_reset: the database is empty again (the table stays)
+// sm_warp_by_time's pose rule (sm_warp.hip, warp_pose) for every stored keyframe pose
+void place_warp_poses(sm_ctx *s, const std::function<void(float *, int32_t)> &warp_pose);
+// sm_track_frame (rgb null) / sm_track_frame_rgb while sm_set_auto_place is on, after the track (and the auto-loop policy's work):
+// the frame's code, the match, one attempt at the matched place, the keyframe.  loop_closed: that policy closed a loop on this call
+int auto_place_after_track(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const sm_track_params *params,
+                           const sm_track_rgb_params *rgb_params, float *pose16_out, int track_status, bool loop_closed);
 // ---- sm_loop.hip ----
 // sm_track_frame (rgb null) / sm_track_frame_rgb while sm_set_auto_loop is on: the young-window track, the census, one attempt
 int auto_loop_track(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params,
@@ -578,10 +621,11 @@ int auto_loop_track(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, con
 // sm_close_loop's rules for its parameters (SM_E_ARG with g_err set)
 int check_loop_params(const sm_loop_params &p, const char *who);
 // sm_close_loop (rgb null: the depth-only measurement) and sm_close_loop_rgb; search: sm_close_loop_search, whose step 1 is
-// sm_search_pose with sp (null: its defaults).  who: the one of the three the call came through.
+// sm_search_pose with sp (null: its defaults); place16 non-null: sm_close_loop_at, whose step 1 is sm_search_pose_at there.
+// who: the one of the four the call came through.
 int close_loop(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *pose16, const sm_map_source *src,
                const sm_track_params *tp, const sm_track_rgb_params *rp, const sm_loop_params *lp, bool search, const sm_search_params *sp,
-               float *pose16_out, sm_loop_info *info, const char *who);
+               float *pose16_out, sm_loop_info *info, const char *who, const float *place16 = nullptr);
 
 // ---- what several sources ask of their arguments (SM_E_ARG with g_err set) ----
 // what works on the whole map (retirement, recall, warp, loop closure and its policy, pose search) refuses a context that holds a

@@ -48,14 +48,14 @@ int check_candidates(const float *cand16, uint32_t n, const char *fn)
 // only the grid changes.  *in_view: the surfels of the window in view of the prediction camera; *ms: the scoring kernels' time.
 int score(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *cand16, uint32_t n, const sm_track_params &tp,
           int32_t stride, float colour_thresh, int32_t min_time, int32_t max_time, bool fresh, uint32_t *scores, bool *no_model,
-          uint32_t *in_view, float *ms, const char *fn)
+          uint32_t *in_view, float *ms, const char *fn, const float *pred16 = nullptr)
 {
     SearchFrame f;
     SearchBufs b;
     int rc;
     *in_view = 0;
     *ms = 0.0f;
-    if ((rc = search_prepare(s, depth_mm, tp, stride, min_time, max_time, fresh, &f, &b, no_model, fn))) return rc;
+    if ((rc = search_prepare(s, depth_mm, tp, stride, min_time, max_time, fresh, &f, &b, no_model, fn, pred16))) return rc;
     if (*no_model) { memset(scores, 0, (size_t)n * 4); return SM_OK; }
     if ((rc = search_alloc(s, n))) return rc;
     Search &q = s->srch;
@@ -240,7 +240,15 @@ int sm_search_pose(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, cons
                    const sm_track_rgb_params *rp, const sm_search_params *sp, int32_t min_time, int32_t max_time, float *pose16_out,
                    sm_search_info *info)
 {
-    const char *fn = "sm_search_pose";
+    return search_pose(s, rgb, depth_mm, nullptr, centre16, tp, rp, sp, min_time, max_time, pose16_out, info, "sm_search_pose");
+}
+
+}  // extern "C"
+
+int sm_impl::search_pose(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *pred16, const float *centre16,
+                         const sm_track_params *tp, const sm_track_rgb_params *rp, const sm_search_params *sp, int32_t min_time,
+                         int32_t max_time, float *pose16_out, sm_search_info *info, const char *fn)
+{
     const auto t_start = std::chrono::steady_clock::now();
     if (!s || !depth_mm || !centre16 || !pose16_out) { g_err = std::string(fn) + ": null argument"; return SM_E_ARG; }
     int rc;
@@ -290,7 +298,7 @@ int sm_search_pose(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, cons
         uint32_t in_view = 0;
         float ms = 0.0f;
         if ((rc = score(s, rgb, depth_mm, cand.data(), n, p, stride, q.colour_thresh, min_time, max_time, l == 0, scores.data(), &no_model,
-                        &in_view, &ms, fn)))
+                        &in_view, &ms, fn, pred16)))
             return rc;
         if (no_model) return finish(SM_TRACK_NO_MODEL);
         inf.levels_run = l + 1;
@@ -324,7 +332,7 @@ int sm_search_pose(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, cons
         float out[16], anchor = -1.0f;
         sm_track_info ti;
         if ((rc = track_windowed(s, rgb, depth_mm, g, &p, rp, &win, out, &ti, nullptr, &anchor,
-                                 rgb ? "sm_track_frame_rgb_window" : "sm_track_frame_window")))
+                                 rgb ? "sm_track_frame_rgb_window" : "sm_track_frame_window", pred16)))
             return rc;
         const bool ok = ti.status == SM_TRACK_OK;
         if ((r == 0 && !ok) || (ok && (!have_ok || ti.inliers > inf.track.inliers))) {
@@ -336,5 +344,3 @@ int sm_search_pose(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, cons
     }
     return finish(inf.track.status);
 }
-
-}  // extern "C"

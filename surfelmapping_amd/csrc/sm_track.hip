@@ -67,12 +67,14 @@ int track_params_check(const sm_ctx *s, const sm_track_params &p, const char *fn
     return SM_OK;
 }
 
-TrackParams track_params(const sm_ctx *s, const sm_track_params &p)
+// pred16 (null: T_prev) is the camera the prediction is drawn at
+TrackParams track_params(const sm_ctx *s, const sm_track_params &p, const float *pred16 = nullptr)
 {
     TrackParams tp;
     memset(&tp, 0, sizeof tp);
     double prev[16], inv[16];
-    if (s->trk.n_hist) sm_pose::widen(s->trk.hist[0], prev);
+    if (pred16) sm_pose::widen(pred16, prev);                         // (sm_search_pose_at: the prediction is drawn elsewhere)
+    else if (s->trk.n_hist) sm_pose::widen(s->trk.hist[0], prev);
     else sm_pose::identity(prev);
     rigid_inv_d(prev, inv);
     for (int e = 0; e < 16; ++e) tp.tinv_prev[e] = (float)inv[e];
@@ -226,10 +228,10 @@ TrackRgbParams track_rgb_params(const sm_ctx *s, const sm_track_rgb_params &q)
     return rp;
 }
 
-TrackParams track_level_params(const sm_ctx *s, sm_track_params p, int level)
+TrackParams track_level_params(const sm_ctx *s, sm_track_params p, int level, const float *pred16 = nullptr)
 {
     p.pixel_stride <<= level;
-    return track_params(s, p);
+    return track_params(s, p, pred16);
 }
 
 // sm_track_frame's preparation on the coarsest level's grid, then the pyramid and the gathered prediction (the rgb upload precedes event 0, as the depth's)
@@ -361,7 +363,7 @@ int null_argument(const char *fn)
 // fn: the public entry point the call came through -- it does not consult the policy of sm_set_auto_loop.
 int sm_impl::track_windowed(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params,
                             const sm_track_rgb_params *rgb_params, const TrackWindow *win, float *pose16_out, sm_track_info *info,
-                            sm_track_rgb_info *rgb_info, float *anchor_time, const char *fn)
+                            sm_track_rgb_info *rgb_info, float *anchor_time, const char *fn, const float *pred16)
 {
     if (!s || !depth_mm || !pose16_out) { g_err = std::string(fn) + ": null argument"; return SM_E_ARG; }
     sm_track_params p;
@@ -399,16 +401,16 @@ int sm_impl::track_windowed(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth
     if (rgb) {
         const TrackRgbParams rp = track_rgb_params(s, q);
         // (the preparation's vertex stage is the coarsest level's; the prediction does not depend on the stride)
-        const TrackParams tpc = track_level_params(s, p, q.levels - 1);
+        const TrackParams tpc = track_level_params(s, p, q.levels - 1, pred16);
         if ((rc = track_rgb_prepare(s, rgb, depth_mm, tpc, rp, g, g, true, q.levels - 1, win))) return rc;
         for (int l = q.levels - 1; l >= 0; --l) {
-            const TrackParams tpl = track_level_params(s, p, l);
+            const TrackParams tpl = track_level_params(s, p, l, pred16);
             if (l < q.levels - 1 && (rc = track_rgb_level(s, tpl, l))) return rc;
             for (int it = 0; it < q.iters[l]; ++it)
                 if ((rc = track_rgb_iteration(s, tpl, rp, l, 0))) return rc;
         }
     } else {
-        const TrackParams tp = track_params(s, p);
+        const TrackParams tp = track_params(s, p, pred16);
         if ((rc = track_prepare(s, depth_mm, tp, g, g, true, win))) return rc;     // (iterates from the orthonormalised guess)
         for (int it = 0; it < p.max_iters; ++it)
             if ((rc = track_iteration(s, tp, 0))) return rc;
@@ -439,7 +441,7 @@ int sm_impl::track_windowed(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth
 
 // ---- what the pose search takes from the preparation (sm_search.hip) ----
 int sm_impl::search_prepare(sm_ctx *s, const uint16_t *depth_mm, const sm_track_params &params, int32_t stride, int32_t min_time,
-                            int32_t max_time, bool fresh, SearchFrame *f, SearchBufs *b, bool *no_model, const char *fn)
+                            int32_t max_time, bool fresh, SearchFrame *f, SearchBufs *b, bool *no_model, const char *fn, const float *pred16)
 {
     sm_track_params p = params;
     p.pixel_stride = stride;
@@ -450,7 +452,7 @@ int sm_impl::search_prepare(sm_ctx *s, const uint16_t *depth_mm, const sm_track_
     *no_model = s->trk.n_hist == 0 || s->h_state->count == s->h_state->garbage;
     if (*no_model) return SM_OK;
     if ((rc = track_alloc(s))) return rc;
-    const TrackParams tp = track_params(s, p);
+    const TrackParams tp = track_params(s, p, pred16);
     if (fresh) {
         float eye[16];
         sm_pose::identity(eye);
@@ -471,13 +473,30 @@ int sm_impl::search_prepare(sm_ctx *s, const uint16_t *depth_mm, const sm_track_
     return SM_OK;
 }
 
+// sm_track_frame (rgb null) and sm_track_frame_rgb: the track -- the auto-loop policy's while it is on -- and then the place policy
+static int track_with_policies(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params,
+                               const sm_track_rgb_params *rgb_params, float *pose16_out, sm_track_info *info, sm_track_rgb_info *rgb_info,
+                               const char *fn)
+{
+    if (!s || !s->place.auto_on) {
+        if (s && s->aloop.on) return auto_loop_track(s, rgb, depth_mm, guess16, params, rgb_params, pose16_out, info, rgb_info);
+        return track_windowed(s, rgb, depth_mm, guess16, params, rgb_params, nullptr, pose16_out, info, rgb_info, nullptr, fn);
+    }
+    sm_track_info inf;
+    const uint32_t closed_before = s->aloop.stats.closed;
+    int rc = s->aloop.on ? auto_loop_track(s, rgb, depth_mm, guess16, params, rgb_params, pose16_out, &inf, rgb_info)
+                         : track_windowed(s, rgb, depth_mm, guess16, params, rgb_params, nullptr, pose16_out, &inf, rgb_info, nullptr, fn);
+    if (rc) return rc;
+    if (info) *info = inf;
+    return auto_place_after_track(s, rgb, depth_mm, params, rgb_params, pose16_out, inf.status, s->aloop.on && s->aloop.stats.closed != closed_before);
+}
+
 extern "C" {
 
 int sm_track_frame(sm_ctx *s, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params, float *pose16_out,
                    sm_track_info *info)
 {
-    if (s && s->aloop.on) return auto_loop_track(s, nullptr, depth_mm, guess16, params, nullptr, pose16_out, info, nullptr);
-    return track_windowed(s, nullptr, depth_mm, guess16, params, nullptr, nullptr, pose16_out, info, nullptr, nullptr, "sm_track_frame");
+    return track_with_policies(s, nullptr, depth_mm, guess16, params, nullptr, pose16_out, info, nullptr, "sm_track_frame");
 }
 
 int sm_track_frame_old(sm_ctx *s, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params, int32_t max_time,
@@ -498,8 +517,7 @@ int sm_track_frame_rgb(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, 
                        const sm_track_rgb_params *rgb_params, float *pose16_out, sm_track_info *info, sm_track_rgb_info *rgb_info)
 {
     if (!rgb) return null_argument("sm_track_frame_rgb");
-    if (s && s->aloop.on) return auto_loop_track(s, rgb, depth_mm, guess16, params, rgb_params, pose16_out, info, rgb_info);
-    return track_windowed(s, rgb, depth_mm, guess16, params, rgb_params, nullptr, pose16_out, info, rgb_info, nullptr, "sm_track_frame_rgb");
+    return track_with_policies(s, rgb, depth_mm, guess16, params, rgb_params, pose16_out, info, rgb_info, "sm_track_frame_rgb");
 }
 
 int sm_track_frame_rgb_window(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params,

@@ -195,6 +195,8 @@ int warp_model(sm_ctx *s, const WarpArgs &wa, int32_t t0, uint32_t n, const floa
     }
     if (s->trk.n_hist >= 1) warp_pose(s->trk.hist[0], s->tick - 1, t0, n, corr12);
     if (s->trk.n_hist >= 2) warp_pose(s->trk.hist[1], s->tick - 2, t0, n, corr12);
+    // ... and the keyframes of place recognition, each by its own time
+    place_warp_poses(s, [&](float *P, int32_t time) { warp_pose(P, time, t0, n, corr12); });
     return SM_OK;
 }
 
@@ -355,7 +357,7 @@ int sm_impl::check_loop_params(const sm_loop_params &p, const char *who)
 
 int sm_impl::close_loop(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *pose16, const sm_map_source *src,
                         const sm_track_params *tp, const sm_track_rgb_params *rp, const sm_loop_params *lp, bool search,
-                        const sm_search_params *sp, float *pose16_out, sm_loop_info *info, const char *who)
+                        const sm_search_params *sp, float *pose16_out, sm_loop_info *info, const char *who, const float *place16)
 {
     if (!s || !depth_mm || !pose16 || !src || !pose16_out || !info) { g_err = std::string(who) + ": null argument"; return SM_E_ARG; }
     int rc;
@@ -373,7 +375,9 @@ int sm_impl::close_loop(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm,
     float t_old[16], anchor = -1.0f;
     if (search) {
         sm_search_info si;
-        if ((rc = sm_search_pose(s, rgb, depth_mm, pose16, tp, rp, sp, INT32_MIN, max_time, t_old, &si))) return rc;
+        rc = search_pose(s, rgb, depth_mm, place16, place16 ? place16 : pose16, tp, rp, sp, INT32_MIN, max_time, t_old, &si,
+                         place16 ? "sm_search_pose_at" : "sm_search_pose");
+        if (rc) return rc;
         info->track = si.track;
         info->track.status = si.status;
         anchor = si.anchor_time;

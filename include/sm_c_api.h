@@ -929,6 +929,58 @@ int sm_default_auto_place_params(const sm_config *c, sm_auto_place_params *p);
 int sm_set_auto_place(sm_ctx *s, const sm_auto_place_params *p);
 int sm_auto_place_stats(sm_ctx *s, sm_auto_place_stats_t *out);
 
+/* ---- stereo depth (DESIGN.md "4m. Stereo depth") ----
+ * Everything above takes a dense depth image.  This stage makes one from a rectified stereo pair: semi-global matching
+ * (Hirschmueller) over a census transform, all integers up to the final division, no weights.  Inputs: rgb_left and rgb_right of
+ * the context's size, each H*W*3 u8, R first.  Parameters (sm_stereo_params): max_disp D one of 64, 128, 192, 256; paths 4 or 8;
+ * 1 <= p1 <= p2 <= 1023; uniqueness a percentage in 0..100; lr_max_diff in 0..D; baseline in metres, finite, > 0.
+ * sm_default_stereo_params: 128, 8, 7, 86, 5, 1, 0.54.
+ *   1. Luminance.  Y = (77*R + 150*G + 29*B + 128) >> 8, a u8 per pixel, for both images.
+ *   2. Census.  The window is 9 wide and 7 high, coordinates clamped to the image (the edge is replicated).  code = 0; for dy in
+ *      -3..3 (outer loop), dx in -4..4 (inner loop), skipping (0, 0): code = (code << 1) | (Y[y+dy][x+dx] < Y[y][x]).  62 bits in a
+ *      uint64.
+ *   3. Matching cost.  For d in 0..D-1: C(x, y, d) = popcount(cL(x, y) ^ cR(x-d, y)) if x - d >= 0, otherwise 64.
+ *   4. Path cost along direction r = (dx, dy), with p' = p - r.  p' outside the image: L_r(p, d) = C(p, d).  Otherwise, with
+ *      m = min_k L_r(p', k):  L_r(p, d) = C(p, d) + min(L_r(p', d), L_r(p', d-1) + p1, L_r(p', d+1) + p1, m + p2) - m, where the terms
+ *      with d-1 < 0 or d+1 >= D are absent.  The directions in order: (1,0), (-1,0), (0,1), (0,-1); with paths == 8 also (1,1), (-1,1),
+ *      (1,-1), (-1,-1).  S(p, d) is the sum over the directions, a u16: the bounds keep it at most 8 * (64 + 1023).
+ *   5. Winner.  d* is the lowest d with the least S(p, d).  Right view: dR(xr, y) is the lowest d with the least S(xr+d, y, d) over
+ *      the d with xr + d < W.  A pixel is valid iff d* >= 1, x - d* >= 0, no d with |d - d*| > 1 has
+ *      S(p, d) * (100 - uniqueness) < S(p, d*) * 100 (32-bit integers), and |dR(x - d*, y) - d*| <= lr_max_diff.
+ *   6. Sub-pixel, in sixteenths.  For 1 <= d* <= D-2: a = S(d*-1) - S(d*), b = S(d*+1) - S(d*), den = a + b; den > 0:
+ *      q = 16*d* - 8 + (32*a + den) / (2*den) (non-negative integer division); den == 0: q = 16*d*.  For d* == D-1: q = 16*d*.
+ *      Invalid pixels have q = 0.  disp16 is q as a u16.
+ *   7. Depth.  On the host, in double: K = ((double)fx * (double)baseline) * 16000.0, fx the context's float.  Per valid pixel, in
+ *      double: mm = floor(K / (double)q + 0.5); mm > 65535 gives 0, otherwise depth_mm = (uint16)mm.  Invalid pixels have 0.
+ * No stereo border, clip or filter is applied here: the fusion's own stereo_border and preprocess chain do that downstream, as
+ * they do for a depth image from a file.
+ * sm_set_stereo allocates the two census planes, the cost volume and the volume of S (W*H*D*2 bytes) and the two outputs on the
+ *   device; p NULL frees them (the default).  Setting it again replaces them.  If an allocation fails: SM_E_HIP, and the context is
+ *   left without stereo.
+ * sm_stereo_depth takes host images and waits; either output may be NULL.  sm_stereo_depth_device takes images resident on the
+ *   context's GPU and outputs that are device pointers the caller owns (2-byte aligned, either may be NULL); its work is enqueued
+ *   on the context's stream and not waited for, so a following sm_process_frame_device(ctx, d_left, d_depth_mm_out, ...) sees
+ *   the result.
+ * sm_stereo_download returns the intermediates of the last call (zeros before the first): the two census planes (H*W uint64 each)
+ *   and the volume of S (row-major y, x, d; H*W*D uint16).  Any pointer may be NULL.  Synchronous.
+ * These entry points change nothing in the model, its counters, the tick, the frame log or the tracker state.
+ * SM_E_ARG: a NULL context or image, parameters outside the ranges above, a misaligned output, a context without stereo (every call
+ *   except sm_set_stereo and the defaults), a call between sm_stage_conflict and sm_stage_cull.
+ *   SM_E_UNSUPPORTED: a sharded or rig context, checked right after the NULL context and before every other argument. */
+typedef struct sm_stereo_params {
+    int32_t max_disp;              /* D: 64, 128, 192 or 256; default 128 */
+    int32_t paths;                 /* 4 or 8; default 8 */
+    int32_t p1, p2;                /* 1 <= p1 <= p2 <= 1023; defaults 7, 86 */
+    int32_t uniqueness;            /* percent, 0..100; default 5 */
+    int32_t lr_max_diff;           /* 0..D; default 1 */
+    float   baseline;              /* metres, finite, > 0; default 0.54 */
+} sm_stereo_params;
+int sm_default_stereo_params(const sm_config *c, sm_stereo_params *p);
+int sm_set_stereo(sm_ctx *s, const sm_stereo_params *p);
+int sm_stereo_depth(sm_ctx *s, const uint8_t *rgb_left, const uint8_t *rgb_right, uint16_t *depth_mm_out, uint16_t *disp16_out);
+int sm_stereo_depth_device(sm_ctx *s, const uint8_t *d_left, const uint8_t *d_right, uint16_t *d_depth_mm_out, uint16_t *d_disp16_out);
+int sm_stereo_download(sm_ctx *s, uint64_t *census_left, uint64_t *census_right, uint16_t *volume);
+
 /* ---- per-pass entry points (GlobalModel / IndexMap methods), synchronous ---- */
 /* Upload RGB / metric depth / semantic textures directly (bypasses p0). */
 int sm_set_frame(sm_ctx *s, const uint8_t *rgb, const float *depth_metric,

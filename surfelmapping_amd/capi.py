@@ -44,6 +44,7 @@ SYMBOLS = (
     "sm_default_fern_params", "sm_fern_table", "sm_set_ferns", "sm_fern_encode", "sm_fern_encode_device", "sm_fern_add", "sm_fern_count",
     "sm_fern_download", "sm_fern_save", "sm_fern_load", "sm_fern_match", "sm_search_pose_at", "sm_close_loop_at",
     "sm_default_auto_place_params", "sm_set_auto_place", "sm_auto_place_stats",
+    "sm_default_stereo_params", "sm_set_stereo", "sm_stereo_depth", "sm_stereo_depth_device", "sm_stereo_download",
 )
 
 SM_COLL_SUM, SM_COLL_MIN, SM_COLL_GATHER = 0, 1, 2
@@ -376,6 +377,22 @@ def fern_table(params, width, height) -> np.ndarray:
     return out
 
 
+class SmStereoParams(C.Structure):
+    _fields_ = [("max_disp", C.c_int32), ("paths", C.c_int32), ("p1", C.c_int32), ("p2", C.c_int32), ("uniqueness", C.c_int32),
+                ("lr_max_diff", C.c_int32), ("baseline", C.c_float)]
+
+
+def stereo_params(cfg, **over) -> SmStereoParams:
+    """sm_default_stereo_params (D 128, 8 paths, p1 7, p2 86, uniqueness 5 %, lr_max_diff 1, baseline 0.54 m) with fields overridden"""
+    p = SmStereoParams()
+    load().sm_default_stereo_params(C.byref(cfg), C.byref(p))
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
 def search_params(**over) -> SmSearchParams:
     """sm_default_search_params (2 levels; +-2 m in x and z at 0.25 m, +-3 deg about y at 0.5 deg; refine 4, stride0 8, top_k 4,
     colour_thresh 0.1) with fields overridden; the four per-axis fields take a sequence of three"""
@@ -696,6 +713,13 @@ def load():
     L.sm_set_auto_place.argtypes = [vp, C.POINTER(SmAutoPlaceParams)]
     L.sm_auto_place_stats.argtypes = [vp, C.POINTER(SmAutoPlaceStats)]
     L.sm_debug_place_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]     # (a diagnostic, not in the header)
+    stp = C.POINTER(SmStereoParams)
+    L.sm_default_stereo_params.argtypes = [C.POINTER(SmConfig), stp]
+    L.sm_set_stereo.argtypes = [vp, stp]
+    L.sm_stereo_depth.argtypes = [vp, vp, vp, vp, vp]
+    L.sm_stereo_depth_device.argtypes = [vp, vp, vp, vp, vp]
+    L.sm_stereo_download.argtypes = [vp, vp, vp, vp]
+    L.sm_debug_stereo_ms.argtypes = [vp, C.POINTER(C.c_float)]                          # (a diagnostic, not in the header)
     for name in SYMBOLS:
         getattr(L, name)          # AttributeError here = the library does not match the header
     _lib = L
@@ -1314,6 +1338,69 @@ class SurfelMap:
         d = {k: int(getattr(st, k)) for k, _ in SmAutoPlaceStats._fields_ if k != "last"}
         d["last"] = _loop_info_dict(st.last)
         return d
+
+    # -- stereo depth (sm_stereo_*)
+    def set_stereo(self, on=True, **params):
+        """Give the context the buffers of the stereo matcher (sm_set_stereo); params override stereo_params(cfg).  on False: free
+        them."""
+        p = stereo_params(self.cfg, **params) if on else None
+        self._chk(self._L.sm_set_stereo(self._h, C.byref(p) if on else None), "sm_set_stereo")
+        self._stereo = p
+
+    def _stereo_pair(self, rgb_left, rgb_right):
+        rgb_left, rgb_right = np.ascontiguousarray(rgb_left, np.uint8), np.ascontiguousarray(rgb_right, np.uint8)
+        assert rgb_left.shape == rgb_right.shape == (self.H, self.W, 3), (rgb_left.shape, rgb_right.shape)
+        return rgb_left, rgb_right
+
+    def stereo_depth(self, rgb_left, rgb_right):
+        """The depth image of a rectified pair (sm_stereo_depth): (depth_mm uint16[H][W], 0 = invalid, as process_frame takes it;
+        disp16 uint16[H][W], the disparity in sixteenths of a pixel, 0 = invalid).  rgb_* uint8[H][W][3]."""
+        rgb_left, rgb_right = self._stereo_pair(rgb_left, rgb_right)
+        depth, disp = np.zeros((self.H, self.W), np.uint16), np.zeros((self.H, self.W), np.uint16)
+        self._chk(self._L.sm_stereo_depth(self._h, _ptr(rgb_left), _ptr(rgb_right), _ptr(depth), _ptr(disp)), "sm_stereo_depth")
+        return depth, disp
+
+    def stereo_depth_device(self, d_left: int, d_right: int, d_depth: int, d_disp: int = 0):
+        """stereo_depth() of images in this context's device memory into device buffers of the caller's (sm_stereo_depth_device):
+        enqueued on the context's stream, not waited for"""
+        self._chk(self._L.sm_stereo_depth_device(self._h, d_left or None, d_right or None, d_depth or None, d_disp or None),
+                  "sm_stereo_depth_device")
+
+    def stereo_debug(self) -> dict:
+        """the intermediates of the last stereo call (sm_stereo_download): census_left, census_right uint64[H][W], volume
+        uint16[H][W][D]"""
+        if getattr(self, "_stereo", None) is None:
+            raise SurfelMapError("sm_stereo_download", SM_E_ARG, "the context has no stereo (set_stereo)")
+        H, W, D = self.H, self.W, int(self._stereo.max_disp)
+        cl, cr, vol = np.zeros((H, W), np.uint64), np.zeros((H, W), np.uint64), np.zeros((H, W, D), np.uint16)
+        self._chk(self._L.sm_stereo_download(self._h, _ptr(cl), _ptr(cr), _ptr(vol)), "sm_stereo_download")
+        return dict(census_left=cl, census_right=cr, volume=vol)
+
+    def stereo_ms(self):
+        """Device times in ms of the kernels of the last stereo call of a context whose set_stereo() ran with SM_STEREO_TIMING=1
+        (sm_debug_stereo_ms, not part of the C-ABI header): dict(census, cost, paths=[one per direction], select); None if it was
+        not timed."""
+        ms = (C.c_float * 11)()
+        self._chk(self._L.sm_debug_stereo_ms(self._h, ms), "sm_debug_stereo_ms")
+        if ms[0] < 0:
+            return None
+        return dict(census=float(ms[0]), cost=float(ms[1]), paths=[float(v) for v in ms[2:10] if v >= 0], select=float(ms[10]))
+
+    def process_frame_stereo(self, rgb_left, rgb_right, sem, pose):
+        """process_frame() with the depth estimated from the pair: the images are uploaded, sm_stereo_depth_device and
+        sm_process_frame_device are enqueued one after the other, and the depth never leaves the device.  sem None: the previous
+        class image stays.  The four device images it stages in are allocated by the first call and live as long as the context."""
+        rgb_left, rgb_right = self._stereo_pair(rgb_left, rgb_right)
+        if getattr(self, "_stereo_dev", None) is None:
+            P = self.P
+            self._stereo_dev = [self.device_alloc(P * 3), self.device_alloc(P * 3), self.device_alloc(P * 2), self.device_alloc(P)]
+        d_left, d_right, d_depth, d_sem = self._stereo_dev
+        self.device_upload(d_left, rgb_left)
+        self.device_upload(d_right, rgb_right)
+        if sem is not None:
+            self.device_upload(d_sem, np.ascontiguousarray(sem, np.uint8))
+        self.stereo_depth_device(d_left, d_right, d_depth)
+        return self.process_frame_device(d_left, d_depth, d_sem if sem is not None else None, pose)
 
     def auto_loop_stats(self) -> dict:
         """checked, attempts, closed, none, rejected, failed, no_old_map, last_census, and last = the last attempt's info as

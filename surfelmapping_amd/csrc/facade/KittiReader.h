@@ -2,8 +2,9 @@
 // gui/KittiReader.{h,cpp}) without OpenCV: reads <dir>/image_2/%06d.png (RGB), <dir>/PSMNet/%06d.png (u16 depth in
 // millimetres), <dir>/semantics/%06d.png (u8 train ids), calibration.txt ("fx fy cx cy" / "width height"), pose.txt
 // (3x4 row-major camera->world per line, right-multiplied by the -0.06 m x-offset T20: gui/KittiReader.cpp:296-302)
-// and times.txt.  PNG decoding: 8/16-bit grey, 8-bit RGB/RGBA, non-interlaced, all five filter types, zlib inflate
-// (link with -lz).  Only subLevel == 0 is supported (the reference's sub-sampling branch is unused by build_map.cpp:279
+// and times.txt.  With estimateDepth the reference skips PSMNet and hands on a null depth (gui/KittiReader.cpp:68,87); here the
+// flag also reads the right camera's <dir>/image_3/%06d.png into rgbRight, for SurfelMapping::processFrameStereo.
+// PNG decoding: 8/16-bit grey, 8-bit RGB/RGBA, non-interlaced, all five filter types, zlib inflate (link with -lz).  Only subLevel == 0 is supported (the reference's sub-sampling branch is unused by build_map.cpp:279
 // and writes the sub-sampled semantics into the depth buffer, gui/KittiReader.cpp:206).
 #pragma once
 #include <zlib.h>
@@ -85,7 +86,7 @@ class KittiReader {
 public:
     // gui/KittiReader.cpp:7-46
     KittiReader(std::string datasetDir, bool estimateDepth, bool useSemantic, int subLevel, bool groundTruth)
-        : depth(nullptr), rgb(nullptr), semantic(nullptr), currentFrameId(-1), time(0.0), savedFrameId(-1),
+        : depth(nullptr), rgb(nullptr), rgbRight(nullptr), semantic(nullptr), currentFrameId(-1), time(0.0), savedFrameId(-1),
           datasetDir_(std::move(datasetDir)), estimate_depth(estimateDepth), use_semantic(useSemantic), ok_(true)
     {
         if (subLevel != 0) { std::printf("KittiReader: subLevel != 0 is not supported\n"); ok_ = false; }
@@ -94,6 +95,7 @@ public:
         while (timesIn >> t) times.push_back(t);
         depthDir = datasetDir_ + "/PSMNet";
         rgbDir = datasetDir_ + "/image_2";
+        rgbRightDir = datasetDir_ + "/image_3";
         semanticDir = datasetDir_ + "/semantics";
         ok_ = loadCalibration() && ok_;
         if (groundTruth) ok_ = loadGroundTruth() && ok_;
@@ -118,6 +120,7 @@ public:
 
     unsigned short *depth;
     unsigned char *rgb;
+    unsigned char *rgbRight;                  // the right camera's image, R first; null unless estimateDepth
     unsigned char *semantic;
     int currentFrameId;
     double time;
@@ -167,15 +170,12 @@ private:
         std::snprintf(name, sizeof name, "/%06d.png", currentFrameId);
         const size_t P = (size_t)width_ * height_;
         sm_png::Image im;
-        if (!sm_png::read(rgbDir + name, im) || im.w != width_ || im.h != height_ || im.depth != 8) {
-            std::printf("CANNOT read RGB image from %s%s", rgbDir.c_str(), name);
-            return false;
-        }
-        rgbBuf_.resize(P * 3);
-        for (size_t p = 0; p < P; ++p)
-            for (int c = 0; c < 3; ++c) rgbBuf_[p * 3 + c] = im.channels >= 3 ? im.data[p * im.channels + c] : im.data[p * im.channels];
+        if (!loadRgb(rgbDir + name, im, rgbBuf_)) return false;
         rgb = rgbBuf_.data();                      // R first, as after the reference's BGR->RGB swap (gui/KittiReader.cpp:131-134)
-        if (!estimate_depth) {
+        if (estimate_depth) {
+            if (!loadRgb(rgbRightDir + name, im, rgbRightBuf_)) return false;
+            rgbRight = rgbRightBuf_.data();
+        } else {
             if (!sm_png::read(depthDir + name, im) || im.w != width_ || im.h != height_ || im.channels != 1) {
                 std::printf("CANNOT read depth image from %s%s", depthDir.c_str(), name);
                 return false;
@@ -196,13 +196,27 @@ private:
         return true;
     }
 
+    // an 8-bit colour (or grey) image of the calibration's size into buf, three bytes per pixel
+    bool loadRgb(const std::string &path, sm_png::Image &im, std::vector<unsigned char> &buf)
+    {
+        const size_t P = (size_t)width_ * height_;
+        if (!sm_png::read(path, im) || im.w != width_ || im.h != height_ || im.depth != 8) {
+            std::printf("CANNOT read RGB image from %s", path.c_str());
+            return false;
+        }
+        buf.resize(P * 3);
+        for (size_t p = 0; p < P; ++p)
+            for (int c = 0; c < 3; ++c) buf[p * 3 + c] = im.channels >= 3 ? im.data[p * im.channels + c] : im.data[p * im.channels];
+        return true;
+    }
+
     const std::string datasetDir_;
-    std::string depthDir, rgbDir, semanticDir;
+    std::string depthDir, rgbDir, rgbRightDir, semanticDir;
     int width_ = 0, height_ = 0;
     float fx_ = 0, fy_ = 0, cx_ = 0, cy_ = 0;
     bool estimate_depth, use_semantic, ok_;
     std::vector<double> times;
     std::vector<Eigen::Matrix4f> groundTruth_;
-    std::vector<unsigned char> rgbBuf_, semBuf_;
+    std::vector<unsigned char> rgbBuf_, rgbRightBuf_, semBuf_;
     std::vector<unsigned short> depthBuf_;
 };

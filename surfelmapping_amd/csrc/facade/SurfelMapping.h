@@ -455,6 +455,42 @@ public:
         return st;
     }
 
+    // Estimate depth from a rectified stereo pair (sm_set_stereo): what the reference's estimateDepth flag leaves undone.  baseline
+    // (metres) / maxDisp, if not negative, replace the defaults (0.54, 128).  on = false: off, and the matcher's buffers are freed.
+    bool setStereo(bool on, float baseline = -1.0f, int maxDisp = -1)
+    {
+        int rc;
+        if (!on) {
+            rc = sm_set_stereo(ctx_, nullptr);
+        } else {
+            sm_config c;
+            sm_default_config(&c, Config::W(), Config::H(), Config::fx(), Config::fy(), Config::cx(), Config::cy());
+            sm_stereo_params sp;
+            sm_default_stereo_params(&c, &sp);
+            if (baseline >= 0.0f) sp.baseline = baseline;
+            if (maxDisp >= 0) sp.max_disp = maxDisp;
+            rc = sm_set_stereo(ctx_, &sp);
+        }
+        if (rc == SM_OK) return true;
+        std::printf("setStereo: %s\n", sm_last_error());
+        return false;
+    }
+    // processFrame with the depth image estimated from the pair (sm_stereo_depth; setStereo(true) first): a null gtPose tracks
+    // with the estimated depth exactly as it would with a file's.  false (and nothing processed) if the estimate fails.
+    bool processFrameStereo(const unsigned char *rgbLeft, const unsigned char *rgbRight, const unsigned char *semantic = nullptr,
+                            const Eigen::Matrix4f *gtPose = nullptr)
+    {
+        stereoDepth_.resize((size_t)Config::W() * Config::H());
+        if (sm_stereo_depth(ctx_, rgbLeft, rgbRight, stereoDepth_.data(), nullptr) != SM_OK) {
+            std::printf("processFrameStereo: %s\n", sm_last_error());
+            return false;
+        }
+        processFrame(rgbLeft, stereoDepth_.data(), semantic, gtPose);
+        return true;
+    }
+    // the depth image (millimetres, 0 = invalid) of the last processFrameStereo; empty before the first
+    const std::vector<unsigned short> &getLastStereoDepth() { return stereoDepth_; }
+
     // With setAutoRetire on: after every retirement, the records of its map files within `radius` metres of that frame's camera
     // come back into the model and leave the files, so that a camera that returns finds what it left (sm_set_auto_recall;
     // 0 < radius <= the retirement's minDistance).  radius <= 0: off.
@@ -503,6 +539,7 @@ private:
         loopParams_.max_trans = loopMaxTrans_;
         return &loopParams_;
     }
+    std::vector<unsigned short> stereoDepth_;
     bool beginCleanPoints = false;
     bool async_ = false;
 };

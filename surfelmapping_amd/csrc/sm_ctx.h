@@ -15,6 +15,7 @@
 //   sm_search.hip    pose search before the tracker (sm_score_poses_window, sm_search_pose)
 //   sm_lidar.hip     lidar sweeps (sm_lidar_*): beams against the live model and against streamed map files
 //   sm_place.hip     place recognition (sm_fern_*, sm_search_pose_at, sm_close_loop_at): fern codes, the keyframe database, the match
+//   sm_stereo.hip    stereo depth (sm_stereo_*): census, matching costs, path costs, winner and depth of a rectified pair
 // and, beside it, for everything that touches a map file: sm_mapfile.h (the format: checked open, writer, chunk plan; host only)
 // and sm_map_stream.h (the double-buffered chunk stream of sm_render_maps.hip and sm_recall.hip); for the occupied slots and the
 // compaction schedule: sm_slots.h (SlotSchedule; host only); for the arithmetic of rigid poses in double: sm_pose.h (host only,
@@ -266,6 +267,20 @@ struct Place {
     sm_auto_place_stats_t stats{};
 };
 
+// stereo depth (sm_stereo.hip, sm_k_stereo.h): everything sm_set_stereo allocates.  on = false: none of it exists.
+struct Stereo {
+    static constexpr int N_EV = 12;    // before the census, after it, after the costs, after each of up to 8 directions, after the selection
+    bool on = false;
+    sm_stereo_params p{};
+    Dev<uint8_t> d_left, d_right;      // sm_stereo_depth's copies of the host images
+    Dev<uint64_t> d_census[2];         // left, right
+    Dev<uint8_t> d_cost;               // the matching costs, [y][x][d]
+    Dev<uint16_t> d_vol;               // S, [y][x][d]
+    Dev<uint16_t> d_depth, d_disp;     // the outputs of a call that names none of its own
+    bool timed = false;                // SM_STEREO_TIMING=1 at sm_set_stereo: events around every kernel (tools/stereo_probe.py)
+    Event ev[N_EV];
+};
+
 // closing loops unasked (sm_loop.hip): the policy of sm_set_auto_loop and its tally
 struct AutoLoop {
     bool on = false;
@@ -498,6 +513,7 @@ struct sm_ctx {
     Search srch;
     Lidar lid;
     Place place;
+    Stereo stereo;
     // host frame state (src/SurfelMapping.h:100-103)
     int tick = 0;
     bool ref_set = false;

@@ -149,6 +149,15 @@ def make_sequence(cam_kw: dict, poses, seed: int = 0, noise_mm: float = 0.0, sce
     return out
 
 
+def stereo_pair(scene: Scene, cam: Camera, pose: np.ndarray, baseline: float = 0.54, **kw):
+    """A rectified stereo pair of the scene: (rgb_left, rgb_right, depth_left, sem_left).  `pose` is the left camera's 4x4
+    camera->world matrix; the right camera is pose @ pose_matrix(baseline, 0, 0), `baseline` metres along the left camera's x.
+    kw goes to Scene.render (noise_mm, noise_seed), for both views."""
+    rgb_l, depth_l, sem_l = scene.render(cam, pose, **kw)
+    rgb_r, _, _ = scene.render(cam, np.asarray(pose, dtype=np.float64) @ pose_matrix(baseline, 0.0, 0.0), **kw)
+    return rgb_l, rgb_r, depth_l, sem_l
+
+
 def _render_job(job):
     cam_kw, pose, seed, k, noise_mm, scene_kw = job
     scene = Scene(**scene_kw) if scene_kw else Scene(seed)

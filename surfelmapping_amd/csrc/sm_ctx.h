@@ -9,21 +9,24 @@
 //   sm_rccl.hip      the RCCL binding (sm_shard_rccl_*)
 //   sm_rig.hip       rig consolidation (sm_rig_*)
 //   sm_retire.hip    retirement (sm_retire*, sm_set_auto_retire)
-//   sm_render_maps.hip  views of a map set (sm_render_*_maps): map files streamed through the renderers
+//   sm_render_maps.hip  views of a map set (sm_render_*_maps): map files streamed through the renderers; the staging's allocation and intake
 //   sm_recall.hip    paging in (sm_recall*, sm_set_auto_recall): records of map files near the camera back into the model
 //   sm_warp.hip      closing loops (sm_warp_by_time, sm_loop_spread): the model and map files warped by surfel time
 //   sm_search.hip    pose search before the tracker (sm_score_poses_window, sm_search_pose)
 //   sm_lidar.hip     lidar sweeps (sm_lidar_*): beams against the live model and against streamed map files
 //   sm_place.hip     place recognition (sm_fern_*, sm_search_pose_at, sm_close_loop_at): fern codes, the keyframe database, the match
 //   sm_stereo.hip    stereo depth (sm_stereo_*): census, matching costs, path costs, winner and depth of a rectified pair
-// and, beside it, for everything that touches a map file: sm_mapfile.h (the format: checked open, writer, chunk plan; host only)
-// and sm_map_stream.h (the double-buffered chunk stream of sm_render_maps.hip and sm_recall.hip); for the occupied slots and the
+// and, beside it, for everything that touches a map file: sm_mapfile.h (the format: checked open, writer, chunk plan; host only),
+// sm_map_set.h (a listed set of files: the file index, the two openings, a rewrite's per-file record and temporary; host only) and
+// sm_map_stream.h (the double-buffered chunk stream of sm_render_maps.hip, sm_lidar.hip, sm_recall.hip and sm_warp.hip).  The staging
+// those four stream through (MapStaging) and the file index (FileIndex) are the context's, no feature's.  For the occupied slots and the
 // compaction schedule: sm_slots.h (SlotSchedule; host only); for the arithmetic of rigid poses in double: sm_pose.h (host only,
 // included by sm_track.hip and sm_warp.hip).  What alternates between consecutive frames is FrameSet, below.
 #pragma once
 
 #include "../../include/sm_c_api.h"
 #include "sm_device.h"
+#include "sm_map_set.h"
 #include "sm_slots.h"
 
 #include <hip/hip_runtime.h>
@@ -162,11 +165,10 @@ struct Retire {
     Event ev[8];
 };
 
-// views of a map set (sm_render_maps.hip, sm_k_render_maps.h): the staging of the file stream, allocated by the first call, and
-// the last call's tally.  Chunk c of a pass goes through buffer c & 1 (MapStream, sm_map_stream.h, which sm_recall.hip uses as
-// well): read into h_rec, copied on `copy` into d_rec, unpacked into the one set of SoA planes by the intake kernel on the
-// context's stream.
-struct RenderMaps {
+// The staging every stream of map-file chunks goes through (streamed renderers, lidar, recall, warp), allocated whole by the first
+// call that reads a file (maps_ensure_staging).  Chunk c of a pass goes through buffer c & 1 (MapStream, sm_map_stream.h): read into
+// h_rec, copied on `copy` into d_rec; the renderers and the lidar unpack it into the one set of SoA planes (maps_intake).
+struct MapStaging {
     static constexpr uint32_t CHUNK = 1u << 20;          // records per chunk (48 MiB), the chunk sm_retire writes files in
     Stream copy;                       // first: what follows is used on it
     Host<float4> h_rec[2];             // pinned
@@ -176,18 +178,19 @@ struct RenderMaps {
     Dev<float4> d_pos_conf, d_norm_rad, d_box;
     Dev<uint32_t> d_color;
     Dev<float> d_time;
+};
+
+// views of a map set (sm_render_maps.hip, sm_k_render_maps.h): the per-view block and the last call's tally
+struct RenderMaps {
     Dev<uint8_t> d_par;                // per-view parameters | shading | skipped counters | hit flags
     size_t par_bytes = 0;
+    Event ev[2];                       // around the live model's kernels
     sm_maps_stats stats{};
     bool stats_valid = false;
 };
 
-// paging in (sm_recall.hip, sm_k_recall.h): scratch allocated by the first call that reads a file, the file index, the last
-// call's tally, the periodic policy and its tally.  The records stream through RenderMaps' staging.
+// paging in (sm_recall.hip, sm_k_recall.h): scratch of the first call that reads a file, the last call's tally, the policy and its tally
 struct Recall {
-    // what the context knows of a map file it has read: valid while the file's size and mtime are these
-    struct Entry { uint64_t size; int64_t mtime_ns; float lo[3], hi[3]; float max_time; };   // box of the rows' finite centres (lo > hi: none); largest non-NaN m[7] (-inf: none)
-    std::map<std::string, Entry> index;
     Dev<uint64_t> d_mask;              // 4 words per block of 256 records: near
     Dev<uint32_t> d_blk_cnt, d_blk_base, d_run;   // near per block, their exclusive prefix, the call's running total
     Dev<float4> d_box;                 // recall_box_of's own block boxes (the retirement policy has no stream staging)
@@ -200,8 +203,7 @@ struct Recall {
     uint64_t surfels = 0;              // ... and the surfels they brought back
 };
 
-// the warp by surfel time (sm_warp.hip, sm_k_warp.h): scratch allocated by the first call, the last call's tally.  The files
-// stream through RenderMaps' staging and are warped in it; the file index is Recall's.
+// the warp by surfel time (sm_warp.hip, sm_k_warp.h): scratch allocated by the first call, the last call's tally
 struct Warp {
     Dev<float4> d_corr;                // the table, 3 float4 per row
     size_t corr_rows = 0;
@@ -228,7 +230,7 @@ struct Search {
 };
 
 // lidar sweeps (sm_lidar.hip, sm_k_lidar.h): the last sensor's tables on the device, the per-sweep poses, the device tally and
-// the last call's.  Keys and output planes live in the export scratch; the files stream through RenderMaps' staging.
+// the last call's.  Keys and output planes live in the export scratch.
 struct Lidar {
     Dev<float> d_dir, d_el;            // the direction table (n_el * n_az * 3) and the elevations in radians
     std::vector<float> key;            // what the tables on the device were made of: n_az, n_el, az0, step, the elevations
@@ -503,6 +505,8 @@ struct sm_ctx {
     // export staging
     Dev<void> d_export;
     size_t export_bytes = 0;
+    MapStaging staging;                // of every stream of map-file chunks
+    sm_mapset::FileIndex index;        // of the map files the context has read or written (retirement, recall, warp)
     ModelView rm;
     Tracker trk;
     Retire ret;
@@ -571,8 +575,8 @@ int view_splat_model(sm_ctx *s, const ViewParams &vp, uint64_t *key, uint32_t *d
 // ---- sm_retire.hip ----
 int auto_retire_after_frame(sm_ctx *s);           // the periodic policy: called once a frame is enqueued (one test unless it is due)
 // ---- sm_render_maps.hip ----
-int maps_ensure_staging(sm_ctx *s);               // RenderMaps' copy stream, record buffers and events: whole or absent
-// k_maps_intake on the context's stream: n records at d_rec into RenderMaps' SoA planes and its one box per 256 records
+int maps_ensure_staging(sm_ctx *s);               // the staging's copy stream, buffers and events: whole or absent
+// k_maps_intake on the context's stream: n records at d_rec into the staging's SoA planes and its one box per 256 records
 void maps_intake(sm_ctx *s, const float4 *d_rec, uint32_t n);
 // ---- sm_recall.hip ----
 // the periodic policy: called by a frame that has just retired (one test unless it is on).  wrote_file: this round's retirement
@@ -580,9 +584,8 @@ void maps_intake(sm_ctx *s, const float4 *d_rec, uint32_t n);
 int auto_recall_after_retire(sm_ctx *s, bool wrote_file);
 // For the file index, when the retirement policy writes a file (its setter has allocated the scratch): the box of the finite
 // centres and the largest non-NaN time of n AoS records in device memory folded into lo / hi / *max_time (k_recall_mark +
-// k_recall_scan on the context's stream; waits), and the entry of a map file the context has just written itself with them
+// k_recall_scan on the context's stream; waits)
 int recall_box_of(sm_ctx *s, const float *d_rec12, uint32_t n, float lo[3], float hi[3], float *max_time);
-void recall_note_written(sm_ctx *s, const std::string &path, const float lo[3], const float hi[3], float max_time);
 int recall_ensure_scratch(sm_ctx *s);             // what recall_box_of needs (sm_set_auto_retire allocates it with its own)
 // what the two policies require of each other when both are on (SM_E_ARG with g_err set otherwise)
 int check_recall_policy(float radius, const sm_retire_params &rp, const char *who);
@@ -649,6 +652,13 @@ int close_loop(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const fl
 inline int check_whole_map(const sm_ctx *s, const char *who)
 {
     if (s->ss_on || s->rig_on) { g_err = std::string(who) + ": a sharded or rig context holds only its own surfels"; return SM_E_UNSUPPORTED; }
+    return SM_OK;
+}
+
+// ... and what reads or changes the whole model refuses the half-done cull of the per-pass stage API
+inline int check_not_mid_cull(const sm_ctx *s, const char *who)
+{
+    if (s->pending_cull) { g_err = std::string(who) + " between sm_stage_conflict and sm_stage_cull"; return SM_E_ARG; }
     return SM_OK;
 }
 

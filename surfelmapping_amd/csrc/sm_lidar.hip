@@ -1,5 +1,5 @@
 // sm_lidar.hip -- lidar sweeps (sm_lidar_sweep, sm_lidar_sweep_maps; DESIGN.md "4k. Lidar sweeps"): the beams of a spherical grid
-// against the live model and against map files streamed in chunks, the live model last.  Kernels: sm_k_lidar.h.
+// against the live model and against map files streamed in chunks through the context's MapStaging, the live model last.  Kernels: sm_k_lidar.h.
 #include "sm_map_stream.h"
 #include "sm_k_lidar.h"
 #include "sm_pose.h"
@@ -81,28 +81,12 @@ int sweep(sm_ctx *s, const sm_map_source *src, const sm_lidar_sensor *sn, const 
     if ((rc = check_sensor(sn, fn))) return rc;
     for (uint32_t i = 0; i < n_sweeps; ++i)
         if ((rc = check_pose(poses16 + (size_t)i * 16, fn))) return rc;
-    if ((rc = check_whole_map(s, fn))) return rc;
-    if (s->pending_cull) { g_err = std::string(fn) + " between sm_stage_conflict and sm_stage_cull"; return SM_E_ARG; }
     static const sm_map_source model_only{nullptr, 0, 1};
     if (!src) src = &model_only;
-    if ((rc = check_map_source(src, fn))) return rc;
-    // the headers of all files, each against its length, before anything else
-    std::vector<sm_mapfile::Header> files(src->n_paths);
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < src->n_paths; ++i) {
-        if (!sm_mapfile::open_checked(src->paths[i], fn, files[i], g_err)) return SM_E_ARG;
-        total += files[i].count;
-    }
-    const std::vector<sm_mapfile::Job> jobs = sm_mapfile::chunk_plan(files, RenderMaps::CHUNK);
-    std::vector<uint64_t> id_base(files.size());         // of each file's first record in the set
-    for (size_t i = 1; i < files.size(); ++i) id_base[i] = id_base[i - 1] + files[i - 1].count;
-    HIPCK(hipSetDevice(s->cfg.device));
-    if ((rc = ensure_compact(s))) return rc;
-    if ((rc = pull_state(s))) return rc;                 // (waits for frames in flight; count is the live surfels)
-    const uint32_t cnt = src->include_model ? s->h_state->count : 0u;
-    const uint64_t file_total = total;
-    total += cnt;
-    if (total > 0x7FFFFFFFull) { g_err = std::string(fn) + ": the map set holds " + std::to_string(total) + " surfels, ids end at 2^31 - 1"; return SM_E_CAPACITY; }
+    sm_mapset::ReadSet set;
+    uint32_t cnt;
+    if ((rc = maps_open(s, src, fn, check_whole_map, set, cnt))) return rc;
+    const uint64_t file_total = set.file_total;
     Lidar &L = s->lid;
     L.stats = sm_lidar_stats_t{};
     L.stats_valid = true;
@@ -110,12 +94,9 @@ int sweep(sm_ctx *s, const sm_map_source *src, const sm_lidar_sensor *sn, const 
     if (file_total && (rc = maps_ensure_staging(s))) return rc;
     if ((rc = ensure_tables(s, sn))) return rc;
 
-    const char *e = std::getenv("SM_LIDAR_NO_CULL");
-    const int cull = (e && e[0] == '1') ? 0 : 1;
-    size_t key_mb = 1024;
-    if (const char *k = std::getenv("SM_LIDAR_KEY_MB")) key_mb = (size_t)std::min(8192L, std::max(1L, std::atol(k)));
     const size_t nb = (size_t)sn->n_az * sn->n_el;
-    const uint32_t B = (uint32_t)std::min<uint64_t>(std::min<uint32_t>(n_sweeps, 4096u), std::max<uint64_t>(1, (key_mb << 20) / (nb * 8)));
+    int cull;
+    const uint32_t B = maps_batch(n_sweeps, nb, "SM_LIDAR_KEY_MB", "SM_LIDAR_NO_CULL", &cull);
 
     LidarGrid g{};
     g.dir = L.d_dir; g.el = L.d_el;
@@ -158,8 +139,7 @@ int sweep(sm_ctx *s, const sm_map_source *src, const sm_lidar_sensor *sn, const 
     int32_t *d_id = (int32_t *)(base + off_id);
     uint8_t *d_rgb = base + off_rgb, *d_sem = base + off_sem;
 
-    RenderMaps &rm = s->maps;
-    const MapsSoA chunk{rm.d_pos_conf, rm.d_norm_rad, rm.d_color, rm.d_time};
+    const MapsSoA chunk = planes(s->staging);
     const SurfelSet cur = s->M.s[s->h_state->cur];
     MapStream in(s, fn, src->paths, {&L.stats.read_ms, &L.stats.copy_ms, &L.stats.device_ms});
 
@@ -175,14 +155,14 @@ int sweep(sm_ctx *s, const sm_map_source *src, const sm_lidar_sensor *sn, const 
         fill_keys(s, d_key, bp);
 
         // ---- the files, chunk by chunk: the host reads chunk c + 1 while the copy and the kernels of chunk c run
-        for (in.begin(jobs); in.more();) {
+        for (in.begin(set.jobs); in.more();) {
             MapStream::Chunk ck;
             if ((rc = in.next(ck))) return rc;
             const uint32_t n = ck.job->n;
             const unsigned nblk = (n + MAPS_BLOCK - 1) / MAPS_BLOCK;
             maps_intake(s, ck.d_rec, n);
-            const uint32_t gid = (uint32_t)(id_base[ck.job->file] + ck.job->first);
-            hipLaunchKernelGGL(k_lidar_splat_maps, dim3(nblk, b), dim3(256), 0, s->stream, chunk, n, gid, (const float4 *)rm.d_box.get(), g,
+            const uint32_t gid = (uint32_t)(set.id_base[ck.job->file] + ck.job->first);
+            hipLaunchKernelGGL(k_lidar_splat_maps, dim3(nblk, b), dim3(256), 0, s->stream, chunk, n, gid, (const float4 *)s->staging.d_box.get(), g,
                                d_poses + v0, d_key, nb, cull, d_tally);
             resolve(chunk.color, gid, n, 0);
             if ((rc = in.done(ck.q))) return rc;

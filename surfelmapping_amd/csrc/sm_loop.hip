@@ -4,7 +4,6 @@
 // internal bodies (track_windowed, close_loop), not the public entry points: the policy is not re-entered.  Host code only: the kernels are the trackers'
 // (sm_k_track.h, sm_k_loop.h) and the warp's (sm_k_warp.h).
 #include "sm_ctx.h"
-#include "sm_mapfile.h"
 
 using namespace sm;
 
@@ -84,13 +83,8 @@ int sm_set_auto_loop(sm_ctx *s, const sm_auto_loop_params *p, const sm_map_sourc
     std::vector<std::string> paths;
     if (src) {
         if ((rc = check_map_source(src, who))) return rc;
-        for (uint32_t i = 0; i < src->n_paths; ++i) {
-            if (std::find(paths.begin(), paths.end(), src->paths[i]) != paths.end()) {
-                g_err = std::string(who) + ": " + src->paths[i] + " is listed twice";
-                return SM_E_ARG;
-            }
-            paths.push_back(src->paths[i]);
-        }
+        if (!sm_mapset::check_distinct_paths(src->paths, src->n_paths, who, g_err)) return SM_E_ARG;
+        paths.assign(src->paths, src->paths + src->n_paths);
     }
     a.on = true;
     a.p = *p;

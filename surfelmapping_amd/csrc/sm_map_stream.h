@@ -1,15 +1,21 @@
-// sm_map_stream.h -- private to sm_render_maps.hip, sm_recall.hip and sm_warp.hip: the double-buffered stream of map-file chunks through
-// RenderMaps' staging, one object per call.  Chunk c of a pass goes through buffer q = c & 1: read into h_rec[q] (timed into
-// read_ms), copied on `copy` into d_rec[q], and the context's stream waits for the copy; the caller then launches its kernels on
-// d_rec[q] and says done(q).  fold(q) waits for them and adds the buffer's event times to the caller's tally.  The host reads
-// chunk c while chunk c - 1 is on the device: next() waits only for chunk c - 2, the last user of its buffer, and that one wait
-// frees both sides (the copy out of h_rec[q] and the kernels that read d_rec[q] precede the event).
+// sm_map_stream.h -- private to sm_render_maps.hip, sm_lidar.hip, sm_recall.hip and sm_warp.hip: the double-buffered stream of
+// map-file chunks through the context's MapStaging, one object per call; behind it what the two readers of whole sets (the
+// streamed renderers, the lidar) do alike: the opening (maps_open) and the batch of views (maps_batch).  Chunk c of a pass goes
+// through buffer q = c & 1: read into h_rec[q] (timed into read_ms), copied on `copy` into d_rec[q], and the context's stream
+// waits for the copy; the caller then launches its kernels on d_rec[q] and says done(q).  fold(q) waits for them and adds the
+// buffer's event times to the caller's tally.  The host reads chunk c while chunk c - 1 is on the device: next() waits only for
+// chunk c - 2, the last user of its buffer, and that one wait frees both sides (the copy out of h_rec[q] and the kernels that
+// read d_rec[q] precede the event).
 #pragma once
 
 #include "sm_ctx.h"
-#include "sm_mapfile.h"
+#include "sm_k_maps_box.h"
+
+#include <cstdlib>
 
 namespace sm_impl __attribute__((visibility("hidden"))) {
+
+inline MapsSoA planes(const MapStaging &st) { return {st.d_pos_conf, st.d_norm_rad, st.d_color, st.d_time}; }
 
 class MapStream {
 public:
@@ -17,12 +23,12 @@ public:
     struct Chunk { int q; const sm_mapfile::Job *job; const float4 *d_rec; };
 
     // paths: by Job::file.  The staging exists (maps_ensure_staging) before the first next().
-    MapStream(sm_ctx *s, const char *who, const char *const *paths, Tally t) : s_(s), rm_(s->maps), who_(who), paths_(paths), t_(t) {}
+    MapStream(sm_ctx *s, const char *who, const char *const *paths, Tally t) : s_(s), st_(s->staging), who_(who), paths_(paths), t_(t) {}
     // A stream that goes away with a chunk in flight -- any failed call -- drains `copy` and the context's stream, nothing wider.
     ~MapStream()
     {
         if (!in_flight_[0] && !in_flight_[1]) return;
-        (void)hipStreamSynchronize(rm_.copy);
+        (void)hipStreamSynchronize(st_.copy);
         (void)hipStreamSynchronize(s_->stream);
     }
     // a pass over `jobs` begins (nothing of an earlier pass is in flight: it ended with fold() of both buffers)
@@ -42,23 +48,23 @@ public:
             if (!in_) return SM_E_ARG;
         }
         const double t0 = sm_mapfile::now_ms();
-        const bool got = sm_mapfile::read_rows(in_.get(), rm_.h_rec[q].get(), j.n);
+        const bool got = sm_mapfile::read_rows(in_.get(), st_.h_rec[q].get(), j.n);
         *t_.read_ms += (float)(sm_mapfile::now_ms() - t0);
         if (!got) { g_err = sm_mapfile::said(who_, paths_[j.file], " read err!!"); return SM_E_ARG; }
         in_flight_[q] = true;
-        HIPCK(hipEventRecord(rm_.ev_copy0[q], rm_.copy));
-        HIPCK(hipMemcpyAsync(rm_.d_rec[q], rm_.h_rec[q], (size_t)j.n * sm_mapfile::RECORD_BYTES, hipMemcpyHostToDevice, rm_.copy));
-        HIPCK(hipEventRecord(rm_.ev_copied[q], rm_.copy));
-        HIPCK(hipStreamWaitEvent(s_->stream, rm_.ev_copied[q], 0));
-        HIPCK(hipEventRecord(rm_.ev_k0[q], s_->stream));
-        ck = {q, &j, rm_.d_rec[q].get()};
+        HIPCK(hipEventRecord(st_.ev_copy0[q], st_.copy));
+        HIPCK(hipMemcpyAsync(st_.d_rec[q], st_.h_rec[q], (size_t)j.n * sm_mapfile::RECORD_BYTES, hipMemcpyHostToDevice, st_.copy));
+        HIPCK(hipEventRecord(st_.ev_copied[q], st_.copy));
+        HIPCK(hipStreamWaitEvent(s_->stream, st_.ev_copied[q], 0));
+        HIPCK(hipEventRecord(st_.ev_k0[q], s_->stream));
+        ck = {q, &j, st_.d_rec[q].get()};
         ++c_;
         return SM_OK;
     }
     // the caller has launched everything that belongs to the chunk in buffer q
     int done(int q)
     {
-        HIPCK(hipEventRecord(rm_.ev_k1[q], s_->stream));
+        HIPCK(hipEventRecord(st_.ev_k1[q], s_->stream));
         return SM_OK;
     }
     // waits for the chunk in buffer q, if there is one, and folds its times into the tally
@@ -66,10 +72,10 @@ public:
     {
         if (!in_flight_[q]) return SM_OK;
         float ms = 0.0f;
-        HIPCK(hipEventSynchronize(rm_.ev_k1[q]));
-        HIPCK(hipEventElapsedTime(&ms, rm_.ev_copy0[q], rm_.ev_copied[q]));
+        HIPCK(hipEventSynchronize(st_.ev_k1[q]));
+        HIPCK(hipEventElapsedTime(&ms, st_.ev_copy0[q], st_.ev_copied[q]));
         *t_.copy_ms += ms;
-        HIPCK(hipEventElapsedTime(&ms, rm_.ev_k0[q], rm_.ev_k1[q]));
+        HIPCK(hipEventElapsedTime(&ms, st_.ev_k0[q], st_.ev_k1[q]));
         *t_.device_ms += ms;
         in_flight_[q] = false;
         return SM_OK;
@@ -78,7 +84,7 @@ public:
 private:
     static constexpr uint32_t NO_FILE = 0xFFFFFFFFu;
     sm_ctx *s_;
-    RenderMaps &rm_;
+    MapStaging &st_;
     const char *who_;
     const char *const *paths_;
     Tally t_;
@@ -88,5 +94,32 @@ private:
     uint32_t in_file_ = NO_FILE;
     bool in_flight_[2] = {false, false};   // the buffer's events have been recorded and not yet folded
 };
+
+// What sm_render_*_maps and sm_lidar_sweep* do between their own argument checks and their own scratch: `whole` (the entry
+// point's own refusal of a context that holds a part of the map), the half-done cull, the source; every file's header against
+// its length before the device is touched; then the model compact and its count known.  cnt: the live surfels that take part.
+template <typename Whole>
+int maps_open(sm_ctx *s, const sm_map_source *src, const char *fn, Whole whole, sm_mapset::ReadSet &set, uint32_t &cnt)
+{
+    int rc;
+    if ((rc = whole(s, fn)) || (rc = check_not_mid_cull(s, fn)) || (rc = check_map_source(src, fn))) return rc;
+    if (!sm_mapset::open_read_set(src->paths, src->n_paths, MapStaging::CHUNK, fn, set, g_err)) return SM_E_ARG;
+    HIPCK(hipSetDevice(s->cfg.device));
+    if ((rc = ensure_compact(s)) || (rc = pull_state(s))) return rc;   // (waits for frames in flight; count is the live surfels)
+    cnt = src->include_model ? s->h_state->count : 0u;
+    const uint64_t total = set.file_total + cnt;
+    if (total > 0x7FFFFFFFull) { g_err = std::string(fn) + ": the map set holds " + std::to_string(total) + " surfels, ids end at 2^31 - 1"; return SM_E_CAPACITY; }
+    return SM_OK;
+}
+
+// Views (sweeps) per pass over the files: all of them, at most 4096, at most what <key_mb_var> MiB (default 1024, 1..8192: at
+// most 2^30 keys per batch) hold at `keys` 8-byte keys per view.  *cull: 0 with <no_cull_var>=1, the splat then tests every block.
+inline uint32_t maps_batch(uint32_t views, size_t keys, const char *key_mb_var, const char *no_cull_var, int *cull)
+{
+    const char *e = std::getenv(no_cull_var), *k = std::getenv(key_mb_var);
+    *cull = (e && e[0] == '1') ? 0 : 1;
+    const size_t key_mb = k ? (size_t)std::min(8192L, std::max(1L, std::atol(k))) : 1024;
+    return (uint32_t)std::min<uint64_t>(std::min<uint32_t>(views, 4096u), std::max<uint64_t>(1, (key_mb << 20) / (keys * 8)));
+}
 
 }  // namespace sm_impl

@@ -31,7 +31,7 @@ int sm_download_model_aos(sm_ctx *s, float *dst12, uint32_t cap, uint32_t *n)
     *n = cnt;
     if (!dst12) return SM_OK;
     if (cap < cnt) { g_err = "sm_download_model_aos: destination too small"; return SM_E_CAPACITY; }
-    if (s->pending_cull) { g_err = "sm_download_model_aos between sm_stage_conflict and sm_stage_cull"; return SM_E_ARG; }
+    if (int rc = check_not_mid_cull(s, "sm_download_model_aos")) return rc;
     const uint32_t CH = 1u << 22;                // 4 Mi surfels (192 MiB) per staging chunk
     if ((rc = ensure_export(s, (size_t)std::min(cnt, CH) * 48))) return rc;
     return drain_export(s, cnt, CH, dst12, 12, [s](float *d, uint32_t first, uint32_t m) { export_aos(s, d, first, m); }, no_hook);
@@ -165,7 +165,7 @@ int sm_render_image(sm_ctx *s, const float *view16, int w, int h, float fx, floa
 {
     if (!s || !view16 || w <= 0 || h <= 0 || (uint64_t)w * h > (1u << 28) || !bgr_out || !sem_out) return SM_E_ARG;
     HIPCK(hipSetDevice(s->cfg.device));
-    if (s->pending_cull) { g_err = "sm_render_image between sm_stage_conflict and sm_stage_cull"; return SM_E_ARG; }
+    if (int rc = check_not_mid_cull(s, "sm_render_image")) return rc;
     int rc = ensure_compact(s);
     if (rc) return rc;
     if ((rc = pull_state(s))) return rc;
@@ -224,7 +224,7 @@ int sm_export_model_device(sm_ctx *s, void **d_aos, uint32_t *n)
     if (!s || !d_aos || !n) return SM_E_ARG;
     if (hip_runtime_conflict("sm_export_model_device")) return SM_E_HIP;     // the pointer goes to foreign code (RCCL)
     HIPCK(hipSetDevice(s->cfg.device));
-    if (s->pending_cull) { g_err = "sm_export_model_device between sm_stage_conflict and sm_stage_cull"; return SM_E_ARG; }
+    if (int rc = check_not_mid_cull(s, "sm_export_model_device")) return rc;
     int rc = ensure_compact(s);
     if (rc) return rc;
     if ((rc = pull_state(s))) return rc;
@@ -245,7 +245,7 @@ int sm_append_model_aos_device(sm_ctx *s, const float *d_src12, uint32_t n)
     if (!s || (!d_src12 && n)) return SM_E_ARG;
     if (hip_runtime_conflict("sm_append_model_aos_device")) return SM_E_HIP;
     HIPCK(hipSetDevice(s->cfg.device));
-    if (s->pending_cull) { g_err = "sm_append_model_aos_device between sm_stage_conflict and sm_stage_cull"; return SM_E_ARG; }
+    if (int rc = check_not_mid_cull(s, "sm_append_model_aos_device")) return rc;
     int rc = ensure_compact(s);
     if (rc) return rc;
     if ((rc = pull_state(s))) return rc;

@@ -1,6 +1,6 @@
 // sm_recall.hip -- paging in (sm_recall, the periodic policy of sm_set_auto_recall; DESIGN.md "4g. Paging in"): the records of
-// map files that lie near the camera come back into the model, streamed through the staging of sm_render_maps.hip.
-// Kernels: sm_k_recall.h.
+// map files that lie near the camera come back into the model, streamed through the context's MapStaging (MapStream); the host half
+// of a rewrite of listed files (index, opening, temporaries, replacement) is sm_map_set.h's.  Kernels: sm_k_recall.h.
 //
 // One pass over the files.  The near records of every chunk are appended speculatively into the free slots above `count`
 // (never at or above MAX_VERTICES); the count is published only when every file has been read and every temporary of a MOVE is
@@ -12,12 +12,12 @@
 #include <cstdlib>
 
 using namespace sm;
-using sm_mapfile::Job;
 using sm_mapfile::now_ms;
+using sm_mapset::MapFile;
 
 namespace {
 
-constexpr uint32_t CHUNK = RenderMaps::CHUNK;
+constexpr uint32_t CHUNK = MapStaging::CHUNK;
 static_assert(CHUNK / RECALL_BLOCK == RECALL_MAX_BLOCKS, "a chunk's blocks are scanned by one workgroup");
 
 // ---------------------------------------------------------------------------------------------
@@ -47,26 +47,12 @@ float axis_gap(float lo, float hi, float c)
     return g > 0.0f ? g : 0.0f;
 }
 
-bool box_out_of_reach(const Recall::Entry &e, const float *c, float r2)
+bool box_out_of_reach(const sm_mapset::FileIndex::Entry &e, const float *c, float r2)
 {
     const float gx = axis_gap(e.lo[0], e.hi[0], c[0]), gy = axis_gap(e.lo[1], e.hi[1], c[1]), gz = axis_gap(e.lo[2], e.hi[2], c[2]);
     const float lb = (gx * gx + gy * gy) + gz * gz;
     return lb > r2;
 }
-
-// one listed file through the call
-struct MapFile {
-    std::string path;
-    bool skipped = false;              // by the index: not opened
-    sm_mapfile::Header h;              // count 0 unless the file is read
-    float lo[3], hi[3];                // box of this read
-    float tmax = -__builtin_inff();    // largest non-NaN time of this read
-    uint32_t chunks_left = 0;
-    // MOVE: the temporary, opened by the first chunk that loses a row; a call that ends before the file is replaced removes it
-    sm_mapfile::Writer tmp;
-    bool tmp_done = false;             // complete and closed, not yet renamed
-    ~MapFile() { if (tmp_done) std::remove(tmp.path().c_str()); }
-};
 
 int ensure_scratch(sm_ctx *s)
 {
@@ -86,96 +72,6 @@ int ensure_scratch(sm_ctx *s)
     return SM_OK;
 }
 
-struct Run {
-    sm_ctx *s;
-    const char *who;
-    int32_t mode;
-    RecallArgs ra;
-    uint32_t base0;                    // |m|: where the first recalled record goes
-    std::vector<MapFile> &files;
-    std::vector<Job> jobs;
-    uint64_t total = 0;                // |R| so far
-};
-
-// the next chunk of the stream: the kernels and the read-back of the chunk's tally, all asynchronous
-int enqueue(Run &R, MapStream &in, MapStream::Chunk &ck)
-{
-    sm_ctx *s = R.s;
-    RenderMaps &rm = s->maps;
-    Recall &r = s->rec;
-    int rc = in.next(ck);
-    if (rc) return rc;
-    const int q = ck.q;
-    const uint32_t n = ck.job->n;
-    const unsigned nblk = (n + RECALL_BLOCK - 1) / RECALL_BLOCK;
-    const float4 *rec = ck.d_rec;
-    hipLaunchKernelGGL(k_recall_mark, dim3(nblk), dim3(256), 0, s->stream, rec, n, R.ra, r.d_mask.get(), r.d_blk_cnt.get(), rm.d_box.get());
-    hipLaunchKernelGGL(k_recall_scan, dim3(1), dim3(1024), 0, s->stream, nblk, (const uint32_t *)r.d_blk_cnt.get(), (const float4 *)rm.d_box.get(),
-                       r.d_blk_base.get(), r.d_run.get(), r.d_chunk.get() + q);
-    if (R.mode != SM_RECALL_COUNT) {
-        float4 *keep = R.mode == SM_RECALL_MOVE ? (float4 *)s->d_export.get() + (size_t)q * CHUNK * 3 : nullptr;
-        hipLaunchKernelGGL(k_recall_place, dim3(nblk), dim3(256), 0, s->stream, rec, n, s->M, (const DevState *)s->d_state.get(),
-                           (const uint64_t *)r.d_mask.get(), (const uint32_t *)r.d_blk_cnt.get(), (const uint32_t *)r.d_blk_base.get(),
-                           (const RecallChunk *)(r.d_chunk.get() + q), R.base0, s->cap, keep);
-    }
-    HIPCK(hipGetLastError());
-    HIPCK(hipMemcpyAsync(r.h_chunk.get() + q, r.d_chunk.get() + q, sizeof(RecallChunk), hipMemcpyDeviceToHost, s->stream));
-    if ((rc = in.done(q))) return rc;
-    r.stats.chunks++;
-    r.stats.records_read += n;
-    return SM_OK;
-}
-
-// the chunk is through the device: its tally, its box, and (MOVE) its rows that stay into the file's temporary
-int finish(Run &R, MapStream &in, const MapStream::Chunk &ck)
-{
-    sm_ctx *s = R.s;
-    RenderMaps &rm = s->maps;
-    Recall &r = s->rec;
-    const Job &j = *ck.job;
-    MapFile &mf = R.files[j.file];
-    const int q = ck.q;
-    int rc = in.fold(q);
-    if (rc) return rc;
-    const RecallChunk rc_q = r.h_chunk.get()[q];
-    R.total += rc_q.total;
-    mf.lo[0] = std::min(mf.lo[0], rc_q.lx); mf.lo[1] = std::min(mf.lo[1], rc_q.ly); mf.lo[2] = std::min(mf.lo[2], rc_q.lz);
-    mf.hi[0] = std::max(mf.hi[0], rc_q.hx); mf.hi[1] = std::max(mf.hi[1], rc_q.hy); mf.hi[2] = std::max(mf.hi[2], rc_q.hz);
-    mf.tmax = std::max(mf.tmax, rc_q.tmax);
-    mf.chunks_left--;
-    if (R.mode != SM_RECALL_MOVE) return SM_OK;
-    const double t0 = now_ms();
-    bool ok = true;
-    // the temporary of a file that is about to lose its first row: the chunks before this one lost nothing and come from the
-    // file itself
-    if (rc_q.total && !mf.tmp.is_open())
-        ok = mf.tmp.open(mf.path + ".recall.tmp", sm_mapfile::Writer::UNKNOWN, mf.h.start_id, mf.h.end_id, R.who, g_err) &&
-             mf.tmp.append_head_of(mf.path, j.first, g_err);
-    if (ok && mf.tmp.is_open()) {
-        const uint32_t kept = j.n - rc_q.total;
-        if (rc_q.total && kept) {
-            // (the copy stream is idle or copying the next chunk in; the kernels that wrote the staging are over)
-            HIPCK(hipMemcpyAsync(rm.h_rec[q], (const float4 *)s->d_export.get() + (size_t)q * CHUNK * 3, (size_t)kept * sm_mapfile::RECORD_BYTES, hipMemcpyDeviceToHost, rm.copy));
-            HIPCK(hipStreamSynchronize(rm.copy));
-        }
-        ok = mf.tmp.append(rm.h_rec[q].get(), kept, g_err);      // (a chunk that lost nothing: as it was read)
-        if (ok && mf.chunks_left == 0) mf.tmp_done = ok = mf.tmp.commit(g_err);
-    }
-    r.stats.write_ms += (float)(now_ms() - t0);
-    return ok ? SM_OK : SM_E_ARG;
-}
-
-int stream_files(Run &R, MapStream &in)
-{
-    int rc;
-    MapStream::Chunk cur{}, prev{};
-    for (in.begin(R.jobs); in.more(); prev = cur) {
-        if ((rc = enqueue(R, in, cur))) return rc;               // the host reads chunk c while the device works on chunk c - 1
-        if (prev.job && (rc = finish(R, in, prev))) return rc;   // ... and writes what stays of chunk c - 1 while it works on chunk c
-    }
-    return prev.job ? finish(R, in, prev) : SM_OK;
-}
-
 int check_args(sm_ctx *s, const sm_map_source *src, const float *pose16, const sm_recall_params *p, int32_t mode, const uint32_t *n,
                const char *who)
 {
@@ -186,11 +82,8 @@ int check_args(sm_ctx *s, const sm_map_source *src, const float *pose16, const s
     if (mode != SM_RECALL_MOVE && mode != SM_RECALL_COPY && mode != SM_RECALL_COUNT) { g_err = std::string(who) + ": unknown mode"; return SM_E_ARG; }
     if (p && !(std::isfinite(p->radius) && p->radius > 0.0f)) { g_err = std::string(who) + ": radius must be finite and > 0"; return SM_E_ARG; }
     if (int rc = check_pose(pose16, who)) return rc;
-    if (s->pending_cull) { g_err = std::string(who) + " between sm_stage_conflict and sm_stage_cull"; return SM_E_ARG; }
-    if (mode == SM_RECALL_MOVE)
-        for (uint32_t i = 0; i < src->n_paths; ++i)
-            for (uint32_t k = 0; k < i; ++k)
-                if (strcmp(src->paths[i], src->paths[k]) == 0) { g_err = std::string(who) + ": " + src->paths[i] + " is listed twice"; return SM_E_ARG; }
+    if (int rc = check_not_mid_cull(s, who)) return rc;
+    if (mode == SM_RECALL_MOVE && !sm_mapset::check_distinct_paths(src->paths, src->n_paths, who, g_err)) return SM_E_ARG;
     return SM_OK;
 }
 
@@ -207,89 +100,105 @@ int recall(sm_ctx *s, const sm_map_source *src, const float *pose16, const sm_re
     if (!(std::isfinite(p.radius) && p.radius > 0.0f)) { g_err = std::string(who) + ": radius must be finite and > 0"; return SM_E_ARG; }
     const float *pose = pose16 ? pose16 : s->last_pose;
     Recall &r = s->rec;
-    const char *e = std::getenv("SM_RECALL_NO_INDEX");
-    const bool use_index = !(e && e[0] == '1');
     RecallArgs ra;
     ra.cx = pose[12]; ra.cy = pose[13]; ra.cz = pose[14];
     ra.r2 = p.radius * p.radius;
     const float c3[3] = {ra.cx, ra.cy, ra.cz};
 
-    // ---- every file is checked before anything changes: skipped by the index on its stat() alone, or its header against its length
+    // ---- every file is checked before anything changes; the index skips a file whose box no near row can lie in
+    sm_mapset::RewriteSet set;
+    std::vector<MapFile> &files = set.files;
+    if (!sm_mapset::open_rewrite_set(src->paths, src->n_paths, CHUNK, s->index, known_far,
+                                     [&](const sm_mapset::FileIndex::Entry &en) { return box_out_of_reach(en, c3, ra.r2); }, who, set, g_err))
+        return SM_E_ARG;
     sm_recall_stats_t st{};
-    st.files_listed = src->n_paths;
-    std::vector<MapFile> files(src->n_paths);
-    Run R{s, who, mode, ra, 0u, files, {}, 0};
-    std::vector<sm_mapfile::Header> headers(src->n_paths);   // (count 0: a file that is not read)
-    const float INF = __builtin_inff();
-    for (uint32_t i = 0; i < src->n_paths; ++i) {
-        MapFile &mf = files[i];
-        mf.path = src->paths[i];
-        for (int a = 0; a < 3; ++a) { mf.lo[a] = INF; mf.hi[a] = -INF; }
-        bool skip = (int64_t)i == known_far;
-        if (!skip && use_index && sm_mapfile::stat_of(mf.path, mf.h)) {
-            auto it = r.index.find(mf.path);
-            skip = it != r.index.end() && it->second.size == mf.h.size && it->second.mtime_ns == mf.h.mtime_ns && box_out_of_reach(it->second, c3, ra.r2);
-        }
-        if (skip) { mf.skipped = true; st.files_skipped++; continue; }
-        if (!sm_mapfile::open_checked(mf.path, who, mf.h, g_err)) return SM_E_ARG;
-        headers[i] = mf.h;
-        st.files_read++;
-    }
-    R.jobs = sm_mapfile::chunk_plan(headers, CHUNK);
-    for (const Job &j : R.jobs) files[j.file].chunks_left++;
+    st.files_listed = set.listed; st.files_skipped = set.skipped; st.files_read = set.read;
 
     HIPCK(hipSetDevice(s->cfg.device));
     // COUNT leaves the model alone altogether; the others append to the rows a download would return
     if (mode != SM_RECALL_COUNT && (rc = ensure_compact(s))) return rc;
     if ((rc = pull_state(s))) return rc;                 // (waits for frames in flight, flushes a held-back association)
-    const uint32_t cnt = s->h_state->count;
-    R.base0 = cnt;
+    const uint32_t cnt = s->h_state->count;              // |m|: where the first recalled record goes
+    uint64_t total = 0;                                  // |R| so far
     r.stats = st;
     r.stats_valid = true;
-    if (!R.jobs.empty()) {
+    if (!set.jobs.empty()) {
         if ((rc = maps_ensure_staging(s)) || (rc = ensure_scratch(s))) return rc;
         uint32_t largest = 0;
-        for (const Job &j : R.jobs) largest = std::max(largest, j.n);
+        for (const sm_mapfile::Job &j : set.jobs) largest = std::max(largest, j.n);
         if (mode == SM_RECALL_MOVE && (rc = ensure_export(s, ((size_t)CHUNK + largest) * sm_mapfile::RECORD_BYTES))) return rc;   // two chunks of rows that stay
         HIPCK(hipMemsetAsync(r.d_run, 0, 4, s->stream));
+        MapStaging &sg = s->staging;
+        const auto stay = [&](int q) { return (float4 *)s->d_export.get() + (size_t)q * CHUNK * 3; };
         // (gone before the renames: an open handle would keep a replaced file's pages alive.  If the call fails, the stream drains
         // what is in flight and the temporaries go with `files`.)
         MapStream in(s, who, src->paths, {&r.stats.read_ms, &r.stats.copy_ms, &r.stats.device_ms});
-        if ((rc = stream_files(R, in))) return rc;
+        // the next chunk of the stream: the kernels and the read-back of the chunk's tally, all asynchronous
+        const auto enqueue = [&](MapStream::Chunk &ck) -> int {
+            if (int e = in.next(ck)) return e;
+            const int q = ck.q;
+            const uint32_t n = ck.job->n;
+            const unsigned nblk = (n + RECALL_BLOCK - 1) / RECALL_BLOCK;
+            hipLaunchKernelGGL(k_recall_mark, dim3(nblk), dim3(256), 0, s->stream, ck.d_rec, n, ra, r.d_mask.get(), r.d_blk_cnt.get(), sg.d_box.get());
+            hipLaunchKernelGGL(k_recall_scan, dim3(1), dim3(1024), 0, s->stream, nblk, (const uint32_t *)r.d_blk_cnt.get(), (const float4 *)sg.d_box.get(),
+                               r.d_blk_base.get(), r.d_run.get(), r.d_chunk.get() + q);
+            if (mode != SM_RECALL_COUNT)
+                hipLaunchKernelGGL(k_recall_place, dim3(nblk), dim3(256), 0, s->stream, ck.d_rec, n, s->M, (const DevState *)s->d_state.get(),
+                                   (const uint64_t *)r.d_mask.get(), (const uint32_t *)r.d_blk_cnt.get(), (const uint32_t *)r.d_blk_base.get(),
+                                   (const RecallChunk *)(r.d_chunk.get() + q), cnt, s->cap, mode == SM_RECALL_MOVE ? stay(q) : nullptr);
+            HIPCK(hipGetLastError());
+            HIPCK(hipMemcpyAsync(r.h_chunk.get() + q, r.d_chunk.get() + q, sizeof(RecallChunk), hipMemcpyDeviceToHost, s->stream));
+            if (int e = in.done(q)) return e;
+            r.stats.chunks++;
+            r.stats.records_read += n;
+            return SM_OK;
+        };
+        // the chunk is through the device: its tally, its box, and (MOVE) its rows that stay into the file's temporary
+        const auto finish = [&](const MapStream::Chunk &ck) -> int {
+            const int q = ck.q;
+            if (int e = in.fold(q)) return e;
+            const RecallChunk t = r.h_chunk.get()[q];
+            MapFile &mf = files[ck.job->file];
+            total += t.total;
+            mf.fold(t.lx, t.ly, t.lz, t.hx, t.hy, t.hz, t.tmax);
+            if (mode != SM_RECALL_MOVE) return SM_OK;
+            const double t0 = now_ms();
+            const uint32_t kept = ck.job->n - t.total;
+            if (t.total && kept) {
+                // (the copy stream is idle or copying the next chunk in; the kernels that wrote the rows that stay are over)
+                HIPCK(hipMemcpyAsync(sg.h_rec[q], stay(q), (size_t)kept * sm_mapfile::RECORD_BYTES, hipMemcpyDeviceToHost, sg.copy));
+                HIPCK(hipStreamSynchronize(sg.copy));
+            }
+            // (a chunk that lost nothing: as it was read)
+            const bool ok = mf.keep(*ck.job, sg.h_rec[q].get(), kept, t.total != 0, ".recall.tmp", sm_mapfile::Writer::UNKNOWN, who, g_err);
+            r.stats.write_ms += (float)(now_ms() - t0);
+            return ok ? SM_OK : SM_E_ARG;
+        };
+        if ((rc = sm_mapset::stream_files(in, set.jobs, enqueue, finish))) return rc;
     }
-    r.stats.recalled = R.total;
-    *n = (uint32_t)std::min<uint64_t>(R.total, 0xFFFFFFFFull);
+    r.stats.recalled = total;
+    *n = (uint32_t)std::min<uint64_t>(total, 0xFFFFFFFFull);
     // what this read has learnt goes into the index, whatever becomes of the call: the files are as they were
-    auto note = [&](const MapFile &mf) {
-        Recall::Entry en{mf.h.size, mf.h.mtime_ns, {mf.lo[0], mf.lo[1], mf.lo[2]}, {mf.hi[0], mf.hi[1], mf.hi[2]}, mf.tmax};   // (a MOVE only takes rows away: tmax stays an upper bound)
-        r.index[mf.path] = en;
-    };
+    // (a MOVE only takes rows away: the box stays a superset, tmax an upper bound)
     for (const MapFile &mf : files)
-        if (!mf.skipped) note(mf);
+        if (!mf.skipped) mf.note_in(s->index);
     if (mode == SM_RECALL_COUNT) { r.stats.total_ms = (float)(now_ms() - t_begin); return SM_OK; }
-    if ((uint64_t)cnt + R.total > s->cap) {
-        g_err = std::string(who) + ": " + std::to_string(cnt) + " surfels + " + std::to_string(R.total) + " recalled exceed MAX_VERTICES";
+    if ((uint64_t)cnt + total > s->cap) {
+        g_err = std::string(who) + ": " + std::to_string(cnt) + " surfels + " + std::to_string(total) + " recalled exceed MAX_VERTICES";
         r.stats.total_ms = (float)(now_ms() - t_begin);
         return SM_E_CAPACITY;
     }
 
     // ---- publish: the state an upload of concat(m, R) leaves; only the tiles that hold a recalled row get new boxes
-    if ((rc = publish_dense(s, cnt + (uint32_t)R.total, cnt))) return rc;   // (a device error: the context is lost anyway)
+    if ((rc = publish_dense(s, cnt + (uint32_t)total, cnt))) return rc;   // (a device error: the context is lost anyway)
 
     // ---- the files, last: a failure from here on leaves rows twice, never nowhere
     const double t0 = now_ms();
-    for (MapFile &mf : files) {
-        if (!mf.tmp_done) continue;
-        if (std::rename(mf.tmp.path().c_str(), mf.path.c_str()) != 0) {
-            if (rc == SM_OK) g_err = std::string(who) + ": " + mf.path + " could not be replaced; its recalled rows are in the model AND still in the file";
-            rc = SM_E_ARG;
-            continue;                                    // (its temporary goes with `files`)
-        }
-        mf.tmp_done = false;
-        r.stats.files_rewritten++;
-        if (sm_mapfile::stat_of(mf.path, mf.h)) note(mf);   // (the old box: a superset)
-        else r.index.erase(mf.path);
-    }
+    // (a file that could not be replaced: its temporary goes with `files`; the first one's text stays)
+    r.stats.files_rewritten += sm_mapset::replace_files(files, s->index, false, [&](const MapFile &mf) {
+        if (rc == SM_OK) g_err = std::string(who) + ": " + mf.path + " could not be replaced; its recalled rows are in the model AND still in the file";
+        rc = SM_E_ARG;
+    });
     r.stats.write_ms += (float)(now_ms() - t0);
     r.stats.total_ms = (float)(now_ms() - t_begin);
     return rc;
@@ -324,19 +233,12 @@ int sm_impl::recall_box_of(sm_ctx *s, const float *d_rec12, uint32_t n, float lo
     return SM_OK;
 }
 
-void sm_impl::recall_note_written(sm_ctx *s, const std::string &path, const float lo[3], const float hi[3], float max_time)
-{
-    sm_mapfile::Header h;
-    if (!sm_mapfile::stat_of(path, h)) { s->rec.index.erase(path); return; }
-    s->rec.index[path] = Recall::Entry{h.size, h.mtime_ns, {lo[0], lo[1], lo[2]}, {hi[0], hi[1], hi[2]}, max_time};
-}
-
 int sm_impl::recall_ensure_scratch(sm_ctx *s) { return ensure_scratch(s); }
 
 // The periodic policy, called by auto_retire_after_frame once that frame's retirement is complete: a MOVE recall at the frame's
 // pose from every file the retirement policy has written.  The file this round has written is listed and not read: each of its
 // rows was retired because d2 > min_distance^2 at this very pose, and radius <= min_distance (check_recall_policy), so by the
-// complement property none of them is near; its box is in the index already (recall_note_written).
+// complement property none of them is near; its box is in the index already (auto_retire_after_frame).
 int sm_impl::auto_recall_after_retire(sm_ctx *s, bool wrote_file)
 {
     Recall &r = s->rec;

@@ -1,5 +1,5 @@
-// sm_render_maps.hip -- views of a map set (sm_render_image_maps, sm_render_model_maps; DESIGN.md "4f. Views of a map set"):
-// map files streamed through the two renderers in chunks, the live model last.  Kernels: sm_k_render_maps.h.
+// sm_render_maps.hip -- views of a map set (sm_render_image_maps, sm_render_model_maps; DESIGN.md "4f. Views of a map set"): map files streamed through the two
+// renderers in chunks, the live model last; for every source that streams map files, the context's MapStaging: its allocation and intake kernel.  Kernels: sm_k_render_maps.h.
 #include "sm_map_stream.h"
 #include "sm_k_render_maps.h"
 
@@ -22,39 +22,24 @@ struct Mode {
 int render_maps(sm_ctx *s, const sm_map_source *src, const char *fn, const Mode &md)
 {
     const double t_begin = now_ms();
-    if (s->ss_on) { g_err = std::string(fn) + ": a sharded context holds only its rank's surfels; rendering the union is not supported"; return SM_E_UNSUPPORTED; }
-    if (s->pending_cull) { g_err = std::string(fn) + " between sm_stage_conflict and sm_stage_cull"; return SM_E_ARG; }
-    int rc = check_map_source(src, fn);
+    sm_mapset::ReadSet set;
+    uint32_t cnt;
+    int rc = maps_open(s, src, fn, [](const sm_ctx *c, const char *who) -> int {
+        if (c->ss_on) { g_err = std::string(who) + ": a sharded context holds only its rank's surfels; rendering the union is not supported"; return SM_E_UNSUPPORTED; }
+        return SM_OK;
+    }, set, cnt);
     if (rc) return rc;
-    // the headers of all files, each against its length, before anything else
-    std::vector<sm_mapfile::Header> files(src->n_paths);
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < src->n_paths; ++i) {
-        if (!sm_mapfile::open_checked(src->paths[i], fn, files[i], g_err)) return SM_E_ARG;
-        total += files[i].count;
-    }
-    const std::vector<sm_mapfile::Job> jobs = sm_mapfile::chunk_plan(files, RenderMaps::CHUNK);
-    std::vector<uint64_t> id_base(files.size());         // of each file's first record in the set
-    for (size_t i = 1; i < files.size(); ++i) id_base[i] = id_base[i - 1] + files[i - 1].count;
-    HIPCK(hipSetDevice(s->cfg.device));
-    if ((rc = ensure_compact(s))) return rc;
-    if ((rc = pull_state(s))) return rc;                          // (waits for frames in flight; count is the live surfels)
-    const uint32_t cnt = src->include_model ? s->h_state->count : 0u;
-    const uint64_t file_total = total;
-    total += cnt;
-    if (total > 0x7FFFFFFFull) { g_err = std::string(fn) + ": the map set holds " + std::to_string(total) + " surfels, ids end at 2^31 - 1"; return SM_E_CAPACITY; }
+    const uint64_t file_total = set.file_total;
+    const MapStaging &st = s->staging;
     RenderMaps &rm = s->maps;
     rm.stats = sm_maps_stats{};
     rm.stats_valid = true;
     if (md.n_views == 0) { rm.stats.total_ms = (float)(now_ms() - t_begin); return SM_OK; }
     if (file_total && (rc = maps_ensure_staging(s))) return rc;
 
-    const char *e = std::getenv("SM_RENDER_MAPS_NO_CULL");
-    const int cull = (e && e[0] == '1') ? 0 : 1;
-    size_t key_mb = 1024;
-    if (const char *k = std::getenv("SM_RENDER_MAPS_KEY_MB")) key_mb = (size_t)std::min(8192L, std::max(1L, std::atol(k)));   // (at most 2^30 keys per batch)
     const size_t npix = (size_t)md.w * md.h;
-    const uint32_t B = (uint32_t)std::min<uint64_t>(std::min<uint32_t>(md.n_views, 4096u), std::max<uint64_t>(1, (key_mb << 20) / (npix * 8)));
+    int cull;
+    const uint32_t B = maps_batch(md.n_views, npix, "SM_RENDER_MAPS_KEY_MB", "SM_RENDER_MAPS_NO_CULL", &cull);
     const unsigned pblocks = (unsigned)((npix + 255) / 256);
 
     // per-view parameters | shading | skipped counters | hit flags
@@ -82,7 +67,8 @@ int render_maps(sm_ctx *s, const sm_map_source *src, const char *fn, const Mode 
     uint8_t *d_out = base + off_out;
     uint32_t *d_ovf_n = (uint32_t *)(base + off_ovf), *d_ovf = (uint32_t *)(base + off_ovf + 256);
 
-    const MapsSoA chunk{rm.d_pos_conf, rm.d_norm_rad, rm.d_color, rm.d_time};
+    if (cnt && !rm.ev[1]) { HIPCK(hipEventCreate(rm.ev[0].put())); HIPCK(hipEventCreate(rm.ev[1].put())); }
+    const MapsSoA chunk = planes(st);
     const SurfelSet cur = s->M.s[s->h_state->cur];
     const MapsSoA live{cur.pos_conf, cur.norm_rad, cur.color, cur.time};
     MapStream in(s, fn, src->paths, {&rm.stats.read_ms, &rm.stats.copy_ms, &rm.stats.device_ms});
@@ -109,19 +95,19 @@ int render_maps(sm_ctx *s, const sm_map_source *src, const char *fn, const Mode 
         fill_keys(s, d_key, bp);
 
         // ---- the files, chunk by chunk: the host reads chunk c + 1 while the copy and the kernels of chunk c run
-        for (in.begin(jobs); in.more();) {
+        for (in.begin(set.jobs); in.more();) {
             MapStream::Chunk ck;
             if ((rc = in.next(ck))) return rc;
             const uint32_t n = ck.job->n;
             const unsigned nblk = (n + MAPS_BLOCK - 1) / MAPS_BLOCK;
             maps_intake(s, ck.d_rec, n);
             HIPCK(hipMemsetAsync(d_hit + v0, 0, b, s->stream));
-            const uint32_t gid = (uint32_t)(id_base[ck.job->file] + ck.job->first);
+            const uint32_t gid = (uint32_t)(set.id_base[ck.job->file] + ck.job->first);
             if (md.image)
-                hipLaunchKernelGGL(k_maps_splat_image, dim3(nblk, b), dim3(256), 0, s->stream, chunk, n, gid, (const float4 *)rm.d_box.get(), d_rp,
+                hipLaunchKernelGGL(k_maps_splat_image, dim3(nblk, b), dim3(256), 0, s->stream, chunk, n, gid, (const float4 *)st.d_box.get(), d_rp,
                                    d_key, npix, cull, d_skip + v0, d_hit + v0);
             else
-                hipLaunchKernelGGL(k_maps_splat_view, dim3(nblk, b), dim3(256), 0, s->stream, chunk, n, gid, (const float4 *)rm.d_box.get(), d_vp,
+                hipLaunchKernelGGL(k_maps_splat_view, dim3(nblk, b), dim3(256), 0, s->stream, chunk, n, gid, (const float4 *)st.d_box.get(), d_vp,
                                    d_key, npix, cull, d_skip + v0, d_hit + v0);
             resolve(chunk, gid, n);
             if ((rc = in.done(ck.q))) return rc;
@@ -134,9 +120,7 @@ int render_maps(sm_ctx *s, const sm_map_source *src, const char *fn, const Mode 
 
         // ---- the live model, by the resident kernels with an id base
         if (cnt) {
-            Event &k0 = rm.ev_k0[0], &k1 = rm.ev_k1[0];          // (free: both buffers have been folded)
-            if (!k0) { HIPCK(hipEventCreate(k0.put())); HIPCK(hipEventCreate(k1.put())); }
-            HIPCK(hipEventRecord(k0, s->stream));
+            HIPCK(hipEventRecord(rm.ev[0], s->stream));
             for (uint32_t i = 0; i < b; ++i) {
                 uint64_t *kv = d_key + (size_t)i * npix;
                 if (md.image) render_splat_model(s, ((const RenderParams *)md.params)[v0 + i], kv, (uint32_t)file_total);
@@ -144,11 +128,11 @@ int render_maps(sm_ctx *s, const sm_map_source *src, const char *fn, const Mode 
             }
             HIPCK(hipMemsetAsync(d_hit + v0, 1, b, s->stream));
             resolve(live, (uint32_t)file_total, cnt);
-            HIPCK(hipEventRecord(k1, s->stream));
+            HIPCK(hipEventRecord(rm.ev[1], s->stream));
             HIPCK(hipGetLastError());
             float ms = 0.0f;
-            HIPCK(hipEventSynchronize(k1));
-            HIPCK(hipEventElapsedTime(&ms, k0, k1));
+            HIPCK(hipEventSynchronize(rm.ev[1]));
+            HIPCK(hipEventElapsedTime(&ms, rm.ev[0], rm.ev[1]));
             rm.stats.device_ms += ms;
         }
 
@@ -178,29 +162,27 @@ int render_maps(sm_ctx *s, const sm_map_source *src, const char *fn, const Mode 
 
 int sm_impl::maps_ensure_staging(sm_ctx *s)
 {
-    RenderMaps &rm = s->maps;
-    if (rm.copy) return SM_OK;
+    MapStaging &st = s->staging;
+    if (st.copy) return SM_OK;
     Stream copy;
     HIPCK(hipStreamCreateWithFlags(copy.put(), hipStreamNonBlocking));
-    const size_t N = RenderMaps::CHUNK;
+    const size_t N = MapStaging::CHUNK;
     for (int b = 0; b < 2; ++b) {
-        HIPCK(hipHostMalloc((void **)rm.h_rec[b].put(), N * sm_mapfile::RECORD_BYTES, hipHostMallocDefault));
-        HIPCK(hipMalloc(rm.d_rec[b].put(), N * sm_mapfile::RECORD_BYTES));
-        for (Event *e : {&rm.ev_copy0[b], &rm.ev_copied[b], &rm.ev_k0[b], &rm.ev_k1[b]}) HIPCK(hipEventCreate(e->put()));
+        HIPCK(hipHostMalloc((void **)st.h_rec[b].put(), N * sm_mapfile::RECORD_BYTES, hipHostMallocDefault));
+        HIPCK(hipMalloc(st.d_rec[b].put(), N * sm_mapfile::RECORD_BYTES));
+        for (Event *e : {&st.ev_copy0[b], &st.ev_copied[b], &st.ev_k0[b], &st.ev_k1[b]}) HIPCK(hipEventCreate(e->put()));
     }
     int rc;
-    if ((rc = dalloc(rm.d_pos_conf, N)) || (rc = dalloc(rm.d_norm_rad, N)) || (rc = dalloc(rm.d_color, N)) || (rc = dalloc(rm.d_time, N)) ||
-        (rc = dalloc(rm.d_box, 2 * (N / MAPS_BLOCK))))
+    if ((rc = dalloc(st.d_pos_conf, N)) || (rc = dalloc(st.d_norm_rad, N)) || (rc = dalloc(st.d_color, N)) || (rc = dalloc(st.d_time, N)) ||
+        (rc = dalloc(st.d_box, 2 * (N / MAPS_BLOCK))))
         return rc;
-    rm.copy = std::move(copy);                           // last: the staging is whole or absent
+    st.copy = std::move(copy);                           // last: the staging is whole or absent
     return SM_OK;
 }
 
 void sm_impl::maps_intake(sm_ctx *s, const float4 *d_rec, uint32_t n)
 {
-    RenderMaps &rm = s->maps;
-    const MapsSoA chunk{rm.d_pos_conf, rm.d_norm_rad, rm.d_color, rm.d_time};
-    hipLaunchKernelGGL(k_maps_intake, dim3((n + MAPS_BLOCK - 1) / MAPS_BLOCK), dim3(256), 0, s->stream, d_rec, n, chunk, rm.d_box.get());
+    hipLaunchKernelGGL(k_maps_intake, dim3((n + MAPS_BLOCK - 1) / MAPS_BLOCK), dim3(256), 0, s->stream, d_rec, n, planes(s->staging), s->staging.d_box.get());
 }
 
 extern "C" {

@@ -30,8 +30,7 @@ int check_args(sm_ctx *s, const float *pose16, const sm_retire_params *p, const 
     if (int rc = check_whole_map(s, who)) return rc;
     if (p && (p->min_age < 0 || !std::isfinite(p->min_distance))) { g_err = std::string(who) + ": bad parameters"; return SM_E_ARG; }
     if (int rc = check_pose(pose16, who)) return rc;
-    if (s->pending_cull) { g_err = std::string(who) + " between sm_stage_conflict and sm_stage_cull"; return SM_E_ARG; }
-    return SM_OK;
+    return check_not_mid_cull(s, who);
 }
 
 sm_retire_params params_or_default(sm_ctx *s, const sm_retire_params *params)
@@ -180,7 +179,7 @@ int sm_impl::auto_retire_after_frame(sm_ctx *s)
                           });
         if (rc) return rc;
         if (!w.commit(g_err)) return SM_E_ARG;
-        recall_note_written(s, path, lo, hi, tmax);
+        s->index.note_now(path, lo, hi, tmax);
         r.files++;
         r.surfels += n;
         r.last_tick = s->tick;

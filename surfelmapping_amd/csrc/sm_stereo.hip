@@ -17,7 +17,7 @@ int stereo_check(sm_ctx *s, bool stereo, const char *who)
 {
     if (!s) { g_err = std::string(who) + ": null context"; return SM_E_ARG; }
     if (int rc = check_whole_map(s, who)) return rc;
-    if (s->pending_cull) { g_err = std::string(who) + " between sm_stage_conflict and sm_stage_cull"; return SM_E_ARG; }
+    if (int rc = check_not_mid_cull(s, who)) return rc;
     if (stereo && !s->stereo.on) { g_err = std::string(who) + ": the context has no stereo (sm_set_stereo)"; return SM_E_ARG; }
     return SM_OK;
 }

@@ -51,7 +51,7 @@ int track_alloc(sm_ctx *s)
 int track_check(sm_ctx *s, const char *fn)
 {
     if (s->ss_on) { g_err = std::string(fn) + ": a sharded context holds only its rank's surfels; tracking is not supported"; return SM_E_UNSUPPORTED; }
-    if (s->pending_cull) { g_err = std::string(fn) + " between sm_stage_conflict and sm_stage_cull"; return SM_E_ARG; }
+    if (int rc = check_not_mid_cull(s, fn)) return rc;
     return SM_OK;
 }
 

@@ -62,7 +62,7 @@ int render_model_enqueue(sm_ctx *s, const sm_model_view *v, const char *fn, uint
         g_err = std::string(fn) + ": outputs must be 4-byte aligned"; return SM_E_ARG;
     }
     if (s->ss_on) { g_err = std::string(fn) + ": a sharded context holds only its rank's surfels; rendering the union is not supported"; return SM_E_UNSUPPORTED; }
-    if (s->pending_cull) { g_err = std::string(fn) + " between sm_stage_conflict and sm_stage_cull"; return SM_E_ARG; }
+    if (int rc = check_not_mid_cull(s, fn)) return rc;
     HIPCK(hipSetDevice(s->cfg.device));
     int rc = ensure_compact(s);
     if (rc) return rc;

@@ -1,7 +1,7 @@
 // sm_warp.hip -- closing loops (DESIGN.md "4h. Closing loops"): sm_warp_by_time moves the live model and the records of map files
 // by a table of world->world transforms indexed by each surfel's last-update time; sm_loop_spread makes the table of a loop
-// closure.  Kernels: sm_k_warp.h.  The files stream through the staging of sm_render_maps.hip (MapStream), are warped IN that
-// staging and copied back from it; the file index is sm_recall.hip's.
+// closure.  Kernels: sm_k_warp.h.  The files stream through the context's MapStaging (MapStream), are warped IN its record
+// buffers and copied back from them; the index, the opening, the temporaries and the replacement are sm_map_set.h's.
 //
 // Durability, in sm_recall MOVE's order: every file's new contents are complete in "<path>.warp.tmp" before the model is touched;
 // then the model is warped; then each temporary is renamed over its file.  A temporary that cannot be written removes all
@@ -15,27 +15,13 @@
 #include <cstdlib>
 
 using namespace sm;
-using sm_mapfile::Job;
 using sm_mapfile::now_ms;
+using sm_mapset::MapFile;
 
 namespace {
 
-constexpr uint32_t CHUNK = RenderMaps::CHUNK;
+constexpr uint32_t CHUNK = MapStaging::CHUNK;
 static_assert(CHUNK / WARP_BLOCK == WARP_MAX_BLOCKS, "a chunk's blocks are folded by one workgroup");
-
-// one listed file through the call
-struct MapFile {
-    std::string path;
-    bool skipped = false;              // by the index: not opened
-    sm_mapfile::Header h;              // count 0 unless the file is read
-    float lo[3], hi[3], tmax;          // of this read, after the warp
-    uint32_t chunks_left = 0;
-    uint64_t moved = 0;
-    // the temporary, opened by the first chunk that holds a selected row; a call that ends before the renames removes it
-    sm_mapfile::Writer tmp;
-    bool tmp_done = false;             // complete and closed, not yet renamed
-    ~MapFile() { if (tmp_done) std::remove(tmp.path().c_str()); }
-};
 
 int ensure_scratch(sm_ctx *s, uint32_t rows)
 {
@@ -59,84 +45,6 @@ int ensure_scratch(sm_ctx *s, uint32_t rows)
         w.corr_rows = rows;
     }
     return SM_OK;
-}
-
-struct Run {
-    sm_ctx *s;
-    const char *who;
-    WarpArgs wa;
-    std::vector<MapFile> &files;
-    std::vector<Job> jobs;
-};
-
-// the next chunk of the stream: its rows warped in the staging buffer, its tally on the way back, all asynchronous
-int enqueue(Run &R, MapStream &in, MapStream::Chunk &ck)
-{
-    sm_ctx *s = R.s;
-    Warp &w = s->warp;
-    int rc = in.next(ck);
-    if (rc) return rc;
-    const int q = ck.q;
-    const uint32_t n = ck.job->n;
-    const unsigned nblk = (n + WARP_BLOCK - 1) / WARP_BLOCK;
-    HIPCK(hipMemsetAsync(w.d_sel.get() + q, 0, 4, s->stream));
-    hipLaunchKernelGGL(k_warp_rows, dim3(nblk), dim3(256), 0, s->stream, s->maps.d_rec[q].get(), n, R.wa, (const float4 *)w.d_corr.get(),
-                       w.d_box.get(), w.d_sel.get() + q);
-    hipLaunchKernelGGL(k_warp_fold, dim3(1), dim3(1024), 0, s->stream, nblk, (const float4 *)w.d_box.get(), (const uint32_t *)(w.d_sel.get() + q),
-                       w.d_chunk.get() + q);
-    HIPCK(hipGetLastError());
-    HIPCK(hipMemcpyAsync(w.h_chunk.get() + q, w.d_chunk.get() + q, sizeof(WarpChunk), hipMemcpyDeviceToHost, s->stream));
-    if ((rc = in.done(q))) return rc;
-    w.stats.chunks++;
-    w.stats.records_read += n;
-    return SM_OK;
-}
-
-// the chunk is through the device: its tally, and its rows into the file's temporary if the file has one by now
-int finish(Run &R, MapStream &in, const MapStream::Chunk &ck)
-{
-    sm_ctx *s = R.s;
-    RenderMaps &rm = s->maps;
-    Warp &w = s->warp;
-    const Job &j = *ck.job;
-    MapFile &mf = R.files[j.file];
-    const int q = ck.q;
-    int rc = in.fold(q);                                 // (waits for the chunk's kernels and the copy of its tally)
-    if (rc) return rc;
-    const WarpChunk wc = w.h_chunk.get()[q];
-    mf.lo[0] = std::min(mf.lo[0], wc.lx); mf.lo[1] = std::min(mf.lo[1], wc.ly); mf.lo[2] = std::min(mf.lo[2], wc.lz);
-    mf.hi[0] = std::max(mf.hi[0], wc.hx); mf.hi[1] = std::max(mf.hi[1], wc.hy); mf.hi[2] = std::max(mf.hi[2], wc.hz);
-    mf.tmax = std::max(mf.tmax, wc.tmax);
-    mf.moved += wc.selected;
-    w.stats.records_moved += wc.selected;
-    mf.chunks_left--;
-    const double t0 = now_ms();
-    bool ok = true;
-    // the temporary of a file whose first selected row has just turned up: the chunks before this one come from the file itself
-    if (wc.selected && !mf.tmp.is_open())
-        ok = mf.tmp.open(mf.path + ".warp.tmp", mf.h.count, mf.h.start_id, mf.h.end_id, R.who, g_err) && mf.tmp.append_head_of(mf.path, j.first, g_err);
-    if (ok && mf.tmp.is_open()) {
-        if (wc.selected) {
-            // (the copy stream is idle or copying the next chunk into the other buffer; the kernels that wrote this one are over)
-            HIPCK(hipMemcpyAsync(rm.h_rec[q], rm.d_rec[q], (size_t)j.n * sm_mapfile::RECORD_BYTES, hipMemcpyDeviceToHost, rm.copy));
-            HIPCK(hipStreamSynchronize(rm.copy));
-        }
-        ok = mf.tmp.append(rm.h_rec[q].get(), j.n, g_err);       // (a chunk without a selected row: as it was read)
-        if (ok && mf.chunks_left == 0) mf.tmp_done = ok = mf.tmp.commit(g_err);
-    }
-    w.stats.write_ms += (float)(now_ms() - t0);
-    return ok ? SM_OK : SM_E_ARG;
-}
-
-int stream_files(Run &R, MapStream &in)
-{
-    int rc;
-    MapStream::Chunk cur{}, prev{};
-    for (in.begin(R.jobs); in.more(); prev = cur) {
-        if ((rc = enqueue(R, in, cur))) return rc;               // the host reads chunk c while the device works on chunk c - 1
-        if (prev.job && (rc = finish(R, in, prev))) return rc;   // ... and writes chunk c - 1 while it works on chunk c
-    }
-    return prev.job ? finish(R, in, prev) : SM_OK;
 }
 
 // the row rule's selection on the host, for a stored pose of tick `tick`
@@ -208,11 +116,8 @@ int check_args(sm_ctx *s, const sm_map_source *src, uint32_t n, const float *cor
     for (size_t i = 0; i < (size_t)n * 12; ++i)
         if (!std::isfinite(corr12[i])) { g_err = std::string(who) + ": non-finite table entry"; return SM_E_ARG; }
     if (int rc = check_map_source(src, who)) return rc;
-    if (s->pending_cull) { g_err = std::string(who) + " between sm_stage_conflict and sm_stage_cull"; return SM_E_ARG; }
-    for (uint32_t i = 0; i < src->n_paths; ++i)
-        for (uint32_t k = 0; k < i; ++k)
-            if (strcmp(src->paths[i], src->paths[k]) == 0) { g_err = std::string(who) + ": " + src->paths[i] + " is listed twice"; return SM_E_ARG; }
-    return SM_OK;
+    if (int rc = check_not_mid_cull(s, who)) return rc;
+    return sm_mapset::check_distinct_paths(src->paths, src->n_paths, who, g_err) ? SM_OK : SM_E_ARG;
 }
 
 int warp(sm_ctx *s, const sm_map_source *src, int32_t t0, uint32_t n, const float *corr12, const char *who)
@@ -221,50 +126,70 @@ int warp(sm_ctx *s, const sm_map_source *src, int32_t t0, uint32_t n, const floa
     int rc = check_args(s, src, n, corr12, who);
     if (rc) return rc;
     Warp &w = s->warp;
-    Recall &r = s->rec;
-    const char *e = std::getenv("SM_RECALL_NO_INDEX");
-    const bool use_index = !(e && e[0] == '1');
     const WarpArgs wa{(float)t0, (float)(n - 1u), n};
 
-    // ---- every file is checked before anything changes: skipped by the index on its stat() alone, or its header against its length
+    // ---- every file is checked before anything changes; the index skips a file none of whose rows is selected:
+    // tau >= float(t0) fails for every non-NaN tau <= max_time, and for every NaN
+    sm_mapset::RewriteSet set;
+    std::vector<MapFile> &files = set.files;
+    if (!sm_mapset::open_rewrite_set(src->paths, src->n_paths, CHUNK, s->index, -1,
+                                     [&](const sm_mapset::FileIndex::Entry &en) { return en.max_time < wa.t0; }, who, set, g_err))
+        return SM_E_ARG;
     sm_warp_stats_t st{};
-    st.files_listed = src->n_paths;
-    std::vector<MapFile> files(src->n_paths);
-    Run R{s, who, wa, files, {}};
-    std::vector<sm_mapfile::Header> headers(src->n_paths);   // (count 0: a file that is not read)
-    const float INF = __builtin_inff();
-    for (uint32_t i = 0; i < src->n_paths; ++i) {
-        MapFile &mf = files[i];
-        mf.path = src->paths[i];
-        for (int a = 0; a < 3; ++a) { mf.lo[a] = INF; mf.hi[a] = -INF; }
-        mf.tmax = -INF;
-        if (use_index && sm_mapfile::stat_of(mf.path, mf.h)) {
-            auto it = r.index.find(mf.path);
-            // no row of the file is selected: tau >= float(t0) fails for every non-NaN tau <= max_time, and for every NaN
-            mf.skipped = it != r.index.end() && it->second.size == mf.h.size && it->second.mtime_ns == mf.h.mtime_ns && it->second.max_time < wa.t0;
-        }
-        if (mf.skipped) { st.files_skipped++; continue; }
-        if (!sm_mapfile::open_checked(mf.path, who, mf.h, g_err)) return SM_E_ARG;
-        headers[i] = mf.h;
-        st.files_read++;
-    }
-    R.jobs = sm_mapfile::chunk_plan(headers, CHUNK);
-    for (const Job &j : R.jobs) files[j.file].chunks_left++;
+    st.files_listed = set.listed; st.files_skipped = set.skipped; st.files_read = set.read;
     w.stats = st;
     w.stats_valid = true;
-    if (R.jobs.empty() && !src->include_model) { w.stats.total_ms = (float)(now_ms() - t_begin); return SM_OK; }
+    if (set.jobs.empty() && !src->include_model) { w.stats.total_ms = (float)(now_ms() - t_begin); return SM_OK; }
 
     HIPCK(hipSetDevice(s->cfg.device));
     if ((rc = pull_state(s))) return rc;                 // (waits for frames in flight, flushes a held-back association)
     if ((rc = ensure_scratch(s, n))) return rc;
     HIPCK(hipMemcpyAsync(w.d_corr, corr12, (size_t)n * 48, hipMemcpyHostToDevice, s->stream));
     HIPCK(hipStreamSynchronize(s->stream));              // (the caller's table is free again)
-    if (!R.jobs.empty()) {
+    if (!set.jobs.empty()) {
         if ((rc = maps_ensure_staging(s))) return rc;
         // (gone before the renames: an open handle would keep a replaced file's pages alive.  If the call fails, the stream drains
         // what is in flight and the temporaries go with `files`.)
         MapStream in(s, who, src->paths, {&w.stats.read_ms, &w.stats.copy_ms, &w.stats.device_ms});
-        if ((rc = stream_files(R, in))) return rc;
+        MapStaging &sg = s->staging;
+        // the next chunk of the stream: its rows warped in the staging buffer, its tally on the way back, all asynchronous
+        const auto enqueue = [&](MapStream::Chunk &ck) -> int {
+            if (int e = in.next(ck)) return e;
+            const int q = ck.q;
+            const uint32_t m = ck.job->n;
+            const unsigned nblk = (m + WARP_BLOCK - 1) / WARP_BLOCK;
+            HIPCK(hipMemsetAsync(w.d_sel.get() + q, 0, 4, s->stream));
+            hipLaunchKernelGGL(k_warp_rows, dim3(nblk), dim3(256), 0, s->stream, sg.d_rec[q].get(), m, wa, (const float4 *)w.d_corr.get(), w.d_box.get(),
+                               w.d_sel.get() + q);
+            hipLaunchKernelGGL(k_warp_fold, dim3(1), dim3(1024), 0, s->stream, nblk, (const float4 *)w.d_box.get(), (const uint32_t *)(w.d_sel.get() + q),
+                               w.d_chunk.get() + q);
+            HIPCK(hipGetLastError());
+            HIPCK(hipMemcpyAsync(w.h_chunk.get() + q, w.d_chunk.get() + q, sizeof(WarpChunk), hipMemcpyDeviceToHost, s->stream));
+            if (int e = in.done(q)) return e;
+            w.stats.chunks++;
+            w.stats.records_read += m;
+            return SM_OK;
+        };
+        // the chunk is through the device: its tally, and its rows into the file's temporary if the file has one by now
+        const auto finish = [&](const MapStream::Chunk &ck) -> int {
+            const int q = ck.q;
+            if (int e = in.fold(q)) return e;                // (waits for the chunk's kernels and the copy of its tally)
+            const WarpChunk wc = w.h_chunk.get()[q];
+            MapFile &mf = files[ck.job->file];
+            mf.fold(wc.lx, wc.ly, wc.lz, wc.hx, wc.hy, wc.hz, wc.tmax);
+            w.stats.records_moved += wc.selected;
+            const double t1 = now_ms();
+            if (wc.selected) {
+                // (the copy stream is idle or copying the next chunk into the other buffer; the kernels that wrote this one are over)
+                HIPCK(hipMemcpyAsync(sg.h_rec[q], sg.d_rec[q], (size_t)ck.job->n * sm_mapfile::RECORD_BYTES, hipMemcpyDeviceToHost, sg.copy));
+                HIPCK(hipStreamSynchronize(sg.copy));
+            }
+            // (a chunk without a selected row: as it was read)
+            const bool ok = mf.keep(*ck.job, sg.h_rec[q].get(), ck.job->n, wc.selected != 0, ".warp.tmp", mf.h.count, who, g_err);
+            w.stats.write_ms += (float)(now_ms() - t1);
+            return ok ? SM_OK : SM_E_ARG;
+        };
+        if ((rc = sm_mapset::stream_files(in, set.jobs, enqueue, finish))) return rc;
     }
 
     // ---- all temporaries are complete: the model
@@ -272,22 +197,15 @@ int warp(sm_ctx *s, const sm_map_source *src, int32_t t0, uint32_t n, const floa
 
     // ---- the files, last; what this read has learnt goes into the index
     const double t1 = now_ms();
-    for (MapFile &mf : files) {
-        if (mf.skipped) continue;
-        if (mf.tmp_done) {
-            mf.tmp_done = false;                         // renamed, or left in place for the operator: not removed either way
-            if (std::rename(mf.tmp.path().c_str(), mf.path.c_str()) != 0) {
-                if (rc == SM_OK)
-                    g_err = std::string(who) + ": " + mf.path + " could not be replaced; its warped rows are in " + mf.tmp.path() + " (rename it over the file)";
-                rc = SM_E_ARG;
-                r.index.erase(mf.path);
-                continue;
-            }
-            w.stats.files_rewritten++;
-            if (!sm_mapfile::stat_of(mf.path, mf.h)) { r.index.erase(mf.path); continue; }
-        }
-        r.index[mf.path] = Recall::Entry{mf.h.size, mf.h.mtime_ns, {mf.lo[0], mf.lo[1], mf.lo[2]}, {mf.hi[0], mf.hi[1], mf.hi[2]}, mf.tmax};
-    }
+    for (const MapFile &mf : files)
+        if (!mf.skipped && !mf.tmp_done) mf.note_in(s->index);   // (read and left as it is)
+    // (a file that could not be replaced: its temporary is left in place for the operator, and the index forgets the file)
+    w.stats.files_rewritten += sm_mapset::replace_files(files, s->index, true, [&](const MapFile &mf) {
+        if (rc == SM_OK)
+            g_err = std::string(who) + ": " + mf.path + " could not be replaced; its warped rows are in " + mf.tmp.path() + " (rename it over the file)";
+        rc = SM_E_ARG;
+        s->index.erase(mf.path);
+    });
     w.stats.write_ms += (float)(now_ms() - t1);
     w.stats.total_ms = (float)(now_ms() - t_begin);
     return rc;

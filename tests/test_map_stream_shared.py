@@ -1,7 +1,7 @@
-"""The consumers of the shared map-file staging (MapStream over RenderMaps' buffers; surfelmapping_amd/csrc/sm_map_stream.h)
-interleaved on ONE context: the streamed renderers, sm_recall in its modes, then the map-file writer and the lenient reader.  Each
-consumer is checked in its own suite (test_render_maps.py, test_recall.py, multi-chunk files included); here every call finds
-the staging as the other consumer left it.  Files of one chunk each: 300 rows, none, 257 (a block with one row)."""
+"""The four consumers of the shared map-file staging (MapStream over the context's MapStaging; surfelmapping_amd/csrc/sm_map_stream.h)
+interleaved on ONE context: the streamed renderers, sm_recall in its modes, the lidar's sweeps of the set, sm_warp_by_time, then the
+map-file writer and the lenient reader.  Each consumer is checked in its own suite (test_render_maps.py, test_recall.py,
+test_lidar.py, test_warp.py, multi-chunk files included); here every call finds the staging as another consumer left it.  Files of one chunk each: 300 rows, none, 257 (a block with one row)."""
 import os
 
 import numpy as np
@@ -10,6 +10,7 @@ import pytest
 import model_view_ref as ref
 import recall_ref as cr
 import retire_ref as rr
+import warp_ref as wr
 from backends import assert_models_equal
 
 CAM, OVER = cr.CAM, cr.OVER
@@ -106,6 +107,20 @@ def test_consumers_interleaved_on_one_context(tmp_path):
     seen = got[2][got[2] >= 0]
     assert len(seen) > 200 and (seen < SIZES[0]).any() and ((seen >= SIZES[0]) & (seen < sum(SIZES))).any() and (seen >= sum(SIZES)).any()
 
+    # 3b. the lidar: two sweeps of the set in one pass, plane for plane the resident sweep of the concatenation
+    sn = capi.lidar_sensor(n_az=90, az0_deg=-178.0, az_step_deg=4.0, el_deg=np.arange(-7, 8, 2, dtype=np.float32), min_range=1.0,
+                           max_range=60.0, min_conf=0.0)
+    sweeps = np.stack([synth.pose_to_colmajor(synth.pose_matrix(*a)) for a in ((0, 0, 20), (2, 0, 8, 10.0))])
+    got = g.lidar_sweep_maps(paths, sweeps, sn)
+    st = g.lidar_stats()
+    assert st["chunks"] == 2 and st["passes"] == 1, st
+    for i, sp in enumerate(sweeps):
+        want = big.lidar_sweep(sp, sn)
+        for name in ("range", "id", "rgb", "sem"):
+            _same(got[name][i], want[name], ("lidar", name, i))
+    assert (got["id"] >= 0).sum() > 300
+    assert [(open(p, "rb").read(), os.stat(p).st_mtime_ns) for p in paths] == before
+
     # 4. the recall that moves: the reference's rows into the model, the rows that stay in the files
     ref_files = [[f.copy(), a, b] for f, (a, b) in zip(files, ids)]
     R, rewritten = cr.recall_files(ref_files, pose, radius)
@@ -123,6 +138,29 @@ def test_consumers_interleaved_on_one_context(tmp_path):
 
     # 5. the novel views of what is now in the files and in the model
     _image_equal(g, paths, views, np.concatenate([f[~k] for f, k in zip(files, near)] + [live, recalled]), "after MOVE")
+
+    # 5b. the warp by time of what the MOVE left, files and model: part of each file's rows is selected
+    table, t0 = wr.rigid_table(4, seed=5), -100
+    left = [f[~k] for f, k in zip(files, near)]
+    model = np.concatenate([live, recalled])
+    for f in left:
+        sel = wr.select(f[:, 7], t0, len(table))[0]
+        assert len(f) == 0 or 0 < sel.sum() < len(f), int(sel.sum())
+    empty = (open(paths[1], "rb").read(), os.stat(paths[1]).st_mtime_ns)
+    g.warp_by_time(paths, t0, table)
+    st = g.warp_stats()
+    assert st["files_rewritten"] == 2 and st["chunks"] == 2 and st["records_read"] == sum(len(f) for f in left), st
+    warped = [wr.warp_rows(f, t0, table) for f in left]
+    for p, f, (a, b) in zip(paths, warped, ids):
+        rows, a1, b1 = rr.read_map(p)
+        _same(rows, f, p)
+        assert (a1, b1) == (a, b)
+    _same(g.download_model(), wr.warp_rows(model, t0, table), "after the warp")
+    assert (open(paths[1], "rb").read(), os.stat(paths[1]).st_mtime_ns) == empty == before[1]
+    assert not [f for f in os.listdir(tmp_path) if f.endswith((".warp.tmp", ".recall.tmp"))]
+
+    # 5c. the novel views of the warped set
+    _image_equal(g, paths, views, np.concatenate(warped + [wr.warp_rows(model, t0, table)]), "after the warp")
 
     # 6. the writer and the lenient reader
     out = str(tmp_path / "saved.bin")

@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define SM_API_VERSION 4   /* bumped whenever a struct or an entry point changes (3, 4: round 3 -- asynchronous host path, rig step, sm_timings::k_scan_own, sm_host_alloc_frame; the staged shard entry points are gone).  Purely additive changes keep it: sm_model_view / sm_render_model*, sm_track_* and sm_track_*rgb* were added at 4, as were sm_warp_by_time / sm_loop_spread / sm_track_*_old / sm_close_loop and sm_track_*_window / sm_close_loop_rgb / sm_old_in_view / sm_*auto_loop*, and sm_fern_* / sm_search_pose_at / sm_close_loop_at / sm_*auto_place*: no existing struct or entry point changed. */
+#define SM_API_VERSION 4   /* bumped whenever a struct or an entry point changes (3, 4: round 3 -- asynchronous host path, rig step, sm_timings::k_scan_own, sm_host_alloc_frame; the staged shard entry points are gone).  Purely additive changes keep it: sm_model_view / sm_render_model*, sm_track_* and sm_track_*rgb* were added at 4, as were sm_warp_by_time / sm_loop_spread / sm_track_*_old / sm_close_loop and sm_track_*_window / sm_close_loop_rgb / sm_old_in_view / sm_*auto_loop*, and sm_fern_* / sm_search_pose_at / sm_close_loop_at / sm_*auto_place*, and sm_fill_* / sm_render_image_ex / sm_render_image_maps_ex: no existing struct or entry point changed. */
 
 /* error codes (reference: void returns + CheckGlDieOnError(); bool for map IO) */
 enum {
@@ -980,6 +980,71 @@ int sm_set_stereo(sm_ctx *s, const sm_stereo_params *p);
 int sm_stereo_depth(sm_ctx *s, const uint8_t *rgb_left, const uint8_t *rgb_right, uint16_t *depth_mm_out, uint16_t *disp16_out);
 int sm_stereo_depth_device(sm_ctx *s, const uint8_t *d_left, const uint8_t *d_right, uint16_t *d_depth_mm_out, uint16_t *d_disp16_out);
 int sm_stereo_download(sm_ctx *s, uint64_t *census_left, uint64_t *census_right, uint16_t *volume);
+
+/* ---- hole filling (DESIGN.md "4n. Hole filling") ----
+ * A novel view (sm_render_image, sm_render_image_maps) is empty (sem 0) between discs and where a near object uncovers what no
+ * frame saw, shows far surfels through one-pixel gaps of a near surface, and carries no depth.  This is the screen-space stage
+ * that mends the three: the view's depth in millimetres from its key map, and a depth-aware push-pull completion of
+ * (bgr, sem, depth_mm) in place.  All arithmetic is in integers; every division is a floor division.
+ *   Depth of a novel view.  A drawn pixel's key carries d24 = key >> 32, the window z = Z / 200 m in 24 bits:
+ *     zmm = (d24 * 200000 + 8388607) / 16777215 in 64 bits; depth_mm = zmm if zmm <= 65535, else 0 (beyond 65.535 m, as the
+ *     stereo stage's).  An empty pixel has depth 0 and sem 0; a drawn pixel beyond range has depth 0 and sem != 0.
+ *   Input, per pixel.  valid = (sem != 0), colour c[3], label s = sem, depth z = depth_mm, or z = 65536 where depth_mm == 0.
+ *   Output.  depth_mm = z if z < 65536, else 0.  A pixel still invalid is all zeros.
+ *   0. See-through (through_count = T > 0).  A valid pixel is made invalid if at least T of its 8 neighbours inside the image
+ *      are valid and nearer: z_n * (256 + tol) < z_p * 256.  The test reads the input's validity and depths, never another
+ *      pixel's verdict.
+ *   1. Pull, level l to l + 1, for l = 0 .. levels - 1; w' = (w + 1) / 2, h' = (h + 1) / 2.  Cell (X, Y) has the children
+ *      (2X + dx, 2Y + dy) inside level l, in the order dy outer, dx inner.  No valid child: the cell is invalid.  Otherwise, with
+ *      zmin the least child depth: the near set is the valid children with z * 256 <= zmin * (256 + tol), n its size;
+ *      c = (sum_near c + n/2) / n per channel; z = (sum_near z + n/2) / n; s = the label of the first child in order with
+ *      z == zmin; cnt = the valid level-0 pixels under the cell after step 0.  The cell may fill iff
+ *      cnt * 256 >= area * min_cover_256, area the level-0 pixels of the cell inside the image.
+ *   2. Push, for l = levels - 1 down to 0, level l + 1 complete first (the top level keeps its invalid cells).  Every pixel
+ *      (x, y) of level l that is invalid after the pull takes four taps, in this order and with these weights: (X, Y) 9, with
+ *      X = x >> 1, Y = y >> 1; (Xn, Y) 3, Xn = X + 1 if x is odd, else X - 1; (X, Yn) 3, Yn likewise; (Xn, Yn) 1.  A tap counts
+ *      if it is inside level l + 1, valid and may fill; if none counts the pixel stays invalid.  The group: with prefer_far the
+ *      taps with z * (256 + tol) >= zmax * 256, without it those with z * 256 <= zmin * (256 + tol).  With Wt the sum of the
+ *      group's weights: c = (sum w*c + Wt/2) / Wt; z = (sum w*z + Wt/2) / Wt; s = the label of the first tap in tap order among
+ *      the group's greatest weight.  The pixel becomes valid and, at levels >= 1, may fill.  Valid pixels of level 0 are never
+ *      rewritten.
+ *   levels bounds the hole: about 1.5 * 2^levels pixels from the nearest observed pixel, so sky stays empty except for a fringe.
+ * sm_fill_image takes n images of w x h in host memory, in place, and waits; depth_mm may be NULL (then every valid pixel has
+ *   depth 0).  sm_fill_image_device takes device pointers (depth_mm 2-byte aligned), is enqueued on the context's stream and not
+ *   waited for.  Both work in any context and touch no model state.
+ * sm_render_image_ex / sm_render_image_maps_ex are sm_render_image / sm_render_image_maps plus: fill (NULL = none) and
+ *   depth_mm_out (NULL = not wanted; per view h*w uint16).  With fill == NULL, bgr_out and sem_out equal the plain entry point's
+ *   bit for bit.  With fill they are, by definition, the completion applied to the call's own unfilled outputs.
+ * sm_fill_stats: of the last call that filled (summed over its images and, for a map set, over its passes); launches counts the
+ *   stage's kernel launches, at most levels + 2 per pass however many views it fills; device_ms is the stage's time (events).
+ * SM_E_ARG: NULL pointers, w or h <= 0, w*h > 2^28, a parameter outside its range, a misaligned depth_mm, sm_fill_stats before
+ *   any call that filled.  The _ex calls otherwise refuse what their plain forms refuse (a call between sm_stage_conflict and
+ *   sm_stage_cull, the file checks) and are SM_E_UNSUPPORTED in a sharded or rig context. */
+typedef struct sm_fill_params {
+    int32_t levels;         /* 0..8 pyramid levels above the image; 0 = no filling                        default 3  */
+    int32_t depth_tol_256;  /* 0..255: two depths are one layer if z_far*256 <= z_near*(256+tol)          default 13 */
+    int32_t through_count;  /* 0 = off, 1..8: nearer neighbours that make a pixel "seen through"          default 6  */
+    int32_t prefer_far;     /* push takes the farthest layer among its taps (1) or the nearest (0)        default 1  */
+    int32_t min_cover_256;  /* 0..256: share of a cell's pixels that must be observed before it may fill  default 64 */
+} sm_fill_params;
+typedef struct sm_fill_stats_t {
+    uint64_t valid;               /* input pixels with sem != 0 */
+    uint64_t seen_through;        /* ... of them, removed by step 0 */
+    uint64_t filled;              /* pixels the level-0 push filled */
+    uint64_t left_empty;          /* pixels invalid in the output */
+    uint32_t launches;
+    float device_ms;
+} sm_fill_stats_t;
+int sm_default_fill_params(sm_fill_params *p);               /* pure, no context */
+int sm_fill_image(sm_ctx *s, const sm_fill_params *p, int w, int h, uint32_t n, uint8_t *bgr, uint8_t *sem, uint16_t *depth_mm);
+int sm_fill_image_device(sm_ctx *s, const sm_fill_params *p, int w, int h, uint32_t n, uint8_t *d_bgr, uint8_t *d_sem,
+                         uint16_t *d_depth_mm);
+int sm_render_image_ex(sm_ctx *s, const float *view16, int w, int h, float fx, float fy, float cx, float cy,
+                       const sm_fill_params *fill, uint8_t *bgr_out, uint8_t *sem_out, uint16_t *depth_mm_out);
+int sm_render_image_maps_ex(sm_ctx *s, const sm_map_source *src, const float *views16, uint32_t n_views, int w, int h, float fx,
+                            float fy, float cx, float cy, const sm_fill_params *fill, uint8_t *bgr_out, uint8_t *sem_out,
+                            uint16_t *depth_mm_out);
+int sm_fill_stats(sm_ctx *s, sm_fill_stats_t *out);
 
 /* ---- per-pass entry points (GlobalModel / IndexMap methods), synchronous ---- */
 /* Upload RGB / metric depth / semantic textures directly (bypasses p0). */

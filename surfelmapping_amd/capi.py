@@ -45,6 +45,7 @@ SYMBOLS = (
     "sm_fern_download", "sm_fern_save", "sm_fern_load", "sm_fern_match", "sm_search_pose_at", "sm_close_loop_at",
     "sm_default_auto_place_params", "sm_set_auto_place", "sm_auto_place_stats",
     "sm_default_stereo_params", "sm_set_stereo", "sm_stereo_depth", "sm_stereo_depth_device", "sm_stereo_download",
+    "sm_default_fill_params", "sm_fill_image", "sm_fill_image_device", "sm_render_image_ex", "sm_render_image_maps_ex", "sm_fill_stats",
 )
 
 SM_COLL_SUM, SM_COLL_MIN, SM_COLL_GATHER = 0, 1, 2
@@ -393,6 +394,36 @@ def stereo_params(cfg, **over) -> SmStereoParams:
     return p
 
 
+class SmFillParams(C.Structure):
+    _fields_ = [("levels", C.c_int32), ("depth_tol_256", C.c_int32), ("through_count", C.c_int32), ("prefer_far", C.c_int32),
+                ("min_cover_256", C.c_int32)]
+
+
+class SmFillStats(C.Structure):
+    _fields_ = [("valid", C.c_uint64), ("seen_through", C.c_uint64), ("filled", C.c_uint64), ("left_empty", C.c_uint64),
+                ("launches", C.c_uint32), ("device_ms", C.c_float)]
+
+
+def fill_params(**over) -> SmFillParams:
+    """sm_default_fill_params (levels 3, depth_tol_256 13, through_count 6, prefer_far 1, min_cover_256 64) with fields overridden"""
+    p = SmFillParams()
+    load().sm_default_fill_params(C.byref(p))
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+def _fill_arg(fill):
+    """what the entry points' `fill` accepts: None (none), True (the defaults), a dict of overrides, or fill_params(...)"""
+    if fill is None or fill is False:
+        return None
+    if fill is True:
+        return fill_params()
+    return fill if isinstance(fill, SmFillParams) else fill_params(**fill)
+
+
 def search_params(**over) -> SmSearchParams:
     """sm_default_search_params (2 levels; +-2 m in x and z at 0.25 m, +-3 deg about y at 0.5 deg; refine 4, stride0 8, top_k 4,
     colour_thresh 0.1) with fields overridden; the four per-axis fields take a sequence of three"""
@@ -720,6 +751,13 @@ def load():
     L.sm_stereo_depth_device.argtypes = [vp, vp, vp, vp, vp]
     L.sm_stereo_download.argtypes = [vp, vp, vp, vp]
     L.sm_debug_stereo_ms.argtypes = [vp, C.POINTER(C.c_float)]                          # (a diagnostic, not in the header)
+    flp = C.POINTER(SmFillParams)
+    L.sm_default_fill_params.argtypes = [flp]
+    L.sm_fill_image.argtypes = [vp, flp, C.c_int, C.c_int, C.c_uint32, vp, vp, vp]
+    L.sm_fill_image_device.argtypes = [vp, flp, C.c_int, C.c_int, C.c_uint32, vp, vp, vp]
+    L.sm_render_image_ex.argtypes = [vp, vp, C.c_int, C.c_int] + [C.c_float] * 4 + [flp, vp, vp, vp]
+    L.sm_render_image_maps_ex.argtypes = [vp, C.POINTER(SmMapSource), vp, C.c_uint32, C.c_int, C.c_int] + [C.c_float] * 4 + [flp, vp, vp, vp]
+    L.sm_fill_stats.argtypes = [vp, C.POINTER(SmFillStats)]
     for name in SYMBOLS:
         getattr(L, name)          # AttributeError here = the library does not match the header
     _lib = L
@@ -1436,13 +1474,49 @@ class SurfelMap:
         self._chk(self._L.sm_download_depth(self._h, which, _ptr(out)), "sm_download_depth")
         return out
 
-    def render_image(self, view, w, h, fx, fy, cx, cy):
-        """Novel view (GlobalModel::renderImage): (bgr uint8[h][w][3], semantic uint8[h][w] = class + 1)."""
+    def render_image(self, view, w, h, fx, fy, cx, cy, fill=None, depth=False):
+        """Novel view (GlobalModel::renderImage): (bgr uint8[h][w][3], semantic uint8[h][w] = class + 1).  fill (True, a dict of
+        overrides or fill_params(...)): the holes are filled (sm_render_image_ex); depth: depth_mm uint16[h][w] comes third."""
         view = np.ascontiguousarray(view, np.float32)
         bgr = np.zeros((h, w, 3), np.uint8)
         sem = np.zeros((h, w), np.uint8)
-        self._chk(self._L.sm_render_image(self._h, _ptr(view), w, h, fx, fy, cx, cy, _ptr(bgr), _ptr(sem)), "sm_render_image")
-        return bgr, sem
+        fp = _fill_arg(fill)
+        if fp is None and not depth:
+            self._chk(self._L.sm_render_image(self._h, _ptr(view), w, h, fx, fy, cx, cy, _ptr(bgr), _ptr(sem)), "sm_render_image")
+            return bgr, sem
+        d = np.zeros((h, w), np.uint16) if depth else None
+        self._chk(self._L.sm_render_image_ex(self._h, _ptr(view), w, h, fx, fy, cx, cy, C.byref(fp) if fp is not None else None,
+                                             _ptr(bgr), _ptr(sem), _ptr(d)), "sm_render_image_ex")
+        return (bgr, sem, d) if depth else (bgr, sem)
+
+    # -- hole filling (sm_fill_*)
+    def fill_image(self, bgr, sem, depth_mm=None, fill=None):
+        """The completion of images that are already there (sm_fill_image): bgr uint8[H][W][3] or [N][H][W][3], sem uint8[H][W] or
+        [N][H][W], depth_mm uint16 likewise or None (every valid pixel then has depth 0).  fill as render_image's (None: the
+        defaults).  Returns new arrays: (bgr, sem) or (bgr, sem, depth_mm)."""
+        bgr, sem = np.array(bgr, np.uint8, order="C"), np.array(sem, np.uint8, order="C")
+        d = None if depth_mm is None else np.array(depth_mm, np.uint16, order="C")
+        if sem.ndim not in (2, 3) or bgr.shape != sem.shape + (3,) or (d is not None and d.shape != sem.shape):
+            raise SurfelMapError("sm_fill_image", SM_E_ARG, "bgr [..][H][W][3], sem and depth_mm [..][H][W] of one size are expected")
+        n = 1 if sem.ndim == 2 else sem.shape[0]
+        h, w = sem.shape[-2:]
+        fp = _fill_arg(True if fill is None else fill)
+        self._chk(self._L.sm_fill_image(self._h, C.byref(fp), w, h, n, _ptr(bgr), _ptr(sem), _ptr(d)), "sm_fill_image")
+        return (bgr, sem) if d is None else (bgr, sem, d)
+
+    def fill_image_device(self, d_bgr: int, d_sem: int, d_depth: int, w, h, n=1, fill=None):
+        """fill_image() of n images in this context's device memory, in place (sm_fill_image_device; d_depth 0: no depth): enqueued,
+        not waited for"""
+        fp = _fill_arg(True if fill is None else fill)
+        self._chk(self._L.sm_fill_image_device(self._h, C.byref(fp), w, h, n, d_bgr or None, d_sem or None, d_depth or None),
+                  "sm_fill_image_device")
+
+    def fill_stats(self) -> dict:
+        """of the last call that filled (sm_fill_stats): valid, seen_through, filled, left_empty (pixels, summed over the images),
+        launches, device_ms"""
+        st = SmFillStats()
+        self._chk(self._L.sm_fill_stats(self._h, C.byref(st)), "sm_fill_stats")
+        return {k: getattr(st, k) for k, _ in SmFillStats._fields_}
 
     def render_model(self, mvp, mv_inv, w, h, threshold=0.0, color_type=0, unstable=True, points=False, window=False,
                      time=0, time_delta=0, clear=(0, 0, 0, 0), depth=False, ids=False):
@@ -1476,19 +1550,27 @@ class SurfelMap:
         return int(n.value), (None if ms[0] < 0 else [float(x) for x in ms])
 
     # -- views of a map set (sm_render_image_maps, sm_render_model_maps)
-    def render_image_maps(self, paths, views, w, h, fx, fy, cx, cy, include_model=True):
+    def render_image_maps(self, paths, views, w, h, fx, fy, cx, cy, include_model=True, fill=None, depth=False):
         """Novel views of a map set -- the map files `paths` in that order, then (include_model) the live model -- streamed
         through the device without loading it: every view equals render_image() of a model that is their concatenation.
         views: float32[V][16] camera->world poses (column-major, as render_image takes them).  Returns (bgr uint8[V][h][w][3],
-        semantic uint8[V][h][w]).  One call reads every file once per batch of views (render_maps_stats()['passes'])."""
+        semantic uint8[V][h][w]).  One call reads every file once per batch of views (render_maps_stats()['passes']).  fill and
+        depth as render_image's (sm_render_image_maps_ex): depth_mm uint16[V][h][w] comes third."""
         views = np.ascontiguousarray(views, np.float32).reshape(-1, 16)
         V = views.shape[0]
         bgr = np.zeros((V, h, w, 3), np.uint8)
         sem = np.zeros((V, h, w), np.uint8)
         src = map_source(paths, include_model)
-        self._chk(self._L.sm_render_image_maps(self._h, C.byref(src), _ptr(views), V, w, h, fx, fy, cx, cy, _ptr(bgr), _ptr(sem)),
-                  "sm_render_image_maps")
-        return bgr, sem
+        fp = _fill_arg(fill)
+        if fp is None and not depth:
+            self._chk(self._L.sm_render_image_maps(self._h, C.byref(src), _ptr(views), V, w, h, fx, fy, cx, cy, _ptr(bgr), _ptr(sem)),
+                      "sm_render_image_maps")
+            return bgr, sem
+        d = np.zeros((V, h, w), np.uint16) if depth else None
+        self._chk(self._L.sm_render_image_maps_ex(self._h, C.byref(src), _ptr(views), V, w, h, fx, fy, cx, cy,
+                                                  C.byref(fp) if fp is not None else None, _ptr(bgr), _ptr(sem), _ptr(d)),
+                  "sm_render_image_maps_ex")
+        return (bgr, sem, d) if depth else (bgr, sem)
 
     def render_model_maps(self, paths, views, include_model=True, depth=False, ids=False):
         """Model views of a map set (see render_image_maps): `views` is a list of model_view(...) structs -- the arguments of

@@ -144,6 +144,12 @@ public:
         if (sm_render_image(ctx_, view.data(), iw_, ih_, ifx_, ify_, icx_, icy_, imageBgr_.data(), imageSem_.data()) != SM_OK)
             std::printf("renderImage: %s\n", sm_last_error());
     }
+    // a view of setImageSize's size that somebody else rendered (acquireImages with hole filling or depth): kept like renderImage's
+    void setImage(const unsigned char *bgr, const unsigned char *sem)
+    {
+        imageBgr_.assign(bgr, bgr + (size_t)iw_ * ih_ * 3);
+        imageSem_.assign(sem, sem + (size_t)iw_ * ih_);
+    }
     pangolin::GlTexture *getImageTex() { return imageTex_.texture; }
     pangolin::GlTexture *getSemanticTex() { return semTex_.texture; }
     const std::vector<unsigned char> &imageBGR() const { return imageBgr_; }      // h*w*3, B,G,R (FragColor = srgb.wzy)

@@ -173,6 +173,7 @@ public:
     void acquireImages(std::string path, const std::vector<Eigen::Matrix4f> &views, int w, int h, float fx, float fy, float cx,
                        float cy, int startId = 0)
     {
+        if (fillHoles_ || writeDepth_) { (void)acquireImagesEx(path, nullptr, true, views, w, h, fx, fy, cx, cy, startId); return; }
         if (path.empty() || path.back() != '/') path += "/";
         const std::string image_path = path + "image/", semantic_path = path + "semantic/";
         ::mkdir(image_path.c_str(), 0755);
@@ -199,6 +200,7 @@ public:
     bool acquireImages(std::string path, const std::vector<std::string> &mapFiles, const std::vector<Eigen::Matrix4f> &views, int w,
                        int h, float fx, float fy, float cx, float cy, int startId = 0, bool includeModel = true)
     {
+        if (fillHoles_ || writeDepth_) return acquireImagesEx(path, &mapFiles, includeModel, views, w, h, fx, fy, cx, cy, startId);
         if (path.empty() || path.back() != '/') path += "/";
         const std::string image_path = path + "image/", semantic_path = path + "semantic/";
         ::mkdir(image_path.c_str(), 0755);
@@ -228,6 +230,19 @@ public:
         }
         return ok;
     }
+
+    // What both acquireImages overloads add once switched on (sm_render_image_ex / sm_render_image_maps_ex; DESIGN.md "4n. Hole
+    // filling").  setFillHoles: the views' holes are closed by the depth-aware push-pull completion before they are written;
+    // levels, if not negative, replaces the default number of pyramid levels (3; 0..8).  setWriteDepth: each view's depth goes to
+    // <path>/depth/%06d.png, a 16-bit grey PNG in millimetres (0 = empty or beyond 65.535 m), the format KittiReader reads from
+    // PSMNet/.  With both off the overloads write what they always wrote.
+    void setFillHoles(bool on, int levels = -1)
+    {
+        fillHoles_ = on;
+        sm_default_fill_params(&fillParams_);
+        if (levels >= 0) fillParams_.levels = levels;
+    }
+    void setWriteDepth(bool on) { writeDepth_ = on; }
 
     // The second sensor's dump: what a lidar `sensor` (sm_lidar_sensor; sm_default_lidar_sensor) at each of `poses` (sensor->world,
     // the camera's axes) measures in the live model, written as <path>/velodyne/%06d.bin next to acquireImages' folders, in KITTI's
@@ -538,6 +553,61 @@ private:
         sm_default_loop_params(&c, &loopParams_);
         loopParams_.max_trans = loopMaxTrans_;
         return &loopParams_;
+    }
+    bool fillHoles_ = false, writeDepth_ = false;
+    sm_fill_params fillParams_{};
+    // acquireImages with setFillHoles or setWriteDepth on: mapFiles null = the live model, one sm_render_image_ex per view;
+    // otherwise the map set, one sm_render_image_maps_ex for all views.  The live model's image (globalModel.imageBGR() /
+    // imageSemantic(), its size) is left as the plain overload leaves it: the last view, filled if filling is on.  One difference
+    // remains: a view that cannot be rendered ends the call with the error printed and no file written (false; the void overload has
+    // no way to return it), where the plain live-model overload prints the error and writes the planes it has.
+    bool acquireImagesEx(std::string path, const std::vector<std::string> *mapFiles, bool includeModel, const std::vector<Eigen::Matrix4f> &views,
+                         int w, int h, float fx, float fy, float cx, float cy, int startId)
+    {
+        if (path.empty() || path.back() != '/') path += "/";
+        const std::string image_path = path + "image/", semantic_path = path + "semantic/", depth_path = path + "depth/";
+        ::mkdir(image_path.c_str(), 0755);
+        ::mkdir(semantic_path.c_str(), 0755);
+        if (writeDepth_) ::mkdir(depth_path.c_str(), 0755);
+        if (w <= 0 || h <= 0) return false;
+        const size_t npix = (size_t)w * h, V = views.size();
+        const sm_fill_params *fill = fillHoles_ ? &fillParams_ : nullptr;
+        std::vector<unsigned char> bgr(V * npix * 3), sem(V * npix), rgb(npix * 3);
+        std::vector<unsigned short> depth(writeDepth_ ? V * npix : 0);
+        (void)sm_sync(ctx_);                                             // (SM_FACADE_ASYNC: frames may still be in flight)
+        int rc = SM_OK;
+        if (mapFiles) {
+            std::vector<float> v16(V * 16);
+            for (size_t i = 0; i < V; ++i) std::memcpy(&v16[i * 16], views[i].data(), 64);
+            std::vector<const char *> paths;
+            for (const std::string &f : *mapFiles) paths.push_back(f.c_str());
+            const sm_map_source src{paths.data(), (uint32_t)paths.size(), includeModel ? 1 : 0};
+            rc = sm_render_image_maps_ex(ctx_, &src, v16.data(), (uint32_t)V, w, h, fx, fy, cx, cy, fill, bgr.data(), sem.data(),
+                                         writeDepth_ ? depth.data() : nullptr);
+        } else {
+            globalModel.setImageSize(w, h, fx, fy, cx, cy);              // as the plain overload leaves the model's image ...
+            for (size_t i = 0; i < V && rc == SM_OK; ++i) {
+                rc = sm_render_image_ex(ctx_, views[i].data(), w, h, fx, fy, cx, cy, fill, &bgr[i * npix * 3], &sem[i * npix],
+                                        writeDepth_ ? &depth[i * npix] : nullptr);
+                if (rc == SM_OK) globalModel.setImage(&bgr[i * npix * 3], &sem[i * npix]);     // ... the last view, here as written
+            }
+        }
+        if (rc != SM_OK) {
+            std::printf("acquireImages: %s\n", sm_last_error());
+            return false;
+        }
+        bool ok = true;
+        for (size_t i = 0; i < V; ++i, ++startId) {
+            char name[32];
+            std::snprintf(name, sizeof name, "%06d.png", startId);
+            const unsigned char *b = &bgr[i * npix * 3];
+            for (size_t p = 0; p < npix; ++p) { rgb[p * 3] = b[p * 3 + 2]; rgb[p * 3 + 1] = b[p * 3 + 1]; rgb[p * 3 + 2] = b[p * 3]; }
+            const bool r1 = sm_png::write((image_path + name).c_str(), rgb.data(), w, h, 3);
+            const bool r2 = sm_png::write((semantic_path + name).c_str(), &sem[i * npix], w, h, 1);
+            const bool r3 = !writeDepth_ || sm_png::write16((depth_path + name).c_str(), &depth[i * npix], w, h);
+            if (!(r1 && r2 && r3)) { std::printf("%s is NOT saved!\n", name); ok = false; }
+        }
+        return ok;
     }
     std::vector<unsigned short> stereoDepth_;
     bool beginCleanPoints = false;

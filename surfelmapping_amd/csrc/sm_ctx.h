@@ -16,6 +16,7 @@
 //   sm_lidar.hip     lidar sweeps (sm_lidar_*): beams against the live model and against streamed map files
 //   sm_place.hip     place recognition (sm_fern_*, sm_search_pose_at, sm_close_loop_at): fern codes, the keyframe database, the match
 //   sm_stereo.hip    stereo depth (sm_stereo_*): census, matching costs, path costs, winner and depth of a rectified pair
+//   sm_fill.hip      hole filling (sm_fill_*, sm_render_image_ex's and sm_render_image_maps_ex's stage): depth of a view, push-pull completion
 // and, beside it, for everything that touches a map file: sm_mapfile.h (the format: checked open, writer, chunk plan; host only),
 // sm_map_set.h (a listed set of files: the file index, the two openings, a rewrite's per-file record and temporary; host only) and
 // sm_map_stream.h (the double-buffered chunk stream of sm_render_maps.hip, sm_lidar.hip, sm_recall.hip and sm_warp.hip).  The staging
@@ -283,6 +284,21 @@ struct Stereo {
     Event ev[N_EV];
 };
 
+// hole filling (sm_fill.hip, sm_k_fill.h): the pyramid scratch beside d_export (which the render path is using), grown on demand;
+// sm_fill_image's device copies of the host images; the last call's tally, folded from per-tile partial sums once its kernels are done
+struct Fill {
+    Dev<uint8_t> d_scratch;            // level-0 validity | records of levels 1.. | level-5 counts | the two kernels' per-tile tallies
+    size_t bytes = 0;
+    Dev<uint8_t> d_img;                // bgr | sem | depth_mm of sm_fill_image's batch
+    size_t img_bytes = 0;
+    Event ev[2];                       // around the stage
+    sm_fill_stats_t stats{};
+    bool stats_valid = false;
+    bool pending = false;              // a stage is enqueued whose tallies and time are not in `stats` yet
+    size_t off_pull = 0, off_push = 0; // ... and where its tallies lie in the scratch
+    size_t n_pull = 0, n_push = 0;
+};
+
 // closing loops unasked (sm_loop.hip): the policy of sm_set_auto_loop and its tally
 struct AutoLoop {
     bool on = false;
@@ -518,6 +534,7 @@ struct sm_ctx {
     Lidar lid;
     Place place;
     Stereo stereo;
+    Fill fill;
     // host frame state (src/SurfelMapping.h:100-103)
     int tick = 0;
     bool ref_set = false;
@@ -632,6 +649,19 @@ void place_warp_poses(sm_ctx *s, const std::function<void(float *, int32_t)> &wa
 // the frame's code, the match, one attempt at the matched place, the keyframe.  loop_closed: that policy closed a loop on this call
 int auto_place_after_track(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const sm_track_params *params,
                            const sm_track_rgb_params *rgb_params, float *pose16_out, int track_status, bool loop_closed);
+// ---- sm_fill.hip ----
+// sm_fill_params' ranges (SM_E_ARG with g_err set); p null: nothing to check
+int check_fill_params(const sm_fill_params *p, const char *who);
+// device bytes the stage needs beside its planes for n images of w x h (the pyramid scratch): what a batch of views costs above its keys
+size_t fill_scratch_bytes(const sm_fill_params &p, int w, int h, size_t n);
+// k_fill_key_depth on the context's stream: depth_mm of `total` keys of novel views
+void fill_key_depth(sm_ctx *s, const uint64_t *key, size_t total, uint16_t *d_depth);
+// The render paths' use of the stage.  fill_begin: a call that may fill starts (the tally is the new call's).  fill_enqueue: the
+// completion of n device images in place on the context's stream (d_depth null: no depth).  fill_fold: waits for the stage and adds
+// its tallies and time to the call's; a call enqueues its next pass only after it.
+void fill_begin(sm_ctx *s);
+int fill_enqueue(sm_ctx *s, const sm_fill_params &p, int w, int h, uint32_t n, uint8_t *d_bgr, uint8_t *d_sem, uint16_t *d_depth);
+int fill_fold(sm_ctx *s);
 // ---- sm_loop.hip ----
 // sm_track_frame (rgb null) / sm_track_frame_rgb while sm_set_auto_loop is on: the young-window track, the census, one attempt
 int auto_loop_track(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params,

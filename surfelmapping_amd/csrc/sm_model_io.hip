@@ -1,5 +1,5 @@
 // sm_model_io.hip -- the model and the frame's textures in and out of the core: AoS download / upload, map files, the index
-// map, the raw feedback cloud, depth textures, the novel-view renderer (sm_render_image), caller device buffers, and the
+// map, the raw feedback cloud, depth textures, the novel-view renderer (sm_render_image, sm_render_image_ex), caller device buffers, and the
 // device-side export / append of sharded and rig runs.  Kernels: sm_k_io.h.
 #include "sm_ctx.h"
 #include "sm_k_io.h"
@@ -16,6 +16,44 @@ void sm_impl::render_splat_model(sm_ctx *s, const RenderParams &rp, uint64_t *ke
 {
     const uint32_t cnt = s->h_state->count;
     if (cnt) hipLaunchKernelGGL(k_render_splat, dim3((cnt + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, rp, key, id_base);
+}
+
+// sm_render_image, and with fill or depth_mm_out what sm_render_image_ex adds to it: the view's depth plane from its keys, the
+// completion of the three planes in place (sm_fill.hip) between the resolve and the copies
+static int render_image(sm_ctx *s, const float *view16, int w, int h, float fx, float fy, float cx, float cy, const sm_fill_params *fill,
+                        uint8_t *bgr_out, uint8_t *sem_out, uint16_t *depth_mm_out, const char *who)
+{
+    if (!s || !view16 || w <= 0 || h <= 0 || (uint64_t)w * h > (1u << 28) || !bgr_out || !sem_out) return SM_E_ARG;
+    HIPCK(hipSetDevice(s->cfg.device));
+    if (int rc = check_not_mid_cull(s, who)) return rc;
+    int rc = ensure_compact(s);
+    if (rc) return rc;
+    if ((rc = pull_state(s))) return rc;
+    const size_t npix = (size_t)w * h;
+    const bool depth = fill || depth_mm_out;
+    if ((rc = ensure_export(s, npix * (depth ? 14 : 12)))) return rc;            // [keys u64 | bgr | sem | depth_mm u16]
+    uint64_t *d_key = (uint64_t *)s->d_export.get();
+    uint8_t *d_bgr = (uint8_t *)s->d_export.get() + npix * 8, *d_sem = d_bgr + npix * 3;
+    uint16_t *d_depth = (uint16_t *)(d_sem + npix);
+    RenderParams rp;
+    invert4(view16, rp.t_inv);
+    rp.fx = fx; rp.fy = fy; rp.cx = cx; rp.cy = cy; rp.cols = (float)w; rp.rows = (float)h; rp.w = w; rp.h = h;
+    fill_keys(s, d_key, npix);
+    render_splat_model(s, rp, d_key, 0u);
+    hipLaunchKernelGGL(k_render_resolve, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s->stream, s->M, s->d_state, d_key,
+                       (int)npix, d_bgr, d_sem);
+    HIPCK(hipGetLastError());
+    if (depth) fill_key_depth(s, d_key, npix, d_depth);
+    if (fill) {
+        fill_begin(s);
+        if ((rc = fill_enqueue(s, *fill, w, h, 1u, d_bgr, d_sem, d_depth))) return rc;
+    }
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpyAsync(bgr_out, d_bgr, npix * 3, hipMemcpyDeviceToHost, s->stream));
+    HIPCK(hipMemcpyAsync(sem_out, d_sem, npix, hipMemcpyDeviceToHost, s->stream));
+    if (depth_mm_out) HIPCK(hipMemcpyAsync(depth_mm_out, d_depth, npix * 2, hipMemcpyDeviceToHost, s->stream));
+    HIPCK(hipStreamSynchronize(s->stream));
+    return fill ? fill_fold(s) : SM_OK;
 }
 
 extern "C" {
@@ -163,28 +201,17 @@ int sm_download_depth(sm_ctx *s, int which, float *dst)
 int sm_render_image(sm_ctx *s, const float *view16, int w, int h, float fx, float fy, float cx, float cy, uint8_t *bgr_out,
                     uint8_t *sem_out)
 {
-    if (!s || !view16 || w <= 0 || h <= 0 || (uint64_t)w * h > (1u << 28) || !bgr_out || !sem_out) return SM_E_ARG;
-    HIPCK(hipSetDevice(s->cfg.device));
-    if (int rc = check_not_mid_cull(s, "sm_render_image")) return rc;
-    int rc = ensure_compact(s);
-    if (rc) return rc;
-    if ((rc = pull_state(s))) return rc;
-    const size_t npix = (size_t)w * h;
-    if ((rc = ensure_export(s, npix * 12))) return rc;            // [keys u64 | bgr | sem]
-    uint64_t *d_key = (uint64_t *)s->d_export.get();
-    uint8_t *d_bgr = (uint8_t *)s->d_export.get() + npix * 8, *d_sem = d_bgr + npix * 3;
-    RenderParams rp;
-    invert4(view16, rp.t_inv);
-    rp.fx = fx; rp.fy = fy; rp.cx = cx; rp.cy = cy; rp.cols = (float)w; rp.rows = (float)h; rp.w = w; rp.h = h;
-    fill_keys(s, d_key, npix);
-    render_splat_model(s, rp, d_key, 0u);
-    hipLaunchKernelGGL(k_render_resolve, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s->stream, s->M, s->d_state, d_key,
-                       (int)npix, d_bgr, d_sem);
-    HIPCK(hipGetLastError());
-    HIPCK(hipMemcpyAsync(bgr_out, d_bgr, npix * 3, hipMemcpyDeviceToHost, s->stream));
-    HIPCK(hipMemcpyAsync(sem_out, d_sem, npix, hipMemcpyDeviceToHost, s->stream));
-    HIPCK(hipStreamSynchronize(s->stream));
-    return SM_OK;
+    return render_image(s, view16, w, h, fx, fy, cx, cy, nullptr, bgr_out, sem_out, nullptr, "sm_render_image");
+}
+
+int sm_render_image_ex(sm_ctx *s, const float *view16, int w, int h, float fx, float fy, float cx, float cy, const sm_fill_params *fill,
+                       uint8_t *bgr_out, uint8_t *sem_out, uint16_t *depth_mm_out)
+{
+    const char *who = "sm_render_image_ex";
+    if (!s) { g_err = std::string(who) + ": null context"; return SM_E_ARG; }
+    if (int rc = check_whole_map(s, who)) return rc;
+    if (int rc = check_fill_params(fill, who)) return rc;
+    return render_image(s, view16, w, h, fx, fy, cx, cy, fill, bgr_out, sem_out, depth_mm_out, who);
 }
 
 void *sm_device_alloc(sm_ctx *s, size_t bytes)

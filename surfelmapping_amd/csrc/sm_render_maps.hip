@@ -1,4 +1,4 @@
-// sm_render_maps.hip -- views of a map set (sm_render_image_maps, sm_render_model_maps; DESIGN.md "4f. Views of a map set"): map files streamed through the two
+// sm_render_maps.hip -- views of a map set (sm_render_image_maps and its _ex form, sm_render_model_maps; DESIGN.md "4f. Views of a map set"): map files streamed through the two
 // renderers in chunks, the live model last; for every source that streams map files, the context's MapStaging: its allocation and intake kernel.  Kernels: sm_k_render_maps.h.
 #include "sm_map_stream.h"
 #include "sm_k_render_maps.h"
@@ -17,6 +17,9 @@ struct Mode {
     const ViewShade *shade;                              // model view only
     // host outputs, per view npix * 3 | npix (image) or npix * 4 each (view: depth and id may be null)
     uint8_t *out0; uint8_t *out1; uint8_t *out2;
+    // image only (sm_render_image_maps_ex): the completion of every batch's planes (null: none), the depth plane (null: not wanted)
+    const sm_fill_params *fill;
+    uint16_t *out_depth;
 };
 
 int render_maps(sm_ctx *s, const sm_map_source *src, const char *fn, const Mode &md)
@@ -39,7 +42,11 @@ int render_maps(sm_ctx *s, const sm_map_source *src, const char *fn, const Mode 
 
     const size_t npix = (size_t)md.w * md.h;
     int cull;
-    const uint32_t B = maps_batch(md.n_views, npix, "SM_RENDER_MAPS_KEY_MB", "SM_RENDER_MAPS_NO_CULL", &cull);
+    // the key budget bounds what a view of the batch holds beside its keys too: the depth plane and the completion's pyramid
+    const bool depth16 = md.fill || md.out_depth;
+    const size_t extra = (depth16 ? npix * 2 : 0) + (md.fill ? fill_scratch_bytes(*md.fill, md.w, md.h, 1) : 0);
+    const uint32_t B = maps_batch(md.n_views, npix + (extra + 7) / 8, "SM_RENDER_MAPS_KEY_MB", "SM_RENDER_MAPS_NO_CULL", &cull);
+    if (md.fill) fill_begin(s);
     const unsigned pblocks = (unsigned)((npix + 255) / 256);
 
     // per-view parameters | shading | skipped counters | hit flags
@@ -59,7 +66,7 @@ int render_maps(sm_ctx *s, const sm_map_source *src, const char *fn, const Mode 
     HIPCK(hipMemsetAsync(d_skip, 0, V * 4, s->stream));
 
     // export scratch: keys | output planes of one batch | (model view + live model) overflow length and list
-    const size_t out_px = md.image ? 4 : 12;
+    const size_t out_px = md.image ? (depth16 ? 6 : 4) : 12;
     const size_t off_out = (size_t)B * npix * 8, off_ovf = off_out + (((size_t)B * npix * out_px + 255) & ~(size_t)255);
     if ((rc = ensure_export(s, off_ovf + ((!md.image && cnt) ? 256 + (size_t)cnt * 4 : 0)))) return rc;
     uint8_t *base = (uint8_t *)s->d_export.get();
@@ -79,6 +86,7 @@ int render_maps(sm_ctx *s, const sm_map_source *src, const char *fn, const Mode 
         rm.stats.passes++;
         // this batch's planes
         uint8_t *d_bgr = d_out, *d_sem = d_out + bp * 3;
+        uint16_t *d_depth16 = (uint16_t *)(d_out + bp * 4);
         uint32_t *d_rgba = (uint32_t *)d_out;
         float *d_depth = (float *)(d_out + bp * 4);
         int32_t *d_id = (int32_t *)(d_out + bp * 8);
@@ -140,8 +148,11 @@ int render_maps(sm_ctx *s, const sm_map_source *src, const char *fn, const Mode 
         if (md.image) hipLaunchKernelGGL(k_maps_finish_image, dim3((unsigned)((bp + 255) / 256)), dim3(256), 0, s->stream, d_key, bp, d_bgr, d_sem);
         else hipLaunchKernelGGL(k_maps_finish_view, dim3(pblocks, b), dim3(256), 0, s->stream, d_vs, d_key, npix, d_rgba, d_depth, d_id);
         HIPCK(hipGetLastError());
+        if (depth16) fill_key_depth(s, d_key, bp, d_depth16);
+        if (md.fill && (rc = fill_enqueue(s, *md.fill, md.w, md.h, b, d_bgr, d_sem, d_depth16))) return rc;
         const size_t vp0 = (size_t)v0 * npix;
         if (md.image) {
+            if (md.out_depth) HIPCK(hipMemcpyAsync(md.out_depth + vp0, d_depth16, bp * 2, hipMemcpyDeviceToHost, s->stream));
             HIPCK(hipMemcpyAsync(md.out0 + vp0 * 3, d_bgr, bp * 3, hipMemcpyDeviceToHost, s->stream));
             HIPCK(hipMemcpyAsync(md.out1 + vp0, d_sem, bp, hipMemcpyDeviceToHost, s->stream));
         } else {
@@ -150,6 +161,7 @@ int render_maps(sm_ctx *s, const sm_map_source *src, const char *fn, const Mode 
             if (md.out2) HIPCK(hipMemcpyAsync(md.out2 + vp0 * 4, d_id, bp * 4, hipMemcpyDeviceToHost, s->stream));
         }
         HIPCK(hipStreamSynchronize(s->stream));
+        if (md.fill && (rc = fill_fold(s))) return rc;
     }
     std::vector<uint32_t> skipped(V);
     HIPCK(hipMemcpy(skipped.data(), d_skip, V * 4, hipMemcpyDeviceToHost));
@@ -187,10 +199,11 @@ void sm_impl::maps_intake(sm_ctx *s, const float4 *d_rec, uint32_t n)
 
 extern "C" {
 
-int sm_render_image_maps(sm_ctx *s, const sm_map_source *src, const float *views16, uint32_t n_views, int w, int h, float fx, float fy,
-                         float cx, float cy, uint8_t *bgr_out, uint8_t *sem_out)
+// sm_render_image_maps (fn) and, with fill or depth_mm_out, what sm_render_image_maps_ex adds to it
+static int render_image_maps(sm_ctx *s, const sm_map_source *src, const float *views16, uint32_t n_views, int w, int h, float fx, float fy,
+                             float cx, float cy, const sm_fill_params *fill, uint8_t *bgr_out, uint8_t *sem_out, uint16_t *depth_mm_out,
+                             const char *fn)
 {
-    const char *fn = "sm_render_image_maps";
     if (!s || !src) { g_err = std::string(fn) + ": null context or source"; return SM_E_ARG; }
     if (n_views && (!views16 || !bgr_out || !sem_out)) { g_err = std::string(fn) + ": null views or outputs"; return SM_E_ARG; }
     if (w <= 0 || h <= 0 || (uint64_t)w * h > (1u << 28)) { g_err = std::string(fn) + ": width and height must be positive, w*h at most 2^28"; return SM_E_ARG; }
@@ -204,7 +217,24 @@ int sm_render_image_maps(sm_ctx *s, const sm_map_source *src, const float *views
     md.image = true; md.w = w; md.h = h; md.n_views = n_views;
     md.params = rps.data(); md.param_size = sizeof(RenderParams);
     md.out0 = bgr_out; md.out1 = sem_out;
+    md.fill = fill; md.out_depth = depth_mm_out;
     return render_maps(s, src, fn, md);
+}
+
+int sm_render_image_maps(sm_ctx *s, const sm_map_source *src, const float *views16, uint32_t n_views, int w, int h, float fx, float fy,
+                         float cx, float cy, uint8_t *bgr_out, uint8_t *sem_out)
+{
+    return render_image_maps(s, src, views16, n_views, w, h, fx, fy, cx, cy, nullptr, bgr_out, sem_out, nullptr, "sm_render_image_maps");
+}
+
+int sm_render_image_maps_ex(sm_ctx *s, const sm_map_source *src, const float *views16, uint32_t n_views, int w, int h, float fx, float fy,
+                            float cx, float cy, const sm_fill_params *fill, uint8_t *bgr_out, uint8_t *sem_out, uint16_t *depth_mm_out)
+{
+    const char *fn = "sm_render_image_maps_ex";
+    if (s)
+        if (int rc = check_whole_map(s, fn)) return rc;
+    if (int rc = check_fill_params(fill, fn)) return rc;
+    return render_image_maps(s, src, views16, n_views, w, h, fx, fy, cx, cy, fill, bgr_out, sem_out, depth_mm_out, fn);
 }
 
 int sm_render_model_maps(sm_ctx *s, const sm_map_source *src, const sm_model_view *views, uint32_t n_views, uint8_t *rgba, float *depth,

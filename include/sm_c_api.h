@@ -277,7 +277,7 @@ typedef struct sm_map_source {
 
 /* what the last sm_render_image_maps / sm_render_model_maps call of the context did */
 typedef struct sm_maps_stats {
-    uint64_t surfels_read;        /* records read from the files, all passes together */
+    uint64_t surfels_read;        /* records read from the files, all passes together (a blended call reads them twice per pass) */
     uint32_t chunks, passes;      /* chunks (at most 2^20 records) copied to the device; passes over the files */
     uint64_t pairs_tested;        /* (block of 256 records, view) pairs the view test ran on (0 with SM_RENDER_MAPS_NO_CULL=1) */
     uint64_t pairs_skipped;       /* ... of them, found outside the view and not drawn */
@@ -1045,6 +1045,54 @@ int sm_render_image_maps_ex(sm_ctx *s, const sm_map_source *src, const float *vi
                             float fy, float cx, float cy, const sm_fill_params *fill, uint8_t *bgr_out, uint8_t *sem_out,
                             uint16_t *depth_mm_out);
 int sm_fill_stats(sm_ctx *s, sm_fill_stats_t *out);
+
+/* ---- blended views (DESIGN.md "4o. Blended views") ----
+ * sm_render_image gives every pixel to exactly one surfel, the nearest; where the discs of one surface overlap the image shows
+ * patches of each disc's own colour.  The blended view draws the visible layer instead: a visibility pass, a weighted sum of the
+ * fragments within a depth band behind the front, a normalisation.  Everything is integer arithmetic on the renderer's own
+ * fragments, so the result is defined bit for bit and depends neither on the order of the surfels, nor on the chunking of a map
+ * set, nor on the views per pass.
+ *   A fragment is a (surfel, pixel) pair that the novel-view rasteriser accepts: the same quad, the same 24.8 fixed-point vertices,
+ *   edge functions and fill rule, the same float32 tx, ty, zw, and the same tests: tx*tx + ty*ty <= 1, 0 <= zw <= 1,
+ *   d24 < 16777215.  The fill rule gives a surfel at most one fragment per pixel.  A fragment carries d24, its 24-bit window
+ *   depth; q = tx*tx + ty*ty, the float32 value the circle test compares; and the surfel's colour word.
+ *   1. Visibility: the key map of sm_render_image, unchanged; front = key >> 32 on a drawn pixel.  sem_out and depth_mm_out come
+ *      from it exactly as in sm_render_image_ex: labels and depth are never blended.
+ *   2. Accumulate: a fragment contributes to its pixel iff (uint64)d24 * 256 <= (uint64)front * (256 + depth_tol_256); the winner
+ *      always does.  With i = min(255, (int32)(q * 256.0f)) its weight wt is 256 (falloff 0), 256 - i (falloff 1) or
+ *      ((256 - i) * (256 - i) + 255) >> 8 (falloff 2): always in 1..256.  Per pixel SW += wt and SC[c] += wt * colour[c] for
+ *      B, G, R.  The sums are exact for any set below 2^31 surfels (up to 2^47): the accumulators are 64 bits wide, four per
+ *      pixel, and a map set counts their 32 bytes in the key budget of a batch (SM_RENDER_MAPS_KEY_MB) next to the keys.
+ *   3. Normalise: on a drawn pixel bgr[c] = (SC[c] + SW / 2) / SW by floor division; an empty pixel stays 0, 0, 0.  A pixel with
+ *      one contributor has exactly that surfel's colour.
+ *   4. Fill, if asked, is applied afterwards to (bgr, sem, depth_mm) by the stage of sm_render_image_ex, unchanged.
+ * blend == NULL is the _ex call, bit for bit.  Over a map set the accumulation needs the finished key map, so every file is read
+ * twice per batch of views: sm_render_maps_stats then counts both readings in surfels_read, chunks and pairs_tested; passes keeps
+ * its meaning (batches).
+ * sm_blend_stats: of the last blended call, summed over its views and batches; launches counts the stage's kernels, device_ms
+ * their time (events; over a map set the second reading's kernels included).
+ * Errors follow the _ex forms: SM_E_ARG for NULLs, sizes, a parameter out of range, a call between sm_stage_conflict and
+ * sm_stage_cull and the file checks, SM_E_UNSUPPORTED in a sharded or rig context; sm_blend_stats before any blended call is
+ * SM_E_ARG.  The model view (sm_render_model) is not blended: it reproduces the reference's draw. */
+typedef struct sm_blend_params {
+    int32_t depth_tol_256;   /* 0..255: the band behind the front, in 1/256 of its depth (fill's layer test)  default 13 */
+    int32_t falloff;         /* 0 box, 1 linear, 2 quadratic in q                                              default 2  */
+} sm_blend_params;
+typedef struct sm_blend_stats_t {
+    uint64_t drawn;          /* pixels with sem != 0 */
+    uint64_t contributions;  /* fragments that passed the band test */
+    uint64_t changed;        /* drawn pixels whose colour differs from the nearest surfel's */
+    uint32_t launches;
+    float device_ms;
+} sm_blend_stats_t;
+int sm_default_blend_params(sm_blend_params *p);             /* pure, no context */
+int sm_render_image_blend(sm_ctx *s, const float *view16, int w, int h, float fx, float fy, float cx, float cy,
+                          const sm_blend_params *blend, const sm_fill_params *fill, uint8_t *bgr_out, uint8_t *sem_out,
+                          uint16_t *depth_mm_out);
+int sm_render_image_maps_blend(sm_ctx *s, const sm_map_source *src, const float *views16, uint32_t n_views, int w, int h, float fx,
+                               float fy, float cx, float cy, const sm_blend_params *blend, const sm_fill_params *fill,
+                               uint8_t *bgr_out, uint8_t *sem_out, uint16_t *depth_mm_out);
+int sm_blend_stats(sm_ctx *s, sm_blend_stats_t *out);
 
 /* ---- per-pass entry points (GlobalModel / IndexMap methods), synchronous ---- */
 /* Upload RGB / metric depth / semantic textures directly (bypasses p0). */

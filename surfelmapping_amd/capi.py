@@ -46,6 +46,7 @@ SYMBOLS = (
     "sm_default_auto_place_params", "sm_set_auto_place", "sm_auto_place_stats",
     "sm_default_stereo_params", "sm_set_stereo", "sm_stereo_depth", "sm_stereo_depth_device", "sm_stereo_download",
     "sm_default_fill_params", "sm_fill_image", "sm_fill_image_device", "sm_render_image_ex", "sm_render_image_maps_ex", "sm_fill_stats",
+    "sm_default_blend_params", "sm_render_image_blend", "sm_render_image_maps_blend", "sm_blend_stats",
 )
 
 SM_COLL_SUM, SM_COLL_MIN, SM_COLL_GATHER = 0, 1, 2
@@ -424,6 +425,35 @@ def _fill_arg(fill):
     return fill if isinstance(fill, SmFillParams) else fill_params(**fill)
 
 
+class SmBlendParams(C.Structure):
+    _fields_ = [("depth_tol_256", C.c_int32), ("falloff", C.c_int32)]
+
+
+class SmBlendStats(C.Structure):
+    _fields_ = [("drawn", C.c_uint64), ("contributions", C.c_uint64), ("changed", C.c_uint64), ("launches", C.c_uint32),
+                ("device_ms", C.c_float)]
+
+
+def blend_params(**over) -> SmBlendParams:
+    """sm_default_blend_params (depth_tol_256 13, falloff 2 = quadratic) with fields overridden"""
+    p = SmBlendParams()
+    load().sm_default_blend_params(C.byref(p))
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+def _blend_arg(blend):
+    """what the entry points' `blend` accepts: None (none), True (the defaults), a dict of overrides, or blend_params(...)"""
+    if blend is None or blend is False:
+        return None
+    if blend is True:
+        return blend_params()
+    return blend if isinstance(blend, SmBlendParams) else blend_params(**blend)
+
+
 def search_params(**over) -> SmSearchParams:
     """sm_default_search_params (2 levels; +-2 m in x and z at 0.25 m, +-3 deg about y at 0.5 deg; refine 4, stride0 8, top_k 4,
     colour_thresh 0.1) with fields overridden; the four per-axis fields take a sequence of three"""
@@ -758,6 +788,11 @@ def load():
     L.sm_render_image_ex.argtypes = [vp, vp, C.c_int, C.c_int] + [C.c_float] * 4 + [flp, vp, vp, vp]
     L.sm_render_image_maps_ex.argtypes = [vp, C.POINTER(SmMapSource), vp, C.c_uint32, C.c_int, C.c_int] + [C.c_float] * 4 + [flp, vp, vp, vp]
     L.sm_fill_stats.argtypes = [vp, C.POINTER(SmFillStats)]
+    blp = C.POINTER(SmBlendParams)
+    L.sm_default_blend_params.argtypes = [blp]
+    L.sm_render_image_blend.argtypes = [vp, vp, C.c_int, C.c_int] + [C.c_float] * 4 + [blp, flp, vp, vp, vp]
+    L.sm_render_image_maps_blend.argtypes = [vp, C.POINTER(SmMapSource), vp, C.c_uint32, C.c_int, C.c_int] + [C.c_float] * 4 + [blp, flp, vp, vp, vp]
+    L.sm_blend_stats.argtypes = [vp, C.POINTER(SmBlendStats)]
     for name in SYMBOLS:
         getattr(L, name)          # AttributeError here = the library does not match the header
     _lib = L
@@ -1474,13 +1509,22 @@ class SurfelMap:
         self._chk(self._L.sm_download_depth(self._h, which, _ptr(out)), "sm_download_depth")
         return out
 
-    def render_image(self, view, w, h, fx, fy, cx, cy, fill=None, depth=False):
+    def render_image(self, view, w, h, fx, fy, cx, cy, fill=None, depth=False, blend=None):
         """Novel view (GlobalModel::renderImage): (bgr uint8[h][w][3], semantic uint8[h][w] = class + 1).  fill (True, a dict of
-        overrides or fill_params(...)): the holes are filled (sm_render_image_ex); depth: depth_mm uint16[h][w] comes third."""
+        overrides or fill_params(...)): the holes are filled (sm_render_image_ex); depth: depth_mm uint16[h][w] comes third.
+        blend (True, a dict of overrides or blend_params(...)): bgr is the blend of the visible layer's discs, not the nearest
+        disc's colour (sm_render_image_blend; blend_stats())."""
         view = np.ascontiguousarray(view, np.float32)
         bgr = np.zeros((h, w, 3), np.uint8)
         sem = np.zeros((h, w), np.uint8)
         fp = _fill_arg(fill)
+        bp = _blend_arg(blend)
+        if bp is not None:
+            d = np.zeros((h, w), np.uint16) if depth else None
+            self._chk(self._L.sm_render_image_blend(self._h, _ptr(view), w, h, fx, fy, cx, cy, C.byref(bp),
+                                                    C.byref(fp) if fp is not None else None, _ptr(bgr), _ptr(sem), _ptr(d)),
+                      "sm_render_image_blend")
+            return (bgr, sem, d) if depth else (bgr, sem)
         if fp is None and not depth:
             self._chk(self._L.sm_render_image(self._h, _ptr(view), w, h, fx, fy, cx, cy, _ptr(bgr), _ptr(sem)), "sm_render_image")
             return bgr, sem
@@ -1518,6 +1562,12 @@ class SurfelMap:
         self._chk(self._L.sm_fill_stats(self._h, C.byref(st)), "sm_fill_stats")
         return {k: getattr(st, k) for k, _ in SmFillStats._fields_}
 
+    def blend_stats(self) -> dict:
+        """of the last blended call (sm_blend_stats): drawn, contributions, changed (summed over its views), launches, device_ms"""
+        st = SmBlendStats()
+        self._chk(self._L.sm_blend_stats(self._h, C.byref(st)), "sm_blend_stats")
+        return {k: getattr(st, k) for k, _ in SmBlendStats._fields_}
+
     def render_model(self, mvp, mv_inv, w, h, threshold=0.0, color_type=0, unstable=True, points=False, window=False,
                      time=0, time_delta=0, clear=(0, 0, 0, 0), depth=False, ids=False):
         """The model view (GlobalModel::renderModel, sm_render_model): mvp / mv_inv column-major float32[16] (or 4x4).
@@ -1550,18 +1600,26 @@ class SurfelMap:
         return int(n.value), (None if ms[0] < 0 else [float(x) for x in ms])
 
     # -- views of a map set (sm_render_image_maps, sm_render_model_maps)
-    def render_image_maps(self, paths, views, w, h, fx, fy, cx, cy, include_model=True, fill=None, depth=False):
+    def render_image_maps(self, paths, views, w, h, fx, fy, cx, cy, include_model=True, fill=None, depth=False, blend=None):
         """Novel views of a map set -- the map files `paths` in that order, then (include_model) the live model -- streamed
         through the device without loading it: every view equals render_image() of a model that is their concatenation.
         views: float32[V][16] camera->world poses (column-major, as render_image takes them).  Returns (bgr uint8[V][h][w][3],
         semantic uint8[V][h][w]).  One call reads every file once per batch of views (render_maps_stats()['passes']).  fill and
-        depth as render_image's (sm_render_image_maps_ex): depth_mm uint16[V][h][w] comes third."""
+        depth as render_image's (sm_render_image_maps_ex): depth_mm uint16[V][h][w] comes third.  blend as render_image's
+        (sm_render_image_maps_blend): every file is then read twice per batch."""
         views = np.ascontiguousarray(views, np.float32).reshape(-1, 16)
         V = views.shape[0]
         bgr = np.zeros((V, h, w, 3), np.uint8)
         sem = np.zeros((V, h, w), np.uint8)
         src = map_source(paths, include_model)
         fp = _fill_arg(fill)
+        bp = _blend_arg(blend)
+        if bp is not None:
+            d = np.zeros((V, h, w), np.uint16) if depth else None
+            self._chk(self._L.sm_render_image_maps_blend(self._h, C.byref(src), _ptr(views), V, w, h, fx, fy, cx, cy, C.byref(bp),
+                                                         C.byref(fp) if fp is not None else None, _ptr(bgr), _ptr(sem), _ptr(d)),
+                      "sm_render_image_maps_blend")
+            return (bgr, sem, d) if depth else (bgr, sem)
         if fp is None and not depth:
             self._chk(self._L.sm_render_image_maps(self._h, C.byref(src), _ptr(views), V, w, h, fx, fy, cx, cy, _ptr(bgr), _ptr(sem)),
                       "sm_render_image_maps")

@@ -173,7 +173,7 @@ public:
     void acquireImages(std::string path, const std::vector<Eigen::Matrix4f> &views, int w, int h, float fx, float fy, float cx,
                        float cy, int startId = 0)
     {
-        if (fillHoles_ || writeDepth_) { (void)acquireImagesEx(path, nullptr, true, views, w, h, fx, fy, cx, cy, startId); return; }
+        if (fillHoles_ || writeDepth_ || blend_) { (void)acquireImagesEx(path, nullptr, true, views, w, h, fx, fy, cx, cy, startId); return; }
         if (path.empty() || path.back() != '/') path += "/";
         const std::string image_path = path + "image/", semantic_path = path + "semantic/";
         ::mkdir(image_path.c_str(), 0755);
@@ -200,7 +200,7 @@ public:
     bool acquireImages(std::string path, const std::vector<std::string> &mapFiles, const std::vector<Eigen::Matrix4f> &views, int w,
                        int h, float fx, float fy, float cx, float cy, int startId = 0, bool includeModel = true)
     {
-        if (fillHoles_ || writeDepth_) return acquireImagesEx(path, &mapFiles, includeModel, views, w, h, fx, fy, cx, cy, startId);
+        if (fillHoles_ || writeDepth_ || blend_) return acquireImagesEx(path, &mapFiles, includeModel, views, w, h, fx, fy, cx, cy, startId);
         if (path.empty() || path.back() != '/') path += "/";
         const std::string image_path = path + "image/", semantic_path = path + "semantic/";
         ::mkdir(image_path.c_str(), 0755);
@@ -243,6 +243,17 @@ public:
         if (levels >= 0) fillParams_.levels = levels;
     }
     void setWriteDepth(bool on) { writeDepth_ = on; }
+    // setBlend (sm_render_image_blend / sm_render_image_maps_blend; DESIGN.md "4o. Blended views"): the colour of a pixel is the
+    // weighted mean of the discs of its visible layer, not the nearest disc's; labels and depth stay the nearest disc's.  tol
+    // (0..255, in 1/256 of the front depth) and falloff (0 box, 1 linear, 2 quadratic), if not negative, replace the defaults (13,
+    // 2).  Off by default; a map set is then read twice per batch of views.
+    void setBlend(bool on, int tol = -1, int falloff = -1)
+    {
+        blend_ = on;
+        sm_default_blend_params(&blendParams_);
+        if (tol >= 0) blendParams_.depth_tol_256 = tol;
+        if (falloff >= 0) blendParams_.falloff = falloff;
+    }
 
     // The second sensor's dump: what a lidar `sensor` (sm_lidar_sensor; sm_default_lidar_sensor) at each of `poses` (sensor->world,
     // the camera's axes) measures in the live model, written as <path>/velodyne/%06d.bin next to acquireImages' folders, in KITTI's
@@ -554,10 +565,11 @@ private:
         loopParams_.max_trans = loopMaxTrans_;
         return &loopParams_;
     }
-    bool fillHoles_ = false, writeDepth_ = false;
+    bool fillHoles_ = false, writeDepth_ = false, blend_ = false;
     sm_fill_params fillParams_{};
-    // acquireImages with setFillHoles or setWriteDepth on: mapFiles null = the live model, one sm_render_image_ex per view;
-    // otherwise the map set, one sm_render_image_maps_ex for all views.  The live model's image (globalModel.imageBGR() /
+    sm_blend_params blendParams_{};
+    // acquireImages with setFillHoles, setWriteDepth or setBlend on: mapFiles null = the live model, one sm_render_image_blend per
+    // view; otherwise the map set, one sm_render_image_maps_blend for all views (with blending off these are the _ex calls).  The live model's image (globalModel.imageBGR() /
     // imageSemantic(), its size) is left as the plain overload leaves it: the last view, filled if filling is on.  One difference
     // remains: a view that cannot be rendered ends the call with the error printed and no file written (false; the void overload has
     // no way to return it), where the plain live-model overload prints the error and writes the planes it has.
@@ -572,6 +584,7 @@ private:
         if (w <= 0 || h <= 0) return false;
         const size_t npix = (size_t)w * h, V = views.size();
         const sm_fill_params *fill = fillHoles_ ? &fillParams_ : nullptr;
+        const sm_blend_params *blend = blend_ ? &blendParams_ : nullptr;
         std::vector<unsigned char> bgr(V * npix * 3), sem(V * npix), rgb(npix * 3);
         std::vector<unsigned short> depth(writeDepth_ ? V * npix : 0);
         (void)sm_sync(ctx_);                                             // (SM_FACADE_ASYNC: frames may still be in flight)
@@ -582,13 +595,13 @@ private:
             std::vector<const char *> paths;
             for (const std::string &f : *mapFiles) paths.push_back(f.c_str());
             const sm_map_source src{paths.data(), (uint32_t)paths.size(), includeModel ? 1 : 0};
-            rc = sm_render_image_maps_ex(ctx_, &src, v16.data(), (uint32_t)V, w, h, fx, fy, cx, cy, fill, bgr.data(), sem.data(),
-                                         writeDepth_ ? depth.data() : nullptr);
+            rc = sm_render_image_maps_blend(ctx_, &src, v16.data(), (uint32_t)V, w, h, fx, fy, cx, cy, blend, fill, bgr.data(), sem.data(),
+                                            writeDepth_ ? depth.data() : nullptr);
         } else {
             globalModel.setImageSize(w, h, fx, fy, cx, cy);              // as the plain overload leaves the model's image ...
             for (size_t i = 0; i < V && rc == SM_OK; ++i) {
-                rc = sm_render_image_ex(ctx_, views[i].data(), w, h, fx, fy, cx, cy, fill, &bgr[i * npix * 3], &sem[i * npix],
-                                        writeDepth_ ? &depth[i * npix] : nullptr);
+                rc = sm_render_image_blend(ctx_, views[i].data(), w, h, fx, fy, cx, cy, blend, fill, &bgr[i * npix * 3], &sem[i * npix],
+                                           writeDepth_ ? &depth[i * npix] : nullptr);
                 if (rc == SM_OK) globalModel.setImage(&bgr[i * npix * 3], &sem[i * npix]);     // ... the last view, here as written
             }
         }

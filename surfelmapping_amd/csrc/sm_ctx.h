@@ -17,6 +17,7 @@
 //   sm_place.hip     place recognition (sm_fern_*, sm_search_pose_at, sm_close_loop_at): fern codes, the keyframe database, the match
 //   sm_stereo.hip    stereo depth (sm_stereo_*): census, matching costs, path costs, winner and depth of a rectified pair
 //   sm_fill.hip      hole filling (sm_fill_*, sm_render_image_ex's and sm_render_image_maps_ex's stage): depth of a view, push-pull completion
+//   sm_blend.hip     blended views (sm_render_image_blend, sm_render_image_maps_blend): the visible layer's accumulation and normalisation, a stage of both render paths
 // and, beside it, for everything that touches a map file: sm_mapfile.h (the format: checked open, writer, chunk plan; host only),
 // sm_map_set.h (a listed set of files: the file index, the two openings, a rewrite's per-file record and temporary; host only) and
 // sm_map_stream.h (the double-buffered chunk stream of sm_render_maps.hip, sm_lidar.hip, sm_recall.hip and sm_warp.hip).  The staging
@@ -299,6 +300,16 @@ struct Fill {
     size_t n_pull = 0, n_push = 0;
 };
 
+// blended views (sm_blend.hip, sm_k_blend.h): the accumulators beside d_export, owned like the fill scratch and grown on demand;
+// the last blended call's tally, folded from the device's once a batch's kernels are done
+struct Blend {
+    Dev<unsigned long long> d_scratch; // the tally (contributions, drawn, changed; 256 bytes) | SW, SB, SG, SR per pixel of a batch
+    size_t bytes = 0;
+    Event ev[2];                       // around what the stage runs outside a chunk stream
+    sm_blend_stats_t stats{};
+    bool stats_valid = false;
+};
+
 // closing loops unasked (sm_loop.hip): the policy of sm_set_auto_loop and its tally
 struct AutoLoop {
     bool on = false;
@@ -535,6 +546,7 @@ struct sm_ctx {
     Place place;
     Stereo stereo;
     Fill fill;
+    Blend blend;
     // host frame state (src/SurfelMapping.h:100-103)
     int tick = 0;
     bool ref_set = false;
@@ -662,6 +674,31 @@ void fill_key_depth(sm_ctx *s, const uint64_t *key, size_t total, uint16_t *d_de
 void fill_begin(sm_ctx *s);
 int fill_enqueue(sm_ctx *s, const sm_fill_params &p, int w, int h, uint32_t n, uint8_t *d_bgr, uint8_t *d_sem, uint16_t *d_depth);
 int fill_fold(sm_ctx *s);
+// ---- sm_blend.hip ----
+// sm_blend_params' ranges (SM_E_ARG with g_err set); p null: nothing to check
+int check_blend_params(const sm_blend_params *p, const char *who);
+// The render paths' use of the stage, all on the context's stream.  blend_begin: a blended call starts (the tally is the new
+// call's).  blend_clear: accumulators for `pixels` pixels (all views of a batch), zeroed with the device's tally.  blend_mark: what
+// follows up to blend_normalise is timed by the stage itself (a chunk stream times its own kernels: blend_add_ms).
+// blend_accum_model: the live model's fragments into the accumulators of the view whose keys are d_key (`acc_pixel`: where that
+// view begins in the batch).  blend_accum_chunk: the chunk in the context's staging (after maps_intake) into `views` views.
+// blend_normalise: the sums become the colours of `views` views of npix pixels in d_bgr, over the nearest colours it holds.
+// blend_fold: waits for the stream and adds the batch's tally and time to the call's.
+void blend_begin(sm_ctx *s);
+int blend_clear(sm_ctx *s, size_t pixels);
+int blend_mark(sm_ctx *s);
+void blend_accum_model(sm_ctx *s, const sm_blend_params &p, const RenderParams &rp, const uint64_t *d_key, size_t acc_pixel);
+void blend_accum_chunk(sm_ctx *s, const sm_blend_params &p, uint32_t n, const RenderParams *d_rps, const uint64_t *d_key, size_t npix,
+                       uint32_t views, int cull);
+int blend_normalise(sm_ctx *s, const uint64_t *d_key, size_t npix, uint32_t views, uint8_t *d_bgr, const uint8_t *d_sem);
+void blend_add_ms(sm_ctx *s, float ms);
+int blend_fold(sm_ctx *s);
+// ---- the novel view behind sm_render_image, _ex and _blend (sm_model_io.hip) and its map-set form (sm_render_maps.hip) ----
+int render_image(sm_ctx *s, const float *view16, int w, int h, float fx, float fy, float cx, float cy, const sm_blend_params *blend,
+                 const sm_fill_params *fill, uint8_t *bgr_out, uint8_t *sem_out, uint16_t *depth_mm_out, const char *who);
+int render_image_maps(sm_ctx *s, const sm_map_source *src, const float *views16, uint32_t n_views, int w, int h, float fx, float fy,
+                      float cx, float cy, const sm_blend_params *blend, const sm_fill_params *fill, uint8_t *bgr_out, uint8_t *sem_out,
+                      uint16_t *depth_mm_out, const char *fn);
 // ---- sm_loop.hip ----
 // sm_track_frame (rgb null) / sm_track_frame_rgb while sm_set_auto_loop is on: the young-window track, the census, one attempt
 int auto_loop_track(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params,

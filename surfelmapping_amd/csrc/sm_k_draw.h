@@ -35,7 +35,20 @@ __device__ __forceinline__ bool top_left(const RVert &a, const RVert &b)
     return (dy == 0 && dx > 0) || (dy < 0);
 }
 
-__device__ __forceinline__ void raster_tri(RVert v0, RVert v1, RVert v2, int w, int h, uint32_t id, uint64_t *__restrict__ key)
+// What is done with a fragment -- a (surfel, pixel) pair that passed every test -- is the caller's: frag(p, d24, q) gets the pixel
+// p = py * w + px, the 24-bit window depth and q = tx*tx + ty*ty, the value the circle test compared.  The key pass (KeyFrag) and
+// the blended view's accumulation (sm_k_blend.h) are two such actions over one walk, so they see the same fragments.
+struct KeyFrag {
+    uint64_t *__restrict__ key;
+    uint32_t id;
+    __device__ __forceinline__ void operator()(size_t p, uint32_t d24, float) const
+    {
+        atomicMin((unsigned long long *)&key[p], (unsigned long long)(((uint64_t)d24 << 32) | id));
+    }
+};
+
+template <typename Frag>
+__device__ __forceinline__ void raster_tri(RVert v0, RVert v1, RVert v2, int w, int h, Frag &frag)
 {
     long long area = edge64(v0, v1, v2.X, v2.Y);
     if (area == 0) return;
@@ -55,18 +68,20 @@ __device__ __forceinline__ void raster_tri(RVert v0, RVert v1, RVert v2, int w, 
                         l2 = (float)((double)e2 / (double)area);
             const float tx = (l0 * v0.tx + l1 * v1.tx) + l2 * v2.tx;
             const float ty = (l0 * v0.ty + l1 * v1.ty) + l2 * v2.ty;
-            if (tx * tx + ty * ty > 1.0f) continue;                         // draw_image.frag:13-14
+            const float q = tx * tx + ty * ty;
+            if (q > 1.0f) continue;                                         // draw_image.frag:13-14
             const float zw = (l0 * v0.zw + l1 * v1.zw) + l2 * v2.zw;
             if (!(zw >= 0.0f && zw <= 1.0f)) continue;
             const uint32_t d24 = (uint32_t)floor((double)zw * 16777215.0 + 0.5);
             if (d24 >= 16777215u) continue;
-            atomicMin((unsigned long long *)&key[(size_t)py * w + px], (unsigned long long)(((uint64_t)d24 << 32) | id));
+            frag((size_t)py * w + px, d24, q);
         }
 }
 
-// One surfel of the novel view (draw_image.vert:18-28, draw_image_adaptive.geom:38-83): row `k` of the source, drawn under `id`.
+// One surfel of the novel view (draw_image.vert:18-28, draw_image_adaptive.geom:38-83): row `k` of the source, its fragments to `frag`.
+template <typename Frag>
 __device__ __forceinline__ void render_surfel(const RenderParams &rp, const float4 *__restrict__ pos_conf,
-                                              const float4 *__restrict__ norm_rad, uint32_t k, uint32_t id, uint64_t *__restrict__ key)
+                                              const float4 *__restrict__ norm_rad, uint32_t k, Frag &frag)
 {
     const float maxDepth = 200.0f;                                          // src/GlobalModel.cpp:797
     const float4 pc = pos_conf[k];
@@ -105,8 +120,16 @@ __device__ __forceinline__ void render_surfel(const RenderParams &rp, const floa
         rv[q].zw = 0.5f * zn + 0.5f;
         rv[q].tx = tcx[q]; rv[q].ty = tcy[q];
     }
-    raster_tri(rv[0], rv[1], rv[2], rp.w, rp.h, id, key);                   // triangle strip
-    raster_tri(rv[2], rv[1], rv[3], rp.w, rp.h, id, key);
+    raster_tri(rv[0], rv[1], rv[2], rp.w, rp.h, frag);                      // triangle strip
+    raster_tri(rv[2], rv[1], rv[3], rp.w, rp.h, frag);
+}
+
+// ... drawn under `id` into a key map
+__device__ __forceinline__ void render_surfel(const RenderParams &rp, const float4 *__restrict__ pos_conf,
+                                              const float4 *__restrict__ norm_rad, uint32_t k, uint32_t id, uint64_t *__restrict__ key)
+{
+    KeyFrag frag{key, id};
+    render_surfel(rp, pos_conf, norm_rad, k, frag);
 }
 
 // draw_image.frag:11-19 from the winner's colour word: B, G, R (vBGR = srgb.wzy) and class + 1

@@ -1,5 +1,5 @@
 // sm_model_io.hip -- the model and the frame's textures in and out of the core: AoS download / upload, map files, the index
-// map, the raw feedback cloud, depth textures, the novel-view renderer (sm_render_image, sm_render_image_ex), caller device buffers, and the
+// map, the raw feedback cloud, depth textures, the novel-view renderer (sm_render_image, sm_render_image_ex and the view behind sm_render_image_blend), caller device buffers, and the
 // device-side export / append of sharded and rig runs.  Kernels: sm_k_io.h.
 #include "sm_ctx.h"
 #include "sm_k_io.h"
@@ -19,9 +19,10 @@ void sm_impl::render_splat_model(sm_ctx *s, const RenderParams &rp, uint64_t *ke
 }
 
 // sm_render_image, and with fill or depth_mm_out what sm_render_image_ex adds to it: the view's depth plane from its keys, the
-// completion of the three planes in place (sm_fill.hip) between the resolve and the copies
-static int render_image(sm_ctx *s, const float *view16, int w, int h, float fx, float fy, float cx, float cy, const sm_fill_params *fill,
-                        uint8_t *bgr_out, uint8_t *sem_out, uint16_t *depth_mm_out, const char *who)
+// completion of the three planes in place (sm_fill.hip) between the resolve and the copies; with blend what sm_render_image_blend
+// adds: the colours of the visible layer blended over the resolve's (sm_blend.hip), ahead of the completion
+int sm_impl::render_image(sm_ctx *s, const float *view16, int w, int h, float fx, float fy, float cx, float cy, const sm_blend_params *blend,
+                          const sm_fill_params *fill, uint8_t *bgr_out, uint8_t *sem_out, uint16_t *depth_mm_out, const char *who)
 {
     if (!s || !view16 || w <= 0 || h <= 0 || (uint64_t)w * h > (1u << 28) || !bgr_out || !sem_out) return SM_E_ARG;
     HIPCK(hipSetDevice(s->cfg.device));
@@ -43,6 +44,12 @@ static int render_image(sm_ctx *s, const float *view16, int w, int h, float fx, 
     hipLaunchKernelGGL(k_render_resolve, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s->stream, s->M, s->d_state, d_key,
                        (int)npix, d_bgr, d_sem);
     HIPCK(hipGetLastError());
+    if (blend) {
+        blend_begin(s);
+        if ((rc = blend_mark(s)) || (rc = blend_clear(s, npix))) return rc;
+        blend_accum_model(s, *blend, rp, d_key, 0);
+        if ((rc = blend_normalise(s, d_key, npix, 1u, d_bgr, d_sem))) return rc;
+    }
     if (depth) fill_key_depth(s, d_key, npix, d_depth);
     if (fill) {
         fill_begin(s);
@@ -53,6 +60,7 @@ static int render_image(sm_ctx *s, const float *view16, int w, int h, float fx, 
     HIPCK(hipMemcpyAsync(sem_out, d_sem, npix, hipMemcpyDeviceToHost, s->stream));
     if (depth_mm_out) HIPCK(hipMemcpyAsync(depth_mm_out, d_depth, npix * 2, hipMemcpyDeviceToHost, s->stream));
     HIPCK(hipStreamSynchronize(s->stream));
+    if (blend && (rc = blend_fold(s))) return rc;
     return fill ? fill_fold(s) : SM_OK;
 }
 
@@ -201,7 +209,7 @@ int sm_download_depth(sm_ctx *s, int which, float *dst)
 int sm_render_image(sm_ctx *s, const float *view16, int w, int h, float fx, float fy, float cx, float cy, uint8_t *bgr_out,
                     uint8_t *sem_out)
 {
-    return render_image(s, view16, w, h, fx, fy, cx, cy, nullptr, bgr_out, sem_out, nullptr, "sm_render_image");
+    return render_image(s, view16, w, h, fx, fy, cx, cy, nullptr, nullptr, bgr_out, sem_out, nullptr, "sm_render_image");
 }
 
 int sm_render_image_ex(sm_ctx *s, const float *view16, int w, int h, float fx, float fy, float cx, float cy, const sm_fill_params *fill,
@@ -211,7 +219,7 @@ int sm_render_image_ex(sm_ctx *s, const float *view16, int w, int h, float fx, f
     if (!s) { g_err = std::string(who) + ": null context"; return SM_E_ARG; }
     if (int rc = check_whole_map(s, who)) return rc;
     if (int rc = check_fill_params(fill, who)) return rc;
-    return render_image(s, view16, w, h, fx, fy, cx, cy, fill, bgr_out, sem_out, depth_mm_out, who);
+    return render_image(s, view16, w, h, fx, fy, cx, cy, nullptr, fill, bgr_out, sem_out, depth_mm_out, who);
 }
 
 void *sm_device_alloc(sm_ctx *s, size_t bytes)

@@ -1,4 +1,4 @@
-// sm_render_maps.hip -- views of a map set (sm_render_image_maps and its _ex form, sm_render_model_maps; DESIGN.md "4f. Views of a map set"): map files streamed through the two
+// sm_render_maps.hip -- views of a map set (sm_render_image_maps, its _ex form and the views behind its _blend form, sm_render_model_maps; DESIGN.md "4f. Views of a map set"): map files streamed through the two
 // renderers in chunks, the live model last; for every source that streams map files, the context's MapStaging: its allocation and intake kernel.  Kernels: sm_k_render_maps.h.
 #include "sm_map_stream.h"
 #include "sm_k_render_maps.h"
@@ -20,6 +20,9 @@ struct Mode {
     // image only (sm_render_image_maps_ex): the completion of every batch's planes (null: none), the depth plane (null: not wanted)
     const sm_fill_params *fill;
     uint16_t *out_depth;
+    // image only (sm_render_image_maps_blend): the colours of the visible layer blended (null: the nearest surfel's), which takes a
+    // second pass over the files per batch
+    const sm_blend_params *blend;
 };
 
 int render_maps(sm_ctx *s, const sm_map_source *src, const char *fn, const Mode &md)
@@ -42,11 +45,13 @@ int render_maps(sm_ctx *s, const sm_map_source *src, const char *fn, const Mode 
 
     const size_t npix = (size_t)md.w * md.h;
     int cull;
-    // the key budget bounds what a view of the batch holds beside its keys too: the depth plane and the completion's pyramid
+    // the key budget bounds what a view of the batch holds beside its keys too: the depth plane, the completion's pyramid and the
+    // blend's four 64-bit sums per pixel
     const bool depth16 = md.fill || md.out_depth;
-    const size_t extra = (depth16 ? npix * 2 : 0) + (md.fill ? fill_scratch_bytes(*md.fill, md.w, md.h, 1) : 0);
+    const size_t extra = (depth16 ? npix * 2 : 0) + (md.fill ? fill_scratch_bytes(*md.fill, md.w, md.h, 1) : 0) + (md.blend ? npix * 32 : 0);
     const uint32_t B = maps_batch(md.n_views, npix + (extra + 7) / 8, "SM_RENDER_MAPS_KEY_MB", "SM_RENDER_MAPS_NO_CULL", &cull);
     if (md.fill) fill_begin(s);
+    if (md.blend) blend_begin(s);
     const unsigned pblocks = (unsigned)((npix + 255) / 256);
 
     // per-view parameters | shading | skipped counters | hit flags
@@ -102,15 +107,27 @@ int render_maps(sm_ctx *s, const sm_map_source *src, const char *fn, const Mode 
         };
         fill_keys(s, d_key, bp);
 
-        // ---- the files, chunk by chunk: the host reads chunk c + 1 while the copy and the kernels of chunk c run
-        for (in.begin(set.jobs); in.more();) {
-            MapStream::Chunk ck;
-            if ((rc = in.next(ck))) return rc;
-            const uint32_t n = ck.job->n;
-            const unsigned nblk = (n + MAPS_BLOCK - 1) / MAPS_BLOCK;
-            maps_intake(s, ck.d_rec, n);
+        // ---- one pass over the files, chunk by chunk: the host reads chunk c + 1 while the copy and the kernels of chunk c run;
+        // launch(chunk's id base, records, blocks) enqueues what the pass does with the chunk in the staging's planes
+        auto pass = [&](auto &&launch) -> int {
+            for (in.begin(set.jobs); in.more();) {
+                MapStream::Chunk ck;
+                if (int e = in.next(ck)) return e;
+                const uint32_t n = ck.job->n;
+                const unsigned nblk = (n + MAPS_BLOCK - 1) / MAPS_BLOCK;
+                maps_intake(s, ck.d_rec, n);
+                if (int e = launch((uint32_t)(set.id_base[ck.job->file] + ck.job->first), n, nblk)) return e;
+                if (int e = in.done(ck.q)) return e;
+                HIPCK(hipGetLastError());
+                rm.stats.surfels_read += n;
+                rm.stats.chunks++;
+                if (cull) rm.stats.pairs_tested += (uint64_t)nblk * b;
+            }
+            if (int e = in.fold(0)) return e;
+            return in.fold(1);
+        };
+        rc = pass([&](uint32_t gid, uint32_t n, unsigned nblk) -> int {
             HIPCK(hipMemsetAsync(d_hit + v0, 0, b, s->stream));
-            const uint32_t gid = (uint32_t)(set.id_base[ck.job->file] + ck.job->first);
             if (md.image)
                 hipLaunchKernelGGL(k_maps_splat_image, dim3(nblk, b), dim3(256), 0, s->stream, chunk, n, gid, (const float4 *)st.d_box.get(), d_rp,
                                    d_key, npix, cull, d_skip + v0, d_hit + v0);
@@ -118,13 +135,9 @@ int render_maps(sm_ctx *s, const sm_map_source *src, const char *fn, const Mode 
                 hipLaunchKernelGGL(k_maps_splat_view, dim3(nblk, b), dim3(256), 0, s->stream, chunk, n, gid, (const float4 *)st.d_box.get(), d_vp,
                                    d_key, npix, cull, d_skip + v0, d_hit + v0);
             resolve(chunk, gid, n);
-            if ((rc = in.done(ck.q))) return rc;
-            HIPCK(hipGetLastError());
-            rm.stats.surfels_read += n;
-            rm.stats.chunks++;
-            if (cull) rm.stats.pairs_tested += (uint64_t)nblk * b;
-        }
-        if ((rc = in.fold(0)) || (rc = in.fold(1))) return rc;
+            return SM_OK;
+        });
+        if (rc) return rc;
 
         // ---- the live model, by the resident kernels with an id base
         if (cnt) {
@@ -148,6 +161,20 @@ int render_maps(sm_ctx *s, const sm_map_source *src, const char *fn, const Mode 
         if (md.image) hipLaunchKernelGGL(k_maps_finish_image, dim3((unsigned)((bp + 255) / 256)), dim3(256), 0, s->stream, d_key, bp, d_bgr, d_sem);
         else hipLaunchKernelGGL(k_maps_finish_view, dim3(pblocks, b), dim3(256), 0, s->stream, d_vs, d_key, npix, d_rgba, d_depth, d_id);
         HIPCK(hipGetLastError());
+
+        // ---- blended: the key map is whole, so every source is walked again, now adding the visible layer's fragments
+        if (md.blend) {
+            if ((rc = blend_clear(s, bp))) return rc;
+            const float ms0 = rm.stats.device_ms;
+            if ((rc = pass([&](uint32_t, uint32_t n, unsigned) -> int { blend_accum_chunk(s, *md.blend, n, d_rp, d_key, npix, b, cull); return SM_OK; })))
+                return rc;
+            blend_add_ms(s, rm.stats.device_ms - ms0);
+            if ((rc = blend_mark(s))) return rc;
+            if (cnt)
+                for (uint32_t i = 0; i < b; ++i)
+                    blend_accum_model(s, *md.blend, ((const RenderParams *)md.params)[v0 + i], d_key + (size_t)i * npix, (size_t)i * npix);
+            if ((rc = blend_normalise(s, d_key, npix, b, d_bgr, d_sem))) return rc;
+        }
         if (depth16) fill_key_depth(s, d_key, bp, d_depth16);
         if (md.fill && (rc = fill_enqueue(s, *md.fill, md.w, md.h, b, d_bgr, d_sem, d_depth16))) return rc;
         const size_t vp0 = (size_t)v0 * npix;
@@ -161,6 +188,7 @@ int render_maps(sm_ctx *s, const sm_map_source *src, const char *fn, const Mode 
             if (md.out2) HIPCK(hipMemcpyAsync(md.out2 + vp0 * 4, d_id, bp * 4, hipMemcpyDeviceToHost, s->stream));
         }
         HIPCK(hipStreamSynchronize(s->stream));
+        if (md.blend && (rc = blend_fold(s))) return rc;
         if (md.fill && (rc = fill_fold(s))) return rc;
     }
     std::vector<uint32_t> skipped(V);
@@ -197,12 +225,10 @@ void sm_impl::maps_intake(sm_ctx *s, const float4 *d_rec, uint32_t n)
     hipLaunchKernelGGL(k_maps_intake, dim3((n + MAPS_BLOCK - 1) / MAPS_BLOCK), dim3(256), 0, s->stream, d_rec, n, planes(s->staging), s->staging.d_box.get());
 }
 
-extern "C" {
-
-// sm_render_image_maps (fn) and, with fill or depth_mm_out, what sm_render_image_maps_ex adds to it
-static int render_image_maps(sm_ctx *s, const sm_map_source *src, const float *views16, uint32_t n_views, int w, int h, float fx, float fy,
-                             float cx, float cy, const sm_fill_params *fill, uint8_t *bgr_out, uint8_t *sem_out, uint16_t *depth_mm_out,
-                             const char *fn)
+// sm_render_image_maps (fn) and, with fill or depth_mm_out, what sm_render_image_maps_ex adds to it; with blend, sm_render_image_maps_blend
+int sm_impl::render_image_maps(sm_ctx *s, const sm_map_source *src, const float *views16, uint32_t n_views, int w, int h, float fx, float fy,
+                               float cx, float cy, const sm_blend_params *blend, const sm_fill_params *fill, uint8_t *bgr_out,
+                               uint8_t *sem_out, uint16_t *depth_mm_out, const char *fn)
 {
     if (!s || !src) { g_err = std::string(fn) + ": null context or source"; return SM_E_ARG; }
     if (n_views && (!views16 || !bgr_out || !sem_out)) { g_err = std::string(fn) + ": null views or outputs"; return SM_E_ARG; }
@@ -217,14 +243,16 @@ static int render_image_maps(sm_ctx *s, const sm_map_source *src, const float *v
     md.image = true; md.w = w; md.h = h; md.n_views = n_views;
     md.params = rps.data(); md.param_size = sizeof(RenderParams);
     md.out0 = bgr_out; md.out1 = sem_out;
-    md.fill = fill; md.out_depth = depth_mm_out;
+    md.fill = fill; md.out_depth = depth_mm_out; md.blend = blend;
     return render_maps(s, src, fn, md);
 }
+
+extern "C" {
 
 int sm_render_image_maps(sm_ctx *s, const sm_map_source *src, const float *views16, uint32_t n_views, int w, int h, float fx, float fy,
                          float cx, float cy, uint8_t *bgr_out, uint8_t *sem_out)
 {
-    return render_image_maps(s, src, views16, n_views, w, h, fx, fy, cx, cy, nullptr, bgr_out, sem_out, nullptr, "sm_render_image_maps");
+    return render_image_maps(s, src, views16, n_views, w, h, fx, fy, cx, cy, nullptr, nullptr, bgr_out, sem_out, nullptr, "sm_render_image_maps");
 }
 
 int sm_render_image_maps_ex(sm_ctx *s, const sm_map_source *src, const float *views16, uint32_t n_views, int w, int h, float fx, float fy,
@@ -234,7 +262,7 @@ int sm_render_image_maps_ex(sm_ctx *s, const sm_map_source *src, const float *vi
     if (s)
         if (int rc = check_whole_map(s, fn)) return rc;
     if (int rc = check_fill_params(fill, fn)) return rc;
-    return render_image_maps(s, src, views16, n_views, w, h, fx, fy, cx, cy, fill, bgr_out, sem_out, depth_mm_out, fn);
+    return render_image_maps(s, src, views16, n_views, w, h, fx, fy, cx, cy, nullptr, fill, bgr_out, sem_out, depth_mm_out, fn);
 }
 
 int sm_render_model_maps(sm_ctx *s, const sm_map_source *src, const sm_model_view *views, uint32_t n_views, uint8_t *rgba, float *depth,

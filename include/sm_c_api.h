@@ -1094,6 +1094,72 @@ int sm_render_image_maps_blend(sm_ctx *s, const sm_map_source *src, const float 
                                uint8_t *bgr_out, uint8_t *sem_out, uint16_t *depth_mm_out);
 int sm_blend_stats(sm_ctx *s, sm_blend_stats_t *out);
 
+/* ---- simplification (DESIGN.md "4p. Simplification") ----
+ * With the reference's defaults almost nothing fuses, and every frame stores the surface it sees again.  This pass makes a model
+ * or a map set smaller: the records that share a cell of a world grid, a class and (split_normals) a facing direction become one.
+ * It is specified in integers: the result is defined bit for bit and is a function of the multiset of (global id, record) pairs
+ * alone -- not of the order the device meets them in, of the chunking of a set, or of how the set is split into files.
+ *   A record is the map file's: x y z conf | colour word, standby, init_time, time | nx ny nz radius, the colour word
+ *   class << 24 | r << 16 | g << 8 | b.  A set is an sm_map_source with the global ids of the map-set calls: the files in list
+ *   order, each in file order, then the live model.
+ *   V = (voxel_mm * 65536 + 500) / 1000 (integer division): the cell edge in units of 2^-16 m.
+ *   Regular records.  x, y, z finite with |(double)p[k] - (double)origin[k]| < 2^24; conf finite and > 0; init_time and time
+ *     finite and >= 0; radius finite, 0 <= radius < 32768; the normal finite and not (0, 0, 0); the cell (below) within
+ *     [-65536, 65535] on every axis.  Every other record is loose.
+ *   Position.  X[k] = (int64)floor(((double)p[k] - (double)origin[k]) * 65536.0), cell[k] = floor_div(X[k], V),
+ *     off[k] = X[k] - cell[k] * V in [0, V).
+ *   Face.  split_normals: a = the axis of the largest |n[k]| (a tie goes to the lower axis), face = 2a + (n[a] < 0); else 0.
+ *   Key.  (cell x, cell y, cell z, face, class): 17 + 17 + 17 + 3 + 8 = 62 bits.
+ *   Contribution of a regular record to its key's cell, with t = conf * 16.0f (float32) and w = 255 if t >= 255, else
+ *     max(1, (int32)t):  n += 1;  SW += w;  SP[k] += w * off[k];  SN[k] += w * ni[k] with ni[k] = (int32)clamp(floorf(n[k] *
+ *     16384.0f + 0.5f), -2^22, 2^22) (a unit normal gives at most 2^14);  SC[c] += w * channel[c] for b, g, r;  lo[k] =
+ *     min(off[k]), hi[k] = max(off[k]);  Rmax = max(RI), RI = (int64)floor((double)radius * 65536.0);  conf_max, time_max,
+ *     init_time_min on the floats' bit patterns as unsigned words (for non-negative values they order like the values);
+ *     first = min(global id).  With 2^31 contributors SP stays below 2^59, SN below 2^61, SC below 2^47: 64-bit sums are exact.
+ *   Output.  One record per loose record, verbatim, and one per cell, in ascending order of the loose record's id / the cell's
+ *     `first`: the output is in set order of its representatives.  A cell with n == 1 gives its record verbatim, so a map whose
+ *     surfels are all alone in their cells comes back unchanged.  A cell with n >= 2 gives
+ *       pos[k] = (float)((double)origin[k] + (double)(cell[k] * V + (SP[k] + SW / 2) / SW) * 2^-16)   (floor division; fp64)
+ *       conf = conf_max;  colour word = class << 24 | the channels (SC[c] + SW / 2) / SW;  standby = 0;
+ *       init_time = init_time_min;  time = time_max;
+ *       normal: s = max(0, bit_length(max |SN[k]|) - 24), f[k] = (float)(SN[k] >> s) (arithmetic shift; exact), len =
+ *         sqrtf((f0 * f0 + f1 * f1) + f2 * f2), n[k] = f[k] / len -- single float32 operations, no contraction, correctly
+ *         rounded / and sqrt.  All three f zero: the normal of the record `first`.
+ *       radius = (float)((double)R * 2^-16), R = max(Rmax, (isqrt(ex * ex + ey * ey + ez * ez) + 1) / 2), e = hi - lo, isqrt the
+ *         integer square root: the merged disc reaches as far as any disc it replaces and spans the box of their centres.
+ *   Capacity.  More distinct cells than max_cells: SM_E_CAPACITY, nothing written, the model unchanged.
+ * sm_simplify replaces the live model by the simplification of sm_download_model_aos's rows (ids = rows), on the device.  Frames
+ *   in flight are waited for; the tick, the stored poses, the fern keyframes and the tracker's state stay; sm_get_counts reports
+ *   the new count.
+ * sm_simplify_maps writes ONE map file, the set's simplification, to out_path (through "<out_path>.simplify.tmp" and a rename; its
+ *   header's frame range spans the files').  The source files and the live model stay as they are; include_model = 1: the
+ *   model's records take part.  Every file is read twice.  The header and set checks and the limit of 2^31 - 1 records are those
+ *   of sm_render_image_maps.  SM_SIMPLIFY_NO_COMBINE=1 (read per call) switches off the in-wave combination of equal keys ahead
+ *   of the atomics: the result is the same.
+ * sm_simplify_stats: of the context's last call of either.
+ * Errors.  SM_E_ARG: NULLs, voxel_mm outside 10..10000, split_normals not 0 or 1, a non-finite origin, max_cells == 0, out_path
+ *   equal to a source path, a call between sm_stage_conflict and sm_stage_cull, the file checks, sm_simplify_stats before any
+ *   call.  SM_E_UNSUPPORTED: a sharded or rig context.  SM_E_CAPACITY as above. */
+typedef struct sm_simplify_params {
+    int32_t voxel_mm;        /* 10..10000                                                                      default 50 */
+    int32_t split_normals;   /* 0 / 1                                                                          default 1  */
+    float origin[3];         /* of the grid, metres                                                            default 0  */
+    uint32_t max_cells;      /* distinct cells the call may make                                               default 1 << 26 */
+} sm_simplify_params;
+typedef struct sm_simplify_stats_t {
+    uint64_t records_in, records_out;
+    uint64_t cells_merged;   /* cells with two or more contributors */
+    uint64_t loose;
+    uint32_t largest_cell;   /* contributors of the fullest cell */
+    uint32_t chunks;         /* pieces of at most 2^20 records, both passes together */
+    uint32_t launches;
+    float device_ms, read_ms, total_ms;
+} sm_simplify_stats_t;
+int sm_default_simplify_params(sm_simplify_params *p);       /* pure, no context */
+int sm_simplify(sm_ctx *s, const sm_simplify_params *p);
+int sm_simplify_maps(sm_ctx *s, const sm_map_source *src, const sm_simplify_params *p, const char *out_path);
+int sm_simplify_stats(sm_ctx *s, sm_simplify_stats_t *out);
+
 /* ---- per-pass entry points (GlobalModel / IndexMap methods), synchronous ---- */
 /* Upload RGB / metric depth / semantic textures directly (bypasses p0). */
 int sm_set_frame(sm_ctx *s, const uint8_t *rgb, const float *depth_metric,

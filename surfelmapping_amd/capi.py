@@ -47,6 +47,7 @@ SYMBOLS = (
     "sm_default_stereo_params", "sm_set_stereo", "sm_stereo_depth", "sm_stereo_depth_device", "sm_stereo_download",
     "sm_default_fill_params", "sm_fill_image", "sm_fill_image_device", "sm_render_image_ex", "sm_render_image_maps_ex", "sm_fill_stats",
     "sm_default_blend_params", "sm_render_image_blend", "sm_render_image_maps_blend", "sm_blend_stats",
+    "sm_default_simplify_params", "sm_simplify", "sm_simplify_maps", "sm_simplify_stats",
 )
 
 SM_COLL_SUM, SM_COLL_MIN, SM_COLL_GATHER = 0, 1, 2
@@ -454,6 +455,36 @@ def _blend_arg(blend):
     return blend if isinstance(blend, SmBlendParams) else blend_params(**blend)
 
 
+class SmSimplifyParams(C.Structure):
+    _fields_ = [("voxel_mm", C.c_int32), ("split_normals", C.c_int32), ("origin", C.c_float * 3), ("max_cells", C.c_uint32)]
+
+
+class SmSimplifyStats(C.Structure):
+    _fields_ = [("records_in", C.c_uint64), ("records_out", C.c_uint64), ("cells_merged", C.c_uint64), ("loose", C.c_uint64),
+                ("largest_cell", C.c_uint32), ("chunks", C.c_uint32), ("launches", C.c_uint32), ("device_ms", C.c_float),
+                ("read_ms", C.c_float), ("total_ms", C.c_float)]
+
+
+def default_simplify_params() -> SmSimplifyParams:
+    """sm_default_simplify_params: voxel_mm 50, split_normals 1, origin (0, 0, 0), max_cells 1 << 26"""
+    p = SmSimplifyParams()
+    load().sm_default_simplify_params(C.byref(p))
+    return p
+
+
+def simplify_params(**over) -> SmSimplifyParams:
+    """default_simplify_params() with fields overridden; origin takes a sequence of three"""
+    p = default_simplify_params()
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise KeyError(k)
+        if k == "origin":
+            p.origin[:] = [float(x) for x in v]
+        else:
+            setattr(p, k, v)
+    return p
+
+
 def search_params(**over) -> SmSearchParams:
     """sm_default_search_params (2 levels; +-2 m in x and z at 0.25 m, +-3 deg about y at 0.5 deg; refine 4, stride0 8, top_k 4,
     colour_thresh 0.1) with fields overridden; the four per-axis fields take a sequence of three"""
@@ -793,6 +824,11 @@ def load():
     L.sm_render_image_blend.argtypes = [vp, vp, C.c_int, C.c_int] + [C.c_float] * 4 + [blp, flp, vp, vp, vp]
     L.sm_render_image_maps_blend.argtypes = [vp, C.POINTER(SmMapSource), vp, C.c_uint32, C.c_int, C.c_int] + [C.c_float] * 4 + [blp, flp, vp, vp, vp]
     L.sm_blend_stats.argtypes = [vp, C.POINTER(SmBlendStats)]
+    smp = C.POINTER(SmSimplifyParams)
+    L.sm_default_simplify_params.argtypes = [smp]
+    L.sm_simplify.argtypes = [vp, smp]
+    L.sm_simplify_maps.argtypes = [vp, C.POINTER(SmMapSource), smp, C.c_char_p]
+    L.sm_simplify_stats.argtypes = [vp, C.POINTER(SmSimplifyStats)]
     for name in SYMBOLS:
         getattr(L, name)          # AttributeError here = the library does not match the header
     _lib = L
@@ -1685,6 +1721,30 @@ class SurfelMap:
         st = SmLidarStats()
         self._chk(self._L.sm_lidar_stats(self._h, C.byref(st)), "sm_lidar_stats")
         return {k: getattr(st, k) for k, _ in SmLidarStats._fields_}
+
+    # -- simplification (sm_simplify, sm_simplify_maps)
+    def simplify(self, **params) -> dict:
+        """The live model merged per voxel cell, in place (sm_simplify): records that share a cell of `voxel_mm`, a class and
+        (split_normals) a facing direction become one; download_model() then gives the rows tests/simplify_ref.py computes.
+        params: the fields of simplify_params().  Returns simplify_stats()."""
+        p = simplify_params(**params)
+        self._chk(self._L.sm_simplify(self._h, C.byref(p)), "sm_simplify")
+        return self.simplify_stats()
+
+    def simplify_maps(self, paths, out_path, include_model=False, **params) -> dict:
+        """The simplification of a map set -- the files `paths` in that order, then (include_model) the live model -- written
+        as ONE map file to out_path (sm_simplify_maps); sources and model stay as they are.  Returns simplify_stats()."""
+        p = simplify_params(**params)
+        src = map_source(paths, include_model)
+        self._chk(self._L.sm_simplify_maps(self._h, C.byref(src), C.byref(p), os.fsencode(out_path)), "sm_simplify_maps")
+        return self.simplify_stats()
+
+    def simplify_stats(self) -> dict:
+        """of the last simplify* call: records_in, records_out, cells_merged, loose, largest_cell, chunks, launches, device_ms,
+        read_ms, total_ms"""
+        st = SmSimplifyStats()
+        self._chk(self._L.sm_simplify_stats(self._h, C.byref(st)), "sm_simplify_stats")
+        return {k: getattr(st, k) for k, _ in SmSimplifyStats._fields_}
 
     # -- per-pass entry points
     def set_frame(self, rgb=None, depth_metric=None, sem=None):

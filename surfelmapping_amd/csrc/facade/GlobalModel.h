@@ -120,6 +120,24 @@ public:
         return (long)n;
     }
 
+    // Not in the reference: the surfels that share a cell of voxelMm millimetres of the world grid, a class and (splitNormals) a
+    // facing direction become one (sm_simplify; DESIGN.md "4p. Simplification"); what is alone in its cell stays as it is.
+    // Returns the surfels the model holds afterwards, or -1 with the error printed (the model is then unchanged).
+    long simplify(int voxelMm = 50, bool splitNormals = true)
+    {
+        sm_simplify_params p;
+        sm_default_simplify_params(&p);
+        p.voxel_mm = voxelMm;
+        p.split_normals = splitNormals ? 1 : 0;
+        sm_simplify_stats_t st;
+        (void)sm_sync(ctx_);                                             // (SM_FACADE_ASYNC: frames may still be in flight)
+        if (sm_simplify(ctx_, &p) != SM_OK || sm_simplify_stats(ctx_, &st) != SM_OK) {
+            std::printf("simplify: %s\n", sm_last_error());
+            return -1;
+        }
+        return (long)st.records_out;
+    }
+
     // model read-back in the reference's AoS layout (12 floats / surfel, src/Config.cpp:17-32)
     std::vector<float> downloadModel()
     {

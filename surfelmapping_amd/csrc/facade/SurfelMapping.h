@@ -255,6 +255,29 @@ public:
         if (falloff >= 0) blendParams_.falloff = falloff;
     }
 
+    // A drive's map made smaller (sm_simplify_maps; DESIGN.md "4p. Simplification"): the records of `mapFiles`, then (includeModel)
+    // of the live model, that share a cell of voxelMm millimetres, a class and (splitNormals) a facing direction become one, and the
+    // result is written as ONE map file to outPath, which may not be one of mapFiles.  The files and the model stay as they are.
+    // Returns the records written, or -1 with the error printed (then outPath has not been touched).
+    long simplifyMaps(const std::vector<std::string> &mapFiles, const std::string &outPath, int voxelMm = 50, bool splitNormals = true,
+                      bool includeModel = false)
+    {
+        std::vector<const char *> paths;
+        for (const std::string &f : mapFiles) paths.push_back(f.c_str());
+        const sm_map_source src{paths.data(), (uint32_t)paths.size(), includeModel ? 1 : 0};
+        sm_simplify_params p;
+        sm_default_simplify_params(&p);
+        p.voxel_mm = voxelMm;
+        p.split_normals = splitNormals ? 1 : 0;
+        sm_simplify_stats_t st;
+        (void)sm_sync(ctx_);                                             // (SM_FACADE_ASYNC: frames may still be in flight)
+        if (sm_simplify_maps(ctx_, &src, &p, outPath.c_str()) != SM_OK || sm_simplify_stats(ctx_, &st) != SM_OK) {
+            std::printf("simplifyMaps: %s\n", sm_last_error());
+            return -1;
+        }
+        return (long)st.records_out;
+    }
+
     // The second sensor's dump: what a lidar `sensor` (sm_lidar_sensor; sm_default_lidar_sensor) at each of `poses` (sensor->world,
     // the camera's axes) measures in the live model, written as <path>/velodyne/%06d.bin next to acquireImages' folders, in KITTI's
     // velodyne layout: per return four floats, (z, -x, -y) of t*d in the sensor frame -- x forward, y left, z up -- and the

@@ -18,9 +18,10 @@
 //   sm_stereo.hip    stereo depth (sm_stereo_*): census, matching costs, path costs, winner and depth of a rectified pair
 //   sm_fill.hip      hole filling (sm_fill_*, sm_render_image_ex's and sm_render_image_maps_ex's stage): depth of a view, push-pull completion
 //   sm_blend.hip     blended views (sm_render_image_blend, sm_render_image_maps_blend): the visible layer's accumulation and normalisation, a stage of both render paths
+//   sm_simplify.hip  simplification (sm_simplify, sm_simplify_maps): the model or a map set merged per voxel cell, two passes over the records
 // and, beside it, for everything that touches a map file: sm_mapfile.h (the format: checked open, writer, chunk plan; host only),
 // sm_map_set.h (a listed set of files: the file index, the two openings, a rewrite's per-file record and temporary; host only) and
-// sm_map_stream.h (the double-buffered chunk stream of sm_render_maps.hip, sm_lidar.hip, sm_recall.hip and sm_warp.hip).  The staging
+// sm_map_stream.h (the double-buffered chunk stream of sm_render_maps.hip, sm_lidar.hip, sm_recall.hip, sm_warp.hip and sm_simplify.hip).  The staging
 // those four stream through (MapStaging) and the file index (FileIndex) are the context's, no feature's.  For the occupied slots and the
 // compaction schedule: sm_slots.h (SlotSchedule; host only); for the arithmetic of rigid poses in double: sm_pose.h (host only,
 // included by sm_track.hip and sm_warp.hip).  What alternates between consecutive frames is FrameSet, below.
@@ -310,6 +311,21 @@ struct Blend {
     bool stats_valid = false;
 };
 
+// simplification (sm_simplify.hip, sm_k_simplify.h): the scratch of one chunk's second pass, the output buffers, the last call's
+// tally.  The table lives for one call.
+struct Simplify {
+    Dev<uint32_t> d_code;              // per record of a chunk: not a representative | loose | its cell's slot
+    Dev<uint32_t> d_blk_cnt, d_blk_base;   // representatives per block of 256 records, their rank in the output
+    Dev<uint32_t> d_tally;             // error word | distinct cells | running rank | loose | merged | largest
+    Dev<uint2> d_info;                 // [2]: (first rank, representatives) of the chunk in buffer c & 1
+    Host<uint2> h_info;                // pinned, [2]
+    Dev<float4> d_out[2];              // the finished records of a chunk (sm_simplify: [0] holds the whole output)
+    size_t out_cap[2] = {0, 0};        // records
+    Event ev[2];                       // around what runs outside a chunk stream
+    sm_simplify_stats_t stats{};
+    bool stats_valid = false;
+};
+
 // closing loops unasked (sm_loop.hip): the policy of sm_set_auto_loop and its tally
 struct AutoLoop {
     bool on = false;
@@ -547,6 +563,7 @@ struct sm_ctx {
     Stereo stereo;
     Fill fill;
     Blend blend;
+    Simplify simp;
     // host frame state (src/SurfelMapping.h:100-103)
     int tick = 0;
     bool ref_set = false;
@@ -590,6 +607,7 @@ int clean_points_device(sm_ctx *s, const uint16_t *d_depth_mm, const uint8_t *d_
 int ss_collective(sm_ctx *s, const void *send, void *recv, size_t count, int op);
 // ---- sm_model_io.hip ----
 void export_aos(sm_ctx *s, float *dst12, uint32_t first, uint32_t n);   // k_export_aos on the context's stream
+void import_aos(sm_ctx *s, const float *d_src12, uint32_t first, uint32_t n);   // k_import_aos on the context's stream: n device records into slots first..
 // the novel view's splat of the live model into `key` with ids id_base + slot (k_render_splat on the context's stream)
 void render_splat_model(sm_ctx *s, const RenderParams &rp, uint64_t *key, uint32_t id_base);
 // ---- sm_view.hip ----

@@ -12,6 +12,11 @@ void sm_impl::export_aos(sm_ctx *s, float *dst12, uint32_t first, uint32_t n)
     hipLaunchKernelGGL(k_export_aos, dim3((n + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, dst12, first, n);
 }
 
+void sm_impl::import_aos(sm_ctx *s, const float *d_src12, uint32_t first, uint32_t n)
+{
+    if (n) hipLaunchKernelGGL(k_import_aos, dim3((n + 255) / 256), dim3(256), 0, s->stream, s->M, s->d_state, d_src12, first, n);
+}
+
 void sm_impl::render_splat_model(sm_ctx *s, const RenderParams &rp, uint64_t *key, uint32_t id_base)
 {
     const uint32_t cnt = s->h_state->count;

@@ -266,22 +266,23 @@ def test_window_equalities(frames, old_map):     # noqa: F811
         assert (want >= 0).mean() > 0.05
         pred, sys = m.track_debug_window(depth, pe, lo, hi)
         assert np.array_equal(pred, want), f"window ({lo}, {hi}]: {int((pred != want).sum())} pixels differ"
-        want_sys = tr.system(vm, nm, want, model, pe, seq[9][3], cam)
-        assert sys[28] == want_sys[28] and sys[28] > 1000
-        np.testing.assert_allclose(sys, want_sys, rtol=0, atol=1e-5 * np.abs(want_sys).max())
+        terms = {1: tr.system_terms(vm, nm, want, model, pe, seq[9][3], cam)}
+        assert sys[28] == len(terms[1]) and sys[28] > 1000
+        tr.assert_system(sys, terms[1], f"window ({lo}, {hi}]")
         _, info = m.track_window(depth, lo, hi, guess=pe)
         assert info["anchor_time"] == float(times[want[want >= 0]].max()) <= min(hi, 9), info
         assert float(times[want[want >= 0]].min()) > lo
         # the colour form: the same prediction, and the level-0 systems of the restatement fed with it
         plane = trr.gather(want, model)
-        wants = {1: want_sys, 2: trr.photo_system(plane, depth, pyr0, pe, cam, level=0, stride=1)}
+        terms[2] = trr.photo_terms_products(plane, depth, pyr0, pe, cam, level=0, stride=1)
         for w in (1, 2):
             pr, got = m.track_rgb_debug_window(rgb, depth, pe, lo, hi, level=0, which=w)
             assert np.array_equal(pr, want)
-            print(f"window ({lo}, {hi}] which {w}: inliers {got[28]:.0f} (restatement {wants[w][28]:.0f}), "
-                  f"max |diff| / max |sys| {np.abs(got - wants[w])[:28].max() / np.abs(wants[w]).max():.3g}")
-            assert got[28] == wants[w][28] and got[28] > 1000
-            np.testing.assert_allclose(got, wants[w], rtol=0, atol=1e-5 * np.abs(wants[w]).max())
+            wsys = tr.sum_terms(terms[w])
+            print(f"window ({lo}, {hi}] which {w}: inliers {got[28]:.0f} (restatement {wsys[28]:.0f}), "
+                  f"max |diff| / max |sys| {np.abs(got - wsys)[:28].max() / np.abs(wsys).max():.3g}")
+            assert got[28] == len(terms[w]) and got[28] > 1000
+            tr.assert_system(got, terms[w], f"window ({lo}, {hi}] which {w}")
         _, rinfo = m.track_rgb_window(rgb, depth, lo, hi, guess=pe)
         assert rinfo["anchor_time"] == info["anchor_time"]
     g = poses[10].astype(f32)

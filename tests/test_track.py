@@ -83,9 +83,10 @@ def test_prediction_and_system_match_restatement(frames):
     assert (want >= 0).mean() > 0.3
     assert np.array_equal(pred, want), f"{int((pred != want).sum())} pixels differ"
     vm, nm = tr.vertex_normal(depth, cam)
-    want_sys = tr.system(vm, nm, want, model, pe, seq[9][3], cam)
+    terms = tr.system_terms(vm, nm, want, model, pe, seq[9][3], cam)
+    want_sys = tr.sum_terms(terms)
     assert sys[28] == want_sys[28] and sys[28] > 50000
-    np.testing.assert_allclose(sys, want_sys, rtol=0, atol=1e-5 * np.abs(want_sys).max())
+    tr.assert_system(sys, terms, "frame 10 against frames 0..9")
     # one Gauss-Newton step of the restatement moves towards the truth
     T1, _ = tr.solve(want_sys, pe)
     assert tr.pose_error(T1, poses[10])[0] < tr.pose_error(pe, poses[10])[0]

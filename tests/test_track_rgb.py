@@ -235,16 +235,16 @@ def test_rgb_systems_match_restatement(frames):
     for level in (0, 2):
         stride = 1 << level
         vm, nm = tr.vertex_normal(depth, cam, stride=stride)
-        want = {1: tr.system(vm, nm, pred, model, pe, seq[9][3], cam),
-                2: rr.photo_system(plane, depth, pyr[level], pe, cam, level=level, stride=stride)}
+        terms = {1: tr.system_terms(vm, nm, pred, model, pe, seq[9][3], cam),
+                 2: rr.photo_terms_products(plane, depth, pyr[level], pe, cam, level=level, stride=stride)}
+        want = {w: tr.sum_terms(terms[w]) for w in (1, 2)}
         got = {w: m.track_rgb_debug(rgb, depth, pe, level=level, which=w) for w in (0, 1, 2)}
         for w in (1, 2):
             print(f"level {level} which {w}: inliers {got[w][28]:.0f} (restatement {want[w][28]:.0f}), "
                   f"max |diff| / max |sys| {np.abs(got[w] - want[w])[:28].max() / np.abs(want[w]).max():.3g}")
             assert got[w][28] == want[w][28] and got[w][28] > 50000 / 4 ** level, (level, w, got[w][28], want[w][28])
-            np.testing.assert_allclose(got[w], want[w], rtol=0, atol=1e-5 * np.abs(want[w]).max())
-        j = rr.joint(got[1], got[2], 0.01)
-        np.testing.assert_allclose(got[0], j, rtol=0, atol=1e-5 * np.abs(j).max())
+            tr.assert_system(got[w], terms[w], f"level {level} which {w}")
+        tr.assert_system(got[0], terms[1], f"level {level} joint", rgb_terms=terms[2], weight=0.01)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -1,7 +1,10 @@
 """numpy restatement of the tracker (sm_track_frame, surfelmapping_amd/csrc/sm_k_track.h) -- the checker of tests/test_track.py.
 Every float32 step below is one IEEE float32 operation of the kernels, in their order (no contraction), so the prediction is
 equal slot for slot; the 29 sums are float32 terms added in float64 (in another order than the GPU's: equal to rounding).
-`solve` restates one Gauss-Newton step of k_track_solve in float64."""
+`solve` restates one Gauss-Newton step of k_track_solve in float64, `solve_ldlt` the same step by the device's route and `track`
+the whole of sm_track_frame.  `system_terms` are the float32 products a reduction sums; `exact_system`, `entry_bound` and
+`assert_system` pin a reduction's result to their exact sums within what any double-precision summation keeps (the checker of
+tests/test_track_pin.py and of every comparison of a system in the tracker tests)."""
 import math
 
 import numpy as np
@@ -158,8 +161,24 @@ def vertex_normal(depth_mm, cam, near=1.0, far=30.0, stereo_border=80.0, stride=
     return vmap.reshape(-1, 4), nmap.reshape(-1, 4)
 
 
-def system(vmap, nmap, pred, model, pose16, t_prev16, cam, dist=0.3, angle_deg=30.0):
-    """k_track_reduce + the fixed-order sum of k_track_solve at pose16: float64[29] (JtJ upper triangle row-major, Jtr, r^2, n)"""
+def products(J, r):
+    """the 28 float32 products one inlier adds to the system, in its layout: float32[n][28] = the 21 J[a]*J[b] (a <= b,
+    row-major), the 6 J[a]*r, r*r -- each one IEEE float32 multiplication, as the reductions form them before they widen"""
+    J, r = np.asarray(J, f32), np.asarray(r, f32)
+    out = np.zeros((len(r), NSYS - 1), f32)
+    e = 0
+    for a in range(6):
+        for b in range(a, 6):
+            out[:, e] = J[:, a] * J[:, b]
+            e += 1
+    for a in range(6):
+        out[:, 21 + a] = J[:, a] * r
+    out[:, 27] = r * r
+    return out
+
+
+def system_rows(vmap, nmap, pred, model, pose16, t_prev16, cam, dist=0.3, angle_deg=30.0):
+    """track_pair at pose16 over the vertex stage's grid: (J float32[n][6], r float32[n]) of the inliers, in grid order"""
     W = cam["width"]
     m = colmajor(pose16)
     tinv = rigid_inv_d(colmajor(t_prev16)).astype(f32)
@@ -182,18 +201,92 @@ def system(vmap, nmap, pred, model, pose16, t_prev16, cam, dist=0.3, angle_deg=3
         ok &= _dot(nw, nm) >= cosa
         r = _dot(nm, d)
         wn = _cross(w, nm)
-    Jc = [nm[0], nm[1], nm[2], wn[0], wn[1], wn[2]]
+    J = np.stack([nm[0], nm[1], nm[2], wn[0], wn[1], wn[2]], axis=1).astype(f32)
+    return J[ok], r[ok].astype(f32)
+
+
+def system_terms(vmap, nmap, pred, model, pose16, t_prev16, cam, dist=0.3, angle_deg=30.0):
+    """the products k_track_reduce sums at pose16: float32[inliers][28] (products)"""
+    return products(*system_rows(vmap, nmap, pred, model, pose16, t_prev16, cam, dist=dist, angle_deg=angle_deg))
+
+
+def sum_terms(terms):
+    """the terms added in float64 (numpy's order, not the GPU's: equal to rounding): float64[29], value 28 the count"""
     out = np.zeros(NSYS)
-    e = 0
-    for a in range(6):
-        for b in range(a, 6):
-            out[e] = (Jc[a][ok] * Jc[b][ok]).astype(np.float64).sum()
-            e += 1
-    for a in range(6):
-        out[21 + a] = (Jc[a][ok] * r[ok]).astype(np.float64).sum()
-    out[27] = (r[ok] * r[ok]).astype(np.float64).sum()
-    out[28] = float(ok.sum())
+    out[:28] = np.asarray(terms, f32).astype(np.float64).sum(axis=0)
+    out[28] = float(len(terms))
     return out
+
+
+def system(vmap, nmap, pred, model, pose16, t_prev16, cam, dist=0.3, angle_deg=30.0):
+    """k_track_reduce + the fixed-order sum of k_track_solve at pose16: float64[29] (JtJ upper triangle row-major, Jtr, r^2, n)"""
+    return sum_terms(system_terms(vmap, nmap, pred, model, pose16, t_prev16, cam, dist=dist, angle_deg=angle_deg))
+
+
+# ---- the exact sums and the bound every double-precision summation of them keeps ----
+U = 2.0 ** -53                # the unit roundoff of a double
+OLD_TOL = 1e-5                # what the tests accepted before the per-entry bound: OLD_TOL * max |sys| over all 29, for every entry
+
+
+def exact_system(terms):
+    """float64[29]: each of the 28 sums of the float32 terms computed exactly and rounded once (math.fsum of the widened column);
+    value 28 the count"""
+    t = np.asarray(terms, f32).astype(np.float64)
+    out = np.zeros(NSYS)
+    for e in range(NSYS - 1):
+        out[e] = math.fsum(t[:, e].tolist())
+    out[28] = float(len(t))
+    return out
+
+
+def abs_sums(terms):
+    """float64[28]: sum of |term| per entry"""
+    return np.abs(np.asarray(terms, f32).astype(np.float64)).sum(axis=0)
+
+
+def entry_bound(terms, rgb_terms=None, weight=0.0):
+    """float64[28]: n * 2^-53 * sum |term_e|, n the number of terms -- what any double-precision summation of n exactly
+    representable terms stays within, whatever its order ((n - 1) u sum|t| for the additions; the last u sum|t| covers the one
+    rounding of exact_system and the second-order terms).  With rgb_terms: the bound of the joint system icp + weight * rgb,
+    bound_icp + weight * bound_rgb + 2 * 2^-53 * (|icp_e| + weight * |rgb_e|) (the product's and the sum's rounding)."""
+    b = len(terms) * U * abs_sums(terms)
+    if rgb_terms is None:
+        return b
+    lam = float(f32(weight))
+    si, sr = np.abs(exact_system(terms)[:28]), np.abs(exact_system(rgb_terms)[:28])
+    return b + lam * (len(rgb_terms) * U * abs_sums(rgb_terms)) + 2.0 * U * (si + lam * sr)
+
+
+def exact_joint(terms, rgb_terms, weight):
+    """float64[29]: exact icp + float(float32(weight)) * exact rgb, formed in rational arithmetic and rounded once; value 28 the
+    geometric count"""
+    from fractions import Fraction
+    lam = Fraction(float(f32(weight)))
+    si, sr = exact_system(terms), exact_system(rgb_terms)
+    out = np.array([float(Fraction(float(si[e])) + lam * Fraction(float(sr[e]))) for e in range(NSYS)])
+    out[28] = si[28]
+    return out
+
+
+def assert_system(got, terms, what, rgb_terms=None, weight=0.0):
+    """`got` (float64[29], a reduction's result) is a double-precision sum of `terms`: the count is equal and every entry lies
+    within entry_bound of the exact sum.  With rgb_terms: got is the joint system icp + weight * rgb (the count the geometric one)."""
+    got = np.asarray(got, np.float64)
+    n = len(terms)
+    assert got[28] == n, f"{what}: {got[28]:.0f} inliers, the restatement has {n}"
+    if rgb_terms is None:
+        exact, sabs = exact_system(terms), abs_sums(terms)
+    else:
+        exact, sabs = exact_joint(terms, rgb_terms, weight), abs_sums(terms) + float(f32(weight)) * abs_sums(rgb_terms)
+    bound = entry_bound(terms, rgb_terms, weight)
+    bad = [e for e in range(NSYS - 1) if not abs(got[e] - exact[e]) <= bound[e]]
+    for e in bad:
+        print(f"{what}: entry {e}: got {got[e]!r} exact {exact[e]!r} |diff| {abs(got[e] - exact[e]):.3e} bound {bound[e]:.3e} "
+              f"sum|term| {sabs[e]:.6e}")
+    assert not bad, f"{what}: entries {bad} of the system are outside the summation bound (n = {n})"
+    # (the tolerance this check replaced was OLD_TOL * max |sys| for every entry: it is never the tighter one)
+    assert (bound <= OLD_TOL * np.abs(exact).max()).all(), f"{what}: a summation bound above the former tolerance"
+    return exact, bound
 
 
 def _ldlt(A):
@@ -250,6 +343,67 @@ def solve(sys29, T):
     A, b = unpack(sys29)
     xi = np.linalg.solve(A, -b)
     return se3_exp(xi) @ np.asarray(T, np.float64), xi
+
+
+def solve_ldlt(sys29, T):
+    """track_step: the step of `solve` through the device's LDLT without pivoting and its two substitutions; (T', xi), or
+    (None, None) where a pivot is not positive"""
+    A, b = unpack(sys29)
+    L, d = _ldlt(A)
+    if L is None:
+        return None, None
+    y, xi = np.zeros(6), np.zeros(6)
+    for i in range(6):
+        y[i] = -b[i] - sum(L[i, k] * y[k] for k in range(i))
+    for i in range(5, -1, -1):
+        xi[i] = y[i] / d[i] - sum(L[k, i] * xi[k] for k in range(i + 1, 6))
+    return se3_exp(xi) @ np.asarray(T, np.float64), xi
+
+
+def start_pose(guess):
+    """what the iterations start from: the float32 guess (4x4) widened, its rotation orthonormalised in double; 4x4 float64"""
+    return orthonormalize_d(colmajor(guess).astype(np.float64)).reshape(4, 4).T.copy()
+
+
+def track(depth_mm, model, t_prev16, guess, cam, max_iters=15, min_inliers=1000, pixel_stride=1, dist=0.3, angle_deg=30.0,
+          bound=1e-4, stereo_border=80.0, live=None):
+    """sm_track_frame (with `live`: its windowed forms) from `guess` (4x4) against `model` (AoS, row = slot) predicted at
+    t_prev16: (pose 4x4 float64 -- the guess unless status is OK --, info) with info = status, iterations, inliers, rmse,
+    pivot_ratio, terms (the last system's products), poses (the float64 estimate after every step) and steps (every xi)"""
+    pred = predict(model, t_prev16, cam, live=live)
+    vm, nm = vertex_normal(depth_mm, cam, stereo_border=stereo_border, stride=pixel_stride)
+    centre = np.asarray(t_prev16, np.float64).reshape(-1)[12:15]
+    g = np.asarray(guess, f32).astype(np.float64)
+    T = start_pose(guess)
+    info = dict(status="OK", iterations=0, inliers=0, rmse=0.0, pivot_ratio=0.0, terms=None, poses=[], steps=[])
+    if not (pred >= 0).any():
+        info["status"] = "NO_MODEL"
+        return g, info
+    for _ in range(max_iters):
+        terms = system_terms(vm, nm, pred, model, T.astype(f32), t_prev16, cam, dist=dist, angle_deg=angle_deg)
+        sys = exact_system(terms)
+        n = len(terms)
+        info["iterations"] += 1
+        info.update(inliers=n, terms=terms, rmse=math.sqrt(sys[27] / n) if n else 0.0)
+        if n < min_inliers or n < 6:
+            info["status"] = "LOST"
+            return g, info
+        info["pivot_ratio"] = pivot_ratio(sys, centre)
+        degenerate = not info["pivot_ratio"] >= bound
+        T1, xi = solve_ldlt(sys, T)
+        if T1 is None:
+            info["status"] = "DEGENERATE"
+            return g, info
+        T = T1
+        info["poses"].append(T.copy())
+        info["steps"].append(xi)
+        converged = np.linalg.norm(xi[3:]) < 1e-6 and np.linalg.norm(xi[:3]) < 1e-6
+        if (converged or info["iterations"] >= max_iters) and degenerate:
+            info["status"] = "DEGENERATE"
+            return g, info
+        if converged:
+            break
+    return T, info
 
 
 def pose_error(a, b):

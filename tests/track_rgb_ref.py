@@ -103,21 +103,15 @@ def photo_terms(plane, depth_mm, img, pose16, cam, level=0, stride=1, dist=0.3, 
     return J, r.astype(f32), ok
 
 
+def photo_terms_products(plane, depth_mm, img, pose16, cam, **kw):
+    """the products k_track_rgb_photo sums: float32[inliers][28] (tr.products of the kept samples, in grid order)"""
+    J, r, ok = photo_terms(plane, depth_mm, img, pose16, cam, **kw)
+    return tr.products(J[ok], r[ok])
+
+
 def photo_system(plane, depth_mm, img, pose16, cam, **kw):
     """k_track_rgb_photo + its fixed-order sum: float64[29], unweighted"""
-    J, r, ok = photo_terms(plane, depth_mm, img, pose16, cam, **kw)
-    J, r = J[ok], r[ok]
-    out = np.zeros(tr.NSYS)
-    e = 0
-    for a in range(6):
-        for b in range(a, 6):
-            out[e] = (J[:, a] * J[:, b]).astype(np.float64).sum()
-            e += 1
-    for a in range(6):
-        out[21 + a] = (J[:, a] * r).astype(np.float64).sum()
-    out[27] = (r * r).astype(np.float64).sum()
-    out[28] = float(ok.sum())
-    return out
+    return tr.sum_terms(photo_terms_products(plane, depth_mm, img, pose16, cam, **kw))
 
 
 def joint(sys_icp, sys_rgb, weight):
@@ -131,32 +125,39 @@ def track(rgb, depth_mm, model, t_prev16, guess, cam, levels=3, iters=DEFAULT_IT
           dist=0.3, angle_deg=30.0, pixel_stride=1, min_inliers=1000, bound=1e-4, stereo_border=80.0):
     """sm_track_frame_rgb from `guess` (4x4) against `model` (AoS, row = slot) predicted at t_prev16: returns (pose 4x4 float64,
     info) with info = status, iterations, level_iterations, pivot_ratio (joint, last system), pivot_ratio_icp (geometric term
-    of that system alone), inliers, rgb_inliers"""
+    of that system alone), inliers, rgb_inliers; and of the last system built: terms_icp, terms_rgb (its products), level, sys"""
     pred = tr.predict(model, t_prev16, cam)
     plane = gather(pred, model)
     pyr = pyramid(rgb, levels)
     centre = np.asarray(t_prev16, np.float64).reshape(-1)[12:15]
-    T = np.asarray(guess, np.float64).copy()
+    T = tr.start_pose(guess)
     info = dict(status="OK", iterations=0, level_iterations=[0] * MAX_LEVELS, pivot_ratio=0.0, pivot_ratio_icp=0.0, inliers=0,
-                rgb_inliers=0)
+                rgb_inliers=0, terms_icp=None, terms_rgb=None, level=levels - 1, sys=None)
     for level in range(levels - 1, -1, -1):
         stride = pixel_stride << level
         vm, nm = tr.vertex_normal(depth_mm, cam, stereo_border=stereo_border, stride=stride)
         for _ in range(iters[level]):
             pose = T.astype(f32)
-            si = tr.system(vm, nm, pred, model, pose, t_prev16, cam, dist=dist, angle_deg=angle_deg)
-            sr = photo_system(plane, depth_mm, pyr[level], pose, cam, level=level, stride=stride, dist=dist,
-                              max_residual=rgb_max_residual, stereo_border=stereo_border)
-            sys = joint(si, sr, rgb_weight)
+            ti = tr.system_terms(vm, nm, pred, model, pose, t_prev16, cam, dist=dist, angle_deg=angle_deg)
+            tp = photo_terms_products(plane, depth_mm, pyr[level], pose, cam, level=level, stride=stride, dist=dist,
+                                      max_residual=rgb_max_residual, stereo_border=stereo_border)
+            si, sr = tr.sum_terms(ti), tr.sum_terms(tp)
+            # (rgb_weight 0: the geometric system itself, no product of the colour term's sums)
+            sys = joint(si, sr, rgb_weight) if float(f32(rgb_weight)) != 0.0 else si.copy()
             info["iterations"] += 1
             info["level_iterations"][level] += 1
             info["inliers"], info["rgb_inliers"] = int(si[28]), int(sr[28])
+            info["terms_icp"], info["terms_rgb"], info["level"], info["sys"] = ti, tp, level, sys
             if si[28] * 4 ** level < min_inliers or si[28] < 6:
                 info["status"] = "LOST"
                 return np.asarray(guess, np.float64), info
             info["pivot_ratio"] = tr.pivot_ratio(sys, centre)
             info["pivot_ratio_icp"] = tr.pivot_ratio(si, centre)
-            T, xi = tr.solve(sys, T)
+            T1, xi = tr.solve_ldlt(sys, T)
+            if T1 is None:
+                info["status"] = "DEGENERATE"
+                return np.asarray(guess, np.float64), info
+            T = T1
             if np.linalg.norm(xi[3:]) < 1e-6 and np.linalg.norm(xi[:3]) < 1e-6:
                 break
     if not info["pivot_ratio"] >= bound:

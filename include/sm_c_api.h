@@ -1160,6 +1160,107 @@ int sm_simplify(sm_ctx *s, const sm_simplify_params *p);
 int sm_simplify_maps(sm_ctx *s, const sm_map_source *src, const sm_simplify_params *p, const char *out_path);
 int sm_simplify_stats(sm_ctx *s, sm_simplify_stats_t *out);
 
+/* ---- registration of one map set against another (DESIGN.md "4q. Registration") ----
+ * Two drives of one street, a drive resumed after a restart, yesterday's map and today's: each set has its own world frame.
+ * sm_register_maps measures the rigid transform T (column-major float[16]) that takes the SOURCE set's world to the TARGET set's:
+ * point-to-plane ICP of a sample of the source records against one representative per occupied cell of a voxel grid over the
+ * target, coarse to fine.  A set is an sm_map_source as in the simplification (files in list order, each in file order, then the
+ * live model; global ids in that order); either may include the live model.  Nothing is modified: files, model, tick, stored
+ * poses, fern keyframes and tracker state stay; frames in flight are waited for.  Whatever is decided is decided in integers or
+ * in single, stated fp64 / fp32 operations (no contraction), so that tests/register_ref.py restates it value for value.
+ *   Levels.  Level l = 0 .. levels - 1 has the cell edge V_l = ((voxel_mm << l) * 65536 + 500) / 1000 in units of 2^-16 m
+ *     (the simplification's V of voxel_mm << l).  Iterations run on level levels - 1 first and on level 0 last.
+ *   1. Target table of a level.  The simplification's regular-record test, X, cell, off, face (always split), weight w and
+ *     normal integers ni, all with V_l and `origin`; the key is its key with the class taken as 0.  Per key the exact sums SW,
+ *     SP[3], SN[3].  A key's representative c has the simplification's merged position, pos[k] = (float)((double)origin[k] +
+ *     (double)(cell[k] * V_l + (SP[k] + SW / 2) / SW) * 2^-16), and its merged normal n_c (f[k] = (float)(SN[k] >> s), n_c = f /
+ *     sqrtf((f0 * f0 + f1 * f1) + f2 * f2)) -- for a key with one record as well.  All three f zero: n_c = (0, 0, 0), which no
+ *     sample pairs with (angle_thresh < 90).  The table is a function of the multiset of target records alone: not of their
+ *     order, the chunking or the split into files.  More than max_cells keys at a level: SM_E_CAPACITY.  One pass over the
+ *     target set fills all levels.
+ *   2. Samples.  stride = the parameter, or if that is 0 max(1, ceil(records of the source set / max_samples)), known from the
+ *     headers before anything is streamed.  The source records with global id % stride == 0 are the samples, sample i the record
+ *     i * stride; there are ceil(records / stride) of them (more than 2^28: SM_E_CAPACITY; a stride that leaves more than
+ *     max_samples: SM_E_ARG).  A sample is regular if its record passes the simplification's tests of its fields (everything
+ *     but the cell range, which is applied to the moved point below); the others never pair.  The source set is read once.
+ *   3. Pair of a regular sample (p, n) at the pose T (fp64, column-major) and level l.  With p and n widened to double:
+ *     q[r] = ((T[r] * p0 + T[4 + r] * p1) + T[8 + r] * p2) + T[12 + r],  nq[r] = (T[r] * n0 + T[4 + r] * n1) + T[8 + r] * n2.
+ *     d[k] = q[k] - (double)origin[k]; no pair unless |d[k]| < 2^24 on every axis.  X, cell, off of q as in the simplification
+ *     with V_l; no pair unless every cell[k] is in [-65536, 65535].  face = the simplification's face of nq (compared in
+ *     double).  Candidates: the 2 x 2 x 2 cells made per axis of cell[k] and its neighbour towards q -- cell[k] + 1 if
+ *     2 * off[k] >= V_l, else cell[k] - 1; a neighbour outside the cell range is no candidate -- with that face and class 0,
+ *     those of them that the table holds.  With e[k] = q[k] - (double)pos[k] and d2 = (e0 * e0 + e1 * e1) + e2 * e2 the
+ *     candidate with the smallest d2 is kept, of equal ones that of the lower key.  The pair counts iff sqrt(d2) <= reach_l =
+ *     (double)reach_cells * ((double)V_l * 2^-16) and (nq0 * n_c0 + nq1 * n_c1) + nq2 * n_c2 >= cos((double)angle_thresh * (pi /
+ *     180)).  Then, in double rounded to float32 once: r = (n_c0 * e0 + n_c1 * e1) + n_c2 * e2 and, with u[k] = q[k] -
+ *     (double)pivot[k], the row J = [n_c, u x n_c] (u x n = (u1 * n2 - u2 * n1, u2 * n0 - u0 * n2, u0 * n1 - u1 * n0)).  The 28
+ *     products J[a] * J[b] (a <= b), J[a] * r, r * r are single float32 multiplications and are added in fp64, in an order
+ *     that depends on the number of samples alone: the system is sm_track_debug's 29 values, value 28 the count.
+ *   4. Step.  The trackers' solve (LDLT without pivoting, two substitutions, exp of the twist xi = (rho, phi)), the twist taken
+ *     about `pivot`: T <- Tr(pivot) * exp(xi) * Tr(-pivot) * T, that is with exp(xi) = [R | t]: t' [r] = (t[r] + pivot[r]) -
+ *     ((R[r][0] * pivot0 + R[r][1] * pivot1) + R[r][2] * pivot2), T's columns rotated by R ((R[r][0] * T[c * 4] + R[r][1] *
+ *     T[c * 4 + 1]) + R[r][2] * T[c * 4 + 2]) and t' added to the last.  A far pivot makes the rotation and the translation of a
+ *     step nearly the same motion of the overlap: pass a point inside it.  The start is guess16 (NULL: the identity) widened,
+ *     its rotation made orthonormal as the trackers make their guess.  A level ends when |rho| < 1e-6 and |phi| < 1e-6 or after
+ *     max_iters iterations; the next finer level starts from its result.
+ *   5. info->status.  SM_REGISTER_OK; _LOST: a system had fewer than min_inliers (or than 6) pairs; _DEGENERATE: a system was
+ *     not positive definite, or the trackers' pivot ratio of the last system of level 0, taken about `pivot`, is below
+ *     SM_TRACK_DEGENERATE_BOUND; _NO_TARGET: a level without a key (nothing is iterated); _NO_SOURCE: no regular sample.  On
+ *     anything but OK pose16_out is guess16 as given (the identity for NULL) and the call still returns SM_OK.
+ *   The iterations are enqueued whole -- levels * max_iters pairs of launches, those after the end returning at once -- and the
+ *   host waits once, after the last.
+ * sm_register_debug: the tables and samples as above, then ONE system at pose16_eval (widened, as given) and `level` into sys29;
+ *   *n_samples = the samples, regular or not.
+ * sm_register_stats: of the context's last sm_register_maps or sm_register_debug.
+ * Errors.  SM_E_ARG: NULLs (guess16 aside), a parameter outside the ranges below, a non-finite guess, origin or pivot, level
+ *   outside 0 .. levels - 1, the header and set checks of sm_render_image_maps for both sets (every header of both before any
+ *   work), a path that is in both sets, a call between sm_stage_conflict and sm_stage_cull, sm_register_stats before any call.
+ *   SM_E_UNSUPPORTED: a sharded or rig context.  SM_E_CAPACITY as above, and for a set of more than 2^31 - 1 records. */
+#define SM_REGISTER_OK 0
+#define SM_REGISTER_LOST 1
+#define SM_REGISTER_DEGENERATE 2
+#define SM_REGISTER_NO_TARGET 3
+#define SM_REGISTER_NO_SOURCE 4
+#define SM_REGISTER_MAX_LEVELS 4
+typedef struct sm_register_params {
+    int32_t voxel_mm;        /* cell edge of level 0, 10..10000                                                default 200 */
+    int32_t levels;          /* 1..4                                                                           default 3 */
+    int32_t max_iters;       /* per level, 1..SM_TRACK_MAX_ITERS                                               default 20 */
+    int32_t min_inliers;     /* >= 0                                                                           default 1000 */
+    float angle_thresh;      /* degrees, in (0, 90)                                                            default 30 */
+    float reach_cells;       /* a pair is kept up to reach_cells * the level's cell edge; finite, > 0          default 1.0 */
+    uint32_t stride;         /* 0 = from max_samples                                                           default 0 */
+    uint32_t max_samples;    /* 1..2^28                                                                        default 1 << 22 */
+    uint32_t max_cells;      /* keys a level may hold, >= 1                                                    default 1 << 24 */
+    float origin[3];         /* of the grids, metres                                                           default 0 */
+    float pivot[3];          /* the point the twist is taken about, in the target's world: inside the overlap  default 0 */
+} sm_register_params;
+typedef struct sm_register_info {
+    int32_t status;
+    int32_t iterations[SM_REGISTER_MAX_LEVELS];   /* by level (level levels - 1 ran first) */
+    uint32_t inliers;        /* of the last system summed */
+    float rmse;              /* of the last system */
+    float pivot_ratio;       /* of the last system that was judged */
+    uint32_t samples;        /* regular samples */
+    uint32_t stride;
+    uint32_t cells[SM_REGISTER_MAX_LEVELS];       /* keys per level */
+} sm_register_info;
+typedef struct sm_register_stats_t {
+    uint64_t source_records, target_records;
+    uint32_t chunks;         /* pieces of at most 2^20 records, both sets together */
+    uint32_t launches;
+    float read_ms;           /* host: reading the files */
+    float table_ms;          /* device: the tables' initialisation (two memsets per level), inserts, representatives and samples */
+    float iterate_ms;        /* device: the iterations */
+    float total_ms;
+} sm_register_stats_t;
+int sm_default_register_params(sm_register_params *p);       /* pure, no context */
+int sm_register_maps(sm_ctx *s, const sm_map_source *source, const sm_map_source *target, const float *guess16,
+                     const sm_register_params *p, float *pose16_out, sm_register_info *info);
+int sm_register_debug(sm_ctx *s, const sm_map_source *source, const sm_map_source *target, const float *pose16_eval, int32_t level,
+                      const sm_register_params *p, double *sys29, uint32_t *n_samples);
+int sm_register_stats(sm_ctx *s, sm_register_stats_t *out);
+
 /* ---- per-pass entry points (GlobalModel / IndexMap methods), synchronous ---- */
 /* Upload RGB / metric depth / semantic textures directly (bypasses p0). */
 int sm_set_frame(sm_ctx *s, const uint8_t *rgb, const float *depth_metric,

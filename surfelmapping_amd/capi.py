@@ -48,6 +48,7 @@ SYMBOLS = (
     "sm_default_fill_params", "sm_fill_image", "sm_fill_image_device", "sm_render_image_ex", "sm_render_image_maps_ex", "sm_fill_stats",
     "sm_default_blend_params", "sm_render_image_blend", "sm_render_image_maps_blend", "sm_blend_stats",
     "sm_default_simplify_params", "sm_simplify", "sm_simplify_maps", "sm_simplify_stats",
+    "sm_default_register_params", "sm_register_maps", "sm_register_debug", "sm_register_stats",
 )
 
 SM_COLL_SUM, SM_COLL_MIN, SM_COLL_GATHER = 0, 1, 2
@@ -485,6 +486,49 @@ def simplify_params(**over) -> SmSimplifyParams:
     return p
 
 
+SM_REGISTER_OK, SM_REGISTER_LOST, SM_REGISTER_DEGENERATE, SM_REGISTER_NO_TARGET, SM_REGISTER_NO_SOURCE = 0, 1, 2, 3, 4
+REGISTER_STATUS = {SM_REGISTER_OK: "OK", SM_REGISTER_LOST: "LOST", SM_REGISTER_DEGENERATE: "DEGENERATE",
+                   SM_REGISTER_NO_TARGET: "NO_TARGET", SM_REGISTER_NO_SOURCE: "NO_SOURCE"}
+REGISTER_MAX_LEVELS = 4
+
+
+class SmRegisterParams(C.Structure):
+    _fields_ = [("voxel_mm", C.c_int32), ("levels", C.c_int32), ("max_iters", C.c_int32), ("min_inliers", C.c_int32),
+                ("angle_thresh", C.c_float), ("reach_cells", C.c_float), ("stride", C.c_uint32), ("max_samples", C.c_uint32),
+                ("max_cells", C.c_uint32), ("origin", C.c_float * 3), ("pivot", C.c_float * 3)]
+
+
+class SmRegisterInfo(C.Structure):
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_int32 * REGISTER_MAX_LEVELS), ("inliers", C.c_uint32), ("rmse", C.c_float),
+                ("pivot_ratio", C.c_float), ("samples", C.c_uint32), ("stride", C.c_uint32), ("cells", C.c_uint32 * REGISTER_MAX_LEVELS)]
+
+
+class SmRegisterStats(C.Structure):
+    _fields_ = [("source_records", C.c_uint64), ("target_records", C.c_uint64), ("chunks", C.c_uint32), ("launches", C.c_uint32),
+                ("read_ms", C.c_float), ("table_ms", C.c_float), ("iterate_ms", C.c_float), ("total_ms", C.c_float)]
+
+
+def default_register_params() -> SmRegisterParams:
+    """sm_default_register_params: voxel_mm 200, levels 3, max_iters 20, min_inliers 1000, angle_thresh 30, reach_cells 1, stride 0
+    (from max_samples = 1 << 22), max_cells 1 << 24, origin and pivot (0, 0, 0)"""
+    p = SmRegisterParams()
+    load().sm_default_register_params(C.byref(p))
+    return p
+
+
+def register_params(**over) -> SmRegisterParams:
+    """default_register_params() with fields overridden; origin and pivot take a sequence of three"""
+    p = default_register_params()
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise KeyError(k)
+        if k in ("origin", "pivot"):
+            getattr(p, k)[:] = [float(x) for x in v]
+        else:
+            setattr(p, k, v)
+    return p
+
+
 def search_params(**over) -> SmSearchParams:
     """sm_default_search_params (2 levels; +-2 m in x and z at 0.25 m, +-3 deg about y at 0.5 deg; refine 4, stride0 8, top_k 4,
     colour_thresh 0.1) with fields overridden; the four per-axis fields take a sequence of three"""
@@ -829,6 +873,11 @@ def load():
     L.sm_simplify.argtypes = [vp, smp]
     L.sm_simplify_maps.argtypes = [vp, C.POINTER(SmMapSource), smp, C.c_char_p]
     L.sm_simplify_stats.argtypes = [vp, C.POINTER(SmSimplifyStats)]
+    rgp, msp = C.POINTER(SmRegisterParams), C.POINTER(SmMapSource)
+    L.sm_default_register_params.argtypes = [rgp]
+    L.sm_register_maps.argtypes = [vp, msp, msp, C.c_void_p, rgp, C.c_void_p, C.POINTER(SmRegisterInfo)]
+    L.sm_register_debug.argtypes = [vp, msp, msp, C.c_void_p, C.c_int32, rgp, C.c_void_p, C.c_void_p]
+    L.sm_register_stats.argtypes = [vp, C.POINTER(SmRegisterStats)]
     for name in SYMBOLS:
         getattr(L, name)          # AttributeError here = the library does not match the header
     _lib = L
@@ -1738,6 +1787,50 @@ class SurfelMap:
         src = map_source(paths, include_model)
         self._chk(self._L.sm_simplify_maps(self._h, C.byref(src), C.byref(p), os.fsencode(out_path)), "sm_simplify_maps")
         return self.simplify_stats()
+
+    # -- registration of one map set against another (sm_register_maps)
+    def register_maps(self, source_paths, target_paths, guess=None, source_model=False, target_model=False, apply=False, **params):
+        """The rigid transform that takes the map set `source_paths` (then, with source_model, the live model) onto the set
+        `target_paths` (target_model likewise): voxel-cell ICP, coarse to fine (sm_register_maps).  guess: a 4x4 source-world to
+        target-world matrix or float32[16] column-major, None = identity; params: the fields of register_params() -- pass `pivot`,
+        a point inside the overlap.  Nothing is changed, unless `apply`: on status "OK" the source FILES are then moved by the
+        pose (warp_by_time with t0 = 0 and one row; the live model stays).  Returns (pose 4x4 float32 -- the guess unless status
+        is "OK" --, info dict: status (name), status_code, iterations and cells per level (level 0 the finest), inliers, rmse,
+        pivot_ratio, samples, stride, applied)."""
+        p = register_params(**params)
+        src, tgt = map_source(source_paths, include_model=source_model), map_source(target_paths, include_model=target_model)
+        g = None if guess is None else _mat16(guess)
+        out = np.zeros(16, np.float32)
+        info = SmRegisterInfo()
+        self._chk(self._L.sm_register_maps(self._h, C.byref(src), C.byref(tgt), _ptr(g), C.byref(p), _ptr(out), C.byref(info)), "sm_register_maps")
+        pose = out.reshape(4, 4).T.copy()
+        d = dict(status=REGISTER_STATUS.get(info.status, str(info.status)), status_code=int(info.status),
+                 iterations=[int(v) for v in info.iterations[:p.levels]], cells=[int(v) for v in info.cells[:p.levels]],
+                 inliers=int(info.inliers), rmse=float(info.rmse), pivot_ratio=float(info.pivot_ratio), samples=int(info.samples),
+                 stride=int(info.stride), applied=False)
+        if apply and info.status == SM_REGISTER_OK and len(source_paths):
+            self.warp_by_time(source_paths, 0, pose[:3, :].reshape(1, 12), include_model=False)
+            d["applied"] = True
+        return pose, d
+
+    def register_debug(self, source_paths, target_paths, pose_eval, level, source_model=False, target_model=False, **params):
+        """ONE system of register_maps at pose_eval on `level` (sm_register_debug).  Returns (sys float64[29] in track_debug()'s
+        layout, the number of samples, regular or not)."""
+        p = register_params(**params)
+        src, tgt = map_source(source_paths, include_model=source_model), map_source(target_paths, include_model=target_model)
+        pe = _mat16(pose_eval)
+        sys29 = np.zeros(29, np.float64)
+        n = C.c_uint32()
+        self._chk(self._L.sm_register_debug(self._h, C.byref(src), C.byref(tgt), _ptr(pe), int(level), C.byref(p), _ptr(sys29), C.addressof(n)),
+                  "sm_register_debug")
+        return sys29, int(n.value)
+
+    def register_stats(self) -> dict:
+        """of the last register_maps / register_debug: source_records, target_records, chunks, launches, read_ms, table_ms,
+        iterate_ms, total_ms"""
+        st = SmRegisterStats()
+        self._chk(self._L.sm_register_stats(self._h, C.byref(st)), "sm_register_stats")
+        return {k: getattr(st, k) for k, _ in SmRegisterStats._fields_}
 
     def simplify_stats(self) -> dict:
         """of the last simplify* call: records_in, records_out, cells_merged, loose, largest_cell, chunks, launches, device_ms,

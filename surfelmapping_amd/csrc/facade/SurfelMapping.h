@@ -278,6 +278,53 @@ public:
         return (long)st.records_out;
     }
 
+    // Which rigid transform takes the map set `sourceFiles` onto the set `targetFiles` (sm_register_maps; DESIGN.md "4q.
+    // Registration"): two drives of one street, each in the world of its own first pose.  guess: source world -> target world, as
+    // far as it is known (within about a cell of the coarsest level, 0.8 m by default); pose: the result, the guess unless the
+    // status is SM_REGISTER_OK.  params (null: the defaults) should name a pivot inside the overlap.  Nothing is changed.
+    // Returns the status (SM_REGISTER_*), or -1 with the error printed.
+    int registerMaps(const std::vector<std::string> &sourceFiles, const std::vector<std::string> &targetFiles, const Eigen::Matrix4f &guess,
+                     Eigen::Matrix4f &pose, const sm_register_params *params = nullptr, sm_register_info *info = nullptr)
+    {
+        std::vector<const char *> sp, tp;
+        for (const std::string &f : sourceFiles) sp.push_back(f.c_str());
+        for (const std::string &f : targetFiles) tp.push_back(f.c_str());
+        const sm_map_source src{sp.data(), (uint32_t)sp.size(), 0}, tgt{tp.data(), (uint32_t)tp.size(), 0};
+        sm_register_params p;
+        sm_default_register_params(&p);
+        if (params) p = *params;
+        sm_register_info got;
+        float out[16];
+        (void)sm_sync(ctx_);                                             // (SM_FACADE_ASYNC: frames may still be in flight)
+        if (sm_register_maps(ctx_, &src, &tgt, guess.data(), &p, out, &got) != SM_OK) {
+            std::printf("registerMaps: %s\n", sm_last_error());
+            return -1;
+        }
+        std::memcpy(pose.data(), out, 64);
+        if (info) *info = got;
+        return got.status;
+    }
+    // registerMaps, and on SM_REGISTER_OK the source files moved into the target's world (sm_warp_by_time with t0 = 0 and one
+    // row, the pose): the two sets can then be viewed, swept or simplified as one.  A file none of whose records moves is left
+    // alone; the live model stays.  Returns as registerMaps; -1 as well if the warp fails (the error is printed).
+    int alignMaps(const std::vector<std::string> &sourceFiles, const std::vector<std::string> &targetFiles, const Eigen::Matrix4f &guess,
+                  Eigen::Matrix4f &pose, const sm_register_params *params = nullptr, sm_register_info *info = nullptr)
+    {
+        const int status = registerMaps(sourceFiles, targetFiles, guess, pose, params, info);
+        if (status != SM_REGISTER_OK || sourceFiles.empty()) return status;
+        std::vector<const char *> sp;
+        for (const std::string &f : sourceFiles) sp.push_back(f.c_str());
+        const sm_map_source src{sp.data(), (uint32_t)sp.size(), 0};
+        float corr[12];                                                  // row-major 3 x 4 of the column-major pose
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 4; ++c) corr[r * 4 + c] = pose.data()[c * 4 + r];
+        if (sm_warp_by_time(ctx_, &src, 0, 1, corr) != SM_OK) {
+            std::printf("alignMaps: %s\n", sm_last_error());
+            return -1;
+        }
+        return status;
+    }
+
     // The second sensor's dump: what a lidar `sensor` (sm_lidar_sensor; sm_default_lidar_sensor) at each of `poses` (sensor->world,
     // the camera's axes) measures in the live model, written as <path>/velodyne/%06d.bin next to acquireImages' folders, in KITTI's
     // velodyne layout: per return four floats, (z, -x, -y) of t*d in the sensor frame -- x forward, y left, z up -- and the

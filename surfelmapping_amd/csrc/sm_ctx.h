@@ -19,10 +19,11 @@
 //   sm_fill.hip      hole filling (sm_fill_*, sm_render_image_ex's and sm_render_image_maps_ex's stage): depth of a view, push-pull completion
 //   sm_blend.hip     blended views (sm_render_image_blend, sm_render_image_maps_blend): the visible layer's accumulation and normalisation, a stage of both render paths
 //   sm_simplify.hip  simplification (sm_simplify, sm_simplify_maps): the model or a map set merged per voxel cell, two passes over the records
+//   sm_register.hip  registration (sm_register_*): the rigid transform from one map set to another, voxel-cell ICP, one pass over each set
 // and, beside it, for everything that touches a map file: sm_mapfile.h (the format: checked open, writer, chunk plan; host only),
 // sm_map_set.h (a listed set of files: the file index, the two openings, a rewrite's per-file record and temporary; host only) and
-// sm_map_stream.h (the double-buffered chunk stream of sm_render_maps.hip, sm_lidar.hip, sm_recall.hip, sm_warp.hip and sm_simplify.hip).  The staging
-// those four stream through (MapStaging) and the file index (FileIndex) are the context's, no feature's.  For the occupied slots and the
+// sm_map_stream.h (the double-buffered chunk stream of sm_render_maps.hip, sm_lidar.hip, sm_recall.hip, sm_warp.hip, sm_simplify.hip and sm_register.hip).  The staging
+// they stream through (MapStaging) and the file index (FileIndex) are the context's, no feature's.  For the occupied slots and the
 // compaction schedule: sm_slots.h (SlotSchedule; host only); for the arithmetic of rigid poses in double: sm_pose.h (host only,
 // included by sm_track.hip and sm_warp.hip).  What alternates between consecutive frames is FrameSet, below.
 #pragma once
@@ -46,7 +47,7 @@
 #include <utility>
 #include <vector>
 
-namespace sm { struct TrackState; struct TrackRgbState; struct RenderParams; struct ViewParams; struct ViewShade; struct RecallChunk; struct WarpChunk; }
+namespace sm { struct TrackState; struct TrackRgbState; struct RegState; struct RenderParams; struct ViewParams; struct ViewShade; struct RecallChunk; struct WarpChunk; }
 
 // Hidden: libsurfelmapping_hip.so exports the C ABI and the kernels' host stubs, nothing of this namespace.  Its functions are
 // defined qualified (sm_impl::name) so that the definitions keep the visibility.
@@ -326,6 +327,19 @@ struct Simplify {
     bool stats_valid = false;
 };
 
+// registration (sm_register.hip, sm_k_register.h): what outlives a call -- the tallies, the partial sums, the state and its pinned
+// mirror, the events -- and the last call's tally.  Tables and samples live for one call.
+struct Register {
+    Dev<uint32_t> d_tally;             // per level the simplification's tally words, then the regular samples
+    Host<uint32_t> h_tally;            // pinned
+    Dev<double> d_part;
+    Dev<RegState> d_state;
+    Host<RegState> h_state;            // pinned
+    Event ev[8];                       // around the target's model and the finish, the source's model, the iterations, the tables' memsets
+    sm_register_stats_t stats{};
+    bool stats_valid = false;
+};
+
 // closing loops unasked (sm_loop.hip): the policy of sm_set_auto_loop and its tally
 struct AutoLoop {
     bool on = false;
@@ -576,6 +590,7 @@ struct sm_ctx {
     std::vector<Dev<void>> user_allocs;
     Timeline tl;
     Dev<FrameLog> d_log;
+    Register reg;                      // (nothing depends on where it lies; behind the frame path's members, which keep their places)
 };
 
 namespace sm_impl __attribute__((visibility("hidden"))) {

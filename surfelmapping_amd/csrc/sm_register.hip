@@ -1,0 +1,347 @@
+// sm_register.hip -- registration of one map set against another (sm_register_maps, sm_register_debug; DESIGN.md "4q.
+// Registration"): the target set streamed once into one voxel table per level, the source set streamed once into resident
+// samples, then the iterations enqueued whole.  Kernels: sm_k_register.h.
+#include "sm_map_stream.h"
+#include "sm_k_register.h"
+#include "sm_pose.h"
+
+using namespace sm;
+using sm_mapfile::now_ms;
+
+namespace {
+
+constexpr uint32_t CHUNK = MapStaging::CHUNK;
+constexpr uint32_t REG_MAX_SAMPLES = 1u << 28;
+constexpr size_t REG_SUM_BYTES = 8 * 7;                  // per slot beside the key: SW, SP[3], SN[3]
+enum { EV_TGT0 = 0, EV_TGT1, EV_SRC0, EV_SRC1, EV_IT0, EV_IT1, EV_CLR0, EV_CLR1 };   // pairs: add_marked(first)
+
+int check_params(const sm_register_params *p, const char *who)
+{
+    auto bad = [&](const char *what) { g_err = std::string(who) + ": " + what; return SM_E_ARG; };
+    if (!p) return bad("null params");
+    if (p->voxel_mm < 10 || p->voxel_mm > 10000) return bad("voxel_mm outside 10..10000");
+    if (p->levels < 1 || p->levels > SM_REGISTER_MAX_LEVELS) return bad("levels outside 1..4");
+    if (p->max_iters < 1 || p->max_iters > SM_TRACK_MAX_ITERS) return bad("max_iters outside 1..100");
+    if (p->min_inliers < 0) return bad("min_inliers is negative");
+    if (!(p->angle_thresh > 0.0f && p->angle_thresh < 90.0f)) return bad("angle_thresh outside (0, 90)");
+    if (!(p->reach_cells > 0.0f) || !std::isfinite(p->reach_cells)) return bad("reach_cells is not a positive number");
+    if (p->max_samples < 1 || p->max_samples > REG_MAX_SAMPLES) return bad("max_samples outside 1..2^28");
+    if (p->max_cells == 0) return bad("max_cells is 0");
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(p->origin[k]) || !std::isfinite(p->pivot[k])) return bad("non-finite origin or pivot");
+    return SM_OK;
+}
+
+// what both entry points ask of their sets, without the device: the sources, no path in both, every header of both
+int open_sets(const sm_map_source *source, const sm_map_source *target, const char *who, sm_mapset::ReadSet &sset, sm_mapset::ReadSet &tset)
+{
+    int rc;
+    if ((rc = check_map_source(source, who)) || (rc = check_map_source(target, who))) return rc;
+    for (uint32_t i = 0; i < source->n_paths; ++i)
+        for (uint32_t k = 0; k < target->n_paths; ++k)
+            if (strcmp(source->paths[i], target->paths[k]) == 0) { g_err = sm_mapfile::said(who, source->paths[i], " is in both sets"); return SM_E_ARG; }
+    if (!sm_mapset::open_read_set(source->paths, source->n_paths, CHUNK, who, sset, g_err)) return SM_E_ARG;
+    if (!sm_mapset::open_read_set(target->paths, target->n_paths, CHUNK, who, tset, g_err)) return SM_E_ARG;
+    return SM_OK;
+}
+
+int reg_alloc(sm_ctx *s)
+{
+    Register &rg = s->reg;
+    if (rg.d_state) return SM_OK;
+    constexpr size_t words = REG_MAX_LEVELS * SIMP_TALLY_WORDS + 1;
+    Dev<uint32_t> tally; Dev<double> part; Dev<RegState> st;
+    int rc;
+    if ((rc = dalloc(tally, words)) || (rc = dalloc(part, (size_t)TRACK_NSYS * TRACK_MAX_PARTS)) || (rc = dalloc(st, 1))) return rc;
+    HIPCK(hipHostMalloc((void **)rg.h_tally.put(), words * 4, hipHostMallocDefault));
+    HIPCK(hipHostMalloc((void **)rg.h_state.put(), sizeof(RegState), hipHostMallocDefault));
+    for (Event &e : rg.ev) HIPCK(hipEventCreate(e.put()));
+    rg.d_tally = std::move(tally); rg.d_part = std::move(part);
+    rg.d_state = std::move(st);                          // last: it marks the set complete
+    return SM_OK;
+}
+
+// One call's device side: the tables of all levels, the samples, the kernel arguments.
+struct RegisterJob {
+    sm_ctx *s;
+    Register &rg;
+    const char *who;
+    const sm_register_params &p;
+    SimplifyArgs a[REG_MAX_LEVELS]{};
+    SimplifyTable T[REG_MAX_LEVELS]{};
+    RegCell *lut[REG_MAX_LEVELS]{};
+    Dev<uint8_t> tables;
+    Dev<float4> pos, nrm;
+    uint32_t stride = 1, n_samples = 0;
+    uint32_t launches = 0;
+
+    RegisterJob(sm_ctx *s_, const char *who_, const sm_register_params &p_) : s(s_), rg(s_->reg), who(who_), p(p_) {}
+    uint32_t *regular() const { return rg.d_tally.get() + REG_MAX_LEVELS * SIMP_TALLY_WORDS; }
+
+    int open(uint64_t target_records, uint64_t source_records)
+    {
+        stride = p.stride ? p.stride : (uint32_t)std::max<uint64_t>(1, (source_records + p.max_samples - 1) / p.max_samples);
+        const uint64_t ns = (source_records + stride - 1) / stride;
+        if (ns > REG_MAX_SAMPLES) { g_err = std::string(who) + ": more than 2^28 samples"; return SM_E_CAPACITY; }
+        if (ns > p.max_samples) { g_err = std::string(who) + ": stride leaves more than max_samples samples"; return SM_E_ARG; }
+        n_samples = (uint32_t)ns;
+        int rc;
+        if ((rc = reg_alloc(s)) || (rc = dalloc(pos, n_samples)) || (rc = dalloc(nrm, n_samples))) return rc;
+        uint64_t S = SIMP_MIN_SLOTS;
+        while (S < 2 * std::min<uint64_t>(target_records, p.max_cells)) S <<= 1;
+        if (S > (1ull << 31)) { g_err = std::string(who) + ": a table would need more than 2^31 slots"; return SM_E_CAPACITY; }
+        const size_t per_level = (size_t)S * (8 + REG_SUM_BYTES + sizeof(RegCell));
+        HIPCK(hipMalloc((void **)tables.put(), per_level * (size_t)p.levels));
+        const char *e = std::getenv("SM_SIMPLIFY_NO_COMBINE");
+        if ((rc = mark(EV_CLR0))) return rc;             // the tables' initialisation is device time of theirs (table_ms)
+        for (int l = 0; l < p.levels; ++l) {
+            uint8_t *b = tables.get() + per_level * (size_t)l;
+            lut[l] = (RegCell *)b;                       // (first: 32-byte aligned)
+            b += (size_t)S * sizeof(RegCell);
+            T[l].key = (unsigned long long *)b;
+            T[l].SW = T[l].key + S; T[l].SP = T[l].SW + S; T[l].SN = T[l].SP + 3 * S;
+            T[l].mask = (uint32_t)(S - 1);
+            T[l].tally = rg.d_tally.get() + l * SIMP_TALLY_WORDS;
+            a[l].V = (((long long)p.voxel_mm << l) * 65536 + 500) / 1000;
+            for (int k = 0; k < 3; ++k) a[l].origin[k] = p.origin[k];
+            a[l].split = 1;
+            a[l].max_cells = p.max_cells;
+            a[l].combine = (e && e[0] == '1') ? 0 : 1;
+            HIPCK(hipMemsetAsync(T[l].key, 0xFF, (size_t)S * 8, s->stream));
+            HIPCK(hipMemsetAsync(T[l].SW, 0, (size_t)S * REG_SUM_BYTES, s->stream));
+        }
+        HIPCK(hipMemsetAsync(rg.d_tally, 0, (REG_MAX_LEVELS * SIMP_TALLY_WORDS + 1) * 4, s->stream));
+        return mark(EV_CLR1);
+    }
+    // n <= CHUNK records of the target into every level's table
+    void insert(const float4 *d_rec, uint32_t n)
+    {
+        for (int l = 0; l < p.levels; ++l)
+            hipLaunchKernelGGL(k_register_insert, dim3((n + 255) / 256), dim3(256), 0, s->stream, d_rec, n, a[l], T[l]);
+        launches += p.levels;
+        rg.stats.chunks++;
+    }
+    void finish()
+    {
+        for (int l = 0; l < p.levels; ++l)
+            hipLaunchKernelGGL(k_register_finish, dim3(T[l].mask / 256u + 1u), dim3(256), 0, s->stream, a[l], T[l], lut[l]);
+        launches += p.levels;
+    }
+    // n <= CHUNK records of the source with ids gid0 ..
+    void gather(const float4 *d_rec, uint32_t n, uint32_t gid0)
+    {
+        hipLaunchKernelGGL(k_register_gather, dim3((n + 255) / 256), dim3(256), 0, s->stream, d_rec, n, gid0, stride, pos.get(), nrm.get(), regular());
+        launches++;
+        rg.stats.chunks++;
+    }
+    RegParams params() const
+    {
+        RegParams rp{};
+        for (int l = 0; l < p.levels; ++l) {
+            rp.lv[l].lut = lut[l];
+            rp.lv[l].mask = T[l].mask;
+            rp.lv[l].V = a[l].V;
+            rp.lv[l].reach = (double)p.reach_cells * ((double)a[l].V * (1.0 / 65536.0));
+        }
+        rp.levels = p.levels;
+        for (int k = 0; k < 3; ++k) { rp.origin[k] = p.origin[k]; rp.pivot[k] = (double)p.pivot[k]; }
+        rp.cos_angle = std::cos((double)p.angle_thresh * (3.14159265358979323846 / 180.0));
+        rp.n_samples = n_samples;
+        rp.nb = (int)std::min<long>(TRACK_MAX_PARTS, std::max<long>(1, ((long)n_samples + TRACK_BLOCK * 4 - 1) / (TRACK_BLOCK * 4)));
+        rp.min_inliers = (uint32_t)p.min_inliers;
+        rp.max_iters = p.max_iters;
+        rp.degenerate_bound = SM_TRACK_DEGENERATE_BOUND;
+        return rp;
+    }
+    void iteration(const RegParams &rp, int sum_only)
+    {
+        hipLaunchKernelGGL(k_register_reduce, dim3(rp.nb), dim3(TRACK_BLOCK), 0, s->stream, rp, (const float4 *)pos.get(), (const float4 *)nrm.get(),
+                           (const RegState *)rg.d_state.get(), rg.d_part.get());
+        hipLaunchKernelGGL(k_register_solve, dim3(1), dim3(256), 0, s->stream, rp, (const double *)rg.d_part.get(), rg.d_state.get(), sum_only);
+        launches += 2;
+    }
+    int mark(int i) { HIPCK(hipEventRecord(rg.ev[i], s->stream)); return SM_OK; }
+    int add_marked(int i, float *ms_sum)
+    {
+        float ms = 0.0f;
+        HIPCK(hipEventElapsedTime(&ms, rg.ev[i], rg.ev[i + 1]));
+        *ms_sum += ms;
+        return SM_OK;
+    }
+};
+
+// Both entry points.  level < 0: sm_register_maps (pose16 the guess, null = identity); else sm_register_debug (pose16 the pose of
+// the one system on `level`).
+int register_run(sm_ctx *s, const sm_map_source *source, const sm_map_source *target, const float *pose16, int32_t level,
+                 const sm_register_params *p, float *pose16_out, sm_register_info *info, double *sys29, uint32_t *n_samples_out, const char *who)
+{
+    const double t_begin = now_ms();
+    const bool debug = level >= 0;
+    int rc;
+    if ((rc = check_whole_map(s, who)) || (rc = check_params(p, who)) || (rc = check_not_mid_cull(s, who)) || (rc = check_pose(pose16, who))) return rc;
+    if (debug && level >= p->levels) { g_err = std::string(who) + ": level outside 0 .. levels - 1"; return SM_E_ARG; }
+    sm_mapset::ReadSet sset, tset;
+    if ((rc = open_sets(source, target, who, sset, tset))) return rc;
+    HIPCK(hipSetDevice(s->cfg.device));
+    if ((rc = ensure_compact(s)) || (rc = pull_state(s))) return rc;      // (waits for frames in flight; count is the live surfels)
+    const uint32_t model = s->h_state->count, scnt = source->include_model ? model : 0u, tcnt = target->include_model ? model : 0u;
+    const uint64_t stotal = sset.file_total + scnt, ttotal = tset.file_total + tcnt;
+    if (stotal > 0x7FFFFFFFull || ttotal > 0x7FFFFFFFull) { g_err = std::string(who) + ": a set of more than 2^31 - 1 records"; return SM_E_CAPACITY; }
+
+    Register &rg = s->reg;
+    rg.stats = sm_register_stats_t{};
+    rg.stats_valid = true;
+    rg.stats.source_records = stotal;
+    rg.stats.target_records = ttotal;
+    float guess[16];
+    if (pose16) memcpy(guess, pose16, 64);
+    else sm_pose::identity(guess);
+    sm_register_info out{};
+    out.status = SM_REGISTER_OK;
+
+    RegisterJob job(s, who, *p);
+    if ((rc = job.open(ttotal, stotal))) return rc;
+    out.stride = job.stride;
+    if (n_samples_out) *n_samples_out = job.n_samples;
+    const float4 *d_model = nullptr;
+    if (scnt || tcnt) {
+        if ((rc = ensure_export(s, (size_t)model * 48))) return rc;
+        export_aos(s, (float *)s->d_export.get(), 0u, model);
+        d_model = (const float4 *)s->d_export.get();
+    }
+    if (sset.jobs.size() + tset.jobs.size())
+        if ((rc = maps_ensure_staging(s))) return rc;
+    float copy_ms = 0.0f;
+    // ---- the target: every chunk into every level's table, then the representatives
+    {
+        MapStream in(s, who, target->paths, {&rg.stats.read_ms, &copy_ms, &rg.stats.table_ms});
+        for (in.begin(tset.jobs); in.more();) {
+            MapStream::Chunk ck;
+            if ((rc = in.next(ck))) return rc;
+            job.insert(ck.d_rec, ck.job->n);
+            if ((rc = in.done(ck.q))) return rc;
+            HIPCK(hipGetLastError());
+        }
+        if ((rc = in.fold(0)) || (rc = in.fold(1))) return rc;
+    }
+    if ((rc = job.mark(EV_TGT0))) return rc;
+    for (uint32_t first = 0; first < tcnt; first += CHUNK) job.insert(d_model + (size_t)first * 3, std::min(CHUNK, tcnt - first));
+    job.finish();
+    if ((rc = job.mark(EV_TGT1))) return rc;
+    // ---- the source: the samples to their places
+    {
+        MapStream in(s, who, source->paths, {&rg.stats.read_ms, &copy_ms, &rg.stats.table_ms});
+        for (in.begin(sset.jobs); in.more();) {
+            MapStream::Chunk ck;
+            if ((rc = in.next(ck))) return rc;
+            job.gather(ck.d_rec, ck.job->n, (uint32_t)(sset.id_base[ck.job->file] + ck.job->first));
+            if ((rc = in.done(ck.q))) return rc;
+            HIPCK(hipGetLastError());
+        }
+        if ((rc = in.fold(0)) || (rc = in.fold(1))) return rc;
+    }
+    if ((rc = job.mark(EV_SRC0))) return rc;
+    for (uint32_t first = 0; first < scnt; first += CHUNK)
+        job.gather(d_model + (size_t)first * 3, std::min(CHUNK, scnt - first), (uint32_t)sset.file_total + first);
+    if ((rc = job.mark(EV_SRC1))) return rc;
+    HIPCK(hipGetLastError());
+    constexpr size_t words = REG_MAX_LEVELS * SIMP_TALLY_WORDS + 1;
+    HIPCK(hipMemcpyAsync(rg.h_tally.get(), rg.d_tally.get(), words * 4, hipMemcpyDeviceToHost, s->stream));
+    HIPCK(hipStreamSynchronize(s->stream));
+    if ((rc = job.add_marked(EV_CLR0, &rg.stats.table_ms)) || (rc = job.add_marked(EV_TGT0, &rg.stats.table_ms)) ||
+        (rc = job.add_marked(EV_SRC0, &rg.stats.table_ms))) return rc;
+    const uint32_t *h = rg.h_tally.get();
+    for (int l = 0; l < p->levels; ++l) {
+        if (h[l * SIMP_TALLY_WORDS + SIMP_ERR]) {
+            g_err = std::string(who) + ": more than max_cells = " + std::to_string(p->max_cells) + " keys at level " + std::to_string(l);
+            return SM_E_CAPACITY;
+        }
+        out.cells[l] = h[l * SIMP_TALLY_WORDS + SIMP_CELLS];
+        if (out.cells[l] == 0) out.status = SM_REGISTER_NO_TARGET;
+    }
+    out.samples = h[REG_MAX_LEVELS * SIMP_TALLY_WORDS];
+    if (out.status == SM_REGISTER_OK && out.samples == 0) out.status = SM_REGISTER_NO_SOURCE;
+
+    RegState &hs = *rg.h_state;
+    memset(&hs, 0, sizeof hs);
+    if (out.status == SM_REGISTER_OK || debug) {
+        // ---- the iterations, enqueued whole; the one wait follows the last
+        const RegParams rp = job.params();
+        for (int e = 0; e < 16; ++e) hs.T[e] = hs.guess[e] = (double)guess[e];
+        if (!debug) sm_pose::orthonormalize_d(hs.T);
+        hs.level = debug ? level : p->levels - 1;
+        HIPCK(hipMemcpyAsync(rg.d_state.get(), &hs, sizeof hs, hipMemcpyHostToDevice, s->stream));
+        if ((rc = job.mark(EV_IT0))) return rc;
+        if (debug) job.iteration(rp, 1);
+        else
+            for (int i = 0; i < p->levels * p->max_iters; ++i) job.iteration(rp, 0);
+        HIPCK(hipGetLastError());
+        if ((rc = job.mark(EV_IT1))) return rc;
+        HIPCK(hipMemcpyAsync(&hs, rg.d_state.get(), sizeof hs, hipMemcpyDeviceToHost, s->stream));
+        HIPCK(hipStreamSynchronize(s->stream));
+        if ((rc = job.add_marked(EV_IT0, &rg.stats.iterate_ms))) return rc;
+    }
+    if (debug) {
+        for (int e = 0; e < TRACK_NSYS; ++e) sys29[e] = hs.sys[e];
+    } else {
+        if (out.status == SM_REGISTER_OK) {
+            out.status = hs.status;
+            for (int l = 0; l < REG_MAX_LEVELS; ++l) out.iterations[l] = hs.iters[l];
+            out.inliers = hs.inliers;
+            out.rmse = (float)hs.rmse;
+            out.pivot_ratio = (float)hs.pivot_ratio;
+        }
+        for (int e = 0; e < 16; ++e) pose16_out[e] = out.status == SM_REGISTER_OK ? (float)hs.T[e] : guess[e];
+        *info = out;
+    }
+    rg.stats.launches = job.launches;
+    rg.stats.total_ms = (float)(now_ms() - t_begin);
+    return SM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sm_default_register_params(sm_register_params *p)
+{
+    if (!p) { g_err = "sm_default_register_params: null argument"; return SM_E_ARG; }
+    *p = sm_register_params{};
+    p->voxel_mm = 200;
+    p->levels = 3;
+    p->max_iters = 20;
+    p->min_inliers = 1000;
+    p->angle_thresh = 30.0f;
+    p->reach_cells = 1.0f;
+    p->stride = 0;
+    p->max_samples = 1u << 22;
+    p->max_cells = 1u << 24;
+    return SM_OK;
+}
+
+int sm_register_maps(sm_ctx *s, const sm_map_source *source, const sm_map_source *target, const float *guess16, const sm_register_params *p,
+                     float *pose16_out, sm_register_info *info)
+{
+    const char *who = "sm_register_maps";
+    if (!s || !source || !target || !p || !pose16_out || !info) { g_err = std::string(who) + ": null argument"; return SM_E_ARG; }
+    return register_run(s, source, target, guess16, -1, p, pose16_out, info, nullptr, nullptr, who);
+}
+
+int sm_register_debug(sm_ctx *s, const sm_map_source *source, const sm_map_source *target, const float *pose16_eval, int32_t level,
+                      const sm_register_params *p, double *sys29, uint32_t *n_samples)
+{
+    const char *who = "sm_register_debug";
+    if (!s || !source || !target || !pose16_eval || !p || !sys29 || !n_samples) { g_err = std::string(who) + ": null argument"; return SM_E_ARG; }
+    if (level < 0) { g_err = std::string(who) + ": level outside 0 .. levels - 1"; return SM_E_ARG; }
+    return register_run(s, source, target, pose16_eval, level, p, nullptr, nullptr, sys29, n_samples, who);
+}
+
+int sm_register_stats(sm_ctx *s, sm_register_stats_t *out)
+{
+    if (!s || !out) { g_err = "sm_register_stats: null argument"; return SM_E_ARG; }
+    if (!s->reg.stats_valid) { g_err = "sm_register_stats: no sm_register_maps / sm_register_debug call yet"; return SM_E_ARG; }
+    *out = s->reg.stats;
+    return SM_OK;
+}
+
+}  // extern "C"

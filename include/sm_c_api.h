@@ -1261,6 +1261,94 @@ int sm_register_debug(sm_ctx *s, const sm_map_source *source, const sm_map_sourc
                       const sm_register_params *p, double *sys29, uint32_t *n_samples);
 int sm_register_stats(sm_ctx *s, sm_register_stats_t *out);
 
+/* ---- change detection between two map sets (DESIGN.md "4r. Change detection") ----
+ * Once yesterday's map and today's share a frame (sm_register_maps), sm_compare_maps says of every record of the QUERY set
+ * whether the REFERENCE set holds its surface: a label per record, and the records with the labels asked for as one map file that
+ * every map-set call can draw, sweep or recall.  Which records of today's map are new: query = today, reference = yesterday;
+ * which have vanished: the other way round.  Sets and global ids are registration's (files in list order, each in file order,
+ * then the live model); either set may include the model.  pose16 (column-major, NULL = the identity) takes the query's world to
+ * the reference's and is widened to fp64 as given, as sm_register_debug's.  Neither set is modified, nor the model, tick, stored
+ * poses, fern keyframes or tracker state; frames in flight are waited for.  Whatever is decided is decided in integers or in
+ * single, stated fp64 / fp32 operations (no contraction): tests/compare_ref.py restates it and the labels agree bit for bit.
+ *   V0 = (voxel_mm * 65536 + 500) / 1000 and V1 = ((voxel_mm << cover_shift) * 65536 + 500) / 1000: the edges of a fine and of a
+ *   cover cell in units of 2^-16 m.
+ *   1. Fine table of the reference.  Registration's step 1 with V0: the simplification's regular-record test, X, cell, off, face
+ *     (always split), weight and normal integers; the key is its key with the class kept iff match_class, else taken as 0.  Per
+ *     key the exact sums SW, SP[3], SN[3]; a key's representative (pos, n_c) has the simplification's merged position and merged
+ *     normal ((0, 0, 0) where all three f vanish: it supports nothing).  The table is a function of the multiset of reference
+ *     records alone.
+ *   2. Cover table of the reference.  The key is the cell alone, with V1, face 0 and class 0: present iff a reference record that
+ *     is regular with V1 (the simplification's test with that edge) lies in the cell.  No sums.
+ *     One pass over the reference set fills both tables.  More than max_cells keys in either: SM_E_CAPACITY, nothing is written
+ *     (no label, no file).
+ *   3. Label of a query record (p, n, class), the first rule that applies:
+ *     LOOSE      it fails the simplification's tests of its fields (everything but the cell range).
+ *     Otherwise q and nq as in registration's step 3: q[r] = ((T[r] * p0 + T[4 + r] * p1) + T[8 + r] * p2) + T[12 + r],
+ *       nq[r] = (T[r] * n0 + T[4 + r] * n1) + T[8 + r] * n2, in double.
+ *     OUTSIDE    by range: |q[k] - (double)origin[k]| >= 2^24 (or not a number) on an axis, or the fine cell (X, cell of q with
+ *       V0, as in the simplification) or the cover cell (with V1) of q outside [-65536, 65535] on an axis.
+ *     Candidate faces.  m = max |nq[k]| (double); the face (a, nq[a] < 0), that is 2a + (nq[a] < 0), is a candidate for every
+ *       axis a with 4.0 * |nq[a]| >= m: one to three faces, the simplification's face of nq among them.  (Within angle_thresh of
+ *       a normal near the 45 degree tie of two axes lie normals of the other dominant axis; with the primary face alone every
+ *       such wall would read as changed.)
+ *     Candidate cells.  Registration's 2 x 2 x 2 with V0: per axis cell[k] and its neighbour towards q -- cell[k] + 1 if
+ *       2 * off[k] >= V0, else cell[k] - 1; a neighbour outside the cell range is dropped.
+ *     Candidate keys.  cells x faces with class 0, or the record's class (colour word >> 24) if match_class; those the fine table
+ *       holds: at most 24.  For one with the representative (pos, n_c): e[k] = q[k] - (double)pos[k], d2 = (e0 * e0 + e1 * e1) +
+ *       e2 * e2, r = (n_c0 * e0 + n_c1 * e1) + n_c2 * e2 (n_c widened).  It passes iff
+ *         sqrt(d2) <= (double)reach_cells * ((double)V0 * 2^-16)  and
+ *         (nq0 * n_c0 + nq1 * n_c1) + nq2 * n_c2 >= cos((double)angle_thresh * (pi / 180))  and
+ *         fabs(r) <= (double)plane_mm / 1000.0.
+ *     SUPPORTED  iff any candidate passes: there is no nearest one, hence no tie and no order.
+ *     CHANGED    otherwise, iff the cover table holds one of the 2 x 2 x 2 cover cells of q (cell and neighbour towards q per
+ *       axis with V1, neighbours outside the range dropped): the reference mapped this neighbourhood, but not this surface.
+ *     OUTSIDE    otherwise: the reference has nothing near -- not mapped there, no statement.
+ *   4. Outputs.  labels[g] for every query id g (if labels is given); info->counts by label; with out_path ONE map file, written
+ *     as sm_simplify_maps writes its own (through "<out_path>.compare.tmp" and a rename; the header's frame range spans the query
+ *     files'), of the query records whose label l has bit l of write_mask set -- verbatim, NOT moved by the pose (sm_warp_by_time
+ *     does that), in set order.  No such record: a valid empty file.  info->written is that file's record count.
+ * sm_compare_stats: of the context's last sm_compare_maps.
+ * Errors.  SM_E_ARG: NULLs other than pose16, labels and out_path; a parameter outside the ranges below; write_mask outside
+ *   1..15 when out_path is given; a non-finite pose or origin; the header and set checks of sm_render_image_maps for both sets
+ *   (every header of both before any work); a path that is in both sets; out_path equal to a path of either set; a call between
+ *   sm_stage_conflict and sm_stage_cull; sm_compare_stats before any call.  SM_E_UNSUPPORTED: a sharded or rig context.
+ *   SM_E_CAPACITY as above, and for a set of more than 2^31 - 1 records. */
+#define SM_COMPARE_SUPPORTED 0   /* the reference holds this surface */
+#define SM_COMPARE_CHANGED   1   /* the reference mapped this neighbourhood, but not this surface */
+#define SM_COMPARE_OUTSIDE   2   /* the reference has nothing near: not mapped there, no statement */
+#define SM_COMPARE_LOOSE     3   /* an irregular record */
+typedef struct sm_compare_params {
+    int32_t voxel_mm;        /* edge of a fine cell, 10..10000                                                 default 100 */
+    int32_t cover_shift;     /* 1..6: cover cell edge = voxel_mm << cover_shift                                default 3 */
+    float reach_cells;       /* lateral reach in fine cell edges; finite, > 0                                  default 2.0 */
+    int32_t plane_mm;        /* 1..10000: largest point-to-plane distance that is still the same surface       default 50 */
+    float angle_thresh;      /* degrees, in (0, 90): largest angle between the normals                         default 30 */
+    int32_t match_class;     /* 0 / 1; 1: a supporting cell must hold records of the query record's class      default 0 */
+    uint32_t write_mask;     /* bit l = label l, 1..15; read only if out_path is given                         default 2 */
+    uint32_t max_cells;      /* keys either table may hold, >= 1                                               default 1 << 24 */
+    float origin[3];         /* of the grids, metres                                                           default 0 */
+} sm_compare_params;
+typedef struct sm_compare_info {
+    uint64_t counts[4];      /* query records by label */
+    uint64_t query_records, reference_records;
+    uint32_t cells_fine, cells_cover;             /* keys of the two tables */
+    uint64_t written;        /* records of the file at out_path (0 without one) */
+} sm_compare_info;
+typedef struct sm_compare_stats_t {
+    uint32_t chunks;         /* pieces of at most 2^20 records, both sets together */
+    uint32_t launches;
+    float read_ms;           /* host: reading the files */
+    float table_ms;          /* device: the tables' initialisation (four memsets), inserts and representatives */
+    float classify_ms;       /* device: labels, ranks and kept records of the query's chunks */
+    float write_ms;          /* host: labels and kept records back from the device and into the file */
+    float total_ms;
+} sm_compare_stats_t;
+int sm_default_compare_params(sm_compare_params *p);         /* pure, no context */
+int sm_compare_maps(sm_ctx *s, const sm_map_source *query, const sm_map_source *reference, const float *pose16,
+                    const sm_compare_params *p, uint8_t *labels /* query records, by global id; may be NULL */,
+                    const char *out_path /* may be NULL */, sm_compare_info *info);
+int sm_compare_stats(sm_ctx *s, sm_compare_stats_t *out);
+
 /* ---- per-pass entry points (GlobalModel / IndexMap methods), synchronous ---- */
 /* Upload RGB / metric depth / semantic textures directly (bypasses p0). */
 int sm_set_frame(sm_ctx *s, const uint8_t *rgb, const float *depth_metric,

@@ -49,6 +49,7 @@ SYMBOLS = (
     "sm_default_blend_params", "sm_render_image_blend", "sm_render_image_maps_blend", "sm_blend_stats",
     "sm_default_simplify_params", "sm_simplify", "sm_simplify_maps", "sm_simplify_stats",
     "sm_default_register_params", "sm_register_maps", "sm_register_debug", "sm_register_stats",
+    "sm_default_compare_params", "sm_compare_maps", "sm_compare_stats",
 )
 
 SM_COLL_SUM, SM_COLL_MIN, SM_COLL_GATHER = 0, 1, 2
@@ -529,6 +530,56 @@ def register_params(**over) -> SmRegisterParams:
     return p
 
 
+SM_COMPARE_SUPPORTED, SM_COMPARE_CHANGED, SM_COMPARE_OUTSIDE, SM_COMPARE_LOOSE = 0, 1, 2, 3
+COMPARE_LABEL = {SM_COMPARE_SUPPORTED: "SUPPORTED", SM_COMPARE_CHANGED: "CHANGED", SM_COMPARE_OUTSIDE: "OUTSIDE", SM_COMPARE_LOOSE: "LOOSE"}
+
+
+class SmCompareParams(C.Structure):
+    _fields_ = [("voxel_mm", C.c_int32), ("cover_shift", C.c_int32), ("reach_cells", C.c_float), ("plane_mm", C.c_int32),
+                ("angle_thresh", C.c_float), ("match_class", C.c_int32), ("write_mask", C.c_uint32), ("max_cells", C.c_uint32),
+                ("origin", C.c_float * 3)]
+
+
+class SmCompareInfo(C.Structure):
+    _fields_ = [("counts", C.c_uint64 * 4), ("query_records", C.c_uint64), ("reference_records", C.c_uint64),
+                ("cells_fine", C.c_uint32), ("cells_cover", C.c_uint32), ("written", C.c_uint64)]
+
+
+class SmCompareStats(C.Structure):
+    _fields_ = [("chunks", C.c_uint32), ("launches", C.c_uint32), ("read_ms", C.c_float), ("table_ms", C.c_float),
+                ("classify_ms", C.c_float), ("write_ms", C.c_float), ("total_ms", C.c_float)]
+
+
+def _map_records(path) -> int:
+    """the records a well-formed map file of this length holds (12 bytes of header, 48 per record); 0 where there is no file --
+    the call that reads it reports that"""
+    try:
+        return max(0, (os.path.getsize(path) - 12) // 48)
+    except OSError:
+        return 0
+
+
+def default_compare_params() -> SmCompareParams:
+    """sm_default_compare_params: voxel_mm 100, cover_shift 3, reach_cells 2, plane_mm 50, angle_thresh 30, match_class 0,
+    write_mask 2 (the CHANGED records), max_cells 1 << 24, origin (0, 0, 0)"""
+    p = SmCompareParams()
+    load().sm_default_compare_params(C.byref(p))
+    return p
+
+
+def compare_params(**over) -> SmCompareParams:
+    """default_compare_params() with fields overridden; origin takes a sequence of three"""
+    p = default_compare_params()
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise KeyError(k)
+        if k == "origin":
+            p.origin[:] = [float(x) for x in v]
+        else:
+            setattr(p, k, v)
+    return p
+
+
 def search_params(**over) -> SmSearchParams:
     """sm_default_search_params (2 levels; +-2 m in x and z at 0.25 m, +-3 deg about y at 0.5 deg; refine 4, stride0 8, top_k 4,
     colour_thresh 0.1) with fields overridden; the four per-axis fields take a sequence of three"""
@@ -878,6 +929,10 @@ def load():
     L.sm_register_maps.argtypes = [vp, msp, msp, C.c_void_p, rgp, C.c_void_p, C.POINTER(SmRegisterInfo)]
     L.sm_register_debug.argtypes = [vp, msp, msp, C.c_void_p, C.c_int32, rgp, C.c_void_p, C.c_void_p]
     L.sm_register_stats.argtypes = [vp, C.POINTER(SmRegisterStats)]
+    cpp = C.POINTER(SmCompareParams)
+    L.sm_default_compare_params.argtypes = [cpp]
+    L.sm_compare_maps.argtypes = [vp, msp, msp, C.c_void_p, cpp, C.c_void_p, C.c_char_p, C.POINTER(SmCompareInfo)]
+    L.sm_compare_stats.argtypes = [vp, C.POINTER(SmCompareStats)]
     for name in SYMBOLS:
         getattr(L, name)          # AttributeError here = the library does not match the header
     _lib = L
@@ -1831,6 +1886,56 @@ class SurfelMap:
         st = SmRegisterStats()
         self._chk(self._L.sm_register_stats(self._h, C.byref(st)), "sm_register_stats")
         return {k: getattr(st, k) for k, _ in SmRegisterStats._fields_}
+
+    # -- change detection between two map sets (sm_compare_maps)
+    def compare_maps(self, query_paths, reference_paths, pose=None, query_model=False, reference_model=False, out_path=None, labels=True,
+                     **params):
+        """Which records of the map set `query_paths` (then, with query_model, the live model) does the set `reference_paths`
+        (reference_model likewise) hold the surface of (sm_compare_maps)?  pose: a 4x4 query-world to reference-world matrix or
+        float32[16] column-major, None = identity; params: the fields of compare_params().  out_path: the query records whose
+        label is in write_mask (default: the CHANGED ones) as one map file, verbatim and in set order.  Nothing else is changed.
+        Returns (uint8[query records] of COMPARE_LABEL codes by global id, or None with labels=False; info dict: counts by label
+        name, counts_by_code, query_records, reference_records, cells_fine, cells_cover, written)."""
+        p = compare_params(**params)
+        qry, ref = map_source(query_paths, include_model=query_model), map_source(reference_paths, include_model=reference_model)
+        g = None if pose is None else _mat16(pose)
+        info = SmCompareInfo()
+        lab = None
+        if labels:
+            # the records of the set are known from the headers; the live model's count from the context
+            n = sum(_map_records(q) for q in query_paths)
+            if query_model:
+                live = C.c_uint32()
+                self._chk(self._L.sm_download_model_aos(self._h, None, 0, C.byref(live)), "sm_download_model_aos")
+                n += live.value
+            lab = np.full(n, 255, np.uint8)
+        out = None if out_path is None else os.fsencode(out_path)
+        self._chk(self._L.sm_compare_maps(self._h, C.byref(qry), C.byref(ref), _ptr(g), C.byref(p), _ptr(lab), out, C.byref(info)), "sm_compare_maps")
+        codes = [int(v) for v in info.counts]
+        d = dict(counts={COMPARE_LABEL[l]: codes[l] for l in range(4)}, counts_by_code=codes, query_records=int(info.query_records),
+                 reference_records=int(info.reference_records), cells_fine=int(info.cells_fine), cells_cover=int(info.cells_cover),
+                 written=int(info.written))
+        if lab is not None and len(lab) != d["query_records"]:
+            raise SurfelMapError(SM_E_ARG, "compare_maps: the query set changed while it was compared")
+        return lab, d
+
+    def diff_maps(self, a_paths, b_paths, pose_a_to_b=None, out_appeared=None, out_vanished=None, **params):
+        """What appeared and what vanished between the map sets a (before) and b (after): compare_maps of b against a -- the
+        records of b that a does not hold, written to out_appeared -- and of a against b, written to out_vanished.
+        pose_a_to_b: a's world to b's (4x4 or float32[16] column-major, None = identity); the first call gets its inverse, taken
+        in float64 and rounded to float32.  Returns (info of b against a, info of a against b), each with its `labels`."""
+        fwd = None if pose_a_to_b is None else _mat16(pose_a_to_b)
+        inv = None if fwd is None else np.linalg.inv(fwd.astype(np.float64).reshape(4, 4).T).astype(np.float32)
+        lab_b, appeared = self.compare_maps(b_paths, a_paths, pose=inv, out_path=out_appeared, **params)
+        lab_a, vanished = self.compare_maps(a_paths, b_paths, pose=None if fwd is None else fwd, out_path=out_vanished, **params)
+        appeared["labels"], vanished["labels"] = lab_b, lab_a
+        return appeared, vanished
+
+    def compare_stats(self) -> dict:
+        """of the last compare_maps: chunks, launches, read_ms, table_ms, classify_ms, write_ms, total_ms"""
+        st = SmCompareStats()
+        self._chk(self._L.sm_compare_stats(self._h, C.byref(st)), "sm_compare_stats")
+        return {k: getattr(st, k) for k, _ in SmCompareStats._fields_}
 
     def simplify_stats(self) -> dict:
         """of the last simplify* call: records_in, records_out, cells_merged, loose, largest_cell, chunks, launches, device_ms,

@@ -325,6 +325,59 @@ public:
         return status;
     }
 
+    // Which records of the map set `queryFiles` does the set `referenceFiles` hold the surface of (sm_compare_maps; DESIGN.md "4r.
+    // Change detection")?  pose: query world -> reference world (registerMaps measures it).  outPath (may be empty): the query
+    // records whose label is in params->write_mask -- by default the CHANGED ones: the reference mapped the place, not this
+    // surface -- as one map file, verbatim and in set order.  params: null = the defaults.  Nothing else is changed.  Returns the
+    // CHANGED records, or -1 with the error printed.
+    long compareMaps(const std::vector<std::string> &queryFiles, const std::vector<std::string> &referenceFiles, const Eigen::Matrix4f &pose,
+                     const std::string &outPath, const sm_compare_params *params = nullptr, sm_compare_info *info = nullptr)
+    {
+        std::vector<const char *> qp, rp;
+        for (const std::string &f : queryFiles) qp.push_back(f.c_str());
+        for (const std::string &f : referenceFiles) rp.push_back(f.c_str());
+        const sm_map_source qry{qp.data(), (uint32_t)qp.size(), 0}, ref{rp.data(), (uint32_t)rp.size(), 0};
+        sm_compare_params p;
+        sm_default_compare_params(&p);
+        if (params) p = *params;
+        sm_compare_info got;
+        (void)sm_sync(ctx_);                                             // (SM_FACADE_ASYNC: frames may still be in flight)
+        if (sm_compare_maps(ctx_, &qry, &ref, pose.data(), &p, nullptr, outPath.empty() ? nullptr : outPath.c_str(), &got) != SM_OK) {
+            std::printf("compareMaps: %s\n", sm_last_error());
+            return -1;
+        }
+        if (info) *info = got;
+        return (long)got.counts[SM_COMPARE_CHANGED];
+    }
+    // What appeared and what vanished between the map sets a (before) and b (after): compareMaps of b against a, its CHANGED
+    // records -- b's surfaces that a does not hold -- to outAppeared, and of a against b to outVanished.  poseAToB: a's world to
+    // b's; the first call gets its inverse, taken in double and rounded to float.  Returns false with the error printed.
+    bool diffMaps(const std::vector<std::string> &aFiles, const std::vector<std::string> &bFiles, const Eigen::Matrix4f &poseAToB,
+                  const std::string &outAppeared, const std::string &outVanished, const sm_compare_params *params = nullptr,
+                  sm_compare_info *appeared = nullptr, sm_compare_info *vanished = nullptr)
+    {
+        // the inverse of [A | t], last row (0, 0, 0, 1): [A^-1 | -A^-1 t], A^-1 by cofactors
+        const float *f = poseAToB.data();
+        double a[3][3], c[3][3];
+        for (int r = 0; r < 3; ++r)
+            for (int k = 0; k < 3; ++k) a[r][k] = (double)f[k * 4 + r];
+        for (int r = 0; r < 3; ++r)
+            for (int k = 0; k < 3; ++k)
+                c[r][k] = a[(r + 1) % 3][(k + 1) % 3] * a[(r + 2) % 3][(k + 2) % 3] - a[(r + 1) % 3][(k + 2) % 3] * a[(r + 2) % 3][(k + 1) % 3];
+        const double det = a[0][0] * c[0][0] + a[0][1] * c[0][1] + a[0][2] * c[0][2];
+        Eigen::Matrix4f inv = Eigen::Matrix4f::Identity();
+        for (int r = 0; r < 3; ++r) {
+            double t = 0.0;
+            for (int k = 0; k < 3; ++k) {
+                inv.data()[k * 4 + r] = (float)(c[k][r] / det);
+                t -= (c[k][r] / det) * (double)f[12 + k];
+            }
+            inv.data()[12 + r] = (float)t;
+        }
+        return compareMaps(bFiles, aFiles, inv, outAppeared, params, appeared) >= 0 &&
+               compareMaps(aFiles, bFiles, poseAToB, outVanished, params, vanished) >= 0;
+    }
+
     // The second sensor's dump: what a lidar `sensor` (sm_lidar_sensor; sm_default_lidar_sensor) at each of `poses` (sensor->world,
     // the camera's axes) measures in the live model, written as <path>/velodyne/%06d.bin next to acquireImages' folders, in KITTI's
     // velodyne layout: per return four floats, (z, -x, -y) of t*d in the sensor frame -- x forward, y left, z up -- and the

@@ -20,9 +20,10 @@
 //   sm_blend.hip     blended views (sm_render_image_blend, sm_render_image_maps_blend): the visible layer's accumulation and normalisation, a stage of both render paths
 //   sm_simplify.hip  simplification (sm_simplify, sm_simplify_maps): the model or a map set merged per voxel cell, two passes over the records
 //   sm_register.hip  registration (sm_register_*): the rigid transform from one map set to another, voxel-cell ICP, one pass over each set
+//   sm_compare.hip   change detection (sm_compare_*): every record of one map set labelled against the voxel tables of another, one pass over each set
 // and, beside it, for everything that touches a map file: sm_mapfile.h (the format: checked open, writer, chunk plan; host only),
 // sm_map_set.h (a listed set of files: the file index, the two openings, a rewrite's per-file record and temporary; host only) and
-// sm_map_stream.h (the double-buffered chunk stream of sm_render_maps.hip, sm_lidar.hip, sm_recall.hip, sm_warp.hip, sm_simplify.hip and sm_register.hip).  The staging
+// sm_map_stream.h (the double-buffered chunk stream of sm_render_maps.hip, sm_lidar.hip, sm_recall.hip, sm_warp.hip, sm_simplify.hip, sm_register.hip and sm_compare.hip).  The staging
 // they stream through (MapStaging) and the file index (FileIndex) are the context's, no feature's.  For the occupied slots and the
 // compaction schedule: sm_slots.h (SlotSchedule; host only); for the arithmetic of rigid poses in double: sm_pose.h (host only,
 // included by sm_track.hip and sm_warp.hip).  What alternates between consecutive frames is FrameSet, below.
@@ -340,6 +341,24 @@ struct Register {
     bool stats_valid = false;
 };
 
+// change detection (sm_compare.hip, sm_k_compare.h): the scratch of one chunk of the query, the buffers its labels and kept records
+// leave through, the tallies and the last call's.  The tables live for one call.
+struct Compare {
+    Dev<uint8_t> d_label[2];           // per record of the chunk in buffer c & 1: its label
+    Dev<uint8_t> d_keep;               // per record of a chunk: 1 = its label is in the write mask
+    Dev<uint32_t> d_blk_cnt, d_blk_base;   // kept records per block of 256, their rank in the output
+    Dev<uint32_t> d_tally;             // the fine table's tally words (SIMP_RUN: the running rank), the cover table's, the label counts
+    Host<uint32_t> h_tally;            // pinned
+    Dev<uint2> d_info;                 // [2]: (first rank, kept records) of the chunk in buffer c & 1
+    Host<uint2> h_info;                // pinned, [2]
+    Host<uint8_t> h_label[2];          // pinned: a chunk's labels on their way to the caller
+    Dev<float4> d_out[2];              // the kept records of a chunk
+    size_t out_cap[2] = {0, 0};        // records
+    Event ev[6];                       // around the tables' memsets, the reference's model and the finish, a chunk of the query's model
+    sm_compare_stats_t stats{};
+    bool stats_valid = false;
+};
+
 // closing loops unasked (sm_loop.hip): the policy of sm_set_auto_loop and its tally
 struct AutoLoop {
     bool on = false;
@@ -591,6 +610,7 @@ struct sm_ctx {
     Timeline tl;
     Dev<FrameLog> d_log;
     Register reg;                      // (nothing depends on where it lies; behind the frame path's members, which keep their places)
+    Compare cmp;
 };
 
 namespace sm_impl __attribute__((visibility("hidden"))) {

@@ -1,6 +1,6 @@
 // sm_d_simplify.h -- the voxel-cell table of the simplification as device functions, for every source that fills or reads such
 // a table (sm_k_simplify.h; sm_k_register.h): the regular-record test, the key, a record's contribution, the probe, the
-// claim-and-add with its in-wave combination, and a cell's merged position, normal and record.  No kernels: a kernel is
+// claim-and-add with its in-wave combination, a cell's merged position, normal and record, and the ranks of pass 2.  No kernels: a kernel is
 // defined in the one header of the source that launches it.
 #pragma once
 
@@ -260,6 +260,32 @@ __device__ __forceinline__ void simp_finish(const SimplifyArgs &a, const Simplif
     nr.w = (float)((double)R * (1.0 / 65536.0));
     pc = make_float4(p[0], p[1], p[2], __uint_as_float(T.conf_max[sl]));
     ct = make_float4(__uint_as_float(col), 0.0f, __uint_as_float(T.init_min[sl]), __uint_as_float(T.time_max[sl]));
+}
+
+// Pass 2's ranks, by one workgroup of 1024 (all of its lanes call it): blk_base[b] = the running rank tally[SIMP_RUN] plus the
+// exclusive prefix of blk_cnt, the running rank moved on by their sum; info (may be null): (this call's first rank, its count)
+__device__ __forceinline__ void simp_scan_ranks(const uint32_t *__restrict__ blk_cnt, uint32_t nblk, uint32_t *__restrict__ blk_base,
+                                                uint32_t *__restrict__ tally, uint2 *__restrict__ info)
+{
+    __shared__ uint32_t s_scan[17];
+    __shared__ uint32_t s_run;
+    if (threadIdx.x == 0) s_run = tally[SIMP_RUN];
+    __syncthreads();
+    const uint32_t run0 = s_run;
+    uint32_t run = run0;
+    for (uint32_t b = 0; b < nblk; b += 1024u) {
+        const uint32_t i = b + threadIdx.x;
+        const uint32_t v = i < nblk ? blk_cnt[i] : 0u;
+        uint32_t tot;
+        const uint32_t excl = block_scan_1024(v, &tot, s_scan);
+        if (i < nblk) blk_base[i] = run + excl;
+        run += tot;
+        __syncthreads();                                 // (s_scan is written again)
+    }
+    if (threadIdx.x == 0) {
+        tally[SIMP_RUN] = run;
+        if (info) *info = make_uint2(run0, run - run0);
+    }
 }
 
 }  // namespace sm

@@ -14,18 +14,13 @@
 // No lane waits for another: a probe walk ends at the key, at an empty slot or after mask + 1 slots.
 #pragma once
 
-#include "sm_d_simplify.h"
+#include "sm_d_register.h"
 #include "sm_d_track.h"
 
 namespace sm {
 
 constexpr int REG_MAX_LEVELS = 4;
 enum { REG_OK = 0, REG_LOST = 1, REG_DEGENERATE = 2, REG_NO_TARGET = 3, REG_NO_SOURCE = 4 };
-
-struct alignas(32) RegCell {
-    unsigned long long key;            // SIMP_EMPTY: the slot holds none
-    float p[3], n[3];
-};
 
 struct RegLevel {
     const RegCell *lut;
@@ -79,22 +74,7 @@ __global__ __launch_bounds__(256) void k_register_finish(SimplifyArgs a, Simplif
 {
     const uint32_t sl = blockIdx.x * 256u + threadIdx.x;
     if (sl > T.mask) return;
-    const size_t S = (size_t)T.mask + 1u;
-    RegCell c;
-    c.key = T.key[sl];
-    c.p[0] = c.p[1] = c.p[2] = 0.0f;
-    c.n[0] = c.n[1] = c.n[2] = 0.0f;
-    if (c.key != SIMP_EMPTY) {
-        const unsigned long long SW = T.SW[sl];
-        long long sn[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            c.p[k] = simp_merged_pos(a, c.key, k, SW, T.SP[k * S + sl]);
-            sn[k] = (long long)T.SN[k * S + sl];
-        }
-        simp_merged_normal(sn, c.n);                     // (all three zero: n stays (0, 0, 0))
-    }
-    lut[sl] = c;
+    lut[sl] = reg_cell_of(a, T, sl);
 }
 
 // ---- the source's samples: pos.w = 1 regular, 0 not ----
@@ -126,28 +106,12 @@ __device__ __forceinline__ bool reg_pair(uint32_t i, const double *T, const RegP
     const float4 pf = pos[i];
     if (pf.w == 0.0f) return false;
     const float4 nf = nrm[i];
-    const double p0 = pf.x, p1 = pf.y, p2 = pf.z, n0 = nf.x, n1 = nf.y, n2 = nf.z;
     double q[3], nq[3];
+    reg_move(T, pf, nf, q, nq);
+    long long cell[3][2];              // the cell and its neighbour towards q
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        q[k] = ((T[k] * p0 + T[4 + k] * p1) + T[8 + k] * p2) + T[12 + k];
-        nq[k] = (T[k] * n0 + T[4 + k] * n1) + T[8 + k] * n2;
-    }
-    long long cell[3][2];              // the cell and its neighbour towards q; -1 << 40: no such cell
-    constexpr long long NO_CELL = -(1ll << 40);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double d = q[k] - (double)rp.origin[k];
-        if (!(fabs(d) < 16777216.0)) return false;
-        const long long X = (long long)floor(d * 65536.0);
-        long long c = X / L.V;
-        if (X - c * L.V < 0) --c;                        // floor division
-        if (c < -65536 || c > 65535) return false;
-        const long long off = X - c * L.V;
-        const long long nb = 2 * off >= L.V ? c + 1 : c - 1;
-        cell[k][0] = c;
-        cell[k][1] = (nb < -65536 || nb > 65535) ? NO_CELL : nb;
-    }
+    for (int k = 0; k < 3; ++k)
+        if (!reg_cells(q[k], rp.origin[k], L.V, cell[k][0], cell[k][1])) return false;
     int ax = 0;
     if (fabs(nq[1]) > fabs(nq[ax])) ax = 1;
     if (fabs(nq[2]) > fabs(nq[ax])) ax = 2;
@@ -158,10 +122,8 @@ __device__ __forceinline__ bool reg_pair(uint32_t i, const double *T, const RegP
     uint32_t sl[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        const long long cx = cell[0][j & 1], cy = cell[1][(j >> 1) & 1], cz = cell[2][j >> 2];
-        const bool valid = cx != NO_CELL && cy != NO_CELL && cz != NO_CELL;
-        const unsigned long long k3 = ((unsigned long long)(cx + 65536) << 34) | ((unsigned long long)(cy + 65536) << 17) | (unsigned long long)(cz + 65536);
-        ck[j] = valid ? (k3 << 11) | (face << 8) : SIMP_EMPTY;
+        bool valid;
+        ck[j] = reg_candidate(cell, j, face << 8, valid);
         sl[j] = (uint32_t)simp_hash(ck[j]) & L.mask;
         cur[j] = valid ? L.lut[sl[j]].key : SIMP_EMPTY;
     }

@@ -72,25 +72,7 @@ __global__ __launch_bounds__(256) void k_simplify_flag(const float4 *__restrict_
 __global__ __launch_bounds__(1024) void k_simplify_scan(const uint32_t *__restrict__ blk_cnt, uint32_t nblk, uint32_t *__restrict__ blk_base,
                                                         uint32_t *__restrict__ tally, uint2 *__restrict__ info)
 {
-    __shared__ uint32_t s_scan[17];
-    __shared__ uint32_t s_run;
-    if (threadIdx.x == 0) s_run = tally[SIMP_RUN];
-    __syncthreads();
-    const uint32_t run0 = s_run;
-    uint32_t run = run0;
-    for (uint32_t b = 0; b < nblk; b += 1024u) {
-        const uint32_t i = b + threadIdx.x;
-        const uint32_t v = i < nblk ? blk_cnt[i] : 0u;
-        uint32_t tot;
-        const uint32_t excl = block_scan_1024(v, &tot, s_scan);
-        if (i < nblk) blk_base[i] = run + excl;
-        run += tot;
-        __syncthreads();                                 // (s_scan is written again)
-    }
-    if (threadIdx.x == 0) {
-        tally[SIMP_RUN] = run;
-        if (info) *info = make_uint2(run0, run - run0);
-    }
+    simp_scan_ranks(blk_cnt, nblk, blk_base, tally, info);
 }
 
 // out[(rank - base) * 3 ..]: base = info->x (a chunk's output begins at out), 0 without info (out is the whole output)

@@ -1,4 +1,4 @@
-// sm_map_stream.h -- private to sm_render_maps.hip, sm_lidar.hip, sm_recall.hip, sm_warp.hip, sm_simplify.hip and sm_register.hip: the double-buffered stream of
+// sm_map_stream.h -- private to sm_render_maps.hip, sm_lidar.hip, sm_recall.hip, sm_warp.hip, sm_simplify.hip, sm_register.hip and sm_compare.hip: the double-buffered stream of
 // map-file chunks through the context's MapStaging, one object per call; behind it what the two readers of whole sets (the
 // streamed renderers, the lidar) do alike: the opening (maps_open) and the batch of views (maps_batch).  Chunk c of a pass goes
 // through buffer q = c & 1: read into h_rec[q] (timed into read_ms), copied on `copy` into d_rec[q], and the context's stream

@@ -21,6 +21,7 @@
 //   sm_simplify.hip  simplification (sm_simplify, sm_simplify_maps): the model or a map set merged per voxel cell, two passes over the records
 //   sm_register.hip  registration (sm_register_*): the rigid transform from one map set to another, voxel-cell ICP, one pass over each set
 //   sm_compare.hip   change detection (sm_compare_*): every record of one map set labelled against the voxel tables of another, one pass over each set
+//   sm_voxel.hip     what those three share (sm_voxel.h): the grid, the slot count and the tally's verdict; the lookup table; the ranked output
 // and, beside it, for everything that touches a map file: sm_mapfile.h (the format: checked open, writer, chunk plan; host only),
 // sm_map_set.h (a listed set of files: the file index, the two openings, a rewrite's per-file record and temporary; host only) and
 // sm_map_stream.h (the double-buffered chunk stream of sm_render_maps.hip, sm_lidar.hip, sm_recall.hip, sm_warp.hip, sm_simplify.hip, sm_register.hip and sm_compare.hip).  The staging
@@ -313,16 +314,22 @@ struct Blend {
     bool stats_valid = false;
 };
 
-// simplification (sm_simplify.hip, sm_k_simplify.h): the scratch of one chunk's second pass, the output buffers, the last call's
-// tally.  The table lives for one call.
+// The scratch of a pass that keeps some records of every chunk and writes them, in order, to one output (sm_voxel.h's
+// RankedOutput: simplification's second pass, change detection's query), allocated by the first such call.  Calls on one context
+// never overlap, so they share it.
+struct RankScratch {
+    Dev<uint32_t> d_blk_cnt, d_blk_base;   // kept records per block of 256 records of a chunk, their rank in the output
+    Dev<uint2> d_info;                 // [2]: (first rank, kept records) of the chunk in buffer c & 1
+    Host<uint2> h_info;                // pinned, [2]
+    Dev<float4> d_out[2];              // the kept records of a chunk (sm_simplify: [0] holds the whole output)
+    size_t out_cap[2] = {0, 0};        // records
+};
+
+// simplification (sm_simplify.hip, sm_k_simplify.h): the scratch of one chunk's second pass beside the context's RankScratch, the
+// last call's tally.  The table lives for one call.
 struct Simplify {
     Dev<uint32_t> d_code;              // per record of a chunk: not a representative | loose | its cell's slot
-    Dev<uint32_t> d_blk_cnt, d_blk_base;   // representatives per block of 256 records, their rank in the output
     Dev<uint32_t> d_tally;             // error word | distinct cells | running rank | loose | merged | largest
-    Dev<uint2> d_info;                 // [2]: (first rank, representatives) of the chunk in buffer c & 1
-    Host<uint2> h_info;                // pinned, [2]
-    Dev<float4> d_out[2];              // the finished records of a chunk (sm_simplify: [0] holds the whole output)
-    size_t out_cap[2] = {0, 0};        // records
     Event ev[2];                       // around what runs outside a chunk stream
     sm_simplify_stats_t stats{};
     bool stats_valid = false;
@@ -341,19 +348,14 @@ struct Register {
     bool stats_valid = false;
 };
 
-// change detection (sm_compare.hip, sm_k_compare.h): the scratch of one chunk of the query, the buffers its labels and kept records
-// leave through, the tallies and the last call's.  The tables live for one call.
+// change detection (sm_compare.hip, sm_k_compare.h): the scratch of one chunk of the query beside the context's RankScratch, the
+// buffers its labels leave through, the tallies and the last call's.  The tables live for one call.
 struct Compare {
     Dev<uint8_t> d_label[2];           // per record of the chunk in buffer c & 1: its label
     Dev<uint8_t> d_keep;               // per record of a chunk: 1 = its label is in the write mask
-    Dev<uint32_t> d_blk_cnt, d_blk_base;   // kept records per block of 256, their rank in the output
     Dev<uint32_t> d_tally;             // the fine table's tally words (SIMP_RUN: the running rank), the cover table's, the label counts
     Host<uint32_t> h_tally;            // pinned
-    Dev<uint2> d_info;                 // [2]: (first rank, kept records) of the chunk in buffer c & 1
-    Host<uint2> h_info;                // pinned, [2]
     Host<uint8_t> h_label[2];          // pinned: a chunk's labels on their way to the caller
-    Dev<float4> d_out[2];              // the kept records of a chunk
-    size_t out_cap[2] = {0, 0};        // records
     Event ev[6];                       // around the tables' memsets, the reference's model and the finish, a chunk of the query's model
     sm_compare_stats_t stats{};
     bool stats_valid = false;
@@ -611,6 +613,7 @@ struct sm_ctx {
     Dev<FrameLog> d_log;
     Register reg;                      // (nothing depends on where it lies; behind the frame path's members, which keep their places)
     Compare cmp;
+    RankScratch ranked;
 };
 
 namespace sm_impl __attribute__((visibility("hidden"))) {
@@ -619,6 +622,18 @@ template <typename T>
 int dalloc(Dev<T> &p, size_t n)
 {
     HIPCK(hipMalloc(p.put(), std::max<size_t>(n, 1) * sizeof(T)));
+    return SM_OK;
+}
+
+// A timed stretch of the context's stream between the events pair[0] and pair[1]: mark() records one of them, add_marked() waits
+// for the second and adds the stretch to *ms_sum.
+inline int mark(sm_ctx *s, const Event &e) { HIPCK(hipEventRecord(e, s->stream)); return SM_OK; }
+inline int add_marked(const Event *pair, float *ms_sum)
+{
+    float ms = 0.0f;
+    HIPCK(hipEventSynchronize(pair[1]));
+    HIPCK(hipEventElapsedTime(&ms, pair[0], pair[1]));
+    *ms_sum += ms;
     return SM_OK;
 }
 

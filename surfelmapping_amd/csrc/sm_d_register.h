@@ -1,8 +1,8 @@
 // sm_d_register.h -- a voxel table read through one lookup record per slot, as device functions, for every source that looks
 // records of one map set up in the table of another (sm_k_register.h; sm_k_compare.h): the lookup record and how a slot's sums
-// become it, a record moved by a pose, the cell of the moved point with its neighbour towards the point, a candidate's key.  The
-// table itself, its keys and its sums are the simplification's (sm_d_simplify.h).  No kernels: a kernel is defined in the one
-// header of the source that launches it.
+// become it, a record moved by a pose, the cell of the moved point with its neighbour towards the point, a candidate's key, the
+// lookup of the eight candidates.  The table itself, its keys and its sums are sm_d_simplify.h's; the kernels that fill and
+// finish it are sm_k_voxel.h's.  No kernels: a kernel is defined in the one header of the source that launches it.
 #pragma once
 
 #include "sm_d_simplify.h"
@@ -72,6 +72,34 @@ __device__ __forceinline__ unsigned long long reg_candidate(const long long cell
     valid = cx != REG_NO_CELL && cy != REG_NO_CELL && cz != REG_NO_CELL;
     const unsigned long long k3 = ((unsigned long long)(cx + 65536) << 34) | ((unsigned long long)(cy + 65536) << 17) | (unsigned long long)(cz + 65536);
     return valid ? (k3 << 11) | low : SIMP_EMPTY;
+}
+
+// The eight candidates of `cell` with the low key bits `low` looked up in a table of mask + 1 slots whose slot s holds the key
+// key_at(s): hit(j, key, slot) for every candidate that is there.  Every first probe is on its way before one is looked at; a
+// walk ends at the key, at an empty slot or after mask + 1 slots, so no lane waits for another.
+template <typename KeyAt, typename Hit>
+__device__ __forceinline__ void reg_lookup8(const long long cell[3][2], unsigned long long low, uint32_t mask, KeyAt key_at, Hit hit)
+{
+    unsigned long long ck[8], cur[8];
+    uint32_t sl[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        bool valid;
+        ck[j] = reg_candidate(cell, j, low, valid);
+        sl[j] = (uint32_t)simp_hash(ck[j]) & mask;
+        cur[j] = valid ? key_at(sl[j]) : SIMP_EMPTY;
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        unsigned long long c = cur[j];
+        uint32_t s = sl[j];
+        for (uint32_t w = 0; w <= mask; ++w) {           // (at most the table's slots)
+            if (c == SIMP_EMPTY) break;
+            if (c == ck[j]) { hit(j, ck[j], s); break; }
+            s = (s + 1u) & mask;
+            c = key_at(s);
+        }
+    }
 }
 
 }  // namespace sm

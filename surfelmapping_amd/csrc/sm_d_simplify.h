@@ -1,7 +1,8 @@
-// sm_d_simplify.h -- the voxel-cell table of the simplification as device functions, for every source that fills or reads such
-// a table (sm_k_simplify.h; sm_k_register.h): the regular-record test, the key, a record's contribution, the probe, the
-// claim-and-add with its in-wave combination, a cell's merged position, normal and record, and the ranks of pass 2.  No kernels: a kernel is
-// defined in the one header of the source that launches it.
+// sm_d_simplify.h -- the voxel-cell table as device functions, for every source that fills or reads such a table (sm_k_simplify.h;
+// sm_k_voxel.h; through sm_d_register.h, sm_k_register.h and sm_k_compare.h): the regular-record test, the key, a record's
+// contribution, the probe, the insert in its pieces -- head of a run, in-wave combination, claim, adds --, a cell's merged
+// position, normal and record, and the ranks of a pass that writes.  No kernels: a kernel is defined in the one header of the
+// source that launches it.
 #pragma once
 
 #include "sm_device.h"
@@ -147,64 +148,83 @@ __device__ __forceinline__ bool simp_probe(const SimplifyTable &T, unsigned long
     return false;
 }
 
-// What pass 1 does with a lane's key and contribution once they are known (all 64 lanes of a wave call it; reg: the lane has one):
-// the in-wave combination, the claim and the adds.  FULL: every accumulator of the table; otherwise the planes a cell's merged
-// position and normal are made of -- SW, SP, SN -- and no others (sm_k_register.h, whose tables have only those).
-template <bool FULL>
-__device__ __forceinline__ void simp_insert(const SimplifyArgs &a, const SimplifyTable &T, unsigned long long key, bool reg, SimpContrib &c)
+// What pass 1 does with a lane's key once it is known, in pieces; all 64 lanes of a wave call each (reg: the lane has a key).
+// Is this lane the first of its run of equal keys?  Every regular lane is without `combine`.  A table of keys only has nothing
+// to combine and stops here.
+__device__ __forceinline__ bool simp_head(const SimplifyArgs &a, unsigned long long key, bool reg)
+{
+    if (!a.combine) return reg;
+    const unsigned long long prev = __shfl_up(key, 1);
+    return reg && !((threadIdx.x & 63) > 0 && prev == key);
+}
+
+// The in-wave combination: a head's contribution becomes the sum of its run's (a segmented shuffle reduction); returns simp_head
+__device__ __forceinline__ bool simp_combine(const SimplifyArgs &a, unsigned long long key, bool reg, SimpContrib &c)
 {
     const int lane = threadIdx.x & 63;
-    bool head = reg;
-    if (a.combine) {
-        const unsigned long long prev = __shfl_up(key, 1);
-        const bool follows = reg && lane > 0 && prev == key;
-        if (__ballot(follows)) {                         // wave-uniform: some run in this wave is longer than one lane
-            head = reg && !follows;
-            const unsigned long long bounds = __ballot(!follows);                // first lanes of runs, and every lane without a key
-            const unsigned long long above = lane == 63 ? 0ull : bounds >> (lane + 1);
-            const int last = above ? lane + __ffsll(above) - 1 : 63;             // the last lane of this lane's run
-            for (int o = 1; o < 64; o <<= 1) {
-                const bool take = lane + o <= last;
-                if (!__ballot(take)) break;
-                simp_take(c, o, take);
-            }
+    const bool head = simp_head(a, key, reg);
+    if (__ballot(reg && !head)) {                        // wave-uniform: some run in this wave is longer than one lane
+        const unsigned long long bounds = __ballot(head || !reg);                // first lanes of runs, and every lane without a key
+        const unsigned long long above = lane == 63 ? 0ull : bounds >> (lane + 1);
+        const int last = above ? lane + __ffsll(above) - 1 : 63;                 // the last lane of this lane's run
+        for (int o = 1; o < 64; o <<= 1) {
+            const bool take = lane + o <= last;
+            if (!__ballot(take)) break;
+            simp_take(c, o, take);
         }
     }
+    return head;
+}
+
+// The claim: a head finds its key's slot or claims an empty one and adds(slot) what it has for it -- atomics without a return
+// value, issued before this step waits for one of its own; then the distinct cells go to the tally, one add per wave, and with
+// them the error bits (1: more than max_cells cells, 2: no slot)
+template <typename Adds>
+__device__ __forceinline__ void simp_claim(const SimplifyArgs &a, const SimplifyTable &T, unsigned long long key, bool head, Adds adds)
+{
+    const int lane = threadIdx.x & 63;
     bool claimed = false, lost = false;
     if (head) {
         uint32_t sl = 0;
-        if (simp_probe(T, key, true, sl, claimed)) {
-            const size_t S = (size_t)T.mask + 1u;
-            if constexpr (FULL) atomicAdd(&T.n[sl], c.n);
-            atomicAdd(&T.SW[sl], c.sw);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                atomicAdd(&T.SP[k * S + sl], c.sp[k]);
-                atomicAdd(&T.SN[k * S + sl], (unsigned long long)c.sn[k]);
-                if constexpr (FULL) {
-                    atomicAdd(&T.SC[k * S + sl], c.sc[k]);
-                    atomicMin(&T.lo[k * S + sl], c.lo[k]);
-                    atomicMax(&T.hi[k * S + sl], c.hi[k]);
-                }
-            }
-            if constexpr (FULL) {
-                atomicMax(&T.rmax[sl], c.rmax);
-                atomicMax(&T.conf_max[sl], c.conf);
-                atomicMax(&T.time_max[sl], c.time);
-                atomicMin(&T.init_min[sl], c.init);
-                atomicMin(&T.first[sl], c.first);
-            }
-        } else {
-            lost = true;
-        }
+        if (simp_probe(T, key, true, sl, claimed)) adds(sl);
+        else lost = true;
     }
-    // the distinct cells, one add per wave
     const unsigned long long cb = __ballot(claimed);
     if (cb && lane == __ffsll(cb) - 1) {
         const uint32_t m = (uint32_t)__popcll(cb);
         if (atomicAdd(&T.tally[SIMP_CELLS], m) + m > a.max_cells) atomicOr(&T.tally[SIMP_ERR], 1u);
     }
     if (lost) atomicOr(&T.tally[SIMP_ERR], 2u);
+}
+
+// The combination, then the claim with the adds.  FULL: every accumulator of the table; otherwise the planes a cell's merged
+// position and normal are made of -- SW, SP, SN -- and no others (the lookup tables of sm_k_voxel.h, which have only those).
+template <bool FULL>
+__device__ __forceinline__ void simp_insert(const SimplifyArgs &a, const SimplifyTable &T, unsigned long long key, bool reg, SimpContrib &c)
+{
+    const bool head = simp_combine(a, key, reg, c);
+    simp_claim(a, T, key, head, [&](uint32_t sl) {
+        const size_t S = (size_t)T.mask + 1u;
+        if constexpr (FULL) atomicAdd(&T.n[sl], c.n);
+        atomicAdd(&T.SW[sl], c.sw);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            atomicAdd(&T.SP[k * S + sl], c.sp[k]);
+            atomicAdd(&T.SN[k * S + sl], (unsigned long long)c.sn[k]);
+            if constexpr (FULL) {
+                atomicAdd(&T.SC[k * S + sl], c.sc[k]);
+                atomicMin(&T.lo[k * S + sl], c.lo[k]);
+                atomicMax(&T.hi[k * S + sl], c.hi[k]);
+            }
+        }
+        if constexpr (FULL) {
+            atomicMax(&T.rmax[sl], c.rmax);
+            atomicMax(&T.conf_max[sl], c.conf);
+            atomicMax(&T.time_max[sl], c.time);
+            atomicMin(&T.init_min[sl], c.init);
+            atomicMin(&T.first[sl], c.first);
+        }
+    });
 }
 
 __device__ __forceinline__ unsigned long long simp_isqrt(unsigned long long v)
@@ -286,6 +306,22 @@ __device__ __forceinline__ void simp_scan_ranks(const uint32_t *__restrict__ blk
         tally[SIMP_RUN] = run;
         if (info) *info = make_uint2(run0, run - run0);
     }
+}
+
+// The rank of a lane's record in its chunk's output, by a workgroup of 256 (all of its lanes call it; kept: the lane has a record
+// that stays): blk_base of the block, less the chunk's first rank info->x (no info: the output is the whole call's), plus the
+// kept lanes below this one
+__device__ __forceinline__ uint32_t simp_rank_in_chunk(bool kept, const uint32_t *__restrict__ blk_base, const uint2 *__restrict__ info)
+{
+    __shared__ uint32_t s_cnt[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long m = __ballot(kept);
+    if (lane == 0) s_cnt[wave] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (!kept) return 0u;
+    uint32_t rank = blk_base[blockIdx.x] - (info ? info->x : 0u) + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    for (int x = 0; x < wave; ++x) rank += s_cnt[x];
+    return rank;
 }
 
 }  // namespace sm

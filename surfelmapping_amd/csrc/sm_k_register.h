@@ -1,11 +1,7 @@
 // sm_k_register.h -- registration of one map set against another (DESIGN.md "4q. Registration"; the specification is
-// sm_c_api.h's "sm_register_maps").  Included by sm_register.hip only.  The table, the claim-and-add and the merged position and
-// normal are the simplification's (sm_d_simplify.h); the 29-value system, its fixed-order sums and the solve are the trackers'
+// sm_c_api.h's "sm_register_maps").  Included by sm_register.hip only.  The target's tables are lookup tables, filled and finished
+// by sm_voxel.hip; their lookup is sm_d_register.h's; the 29-value system, its fixed-order sums and the solve are the trackers'
 // (sm_d_track.h).
-//   k_register_insert  per level and chunk of the target: every regular record's key, with the class taken as 0, into the level's
-//                      table and its SW, SP, SN into the key's sums (simp_insert<false>: the in-wave combination, then atomics)
-//   k_register_finish  one lane per slot: the sums become the lookup record -- key, position, normal in 32 aligned bytes, so a
-//                      probe that hits has the representative in the line it has just read
 //   k_register_gather  per chunk of the source: record id goes to sample id / stride if stride divides it (no scan)
 //   k_register_reduce  one lane per sample: the moved point, its eight candidate keys, their first probes issued together, the
 //                      nearest representative, the gates, the 28 float32 products into fp64 sums; track_block_sum per workgroup
@@ -52,31 +48,6 @@ struct RegState {
     uint32_t inliers, pad;
 };
 
-// ---- the target's tables ----
-
-__global__ __launch_bounds__(256) void k_register_insert(const float4 *__restrict__ rec, uint32_t n, SimplifyArgs a, SimplifyTable T)
-{
-    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    unsigned long long key = SIMP_EMPTY;
-    bool reg = false;
-    SimpContrib c{};
-    if (t < n) {
-        const float4 pc = rec[(size_t)t * 3], ct = rec[(size_t)t * 3 + 1], nr = rec[(size_t)t * 3 + 2];
-        uint32_t off[3];
-        reg = simp_classify(a, pc, ct, nr, key, off);
-        if (reg) { simp_contribution(pc, ct, nr, off, 0u, c); key &= ~0xFFull; }
-        else key = SIMP_EMPTY;
-    }
-    simp_insert<false>(a, T, key, reg, c);
-}
-
-__global__ __launch_bounds__(256) void k_register_finish(SimplifyArgs a, SimplifyTable T, RegCell *__restrict__ lut)
-{
-    const uint32_t sl = blockIdx.x * 256u + threadIdx.x;
-    if (sl > T.mask) return;
-    lut[sl] = reg_cell_of(a, T, sl);
-}
-
 // ---- the source's samples: pos.w = 1 regular, 0 not ----
 
 __global__ __launch_bounds__(256) void k_register_gather(const float4 *__restrict__ rec, uint32_t n, uint32_t gid0, uint32_t stride,
@@ -117,40 +88,20 @@ __device__ __forceinline__ bool reg_pair(uint32_t i, const double *T, const RegP
     if (fabs(nq[2]) > fabs(nq[ax])) ax = 2;
     const unsigned long long face = 2ull * (unsigned long long)ax + (nq[ax] < 0.0 ? 1ull : 0ull);
 
-    // the eight candidates: every first probe is on its way before one is looked at
-    unsigned long long ck[8], cur[8];
-    uint32_t sl[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        bool valid;
-        ck[j] = reg_candidate(cell, j, face << 8, valid);
-        sl[j] = (uint32_t)simp_hash(ck[j]) & L.mask;
-        cur[j] = valid ? L.lut[sl[j]].key : SIMP_EMPTY;
-    }
+    // the nearest representative among the eight candidates; of two equally near the one with the smaller key
     double best = 0.0, e[3] = {0.0, 0.0, 0.0};
     float nc[3] = {0.0f, 0.0f, 0.0f};
     unsigned long long best_key = SIMP_EMPTY;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        unsigned long long c = cur[j];
-        uint32_t s = sl[j];
-        bool hit = false;
-        for (uint32_t w = 0; w <= L.mask; ++w) {         // (at most the table's slots)
-            if (c == SIMP_EMPTY) break;
-            if (c == ck[j]) { hit = true; break; }
-            s = (s + 1u) & L.mask;
-            c = L.lut[s].key;
-        }
-        if (!hit) continue;
+    reg_lookup8(cell, face << 8, L.mask, [&](uint32_t s) { return L.lut[s].key; }, [&](int, unsigned long long key, uint32_t s) {
         const RegCell &rc = L.lut[s];
         const double e0 = q[0] - (double)rc.p[0], e1 = q[1] - (double)rc.p[1], e2 = q[2] - (double)rc.p[2];
         const double d2 = (e0 * e0 + e1 * e1) + e2 * e2;
-        if (best_key == SIMP_EMPTY || d2 < best || (d2 == best && ck[j] < best_key)) {
-            best = d2; best_key = ck[j];
+        if (best_key == SIMP_EMPTY || d2 < best || (d2 == best && key < best_key)) {
+            best = d2; best_key = key;
             e[0] = e0; e[1] = e1; e[2] = e2;
             nc[0] = rc.n[0]; nc[1] = rc.n[1]; nc[2] = rc.n[2];
         }
-    }
+    });
     if (best_key == SIMP_EMPTY) return false;
     if (!(sqrt(best) <= L.reach)) return false;
     const double m0 = nc[0], m1 = nc[1], m2 = nc[2];

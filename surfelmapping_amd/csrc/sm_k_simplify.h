@@ -1,5 +1,6 @@
 // sm_k_simplify.h -- voxel-cell simplification (DESIGN.md "4p. Simplification"; the specification is sm_c_api.h's "sm_simplify").
-// Included by sm_simplify.hip only; the table and what fills and reads it are sm_d_simplify.h's, which sm_k_register.h shares.
+// Included by sm_simplify.hip only; the table and what fills and reads it are sm_d_simplify.h's, which the lookup tables share
+// (sm_k_voxel.h); between flag and emit sm_voxel.hip ranks the representatives.
 // Records come as 48-byte AoS rows (three float4), a chunk of a map file or the exported model.
 //   k_simplify_insert  pass 1: per regular record the key into the open-addressing table (64-bit atomicCAS, a probe loop bounded
 //                      by the table size) and the contribution into the key's accumulators (integer atomics, no return value).
@@ -7,8 +8,7 @@
 //                      are summed by a segmented shuffle reduction first and only the run's first lane goes to memory.
 //   k_simplify_flag    pass 2: per record its code (not a representative | loose | the slot of the cell it is `first` of), the
 //                      representatives per block of 256, and the call's tallies (one atomic per wave)
-//   k_simplify_scan    exclusive prefix of the per-block counts on top of the running rank (one workgroup, block_scan_1024)
-//   k_simplify_emit    every representative writes its finished record at its rank: three 16-byte stores
+//   k_simplify_emit    every representative writes its finished record at its rank (simp_rank_in_chunk): three 16-byte stores
 // No kernel waits for another lane: the accumulators are initialised before pass 1 starts (two memsets), so a claimed key can be
 // added to at once, and a key that finds no slot sets the sticky error word and gives up.
 #pragma once
@@ -68,28 +68,15 @@ __global__ __launch_bounds__(256) void k_simplify_flag(const float4 *__restrict_
     if (threadIdx.x == 0) blk_cnt[blockIdx.x] = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
 }
 
-// blk_base[b] = the rank of block b's first representative in the whole output; info (may be null): (this call's first rank, its count)
-__global__ __launch_bounds__(1024) void k_simplify_scan(const uint32_t *__restrict__ blk_cnt, uint32_t nblk, uint32_t *__restrict__ blk_base,
-                                                        uint32_t *__restrict__ tally, uint2 *__restrict__ info)
-{
-    simp_scan_ranks(blk_cnt, nblk, blk_base, tally, info);
-}
-
 // out[(rank - base) * 3 ..]: base = info->x (a chunk's output begins at out), 0 without info (out is the whole output)
 __global__ __launch_bounds__(256) void k_simplify_emit(const float4 *__restrict__ rec, uint32_t n, SimplifyArgs a, SimplifyTable T,
                                                        const uint32_t *__restrict__ code, const uint32_t *__restrict__ blk_base,
                                                        const uint2 *__restrict__ info, float4 *__restrict__ out)
 {
-    __shared__ uint32_t s_cnt[4];
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t c = t < n ? code[t] : SIMP_NONE;
-    const unsigned long long reps = __ballot(c != SIMP_NONE);
-    if (lane == 0) s_cnt[wave] = (uint32_t)__popcll(reps);
-    __syncthreads();
+    const uint32_t rank = simp_rank_in_chunk(c != SIMP_NONE, blk_base, info);
     if (c == SIMP_NONE) return;
-    uint32_t rank = blk_base[blockIdx.x] - (info ? info->x : 0u) + (uint32_t)__popcll(reps & ((1ull << lane) - 1ull));
-    for (int x = 0; x < wave; ++x) rank += s_cnt[x];
     float4 pc = rec[(size_t)t * 3], ct = rec[(size_t)t * 3 + 1], nr = rec[(size_t)t * 3 + 2];
     if (c != SIMP_LOOSE && T.n[c] >= 2u) simp_finish(a, T, c, nr, pc, ct, nr);
     out[(size_t)rank * 3] = pc;

@@ -1,6 +1,7 @@
 // sm_map_stream.h -- private to sm_render_maps.hip, sm_lidar.hip, sm_recall.hip, sm_warp.hip, sm_simplify.hip, sm_register.hip and sm_compare.hip: the double-buffered stream of
 // map-file chunks through the context's MapStaging, one object per call; behind it what the two readers of whole sets (the
-// streamed renderers, the lidar) do alike: the opening (maps_open) and the batch of views (maps_batch).  Chunk c of a pass goes
+// streamed renderers, the lidar) do alike: the opening (maps_open) and the batch of views (maps_batch), the opening of two sets
+// (check_sets, open_sets) and the pass over a set that only launches (maps_feed).  Chunk c of a pass goes
 // through buffer q = c & 1: read into h_rec[q] (timed into read_ms), copied on `copy` into d_rec[q], and the context's stream
 // waits for the copy; the caller then launches its kernels on d_rec[q] and says done(q).  fold(q) waits for them and adds the
 // buffer's event times to the caller's tally.  The host reads chunk c while chunk c - 1 is on the device: next() waits only for
@@ -109,6 +110,47 @@ int maps_open(sm_ctx *s, const sm_map_source *src, const char *fn, Whole whole, 
     cnt = src->include_model ? s->h_state->count : 0u;
     const uint64_t total = set.file_total + cnt;
     if (total > 0x7FFFFFFFull) { g_err = std::string(fn) + ": the map set holds " + std::to_string(total) + " surfels, ids end at 2^31 - 1"; return SM_E_CAPACITY; }
+    return SM_OK;
+}
+
+// What a call on two sets asks of them, without the device (registration, change detection), in two steps so that a caller's own
+// rules for its paths come between them: the sources and no path in both (check_sets), then every header of both (open_sets)
+inline int check_sets(const sm_map_source *a, const sm_map_source *b, const char *who)
+{
+    int rc;
+    if ((rc = check_map_source(a, who)) || (rc = check_map_source(b, who))) return rc;
+    for (uint32_t i = 0; i < a->n_paths; ++i)
+        for (uint32_t k = 0; k < b->n_paths; ++k)
+            if (strcmp(a->paths[i], b->paths[k]) == 0) { g_err = sm_mapfile::said(who, a->paths[i], " is in both sets"); return SM_E_ARG; }
+    return SM_OK;
+}
+inline int open_sets(const sm_map_source *a, const sm_map_source *b, const char *who, sm_mapset::ReadSet &aset, sm_mapset::ReadSet &bset)
+{
+    if (!sm_mapset::open_read_set(a->paths, a->n_paths, MapStaging::CHUNK, who, aset, g_err)) return SM_E_ARG;
+    if (!sm_mapset::open_read_set(b->paths, b->n_paths, MapStaging::CHUNK, who, bset, g_err)) return SM_E_ARG;
+    return SM_OK;
+}
+
+// One pass over a set that only launches: launch(d_rec, n, gid0) for every chunk of the files (paths: the source's), through a
+// stream of its own with the tally t, then for every chunk of the `cnt` live records at d_model; gid0: the set id of the chunk's
+// first record.  model_begins is recorded between the two; the caller marks the end of that stretch once everything it counts
+// into it is enqueued.
+template <typename Launch>
+int maps_feed(sm_ctx *s, const char *who, const sm_mapset::ReadSet &set, const char *const *paths, uint32_t cnt, const float4 *d_model,
+              MapStream::Tally t, const Event &model_begins, Launch launch)
+{
+    int rc;
+    MapStream in(s, who, paths, t);
+    for (in.begin(set.jobs); in.more();) {
+        MapStream::Chunk ck;
+        if ((rc = in.next(ck))) return rc;
+        launch(ck.d_rec, ck.job->n, (uint32_t)(set.id_base[ck.job->file] + ck.job->first));
+        if ((rc = in.done(ck.q))) return rc;
+        HIPCK(hipGetLastError());
+    }
+    if ((rc = in.fold(0)) || (rc = in.fold(1)) || (rc = mark(s, model_begins))) return rc;
+    for (uint32_t first = 0; first < cnt; first += MapStaging::CHUNK)
+        launch(d_model + (size_t)first * 3, std::min(MapStaging::CHUNK, cnt - first), (uint32_t)set.file_total + first);
     return SM_OK;
 }
 

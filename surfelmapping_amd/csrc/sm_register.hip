@@ -1,7 +1,7 @@
 // sm_register.hip -- registration of one map set against another (sm_register_maps, sm_register_debug; DESIGN.md "4q.
 // Registration"): the target set streamed once into one voxel table per level, the source set streamed once into resident
-// samples, then the iterations enqueued whole.  Kernels: sm_k_register.h.
-#include "sm_map_stream.h"
+// samples, then the iterations enqueued whole.  Kernels: sm_k_register.h; the tables themselves: sm_voxel.h.
+#include "sm_voxel.h"
 #include "sm_k_register.h"
 #include "sm_pose.h"
 
@@ -10,10 +10,8 @@ using sm_mapfile::now_ms;
 
 namespace {
 
-constexpr uint32_t CHUNK = MapStaging::CHUNK;
 constexpr uint32_t REG_MAX_SAMPLES = 1u << 28;
-constexpr size_t REG_SUM_BYTES = 8 * 7;                  // per slot beside the key: SW, SP[3], SN[3]
-enum { EV_TGT0 = 0, EV_TGT1, EV_SRC0, EV_SRC1, EV_IT0, EV_IT1, EV_CLR0, EV_CLR1 };   // pairs: add_marked(first)
+enum { EV_TGT0 = 0, EV_TGT1, EV_SRC0, EV_SRC1, EV_IT0, EV_IT1, EV_CLR0, EV_CLR1 };   // pairs: add_marked(&ev[first])
 
 int check_params(const sm_register_params *p, const char *who)
 {
@@ -29,19 +27,6 @@ int check_params(const sm_register_params *p, const char *who)
     if (p->max_cells == 0) return bad("max_cells is 0");
     for (int k = 0; k < 3; ++k)
         if (!std::isfinite(p->origin[k]) || !std::isfinite(p->pivot[k])) return bad("non-finite origin or pivot");
-    return SM_OK;
-}
-
-// what both entry points ask of their sets, without the device: the sources, no path in both, every header of both
-int open_sets(const sm_map_source *source, const sm_map_source *target, const char *who, sm_mapset::ReadSet &sset, sm_mapset::ReadSet &tset)
-{
-    int rc;
-    if ((rc = check_map_source(source, who)) || (rc = check_map_source(target, who))) return rc;
-    for (uint32_t i = 0; i < source->n_paths; ++i)
-        for (uint32_t k = 0; k < target->n_paths; ++k)
-            if (strcmp(source->paths[i], target->paths[k]) == 0) { g_err = sm_mapfile::said(who, source->paths[i], " is in both sets"); return SM_E_ARG; }
-    if (!sm_mapset::open_read_set(source->paths, source->n_paths, CHUNK, who, sset, g_err)) return SM_E_ARG;
-    if (!sm_mapset::open_read_set(target->paths, target->n_paths, CHUNK, who, tset, g_err)) return SM_E_ARG;
     return SM_OK;
 }
 
@@ -67,9 +52,7 @@ struct RegisterJob {
     Register &rg;
     const char *who;
     const sm_register_params &p;
-    SimplifyArgs a[REG_MAX_LEVELS]{};
-    SimplifyTable T[REG_MAX_LEVELS]{};
-    RegCell *lut[REG_MAX_LEVELS]{};
+    LookupTable t[REG_MAX_LEVELS];
     Dev<uint8_t> tables;
     Dev<float4> pos, nrm;
     uint32_t stride = 1, n_samples = 0;
@@ -87,45 +70,24 @@ struct RegisterJob {
         n_samples = (uint32_t)ns;
         int rc;
         if ((rc = reg_alloc(s)) || (rc = dalloc(pos, n_samples)) || (rc = dalloc(nrm, n_samples))) return rc;
-        uint64_t S = SIMP_MIN_SLOTS;
-        while (S < 2 * std::min<uint64_t>(target_records, p.max_cells)) S <<= 1;
-        if (S > (1ull << 31)) { g_err = std::string(who) + ": a table would need more than 2^31 slots"; return SM_E_CAPACITY; }
-        const size_t per_level = (size_t)S * (8 + REG_SUM_BYTES + sizeof(RegCell));
-        HIPCK(hipMalloc((void **)tables.put(), per_level * (size_t)p.levels));
-        const char *e = std::getenv("SM_SIMPLIFY_NO_COMBINE");
-        if ((rc = mark(EV_CLR0))) return rc;             // the tables' initialisation is device time of theirs (table_ms)
-        for (int l = 0; l < p.levels; ++l) {
-            uint8_t *b = tables.get() + per_level * (size_t)l;
-            lut[l] = (RegCell *)b;                       // (first: 32-byte aligned)
-            b += (size_t)S * sizeof(RegCell);
-            T[l].key = (unsigned long long *)b;
-            T[l].SW = T[l].key + S; T[l].SP = T[l].SW + S; T[l].SN = T[l].SP + 3 * S;
-            T[l].mask = (uint32_t)(S - 1);
-            T[l].tally = rg.d_tally.get() + l * SIMP_TALLY_WORDS;
-            a[l].V = (((long long)p.voxel_mm << l) * 65536 + 500) / 1000;
-            for (int k = 0; k < 3; ++k) a[l].origin[k] = p.origin[k];
-            a[l].split = 1;
-            a[l].max_cells = p.max_cells;
-            a[l].combine = (e && e[0] == '1') ? 0 : 1;
-            HIPCK(hipMemsetAsync(T[l].key, 0xFF, (size_t)S * 8, s->stream));
-            HIPCK(hipMemsetAsync(T[l].SW, 0, (size_t)S * REG_SUM_BYTES, s->stream));
-        }
+        uint64_t S;
+        if ((rc = voxel_slots(target_records, p.max_cells, who, "a table", S))) return rc;
+        for (int l = 0; l < p.levels; ++l) t[l].a = voxel_args(p.voxel_mm, l, p.origin, 1, p.max_cells);
+        if ((rc = lut_open(tables, t, p.levels, S, false, rg.d_tally.get()))) return rc;
+        // the tables' initialisation is device time of theirs (table_ms)
+        if ((rc = mark(s, rg.ev[EV_CLR0])) || (rc = lut_clear(s, t, p.levels))) return rc;
         HIPCK(hipMemsetAsync(rg.d_tally, 0, (REG_MAX_LEVELS * SIMP_TALLY_WORDS + 1) * 4, s->stream));
-        return mark(EV_CLR1);
+        return mark(s, rg.ev[EV_CLR1]);
     }
-    // n <= CHUNK records of the target into every level's table
+    // n <= CHUNK records of the target into every level's table, the class taken as 0
     void insert(const float4 *d_rec, uint32_t n)
     {
-        for (int l = 0; l < p.levels; ++l)
-            hipLaunchKernelGGL(k_register_insert, dim3((n + 255) / 256), dim3(256), 0, s->stream, d_rec, n, a[l], T[l]);
-        launches += p.levels;
+        for (int l = 0; l < p.levels; ++l) lut_insert(s, t[l], d_rec, n, 0, launches);
         rg.stats.chunks++;
     }
     void finish()
     {
-        for (int l = 0; l < p.levels; ++l)
-            hipLaunchKernelGGL(k_register_finish, dim3(T[l].mask / 256u + 1u), dim3(256), 0, s->stream, a[l], T[l], lut[l]);
-        launches += p.levels;
+        for (int l = 0; l < p.levels; ++l) lut_finish(s, t[l], launches);
     }
     // n <= CHUNK records of the source with ids gid0 ..
     void gather(const float4 *d_rec, uint32_t n, uint32_t gid0)
@@ -138,10 +100,10 @@ struct RegisterJob {
     {
         RegParams rp{};
         for (int l = 0; l < p.levels; ++l) {
-            rp.lv[l].lut = lut[l];
-            rp.lv[l].mask = T[l].mask;
-            rp.lv[l].V = a[l].V;
-            rp.lv[l].reach = (double)p.reach_cells * ((double)a[l].V * (1.0 / 65536.0));
+            rp.lv[l].lut = t[l].lut;
+            rp.lv[l].mask = t[l].T.mask;
+            rp.lv[l].V = t[l].a.V;
+            rp.lv[l].reach = (double)p.reach_cells * ((double)t[l].a.V * (1.0 / 65536.0));
         }
         rp.levels = p.levels;
         for (int k = 0; k < 3; ++k) { rp.origin[k] = p.origin[k]; rp.pivot[k] = (double)p.pivot[k]; }
@@ -160,14 +122,6 @@ struct RegisterJob {
         hipLaunchKernelGGL(k_register_solve, dim3(1), dim3(256), 0, s->stream, rp, (const double *)rg.d_part.get(), rg.d_state.get(), sum_only);
         launches += 2;
     }
-    int mark(int i) { HIPCK(hipEventRecord(rg.ev[i], s->stream)); return SM_OK; }
-    int add_marked(int i, float *ms_sum)
-    {
-        float ms = 0.0f;
-        HIPCK(hipEventElapsedTime(&ms, rg.ev[i], rg.ev[i + 1]));
-        *ms_sum += ms;
-        return SM_OK;
-    }
 };
 
 // Both entry points.  level < 0: sm_register_maps (pose16 the guess, null = identity); else sm_register_debug (pose16 the pose of
@@ -181,7 +135,7 @@ int register_run(sm_ctx *s, const sm_map_source *source, const sm_map_source *ta
     if ((rc = check_whole_map(s, who)) || (rc = check_params(p, who)) || (rc = check_not_mid_cull(s, who)) || (rc = check_pose(pose16, who))) return rc;
     if (debug && level >= p->levels) { g_err = std::string(who) + ": level outside 0 .. levels - 1"; return SM_E_ARG; }
     sm_mapset::ReadSet sset, tset;
-    if ((rc = open_sets(source, target, who, sset, tset))) return rc;
+    if ((rc = check_sets(source, target, who)) || (rc = open_sets(source, target, who, sset, tset))) return rc;
     HIPCK(hipSetDevice(s->cfg.device));
     if ((rc = ensure_compact(s)) || (rc = pull_state(s))) return rc;      // (waits for frames in flight; count is the live surfels)
     const uint32_t model = s->h_state->count, scnt = source->include_model ? model : 0u, tcnt = target->include_model ? model : 0u;
@@ -212,50 +166,23 @@ int register_run(sm_ctx *s, const sm_map_source *source, const sm_map_source *ta
     if (sset.jobs.size() + tset.jobs.size())
         if ((rc = maps_ensure_staging(s))) return rc;
     float copy_ms = 0.0f;
+    const MapStream::Tally times = {&rg.stats.read_ms, &copy_ms, &rg.stats.table_ms};
     // ---- the target: every chunk into every level's table, then the representatives
-    {
-        MapStream in(s, who, target->paths, {&rg.stats.read_ms, &copy_ms, &rg.stats.table_ms});
-        for (in.begin(tset.jobs); in.more();) {
-            MapStream::Chunk ck;
-            if ((rc = in.next(ck))) return rc;
-            job.insert(ck.d_rec, ck.job->n);
-            if ((rc = in.done(ck.q))) return rc;
-            HIPCK(hipGetLastError());
-        }
-        if ((rc = in.fold(0)) || (rc = in.fold(1))) return rc;
-    }
-    if ((rc = job.mark(EV_TGT0))) return rc;
-    for (uint32_t first = 0; first < tcnt; first += CHUNK) job.insert(d_model + (size_t)first * 3, std::min(CHUNK, tcnt - first));
+    if ((rc = maps_feed(s, who, tset, target->paths, tcnt, d_model, times, rg.ev[EV_TGT0],
+                        [&](const float4 *d_rec, uint32_t n, uint32_t) { job.insert(d_rec, n); })))
+        return rc;
     job.finish();
-    if ((rc = job.mark(EV_TGT1))) return rc;
+    if ((rc = mark(s, rg.ev[EV_TGT1]))) return rc;
     // ---- the source: the samples to their places
-    {
-        MapStream in(s, who, source->paths, {&rg.stats.read_ms, &copy_ms, &rg.stats.table_ms});
-        for (in.begin(sset.jobs); in.more();) {
-            MapStream::Chunk ck;
-            if ((rc = in.next(ck))) return rc;
-            job.gather(ck.d_rec, ck.job->n, (uint32_t)(sset.id_base[ck.job->file] + ck.job->first));
-            if ((rc = in.done(ck.q))) return rc;
-            HIPCK(hipGetLastError());
-        }
-        if ((rc = in.fold(0)) || (rc = in.fold(1))) return rc;
-    }
-    if ((rc = job.mark(EV_SRC0))) return rc;
-    for (uint32_t first = 0; first < scnt; first += CHUNK)
-        job.gather(d_model + (size_t)first * 3, std::min(CHUNK, scnt - first), (uint32_t)sset.file_total + first);
-    if ((rc = job.mark(EV_SRC1))) return rc;
-    HIPCK(hipGetLastError());
-    constexpr size_t words = REG_MAX_LEVELS * SIMP_TALLY_WORDS + 1;
-    HIPCK(hipMemcpyAsync(rg.h_tally.get(), rg.d_tally.get(), words * 4, hipMemcpyDeviceToHost, s->stream));
-    HIPCK(hipStreamSynchronize(s->stream));
-    if ((rc = job.add_marked(EV_CLR0, &rg.stats.table_ms)) || (rc = job.add_marked(EV_TGT0, &rg.stats.table_ms)) ||
-        (rc = job.add_marked(EV_SRC0, &rg.stats.table_ms))) return rc;
+    if ((rc = maps_feed(s, who, sset, source->paths, scnt, d_model, times, rg.ev[EV_SRC0],
+                        [&](const float4 *d_rec, uint32_t n, uint32_t gid0) { job.gather(d_rec, n, gid0); })))
+        return rc;
+    if ((rc = mark(s, rg.ev[EV_SRC1])) || (rc = voxel_read_tally(s, rg.d_tally.get(), rg.h_tally.get(), REG_MAX_LEVELS * SIMP_TALLY_WORDS + 1))) return rc;
+    for (int pair : {EV_CLR0, EV_TGT0, EV_SRC0})
+        if ((rc = add_marked(&rg.ev[pair], &rg.stats.table_ms))) return rc;
     const uint32_t *h = rg.h_tally.get();
     for (int l = 0; l < p->levels; ++l) {
-        if (h[l * SIMP_TALLY_WORDS + SIMP_ERR]) {
-            g_err = std::string(who) + ": more than max_cells = " + std::to_string(p->max_cells) + " keys at level " + std::to_string(l);
-            return SM_E_CAPACITY;
-        }
+        if ((rc = voxel_check_tally(h + l * SIMP_TALLY_WORDS, p->max_cells, who, "keys at level " + std::to_string(l)))) return rc;
         out.cells[l] = h[l * SIMP_TALLY_WORDS + SIMP_CELLS];
         if (out.cells[l] == 0) out.status = SM_REGISTER_NO_TARGET;
     }
@@ -271,15 +198,15 @@ int register_run(sm_ctx *s, const sm_map_source *source, const sm_map_source *ta
         if (!debug) sm_pose::orthonormalize_d(hs.T);
         hs.level = debug ? level : p->levels - 1;
         HIPCK(hipMemcpyAsync(rg.d_state.get(), &hs, sizeof hs, hipMemcpyHostToDevice, s->stream));
-        if ((rc = job.mark(EV_IT0))) return rc;
+        if ((rc = mark(s, rg.ev[EV_IT0]))) return rc;
         if (debug) job.iteration(rp, 1);
         else
             for (int i = 0; i < p->levels * p->max_iters; ++i) job.iteration(rp, 0);
         HIPCK(hipGetLastError());
-        if ((rc = job.mark(EV_IT1))) return rc;
+        if ((rc = mark(s, rg.ev[EV_IT1]))) return rc;
         HIPCK(hipMemcpyAsync(&hs, rg.d_state.get(), sizeof hs, hipMemcpyDeviceToHost, s->stream));
         HIPCK(hipStreamSynchronize(s->stream));
-        if ((rc = job.add_marked(EV_IT0, &rg.stats.iterate_ms))) return rc;
+        if ((rc = add_marked(&rg.ev[EV_IT0], &rg.stats.iterate_ms))) return rc;
     }
     if (debug) {
         for (int e = 0; e < TRACK_NSYS; ++e) sys29[e] = hs.sys[e];

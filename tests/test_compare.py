@@ -14,6 +14,7 @@ import compare_ref as cf
 import recall_ref as cr
 import register_scenes as sc
 import retire_ref as ret
+import table_ref as tb
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY_POINTS = ("sm_default_compare_params", "sm_compare_maps", "sm_compare_stats")
@@ -29,6 +30,10 @@ HAND_POSE = np.array([[0.0, -1.0, 0.0, 1.0], [1.0, 0.0, 0.0, 2.0], [0.0, 0.0, 1.
 # The street (test_gpu_street_matches_the_restatement): cells of 1 m -- the 5 000 reference records are 7 to the square metre, so
 # a cell a surface crosses is all but never empty --, cover cells of 2 m, the other parameters the defaults
 STREET = dict(voxel_mm=1000, cover_shift=1)
+# The smallest tables (test_gpu_smallest_tables_with_wrap_around): cells of 1/8 m, cover cells of 1/4 m -- at cover_shift 3 a
+# thousand records have too few cover keys for one of them to be carried past the end of 2048 slots at any origin of the grid
+WRAP = dict(voxel_mm=125, cover_shift=1, reach_cells=0.5, origin=(0.0, 0.21 * 19, 0.0))
+WRAP_REF_ROWS = 1000
 U = 2.0 ** -16
 
 
@@ -447,6 +452,71 @@ def test_gpu_more_than_a_chunk(street, tmp_path):
     m.close()
     _same(lab, info, out, want, "two chunks")
     assert st["chunks"] == 3 and st["launches"] == 1 + 1 + 2 * 3
+
+
+def _wrap_case(street):
+    """The first 1 000 reference records of the street -- 7 to the square metre, so with cells of 1/8 m nearly every record has a
+    fine cell and, at cover_shift 1, a cover cell of its own: about as many cover keys as fine keys, both tables half full.  The
+    query: 1 000 records of the street's query and the reference's own records moved back by the inverse pose, which look for
+    the cell they came from; the reach of half a cell leaves most of them no other."""
+    ref, pose = street["ref"][:WRAP_REF_ROWS], street["pose"]
+    inv = np.linalg.inv(pose.astype(F64))
+    back = ref.copy()
+    back[:, 0:3] = (ref[:, 0:3].astype(F64) @ inv[:3, :3].T + inv[:3, 3]).astype(F32)
+    back[:, 8:11] = (ref[:, 8:11].astype(F64) @ inv[:3, :3].T).astype(F32)
+    return np.concatenate([street["query"][:1000], back]), ref, pose
+
+
+def wrap_tables(ref, params):
+    """what the smallest tables of `ref` hold at params' grid: dict(fine, cover: the keys; size: the slots of either; carried:
+    how many fine and cover keys go past the last slot; at_the_end: table_ref.end_run of the fine keys; key_of: per record of
+    ref its fine key, valid where ok)"""
+    origin = params["origin"]
+    V0 = cf.rr.cell_edge(params["voxel_mm"])
+    ok = cf.rr.fields_ok(ref)
+    in_grid, cell, _ = cf.rr.grid(ref[:, 0:3].astype(F64), V0, origin)
+    ok &= in_grid
+    key_of = cf.rr.pack(np.where(ok[:, None], cell, 0), cf.rr.face_of(ref[:, 8:11]))
+    fine = sorted(set(key_of[ok].tolist()))
+    cover = cf.cover_table(ref, cf.rr.cell_edge(params["voxel_mm"] << params["cover_shift"]), origin).tolist()
+    size = 1024
+    while size < 2 * len(fine):
+        size <<= 1
+    return dict(fine=fine, cover=cover, size=size, carried=(tb.wraps(fine, size - 1), tb.wraps(cover, size - 1)),
+                at_the_end=tb.end_run(fine, size - 1), ok=ok, key_of=key_of)
+
+
+def not_the_only_support(qry, ref, pose, params, t, labels):
+    """the keys of t["at_the_end"] without which no SUPPORTED label of `labels` changes"""
+    return [k for k in t["at_the_end"]
+            if not ((labels == S) & (cf.compare(qry, ref[~(t["ok"] & (t["key_of"] == np.uint64(k)))], pose, **params)["labels"] != S)).any()]
+
+
+@pytest.mark.gpu
+def test_gpu_smallest_tables_with_wrap_around(street, tmp_path):
+    """max_cells = the fine keys leaves the smallest tables the rule allows (the power of two >= 2 * max_cells); the origin is one
+    at which a run of occupied slots crosses the end of the fine table and one that of the cover table, so that probes walk
+    from the last slot to slot 0.  tools/compare_wrap_origin.py found it, with the functions above, as the first of the grid
+    (0.37 i, 0.21 j, 0), i, j < 40, that meets what is asserted here, and found none in that grid at cover_shift 3.
+    Which keys of such a run the device carries past the end depends on the order it inserts them in, but they are keys whose
+    home slot lies in the run (table_ref.end_run): each of those is the only support of some query record, so whichever is
+    carried, a label depends on the lookup that follows it"""
+    qry, ref, pose = _wrap_case(street)
+    t = wrap_tables(ref, WRAP)
+    fine, size = t["fine"], t["size"]
+    assert fine == cf.fine_table(ref, cf.rr.cell_edge(WRAP["voxel_mm"]), WRAP["origin"], 0)["keys"].tolist()
+    assert size == 2048 and t["carried"][0] >= 1 and t["carried"][1] >= 1
+    want = cf.compare(qry, ref, pose, write_mask=3, **WRAP)
+    assert not_the_only_support(qry, ref, pose, WRAP, t, want["labels"]) == []
+    print(f"origin {WRAP['origin']}: {len(fine)} fine and {len(t['cover'])} cover keys in {size} slots, {t['carried'][0]} and "
+          f"{t['carried'][1]} carried past the end, {len(t['at_the_end'])} fine keys in the run at the end; labels {want['counts']}")
+    assert all(c > 0 for c in want["counts"])
+    m = _ctx()
+    out = str(tmp_path / "out.bin")
+    lab, info = m.compare_maps([_write(tmp_path, "q.bin", qry)], [_write(tmp_path, "r.bin", ref)], pose=pose, out_path=out, write_mask=3,
+                               max_cells=len(fine), **WRAP)
+    m.close()
+    _same(lab, info, out, want, f"tables of {size} slots")
 
 
 @pytest.mark.gpu

@@ -17,6 +17,7 @@ import register_ref as rr
 import register_scenes as sc
 import retire_ref as ret
 import simplify_ref as sr
+import table_ref as tb
 import track_ref as tr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -301,22 +302,6 @@ def test_gpu_system_is_the_exact_sum(base, tmp_path, n, level):
     tr.assert_system(got, terms, f"n = {n}, level {level}")
 
 
-def _wraps(keys, mask):
-    """keys that linear probing from simp_hash carries from the last slot of a table of mask + 1 to slot 0: how many cross that
-    boundary does not depend on the insertion order"""
-    M = (1 << 64) - 1
-    used, wraps = set(), 0
-    for k in (int(v) for v in keys):
-        k ^= k >> 33; k = (k * 0xff51afd7ed558ccd) & M
-        k ^= k >> 33; k = (k * 0xc4ceb9fe1a85ec53) & M
-        s = (k ^ (k >> 33)) & mask
-        while s in used:
-            wraps += s == mask
-            s = (s + 1) & mask
-        used.add(s)
-    return wraps
-
-
 @pytest.mark.gpu
 def test_gpu_smallest_table_with_wrap_around(base, tmp_path):
     """max_cells = the keys of the coarsest level leaves the smallest table the rule allows (the power of two >= 2 * max_cells);
@@ -326,8 +311,9 @@ def test_gpu_smallest_table_with_wrap_around(base, tmp_path):
     size = 1024
     while size < 2 * pb.cells[0]:
         size <<= 1
-    assert size == 2048 and _wraps(pb.levels[0]["keys"], size - 1) >= 1
-    print(f"origin {origin}: {pb.cells[0]} keys in {size} slots, {_wraps(pb.levels[0]['keys'], size - 1)} carried past the end")
+    carried = tb.wraps(pb.levels[0]["keys"].tolist(), size - 1)
+    assert size == 2048 and carried >= 1
+    print(f"origin {origin}: {pb.cells[0]} keys in {size} slots, {carried} carried past the end")
     terms = pb.terms(base["pe"].astype(F64), 0)
     m = _ctx()
     got, _ = m.register_debug([_write(tmp_path, "s.bin", base["src"])], [_write(tmp_path, "t.bin", tgt)], base["pe"], 0, max_cells=pb.cells[0],

@@ -340,6 +340,44 @@ def test_gpu_map_sets(scene, tmp_path):
 
 
 @pytest.mark.gpu
+def test_gpu_output_scratch_is_shared_with_change_detection(scene, tmp_path):
+    """sm_simplify_maps, sm_compare_maps with an output, sm_simplify_maps again on one context: both write what they keep of a
+    chunk through the same device buffers, which the second call -- its largest chunk has 958 records, the first call's 400 --
+    has to grow.  Each result is its restatement's, and the third file is the first's, byte for byte"""
+    import compare_ref as cf
+    rows = scene.rows
+    small = [rows[:300], rows[300:700]]
+    query, ref = [rows[:900], rows[900:]], [rows[200:800], rows[800:1500]]
+    assert max(len(p) for p in query) > max(len(p) for p in small)
+
+    def write(name, parts):
+        paths = [str(tmp_path / f"{name}{i}.bin") for i in range(len(parts))]
+        for p, part in zip(paths, parts):
+            cr.write_map(p, part, 1, 2)
+        return paths
+    sp, qp, rp = write("s", small), write("q", query), write("r", ref)
+    want, st = sr.simplify_set(small, voxel_mm=BITE_MM)
+    kw = dict(voxel_mm=BITE_MM, cover_shift=2, write_mask=0b0111)
+    want_cmp = cf.compare_sets(query, ref, None, **kw)
+    assert st["cells_merged"] > 0 and len(want) < 700 and 900 < len(want_cmp["written"]) and min(want_cmp["counts"][:3]) > 0
+    m = _ctx()
+    outs = [str(tmp_path / f"out{i}.bin") for i in range(3)]
+    got = m.simplify_maps(sp, outs[0], voxel_mm=BITE_MM)
+    same_rows(rr.read_map(outs[0])[0], want, "before")
+    assert {k: got[k] for k in STAT_KEYS} == st
+    lab, info = m.compare_maps(qp, rp, out_path=outs[1], **kw)
+    assert np.array_equal(lab, want_cmp["labels"]) and info["counts_by_code"] == want_cmp["counts"]
+    assert info["written"] == len(want_cmp["written"])
+    same_rows(rr.read_map(outs[1])[0], want_cmp["written"], "change detection")
+    got = m.simplify_maps(sp, outs[2], voxel_mm=BITE_MM)
+    same_rows(rr.read_map(outs[2])[0], want, "after")
+    assert {k: got[k] for k in STAT_KEYS} == st
+    assert open(outs[0], "rb").read() == open(outs[2], "rb").read()
+    _no_tmp(tmp_path)
+    m.close()
+
+
+@pytest.mark.gpu
 def test_gpu_one_cell_across_files(tmp_path):
     """300 copies of one position with different colours and weights in three files, between records that are alone in their cells:
     more than a wave's worth, so the combine step, the atomics across waves and the rank across chunks all take part"""

@@ -1349,6 +1349,73 @@ int sm_compare_maps(sm_ctx *s, const sm_map_source *query, const sm_map_source *
                     const char *out_path /* may be NULL */, sm_compare_info *info);
 int sm_compare_stats(sm_ctx *s, sm_compare_stats_t *out);
 
+/* ---- tiling: a map set sorted in space (DESIGN.md "4s. Spatial tiling") ----
+ * sm_tile_maps rewrites a map set -- an sm_map_source with the global ids of the map-set calls: the files in list order, each in
+ * file order, then (include_model) the live model -- as a NEW set: the same records, verbatim (48 bytes each), sorted along a 3-D
+ * Morton curve over a world grid and cut into files at tile boundaries.  Sources and model stay as they are.  Nothing calls it
+ * unasked.  The boxes every map-set call skips by (one per block of 256 consecutive records in the streamed renderers and the lidar,
+ * one per file in sm_recall and the warp) are tight on its output whatever order the sources were written in.
+ *   Definition, in integers (restated by tests/tile_ref.py):
+ *   Grid.  The simplification's: V = (cell_mm * 65536 + 500) / 1000 (integer division), X[k] = (int64)floor(((double)p[k] -
+ *     (double)origin[k]) * 65536.0), cell[k] = floor_div(X[k], V).
+ *   Placed.  A record is placed if x, y, z are finite, |(double)p[k] - (double)origin[k]| < 2^24 and every cell[k] lies in
+ *     [-65536, 65535]; every other record is loose.  Only the position is examined: a record with conf <= 0, a NaN normal or a
+ *     negative radius is placed (this is not the simplification's "regular").
+ *   Key.  u[k] = cell[k] + 65536 in [0, 2^17); bit 3 i + k of M is bit i of u[k] (x lowest): 51 bits.
+ *   Tile.  M >> (3 * tile_shift): an aligned cube of 2^tile_shift cells per axis.
+ *   Order.  The placed records in ascending (M, global id), then the loose ones in ascending global id.
+ *   Files.  The tiles are walked in ascending tile id; a file takes successive whole tiles while its count stays <=
+ *     max_file_records; a tile with more records than that is written alone, as consecutive files of max_file_records records, the
+ *     last of them shorter; the loose records, if any, form one last file.  Names: "<out_prefix>_%06u.bin", 0, 1, ...  Each header
+ *     carries the frame range that spans the sources' (0, 0 without files).  An empty set writes no file.
+ *   The result is a function of the multiset of (global id, record) pairs alone: the chunking, the split into source files, the
+ *     device's order and the sort capacity do not change a byte.  Tiling the output again with the same parameters, files in
+ *     order, reproduces it byte for byte.
+ *   Example, cell_mm 1000 (V = 65536), origin 0: centres F (-0.5, .5, .5), A (.5, .5, .5), G (-0.0, .5, .5), B (1.5, .5, .5),
+ *     C (.5, 1.5, .5), D (.5, .5, 1.5), E (2.5, .5, .5) have M = 0x6249249249249, 0x7000000000000, 0x7000000000000,
+ *     0x7000000000001, ..2, ..4, ..8: the order is F, A and G by id, B, C, D, E; with tile_shift 1 A, G, B, C, D share a tile, E
+ *     and F have one each.  cell_mm 100: V = 6554; 200: 13107; 10: 655 (the grid then ends at +-429 m).
+ *   Cost.  1 + the number of batches readings of the set: one that counts the records per tile, then one per batch -- a maximal
+ *     run of successive whole tiles whose total stays <= the sort capacity, 1 << 22 records (SM_TILE_SORT_RECORDS, read per call,
+ *     256 .. 1 << 26, overrides it; the result does not depend on it).  Loose records are collected by the first batch's reading
+ *     (by a reading of their own if nothing is placed) and held on the device until they are written.
+ *   Writing.  Every file is written as "<name>.tile.tmp"; all are renamed into place only after the last one is complete.  On any
+ *     error nothing is renamed and no temporary is left.  Files an earlier call left under higher numbers of the same prefix are
+ *     not removed.  After the renames each file is noted in the context's file index with the box of its finite centres and its
+ *     largest time: an sm_recall that follows skips files out of reach without opening them.
+ *   A tiled set no longer has time-ordered files: sm_warp_by_time (closing a loop) will open every one of them, so tile once the
+ *     drive is closed.
+ * Errors.  SM_E_ARG: NULLs; a parameter outside the ranges below; a non-finite origin; max_file_records above the sort capacity; an
+ *   output name equal to a source path (every name of the plan is checked before anything is written); a call between
+ *   sm_stage_conflict and sm_stage_cull; the file checks of sm_render_image_maps; sm_tile_stats before any call.
+ *   SM_E_UNSUPPORTED: a sharded or rig context.  SM_E_CAPACITY: more than max_tiles tiles; a single tile above the sort capacity
+ *   (lower tile_shift); a set of more than 2^31 - 1 records.  Nothing is written in any of these cases. */
+typedef struct sm_tile_params {
+    int32_t cell_mm;            /* 10..10000                               default 200 */
+    int32_t tile_shift;         /* 0..17: tile edge = cell << shift        default 7 (25.6 m) */
+    float origin[3];            /*                                         default 0 */
+    uint32_t max_file_records;  /* 256..sort capacity                      default 1 << 20 */
+    uint32_t max_tiles;         /* distinct tiles the call may meet, >= 1  default 1 << 20 */
+} sm_tile_params;
+typedef struct sm_tile_stats_t {
+    uint64_t records_in, placed, loose;
+    uint32_t tiles;             /* distinct tiles */
+    uint32_t largest_tile;      /* records in the fullest */
+    uint32_t files_written;
+    uint32_t readings;          /* passes over the set */
+    uint32_t chunks;            /* of at most 2^20 records, over all readings */
+    uint32_t launches;
+    uint32_t sort_passes;       /* radix passes run, over all batches: a pass whose digit is the same in all keys is skipped */
+    float device_ms;            /* kernels of the readings, the sort and the gather */
+    float sort_ms;              /* ... of which the sort */
+    float read_ms;              /* host: reading the files */
+    float write_ms;             /* host: writing the files */
+    float total_ms;
+} sm_tile_stats_t;
+int sm_default_tile_params(sm_tile_params *p);               /* pure, no context */
+int sm_tile_maps(sm_ctx *s, const sm_map_source *src, const sm_tile_params *p, const char *out_prefix);
+int sm_tile_stats(sm_ctx *s, sm_tile_stats_t *out);
+
 /* ---- per-pass entry points (GlobalModel / IndexMap methods), synchronous ---- */
 /* Upload RGB / metric depth / semantic textures directly (bypasses p0). */
 int sm_set_frame(sm_ctx *s, const uint8_t *rgb, const float *depth_metric,

@@ -50,6 +50,7 @@ SYMBOLS = (
     "sm_default_simplify_params", "sm_simplify", "sm_simplify_maps", "sm_simplify_stats",
     "sm_default_register_params", "sm_register_maps", "sm_register_debug", "sm_register_stats",
     "sm_default_compare_params", "sm_compare_maps", "sm_compare_stats",
+    "sm_default_tile_params", "sm_tile_maps", "sm_tile_stats",
 )
 
 SM_COLL_SUM, SM_COLL_MIN, SM_COLL_GATHER = 0, 1, 2
@@ -477,6 +478,38 @@ def default_simplify_params() -> SmSimplifyParams:
 def simplify_params(**over) -> SmSimplifyParams:
     """default_simplify_params() with fields overridden; origin takes a sequence of three"""
     p = default_simplify_params()
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise KeyError(k)
+        if k == "origin":
+            p.origin[:] = [float(x) for x in v]
+        else:
+            setattr(p, k, v)
+    return p
+
+
+class SmTileParams(C.Structure):
+    _fields_ = [("cell_mm", C.c_int32), ("tile_shift", C.c_int32), ("origin", C.c_float * 3), ("max_file_records", C.c_uint32),
+                ("max_tiles", C.c_uint32)]
+
+
+class SmTileStats(C.Structure):
+    _fields_ = [("records_in", C.c_uint64), ("placed", C.c_uint64), ("loose", C.c_uint64), ("tiles", C.c_uint32), ("largest_tile", C.c_uint32),
+                ("files_written", C.c_uint32), ("readings", C.c_uint32), ("chunks", C.c_uint32), ("launches", C.c_uint32),
+                ("sort_passes", C.c_uint32), ("device_ms", C.c_float), ("sort_ms", C.c_float), ("read_ms", C.c_float), ("write_ms", C.c_float),
+                ("total_ms", C.c_float)]
+
+
+def default_tile_params() -> SmTileParams:
+    """sm_default_tile_params: cell_mm 200, tile_shift 7, origin (0, 0, 0), max_file_records 1 << 20, max_tiles 1 << 20"""
+    p = SmTileParams()
+    load().sm_default_tile_params(C.byref(p))
+    return p
+
+
+def tile_params(**over) -> SmTileParams:
+    """default_tile_params() with fields overridden; origin takes a sequence of three"""
+    p = default_tile_params()
     for k, v in over.items():
         if not hasattr(p, k):
             raise KeyError(k)
@@ -933,6 +966,10 @@ def load():
     L.sm_default_compare_params.argtypes = [cpp]
     L.sm_compare_maps.argtypes = [vp, msp, msp, C.c_void_p, cpp, C.c_void_p, C.c_char_p, C.POINTER(SmCompareInfo)]
     L.sm_compare_stats.argtypes = [vp, C.POINTER(SmCompareStats)]
+    tpp = C.POINTER(SmTileParams)
+    L.sm_default_tile_params.argtypes = [tpp]
+    L.sm_tile_maps.argtypes = [vp, msp, tpp, C.c_char_p]
+    L.sm_tile_stats.argtypes = [vp, C.POINTER(SmTileStats)]
     for name in SYMBOLS:
         getattr(L, name)          # AttributeError here = the library does not match the header
     _lib = L
@@ -1842,6 +1879,24 @@ class SurfelMap:
         src = map_source(paths, include_model)
         self._chk(self._L.sm_simplify_maps(self._h, C.byref(src), C.byref(p), os.fsencode(out_path)), "sm_simplify_maps")
         return self.simplify_stats()
+
+    # -- spatial tiling of a map set (sm_tile_maps)
+    def tile_maps(self, paths, out_prefix, include_model=False, **params) -> list:
+        """The map set -- the files `paths` in that order, then (include_model) the live model -- rewritten as a new set: the same
+        records sorted along a Morton curve over a grid of `cell_mm` and cut into files "<out_prefix>_%06u.bin" at the boundaries
+        of tiles of cell_mm << tile_shift (sm_tile_maps; tests/tile_ref.py restates it).  Sources and model stay as they are.
+        params: the fields of tile_params().  Returns the files written, in order."""
+        p = tile_params(**params)
+        src = map_source(paths, include_model)
+        self._chk(self._L.sm_tile_maps(self._h, C.byref(src), C.byref(p), os.fsencode(out_prefix)), "sm_tile_maps")
+        return ["%s_%06d.bin" % (os.fspath(out_prefix), i) for i in range(self.tile_stats()["files_written"])]
+
+    def tile_stats(self) -> dict:
+        """of the last tile_maps: records_in, placed, loose, tiles, largest_tile, files_written, readings, chunks, launches,
+        sort_passes, device_ms, sort_ms, read_ms, write_ms, total_ms"""
+        st = SmTileStats()
+        self._chk(self._L.sm_tile_stats(self._h, C.byref(st)), "sm_tile_stats")
+        return {k: getattr(st, k) for k, _ in SmTileStats._fields_}
 
     # -- registration of one map set against another (sm_register_maps)
     def register_maps(self, source_paths, target_paths, guess=None, source_model=False, target_model=False, apply=False, **params):

@@ -278,6 +278,35 @@ public:
         return (long)st.records_out;
     }
 
+    // A map set sorted in space (sm_tile_maps; DESIGN.md "4s. Spatial tiling"): the records of `mapFiles`, then (withModel) of the
+    // live model, verbatim, in Morton order over a world grid and cut at tile boundaries into the files "<prefix>_%06u.bin", none
+    // of which may be one of mapFiles.  params null: the defaults (200 mm cells, tiles of 25.6 m, files of up to 2^20 records).
+    // The files and the model stay as they are.  Returns the files written, in order; on an error it is printed, nothing has
+    // been written and the list is empty (as it is for an empty set: sm_tile_stats tells the two apart).
+    std::vector<std::string> tileMaps(const std::vector<std::string> &mapFiles, const std::string &prefix, bool withModel = false,
+                                      const sm_tile_params *params = nullptr)
+    {
+        std::vector<const char *> paths;
+        for (const std::string &f : mapFiles) paths.push_back(f.c_str());
+        const sm_map_source src{paths.data(), (uint32_t)paths.size(), withModel ? 1 : 0};
+        sm_tile_params p;
+        sm_default_tile_params(&p);
+        if (params) p = *params;
+        sm_tile_stats_t st;
+        std::vector<std::string> written;
+        (void)sm_sync(ctx_);                                             // (SM_FACADE_ASYNC: frames may still be in flight)
+        if (sm_tile_maps(ctx_, &src, &p, prefix.c_str()) != SM_OK || sm_tile_stats(ctx_, &st) != SM_OK) {
+            std::printf("tileMaps: %s\n", sm_last_error());
+            return written;
+        }
+        for (uint32_t i = 0; i < st.files_written; ++i) {
+            char name[32];
+            std::snprintf(name, sizeof name, "_%06u.bin", i);
+            written.push_back(prefix + name);
+        }
+        return written;
+    }
+
     // Which rigid transform takes the map set `sourceFiles` onto the set `targetFiles` (sm_register_maps; DESIGN.md "4q.
     // Registration"): two drives of one street, each in the world of its own first pose.  guess: source world -> target world, as
     // far as it is known (within about a cell of the coarsest level, 0.8 m by default); pose: the result, the guess unless the

@@ -361,6 +361,17 @@ struct Compare {
     bool stats_valid = false;
 };
 
+// spatial tiling (sm_tile.hip, sm_k_tile.h): the tallies and events that outlive a call, the last call's tally.  The tile table,
+// the batch buffers and the sort's scratch live for one call.
+struct Tile {
+    Dev<uint32_t> d_tally;             // [0]: error word | distinct tiles | running rank | loose; [1]: the loose records' running rank
+    Dev<unsigned long long> d_bits;    // the OR and the AND of a batch's keys
+    static constexpr int N_EV = 10;    // around what runs outside a chunk stream and around the sort; per piece buffer (two): around the gather, after the copy
+    Event ev[N_EV];
+    sm_tile_stats_t stats{};
+    bool stats_valid = false;
+};
+
 // closing loops unasked (sm_loop.hip): the policy of sm_set_auto_loop and its tally
 struct AutoLoop {
     bool on = false;
@@ -614,6 +625,7 @@ struct sm_ctx {
     Register reg;                      // (nothing depends on where it lies; behind the frame path's members, which keep their places)
     Compare cmp;
     RankScratch ranked;
+    Tile tile;
 };
 
 namespace sm_impl __attribute__((visibility("hidden"))) {

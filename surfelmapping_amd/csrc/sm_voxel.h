@@ -1,4 +1,4 @@
-// sm_voxel.h -- private to sm_simplify.hip, sm_register.hip, sm_compare.hip and sm_voxel.hip, which defines what is declared
+// sm_voxel.h -- private to sm_simplify.hip, sm_register.hip, sm_compare.hip, sm_tile.hip and sm_voxel.hip, which defines what is declared
 // here: what the users of a voxel table do alike on the host.  The grid and the table's size from a call's parameters and the
 // tally's verdict (all three); the lookup table -- sums finished into one RegCell per slot, with or without a cover table of keys
 // -- of registration and change detection; the ranked output -- what a pass keeps of every chunk, in order, in one map file -- of
@@ -36,6 +36,9 @@ int lut_clear(sm_ctx *s, const LookupTable *t, int n);
 void lut_insert(sm_ctx *s, const LookupTable &t, const float4 *d_rec, uint32_t n, int keep_class, uint32_t &launches);
 // the sums become the lookup records
 void lut_finish(sm_ctx *s, const LookupTable &t, uint32_t &launches);
+
+// the frame range a file made of a set's records carries in its header: the one that spans the files' (0, 0 without files)
+void frame_range(const sm_mapset::ReadSet &set, int32_t &start_id, int32_t &end_id);
 
 // One call's ranked output on the context's RankScratch.  A chunk's kernels count what they keep per block of 256 (blk_cnt), scan()
 // ranks the blocks on top of the call's running rank, the caller's emit kernel writes the kept records to out(q); fetch(q) brings

@@ -93,6 +93,15 @@ void sm_impl::lut_finish(sm_ctx *s, const LookupTable &t, uint32_t &launches)
 
 // ---- the ranked output
 
+void sm_impl::frame_range(const sm_mapset::ReadSet &set, int32_t &start_id, int32_t &end_id)
+{
+    start_id = end_id = 0;
+    for (size_t i = 0; i < set.files.size(); ++i) {
+        start_id = i ? std::min(start_id, set.files[i].start_id) : set.files[i].start_id;
+        end_id = i ? std::max(end_id, set.files[i].end_id) : set.files[i].end_id;
+    }
+}
+
 int sm_impl::RankedOutput::ensure(int q, size_t records)
 {
     if (!rs.d_info) {
@@ -114,11 +123,8 @@ int sm_impl::RankedOutput::open(const char *out_path, const char *suffix, const 
     uint32_t largest_job = std::min(cnt, CHUNK);
     for (const sm_mapfile::Job &j : set.jobs) largest_job = std::max(largest_job, j.n);
     if (largest_job && ((rc = ensure(0, largest_job)) || (rc = ensure(1, largest_job)))) return rc;   // (an empty set: the file alone)
-    int32_t start_id = 0, end_id = 0;                    // the header's frame range: the files' together
-    for (size_t i = 0; i < set.files.size(); ++i) {
-        start_id = i ? std::min(start_id, set.files[i].start_id) : set.files[i].start_id;
-        end_id = i ? std::max(end_id, set.files[i].end_id) : set.files[i].end_id;
-    }
+    int32_t start_id, end_id;
+    frame_range(set, start_id, end_id);
     tmp = std::string(out_path) + suffix;
     return w.open(tmp, sm_mapfile::Writer::UNKNOWN, start_id, end_id, who, g_err) ? SM_OK : SM_E_ARG;
 }

@@ -1416,6 +1416,104 @@ int sm_default_tile_params(sm_tile_params *p);               /* pure, no context
 int sm_tile_maps(sm_ctx *s, const sm_map_source *src, const sm_tile_params *p, const char *out_prefix);
 int sm_tile_stats(sm_ctx *s, sm_tile_stats_t *out);
 
+/* ---- segmentation: the records of a map set grouped into objects (DESIGN.md "4t. Segmentation") ----
+ * sm_segment_maps groups the records of a map set -- an sm_map_source with the global ids of the map-set calls: the files in list
+ * order, each in file order, then (include_model) the live model -- into connected components of occupied voxel cells: a label per
+ * record, a row per component, and with out_path the records of the label kinds asked for as ONE map file.  A component of fewer
+ * than min_records records is a speck: write_mask 1 with min_records N writes the set without its specks.  Sources, model, tick,
+ * stored poses, fern keyframes and tracker state are untouched; frames in flight are waited for.
+ *   Definition, in integers (restated by tests/segment_ref.py):
+ *   Grid.  The simplification's: V = (voxel_mm * 65536 + 500) / 1000 (integer division), X[k] = (int64)floor(((double)p[k] -
+ *     (double)origin[k]) * 65536.0), cell[k] = floor_div(X[k], V), and its regular-record test: every field finite, conf > 0, both
+ *     times >= 0, 0 <= radius < 32768, a normal that is not (0, 0, 0), |(double)p[k] - (double)origin[k]| < 2^24 and every cell[k]
+ *     in [-65536, 65535].  The class c of a record is its colour word >> 24.
+ *   Label of a record, the first rule that applies:
+ *     1. LOOSE    it is not regular.
+ *     2. SKIPPED  bit c & 31 of class_mask[c >> 5] is clear.
+ *     3. Otherwise it belongs to the node (cell, kc), kc = c with by_class, else 0.  (The node's key is the simplification's key
+ *        with face 0 and class kc.)
+ *   Edges.  Two nodes are joined iff they have the same kc and their cells differ by a d in {-1, 0, 1}^3 \ {0} with |d|_1 <= 1
+ *     (connectivity 6), <= 2 (18) or <= 3 (26).  A neighbour cell outside [-65536, 65535] on any axis does not exist (it is
+ *     dropped before a key is made of it: cell 65535 and cell -65536 of an axis are not neighbours).
+ *   Components.  The connected components of that graph.  records: the records in its nodes; cells: its nodes; first: the smallest
+ *     global id among its records; cell_lo / cell_hi: the box of its cells; sum_cell[k]: the sum over its records of cell[k] +
+ *     65536 (the centroid in cells is sum_cell[k] / records - 65536 + 1/2).
+ *   Small.  A component with records < min_records is small: its records are labelled SMALL, it gets no number and no row and
+ *     counts in info->small_components.
+ *   Numbering.  The other components are numbered 0, 1, ... in ascending `first` -- in set order of first appearance.  Their
+ *     records are labelled with that number; row i of `components` describes component i.  Rows i >= cap are not written;
+ *     info->components is the total whatever cap is.  info->largest: the largest `records` of any component, small ones included
+ *     (0 without a component).  info->counts: records labelled with a number, SMALL, SKIPPED, LOOSE; info->cells: all nodes.
+ *   The result is a function of the multiset of (global id, record) pairs alone: the chunking, the split into files, the table's
+ *     size and hash order and the device's order do not change a bit of it.
+ *   Example, voxel_mm 1000 (V = 65536), origin 0, one class: centres A (.5, .5, .5), B (1.5, .5, .5), C (2.5, 1.5, .5),
+ *     D (3.5, 2.5, 1.5), E (5.5, .5, .5) with the ids 0..4 lie in the cells (0,0,0) (1,0,0) (2,1,0) (3,2,1) (5,0,0).  B-C differ by
+ *     (1,1,0), C-D by (1,1,1).  Connectivity 6: {A,B} {C} {D} {E}; 18: {A,B,C} {D} {E}; 26: {A,B,C,D} {E}.  With 26 and
+ *     min_records 2, E is SMALL and there is one row: first 0, records 4, cells 4, cell_lo (0,0,0), cell_hi (3,2,1), sum_cell
+ *     (4 * 65536 + 6, 4 * 65536 + 3, 4 * 65536 + 1).
+ *   out_path.  One map file, written as sm_compare_maps writes its own (through "<out_path>.segment.tmp" and a rename; the header's
+ *     frame range spans the files'), of the records whose label kind -- bit 0 a number, 1 SMALL, 2 SKIPPED, 3 LOOSE -- has its bit
+ *     in write_mask, verbatim and in set order.  No such record: a valid empty file.  info->written is its record count.
+ *   Cost.  Two readings of the set.  The first claims every node in an open-addressing table (key, records, smallest id); one
+ *     launch over the table's slots then unites every node with the neighbours of the forward half of its neighbourhood (3, 9 or
+ *     13 keys) by a lock-free union-find -- only roots are hooked, the larger slot under the smaller, by compare-and-swap --, one
+ *     flattens the trees, one sums the components at their roots (SM_SEGMENT_NO_COMBINE=1, read per call, switches the in-wave
+ *     combination of that step off; the result is the same).  The second reading labels.  Every device loop is bounded by the
+ *     table's size: a bound reached is SM_E_STALL, never a hang.
+ * sm_segment_stats: of the context's last sm_segment_maps.
+ * Errors.  SM_E_ARG: NULLs other than labels, components and out_path; components == NULL with cap != 0; a parameter outside the
+ *   ranges below; write_mask outside 1..15 when out_path is given; a non-finite origin; out_path equal to a source path; the
+ *   header and set checks of sm_render_image_maps (every header before any work); a call between sm_stage_conflict and
+ *   sm_stage_cull; sm_segment_stats before any call.  SM_E_UNSUPPORTED: a sharded or rig context.  SM_E_CAPACITY: more than
+ *   max_cells nodes; a set of more than 2^31 - 1 records; a table of more than 2^31 slots.  SM_E_STALL as above.  In the last two
+ *   cases no label, no row and no file is written. */
+#define SM_SEGMENT_LOOSE   0xFFFFFFFEu   /* an irregular record */
+#define SM_SEGMENT_SMALL   0xFFFFFFFDu   /* its component has fewer than min_records records */
+#define SM_SEGMENT_SKIPPED 0xFFFFFFFCu   /* its class is not in class_mask */
+typedef struct sm_segment_params {
+    int32_t  voxel_mm;        /* edge of a cell, 10..10000                                            default 200 */
+    int32_t  connectivity;    /* 6, 18 or 26                                                          default 26 */
+    int32_t  by_class;        /* 0 / 1; 1: only cells of one class connect                            default 1 */
+    uint32_t class_mask[8];   /* bit c & 31 of word c >> 5: class c takes part                        default all ones */
+    uint32_t min_records;     /* >= 1: a component of fewer records is small                          default 1 */
+    uint32_t write_mask;      /* bit 0 numbered components, 1 SMALL, 2 SKIPPED, 3 LOOSE; 1..15; read only if out_path is given; default 1 */
+    uint32_t max_cells;       /* nodes the table may hold, >= 1                                       default 1 << 24 */
+    float    origin[3];       /* of the grid, metres                                                  default 0 */
+} sm_segment_params;
+typedef struct sm_segment_component {   /* 64 bytes */
+    uint32_t first;           /* smallest global id among its records */
+    uint32_t records, cells;
+    int32_t  cls;             /* the class with by_class, else -1 */
+    int32_t  cell_lo[3], cell_hi[3];
+    uint64_t sum_cell[3];     /* sum over its records of cell[k] + 65536 */
+} sm_segment_component;
+typedef struct sm_segment_info {
+    uint64_t records;         /* of the set */
+    uint64_t counts[4];       /* records labelled with a number, SMALL, SKIPPED, LOOSE */
+    uint64_t written;         /* records of the file at out_path (0 without one) */
+    uint32_t cells;           /* nodes */
+    uint32_t components;      /* numbered components, whatever cap is */
+    uint32_t small_components;
+    uint32_t largest;         /* records of the largest component */
+} sm_segment_info;
+typedef struct sm_segment_stats_t {
+    uint32_t chunks;          /* pieces of at most 2^20 records, both readings together */
+    uint32_t launches;
+    uint32_t readings;        /* passes over the set: 2 */
+    float read_ms;            /* host: reading the files */
+    float table_ms;           /* device: the table's initialisation and reading 1's inserts */
+    float link_ms;            /* device: link, flatten and reduce */
+    float label_ms;           /* device: reading 2's marks, ranks, rows, labels and kept records */
+    float write_ms;           /* host: labels and kept records back from the device and into the file */
+    float total_ms;
+} sm_segment_stats_t;
+int sm_default_segment_params(sm_segment_params *p);         /* pure, no context */
+int sm_segment_maps(sm_ctx *s, const sm_map_source *src, const sm_segment_params *p,
+                    uint32_t *labels /* by global id; may be NULL */,
+                    sm_segment_component *components, uint32_t cap /* rows at components; NULL needs 0 */,
+                    const char *out_path /* may be NULL */, sm_segment_info *info);
+int sm_segment_stats(sm_ctx *s, sm_segment_stats_t *out);
+
 /* ---- per-pass entry points (GlobalModel / IndexMap methods), synchronous ---- */
 /* Upload RGB / metric depth / semantic textures directly (bypasses p0). */
 int sm_set_frame(sm_ctx *s, const uint8_t *rgb, const float *depth_metric,

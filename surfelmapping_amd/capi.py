@@ -51,6 +51,7 @@ SYMBOLS = (
     "sm_default_register_params", "sm_register_maps", "sm_register_debug", "sm_register_stats",
     "sm_default_compare_params", "sm_compare_maps", "sm_compare_stats",
     "sm_default_tile_params", "sm_tile_maps", "sm_tile_stats",
+    "sm_default_segment_params", "sm_segment_maps", "sm_segment_stats",
 )
 
 SM_COLL_SUM, SM_COLL_MIN, SM_COLL_GATHER = 0, 1, 2
@@ -520,6 +521,84 @@ def tile_params(**over) -> SmTileParams:
     return p
 
 
+SM_SEGMENT_LOOSE, SM_SEGMENT_SMALL, SM_SEGMENT_SKIPPED = 0xFFFFFFFE, 0xFFFFFFFD, 0xFFFFFFFC
+SEGMENT_KINDS = ("NUMBERED", "SMALL", "SKIPPED", "LOOSE")                # the bits of write_mask, the entries of info.counts
+
+
+class SmSegmentParams(C.Structure):
+    _fields_ = [("voxel_mm", C.c_int32), ("connectivity", C.c_int32), ("by_class", C.c_int32), ("class_mask", C.c_uint32 * 8),
+                ("min_records", C.c_uint32), ("write_mask", C.c_uint32), ("max_cells", C.c_uint32), ("origin", C.c_float * 3)]
+
+
+class SmSegmentComponent(C.Structure):
+    _fields_ = [("first", C.c_uint32), ("records", C.c_uint32), ("cells", C.c_uint32), ("cls", C.c_int32), ("cell_lo", C.c_int32 * 3),
+                ("cell_hi", C.c_int32 * 3), ("sum_cell", C.c_uint64 * 3)]
+
+
+class SmSegmentInfo(C.Structure):
+    _fields_ = [("records", C.c_uint64), ("counts", C.c_uint64 * 4), ("written", C.c_uint64), ("cells", C.c_uint32), ("components", C.c_uint32),
+                ("small_components", C.c_uint32), ("largest", C.c_uint32)]
+
+
+class SmSegmentStats(C.Structure):
+    _fields_ = [("chunks", C.c_uint32), ("launches", C.c_uint32), ("readings", C.c_uint32), ("read_ms", C.c_float), ("table_ms", C.c_float),
+                ("link_ms", C.c_float), ("label_ms", C.c_float), ("write_ms", C.c_float), ("total_ms", C.c_float)]
+
+
+# a row of the component table as a numpy record: sm_segment_component, 64 bytes
+SEGMENT_COMPONENT = np.dtype([("first", "<u4"), ("records", "<u4"), ("cells", "<u4"), ("cls", "<i4"), ("cell_lo", "<i4", 3), ("cell_hi", "<i4", 3),
+                              ("sum_cell", "<u8", 3)])
+assert SEGMENT_COMPONENT.itemsize == C.sizeof(SmSegmentComponent) == 64
+
+
+def default_segment_params() -> SmSegmentParams:
+    """sm_default_segment_params: voxel_mm 200, connectivity 26, by_class 1, every class, min_records 1, write_mask 1 (the records of
+    numbered components), max_cells 1 << 24, origin (0, 0, 0)"""
+    p = SmSegmentParams()
+    load().sm_default_segment_params(C.byref(p))
+    return p
+
+
+def segment_params(**over) -> SmSegmentParams:
+    """default_segment_params() with fields overridden; origin takes a sequence of three, class_mask eight words or an iterable of
+    the classes that take part (`classes=` does the latter too)"""
+    p = default_segment_params()
+    for k, v in over.items():
+        if k == "classes":
+            p.class_mask[:] = segment_class_mask(v)
+        elif not hasattr(p, k):
+            raise KeyError(k)
+        elif k == "origin":
+            p.origin[:] = [float(x) for x in v]
+        elif k == "class_mask":
+            p.class_mask[:] = [int(x) for x in v]
+        else:
+            setattr(p, k, v)
+    return p
+
+
+def segment_class_mask(classes) -> list:
+    """the eight words of class_mask with the bits of `classes` (0..255) set"""
+    words = [0] * 8
+    for c in classes:
+        if not 0 <= int(c) <= 255:
+            raise ValueError(c)
+        words[int(c) >> 5] |= 1 << (int(c) & 31)
+    return words
+
+
+def segment_boxes(components, voxel_mm=200, origin=(0.0, 0.0, 0.0)):
+    """(lo, hi, centroid), float64[n, 3] each, in metres, of the rows of a component table: the box of a component's cells -- from
+    the low face of cell_lo to the high face of cell_hi -- and the mean over its records of their cells' centres"""
+    c = np.asarray(components, SEGMENT_COMPONENT).reshape(-1)
+    edge = ((int(voxel_mm) * 65536 + 500) // 1000) / 65536.0
+    o = np.asarray([np.float32(v) for v in origin], np.float64)
+    lo = o + c["cell_lo"].astype(np.float64) * edge
+    hi = o + (c["cell_hi"].astype(np.float64) + 1.0) * edge
+    mean = c["sum_cell"].astype(np.float64) / np.maximum(c["records"], 1).astype(np.float64)[:, None] - 65536.0 + 0.5
+    return lo, hi, o + mean * edge
+
+
 SM_REGISTER_OK, SM_REGISTER_LOST, SM_REGISTER_DEGENERATE, SM_REGISTER_NO_TARGET, SM_REGISTER_NO_SOURCE = 0, 1, 2, 3, 4
 REGISTER_STATUS = {SM_REGISTER_OK: "OK", SM_REGISTER_LOST: "LOST", SM_REGISTER_DEGENERATE: "DEGENERATE",
                    SM_REGISTER_NO_TARGET: "NO_TARGET", SM_REGISTER_NO_SOURCE: "NO_SOURCE"}
@@ -970,6 +1049,10 @@ def load():
     L.sm_default_tile_params.argtypes = [tpp]
     L.sm_tile_maps.argtypes = [vp, msp, tpp, C.c_char_p]
     L.sm_tile_stats.argtypes = [vp, C.POINTER(SmTileStats)]
+    spp = C.POINTER(SmSegmentParams)
+    L.sm_default_segment_params.argtypes = [spp]
+    L.sm_segment_maps.argtypes = [vp, msp, spp, C.c_void_p, C.c_void_p, C.c_uint32, C.c_char_p, C.POINTER(SmSegmentInfo)]
+    L.sm_segment_stats.argtypes = [vp, C.POINTER(SmSegmentStats)]
     for name in SYMBOLS:
         getattr(L, name)          # AttributeError here = the library does not match the header
     _lib = L
@@ -1941,6 +2024,46 @@ class SurfelMap:
         st = SmRegisterStats()
         self._chk(self._L.sm_register_stats(self._h, C.byref(st)), "sm_register_stats")
         return {k: getattr(st, k) for k, _ in SmRegisterStats._fields_}
+
+    # -- segmentation of a map set into connected voxel components (sm_segment_maps)
+    def segment_maps(self, paths, include_model=False, labels=True, max_components=1 << 20, out_path=None, **params) -> dict:
+        """The records of the map set `paths` (then, with include_model, the live model) grouped into connected components of
+        occupied voxel cells (sm_segment_maps; tests/segment_ref.py restates it).  params: the fields of segment_params().
+        out_path: the records whose label kind is in write_mask (default: those of numbered components, which with min_records
+        N drops every speck of fewer than N records) as one map file, verbatim and in set order.  Nothing else is changed.
+        Returns dict(labels: uint32[records] by global id -- a component's number, or SM_SEGMENT_SMALL / SKIPPED / LOOSE -- or None
+        with labels=False; components: SEGMENT_COMPONENT[min(components, max_components)], row i for number i (segment_boxes
+        gives them in metres); info: records, counts by kind name, counts_by_kind, written, cells, components, small_components,
+        largest)."""
+        p = segment_params(**params)
+        src = map_source(paths, include_model=include_model)
+        info = SmSegmentInfo()
+        lab = None
+        if labels:
+            # the records of the set are known from the headers; the live model's count from the context
+            n = sum(_map_records(q) for q in paths)
+            if include_model:
+                live = C.c_uint32()
+                self._chk(self._L.sm_download_model_aos(self._h, None, 0, C.byref(live)), "sm_download_model_aos")
+                n += live.value
+            lab = np.full(n, 0xFFFFFFFF, np.uint32)
+        cap = int(max_components)
+        rows = np.zeros(cap, SEGMENT_COMPONENT)
+        out = None if out_path is None else os.fsencode(out_path)
+        self._chk(self._L.sm_segment_maps(self._h, C.byref(src), C.byref(p), _ptr(lab), _ptr(rows) if cap else None, cap, out, C.byref(info)),
+                  "sm_segment_maps")
+        counts = [int(v) for v in info.counts]
+        d = dict(records=int(info.records), counts=dict(zip(SEGMENT_KINDS, counts)), counts_by_kind=counts, written=int(info.written),
+                 cells=int(info.cells), components=int(info.components), small_components=int(info.small_components), largest=int(info.largest))
+        if lab is not None and len(lab) != d["records"]:
+            raise SurfelMapError("segment_maps", SM_E_ARG, "the set changed while it was segmented")
+        return dict(labels=lab, components=rows[:min(cap, d["components"])].copy(), info=d)
+
+    def segment_stats(self) -> dict:
+        """of the last segment_maps: chunks, launches, readings, read_ms, table_ms, link_ms, label_ms, write_ms, total_ms"""
+        st = SmSegmentStats()
+        self._chk(self._L.sm_segment_stats(self._h, C.byref(st)), "sm_segment_stats")
+        return {k: getattr(st, k) for k, _ in SmSegmentStats._fields_}
 
     # -- change detection between two map sets (sm_compare_maps)
     def compare_maps(self, query_paths, reference_paths, pose=None, query_model=False, reference_model=False, out_path=None, labels=True,

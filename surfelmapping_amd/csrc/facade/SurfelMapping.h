@@ -407,6 +407,42 @@ public:
                compareMaps(aFiles, bFiles, poseAToB, outVanished, params, vanished) >= 0;
     }
 
+    // The records of the map set `mapFiles`, then (withModel) of the live model, grouped into objects (sm_segment_maps; DESIGN.md
+    // "4t. Segmentation"): connected components of occupied voxel cells, numbered in set order of first appearance.  components:
+    // a row per numbered component (the set is segmented twice: once to count them, once to fill the vectors);
+    // labels (may be null): per record of the set its component's number, or SM_SEGMENT_SMALL / SKIPPED / LOOSE.  outPath (may be
+    // empty): the records whose label kind is in params->write_mask -- by default those of numbered components, so that
+    // min_records N drops every speck of fewer than N records -- as one map file, verbatim and in set order.  params: null = the
+    // defaults.  Nothing else is changed.  Returns the numbered components, or -1 with the error printed.
+    long segmentMaps(const std::vector<std::string> &mapFiles, const std::string &outPath, const sm_segment_params *params,
+                     std::vector<sm_segment_component> &components, std::vector<uint32_t> *labels = nullptr, bool withModel = false,
+                     sm_segment_info *info = nullptr)
+    {
+        std::vector<const char *> paths;
+        for (const std::string &f : mapFiles) paths.push_back(f.c_str());
+        const sm_map_source src{paths.data(), (uint32_t)paths.size(), withModel ? 1 : 0};
+        sm_segment_params p;
+        sm_default_segment_params(&p);
+        if (params) p = *params;
+        const char *out = outPath.empty() ? nullptr : outPath.c_str();
+        sm_segment_info got;
+        (void)sm_sync(ctx_);                                             // (SM_FACADE_ASYNC: frames may still be in flight)
+        // the first call counts (it writes no row, no label and no file), the second fills vectors of the right size
+        if (sm_segment_maps(ctx_, &src, &p, nullptr, nullptr, 0, nullptr, &got) != SM_OK) {
+            std::printf("segmentMaps: %s\n", sm_last_error());
+            return -1;
+        }
+        components.assign(got.components, sm_segment_component{});
+        if (labels) labels->assign((size_t)got.records, 0u);
+        if (sm_segment_maps(ctx_, &src, &p, labels && got.records ? labels->data() : nullptr, got.components ? components.data() : nullptr, got.components,
+                            out, &got) != SM_OK) {
+            std::printf("segmentMaps: %s\n", sm_last_error());
+            return -1;
+        }
+        if (info) *info = got;
+        return (long)got.components;
+    }
+
     // The second sensor's dump: what a lidar `sensor` (sm_lidar_sensor; sm_default_lidar_sensor) at each of `poses` (sensor->world,
     // the camera's axes) measures in the live model, written as <path>/velodyne/%06d.bin next to acquireImages' folders, in KITTI's
     // velodyne layout: per return four floats, (z, -x, -y) of t*d in the sensor frame -- x forward, y left, z up -- and the

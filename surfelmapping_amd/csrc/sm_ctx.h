@@ -318,7 +318,8 @@ struct Blend {
 // RankedOutput: simplification's second pass, change detection's query), allocated by the first such call.  Calls on one context
 // never overlap, so they share it.
 struct RankScratch {
-    Dev<uint32_t> d_blk_cnt, d_blk_base;   // kept records per block of 256 records of a chunk, their rank in the output
+    static constexpr uint32_t BLOCKS = (1u << 20) / 256u;   // the blocks of 256 records of a chunk: one plane
+    Dev<uint32_t> d_blk_cnt, d_blk_base;   // two planes: kept records per block of 256 records of a chunk, their rank in the output
     Dev<uint2> d_info;                 // [2]: (first rank, kept records) of the chunk in buffer c & 1
     Host<uint2> h_info;                // pinned, [2]
     Dev<float4> d_out[2];              // the kept records of a chunk (sm_simplify: [0] holds the whole output)
@@ -369,6 +370,19 @@ struct Tile {
     static constexpr int N_EV = 10;    // around what runs outside a chunk stream and around the sort; per piece buffer (two): around the gather, after the copy
     Event ev[N_EV];
     sm_tile_stats_t stats{};
+    bool stats_valid = false;
+};
+
+// segmentation (sm_segment.hip, sm_k_segment.h): the scratch of one chunk's labelling beside the context's RankScratch, the buffers
+// its labels leave through, the tallies and the last call's.  The table and the component rows live for one call.
+struct Segment {
+    Dev<uint32_t> d_code;              // per record of a chunk: its component's root slot | SMALL | SKIPPED | LOOSE
+    Dev<uint32_t> d_label[2];          // per record of the chunk in buffer c & 1: its label
+    Host<uint32_t> h_label[2];         // pinned: a chunk's labels on their way to the caller
+    Dev<uint32_t> d_tally;             // the table's tally words (SIMP_RUN: the kept records' running rank), the openers', the counts
+    Host<uint32_t> h_tally;            // pinned
+    Event ev[8];                       // around the memsets, reading 1's model, link to reduce, a chunk of reading 2's model
+    sm_segment_stats_t stats{};
     bool stats_valid = false;
 };
 
@@ -626,6 +640,7 @@ struct sm_ctx {
     Compare cmp;
     RankScratch ranked;
     Tile tile;
+    Segment seg;
 };
 
 namespace sm_impl __attribute__((visibility("hidden"))) {

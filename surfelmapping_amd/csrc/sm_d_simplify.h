@@ -1,5 +1,5 @@
 // sm_d_simplify.h -- the voxel-cell table as device functions, for every source that fills or reads such a table (sm_k_simplify.h;
-// sm_k_voxel.h; through sm_d_register.h, sm_k_register.h and sm_k_compare.h; sm_k_tile.h, which keeps tiles and counts in one): the regular-record test, the key, a record's
+// sm_k_voxel.h; through sm_d_register.h, sm_k_register.h and sm_k_compare.h; sm_k_tile.h, which keeps tiles and counts in one; sm_k_segment.h, whose slots are the nodes of a union-find): the regular-record test, the key, a record's
 // contribution, the probe, the insert in its pieces -- head of a run, in-wave combination, claim, adds --, a cell's merged
 // position, normal and record, and the ranks of a pass that writes.  No kernels: a kernel is defined in the one header of the
 // source that launches it.
@@ -158,15 +158,22 @@ __device__ __forceinline__ bool simp_head(const SimplifyArgs &a, unsigned long l
     return reg && !((threadIdx.x & 63) > 0 && prev == key);
 }
 
+// The last lane of this lane's run; all 64 lanes call it with what simp_head gave
+__device__ __forceinline__ int simp_run_last(bool reg, bool head)
+{
+    const int lane = threadIdx.x & 63;
+    const unsigned long long bounds = __ballot(head || !reg);                    // first lanes of runs, and every lane without a key
+    const unsigned long long above = lane == 63 ? 0ull : bounds >> (lane + 1);
+    return above ? lane + __ffsll(above) - 1 : 63;
+}
+
 // The in-wave combination: a head's contribution becomes the sum of its run's (a segmented shuffle reduction); returns simp_head
 __device__ __forceinline__ bool simp_combine(const SimplifyArgs &a, unsigned long long key, bool reg, SimpContrib &c)
 {
     const int lane = threadIdx.x & 63;
     const bool head = simp_head(a, key, reg);
     if (__ballot(reg && !head)) {                        // wave-uniform: some run in this wave is longer than one lane
-        const unsigned long long bounds = __ballot(head || !reg);                // first lanes of runs, and every lane without a key
-        const unsigned long long above = lane == 63 ? 0ull : bounds >> (lane + 1);
-        const int last = above ? lane + __ffsll(above) - 1 : 63;                 // the last lane of this lane's run
+        const int last = simp_run_last(reg, head);
         for (int o = 1; o < 64; o <<= 1) {
             const bool take = lane + o <= last;
             if (!__ballot(take)) break;

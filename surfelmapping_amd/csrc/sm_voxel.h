@@ -1,4 +1,4 @@
-// sm_voxel.h -- private to sm_simplify.hip, sm_register.hip, sm_compare.hip, sm_tile.hip and sm_voxel.hip, which defines what is declared
+// sm_voxel.h -- private to sm_simplify.hip, sm_register.hip, sm_compare.hip, sm_tile.hip, sm_segment.hip and sm_voxel.hip, which defines what is declared
 // here: what the users of a voxel table do alike on the host.  The grid and the table's size from a call's parameters and the
 // tally's verdict (all three); the lookup table -- sums finished into one RegCell per slot, with or without a cover table of keys
 // -- of registration and change detection; the ranked output -- what a pass keeps of every chunk, in order, in one map file -- of
@@ -43,7 +43,9 @@ void frame_range(const sm_mapset::ReadSet &set, int32_t &start_id, int32_t &end_
 // One call's ranked output on the context's RankScratch.  A chunk's kernels count what they keep per block of 256 (blk_cnt), scan()
 // ranks the blocks on top of the call's running rank, the caller's emit kernel writes the kept records to out(q); fetch(q) brings
 // the chunk's count to the host, stage(q) and write(q) its records into the file.  Without open() there is no file: sm_simplify's whole output
-// stays on the device (out(0), no info), a change detection that only labels writes nothing.
+// stays on the device (out(0), no info), a change detection that only labels writes nothing.  A pass that ranks two things at once
+// (segmentation: the kept records and the components' openers) counts the second in plane 1 of the block counts and scans it on
+// top of a running rank of its own.
 struct RankedOutput {
     sm_ctx *s;
     RankScratch &rs;
@@ -53,8 +55,8 @@ struct RankedOutput {
 
     RankedOutput(sm_ctx *s_, const char *who_) : s(s_), rs(s_->ranked), who(who_) {}
     bool writes() const { return !tmp.empty(); }
-    uint32_t *blk_cnt() const { return rs.d_blk_cnt.get(); }
-    const uint32_t *blk_base() const { return rs.d_blk_base.get(); }
+    uint32_t *blk_cnt(int plane = 0) const { return rs.d_blk_cnt.get() + plane * RankScratch::BLOCKS; }
+    const uint32_t *blk_base(int plane = 0) const { return rs.d_blk_base.get() + plane * RankScratch::BLOCKS; }
     const uint2 *info(int q) const { return rs.d_info.get() + q; }
     float4 *out(int q) const { return rs.d_out[q].get(); }
 
@@ -63,8 +65,8 @@ struct RankedOutput {
     // ... with both buffers for the largest chunk of `set` and of `cnt` live records, and "<out_path><suffix>" open with the frame
     // range of the set's files
     int open(const char *out_path, const char *suffix, const sm_mapset::ReadSet &set, uint32_t cnt);
-    // nblk blocks of a chunk ranked on top of tally[SIMP_RUN]; q < 0: no info, the output is the whole call's
-    void scan(uint32_t nblk, uint32_t *tally, int q, uint32_t &launches);
+    // nblk blocks of a chunk (their counts in `plane`) ranked on top of tally[SIMP_RUN]; q < 0: no info, the output is the whole call's
+    void scan(uint32_t nblk, uint32_t *tally, int q, uint32_t &launches, int plane = 0);
     int fetch(int q);
     // the chunk's kept records through the staging's host buffer q (free until chunk c + 2 is read into it): stage() enqueues their
     // copy on `stream` and says how many there are, write() puts them into the file once the caller has waited for `stream`

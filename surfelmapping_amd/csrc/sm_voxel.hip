@@ -7,6 +7,7 @@
 using namespace sm;
 
 static constexpr uint32_t CHUNK = MapStaging::CHUNK;
+static_assert(RankScratch::BLOCKS == CHUNK / 256, "a plane of block counts holds a chunk's");
 static constexpr size_t LUT_SUM_BYTES = 8 * 7;           // per slot beside the key and the lookup record: SW, SP[3], SN[3]
 
 SimplifyArgs sm_impl::voxel_args(int32_t voxel_mm, int shift, const float origin[3], int split, uint32_t max_cells)
@@ -106,7 +107,7 @@ int sm_impl::RankedOutput::ensure(int q, size_t records)
 {
     if (!rs.d_info) {
         int rc;
-        if ((rc = dalloc(rs.d_blk_cnt, CHUNK / 256)) || (rc = dalloc(rs.d_blk_base, CHUNK / 256))) return rc;
+        if ((rc = dalloc(rs.d_blk_cnt, 2 * RankScratch::BLOCKS)) || (rc = dalloc(rs.d_blk_base, 2 * RankScratch::BLOCKS))) return rc;
         HIPCK(hipHostMalloc((void **)rs.h_info.put(), 2 * sizeof(uint2), hipHostMallocDefault));
         if ((rc = dalloc(rs.d_info, 2))) return rc;      // last: it marks the set complete
     }
@@ -129,10 +130,10 @@ int sm_impl::RankedOutput::open(const char *out_path, const char *suffix, const 
     return w.open(tmp, sm_mapfile::Writer::UNKNOWN, start_id, end_id, who, g_err) ? SM_OK : SM_E_ARG;
 }
 
-void sm_impl::RankedOutput::scan(uint32_t nblk, uint32_t *tally, int q, uint32_t &launches)
+void sm_impl::RankedOutput::scan(uint32_t nblk, uint32_t *tally, int q, uint32_t &launches, int plane)
 {
-    hipLaunchKernelGGL(k_rank_scan, dim3(1), dim3(1024), 0, s->stream, (const uint32_t *)rs.d_blk_cnt.get(), nblk, rs.d_blk_base.get(), tally,
-                       q < 0 ? nullptr : rs.d_info.get() + q);
+    hipLaunchKernelGGL(k_rank_scan, dim3(1), dim3(1024), 0, s->stream, (const uint32_t *)blk_cnt(plane), nblk, rs.d_blk_base.get() + plane * RankScratch::BLOCKS,
+                       tally, q < 0 ? nullptr : rs.d_info.get() + q);
     launches++;
 }
 

@@ -1514,6 +1514,113 @@ int sm_segment_maps(sm_ctx *s, const sm_map_source *src, const sm_segment_params
                     const char *out_path /* may be NULL */, sm_segment_info *info);
 int sm_segment_stats(sm_ctx *s, sm_segment_stats_t *out);
 
+/* ---- meshing: the records of a map set turned into a triangle mesh (DESIGN.md "4u. Meshing") ----
+ * sm_mesh_maps reads a map set ONCE -- an sm_map_source with the global ids of the map-set calls: the files in list order, each in
+ * file order, then (include_model) the live model -- and gives the surface its surfels lie on as an indexed triangle mesh: one
+ * plane per occupied voxel cell, a signed field sampled at the grid's lattice points, marching tetrahedra over the cubes between
+ * them.  Sources, model, tick, stored poses, fern keyframes and tracker state are untouched; frames in flight are waited for.
+ *   Definition, in integers and stated fp64 operations, none contracted (restated by tests/mesh_ref.py):
+ *   Grid.  The simplification's V, X, cell and off (off[k] = X[k] - cell[k] * V) and its regular-record test, with voxel_mm and
+ *     origin.  A record that is not regular is LOOSE.  A regular record whose class c (colour word >> 24) has bit c & 31 of
+ *     class_mask[c >> 5] clear is SKIPPED.  Otherwise it is OUTSIDE if some cell[k] lies outside [-65536 + reach, 65535 - reach]
+ *     (decided before a key is packed: every lattice point a record can reach is on the grid).  Every other record is USED.
+ *   Cells.  Per cell, of its USED records (no face and no class in the key): n; the simplification's SW, SP[3], SN[3], SC[3]; cmin,
+ *     the minimum of ((uint64)global id << 8) | c.  A cell with n < min_records does not exist anywhere below.  Its plane:
+ *     mp[k] = (SP[k] + SW / 2) / SW, an integer offset in the cell, and n_c = the simplification's merged normal of SN; if that
+ *     fails (all three components vanish) the cell has no plane: it exists, but adds nothing to F.
+ *   Lattice points.  l is an integer triple at position l * V.  Its inner cells are the 2 x 2 x 2 cells l - b, b in {0, 1}^3, its
+ *     outer cells the 4 x 4 x 4 cells c with l - 2 <= c <= l + 1.  reach 1: l is sampled iff an inner cell exists.  reach 2: iff
+ *     an outer cell exists.  Its contributors are the inner cells that exist; if none does (reach 2), all outer cells that exist.
+ *     Over the contributors in ascending lexicographic order of c - l, in fp64, beginning with 0.0:
+ *       F += (double)SW_c * ((n0 * e0 + n1 * e1) + n2 * e2),  e[k] = (double)((l[k] - c[k]) * V - mp_c[k]),  n_c widened from float
+ *     (a cell without a plane is left out of F only); W, NS[3], CS[3] are the integer sums of SW_c, SN_c, SC_c and cmin the minimum
+ *     of cmin_c over all contributors (so W >= 1).  l is inside iff F < 0.
+ *   Cubes.  The cube at l has the corners l + b.  It is meshed iff all eight are sampled.  It is cut into six Kuhn tetrahedra, one
+ *     per permutation (a, b, c) of the axes in lexicographic order: t0 = l, t1 = l + e_a, t2 = l + e_a + e_b, t3 = l + (1, 1, 1);
+ *     for an odd permutation t2 and t3 are exchanged, so that every tetrahedron is positively oriented.
+ *   Faces of a tetrahedron, by which corners are inside.  None with 0 or 4.  One corner i unlike the other three: take those in
+ *     ascending order j < k < l and exchange k and l if (i, j, k, l) is an odd permutation of (0, 1, 2, 3) (i odd); the triangle is
+ *     (v_ij, v_ik, v_il), its first and last exchanged if the lone corner is the outside one.  Two inside i < j, two outside
+ *     k < l: exchange k and l if (i, j, k, l) is odd; the triangles are (v_ik, v_il, v_jl), then (v_ik, v_jl, v_jk).  The
+ *     orientation is combinatorial, never from computed coordinates: face normals point from inside to outside, the way the
+ *     surfel normals point.  Each triangle's indices are then rotated so that the smallest comes first.
+ *   Vertices.  v_ab lies on the edge from lattice point a to b = a + d, d in {0, 1}^3 \ {0}; a owns it; its kind is d0 + 2 d1 +
+ *     4 d2 (every edge of a Kuhn tetrahedron is such an edge).  It exists iff a face refers to it.
+ *       t = A / (A - B), A = F_a * (double)W_b, B = F_b * (double)W_a   (one end is inside: 0 <= t <= 1, never 0 / 0)
+ *       pos[k] = (float)((double)origin[k] + ((double)(a[k] * V) + t * (double)(d[k] * V)) * (1.0 / 65536.0))
+ *       normal = the merged normal of NS_a + NS_b, or (0, 0, 0) if that fails
+ *       colour channel k = ((CS_a + CS_b)[k] + (W_a + W_b) / 2) / (W_a + W_b);  class = the low byte of min(cmin_a, cmin_b)
+ *     Zero-area triangles (t = 0) may occur and are kept.
+ *   Order.  Vertices ascending by (key of the owner, kind), the key the simplification's packing of l + 65536: lexicographic, x
+ *     major.  Faces ascending by (key of the cube's l, tetrahedron, triangle).
+ *   The result is a function of the multiset of (global id, record) pairs alone: the chunking, the split into files, the tables'
+ *     sizes and hash order and the device's order do not change a byte of it.
+ *   Example, voxel_mm 1000 (V = 65536), origin 0: one record at (.5, .5, .5) with normal +z.  Cell (0, 0, 0), mp = (32768, 32768,
+ *     32768); F(l) = w (l_z * 65536 - 32768): inside iff l_z <= 0, t = 1/2 on every cut edge.  reach 1: 8 lattice points, 1 cube,
+ *     9 vertices (on the 4 upright edges, the 4 upright face diagonals, the body diagonal), 8 faces, all at z = 0.5 exactly, every
+ *     face normal +z.  reach 2: 64 lattice points, 27 cubes, the 9 of the layer l_z = 0 cut: 49 vertices, 72 faces.
+ *   Output.  vertices: row i < vcap of the vertex list; faces: row i < fcap of the face list; rows beyond a cap are not written;
+ *     info carries the totals whatever the caps are.  vertices, faces and ply_path may each be NULL (NULL needs cap 0).
+ *   ply_path.  A binary little-endian PLY written through "<ply_path>.mesh.tmp" and a rename: per vertex x y z nx ny nz as float,
+ *     red green blue as uchar -- bytes 2, 1, 0 of the colour word, as the renderers map them -- and a uchar `class`; per face
+ *     `list uchar int vertex_indices`.  An empty mesh is a valid empty file.
+ *   Cost.  One reading into an open-addressing table of cells (in-wave combination of runs, 64-bit atomicCAS claims, integer
+ *     atomics).  The lanes of a wave then claim each of its cells' 8 or 64 lattice points in a second table sized from the cell
+ *     count (doubled and claimed again should it prove too small: sparse cells share few points); one launch sums the field
+ *     per lattice point; one classifies the cubes, counts their faces and marks the used edges at their owners; the owners of a
+ *     vertex or face are sorted by key (the tiling's radix sort), ranked, and two launches write vertices and faces, which come
+ *     back in pieces while the host writes the file.
+ * sm_mesh_stats: of the context's last sm_mesh_maps that succeeded (a call that fails leaves them as they were).
+ * Errors.  SM_E_ARG: NULLs other than vertices, faces and ply_path; a NULL buffer with a cap != 0; a parameter outside the ranges
+ *   below; a non-finite origin; ply_path equal to a source path; the header and set checks of sm_render_image_maps (every header
+ *   before any work); a call between sm_stage_conflict and sm_stage_cull; sm_mesh_stats before any call has succeeded.  SM_E_UNSUPPORTED: a
+ *   sharded or rig context.  SM_E_CAPACITY: more than max_cells cells in the table (whatever min_records is); more than 2^32 - 1
+ *   vertices or faces; a table of more than 2^31 slots; a set of more than 2^31 - 1 records.  Then nothing is written: no row, no
+ *   file, not info. */
+#define SM_MESH_USED    0
+#define SM_MESH_SKIPPED 1
+#define SM_MESH_LOOSE   2
+#define SM_MESH_OUTSIDE 3
+typedef struct sm_mesh_params {
+    int32_t  voxel_mm;        /* edge of a cell, 10..10000                                            default 100 */
+    int32_t  reach;           /* 1 or 2: the cells around a lattice point that make it sampled        default 2 */
+    uint32_t min_records;     /* >= 1: a cell of fewer records does not exist                         default 1 */
+    uint32_t class_mask[8];   /* bit c & 31 of word c >> 5: class c takes part                        default all ones */
+    uint32_t max_cells;       /* cells the table may hold, >= 1                                       default 1 << 24 */
+    float    origin[3];       /* of the grid, metres                                                  default 0 */
+} sm_mesh_params;
+typedef struct sm_mesh_vertex {         /* 28 bytes */
+    float    pos[3];
+    float    normal[3];
+    uint32_t colour;          /* laid out as a record's colour word: channels in bytes 0..2, the class in byte 3 */
+} sm_mesh_vertex;
+typedef struct sm_mesh_info {
+    uint64_t records;         /* of the set */
+    uint64_t counts[4];       /* records USED, SKIPPED, LOOSE, OUTSIDE */
+    uint32_t cells;           /* cells that exist (n >= min_records) */
+    uint32_t lattice_points;  /* sampled */
+    uint32_t cubes;           /* meshed */
+    uint32_t vertices, faces; /* the totals, whatever the caps are */
+    uint32_t reserved;
+} sm_mesh_info;
+typedef struct sm_mesh_stats_t {
+    uint32_t chunks;          /* pieces of at most 2^20 records read */
+    uint32_t launches;
+    float read_ms;            /* host: reading the files */
+    float table_ms;           /* device: the cell table's initialisation and inserts */
+    float field_ms;           /* device: lattice claim, field, cubes */
+    float sort_ms;            /* device: the owners listed, sorted and ranked */
+    float emit_ms;            /* device: vertices and faces written */
+    float write_ms;           /* host: rows back from the device, into the caller's buffers and the file */
+    float total_ms;
+} sm_mesh_stats_t;
+int sm_default_mesh_params(sm_mesh_params *p);               /* pure, no context */
+int sm_mesh_maps(sm_ctx *s, const sm_map_source *src, const sm_mesh_params *p,
+                 sm_mesh_vertex *vertices, uint32_t vcap /* rows at vertices; NULL needs 0 */,
+                 uint32_t *faces /* three indices a row */, uint32_t fcap /* rows at faces; NULL needs 0 */,
+                 const char *ply_path /* may be NULL */, sm_mesh_info *info);
+int sm_mesh_stats(sm_ctx *s, sm_mesh_stats_t *out);
+
 /* ---- per-pass entry points (GlobalModel / IndexMap methods), synchronous ---- */
 /* Upload RGB / metric depth / semantic textures directly (bypasses p0). */
 int sm_set_frame(sm_ctx *s, const uint8_t *rgb, const float *depth_metric,

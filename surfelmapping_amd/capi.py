@@ -52,6 +52,7 @@ SYMBOLS = (
     "sm_default_compare_params", "sm_compare_maps", "sm_compare_stats",
     "sm_default_tile_params", "sm_tile_maps", "sm_tile_stats",
     "sm_default_segment_params", "sm_segment_maps", "sm_segment_stats",
+    "sm_default_mesh_params", "sm_mesh_maps", "sm_mesh_stats",
 )
 
 SM_COLL_SUM, SM_COLL_MIN, SM_COLL_GATHER = 0, 1, 2
@@ -599,6 +600,93 @@ def segment_boxes(components, voxel_mm=200, origin=(0.0, 0.0, 0.0)):
     return lo, hi, o + mean * edge
 
 
+MESH_KINDS = ("USED", "SKIPPED", "LOOSE", "OUTSIDE")                     # the entries of a mesh's info.counts
+
+
+class SmMeshParams(C.Structure):
+    _fields_ = [("voxel_mm", C.c_int32), ("reach", C.c_int32), ("min_records", C.c_uint32), ("class_mask", C.c_uint32 * 8),
+                ("max_cells", C.c_uint32), ("origin", C.c_float * 3)]
+
+
+class SmMeshVertex(C.Structure):
+    _fields_ = [("pos", C.c_float * 3), ("normal", C.c_float * 3), ("colour", C.c_uint32)]
+
+
+class SmMeshInfo(C.Structure):
+    _fields_ = [("records", C.c_uint64), ("counts", C.c_uint64 * 4), ("cells", C.c_uint32), ("lattice_points", C.c_uint32), ("cubes", C.c_uint32),
+                ("vertices", C.c_uint32), ("faces", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SmMeshStats(C.Structure):
+    _fields_ = [("chunks", C.c_uint32), ("launches", C.c_uint32), ("read_ms", C.c_float), ("table_ms", C.c_float), ("field_ms", C.c_float),
+                ("sort_ms", C.c_float), ("emit_ms", C.c_float), ("write_ms", C.c_float), ("total_ms", C.c_float)]
+
+
+# a vertex of a mesh as a numpy record: sm_mesh_vertex, 28 bytes; colour is laid out as a record's colour word
+MESH_VERTEX = np.dtype([("pos", "<f4", 3), ("normal", "<f4", 3), ("colour", "<u4")])
+assert MESH_VERTEX.itemsize == C.sizeof(SmMeshVertex) == 28
+
+
+def default_mesh_params() -> SmMeshParams:
+    """sm_default_mesh_params: voxel_mm 100, reach 2, min_records 1, every class, max_cells 1 << 24, origin (0, 0, 0)"""
+    p = SmMeshParams()
+    load().sm_default_mesh_params(C.byref(p))
+    return p
+
+
+def mesh_params(**over) -> SmMeshParams:
+    """default_mesh_params() with fields overridden; origin takes a sequence of three, class_mask eight words or an iterable of the
+    classes that take part (`classes=` does the latter too)"""
+    p = default_mesh_params()
+    for k, v in over.items():
+        if k == "classes":
+            p.class_mask[:] = segment_class_mask(v)
+        elif not hasattr(p, k):
+            raise KeyError(k)
+        elif k == "origin":
+            p.origin[:] = [float(x) for x in v]
+        elif k == "class_mask":
+            p.class_mask[:] = [int(x) for x in v]
+        else:
+            setattr(p, k, v)
+    return p
+
+
+_PLY_PROPERTIES = ["property float x", "property float y", "property float z", "property float nx", "property float ny", "property float nz",
+                   "property uchar red", "property uchar green", "property uchar blue", "property uchar class"]
+
+
+def read_ply(path):
+    """(vertices: MESH_VERTEX[n], faces: uint32[m, 3]) of a file sm_mesh_maps wrote -- that layout alone: binary little-endian, per
+    vertex x y z nx ny nz as float and red green blue class as uchar, per face `list uchar int vertex_indices` of three.  The colour
+    word is put together again: blue, green, red in bytes 0..2, the class in byte 3."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header\n")
+    if end < 0:
+        raise ValueError(f"{path}: no PLY header")
+    lines = data[:end].decode("ascii").split("\n")
+    body = data[end + len(b"end_header\n"):]
+    if lines[:2] != ["ply", "format binary_little_endian 1.0"]:
+        raise ValueError(f"{path}: not a binary little-endian PLY")
+    lines = [l for l in lines[2:] if l and not l.startswith("comment")]
+    if (len(lines) != 13 or not lines[0].startswith("element vertex ") or lines[1:11] != _PLY_PROPERTIES or not lines[11].startswith("element face ")
+            or lines[12] != "property list uchar int vertex_indices"):
+        raise ValueError(f"{path}: not the layout sm_mesh_maps writes")
+    nv, nf = int(lines[0].split()[2]), int(lines[11].split()[2])
+    if len(body) != nv * 28 + nf * 13:
+        raise ValueError(f"{path}: {len(body)} bytes after the header, {nv} vertices and {nf} faces need {nv * 28 + nf * 13}")
+    raw = np.frombuffer(body, np.dtype([("pos", "<f4", 3), ("normal", "<f4", 3), ("rgbc", "u1", 4)]), nv)
+    vertices = np.zeros(nv, MESH_VERTEX)
+    vertices["pos"], vertices["normal"] = raw["pos"], raw["normal"]
+    c = raw["rgbc"].astype(np.uint32)
+    vertices["colour"] = c[:, 3] << 24 | c[:, 0] << 16 | c[:, 1] << 8 | c[:, 2]
+    rows = np.frombuffer(body, np.dtype([("n", "u1"), ("v", "<i4", 3)]), nf, nv * 28)
+    if nf and (rows["n"] != 3).any():
+        raise ValueError(f"{path}: a face that is no triangle")
+    return vertices, rows["v"].view(np.uint32).copy().reshape(-1, 3)
+
+
 SM_REGISTER_OK, SM_REGISTER_LOST, SM_REGISTER_DEGENERATE, SM_REGISTER_NO_TARGET, SM_REGISTER_NO_SOURCE = 0, 1, 2, 3, 4
 REGISTER_STATUS = {SM_REGISTER_OK: "OK", SM_REGISTER_LOST: "LOST", SM_REGISTER_DEGENERATE: "DEGENERATE",
                    SM_REGISTER_NO_TARGET: "NO_TARGET", SM_REGISTER_NO_SOURCE: "NO_SOURCE"}
@@ -1053,6 +1141,10 @@ def load():
     L.sm_default_segment_params.argtypes = [spp]
     L.sm_segment_maps.argtypes = [vp, msp, spp, C.c_void_p, C.c_void_p, C.c_uint32, C.c_char_p, C.POINTER(SmSegmentInfo)]
     L.sm_segment_stats.argtypes = [vp, C.POINTER(SmSegmentStats)]
+    mpp = C.POINTER(SmMeshParams)
+    L.sm_default_mesh_params.argtypes = [mpp]
+    L.sm_mesh_maps.argtypes = [vp, msp, mpp, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_char_p, C.POINTER(SmMeshInfo)]
+    L.sm_mesh_stats.argtypes = [vp, C.POINTER(SmMeshStats)]
     for name in SYMBOLS:
         getattr(L, name)          # AttributeError here = the library does not match the header
     _lib = L
@@ -2064,6 +2156,38 @@ class SurfelMap:
         st = SmSegmentStats()
         self._chk(self._L.sm_segment_stats(self._h, C.byref(st)), "sm_segment_stats")
         return {k: getattr(st, k) for k, _ in SmSegmentStats._fields_}
+
+    # -- a map set as a triangle mesh (sm_mesh_maps)
+    def mesh_maps(self, paths, include_model=False, ply_path=None, max_vertices=None, max_faces=None, **params) -> dict:
+        """The surface the records of the map set `paths` (then, with include_model, the live model) lie on, as an indexed triangle
+        mesh: one plane per occupied voxel cell, a signed field at the lattice points, marching tetrahedra (sm_mesh_maps;
+        tests/mesh_ref.py restates it).  params: the fields of mesh_params().  ply_path: the mesh as a binary PLY (read_ply reads it
+        back).  max_vertices / max_faces: rows to bring back; None: all of them, for which the set is first read once more to
+        count them.  Nothing else is changed.  Returns dict(vertices: MESH_VERTEX[..], faces: uint32[.., 3] -- counter-clockwise
+        seen from outside, the way the surfel normals point --, info: records, counts by kind name, counts_by_kind, cells,
+        lattice_points, cubes, vertices, faces: the totals whatever the caps are)."""
+        p = mesh_params(**params)
+        src = map_source(paths, include_model=include_model)
+        info = SmMeshInfo()
+        if max_vertices is None or max_faces is None:
+            self._chk(self._L.sm_mesh_maps(self._h, C.byref(src), C.byref(p), None, 0, None, 0, None, C.byref(info)), "sm_mesh_maps")
+            max_vertices = info.vertices if max_vertices is None else max_vertices
+            max_faces = info.faces if max_faces is None else max_faces
+        vcap, fcap = int(max_vertices), int(max_faces)
+        vertices, faces = np.zeros(vcap, MESH_VERTEX), np.zeros((fcap, 3), np.uint32)
+        out = None if ply_path is None else os.fsencode(ply_path)
+        self._chk(self._L.sm_mesh_maps(self._h, C.byref(src), C.byref(p), _ptr(vertices) if vcap else None, vcap, _ptr(faces) if fcap else None, fcap,
+                                       out, C.byref(info)), "sm_mesh_maps")
+        counts = [int(v) for v in info.counts]
+        d = dict(records=int(info.records), counts=dict(zip(MESH_KINDS, counts)), counts_by_kind=counts, cells=int(info.cells),
+                 lattice_points=int(info.lattice_points), cubes=int(info.cubes), vertices=int(info.vertices), faces=int(info.faces))
+        return dict(vertices=vertices[:min(vcap, d["vertices"])].copy(), faces=faces[:min(fcap, d["faces"])].copy(), info=d)
+
+    def mesh_stats(self) -> dict:
+        """of the last mesh_maps: chunks, launches, read_ms, table_ms, field_ms, sort_ms, emit_ms, write_ms, total_ms"""
+        st = SmMeshStats()
+        self._chk(self._L.sm_mesh_stats(self._h, C.byref(st)), "sm_mesh_stats")
+        return {k: getattr(st, k) for k, _ in SmMeshStats._fields_}
 
     # -- change detection between two map sets (sm_compare_maps)
     def compare_maps(self, query_paths, reference_paths, pose=None, query_model=False, reference_model=False, out_path=None, labels=True,

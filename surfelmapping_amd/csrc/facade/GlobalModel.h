@@ -138,6 +138,26 @@ public:
         return (long)st.records_out;
     }
 
+    // Not in the reference: the surface the model's surfels lie on as a triangle mesh (sm_mesh_maps on the live model alone;
+    // DESIGN.md "4u. Meshing"), written to plyPath as a binary PLY.  voxelMm: the cell edge; reach 2 closes the holes reach 1
+    // leaves where the surface clips a cell corner.  The model is unchanged.  Returns the faces, or -1 with the error printed.
+    long mesh(const std::string &plyPath, int voxelMm = 100, int reach = 2, sm_mesh_info *info = nullptr)
+    {
+        sm_mesh_params p;
+        sm_default_mesh_params(&p);
+        p.voxel_mm = voxelMm;
+        p.reach = reach;
+        const sm_map_source src{nullptr, 0u, 1};
+        sm_mesh_info got;
+        (void)sm_sync(ctx_);                                             // (SM_FACADE_ASYNC: frames may still be in flight)
+        if (sm_mesh_maps(ctx_, &src, &p, nullptr, 0, nullptr, 0, plyPath.empty() ? nullptr : plyPath.c_str(), &got) != SM_OK) {
+            std::printf("mesh: %s\n", sm_last_error());
+            return -1;
+        }
+        if (info) *info = got;
+        return (long)got.faces;
+    }
+
     // model read-back in the reference's AoS layout (12 floats / surfel, src/Config.cpp:17-32)
     std::vector<float> downloadModel()
     {

@@ -443,6 +443,40 @@ public:
         return (long)got.components;
     }
 
+    // The surface the records of the map set `mapFiles`, then (withModel) of the live model, lie on, as a triangle mesh
+    // (sm_mesh_maps; DESIGN.md "4u. Meshing"): one plane per occupied voxel cell, a signed field at the grid's lattice points,
+    // marching tetrahedra; faces counter-clockwise seen from outside, the way the surfel normals point.  plyPath (may be empty):
+    // the mesh as a binary little-endian PLY with per-vertex normal, colour and class.  params: null = the defaults (100 mm cells,
+    // reach 2).  vertices / faces (may be null): filled with the whole mesh, for which the set is read twice: once to count, once
+    // to fill.  Nothing else is changed.  Returns the faces, or -1 with the error printed.
+    long meshMaps(const std::vector<std::string> &mapFiles, const sm_mesh_params *params, const std::string &plyPath,
+                  std::vector<sm_mesh_vertex> *vertices = nullptr, std::vector<uint32_t> *faces = nullptr, bool withModel = false,
+                  sm_mesh_info *info = nullptr)
+    {
+        std::vector<const char *> paths;
+        for (const std::string &f : mapFiles) paths.push_back(f.c_str());
+        const sm_map_source src{paths.data(), (uint32_t)paths.size(), withModel ? 1 : 0};
+        sm_mesh_params p;
+        sm_default_mesh_params(&p);
+        if (params) p = *params;
+        const char *out = plyPath.empty() ? nullptr : plyPath.c_str();
+        sm_mesh_info got{};
+        (void)sm_sync(ctx_);                                             // (SM_FACADE_ASYNC: frames may still be in flight)
+        if ((vertices || faces) && sm_mesh_maps(ctx_, &src, &p, nullptr, 0, nullptr, 0, nullptr, &got) != SM_OK) {
+            std::printf("meshMaps: %s\n", sm_last_error());
+            return -1;
+        }
+        if (vertices) vertices->assign(got.vertices, sm_mesh_vertex{});
+        if (faces) faces->assign((size_t)got.faces * 3, 0u);
+        const uint32_t vcap = vertices ? got.vertices : 0u, fcap = faces ? got.faces : 0u;
+        if (sm_mesh_maps(ctx_, &src, &p, vcap ? vertices->data() : nullptr, vcap, fcap ? faces->data() : nullptr, fcap, out, &got) != SM_OK) {
+            std::printf("meshMaps: %s\n", sm_last_error());
+            return -1;
+        }
+        if (info) *info = got;
+        return (long)got.faces;
+    }
+
     // The second sensor's dump: what a lidar `sensor` (sm_lidar_sensor; sm_default_lidar_sensor) at each of `poses` (sensor->world,
     // the camera's axes) measures in the live model, written as <path>/velodyne/%06d.bin next to acquireImages' folders, in KITTI's
     // velodyne layout: per return four floats, (z, -x, -y) of t*d in the sensor frame -- x forward, y left, z up -- and the

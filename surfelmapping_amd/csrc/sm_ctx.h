@@ -386,6 +386,17 @@ struct Segment {
     bool stats_valid = false;
 };
 
+// meshing (sm_mesh.hip, sm_k_mesh.h): the tally, its pinned mirror, the events and the last call's tally.  The tables, the owners'
+// pairs and the mesh live for one call.
+struct Mesh {
+    Dev<uint32_t> d_tally;             // the cell table's tally words, the lattice table's, the running ranks, the counts, the totals
+    Host<uint32_t> h_tally;            // pinned
+    static constexpr int N_EV = 12;    // around the memsets, the model's inserts, claim to cubes, the owners' sort, the emit; per piece buffer (two): after the copy
+    Event ev[N_EV];
+    sm_mesh_stats_t stats{};
+    bool stats_valid = false;
+};
+
 // closing loops unasked (sm_loop.hip): the policy of sm_set_auto_loop and its tally
 struct AutoLoop {
     bool on = false;
@@ -641,6 +652,7 @@ struct sm_ctx {
     RankScratch ranked;
     Tile tile;
     Segment seg;
+    Mesh mesh;
 };
 
 namespace sm_impl __attribute__((visibility("hidden"))) {

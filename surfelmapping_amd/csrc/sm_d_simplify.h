@@ -1,5 +1,5 @@
 // sm_d_simplify.h -- the voxel-cell table as device functions, for every source that fills or reads such a table (sm_k_simplify.h;
-// sm_k_voxel.h; through sm_d_register.h, sm_k_register.h and sm_k_compare.h; sm_k_tile.h, which keeps tiles and counts in one; sm_k_segment.h, whose slots are the nodes of a union-find): the regular-record test, the key, a record's
+// sm_k_voxel.h; through sm_d_register.h, sm_k_register.h and sm_k_compare.h; sm_k_tile.h, which keeps tiles and counts in one; sm_k_segment.h, whose slots are the nodes of a union-find; sm_k_mesh.h, which keeps cells in one and lattice points in another): the regular-record test, the key, a record's
 // contribution, the probe, the insert in its pieces -- head of a run, in-wave combination, claim, adds --, a cell's merged
 // position, normal and record, and the ranks of a pass that writes.  No kernels: a kernel is defined in the one header of the
 // source that launches it.
@@ -130,12 +130,14 @@ __device__ __forceinline__ void simp_take(SimpContrib &c, int o, bool take)
 #undef SIMP_MAX
 }
 
-// the slot that holds `key`, claiming an empty one if `claim`; false after mask + 1 probes without it
-__device__ __forceinline__ bool simp_probe(const SimplifyTable &T, unsigned long long key, bool claim, uint32_t &slot, bool &claimed)
+// the slot that holds `key`, claiming an empty one if `claim`; false after mask + 1 probes without it -- or after `walk` probes, for
+// a caller whose table may fill (meshing's lattice table): in a table at most half full no walk comes near a thousand slots
+__device__ __forceinline__ bool simp_probe(const SimplifyTable &T, unsigned long long key, bool claim, uint32_t &slot, bool &claimed,
+                                           uint32_t walk = 0xFFFFFFFFu)
 {
     uint32_t sl = (uint32_t)simp_hash(key) & T.mask;
     claimed = false;
-    for (uint32_t i = 0; i <= T.mask; ++i) {
+    for (uint32_t i = 0; i <= T.mask && i < walk; ++i) {
         unsigned long long cur = T.key[sl];              // (a stale "empty" is settled by the CAS; a key never changes)
         if (cur == SIMP_EMPTY) {
             if (!claim) return false;
@@ -187,13 +189,14 @@ __device__ __forceinline__ bool simp_combine(const SimplifyArgs &a, unsigned lon
 // value, issued before this step waits for one of its own; then the distinct cells go to the tally, one add per wave, and with
 // them the error bits (1: more than max_cells cells, 2: no slot)
 template <typename Adds>
-__device__ __forceinline__ void simp_claim(const SimplifyArgs &a, const SimplifyTable &T, unsigned long long key, bool head, Adds adds)
+__device__ __forceinline__ void simp_claim(const SimplifyArgs &a, const SimplifyTable &T, unsigned long long key, bool head, Adds adds,
+                                           uint32_t walk = 0xFFFFFFFFu)
 {
     const int lane = threadIdx.x & 63;
     bool claimed = false, lost = false;
     if (head) {
         uint32_t sl = 0;
-        if (simp_probe(T, key, true, sl, claimed)) adds(sl);
+        if (simp_probe(T, key, true, sl, claimed, walk)) adds(sl);
         else lost = true;
     }
     const unsigned long long cb = __ballot(claimed);

@@ -1,6 +1,6 @@
 // sm_k_tile.h -- spatial tiling of a map set (DESIGN.md "4s. Spatial tiling"; the specification is sm_c_api.h's "tiling").
 // Included by sm_tile.hip only.  The grid, the probe and the claim are sm_d_simplify.h's; sm_voxel.hip ranks the
-// records a reading keeps (k_rank_scan) between k_tile_mark and k_tile_select.
+// records a reading keeps (k_rank_scan) between k_tile_mark and k_tile_select, and sorts a batch's (key, idx) pairs (pair_sort).
 // Records come as 48-byte AoS rows (three float4), a chunk of a map file or the exported model.
 //   k_tile_count        pass 1: per placed record its tile; the lanes of a wave with one tile are counted together, and only the
 //                       lowest of them claims the tile in the open-addressing table (64-bit atomicCAS, a probe loop bounded by
@@ -10,10 +10,6 @@
 //                       or the loose ones -- and, of the former, the OR and the AND of their keys (at most one atomic each per wave)
 //   k_tile_select<LOOSE> every kept record to slot `rank` of the batch (three 16-byte stores), its key to key[rank], rank to idx[rank];
 //                       ranks run on across chunks and files, so the batch fills in global-id order
-//   k_tile_sort_hist    one pass of the LSD radix sort, 8 bits: per block of 8192 keys the digits' histogram, built in LDS
-//   k_tile_sort_scan    ... the exclusive scan over (digit, block) in place, one workgroup, block_scan_1024 over tiles of 4096 entries
-//   k_tile_sort_scatter ... (key, idx) to their places, stable: a block takes its keys in 32 rounds of 256; per round a wave matches
-//                       its lanes on the digit (ballots over the 8 bits) and the waves' counts per digit go through LDS
 //   k_tile_gather       out[i] = rec[idx[i]]: three lanes per record, consecutive lanes store consecutive 16-byte pieces
 // No lane waits for another.  Integer atomics only.
 #pragma once
@@ -21,9 +17,6 @@
 #include "sm_d_simplify.h"
 
 namespace sm {
-
-constexpr uint32_t TILE_SORT_BLOCK = 8192u;              // keys per workgroup of a sort pass: 32 rounds of 256
-constexpr uint32_t TILE_SCAN_TILE = 4096u;               // entries per step of k_tile_sort_scan: four per lane
 
 struct TileRange { unsigned long long lo, hi; int shift3; };   // tiles lo..hi (lo > hi: none); shift3 = 3 * tile_shift
 
@@ -159,80 +152,6 @@ __global__ __launch_bounds__(256) void k_tile_select(const float4 *__restrict__ 
     out[(size_t)rank * 3 + 1] = rec[(size_t)t * 3 + 1];
     out[(size_t)rank * 3 + 2] = rec[(size_t)t * 3 + 2];
     if constexpr (!LOOSE) { key[rank] = M; idx[rank] = rank; }
-}
-
-// ---- the sort: block b of a pass has the keys [b * 8192, b * 8192 + 8192) of n; hist[digit * nblk + b]
-__global__ __launch_bounds__(256) void k_tile_sort_hist(const unsigned long long *__restrict__ key, uint32_t n, int shift, uint32_t nblk,
-                                                        uint32_t *__restrict__ hist)
-{
-    __shared__ uint32_t s_h[256];
-    s_h[threadIdx.x] = 0u;
-    __syncthreads();
-    const uint32_t first = blockIdx.x * TILE_SORT_BLOCK;
-#pragma unroll
-    for (uint32_t r = 0; r < TILE_SORT_BLOCK / 256u; ++r) {
-        const uint32_t i = first + r * 256u + threadIdx.x;
-        if (i < n) atomicAdd(&s_h[(uint32_t)(key[i] >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    hist[threadIdx.x * nblk + blockIdx.x] = s_h[threadIdx.x];
-}
-
-// entries: a multiple of 4 (256 digits per block)
-__global__ __launch_bounds__(1024) void k_tile_sort_scan(uint32_t *__restrict__ hist, uint32_t entries)
-{
-    __shared__ uint32_t s_scan[17];
-    uint32_t run = 0;
-    for (uint32_t b = 0; b < entries; b += TILE_SCAN_TILE) {
-        const uint32_t i = b + threadIdx.x * 4u;
-        uint4 v = make_uint4(0u, 0u, 0u, 0u);
-        if (i < entries) v = *(const uint4 *)(hist + i);
-        uint32_t tot;
-        const uint32_t at = run + block_scan_1024((v.x + v.y) + (v.z + v.w), &tot, s_scan);
-        if (i < entries) *(uint4 *)(hist + i) = make_uint4(at, at + v.x, at + v.x + v.y, at + v.x + v.y + v.z);
-        run += tot;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_tile_sort_scatter(const unsigned long long *__restrict__ key_in, const uint32_t *__restrict__ idx_in, uint32_t n,
-                                                           int shift, uint32_t nblk, const uint32_t *__restrict__ hist,
-                                                           unsigned long long *__restrict__ key_out, uint32_t *__restrict__ idx_out)
-{
-    __shared__ uint32_t s_run[256];                      // per digit: where the block's next key with it goes
-    __shared__ uint32_t s_wave[4][256];                  // per wave and digit: the keys of this round
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    s_run[threadIdx.x] = hist[threadIdx.x * nblk + blockIdx.x];
-#pragma unroll
-    for (int w = 0; w < 4; ++w) s_wave[w][threadIdx.x] = 0u;
-    __syncthreads();
-    const uint32_t first = blockIdx.x * TILE_SORT_BLOCK;
-    for (uint32_t r = 0; r < TILE_SORT_BLOCK / 256u; ++r) {
-        if (first + r * 256u >= n) break;                // (the same for every lane of the block)
-        const uint32_t i = first + r * 256u + threadIdx.x;
-        const bool valid = i < n;
-        const unsigned long long k = valid ? key_in[i] : 0ull;
-        const uint32_t d = (uint32_t)(k >> shift) & 255u;
-        unsigned long long m = __ballot(valid);          // the wave's lanes with this lane's digit
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const bool on = (d >> b) & 1u;
-            const unsigned long long bb = __ballot(on);
-            m &= on ? bb : ~bb;
-        }
-        const uint32_t below = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-        if (valid && below == 0u) s_wave[wave][d] = (uint32_t)__popcll(m);
-        __syncthreads();
-        if (valid) {
-            uint32_t at = s_run[d] + below;
-            for (int w = 0; w < wave; ++w) at += s_wave[w][d];
-            if (at < n) { key_out[at] = k; idx_out[at] = idx_in[i]; }
-        }
-        __syncthreads();
-        s_run[threadIdx.x] += (s_wave[0][threadIdx.x] + s_wave[1][threadIdx.x]) + (s_wave[2][threadIdx.x] + s_wave[3][threadIdx.x]);
-#pragma unroll
-        for (int w = 0; w < 4; ++w) s_wave[w][threadIdx.x] = 0u;
-        __syncthreads();
-    }
 }
 
 // ---- out[i] = rec[idx[first + i]], i < n: lane t moves 16-byte piece t % 3 of record t / 3.  cap: the records at rec

@@ -218,7 +218,7 @@ struct TileJob {
         if ((rc = dalloc(d_batch, (size_t)batch * 3)) || (rc = dalloc(d_key[0], batch)) || (rc = dalloc(d_key[1], batch)) || (rc = dalloc(d_idx[0], batch)) ||
             (rc = dalloc(d_idx[1], batch)))
             return rc;
-        return dalloc(d_hist, (size_t)((batch + TILE_SORT_BLOCK - 1) / TILE_SORT_BLOCK) * 256);
+        return dalloc(d_hist, pair_sort_hist_words(batch));
     }
     // a batch's reading begins: no rank given, no key seen
     int begin_batch()
@@ -260,26 +260,14 @@ struct TileJob {
         varying = ranks ? bits[0] ^ bits[1] : 0ull;
         return SM_OK;
     }
-    // n (key, idx) pairs of buffer 0 sorted by key, stably; which: the buffer that holds them then
+    // n (key, idx) pairs of buffer 0 sorted by key, stably (sm_voxel.h's pair sort); which: the buffer that holds them then
     int sort(uint32_t n, unsigned long long varying, int &which)
     {
         int rc;
-        const uint32_t nblk = (n + TILE_SORT_BLOCK - 1) / TILE_SORT_BLOCK;
-        which = 0;
         if ((rc = mark(s, tl.ev[EV_SORT0]))) return rc;
-        for (int shift = 0; shift < 56; shift += 8) {
-            if (!((varying >> shift) & 255ull)) continue;                            // (every key has the same digit here)
-            hipLaunchKernelGGL(k_tile_sort_hist, dim3(nblk), dim3(256), 0, s->stream, (const unsigned long long *)d_key[which].get(), n, shift, nblk,
-                               d_hist.get());
-            hipLaunchKernelGGL(k_tile_sort_scan, dim3(1), dim3(1024), 0, s->stream, d_hist.get(), nblk * 256u);
-            hipLaunchKernelGGL(k_tile_sort_scatter, dim3(nblk), dim3(256), 0, s->stream, (const unsigned long long *)d_key[which].get(),
-                               (const uint32_t *)d_idx[which].get(), n, shift, nblk, (const uint32_t *)d_hist.get(), d_key[which ^ 1].get(),
-                               d_idx[which ^ 1].get());
-            launches += 3;
-            tl.stats.sort_passes++;
-            which ^= 1;
-        }
-        HIPCK(hipGetLastError());
+        unsigned long long *const key[2] = {d_key[0].get(), d_key[1].get()};
+        uint32_t *const idx[2] = {d_idx[0].get(), d_idx[1].get()};
+        if ((rc = pair_sort(s, key, idx, d_hist.get(), n, varying, which, launches, tl.stats.sort_passes))) return rc;
         if ((rc = mark(s, tl.ev[EV_SORT1])) || (rc = add_marked(&tl.ev[EV_SORT0], &tl.stats.sort_ms))) return rc;
         return SM_OK;
     }

@@ -1,4 +1,4 @@
-// sm_voxel.h -- private to sm_simplify.hip, sm_register.hip, sm_compare.hip, sm_tile.hip, sm_segment.hip and sm_voxel.hip, which defines what is declared
+// sm_voxel.h -- private to sm_simplify.hip, sm_register.hip, sm_compare.hip, sm_tile.hip, sm_segment.hip, sm_mesh.hip and sm_voxel.hip, which defines what is declared
 // here: what the users of a voxel table do alike on the host.  The grid and the table's size from a call's parameters and the
 // tally's verdict (all three); the lookup table -- sums finished into one RegCell per slot, with or without a cover table of keys
 // -- of registration and change detection; the ranked output -- what a pass keeps of every chunk, in order, in one map file -- of
@@ -36,6 +36,13 @@ int lut_clear(sm_ctx *s, const LookupTable *t, int n);
 void lut_insert(sm_ctx *s, const LookupTable &t, const float4 *d_rec, uint32_t n, int keep_class, uint32_t &launches);
 // the sums become the lookup records
 void lut_finish(sm_ctx *s, const LookupTable &t, uint32_t &launches);
+
+// The pair sort of tiling and meshing: n (key, idx) pairs in key[0] / idx[0] sorted by key, stably, by an LSD radix sort of 8 bits a
+// pass over the bits 0..55; a pass whose digit no bit of `varying` touches is skipped (every key has the same digit there).
+// hist: pair_sort_hist_words(n) words.  which: the buffer that holds the pairs then; passes: those that ran.
+size_t pair_sort_hist_words(uint32_t n);
+int pair_sort(sm_ctx *s, unsigned long long *const key[2], uint32_t *const idx[2], uint32_t *hist, uint32_t n, unsigned long long varying, int &which,
+              uint32_t &launches, uint32_t &passes);
 
 // the frame range a file made of a set's records carries in its header: the one that spans the files' (0, 0 without files)
 void frame_range(const sm_mapset::ReadSet &set, int32_t &start_id, int32_t &end_id);

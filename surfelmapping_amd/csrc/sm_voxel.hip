@@ -1,6 +1,6 @@
 // sm_voxel.hip -- what the users of a voxel table share on the host (sm_voxel.h): the grid, the slot count and the tally's verdict
 // of simplification, registration and change detection; the lookup table of the latter two, its layout, initialisation, insert and
-// finish; the ranked output of the first and the last.  Kernels: sm_k_voxel.h.
+// finish; the ranked output of the first and the last; the pair sort of tiling and meshing.  Kernels: sm_k_voxel.h.
 #include "sm_voxel.h"
 #include "sm_k_voxel.h"
 
@@ -90,6 +90,29 @@ void sm_impl::lut_finish(sm_ctx *s, const LookupTable &t, uint32_t &launches)
 {
     hipLaunchKernelGGL(k_lut_finish, dim3(t.T.mask / 256u + 1u), dim3(256), 0, s->stream, t.a, t.T, t.lut);
     launches++;
+}
+
+// ---- the pair sort
+
+size_t sm_impl::pair_sort_hist_words(uint32_t n) { return (size_t)((n + PAIR_SORT_BLOCK - 1) / PAIR_SORT_BLOCK) * 256; }
+
+int sm_impl::pair_sort(sm_ctx *s, unsigned long long *const key[2], uint32_t *const idx[2], uint32_t *hist, uint32_t n, unsigned long long varying,
+                       int &which, uint32_t &launches, uint32_t &passes)
+{
+    const uint32_t nblk = (n + PAIR_SORT_BLOCK - 1) / PAIR_SORT_BLOCK;
+    which = 0;
+    for (int shift = 0; shift < 56; shift += 8) {
+        if (!((varying >> shift) & 255ull)) continue;                            // (every key has the same digit here)
+        hipLaunchKernelGGL(k_pair_sort_hist, dim3(nblk), dim3(256), 0, s->stream, (const unsigned long long *)key[which], n, shift, nblk, hist);
+        hipLaunchKernelGGL(k_pair_sort_scan, dim3(1), dim3(1024), 0, s->stream, hist, nblk * 256u);
+        hipLaunchKernelGGL(k_pair_sort_scatter, dim3(nblk), dim3(256), 0, s->stream, (const unsigned long long *)key[which], (const uint32_t *)idx[which], n,
+                           shift, nblk, (const uint32_t *)hist, key[which ^ 1], idx[which ^ 1]);
+        launches += 3;
+        passes++;
+        which ^= 1;
+    }
+    HIPCK(hipGetLastError());
+    return SM_OK;
 }
 
 // ---- the ranked output

@@ -1621,6 +1621,119 @@ int sm_mesh_maps(sm_ctx *s, const sm_map_source *src, const sm_mesh_params *p,
                  const char *ply_path /* may be NULL */, sm_mesh_info *info);
 int sm_mesh_stats(sm_ctx *s, sm_mesh_stats_t *out);
 
+/* ---- ground map: a map set as a planner's bird's-eye raster (DESIGN.md "4v. Ground map") ----
+ * sm_ground_maps reads a map set TWICE -- an sm_map_source with the global ids of the map-set calls: the files in list order, each
+ * in file order, then (include_model) the live model -- and gives, over a stated window of nu x nv square cells in the world frame,
+ * per cell: the ground height, the state FREE / OBSTACLE / STEP / UNKNOWN, the ground's colour and class (a top-down ortho image of
+ * the driving surface), the height of the tallest obstacle and the exact squared distance, in cells, to the nearest blocking cell.
+ * Sources, model, tick, stored poses, fern keyframes and tracker state are untouched; frames in flight are waited for.
+ *   Definition, in integers (restated by tests/ground_ref.py):
+ *   Units.  Q(mm) = (mm * 65536 + 500) / 1000 by integer division: lengths are in 2^-16 m.  C = Q(cell_mm), B = Q(band_mm),
+ *     L = Q(clear_lo_mm), Hi = Q(clear_hi_mm), S = Q(step_mm).
+ *   Axes.  a = up >> 1, sgn = (up & 1) ? -1 : +1: axis a points up, negated if the low bit is set.  The horizontal axes are the
+ *     other two in ascending order, ua < va: for a = 1, u = x and v = z.  The default, 3, is -y: a camera-frame world with y down.
+ *   Record quantities.  The simplification's: its regular-record test on the fields and |(double)p[k] - (double)origin[k]| < 2^24;
+ *     X[k] = floor(((double)p[k] - (double)origin[k]) * 65536.0); the quantised normal ni[k]; the weight w; the class c = colour
+ *     word >> 24.  (Not its cell range: the window bounds the cells here.)  A record that fails the test is LOOSE.
+ *   Placement.  cu = floor_div(X[ua], C), cv = floor_div(X[va], C), H = sgn * X[a].  A regular record with cu outside [0, nu), cv
+ *     outside [0, nv) or |H| >= 2^30 is OUTSIDE; the rest lie in cell (cu, cv).  origin is the window's low corner on the two
+ *     horizontal axes and height zero on the up axis.
+ *   Ground-like.  The record's class has its bit in ground_mask and normal_sign * sgn * ni[a] >= min_up.  normal_sign is +1 for
+ *     normals that point out of the surface, towards the viewer, and -1 for normals that point into it, away from the camera that
+ *     saw it: the fusion stores the latter (a road seen from above has a normal that points down), so -1 is the default.
+ *   Reading 1.  Z[cell] = the minimum H of the cell's ground-like records; a cell that has one "has ground".
+ *   Reference height R[cell].  Z[cell] if the cell has ground; otherwise Z of the cell (u', v') with ground that minimises
+ *     (du^2 + dv^2, v', u') lexicographically among the cells of the window with |du| <= fill_cells and |dv| <= fill_cells;
+ *     otherwise none.
+ *   Reading 2.  For every record in the window, with d = H - R[cell], the first rule that applies:
+ *     1. no R: UNREFERENCED.
+ *     2. GROUND: the record is ground-like, its cell has ground and 0 <= d <= B.  SW += w, SH += w * d, SC[ch] += w * channel[ch]
+ *        (ch = 0, 1, 2: bytes 0, 1, 2 of the colour word, b g r), best = max(best, w << 40 | (0x7FFFFFFF - id) << 8 | c).
+ *     3. OBSTACLE: L < d < Hi.  n_obst += 1, top = max(top, d).
+ *     4. IGNORED: overhangs above the body band (bridges, canopies), anything below the reference, the slab between the ground
+ *        band and clear_lo.
+ *   Planes.  A cell with ground: ground = Z + (SH + SW / 2) / SW, bgr[ch] = (SC[ch] + SW / 2) / SW, cls = best & 255 (the class
+ *     of the heaviest ground record, the smallest id among equals).  A cell without: ground = SM_GROUND_NONE, bgr = 0, cls = 255.
+ *     top = the cell's largest obstacle d, 0 when it has none.  Heights are in 2^-16 m above origin[a] along the up direction.
+ *   State.  The first rule that applies: OBSTACLE (2) n_obst >= min_obstacle; UNKNOWN (0) no ground; STEP (3) step_mm > 0 and a
+ *     4-neighbour inside the window has ground with |ground - ground'| > S; FREE (1).
+ *   Clearance.  clear2 = min(reach_cells^2, min over blocking cells of du^2 + dv^2).  Blocking: OBSTACLE, STEP, and UNKNOWN when
+ *     unknown_blocks is set.  A blocking cell has 0.  Cells outside the window do not block.
+ *   Info.  records: of the set.  counts: records GROUND, OBSTACLE, IGNORED, UNREFERENCED, OUTSIDE, LOOSE.  cells: by state.
+ *   The result is a function of the multiset of (global id, record) pairs alone: the chunking, the split into files and the
+ *     device's order do not change a bit of it.  The 64-bit sums cannot overflow: w <= 255, d <= Q(10000) and fewer than 2^31
+ *     records keep SH below 2^59.
+ *   Example, cell_mm 1000 (C = 65536), up 3, origin 0, nu 5, nv 1, normal_sign +1 (the normals below point out of the surface),
+ *     the other parameters at their defaults (B = 13107, L = 9830,
+ *     Hi = 131072, S = 9830); seven records of conf 1 (w = 16), ids 0..6: (0.5, 1, 0.5) normal (0, -1, 0) class 0;
+ *     (1.5, 1, 0.5) (0, -1, 0) class 0; (1.5, 0.875, 0.5) (0, -1, 0) class 1; (2.5, 0, 0.5) (-1, 0, 0); (2.5, -0.5, 0.5) (-1, 0, 0);
+ *     (3.5, 1, 0.5) (0, -1, 0); (4.5, 0.5, 0.5) (0, -1, 0).  Z = -65536, -65536, none, -65536, -32768.  Cell 1: ground = -65536 +
+ *     (16 * 8192 + 16) / 32 = -61440, class 0 (the weights tie: the lower id wins).  Cell 2 borrows R = -65536 from cell 1 (cells 1
+ *     and 3 are equally near: the lower u wins); its records have d = 65536 and 98304: OBSTACLE, top = 98304.  Cells 3 and 4
+ *     differ by 32768 > S: both STEP.  state = 1 1 2 3 3, clear2 = 4 1 0 0 0, counts = 5 2 0 0 0 0.
+ *   Output.  Planes are row-major, row = cell v, column = cell u, nu * nv entries each (bgr: three bytes a cell).  Every plane may
+ *     be NULL; clear2 == NULL skips the distance transform.  A failing call writes no plane and not info.
+ *   File skipping.  A file is read in neither reading when the box of its valid entry in the context's file index misses the
+ *     window's horizontal extent (the box is grown by nothing: a record's cell depends on its centre only).  Its header is still
+ *     checked and counts towards the ids; its records count as OUTSIDE.  SM_RECALL_NO_INDEX=1 turns the lookups off.
+ *   Cost.  Reading 1: one atomicMin per run of ground-like records of one cell among neighbouring lanes of a wave.  One launch
+ *     over the cells fills R from an LDS tile with a halo of fill_cells.  Reading 2: a record's contribution combined in the wave
+ *     per run of equal cells, then integer atomics without return value.  Two launches finish the planes and the states (a
+ *     4-neighbour stencil), two make the capped Euclidean distance transform: columns (the 1-D distance, capped), then rows (the
+ *     minimum of du^2 + g(u')^2 over |du| <= reach_cells, from LDS).  SM_GROUND_NO_COMBINE=1, read per call, switches the in-wave
+ *     combination off in both readings; the result is the same.  Device memory: 64 bytes a cell of accumulators plus the planes,
+ *     allocated per call and freed when it ends.
+ * sm_ground_stats: of the context's last sm_ground_maps that succeeded (a call that fails leaves them as they were).
+ * Errors.  SM_E_ARG: NULLs other than the planes; a parameter outside the ranges below; nu * nv > 2^24; a non-finite origin; the
+ *   header and set checks of sm_render_image_maps (every header before any work); a call between sm_stage_conflict and
+ *   sm_stage_cull; sm_ground_stats before any call has succeeded.  SM_E_UNSUPPORTED: a sharded or rig context.  SM_E_CAPACITY: a
+ *   set of more than 2^31 - 1 records. */
+#define SM_GROUND_NONE     INT32_MIN     /* `ground` of a cell without ground */
+#define SM_GROUND_UNKNOWN  0
+#define SM_GROUND_FREE     1
+#define SM_GROUND_OBSTACLE 2
+#define SM_GROUND_STEP     3
+typedef struct sm_ground_params {
+    int32_t  cell_mm;         /* edge of a cell, 10..10000                                            default 100 */
+    int32_t  up;              /* 2 * axis + negated, 0..5                                             default 3 (-y) */
+    float    origin[3];       /* metres: the window's low corner; height zero on the up axis          default 0 */
+    int32_t  nu, nv;          /* cells, 1..8192 each, nu * nv <= 2^24                                 default 256 each */
+    int32_t  min_up;          /* least up-component of a ground-like normal in 2^-14, 0..16384        default 11585 (45 degrees) */
+    uint32_t ground_mask[8];  /* bit c & 31 of word c >> 5: class c may be ground                     default all ones */
+    int32_t  band_mm;         /* ground band above a cell's lowest ground-like record, 0..10000       default 200 */
+    int32_t  clear_lo_mm;     /* the body band above the reference height:                            default 150 */
+    int32_t  clear_hi_mm;     /*   0 <= clear_lo_mm < clear_hi_mm <= 100000                           default 2000 */
+    uint32_t min_obstacle;    /* >= 1: records in the body band that make a cell an obstacle          default 2 */
+    int32_t  fill_cells;      /* how far a cell without ground looks for a neighbour's, 0..16         default 3 */
+    int32_t  step_mm;         /* height step between 4-neighbours that blocks, 0..10000; 0: off       default 150 */
+    int32_t  reach_cells;     /* the clearance saturates here, 1..255                                 default 32 */
+    int32_t  unknown_blocks;  /* 0 / 1: UNKNOWN cells count as blocking                               default 0 */
+    int32_t  normal_sign;     /* +1: normals point out of the surface; -1: into it, as stored         default -1 */
+} sm_ground_params;
+typedef struct sm_ground_info {
+    uint64_t records;         /* of the set */
+    uint64_t counts[6];       /* records GROUND, OBSTACLE, IGNORED, UNREFERENCED, OUTSIDE, LOOSE */
+    uint32_t cells[4];        /* by state: UNKNOWN, FREE, OBSTACLE, STEP */
+} sm_ground_info;
+typedef struct sm_ground_stats_t {
+    uint32_t chunks;          /* pieces of at most 2^20 records, both readings together */
+    uint32_t launches;
+    uint32_t files_skipped;   /* by the file index */
+    float read_ms;            /* host: reading the files */
+    float ground_ms;          /* device: the planes' initialisation and reading 1 */
+    float fill_ms;            /* device: the reference heights */
+    float accumulate_ms;      /* device: reading 2 */
+    float state_ms;           /* device: planes, states, steps */
+    float clear_ms;           /* device: the distance transform */
+    float copy_ms;            /* the planes back to the caller */
+    float total_ms;
+} sm_ground_stats_t;
+int sm_default_ground_params(sm_ground_params *p);           /* pure, no context */
+int sm_ground_maps(sm_ctx *s, const sm_map_source *src, const sm_ground_params *p,
+                   int32_t *ground, int32_t *top, uint8_t *state, uint8_t *cls, uint8_t *bgr /* three bytes a cell */,
+                   uint32_t *clear2, sm_ground_info *info);   /* every plane may be NULL; info may not */
+int sm_ground_stats(sm_ctx *s, sm_ground_stats_t *out);      /* SM_E_ARG before the first call */
+
 /* ---- per-pass entry points (GlobalModel / IndexMap methods), synchronous ---- */
 /* Upload RGB / metric depth / semantic textures directly (bypasses p0). */
 int sm_set_frame(sm_ctx *s, const uint8_t *rgb, const float *depth_metric,

@@ -53,6 +53,7 @@ SYMBOLS = (
     "sm_default_tile_params", "sm_tile_maps", "sm_tile_stats",
     "sm_default_segment_params", "sm_segment_maps", "sm_segment_stats",
     "sm_default_mesh_params", "sm_mesh_maps", "sm_mesh_stats",
+    "sm_default_ground_params", "sm_ground_maps", "sm_ground_stats",
 )
 
 SM_COLL_SUM, SM_COLL_MIN, SM_COLL_GATHER = 0, 1, 2
@@ -652,6 +653,56 @@ def mesh_params(**over) -> SmMeshParams:
     return p
 
 
+GROUND_KINDS = ("GROUND", "OBSTACLE", "IGNORED", "UNREFERENCED", "OUTSIDE", "LOOSE")   # the entries of a ground map's info.counts
+GROUND_STATES = ("UNKNOWN", "FREE", "OBSTACLE", "STEP")                  # the values of its `state` plane, the entries of info.cells
+GROUND_NONE = -(1 << 31)                                                 # SM_GROUND_NONE: `ground` of a cell without ground
+GROUND_PLANES = ("ground", "top", "state", "cls", "bgr", "clear2")
+
+
+class SmGroundParams(C.Structure):
+    _fields_ = [("cell_mm", C.c_int32), ("up", C.c_int32), ("origin", C.c_float * 3), ("nu", C.c_int32), ("nv", C.c_int32), ("min_up", C.c_int32),
+                ("ground_mask", C.c_uint32 * 8), ("band_mm", C.c_int32), ("clear_lo_mm", C.c_int32), ("clear_hi_mm", C.c_int32),
+                ("min_obstacle", C.c_uint32), ("fill_cells", C.c_int32), ("step_mm", C.c_int32), ("reach_cells", C.c_int32),
+                ("unknown_blocks", C.c_int32), ("normal_sign", C.c_int32)]
+
+
+class SmGroundInfo(C.Structure):
+    _fields_ = [("records", C.c_uint64), ("counts", C.c_uint64 * 6), ("cells", C.c_uint32 * 4)]
+
+
+class SmGroundStats(C.Structure):
+    _fields_ = [("chunks", C.c_uint32), ("launches", C.c_uint32), ("files_skipped", C.c_uint32), ("read_ms", C.c_float), ("ground_ms", C.c_float),
+                ("fill_ms", C.c_float), ("accumulate_ms", C.c_float), ("state_ms", C.c_float), ("clear_ms", C.c_float), ("copy_ms", C.c_float),
+                ("total_ms", C.c_float)]
+
+
+def default_ground_params() -> SmGroundParams:
+    """sm_default_ground_params: cell_mm 100, up 3 (-y), origin (0, 0, 0), 256 x 256 cells, min_up 11585 (45 degrees), every class,
+    band_mm 200, the body band 150..2000 mm, min_obstacle 2, fill_cells 3, step_mm 150, reach_cells 32, unknown_blocks 0, normal_sign -1
+    (normals that point into the surface, as the fusion stores them)"""
+    p = SmGroundParams()
+    load().sm_default_ground_params(C.byref(p))
+    return p
+
+
+def ground_params(**over) -> SmGroundParams:
+    """default_ground_params() with fields overridden; origin takes a sequence of three, ground_mask eight words or an iterable of
+    the classes that may be ground (`classes=` does the latter too)"""
+    p = default_ground_params()
+    for k, v in over.items():
+        if k == "classes":
+            p.ground_mask[:] = segment_class_mask(v)
+        elif not hasattr(p, k):
+            raise KeyError(k)
+        elif k == "origin":
+            p.origin[:] = [float(x) for x in v]
+        elif k == "ground_mask":
+            p.ground_mask[:] = [int(x) for x in v]
+        else:
+            setattr(p, k, v)
+    return p
+
+
 _PLY_PROPERTIES = ["property float x", "property float y", "property float z", "property float nx", "property float ny", "property float nz",
                    "property uchar red", "property uchar green", "property uchar blue", "property uchar class"]
 
@@ -1145,6 +1196,10 @@ def load():
     L.sm_default_mesh_params.argtypes = [mpp]
     L.sm_mesh_maps.argtypes = [vp, msp, mpp, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_char_p, C.POINTER(SmMeshInfo)]
     L.sm_mesh_stats.argtypes = [vp, C.POINTER(SmMeshStats)]
+    gpp = C.POINTER(SmGroundParams)
+    L.sm_default_ground_params.argtypes = [gpp]
+    L.sm_ground_maps.argtypes = [vp, msp, gpp] + [C.c_void_p] * 6 + [C.POINTER(SmGroundInfo)]
+    L.sm_ground_stats.argtypes = [vp, C.POINTER(SmGroundStats)]
     for name in SYMBOLS:
         getattr(L, name)          # AttributeError here = the library does not match the header
     _lib = L
@@ -2188,6 +2243,40 @@ class SurfelMap:
         st = SmMeshStats()
         self._chk(self._L.sm_mesh_stats(self._h, C.byref(st)), "sm_mesh_stats")
         return {k: getattr(st, k) for k, _ in SmMeshStats._fields_}
+
+    # -- a map set as a planner's ground map (sm_ground_maps)
+    def ground_maps(self, paths, include_model=False, planes=GROUND_PLANES, **params) -> dict:
+        """A bird's-eye raster of the map set `paths` (then, with include_model, the live model) over the window of nu x nv cells
+        of cell_mm at origin (sm_ground_maps; tests/ground_ref.py restates it).  params: the fields of ground_params().  planes:
+        those to bring back, the others come as None; without clear2 the distance transform is not run.  Nothing else is changed.
+        Returns dict(ground: int32[nv, nu] in 2^-16 m, GROUND_NONE without ground; top: int32[nv, nu], the tallest obstacle above
+        the reference height; state: uint8[nv, nu] of GROUND_STATES; cls: uint8[nv, nu], 255 without ground; bgr: uint8[nv, nu, 3];
+        clear2: uint32[nv, nu], the squared distance in cells to the nearest blocking cell, at most reach_cells^2; info: records,
+        counts by kind name, counts_by_kind, cells by state name, cells_by_state)."""
+        p = ground_params(**params)
+        unknown = set(planes) - set(GROUND_PLANES)
+        if unknown:
+            raise KeyError(sorted(unknown))
+        src = map_source(paths, include_model=include_model)
+        info = SmGroundInfo()
+        nu, nv = max(int(p.nu), 0), max(int(p.nv), 0)
+        if nu * nv > 1 << 24:                                                 # (refused below: nothing that large is allocated here)
+            nu = nv = 0
+        kinds = dict(ground=(np.int32, ()), top=(np.int32, ()), state=(np.uint8, ()), cls=(np.uint8, ()), bgr=(np.uint8, (3,)), clear2=(np.uint32, ()))
+        out = {k: (np.zeros((nv, nu) + kinds[k][1], kinds[k][0]) if k in planes else None) for k in GROUND_PLANES}
+        self._chk(self._L.sm_ground_maps(self._h, C.byref(src), C.byref(p), *[None if out[k] is None else _ptr(out[k]) for k in GROUND_PLANES],
+                                         C.byref(info)), "sm_ground_maps")
+        counts, cells = [int(v) for v in info.counts], [int(v) for v in info.cells]
+        out["info"] = dict(records=int(info.records), counts=dict(zip(GROUND_KINDS, counts)), counts_by_kind=counts,
+                           cells=dict(zip(GROUND_STATES, cells)), cells_by_state=cells)
+        return out
+
+    def ground_stats(self) -> dict:
+        """of the last ground_maps: chunks, launches, files_skipped, read_ms, ground_ms, fill_ms, accumulate_ms, state_ms, clear_ms,
+        copy_ms, total_ms"""
+        st = SmGroundStats()
+        self._chk(self._L.sm_ground_stats(self._h, C.byref(st)), "sm_ground_stats")
+        return {k: getattr(st, k) for k, _ in SmGroundStats._fields_}
 
     # -- change detection between two map sets (sm_compare_maps)
     def compare_maps(self, query_paths, reference_paths, pose=None, query_model=False, reference_model=False, out_path=None, labels=True,

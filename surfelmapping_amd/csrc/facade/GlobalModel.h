@@ -12,6 +12,33 @@
 #include "GPUTexture.h"
 #include "sm_compat.h"
 
+// Not in the reference: a ground map's planes (sm_ground_maps; DESIGN.md "4v. Ground map"), row-major, row = cell v, column = cell u.
+struct GroundMap {
+    int nu = 0, nv = 0;
+    std::vector<int32_t> ground, top;  // 2^-16 m; ground: SM_GROUND_NONE without ground
+    std::vector<uint8_t> state, cls;   // SM_GROUND_UNKNOWN / FREE / OBSTACLE / STEP; the ground's class, 255 without ground
+    std::vector<uint8_t> bgr;          // three bytes a cell
+    std::vector<uint32_t> clear2;      // squared distance in cells to the nearest blocking cell
+    sm_ground_info info{};
+    bool ok = false;                   // false: the call failed (the error is printed) and the planes are empty
+
+    // the planes of nu x nv cells filled by sm_ground_maps of `src`
+    static GroundMap of(sm_ctx *ctx, const sm_map_source &src, const sm_ground_params &p, const char *who)
+    {
+        GroundMap m;
+        const size_t n = p.nu > 0 && p.nv > 0 && (long long)p.nu * p.nv <= (1ll << 24) ? (size_t)p.nu * (size_t)p.nv : 0;   // (else refused below)
+        m.ground.assign(n, 0); m.top.assign(n, 0); m.state.assign(n, 0); m.cls.assign(n, 0); m.bgr.assign(n * 3, 0); m.clear2.assign(n, 0u);
+        (void)sm_sync(ctx);                                              // (SM_FACADE_ASYNC: frames may still be in flight)
+        if (sm_ground_maps(ctx, &src, &p, m.ground.data(), m.top.data(), m.state.data(), m.cls.data(), m.bgr.data(), m.clear2.data(), &m.info) != SM_OK) {
+            std::printf("%s: %s\n", who, sm_last_error());
+            return GroundMap{};
+        }
+        m.nu = p.nu; m.nv = p.nv;
+        m.ok = true;
+        return m;
+    }
+};
+
 class GlobalModel {
 public:
     explicit GlobalModel(sm_ctx *ctx = nullptr)
@@ -156,6 +183,18 @@ public:
         }
         if (info) *info = got;
         return (long)got.faces;
+    }
+
+    // Not in the reference: the live model alone as a planner's ground map (sm_ground_maps; DESIGN.md "4v. Ground map"): per cell of
+    // the window the ground height, the state FREE / OBSTACLE / STEP / UNKNOWN, the ground's colour and class and the squared
+    // distance to the nearest blocking cell.  params: null = the defaults (100 mm cells, 256 x 256 of them at the origin, -y up).
+    // The model is unchanged.
+    GroundMap groundMap(const sm_ground_params *params = nullptr)
+    {
+        sm_ground_params p;
+        sm_default_ground_params(&p);
+        if (params) p = *params;
+        return GroundMap::of(ctx_, sm_map_source{nullptr, 0u, 1}, p, "groundMap");
     }
 
     // model read-back in the reference's AoS layout (12 floats / surfel, src/Config.cpp:17-32)

@@ -477,6 +477,21 @@ public:
         return (long)got.faces;
     }
 
+    // The records of the map set `mapFiles`, then (withModel) of the live model, as a planner's ground map (sm_ground_maps; DESIGN.md
+    // "4v. Ground map"): a bird's-eye raster over the window params states -- per cell the ground height, the state FREE / OBSTACLE /
+    // STEP / UNKNOWN, the ground's colour and class, the tallest obstacle and the exact squared distance to the nearest blocking
+    // cell.  params: null = the defaults.  Nothing else is changed.  The result's `ok` is false, with the error printed, if the call failed.
+    GroundMap groundMaps(const std::vector<std::string> &mapFiles, const sm_ground_params *params = nullptr, bool withModel = false)
+    {
+        std::vector<const char *> paths;
+        for (const std::string &f : mapFiles) paths.push_back(f.c_str());
+        const sm_map_source src{paths.data(), (uint32_t)paths.size(), withModel ? 1 : 0};
+        sm_ground_params p;
+        sm_default_ground_params(&p);
+        if (params) p = *params;
+        return GroundMap::of(ctx_, src, p, "groundMaps");
+    }
+
     // The second sensor's dump: what a lidar `sensor` (sm_lidar_sensor; sm_default_lidar_sensor) at each of `poses` (sensor->world,
     // the camera's axes) measures in the live model, written as <path>/velodyne/%06d.bin next to acquireImages' folders, in KITTI's
     // velodyne layout: per return four floats, (z, -x, -y) of t*d in the sensor frame -- x forward, y left, z up -- and the

@@ -397,6 +397,17 @@ struct Mesh {
     bool stats_valid = false;
 };
 
+// the ground map (sm_ground.hip, sm_k_ground.h): the tally, its pinned mirror, the events and the last call's stats.  The cells'
+// accumulators and the planes live for one call.
+struct Ground {
+    Dev<uint32_t> d_tally;             // the counts by record kind and by cell state
+    Host<uint32_t> h_tally;            // pinned
+    static constexpr int N_EV = 12;    // around: the memsets, reading 1's model, the fill, reading 2's model, finish and state, the transform
+    Event ev[N_EV];
+    sm_ground_stats_t stats{};
+    bool stats_valid = false;
+};
+
 // closing loops unasked (sm_loop.hip): the policy of sm_set_auto_loop and its tally
 struct AutoLoop {
     bool on = false;
@@ -653,6 +664,7 @@ struct sm_ctx {
     Tile tile;
     Segment seg;
     Mesh mesh;
+    Ground ground;
 };
 
 namespace sm_impl __attribute__((visibility("hidden"))) {

@@ -1,5 +1,5 @@
 // sm_d_simplify.h -- the voxel-cell table as device functions, for every source that fills or reads such a table (sm_k_simplify.h;
-// sm_k_voxel.h; through sm_d_register.h, sm_k_register.h and sm_k_compare.h; sm_k_tile.h, which keeps tiles and counts in one; sm_k_segment.h, whose slots are the nodes of a union-find; sm_k_mesh.h, which keeps cells in one and lattice points in another): the regular-record test, the key, a record's
+// sm_k_voxel.h; through sm_d_register.h, sm_k_register.h and sm_k_compare.h; sm_k_tile.h, which keeps tiles and counts in one; sm_k_segment.h, whose slots are the nodes of a union-find; sm_k_mesh.h, which keeps cells in one and lattice points in another; sm_k_ground.h, which has no table and takes the record test and the run logic): the regular-record test, the key, a record's
 // contribution, the probe, the insert in its pieces -- head of a run, in-wave combination, claim, adds --, a cell's merged
 // position, normal and record, and the ranks of a pass that writes.  No kernels: a kernel is defined in the one header of the
 // source that launches it.

@@ -1734,6 +1734,70 @@ int sm_ground_maps(sm_ctx *s, const sm_map_source *src, const sm_ground_params *
                    uint32_t *clear2, sm_ground_info *info);   /* every plane may be NULL; info may not */
 int sm_ground_stats(sm_ctx *s, sm_ground_stats_t *out);      /* SM_E_ARG before the first call */
 
+/* ---- scenes: a map set with moving actors in it (DESIGN.md "4w. Scenes") ----
+ * Everything above replays a static world.  A scene is a map set plus actors: an actor is a map file whose records are in the
+ * actor's OWN frame, with one actor->world pose per view (or sweep).  The actor files are read once per call and stay on the
+ * device; every view draws each actor under that view's pose into the key planes the static set is drawn into.  No file is
+ * copied, warped or rewritten, and the static set is read once per batch of views, not once per view.
+ *   Two calls draw scenes: the novel view with sm_render_image_maps_ex's extras (sm_render_image_scene) and the lidar sweep
+ *   (sm_lidar_sweep_scene).  The model view (sm_render_model_maps) and the blended view (sm_render_image_maps_blend) draw no scenes.
+ * Placed row.  Row m of actor j in view i becomes m' by sm_warp_by_time's row rule with C = poses12 row i of actor j (ROW-major
+ *   3x4 [R|t], corr12's layout), applied to every row whatever its time:
+ *     m'[0] = ((C[0]*m[0] + C[1]*m[1]) + C[2]*m[2]) + C[3],   m'[1], m'[2] likewise with C[4..7], C[8..11];
+ *     m'[8] = (C[0]*m[8] + C[1]*m[9]) + C[2]*m[10],           m'[9], m'[10] likewise; no translation, no renormalisation;
+ *   fp32, no contraction; every other field bit-identical.  sm_scene_place_rows is that rule on the host (no context; n rows of 12
+ *   floats from rows_in to rows_out, which may be the same array), so the definition is executable from C.
+ * Scene of view i.  S_i = the files of `src` in order, then (include_model) the live model's rows, then for every actor present
+ *   in view i, in list order, its placed rows in file order.
+ * Equality.  For every view i, sm_render_image_scene writes bgr, sem and depth_mm that equal sm_render_image_ex of a context
+ *   holding S_i, bit for bit, the fill included; sm_lidar_sweep_scene writes range, rgb and sem that equal sm_lidar_sweep of that
+ *   context, bit for bit.  A depth or range tie goes to the earlier source: static beats actor, an earlier actor a later one.
+ * Ids (the lidar's id plane).  Static ids are sm_lidar_sweep_maps'.  Row r of actor j has id A + off_j + r: A is the static total
+ *   (files and live model), off_j the sum of the record counts of actors 0..j-1, PRESENT OR NOT, so an id does not depend on the
+ *   view; with every actor present it is the concatenation's id.  More than 2^31 - 1 ids in all: SM_E_CAPACITY before anything is drawn.
+ * Independence.  The result depends neither on the chunking, nor on the views per pass, nor on the key budget
+ *   (SM_RENDER_MAPS_KEY_MB, SM_LIDAR_KEY_MB), nor on the culling switches, nor on whether two actors name the same file.
+ * Degenerate scenes.  scene == NULL or n_actors == 0 equals sm_render_image_maps_ex / sm_lidar_sweep_maps bit for bit (and
+ *   enqueues exactly what they enqueue); an actor file of 0 records is valid and takes no ids; n_views == 0 checks the set and the
+ *   actors and draws nothing.
+ * Limits.  At most SM_SCENE_MAX_ACTORS actors; at most SM_SCENE_MAX_RECORDS records summed over the DISTINCT actor files (two
+ *   actors whose paths compare equal share one resident copy).  Beyond either: SM_E_CAPACITY.
+ * Errors.  The scene's arguments and every actor's header are checked first, then the set's, before any work; every error leaves
+ *   the outputs unwritten.  SM_E_ARG: a NULL actor list with n_actors > 0, a NULL path or NULL poses12; a non-finite entry in a
+ *   pose row of a view where the actor is present; a rotation part farther than 1e-3 from orthonormal (largest entry of
+ *   |R^T R - I|, in double) or with det <= 0 (sm_loop_spread's test: the culling proof needs near-rigid poses; rows of views the actor is
+ *   absent from are not read); an actor file that is missing or whose length disagrees with its header; the argument errors of
+ *   sm_render_image_maps_ex / sm_lidar_sweep_maps.  SM_E_UNSUPPORTED: a sharded or rig context.
+ * Side effects.  Those of the _maps calls and no more: actor files are read, never written; the model, the tick, the poses and
+ *   the frame log are untouched.  sm_render_maps_stats / sm_lidar_stats / sm_fill_stats tell of the static part exactly as after the
+ *   _maps calls; sm_scene_stats tells of the actors.
+ * SM_SCENE_NO_CULL=1 (read per call) turns the per-(actor block, view) test off (an A/B switch: the outputs are the same). */
+#define SM_SCENE_MAX_ACTORS  4096u
+#define SM_SCENE_MAX_RECORDS (1u << 22)
+typedef struct sm_scene_actor {
+    const char    *path;      /* a map file (sm_save_map's format); its records are in the actor's own frame */
+    const float   *poses12;   /* n_views rows of 12 floats: ROW-major 3x4 [R|t], actor -> world -- corr12's layout */
+    const uint8_t *present;   /* n_views bytes, 0 = the actor is not in that view; NULL = in every view */
+} sm_scene_actor;
+typedef struct sm_scene { const sm_scene_actor *actors; uint32_t n_actors; } sm_scene;
+/* what the last scene call of the context did with its actors */
+typedef struct sm_scene_stats_t {
+    uint32_t actors, files;        /* actors listed; distinct files among them */
+    uint64_t records, bytes;       /* resident: records of the distinct files; device bytes of their planes, boxes and tables */
+    uint64_t pairs_tested;         /* (actor block of 256 records, view) pairs with the actor present that the box test ran on (0 with SM_SCENE_NO_CULL=1) */
+    uint64_t pairs_skipped;        /* ... of them, found outside the view or out of range and not drawn */
+    float load_ms;                 /* reading the actor files, uploading and unpacking them (host clock) */
+    float actor_ms;                /* device: the actors' splat and resolve launches (events), all batches together */
+    float total_ms;                /* the whole call (host clock) */
+} sm_scene_stats_t;
+int sm_render_image_scene(sm_ctx *s, const sm_map_source *src, const sm_scene *scene, const float *views16, uint32_t n_views,
+                          int w, int h, float fx, float fy, float cx, float cy, const sm_fill_params *fill /* NULL: none */,
+                          uint8_t *bgr_out, uint8_t *sem_out, uint16_t *depth_mm_out /* NULL: not wanted */);
+int sm_lidar_sweep_scene(sm_ctx *s, const sm_map_source *src, const sm_scene *scene, const sm_lidar_sensor *sn,
+                         const float *poses16, uint32_t n_sweeps, float *range, int32_t *id, uint8_t *rgb, uint8_t *sem);
+int sm_scene_place_rows(const float *pose12, const float *rows_in, uint32_t n, float *rows_out);   /* host only, no context */
+int sm_scene_stats(sm_ctx *s, sm_scene_stats_t *out);        /* SM_E_ARG before the first scene call */
+
 /* ---- per-pass entry points (GlobalModel / IndexMap methods), synchronous ---- */
 /* Upload RGB / metric depth / semantic textures directly (bypasses p0). */
 int sm_set_frame(sm_ctx *s, const uint8_t *rgb, const float *depth_metric,

@@ -54,6 +54,7 @@ SYMBOLS = (
     "sm_default_segment_params", "sm_segment_maps", "sm_segment_stats",
     "sm_default_mesh_params", "sm_mesh_maps", "sm_mesh_stats",
     "sm_default_ground_params", "sm_ground_maps", "sm_ground_stats",
+    "sm_render_image_scene", "sm_lidar_sweep_scene", "sm_scene_place_rows", "sm_scene_stats",
 )
 
 SM_COLL_SUM, SM_COLL_MIN, SM_COLL_GATHER = 0, 1, 2
@@ -189,6 +190,63 @@ def lidar_points(range, dirs, rgb=None) -> np.ndarray:
     if rgb is not None:
         c = np.ascontiguousarray(rgb, np.uint8).reshape(-1, 3)[got].astype(f32)
         out[:, 3] = ((f32(0.299) * c[:, 0] + f32(0.587) * c[:, 1]) + f32(0.114) * c[:, 2]) / f32(255.0)
+    return out
+
+
+class SmSceneActor(C.Structure):
+    _fields_ = [("path", C.c_char_p), ("poses12", C.POINTER(C.c_float)), ("present", C.POINTER(C.c_uint8))]
+
+
+class SmScene(C.Structure):
+    _fields_ = [("actors", C.POINTER(SmSceneActor)), ("n_actors", C.c_uint32)]
+
+
+class SmSceneStats(C.Structure):
+    _fields_ = [("actors", C.c_uint32), ("files", C.c_uint32), ("records", C.c_uint64), ("bytes", C.c_uint64),
+                ("pairs_tested", C.c_uint64), ("pairs_skipped", C.c_uint64), ("load_ms", C.c_float), ("actor_ms", C.c_float),
+                ("total_ms", C.c_float)]
+
+
+SCENE_MAX_ACTORS, SCENE_MAX_RECORDS = 4096, 1 << 22
+
+
+def scene_poses12(poses) -> np.ndarray:
+    """actor->world poses as the scene calls take them, float32[V][12] ROW-major 3x4 [R|t]: from float32[V][12] as they are, or
+    from [V][4][4] matrices (their top three rows)"""
+    p = np.asarray(poses, np.float32)
+    if p.ndim == 3 and p.shape[1:] == (4, 4):
+        p = p[:, :3, :]
+    return np.ascontiguousarray(p.reshape(-1, 12))
+
+
+def scene(actors, n_views=None) -> SmScene:
+    """a scene's actors: a list of (path, poses[, present]) -- a map file in the actor's own frame, its poses per view
+    (scene_poses12 forms), optionally uint8[V], 0 = not in that view.  n_views: what every actor's arrays must hold (None: not
+    checked).  Keeps the strings and arrays alive."""
+    keep, arr = [], (SmSceneActor * max(len(actors), 1))()
+    for j, a in enumerate(actors):
+        path, poses = os.fsencode(a[0]), scene_poses12(a[1])
+        present = None if len(a) < 3 or a[2] is None else np.ascontiguousarray(a[2], np.uint8).reshape(-1)
+        if n_views is not None and (len(poses) != n_views or (present is not None and len(present) != n_views)):
+            raise ValueError(f"actor {j}: {len(poses)} poses for {n_views} views")
+        arr[j].path = path
+        arr[j].poses12 = poses.ctypes.data_as(C.POINTER(C.c_float))
+        arr[j].present = None if present is None else present.ctypes.data_as(C.POINTER(C.c_uint8))
+        keep.append((path, poses, present))
+    sc = SmScene(C.cast(arr, C.POINTER(SmSceneActor)), len(actors))
+    sc._keep = (keep, arr)
+    return sc
+
+
+def scene_place_rows(pose, rows) -> np.ndarray:
+    """sm_scene_place_rows: float32[N][12] records under one actor->world pose (float32[12] row-major 3x4, or 4x4) by
+    sm_warp_by_time's row rule, on the host"""
+    pose = scene_poses12(np.asarray(pose, np.float32).reshape((1, 4, 4) if np.size(pose) == 16 else (1, 12)))
+    rows = np.ascontiguousarray(rows, np.float32).reshape(-1, 12)
+    out = np.empty_like(rows)
+    rc = load().sm_scene_place_rows(_ptr(pose), _ptr(rows), len(rows), _ptr(out))
+    if rc:
+        raise SurfelMapError("sm_scene_place_rows", rc, load().sm_last_error().decode())
     return out
 
 
@@ -1200,6 +1258,11 @@ def load():
     L.sm_default_ground_params.argtypes = [gpp]
     L.sm_ground_maps.argtypes = [vp, msp, gpp] + [C.c_void_p] * 6 + [C.POINTER(SmGroundInfo)]
     L.sm_ground_stats.argtypes = [vp, C.POINTER(SmGroundStats)]
+    scp = C.POINTER(SmScene)
+    L.sm_render_image_scene.argtypes = [vp, msp, scp, vp, C.c_uint32, C.c_int, C.c_int] + [C.c_float] * 4 + [flp, vp, vp, vp]
+    L.sm_lidar_sweep_scene.argtypes = [vp, msp, scp, lsp, vp, C.c_uint32, vp, vp, vp, vp]
+    L.sm_scene_place_rows.argtypes = [vp, vp, C.c_uint32, vp]
+    L.sm_scene_stats.argtypes = [vp, C.POINTER(SmSceneStats)]
     for name in SYMBOLS:
         getattr(L, name)          # AttributeError here = the library does not match the header
     _lib = L
@@ -2092,6 +2155,45 @@ class SurfelMap:
         st = SmLidarStats()
         self._chk(self._L.sm_lidar_stats(self._h, C.byref(st)), "sm_lidar_stats")
         return {k: getattr(st, k) for k, _ in SmLidarStats._fields_}
+
+    # -- scenes (sm_render_image_scene, sm_lidar_sweep_scene)
+    def render_scene(self, paths, actors, views, w, h, fx, fy, cx, cy, include_model=True, fill=None, depth=False):
+        """render_image_maps of a scene: the map set plus `actors`, a list of (path, poses[, present]) -- map files in the actor's
+        own frame, each drawn under its pose of the view (float32[V][12] row-major 3x4 or [V][4][4], actor->world) where it is
+        present (uint8[V]; None: everywhere).  Every view equals render_image_maps of the set followed by the present actors' files
+        moved by sm_warp_by_time's row rule.  Returns (bgr, sem[, depth_mm]) as render_image_maps."""
+        views = np.ascontiguousarray(views, np.float32).reshape(-1, 16)
+        V = views.shape[0]
+        bgr = np.zeros((V, h, w, 3), np.uint8)
+        sem = np.zeros((V, h, w), np.uint8)
+        d = np.zeros((V, h, w), np.uint16) if depth else None
+        src = map_source(paths, include_model)
+        sc = scene(actors, V)
+        fp = _fill_arg(fill)
+        self._chk(self._L.sm_render_image_scene(self._h, C.byref(src), C.byref(sc), _ptr(views), V, w, h, fx, fy, cx, cy,
+                                                C.byref(fp) if fp is not None else None, _ptr(bgr), _ptr(sem), _ptr(d)),
+                  "sm_render_image_scene")
+        return (bgr, sem, d) if depth else (bgr, sem)
+
+    def lidar_sweep_scene(self, paths, actors, poses, sensor=None, include_model=True) -> dict:
+        """lidar_sweep_maps of a scene (see render_scene; an actor's poses are per sweep): the same dict.  Row r of actor j has
+        the id A + off_j + r -- A the static total, off_j the records of the actors before it, present or not."""
+        sensor = lidar_sensor() if sensor is None else sensor
+        poses = np.ascontiguousarray(poses, np.float32).reshape(-1, 16)
+        V = poses.shape[0]
+        out = _lidar_planes((V, sensor.n_el, sensor.n_az))
+        src = map_source(paths, include_model)
+        sc = scene(actors, V)
+        self._chk(self._L.sm_lidar_sweep_scene(self._h, C.byref(src), C.byref(sc), C.byref(sensor), _ptr(poses), V,
+                                               *[_ptr(out[k]) for k in ("range", "id", "rgb", "sem")]), "sm_lidar_sweep_scene")
+        return out
+
+    def scene_stats(self) -> dict:
+        """of the last render_scene / lidar_sweep_scene call (sm_scene_stats): actors, files (distinct), records and bytes
+        resident, pairs_tested / pairs_skipped ((actor block of 256, view) pairs), load_ms, actor_ms, total_ms"""
+        st = SmSceneStats()
+        self._chk(self._L.sm_scene_stats(self._h, C.byref(st)), "sm_scene_stats")
+        return {k: getattr(st, k) for k, _ in SmSceneStats._fields_}
 
     # -- simplification (sm_simplify, sm_simplify_maps)
     def simplify(self, **params) -> dict:

@@ -21,6 +21,14 @@
 
 class Checker;          // debug aid of the reference (src/Utils/Checker.h); never constructed here
 
+// One moving actor of a scene (sm_c_api.h "scenes"; DESIGN.md "4w. Scenes"): a map file whose records are in the actor's own frame,
+// one actor->world pose per view (or sweep) and, if not empty, one byte per view: 0 = the actor is not in that view.
+struct SceneActor {
+    std::string file;
+    std::vector<Eigen::Matrix4f> poses;
+    std::vector<uint8_t> present;
+};
+
 class SurfelMapping {
 public:
     // src/SurfelMapping.cpp:12-25: reads the Config singleton, which must have been initialised
@@ -504,44 +512,26 @@ public:
     bool acquireSweeps(std::string path, const std::vector<std::string> &mapFiles, const std::vector<Eigen::Matrix4f> &poses,
                        const sm_lidar_sensor &sensor, int startId = 0, bool includeModel = true)
     {
-        if (path.empty() || path.back() != '/') path += "/";
-        const std::string velo_path = path + "velodyne/";
-        ::mkdir(velo_path.c_str(), 0755);
-        if (sensor.n_az <= 0 || sensor.n_el <= 0 || (unsigned long long)sensor.n_az * (unsigned long long)sensor.n_el > SM_LIDAR_MAX_BEAMS) return false;
-        const size_t nb = (size_t)sensor.n_az * sensor.n_el;
-        std::vector<float> p16(poses.size() * 16), dir(nb * 3), range(poses.size() * nb);
-        for (size_t i = 0; i < poses.size(); ++i) std::memcpy(&p16[i * 16], poses[i].data(), 64);
-        std::vector<unsigned char> rgb(poses.size() * nb * 3);
-        std::vector<const char *> paths;
-        for (const std::string &f : mapFiles) paths.push_back(f.c_str());
-        const sm_map_source src{paths.data(), (uint32_t)paths.size(), includeModel ? 1 : 0};
-        (void)sm_sync(ctx_);                                             // (SM_FACADE_ASYNC: frames may still be in flight)
-        if (sm_lidar_directions(&sensor, dir.data()) != SM_OK ||
-            sm_lidar_sweep_maps(ctx_, &src, &sensor, p16.data(), (uint32_t)poses.size(), range.data(), nullptr, rgb.data(), nullptr) != SM_OK) {
-            std::printf("acquireSweeps: %s\n", sm_last_error());
+        return acquireSweepsOf(path, mapFiles, poses, sensor, startId, includeModel, nullptr);
+    }
+
+    // Scenes (sm_render_image_scene / sm_lidar_sweep_scene; DESIGN.md "4w. Scenes"): the map set with moving actors in it.  Every
+    // actor's file is read once and drawn under its pose of each view where it is present; no file is copied or rewritten.
+    // acquireSceneImages writes what acquireImages writes and honours setFillHoles / setWriteDepth; the blended view draws no
+    // scenes, so with setBlend on it refuses.  acquireSceneSweeps writes velodyne/%06d.bin as acquireSweeps does.
+    bool acquireSceneImages(std::string path, const std::vector<std::string> &mapFiles, bool includeModel, const std::vector<SceneActor> &actors,
+                            const std::vector<Eigen::Matrix4f> &views, int w, int h, float fx, float fy, float cx, float cy, int startId = 0)
+    {
+        if (blend_) {
+            std::printf("acquireSceneImages: blended views draw no scenes (setBlend is on)\n");
             return false;
         }
-        bool ok = true;
-        std::vector<float> pts;
-        for (size_t i = 0; i < poses.size(); ++i, ++startId) {
-            char name[32];
-            std::snprintf(name, sizeof name, "%06d.bin", startId);
-            pts.clear();
-            for (size_t b = 0; b < nb; ++b) {
-                const float t = range[i * nb + b];
-                if (!(t > 0.0f)) continue;
-                const unsigned char *c = &rgb[(i * nb + b) * 3];
-                const float x = t * dir[3 * b], y = t * dir[3 * b + 1], z = t * dir[3 * b + 2];
-                const float lum = 0.299f * (float)c[0] + 0.587f * (float)c[1];
-                pts.push_back(z); pts.push_back(-x); pts.push_back(-y);
-                pts.push_back((lum + 0.114f * (float)c[2]) / 255.0f);
-            }
-            FILE *f = std::fopen((velo_path + name).c_str(), "wb");
-            const bool w = f && std::fwrite(pts.data(), 4, pts.size(), f) == pts.size();
-            if (f && std::fclose(f) != 0) ok = false;
-            if (!w) { std::printf("%s is NOT saved!\n", name); ok = false; }
-        }
-        return ok;
+        return acquireImagesEx(path, &mapFiles, includeModel, views, w, h, fx, fy, cx, cy, startId, &actors);
+    }
+    bool acquireSceneSweeps(std::string path, const std::vector<std::string> &mapFiles, bool includeModel, const std::vector<SceneActor> &actors,
+                            const std::vector<Eigen::Matrix4f> &poses, const sm_lidar_sensor &sensor, int startId = 0)
+    {
+        return acquireSweepsOf(path, mapFiles, poses, sensor, startId, includeModel, &actors);
     }
 
     // extras of the HIP core
@@ -810,8 +800,9 @@ private:
     // imageSemantic(), its size) is left as the plain overload leaves it: the last view, filled if filling is on.  One difference
     // remains: a view that cannot be rendered ends the call with the error printed and no file written (false; the void overload has
     // no way to return it), where the plain live-model overload prints the error and writes the planes it has.
+    // actors (with mapFiles) non-null: the scene call, sm_render_image_scene, which draws no blended views.
     bool acquireImagesEx(std::string path, const std::vector<std::string> *mapFiles, bool includeModel, const std::vector<Eigen::Matrix4f> &views,
-                         int w, int h, float fx, float fy, float cx, float cy, int startId)
+                         int w, int h, float fx, float fy, float cx, float cy, int startId, const std::vector<SceneActor> *actors = nullptr)
     {
         if (path.empty() || path.back() != '/') path += "/";
         const std::string image_path = path + "image/", semantic_path = path + "semantic/", depth_path = path + "depth/";
@@ -832,8 +823,12 @@ private:
             std::vector<const char *> paths;
             for (const std::string &f : *mapFiles) paths.push_back(f.c_str());
             const sm_map_source src{paths.data(), (uint32_t)paths.size(), includeModel ? 1 : 0};
-            rc = sm_render_image_maps_blend(ctx_, &src, v16.data(), (uint32_t)V, w, h, fx, fy, cx, cy, blend, fill, bgr.data(), sem.data(),
-                                            writeDepth_ ? depth.data() : nullptr);
+            SceneArgs sc;
+            if (actors && !sceneArgs(*actors, V, sc, "acquireSceneImages")) return false;
+            rc = actors ? sm_render_image_scene(ctx_, &src, &sc.scene, v16.data(), (uint32_t)V, w, h, fx, fy, cx, cy, fill, bgr.data(), sem.data(),
+                                                writeDepth_ ? depth.data() : nullptr)
+                        : sm_render_image_maps_blend(ctx_, &src, v16.data(), (uint32_t)V, w, h, fx, fy, cx, cy, blend, fill, bgr.data(), sem.data(),
+                                                     writeDepth_ ? depth.data() : nullptr);
         } else {
             globalModel.setImageSize(w, h, fx, fy, cx, cy);              // as the plain overload leaves the model's image ...
             for (size_t i = 0; i < V && rc == SM_OK; ++i) {
@@ -843,7 +838,7 @@ private:
             }
         }
         if (rc != SM_OK) {
-            std::printf("acquireImages: %s\n", sm_last_error());
+            std::printf("%s: %s\n", actors ? "acquireSceneImages" : "acquireImages", sm_last_error());
             return false;
         }
         bool ok = true;
@@ -856,6 +851,73 @@ private:
             const bool r2 = sm_png::write((semantic_path + name).c_str(), &sem[i * npix], w, h, 1);
             const bool r3 = !writeDepth_ || sm_png::write16((depth_path + name).c_str(), &depth[i * npix], w, h);
             if (!(r1 && r2 && r3)) { std::printf("%s is NOT saved!\n", name); ok = false; }
+        }
+        return ok;
+    }
+    // a scene's C structs for n views: the poses as ROW-major 3x4 rows; false (a line printed) where an actor's arrays do not hold n
+    struct SceneArgs { std::vector<std::vector<float>> poses; std::vector<sm_scene_actor> list; sm_scene scene{nullptr, 0}; };
+    static bool sceneArgs(const std::vector<SceneActor> &actors, size_t n, SceneArgs &a, const char *who)
+    {
+        a.poses.resize(actors.size());
+        a.list.resize(actors.size());
+        for (size_t j = 0; j < actors.size(); ++j) {
+            const SceneActor &act = actors[j];
+            if (act.poses.size() != n || (!act.present.empty() && act.present.size() != n)) {
+                std::printf("%s: actor %zu has %zu poses for %zu views\n", who, j, act.poses.size(), n);
+                return false;
+            }
+            a.poses[j].resize(n * 12);
+            for (size_t i = 0; i < n; ++i)
+                for (int r = 0; r < 3; ++r)
+                    for (int c = 0; c < 4; ++c) a.poses[j][i * 12 + r * 4 + c] = act.poses[i](r, c);
+            a.list[j] = sm_scene_actor{act.file.c_str(), a.poses[j].data(), act.present.empty() ? nullptr : act.present.data()};
+        }
+        a.scene = sm_scene{a.list.data(), (uint32_t)a.list.size()};
+        return true;
+    }
+    // acquireSweeps of a map set and, with actors, acquireSceneSweeps
+    bool acquireSweepsOf(std::string path, const std::vector<std::string> &mapFiles, const std::vector<Eigen::Matrix4f> &poses,
+                         const sm_lidar_sensor &sensor, int startId, bool includeModel, const std::vector<SceneActor> *actors)
+    {
+        if (path.empty() || path.back() != '/') path += "/";
+        const std::string velo_path = path + "velodyne/";
+        ::mkdir(velo_path.c_str(), 0755);
+        if (sensor.n_az <= 0 || sensor.n_el <= 0 || (unsigned long long)sensor.n_az * (unsigned long long)sensor.n_el > SM_LIDAR_MAX_BEAMS) return false;
+        const size_t nb = (size_t)sensor.n_az * sensor.n_el;
+        std::vector<float> p16(poses.size() * 16), dir(nb * 3), range(poses.size() * nb);
+        for (size_t i = 0; i < poses.size(); ++i) std::memcpy(&p16[i * 16], poses[i].data(), 64);
+        std::vector<unsigned char> rgb(poses.size() * nb * 3);
+        std::vector<const char *> paths;
+        for (const std::string &f : mapFiles) paths.push_back(f.c_str());
+        const sm_map_source src{paths.data(), (uint32_t)paths.size(), includeModel ? 1 : 0};
+        (void)sm_sync(ctx_);                                             // (SM_FACADE_ASYNC: frames may still be in flight)
+        SceneArgs sc;
+        if (actors && !sceneArgs(*actors, poses.size(), sc, "acquireSceneSweeps")) return false;
+        if (sm_lidar_directions(&sensor, dir.data()) != SM_OK ||
+            (actors ? sm_lidar_sweep_scene(ctx_, &src, &sc.scene, &sensor, p16.data(), (uint32_t)poses.size(), range.data(), nullptr, rgb.data(), nullptr)
+                    : sm_lidar_sweep_maps(ctx_, &src, &sensor, p16.data(), (uint32_t)poses.size(), range.data(), nullptr, rgb.data(), nullptr)) != SM_OK) {
+            std::printf("%s: %s\n", actors ? "acquireSceneSweeps" : "acquireSweeps", sm_last_error());
+            return false;
+        }
+        bool ok = true;
+        std::vector<float> pts;
+        for (size_t i = 0; i < poses.size(); ++i, ++startId) {
+            char name[32];
+            std::snprintf(name, sizeof name, "%06d.bin", startId);
+            pts.clear();
+            for (size_t b = 0; b < nb; ++b) {
+                const float t = range[i * nb + b];
+                if (!(t > 0.0f)) continue;
+                const unsigned char *c = &rgb[(i * nb + b) * 3];
+                const float x = t * dir[3 * b], y = t * dir[3 * b + 1], z = t * dir[3 * b + 2];
+                const float lum = 0.299f * (float)c[0] + 0.587f * (float)c[1];
+                pts.push_back(z); pts.push_back(-x); pts.push_back(-y);
+                pts.push_back((lum + 0.114f * (float)c[2]) / 255.0f);
+            }
+            FILE *f = std::fopen((velo_path + name).c_str(), "wb");
+            const bool w = f && std::fwrite(pts.data(), 4, pts.size(), f) == pts.size();
+            if (f && std::fclose(f) != 0) ok = false;
+            if (!w) { std::printf("%s is NOT saved!\n", name); ok = false; }
         }
         return ok;
     }

@@ -14,6 +14,7 @@
 //   sm_warp.hip      closing loops (sm_warp_by_time, sm_loop_spread): the model and map files warped by surfel time
 //   sm_search.hip    pose search before the tracker (sm_score_poses_window, sm_search_pose)
 //   sm_lidar.hip     lidar sweeps (sm_lidar_*): beams against the live model and against streamed map files
+//   sm_scene.hip     scenes (sm_render_image_scene, sm_lidar_sweep_scene): actor files resident for a call, drawn under a pose per view by both of the above
 //   sm_place.hip     place recognition (sm_fern_*, sm_search_pose_at, sm_close_loop_at): fern codes, the keyframe database, the match
 //   sm_stereo.hip    stereo depth (sm_stereo_*): census, matching costs, path costs, winner and depth of a rectified pair
 //   sm_fill.hip      hole filling (sm_fill_*, sm_render_image_ex's and sm_render_image_maps_ex's stage): depth of a view, push-pull completion
@@ -49,7 +50,7 @@
 #include <utility>
 #include <vector>
 
-namespace sm { struct TrackState; struct TrackRgbState; struct RegState; struct RenderParams; struct ViewParams; struct ViewShade; struct RecallChunk; struct WarpChunk; }
+namespace sm { struct TrackState; struct TrackRgbState; struct RegState; struct RenderParams; struct ViewParams; struct ViewShade; struct RecallChunk; struct WarpChunk; struct MapsSoA; struct LidarGrid; struct LidarPose; }
 
 // Hidden: libsurfelmapping_hip.so exports the C ABI and the kernels' host stubs, nothing of this namespace.  Its functions are
 // defined qualified (sm_impl::name) so that the definitions keep the visibility.
@@ -408,6 +409,23 @@ struct Ground {
     bool stats_valid = false;
 };
 
+// scenes (sm_scene.hip, sm_k_scene.h): the actors of one call resident on the device -- the distinct files' records as they were
+// read, the SoA planes and boxes k_maps_intake makes of them, the call's tables -- grown on demand and reloaded by every call (no
+// cache across calls); the last call's tally
+struct Scene {
+    Dev<float4> d_rec;                 // the distinct files' records, three float4 each, file after file
+    size_t rec_cap = 0;                // records
+    Dev<float4> d_pos_conf, d_norm_rad, d_box;
+    Dev<uint32_t> d_color;
+    Dev<float> d_time;
+    size_t row_cap = 0;                // rows of the planes (a multiple of 256; every file begins a block)
+    Dev<uint8_t> d_tab;                // the device tally | SceneActor per actor | a pose row per (actor, view) | present per (actor, view)
+    size_t tab_bytes = 0;
+    Event ev[2];                       // around a batch's actor launches
+    sm_scene_stats_t stats{};
+    bool stats_valid = false;
+};
+
 // closing loops unasked (sm_loop.hip): the policy of sm_set_auto_loop and its tally
 struct AutoLoop {
     bool on = false;
@@ -665,6 +683,7 @@ struct sm_ctx {
     Segment seg;
     Mesh mesh;
     Ground ground;
+    Scene scene;
 };
 
 namespace sm_impl __attribute__((visibility("hidden"))) {
@@ -726,6 +745,41 @@ int auto_retire_after_frame(sm_ctx *s);           // the periodic policy: called
 int maps_ensure_staging(sm_ctx *s);               // the staging's copy stream, buffers and events: whole or absent
 // k_maps_intake on the context's stream: n records at d_rec into the staging's SoA planes and its one box per 256 records
 void maps_intake(sm_ctx *s, const float4 *d_rec, uint32_t n);
+// ... into planes and boxes of the caller's (the scenes' resident actors)
+void maps_intake_to(sm_ctx *s, const float4 *d_rec, uint32_t n, const MapsSoA &out, float4 *d_box);
+// ---- sm_scene.hip ----
+// The actors of a scene call as the host knows them once its arguments and every actor's header are checked (scene_check), and,
+// after scene_load, what the static sources' loops need to draw them.  The render path and the lidar's pass get it as a pointer,
+// null without actors: they then enqueue what they always did.
+struct ScenePlan {
+    struct File { std::string path; uint32_t count, rec0, row0; };   // rec0: first record in d_rec; row0: first row of the planes
+    const sm_scene *scene = nullptr;
+    uint32_t n_views = 0;
+    std::vector<File> files;           // the distinct ones, in order of first mention
+    std::vector<uint32_t> file_of;     // per actor
+    uint64_t ids = 0;                  // records summed over the actors, present or not
+    uint64_t resident = 0, rows = 0;   // records of the distinct files; rows of the planes they take
+    uint32_t id_base = 0;              // A, the static total (scene_load)
+    uint32_t n_wg = 0;                 // workgroups of a splat: the actors' blocks
+    int cull = 1;
+};
+// host only: SM_E_ARG / SM_E_CAPACITY with g_err set, else the plan
+int scene_check(const sm_scene *scene, uint32_t n_views, const char *fn, ScenePlan &plan);
+// the id limit against the static total; then, unless the call draws nothing, the files read, uploaded and unpacked and the
+// call's tables on the device.  The call's tally begins here.
+int scene_load(sm_ctx *s, ScenePlan &plan, uint64_t static_total, bool draw, const char *fn);
+// One batch's actor launches on the context's stream, after every static source: the splat of views [v0, v0 + b) into the batch's
+// key planes, then the resolve of the actors' keys into the batch's output planes.  d_rps / d_poses: the batch's first.
+int scene_draw_image(sm_ctx *s, const ScenePlan &plan, const RenderParams *d_rps, uint32_t v0, uint32_t b, uint64_t *d_key, size_t npix,
+                     uint8_t *d_bgr, uint8_t *d_sem);
+int scene_draw_lidar(sm_ctx *s, const ScenePlan &plan, const LidarGrid &g, const LidarPose *d_poses, uint32_t v0, uint32_t b, uint64_t *d_key,
+                     size_t nbeams, float *d_range, int32_t *d_id, uint8_t *d_rgb, uint8_t *d_sem);
+int scene_fold(sm_ctx *s);             // once the batch's stream is waited for: its actor time into the tally
+int scene_end(sm_ctx *s, const ScenePlan &plan);   // the device tally into the call's
+// ---- sm_lidar.hip ----
+// sm_lidar_sweep (src null), sm_lidar_sweep_maps and, with a plan, sm_lidar_sweep_scene; fn: the one the call came through
+int lidar_sweep(sm_ctx *s, const sm_map_source *src, const sm_lidar_sensor *sn, const float *poses16, uint32_t n_sweeps, float *range, int32_t *id,
+                uint8_t *rgb, uint8_t *sem, const char *fn, ScenePlan *scene = nullptr);
 // ---- sm_recall.hip ----
 // the periodic policy: called by a frame that has just retired (one test unless it is on).  wrote_file: this round's retirement
 // wrote the policy's newest file, at this pose -- every row of it is far, so the recall does not read it
@@ -817,7 +871,7 @@ int render_image(sm_ctx *s, const float *view16, int w, int h, float fx, float f
                  const sm_fill_params *fill, uint8_t *bgr_out, uint8_t *sem_out, uint16_t *depth_mm_out, const char *who);
 int render_image_maps(sm_ctx *s, const sm_map_source *src, const float *views16, uint32_t n_views, int w, int h, float fx, float fy,
                       float cx, float cy, const sm_blend_params *blend, const sm_fill_params *fill, uint8_t *bgr_out, uint8_t *sem_out,
-                      uint16_t *depth_mm_out, const char *fn);
+                      uint16_t *depth_mm_out, const char *fn, ScenePlan *scene = nullptr);
 // ---- sm_loop.hip ----
 // sm_track_frame (rgb null) / sm_track_frame_rgb while sm_set_auto_loop is on: the young-window track, the census, one attempt
 int auto_loop_track(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const float *guess16, const sm_track_params *params,

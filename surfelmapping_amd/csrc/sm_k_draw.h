@@ -78,16 +78,16 @@ __device__ __forceinline__ void raster_tri(RVert v0, RVert v1, RVert v2, int w, 
         }
 }
 
-// One surfel of the novel view (draw_image.vert:18-28, draw_image_adaptive.geom:38-83): row `k` of the source, its fragments to `frag`.
-template <typename Frag>
-__device__ __forceinline__ void render_surfel(const RenderParams &rp, const float4 *__restrict__ pos_conf,
-                                              const float4 *__restrict__ norm_rad, uint32_t k, Frag &frag)
+// One surfel of the novel view (draw_image.vert:18-28, draw_image_adaptive.geom:38-83): centre `pc`, normal and radius from
+// nr_of() -- asked for only once the centre has passed the depth test --, its fragments to `frag`.  The one statement of the rule:
+// the forms below say where the two float4 come from.
+template <typename Frag, typename NormRad>
+__device__ __forceinline__ void render_surfel_of(const RenderParams &rp, const float4 pc, NormRad nr_of, Frag &frag)
 {
     const float maxDepth = 200.0f;                                          // src/GlobalModel.cpp:797
-    const float4 pc = pos_conf[k];
     const float3 ph = xform3(rp.t_inv, pc.x, pc.y, pc.z);                  // draw_image.vert:20
     if (ph.z >= maxDepth || ph.z <= 1.0f) return;                           // draw_image_adaptive.geom:41
-    const float4 nr = norm_rad[k];
+    const float4 nr = nr_of();
     const float3 n = normalize3(rot3(rp.t_inv, nr.x, nr.y, nr.z));
     const float r = nr.w;
     float3 x, y;
@@ -124,7 +124,22 @@ __device__ __forceinline__ void render_surfel(const RenderParams &rp, const floa
     raster_tri(rv[2], rv[1], rv[3], rp.w, rp.h, frag);
 }
 
-// ... drawn under `id` into a key map
+// ... row `k` of a source
+template <typename Frag>
+__device__ __forceinline__ void render_surfel(const RenderParams &rp, const float4 *__restrict__ pos_conf,
+                                              const float4 *__restrict__ norm_rad, uint32_t k, Frag &frag)
+{
+    render_surfel_of(rp, pos_conf[k], [&]() { return norm_rad[k]; }, frag);
+}
+
+// ... a surfel the caller holds in registers (an actor's row placed by its pose: sm_k_scene.h), drawn under `id` into a key map
+__device__ __forceinline__ void render_surfel(const RenderParams &rp, const float4 pc, const float4 nr, uint32_t id, uint64_t *__restrict__ key)
+{
+    KeyFrag frag{key, id};
+    render_surfel_of(rp, pc, [&]() { return nr; }, frag);
+}
+
+// ... row `k` drawn under `id` into a key map
 __device__ __forceinline__ void render_surfel(const RenderParams &rp, const float4 *__restrict__ pos_conf,
                                               const float4 *__restrict__ norm_rad, uint32_t k, uint32_t id, uint64_t *__restrict__ key)
 {

@@ -70,9 +70,11 @@ int ensure_tables(sm_ctx *s, const sm_lidar_sensor *sn)
     return SM_OK;
 }
 
-// src null: the live model alone (sm_lidar_sweep)
-int sweep(sm_ctx *s, const sm_map_source *src, const sm_lidar_sensor *sn, const float *poses16, uint32_t n_sweeps, float *range, int32_t *id,
-          uint8_t *rgb, uint8_t *sem, const char *fn)
+}  // namespace
+
+// src null: the live model alone (sm_lidar_sweep); scene non-null: its actors after every static source (sm_lidar_sweep_scene)
+int sm_impl::lidar_sweep(sm_ctx *s, const sm_map_source *src, const sm_lidar_sensor *sn, const float *poses16, uint32_t n_sweeps, float *range,
+                         int32_t *id, uint8_t *rgb, uint8_t *sem, const char *fn, ScenePlan *scene)
 {
     const double t_begin = now_ms();
     if (!s || !sn) { g_err = std::string(fn) + ": null context or sensor"; return SM_E_ARG; }
@@ -90,6 +92,7 @@ int sweep(sm_ctx *s, const sm_map_source *src, const sm_lidar_sensor *sn, const 
     Lidar &L = s->lid;
     L.stats = sm_lidar_stats_t{};
     L.stats_valid = true;
+    if (scene && (rc = scene_load(s, *scene, file_total + cnt, n_sweeps != 0, fn))) return rc;
     if (n_sweeps == 0) { L.stats.total_ms = (float)(now_ms() - t_begin); return SM_OK; }
     if (file_total && (rc = maps_ensure_staging(s))) return rc;
     if ((rc = ensure_tables(s, sn))) return rc;
@@ -180,9 +183,11 @@ int sweep(sm_ctx *s, const sm_map_source *src, const sm_lidar_sensor *sn, const 
                                    (const uint64_t *)s->d_alive.get(), g, poses[v0 + i], d_key + (size_t)i * nb, (uint32_t)file_total, d_tally);
             L.stats.surfels += cnt;
         }
-        resolve(cur.color, (uint32_t)file_total, cnt, 1);
+        resolve(cur.color, (uint32_t)file_total, cnt, scene ? 0 : 1);
         HIPCK(hipEventRecord(L.ev[1], s->stream));
         HIPCK(hipGetLastError());
+        // ---- the scene's actors, under this batch's poses; their resolve is the pass's last
+        if (scene && (rc = scene_draw_lidar(s, *scene, g, d_poses + v0, v0, b, d_key, nb, d_range, d_id, d_rgb, d_sem))) return rc;
 
         const size_t vp0 = (size_t)v0 * nb;
         HIPCK(hipMemcpyAsync(range + vp0, d_range, bp * 4, hipMemcpyDeviceToHost, s->stream));
@@ -193,15 +198,14 @@ int sweep(sm_ctx *s, const sm_map_source *src, const sm_lidar_sensor *sn, const 
         float ms = 0.0f;
         HIPCK(hipEventElapsedTime(&ms, L.ev[0], L.ev[1]));
         L.stats.device_ms += ms;
+        if (scene && (rc = scene_fold(s))) return rc;
     }
     LidarTally t{};
     HIPCK(hipMemcpy(&t, d_tally, sizeof t, hipMemcpyDeviceToHost));
     L.stats.tests = t.tests; L.stats.wide = t.wide; L.stats.blocks_skipped = t.skipped;
     L.stats.total_ms = (float)(now_ms() - t_begin);
-    return SM_OK;
+    return scene ? scene_end(s, *scene) : SM_OK;
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -229,7 +233,7 @@ int sm_lidar_sweep(sm_ctx *s, const sm_lidar_sensor *sn, const float *pose16, fl
 {
     const char *fn = "sm_lidar_sweep";
     if (!pose16 || !range) { g_err = std::string(fn) + ": null pose or range"; return SM_E_ARG; }
-    return sweep(s, nullptr, sn, pose16, 1, range, id, rgb, sem, fn);
+    return lidar_sweep(s, nullptr, sn, pose16, 1, range, id, rgb, sem, fn);
 }
 
 int sm_lidar_sweep_maps(sm_ctx *s, const sm_map_source *src, const sm_lidar_sensor *sn, const float *poses16, uint32_t n_sweeps, float *range,
@@ -237,7 +241,7 @@ int sm_lidar_sweep_maps(sm_ctx *s, const sm_map_source *src, const sm_lidar_sens
 {
     const char *fn = "sm_lidar_sweep_maps";
     if (!src) { g_err = std::string(fn) + ": null source"; return SM_E_ARG; }
-    return sweep(s, src, sn, poses16, n_sweeps, range, id, rgb, sem, fn);
+    return lidar_sweep(s, src, sn, poses16, n_sweeps, range, id, rgb, sem, fn);
 }
 
 int sm_lidar_stats(sm_ctx *s, sm_lidar_stats_t *out)

@@ -1,4 +1,4 @@
-// sm_map_stream.h -- private to sm_render_maps.hip, sm_lidar.hip, sm_recall.hip, sm_warp.hip, sm_simplify.hip, sm_register.hip, sm_compare.hip, sm_tile.hip, sm_segment.hip, sm_mesh.hip and sm_ground.hip: the double-buffered stream of
+// sm_map_stream.h -- private to sm_render_maps.hip, sm_lidar.hip, sm_recall.hip, sm_warp.hip, sm_simplify.hip, sm_register.hip, sm_compare.hip, sm_tile.hip, sm_segment.hip, sm_mesh.hip, sm_ground.hip and sm_scene.hip (which takes the planes' layout and the file format from here, no stream): the double-buffered stream of
 // map-file chunks through the context's MapStaging, one object per call; behind it what the two readers of whole sets (the
 // streamed renderers, the lidar) do alike: the opening (maps_open) and the batch of views (maps_batch), the opening of two sets
 // (check_sets, open_sets) and the pass over a set that only launches (maps_feed).  Chunk c of a pass goes

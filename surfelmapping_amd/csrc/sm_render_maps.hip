@@ -23,6 +23,8 @@ struct Mode {
     // image only (sm_render_image_maps_blend): the colours of the visible layer blended (null: the nearest surfel's), which takes a
     // second pass over the files per batch
     const sm_blend_params *blend;
+    // image only (sm_render_image_scene): the actors drawn after every static source (null: none)
+    ScenePlan *scene;
 };
 
 int render_maps(sm_ctx *s, const sm_map_source *src, const char *fn, const Mode &md)
@@ -40,6 +42,7 @@ int render_maps(sm_ctx *s, const sm_map_source *src, const char *fn, const Mode 
     RenderMaps &rm = s->maps;
     rm.stats = sm_maps_stats{};
     rm.stats_valid = true;
+    if (md.scene && (rc = scene_load(s, *md.scene, file_total + cnt, md.n_views != 0, fn))) return rc;
     if (md.n_views == 0) { rm.stats.total_ms = (float)(now_ms() - t_begin); return SM_OK; }
     if (file_total && (rc = maps_ensure_staging(s))) return rc;
 
@@ -157,6 +160,9 @@ int render_maps(sm_ctx *s, const sm_map_source *src, const char *fn, const Mode 
             rm.stats.device_ms += ms;
         }
 
+        // ---- the scene's actors, under this batch's poses
+        if (md.scene && (rc = scene_draw_image(s, *md.scene, d_rp, v0, b, d_key, npix, d_bgr, d_sem))) return rc;
+
         // ---- pixels nobody won, then the batch's planes to the caller
         if (md.image) hipLaunchKernelGGL(k_maps_finish_image, dim3((unsigned)((bp + 255) / 256)), dim3(256), 0, s->stream, d_key, bp, d_bgr, d_sem);
         else hipLaunchKernelGGL(k_maps_finish_view, dim3(pblocks, b), dim3(256), 0, s->stream, d_vs, d_key, npix, d_rgba, d_depth, d_id);
@@ -190,12 +196,13 @@ int render_maps(sm_ctx *s, const sm_map_source *src, const char *fn, const Mode 
         HIPCK(hipStreamSynchronize(s->stream));
         if (md.blend && (rc = blend_fold(s))) return rc;
         if (md.fill && (rc = fill_fold(s))) return rc;
+        if (md.scene && (rc = scene_fold(s))) return rc;
     }
     std::vector<uint32_t> skipped(V);
     HIPCK(hipMemcpy(skipped.data(), d_skip, V * 4, hipMemcpyDeviceToHost));
     for (uint32_t x : skipped) rm.stats.pairs_skipped += x;
     rm.stats.total_ms = (float)(now_ms() - t_begin);
-    return SM_OK;
+    return md.scene ? scene_end(s, *md.scene) : SM_OK;
 }
 
 }  // namespace
@@ -222,13 +229,18 @@ int sm_impl::maps_ensure_staging(sm_ctx *s)
 
 void sm_impl::maps_intake(sm_ctx *s, const float4 *d_rec, uint32_t n)
 {
-    hipLaunchKernelGGL(k_maps_intake, dim3((n + MAPS_BLOCK - 1) / MAPS_BLOCK), dim3(256), 0, s->stream, d_rec, n, planes(s->staging), s->staging.d_box.get());
+    maps_intake_to(s, d_rec, n, planes(s->staging), s->staging.d_box.get());
+}
+
+void sm_impl::maps_intake_to(sm_ctx *s, const float4 *d_rec, uint32_t n, const MapsSoA &out, float4 *d_box)
+{
+    hipLaunchKernelGGL(k_maps_intake, dim3((n + MAPS_BLOCK - 1) / MAPS_BLOCK), dim3(256), 0, s->stream, d_rec, n, out, d_box);
 }
 
 // sm_render_image_maps (fn) and, with fill or depth_mm_out, what sm_render_image_maps_ex adds to it; with blend, sm_render_image_maps_blend
 int sm_impl::render_image_maps(sm_ctx *s, const sm_map_source *src, const float *views16, uint32_t n_views, int w, int h, float fx, float fy,
                                float cx, float cy, const sm_blend_params *blend, const sm_fill_params *fill, uint8_t *bgr_out,
-                               uint8_t *sem_out, uint16_t *depth_mm_out, const char *fn)
+                               uint8_t *sem_out, uint16_t *depth_mm_out, const char *fn, ScenePlan *scene)
 {
     if (!s || !src) { g_err = std::string(fn) + ": null context or source"; return SM_E_ARG; }
     if (n_views && (!views16 || !bgr_out || !sem_out)) { g_err = std::string(fn) + ": null views or outputs"; return SM_E_ARG; }
@@ -243,7 +255,7 @@ int sm_impl::render_image_maps(sm_ctx *s, const sm_map_source *src, const float 
     md.image = true; md.w = w; md.h = h; md.n_views = n_views;
     md.params = rps.data(); md.param_size = sizeof(RenderParams);
     md.out0 = bgr_out; md.out1 = sem_out;
-    md.fill = fill; md.out_depth = depth_mm_out; md.blend = blend;
+    md.fill = fill; md.out_depth = depth_mm_out; md.blend = blend; md.scene = scene;
     return render_maps(s, src, fn, md);
 }
 

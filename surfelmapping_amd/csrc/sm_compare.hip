@@ -1,8 +1,9 @@
 // sm_compare.hip -- change detection between two map sets (sm_compare_maps; DESIGN.md "4r. Change detection"): the reference set
 // streamed once into a fine voxel table with one representative per key and a cover table of keys, then the query set streamed
 // once, every record labelled against them and the records whose label is asked for written, in set order, to one map file.
-// Kernels: sm_k_compare.h; the tables themselves and the ranked output: sm_voxel.h.
-#include "sm_voxel.h"
+// Kernels: sm_k_compare.h; the tables themselves and the ranked output: sm_voxel.h; the scratch, the export and the collect of a
+// call: sm_set_call.h.
+#include "sm_set_call.h"
 #include "sm_k_compare.h"
 
 using namespace sm;
@@ -11,7 +12,7 @@ using sm_mapfile::now_ms;
 namespace {
 
 constexpr uint32_t CHUNK = MapStaging::CHUNK;
-enum { EV_CLR0 = 0, EV_CLR1, EV_REF0, EV_REF1, EV_QRY0, EV_QRY1 };     // pairs: add_marked(&ev[first])
+enum { EV_CLR0 = 0, EV_CLR1, EV_REF0, EV_REF1, EV_QRY0, EV_QRY1 };     // pairs of the scratch's events: add_marked(&ev[first])
 static_assert(CMP_FINE == 0 && CMP_COVER == SIMP_TALLY_WORDS, "lut_open puts a table's tally words first and its cover's behind them");
 
 int check_params(const sm_compare_params *p, bool writes, const char *who)
@@ -30,26 +31,11 @@ int check_params(const sm_compare_params *p, bool writes, const char *who)
     return SM_OK;
 }
 
-int cmp_alloc(sm_ctx *s)
-{
-    Compare &cm = s->cmp;
-    if (cm.d_tally) return SM_OK;
-    Dev<uint8_t> label[2], keep;
-    Dev<uint32_t> tally;
-    int rc;
-    if ((rc = dalloc(label[0], CHUNK)) || (rc = dalloc(label[1], CHUNK)) || (rc = dalloc(keep, CHUNK)) || (rc = dalloc(tally, CMP_TALLY_WORDS))) return rc;
-    HIPCK(hipHostMalloc((void **)cm.h_tally.put(), CMP_TALLY_WORDS * 4, hipHostMallocDefault));
-    for (Host<uint8_t> &h : cm.h_label) HIPCK(hipHostMalloc((void **)h.put(), CHUNK, hipHostMallocDefault));
-    for (Event &e : cm.ev) HIPCK(hipEventCreate(e.put()));
-    cm.d_label[0] = std::move(label[0]); cm.d_label[1] = std::move(label[1]); cm.d_keep = std::move(keep);
-    cm.d_tally = std::move(tally);                       // last: it marks the set complete
-    return SM_OK;
-}
-
 // One call's device side: both tables, the kernel arguments, the launches on the context's stream.
 struct CompareJob {
     sm_ctx *s;
     Compare &cm;
+    const Event *ev;
     const char *who;
     const sm_compare_params &p;
     LookupTable t;                     // the fine table (split faces) with its cover table (no faces); tally words CMP_FINE, CMP_COVER
@@ -58,20 +44,19 @@ struct CompareJob {
     RankedOutput out;
     uint32_t launches = 0;
 
-    CompareJob(sm_ctx *s_, const char *who_, const sm_compare_params &p_) : s(s_), cm(s_->cmp), who(who_), p(p_), out(s_, who_) {}
+    CompareJob(sm_ctx *s_, const char *who_, const sm_compare_params &p_) : s(s_), cm(s_->cmp), ev(s_->cmp.scratch.ev), who(who_), p(p_), out(s_, who_) {}
 
     int open(uint64_t reference_records, const float *pose16, bool writes)
     {
         int rc;
         uint64_t S;
-        if ((rc = cmp_alloc(s)) || (rc = voxel_slots(reference_records, p.max_cells, who, "a table", S))) return rc;
+        if ((rc = cm.scratch.ensure(CMP_TALLY_WORDS)) || (rc = cm.label.ensure()) || (!cm.d_keep && (rc = dalloc(cm.d_keep, CHUNK)))) return rc;
+        if ((rc = voxel_slots(reference_records, p.max_cells, who, "a table", S))) return rc;
         t.a = voxel_args(p.voxel_mm, 0, p.origin, 1, p.max_cells);
         t.ac = voxel_args(p.voxel_mm, p.cover_shift, p.origin, 0, p.max_cells);
-        if ((rc = lut_open(tables, &t, 1, S, true, cm.d_tally.get()))) return rc;
+        if ((rc = lut_open(tables, &t, 1, S, true, cm.scratch.d_tally.get()))) return rc;
         // the tables' initialisation is device time of theirs (table_ms)
-        if ((rc = mark(s, cm.ev[EV_CLR0])) || (rc = lut_clear(s, &t, 1))) return rc;
-        HIPCK(hipMemsetAsync(cm.d_tally, 0, CMP_TALLY_WORDS * 4, s->stream));
-        if ((rc = mark(s, cm.ev[EV_CLR1]))) return rc;
+        if ((rc = mark(s, ev[EV_CLR0])) || (rc = lut_clear(s, &t, 1)) || (rc = cm.scratch.clear(s->stream)) || (rc = mark(s, ev[EV_CLR1]))) return rc;
 
         cp.lut = t.lut;
         cp.cover = t.TC.key;
@@ -96,11 +81,11 @@ struct CompareJob {
     void classify(const float4 *d_rec, uint32_t n, int q)
     {
         const unsigned nblk = (n + 255) / 256;
-        hipLaunchKernelGGL(k_compare_classify, dim3(nblk), dim3(256), 0, s->stream, d_rec, n, cp, cm.d_label[q].get(), cm.d_keep.get(), out.blk_cnt(),
-                           cm.d_tally.get());
+        hipLaunchKernelGGL(k_compare_classify, dim3(nblk), dim3(256), 0, s->stream, d_rec, n, cp, cm.label.d[q].get(), cm.d_keep.get(), out.blk_cnt(),
+                           cm.scratch.d_tally.get());
         launches++;
         if (out.writes()) {
-            out.scan(nblk, cm.d_tally.get() + CMP_FINE, q, launches);
+            out.scan(nblk, cm.scratch.d_tally.get() + CMP_FINE, q, launches);
             hipLaunchKernelGGL(k_compare_emit, dim3(nblk), dim3(256), 0, s->stream, d_rec, n, (const uint8_t *)cm.d_keep.get(), out.blk_base(),
                                out.info(q), out.out(q));
             launches++;
@@ -108,7 +93,7 @@ struct CompareJob {
         cm.stats.chunks++;
     }
     // the tally, once the stream is idle
-    int tally() { return voxel_read_tally(s, cm.d_tally.get(), cm.h_tally.get(), CMP_TALLY_WORDS); }
+    int tally() { return cm.scratch.read(s); }
 };
 
 }  // namespace
@@ -141,16 +126,14 @@ int sm_compare_maps(sm_ctx *s, const sm_map_source *query, const sm_map_source *
     if ((rc = check_whole_map(s, who)) || (rc = check_params(p, writes, who)) || (rc = check_not_mid_cull(s, who)) || (rc = check_pose(pose16, who)))
         return rc;
     sm_mapset::ReadSet qset, rset;
-    if ((rc = check_sets(query, reference, who))) return rc;
-    for (const sm_map_source *src : {query, reference})  // the output needs a path of its own
-        for (uint32_t i = 0; out_path && i < src->n_paths; ++i)
-            if (strcmp(src->paths[i], out_path) == 0) { g_err = sm_mapfile::said(who, out_path, " is a file of a set: the output needs a path of its own"); return SM_E_ARG; }
+    if ((rc = check_sets(query, reference, who)) || (rc = check_own_path(query, out_path, who)) || (rc = check_own_path(reference, out_path, who))) return rc;
     if ((rc = open_sets(query, reference, who, qset, rset))) return rc;
-    HIPCK(hipSetDevice(s->cfg.device));
-    if ((rc = ensure_compact(s)) || (rc = pull_state(s))) return rc;      // (waits for frames in flight; count is the live surfels)
-    const uint32_t model = s->h_state->count, qcnt = query->include_model ? model : 0u, rcnt = reference->include_model ? model : 0u;
+    const sm_map_source *const srcs[2] = {query, reference};
+    const sm_mapset::ReadSet *const sets[2] = {&qset, &rset};
+    uint32_t live[2];
+    if ((rc = maps_counts(s, who, 2, srcs, sets, live))) return rc;
+    const uint32_t qcnt = live[0], rcnt = live[1];
     const uint64_t qtotal = qset.file_total + qcnt, rtotal = rset.file_total + rcnt;
-    if (qtotal > 0x7FFFFFFFull || rtotal > 0x7FFFFFFFull) { g_err = std::string(who) + ": a set of more than 2^31 - 1 records"; return SM_E_CAPACITY; }
 
     Compare &cm = s->cmp;
     cm.stats = sm_compare_stats_t{};
@@ -161,25 +144,21 @@ int sm_compare_maps(sm_ctx *s, const sm_map_source *query, const sm_map_source *
 
     CompareJob job(s, who, *p);
     RankedOutput &ro = job.out;
-    if ((rc = job.open(rtotal, pose16, writes))) return rc;
-    const float4 *d_model = nullptr;
-    if (qcnt || rcnt) {
-        if ((rc = ensure_export(s, (size_t)model * 48))) return rc;
-        export_aos(s, (float *)s->d_export.get(), 0u, model);
-        d_model = (const float4 *)s->d_export.get();
-    }
+    const Event *ev = job.ev;
+    const float4 *d_model;
+    if ((rc = job.open(rtotal, pose16, writes)) || (rc = maps_export(s, std::max(qcnt, rcnt), d_model))) return rc;
     if (qset.jobs.size() + rset.jobs.size() || (qcnt && writes))       // (the live model's kept records leave through its host buffer too)
         if ((rc = maps_ensure_staging(s))) return rc;
     float copy_ms = 0.0f;
 
     // ---- the reference: every chunk into both tables, then the representatives
-    if ((rc = maps_feed(s, who, rset, reference->paths, rcnt, d_model, {&cm.stats.read_ms, &copy_ms, &cm.stats.table_ms}, cm.ev[EV_REF0],
+    if ((rc = maps_feed(s, who, rset, reference->paths, rcnt, d_model, {&cm.stats.read_ms, &copy_ms, &cm.stats.table_ms}, ev[EV_REF0],
                         [&](const float4 *d_rec, uint32_t n, uint32_t) { job.insert(d_rec, n); })))
         return rc;
     lut_finish(s, job.t, job.launches);
-    if ((rc = mark(s, cm.ev[EV_REF1])) || (rc = job.tally())) return rc;
-    if ((rc = add_marked(&cm.ev[EV_CLR0], &cm.stats.table_ms)) || (rc = add_marked(&cm.ev[EV_REF0], &cm.stats.table_ms))) return rc;
-    const uint32_t *h = cm.h_tally.get();
+    if ((rc = mark(s, ev[EV_REF1])) || (rc = job.tally())) return rc;
+    if ((rc = add_marked(&ev[EV_CLR0], &cm.stats.table_ms)) || (rc = add_marked(&ev[EV_REF0], &cm.stats.table_ms))) return rc;
+    const uint32_t *h = cm.scratch.h();
     // (nothing has been written: the labels and the output follow)
     if ((rc = voxel_check_tally(h + CMP_FINE, p->max_cells, who, "keys in the fine table")) ||
         (rc = voxel_check_tally(h + CMP_COVER, p->max_cells, who, "keys in the cover table")))
@@ -190,20 +169,10 @@ int sm_compare_maps(sm_ctx *s, const sm_map_source *query, const sm_map_source *
     // ---- the query: the labels of chunk c, and what is kept of it, come back while chunk c + 1 is on the device
     // (without an output the scratch alone: the labelling counts per block either way)
     if ((rc = writes ? ro.open(out_path, ".compare.tmp", qset, qcnt) : ro.ensure(0, 0))) return rc;
-    // the chunk of n records in buffer q, ids gid0 ..: its kernels are over; on `stream`, behind one wait: the kept records through the
-    // staging's host buffer q, the labels through the pinned buffer q of this call's own
-    const auto collect = [&](int q, uint32_t n, uint64_t gid0, hipStream_t stream) -> int {
-        const double t0 = now_ms();
-        uint32_t m;
-        if (int e = ro.stage(q, stream, m)) return e;
-        if (labels) HIPCK(hipMemcpyAsync(cm.h_label[q], cm.d_label[q], n, hipMemcpyDeviceToHost, stream));
-        if (m || labels) HIPCK(hipStreamSynchronize(stream));
-        if (labels) memcpy(labels + gid0, cm.h_label[q].get(), n);
-        const int e = ro.write(q, m);
-        cm.stats.write_ms += (float)(now_ms() - t0);
-        return e;
+    const auto collect = [&](int q, uint32_t n, uint64_t gid0, hipStream_t stream) {
+        return collect_labelled(ro, cm.label, labels, q, n, gid0, stream, &cm.stats.write_ms);
     };
-    if ((rc = ro.run(qset, query->paths, qcnt, d_model, {&cm.stats.read_ms, &copy_ms, &cm.stats.classify_ms}, &cm.ev[EV_QRY0],
+    if ((rc = ro.run(qset, query->paths, qcnt, d_model, {&cm.stats.read_ms, &copy_ms, &cm.stats.classify_ms}, &ev[EV_QRY0],
                      [&](const float4 *d_rec, uint32_t n, uint64_t, int q) { job.classify(d_rec, n, q); }, collect)))
         return rc;
     if ((rc = job.tally())) return rc;
@@ -215,12 +184,6 @@ int sm_compare_maps(sm_ctx *s, const sm_map_source *query, const sm_map_source *
     return SM_OK;
 }
 
-int sm_compare_stats(sm_ctx *s, sm_compare_stats_t *out)
-{
-    if (!s || !out) { g_err = "sm_compare_stats: null argument"; return SM_E_ARG; }
-    if (!s->cmp.stats_valid) { g_err = "sm_compare_stats: no sm_compare_maps call yet"; return SM_E_ARG; }
-    *out = s->cmp.stats;
-    return SM_OK;
-}
+SM_STATS_GETTER(sm_compare_stats, sm_compare_stats_t, cmp, "sm_compare_maps")
 
 }  // extern "C"

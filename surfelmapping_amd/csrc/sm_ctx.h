@@ -327,12 +327,34 @@ struct RankScratch {
     size_t out_cap[2] = {0, 0};        // records
 };
 
+// What every map-set analysis call keeps on its context (sm_set_call.h defines the members): the device tally of `words` words,
+// its pinned mirror and N events, made whole or not at all by the context's first such call.
+template <int N>
+struct CallScratch {
+    static constexpr int N_EV = N;
+    Dev<uint32_t> d_tally;             // (set last: it marks the scratch complete)
+    Host<uint32_t> h_tally;            // pinned
+    size_t words = 0;
+    Event ev[N];
+    int ensure(size_t tally_words);
+    int clear(hipStream_t stream) const;             // the memset of the whole tally
+    int read(sm_ctx *s, size_t n = 0) const;         // the tally's first n words (0: all) at h(), once the context's stream is idle
+    const uint32_t *h() const { return h_tally.get(); }
+};
+// The labels of a labelled pass (sm_set_call.h's collect_labelled): per record of the chunk in buffer c & 1 its label, and the
+// pinned buffers a chunk's labels leave through on their way to the caller.  Whole or absent, like the scratch.
+template <typename T>
+struct LabelPair {
+    Dev<T> d[2];
+    Host<T> h[2];                      // (h[1] is set last)
+    int ensure();
+};
+
 // simplification (sm_simplify.hip, sm_k_simplify.h): the scratch of one chunk's second pass beside the context's RankScratch, the
 // last call's tally.  The table lives for one call.
 struct Simplify {
     Dev<uint32_t> d_code;              // per record of a chunk: not a representative | loose | its cell's slot
-    Dev<uint32_t> d_tally;             // error word | distinct cells | running rank | loose | merged | largest
-    Event ev[2];                       // around what runs outside a chunk stream
+    CallScratch<2> scratch;            // error word | distinct cells | running rank | loose | merged | largest; around what runs outside a chunk stream
     sm_simplify_stats_t stats{};
     bool stats_valid = false;
 };
@@ -340,12 +362,10 @@ struct Simplify {
 // registration (sm_register.hip, sm_k_register.h): what outlives a call -- the tallies, the partial sums, the state and its pinned
 // mirror, the events -- and the last call's tally.  Tables and samples live for one call.
 struct Register {
-    Dev<uint32_t> d_tally;             // per level the simplification's tally words, then the regular samples
-    Host<uint32_t> h_tally;            // pinned
+    CallScratch<8> scratch;            // per level the simplification's tally words, then the regular samples; around the target's model and the finish, the source's model, the iterations, the tables' memsets
     Dev<double> d_part;
     Dev<RegState> d_state;
     Host<RegState> h_state;            // pinned
-    Event ev[8];                       // around the target's model and the finish, the source's model, the iterations, the tables' memsets
     sm_register_stats_t stats{};
     bool stats_valid = false;
 };
@@ -353,12 +373,9 @@ struct Register {
 // change detection (sm_compare.hip, sm_k_compare.h): the scratch of one chunk of the query beside the context's RankScratch, the
 // buffers its labels leave through, the tallies and the last call's.  The tables live for one call.
 struct Compare {
-    Dev<uint8_t> d_label[2];           // per record of the chunk in buffer c & 1: its label
+    LabelPair<uint8_t> label;
     Dev<uint8_t> d_keep;               // per record of a chunk: 1 = its label is in the write mask
-    Dev<uint32_t> d_tally;             // the fine table's tally words (SIMP_RUN: the running rank), the cover table's, the label counts
-    Host<uint32_t> h_tally;            // pinned
-    Host<uint8_t> h_label[2];          // pinned: a chunk's labels on their way to the caller
-    Event ev[6];                       // around the tables' memsets, the reference's model and the finish, a chunk of the query's model
+    CallScratch<6> scratch;            // the fine table's tally words (SIMP_RUN: the running rank), the cover table's, the label counts; around the tables' memsets, the reference's model and the finish, a chunk of the query's model
     sm_compare_stats_t stats{};
     bool stats_valid = false;
 };
@@ -366,10 +383,10 @@ struct Compare {
 // spatial tiling (sm_tile.hip, sm_k_tile.h): the tallies and events that outlive a call, the last call's tally.  The tile table,
 // the batch buffers and the sort's scratch live for one call.
 struct Tile {
-    Dev<uint32_t> d_tally;             // [0]: error word | distinct tiles | running rank | loose; [1]: the loose records' running rank
+    // [0]: error word | distinct tiles | running rank | loose; [1]: the loose records' running rank.  Events: around what runs outside
+    // a chunk stream and around the sort; per piece buffer (two): around the gather, after the copy
+    CallScratch<10> scratch;
     Dev<unsigned long long> d_bits;    // the OR and the AND of a batch's keys
-    static constexpr int N_EV = 10;    // around what runs outside a chunk stream and around the sort; per piece buffer (two): around the gather, after the copy
-    Event ev[N_EV];
     sm_tile_stats_t stats{};
     bool stats_valid = false;
 };
@@ -378,11 +395,8 @@ struct Tile {
 // its labels leave through, the tallies and the last call's.  The table and the component rows live for one call.
 struct Segment {
     Dev<uint32_t> d_code;              // per record of a chunk: its component's root slot | SMALL | SKIPPED | LOOSE
-    Dev<uint32_t> d_label[2];          // per record of the chunk in buffer c & 1: its label
-    Host<uint32_t> h_label[2];         // pinned: a chunk's labels on their way to the caller
-    Dev<uint32_t> d_tally;             // the table's tally words (SIMP_RUN: the kept records' running rank), the openers', the counts
-    Host<uint32_t> h_tally;            // pinned
-    Event ev[8];                       // around the memsets, reading 1's model, link to reduce, a chunk of reading 2's model
+    LabelPair<uint32_t> label;
+    CallScratch<8> scratch;            // the table's tally words (SIMP_RUN: the kept records' running rank), the openers', the counts; around the memsets, reading 1's model, link to reduce, a chunk of reading 2's model
     sm_segment_stats_t stats{};
     bool stats_valid = false;
 };
@@ -390,10 +404,9 @@ struct Segment {
 // meshing (sm_mesh.hip, sm_k_mesh.h): the tally, its pinned mirror, the events and the last call's tally.  The tables, the owners'
 // pairs and the mesh live for one call.
 struct Mesh {
-    Dev<uint32_t> d_tally;             // the cell table's tally words, the lattice table's, the running ranks, the counts, the totals
-    Host<uint32_t> h_tally;            // pinned
-    static constexpr int N_EV = 12;    // around the memsets, the model's inserts, claim to cubes, the owners' sort, the emit; per piece buffer (two): after the copy
-    Event ev[N_EV];
+    // the cell table's tally words, the lattice table's, the running ranks, the counts, the totals.  Events: around the memsets, the
+    // model's inserts, claim to cubes, the owners' sort, the emit; per piece buffer (two): after the copy
+    CallScratch<12> scratch;
     sm_mesh_stats_t stats{};
     bool stats_valid = false;
 };
@@ -401,10 +414,9 @@ struct Mesh {
 // the ground map (sm_ground.hip, sm_k_ground.h): the tally, its pinned mirror, the events and the last call's stats.  The cells'
 // accumulators and the planes live for one call.
 struct Ground {
-    Dev<uint32_t> d_tally;             // the counts by record kind and by cell state
-    Host<uint32_t> h_tally;            // pinned
-    static constexpr int N_EV = 12;    // around: the memsets, reading 1's model, the fill, reading 2's model, finish and state, the transform
-    Event ev[N_EV];
+    // the counts by record kind and by cell state.  Events around: the memsets, reading 1's model, the fill, reading 2's model, finish
+    // and state, the transform
+    CallScratch<12> scratch;
     sm_ground_stats_t stats{};
     bool stats_valid = false;
 };

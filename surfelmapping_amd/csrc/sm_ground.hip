@@ -2,8 +2,9 @@
 // lowest ground-like record of every cell of the window, the reference heights filled in from neighbouring cells, the set streamed
 // again for the ground's sums and the obstacles, the planes and states finished per cell, the blocking cells' capped Euclidean
 // distance transform, and every plane asked for back with one copy.  A file whose index box misses the window is read in neither
-// reading.  Kernels: sm_k_ground.h.  The accumulators and planes are allocated per call and freed when it ends.
-#include "sm_map_stream.h"
+// reading.  Kernels: sm_k_ground.h; the call's frame: sm_set_call.h.  The accumulators and planes are allocated per call and freed
+// when it ends.
+#include "sm_set_call.h"
 #include "sm_k_ground.h"
 
 using namespace sm;
@@ -12,7 +13,7 @@ using sm_mapfile::now_ms;
 namespace {
 
 enum { EV_CLR0 = 0, EV_CLR1, EV_MIN0, EV_MIN1, EV_FILL0, EV_FILL1, EV_ACC0, EV_ACC1, EV_STATE0, EV_STATE1, EV_CLEAR0, EV_CLEAR1, N_EV };
-static_assert(N_EV == Ground::N_EV, "the context holds the events of a call");
+static_assert(N_EV == decltype(Ground::scratch)::N_EV, "the context holds the events of a call");
 static_assert(GROUND_NONE == SM_GROUND_NONE && GROUND_UNKNOWN == SM_GROUND_UNKNOWN && GROUND_FREE == SM_GROUND_FREE &&
               GROUND_OBSTACLE == SM_GROUND_OBSTACLE && GROUND_STEP == SM_GROUND_STEP, "the states are the header's");
 
@@ -60,8 +61,7 @@ GroundArgs ground_args(const sm_ground_params &p)
     g.reach = p.reach_cells;
     g.unknown_blocks = p.unknown_blocks;
     g.step_on = p.step_mm > 0 ? 1 : 0;
-    const char *e = std::getenv("SM_GROUND_NO_COMBINE");
-    g.combine = (e && e[0] == '1') ? 0 : 1;
+    g.combine = env_is_one("SM_GROUND_NO_COMBINE") ? 0 : 1;
     return g;
 }
 
@@ -80,22 +80,11 @@ bool box_misses_window(const sm_mapset::FileIndex::Entry &e, const GroundArgs &g
     return false;
 }
 
-int ground_alloc(sm_ctx *s)
-{
-    Ground &gr = s->ground;
-    if (gr.d_tally) return SM_OK;
-    Dev<uint32_t> tally;
-    if (int rc = dalloc(tally, GROUND_TALLY_WORDS)) return rc;
-    HIPCK(hipHostMalloc((void **)gr.h_tally.put(), GROUND_TALLY_WORDS * 4, hipHostMallocDefault));
-    for (Event &e : gr.ev) HIPCK(hipEventCreate(e.put()));
-    gr.d_tally = std::move(tally);                       // last: it marks the set complete
-    return SM_OK;
-}
-
 // One call's device side: the accumulators and the planes of N cells, the launches on the context's stream.
 struct GroundJob {
     sm_ctx *s;
     Ground &gr;
+    const Event *ev;
     GroundArgs g;
     size_t N;
     Dev<uint8_t> mem;                  // freed when the call ends
@@ -106,15 +95,15 @@ struct GroundJob {
     uint32_t launches = 0;
     sm_ground_stats_t stats{};         // this call's; the context's once the call has succeeded
 
-    GroundJob(sm_ctx *s_, const GroundArgs &g_) : s(s_), gr(s_->ground), g(g_), N((size_t)g_.nu * g_.nv) {}
+    GroundJob(sm_ctx *s_, const GroundArgs &g_) : s(s_), gr(s_->ground), ev(s_->ground.scratch.ev), g(g_), N((size_t)g_.nu * g_.nv) {}
 
-    uint32_t *tally() const { return gr.d_tally.get(); }
+    uint32_t *tally() const { return gr.scratch.d_tally.get(); }
 
     int open()
     {
         int rc;
         // SW, SH, SC[3], best, n_obst, top (zero) | Z (no ground) | R, ground, clear2 | state, cls, gcol, bgr[3]
-        if ((rc = ground_alloc(s)) || (rc = dalloc(mem, N * (GROUND_ZERO_BYTES + 4 * 4 + 6)))) return rc;
+        if ((rc = gr.scratch.ensure(GROUND_TALLY_WORDS)) || (rc = dalloc(mem, N * (GROUND_ZERO_BYTES + 4 * 4 + 6)))) return rc;
         uint8_t *b = mem.get();
         P.SW = (unsigned long long *)b; P.SH = P.SW + N; P.SC = P.SH + N; P.best = P.SC + 3 * N;
         P.n_obst = (uint32_t *)(P.best + N);
@@ -122,11 +111,11 @@ struct GroundJob {
         Z = P.top + N; R = Z + N; ground = R + N;
         clear2 = (uint32_t *)(ground + N);
         state = (uint8_t *)(clear2 + N); cls = state + N; gcol = cls + N; bgr = gcol + N;
-        if ((rc = mark(s, gr.ev[EV_CLR0]))) return rc;
+        if ((rc = mark(s, ev[EV_CLR0]))) return rc;
         HIPCK(hipMemsetAsync(b, 0, N * GROUND_ZERO_BYTES, s->stream));
         HIPCK(hipMemsetAsync(Z, 0x7F, N * 4, s->stream));
-        HIPCK(hipMemsetAsync(tally(), 0, GROUND_TALLY_WORDS * 4, s->stream));
-        return mark(s, gr.ev[EV_CLR1]);
+        if ((rc = gr.scratch.clear(s->stream))) return rc;
+        return mark(s, ev[EV_CLR1]);
     }
     void lowest(const float4 *d_rec, uint32_t n)
     {
@@ -161,13 +150,6 @@ struct GroundJob {
         hipLaunchKernelGGL(k_ground_rows, dim3((g.nu + 255) / 256, g.nv), dim3(256), 0, s->stream, g, (const uint8_t *)gcol, clear2);
         launches += 2;
     }
-    int read_tally()
-    {
-        HIPCK(hipGetLastError());
-        HIPCK(hipMemcpyAsync(gr.h_tally.get(), tally(), GROUND_TALLY_WORDS * 4, hipMemcpyDeviceToHost, s->stream));
-        HIPCK(hipStreamSynchronize(s->stream));
-        return SM_OK;
-    }
 };
 
 }  // namespace
@@ -199,14 +181,13 @@ int sm_ground_maps(sm_ctx *s, const sm_map_source *src, const sm_ground_params *
                    uint8_t *bgr, uint32_t *clear2, sm_ground_info *info)
 {
     const char *who = "sm_ground_maps";
-    const double t_begin = now_ms();
+    SetCall call(s, src, who);
     if (!s || !src || !p || !info) { g_err = std::string(who) + ": null argument"; return SM_E_ARG; }
     int rc;
-    if ((rc = check_whole_map(s, who)) || (rc = check_params(p, who)) || (rc = check_not_mid_cull(s, who)) || (rc = check_map_source(src, who))) return rc;
-    sm_mapset::ReadSet set;
-    uint32_t cnt;
-    if ((rc = maps_open(s, src, who, check_whole_map, set, cnt))) return rc;
-    const uint64_t total = set.file_total + cnt;
+    if ((rc = call.open([&] { return check_params(p, who); }))) return rc;
+    sm_mapset::ReadSet &set = call.set;
+    const uint32_t cnt = call.cnt;
+    const uint64_t total = call.total;
 
     GroundJob job(s, ground_args(*p));
     const GroundArgs &g = job.g;
@@ -228,43 +209,39 @@ int sm_ground_maps(sm_ctx *s, const sm_map_source *src, const sm_ground_params *
     }
 
     Ground &gr = s->ground;
-    if ((rc = job.open())) return rc;
-    const float4 *d_model = nullptr;
-    if (cnt) {
-        if ((rc = ensure_export(s, (size_t)cnt * 48))) return rc;
-        export_aos(s, (float *)s->d_export.get(), 0u, cnt);
-        d_model = (const float4 *)s->d_export.get();
-    }
-    if (!set.jobs.empty() && (rc = maps_ensure_staging(s))) return rc;
-    float h2d_ms = 0.0f;
+    const Event *ev = job.ev;
+    if ((rc = job.open()) || (rc = call.model())) return rc;
+    const float4 *d_model = call.d_model;
+    if (!set.jobs.empty() && (rc = call.staging())) return rc;
+    float &h2d_ms = call.copy_ms;
 
     // ---- reading 1: the lowest ground-like record of every cell; then the reference heights
-    if ((rc = maps_feed(s, who, set, src->paths, cnt, d_model, {&st.read_ms, &h2d_ms, &st.ground_ms}, gr.ev[EV_MIN0],
+    if ((rc = maps_feed(s, who, set, src->paths, cnt, d_model, {&st.read_ms, &h2d_ms, &st.ground_ms}, ev[EV_MIN0],
                         [&](const float4 *d_rec, uint32_t n, uint32_t) { job.lowest(d_rec, n); })))
         return rc;
-    if ((rc = mark(s, gr.ev[EV_MIN1])) || (rc = mark(s, gr.ev[EV_FILL0]))) return rc;
+    if ((rc = mark(s, ev[EV_MIN1])) || (rc = mark(s, ev[EV_FILL0]))) return rc;
     job.fill();
-    if ((rc = mark(s, gr.ev[EV_FILL1]))) return rc;
+    if ((rc = mark(s, ev[EV_FILL1]))) return rc;
     HIPCK(hipGetLastError());
-    if ((rc = add_marked(&gr.ev[EV_CLR0], &st.ground_ms)) || (rc = add_marked(&gr.ev[EV_MIN0], &st.ground_ms)) ||
-        (rc = add_marked(&gr.ev[EV_FILL0], &st.fill_ms)))
+    if ((rc = add_marked(&ev[EV_CLR0], &st.ground_ms)) || (rc = add_marked(&ev[EV_MIN0], &st.ground_ms)) ||
+        (rc = add_marked(&ev[EV_FILL0], &st.fill_ms)))
         return rc;
 
     // ---- reading 2: the ground's sums and the obstacles
-    if ((rc = maps_feed(s, who, set, src->paths, cnt, d_model, {&st.read_ms, &h2d_ms, &st.accumulate_ms}, gr.ev[EV_ACC0],
+    if ((rc = maps_feed(s, who, set, src->paths, cnt, d_model, {&st.read_ms, &h2d_ms, &st.accumulate_ms}, ev[EV_ACC0],
                         [&](const float4 *d_rec, uint32_t n, uint32_t gid0) { job.accumulate(d_rec, n, gid0); })))
         return rc;
-    if ((rc = mark(s, gr.ev[EV_ACC1])) || (rc = mark(s, gr.ev[EV_STATE0]))) return rc;
+    if ((rc = mark(s, ev[EV_ACC1])) || (rc = mark(s, ev[EV_STATE0]))) return rc;
 
     // ---- planes, states, clearance
     job.finish();
-    if ((rc = mark(s, gr.ev[EV_STATE1])) || (rc = mark(s, gr.ev[EV_CLEAR0]))) return rc;
+    if ((rc = mark(s, ev[EV_STATE1])) || (rc = mark(s, ev[EV_CLEAR0]))) return rc;
     if (clear2) job.clearance();
-    if ((rc = mark(s, gr.ev[EV_CLEAR1])) || (rc = job.read_tally())) return rc;
-    if ((rc = add_marked(&gr.ev[EV_ACC0], &st.accumulate_ms)) || (rc = add_marked(&gr.ev[EV_STATE0], &st.state_ms)) ||
-        (rc = add_marked(&gr.ev[EV_CLEAR0], &st.clear_ms)))
+    if ((rc = mark(s, ev[EV_CLEAR1])) || (rc = gr.scratch.read(s))) return rc;
+    if ((rc = add_marked(&ev[EV_ACC0], &st.accumulate_ms)) || (rc = add_marked(&ev[EV_STATE0], &st.state_ms)) ||
+        (rc = add_marked(&ev[EV_CLEAR0], &st.clear_ms)))
         return rc;
-    const uint32_t *h = gr.h_tally.get();
+    const uint32_t *h = gr.scratch.h();
     uint64_t seen = 0;
     for (int k = 0; k < GROUND_KINDS; ++k) { got.counts[k] = h[GROUND_COUNTS + k]; seen += got.counts[k]; }
     got.counts[GROUND_K_OUTSIDE] += skipped_records;
@@ -285,18 +262,12 @@ int sm_ground_maps(sm_ctx *s, const sm_map_source *src, const sm_ground_params *
     st.copy_ms = (float)(now_ms() - t_copy);
     *info = got;
     st.launches = job.launches;
-    st.total_ms = (float)(now_ms() - t_begin);
+    st.total_ms = call.elapsed_ms();
     gr.stats = st;                                       // (a call that fails leaves the last one's)
     gr.stats_valid = true;
     return SM_OK;
 }
 
-int sm_ground_stats(sm_ctx *s, sm_ground_stats_t *out)
-{
-    if (!s || !out) { g_err = "sm_ground_stats: null argument"; return SM_E_ARG; }
-    if (!s->ground.stats_valid) { g_err = "sm_ground_stats: no sm_ground_maps call yet"; return SM_E_ARG; }
-    *out = s->ground.stats;
-    return SM_OK;
-}
+SM_STATS_GETTER(sm_ground_stats, sm_ground_stats_t, ground, "sm_ground_maps")
 
 }  // extern "C"

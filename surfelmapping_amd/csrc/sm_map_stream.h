@@ -1,12 +1,13 @@
-// sm_map_stream.h -- private to sm_render_maps.hip, sm_lidar.hip, sm_recall.hip, sm_warp.hip, sm_simplify.hip, sm_register.hip, sm_compare.hip, sm_tile.hip, sm_segment.hip, sm_mesh.hip, sm_ground.hip and sm_scene.hip (which takes the planes' layout and the file format from here, no stream): the double-buffered stream of
-// map-file chunks through the context's MapStaging, one object per call; behind it what the two readers of whole sets (the
-// streamed renderers, the lidar) do alike: the opening (maps_open) and the batch of views (maps_batch), the opening of two sets
-// (check_sets, open_sets) and the pass over a set that only launches (maps_feed).  Chunk c of a pass goes
-// through buffer q = c & 1: read into h_rec[q] (timed into read_ms), copied on `copy` into d_rec[q], and the context's stream
-// waits for the copy; the caller then launches its kernels on d_rec[q] and says done(q).  fold(q) waits for them and adds the
-// buffer's event times to the caller's tally.  The host reads chunk c while chunk c - 1 is on the device: next() waits only for
-// chunk c - 2, the last user of its buffer, and that one wait frees both sides (the copy out of h_rec[q] and the kernels that
-// read d_rec[q] precede the event).
+// sm_map_stream.h -- private to the sources that read map files ($(MAPS) in csrc/Makefile names them; sm_scene.hip takes the planes'
+// layout and the file format from here, no stream): the double-buffered stream of map-file chunks through the context's
+// MapStaging, one object per call; behind it what the readers of whole sets do alike: the opening (maps_open; its tail
+// maps_counts also ends the openings with rules of their own -- sm_set_call.h's, the calls on two sets) and the batch of views
+// (maps_batch), the opening of two sets (check_sets, open_sets) and the pass over a set that only launches (maps_feed).  Chunk c
+// of a pass goes through buffer q = c & 1: read into h_rec[q] (timed into read_ms), copied on `copy` into d_rec[q], and the
+// context's stream waits for the copy; the caller then launches its kernels on d_rec[q] and says done(q).  fold(q) waits for them
+// and adds the buffer's event times to the caller's tally.  The host reads chunk c while chunk c - 1 is on the device: next()
+// waits only for chunk c - 2, the last user of its buffer, and that one wait frees both sides (the copy out of h_rec[q] and the
+// kernels that read d_rec[q] precede the event).
 #pragma once
 
 #include "sm_ctx.h"
@@ -15,6 +16,13 @@
 #include <cstdlib>
 
 namespace sm_impl __attribute__((visibility("hidden"))) {
+
+// a switch of the environment, read per call: on iff the variable begins with 1
+inline bool env_is_one(const char *name)
+{
+    const char *e = std::getenv(name);
+    return e && e[0] == '1';
+}
 
 inline MapsSoA planes(const MapStaging &st) { return {st.d_pos_conf, st.d_norm_rad, st.d_color, st.d_time}; }
 
@@ -96,21 +104,34 @@ private:
     bool in_flight_[2] = {false, false};   // the buffer's events have been recorded and not yet folded
 };
 
+// The tail of every opening, once the headers of its n sets (1 or 2) are read: the device, the model compact and its count known
+// (waits for frames in flight); per set the live surfels that take part (cnt) and the limit of its ids.
+inline int maps_counts(sm_ctx *s, const char *fn, int n, const sm_map_source *const *src, const sm_mapset::ReadSet *const *set, uint32_t *cnt)
+{
+    int rc;
+    HIPCK(hipSetDevice(s->cfg.device));
+    if ((rc = ensure_compact(s)) || (rc = pull_state(s))) return rc;
+    for (int i = 0; i < n; ++i) cnt[i] = src[i]->include_model ? s->h_state->count : 0u;
+    for (int i = 0; i < n; ++i) {
+        const uint64_t total = set[i]->file_total + cnt[i];
+        if (total <= 0x7FFFFFFFull) continue;
+        g_err = std::string(fn) + (n == 1 ? ": the map set holds " + std::to_string(total) + " surfels, ids end at 2^31 - 1" : ": a set of more than 2^31 - 1 records");
+        return SM_E_CAPACITY;
+    }
+    return SM_OK;
+}
+
 // What sm_render_*_maps and sm_lidar_sweep* do between their own argument checks and their own scratch: `whole` (the entry
 // point's own refusal of a context that holds a part of the map), the half-done cull, the source; every file's header against
-// its length before the device is touched; then the model compact and its count known.  cnt: the live surfels that take part.
+// its length before the device is touched; then the tail above.  cnt: the live surfels that take part.
 template <typename Whole>
 int maps_open(sm_ctx *s, const sm_map_source *src, const char *fn, Whole whole, sm_mapset::ReadSet &set, uint32_t &cnt)
 {
     int rc;
     if ((rc = whole(s, fn)) || (rc = check_not_mid_cull(s, fn)) || (rc = check_map_source(src, fn))) return rc;
     if (!sm_mapset::open_read_set(src->paths, src->n_paths, MapStaging::CHUNK, fn, set, g_err)) return SM_E_ARG;
-    HIPCK(hipSetDevice(s->cfg.device));
-    if ((rc = ensure_compact(s)) || (rc = pull_state(s))) return rc;   // (waits for frames in flight; count is the live surfels)
-    cnt = src->include_model ? s->h_state->count : 0u;
-    const uint64_t total = set.file_total + cnt;
-    if (total > 0x7FFFFFFFull) { g_err = std::string(fn) + ": the map set holds " + std::to_string(total) + " surfels, ids end at 2^31 - 1"; return SM_E_CAPACITY; }
-    return SM_OK;
+    const sm_mapset::ReadSet *sets[1] = {&set};
+    return maps_counts(s, fn, 1, &src, sets, &cnt);
 }
 
 // What a call on two sets asks of them, without the device (registration, change detection), in two steps so that a caller's own
@@ -158,8 +179,8 @@ int maps_feed(sm_ctx *s, const char *who, const sm_mapset::ReadSet &set, const c
 // most 2^30 keys per batch) hold at `keys` 8-byte keys per view.  *cull: 0 with <no_cull_var>=1, the splat then tests every block.
 inline uint32_t maps_batch(uint32_t views, size_t keys, const char *key_mb_var, const char *no_cull_var, int *cull)
 {
-    const char *e = std::getenv(no_cull_var), *k = std::getenv(key_mb_var);
-    *cull = (e && e[0] == '1') ? 0 : 1;
+    const char *k = std::getenv(key_mb_var);
+    *cull = env_is_one(no_cull_var) ? 0 : 1;
     const size_t key_mb = k ? (size_t)std::min(8192L, std::max(1L, std::atol(k))) : 1024;
     return (uint32_t)std::min<uint64_t>(std::min<uint32_t>(views, 4096u), std::max<uint64_t>(1, (key_mb << 20) / (keys * 8)));
 }

@@ -2,8 +2,8 @@
 // table of cells; the cells' lattice points claimed in a second table sized from the cell count; the field summed per lattice
 // point, the cubes classified, the owners of a vertex or a face sorted by key and ranked; vertices and faces written at their ranks
 // and brought back in pieces while the host fills the caller's buffers and the PLY file.  Kernels: sm_k_mesh.h; the grid, the
-// tables' sizes, the tally's verdict, the pair sort and the ranks: sm_voxel.h.
-#include "sm_voxel.h"
+// tables' sizes, the tally's verdict, the pair sort and the ranks: sm_voxel.h; the call's frame and the drain: sm_set_call.h.
+#include "sm_set_call.h"
 #include "sm_k_mesh.h"
 
 using namespace sm;
@@ -12,9 +12,8 @@ using sm_mapfile::now_ms;
 namespace {
 
 constexpr uint32_t CHUNK = MapStaging::CHUNK;
-constexpr size_t PIECE_BYTES = (size_t)CHUNK * 48;       // a staging buffer
 enum { EV_CLR0 = 0, EV_CLR1, EV_INS0, EV_INS1, EV_FIELD0, EV_FIELD1, EV_SORT0, EV_SORT1, EV_EMIT0, EV_EMIT1, EV_PIECE, N_EV = EV_PIECE + 2 };
-static_assert(N_EV == Mesh::N_EV, "the context holds the events of a call");
+static_assert(N_EV == decltype(Mesh::scratch)::N_EV, "the context holds the events of a call");
 static_assert(sizeof(MeshVertex) == sizeof(sm_mesh_vertex), "a vertex leaves the device as it is");
 static_assert(MESH_USED == SM_MESH_USED && MESH_SKIPPED == SM_MESH_SKIPPED && MESH_LOOSE == SM_MESH_LOOSE && MESH_OUTSIDE == SM_MESH_OUTSIDE,
               "the kinds are the entries of info->counts");
@@ -28,18 +27,6 @@ int check_params(const sm_mesh_params *p, const char *who)
     if (p->max_cells == 0) return bad("max_cells is 0");
     for (int k = 0; k < 3; ++k)
         if (!std::isfinite(p->origin[k])) return bad("non-finite origin");
-    return SM_OK;
-}
-
-int mesh_alloc(sm_ctx *s)
-{
-    Mesh &me = s->mesh;
-    if (me.d_tally) return SM_OK;
-    Dev<uint32_t> tally;
-    if (int rc = dalloc(tally, MESH_TALLY_WORDS)) return rc;
-    HIPCK(hipHostMalloc((void **)me.h_tally.put(), MESH_TALLY_WORDS * 4, hipHostMallocDefault));
-    for (Event &e : me.ev) HIPCK(hipEventCreate(e.put()));
-    me.d_tally = std::move(tally);                       // last: it marks the set complete
     return SM_OK;
 }
 
@@ -104,6 +91,7 @@ struct PlyFile {
 struct MeshJob {
     sm_ctx *s;
     Mesh &me;
+    const Event *ev;
     const char *who;
     const sm_mesh_params &p;
     SimplifyArgs a{};
@@ -119,17 +107,17 @@ struct MeshJob {
     uint32_t launches = 0;
     sm_mesh_stats_t stats{};           // this call's; the context's once the call has succeeded
 
-    MeshJob(sm_ctx *s_, const char *who_, const sm_mesh_params &p_) : s(s_), me(s_->mesh), who(who_), p(p_), out(s_, who_) {}
+    MeshJob(sm_ctx *s_, const char *who_, const sm_mesh_params &p_) : s(s_), me(s_->mesh), ev(s_->mesh.scratch.ev), who(who_), p(p_), out(s_, who_) {}
 
-    uint32_t *tally() const { return me.d_tally.get(); }
-    const uint32_t *h() const { return me.h_tally.get(); }
-    int read_tally() { return voxel_read_tally(s, tally(), me.h_tally.get(), MESH_TALLY_WORDS); }
+    uint32_t *tally() const { return me.scratch.d_tally.get(); }
+    const uint32_t *h() const { return me.scratch.h(); }
+    int read_tally() { return me.scratch.read(s); }
 
     int open(uint64_t records)
     {
         int rc;
         uint64_t slots;
-        if ((rc = mesh_alloc(s)) || (rc = voxel_slots(records, p.max_cells, who, "the cell table", slots)) || (rc = out.ensure(0, 0))) return rc;
+        if ((rc = me.scratch.ensure(MESH_TALLY_WORDS)) || (rc = voxel_slots(records, p.max_cells, who, "the cell table", slots)) || (rc = out.ensure(0, 0))) return rc;
         a = voxel_args(p.voxel_mm, 0, p.origin, 0, p.max_cells);
         for (int i = 0; i < 8; ++i) ma.class_mask[i] = p.class_mask[i];
         ma.reach = p.reach;
@@ -144,12 +132,12 @@ struct MeshJob {
         T.n = (uint32_t *)(T.SC + 3 * S);
         T.mask = (uint32_t)(S - 1);
         T.tally = tally();
-        if ((rc = mark(s, me.ev[EV_CLR0]))) return rc;
+        if ((rc = mark(s, ev[EV_CLR0]))) return rc;
         HIPCK(hipMemsetAsync(b, 0xFF, S * MESH_CELL_ONES, s->stream));
         HIPCK(hipMemsetAsync(b + S * MESH_CELL_ONES, 0, S * MESH_CELL_ZERO, s->stream));
-        HIPCK(hipMemsetAsync(tally(), 0, MESH_TALLY_WORDS * 4, s->stream));
+        if ((rc = me.scratch.clear(s->stream))) return rc;
         HIPCK(hipMemsetAsync(tally() + MESH_AND, 0xFF, 8, s->stream));
-        return mark(s, me.ev[EV_CLR1]);
+        return mark(s, ev[EV_CLR1]);
     }
     // the reading of n <= CHUNK records
     void insert(const float4 *d_rec, uint32_t n, uint32_t gid0)
@@ -241,31 +229,6 @@ struct MeshJob {
         HIPCK(hipGetLastError());
         return SM_OK;
     }
-    // `rows` rows of row_bytes at d_src back through the staging's host buffers, which no reading is using, a piece at a time:
-    // piece p is copied while the host takes piece p - 1 (take(host rows, first row, rows))
-    template <typename Take>
-    int drain(const void *d_src, size_t rows, size_t row_bytes, Take take)
-    {
-        MapStaging &st = s->staging;
-        const size_t per = PIECE_BYTES / row_bytes, pieces = (rows + per - 1) / per;
-        const auto finish = [&](size_t pc) -> int {
-            const int q = (int)(pc & 1u);
-            const double t0 = now_ms();                  // (the wait for the piece's copy counts as writing)
-            HIPCK(hipEventSynchronize(me.ev[EV_PIECE + q]));
-            const int rc = take((const void *)st.h_rec[q].get(), pc * per, std::min(per, rows - pc * per));
-            stats.write_ms += (float)(now_ms() - t0);
-            return rc;
-        };
-        for (size_t pc = 0; pc < pieces; ++pc) {
-            const int q = (int)(pc & 1u);
-            const size_t m = std::min(per, rows - pc * per);
-            HIPCK(hipMemcpyAsync(st.h_rec[q].get(), (const uint8_t *)d_src + pc * per * row_bytes, m * row_bytes, hipMemcpyDeviceToHost, s->stream));
-            HIPCK(hipEventRecord(me.ev[EV_PIECE + q], s->stream));
-            if (pc)
-                if (int rc = finish(pc - 1)) return rc;
-        }
-        return pieces ? finish(pieces - 1) : SM_OK;
-    }
 };
 
 }  // namespace
@@ -288,18 +251,15 @@ int sm_mesh_maps(sm_ctx *s, const sm_map_source *src, const sm_mesh_params *p, s
                  const char *ply_path, sm_mesh_info *info)
 {
     const char *who = "sm_mesh_maps";
-    const double t_begin = now_ms();
+    SetCall call(s, src, who);
     if (!s || !src || !p || !info) { g_err = std::string(who) + ": null argument"; return SM_E_ARG; }
     if (!vertices && vcap) { g_err = std::string(who) + ": no vertices to hold vcap = " + std::to_string(vcap) + " rows"; return SM_E_ARG; }
     if (!faces && fcap) { g_err = std::string(who) + ": no faces to hold fcap = " + std::to_string(fcap) + " rows"; return SM_E_ARG; }
     int rc;
-    if ((rc = check_whole_map(s, who)) || (rc = check_params(p, who)) || (rc = check_not_mid_cull(s, who)) || (rc = check_map_source(src, who))) return rc;
-    for (uint32_t i = 0; ply_path && i < src->n_paths; ++i)                  // the output needs a path of its own
-        if (strcmp(src->paths[i], ply_path) == 0) { g_err = sm_mapfile::said(who, ply_path, " is a file of the set: the output needs a path of its own"); return SM_E_ARG; }
-    sm_mapset::ReadSet set;
-    uint32_t cnt;
-    if ((rc = maps_open(s, src, who, check_whole_map, set, cnt))) return rc;
-    const uint64_t total = set.file_total + cnt;
+    if ((rc = call.open([&] { return check_params(p, who); }, {ply_path}))) return rc;
+    const sm_mapset::ReadSet &set = call.set;
+    const uint32_t cnt = call.cnt;
+    const uint64_t total = call.total;
 
     Mesh &me = s->mesh;
     sm_mesh_info got{};
@@ -307,22 +267,17 @@ int sm_mesh_maps(sm_ctx *s, const sm_map_source *src, const sm_mesh_params *p, s
 
     MeshJob job(s, who, *p);
     sm_mesh_stats_t &st = job.stats;
-    if ((rc = job.open(total))) return rc;
-    const float4 *d_model = nullptr;
-    if (cnt) {
-        if ((rc = ensure_export(s, (size_t)cnt * 48))) return rc;
-        export_aos(s, (float *)s->d_export.get(), 0u, cnt);
-        d_model = (const float4 *)s->d_export.get();
-    }
-    if ((rc = maps_ensure_staging(s))) return rc;        // (the mesh leaves through the staging's host buffers)
-    float copy_ms = 0.0f;
+    const Event *ev = job.ev;
+    if ((rc = job.open(total)) || (rc = call.model())) return rc;
+    const float4 *d_model = call.d_model;
+    if ((rc = call.staging())) return rc;                // (the mesh leaves through the staging's host buffers)
 
     // ---- the reading: the cells
-    if ((rc = maps_feed(s, who, set, src->paths, cnt, d_model, {&st.read_ms, &copy_ms, &st.table_ms}, me.ev[EV_INS0],
+    if ((rc = maps_feed(s, who, set, src->paths, cnt, d_model, {&st.read_ms, &call.copy_ms, &st.table_ms}, ev[EV_INS0],
                         [&](const float4 *d_rec, uint32_t n, uint32_t gid0) { job.insert(d_rec, n, gid0); })))
         return rc;
-    if ((rc = mark(s, me.ev[EV_INS1])) || (rc = job.read_tally())) return rc;
-    if ((rc = add_marked(&me.ev[EV_CLR0], &st.table_ms)) || (rc = add_marked(&me.ev[EV_INS0], &st.table_ms))) return rc;
+    if ((rc = mark(s, ev[EV_INS1])) || (rc = job.read_tally())) return rc;
+    if ((rc = add_marked(&ev[EV_CLR0], &st.table_ms)) || (rc = add_marked(&ev[EV_INS0], &st.table_ms))) return rc;
     const uint32_t *h = job.h();
     // (nothing has been written: rows, file and info follow)
     if ((rc = voxel_check_tally(h + MESH_CELL, p->max_cells, who, "cells"))) return rc;
@@ -332,18 +287,18 @@ int sm_mesh_maps(sm_ctx *s, const sm_map_source *src, const sm_mesh_params *p, s
     // ---- lattice points, field, cubes, owners; then the sort and the ranks
     uint32_t owners = 0;
     if (table_cells) {
-        if ((rc = mark(s, me.ev[EV_FIELD0])) || (rc = job.claim(table_cells))) return rc;
+        if ((rc = mark(s, ev[EV_FIELD0])) || (rc = job.claim(table_cells))) return rc;
         got.cells = h[MESH_EXIST];
         got.lattice_points = h[MESH_LAT + SIMP_CELLS];
         if (got.lattice_points) {
             job.field_and_cubes();
-            if ((rc = mark(s, me.ev[EV_FIELD1])) || (rc = mark(s, me.ev[EV_SORT0])) || (rc = job.owners(got.lattice_points))) return rc;
-            if ((rc = add_marked(&me.ev[EV_FIELD0], &st.field_ms))) return rc;
+            if ((rc = mark(s, ev[EV_FIELD1])) || (rc = mark(s, ev[EV_SORT0])) || (rc = job.owners(got.lattice_points))) return rc;
+            if ((rc = add_marked(&ev[EV_FIELD0], &st.field_ms))) return rc;
             got.cubes = h[MESH_CUBES];
             owners = h[MESH_OWNERS];
             if (owners > got.lattice_points) { g_err = std::string(who) + ": internal: more owners than lattice points"; return SM_E_HIP; }
             if (owners && (rc = job.rank(owners))) return rc;
-            if ((rc = mark(s, me.ev[EV_SORT1])) || (rc = add_marked(&me.ev[EV_SORT0], &st.sort_ms))) return rc;
+            if ((rc = mark(s, ev[EV_SORT1])) || (rc = add_marked(&ev[EV_SORT0], &st.sort_ms))) return rc;
         }
     }
     unsigned long long totals[2];
@@ -358,7 +313,7 @@ int sm_mesh_maps(sm_ctx *s, const sm_map_source *src, const sm_mesh_params *p, s
 
     // ---- the emit; the rows come back while the host fills the buffers and the file
     if (got.vertices || got.faces) {
-        if ((rc = mark(s, me.ev[EV_EMIT0])) || (rc = job.emit(got.vertices, got.faces)) || (rc = mark(s, me.ev[EV_EMIT1]))) return rc;
+        if ((rc = mark(s, ev[EV_EMIT0])) || (rc = job.emit(got.vertices, got.faces)) || (rc = mark(s, ev[EV_EMIT1]))) return rc;
     }
     PlyFile ply(who);
     if (ply_path) {                                      // (the file's opening and its close count as writing)
@@ -368,21 +323,23 @@ int sm_mesh_maps(sm_ctx *s, const sm_map_source *src, const sm_mesh_params *p, s
         if (rc) return rc;
     }
     if (got.vertices && (vcap || ply_path)) {
-        rc = job.drain(job.d_vert.get(), got.vertices, sizeof(MeshVertex), [&](const void *rows, size_t first, size_t m) -> int {
-            if (first < vcap) memcpy(vertices + first, rows, std::min<size_t>(m, vcap - first) * sizeof(sm_mesh_vertex));
-            return ply_path ? ply.vertices((const sm_mesh_vertex *)rows, m) : SM_OK;
-        });
+        rc = drain(s, job.d_vert.get(), got.vertices, sizeof(MeshVertex), &ev[EV_PIECE], &st.write_ms, true,
+                   [&](int, const void *rows, size_t first, size_t m) -> int {
+                       if (first < vcap) memcpy(vertices + first, rows, std::min<size_t>(m, vcap - first) * sizeof(sm_mesh_vertex));
+                       return ply_path ? ply.vertices((const sm_mesh_vertex *)rows, m) : SM_OK;
+                   });
         if (rc) return rc;
     }
     if (got.faces && (fcap || ply_path)) {
-        rc = job.drain(job.d_faces.get(), got.faces, 12, [&](const void *rows, size_t first, size_t m) -> int {
-            if (first < fcap) memcpy(faces + first * 3, rows, std::min<size_t>(m, fcap - first) * 12);
-            return ply_path ? ply.faces((const uint32_t *)rows, m) : SM_OK;
-        });
+        rc = drain(s, job.d_faces.get(), got.faces, 12, &ev[EV_PIECE], &st.write_ms, true,
+                   [&](int, const void *rows, size_t first, size_t m) -> int {
+                       if (first < fcap) memcpy(faces + first * 3, rows, std::min<size_t>(m, fcap - first) * 12);
+                       return ply_path ? ply.faces((const uint32_t *)rows, m) : SM_OK;
+                   });
         if (rc) return rc;
     }
     HIPCK(hipStreamSynchronize(s->stream));
-    if ((got.vertices || got.faces) && (rc = add_marked(&me.ev[EV_EMIT0], &st.emit_ms))) return rc;
+    if ((got.vertices || got.faces) && (rc = add_marked(&ev[EV_EMIT0], &st.emit_ms))) return rc;
     if (ply_path) {
         const double t0 = now_ms();
         rc = ply.commit();
@@ -391,18 +348,12 @@ int sm_mesh_maps(sm_ctx *s, const sm_map_source *src, const sm_mesh_params *p, s
     }
     *info = got;
     st.launches = job.launches;
-    st.total_ms = (float)(now_ms() - t_begin);
+    st.total_ms = call.elapsed_ms();
     me.stats = st;                                       // (a call that fails leaves the last one's)
     me.stats_valid = true;
     return SM_OK;
 }
 
-int sm_mesh_stats(sm_ctx *s, sm_mesh_stats_t *out)
-{
-    if (!s || !out) { g_err = "sm_mesh_stats: null argument"; return SM_E_ARG; }
-    if (!s->mesh.stats_valid) { g_err = "sm_mesh_stats: no sm_mesh_maps call yet"; return SM_E_ARG; }
-    *out = s->mesh.stats;
-    return SM_OK;
-}
+SM_STATS_GETTER(sm_mesh_stats, sm_mesh_stats_t, mesh, "sm_mesh_maps")
 
 }  // extern "C"

@@ -1,7 +1,8 @@
 // sm_register.hip -- registration of one map set against another (sm_register_maps, sm_register_debug; DESIGN.md "4q.
 // Registration"): the target set streamed once into one voxel table per level, the source set streamed once into resident
-// samples, then the iterations enqueued whole.  Kernels: sm_k_register.h; the tables themselves: sm_voxel.h.
-#include "sm_voxel.h"
+// samples, then the iterations enqueued whole.  Kernels: sm_k_register.h; the tables themselves: sm_voxel.h; the scratch and the
+// export of a call: sm_set_call.h.
+#include "sm_set_call.h"
 #include "sm_k_register.h"
 #include "sm_pose.h"
 
@@ -11,7 +12,8 @@ using sm_mapfile::now_ms;
 namespace {
 
 constexpr uint32_t REG_MAX_SAMPLES = 1u << 28;
-enum { EV_TGT0 = 0, EV_TGT1, EV_SRC0, EV_SRC1, EV_IT0, EV_IT1, EV_CLR0, EV_CLR1 };   // pairs: add_marked(&ev[first])
+constexpr size_t REG_TALLY_WORDS = REG_MAX_LEVELS * SIMP_TALLY_WORDS + 1;    // per level a table's, then the regular samples
+enum { EV_TGT0 = 0, EV_TGT1, EV_SRC0, EV_SRC1, EV_IT0, EV_IT1, EV_CLR0, EV_CLR1 };   // pairs of the scratch's events: add_marked(&ev[first])
 
 int check_params(const sm_register_params *p, const char *who)
 {
@@ -30,26 +32,11 @@ int check_params(const sm_register_params *p, const char *who)
     return SM_OK;
 }
 
-int reg_alloc(sm_ctx *s)
-{
-    Register &rg = s->reg;
-    if (rg.d_state) return SM_OK;
-    constexpr size_t words = REG_MAX_LEVELS * SIMP_TALLY_WORDS + 1;
-    Dev<uint32_t> tally; Dev<double> part; Dev<RegState> st;
-    int rc;
-    if ((rc = dalloc(tally, words)) || (rc = dalloc(part, (size_t)TRACK_NSYS * TRACK_MAX_PARTS)) || (rc = dalloc(st, 1))) return rc;
-    HIPCK(hipHostMalloc((void **)rg.h_tally.put(), words * 4, hipHostMallocDefault));
-    HIPCK(hipHostMalloc((void **)rg.h_state.put(), sizeof(RegState), hipHostMallocDefault));
-    for (Event &e : rg.ev) HIPCK(hipEventCreate(e.put()));
-    rg.d_tally = std::move(tally); rg.d_part = std::move(part);
-    rg.d_state = std::move(st);                          // last: it marks the set complete
-    return SM_OK;
-}
-
 // One call's device side: the tables of all levels, the samples, the kernel arguments.
 struct RegisterJob {
     sm_ctx *s;
     Register &rg;
+    const Event *ev;
     const char *who;
     const sm_register_params &p;
     LookupTable t[REG_MAX_LEVELS];
@@ -58,8 +45,8 @@ struct RegisterJob {
     uint32_t stride = 1, n_samples = 0;
     uint32_t launches = 0;
 
-    RegisterJob(sm_ctx *s_, const char *who_, const sm_register_params &p_) : s(s_), rg(s_->reg), who(who_), p(p_) {}
-    uint32_t *regular() const { return rg.d_tally.get() + REG_MAX_LEVELS * SIMP_TALLY_WORDS; }
+    RegisterJob(sm_ctx *s_, const char *who_, const sm_register_params &p_) : s(s_), rg(s_->reg), ev(s_->reg.scratch.ev), who(who_), p(p_) {}
+    uint32_t *regular() const { return rg.scratch.d_tally.get() + REG_MAX_LEVELS * SIMP_TALLY_WORDS; }
 
     int open(uint64_t target_records, uint64_t source_records)
     {
@@ -69,15 +56,19 @@ struct RegisterJob {
         if (ns > p.max_samples) { g_err = std::string(who) + ": stride leaves more than max_samples samples"; return SM_E_ARG; }
         n_samples = (uint32_t)ns;
         int rc;
-        if ((rc = reg_alloc(s)) || (rc = dalloc(pos, n_samples)) || (rc = dalloc(nrm, n_samples))) return rc;
+        // (beside the scratch a call keeps the partial sums, the state and its pinned mirror on its context)
+        if ((rc = rg.scratch.ensure(REG_TALLY_WORDS)) || (!rg.d_part && (rc = dalloc(rg.d_part, (size_t)TRACK_NSYS * TRACK_MAX_PARTS))) ||
+            (!rg.d_state && (rc = dalloc(rg.d_state, 1))))
+            return rc;
+        if (!rg.h_state) HIPCK(hipHostMalloc((void **)rg.h_state.put(), sizeof(RegState), hipHostMallocDefault));
+        if ((rc = dalloc(pos, n_samples)) || (rc = dalloc(nrm, n_samples))) return rc;
         uint64_t S;
         if ((rc = voxel_slots(target_records, p.max_cells, who, "a table", S))) return rc;
         for (int l = 0; l < p.levels; ++l) t[l].a = voxel_args(p.voxel_mm, l, p.origin, 1, p.max_cells);
-        if ((rc = lut_open(tables, t, p.levels, S, false, rg.d_tally.get()))) return rc;
+        if ((rc = lut_open(tables, t, p.levels, S, false, rg.scratch.d_tally.get()))) return rc;
         // the tables' initialisation is device time of theirs (table_ms)
-        if ((rc = mark(s, rg.ev[EV_CLR0])) || (rc = lut_clear(s, t, p.levels))) return rc;
-        HIPCK(hipMemsetAsync(rg.d_tally, 0, (REG_MAX_LEVELS * SIMP_TALLY_WORDS + 1) * 4, s->stream));
-        return mark(s, rg.ev[EV_CLR1]);
+        if ((rc = mark(s, ev[EV_CLR0])) || (rc = lut_clear(s, t, p.levels)) || (rc = rg.scratch.clear(s->stream))) return rc;
+        return mark(s, ev[EV_CLR1]);
     }
     // n <= CHUNK records of the target into every level's table, the class taken as 0
     void insert(const float4 *d_rec, uint32_t n)
@@ -136,11 +127,12 @@ int register_run(sm_ctx *s, const sm_map_source *source, const sm_map_source *ta
     if (debug && level >= p->levels) { g_err = std::string(who) + ": level outside 0 .. levels - 1"; return SM_E_ARG; }
     sm_mapset::ReadSet sset, tset;
     if ((rc = check_sets(source, target, who)) || (rc = open_sets(source, target, who, sset, tset))) return rc;
-    HIPCK(hipSetDevice(s->cfg.device));
-    if ((rc = ensure_compact(s)) || (rc = pull_state(s))) return rc;      // (waits for frames in flight; count is the live surfels)
-    const uint32_t model = s->h_state->count, scnt = source->include_model ? model : 0u, tcnt = target->include_model ? model : 0u;
+    const sm_map_source *const srcs[2] = {source, target};
+    const sm_mapset::ReadSet *const sets[2] = {&sset, &tset};
+    uint32_t live[2];
+    if ((rc = maps_counts(s, who, 2, srcs, sets, live))) return rc;
+    const uint32_t scnt = live[0], tcnt = live[1];
     const uint64_t stotal = sset.file_total + scnt, ttotal = tset.file_total + tcnt;
-    if (stotal > 0x7FFFFFFFull || ttotal > 0x7FFFFFFFull) { g_err = std::string(who) + ": a set of more than 2^31 - 1 records"; return SM_E_CAPACITY; }
 
     Register &rg = s->reg;
     rg.stats = sm_register_stats_t{};
@@ -157,30 +149,27 @@ int register_run(sm_ctx *s, const sm_map_source *source, const sm_map_source *ta
     if ((rc = job.open(ttotal, stotal))) return rc;
     out.stride = job.stride;
     if (n_samples_out) *n_samples_out = job.n_samples;
-    const float4 *d_model = nullptr;
-    if (scnt || tcnt) {
-        if ((rc = ensure_export(s, (size_t)model * 48))) return rc;
-        export_aos(s, (float *)s->d_export.get(), 0u, model);
-        d_model = (const float4 *)s->d_export.get();
-    }
+    const Event *ev = job.ev;
+    const float4 *d_model;
+    if ((rc = maps_export(s, std::max(scnt, tcnt), d_model))) return rc;
     if (sset.jobs.size() + tset.jobs.size())
         if ((rc = maps_ensure_staging(s))) return rc;
     float copy_ms = 0.0f;
     const MapStream::Tally times = {&rg.stats.read_ms, &copy_ms, &rg.stats.table_ms};
     // ---- the target: every chunk into every level's table, then the representatives
-    if ((rc = maps_feed(s, who, tset, target->paths, tcnt, d_model, times, rg.ev[EV_TGT0],
+    if ((rc = maps_feed(s, who, tset, target->paths, tcnt, d_model, times, ev[EV_TGT0],
                         [&](const float4 *d_rec, uint32_t n, uint32_t) { job.insert(d_rec, n); })))
         return rc;
     job.finish();
-    if ((rc = mark(s, rg.ev[EV_TGT1]))) return rc;
+    if ((rc = mark(s, ev[EV_TGT1]))) return rc;
     // ---- the source: the samples to their places
-    if ((rc = maps_feed(s, who, sset, source->paths, scnt, d_model, times, rg.ev[EV_SRC0],
+    if ((rc = maps_feed(s, who, sset, source->paths, scnt, d_model, times, ev[EV_SRC0],
                         [&](const float4 *d_rec, uint32_t n, uint32_t gid0) { job.gather(d_rec, n, gid0); })))
         return rc;
-    if ((rc = mark(s, rg.ev[EV_SRC1])) || (rc = voxel_read_tally(s, rg.d_tally.get(), rg.h_tally.get(), REG_MAX_LEVELS * SIMP_TALLY_WORDS + 1))) return rc;
+    if ((rc = mark(s, ev[EV_SRC1])) || (rc = rg.scratch.read(s))) return rc;
     for (int pair : {EV_CLR0, EV_TGT0, EV_SRC0})
-        if ((rc = add_marked(&rg.ev[pair], &rg.stats.table_ms))) return rc;
-    const uint32_t *h = rg.h_tally.get();
+        if ((rc = add_marked(&ev[pair], &rg.stats.table_ms))) return rc;
+    const uint32_t *h = rg.scratch.h();
     for (int l = 0; l < p->levels; ++l) {
         if ((rc = voxel_check_tally(h + l * SIMP_TALLY_WORDS, p->max_cells, who, "keys at level " + std::to_string(l)))) return rc;
         out.cells[l] = h[l * SIMP_TALLY_WORDS + SIMP_CELLS];
@@ -198,15 +187,15 @@ int register_run(sm_ctx *s, const sm_map_source *source, const sm_map_source *ta
         if (!debug) sm_pose::orthonormalize_d(hs.T);
         hs.level = debug ? level : p->levels - 1;
         HIPCK(hipMemcpyAsync(rg.d_state.get(), &hs, sizeof hs, hipMemcpyHostToDevice, s->stream));
-        if ((rc = mark(s, rg.ev[EV_IT0]))) return rc;
+        if ((rc = mark(s, ev[EV_IT0]))) return rc;
         if (debug) job.iteration(rp, 1);
         else
             for (int i = 0; i < p->levels * p->max_iters; ++i) job.iteration(rp, 0);
         HIPCK(hipGetLastError());
-        if ((rc = mark(s, rg.ev[EV_IT1]))) return rc;
+        if ((rc = mark(s, ev[EV_IT1]))) return rc;
         HIPCK(hipMemcpyAsync(&hs, rg.d_state.get(), sizeof hs, hipMemcpyDeviceToHost, s->stream));
         HIPCK(hipStreamSynchronize(s->stream));
-        if ((rc = add_marked(&rg.ev[EV_IT0], &rg.stats.iterate_ms))) return rc;
+        if ((rc = add_marked(&ev[EV_IT0], &rg.stats.iterate_ms))) return rc;
     }
     if (debug) {
         for (int e = 0; e < TRACK_NSYS; ++e) sys29[e] = hs.sys[e];
@@ -263,12 +252,6 @@ int sm_register_debug(sm_ctx *s, const sm_map_source *source, const sm_map_sourc
     return register_run(s, source, target, pose16_eval, level, p, nullptr, nullptr, sys29, n_samples, who);
 }
 
-int sm_register_stats(sm_ctx *s, sm_register_stats_t *out)
-{
-    if (!s || !out) { g_err = "sm_register_stats: null argument"; return SM_E_ARG; }
-    if (!s->reg.stats_valid) { g_err = "sm_register_stats: no sm_register_maps / sm_register_debug call yet"; return SM_E_ARG; }
-    *out = s->reg.stats;
-    return SM_OK;
-}
+SM_STATS_GETTER(sm_register_stats, sm_register_stats_t, reg, "sm_register_maps / sm_register_debug")
 
 }  // extern "C"

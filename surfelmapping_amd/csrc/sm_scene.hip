@@ -128,8 +128,7 @@ int sm_impl::scene_check(const sm_scene *scene, uint32_t n_views, const char *fn
         plan.file_of[j] = f;
         plan.ids += plan.files[f].count;
     }
-    const char *e = std::getenv("SM_SCENE_NO_CULL");
-    plan.cull = (e && e[0] == '1') ? 0 : 1;
+    plan.cull = env_is_one("SM_SCENE_NO_CULL") ? 0 : 1;
     return SM_OK;
 }
 

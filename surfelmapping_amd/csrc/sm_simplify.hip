@@ -1,8 +1,8 @@
 // sm_simplify.hip -- voxel-cell simplification (sm_simplify, sm_simplify_maps; DESIGN.md "4p. Simplification"): the records of
 // the live model or of a map set merged per cell of a world grid, in two passes over the records.  A map set's files go through
 // the context's chunk stream twice, the live model through the export scratch.  Kernels: sm_k_simplify.h; the grid, the table's
-// size and the ranked output of pass 2: sm_voxel.h.
-#include "sm_voxel.h"
+// size and the ranked output of pass 2: sm_voxel.h; the frame of the call on a set: sm_set_call.h.
+#include "sm_set_call.h"
 #include "sm_k_simplify.h"
 
 using namespace sm;
@@ -28,6 +28,7 @@ int check_params(const sm_simplify_params *p, const char *who)
 struct SimplifyJob {
     sm_ctx *s;
     Simplify &sp;
+    const Event *ev;
     const char *who;
     SimplifyArgs a{};
     SimplifyTable T{};
@@ -35,17 +36,13 @@ struct SimplifyJob {
     RankedOutput out;
     uint32_t launches = 0;
 
-    SimplifyJob(sm_ctx *s_, const char *who_) : s(s_), sp(s_->simp), who(who_), out(s_, who_) {}
+    SimplifyJob(sm_ctx *s_, const char *who_) : s(s_), sp(s_->simp), ev(s_->simp.scratch.ev), who(who_), out(s_, who_) {}
 
     // the scratch every call shares, the table for `records` records, everything initialised
     int open(uint64_t records, const sm_simplify_params &p)
     {
         int rc;
-        if (!sp.d_code) {
-            if ((rc = dalloc(sp.d_code, CHUNK)) || (rc = dalloc(sp.d_tally, SIMP_TALLY_WORDS))) return rc;
-            HIPCK(hipEventCreate(sp.ev[0].put()));
-            HIPCK(hipEventCreate(sp.ev[1].put()));
-        }
+        if ((rc = sp.scratch.ensure(SIMP_TALLY_WORDS)) || (!sp.d_code && (rc = dalloc(sp.d_code, CHUNK)))) return rc;
         a = voxel_args(p.voxel_mm, 0, p.origin, p.split_normals, p.max_cells);
         uint64_t S;
         if ((rc = voxel_slots(records, p.max_cells, who, "the table", S))) return rc;
@@ -57,11 +54,10 @@ struct SimplifyJob {
         take(T.SW, 1, 8); take(T.SP, 3, 8); take(T.SN, 3, 8); take(T.SC, 3, 8);
         take(T.n, 1, 4); take(T.hi, 3, 4); take(T.rmax, 1, 4); take(T.conf_max, 1, 4); take(T.time_max, 1, 4);
         T.mask = (uint32_t)(S - 1);
-        T.tally = sp.d_tally;
+        T.tally = sp.scratch.d_tally;
         HIPCK(hipMemsetAsync(table.get(), 0xFF, (size_t)S * SIMP_ONES_BYTES, s->stream));
         HIPCK(hipMemsetAsync(zeros, 0, (size_t)S * SIMP_ZERO_BYTES, s->stream));
-        HIPCK(hipMemsetAsync(sp.d_tally, 0, SIMP_TALLY_WORDS * 4, s->stream));
-        return SM_OK;
+        return sp.scratch.clear(s->stream);
     }
     // pass 1 of n <= CHUNK records
     void insert(const float4 *d_rec, uint32_t n, uint32_t gid0)
@@ -76,21 +72,24 @@ struct SimplifyJob {
         const unsigned nblk = (n + 255) / 256;
         hipLaunchKernelGGL(k_simplify_flag, dim3(nblk), dim3(256), 0, s->stream, d_rec, n, gid0, a, T, sp.d_code.get(), out.blk_cnt());
         launches++;
-        out.scan(nblk, sp.d_tally.get(), q, launches);
+        out.scan(nblk, sp.scratch.d_tally.get(), q, launches);
         hipLaunchKernelGGL(k_simplify_emit, dim3(nblk), dim3(256), 0, s->stream, d_rec, n, a, T, (const uint32_t *)sp.d_code.get(), out.blk_base(),
                            q < 0 ? nullptr : out.info(q), out.out(std::max(q, 0)));
         launches++;
         sp.stats.chunks++;
     }
-    // the tally, once the stream is idle; after pass 1 the sticky error word decides
-    int tally(uint32_t t[SIMP_TALLY_WORDS])
+    // the tally at h(), once the stream is idle; after pass 1 the sticky error word decides
+    const uint32_t *h() const { return sp.scratch.h(); }
+    int tally()
     {
-        if (int rc = voxel_read_tally(s, sp.d_tally.get(), t, SIMP_TALLY_WORDS)) return rc;
+        if (int rc = sp.scratch.read(s)) return rc;
+        const uint32_t *t = h();
         if (t[SIMP_ERR] & 4u) { g_err = std::string(who) + ": internal: a key of pass 1 is missing in pass 2"; return SM_E_HIP; }
         return voxel_check_tally(t, a.max_cells, who, "distinct cells");
     }
-    void fold_tally(const uint32_t t[SIMP_TALLY_WORDS])
+    void fold_tally()
     {
+        const uint32_t *t = h();
         sp.stats.cells_merged = t[SIMP_MERGED];
         sp.stats.loose = t[SIMP_N_LOOSE];
         sp.stats.largest_cell = std::max(t[SIMP_LARGEST], t[SIMP_CELLS] ? 1u : 0u);
@@ -132,14 +131,13 @@ int sm_simplify(sm_ctx *s, const sm_simplify_params *p)
     if ((rc = ensure_export(s, (size_t)cnt * 48)) || (rc = job.out.ensure(0, cnt)) || (rc = job.open(cnt, *p))) return rc;
     const float4 *d_in = (const float4 *)s->d_export.get();
     export_aos(s, (float *)s->d_export.get(), 0u, cnt);
-    if ((rc = mark(s, sp.ev[0]))) return rc;
+    if ((rc = mark(s, job.ev[0]))) return rc;
     for (uint32_t first = 0; first < cnt; first += CHUNK) job.insert(d_in + (size_t)first * 3, std::min(CHUNK, cnt - first), first);
-    uint32_t t[SIMP_TALLY_WORDS];
-    if ((rc = job.tally(t))) return rc;                  // (SM_E_CAPACITY: the model has only been read)
+    if ((rc = job.tally())) return rc;                   // (SM_E_CAPACITY: the model has only been read)
     for (uint32_t first = 0; first < cnt; first += CHUNK) job.emit(d_in + (size_t)first * 3, std::min(CHUNK, cnt - first), first, -1);
-    if ((rc = mark(s, sp.ev[1])) || (rc = job.tally(t)) || (rc = add_marked(sp.ev, &sp.stats.device_ms))) return rc;
-    const uint32_t n_out = t[SIMP_RUN];
-    job.fold_tally(t);
+    if ((rc = mark(s, job.ev[1])) || (rc = job.tally()) || (rc = add_marked(job.ev, &sp.stats.device_ms))) return rc;
+    const uint32_t n_out = job.h()[SIMP_RUN];
+    job.fold_tally();
     sp.stats.records_out = n_out;
 
     // the model is the output's rows: what an upload of them leaves
@@ -156,44 +154,34 @@ int sm_simplify(sm_ctx *s, const sm_simplify_params *p)
 int sm_simplify_maps(sm_ctx *s, const sm_map_source *src, const sm_simplify_params *p, const char *out_path)
 {
     const char *who = "sm_simplify_maps";
-    const double t_begin = now_ms();
+    SetCall call(s, src, who);
     if (!s || !src || !out_path) { g_err = std::string(who) + ": null context, source or output path"; return SM_E_ARG; }
     int rc;
-    if ((rc = check_whole_map(s, who)) || (rc = check_params(p, who)) || (rc = check_map_source(src, who))) return rc;
-    for (uint32_t i = 0; i < src->n_paths; ++i)
-        if (strcmp(src->paths[i], out_path) == 0) { g_err = sm_mapfile::said(who, out_path, " is a source of the set: the output needs a path of its own"); return SM_E_ARG; }
-    sm_mapset::ReadSet set;
-    uint32_t cnt;
-    if ((rc = maps_open(s, src, who, check_whole_map, set, cnt))) return rc;
+    if ((rc = call.open([&] { return check_params(p, who); }, {out_path}))) return rc;
+    const sm_mapset::ReadSet &set = call.set;
+    const uint32_t cnt = call.cnt;
+    const uint64_t total = call.total;
     Simplify &sp = s->simp;
     sp.stats = sm_simplify_stats_t{};
     sp.stats_valid = true;
-    const uint64_t total = set.file_total + cnt;
     sp.stats.records_in = total;
 
     SimplifyJob job(s, who);
     RankedOutput &out = job.out;
-    uint32_t t[SIMP_TALLY_WORDS] = {};
     if (total) {
-        if ((rc = maps_ensure_staging(s)) || (rc = job.open(total, *p))) return rc;
-        const float4 *d_model = nullptr;
-        if (cnt) {
-            if ((rc = ensure_export(s, (size_t)cnt * 48))) return rc;
-            export_aos(s, (float *)s->d_export.get(), 0u, cnt);
-            d_model = (const float4 *)s->d_export.get();
-        }
-        float copy_ms = 0.0f;
-        const MapStream::Tally times = {&sp.stats.read_ms, &copy_ms, &sp.stats.device_ms};
+        if ((rc = call.staging()) || (rc = job.open(total, *p)) || (rc = call.model())) return rc;
+        const float4 *d_model = call.d_model;
+        const MapStream::Tally times = {&sp.stats.read_ms, &call.copy_ms, &sp.stats.device_ms};
 
         // ---- pass 1: the files, chunk by chunk, then the live model
-        if ((rc = maps_feed(s, who, set, src->paths, cnt, d_model, times, sp.ev[0],
+        if ((rc = maps_feed(s, who, set, src->paths, cnt, d_model, times, job.ev[0],
                             [&](const float4 *d_rec, uint32_t n, uint32_t gid0) { job.insert(d_rec, n, gid0); })))
             return rc;
-        if ((rc = mark(s, sp.ev[1])) || (rc = job.tally(t)) || (rc = add_marked(sp.ev, &sp.stats.device_ms))) return rc;   // (SM_E_CAPACITY: nothing is written)
+        if ((rc = mark(s, job.ev[1])) || (rc = job.tally()) || (rc = add_marked(job.ev, &sp.stats.device_ms))) return rc;   // (SM_E_CAPACITY: nothing is written)
 
         // ---- pass 2: the representatives of chunk c into the output while chunk c + 1 is on the device
         if ((rc = out.open(out_path, ".simplify.tmp", set, cnt))) return rc;
-        if ((rc = out.run(set, src->paths, cnt, d_model, times, sp.ev,
+        if ((rc = out.run(set, src->paths, cnt, d_model, times, job.ev,
                           [&](const float4 *d_rec, uint32_t n, uint64_t gid0, int q) { job.emit(d_rec, n, (uint32_t)gid0, q); },
                           [&](int q, uint32_t, uint64_t, hipStream_t stream) -> int {
                               uint32_t m;
@@ -202,22 +190,16 @@ int sm_simplify_maps(sm_ctx *s, const sm_map_source *src, const sm_simplify_para
                               return out.write(q, m);
                           })))
             return rc;
-        if ((rc = job.tally(t))) return rc;
-        job.fold_tally(t);
+        if ((rc = job.tally())) return rc;
+        job.fold_tally();
     } else if ((rc = out.open(out_path, ".simplify.tmp", set, cnt))) {
         return rc;
     }
-    if ((rc = out.commit(out_path, t[SIMP_RUN], sp.stats.records_out))) return rc;
-    sp.stats.total_ms = (float)(now_ms() - t_begin);
+    if ((rc = out.commit(out_path, total ? job.h()[SIMP_RUN] : 0u, sp.stats.records_out))) return rc;
+    sp.stats.total_ms = call.elapsed_ms();
     return SM_OK;
 }
 
-int sm_simplify_stats(sm_ctx *s, sm_simplify_stats_t *out)
-{
-    if (!s || !out) { g_err = "sm_simplify_stats: null argument"; return SM_E_ARG; }
-    if (!s->simp.stats_valid) { g_err = "sm_simplify_stats: no sm_simplify / sm_simplify_maps call yet"; return SM_E_ARG; }
-    *out = s->simp.stats;
-    return SM_OK;
-}
+SM_STATS_GETTER(sm_simplify_stats, sm_simplify_stats_t, simp, "sm_simplify / sm_simplify_maps")
 
 }  // extern "C"

@@ -2,20 +2,18 @@
 // Morton curve over a world grid and cut into files at tile boundaries.  One reading of the set counts the records per tile; the
 // host plans the files and the batches; one reading per batch collects the batch's records in id order, a stable radix sort orders
 // their keys, a gather moves the records once and the host cuts the stream into the planned files.  Kernels: sm_k_tile.h; the
-// grid, the table's size, the tally's verdict and the ranks of a reading: sm_voxel.h.
-#include "sm_voxel.h"
+// grid, the table's size, the tally's verdict and the ranks of a reading: sm_voxel.h; the call's frame and the drain: sm_set_call.h.
+#include "sm_set_call.h"
 #include "sm_k_tile.h"
 
 using namespace sm;
-using sm_mapfile::now_ms;
 
 namespace {
 
-constexpr uint32_t CHUNK = MapStaging::CHUNK;
 constexpr uint32_t SORT_RECORDS = 1u << 22, SORT_RECORDS_MAX = 1u << 26;
 constexpr int LOOSE_TALLY = SIMP_TALLY_WORDS;            // the second block of tally words: the loose records' running rank
 enum { EV_MODEL0 = 0, EV_MODEL1, EV_SORT0, EV_SORT1, EV_GATHER0, EV_GATHER1 = EV_GATHER0 + 2, EV_PIECE = EV_GATHER1 + 2, N_EV = EV_PIECE + 2 };
-static_assert(N_EV == Tile::N_EV, "the context holds the events of a call");
+static_assert(N_EV == decltype(Tile::scratch)::N_EV, "the context holds the events of a call");
 
 // records a batch may hold; SM_TILE_SORT_RECORDS (read per call) overrides it
 uint32_t sort_capacity()
@@ -138,6 +136,7 @@ struct TileFiles {
 struct TileJob {
     sm_ctx *s;
     Tile &tl;
+    const Event *ev;
     const char *who;
     SimplifyArgs a{};
     SimplifyTable T{};                 // key and n (the tile's records) only
@@ -150,19 +149,14 @@ struct TileJob {
     RankedOutput out;                  // (for the ranks of a reading; it opens no file)
     uint32_t launches = 0;
 
-    TileJob(sm_ctx *s_, const char *who_) : s(s_), tl(s_->tile), who(who_), out(s_, who_) {}
+    TileJob(sm_ctx *s_, const char *who_) : s(s_), tl(s_->tile), ev(s_->tile.scratch.ev), who(who_), out(s_, who_) {}
 
-    uint32_t *tally() const { return tl.d_tally.get(); }
+    uint32_t *tally() const { return tl.scratch.d_tally.get(); }
 
     int open(uint64_t records, const sm_tile_params &p)
     {
         int rc;
-        if (!tl.d_bits) {
-            if ((rc = dalloc(tl.d_tally, 2 * SIMP_TALLY_WORDS))) return rc;
-            for (int i = 0; i < N_EV; ++i) HIPCK(hipEventCreate(tl.ev[i].put()));
-            if ((rc = dalloc(tl.d_bits, 2))) return rc;  // last: it marks the set complete
-        }
-        if ((rc = out.ensure(0, 0))) return rc;
+        if ((rc = tl.scratch.ensure(2 * SIMP_TALLY_WORDS)) || (!tl.d_bits && (rc = dalloc(tl.d_bits, 2))) || (rc = out.ensure(0, 0))) return rc;
         a = voxel_args(p.cell_mm, 0, p.origin, 0, p.max_tiles);
         shift3 = 3 * p.tile_shift;
         uint64_t S;
@@ -174,8 +168,7 @@ struct TileJob {
         T.tally = tally();
         HIPCK(hipMemsetAsync(T.key, 0xFF, (size_t)S * 8, s->stream));
         HIPCK(hipMemsetAsync(T.n, 0, (size_t)S * 4, s->stream));
-        HIPCK(hipMemsetAsync(tally(), 0, 2 * SIMP_TALLY_WORDS * 4, s->stream));
-        return SM_OK;
+        return tl.scratch.clear(s->stream);
     }
     // pass 1 of n <= CHUNK records
     void count(const float4 *d_rec, uint32_t n)
@@ -251,10 +244,10 @@ struct TileJob {
     // the ranks a batch's reading gave and the bits in which its keys differ, once the stream is idle
     int batch_tally(uint32_t &ranks, uint32_t &loose_ranks, unsigned long long &varying)
     {
-        uint32_t t[2 * SIMP_TALLY_WORDS];
+        const uint32_t *t = tl.scratch.h();
         unsigned long long bits[2];
         HIPCK(hipMemcpyAsync(bits, tl.d_bits, 16, hipMemcpyDeviceToHost, s->stream));
-        if (int rc = voxel_read_tally(s, tally(), t, 2 * SIMP_TALLY_WORDS)) return rc;
+        if (int rc = tl.scratch.read(s)) return rc;
         ranks = t[SIMP_RUN];
         loose_ranks = t[LOOSE_TALLY + SIMP_RUN];
         varying = ranks ? bits[0] ^ bits[1] : 0ull;
@@ -264,50 +257,36 @@ struct TileJob {
     int sort(uint32_t n, unsigned long long varying, int &which)
     {
         int rc;
-        if ((rc = mark(s, tl.ev[EV_SORT0]))) return rc;
+        if ((rc = mark(s, ev[EV_SORT0]))) return rc;
         unsigned long long *const key[2] = {d_key[0].get(), d_key[1].get()};
         uint32_t *const idx[2] = {d_idx[0].get(), d_idx[1].get()};
         if ((rc = pair_sort(s, key, idx, d_hist.get(), n, varying, which, launches, tl.stats.sort_passes))) return rc;
-        if ((rc = mark(s, tl.ev[EV_SORT1])) || (rc = add_marked(&tl.ev[EV_SORT0], &tl.stats.sort_ms))) return rc;
+        if ((rc = mark(s, ev[EV_SORT1])) || (rc = add_marked(&ev[EV_SORT0], &tl.stats.sort_ms))) return rc;
         return SM_OK;
     }
-    // n records into the files, a piece of CHUNK at a time through the staging's buffers, which no reading is using: piece p is
-    // gathered and copied while the host writes piece p - 1.  d_idx: the records are d_batch[d_idx[i]]; null: d_src[i].
-    int drain(const uint32_t *d_idx_sorted, const float4 *d_src, uint32_t n, TileFiles &files)
+    // n records into the files, a piece of CHUNK at a time (sm_set_call.h's drain): piece p is gathered and copied while the host
+    // writes piece p - 1.  d_idx: the records are d_batch[d_idx[i]], gathered into the staging's device buffer; null: d_src[i].
+    int to_files(const uint32_t *d_idx_sorted, const float4 *d_src, uint32_t n, TileFiles &files)
     {
-        MapStaging &st = s->staging;
-        const auto finish = [&](uint32_t p) -> int {
-            const int q = (int)(p & 1u);
-            HIPCK(hipEventSynchronize(tl.ev[EV_PIECE + q]));
+        const auto gather = [&](int q, size_t first, size_t m) -> int {
+            if (!d_idx_sorted) return SM_OK;
+            HIPCK(hipEventRecord(ev[EV_GATHER0 + q], s->stream));
+            hipLaunchKernelGGL(k_tile_gather, dim3(((uint32_t)m * 3u + 255u) / 256u), dim3(256), 0, s->stream, (const float4 *)d_batch.get(), d_idx_sorted,
+                               (uint32_t)first, (uint32_t)m, cap_batch, s->staging.d_rec[q].get());
+            launches++;
+            HIPCK(hipGetLastError());
+            HIPCK(hipEventRecord(ev[EV_GATHER1 + q], s->stream));
+            return SM_OK;
+        };
+        const auto put = [&](int q, const void *rows, size_t, size_t m) -> int {
             if (d_idx_sorted) {
                 float ms = 0.0f;
-                HIPCK(hipEventElapsedTime(&ms, tl.ev[EV_GATHER0 + q], tl.ev[EV_GATHER1 + q]));
+                HIPCK(hipEventElapsedTime(&ms, ev[EV_GATHER0 + q], ev[EV_GATHER1 + q]));
                 tl.stats.device_ms += ms;
             }
-            const double t0 = now_ms();
-            const int rc = files.put((const float *)st.h_rec[q].get(), std::min(CHUNK, n - p * CHUNK));
-            tl.stats.write_ms += (float)(now_ms() - t0);
-            return rc;
+            return files.put((const float *)rows, (uint32_t)m);
         };
-        const uint32_t pieces = (n + CHUNK - 1) / CHUNK;
-        for (uint32_t p = 0; p < pieces; ++p) {
-            const int q = (int)(p & 1u);
-            const uint32_t first = p * CHUNK, m = std::min(CHUNK, n - first);
-            const float4 *from = d_src ? d_src + (size_t)first * 3 : st.d_rec[q].get();
-            if (d_idx_sorted) {
-                HIPCK(hipEventRecord(tl.ev[EV_GATHER0 + q], s->stream));
-                hipLaunchKernelGGL(k_tile_gather, dim3((m * 3u + 255u) / 256u), dim3(256), 0, s->stream, (const float4 *)d_batch.get(), d_idx_sorted, first, m,
-                                   cap_batch, st.d_rec[q].get());
-                launches++;
-                HIPCK(hipGetLastError());
-                HIPCK(hipEventRecord(tl.ev[EV_GATHER1 + q], s->stream));
-            }
-            HIPCK(hipMemcpyAsync(st.h_rec[q], from, (size_t)m * 48, hipMemcpyDeviceToHost, s->stream));
-            HIPCK(hipEventRecord(tl.ev[EV_PIECE + q], s->stream));
-            if (p)
-                if (int rc = finish(p - 1)) return rc;
-        }
-        return pieces ? finish(pieces - 1) : SM_OK;
+        return drain(s, d_src, n, 48, &ev[EV_PIECE], &tl.stats.write_ms, false, put, gather);
     }
 };
 
@@ -329,39 +308,32 @@ int sm_default_tile_params(sm_tile_params *p)
 int sm_tile_maps(sm_ctx *s, const sm_map_source *src, const sm_tile_params *p, const char *out_prefix)
 {
     const char *who = "sm_tile_maps";
-    const double t_begin = now_ms();
+    SetCall call(s, src, who);
     if (!s || !src || !out_prefix) { g_err = std::string(who) + ": null context, source or output prefix"; return SM_E_ARG; }
     int rc;
     const uint32_t capacity = sort_capacity();
-    if ((rc = check_whole_map(s, who)) || (rc = check_params(p, capacity, who))) return rc;
-    sm_mapset::ReadSet set;
-    uint32_t cnt;
-    if ((rc = maps_open(s, src, who, check_whole_map, set, cnt))) return rc;
+    if ((rc = call.open([&] { return check_params(p, capacity, who); }))) return rc;   // (the names come from the plan: their rule is below)
+    const sm_mapset::ReadSet &set = call.set;
+    const uint32_t cnt = call.cnt;
     Tile &tl = s->tile;
     tl.stats = sm_tile_stats_t{};
     tl.stats_valid = true;
-    const uint64_t total = set.file_total + cnt;
+    const uint64_t total = call.total;
     tl.stats.records_in = total;
-    if (!total) { tl.stats.total_ms = (float)(now_ms() - t_begin); return SM_OK; }      // (an empty set: no file)
+    if (!total) { tl.stats.total_ms = call.elapsed_ms(); return SM_OK; }      // (an empty set: no file)
 
     TileJob job(s, who);
-    if ((rc = maps_ensure_staging(s)) || (rc = job.open(total, *p))) return rc;
-    const float4 *d_model = nullptr;
-    if (cnt) {
-        if ((rc = ensure_export(s, (size_t)cnt * 48))) return rc;
-        export_aos(s, (float *)s->d_export.get(), 0u, cnt);
-        d_model = (const float4 *)s->d_export.get();
-    }
-    float copy_ms = 0.0f;
-    const MapStream::Tally times = {&tl.stats.read_ms, &copy_ms, &tl.stats.device_ms};
-    const Event *model = &tl.ev[EV_MODEL0];
+    if ((rc = call.staging()) || (rc = job.open(total, *p)) || (rc = call.model())) return rc;
+    const float4 *d_model = call.d_model;
+    const MapStream::Tally times = {&tl.stats.read_ms, &call.copy_ms, &tl.stats.device_ms};
+    const Event *model = &job.ev[EV_MODEL0];
 
     // ---- pass 1: the records per tile
     if ((rc = maps_feed(s, who, set, src->paths, cnt, d_model, times, model[0], [&](const float4 *d_rec, uint32_t n, uint32_t) { job.count(d_rec, n); })))
         return rc;
     tl.stats.readings = 1;
-    uint32_t t[SIMP_TALLY_WORDS];
-    if ((rc = mark(s, model[1])) || (rc = voxel_read_tally(s, job.tally(), t, SIMP_TALLY_WORDS)) || (rc = add_marked(model, &tl.stats.device_ms))) return rc;
+    const uint32_t *t = tl.scratch.h();
+    if ((rc = mark(s, model[1])) || (rc = tl.scratch.read(s, SIMP_TALLY_WORDS)) || (rc = add_marked(model, &tl.stats.device_ms))) return rc;
     if (voxel_check_tally(t, p->max_tiles, who, "tiles")) {
         g_err = std::string(who) + ": more than max_tiles = " + std::to_string(p->max_tiles) + " tiles";
         return SM_E_CAPACITY;
@@ -390,7 +362,7 @@ int sm_tile_maps(sm_ctx *s, const sm_map_source *src, const sm_tile_params *p, c
     frame_range(set, files.start_id, files.end_id);
     for (size_t i = 0; i < files.want.size(); ++i)
         for (uint32_t k = 0; k < src->n_paths; ++k)
-            if (files.name(i) == src->paths[k]) { g_err = sm_mapfile::said(who, src->paths[k], " is a source of the set: the output needs names of its own"); return SM_E_ARG; }
+            if (files.name(i) == src->paths[k]) return own_path_taken(who, src->paths[k]);
     std::vector<Batch> batches = plan_batches(tiles, capacity);
     uint32_t largest_batch = 0;
     for (const Batch &b : batches) largest_batch = std::max(largest_batch, b.n);
@@ -412,23 +384,17 @@ int sm_tile_maps(sm_ctx *s, const sm_map_source *src, const sm_tile_params *p, c
         if (ranks != batches[b].n || (with_loose && loose_ranks != loose)) { g_err = std::string(who) + ": the set changed while it was read"; return SM_E_ARG; }
         if (!ranks) continue;
         int which;
-        if ((rc = job.sort(ranks, varying, which)) || (rc = job.drain(job.d_idx[which].get(), nullptr, ranks, files))) return rc;
+        if ((rc = job.sort(ranks, varying, which)) || (rc = job.to_files(job.d_idx[which].get(), nullptr, ranks, files))) return rc;
     }
-    if (loose && (rc = job.drain(nullptr, job.d_loose.get(), (uint32_t)loose, files))) return rc;
+    if (loose && (rc = job.to_files(nullptr, job.d_loose.get(), (uint32_t)loose, files))) return rc;
     tl.stats.device_ms += tl.stats.sort_ms;
     tl.stats.launches = job.launches;
     if ((rc = files.rename(s->index))) return rc;
     tl.stats.files_written = (uint32_t)files.done.size();
-    tl.stats.total_ms = (float)(now_ms() - t_begin);
+    tl.stats.total_ms = call.elapsed_ms();
     return SM_OK;
 }
 
-int sm_tile_stats(sm_ctx *s, sm_tile_stats_t *out)
-{
-    if (!s || !out) { g_err = "sm_tile_stats: null argument"; return SM_E_ARG; }
-    if (!s->tile.stats_valid) { g_err = "sm_tile_stats: no sm_tile_maps call yet"; return SM_E_ARG; }
-    *out = s->tile.stats;
-    return SM_OK;
-}
+SM_STATS_GETTER(sm_tile_stats, sm_tile_stats_t, tile, "sm_tile_maps")
 
 }  // extern "C"

@@ -1,5 +1,5 @@
-// sm_voxel.h -- private to sm_simplify.hip, sm_register.hip, sm_compare.hip, sm_tile.hip, sm_segment.hip, sm_mesh.hip and sm_voxel.hip, which defines what is declared
-// here: what the users of a voxel table do alike on the host.  The grid and the table's size from a call's parameters and the
+// sm_voxel.h -- private to sm_voxel.hip, which defines what is declared here, and to sm_set_call.h, through which the map-set
+// analysis calls take it: what the users of a voxel table do alike on the host.  The grid and the table's size from a call's parameters and the
 // tally's verdict (all three); the lookup table -- sums finished into one RegCell per slot, with or without a cover table of keys
 // -- of registration and change detection; the ranked output -- what a pass keeps of every chunk, in order, in one map file -- of
 // simplification and change detection.  Kernels: sm_k_voxel.h.
@@ -15,8 +15,6 @@ SimplifyArgs voxel_args(int32_t voxel_mm, int shift, const float origin[3], int 
 // the slots of a table for `records` records of at most max_cells cells: a power of two, at least twice the cells it may hold;
 // SM_E_CAPACITY, "<who>: <what> would need ...", beyond 2^31
 int voxel_slots(uint64_t records, uint32_t max_cells, const char *who, const char *what, uint64_t &slots);
-// `words` tally words from the device at d to h, once the stream is idle
-int voxel_read_tally(sm_ctx *s, const uint32_t *d, uint32_t *h, size_t words);
 // SM_E_CAPACITY, "<who>: more than max_cells = N <what>", if a table's tally t has its error word set
 int voxel_check_tally(const uint32_t *t, uint32_t max_cells, const char *who, const std::string &what);
 

@@ -17,8 +17,7 @@ SimplifyArgs sm_impl::voxel_args(int32_t voxel_mm, int shift, const float origin
     for (int k = 0; k < 3; ++k) a.origin[k] = origin[k];
     a.split = split;
     a.max_cells = max_cells;
-    const char *e = std::getenv("SM_SIMPLIFY_NO_COMBINE");
-    a.combine = (e && e[0] == '1') ? 0 : 1;
+    a.combine = env_is_one("SM_SIMPLIFY_NO_COMBINE") ? 0 : 1;
     return a;
 }
 
@@ -27,14 +26,6 @@ int sm_impl::voxel_slots(uint64_t records, uint32_t max_cells, const char *who, 
     slots = SIMP_MIN_SLOTS;
     while (slots < 2 * std::min<uint64_t>(records, max_cells)) slots <<= 1;
     if (slots > (1ull << 31)) { g_err = std::string(who) + ": " + what + " would need more than 2^31 slots"; return SM_E_CAPACITY; }
-    return SM_OK;
-}
-
-int sm_impl::voxel_read_tally(sm_ctx *s, const uint32_t *d, uint32_t *h, size_t words)
-{
-    HIPCK(hipGetLastError());
-    HIPCK(hipMemcpyAsync(h, d, words * 4, hipMemcpyDeviceToHost, s->stream));
-    HIPCK(hipStreamSynchronize(s->stream));
     return SM_OK;
 }
 

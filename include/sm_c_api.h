@@ -1798,6 +1798,73 @@ int sm_lidar_sweep_scene(sm_ctx *s, const sm_map_source *src, const sm_scene *sc
 int sm_scene_place_rows(const float *pose12, const float *rows_in, uint32_t n, float *rows_out);   /* host only, no context */
 int sm_scene_stats(sm_ctx *s, sm_scene_stats_t *out);        /* SM_E_ARG before the first scene call */
 
+/* ---- ray casts: what a list of rays hits in a map set (DESIGN.md "4x. Ray casts") ----
+ * sm_cast_rays_maps casts n_rays arbitrary rays into a map set -- an sm_map_source with the global ids of the map-set calls: the
+ * files in list order, each in file order, then (include_model) the live model; no paths and include_model = 1: the live model
+ * alone.  Ids are sm_lidar_sweep_maps' ids.  The set is read ONCE per call, whatever n_rays.
+ * The rule (fp32, in the order written, no contraction).  For a ray (o, d, t_min, t_max) and a record with centre p, stored normal
+ *   n (not normalised) and stored radius r:
+ *     c_i = p_i - o_i
+ *     den = (n.x*d.x + n.y*d.y) + n.z*d.z
+ *     num = (n.x*c.x + n.y*c.y) + n.z*c.z
+ *     t   = num / den
+ *     q_i = t*d_i - c_i
+ *     hit = t >= t_min && t <= t_max && ((q.x*q.x + q.y*q.y) + q.z*q.z) <= r*r
+ *   Every comparison is false on a NaN; there is no epsilon; discs are two-sided; dir is used as given, so t is in units of its
+ *   length.  A record takes part iff conf >= min_conf (in the live model: the occupied slots after the compaction every map-set
+ *   call begins with -- dead slots are gone).  The return of a ray is the hitting record with the smallest t, ties to the lower
+ *   id: the least key (bits(t + 0.0f) << 32) | id under a 64-bit atomicMin (the + 0.0f makes a t of -0 order as 0), and t + 0.0f is
+ *   the t returned.
+ * Rays.  A ray is valid iff its eight floats are finite, t_min >= 0, t_max >= t_min and dir is not all zeros.  An invalid ray
+ *   returns the empty values and counts in stats.bad_rays; it is no error.
+ * Outputs, one entry per ray; any but t may be NULL.  Empty values: t 0, id -1, rgb 0 0 0, sem 0, normal3 0 0 0.  rgb (3 bytes) and
+ *   sem (class + 1) are made of the record's colour word exactly as sm_lidar_sweep makes them; normal3 is the returned record's
+ *   stored normal, verbatim.
+ * Independence.  The answer is defined by the rule alone: it depends neither on cell_mm, nor on origin, nor on the chunking, nor
+ *   on the split of the set into files, nor on the order of work.  The voxel index only leaves out (ray, record) pairs that are
+ *   proven to fail the test (csrc/sm_k_rays.h states the proof).  SM_RAYS_NO_INDEX=1 (read per call) tests every record against
+ *   every ray (an A/B switch: the outputs are the same).
+ * Lidar equality.  Under a pose whose rotation is the identity the lidar's c is p - o bit for bit, so a cast of
+ *   sm_lidar_directions' table from that origin with [min_range, max_range] equals sm_lidar_sweep / sm_lidar_sweep_maps in all
+ *   four planes, bit for bit.
+ * Side effects: none on the model, the counters, the tick, the frame log or the trackers.  Synchronous.
+ * Errors.  Everything is checked, every file's header included, before an output is written.  SM_E_ARG: a NULL ctx, source or
+ *   params; NULL rays or t with n_rays > 0; cell_mm < 1 or above 2^24; a non-finite origin; n_rays > SM_RAYS_MAX; a
+ *   call between sm_stage_conflict and sm_stage_cull; a missing file or one whose length disagrees with its header;
+ *   sm_cast_rays_stats before any call has succeeded.  SM_E_UNSUPPORTED: a sharded or rig context.  n_rays == 0 checks the set only.
+ * Files are never skipped: the file index bounds the centres of a file, not its radii, so no file is proven out of reach. */
+#define SM_RAYS_MAX (1u << 24)
+typedef struct sm_ray { float origin[3]; float t_min; float dir[3]; float t_max; } sm_ray;   /* 32 bytes, world frame */
+typedef struct sm_rays_params {
+    int32_t cell_mm;          /* the index grid's cell edge, 1..2^24 (speed only)                     default 250 */
+    float   origin[3];        /* the index grid's origin (speed only)                                 default 0 0 0 */
+    float   min_conf;         /* a record takes part iff conf >= min_conf (a NaN: none does)          default 0 */
+    int32_t reserved[3];
+} sm_rays_params;
+typedef struct sm_rays_stats_t {
+    uint64_t rays, bad_rays;  /* rays given; invalid ones among them */
+    uint64_t records;         /* of the set */
+    uint64_t wide;            /* records every ray tests directly: a cube over more than 8 cells, loose to the grid, a radius that
+                                 is not finite, no slot in the table (or all taking part with SM_RAYS_NO_INDEX=1) */
+    uint64_t pairs, cells;    /* (cell, record) pairs and distinct cells of the largest chunk */
+    uint64_t probes, tests;   /* table probes (slots read) and exact tests, all rays and chunks */
+    uint64_t no_slot;         /* of `wide`: regular records whose cells found no slot in an overfull table */
+    uint64_t gave_up;         /* (ray, chunk) walks that visited more than 64 + n / 8 cells of a chunk of n records and tested its
+                                 regular records one by one instead: at most n tests per ray and chunk */
+    uint32_t chunks;          /* pieces of at most 2^20 records */
+    uint32_t files_skipped;   /* always 0: see above */
+    float read_ms;            /* host: reading the files */
+    float copy_ms;            /* device: the chunks' copies */
+    float index_ms;           /* device: building the chunks' indices */
+    float cast_ms;            /* device: traversal, wide lists, resolve */
+    float device_ms;          /* device: everything between the upload of the rays and the planes' copies back */
+    float total_ms;
+} sm_rays_stats_t;
+int sm_default_rays_params(sm_rays_params *p);               /* pure, no context */
+int sm_cast_rays_maps(sm_ctx *s, const sm_map_source *src, const sm_rays_params *p, const sm_ray *rays, uint32_t n_rays,
+                      float *t, int32_t *id, uint8_t *rgb, uint8_t *sem, float *normal3);
+int sm_cast_rays_stats(sm_ctx *s, sm_rays_stats_t *out);     /* SM_E_ARG before the first call */
+
 /* ---- per-pass entry points (GlobalModel / IndexMap methods), synchronous ---- */
 /* Upload RGB / metric depth / semantic textures directly (bypasses p0). */
 int sm_set_frame(sm_ctx *s, const uint8_t *rgb, const float *depth_metric,

@@ -55,6 +55,7 @@ SYMBOLS = (
     "sm_default_mesh_params", "sm_mesh_maps", "sm_mesh_stats",
     "sm_default_ground_params", "sm_ground_maps", "sm_ground_stats",
     "sm_render_image_scene", "sm_lidar_sweep_scene", "sm_scene_place_rows", "sm_scene_stats",
+    "sm_default_rays_params", "sm_cast_rays_maps", "sm_cast_rays_stats",
 )
 
 SM_COLL_SUM, SM_COLL_MIN, SM_COLL_GATHER = 0, 1, 2
@@ -191,6 +192,63 @@ def lidar_points(range, dirs, rgb=None) -> np.ndarray:
         c = np.ascontiguousarray(rgb, np.uint8).reshape(-1, 3)[got].astype(f32)
         out[:, 3] = ((f32(0.299) * c[:, 0] + f32(0.587) * c[:, 1]) + f32(0.114) * c[:, 2]) / f32(255.0)
     return out
+
+
+class SmRay(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("t_min", C.c_float), ("dir", C.c_float * 3), ("t_max", C.c_float)]
+
+
+class SmRaysParams(C.Structure):
+    _fields_ = [("cell_mm", C.c_int32), ("origin", C.c_float * 3), ("min_conf", C.c_float), ("reserved", C.c_int32 * 3)]
+
+
+class SmRaysStats(C.Structure):
+    _fields_ = [("rays", C.c_uint64), ("bad_rays", C.c_uint64), ("records", C.c_uint64), ("wide", C.c_uint64), ("pairs", C.c_uint64),
+                ("cells", C.c_uint64), ("probes", C.c_uint64), ("tests", C.c_uint64), ("no_slot", C.c_uint64), ("gave_up", C.c_uint64),
+                ("chunks", C.c_uint32), ("files_skipped", C.c_uint32),
+                ("read_ms", C.c_float), ("copy_ms", C.c_float), ("index_ms", C.c_float), ("cast_ms", C.c_float), ("device_ms", C.c_float),
+                ("total_ms", C.c_float)]
+
+
+RAYS_MAX = 1 << 24
+
+
+def rays_params(**over) -> SmRaysParams:
+    """sm_default_rays_params with fields replaced: cell_mm, origin (three floats), min_conf"""
+    p = SmRaysParams()
+    load().sm_default_rays_params(C.byref(p))
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise KeyError(k)
+        setattr(p, k, (C.c_float * 3)(*[float(x) for x in v]) if k == "origin" else v)
+    return p
+
+
+def lidar_rays(sensor, poses16) -> np.ndarray:
+    """The beams of a sweep as rays for SurfelMap.cast_rays: float32[n_el * n_az][8] = (origin, t_min, dir, t_max), row-major over
+    the sensor's grid.  poses16: one sensor->world pose (float32[16] column-major or 4x4), or n_az of them, one per column -- the
+    sweep of a vehicle that moves while the sensor turns.  The origin is the pose's translation, the direction R * d of
+    lidar_directions' table, computed in double ((R0 dx + R1 dy) + R2 dz, terms with a zero coefficient left out) and rounded
+    once; t_min / t_max are the sensor's range limits.  Needs no context."""
+    d = lidar_directions(sensor).astype(np.float64)                       # [n_el][n_az][3]
+    n_el, n_az = d.shape[0], d.shape[1]
+    P = np.asarray(poses16, np.float32)
+    if P.ndim >= 2 and P.shape[-2:] == (4, 4):
+        P = np.swapaxes(P, -1, -2)                                        # (numpy row/col indexing -> column-major)
+    P = np.ascontiguousarray(P).reshape(-1, 16)
+    if P.shape[0] not in (1, n_az):
+        raise ValueError("poses16: one pose, or one per column (n_az)")
+    P = np.broadcast_to(P, (n_az, 16))
+    R = P.astype(np.float64).reshape(n_az, 4, 4)[:, :3, :3]               # R[j][c][r]: column c, row r of pose j
+    # a term whose coefficient is 0 is left out (-0.0 is the sum's neutral element), so an identity rotation returns d bit for bit
+    term = [np.where(R[None, :, c, :] != 0.0, R[None, :, c, :] * d[:, :, None, c], -0.0) for c in range(3)]
+    dirs = (term[0] + term[1]) + term[2]
+    rays = np.zeros((n_el, n_az, 8), np.float32)
+    rays[:, :, 0:3] = P[None, :, 12:15]
+    rays[:, :, 3] = np.float32(sensor.min_range)
+    rays[:, :, 4:7] = dirs.astype(np.float32)
+    rays[:, :, 7] = np.float32(sensor.max_range)
+    return rays.reshape(n_el * n_az, 8)
 
 
 class SmSceneActor(C.Structure):
@@ -1258,6 +1316,9 @@ def load():
     L.sm_default_ground_params.argtypes = [gpp]
     L.sm_ground_maps.argtypes = [vp, msp, gpp] + [C.c_void_p] * 6 + [C.POINTER(SmGroundInfo)]
     L.sm_ground_stats.argtypes = [vp, C.POINTER(SmGroundStats)]
+    L.sm_default_rays_params.argtypes = [C.POINTER(SmRaysParams)]
+    L.sm_cast_rays_maps.argtypes = [vp, C.POINTER(SmMapSource), C.POINTER(SmRaysParams), vp, C.c_uint32, vp, vp, vp, vp, vp]
+    L.sm_cast_rays_stats.argtypes = [vp, C.POINTER(SmRaysStats)]
     scp = C.POINTER(SmScene)
     L.sm_render_image_scene.argtypes = [vp, msp, scp, vp, C.c_uint32, C.c_int, C.c_int] + [C.c_float] * 4 + [flp, vp, vp, vp]
     L.sm_lidar_sweep_scene.argtypes = [vp, msp, scp, lsp, vp, C.c_uint32, vp, vp, vp, vp]
@@ -2155,6 +2216,33 @@ class SurfelMap:
         st = SmLidarStats()
         self._chk(self._L.sm_lidar_stats(self._h, C.byref(st)), "sm_lidar_stats")
         return {k: getattr(st, k) for k, _ in SmLidarStats._fields_}
+
+    # -- ray casts (sm_cast_rays_maps)
+    def cast_rays(self, rays, paths=(), include_model=True, cell_mm=250, origin=None, min_conf=0.0, normal=False) -> dict:
+        """What the rays float32[n][8] = (origin, t_min, dir, t_max), world frame, hit in the map set `paths` (then, with
+        include_model, the live model): a dict of t float32[n] (in units of |dir|; 0 = no return), id int32 (position in the
+        concatenation, -1), rgb uint8[n][3], sem uint8 (class + 1, 0) and, with normal, normal float32[n][3] (the record's stored
+        normal).  The nearest hitting record per ray, ties to the lower id (sm_cast_rays_maps; tests/rays_ref.py restates the
+        rule).  cell_mm and origin shape the voxel index and change nothing in the answer.  An invalid ray returns the empty values."""
+        rays = np.ascontiguousarray(rays, np.float32)
+        if rays.ndim != 2 or rays.shape[1] != 8:
+            raise ValueError("rays: float32[n][8]")
+        n = rays.shape[0]
+        p = rays_params(cell_mm=cell_mm, origin=(0.0, 0.0, 0.0) if origin is None else origin, min_conf=min_conf)
+        src = map_source(paths, include_model)
+        out = dict(t=np.zeros(n, np.float32), id=np.full(n, -1, np.int32), rgb=np.zeros((n, 3), np.uint8), sem=np.zeros(n, np.uint8))
+        if normal:
+            out["normal"] = np.zeros((n, 3), np.float32)
+        self._chk(self._L.sm_cast_rays_maps(self._h, C.byref(src), C.byref(p), _ptr(rays), n, *[_ptr(out[k]) for k in ("t", "id", "rgb", "sem")],
+                                            _ptr(out["normal"]) if normal else None), "sm_cast_rays_maps")
+        return out
+
+    def cast_rays_stats(self) -> dict:
+        """of the last cast_rays: rays, bad_rays, records, wide, pairs and cells (of the largest chunk), probes, tests, no_slot, gave_up, chunks,
+        files_skipped (always 0), read_ms, copy_ms, index_ms, cast_ms, device_ms, total_ms"""
+        st = SmRaysStats()
+        self._chk(self._L.sm_cast_rays_stats(self._h, C.byref(st)), "sm_cast_rays_stats")
+        return {k: getattr(st, k) for k, _ in SmRaysStats._fields_}
 
     # -- scenes (sm_render_image_scene, sm_lidar_sweep_scene)
     def render_scene(self, paths, actors, views, w, h, fx, fy, cx, cy, include_model=True, fill=None, depth=False):

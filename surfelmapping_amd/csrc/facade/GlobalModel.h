@@ -317,6 +317,33 @@ public:
         return true;
     }
 
+    // What a list of rays (sm_ray: origin, t_min, dir, t_max; world frame) hits in the model (sm_cast_rays_maps): per ray the t of the
+    // nearest hitting surfel in units of |dir| (0: none), its id (-1), its colour bytes, its class + 1 (0) and its stored normal.
+    struct RayReturns { std::vector<float> t; std::vector<int32_t> id; std::vector<unsigned char> rgb, sem; std::vector<float> normal; };
+    bool castRays(const std::vector<sm_ray> &rays, RayReturns &out, const sm_rays_params *params = nullptr)
+    {
+        return castRaysOf(ctx_, {}, true, rays, out, params, "castRays");
+    }
+    // (SurfelMapping::castRays casts into a map set through this)
+    static bool castRaysOf(sm_ctx *ctx, const std::vector<std::string> &mapFiles, bool includeModel, const std::vector<sm_ray> &rays, RayReturns &out,
+                           const sm_rays_params *params, const char *who)
+    {
+        const size_t n = rays.size();
+        out.t.assign(n, 0.0f); out.id.assign(n, -1); out.rgb.assign(n * 3, 0); out.sem.assign(n, 0); out.normal.assign(n * 3, 0.0f);
+        sm_rays_params p;
+        sm_default_rays_params(&p);
+        if (params) p = *params;
+        std::vector<const char *> paths;
+        for (const std::string &f : mapFiles) paths.push_back(f.c_str());
+        const sm_map_source src{paths.data(), (uint32_t)paths.size(), includeModel ? 1 : 0};
+        (void)sm_sync(ctx);                                              // (SM_FACADE_ASYNC: frames may still be in flight)
+        if (sm_cast_rays_maps(ctx, &src, &p, rays.data(), (uint32_t)n, out.t.data(), out.id.data(), out.rgb.data(), out.sem.data(), out.normal.data()) != SM_OK) {
+            std::printf("%s: %s\n", who, sm_last_error());
+            return false;
+        }
+        return true;
+    }
+
     // The model-aligned mirror textures (src/GlobalModel.cpp:639-681) do not exist in the compute core.  GUI::drawCapacity
     // (build_map.cpp:204) shows the fill level of the TEXTURE_DIMENSION^2 normal/radius mirror: the handle is filled lazily --
     // size TEXTURE_DIMENSION x TEXTURE_DIMENSION, and (without GL) the host copy of the plane for whoever wants to look.

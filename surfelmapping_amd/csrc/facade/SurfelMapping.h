@@ -515,6 +515,14 @@ public:
         return acquireSweepsOf(path, mapFiles, poses, sensor, startId, includeModel, nullptr);
     }
 
+    // What a list of rays hits in a map set (sm_cast_rays_maps; DESIGN.md "4x. Ray casts"): the map files in that order, then --
+    // includeModel -- the live model, read once whatever the number of rays.  GlobalModel::castRays is the live model alone.
+    bool castRays(const std::vector<std::string> &mapFiles, const std::vector<sm_ray> &rays, GlobalModel::RayReturns &out, bool includeModel = true,
+                  const sm_rays_params *params = nullptr)
+    {
+        return GlobalModel::castRaysOf(ctx_, mapFiles, includeModel, rays, out, params, "castRays");
+    }
+
     // Scenes (sm_render_image_scene / sm_lidar_sweep_scene; DESIGN.md "4w. Scenes"): the map set with moving actors in it.  Every
     // actor's file is read once and drawn under its pose of each view where it is present; no file is copied or rewritten.
     // acquireSceneImages writes what acquireImages writes and honours setFillHoles / setWriteDepth; the blended view draws no

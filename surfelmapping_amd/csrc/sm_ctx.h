@@ -421,6 +421,12 @@ struct Ground {
     bool stats_valid = false;
 };
 
+// ray casts (sm_rays.hip, sm_k_rays.h): the last call's stats.  The index, the rays and the planes live for one call.
+struct Rays {
+    sm_rays_stats_t stats{};
+    bool stats_valid = false;
+};
+
 // scenes (sm_scene.hip, sm_k_scene.h): the actors of one call resident on the device -- the distinct files' records as they were
 // read, the SoA planes and boxes k_maps_intake makes of them, the call's tables -- grown on demand and reloaded by every call (no
 // cache across calls); the last call's tally
@@ -695,6 +701,7 @@ struct sm_ctx {
     Segment seg;
     Mesh mesh;
     Ground ground;
+    Rays rays;
     Scene scene;
 };
 

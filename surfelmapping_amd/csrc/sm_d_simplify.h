@@ -334,4 +334,30 @@ __device__ __forceinline__ uint32_t simp_rank_in_chunk(bool kept, const uint32_t
     return rank;
 }
 
+// ---- the lean claim table (ray casts, DESIGN.md "4x"): a key plane and a plane of (count, first) per slot, nothing of the 148 bytes
+// a SimplifyTable slot holds.  sm_voxel.hip sizes and clears it (lean_slots, lean_clear).  lean_probe is simp_probe's walk over
+// the key plane alone, bounded by LEAN_WALK, counting the slots it reads: a key that was claimed lies within LEAN_WALK of its
+// hash and slots never empty again, so a later walk finds it in as many steps.  With `claim` a stale "empty" is settled by the
+// CAS, so a lane that has claimed or seen a key finds it again whatever its cache holds; without it the walk uses plain loads and
+// belongs in a LATER launch than the claims.
+constexpr uint32_t LEAN_WALK = 256u;
+struct LeanTable { unsigned long long *key; uint2 *run; uint32_t mask; };   // run: (records of the cell, their first pair)
+
+__device__ __forceinline__ bool lean_probe(const LeanTable &T, unsigned long long key, bool claim, uint32_t &slot, uint32_t &probes)
+{
+    uint32_t sl = (uint32_t)simp_hash(key) & T.mask;
+    for (uint32_t i = 0; i < LEAN_WALK && i <= T.mask; ++i) {
+        unsigned long long cur = T.key[sl];              // (a key never changes)
+        ++probes;
+        if (cur == SIMP_EMPTY) {
+            if (!claim) return false;
+            cur = atomicCAS(&T.key[sl], SIMP_EMPTY, key);
+            if (cur == SIMP_EMPTY) cur = key;
+        }
+        if (cur == key) { slot = sl; return true; }
+        sl = (sl + 1u) & T.mask;
+    }
+    return false;
+}
+
 }  // namespace sm

@@ -35,6 +35,11 @@ void lut_insert(sm_ctx *s, const LookupTable &t, const float4 *d_rec, uint32_t n
 // the sums become the lookup records
 void lut_finish(sm_ctx *s, const LookupTable &t, uint32_t &launches);
 
+// The lean claim table of the ray casts (sm_d_simplify.h: LeanTable, lean_probe): 4 slots per record of the chunk it indexes, at
+// least SIMP_MIN_SLOTS, a power of two; 16 bytes a slot.  lean_clear: keys empty, runs zero, on the context's stream.
+size_t lean_slots(uint32_t records);
+int lean_clear(sm_ctx *s, const sm::LeanTable &t);
+
 // The pair sort of tiling and meshing: n (key, idx) pairs in key[0] / idx[0] sorted by key, stably, by an LSD radix sort of 8 bits a
 // pass over the bits 0..55; a pass whose digit no bit of `varying` touches is skipped (every key has the same digit there).
 // hist: pair_sort_hist_words(n) words.  which: the buffer that holds the pairs then; passes: those that ran.

@@ -83,6 +83,23 @@ void sm_impl::lut_finish(sm_ctx *s, const LookupTable &t, uint32_t &launches)
     launches++;
 }
 
+// ---- the lean claim table
+
+size_t sm_impl::lean_slots(uint32_t records)
+{
+    uint64_t slots = SIMP_MIN_SLOTS;
+    while (slots < 4ull * records) slots <<= 1;
+    return (size_t)slots;
+}
+
+int sm_impl::lean_clear(sm_ctx *s, const LeanTable &t)
+{
+    const size_t S = (size_t)t.mask + 1u;
+    HIPCK(hipMemsetAsync(t.key, 0xFF, S * 8, s->stream));
+    HIPCK(hipMemsetAsync(t.run, 0, S * 8, s->stream));
+    return SM_OK;
+}
+
 // ---- the pair sort
 
 size_t sm_impl::pair_sort_hist_words(uint32_t n) { return (size_t)((n + PAIR_SORT_BLOCK - 1) / PAIR_SORT_BLOCK) * 256; }

@@ -2,6 +2,9 @@
 
 This is plumbing only: every call goes straight to the HIP library.  There is NO CPU
 fallback -- if the shared library is missing or no GPU is visible, calls fail loudly.
+
+Three parts, in this order: the header's mirror (constants, structures, record types and ONE table of prototypes), the helpers
+(loading, the parameter builders, what the calls share) and SurfelMap.
 """
 from __future__ import annotations
 
@@ -12,57 +15,25 @@ import numpy as np
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SM_HIP_LIB") or os.path.join(_PKG, "libsurfelmapping_hip.so")      # (SM_HIP_LIB: another build of the core, for A/B runs)
+
+# =====================================================================================================================
+# The header's mirror
+# =====================================================================================================================
 API_VERSION = 4                # SM_API_VERSION of include/sm_c_api.h
 
 SM_OK, SM_E_ARG, SM_E_CAPACITY, SM_E_UNSUPPORTED, SM_E_HIP, SM_E_NO_DEVICE = 0, -1, -2, -3, -4, -5
 TEX_DEPTH_METRIC, TEX_DEPTH_FILTERED, TEX_LAST = 0, 1, 2
-
-# every extern "C" symbol include/sm_c_api.h declares
-SYMBOLS = (
-    "sm_api_version", "sm_last_error", "sm_default_config", "sm_create", "sm_destroy",
-    "sm_process_frame", "sm_process_frame_device", "sm_process_frame_async",
-    "sm_inputs_consumed", "sm_host_alloc", "sm_host_alloc_frame", "sm_host_free", "sm_debug_slow_frames", "sm_debug_squeezes", "sm_sync", "sm_clean_points", "sm_clean_points_ex", "sm_clean_points_cb", "sm_reset",
-    "sm_get_counts", "sm_download_model_aos", "sm_upload_model_aos", "sm_save_map", "sm_load_map",
-    "sm_download_index_map", "sm_download_raw_cloud", "sm_download_depth", "sm_render_image", "sm_render_model",
-    "sm_render_model_device", "sm_render_image_maps", "sm_render_model_maps", "sm_render_maps_stats", "sm_set_frame", "sm_set_tick",
-    "sm_stage_conflict", "sm_stage_cull", "sm_stage_splat", "sm_stage_associate_fuse",
-    "sm_stage_timings", "sm_read_frame_log", "sm_device_alloc", "sm_device_free", "sm_device_upload",
-    "sm_export_model_device", "sm_append_model_aos_device", "sm_device_download",
-    "sm_shard_stream_configure", "sm_shard_set_collective", "sm_shard_rccl_unique_id", "sm_shard_rccl_init",
-    "sm_shard_rccl_finalize", "sm_shard_rccl_nranks", "sm_shard_frame_device", "sm_shard_frame", "sm_shard_compact", "sm_shard_export_dense_device",
-    "sm_gpu_process_count", "sm_rig_configure", "sm_rig_consolidate", "sm_rig_consolidate_step",
-    "sm_default_track_params", "sm_track_frame", "sm_track_debug",
-    "sm_default_track_rgb_params", "sm_track_frame_rgb", "sm_track_rgb_debug",
-    "sm_default_retire_params", "sm_retire", "sm_retire_device", "sm_set_auto_retire", "sm_auto_retire_stats",
-    "sm_default_recall_params", "sm_recall", "sm_recall_stats", "sm_set_auto_recall", "sm_auto_recall_stats",
-    "sm_warp_by_time", "sm_warp_stats", "sm_loop_spread", "sm_track_frame_old", "sm_track_debug_old",
-    "sm_default_loop_params", "sm_close_loop",
-    "sm_track_frame_window", "sm_track_debug_window", "sm_track_frame_rgb_window", "sm_track_rgb_debug_window", "sm_close_loop_rgb",
-    "sm_old_in_view", "sm_default_auto_loop_params", "sm_set_auto_loop", "sm_auto_loop_stats",
-    "sm_default_search_params", "sm_score_poses_window", "sm_search_pose", "sm_close_loop_search", "sm_set_auto_loop_search",
-    "sm_default_lidar_sensor", "sm_lidar_directions", "sm_lidar_sweep", "sm_lidar_sweep_maps", "sm_lidar_stats",
-    "sm_default_fern_params", "sm_fern_table", "sm_set_ferns", "sm_fern_encode", "sm_fern_encode_device", "sm_fern_add", "sm_fern_count",
-    "sm_fern_download", "sm_fern_save", "sm_fern_load", "sm_fern_match", "sm_search_pose_at", "sm_close_loop_at",
-    "sm_default_auto_place_params", "sm_set_auto_place", "sm_auto_place_stats",
-    "sm_default_stereo_params", "sm_set_stereo", "sm_stereo_depth", "sm_stereo_depth_device", "sm_stereo_download",
-    "sm_default_fill_params", "sm_fill_image", "sm_fill_image_device", "sm_render_image_ex", "sm_render_image_maps_ex", "sm_fill_stats",
-    "sm_default_blend_params", "sm_render_image_blend", "sm_render_image_maps_blend", "sm_blend_stats",
-    "sm_default_simplify_params", "sm_simplify", "sm_simplify_maps", "sm_simplify_stats",
-    "sm_default_register_params", "sm_register_maps", "sm_register_debug", "sm_register_stats",
-    "sm_default_compare_params", "sm_compare_maps", "sm_compare_stats",
-    "sm_default_tile_params", "sm_tile_maps", "sm_tile_stats",
-    "sm_default_segment_params", "sm_segment_maps", "sm_segment_stats",
-    "sm_default_mesh_params", "sm_mesh_maps", "sm_mesh_stats",
-    "sm_default_ground_params", "sm_ground_maps", "sm_ground_stats",
-    "sm_render_image_scene", "sm_lidar_sweep_scene", "sm_scene_place_rows", "sm_scene_stats",
-    "sm_default_rays_params", "sm_cast_rays_maps", "sm_cast_rays_stats",
-)
 
 SM_COLL_SUM, SM_COLL_MIN, SM_COLL_GATHER = 0, 1, 2
 # int fn(void *user, const void *send, void *recv, size_t count_u64, int op, void *hip_stream)
 COLLECTIVE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
 # long long fn(void *user, uint32_t local_conflicts)
 CAP_FN = C.CFUNCTYPE(C.c_longlong, C.c_void_p, C.c_uint32)
+
+
+def _as_dict(st) -> dict:
+    """the fields of a structure by name"""
+    return {n: getattr(st, n) for n, _ in st._fields_}
 
 
 class SmConfig(C.Structure):
@@ -83,9 +54,7 @@ class SmCounts(C.Structure):
         ("conflict_count", C.c_uint32), ("unstable_count", C.c_uint32),
         ("fused_count", C.c_uint32), ("visible_count", C.c_uint32), ("tick", C.c_int32),
     ]
-
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_}
+    as_dict = _as_dict
 
 
 class SmTimings(C.Structure):
@@ -97,9 +66,7 @@ class SmTimings(C.Structure):
         "k_surfel_pass", "k_pass_fixup", "k_conflict_own", "k_associate_direct", "k_associate_own", "k_append_own")] + [
         ("frames_one_pass", C.c_uint32), ("frames_direct", C.c_uint32), ("k_assoc_prep", C.c_float), ("k_prep_own", C.c_float),
         ("frames_merged", C.c_uint32), ("frames_assoc_alone", C.c_uint32), ("k_scan_own", C.c_float)]
-
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_}
+    as_dict = _as_dict
 
 
 FRAME_LOG_LEN = 1024
@@ -126,15 +93,6 @@ class SmMapsStats(C.Structure):
                 ("total_ms", C.c_float)]
 
 
-def map_source(paths, include_model=True) -> SmMapSource:
-    """a map set: the files in drawing order, then (include_model) the live model; keeps the path strings alive"""
-    enc = [os.fsencode(p) for p in paths]
-    arr = (C.c_char_p * max(len(enc), 1))(*enc)
-    src = SmMapSource(C.cast(arr, C.POINTER(C.c_char_p)), len(enc), int(bool(include_model)))
-    src._keep = (enc, arr)
-    return src
-
-
 class SmLidarSensor(C.Structure):
     _fields_ = [("n_az", C.c_int32), ("n_el", C.c_int32), ("az0_deg", C.c_float), ("az_step_deg", C.c_float),
                 ("el_deg", C.POINTER(C.c_float)), ("min_range", C.c_float), ("max_range", C.c_float), ("min_conf", C.c_float)]
@@ -147,51 +105,6 @@ class SmLidarStats(C.Structure):
 
 
 LIDAR_MAX_BEAMS = 1 << 22
-
-
-def lidar_sensor(**over) -> SmLidarSensor:
-    """sm_default_lidar_sensor with fields replaced: n_az, n_el, az0_deg, az_step_deg, el_deg (a sequence of n_el elevations; giving
-    it sets n_el unless that is given too), min_range, max_range, min_conf.  Keeps the elevation array alive."""
-    p = SmLidarSensor()
-    load().sm_default_lidar_sensor(C.byref(p))
-    el = over.pop("el_deg", None)
-    if el is None:
-        el = np.array([p.el_deg[i] for i in range(p.n_el)], np.float32)
-    el = np.ascontiguousarray(el, np.float32).reshape(-1)
-    p.n_el = len(el)
-    for k, v in over.items():
-        if not hasattr(p, k):
-            raise KeyError(k)
-        setattr(p, k, v)
-    p.el_deg = el.ctypes.data_as(C.POINTER(C.c_float))
-    p._keep = el
-    return p
-
-
-def lidar_directions(sensor) -> np.ndarray:
-    """the sensor's beam directions in its own frame (sm_lidar_directions): float32[n_el][n_az][3]"""
-    d = np.zeros((max(sensor.n_el, 0), max(sensor.n_az, 0), 3), np.float32)
-    rc = load().sm_lidar_directions(C.byref(sensor), _ptr(d))
-    if rc:
-        raise SurfelMapError("sm_lidar_directions", rc, load().sm_last_error().decode())
-    return d
-
-
-def lidar_points(range, dirs, rgb=None) -> np.ndarray:
-    """the returns of a sweep as KITTI velodyne points: float32[N][4] = (z, -x, -y) of t*d in the sensor frame (x forward, y left,
-    z up) and the reflectance -- the luminance of rgb by the colour tracker's weights, ((0.299 r + 0.587 g) + 0.114 b) / 255 in
-    float32, or 0 without rgb.  Beams without a return (range 0) are left out; the order is the grid's, row-major."""
-    f32 = np.float32
-    t = np.ascontiguousarray(range, f32).reshape(-1)
-    d = np.ascontiguousarray(dirs, f32).reshape(-1, 3)
-    got = t > 0
-    p = t[got, None] * d[got]
-    out = np.zeros((int(got.sum()), 4), f32)
-    out[:, 0], out[:, 1], out[:, 2] = p[:, 2], -p[:, 0], -p[:, 1]
-    if rgb is not None:
-        c = np.ascontiguousarray(rgb, np.uint8).reshape(-1, 3)[got].astype(f32)
-        out[:, 3] = ((f32(0.299) * c[:, 0] + f32(0.587) * c[:, 1]) + f32(0.114) * c[:, 2]) / f32(255.0)
-    return out
 
 
 class SmRay(C.Structure):
@@ -213,44 +126,6 @@ class SmRaysStats(C.Structure):
 RAYS_MAX = 1 << 24
 
 
-def rays_params(**over) -> SmRaysParams:
-    """sm_default_rays_params with fields replaced: cell_mm, origin (three floats), min_conf"""
-    p = SmRaysParams()
-    load().sm_default_rays_params(C.byref(p))
-    for k, v in over.items():
-        if not hasattr(p, k):
-            raise KeyError(k)
-        setattr(p, k, (C.c_float * 3)(*[float(x) for x in v]) if k == "origin" else v)
-    return p
-
-
-def lidar_rays(sensor, poses16) -> np.ndarray:
-    """The beams of a sweep as rays for SurfelMap.cast_rays: float32[n_el * n_az][8] = (origin, t_min, dir, t_max), row-major over
-    the sensor's grid.  poses16: one sensor->world pose (float32[16] column-major or 4x4), or n_az of them, one per column -- the
-    sweep of a vehicle that moves while the sensor turns.  The origin is the pose's translation, the direction R * d of
-    lidar_directions' table, computed in double ((R0 dx + R1 dy) + R2 dz, terms with a zero coefficient left out) and rounded
-    once; t_min / t_max are the sensor's range limits.  Needs no context."""
-    d = lidar_directions(sensor).astype(np.float64)                       # [n_el][n_az][3]
-    n_el, n_az = d.shape[0], d.shape[1]
-    P = np.asarray(poses16, np.float32)
-    if P.ndim >= 2 and P.shape[-2:] == (4, 4):
-        P = np.swapaxes(P, -1, -2)                                        # (numpy row/col indexing -> column-major)
-    P = np.ascontiguousarray(P).reshape(-1, 16)
-    if P.shape[0] not in (1, n_az):
-        raise ValueError("poses16: one pose, or one per column (n_az)")
-    P = np.broadcast_to(P, (n_az, 16))
-    R = P.astype(np.float64).reshape(n_az, 4, 4)[:, :3, :3]               # R[j][c][r]: column c, row r of pose j
-    # a term whose coefficient is 0 is left out (-0.0 is the sum's neutral element), so an identity rotation returns d bit for bit
-    term = [np.where(R[None, :, c, :] != 0.0, R[None, :, c, :] * d[:, :, None, c], -0.0) for c in range(3)]
-    dirs = (term[0] + term[1]) + term[2]
-    rays = np.zeros((n_el, n_az, 8), np.float32)
-    rays[:, :, 0:3] = P[None, :, 12:15]
-    rays[:, :, 3] = np.float32(sensor.min_range)
-    rays[:, :, 4:7] = dirs.astype(np.float32)
-    rays[:, :, 7] = np.float32(sensor.max_range)
-    return rays.reshape(n_el * n_az, 8)
-
-
 class SmSceneActor(C.Structure):
     _fields_ = [("path", C.c_char_p), ("poses12", C.POINTER(C.c_float)), ("present", C.POINTER(C.c_uint8))]
 
@@ -267,47 +142,6 @@ class SmSceneStats(C.Structure):
 
 SCENE_MAX_ACTORS, SCENE_MAX_RECORDS = 4096, 1 << 22
 
-
-def scene_poses12(poses) -> np.ndarray:
-    """actor->world poses as the scene calls take them, float32[V][12] ROW-major 3x4 [R|t]: from float32[V][12] as they are, or
-    from [V][4][4] matrices (their top three rows)"""
-    p = np.asarray(poses, np.float32)
-    if p.ndim == 3 and p.shape[1:] == (4, 4):
-        p = p[:, :3, :]
-    return np.ascontiguousarray(p.reshape(-1, 12))
-
-
-def scene(actors, n_views=None) -> SmScene:
-    """a scene's actors: a list of (path, poses[, present]) -- a map file in the actor's own frame, its poses per view
-    (scene_poses12 forms), optionally uint8[V], 0 = not in that view.  n_views: what every actor's arrays must hold (None: not
-    checked).  Keeps the strings and arrays alive."""
-    keep, arr = [], (SmSceneActor * max(len(actors), 1))()
-    for j, a in enumerate(actors):
-        path, poses = os.fsencode(a[0]), scene_poses12(a[1])
-        present = None if len(a) < 3 or a[2] is None else np.ascontiguousarray(a[2], np.uint8).reshape(-1)
-        if n_views is not None and (len(poses) != n_views or (present is not None and len(present) != n_views)):
-            raise ValueError(f"actor {j}: {len(poses)} poses for {n_views} views")
-        arr[j].path = path
-        arr[j].poses12 = poses.ctypes.data_as(C.POINTER(C.c_float))
-        arr[j].present = None if present is None else present.ctypes.data_as(C.POINTER(C.c_uint8))
-        keep.append((path, poses, present))
-    sc = SmScene(C.cast(arr, C.POINTER(SmSceneActor)), len(actors))
-    sc._keep = (keep, arr)
-    return sc
-
-
-def scene_place_rows(pose, rows) -> np.ndarray:
-    """sm_scene_place_rows: float32[N][12] records under one actor->world pose (float32[12] row-major 3x4, or 4x4) by
-    sm_warp_by_time's row rule, on the host"""
-    pose = scene_poses12(np.asarray(pose, np.float32).reshape((1, 4, 4) if np.size(pose) == 16 else (1, 12)))
-    rows = np.ascontiguousarray(rows, np.float32).reshape(-1, 12)
-    out = np.empty_like(rows)
-    rc = load().sm_scene_place_rows(_ptr(pose), _ptr(rows), len(rows), _ptr(out))
-    if rc:
-        raise SurfelMapError("sm_scene_place_rows", rc, load().sm_last_error().decode())
-    return out
-
-
 SM_TRACK_OK, SM_TRACK_LOST, SM_TRACK_DEGENERATE, SM_TRACK_NO_MODEL = 0, 1, 2, 3
 TRACK_STATUS = {SM_TRACK_OK: "OK", SM_TRACK_LOST: "LOST", SM_TRACK_DEGENERATE: "DEGENERATE", SM_TRACK_NO_MODEL: "NO_MODEL"}
 
@@ -322,17 +156,6 @@ class SmTrackInfo(C.Structure):
                 ("guess", C.c_float * 16)]
 
 
-def track_params(**over) -> SmTrackParams:
-    """sm_default_track_params with fields overridden (max_iters, dist_thresh, angle_thresh, min_inliers, pixel_stride)"""
-    p = SmTrackParams()
-    load().sm_default_track_params(C.byref(p))
-    for k, v in over.items():
-        if not hasattr(p, k):
-            raise KeyError(k)
-        setattr(p, k, v)
-    return p
-
-
 class SmTrackRgbParams(C.Structure):
     _fields_ = [("levels", C.c_int32), ("iters", C.c_int32 * 6), ("rgb_weight", C.c_float), ("rgb_max_residual", C.c_float)]
 
@@ -342,35 +165,8 @@ class SmTrackRgbInfo(C.Structure):
                 ("level_iterations", C.c_int32 * 6)]
 
 
-def track_rgb_params(**over) -> SmTrackRgbParams:
-    """sm_default_track_rgb_params with fields overridden (levels, iters: a sequence whose index is the level, the levels it
-    does not name keep their default; rgb_weight, rgb_max_residual)"""
-    p = SmTrackRgbParams()
-    load().sm_default_track_rgb_params(C.byref(p))
-    for k, v in over.items():
-        if not hasattr(p, k):
-            raise KeyError(k)
-        if k == "iters":
-            for l, n in enumerate(v):
-                p.iters[l] = int(n)
-        else:
-            setattr(p, k, v)
-    return p
-
-
 class SmRetireParams(C.Structure):
     _fields_ = [("min_age", C.c_int32), ("min_distance", C.c_float)]
-
-
-def retire_params(cfg, **over) -> SmRetireParams:
-    """sm_default_retire_params of a config (min_age = time_delta, min_distance = 1.5 * far_clip) with fields overridden"""
-    p = SmRetireParams()
-    load().sm_default_retire_params(C.byref(cfg), C.byref(p))
-    for k, v in over.items():
-        if not hasattr(p, k):
-            raise KeyError(k)
-        setattr(p, k, v)
-    return p
 
 
 SM_RECALL_MOVE, SM_RECALL_COPY, SM_RECALL_COUNT = 0, 1, 2
@@ -385,17 +181,6 @@ class SmRecallStats(C.Structure):
     _fields_ = [("files_listed", C.c_uint32), ("files_skipped", C.c_uint32), ("files_read", C.c_uint32), ("files_rewritten", C.c_uint32),
                 ("records_read", C.c_uint64), ("recalled", C.c_uint64), ("chunks", C.c_uint32), ("read_ms", C.c_float),
                 ("copy_ms", C.c_float), ("device_ms", C.c_float), ("write_ms", C.c_float), ("total_ms", C.c_float)]
-
-
-def recall_params(cfg, **over) -> SmRecallParams:
-    """sm_default_recall_params of a config (radius = 1.5 * far_clip) with fields overridden"""
-    p = SmRecallParams()
-    load().sm_default_recall_params(C.byref(cfg), C.byref(p))
-    for k, v in over.items():
-        if not hasattr(p, k):
-            raise KeyError(k)
-        setattr(p, k, v)
-    return p
 
 
 class SmWarpStats(C.Structure):
@@ -418,17 +203,6 @@ class SmLoopInfo(C.Structure):
     _fields_ = [("status", C.c_int32), ("track", SmTrackInfo), ("D", C.c_float * 16), ("t_a", C.c_int32), ("t_b", C.c_int32)]
 
 
-def loop_params(cfg, **over) -> SmLoopParams:
-    """sm_default_loop_params of a config (min_age = time_delta; 0.02 m, 0.05 deg; 2 m, 10 deg) with fields overridden"""
-    p = SmLoopParams()
-    load().sm_default_loop_params(C.byref(cfg), C.byref(p))
-    for k, v in over.items():
-        if not hasattr(p, k):
-            raise KeyError(k)
-        setattr(p, k, v)
-    return p
-
-
 class SmAutoLoopParams(C.Structure):
     _fields_ = [("every", C.c_int32), ("rest", C.c_int32), ("min_old", C.c_uint32), ("loop", SmLoopParams)]
 
@@ -437,21 +211,6 @@ class SmAutoLoopStats(C.Structure):
     _fields_ = [("checked", C.c_uint32), ("attempts", C.c_uint32), ("closed", C.c_uint32), ("none", C.c_uint32),
                 ("rejected", C.c_uint32), ("failed", C.c_uint32), ("no_old_map", C.c_uint32), ("last_census", C.c_uint32),
                 ("last", SmLoopInfo)]
-
-
-def auto_loop_params(cfg, **over) -> SmAutoLoopParams:
-    """sm_default_auto_loop_params of a config (every 1, rest 10, min_old 1000, loop = loop_params(cfg)) with fields overridden;
-    the fields of sm_loop_params are given by their own names (min_age, max_trans, ...)"""
-    p = SmAutoLoopParams()
-    load().sm_default_auto_loop_params(C.byref(cfg), C.byref(p))
-    for k, v in over.items():
-        if k != "loop" and hasattr(p, k):
-            setattr(p, k, v)
-        elif hasattr(p.loop, k):
-            setattr(p.loop, k, v)
-        else:
-            raise KeyError(k)
-    return p
 
 
 class SmSearchParams(C.Structure):
@@ -481,41 +240,20 @@ FERN_MAX_KEYFRAMES = 1 << 20
 FERN_DTYPE = np.dtype([(n, np.uint16) for n, _ in SmFern._fields_])
 
 
-def fern_params(cfg, **over) -> SmFernParams:
-    """sm_default_fern_params (512 ferns, cell 8, seed 1, the config's near and far clip in millimetres) with fields overridden"""
-    p = SmFernParams()
-    load().sm_default_fern_params(C.byref(cfg), C.byref(p))
-    for k, v in over.items():
-        if not hasattr(p, k):
-            raise KeyError(k)
-        setattr(p, k, v)
-    return p
+class SmAutoPlaceParams(C.Structure):
+    _fields_ = [("every", C.c_int32), ("rest", C.c_int32), ("add_above", C.c_float), ("match_below", C.c_float), ("min_jump", C.c_float),
+                ("loop", SmLoopParams), ("search", SmSearchParams)]
 
 
-def fern_table(params, width, height) -> np.ndarray:
-    """sm_fern_table: the ferns of `params` for an image size, a structured array (x, y, tr, tg, tb, td; uint16).  Host only."""
-    L = load()
-    out = np.zeros(max(int(params.n_ferns), 0), FERN_DTYPE)
-    rc = L.sm_fern_table(C.byref(params), int(width), int(height), _ptr(out))
-    if rc != SM_OK:
-        raise SurfelMapError("sm_fern_table", rc, L.sm_last_error().decode())
-    return out
+class SmAutoPlaceStats(C.Structure):
+    _fields_ = [("encoded", C.c_uint32), ("added", C.c_uint32), ("matched", C.c_uint32), ("attempts", C.c_uint32), ("closed", C.c_uint32),
+                ("none", C.c_uint32), ("rejected", C.c_uint32), ("failed", C.c_uint32), ("no_old_map", C.c_uint32), ("last_k", C.c_int32),
+                ("last_dis", C.c_uint32), ("last", SmLoopInfo)]
 
 
 class SmStereoParams(C.Structure):
     _fields_ = [("max_disp", C.c_int32), ("paths", C.c_int32), ("p1", C.c_int32), ("p2", C.c_int32), ("uniqueness", C.c_int32),
                 ("lr_max_diff", C.c_int32), ("baseline", C.c_float)]
-
-
-def stereo_params(cfg, **over) -> SmStereoParams:
-    """sm_default_stereo_params (D 128, 8 paths, p1 7, p2 86, uniqueness 5 %, lr_max_diff 1, baseline 0.54 m) with fields overridden"""
-    p = SmStereoParams()
-    load().sm_default_stereo_params(C.byref(cfg), C.byref(p))
-    for k, v in over.items():
-        if not hasattr(p, k):
-            raise KeyError(k)
-        setattr(p, k, v)
-    return p
 
 
 class SmFillParams(C.Structure):
@@ -528,26 +266,6 @@ class SmFillStats(C.Structure):
                 ("launches", C.c_uint32), ("device_ms", C.c_float)]
 
 
-def fill_params(**over) -> SmFillParams:
-    """sm_default_fill_params (levels 3, depth_tol_256 13, through_count 6, prefer_far 1, min_cover_256 64) with fields overridden"""
-    p = SmFillParams()
-    load().sm_default_fill_params(C.byref(p))
-    for k, v in over.items():
-        if not hasattr(p, k):
-            raise KeyError(k)
-        setattr(p, k, v)
-    return p
-
-
-def _fill_arg(fill):
-    """what the entry points' `fill` accepts: None (none), True (the defaults), a dict of overrides, or fill_params(...)"""
-    if fill is None or fill is False:
-        return None
-    if fill is True:
-        return fill_params()
-    return fill if isinstance(fill, SmFillParams) else fill_params(**fill)
-
-
 class SmBlendParams(C.Structure):
     _fields_ = [("depth_tol_256", C.c_int32), ("falloff", C.c_int32)]
 
@@ -555,26 +273,6 @@ class SmBlendParams(C.Structure):
 class SmBlendStats(C.Structure):
     _fields_ = [("drawn", C.c_uint64), ("contributions", C.c_uint64), ("changed", C.c_uint64), ("launches", C.c_uint32),
                 ("device_ms", C.c_float)]
-
-
-def blend_params(**over) -> SmBlendParams:
-    """sm_default_blend_params (depth_tol_256 13, falloff 2 = quadratic) with fields overridden"""
-    p = SmBlendParams()
-    load().sm_default_blend_params(C.byref(p))
-    for k, v in over.items():
-        if not hasattr(p, k):
-            raise KeyError(k)
-        setattr(p, k, v)
-    return p
-
-
-def _blend_arg(blend):
-    """what the entry points' `blend` accepts: None (none), True (the defaults), a dict of overrides, or blend_params(...)"""
-    if blend is None or blend is False:
-        return None
-    if blend is True:
-        return blend_params()
-    return blend if isinstance(blend, SmBlendParams) else blend_params(**blend)
 
 
 class SmSimplifyParams(C.Structure):
@@ -587,26 +285,6 @@ class SmSimplifyStats(C.Structure):
                 ("read_ms", C.c_float), ("total_ms", C.c_float)]
 
 
-def default_simplify_params() -> SmSimplifyParams:
-    """sm_default_simplify_params: voxel_mm 50, split_normals 1, origin (0, 0, 0), max_cells 1 << 26"""
-    p = SmSimplifyParams()
-    load().sm_default_simplify_params(C.byref(p))
-    return p
-
-
-def simplify_params(**over) -> SmSimplifyParams:
-    """default_simplify_params() with fields overridden; origin takes a sequence of three"""
-    p = default_simplify_params()
-    for k, v in over.items():
-        if not hasattr(p, k):
-            raise KeyError(k)
-        if k == "origin":
-            p.origin[:] = [float(x) for x in v]
-        else:
-            setattr(p, k, v)
-    return p
-
-
 class SmTileParams(C.Structure):
     _fields_ = [("cell_mm", C.c_int32), ("tile_shift", C.c_int32), ("origin", C.c_float * 3), ("max_file_records", C.c_uint32),
                 ("max_tiles", C.c_uint32)]
@@ -617,26 +295,6 @@ class SmTileStats(C.Structure):
                 ("files_written", C.c_uint32), ("readings", C.c_uint32), ("chunks", C.c_uint32), ("launches", C.c_uint32),
                 ("sort_passes", C.c_uint32), ("device_ms", C.c_float), ("sort_ms", C.c_float), ("read_ms", C.c_float), ("write_ms", C.c_float),
                 ("total_ms", C.c_float)]
-
-
-def default_tile_params() -> SmTileParams:
-    """sm_default_tile_params: cell_mm 200, tile_shift 7, origin (0, 0, 0), max_file_records 1 << 20, max_tiles 1 << 20"""
-    p = SmTileParams()
-    load().sm_default_tile_params(C.byref(p))
-    return p
-
-
-def tile_params(**over) -> SmTileParams:
-    """default_tile_params() with fields overridden; origin takes a sequence of three"""
-    p = default_tile_params()
-    for k, v in over.items():
-        if not hasattr(p, k):
-            raise KeyError(k)
-        if k == "origin":
-            p.origin[:] = [float(x) for x in v]
-        else:
-            setattr(p, k, v)
-    return p
 
 
 SM_SEGMENT_LOOSE, SM_SEGMENT_SMALL, SM_SEGMENT_SKIPPED = 0xFFFFFFFE, 0xFFFFFFFD, 0xFFFFFFFC
@@ -668,55 +326,6 @@ SEGMENT_COMPONENT = np.dtype([("first", "<u4"), ("records", "<u4"), ("cells", "<
                               ("sum_cell", "<u8", 3)])
 assert SEGMENT_COMPONENT.itemsize == C.sizeof(SmSegmentComponent) == 64
 
-
-def default_segment_params() -> SmSegmentParams:
-    """sm_default_segment_params: voxel_mm 200, connectivity 26, by_class 1, every class, min_records 1, write_mask 1 (the records of
-    numbered components), max_cells 1 << 24, origin (0, 0, 0)"""
-    p = SmSegmentParams()
-    load().sm_default_segment_params(C.byref(p))
-    return p
-
-
-def segment_params(**over) -> SmSegmentParams:
-    """default_segment_params() with fields overridden; origin takes a sequence of three, class_mask eight words or an iterable of
-    the classes that take part (`classes=` does the latter too)"""
-    p = default_segment_params()
-    for k, v in over.items():
-        if k == "classes":
-            p.class_mask[:] = segment_class_mask(v)
-        elif not hasattr(p, k):
-            raise KeyError(k)
-        elif k == "origin":
-            p.origin[:] = [float(x) for x in v]
-        elif k == "class_mask":
-            p.class_mask[:] = [int(x) for x in v]
-        else:
-            setattr(p, k, v)
-    return p
-
-
-def segment_class_mask(classes) -> list:
-    """the eight words of class_mask with the bits of `classes` (0..255) set"""
-    words = [0] * 8
-    for c in classes:
-        if not 0 <= int(c) <= 255:
-            raise ValueError(c)
-        words[int(c) >> 5] |= 1 << (int(c) & 31)
-    return words
-
-
-def segment_boxes(components, voxel_mm=200, origin=(0.0, 0.0, 0.0)):
-    """(lo, hi, centroid), float64[n, 3] each, in metres, of the rows of a component table: the box of a component's cells -- from
-    the low face of cell_lo to the high face of cell_hi -- and the mean over its records of their cells' centres"""
-    c = np.asarray(components, SEGMENT_COMPONENT).reshape(-1)
-    edge = ((int(voxel_mm) * 65536 + 500) // 1000) / 65536.0
-    o = np.asarray([np.float32(v) for v in origin], np.float64)
-    lo = o + c["cell_lo"].astype(np.float64) * edge
-    hi = o + (c["cell_hi"].astype(np.float64) + 1.0) * edge
-    mean = c["sum_cell"].astype(np.float64) / np.maximum(c["records"], 1).astype(np.float64)[:, None] - 65536.0 + 0.5
-    return lo, hi, o + mean * edge
-
-
 MESH_KINDS = ("USED", "SKIPPED", "LOOSE", "OUTSIDE")                     # the entries of a mesh's info.counts
 
 
@@ -743,32 +352,6 @@ class SmMeshStats(C.Structure):
 MESH_VERTEX = np.dtype([("pos", "<f4", 3), ("normal", "<f4", 3), ("colour", "<u4")])
 assert MESH_VERTEX.itemsize == C.sizeof(SmMeshVertex) == 28
 
-
-def default_mesh_params() -> SmMeshParams:
-    """sm_default_mesh_params: voxel_mm 100, reach 2, min_records 1, every class, max_cells 1 << 24, origin (0, 0, 0)"""
-    p = SmMeshParams()
-    load().sm_default_mesh_params(C.byref(p))
-    return p
-
-
-def mesh_params(**over) -> SmMeshParams:
-    """default_mesh_params() with fields overridden; origin takes a sequence of three, class_mask eight words or an iterable of the
-    classes that take part (`classes=` does the latter too)"""
-    p = default_mesh_params()
-    for k, v in over.items():
-        if k == "classes":
-            p.class_mask[:] = segment_class_mask(v)
-        elif not hasattr(p, k):
-            raise KeyError(k)
-        elif k == "origin":
-            p.origin[:] = [float(x) for x in v]
-        elif k == "class_mask":
-            p.class_mask[:] = [int(x) for x in v]
-        else:
-            setattr(p, k, v)
-    return p
-
-
 GROUND_KINDS = ("GROUND", "OBSTACLE", "IGNORED", "UNREFERENCED", "OUTSIDE", "LOOSE")   # the entries of a ground map's info.counts
 GROUND_STATES = ("UNKNOWN", "FREE", "OBSTACLE", "STEP")                  # the values of its `state` plane, the entries of info.cells
 GROUND_NONE = -(1 << 31)                                                 # SM_GROUND_NONE: `ground` of a cell without ground
@@ -790,68 +373,6 @@ class SmGroundStats(C.Structure):
     _fields_ = [("chunks", C.c_uint32), ("launches", C.c_uint32), ("files_skipped", C.c_uint32), ("read_ms", C.c_float), ("ground_ms", C.c_float),
                 ("fill_ms", C.c_float), ("accumulate_ms", C.c_float), ("state_ms", C.c_float), ("clear_ms", C.c_float), ("copy_ms", C.c_float),
                 ("total_ms", C.c_float)]
-
-
-def default_ground_params() -> SmGroundParams:
-    """sm_default_ground_params: cell_mm 100, up 3 (-y), origin (0, 0, 0), 256 x 256 cells, min_up 11585 (45 degrees), every class,
-    band_mm 200, the body band 150..2000 mm, min_obstacle 2, fill_cells 3, step_mm 150, reach_cells 32, unknown_blocks 0, normal_sign -1
-    (normals that point into the surface, as the fusion stores them)"""
-    p = SmGroundParams()
-    load().sm_default_ground_params(C.byref(p))
-    return p
-
-
-def ground_params(**over) -> SmGroundParams:
-    """default_ground_params() with fields overridden; origin takes a sequence of three, ground_mask eight words or an iterable of
-    the classes that may be ground (`classes=` does the latter too)"""
-    p = default_ground_params()
-    for k, v in over.items():
-        if k == "classes":
-            p.ground_mask[:] = segment_class_mask(v)
-        elif not hasattr(p, k):
-            raise KeyError(k)
-        elif k == "origin":
-            p.origin[:] = [float(x) for x in v]
-        elif k == "ground_mask":
-            p.ground_mask[:] = [int(x) for x in v]
-        else:
-            setattr(p, k, v)
-    return p
-
-
-_PLY_PROPERTIES = ["property float x", "property float y", "property float z", "property float nx", "property float ny", "property float nz",
-                   "property uchar red", "property uchar green", "property uchar blue", "property uchar class"]
-
-
-def read_ply(path):
-    """(vertices: MESH_VERTEX[n], faces: uint32[m, 3]) of a file sm_mesh_maps wrote -- that layout alone: binary little-endian, per
-    vertex x y z nx ny nz as float and red green blue class as uchar, per face `list uchar int vertex_indices` of three.  The colour
-    word is put together again: blue, green, red in bytes 0..2, the class in byte 3."""
-    with open(path, "rb") as f:
-        data = f.read()
-    end = data.find(b"end_header\n")
-    if end < 0:
-        raise ValueError(f"{path}: no PLY header")
-    lines = data[:end].decode("ascii").split("\n")
-    body = data[end + len(b"end_header\n"):]
-    if lines[:2] != ["ply", "format binary_little_endian 1.0"]:
-        raise ValueError(f"{path}: not a binary little-endian PLY")
-    lines = [l for l in lines[2:] if l and not l.startswith("comment")]
-    if (len(lines) != 13 or not lines[0].startswith("element vertex ") or lines[1:11] != _PLY_PROPERTIES or not lines[11].startswith("element face ")
-            or lines[12] != "property list uchar int vertex_indices"):
-        raise ValueError(f"{path}: not the layout sm_mesh_maps writes")
-    nv, nf = int(lines[0].split()[2]), int(lines[11].split()[2])
-    if len(body) != nv * 28 + nf * 13:
-        raise ValueError(f"{path}: {len(body)} bytes after the header, {nv} vertices and {nf} faces need {nv * 28 + nf * 13}")
-    raw = np.frombuffer(body, np.dtype([("pos", "<f4", 3), ("normal", "<f4", 3), ("rgbc", "u1", 4)]), nv)
-    vertices = np.zeros(nv, MESH_VERTEX)
-    vertices["pos"], vertices["normal"] = raw["pos"], raw["normal"]
-    c = raw["rgbc"].astype(np.uint32)
-    vertices["colour"] = c[:, 3] << 24 | c[:, 0] << 16 | c[:, 1] << 8 | c[:, 2]
-    rows = np.frombuffer(body, np.dtype([("n", "u1"), ("v", "<i4", 3)]), nf, nv * 28)
-    if nf and (rows["n"] != 3).any():
-        raise ValueError(f"{path}: a face that is no triangle")
-    return vertices, rows["v"].view(np.uint32).copy().reshape(-1, 3)
 
 
 SM_REGISTER_OK, SM_REGISTER_LOST, SM_REGISTER_DEGENERATE, SM_REGISTER_NO_TARGET, SM_REGISTER_NO_SOURCE = 0, 1, 2, 3, 4
@@ -876,27 +397,6 @@ class SmRegisterStats(C.Structure):
                 ("read_ms", C.c_float), ("table_ms", C.c_float), ("iterate_ms", C.c_float), ("total_ms", C.c_float)]
 
 
-def default_register_params() -> SmRegisterParams:
-    """sm_default_register_params: voxel_mm 200, levels 3, max_iters 20, min_inliers 1000, angle_thresh 30, reach_cells 1, stride 0
-    (from max_samples = 1 << 22), max_cells 1 << 24, origin and pivot (0, 0, 0)"""
-    p = SmRegisterParams()
-    load().sm_default_register_params(C.byref(p))
-    return p
-
-
-def register_params(**over) -> SmRegisterParams:
-    """default_register_params() with fields overridden; origin and pivot take a sequence of three"""
-    p = default_register_params()
-    for k, v in over.items():
-        if not hasattr(p, k):
-            raise KeyError(k)
-        if k in ("origin", "pivot"):
-            getattr(p, k)[:] = [float(x) for x in v]
-        else:
-            setattr(p, k, v)
-    return p
-
-
 SM_COMPARE_SUPPORTED, SM_COMPARE_CHANGED, SM_COMPARE_OUTSIDE, SM_COMPARE_LOOSE = 0, 1, 2, 3
 COMPARE_LABEL = {SM_COMPARE_SUPPORTED: "SUPPORTED", SM_COMPARE_CHANGED: "CHANGED", SM_COMPARE_OUTSIDE: "OUTSIDE", SM_COMPARE_LOOSE: "LOOSE"}
 
@@ -917,147 +417,203 @@ class SmCompareStats(C.Structure):
                 ("classify_ms", C.c_float), ("write_ms", C.c_float), ("total_ms", C.c_float)]
 
 
-def _map_records(path) -> int:
-    """the records a well-formed map file of this length holds (12 bytes of header, 48 per record); 0 where there is no file --
-    the call that reads it reports that"""
-    try:
-        return max(0, (os.path.getsize(path) - 12) // 48)
-    except OSError:
-        return 0
-
-
-def default_compare_params() -> SmCompareParams:
-    """sm_default_compare_params: voxel_mm 100, cover_shift 3, reach_cells 2, plane_mm 50, angle_thresh 30, match_class 0,
-    write_mask 2 (the CHANGED records), max_cells 1 << 24, origin (0, 0, 0)"""
-    p = SmCompareParams()
-    load().sm_default_compare_params(C.byref(p))
-    return p
-
-
-def compare_params(**over) -> SmCompareParams:
-    """default_compare_params() with fields overridden; origin takes a sequence of three"""
-    p = default_compare_params()
-    for k, v in over.items():
-        if not hasattr(p, k):
-            raise KeyError(k)
-        if k == "origin":
-            p.origin[:] = [float(x) for x in v]
-        else:
-            setattr(p, k, v)
-    return p
-
-
-def search_params(**over) -> SmSearchParams:
-    """sm_default_search_params (2 levels; +-2 m in x and z at 0.25 m, +-3 deg about y at 0.5 deg; refine 4, stride0 8, top_k 4,
-    colour_thresh 0.1) with fields overridden; the four per-axis fields take a sequence of three"""
-    p = SmSearchParams()
-    load().sm_default_search_params(C.byref(p))
-    for k, v in over.items():
-        if not hasattr(p, k):
-            raise KeyError(k)
-        if k in ("trans_half", "trans_step", "rot_half_deg", "rot_step_deg"):
-            for a, x in enumerate(v):
-                getattr(p, k)[a] = float(x)
-        else:
-            setattr(p, k, v)
-    return p
-
-
-class SmAutoPlaceParams(C.Structure):
-    _fields_ = [("every", C.c_int32), ("rest", C.c_int32), ("add_above", C.c_float), ("match_below", C.c_float), ("min_jump", C.c_float),
-                ("loop", SmLoopParams), ("search", SmSearchParams)]
-
-
-class SmAutoPlaceStats(C.Structure):
-    _fields_ = [("encoded", C.c_uint32), ("added", C.c_uint32), ("matched", C.c_uint32), ("attempts", C.c_uint32), ("closed", C.c_uint32),
-                ("none", C.c_uint32), ("rejected", C.c_uint32), ("failed", C.c_uint32), ("no_old_map", C.c_uint32), ("last_k", C.c_int32),
-                ("last_dis", C.c_uint32), ("last", SmLoopInfo)]
-
-
-def auto_place_params(cfg, **over) -> SmAutoPlaceParams:
-    """sm_default_auto_place_params (every 1, rest 10, add_above 0.2, match_below 0.3, min_jump 2 m, loop = loop_params(cfg) with
-    max_trans 50 and max_rot_deg 45, search = search_params()) with fields overridden: a field of sm_loop_params by its own name,
-    search as a dict of search_params() overrides"""
-    p = SmAutoPlaceParams()
-    load().sm_default_auto_place_params(C.byref(cfg), C.byref(p))
-    for k, v in over.items():
-        if k == "search":
-            p.search = search_params(**dict(v))
-        elif hasattr(p.loop, k):
-            setattr(p.loop, k, v)
-        elif hasattr(p, k) and k != "loop":
-            setattr(p, k, v)
-        else:
-            raise KeyError(k)
-    return p
-
-
-def _search_arg(search):
-    """close_loop(search=...) / set_auto_loop(search=...): None or False = no search, True = the defaults, a dict = overrides"""
-    if search is None or search is False:
-        return None
-    return search_params(**({} if search is True else dict(search)))
-
-
 INT32_MIN, INT32_MAX = -2 ** 31, 2 ** 31 - 1
 
+# ---- the prototypes: entry point -> (restype, argtypes), in the header's order.  load() gives every function of the library its row,
+# so a NEW ENTRY POINT takes one row here and nothing else; a row reads like the declaration.  An entry point without a row does
+# not exist for this module (tests/test_capi_abi.py holds the table against the header: names, parameter counts, return kinds).
+P = C.POINTER
+vp, cs, sz, ci, cf, i32, u32 = C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.c_float, C.c_int32, C.c_uint32
+vpp, i32p, u32p, u64p, cfp = P(vp), P(i32), P(u32), P(C.c_uint64), P(cf)
+_VIEW = [ci, ci, cf, cf, cf, cf]                                        # w, h, fx, fy, cx, cy
+_CFG, _SRC, _TRACK, _RGB, _LOOP, _SEARCH = P(SmConfig), P(SmMapSource), P(SmTrackParams), P(SmTrackRgbParams), P(SmLoopParams), P(SmSearchParams)
+_SENSOR, _FILL, _BLEND, _SCENE = P(SmLidarSensor), P(SmFillParams), P(SmBlendParams), P(SmScene)
 
-def _track_info_dict(info, rinfo=None, anchor=None) -> dict:
-    """SmTrackInfo as the trackers' info dict; rinfo (SmTrackRgbInfo) and anchor (c_float) add their keys when given"""
-    d = dict(status=TRACK_STATUS.get(info.status, str(info.status)), status_code=int(info.status), iterations=int(info.iterations),
-             inliers=int(info.inliers), rmse=float(info.rmse), guess=np.array(info.guess[:], np.float32).reshape(4, 4).T.copy())
-    if rinfo is not None:
-        d.update(rgb_inliers=int(rinfo.rgb_inliers), rgb_rmse=float(rinfo.rgb_rmse), pivot_ratio=float(rinfo.pivot_ratio),
-                 level_iterations=[int(x) for x in rinfo.level_iterations])
-    if anchor is not None:
-        d["anchor_time"] = float(anchor.value)
-    return d
+PROTOTYPES = {
+    "sm_api_version": (ci, []),
+    "sm_last_error": (cs, []),
+    "sm_default_config": (ci, [_CFG] + _VIEW),
+    "sm_create": (vp, [_CFG]),
+    "sm_destroy": (None, [vp]),
+    "sm_process_frame": (ci, [vp, vp, vp, vp, vp]),
+    "sm_process_frame_device": (ci, [vp, vp, vp, vp, vp]),
+    "sm_process_frame_async": (ci, [vp, vp, vp, vp, vp]),
+    "sm_inputs_consumed": (ci, [vp]),
+    "sm_host_alloc": (vp, [vp, sz]),
+    "sm_host_alloc_frame": (ci, [vp, vpp, vpp, vpp]),
+    "sm_host_free": (ci, [vp, vp]),
+    "sm_debug_slow_frames": (ci, [vp, u32p]),
+    "sm_debug_squeezes": (ci, [vp, u32p, u32p]),
+    "sm_sync": (ci, [vp]),
+    "sm_clean_points": (ci, [vp, vp, vp, vp]),
+    "sm_clean_points_ex": (ci, [vp, vp, vp, vp, ci]),
+    "sm_clean_points_cb": (ci, [vp, vp, vp, vp, ci, CAP_FN, vp]),
+    "sm_reset": (ci, [vp]),
+    "sm_get_counts": (ci, [vp, P(SmCounts)]),
+    "sm_download_model_aos": (ci, [vp, vp, u32, u32p]),
+    "sm_upload_model_aos": (ci, [vp, vp, u32]),
+    "sm_save_map": (ci, [vp, cs, i32, i32]),
+    "sm_load_map": (ci, [vp, cs, i32p, i32p]),
+    "sm_download_index_map": (ci, [vp, vp, vp, vp, vp]),
+    "sm_download_raw_cloud": (ci, [vp, vp, u32, u32p]),
+    "sm_download_depth": (ci, [vp, ci, vp]),
+    "sm_render_image": (ci, [vp, vp] + _VIEW + [vp, vp]),
+    "sm_render_model": (ci, [vp, P(SmModelView), vp, vp, vp]),
+    "sm_render_model_device": (ci, [vp, P(SmModelView), vp, vp, vp]),
+    "sm_render_image_maps": (ci, [vp, _SRC, vp, u32] + _VIEW + [vp, vp]),
+    "sm_render_model_maps": (ci, [vp, _SRC, P(SmModelView), u32, vp, vp, vp]),
+    "sm_render_maps_stats": (ci, [vp, P(SmMapsStats)]),
+    "sm_set_frame": (ci, [vp, vp, vp, vp]),
+    "sm_set_tick": (ci, [vp, i32]),
+    "sm_stage_conflict": (ci, [vp, vp, cf, cf, cf, ci]),
+    "sm_stage_cull": (ci, [vp]),
+    "sm_stage_splat": (ci, [vp, vp, i32, cf, i32]),
+    "sm_stage_associate_fuse": (ci, [vp, vp, i32, cf, cf]),
+    "sm_stage_timings": (ci, [vp, P(SmTimings)]),
+    "sm_read_frame_log": (ci, [vp, vp, u32, u32p]),
+    "sm_device_alloc": (vp, [vp, sz]),
+    "sm_device_free": (ci, [vp, vp]),
+    "sm_device_upload": (ci, [vp, vp, vp, sz]),
+    "sm_export_model_device": (ci, [vp, vpp, u32p]),
+    "sm_append_model_aos_device": (ci, [vp, vp, u32]),
+    "sm_device_download": (ci, [vp, vp, vp, sz]),
+    "sm_shard_stream_configure": (ci, [vp, ci, ci]),
+    "sm_shard_set_collective": (ci, [vp, COLLECTIVE_FN, vp]),
+    "sm_shard_rccl_unique_id": (ci, [vp]),
+    "sm_shard_rccl_init": (ci, [vp, vp]),
+    "sm_shard_rccl_finalize": (ci, [vp]),
+    "sm_shard_rccl_nranks": (ci, [vp]),
+    "sm_shard_frame_device": (ci, [vp, vp, vp, vp, vp]),
+    "sm_shard_frame": (ci, [vp, vp, vp, vp, vp]),
+    "sm_shard_compact": (ci, [vp]),
+    "sm_shard_export_dense_device": (ci, [vp, vpp, u32p]),
+    "sm_gpu_process_count": (ci, [vp]),
+    "sm_rig_configure": (ci, [vp, ci, ci]),
+    "sm_rig_consolidate": (ci, [vp, vp, vp, vp, vp, u32p, u32p]),
+    "sm_rig_consolidate_step": (ci, [vp, vp, vp, vp, vp, u32p, u32p]),
+    "sm_default_track_params": (ci, [_TRACK]),
+    "sm_track_frame": (ci, [vp, vp, vp, _TRACK, vp, P(SmTrackInfo)]),
+    "sm_track_debug": (ci, [vp, vp, vp, vp, vp]),
+    "sm_default_track_rgb_params": (ci, [_RGB]),
+    "sm_track_frame_rgb": (ci, [vp, vp, vp, vp, _TRACK, _RGB, vp, P(SmTrackInfo), P(SmTrackRgbInfo)]),
+    "sm_track_rgb_debug": (ci, [vp, vp, vp, vp, ci, ci, vp]),
+    "sm_default_retire_params": (ci, [_CFG, P(SmRetireParams)]),
+    "sm_retire": (ci, [vp, vp, P(SmRetireParams), vp, u32, u32p]),
+    "sm_retire_device": (ci, [vp, vp, P(SmRetireParams), vp, u32, u32p]),
+    "sm_set_auto_retire": (ci, [vp, P(SmRetireParams), i32, cs]),
+    "sm_auto_retire_stats": (ci, [vp, u32p, u64p]),
+    "sm_default_recall_params": (ci, [_CFG, P(SmRecallParams)]),
+    "sm_recall": (ci, [vp, _SRC, vp, P(SmRecallParams), i32, u32p]),
+    "sm_recall_stats": (ci, [vp, P(SmRecallStats)]),
+    "sm_set_auto_recall": (ci, [vp, P(SmRecallParams)]),
+    "sm_auto_recall_stats": (ci, [vp, u32p, u64p]),
+    "sm_warp_by_time": (ci, [vp, _SRC, i32, u32, vp]),
+    "sm_warp_stats": (ci, [vp, P(SmWarpStats)]),
+    "sm_loop_spread": (ci, [vp, i32, i32, vp]),
+    "sm_track_frame_old": (ci, [vp, vp, vp, _TRACK, i32, vp, P(SmTrackInfo), cfp]),
+    "sm_track_debug_old": (ci, [vp, vp, vp, i32, vp, vp]),
+    "sm_default_loop_params": (ci, [_CFG, _LOOP]),
+    "sm_close_loop": (ci, [vp, vp, vp, _SRC, _TRACK, _LOOP, vp, P(SmLoopInfo)]),
+    "sm_track_frame_window": (ci, [vp, vp, vp, _TRACK, i32, i32, vp, P(SmTrackInfo), cfp]),
+    "sm_track_debug_window": (ci, [vp, vp, vp, i32, i32, vp, vp]),
+    "sm_track_frame_rgb_window": (ci, [vp, vp, vp, vp, _TRACK, _RGB, i32, i32, vp, P(SmTrackInfo), P(SmTrackRgbInfo), cfp]),
+    "sm_track_rgb_debug_window": (ci, [vp, vp, vp, vp, ci, ci, i32, i32, vp, vp]),
+    "sm_close_loop_rgb": (ci, [vp, vp, vp, vp, _SRC, _TRACK, _RGB, _LOOP, vp, P(SmLoopInfo)]),
+    "sm_old_in_view": (ci, [vp, vp, i32, u32p]),
+    "sm_default_auto_loop_params": (ci, [_CFG, P(SmAutoLoopParams)]),
+    "sm_set_auto_loop": (ci, [vp, P(SmAutoLoopParams), _SRC]),
+    "sm_auto_loop_stats": (ci, [vp, P(SmAutoLoopStats)]),
+    "sm_default_search_params": (ci, [_SEARCH]),
+    "sm_score_poses_window": (ci, [vp, vp, vp, vp, u32, _TRACK, i32, cf, i32, i32, vp]),
+    "sm_search_pose": (ci, [vp, vp, vp, vp, _TRACK, _RGB, _SEARCH, i32, i32, vp, P(SmSearchInfo)]),
+    "sm_close_loop_search": (ci, [vp, vp, vp, vp, _SRC, _TRACK, _RGB, _LOOP, _SEARCH, vp, P(SmLoopInfo)]),
+    "sm_set_auto_loop_search": (ci, [vp, _SEARCH]),
+    "sm_default_lidar_sensor": (ci, [_SENSOR]),
+    "sm_lidar_directions": (ci, [_SENSOR, vp]),
+    "sm_lidar_sweep": (ci, [vp, _SENSOR, vp, vp, vp, vp, vp]),
+    "sm_lidar_sweep_maps": (ci, [vp, _SRC, _SENSOR, vp, u32, vp, vp, vp, vp]),
+    "sm_lidar_stats": (ci, [vp, P(SmLidarStats)]),
+    "sm_default_fern_params": (ci, [_CFG, P(SmFernParams)]),
+    "sm_fern_table": (ci, [P(SmFernParams), i32, i32, vp]),
+    "sm_set_ferns": (ci, [vp, P(SmFernParams)]),
+    "sm_fern_encode": (ci, [vp, vp, vp, vp]),
+    "sm_fern_encode_device": (ci, [vp, vp, vp, vp]),
+    "sm_fern_add": (ci, [vp, vp, vp, i32, u32p]),
+    "sm_fern_count": (ci, [vp, u32p]),
+    "sm_fern_download": (ci, [vp, vp, vp, vp]),
+    "sm_fern_save": (ci, [vp, cs]),
+    "sm_fern_load": (ci, [vp, cs]),
+    "sm_fern_match": (ci, [vp, vp, i32, i32, i32p, u32p, vp]),
+    "sm_search_pose_at": (ci, [vp, vp, vp, vp, vp, _TRACK, _RGB, _SEARCH, i32, i32, vp, P(SmSearchInfo)]),
+    "sm_close_loop_at": (ci, [vp, vp, vp, vp, vp, _SRC, _TRACK, _RGB, _LOOP, _SEARCH, vp, P(SmLoopInfo)]),
+    "sm_default_auto_place_params": (ci, [_CFG, P(SmAutoPlaceParams)]),
+    "sm_set_auto_place": (ci, [vp, P(SmAutoPlaceParams)]),
+    "sm_auto_place_stats": (ci, [vp, P(SmAutoPlaceStats)]),
+    "sm_default_stereo_params": (ci, [_CFG, P(SmStereoParams)]),
+    "sm_set_stereo": (ci, [vp, P(SmStereoParams)]),
+    "sm_stereo_depth": (ci, [vp, vp, vp, vp, vp]),
+    "sm_stereo_depth_device": (ci, [vp, vp, vp, vp, vp]),
+    "sm_stereo_download": (ci, [vp, vp, vp, vp]),
+    "sm_default_fill_params": (ci, [_FILL]),
+    "sm_fill_image": (ci, [vp, _FILL, ci, ci, u32, vp, vp, vp]),
+    "sm_fill_image_device": (ci, [vp, _FILL, ci, ci, u32, vp, vp, vp]),
+    "sm_render_image_ex": (ci, [vp, vp] + _VIEW + [_FILL, vp, vp, vp]),
+    "sm_render_image_maps_ex": (ci, [vp, _SRC, vp, u32] + _VIEW + [_FILL, vp, vp, vp]),
+    "sm_fill_stats": (ci, [vp, P(SmFillStats)]),
+    "sm_default_blend_params": (ci, [_BLEND]),
+    "sm_render_image_blend": (ci, [vp, vp] + _VIEW + [_BLEND, _FILL, vp, vp, vp]),
+    "sm_render_image_maps_blend": (ci, [vp, _SRC, vp, u32] + _VIEW + [_BLEND, _FILL, vp, vp, vp]),
+    "sm_blend_stats": (ci, [vp, P(SmBlendStats)]),
+    "sm_default_simplify_params": (ci, [P(SmSimplifyParams)]),
+    "sm_simplify": (ci, [vp, P(SmSimplifyParams)]),
+    "sm_simplify_maps": (ci, [vp, _SRC, P(SmSimplifyParams), cs]),
+    "sm_simplify_stats": (ci, [vp, P(SmSimplifyStats)]),
+    "sm_default_register_params": (ci, [P(SmRegisterParams)]),
+    "sm_register_maps": (ci, [vp, _SRC, _SRC, vp, P(SmRegisterParams), vp, P(SmRegisterInfo)]),
+    "sm_register_debug": (ci, [vp, _SRC, _SRC, vp, i32, P(SmRegisterParams), vp, vp]),
+    "sm_register_stats": (ci, [vp, P(SmRegisterStats)]),
+    "sm_default_compare_params": (ci, [P(SmCompareParams)]),
+    "sm_compare_maps": (ci, [vp, _SRC, _SRC, vp, P(SmCompareParams), vp, cs, P(SmCompareInfo)]),
+    "sm_compare_stats": (ci, [vp, P(SmCompareStats)]),
+    "sm_default_tile_params": (ci, [P(SmTileParams)]),
+    "sm_tile_maps": (ci, [vp, _SRC, P(SmTileParams), cs]),
+    "sm_tile_stats": (ci, [vp, P(SmTileStats)]),
+    "sm_default_segment_params": (ci, [P(SmSegmentParams)]),
+    "sm_segment_maps": (ci, [vp, _SRC, P(SmSegmentParams), vp, vp, u32, cs, P(SmSegmentInfo)]),
+    "sm_segment_stats": (ci, [vp, P(SmSegmentStats)]),
+    "sm_default_mesh_params": (ci, [P(SmMeshParams)]),
+    "sm_mesh_maps": (ci, [vp, _SRC, P(SmMeshParams), vp, u32, vp, u32, cs, P(SmMeshInfo)]),
+    "sm_mesh_stats": (ci, [vp, P(SmMeshStats)]),
+    "sm_default_ground_params": (ci, [P(SmGroundParams)]),
+    "sm_ground_maps": (ci, [vp, _SRC, P(SmGroundParams)] + [vp] * 6 + [P(SmGroundInfo)]),
+    "sm_ground_stats": (ci, [vp, P(SmGroundStats)]),
+    "sm_render_image_scene": (ci, [vp, _SRC, _SCENE, vp, u32] + _VIEW + [_FILL, vp, vp, vp]),
+    "sm_lidar_sweep_scene": (ci, [vp, _SRC, _SCENE, _SENSOR, vp, u32, vp, vp, vp, vp]),
+    "sm_scene_place_rows": (ci, [vp, vp, u32, vp]),
+    "sm_scene_stats": (ci, [vp, P(SmSceneStats)]),
+    "sm_default_rays_params": (ci, [P(SmRaysParams)]),
+    "sm_cast_rays_maps": (ci, [vp, _SRC, P(SmRaysParams), vp, u32, vp, vp, vp, vp, vp]),
+    "sm_cast_rays_stats": (ci, [vp, P(SmRaysStats)]),
+}
+# ---- NOT IN THE HEADER: the diagnostics the library exports beside its C-ABI (timings of the last call of a kind; SurfelMap's
+# *_ms / *_stats readers say what each gives).  They are typed and required like the rest, but are no part of SYMBOLS.
+DIAGNOSTICS = {
+    "sm_debug_track_stats": (ci, [vp, cfp, ci, P(ci)]),
+    "sm_debug_track_rgb_stats": (ci, [vp, cfp, P(ci), ci, P(ci)]),
+    "sm_debug_retire_stats": (ci, [vp, cfp]),
+    "sm_debug_census_ms": (ci, [vp, cfp]),
+    "sm_debug_place_ms": (ci, [vp, cfp, cfp]),
+    "sm_debug_stereo_ms": (ci, [vp, cfp]),
+    "sm_debug_render_model_stats": (ci, [vp, u32p, cfp]),
+}
+PROTOTYPES.update(DIAGNOSTICS)
+SYMBOLS = tuple(k for k in PROTOTYPES if k not in DIAGNOSTICS)    # every extern "C" symbol include/sm_c_api.h declares
+del P, vp, cs, sz, ci, cf, i32, u32, vpp, i32p, u32p, u64p, cfp  # (the rows' shorthand is the table's alone)
 
 
-def _loop_info_dict(info) -> dict:
-    return dict(status=LOOP_STATUS.get(info.status, str(info.status)), status_code=int(info.status), track=_track_info_dict(info.track),
-                D=np.array(info.D[:], np.float32).reshape(4, 4).T.copy(), t_a=int(info.t_a), t_b=int(info.t_b))
-
-
-def loop_spread(D, t_a, t_b) -> np.ndarray:
-    """sm_loop_spread: the table float32[t_b - t_a + 1][12] (row-major 3x4 [R|t] per tick) that ramps the world->world correction D
-    (4x4, numpy row/col indexing, or float32[16] column-major) from nothing at tick t_a to all of it at t_b.  Host only."""
-    L = load()
-    d = _mat16(D)
-    t_a, t_b = int(t_a), int(t_b)
-    out = np.zeros((max(t_b - t_a + 1, 1), 12), np.float32)
-    rc = L.sm_loop_spread(_ptr(d), t_a, t_b, _ptr(out))
-    if rc != SM_OK:
-        raise SurfelMapError("sm_loop_spread", rc, L.sm_last_error().decode())
-    return out
-
-
-def _mat16(m):
-    """float32[16] column-major; a 4x4 matrix (numpy row/col indexing) is converted"""
-    a = np.asarray(m, np.float32)
-    if a.shape == (4, 4):
-        a = a.T
-    a = np.ascontiguousarray(a.reshape(16))
-    return a
-
-
-def model_view(mvp, mv_inv, w, h, threshold=0.0, color_type=0, unstable=True, points=False, window=False, time=0,
-               time_delta=0, clear=(0, 0, 0, 0)) -> SmModelView:
-    v = SmModelView()
-    v.mvp[:] = [float(x) for x in _mat16(mvp)]
-    v.mv_inv[:] = [float(x) for x in _mat16(mv_inv)]
-    v.threshold = threshold
-    v.color_type, v.draw_unstable, v.draw_points, v.draw_window = int(color_type), int(bool(unstable)), int(bool(points)), int(bool(window))
-    v.time, v.time_delta, v.width, v.height = int(time), int(time_delta), int(w), int(h)
-    v.clear_rgba[:] = [int(c) for c in clear]
-    return v
-
-
-def _lidar_planes(shape) -> dict:
-    return dict(range=np.zeros(shape, np.float32), id=np.zeros(shape, np.int32), rgb=np.zeros(tuple(shape) + (3,), np.uint8),
-                sem=np.zeros(shape, np.uint8))
-
-
+# =====================================================================================================================
+# The helpers
+# =====================================================================================================================
 class SurfelMapError(RuntimeError):
     def __init__(self, what, rc, detail=""):
         super().__init__(f"{what} failed: rc={rc} {detail}".strip())
@@ -1110,17 +666,6 @@ def _choose_rccl():
             os.environ["SM_RCCL_LIB"] = cand
 
 
-def rccl_unique_id() -> bytes:
-    """128-byte RCCL id made by one rank and handed to all (sm_shard_rccl_unique_id)"""
-    _choose_rccl()
-    L = load()
-    buf = C.create_string_buffer(128)
-    rc = L.sm_shard_rccl_unique_id(buf)
-    if rc:
-        raise SurfelMapError("sm_shard_rccl_unique_id", rc, L.sm_last_error().decode())
-    return buf.raw
-
-
 def load():
     """dlopen the HIP library (no compute).  Raises if it has not been built."""
     global _lib
@@ -1132,206 +677,42 @@ def load():
             "(make -C surfelmapping_amd/csrc). surfelmapping_amd has no CPU fallback.")
     _preload_torch_hip_runtime()
     L = C.CDLL(LIB_PATH)
-    vp, u32p = C.c_void_p, C.POINTER(C.c_uint32)
-    L.sm_api_version.restype = C.c_int
-    if L.sm_api_version() != API_VERSION:     # a stale build: the struct layouts below would not match
+
+    def typed(name):
+        fn = getattr(L, name)     # AttributeError here = the library does not match the header
+        fn.restype, fn.argtypes = PROTOTYPES[name]
+        return fn
+    if typed("sm_api_version")() != API_VERSION:     # a stale build: the struct layouts above would not match
         raise ImportError(f"{LIB_PATH} has API version {L.sm_api_version()}, this binding expects {API_VERSION}: rebuild it "
                           "(python -c 'import __graft_entry__ as g; g.build()')")
-    L.sm_last_error.restype = C.c_char_p
-    L.sm_default_config.argtypes = [C.POINTER(SmConfig), C.c_int, C.c_int] + [C.c_float] * 4
-    L.sm_create.restype = vp
-    L.sm_create.argtypes = [C.POINTER(SmConfig)]
-    L.sm_destroy.restype = None
-    L.sm_destroy.argtypes = [vp]
-    L.sm_process_frame.argtypes = [vp, vp, vp, vp, vp]
-    L.sm_process_frame_device.argtypes = [vp, vp, vp, vp, vp]
-    L.sm_process_frame_async.argtypes = [vp, vp, vp, vp, vp]
-    L.sm_inputs_consumed.argtypes = [vp]
-    L.sm_host_alloc.restype = vp
-    L.sm_host_alloc.argtypes = [vp, C.c_size_t]
-    L.sm_host_free.argtypes = [vp, vp]
-    L.sm_host_alloc_frame.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
-    L.sm_debug_slow_frames.argtypes = [vp, u32p]
-    L.sm_debug_squeezes.argtypes = [vp, u32p, u32p]
-    L.sm_sync.argtypes = [vp]
-    L.sm_clean_points.argtypes = [vp, vp, vp, vp]
-    L.sm_clean_points_ex.argtypes = [vp, vp, vp, vp, C.c_int]
-    L.sm_clean_points_cb.argtypes = [vp, vp, vp, vp, C.c_int, CAP_FN, vp]
-    L.sm_reset.argtypes = [vp]
-    L.sm_get_counts.argtypes = [vp, C.POINTER(SmCounts)]
-    L.sm_download_model_aos.argtypes = [vp, vp, C.c_uint32, u32p]
-    L.sm_upload_model_aos.argtypes = [vp, vp, C.c_uint32]
-    L.sm_save_map.argtypes = [vp, C.c_char_p, C.c_int32, C.c_int32]
-    L.sm_load_map.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-    L.sm_download_index_map.argtypes = [vp, vp, vp, vp, vp]
-    L.sm_download_raw_cloud.argtypes = [vp, vp, C.c_uint32, u32p]
-    L.sm_download_depth.argtypes = [vp, C.c_int, vp]
-    L.sm_render_image.argtypes = [vp, vp, C.c_int, C.c_int] + [C.c_float] * 4 + [vp, vp]
-    L.sm_render_model.argtypes = [vp, C.POINTER(SmModelView), vp, vp, vp]
-    L.sm_render_model_device.argtypes = [vp, C.POINTER(SmModelView), vp, vp, vp]
-    L.sm_render_image_maps.argtypes = [vp, C.POINTER(SmMapSource), vp, C.c_uint32, C.c_int, C.c_int] + [C.c_float] * 4 + [vp, vp]
-    L.sm_render_model_maps.argtypes = [vp, C.POINTER(SmMapSource), C.POINTER(SmModelView), C.c_uint32, vp, vp, vp]
-    L.sm_render_maps_stats.argtypes = [vp, C.POINTER(SmMapsStats)]
-    L.sm_set_frame.argtypes = [vp, vp, vp, vp]
-    L.sm_set_tick.argtypes = [vp, C.c_int32]
-    L.sm_stage_conflict.argtypes = [vp, vp, C.c_float, C.c_float, C.c_float, C.c_int]
-    L.sm_stage_cull.argtypes = [vp]
-    L.sm_stage_splat.argtypes = [vp, vp, C.c_int32, C.c_float, C.c_int32]
-    L.sm_stage_associate_fuse.argtypes = [vp, vp, C.c_int32, C.c_float, C.c_float]
-    L.sm_stage_timings.argtypes = [vp, C.POINTER(SmTimings)]
-    L.sm_read_frame_log.argtypes = [vp, vp, C.c_uint32, u32p]
-    L.sm_device_alloc.restype = vp
-    L.sm_device_alloc.argtypes = [vp, C.c_size_t]
-    L.sm_device_free.argtypes = [vp, vp]
-    L.sm_device_upload.argtypes = [vp, vp, vp, C.c_size_t]
-    L.sm_export_model_device.argtypes = [vp, C.POINTER(vp), u32p]
-    L.sm_append_model_aos_device.argtypes = [vp, vp, C.c_uint32]
-    L.sm_device_download.argtypes = [vp, vp, vp, C.c_size_t]
-    L.sm_shard_stream_configure.argtypes = [vp, C.c_int, C.c_int]
-    L.sm_shard_set_collective.argtypes = [vp, COLLECTIVE_FN, vp]
-    L.sm_shard_rccl_unique_id.argtypes = [vp]
-    L.sm_shard_rccl_init.argtypes = [vp, vp]
-    L.sm_shard_rccl_finalize.argtypes = [vp]
-    L.sm_shard_rccl_nranks.argtypes = [vp]
-    L.sm_shard_frame_device.argtypes = [vp, vp, vp, vp, vp]
-    L.sm_shard_frame.argtypes = [vp, vp, vp, vp, vp]
-    L.sm_shard_compact.argtypes = [vp]
-    L.sm_shard_export_dense_device.argtypes = [vp, C.POINTER(vp), u32p]
-    L.sm_gpu_process_count.argtypes = [vp]
-    L.sm_rig_configure.argtypes = [vp, C.c_int, C.c_int]
-    L.sm_rig_consolidate.argtypes = [vp, vp, vp, vp, vp, u32p, u32p]
-    L.sm_rig_consolidate_step.argtypes = [vp, vp, vp, vp, vp, u32p, u32p]
-    L.sm_default_track_params.argtypes = [C.POINTER(SmTrackParams)]
-    L.sm_track_frame.argtypes = [vp, vp, vp, C.POINTER(SmTrackParams), vp, C.POINTER(SmTrackInfo)]
-    L.sm_track_debug.argtypes = [vp, vp, vp, vp, vp]
-    L.sm_default_track_rgb_params.argtypes = [C.POINTER(SmTrackRgbParams)]
-    L.sm_track_frame_rgb.argtypes = [vp, vp, vp, vp, C.POINTER(SmTrackParams), C.POINTER(SmTrackRgbParams), vp,
-                                     C.POINTER(SmTrackInfo), C.POINTER(SmTrackRgbInfo)]
-    L.sm_track_rgb_debug.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp]
-    L.sm_default_retire_params.argtypes = [C.POINTER(SmConfig), C.POINTER(SmRetireParams)]
-    L.sm_retire.argtypes = [vp, vp, C.POINTER(SmRetireParams), vp, C.c_uint32, u32p]
-    L.sm_retire_device.argtypes = [vp, vp, C.POINTER(SmRetireParams), vp, C.c_uint32, u32p]
-    L.sm_set_auto_retire.argtypes = [vp, C.POINTER(SmRetireParams), C.c_int32, C.c_char_p]
-    L.sm_auto_retire_stats.argtypes = [vp, u32p, C.POINTER(C.c_uint64)]
-    L.sm_default_recall_params.argtypes = [C.POINTER(SmConfig), C.POINTER(SmRecallParams)]
-    L.sm_recall.argtypes = [vp, C.POINTER(SmMapSource), vp, C.POINTER(SmRecallParams), C.c_int32, u32p]
-    L.sm_recall_stats.argtypes = [vp, C.POINTER(SmRecallStats)]
-    L.sm_set_auto_recall.argtypes = [vp, C.POINTER(SmRecallParams)]
-    L.sm_auto_recall_stats.argtypes = [vp, u32p, C.POINTER(C.c_uint64)]
-    L.sm_warp_by_time.argtypes = [vp, C.POINTER(SmMapSource), C.c_int32, C.c_uint32, vp]
-    L.sm_warp_stats.argtypes = [vp, C.POINTER(SmWarpStats)]
-    L.sm_loop_spread.argtypes = [vp, C.c_int32, C.c_int32, vp]
-    L.sm_track_frame_old.argtypes = [vp, vp, vp, C.POINTER(SmTrackParams), C.c_int32, vp, C.POINTER(SmTrackInfo), C.POINTER(C.c_float)]
-    L.sm_track_debug_old.argtypes = [vp, vp, vp, C.c_int32, vp, vp]
-    L.sm_default_loop_params.argtypes = [C.POINTER(SmConfig), C.POINTER(SmLoopParams)]
-    L.sm_close_loop.argtypes = [vp, vp, vp, C.POINTER(SmMapSource), C.POINTER(SmTrackParams), C.POINTER(SmLoopParams), vp,
-                                C.POINTER(SmLoopInfo)]
-    i32, tpp, rpp, lpp = C.c_int32, C.POINTER(SmTrackParams), C.POINTER(SmTrackRgbParams), C.POINTER(SmLoopParams)
-    L.sm_track_frame_window.argtypes = [vp, vp, vp, tpp, i32, i32, vp, C.POINTER(SmTrackInfo), C.POINTER(C.c_float)]
-    L.sm_track_debug_window.argtypes = [vp, vp, vp, i32, i32, vp, vp]
-    L.sm_track_frame_rgb_window.argtypes = [vp, vp, vp, vp, tpp, rpp, i32, i32, vp, C.POINTER(SmTrackInfo), C.POINTER(SmTrackRgbInfo),
-                                            C.POINTER(C.c_float)]
-    L.sm_track_rgb_debug_window.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, i32, i32, vp, vp]
-    L.sm_close_loop_rgb.argtypes = [vp, vp, vp, vp, C.POINTER(SmMapSource), tpp, rpp, lpp, vp, C.POINTER(SmLoopInfo)]
-    L.sm_old_in_view.argtypes = [vp, vp, i32, u32p]
-    L.sm_default_auto_loop_params.argtypes = [C.POINTER(SmConfig), C.POINTER(SmAutoLoopParams)]
-    L.sm_set_auto_loop.argtypes = [vp, C.POINTER(SmAutoLoopParams), C.POINTER(SmMapSource)]
-    L.sm_auto_loop_stats.argtypes = [vp, C.POINTER(SmAutoLoopStats)]
-    spp = C.POINTER(SmSearchParams)
-    L.sm_default_search_params.argtypes = [spp]
-    L.sm_score_poses_window.argtypes = [vp, vp, vp, vp, C.c_uint32, tpp, i32, C.c_float, i32, i32, vp]
-    L.sm_search_pose.argtypes = [vp, vp, vp, vp, tpp, rpp, spp, i32, i32, vp, C.POINTER(SmSearchInfo)]
-    L.sm_close_loop_search.argtypes = [vp, vp, vp, vp, C.POINTER(SmMapSource), tpp, rpp, lpp, spp, vp, C.POINTER(SmLoopInfo)]
-    L.sm_set_auto_loop_search.argtypes = [vp, spp]
-    lsp = C.POINTER(SmLidarSensor)
-    L.sm_default_lidar_sensor.argtypes = [lsp]
-    L.sm_lidar_directions.argtypes = [lsp, vp]
-    L.sm_lidar_sweep.argtypes = [vp, lsp, vp, vp, vp, vp, vp]
-    L.sm_lidar_sweep_maps.argtypes = [vp, C.POINTER(SmMapSource), lsp, vp, C.c_uint32, vp, vp, vp, vp]
-    L.sm_lidar_stats.argtypes = [vp, C.POINTER(SmLidarStats)]
-    fpp = C.POINTER(SmFernParams)
-    L.sm_default_fern_params.argtypes = [C.POINTER(SmConfig), fpp]
-    L.sm_fern_table.argtypes = [fpp, i32, i32, vp]
-    L.sm_set_ferns.argtypes = [vp, fpp]
-    L.sm_fern_encode.argtypes = [vp, vp, vp, vp]
-    L.sm_fern_encode_device.argtypes = [vp, vp, vp, vp]
-    L.sm_fern_add.argtypes = [vp, vp, vp, i32, u32p]
-    L.sm_fern_count.argtypes = [vp, u32p]
-    L.sm_fern_download.argtypes = [vp, vp, vp, vp]
-    L.sm_fern_save.argtypes = [vp, C.c_char_p]
-    L.sm_fern_load.argtypes = [vp, C.c_char_p]
-    L.sm_fern_match.argtypes = [vp, vp, i32, i32, C.POINTER(i32), u32p, vp]
-    L.sm_search_pose_at.argtypes = [vp, vp, vp, vp, vp, tpp, rpp, spp, i32, i32, vp, C.POINTER(SmSearchInfo)]
-    L.sm_close_loop_at.argtypes = [vp, vp, vp, vp, vp, C.POINTER(SmMapSource), tpp, rpp, lpp, spp, vp, C.POINTER(SmLoopInfo)]
-    L.sm_default_auto_place_params.argtypes = [C.POINTER(SmConfig), C.POINTER(SmAutoPlaceParams)]
-    L.sm_set_auto_place.argtypes = [vp, C.POINTER(SmAutoPlaceParams)]
-    L.sm_auto_place_stats.argtypes = [vp, C.POINTER(SmAutoPlaceStats)]
-    L.sm_debug_place_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]     # (a diagnostic, not in the header)
-    stp = C.POINTER(SmStereoParams)
-    L.sm_default_stereo_params.argtypes = [C.POINTER(SmConfig), stp]
-    L.sm_set_stereo.argtypes = [vp, stp]
-    L.sm_stereo_depth.argtypes = [vp, vp, vp, vp, vp]
-    L.sm_stereo_depth_device.argtypes = [vp, vp, vp, vp, vp]
-    L.sm_stereo_download.argtypes = [vp, vp, vp, vp]
-    L.sm_debug_stereo_ms.argtypes = [vp, C.POINTER(C.c_float)]                          # (a diagnostic, not in the header)
-    flp = C.POINTER(SmFillParams)
-    L.sm_default_fill_params.argtypes = [flp]
-    L.sm_fill_image.argtypes = [vp, flp, C.c_int, C.c_int, C.c_uint32, vp, vp, vp]
-    L.sm_fill_image_device.argtypes = [vp, flp, C.c_int, C.c_int, C.c_uint32, vp, vp, vp]
-    L.sm_render_image_ex.argtypes = [vp, vp, C.c_int, C.c_int] + [C.c_float] * 4 + [flp, vp, vp, vp]
-    L.sm_render_image_maps_ex.argtypes = [vp, C.POINTER(SmMapSource), vp, C.c_uint32, C.c_int, C.c_int] + [C.c_float] * 4 + [flp, vp, vp, vp]
-    L.sm_fill_stats.argtypes = [vp, C.POINTER(SmFillStats)]
-    blp = C.POINTER(SmBlendParams)
-    L.sm_default_blend_params.argtypes = [blp]
-    L.sm_render_image_blend.argtypes = [vp, vp, C.c_int, C.c_int] + [C.c_float] * 4 + [blp, flp, vp, vp, vp]
-    L.sm_render_image_maps_blend.argtypes = [vp, C.POINTER(SmMapSource), vp, C.c_uint32, C.c_int, C.c_int] + [C.c_float] * 4 + [blp, flp, vp, vp, vp]
-    L.sm_blend_stats.argtypes = [vp, C.POINTER(SmBlendStats)]
-    smp = C.POINTER(SmSimplifyParams)
-    L.sm_default_simplify_params.argtypes = [smp]
-    L.sm_simplify.argtypes = [vp, smp]
-    L.sm_simplify_maps.argtypes = [vp, C.POINTER(SmMapSource), smp, C.c_char_p]
-    L.sm_simplify_stats.argtypes = [vp, C.POINTER(SmSimplifyStats)]
-    rgp, msp = C.POINTER(SmRegisterParams), C.POINTER(SmMapSource)
-    L.sm_default_register_params.argtypes = [rgp]
-    L.sm_register_maps.argtypes = [vp, msp, msp, C.c_void_p, rgp, C.c_void_p, C.POINTER(SmRegisterInfo)]
-    L.sm_register_debug.argtypes = [vp, msp, msp, C.c_void_p, C.c_int32, rgp, C.c_void_p, C.c_void_p]
-    L.sm_register_stats.argtypes = [vp, C.POINTER(SmRegisterStats)]
-    cpp = C.POINTER(SmCompareParams)
-    L.sm_default_compare_params.argtypes = [cpp]
-    L.sm_compare_maps.argtypes = [vp, msp, msp, C.c_void_p, cpp, C.c_void_p, C.c_char_p, C.POINTER(SmCompareInfo)]
-    L.sm_compare_stats.argtypes = [vp, C.POINTER(SmCompareStats)]
-    tpp = C.POINTER(SmTileParams)
-    L.sm_default_tile_params.argtypes = [tpp]
-    L.sm_tile_maps.argtypes = [vp, msp, tpp, C.c_char_p]
-    L.sm_tile_stats.argtypes = [vp, C.POINTER(SmTileStats)]
-    spp = C.POINTER(SmSegmentParams)
-    L.sm_default_segment_params.argtypes = [spp]
-    L.sm_segment_maps.argtypes = [vp, msp, spp, C.c_void_p, C.c_void_p, C.c_uint32, C.c_char_p, C.POINTER(SmSegmentInfo)]
-    L.sm_segment_stats.argtypes = [vp, C.POINTER(SmSegmentStats)]
-    mpp = C.POINTER(SmMeshParams)
-    L.sm_default_mesh_params.argtypes = [mpp]
-    L.sm_mesh_maps.argtypes = [vp, msp, mpp, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_char_p, C.POINTER(SmMeshInfo)]
-    L.sm_mesh_stats.argtypes = [vp, C.POINTER(SmMeshStats)]
-    gpp = C.POINTER(SmGroundParams)
-    L.sm_default_ground_params.argtypes = [gpp]
-    L.sm_ground_maps.argtypes = [vp, msp, gpp] + [C.c_void_p] * 6 + [C.POINTER(SmGroundInfo)]
-    L.sm_ground_stats.argtypes = [vp, C.POINTER(SmGroundStats)]
-    L.sm_default_rays_params.argtypes = [C.POINTER(SmRaysParams)]
-    L.sm_cast_rays_maps.argtypes = [vp, C.POINTER(SmMapSource), C.POINTER(SmRaysParams), vp, C.c_uint32, vp, vp, vp, vp, vp]
-    L.sm_cast_rays_stats.argtypes = [vp, C.POINTER(SmRaysStats)]
-    scp = C.POINTER(SmScene)
-    L.sm_render_image_scene.argtypes = [vp, msp, scp, vp, C.c_uint32, C.c_int, C.c_int] + [C.c_float] * 4 + [flp, vp, vp, vp]
-    L.sm_lidar_sweep_scene.argtypes = [vp, msp, scp, lsp, vp, C.c_uint32, vp, vp, vp, vp]
-    L.sm_scene_place_rows.argtypes = [vp, vp, C.c_uint32, vp]
-    L.sm_scene_stats.argtypes = [vp, C.POINTER(SmSceneStats)]
-    for name in SYMBOLS:
-        getattr(L, name)          # AttributeError here = the library does not match the header
+    for name in PROTOTYPES:
+        typed(name)
     _lib = L
     return L
 
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _mat16(m):
+    """float32[16] column-major; a 4x4 matrix (numpy row/col indexing) is converted"""
+    a = np.asarray(m, np.float32)
+    if a.shape == (4, 4):
+        a = a.T
+    a = np.ascontiguousarray(a.reshape(16))
+    return a
+
+
+def rccl_unique_id() -> bytes:
+    """128-byte RCCL id made by one rank and handed to all (sm_shard_rccl_unique_id)"""
+    _choose_rccl()
+    L = load()
+    buf = C.create_string_buffer(128)
+    rc = L.sm_shard_rccl_unique_id(buf)
+    if rc:
+        raise SurfelMapError("sm_shard_rccl_unique_id", rc, L.sm_last_error().decode())
+    return buf.raw
 
 
 def make_config(width, height, fx, fy, cx, cy, **over) -> SmConfig:
@@ -1344,6 +725,502 @@ def make_config(width, height, fx, fy, cx, cy, **over) -> SmConfig:
     return c
 
 
+# ---- the parameter builders.  _params() is all of them: the defaults of the C side, then the overrides -- a plain field by setattr,
+# an unknown key a KeyError, and the keys of the structure's table below (key -> setter(p, key, value)) by their setter.  A NEW
+# PARAMETER STRUCTURE takes its public xxx_params() with one call of _params(), and a row of _SPECIAL only if it has such keys.
+def _params(struct, default, cfg, over):
+    """`struct` filled by the library's `default` function (of the config `cfg`, where it takes one), then overridden by `over`"""
+    p = struct()
+    getattr(load(), default)(*([] if cfg is None else [C.byref(cfg)]), C.byref(p))
+    special = _SPECIAL.get(struct, {})
+    for k, v in over.items():
+        if k in special:
+            special[k](p, k, v)
+        elif not hasattr(p, k):
+            raise KeyError(k)
+        else:
+            setattr(p, k, v)
+    return p
+
+
+def _whole(convert):
+    """an array field takes a sequence of exactly its length"""
+    def set_(p, k, v):
+        getattr(p, k)[:] = [convert(x) for x in v]
+    return set_
+
+
+def _leading(convert):
+    """an array field takes its leading entries; those the sequence does not name keep their default"""
+    def set_(p, k, v):
+        a = getattr(p, k)
+        for i, x in enumerate(v):
+            a[i] = convert(x)
+    return set_
+
+
+def _classes(mask):
+    """classes= sets the eight words of the field `mask` from the classes that take part"""
+    def set_(p, k, v):
+        getattr(p, mask)[:] = segment_class_mask(v)
+    return set_
+
+
+def _inner(field):
+    """a field of the nested structure `field`, given by its own name"""
+    def set_(p, k, v):
+        setattr(getattr(p, field), k, v)
+    return set_
+
+
+def _refused(p, k, v):
+    raise KeyError(k)
+
+
+def _padded3(p, k, v):
+    """(rays_params' origin: a shorter sequence is padded with zeros)"""
+    setattr(p, k, (C.c_float * 3)(*[float(x) for x in v]))
+
+
+_ORIGIN = {"origin": _whole(float)}
+_SPECIAL = {
+    SmRaysParams: {"origin": _padded3},
+    SmTrackRgbParams: {"iters": _leading(int)},
+    SmSearchParams: {k: _leading(float) for k in ("trans_half", "trans_step", "rot_half_deg", "rot_step_deg")},
+    SmSimplifyParams: _ORIGIN,
+    SmTileParams: _ORIGIN,
+    SmCompareParams: _ORIGIN,
+    SmRegisterParams: {"origin": _whole(float), "pivot": _whole(float)},
+    SmSegmentParams: {"origin": _whole(float), "class_mask": _whole(int), "classes": _classes("class_mask")},
+    SmMeshParams: {"origin": _whole(float), "class_mask": _whole(int), "classes": _classes("class_mask")},
+    SmGroundParams: {"origin": _whole(float), "ground_mask": _whole(int), "classes": _classes("ground_mask")},
+    # the fields of sm_loop_params by their own names; `loop` itself is no key
+    SmAutoLoopParams: {**{n: _inner("loop") for n, _ in SmLoopParams._fields_}, "loop": _refused},
+}
+_SPECIAL[SmAutoPlaceParams] = {**_SPECIAL[SmAutoLoopParams], "search": lambda p, k, v: setattr(p, k, search_params(**dict(v)))}
+
+
+def rays_params(**over) -> SmRaysParams:
+    """sm_default_rays_params with fields replaced: cell_mm, origin (three floats), min_conf"""
+    return _params(SmRaysParams, "sm_default_rays_params", None, over)
+
+
+def track_params(**over) -> SmTrackParams:
+    """sm_default_track_params with fields overridden (max_iters, dist_thresh, angle_thresh, min_inliers, pixel_stride)"""
+    return _params(SmTrackParams, "sm_default_track_params", None, over)
+
+
+def track_rgb_params(**over) -> SmTrackRgbParams:
+    """sm_default_track_rgb_params with fields overridden (levels, iters: a sequence whose index is the level, the levels it
+    does not name keep their default; rgb_weight, rgb_max_residual)"""
+    return _params(SmTrackRgbParams, "sm_default_track_rgb_params", None, over)
+
+
+def retire_params(cfg, **over) -> SmRetireParams:
+    """sm_default_retire_params of a config (min_age = time_delta, min_distance = 1.5 * far_clip) with fields overridden"""
+    return _params(SmRetireParams, "sm_default_retire_params", cfg, over)
+
+
+def recall_params(cfg, **over) -> SmRecallParams:
+    """sm_default_recall_params of a config (radius = 1.5 * far_clip) with fields overridden"""
+    return _params(SmRecallParams, "sm_default_recall_params", cfg, over)
+
+
+def loop_params(cfg, **over) -> SmLoopParams:
+    """sm_default_loop_params of a config (min_age = time_delta; 0.02 m, 0.05 deg; 2 m, 10 deg) with fields overridden"""
+    return _params(SmLoopParams, "sm_default_loop_params", cfg, over)
+
+
+def auto_loop_params(cfg, **over) -> SmAutoLoopParams:
+    """sm_default_auto_loop_params of a config (every 1, rest 10, min_old 1000, loop = loop_params(cfg)) with fields overridden;
+    the fields of sm_loop_params are given by their own names (min_age, max_trans, ...)"""
+    return _params(SmAutoLoopParams, "sm_default_auto_loop_params", cfg, over)
+
+
+def search_params(**over) -> SmSearchParams:
+    """sm_default_search_params (2 levels; +-2 m in x and z at 0.25 m, +-3 deg about y at 0.5 deg; refine 4, stride0 8, top_k 4,
+    colour_thresh 0.1) with fields overridden; the four per-axis fields take a sequence of three"""
+    return _params(SmSearchParams, "sm_default_search_params", None, over)
+
+
+def auto_place_params(cfg, **over) -> SmAutoPlaceParams:
+    """sm_default_auto_place_params (every 1, rest 10, add_above 0.2, match_below 0.3, min_jump 2 m, loop = loop_params(cfg) with
+    max_trans 50 and max_rot_deg 45, search = search_params()) with fields overridden: a field of sm_loop_params by its own name,
+    search as a dict of search_params() overrides"""
+    return _params(SmAutoPlaceParams, "sm_default_auto_place_params", cfg, over)
+
+
+def fern_params(cfg, **over) -> SmFernParams:
+    """sm_default_fern_params (512 ferns, cell 8, seed 1, the config's near and far clip in millimetres) with fields overridden"""
+    return _params(SmFernParams, "sm_default_fern_params", cfg, over)
+
+
+def stereo_params(cfg, **over) -> SmStereoParams:
+    """sm_default_stereo_params (D 128, 8 paths, p1 7, p2 86, uniqueness 5 %, lr_max_diff 1, baseline 0.54 m) with fields overridden"""
+    return _params(SmStereoParams, "sm_default_stereo_params", cfg, over)
+
+
+def fill_params(**over) -> SmFillParams:
+    """sm_default_fill_params (levels 3, depth_tol_256 13, through_count 6, prefer_far 1, min_cover_256 64) with fields overridden"""
+    return _params(SmFillParams, "sm_default_fill_params", None, over)
+
+
+def blend_params(**over) -> SmBlendParams:
+    """sm_default_blend_params (depth_tol_256 13, falloff 2 = quadratic) with fields overridden"""
+    return _params(SmBlendParams, "sm_default_blend_params", None, over)
+
+
+def default_simplify_params() -> SmSimplifyParams:
+    """sm_default_simplify_params: voxel_mm 50, split_normals 1, origin (0, 0, 0), max_cells 1 << 26"""
+    return simplify_params()
+
+
+def simplify_params(**over) -> SmSimplifyParams:
+    """default_simplify_params() with fields overridden; origin takes a sequence of three"""
+    return _params(SmSimplifyParams, "sm_default_simplify_params", None, over)
+
+
+def default_tile_params() -> SmTileParams:
+    """sm_default_tile_params: cell_mm 200, tile_shift 7, origin (0, 0, 0), max_file_records 1 << 20, max_tiles 1 << 20"""
+    return tile_params()
+
+
+def tile_params(**over) -> SmTileParams:
+    """default_tile_params() with fields overridden; origin takes a sequence of three"""
+    return _params(SmTileParams, "sm_default_tile_params", None, over)
+
+
+def default_segment_params() -> SmSegmentParams:
+    """sm_default_segment_params: voxel_mm 200, connectivity 26, by_class 1, every class, min_records 1, write_mask 1 (the records of
+    numbered components), max_cells 1 << 24, origin (0, 0, 0)"""
+    return segment_params()
+
+
+def segment_params(**over) -> SmSegmentParams:
+    """default_segment_params() with fields overridden; origin takes a sequence of three, class_mask eight words or an iterable of
+    the classes that take part (`classes=` does the latter too)"""
+    return _params(SmSegmentParams, "sm_default_segment_params", None, over)
+
+
+def segment_class_mask(classes) -> list:
+    """the eight words of class_mask with the bits of `classes` (0..255) set"""
+    words = [0] * 8
+    for c in classes:
+        if not 0 <= int(c) <= 255:
+            raise ValueError(c)
+        words[int(c) >> 5] |= 1 << (int(c) & 31)
+    return words
+
+
+def default_mesh_params() -> SmMeshParams:
+    """sm_default_mesh_params: voxel_mm 100, reach 2, min_records 1, every class, max_cells 1 << 24, origin (0, 0, 0)"""
+    return mesh_params()
+
+
+def mesh_params(**over) -> SmMeshParams:
+    """default_mesh_params() with fields overridden; origin takes a sequence of three, class_mask eight words or an iterable of the
+    classes that take part (`classes=` does the latter too)"""
+    return _params(SmMeshParams, "sm_default_mesh_params", None, over)
+
+
+def default_ground_params() -> SmGroundParams:
+    """sm_default_ground_params: cell_mm 100, up 3 (-y), origin (0, 0, 0), 256 x 256 cells, min_up 11585 (45 degrees), every class,
+    band_mm 200, the body band 150..2000 mm, min_obstacle 2, fill_cells 3, step_mm 150, reach_cells 32, unknown_blocks 0, normal_sign -1
+    (normals that point into the surface, as the fusion stores them)"""
+    return ground_params()
+
+
+def ground_params(**over) -> SmGroundParams:
+    """default_ground_params() with fields overridden; origin takes a sequence of three, ground_mask eight words or an iterable of
+    the classes that may be ground (`classes=` does the latter too)"""
+    return _params(SmGroundParams, "sm_default_ground_params", None, over)
+
+
+def default_register_params() -> SmRegisterParams:
+    """sm_default_register_params: voxel_mm 200, levels 3, max_iters 20, min_inliers 1000, angle_thresh 30, reach_cells 1, stride 0
+    (from max_samples = 1 << 22), max_cells 1 << 24, origin and pivot (0, 0, 0)"""
+    return register_params()
+
+
+def register_params(**over) -> SmRegisterParams:
+    """default_register_params() with fields overridden; origin and pivot take a sequence of three"""
+    return _params(SmRegisterParams, "sm_default_register_params", None, over)
+
+
+def default_compare_params() -> SmCompareParams:
+    """sm_default_compare_params: voxel_mm 100, cover_shift 3, reach_cells 2, plane_mm 50, angle_thresh 30, match_class 0,
+    write_mask 2 (the CHANGED records), max_cells 1 << 24, origin (0, 0, 0)"""
+    return compare_params()
+
+
+def compare_params(**over) -> SmCompareParams:
+    """default_compare_params() with fields overridden; origin takes a sequence of three"""
+    return _params(SmCompareParams, "sm_default_compare_params", None, over)
+
+
+def _fill_arg(fill):
+    """what the entry points' `fill` accepts: None (none), True (the defaults), a dict of overrides, or fill_params(...)"""
+    if fill is None or fill is False:
+        return None
+    if fill is True:
+        return fill_params()
+    return fill if isinstance(fill, SmFillParams) else fill_params(**fill)
+
+
+def _blend_arg(blend):
+    """what the entry points' `blend` accepts: None (none), True (the defaults), a dict of overrides, or blend_params(...)"""
+    if blend is None or blend is False:
+        return None
+    if blend is True:
+        return blend_params()
+    return blend if isinstance(blend, SmBlendParams) else blend_params(**blend)
+
+
+def _search_arg(search):
+    """close_loop(search=...) / set_auto_loop(search=...): None or False = no search, True = the defaults, a dict = overrides"""
+    if search is None or search is False:
+        return None
+    return search_params(**({} if search is True else dict(search)))
+
+
+# ---- map sets, sensors, scenes and what else the calls take or give
+def map_source(paths, include_model=True) -> SmMapSource:
+    """a map set: the files in drawing order, then (include_model) the live model; keeps the path strings alive"""
+    enc = [os.fsencode(p) for p in paths]
+    arr = (C.c_char_p * max(len(enc), 1))(*enc)
+    src = SmMapSource(C.cast(arr, C.POINTER(C.c_char_p)), len(enc), int(bool(include_model)))
+    src._keep = (enc, arr)
+    return src
+
+
+def _map_records(path) -> int:
+    """the records a well-formed map file of this length holds (12 bytes of header, 48 per record); 0 where there is no file --
+    the call that reads it reports that"""
+    try:
+        return max(0, (os.path.getsize(path) - 12) // 48)
+    except OSError:
+        return 0
+
+
+def lidar_sensor(**over) -> SmLidarSensor:
+    """sm_default_lidar_sensor with fields replaced: n_az, n_el, az0_deg, az_step_deg, el_deg (a sequence of n_el elevations; giving
+    it sets n_el unless that is given too), min_range, max_range, min_conf.  Keeps the elevation array alive."""
+    p = SmLidarSensor()
+    load().sm_default_lidar_sensor(C.byref(p))
+    el = over.pop("el_deg", None)
+    if el is None:
+        el = np.array([p.el_deg[i] for i in range(p.n_el)], np.float32)
+    el = np.ascontiguousarray(el, np.float32).reshape(-1)
+    p.n_el = len(el)
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise KeyError(k)
+        setattr(p, k, v)
+    p.el_deg = el.ctypes.data_as(C.POINTER(C.c_float))
+    p._keep = el
+    return p
+
+
+def lidar_directions(sensor) -> np.ndarray:
+    """the sensor's beam directions in its own frame (sm_lidar_directions): float32[n_el][n_az][3]"""
+    d = np.zeros((max(sensor.n_el, 0), max(sensor.n_az, 0), 3), np.float32)
+    rc = load().sm_lidar_directions(C.byref(sensor), _ptr(d))
+    if rc:
+        raise SurfelMapError("sm_lidar_directions", rc, load().sm_last_error().decode())
+    return d
+
+
+def lidar_points(range, dirs, rgb=None) -> np.ndarray:
+    """the returns of a sweep as KITTI velodyne points: float32[N][4] = (z, -x, -y) of t*d in the sensor frame (x forward, y left,
+    z up) and the reflectance -- the luminance of rgb by the colour tracker's weights, ((0.299 r + 0.587 g) + 0.114 b) / 255 in
+    float32, or 0 without rgb.  Beams without a return (range 0) are left out; the order is the grid's, row-major."""
+    f32 = np.float32
+    t = np.ascontiguousarray(range, f32).reshape(-1)
+    d = np.ascontiguousarray(dirs, f32).reshape(-1, 3)
+    got = t > 0
+    p = t[got, None] * d[got]
+    out = np.zeros((int(got.sum()), 4), f32)
+    out[:, 0], out[:, 1], out[:, 2] = p[:, 2], -p[:, 0], -p[:, 1]
+    if rgb is not None:
+        c = np.ascontiguousarray(rgb, np.uint8).reshape(-1, 3)[got].astype(f32)
+        out[:, 3] = ((f32(0.299) * c[:, 0] + f32(0.587) * c[:, 1]) + f32(0.114) * c[:, 2]) / f32(255.0)
+    return out
+
+
+def lidar_rays(sensor, poses16) -> np.ndarray:
+    """The beams of a sweep as rays for SurfelMap.cast_rays: float32[n_el * n_az][8] = (origin, t_min, dir, t_max), row-major over
+    the sensor's grid.  poses16: one sensor->world pose (float32[16] column-major or 4x4), or n_az of them, one per column -- the
+    sweep of a vehicle that moves while the sensor turns.  The origin is the pose's translation, the direction R * d of
+    lidar_directions' table, computed in double ((R0 dx + R1 dy) + R2 dz, terms with a zero coefficient left out) and rounded
+    once; t_min / t_max are the sensor's range limits.  Needs no context."""
+    d = lidar_directions(sensor).astype(np.float64)                       # [n_el][n_az][3]
+    n_el, n_az = d.shape[0], d.shape[1]
+    P = np.asarray(poses16, np.float32)
+    if P.ndim >= 2 and P.shape[-2:] == (4, 4):
+        P = np.swapaxes(P, -1, -2)                                        # (numpy row/col indexing -> column-major)
+    P = np.ascontiguousarray(P).reshape(-1, 16)
+    if P.shape[0] not in (1, n_az):
+        raise ValueError("poses16: one pose, or one per column (n_az)")
+    P = np.broadcast_to(P, (n_az, 16))
+    R = P.astype(np.float64).reshape(n_az, 4, 4)[:, :3, :3]               # R[j][c][r]: column c, row r of pose j
+    # a term whose coefficient is 0 is left out (-0.0 is the sum's neutral element), so an identity rotation returns d bit for bit
+    term = [np.where(R[None, :, c, :] != 0.0, R[None, :, c, :] * d[:, :, None, c], -0.0) for c in range(3)]
+    dirs = (term[0] + term[1]) + term[2]
+    rays = np.zeros((n_el, n_az, 8), np.float32)
+    rays[:, :, 0:3] = P[None, :, 12:15]
+    rays[:, :, 3] = np.float32(sensor.min_range)
+    rays[:, :, 4:7] = dirs.astype(np.float32)
+    rays[:, :, 7] = np.float32(sensor.max_range)
+    return rays.reshape(n_el * n_az, 8)
+
+
+def scene_poses12(poses) -> np.ndarray:
+    """actor->world poses as the scene calls take them, float32[V][12] ROW-major 3x4 [R|t]: from float32[V][12] as they are, or
+    from [V][4][4] matrices (their top three rows)"""
+    p = np.asarray(poses, np.float32)
+    if p.ndim == 3 and p.shape[1:] == (4, 4):
+        p = p[:, :3, :]
+    return np.ascontiguousarray(p.reshape(-1, 12))
+
+
+def scene(actors, n_views=None) -> SmScene:
+    """a scene's actors: a list of (path, poses[, present]) -- a map file in the actor's own frame, its poses per view
+    (scene_poses12 forms), optionally uint8[V], 0 = not in that view.  n_views: what every actor's arrays must hold (None: not
+    checked).  Keeps the strings and arrays alive."""
+    keep, arr = [], (SmSceneActor * max(len(actors), 1))()
+    for j, a in enumerate(actors):
+        path, poses = os.fsencode(a[0]), scene_poses12(a[1])
+        present = None if len(a) < 3 or a[2] is None else np.ascontiguousarray(a[2], np.uint8).reshape(-1)
+        if n_views is not None and (len(poses) != n_views or (present is not None and len(present) != n_views)):
+            raise ValueError(f"actor {j}: {len(poses)} poses for {n_views} views")
+        arr[j].path = path
+        arr[j].poses12 = poses.ctypes.data_as(C.POINTER(C.c_float))
+        arr[j].present = None if present is None else present.ctypes.data_as(C.POINTER(C.c_uint8))
+        keep.append((path, poses, present))
+    sc = SmScene(C.cast(arr, C.POINTER(SmSceneActor)), len(actors))
+    sc._keep = (keep, arr)
+    return sc
+
+
+def scene_place_rows(pose, rows) -> np.ndarray:
+    """sm_scene_place_rows: float32[N][12] records under one actor->world pose (float32[12] row-major 3x4, or 4x4) by
+    sm_warp_by_time's row rule, on the host"""
+    pose = scene_poses12(np.asarray(pose, np.float32).reshape((1, 4, 4) if np.size(pose) == 16 else (1, 12)))
+    rows = np.ascontiguousarray(rows, np.float32).reshape(-1, 12)
+    out = np.empty_like(rows)
+    rc = load().sm_scene_place_rows(_ptr(pose), _ptr(rows), len(rows), _ptr(out))
+    if rc:
+        raise SurfelMapError("sm_scene_place_rows", rc, load().sm_last_error().decode())
+    return out
+
+
+def fern_table(params, width, height) -> np.ndarray:
+    """sm_fern_table: the ferns of `params` for an image size, a structured array (x, y, tr, tg, tb, td; uint16).  Host only."""
+    L = load()
+    out = np.zeros(max(int(params.n_ferns), 0), FERN_DTYPE)
+    rc = L.sm_fern_table(C.byref(params), int(width), int(height), _ptr(out))
+    if rc != SM_OK:
+        raise SurfelMapError("sm_fern_table", rc, L.sm_last_error().decode())
+    return out
+
+
+def segment_boxes(components, voxel_mm=200, origin=(0.0, 0.0, 0.0)):
+    """(lo, hi, centroid), float64[n, 3] each, in metres, of the rows of a component table: the box of a component's cells -- from
+    the low face of cell_lo to the high face of cell_hi -- and the mean over its records of their cells' centres"""
+    c = np.asarray(components, SEGMENT_COMPONENT).reshape(-1)
+    edge = ((int(voxel_mm) * 65536 + 500) // 1000) / 65536.0
+    o = np.asarray([np.float32(v) for v in origin], np.float64)
+    lo = o + c["cell_lo"].astype(np.float64) * edge
+    hi = o + (c["cell_hi"].astype(np.float64) + 1.0) * edge
+    mean = c["sum_cell"].astype(np.float64) / np.maximum(c["records"], 1).astype(np.float64)[:, None] - 65536.0 + 0.5
+    return lo, hi, o + mean * edge
+
+
+_PLY_PROPERTIES = ["property float x", "property float y", "property float z", "property float nx", "property float ny", "property float nz",
+                   "property uchar red", "property uchar green", "property uchar blue", "property uchar class"]
+
+
+def read_ply(path):
+    """(vertices: MESH_VERTEX[n], faces: uint32[m, 3]) of a file sm_mesh_maps wrote -- that layout alone: binary little-endian, per
+    vertex x y z nx ny nz as float and red green blue class as uchar, per face `list uchar int vertex_indices` of three.  The colour
+    word is put together again: blue, green, red in bytes 0..2, the class in byte 3."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header\n")
+    if end < 0:
+        raise ValueError(f"{path}: no PLY header")
+    lines = data[:end].decode("ascii").split("\n")
+    body = data[end + len(b"end_header\n"):]
+    if lines[:2] != ["ply", "format binary_little_endian 1.0"]:
+        raise ValueError(f"{path}: not a binary little-endian PLY")
+    lines = [l for l in lines[2:] if l and not l.startswith("comment")]
+    if (len(lines) != 13 or not lines[0].startswith("element vertex ") or lines[1:11] != _PLY_PROPERTIES or not lines[11].startswith("element face ")
+            or lines[12] != "property list uchar int vertex_indices"):
+        raise ValueError(f"{path}: not the layout sm_mesh_maps writes")
+    nv, nf = int(lines[0].split()[2]), int(lines[11].split()[2])
+    if len(body) != nv * 28 + nf * 13:
+        raise ValueError(f"{path}: {len(body)} bytes after the header, {nv} vertices and {nf} faces need {nv * 28 + nf * 13}")
+    raw = np.frombuffer(body, np.dtype([("pos", "<f4", 3), ("normal", "<f4", 3), ("rgbc", "u1", 4)]), nv)
+    vertices = np.zeros(nv, MESH_VERTEX)
+    vertices["pos"], vertices["normal"] = raw["pos"], raw["normal"]
+    c = raw["rgbc"].astype(np.uint32)
+    vertices["colour"] = c[:, 3] << 24 | c[:, 0] << 16 | c[:, 1] << 8 | c[:, 2]
+    rows = np.frombuffer(body, np.dtype([("n", "u1"), ("v", "<i4", 3)]), nf, nv * 28)
+    if nf and (rows["n"] != 3).any():
+        raise ValueError(f"{path}: a face that is no triangle")
+    return vertices, rows["v"].view(np.uint32).copy().reshape(-1, 3)
+
+
+def _track_info_dict(info, rinfo=None, anchor=None) -> dict:
+    """SmTrackInfo as the trackers' info dict; rinfo (SmTrackRgbInfo) and anchor (c_float) add their keys when given"""
+    d = dict(status=TRACK_STATUS.get(info.status, str(info.status)), status_code=int(info.status), iterations=int(info.iterations),
+             inliers=int(info.inliers), rmse=float(info.rmse), guess=np.array(info.guess[:], np.float32).reshape(4, 4).T.copy())
+    if rinfo is not None:
+        d.update(rgb_inliers=int(rinfo.rgb_inliers), rgb_rmse=float(rinfo.rgb_rmse), pivot_ratio=float(rinfo.pivot_ratio),
+                 level_iterations=[int(x) for x in rinfo.level_iterations])
+    if anchor is not None:
+        d["anchor_time"] = float(anchor.value)
+    return d
+
+
+def _loop_info_dict(info) -> dict:
+    return dict(status=LOOP_STATUS.get(info.status, str(info.status)), status_code=int(info.status), track=_track_info_dict(info.track),
+                D=np.array(info.D[:], np.float32).reshape(4, 4).T.copy(), t_a=int(info.t_a), t_b=int(info.t_b))
+
+
+def loop_spread(D, t_a, t_b) -> np.ndarray:
+    """sm_loop_spread: the table float32[t_b - t_a + 1][12] (row-major 3x4 [R|t] per tick) that ramps the world->world correction D
+    (4x4, numpy row/col indexing, or float32[16] column-major) from nothing at tick t_a to all of it at t_b.  Host only."""
+    L = load()
+    d = _mat16(D)
+    t_a, t_b = int(t_a), int(t_b)
+    out = np.zeros((max(t_b - t_a + 1, 1), 12), np.float32)
+    rc = L.sm_loop_spread(_ptr(d), t_a, t_b, _ptr(out))
+    if rc != SM_OK:
+        raise SurfelMapError("sm_loop_spread", rc, L.sm_last_error().decode())
+    return out
+
+
+def model_view(mvp, mv_inv, w, h, threshold=0.0, color_type=0, unstable=True, points=False, window=False, time=0,
+               time_delta=0, clear=(0, 0, 0, 0)) -> SmModelView:
+    v = SmModelView()
+    v.mvp[:] = [float(x) for x in _mat16(mvp)]
+    v.mv_inv[:] = [float(x) for x in _mat16(mv_inv)]
+    v.threshold = threshold
+    v.color_type, v.draw_unstable, v.draw_points, v.draw_window = int(color_type), int(bool(unstable)), int(bool(points)), int(bool(window))
+    v.time, v.time_delta, v.width, v.height = int(time), int(time_delta), int(w), int(h)
+    v.clear_rgba[:] = [int(c) for c in clear]
+    return v
+
+
+def _view_planes(shape, depth):
+    """the outputs of a novel-view call: bgr uint8[shape][3], sem uint8[shape], depth_mm uint16[shape] (None unless depth)"""
+    return np.zeros(tuple(shape) + (3,), np.uint8), np.zeros(shape, np.uint8), np.zeros(shape, np.uint16) if depth else None
+
+
+# =====================================================================================================================
+# SurfelMap
+# =====================================================================================================================
 class SurfelMap:
     """Host-side handle mirroring SurfelMapping / GlobalModel / IndexMap of the reference
     (src/SurfelMapping.h:31-96, src/GlobalModel.h:22-120, src/IndexMap.h:34-88)."""
@@ -1361,6 +1238,61 @@ class SurfelMap:
         if rc not in allow:
             raise SurfelMapError(what, rc, self._L.sm_last_error().decode())
         return rc
+
+    def _stats(self, struct, getter) -> dict:
+        """the fields of a stats structure read through its getter, int getter(ctx, struct *out).  A NEW STATS STRUCTURE takes its
+        xxx_stats() with one call of this."""
+        st = struct()
+        self._chk(getattr(self._L, getter)(self._h, C.byref(st)), getter)
+        return _as_dict(st)
+
+    def _row_count(self, fn):
+        """how many float32[12] rows the count-then-fetch entry point `fn` holds -- its call without a destination (a c_uint32)"""
+        n = C.c_uint32()
+        self._chk(getattr(self._L, fn)(self._h, None, 0, C.byref(n)), fn)
+        return n
+
+    def _fetch_rows(self, fn, n) -> np.ndarray:
+        """... and the n rows themselves"""
+        out = np.zeros((n.value, 12), np.float32)
+        self._chk(getattr(self._L, fn)(self._h, _ptr(out), n.value, C.byref(n)), fn)
+        return out
+
+    def _label_buffer(self, paths, include_model, empty, dtype) -> np.ndarray:
+        """the label buffer of a map set, one entry per record, filled with `empty`: the records of the files are known from their
+        headers, the live model's count from the context"""
+        n = sum(_map_records(q) for q in paths)
+        if include_model:
+            n += self._row_count("sm_download_model_aos").value
+        return np.full(n, empty, dtype)
+
+    def _check_labels(self, lab, records, what, detail):
+        """the call has counted the set's records: a label buffer of another length was sized for another set"""
+        if lab is not None and len(lab) != records:
+            raise SurfelMapError(what, SM_E_ARG, detail)
+
+    def _novel_views(self, stem, head, shape, camera, fill, depth, blend):
+        """The novel views of render_image and render_image_maps: the output planes, and the entry point of the family `stem` that
+        the arguments ask for -- stem_blend with blend, stem itself with neither fill nor depth, else stem_ex.  head: the arguments
+        between the context and camera = (w, h, fx, fy, cx, cy).  Returns (bgr, sem) or (bgr, sem, depth_mm)."""
+        bgr, sem, d = _view_planes(shape, depth)
+        fp, bp = _fill_arg(fill), _blend_arg(blend)
+        fill_ref = C.byref(fp) if fp is not None else None
+        if bp is not None:
+            fn, tail = stem + "_blend", (C.byref(bp), fill_ref, _ptr(bgr), _ptr(sem), _ptr(d))
+        elif fp is None and not depth:
+            fn, tail = stem, (_ptr(bgr), _ptr(sem))
+        else:
+            fn, tail = stem + "_ex", (fill_ref, _ptr(bgr), _ptr(sem), _ptr(d))
+        self._chk(getattr(self._L, fn)(self._h, *head, *camera, *tail), fn)
+        return (bgr, sem, d) if depth else (bgr, sem)
+
+    def _lidar_sweep(self, fn, shape, *head) -> dict:
+        """the sweep calls: the four output planes of `shape`, filled by `fn`(ctx, *head, range, id, rgb, sem)"""
+        out = dict(range=np.zeros(shape, np.float32), id=np.zeros(shape, np.int32), rgb=np.zeros(tuple(shape) + (3,), np.uint8),
+                   sem=np.zeros(shape, np.uint8))
+        self._chk(getattr(self._L, fn)(self._h, *head, *[_ptr(out[k]) for k in ("range", "id", "rgb", "sem")]), fn)
+        return out
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1530,10 +1462,8 @@ class SurfelMap:
     def track_stats(self):
         """device times in ms of the last track()/track_debug() call made with SM_TRACK_TIMING=1 (sm_debug_track_stats, not part
         of the C-ABI header): [prediction, vertex stage, reduce_0, solve_0, reduce_1, solve_1, ...], or [] if it was not timed"""
-        f = self._L.sm_debug_track_stats
-        f.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int)]
         ms, n = (C.c_float * 256)(), C.c_int()
-        self._chk(f(self._h, ms, 256, C.byref(n)), "sm_debug_track_stats")
+        self._chk(self._L.sm_debug_track_stats(self._h, ms, 256, C.byref(n)), "sm_debug_track_stats")
         return [float(x) for x in ms[:n.value]]
 
     def process_frame_tracked(self, rgb, depth, sem, guess=None, **params):
@@ -1564,10 +1494,8 @@ class SurfelMap:
         """device times of the last track_rgb()/track_rgb_debug() call made with SM_TRACK_TIMING=1 (sm_debug_track_rgb_stats, not
         part of the C-ABI header): a list of (kind, level, ms), kind one of "prediction", "vertex", "pyramid", "gather",
         "level_vertex", "icp", "photo", "solve"; [] if it was not timed"""
-        f = self._L.sm_debug_track_rgb_stats
-        f.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]
         ms, kind, n = (C.c_float * 512)(), (C.c_int * 512)(), C.c_int()
-        self._chk(f(self._h, ms, kind, 512, C.byref(n)), "sm_debug_track_rgb_stats")
+        self._chk(self._L.sm_debug_track_rgb_stats(self._h, ms, kind, 512, C.byref(n)), "sm_debug_track_rgb_stats")
         names = ("prediction", "vertex", "pyramid", "gather", "level_vertex", "icp", "photo", "solve")
         return [(names[kind[i] & 15], kind[i] >> 4, float(ms[i])) for i in range(n.value)]
 
@@ -1585,11 +1513,7 @@ class SurfelMap:
         return c.as_dict()
 
     def download_model(self) -> np.ndarray:
-        n = C.c_uint32()
-        self._chk(self._L.sm_download_model_aos(self._h, None, 0, C.byref(n)), "sm_download_model_aos")
-        out = np.zeros((n.value, 12), np.float32)
-        self._chk(self._L.sm_download_model_aos(self._h, _ptr(out), n.value, C.byref(n)), "sm_download_model_aos")
-        return out
+        return self._fetch_rows("sm_download_model_aos", self._row_count("sm_download_model_aos"))
 
     def upload_model(self, m):
         m = np.ascontiguousarray(m, np.float32)
@@ -1638,10 +1562,8 @@ class SurfelMap:
     def retire_stats(self):
         """device times in ms of the last retirement made with SM_RETIRE_TIMING=1 (sm_debug_retire_stats, not part of the C-ABI
         header): dict(mark, scan, gather, compact, bounds), or None if it was not timed"""
-        f = self._L.sm_debug_retire_stats
-        f.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         ms = (C.c_float * 5)()
-        self._chk(f(self._h, ms), "sm_debug_retire_stats")
+        self._chk(self._L.sm_debug_retire_stats(self._h, ms), "sm_debug_retire_stats")
         return None if ms[0] < 0 else dict(zip(("mark", "scan", "gather", "compact", "bounds"), [float(x) for x in ms]))
 
     # -- paging in (sm_recall, sm_set_auto_recall)
@@ -1662,9 +1584,7 @@ class SurfelMap:
     def recall_stats(self) -> dict:
         """of the last recall (the policy's included): files_listed, files_skipped (by the file index), files_read,
         files_rewritten, records_read, recalled, chunks, read_ms, copy_ms, device_ms, write_ms, total_ms"""
-        st = SmRecallStats()
-        self._chk(self._L.sm_recall_stats(self._h, C.byref(st)), "sm_recall_stats")
-        return {k: getattr(st, k) for k, _ in SmRecallStats._fields_}
+        return self._stats(SmRecallStats, "sm_recall_stats")
 
     def set_auto_recall(self, **params):
         """While set_auto_retire is on: after every retirement, move back the records of its files within `radius` of that
@@ -1692,9 +1612,7 @@ class SurfelMap:
     def warp_stats(self) -> dict:
         """of the last warp_by_time: files_listed, files_skipped (by the file index), files_read, files_rewritten, records_read,
         records_moved, model_moved, chunks, read_ms, copy_ms, device_ms, write_ms, total_ms"""
-        st = SmWarpStats()
-        self._chk(self._L.sm_warp_stats(self._h, C.byref(st)), "sm_warp_stats")
-        return {k: getattr(st, k) for k, _ in SmWarpStats._fields_}
+        return self._stats(SmWarpStats, "sm_warp_stats")
 
     def track_old(self, depth, max_time, guess=None, **params):
         """track() against the map as it was: the prediction holds only surfels last updated at or before max_time
@@ -1753,10 +1671,8 @@ class SurfelMap:
     def census_ms(self):
         """device time in ms of the census kernel of the last old_in_view() made with SM_TRACK_TIMING=1 (sm_debug_census_ms, not
         part of the C-ABI header); None if it was not timed"""
-        f = self._L.sm_debug_census_ms
-        f.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         ms = C.c_float()
-        self._chk(f(self._h, C.byref(ms)), "sm_debug_census_ms")
+        self._chk(self._L.sm_debug_census_ms(self._h, C.byref(ms)), "sm_debug_census_ms")
         return None if ms.value < 0 else float(ms.value)
 
     def track_window(self, depth, min_time, max_time, guess=None, **params):
@@ -2028,12 +1944,8 @@ class SurfelMap:
 
     def download_raw_cloud(self) -> np.ndarray:
         """FeedbackBuffer "RAW": the raw camera-frame surfel cloud of the last processed frame, float32 [n][12]."""
-        n = C.c_uint32()
-        self._chk(self._L.sm_download_raw_cloud(self._h, None, 0, C.byref(n)), "sm_download_raw_cloud")
-        out = np.zeros((n.value, 12), np.float32)
-        if n.value:
-            self._chk(self._L.sm_download_raw_cloud(self._h, _ptr(out), n.value, C.byref(n)), "sm_download_raw_cloud")
-        return out
+        n = self._row_count("sm_download_raw_cloud")
+        return self._fetch_rows("sm_download_raw_cloud", n) if n.value else np.zeros((0, 12), np.float32)
 
     def download_depth(self, which=TEX_DEPTH_METRIC):
         out = np.zeros((self.H, self.W), np.float32)
@@ -2046,23 +1958,7 @@ class SurfelMap:
         blend (True, a dict of overrides or blend_params(...)): bgr is the blend of the visible layer's discs, not the nearest
         disc's colour (sm_render_image_blend; blend_stats())."""
         view = np.ascontiguousarray(view, np.float32)
-        bgr = np.zeros((h, w, 3), np.uint8)
-        sem = np.zeros((h, w), np.uint8)
-        fp = _fill_arg(fill)
-        bp = _blend_arg(blend)
-        if bp is not None:
-            d = np.zeros((h, w), np.uint16) if depth else None
-            self._chk(self._L.sm_render_image_blend(self._h, _ptr(view), w, h, fx, fy, cx, cy, C.byref(bp),
-                                                    C.byref(fp) if fp is not None else None, _ptr(bgr), _ptr(sem), _ptr(d)),
-                      "sm_render_image_blend")
-            return (bgr, sem, d) if depth else (bgr, sem)
-        if fp is None and not depth:
-            self._chk(self._L.sm_render_image(self._h, _ptr(view), w, h, fx, fy, cx, cy, _ptr(bgr), _ptr(sem)), "sm_render_image")
-            return bgr, sem
-        d = np.zeros((h, w), np.uint16) if depth else None
-        self._chk(self._L.sm_render_image_ex(self._h, _ptr(view), w, h, fx, fy, cx, cy, C.byref(fp) if fp is not None else None,
-                                             _ptr(bgr), _ptr(sem), _ptr(d)), "sm_render_image_ex")
-        return (bgr, sem, d) if depth else (bgr, sem)
+        return self._novel_views("sm_render_image", (_ptr(view),), (h, w), (w, h, fx, fy, cx, cy), fill, depth, blend)
 
     # -- hole filling (sm_fill_*)
     def fill_image(self, bgr, sem, depth_mm=None, fill=None):
@@ -2089,15 +1985,11 @@ class SurfelMap:
     def fill_stats(self) -> dict:
         """of the last call that filled (sm_fill_stats): valid, seen_through, filled, left_empty (pixels, summed over the images),
         launches, device_ms"""
-        st = SmFillStats()
-        self._chk(self._L.sm_fill_stats(self._h, C.byref(st)), "sm_fill_stats")
-        return {k: getattr(st, k) for k, _ in SmFillStats._fields_}
+        return self._stats(SmFillStats, "sm_fill_stats")
 
     def blend_stats(self) -> dict:
         """of the last blended call (sm_blend_stats): drawn, contributions, changed (summed over its views), launches, device_ms"""
-        st = SmBlendStats()
-        self._chk(self._L.sm_blend_stats(self._h, C.byref(st)), "sm_blend_stats")
-        return {k: getattr(st, k) for k, _ in SmBlendStats._fields_}
+        return self._stats(SmBlendStats, "sm_blend_stats")
 
     def render_model(self, mvp, mv_inv, w, h, threshold=0.0, color_type=0, unstable=True, points=False, window=False,
                      time=0, time_delta=0, clear=(0, 0, 0, 0), depth=False, ids=False):
@@ -2124,10 +2016,8 @@ class SurfelMap:
     def render_model_stats(self):
         """diagnostic of the last render_model* call (sm_debug_render_model_stats, not part of the C-ABI header): (surfels on the
         overflow path, [splat, overflow, resolve] ms or None unless SM_RENDER_MODEL_TIMING=1 was set for that call)"""
-        f = self._L.sm_debug_render_model_stats
-        f.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
         n, ms = C.c_uint32(), (C.c_float * 3)()
-        self._chk(f(self._h, C.byref(n), ms), "sm_debug_render_model_stats")
+        self._chk(self._L.sm_debug_render_model_stats(self._h, C.byref(n), ms), "sm_debug_render_model_stats")
         return int(n.value), (None if ms[0] < 0 else [float(x) for x in ms])
 
     # -- views of a map set (sm_render_image_maps, sm_render_model_maps)
@@ -2140,26 +2030,9 @@ class SurfelMap:
         (sm_render_image_maps_blend): every file is then read twice per batch."""
         views = np.ascontiguousarray(views, np.float32).reshape(-1, 16)
         V = views.shape[0]
-        bgr = np.zeros((V, h, w, 3), np.uint8)
-        sem = np.zeros((V, h, w), np.uint8)
         src = map_source(paths, include_model)
-        fp = _fill_arg(fill)
-        bp = _blend_arg(blend)
-        if bp is not None:
-            d = np.zeros((V, h, w), np.uint16) if depth else None
-            self._chk(self._L.sm_render_image_maps_blend(self._h, C.byref(src), _ptr(views), V, w, h, fx, fy, cx, cy, C.byref(bp),
-                                                         C.byref(fp) if fp is not None else None, _ptr(bgr), _ptr(sem), _ptr(d)),
-                      "sm_render_image_maps_blend")
-            return (bgr, sem, d) if depth else (bgr, sem)
-        if fp is None and not depth:
-            self._chk(self._L.sm_render_image_maps(self._h, C.byref(src), _ptr(views), V, w, h, fx, fy, cx, cy, _ptr(bgr), _ptr(sem)),
-                      "sm_render_image_maps")
-            return bgr, sem
-        d = np.zeros((V, h, w), np.uint16) if depth else None
-        self._chk(self._L.sm_render_image_maps_ex(self._h, C.byref(src), _ptr(views), V, w, h, fx, fy, cx, cy,
-                                                  C.byref(fp) if fp is not None else None, _ptr(bgr), _ptr(sem), _ptr(d)),
-                  "sm_render_image_maps_ex")
-        return (bgr, sem, d) if depth else (bgr, sem)
+        return self._novel_views("sm_render_image_maps", (C.byref(src), _ptr(views), V), (V, h, w), (w, h, fx, fy, cx, cy),
+                                 fill, depth, blend)
 
     def render_model_maps(self, paths, views, include_model=True, depth=False, ids=False):
         """Model views of a map set (see render_image_maps): `views` is a list of model_view(...) structs -- the arguments of
@@ -2182,9 +2055,7 @@ class SurfelMap:
     def render_maps_stats(self) -> dict:
         """of the last render_*_maps call: surfels_read, chunks, passes, pairs_tested, pairs_skipped ((block of 256 records,
         view) pairs the view test ran on / found outside), read_ms, copy_ms, device_ms, total_ms"""
-        st = SmMapsStats()
-        self._chk(self._L.sm_render_maps_stats(self._h, C.byref(st)), "sm_render_maps_stats")
-        return {k: getattr(st, k) for k, _ in SmMapsStats._fields_}
+        return self._stats(SmMapsStats, "sm_render_maps_stats")
 
     # -- lidar sweeps (sm_lidar_sweep, sm_lidar_sweep_maps)
     def lidar_sweep(self, pose, sensor=None) -> dict:
@@ -2193,10 +2064,7 @@ class SurfelMap:
         0).  sensor: lidar_sensor(...); None = the default."""
         sensor = lidar_sensor() if sensor is None else sensor
         pose = _mat16(pose)
-        out = _lidar_planes((sensor.n_el, sensor.n_az))
-        self._chk(self._L.sm_lidar_sweep(self._h, C.byref(sensor), _ptr(pose), *[_ptr(out[k]) for k in ("range", "id", "rgb", "sem")]),
-                  "sm_lidar_sweep")
-        return out
+        return self._lidar_sweep("sm_lidar_sweep", (sensor.n_el, sensor.n_az), C.byref(sensor), _ptr(pose))
 
     def lidar_sweep_maps(self, paths, poses, sensor=None, include_model=True) -> dict:
         """lidar_sweep of a map set (see render_image_maps) from every pose of `poses` (float32[V][16]): the same dict with a
@@ -2204,18 +2072,13 @@ class SurfelMap:
         sensor = lidar_sensor() if sensor is None else sensor
         poses = np.ascontiguousarray(poses, np.float32).reshape(-1, 16)
         V = poses.shape[0]
-        out = _lidar_planes((V, sensor.n_el, sensor.n_az))
         src = map_source(paths, include_model)
-        self._chk(self._L.sm_lidar_sweep_maps(self._h, C.byref(src), C.byref(sensor), _ptr(poses), V,
-                                              *[_ptr(out[k]) for k in ("range", "id", "rgb", "sem")]), "sm_lidar_sweep_maps")
-        return out
+        return self._lidar_sweep("sm_lidar_sweep_maps", (V, sensor.n_el, sensor.n_az), C.byref(src), C.byref(sensor), _ptr(poses), V)
 
     def lidar_stats(self) -> dict:
         """of the last lidar_sweep* call: surfels offered, exact tests, wide (surfel, sweep) pairs, blocks_skipped, chunks, passes,
         read_ms, copy_ms, device_ms, total_ms"""
-        st = SmLidarStats()
-        self._chk(self._L.sm_lidar_stats(self._h, C.byref(st)), "sm_lidar_stats")
-        return {k: getattr(st, k) for k, _ in SmLidarStats._fields_}
+        return self._stats(SmLidarStats, "sm_lidar_stats")
 
     # -- ray casts (sm_cast_rays_maps)
     def cast_rays(self, rays, paths=(), include_model=True, cell_mm=250, origin=None, min_conf=0.0, normal=False) -> dict:
@@ -2240,9 +2103,7 @@ class SurfelMap:
     def cast_rays_stats(self) -> dict:
         """of the last cast_rays: rays, bad_rays, records, wide, pairs and cells (of the largest chunk), probes, tests, no_slot, gave_up, chunks,
         files_skipped (always 0), read_ms, copy_ms, index_ms, cast_ms, device_ms, total_ms"""
-        st = SmRaysStats()
-        self._chk(self._L.sm_cast_rays_stats(self._h, C.byref(st)), "sm_cast_rays_stats")
-        return {k: getattr(st, k) for k, _ in SmRaysStats._fields_}
+        return self._stats(SmRaysStats, "sm_cast_rays_stats")
 
     # -- scenes (sm_render_image_scene, sm_lidar_sweep_scene)
     def render_scene(self, paths, actors, views, w, h, fx, fy, cx, cy, include_model=True, fill=None, depth=False):
@@ -2252,11 +2113,9 @@ class SurfelMap:
         moved by sm_warp_by_time's row rule.  Returns (bgr, sem[, depth_mm]) as render_image_maps."""
         views = np.ascontiguousarray(views, np.float32).reshape(-1, 16)
         V = views.shape[0]
-        bgr = np.zeros((V, h, w, 3), np.uint8)
-        sem = np.zeros((V, h, w), np.uint8)
-        d = np.zeros((V, h, w), np.uint16) if depth else None
         src = map_source(paths, include_model)
         sc = scene(actors, V)
+        bgr, sem, d = _view_planes((V, h, w), depth)
         fp = _fill_arg(fill)
         self._chk(self._L.sm_render_image_scene(self._h, C.byref(src), C.byref(sc), _ptr(views), V, w, h, fx, fy, cx, cy,
                                                 C.byref(fp) if fp is not None else None, _ptr(bgr), _ptr(sem), _ptr(d)),
@@ -2269,19 +2128,15 @@ class SurfelMap:
         sensor = lidar_sensor() if sensor is None else sensor
         poses = np.ascontiguousarray(poses, np.float32).reshape(-1, 16)
         V = poses.shape[0]
-        out = _lidar_planes((V, sensor.n_el, sensor.n_az))
         src = map_source(paths, include_model)
         sc = scene(actors, V)
-        self._chk(self._L.sm_lidar_sweep_scene(self._h, C.byref(src), C.byref(sc), C.byref(sensor), _ptr(poses), V,
-                                               *[_ptr(out[k]) for k in ("range", "id", "rgb", "sem")]), "sm_lidar_sweep_scene")
-        return out
+        return self._lidar_sweep("sm_lidar_sweep_scene", (V, sensor.n_el, sensor.n_az), C.byref(src), C.byref(sc), C.byref(sensor),
+                                 _ptr(poses), V)
 
     def scene_stats(self) -> dict:
         """of the last render_scene / lidar_sweep_scene call (sm_scene_stats): actors, files (distinct), records and bytes
         resident, pairs_tested / pairs_skipped ((actor block of 256, view) pairs), load_ms, actor_ms, total_ms"""
-        st = SmSceneStats()
-        self._chk(self._L.sm_scene_stats(self._h, C.byref(st)), "sm_scene_stats")
-        return {k: getattr(st, k) for k, _ in SmSceneStats._fields_}
+        return self._stats(SmSceneStats, "sm_scene_stats")
 
     # -- simplification (sm_simplify, sm_simplify_maps)
     def simplify(self, **params) -> dict:
@@ -2314,9 +2169,7 @@ class SurfelMap:
     def tile_stats(self) -> dict:
         """of the last tile_maps: records_in, placed, loose, tiles, largest_tile, files_written, readings, chunks, launches,
         sort_passes, device_ms, sort_ms, read_ms, write_ms, total_ms"""
-        st = SmTileStats()
-        self._chk(self._L.sm_tile_stats(self._h, C.byref(st)), "sm_tile_stats")
-        return {k: getattr(st, k) for k, _ in SmTileStats._fields_}
+        return self._stats(SmTileStats, "sm_tile_stats")
 
     # -- registration of one map set against another (sm_register_maps)
     def register_maps(self, source_paths, target_paths, guess=None, source_model=False, target_model=False, apply=False, **params):
@@ -2358,9 +2211,7 @@ class SurfelMap:
     def register_stats(self) -> dict:
         """of the last register_maps / register_debug: source_records, target_records, chunks, launches, read_ms, table_ms,
         iterate_ms, total_ms"""
-        st = SmRegisterStats()
-        self._chk(self._L.sm_register_stats(self._h, C.byref(st)), "sm_register_stats")
-        return {k: getattr(st, k) for k, _ in SmRegisterStats._fields_}
+        return self._stats(SmRegisterStats, "sm_register_stats")
 
     # -- segmentation of a map set into connected voxel components (sm_segment_maps)
     def segment_maps(self, paths, include_model=False, labels=True, max_components=1 << 20, out_path=None, **params) -> dict:
@@ -2375,15 +2226,7 @@ class SurfelMap:
         p = segment_params(**params)
         src = map_source(paths, include_model=include_model)
         info = SmSegmentInfo()
-        lab = None
-        if labels:
-            # the records of the set are known from the headers; the live model's count from the context
-            n = sum(_map_records(q) for q in paths)
-            if include_model:
-                live = C.c_uint32()
-                self._chk(self._L.sm_download_model_aos(self._h, None, 0, C.byref(live)), "sm_download_model_aos")
-                n += live.value
-            lab = np.full(n, 0xFFFFFFFF, np.uint32)
+        lab = self._label_buffer(paths, include_model, 0xFFFFFFFF, np.uint32) if labels else None
         cap = int(max_components)
         rows = np.zeros(cap, SEGMENT_COMPONENT)
         out = None if out_path is None else os.fsencode(out_path)
@@ -2392,15 +2235,12 @@ class SurfelMap:
         counts = [int(v) for v in info.counts]
         d = dict(records=int(info.records), counts=dict(zip(SEGMENT_KINDS, counts)), counts_by_kind=counts, written=int(info.written),
                  cells=int(info.cells), components=int(info.components), small_components=int(info.small_components), largest=int(info.largest))
-        if lab is not None and len(lab) != d["records"]:
-            raise SurfelMapError("segment_maps", SM_E_ARG, "the set changed while it was segmented")
+        self._check_labels(lab, d["records"], "segment_maps", "the set changed while it was segmented")
         return dict(labels=lab, components=rows[:min(cap, d["components"])].copy(), info=d)
 
     def segment_stats(self) -> dict:
         """of the last segment_maps: chunks, launches, readings, read_ms, table_ms, link_ms, label_ms, write_ms, total_ms"""
-        st = SmSegmentStats()
-        self._chk(self._L.sm_segment_stats(self._h, C.byref(st)), "sm_segment_stats")
-        return {k: getattr(st, k) for k, _ in SmSegmentStats._fields_}
+        return self._stats(SmSegmentStats, "sm_segment_stats")
 
     # -- a map set as a triangle mesh (sm_mesh_maps)
     def mesh_maps(self, paths, include_model=False, ply_path=None, max_vertices=None, max_faces=None, **params) -> dict:
@@ -2430,9 +2270,7 @@ class SurfelMap:
 
     def mesh_stats(self) -> dict:
         """of the last mesh_maps: chunks, launches, read_ms, table_ms, field_ms, sort_ms, emit_ms, write_ms, total_ms"""
-        st = SmMeshStats()
-        self._chk(self._L.sm_mesh_stats(self._h, C.byref(st)), "sm_mesh_stats")
-        return {k: getattr(st, k) for k, _ in SmMeshStats._fields_}
+        return self._stats(SmMeshStats, "sm_mesh_stats")
 
     # -- a map set as a planner's ground map (sm_ground_maps)
     def ground_maps(self, paths, include_model=False, planes=GROUND_PLANES, **params) -> dict:
@@ -2464,9 +2302,7 @@ class SurfelMap:
     def ground_stats(self) -> dict:
         """of the last ground_maps: chunks, launches, files_skipped, read_ms, ground_ms, fill_ms, accumulate_ms, state_ms, clear_ms,
         copy_ms, total_ms"""
-        st = SmGroundStats()
-        self._chk(self._L.sm_ground_stats(self._h, C.byref(st)), "sm_ground_stats")
-        return {k: getattr(st, k) for k, _ in SmGroundStats._fields_}
+        return self._stats(SmGroundStats, "sm_ground_stats")
 
     # -- change detection between two map sets (sm_compare_maps)
     def compare_maps(self, query_paths, reference_paths, pose=None, query_model=False, reference_model=False, out_path=None, labels=True,
@@ -2481,23 +2317,14 @@ class SurfelMap:
         qry, ref = map_source(query_paths, include_model=query_model), map_source(reference_paths, include_model=reference_model)
         g = None if pose is None else _mat16(pose)
         info = SmCompareInfo()
-        lab = None
-        if labels:
-            # the records of the set are known from the headers; the live model's count from the context
-            n = sum(_map_records(q) for q in query_paths)
-            if query_model:
-                live = C.c_uint32()
-                self._chk(self._L.sm_download_model_aos(self._h, None, 0, C.byref(live)), "sm_download_model_aos")
-                n += live.value
-            lab = np.full(n, 255, np.uint8)
+        lab = self._label_buffer(query_paths, query_model, 255, np.uint8) if labels else None
         out = None if out_path is None else os.fsencode(out_path)
         self._chk(self._L.sm_compare_maps(self._h, C.byref(qry), C.byref(ref), _ptr(g), C.byref(p), _ptr(lab), out, C.byref(info)), "sm_compare_maps")
         codes = [int(v) for v in info.counts]
         d = dict(counts={COMPARE_LABEL[l]: codes[l] for l in range(4)}, counts_by_code=codes, query_records=int(info.query_records),
                  reference_records=int(info.reference_records), cells_fine=int(info.cells_fine), cells_cover=int(info.cells_cover),
                  written=int(info.written))
-        if lab is not None and len(lab) != d["query_records"]:
-            raise SurfelMapError(SM_E_ARG, "compare_maps: the query set changed while it was compared")
+        self._check_labels(lab, d["query_records"], "compare_maps", "the query set changed while it was compared")
         return lab, d
 
     def diff_maps(self, a_paths, b_paths, pose_a_to_b=None, out_appeared=None, out_vanished=None, **params):
@@ -2514,16 +2341,12 @@ class SurfelMap:
 
     def compare_stats(self) -> dict:
         """of the last compare_maps: chunks, launches, read_ms, table_ms, classify_ms, write_ms, total_ms"""
-        st = SmCompareStats()
-        self._chk(self._L.sm_compare_stats(self._h, C.byref(st)), "sm_compare_stats")
-        return {k: getattr(st, k) for k, _ in SmCompareStats._fields_}
+        return self._stats(SmCompareStats, "sm_compare_stats")
 
     def simplify_stats(self) -> dict:
         """of the last simplify* call: records_in, records_out, cells_merged, loose, largest_cell, chunks, launches, device_ms,
         read_ms, total_ms"""
-        st = SmSimplifyStats()
-        self._chk(self._L.sm_simplify_stats(self._h, C.byref(st)), "sm_simplify_stats")
-        return {k: getattr(st, k) for k, _ in SmSimplifyStats._fields_}
+        return self._stats(SmSimplifyStats, "sm_simplify_stats")
 
     # -- per-pass entry points
     def set_frame(self, rgb=None, depth_metric=None, sem=None):

@@ -267,19 +267,3 @@ def test_arguments_rejected_before_any_device_call():
         assert rc == capi.SM_E_ARG and "color_type" in msg
         rc, msg = call(capi.model_view(O_MVP, O_INV, 32, 32, color_type=-1), fn=fn)
         assert rc == capi.SM_E_ARG and "color_type" in msg
-
-
-def test_model_view_struct_matches_header(tmp_path):
-    import os
-    import subprocess
-    from surfelmapping_amd import capi
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    lines = ['printf("size %zu\\n", sizeof(sm_model_view));'] + [
-        f'printf("{n} %zu\\n", offsetof(sm_model_view, {n}));' for n, _ in capi.SmModelView._fields_]
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "sm_c_api.h"\nint main(void) {\n' + "\n".join(lines) + "\nreturn 0; }\n")
-    subprocess.check_call(["gcc", "-I", os.path.join(root, "include"), "-o", str(tmp_path / "layout"), str(src)])
-    got = dict(l.split() for l in subprocess.check_output([str(tmp_path / "layout")]).decode().splitlines())
-    assert int(got["size"]) == C.sizeof(capi.SmModelView)
-    for n, _ in capi.SmModelView._fields_:
-        assert int(got[n]) == getattr(capi.SmModelView, n).offset, n

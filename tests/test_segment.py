@@ -4,7 +4,6 @@ library's symbols, defaults, header and the argument rules that need no device. 
 path against the restatement, bit for bit."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -282,27 +281,6 @@ def test_argument_rules_that_need_no_device():
     assert L.sm_segment_maps(None, C.byref(src), C.byref(p), None, None, 0, b"segmented.bin", C.byref(info)) == capi.SM_E_ARG
     assert L.sm_segment_stats(None, C.byref(st)) == capi.SM_E_ARG
     assert not os.path.exists("segmented.bin")
-
-
-def test_structs_match_header(tmp_path):
-    from surfelmapping_amd import capi
-    pairs = (("sm_segment_params", capi.SmSegmentParams), ("sm_segment_component", capi.SmSegmentComponent), ("sm_segment_info", capi.SmSegmentInfo),
-             ("sm_segment_stats_t", capi.SmSegmentStats))
-    lines = []
-    for cname, cls in pairs:
-        lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
-        lines += [f'printf("{cname}.{n} %zu\\n", offsetof({cname}, {n}));' for n, _ in cls._fields_]
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "sm_c_api.h"\nint main(void) {\n' + "\n".join(lines) + "\nreturn 0; }\n")
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(tmp_path / "layout"), str(src)])
-    got = dict(l.split() for l in subprocess.check_output([str(tmp_path / "layout")]).decode().splitlines())
-    assert int(got["sm_segment_component"]) == 64
-    for cname, cls in pairs:
-        assert int(got[cname]) == C.sizeof(cls)
-        for n, _ in cls._fields_:
-            assert int(got[f"{cname}.{n}"]) == getattr(cls, n).offset, (cname, n)
-    for n in capi.SEGMENT_COMPONENT.names:
-        assert capi.SEGMENT_COMPONENT.fields[n][1] == getattr(capi.SmSegmentComponent, n).offset, n
 
 
 # ---------------------------------------------------------------------------------------------------------------------

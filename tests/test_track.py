@@ -5,7 +5,6 @@ map (and the oracle's map) built from those poses given explicitly, and tracking
 import ctypes as C
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -279,29 +278,6 @@ def test_null_context_and_defaults_without_a_gpu():
     p = capi.track_params()
     assert (p.max_iters, p.min_inliers, p.pixel_stride) == (15, 1000, 1)
     assert math.isclose(p.dist_thresh, 0.3, rel_tol=1e-7) and p.angle_thresh == 30.0
-
-
-def test_track_structs_match_header(tmp_path):
-    from surfelmapping_amd import capi
-    mirrors = {"sm_track_params": capi.SmTrackParams, "sm_track_info": capi.SmTrackInfo}
-    lines = []
-    for cname, cls in mirrors.items():
-        lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
-        for fname, _ in cls._fields_:
-            lines.append(f'printf("{cname}.{fname} %zu\\n", offsetof({cname}, {fname}));')
-    lines.append('printf("codes %d %d %d %d\\n", SM_TRACK_OK, SM_TRACK_LOST, SM_TRACK_DEGENERATE, SM_TRACK_NO_MODEL);')
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "sm_c_api.h"\nint main(void) {\n' + "\n".join(lines) + "\nreturn 0; }\n")
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    rows = [l.split(maxsplit=1) for l in subprocess.check_output([str(exe)]).decode().splitlines()]
-    got = dict(rows)
-    for cname, cls in mirrors.items():
-        assert int(got[cname]) == C.sizeof(cls), cname
-        for fname, _ in cls._fields_:
-            assert int(got[f"{cname}.{fname}"]) == getattr(cls, fname).offset, f"{cname}.{fname}"
-    assert got["codes"].split() == [str(capi.SM_TRACK_OK), str(capi.SM_TRACK_LOST), str(capi.SM_TRACK_DEGENERATE),
-                                    str(capi.SM_TRACK_NO_MODEL)]
 
 
 def test_restatement_pieces():

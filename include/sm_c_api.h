@@ -1865,6 +1865,75 @@ int sm_cast_rays_maps(sm_ctx *s, const sm_map_source *src, const sm_rays_params 
                       float *t, int32_t *id, uint8_t *rgb, uint8_t *sem, float *normal3);
 int sm_cast_rays_stats(sm_ctx *s, sm_rays_stats_t *out);     /* SM_E_ARG before the first call */
 
+/* ---- point queries: the nearest disc of a map set to arbitrary points (DESIGN.md "4y. Point queries") ----
+ * sm_query_points_maps takes n_pts points, each with a reach of its own, and returns per point the nearest DISC of a map set within
+ * that reach -- an sm_map_source with the global ids of the map-set calls: the files in list order, each in file order, then
+ * (include_model) the live model; no paths and include_model = 1: the live model alone.  Ids are sm_cast_rays_maps' ids.  The set is
+ * read ONCE per call, whatever n_pts.
+ * The rule (fp32, in the order written, no contraction; / and sqrt correctly rounded).  For a point x with reach R and a record with
+ *   centre p, stored normal n (not normalised) and stored radius r:
+ *     c_i  = x_i - p_i
+ *     nn   = (n.x*n.x + n.y*n.y) + n.z*n.z
+ *     h    = (n.x*c.x + n.y*c.y) + n.z*c.z
+ *     h2   = (h*h) / nn                       squared distance to the disc's plane
+ *     cc   = (c.x*c.x + c.y*c.y) + c.z*c.z
+ *     rho2 = cc - h2;            if !(rho2 > 0) rho2 = 0
+ *     e    = sqrt(rho2) - |r|;   if !(e > 0)    e = 0        distance past the rim, in the plane
+ *     dd   = h2 + e*e                         squared distance to the disc
+ *     near = dd <= R*R  &&  dd < +inf
+ *   Every comparison is false on a NaN; there is no epsilon.  A record takes part iff conf >= min_conf (in the live model: the
+ *   occupied slots after the compaction every map-set call begins with -- dead slots are gone), none of its centre, normal and
+ *   radius is a NaN, and nn > 0 and nn is finite: a zero normal takes no part, just as no ray can hit it; an infinite radius is
+ *   the whole plane and takes part.  The answer for a point is the near record that takes part with the smallest dd, ties to the
+ *   lower id: the least key (bits(dd + 0.0f) << 32) | id under a 64-bit atomicMin, and dd + 0.0f is the d2 returned.
+ * Points.  A point is valid iff its three coordinates are finite and R >= 0; R = +inf is valid and asks for the nearest disc of the
+ *   whole set (so does an R whose square overflows).  An invalid point returns the empty values and counts in stats.bad_points; it
+ *   is no error.
+ * Outputs, one entry per point; any but d2 may be NULL.  Empty values: d2 +inf, id -1, centre3 0 0 0, normal3 0 0 0, radius 0,
+ *   rgb 0 0 0, sem 0.  centre3, normal3 and radius are the returned record's, verbatim; rgb (3 bytes) and sem (class + 1) are made
+ *   of its colour word exactly as sm_cast_rays_maps makes them.
+ * Independence.  The answer is defined by the rule alone: it depends neither on cell_mm, nor on origin, nor on the chunking, nor
+ *   on the split of the set into files, nor on the order of work.  The voxel index -- the ray casts' -- only leaves out (point,
+ *   record) pairs that are proven not to be near or not to win (csrc/sm_k_points.h states the proof).  SM_POINTS_NO_INDEX=1 (read
+ *   per call) tests every record against every point (an A/B switch: the outputs are the same).
+ * Side effects: none on the model, the counters, the tick, the frame log or the trackers.  Synchronous.
+ * Errors.  Everything is checked, every file's header included, before an output is written.  SM_E_ARG: a NULL ctx, source or
+ *   params; NULL points or d2 with n_pts > 0; cell_mm < 1 or above 2^24; a non-finite origin; n_pts > SM_POINTS_MAX; a
+ *   call between sm_stage_conflict and sm_stage_cull; a missing file or one whose length disagrees with its header;
+ *   sm_query_points_stats before any call has succeeded.  SM_E_UNSUPPORTED: a sharded or rig context.  n_pts == 0 checks the set only.
+ * Files are never skipped: the file index bounds the centres of a file, not its radii, so no file is proven out of reach. */
+#define SM_POINTS_MAX (1u << 24)
+typedef struct sm_point { float pos[3]; float reach; } sm_point;   /* 16 bytes, world frame, metres */
+typedef struct sm_points_params {
+    int32_t cell_mm;          /* the index grid's cell edge, 1..2^24 (speed only)                     default 250 */
+    float   origin[3];        /* the index grid's origin (speed only)                                 default 0 0 0 */
+    float   min_conf;         /* a record takes part iff conf >= min_conf (a NaN: none does)          default 0 */
+    int32_t reserved[3];
+} sm_points_params;
+typedef struct sm_points_stats_t {
+    uint64_t points, bad_points;  /* points given; invalid ones among them */
+    uint64_t records;         /* of the set */
+    uint64_t wide;            /* records every point tests directly: a cube over more than 8 cells, loose to the grid, a radius that
+                                 is not finite, no slot in the table (or all that pass the gate with SM_POINTS_NO_INDEX=1) */
+    uint64_t pairs, cells;    /* (cell, record) pairs and distinct cells of the largest chunk */
+    uint64_t probes, tests;   /* table probes (slots read) and exact tests, all points and chunks */
+    uint64_t no_slot;         /* of `wide`: regular records whose cells found no slot in an overfull table */
+    uint64_t gave_up;         /* (point, chunk) walks whose cube met more than 64 + n / 8 cells of a chunk of n records and tested its
+                                 regular records one by one instead: at most n tests per point and chunk */
+    uint32_t chunks;          /* pieces of at most 2^20 records */
+    uint32_t files_skipped;   /* always 0: see above */
+    float read_ms;            /* host: reading the files */
+    float copy_ms;            /* device: the chunks' copies */
+    float index_ms;           /* device: building the chunks' indices */
+    float walk_ms;            /* device: walks, wide lists, resolve */
+    float device_ms;          /* device: everything between the upload of the points and the planes' copies back */
+    float total_ms;
+} sm_points_stats_t;
+int sm_default_points_params(sm_points_params *p);           /* pure, no context */
+int sm_query_points_maps(sm_ctx *s, const sm_map_source *src, const sm_points_params *p, const sm_point *pts, uint32_t n_pts,
+                         float *d2, int32_t *id, float *centre3, float *normal3, float *radius, uint8_t *rgb, uint8_t *sem);
+int sm_query_points_stats(sm_ctx *s, sm_points_stats_t *out); /* SM_E_ARG before the first call */
+
 /* ---- per-pass entry points (GlobalModel / IndexMap methods), synchronous ---- */
 /* Upload RGB / metric depth / semantic textures directly (bypasses p0). */
 int sm_set_frame(sm_ctx *s, const uint8_t *rgb, const float *depth_metric,

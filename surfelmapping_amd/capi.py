@@ -126,6 +126,25 @@ class SmRaysStats(C.Structure):
 RAYS_MAX = 1 << 24
 
 
+class SmPoint(C.Structure):
+    _fields_ = [("pos", C.c_float * 3), ("reach", C.c_float)]
+
+
+class SmPointsParams(C.Structure):
+    _fields_ = [("cell_mm", C.c_int32), ("origin", C.c_float * 3), ("min_conf", C.c_float), ("reserved", C.c_int32 * 3)]
+
+
+class SmPointsStats(C.Structure):
+    _fields_ = [("points", C.c_uint64), ("bad_points", C.c_uint64), ("records", C.c_uint64), ("wide", C.c_uint64), ("pairs", C.c_uint64),
+                ("cells", C.c_uint64), ("probes", C.c_uint64), ("tests", C.c_uint64), ("no_slot", C.c_uint64), ("gave_up", C.c_uint64),
+                ("chunks", C.c_uint32), ("files_skipped", C.c_uint32),
+                ("read_ms", C.c_float), ("copy_ms", C.c_float), ("index_ms", C.c_float), ("walk_ms", C.c_float), ("device_ms", C.c_float),
+                ("total_ms", C.c_float)]
+
+
+POINTS_MAX = 1 << 24
+
+
 class SmSceneActor(C.Structure):
     _fields_ = [("path", C.c_char_p), ("poses12", C.POINTER(C.c_float)), ("present", C.POINTER(C.c_uint8))]
 
@@ -594,6 +613,9 @@ PROTOTYPES = {
     "sm_default_rays_params": (ci, [P(SmRaysParams)]),
     "sm_cast_rays_maps": (ci, [vp, _SRC, P(SmRaysParams), vp, u32, vp, vp, vp, vp, vp]),
     "sm_cast_rays_stats": (ci, [vp, P(SmRaysStats)]),
+    "sm_default_points_params": (ci, [P(SmPointsParams)]),
+    "sm_query_points_maps": (ci, [vp, _SRC, P(SmPointsParams), vp, u32, vp, vp, vp, vp, vp, vp, vp]),
+    "sm_query_points_stats": (ci, [vp, P(SmPointsStats)]),
 }
 # ---- NOT IN THE HEADER: the diagnostics the library exports beside its C-ABI (timings of the last call of a kind; SurfelMap's
 # *_ms / *_stats readers say what each gives).  They are typed and required like the rest, but are no part of SYMBOLS.
@@ -785,6 +807,7 @@ def _padded3(p, k, v):
 _ORIGIN = {"origin": _whole(float)}
 _SPECIAL = {
     SmRaysParams: {"origin": _padded3},
+    SmPointsParams: {"origin": _padded3},
     SmTrackRgbParams: {"iters": _leading(int)},
     SmSearchParams: {k: _leading(float) for k in ("trans_half", "trans_step", "rot_half_deg", "rot_step_deg")},
     SmSimplifyParams: _ORIGIN,
@@ -803,6 +826,11 @@ _SPECIAL[SmAutoPlaceParams] = {**_SPECIAL[SmAutoLoopParams], "search": lambda p,
 def rays_params(**over) -> SmRaysParams:
     """sm_default_rays_params with fields replaced: cell_mm, origin (three floats), min_conf"""
     return _params(SmRaysParams, "sm_default_rays_params", None, over)
+
+
+def points_params(**over) -> SmPointsParams:
+    """sm_default_points_params with fields replaced: cell_mm, origin (three floats), min_conf"""
+    return _params(SmPointsParams, "sm_default_points_params", None, over)
 
 
 def track_params(**over) -> SmTrackParams:
@@ -1072,6 +1100,30 @@ def lidar_rays(sensor, poses16) -> np.ndarray:
     rays[:, :, 4:7] = dirs.astype(np.float32)
     rays[:, :, 7] = np.float32(sensor.max_range)
     return rays.reshape(n_el * n_az, 8)
+
+
+def body_points(poses16, spheres) -> np.ndarray:
+    """A body of spheres under poses as points for SurfelMap.query_points: float32[k * m][4] = (centre, reach), pose-major.  spheres:
+    float32[m][4] = (centre in the body frame, radius); poses16: one body->world pose (float32[16] column-major or 4x4) or k of
+    them.  Each centre is R * c + t, computed in double (((R0 cx + R1 cy) + R2 cz) + t, terms with a zero coefficient left out, as
+    lidar_rays does) and rounded once; the radius is the reach, so id >= 0 in the answer reads "this sphere at this pose touches
+    the map".  Needs no context."""
+    S = np.asarray(spheres, np.float32)
+    if S.ndim != 2 or S.shape[1] != 4:
+        raise ValueError("spheres: float32[m][4]")
+    P = np.asarray(poses16, np.float32)
+    if P.ndim >= 2 and P.shape[-2:] == (4, 4):
+        P = np.swapaxes(P, -1, -2)                                        # (numpy row/col indexing -> column-major)
+    P = np.ascontiguousarray(P).reshape(-1, 16)
+    k, m = P.shape[0], S.shape[0]
+    R = P.astype(np.float64).reshape(k, 4, 4)[:, :3, :3]                  # R[j][c][r]: column c, row r of pose j
+    c = S[:, 0:3].astype(np.float64)
+    term = [np.where(R[:, None, a, :] != 0.0, R[:, None, a, :] * c[None, :, None, a], -0.0) for a in range(3)]
+    centre = ((term[0] + term[1]) + term[2]) + P[:, None, 12:15].astype(np.float64)
+    out = np.zeros((k, m, 4), np.float32)
+    out[:, :, 0:3] = centre.astype(np.float32)
+    out[:, :, 3] = S[None, :, 3]
+    return out.reshape(k * m, 4)
 
 
 def scene_poses12(poses) -> np.ndarray:
@@ -2104,6 +2156,38 @@ class SurfelMap:
         """of the last cast_rays: rays, bad_rays, records, wide, pairs and cells (of the largest chunk), probes, tests, no_slot, gave_up, chunks,
         files_skipped (always 0), read_ms, copy_ms, index_ms, cast_ms, device_ms, total_ms"""
         return self._stats(SmRaysStats, "sm_cast_rays_stats")
+
+    # -- point queries (sm_query_points_maps)
+    def query_points(self, points, paths=(), include_model=True, cell_mm=250, origin=None, min_conf=0.0,
+                     planes=("centre", "normal", "radius", "rgb", "sem")) -> dict:
+        """The nearest disc of the map set `paths` (then, with include_model, the live model) to each of the points float32[n][4] =
+        (position, reach), world frame, metres, within that reach: a dict of d2 float32[n] (the squared distance; +inf = none),
+        dist (its square root), id int32 (position in the concatenation, -1) and the `planes` asked for: centre float32[n][3],
+        normal float32[n][3], radius float32[n] (the record's, verbatim), rgb uint8[n][3], sem uint8 (class + 1, 0).  Ties go to the
+        lower id (sm_query_points_maps; tests/points_ref.py restates the rule).  cell_mm and origin shape the voxel index and change
+        nothing in the answer.  A reach of +inf asks for the nearest disc of the whole set; an invalid point returns the empty values."""
+        pts = np.ascontiguousarray(points, np.float32)
+        if pts.ndim != 2 or pts.shape[1] != 4:
+            raise ValueError("points: float32[n][4]")
+        shapes = dict(centre=((3,), np.float32), normal=((3,), np.float32), radius=((), np.float32), rgb=((3,), np.uint8), sem=((), np.uint8))
+        for k in planes:
+            if k not in shapes:
+                raise KeyError(k)
+        n = pts.shape[0]
+        p = points_params(cell_mm=cell_mm, origin=(0.0, 0.0, 0.0) if origin is None else origin, min_conf=min_conf)
+        src = map_source(paths, include_model)
+        out = dict(d2=np.full(n, np.inf, np.float32), id=np.full(n, -1, np.int32))
+        for k in planes:
+            out[k] = np.zeros((n,) + shapes[k][0], shapes[k][1])
+        self._chk(self._L.sm_query_points_maps(self._h, C.byref(src), C.byref(p), _ptr(pts), n, _ptr(out["d2"]), _ptr(out["id"]),
+                                               *[_ptr(out[k]) if k in out else None for k in shapes]), "sm_query_points_maps")
+        out["dist"] = np.sqrt(out["d2"])
+        return out
+
+    def query_points_stats(self) -> dict:
+        """of the last query_points: points, bad_points, records, wide, pairs and cells (of the largest chunk), probes, tests, no_slot,
+        gave_up, chunks, files_skipped (always 0), read_ms, copy_ms, index_ms, walk_ms, device_ms, total_ms"""
+        return self._stats(SmPointsStats, "sm_query_points_stats")
 
     # -- scenes (sm_render_image_scene, sm_lidar_sweep_scene)
     def render_scene(self, paths, actors, views, w, h, fx, fy, cx, cy, include_model=True, fill=None, depth=False):

@@ -4,6 +4,7 @@
 #pragma once
 #include <cmath>
 #include <cstdio>
+#include <limits>
 #include <string>
 #include <utility>
 #include <vector>
@@ -338,6 +339,38 @@ public:
         const sm_map_source src{paths.data(), (uint32_t)paths.size(), includeModel ? 1 : 0};
         (void)sm_sync(ctx);                                              // (SM_FACADE_ASYNC: frames may still be in flight)
         if (sm_cast_rays_maps(ctx, &src, &p, rays.data(), (uint32_t)n, out.t.data(), out.id.data(), out.rgb.data(), out.sem.data(), out.normal.data()) != SM_OK) {
+            std::printf("%s: %s\n", who, sm_last_error());
+            return false;
+        }
+        return true;
+    }
+
+    // The nearest disc of the model to each of a list of points (sm_point: position and reach; world frame, metres) within that reach
+    // (sm_query_points_maps): per point the squared distance (+inf: none), the surfel's id (-1), its centre, stored normal and
+    // radius, its colour bytes and its class + 1 (0).
+    struct PointReturns {
+        std::vector<float> d2; std::vector<int32_t> id; std::vector<float> centre, normal, radius; std::vector<unsigned char> rgb, sem;
+    };
+    bool queryPoints(const std::vector<sm_point> &points, PointReturns &out, const sm_points_params *params = nullptr)
+    {
+        return queryPointsOf(ctx_, {}, true, points, out, params, "queryPoints");
+    }
+    // (SurfelMapping::queryPoints queries a map set through this)
+    static bool queryPointsOf(sm_ctx *ctx, const std::vector<std::string> &mapFiles, bool includeModel, const std::vector<sm_point> &points,
+                              PointReturns &out, const sm_points_params *params, const char *who)
+    {
+        const size_t n = points.size();
+        out.d2.assign(n, std::numeric_limits<float>::infinity()); out.id.assign(n, -1); out.centre.assign(n * 3, 0.0f); out.normal.assign(n * 3, 0.0f);
+        out.radius.assign(n, 0.0f); out.rgb.assign(n * 3, 0); out.sem.assign(n, 0);
+        sm_points_params p;
+        sm_default_points_params(&p);
+        if (params) p = *params;
+        std::vector<const char *> paths;
+        for (const std::string &f : mapFiles) paths.push_back(f.c_str());
+        const sm_map_source src{paths.data(), (uint32_t)paths.size(), includeModel ? 1 : 0};
+        (void)sm_sync(ctx);                                              // (SM_FACADE_ASYNC: frames may still be in flight)
+        if (sm_query_points_maps(ctx, &src, &p, points.data(), (uint32_t)n, out.d2.data(), out.id.data(), out.centre.data(), out.normal.data(),
+                                 out.radius.data(), out.rgb.data(), out.sem.data()) != SM_OK) {
             std::printf("%s: %s\n", who, sm_last_error());
             return false;
         }

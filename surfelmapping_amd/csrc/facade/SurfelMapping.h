@@ -523,6 +523,15 @@ public:
         return GlobalModel::castRaysOf(ctx_, mapFiles, includeModel, rays, out, params, "castRays");
     }
 
+    // The nearest disc of a map set to each of a list of points, within the point's reach (sm_query_points_maps; DESIGN.md "4y.
+    // Point queries"): the map files in that order, then -- includeModel -- the live model, read once whatever the number of points.
+    // GlobalModel::queryPoints is the live model alone.
+    bool queryPoints(const std::vector<std::string> &mapFiles, const std::vector<sm_point> &points, GlobalModel::PointReturns &out,
+                     bool includeModel = true, const sm_points_params *params = nullptr)
+    {
+        return GlobalModel::queryPointsOf(ctx_, mapFiles, includeModel, points, out, params, "queryPoints");
+    }
+
     // Scenes (sm_render_image_scene / sm_lidar_sweep_scene; DESIGN.md "4w. Scenes"): the map set with moving actors in it.  Every
     // actor's file is read once and drawn under its pose of each view where it is present; no file is copied or rewritten.
     // acquireSceneImages writes what acquireImages writes and honours setFillHoles / setWriteDepth; the blended view draws no

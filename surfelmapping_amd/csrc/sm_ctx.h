@@ -427,6 +427,12 @@ struct Rays {
     bool stats_valid = false;
 };
 
+// point queries (sm_points.hip, sm_k_points.h): the last call's stats.  The index, the points and the planes live for one call.
+struct Points {
+    sm_points_stats_t stats{};
+    bool stats_valid = false;
+};
+
 // scenes (sm_scene.hip, sm_k_scene.h): the actors of one call resident on the device -- the distinct files' records as they were
 // read, the SoA planes and boxes k_maps_intake makes of them, the call's tables -- grown on demand and reloaded by every call (no
 // cache across calls); the last call's tally
@@ -703,6 +709,7 @@ struct sm_ctx {
     Ground ground;
     Rays rays;
     Scene scene;
+    Points points;
 };
 
 namespace sm_impl __attribute__((visibility("hidden"))) {

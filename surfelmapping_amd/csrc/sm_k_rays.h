@@ -1,5 +1,7 @@
 // sm_k_rays.h -- ray casts (DESIGN.md "4x. Ray casts"; the rule: include/sm_c_api.h "ray casts"): arbitrary rays against the records of
-// a chunk, the exact ray-against-disc test of the header in front of a 64-bit atomicMin per ray.  Included by sm_rays.hip only.
+// a chunk, the exact ray-against-disc test of the header in front of a 64-bit atomicMin per ray.  Included by sm_rays.hip, and through
+// sm_k_points.h by sm_points.hip, which builds the same index (k_rays_count, k_rays_alloc, k_rays_fill) and walks it otherwise
+// -- so the kernels are static: each of the two sources has its own copy of those it launches.
 //   k_rays_count    one lane per record: dropped, wide or regular; a regular record claims the cells of its cube in the lean
 //                   table (key | count, first) and counts itself into each; the chunk's box in cells
 //   k_rays_alloc    one lane per slot: a cell's run in the pair list, from a cursor one wave adds to once
@@ -148,8 +150,8 @@ __device__ __forceinline__ void rays_tally(RaysTally *__restrict__ tally, uint32
     }
 }
 
-__global__ __launch_bounds__(256) void k_rays_count(const float4 *__restrict__ rec, uint32_t n, SimplifyArgs a, float min_conf, int no_index, LeanTable T,
-                                                    uint8_t *__restrict__ flag, uint32_t *__restrict__ wide, RaysChunk *__restrict__ ck)
+static __global__ __launch_bounds__(256) void k_rays_count(const float4 *__restrict__ rec, uint32_t n, SimplifyArgs a, float min_conf, int no_index, LeanTable T,
+                                                           uint8_t *__restrict__ flag, uint32_t *__restrict__ wide, RaysChunk *__restrict__ ck)
 {
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
     if (t >= n) return;
@@ -178,7 +180,7 @@ __global__ __launch_bounds__(256) void k_rays_count(const float4 *__restrict__ r
 }
 
 // run.y becomes the END of the cell's run; k_rays_fill counts it down to the start
-__global__ __launch_bounds__(256) void k_rays_alloc(LeanTable T, RaysChunk *__restrict__ ck)
+static __global__ __launch_bounds__(256) void k_rays_alloc(LeanTable T, RaysChunk *__restrict__ ck)
 {
     const uint32_t sl = blockIdx.x * 256u + threadIdx.x;
     const int lane = threadIdx.x & 63;
@@ -197,8 +199,8 @@ __global__ __launch_bounds__(256) void k_rays_alloc(LeanTable T, RaysChunk *__re
     if (cnt) T.run[sl].y = base + incl;
 }
 
-__global__ __launch_bounds__(256) void k_rays_fill(const float4 *__restrict__ rec, uint32_t n, SimplifyArgs a, float min_conf, LeanTable T,
-                                                   const uint8_t *__restrict__ flag, uint32_t *__restrict__ pairs)
+static __global__ __launch_bounds__(256) void k_rays_fill(const float4 *__restrict__ rec, uint32_t n, SimplifyArgs a, float min_conf, LeanTable T,
+                                                          const uint8_t *__restrict__ flag, uint32_t *__restrict__ pairs)
 {
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
     if (t >= n || flag[t] != RAYS_REG) return;
@@ -213,10 +215,10 @@ __global__ __launch_bounds__(256) void k_rays_fill(const float4 *__restrict__ re
 }
 
 // rays: two float4 per ray.  The chunk's n records at rec have the ids gid0 ..
-__global__ __launch_bounds__(256) void k_rays_cast(const float4 *__restrict__ rays, uint32_t n_rays, const float4 *__restrict__ rec, uint32_t n,
-                                                   uint32_t gid0, SimplifyArgs a, LeanTable T, const uint32_t *__restrict__ pairs,
-                                                   const uint8_t *__restrict__ flag, const RaysChunk *__restrict__ ck,
-                                                   unsigned long long *__restrict__ key, RaysTally *__restrict__ tally)
+static __global__ __launch_bounds__(256) void k_rays_cast(const float4 *__restrict__ rays, uint32_t n_rays, const float4 *__restrict__ rec, uint32_t n,
+                                                          uint32_t gid0, SimplifyArgs a, LeanTable T, const uint32_t *__restrict__ pairs,
+                                                          const uint8_t *__restrict__ flag, const RaysChunk *__restrict__ ck,
+                                                          unsigned long long *__restrict__ key, RaysTally *__restrict__ tally)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     uint32_t probes = 0, tests = 0;
@@ -299,9 +301,9 @@ __global__ __launch_bounds__(256) void k_rays_cast(const float4 *__restrict__ ra
     rays_tally(tally, probes, tests);
 }
 
-__global__ __launch_bounds__(256) void k_rays_wide(const float4 *__restrict__ rays, uint32_t n_rays, const float4 *__restrict__ rec, uint32_t gid0,
-                                                   const uint32_t *__restrict__ wide, const RaysChunk *__restrict__ ck,
-                                                   unsigned long long *__restrict__ key, RaysTally *__restrict__ tally)
+static __global__ __launch_bounds__(256) void k_rays_wide(const float4 *__restrict__ rays, uint32_t n_rays, const float4 *__restrict__ rec, uint32_t gid0,
+                                                          const uint32_t *__restrict__ wide, const RaysChunk *__restrict__ ck,
+                                                          unsigned long long *__restrict__ key, RaysTally *__restrict__ tally)
 {
     __shared__ float4 s_pc[RAYS_PIECE], s_nr[RAYS_PIECE];
     __shared__ uint32_t s_id[RAYS_PIECE];
@@ -331,8 +333,8 @@ __global__ __launch_bounds__(256) void k_rays_wide(const float4 *__restrict__ ra
 }
 
 // A later chunk that wins a ray overwrites it.  The planes start as zeros: the empty values.  Any plane may be null.
-__global__ void k_rays_resolve(const float4 *__restrict__ rec, uint32_t gid0, uint32_t n, const unsigned long long *__restrict__ key, uint32_t n_rays,
-                               uint8_t *__restrict__ rgb, uint8_t *__restrict__ sem, float *__restrict__ nrm)
+static __global__ void k_rays_resolve(const float4 *__restrict__ rec, uint32_t gid0, uint32_t n, const unsigned long long *__restrict__ key, uint32_t n_rays,
+                                      uint8_t *__restrict__ rgb, uint8_t *__restrict__ sem, float *__restrict__ nrm)
 {
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= n_rays) return;
@@ -347,8 +349,8 @@ __global__ void k_rays_resolve(const float4 *__restrict__ rec, uint32_t gid0, ui
 }
 
 // ... and the invalid rays are counted, by the rule the casts used (all 64 lanes of a wave reach the ballot)
-__global__ __launch_bounds__(256) void k_rays_finish(const float4 *__restrict__ rays, const unsigned long long *__restrict__ key, uint32_t n_rays,
-                                                     float *__restrict__ t, int32_t *__restrict__ ids, RaysTally *__restrict__ tally)
+static __global__ __launch_bounds__(256) void k_rays_finish(const float4 *__restrict__ rays, const unsigned long long *__restrict__ key, uint32_t n_rays,
+                                                            float *__restrict__ t, int32_t *__restrict__ ids, RaysTally *__restrict__ tally)
 {
     const uint32_t q = blockIdx.x * 256u + threadIdx.x;
     bool bad = false;

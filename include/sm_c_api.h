@@ -981,6 +981,88 @@ int sm_stereo_depth(sm_ctx *s, const uint8_t *rgb_left, const uint8_t *rgb_right
 int sm_stereo_depth_device(sm_ctx *s, const uint8_t *d_left, const uint8_t *d_right, uint16_t *d_depth_mm_out, uint16_t *d_disp16_out);
 int sm_stereo_download(sm_ctx *s, uint64_t *census_left, uint64_t *census_right, uint16_t *volume);
 
+/* ---- lidar depth (DESIGN.md "4z. Lidar depth") ----
+ * The depth image of a frame from a lidar scan: the points are z-buffered into the camera, and the sparse image is completed to a
+ * dense one by a fixed chain of morphological steps, in the manner of IP-Basic (Ku et al. 2018), all in integers.
+ * Inputs: points, n x 4 fp32 (x, y, z, reflectance: the layout of a KITTI velodyne file), n <= SM_LIDAR_DEPTH_MAX_POINTS, n = 0
+ * allowed; T, 16 floats, row-major 4 x 4, lidar frame to camera frame, of which rows 0..2 are used; fx, fy, cx, cy, W, H the
+ * context's.  All float work is fp32, every operation rounded once, in the order written, nothing contracted.
+ *   1. Project, per point i.  X = ((T[0]*x + T[1]*y) + T[2]*z) + T[3]; Y with row 1 and Z with row 2 in the same way.  The point
+ *      is dropped unless X, Y, Z are finite and min_z <= Z <= max_z.  u = (fx*X)/Z + cx, v = (fy*Y)/Z + cy; dropped unless u and v
+ *      are finite, -0.5 <= u < W-0.5 and -0.5 <= v < H-0.5.  px = (int)floorf(u + 0.5f), py likewise,
+ *      mm = (int)floorf(Z*1000.0f + 0.5f); dropped unless 1 <= mm <= 65535, px < W and py < H.  Splat: a 64-bit minimum of
+ *      key = (uint64)mm << 32 | i per pixel: the nearest point wins, among equal mm the lowest index.  sparse_mm = the winner's
+ *      mm, 0 where no point landed; index = the winner's i, or -1.  The reflectance is not used; index lets a caller gather it.
+ *   2. Complete, on v = 65536 - mm for measured pixels and v = 0 for empty ones: near is large, and a maximum takes the nearest,
+ *      which is also what removes far points the lidar saw past an edge the camera cannot see past.  In every window the taps
+ *      outside the image do not exist: they enter neither a maximum nor a minimum.  Each step reads the complete output of the
+ *      step before, never its own, and is switched off by clearing its bit in `stages`.
+ *      bit 0 DILATE      v <- max over the 13-tap diamond |dx| + |dy| <= 2; every pixel takes it, measured ones included.
+ *      bit 1 CLOSE       v <- max over the 5 x 5 box, then v <- min over the 5 x 5 box (empty taps count as 0 in the min).
+ *      bit 2 FILL_SMALL  pixels with v = 0 take the max over the 7 x 7 box; others keep v.
+ *      bit 3 EXTEND_TOP  in each column the pixels above the topmost pixel with v > 0 take its v; a column without one stays empty.
+ *      bit 4 FILL_LARGE  pixels with v = 0 take the max over the large x large box.
+ *      bit 5 MEDIAN      a pixel with v > 0 takes the lower median of the taps with v > 0 in its 5 x 5 box: element (n-1)/2 of
+ *                        the n values sorted ascending.  Empty pixels stay empty.
+ *      bit 6 SMOOTH      a pixel with v > 0 and depth z0 = 65536 - v takes (sum w*v + Wt/2) / Wt in 64-bit integers over the taps
+ *                        of its 5 x 5 box that have v > 0 and lie in its layer: max(z, z0)*256 <= min(z, z0)*(256 + tol_256).
+ *                        w = b[dy]*b[dx], b = 1, 4, 6, 4, 1; Wt the sum of the weights that counted (the pixel itself always does).
+ *      depth_mm = 65536 - v where v > 0, else 0.
+ * No stereo border, clip or filter is applied here: the fusion's own rules do that downstream, as for a depth image from a file.
+ * Parameters (sm_lidar_depth_params): 0 < min_z <= max_z <= 65.535, both finite; stages in 0..127; large odd, in 3..31; tol_256
+ *   in 0..255.  sm_default_lidar_depth_params: 0.5, 65.0, 127, 31, 13.
+ * sm_set_lidar_depth allocates the key plane and the work planes on the device; p NULL frees them (the default).  Setting it
+ *   again replaces them.  A call that is rejected for its arguments (SM_E_ARG, SM_E_UNSUPPORTED) changes nothing: a context that
+ *   had the stage keeps its planes and parameters.  If an allocation fails: SM_E_HIP, and the context is left without the stage.
+ * sm_lidar_depth takes host pointers and waits; any output may be NULL.  sm_lidar_depth_device takes a scan resident on the
+ *   context's GPU (16-byte aligned) and outputs that are device pointers the caller owns (depth_mm and sparse_mm 2-byte, index
+ *   4-byte aligned, any may be NULL); T16 is on the host.  Its work -- four kernel launches, three with FILL_LARGE off -- is
+ *   enqueued on the context's stream and not waited for, so a following sm_process_frame_device(ctx, d_rgb, d_depth_mm_out, ...)
+ *   sees the result.
+ * sm_lidar_depth_stats returns the last call's tally (it waits for that call; a call whose tally nobody asked for before the
+ *   next one costs no wait: the next call's tally replaces it).  launch_ms is diagnostic only: what it holds, and how many of
+ *   its entries mean anything, may change without a new SM_API_VERSION.  It holds the device time of each launch
+ *   (0 the projection, 1 the DILATE..FILL_SMALL chain, 2 FILL_LARGE's row pass, 3 the rest) when SM_LIDAR_DEPTH_TIMING=1 was in
+ *   the environment of sm_set_lidar_depth, -1 each otherwise and for a launch that was not made.
+ *   A measuring aid: with SM_LIDAR_DEPTH_UNFUSED=1 in the environment of sm_set_lidar_depth every step is a launch of its own,
+ *   through planes in global memory -- the same results from up to SM_LIDAR_DEPTH_MAX_LAUNCHES launches (0 the projection, 1 keys to
+ *   v, 2 DILATE, 3 and 4 CLOSE, 5 FILL_SMALL, 6 EXTEND_TOP, 7 and 8 FILL_LARGE, 9 MEDIAN, 10 SMOOTH, 11 the output).
+ * These entry points change nothing in the model, its counters, the tick, the frame log or the tracker state.
+ * SM_E_ARG: a NULL context, NULL points with n > 0, n above the cap, parameters outside the ranges above, a misaligned pointer, a
+ *   context without the stage (every call except sm_set_lidar_depth and the defaults), sm_lidar_depth_stats before the first
+ *   call, a call between sm_stage_conflict and sm_stage_cull.
+ *   SM_E_UNSUPPORTED: a sharded or rig context, checked right after the NULL context and before every other argument. */
+#define SM_LIDAR_DEPTH_MAX_POINTS (1u << 24)
+#define SM_LIDAR_DEPTH_MAX_LAUNCHES 12
+#define SM_LIDAR_DEPTH_DILATE 1
+#define SM_LIDAR_DEPTH_CLOSE 2
+#define SM_LIDAR_DEPTH_FILL_SMALL 4
+#define SM_LIDAR_DEPTH_EXTEND_TOP 8
+#define SM_LIDAR_DEPTH_FILL_LARGE 16
+#define SM_LIDAR_DEPTH_MEDIAN 32
+#define SM_LIDAR_DEPTH_SMOOTH 64
+typedef struct sm_lidar_depth_params {
+    float   min_z, max_z;          /* metres along the camera's z; defaults 0.5, 65.0 */
+    int32_t stages;                /* bits 0..6 as above; default 127 */
+    int32_t large;                 /* FILL_LARGE's window: odd, 3..31; default 31 */
+    int32_t tol_256;               /* SMOOTH's layer gate, 0..255; default 13 (the fill stage's) */
+} sm_lidar_depth_params;
+typedef struct sm_lidar_depth_stats_t {
+    uint64_t points;               /* given */
+    uint64_t landed;               /* ... that reached the splat */
+    uint64_t measured;             /* pixels of sparse_mm that are not 0 */
+    uint64_t filled_small, filled_top, filled_large;   /* pixels that FILL_SMALL, EXTEND_TOP and FILL_LARGE made non-empty */
+    uint64_t left_empty;           /* pixels of depth_mm that are 0 */
+    uint32_t launches;             /* kernel launches of the call */
+    float    device_ms;            /* from before the first to after the last, by events */
+    float    launch_ms[SM_LIDAR_DEPTH_MAX_LAUNCHES];   /* each launch's own (see above) */
+} sm_lidar_depth_stats_t;
+int sm_default_lidar_depth_params(const sm_config *c, sm_lidar_depth_params *p);
+int sm_set_lidar_depth(sm_ctx *s, const sm_lidar_depth_params *p);
+int sm_lidar_depth(sm_ctx *s, const float *points4, uint32_t n, const float *T16, uint16_t *depth_mm_out, uint16_t *sparse_mm_out, int32_t *index_out);
+int sm_lidar_depth_device(sm_ctx *s, const float *d_points4, uint32_t n, const float *T16, uint16_t *d_depth_mm_out, uint16_t *d_sparse_mm_out, int32_t *d_index_out);
+int sm_lidar_depth_stats(sm_ctx *s, sm_lidar_depth_stats_t *out);
+
 /* ---- hole filling (DESIGN.md "4n. Hole filling") ----
  * A novel view (sm_render_image, sm_render_image_maps) is empty (sem 0) between discs and where a near object uncovers what no
  * frame saw, shows far surfels through one-pixel gaps of a near surface, and carries no depth.  This is the screen-space stage

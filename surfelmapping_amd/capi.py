@@ -275,6 +275,19 @@ class SmStereoParams(C.Structure):
                 ("lr_max_diff", C.c_int32), ("baseline", C.c_float)]
 
 
+class SmLidarDepthParams(C.Structure):
+    _fields_ = [("min_z", C.c_float), ("max_z", C.c_float), ("stages", C.c_int32), ("large", C.c_int32), ("tol_256", C.c_int32)]
+
+
+class SmLidarDepthStats(C.Structure):
+    _fields_ = [("points", C.c_uint64), ("landed", C.c_uint64), ("measured", C.c_uint64), ("filled_small", C.c_uint64),
+                ("filled_top", C.c_uint64), ("filled_large", C.c_uint64), ("left_empty", C.c_uint64), ("launches", C.c_uint32),
+                ("device_ms", C.c_float), ("launch_ms", C.c_float * 12)]
+
+
+LIDAR_DEPTH_MAX_POINTS = 1 << 24
+
+
 class SmFillParams(C.Structure):
     _fields_ = [("levels", C.c_int32), ("depth_tol_256", C.c_int32), ("through_count", C.c_int32), ("prefer_far", C.c_int32),
                 ("min_cover_256", C.c_int32)]
@@ -573,6 +586,11 @@ PROTOTYPES = {
     "sm_stereo_depth": (ci, [vp, vp, vp, vp, vp]),
     "sm_stereo_depth_device": (ci, [vp, vp, vp, vp, vp]),
     "sm_stereo_download": (ci, [vp, vp, vp, vp]),
+    "sm_default_lidar_depth_params": (ci, [_CFG, P(SmLidarDepthParams)]),
+    "sm_set_lidar_depth": (ci, [vp, P(SmLidarDepthParams)]),
+    "sm_lidar_depth": (ci, [vp, vp, u32, vp, vp, vp, vp]),
+    "sm_lidar_depth_device": (ci, [vp, vp, u32, vp, vp, vp, vp]),
+    "sm_lidar_depth_stats": (ci, [vp, P(SmLidarDepthStats)]),
     "sm_default_fill_params": (ci, [_FILL]),
     "sm_fill_image": (ci, [vp, _FILL, ci, ci, u32, vp, vp, vp]),
     "sm_fill_image_device": (ci, [vp, _FILL, ci, ci, u32, vp, vp, vp]),
@@ -888,6 +906,11 @@ def stereo_params(cfg, **over) -> SmStereoParams:
     return _params(SmStereoParams, "sm_default_stereo_params", cfg, over)
 
 
+def lidar_depth_params(cfg, **over) -> SmLidarDepthParams:
+    """sm_default_lidar_depth_params (min_z 0.5, max_z 65, stages 127, large 31, tol_256 13) with fields overridden"""
+    return _params(SmLidarDepthParams, "sm_default_lidar_depth_params", cfg, over)
+
+
 def fill_params(**over) -> SmFillParams:
     """sm_default_fill_params (levels 3, depth_tol_256 13, through_count 6, prefer_far 1, min_cover_256 64) with fields overridden"""
     return _params(SmFillParams, "sm_default_fill_params", None, over)
@@ -1073,6 +1096,28 @@ def lidar_points(range, dirs, rgb=None) -> np.ndarray:
         c = np.ascontiguousarray(rgb, np.uint8).reshape(-1, 3)[got].astype(f32)
         out[:, 3] = ((f32(0.299) * c[:, 0] + f32(0.587) * c[:, 1]) + f32(0.114) * c[:, 2]) / f32(255.0)
     return out
+
+
+def sweep_points(range, sensor) -> np.ndarray:
+    """The returns of a sweep as a scan for SurfelMap.lidar_depth: float32[N][4] = t*d in the sensor's own frame (the frame of
+    lidar_directions' table and of the sweep's pose), one float32 product per component, and a reflectance of 0.  Beams without
+    a return (range 0) are left out; the order is the grid's, row-major."""
+    t = np.ascontiguousarray(range, np.float32).reshape(-1)
+    d = lidar_directions(sensor).reshape(-1, 3)
+    if len(t) != len(d):
+        raise ValueError("range: not the sensor's grid")
+    got = t > 0
+    out = np.zeros((int(got.sum()), 4), np.float32)
+    out[:, :3] = t[got, None] * d[got]
+    return out
+
+
+def read_velodyne(path) -> np.ndarray:
+    """a KITTI velodyne file (float32 x, y, z, reflectance per point, nothing else): float32[N][4]"""
+    raw = np.fromfile(path, np.float32)
+    if raw.size % 4:
+        raise ValueError(f"{path}: not a whole number of 16-byte points")
+    return raw.reshape(-1, 4)
 
 
 def lidar_rays(sensor, poses16) -> np.ndarray:
@@ -1973,6 +2018,72 @@ class SurfelMap:
             self.device_upload(d_sem, np.ascontiguousarray(sem, np.uint8))
         self.stereo_depth_device(d_left, d_right, d_depth)
         return self.process_frame_device(d_left, d_depth, d_sem if sem is not None else None, pose)
+
+    # -- lidar depth (sm_lidar_depth*)
+    def set_lidar_depth(self, on=True, **params):
+        """Give the context the planes of the lidar depth stage (sm_set_lidar_depth); params override lidar_depth_params(cfg).  on
+        False: free them."""
+        p = lidar_depth_params(self.cfg, **params) if on else None
+        self._chk(self._L.sm_set_lidar_depth(self._h, C.byref(p) if on else None), "sm_set_lidar_depth")
+
+    @staticmethod
+    def _scan(points, T):
+        points = np.ascontiguousarray(points, np.float32).reshape(-1, 4)
+        T = np.ascontiguousarray(T, np.float32).reshape(-1)
+        assert T.size in (12, 16), T.shape
+        return points, np.concatenate([T, np.array([0, 0, 0, 1], np.float32)])[:16]
+
+    def lidar_depth(self, points, T):
+        """The depth image of a scan (sm_lidar_depth): (depth_mm uint16[H][W], completed, 0 = empty, as process_frame takes it;
+        sparse_mm uint16[H][W], the z-buffered points alone; index int32[H][W], the row of `points` each measured pixel shows,
+        -1).  points float32[N][4] (x, y, z, reflectance); T the lidar->camera transform, row-major 4 x 4 or 3 x 4."""
+        points, T = self._scan(points, T)
+        depth, sparse = np.zeros((self.H, self.W), np.uint16), np.zeros((self.H, self.W), np.uint16)
+        index = np.zeros((self.H, self.W), np.int32)
+        self._chk(self._L.sm_lidar_depth(self._h, _ptr(points) if len(points) else None, len(points), _ptr(T), _ptr(depth),
+                                         _ptr(sparse), _ptr(index)), "sm_lidar_depth")
+        return depth, sparse, index
+
+    def lidar_depth_device(self, d_points: int, n: int, T, d_depth: int, d_sparse: int = 0, d_index: int = 0):
+        """lidar_depth() of a scan in this context's device memory into device buffers of the caller's (sm_lidar_depth_device):
+        enqueued on the context's stream, not waited for.  T is on the host."""
+        T = self._scan(np.zeros((0, 4), np.float32), T)[1]
+        self._chk(self._L.sm_lidar_depth_device(self._h, d_points or None, n, _ptr(T), d_depth or None, d_sparse or None,
+                                                d_index or None), "sm_lidar_depth_device")
+
+    def lidar_depth_stats(self) -> dict:
+        """of the last lidar_depth call: points, landed, measured, filled_small, filled_top, filled_large, left_empty, launches,
+        device_ms, launch_ms (a list of twelve, of which the default form uses four; -1 unless SM_LIDAR_DEPTH_TIMING=1 was set at
+        set_lidar_depth)"""
+        d = self._stats(SmLidarDepthStats, "sm_lidar_depth_stats")
+        d["launch_ms"] = [float(v) for v in d["launch_ms"]]
+        return d
+
+    def process_frame_lidar(self, rgb, points, T, sem, pose):
+        """process_frame() with the depth made from the scan: the image and the points are uploaded, sm_lidar_depth_device and
+        sm_process_frame_device are enqueued one after the other, and the depth never leaves the device.  sem None: the previous
+        class image stays.  The device buffers it stages in are allocated by the first call and live as long as the context; the
+        scan's grows by at least half when a scan has more points than it holds, and the one it replaces is freed."""
+        rgb = np.ascontiguousarray(rgb, np.uint8)
+        assert rgb.shape == (self.H, self.W, 3), rgb.shape
+        points, _ = self._scan(points, T)
+        if getattr(self, "_ldepth_dev", None) is None:
+            P = self.P
+            self._ldepth_dev = [self.device_alloc(P * 3), self.device_alloc(P * 2), self.device_alloc(P), 0, 0]
+        if len(points) > self._ldepth_dev[4]:
+            cap = max(len(points), self._ldepth_dev[4] * 3 // 2)
+            if self._ldepth_dev[3]:
+                self.device_free(self._ldepth_dev[3])                     # (waits for the calls that still read it)
+                self._ldepth_dev[3] = self._ldepth_dev[4] = 0
+            self._ldepth_dev[3], self._ldepth_dev[4] = self.device_alloc(cap * 16), cap
+        d_rgb, d_depth, d_sem, d_points, _ = self._ldepth_dev
+        self.device_upload(d_rgb, rgb)
+        if len(points):
+            self.device_upload(d_points, points)
+        if sem is not None:
+            self.device_upload(d_sem, np.ascontiguousarray(sem, np.uint8))
+        self.lidar_depth_device(d_points, len(points), T, d_depth)
+        return self.process_frame_device(d_rgb, d_depth, d_sem if sem is not None else None, pose)
 
     def auto_loop_stats(self) -> dict:
         """checked, attempts, closed, none, rejected, failed, no_old_map, last_census, and last = the last attempt's info as

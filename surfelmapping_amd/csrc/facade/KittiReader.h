@@ -4,11 +4,16 @@
 // (3x4 row-major camera->world per line, right-multiplied by the -0.06 m x-offset T20: gui/KittiReader.cpp:296-302)
 // and times.txt.  With estimateDepth the reference skips PSMNet and hands on a null depth (gui/KittiReader.cpp:68,87); here the
 // flag also reads the right camera's <dir>/image_3/%06d.png into rgbRight, for SurfelMapping::processFrameStereo.
+// setUseLidar(true) (off by default) reads <dir>/velo_to_cam.txt (12 floats, a row-major 3 x 4: the odometry benchmark's Tr line)
+// and, per frame, <dir>/velodyne/%06d.bin (x, y, z, reflectance as floats) into velodyne, for SurfelMapping::processFrameLidar; the
+// frame's depth image is then not read (depth stays null).  With estimateDepth as well, both the right image and the scan are read.
+// An empty scan is a frame with numPoints == 0 and velodyne not null.  setUseLidar(false) puts velodyne and numPoints back to none.
 // PNG decoding: 8/16-bit grey, 8-bit RGB/RGBA, non-interlaced, all five filter types, zlib inflate (link with -lz).  Only subLevel == 0 is supported (the reference's sub-sampling branch is unused by build_map.cpp:279
 // and writes the sub-sampled semantics into the depth buffer, gui/KittiReader.cpp:206).
 #pragma once
 #include <zlib.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -102,6 +107,21 @@ public:
     }
     bool good() const { return ok_; }
 
+    // Read the lidar scan of every frame instead of its depth image.  false (and the reader no longer good) if the
+    // lidar-to-camera transform cannot be read.
+    bool setUseLidar(bool on)
+    {
+        use_lidar = on;
+        if (!on) { velodyne = nullptr; numPoints = 0; return true; }
+        depth = nullptr;                           // (a frame read before the switch no longer stands for the next ones)
+        std::ifstream file(datasetDir_ + "/velo_to_cam.txt");
+        int n = 0;
+        for (int i = 0; i < 16; ++i) veloToCam[i] = (i % 5 == 0) ? 1.0f : 0.0f;
+        while (n < 12 && (file >> veloToCam[n])) ++n;
+        if (n != 12) { std::printf("CANNOT read the lidar-to-camera transform from %s/velo_to_cam.txt\n", datasetDir_.c_str()); ok_ = false; }
+        return n == 12;
+    }
+
     bool getNext() { ++currentFrameId; return load(); }                       // gui/KittiReader.cpp:56-75
     bool getLast() { --currentFrameId; return load(); }                       // :77-96
     void saveState() { savedFrameId = currentFrameId; }
@@ -122,6 +142,9 @@ public:
     unsigned char *rgb;
     unsigned char *rgbRight;                  // the right camera's image, R first; null unless estimateDepth
     unsigned char *semantic;
+    const float *velodyne = nullptr;          // the frame's scan, numPoints x (x, y, z, reflectance); null unless setUseLidar(true)
+    unsigned numPoints = 0;
+    float veloToCam[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};   // lidar frame -> camera frame, row-major 4 x 4
     int currentFrameId;
     double time;
     int savedFrameId;
@@ -175,7 +198,7 @@ private:
         if (estimate_depth) {
             if (!loadRgb(rgbRightDir + name, im, rgbRightBuf_)) return false;
             rgbRight = rgbRightBuf_.data();
-        } else {
+        } else if (!use_lidar) {
             if (!sm_png::read(depthDir + name, im) || im.w != width_ || im.h != height_ || im.channels != 1) {
                 std::printf("CANNOT read depth image from %s%s", depthDir.c_str(), name);
                 return false;
@@ -184,6 +207,18 @@ private:
             for (size_t p = 0; p < P; ++p)
                 depthBuf_[p] = im.depth == 16 ? (unsigned short)((im.data[p * 2] << 8) | im.data[p * 2 + 1]) : im.data[p];
             depth = depthBuf_.data();
+        }
+        if (use_lidar) {
+            char bin[32];
+            std::snprintf(bin, sizeof bin, "/velodyne/%06d.bin", currentFrameId);
+            std::ifstream f(datasetDir_ + bin, std::ios::binary);
+            if (!f) { std::printf("CANNOT read the lidar scan from %s%s", datasetDir_.c_str(), bin); return false; }
+            std::vector<char> raw((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+            if (raw.size() % 16) { std::printf("%s%s is not a whole number of points", datasetDir_.c_str(), bin); return false; }
+            veloBuf_.assign(std::max<size_t>(raw.size() / 4, 4), 0.0f);      // (never empty: velodyne is not null for a frame)
+            if (!raw.empty()) std::memcpy(veloBuf_.data(), raw.data(), raw.size());
+            velodyne = veloBuf_.data();
+            numPoints = (unsigned)(raw.size() / 16);
         }
         if (use_semantic) {
             if (!sm_png::read(semanticDir + name, im) || im.w != width_ || im.h != height_ || im.channels != 1 || im.depth != 8) {
@@ -215,6 +250,8 @@ private:
     int width_ = 0, height_ = 0;
     float fx_ = 0, fy_ = 0, cx_ = 0, cy_ = 0;
     bool estimate_depth, use_semantic, ok_;
+    bool use_lidar = false;
+    std::vector<float> veloBuf_;
     std::vector<double> times;
     std::vector<Eigen::Matrix4f> groundTruth_;
     std::vector<unsigned char> rgbBuf_, rgbRightBuf_, semBuf_;

@@ -761,6 +761,41 @@ public:
     // the depth image (millimetres, 0 = invalid) of the last processFrameStereo; empty before the first
     const std::vector<unsigned short> &getLastStereoDepth() { return stereoDepth_; }
 
+    // Make the depth image of a frame from its lidar scan (sm_set_lidar_depth).  params null: the defaults
+    // (sm_default_lidar_depth_params).  on = false: off, and the stage's planes are freed.
+    bool setLidarDepth(bool on, const sm_lidar_depth_params *params = nullptr)
+    {
+        int rc;
+        if (!on) {
+            rc = sm_set_lidar_depth(ctx_, nullptr);
+        } else {
+            sm_config c;
+            sm_default_config(&c, Config::W(), Config::H(), Config::fx(), Config::fy(), Config::cx(), Config::cy());
+            sm_lidar_depth_params lp;
+            sm_default_lidar_depth_params(&c, &lp);
+            rc = sm_set_lidar_depth(ctx_, params ? params : &lp);
+        }
+        if (rc == SM_OK) return true;
+        std::printf("setLidarDepth: %s\n", sm_last_error());
+        return false;
+    }
+    // processFrame with the depth image made from the scan (sm_lidar_depth; setLidarDepth(true) first): points4 holds n points
+    // (x, y, z, reflectance) in the lidar's frame, veloToCam16 the row-major 4 x 4 from there to the camera's (KittiReader's
+    // velodyne, numPoints and veloToCam).  false (and nothing processed) if the stage fails.
+    bool processFrameLidar(const unsigned char *rgb, const float *points4, unsigned n, const float *veloToCam16,
+                           const unsigned char *semantic = nullptr, const Eigen::Matrix4f *gtPose = nullptr)
+    {
+        lidarDepth_.resize((size_t)Config::W() * Config::H());
+        if (sm_lidar_depth(ctx_, points4, n, veloToCam16, lidarDepth_.data(), nullptr, nullptr) != SM_OK) {
+            std::printf("processFrameLidar: %s\n", sm_last_error());
+            return false;
+        }
+        processFrame(rgb, lidarDepth_.data(), semantic, gtPose);
+        return true;
+    }
+    // the depth image (millimetres, 0 = empty) of the last processFrameLidar; empty before the first
+    const std::vector<unsigned short> &getLastLidarDepth() { return lidarDepth_; }
+
     // With setAutoRetire on: after every retirement, the records of its map files within `radius` metres of that frame's camera
     // come back into the model and leave the files, so that a camera that returns finds what it left (sm_set_auto_recall;
     // 0 < radius <= the retirement's minDistance).  radius <= 0: off.
@@ -939,6 +974,7 @@ private:
         return ok;
     }
     std::vector<unsigned short> stereoDepth_;
+    std::vector<unsigned short> lidarDepth_;
     bool beginCleanPoints = false;
     bool async_ = false;
 };

@@ -17,6 +17,7 @@
 //   sm_scene.hip     scenes (sm_render_image_scene, sm_lidar_sweep_scene): actor files resident for a call, drawn under a pose per view by both of the above
 //   sm_place.hip     place recognition (sm_fern_*, sm_search_pose_at, sm_close_loop_at): fern codes, the keyframe database, the match
 //   sm_stereo.hip    stereo depth (sm_stereo_*): census, matching costs, path costs, winner and depth of a rectified pair
+//   sm_lidar_depth.hip  lidar depth (sm_lidar_depth*): a scan z-buffered into the camera and completed to a dense depth image
 //   sm_fill.hip      hole filling (sm_fill_*, sm_render_image_ex's and sm_render_image_maps_ex's stage): depth of a view, push-pull completion
 //   sm_blend.hip     blended views (sm_render_image_blend, sm_render_image_maps_blend): the visible layer's accumulation and normalisation, a stage of both render paths
 //   sm_simplify.hip  simplification (sm_simplify, sm_simplify_maps): the model or a map set merged per voxel cell, two passes over the records
@@ -303,6 +304,35 @@ struct Fill {
     bool pending = false;              // a stage is enqueued whose tallies and time are not in `stats` yet
     size_t off_pull = 0, off_push = 0; // ... and where its tallies lie in the scratch
     size_t n_pull = 0, n_push = 0;
+};
+
+// lidar depth (sm_lidar_depth.hip, sm_k_lidar_depth.h): everything sm_set_lidar_depth allocates, and the last call's tally, folded
+// from the kernels' per-block parts once they are done.  on = false: none of it exists.
+struct LidarDepth {
+    static constexpr int MAX_LAUNCHES = 12;    // of the debug form, every step a launch; the default form makes four
+    static constexpr int N_EV = MAX_LAUNCHES + 1;      // before the first launch and after each
+    bool on = false;
+    sm_lidar_depth_params p{};
+    Dev<uint64_t> d_key;               // W * H, KEY_EMPTY between calls
+    Dev<uint16_t> d_v, d_rowmax;       // the v plane after FILL_SMALL; FILL_LARGE's row pass
+    Dev<uint16_t> d_tmp;               // the debug form's second v plane
+    Dev<uint32_t> d_top;               // [W]
+    Dev<uint32_t> d_part;              // the tallies: project's blocks | finish's tiles (uint4) | chain's tiles (uint2); the debug form:
+                                       // project's blocks | eight words
+    size_t part_project = 0, tiles = 0;
+    Dev<uint16_t> d_depth, d_sparse;   // sm_lidar_depth's outputs on the device
+    Dev<int32_t> d_index;
+    Dev<float4> d_points;              // ... and its copy of the scan, grown on demand
+    size_t points_cap = 0;
+    bool timed = false;                // SM_LIDAR_DEPTH_TIMING=1 at sm_set_lidar_depth: an event after every launch (tools/lidar_depth_probe.py)
+    bool unfused = false;              // SM_LIDAR_DEPTH_UNFUSED=1 at sm_set_lidar_depth: the debug form
+    Event ev[N_EV];
+    sm_lidar_depth_stats_t stats{};
+    bool stats_valid = false;
+    bool pending = false;              // a call is enqueued whose tallies and times are not in `stats` yet
+    uint32_t blocks_project = 0;       // ... and how many blocks its projection had
+    int n_slots = 0;                   // ... how many entries of launch_ms it has,
+    bool ran[MAX_LAUNCHES] = {};       // ... and which of them it launched
 };
 
 // blended views (sm_blend.hip, sm_k_blend.h): the accumulators beside d_export, owned like the fill scratch and grown on demand;
@@ -685,6 +715,7 @@ struct sm_ctx {
     Lidar lid;
     Place place;
     Stereo stereo;
+    LidarDepth ldepth;
     Fill fill;
     Blend blend;
     Simplify simp;

@@ -10,10 +10,13 @@ __device__ __forceinline__ PixelLoads load_pixel(int q, int i, int j, const Fram
 {
     const int H = fp.H, W = fp.W;
     PixelLoads r;
+    // a lane behind the last pixel (the second block of an odd block count, the rest of a partial block) loads pixel P - 1's words
+    // and nobody uses them, but (i, j) are still those of the lane's own q there: in a one-column image i > 0 then, and q - H would
+    // be the word before the plane.  (j > 0 implies q >= 1 everywhere: H = 1 leaves j = 0.)
     q = min(q, fp.P - 1);
     r.key = keyT[q];
     r.z = depthT[q];
-    r.zl = depthT[i > 0 ? q - H : q];
+    r.zl = depthT[i > 0 ? max(q - H, 0) : q];
     r.zu = depthT[j > 0 ? q - 1 : q];
     r.zr = depthT[i < W - 1 && q + H < fp.P ? q + H : q];
     r.zd = depthT[j < H - 1 && q + 1 < fp.P ? q + 1 : q];

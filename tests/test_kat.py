@@ -1,4 +1,5 @@
-"""Known-answer tests K1..K13 for the CPU oracle.
+"""Known-answer tests K1..K16, K18 and K19 for the CPU oracle and the HIP product (K17 is the raw feedback
+cloud's, K20 and K22 are open).
 
 The reference ships no tests or golden vectors for the fusion path ("parity unpinned"),
 so the oracle is pinned by answers derived by hand from the cited shader lines
@@ -284,6 +285,8 @@ def test_k11_time_window(backend):
     assert set(np.unique(idx).tolist()) == {0, 2}       # 250-1 > 200 -> id 1 absent
     o.stage_predict_indices(IDENT, 201, 30.0, 200)      # 201-1 == 200 -> not > -> present
     assert set(np.unique(o.download_index_map()[0]).tolist()) == {0, 1, 2}
+    o.stage_predict_indices(IDENT, 202, 30.0, 200)      # 202-1 == 201 > 200 -> absent: the edge is bracketed on both sides
+    assert set(np.unique(o.download_index_map()[0]).tolist()) == {0, 2}
     dm = np.zeros((cfg.height, cfg.width), np.float32)
     o.set_frame(depth_metric=dm, sem=np.zeros_like(dm, dtype=np.uint8))
     o.stage_process_conflict(IDENT, 1.0, 30.0, 0.0, 0)
@@ -511,3 +514,157 @@ def test_k16_first_wh_conflicts_only_hand_derived(backend, cap):
     assert c["offset"] == (22 if cap else 1)
     m2 = o2.download_model()
     np.testing.assert_array_equal(m2[:c["offset"]], m)
+
+
+# ---------------------------------------------------------------- K18 geometry.glsl:12-24 at the image border
+def _k18_depth_mm(W, H):
+    i, j = np.meshgrid(np.arange(W), np.arange(H))
+    return (4000 + 50 * i + 30 * j).astype(np.uint16)              # tilted both ways: 5 cm per column, 3 cm per row
+
+
+def _k18_surfel(zmm, i, j, f, cx, cy, reading):
+    """(position, unit normal, radius) of the new surfel of pixel (i, j) in float64.  getVertex geometry.glsl:5-9, getNormal
+    :12-24, getRadius surfels.glsl:19-32; `reading` says what a neighbour OUTSIDE the image is taken to be:
+      'edge'      GL_CLAMP_TO_EDGE as the shader has it: the texel fetch clamps, i.e. the depth is the pixel's own (one step
+                  out of the image lands on the pixel's own texel), while the coordinate handed to getVertex stays x +- 1, y +- 1
+      'coord'     the coordinate is clamped to the image, [0, cols] x [0, rows], as well
+      'one-sided' the neighbour is the pixel's own vertex: a one-sided difference
+      'zero'      the depth outside the image reads as 0"""
+    H, W = zmm.shape
+    x, y = i + 0.5, j + 0.5                                         # data.vert:62-63 at a texel centre
+    z = zmm.astype(np.float64) / 1000.0
+
+    def vertex(zz, xx, yy):
+        return np.array([(xx - cx) * zz / f, (yy - cy) * zz / f, zz])
+
+    own = vertex(z[j, i], x, y)
+
+    def neighbour(di, dj):
+        ii, jj = i + di, j + dj
+        if 0 <= ii < W and 0 <= jj < H:
+            return vertex(z[jj, ii], x + di, y + dj)
+        if reading == "edge":
+            return vertex(z[j, i], x + di, y + dj)
+        if reading == "coord":
+            return vertex(z[j, i], min(max(x + di, 0.0), float(W)), min(max(y + dj, 0.0), float(H)))
+        if reading == "one-sided":
+            return own
+        return vertex(0.0, x + di, y + dj)
+
+    n = np.cross(neighbour(-1, 0) - neighbour(1, 0), neighbour(0, -1) - neighbour(0, 1))
+    n /= np.linalg.norm(n)
+    r = own[2] / f * 1.41421356237                                  # meanFocal = f: fx == fy
+    return own, n, min(2.0 * r, r / abs(n[2]))
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_k18_border_normals_clamp_to_edge_hand_derived(backend):
+    """New surfels of the pixels ON the image border: their out-of-image neighbour has the pixel's own depth at the coordinate
+    x +- 1 / y +- 1.  Expected values from the shader lines in float64; the float32 cross product and normalisation of a
+    unit vector lose at most a few 1e-7 per component, hence atol 1e-5 (K7 uses 1e-6 for positions).  The three other readings
+    one could have of the border are shown to be more than 1e-2 away at every one of these pixels, so the tolerance tells
+    them apart a thousand times over."""
+    W, H, f = 16, 12, 100.0
+    cfg, o = mk(backend, W=W, H=H)
+    zmm = _k18_depth_mm(W, H)
+    rgb, _, sem = plane_frame(cfg, 0)
+    o.process_frame(rgb, zmm, sem, IDENT)
+    o.process_frame(rgb, zmm, sem, IDENT)
+    m = o.download_model()
+    i = np.rint(m[:, 0] / m[:, 2] * f + cfg.cx - 0.5).astype(int)
+    j = np.rint(m[:, 1] / m[:, 2] * f + cfg.cy - 0.5).astype(int)
+    at = {(a, b): k for k, (a, b) in enumerate(zip(i.tolist(), j.tolist()))}
+    border = [(a, b) for a in range(W) for b in range(H) if (a + b) % 2 == 1 and (a in (0, W - 1) or b in (0, H - 1))]
+    for must in [(0, 5), (W - 1, 4), (5, 0), (4, H - 1), (W - 1, 0), (0, H - 1), (1, 0), (0, 1), (W - 2, H - 1), (W - 1, H - 2)]:
+        assert must in border        # column 0, column W-1, row 0, row H-1, the two corners on the checkerboard, corner-adjacent ones
+    assert len(at) == m.shape[0] == W * H // 2                      # every checkerboard pixel is emitted (K3), the border's included
+    for px in border:
+        assert px in at, f"border pixel {px} was not emitted"
+        pos, n, r = _k18_surfel(zmm, *px, f, cfg.cx, cfg.cy, "edge")
+        for other in ("coord", "one-sided", "zero"):
+            n_other = _k18_surfel(zmm, *px, f, cfg.cx, cfg.cy, other)[1]
+            assert not np.all(np.isfinite(n_other)) or np.abs(n_other - n).max() > 1e-2, (px, other, n, n_other)
+        got = m[at[px]]
+        np.testing.assert_allclose(got[0:3], pos, rtol=0, atol=1e-6, err_msg=f"position at {px}")
+        np.testing.assert_allclose(got[8:11], n, rtol=0, atol=1e-5, err_msg=f"normal at {px}")
+        assert got[11] == pytest.approx(r, rel=1e-5), f"radius at {px}"
+    # an interior pixel for comparison: every reading agrees there, and so must the backend
+    pos, n, r = _k18_surfel(zmm, 6, 5, f, cfg.cx, cfg.cy, "zero")
+    np.testing.assert_allclose(m[at[(6, 5)]][8:11], n, rtol=0, atol=1e-5)
+
+
+# ---------------------------------------------------------------- K19 conflict.vert:35 (the edges of the view test are inclusive)
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_k19_conflict_view_edges_hand_derived(backend):
+    """conflict.vert:35 `if(u < stereoBorder || u > cols || v < 0 || v > rows || z <= minDepth || z >= maxDepth)` skips a surfel:
+    u and v exactly ON an edge are tested, the depth limits themselves are not.  fx = fy = 64, z = 4, cx = 15.5, cy = 7.5 and
+    coordinates that are short binary fractions make u = fx * (x / z) + cx = 16 x + 15.5 exact in float32 (two scalings by powers
+    of two, then one addition whose result is representable -- or, for the neighbours, rounds as worked out below).
+    A surfel at u == cols samples texcoord 1.0, i.e. texel floor(1.0 * cols) clamped to the LAST column (GL_NEAREST,
+    GL_CLAMP_TO_EDGE); likewise v == rows and the last row."""
+    W, H = 32, 16
+    f32 = np.float32
+    inst = make(backend, W, H, 64.0, 64.0, W / 2 - 0.5, H / 2 - 0.5, stereo_border=8.0, preprocess=0)
+    e = 2.0 ** -25
+    #                x                     y                     z     tested?
+    cases = [
+        (-0.46875,            0.0,                  4.0,  True),     # 1  16 x + 15.5 = 8 = stereoBorder exactly
+        (-0.46875 - e,        0.0,                  4.0,  False),    # 2  x one ulp (2^-25) down: 8 - 2^-21, the float32 below 8
+        (1.03125,             0.0,                  4.0,  True),     # 3  16 x + 15.5 = 32 = cols exactly
+        (1.03125 + 8 * e,     0.0,                  4.0,  False),    # 4  x two ulps (2^-22) up: 32 + 2^-18, the float32 above 32 (one ulp
+                                                                     #    of x gives 32 + 2^-19, a tie that rounds back to the even 32)
+        (0.0,                 -0.46875,             4.0,  True),     # 5  16 y + 7.5 = 0 exactly
+        (0.0,                 -0.46875 - e,         4.0,  False),    # 6  y one ulp down: v = -2^-21, the nearest v below 0 this form can give
+        (0.0,                 0.53125,              4.0,  True),     # 7  16 y + 7.5 = 16 = rows exactly
+        (0.0,                 0.53125 + 4 * e,      4.0,  False),    # 8  y two ulps (2^-23) up: 16 + 2^-19, the float32 above 16
+        (0.0,                 0.0,                  1.0,  False),    # 9  z == minDepth
+        (0.0,                 0.0,                  float(np.nextafter(f32(1.0), f32(2.0))), True),      # 10
+        (0.0,                 0.0,                  30.0, False),    # 11 z == maxDepth
+        (0.0,                 0.0,                  float(np.nextafter(f32(30.0), f32(0.0))), True),     # 12
+    ]
+    # the derivation above, replayed in float32 (conflict.vert:27-33: xl = x / z, u = cam.z * xl + cam.x)
+    def uv(x, y, z):
+        return f32(64.0) * (f32(x) / f32(z)) + f32(15.5), f32(64.0) * (f32(y) / f32(z)) + f32(7.5)
+    assert [f32(c[0]) == c[0] and f32(c[1]) == c[1] for c in cases] == [True] * len(cases)        # every coordinate IS a float32
+    assert uv(*cases[0][:3])[0] == f32(8.0) and uv(*cases[1][:3])[0] == np.nextafter(f32(8.0), f32(0.0))
+    assert uv(*cases[2][:3])[0] == f32(32.0) and uv(*cases[3][:3])[0] == np.nextafter(f32(32.0), f32(64.0))
+    assert uv(*cases[4][:3])[1] == f32(0.0) and uv(*cases[5][:3])[1] == f32(-2.0 ** -21)
+    assert uv(*cases[6][:3])[1] == f32(16.0) and uv(*cases[7][:3])[1] == np.nextafter(f32(16.0), f32(32.0))
+    model = np.stack([surfel(0, 0, 9.0)] + [surfel(x, y, z, conf=1.8) for x, y, z, _ in cases])    # id 0 never conflicts (K6)
+    expect = np.array([False] + [c[3] for c in cases])
+    sem = np.zeros((H, W), np.uint8)
+
+    def conflicts(dm):
+        inst.upload_model(model)
+        inst.set_frame(depth_metric=dm, sem=sem)
+        inst.stage_process_conflict(IDENT, 1.0, 30.0, 0.0, 0)
+        n = inst.counts()["conflict_count"]
+        inst.stage_update_conflict(); inst.stage_back_mapping()
+        m = inst.download_model()
+        assert m.shape[0] == model.shape[0]                         # 1.8 - 1 > 0: nobody dies, the order stands
+        hit = m[:, 3] == f32(1.8) - f32(1.0)
+        assert np.all(hit | (m[:, 3] == model[:, 3])) and hit.sum() == n
+        return hit
+
+    # a zero depth reads as maxDepth + 20 (conflict.vert:56-59): every surfel the view test lets through conflicts
+    np.testing.assert_array_equal(conflicts(np.zeros((H, W), np.float32)), expect)
+    # which texel u == cols and v == rows sample: the measurement equals the surfels' depth (4 * lambda - 4 * lambda = 0, not > 0)
+    # everywhere but in one column / one row, where it is farther
+    def only(col=None, row=None):
+        dm = np.full((H, W), 4.0, np.float32)
+        if col is not None:
+            dm[:, col] = 5.0
+        if row is not None:
+            dm[row, :] = 5.0
+        hit = conflicts(dm)
+        return set(np.flatnonzero(hit).tolist())
+    near = {10}                                    # (surfel 10 at z = 1 + ulp is in front of a measurement of 4 m wherever that is)
+    assert only() == near
+    assert only(col=W - 1) == near | {3}           # surfel 3 (u == cols) reads the last column ...
+    assert only(col=W - 2) == near                 # ... and nothing else
+    assert only(row=H - 1) == near | {7}           # surfel 7 (v == rows) reads the last row
+    assert only(row=H - 2) == near
+    assert only(col=8) == near | {1}               # u == stereoBorder == 8.0 reads column 8
+    assert only(col=7) == near
+    assert only(row=0) == near | {5}               # v == 0 reads row 0
+    assert only(row=1) == near

@@ -2016,6 +2016,76 @@ int sm_query_points_maps(sm_ctx *s, const sm_map_source *src, const sm_points_pa
                          float *d2, int32_t *id, float *centre3, float *normal3, float *radius, uint8_t *rgb, uint8_t *sem);
 int sm_query_points_stats(sm_ctx *s, sm_points_stats_t *out); /* SM_E_ARG before the first call */
 
+/* ---- packed map files: 20-byte records that every map-set call reads (DESIGN.md "4aa. Packed map files") ----
+ * A map file (u32 count | i32 startId | i32 endId | count x 12 fp32, 48 bytes a record) carries far less than 48 bytes of
+ * information per record.  sm_pack_maps writes the files of a map set in a packed format of 20 bytes a record; every call that
+ * READS a map set -- an sm_map_source -- takes plain and packed files, mixed in one list, and decodes a packed chunk on the GPU as
+ * it lands.  A record's id stays its position in the set.  sm_unpack_maps makes plain files again.  Nothing calls either unasked.
+ *   The file, little-endian:
+ *     header, 32 bytes: u32 magic "SMPK" (0x4B504D53) | u32 version = 1 | u32 count | i32 startId | i32 endId | i32 pos_step_log2
+ *       (s, -14..-6) | u32 n_blocks = ceil(count / 256) | u32 0.
+ *     directory, n_blocks entries of 32 bytes, one per 256 consecutive records (the last block may be shorter): float origin[3] |
+ *       float time_base | float init_base | u32 flags (bit 0 = RAW, the others 0) | u64 offset of the block in the payload.
+ *     payload, block after block without gaps: a packed block of m records is m x 20 bytes, a RAW block its m x 48 bytes verbatim.
+ *     The offsets are the prefix sums of the blocks' sizes, and the file's length is exactly 32 + 32 * n_blocks + their sum; a file
+ *     that fails either is refused (SM_E_ARG, sm_last_error() names it) by every call, before anything is computed.  A file that
+ *     begins with the magic is a packed one unless it has the very length of a plain file of 0x4B504D53 records (60 GB).
+ *   A packed record m[0..11] = x y z conf | colour 0 init_time time | nx ny nz radius, five u32:
+ *     w0 = qx | qy << 16      w1 = qz | qr << 16      w2 = the bits of m[4]      w3 = ou | ov << 10 | qc << 20      w4 = dt | di << 16
+ *   All arithmetic is IEEE fp32, one operation at a time in the written order (no fused multiply-add), U = 2^-s, D = 2^s:
+ *     origin[k] = floor(min over the block of m[k] * U) * D + 0;   q = floor((m[k] - origin[k]) * U + 0.5);   decoded origin[k] + (float)q * D
+ *     qr = floor(radius * 8192 + 0.5), decoded qr / 8192;   qc = floor(conf * 16 + 0.5) in 12 bits, decoded qc / 16
+ *     time_base, init_base = the block's minima of m[7], m[6];   dt = m[7] - time_base, di = m[6] - init_base, decoded base + (float)d
+ *     normal, octahedral: a = (|nx| + |ny|) + |nz|, p = (nx / a, ny / a); if nz < 0: p = ((1 - |py|) * sgn(px), (1 - |px|) * sgn(py))
+ *       with sgn(v) = v >= 0 ? 1 : -1; ou = clamp(floor((px * 0.5 + 0.5) * 1023 + 0.5), 0, 1023), ov likewise.  Decoded in integers:
+ *       ui = 2 ou - 1023, vi = 2 ov - 1023, zi = 1023 - |ui| - |vi|, t = max(-zi, 0), xi = ui >= 0 ? ui - t : ui + t, yi likewise, then
+ *       (xi, yi, zi) / sqrt((float)(xi^2 + yi^2 + zi^2)): decode(encode(decode(c))) == decode(c) for every one of the 2^20 codes.
+ *     m[5] decodes to +0.
+ *   A block is packed if and only if every one of its records has: every field but the colour word finite; |x|, |y|, |z| < 8192;
+ *     every q <= 65535 (at the default step of 2^-10 m: an extent below 64 m); radius >= 0 and qr <= 65535; conf >= 0 and qc <=
+ *     4095; m[5] = +0; both times integers in [+0, 2^24) with dt, di <= 65535; | |n|^2 - 1 | <= 2^-10 with |n|^2 = (nx nx + ny ny) +
+ *     nz nz.  Every other block is RAW, and its directory entry holds zeros beside the flag and the offset.  RAW is what makes the
+ *     format safe for NaN rows, for a tiled file that jumps across the map and for anything a caller has written into a file.
+ *   Errors of a packed block against its source: position <= D / 2 plus one fp32 ulp of the coordinate, radius <= 2^-14 m, conf <=
+ *     1 / 32, normal <= 0.25 degrees (worst case seen 0.235); colour, times and order exact.  unpack(pack(unpack(P))) ==
+ *     unpack(P) byte for byte.
+ * sm_pack_maps: file i of the source becomes "<out_prefix>_%06u.smp" with i's frame range; with include_model the live model
+ *   follows as the next number, frame range 0, 0.  An empty file becomes a packed file of no block, so the lists stay parallel.  A
+ *   packed source is packed again from its decoded records.  Sources and model stay as they are.  Every output is written as
+ *   "<name>.pack.tmp"; all are renamed into place only after the last one is complete, and on any error none is and no temporary
+ *   is left.  SM_E_ARG: NULLs, pos_step_log2 outside -14..-6, an output name equal to a source path (checked before anything is
+ *   written), the file checks of sm_render_image_maps; SM_E_UNSUPPORTED: a sharded or rig context.
+ * sm_unpack_maps: file i becomes "<out_prefix>_%06u.bin", a plain file: a packed source decoded, a plain one copied through
+ *   verbatim.  include_model must be 0.  Written and refused as above (temporaries "<name>.unpack.tmp").
+ * sm_pack_stats: what the context's last sm_pack_maps or sm_unpack_maps did (SM_E_ARG before the first).
+ * What does NOT take a packed file: sm_load_map and a scene's actor files ("<path> is a packed map file; sm_unpack_maps makes a
+ *   plain one": SM_E_ARG, for an actor file SM_E_UNSUPPORTED), and the calls that rewrite the files they are given -- sm_recall in
+ *   SM_RECALL_MOVE, sm_warp_by_time and through it the loop closures: SM_E_UNSUPPORTED naming the file, before anything changes
+ *   (a file the context's file index lets them skip unopened is not examined).  SM_RECALL_COUNT and SM_RECALL_COPY read packed
+ *   files like plain ones.  Retirement writes plain files. */
+typedef struct sm_pack_params {
+    int32_t pos_step_log2;      /* -14..-6: the position step is 2^pos_step_log2 m      default -10 (0.977 mm) */
+} sm_pack_params;
+typedef struct sm_pack_stats_t {
+    uint64_t records;           /* of all sources */
+    uint64_t bytes_in;          /* the source files' sizes, plus 48 per record of the live model */
+    uint64_t bytes_out;         /* the output files' sizes */
+    uint32_t files;             /* written */
+    uint32_t blocks;            /* of 256 records in the packed files (written by sm_pack_maps, read by sm_unpack_maps) */
+    uint32_t raw_blocks;        /* ... of which RAW */
+    uint32_t chunks;            /* of at most 2^20 records through the device */
+    float read_ms;              /* host: reading the files */
+    float copy_ms;              /* device: the chunks' copies in (and the decode of packed sources) */
+    float unpack_ms;            /* ... of which the decode of packed sources (k_unpack) */
+    float device_ms;            /* device: the encoder's kernels (sm_unpack_maps: 0, the decode is part of copy_ms) */
+    float write_ms;             /* host: the copies back and writing the files */
+    float total_ms;
+} sm_pack_stats_t;
+int sm_default_pack_params(sm_pack_params *p);               /* pure, no context */
+int sm_pack_maps(sm_ctx *s, const sm_map_source *src, const sm_pack_params *p, const char *out_prefix);
+int sm_unpack_maps(sm_ctx *s, const sm_map_source *src, const char *out_prefix);
+int sm_pack_stats(sm_ctx *s, sm_pack_stats_t *out);
+
 /* ---- per-pass entry points (GlobalModel / IndexMap methods), synchronous ---- */
 /* Upload RGB / metric depth / semantic textures directly (bypasses p0). */
 int sm_set_frame(sm_ctx *s, const uint8_t *rgb, const float *depth_metric,

@@ -329,6 +329,16 @@ class SmTileStats(C.Structure):
                 ("total_ms", C.c_float)]
 
 
+class SmPackParams(C.Structure):
+    _fields_ = [("pos_step_log2", C.c_int32)]
+
+
+class SmPackStats(C.Structure):
+    _fields_ = [("records", C.c_uint64), ("bytes_in", C.c_uint64), ("bytes_out", C.c_uint64), ("files", C.c_uint32), ("blocks", C.c_uint32),
+                ("raw_blocks", C.c_uint32), ("chunks", C.c_uint32), ("read_ms", C.c_float), ("copy_ms", C.c_float), ("unpack_ms", C.c_float),
+                ("device_ms", C.c_float), ("write_ms", C.c_float), ("total_ms", C.c_float)]
+
+
 SM_SEGMENT_LOOSE, SM_SEGMENT_SMALL, SM_SEGMENT_SKIPPED = 0xFFFFFFFE, 0xFFFFFFFD, 0xFFFFFFFC
 SEGMENT_KINDS = ("NUMBERED", "SMALL", "SKIPPED", "LOOSE")                # the bits of write_mask, the entries of info.counts
 
@@ -615,6 +625,10 @@ PROTOTYPES = {
     "sm_default_tile_params": (ci, [P(SmTileParams)]),
     "sm_tile_maps": (ci, [vp, _SRC, P(SmTileParams), cs]),
     "sm_tile_stats": (ci, [vp, P(SmTileStats)]),
+    "sm_default_pack_params": (ci, [P(SmPackParams)]),
+    "sm_pack_maps": (ci, [vp, _SRC, P(SmPackParams), cs]),
+    "sm_unpack_maps": (ci, [vp, _SRC, cs]),
+    "sm_pack_stats": (ci, [vp, P(SmPackStats)]),
     "sm_default_segment_params": (ci, [P(SmSegmentParams)]),
     "sm_segment_maps": (ci, [vp, _SRC, P(SmSegmentParams), vp, vp, u32, cs, P(SmSegmentInfo)]),
     "sm_segment_stats": (ci, [vp, P(SmSegmentStats)]),
@@ -941,6 +955,59 @@ def tile_params(**over) -> SmTileParams:
     return _params(SmTileParams, "sm_default_tile_params", None, over)
 
 
+def pack_params(**over) -> SmPackParams:
+    """sm_default_pack_params (pos_step_log2 -10: positions in steps of 2^-10 m) with fields overridden"""
+    return _params(SmPackParams, "sm_default_pack_params", None, over)
+
+
+# the packed map-file format (include/sm_c_api.h "packed map files")
+PACK_MAGIC = 0x4B504D53
+PACK_DIR = np.dtype([("origin", "<f4", 3), ("time_base", "<f4"), ("init_base", "<f4"), ("flags", "<u4"), ("offset", "<u8")])
+
+
+def read_packed_map(path):
+    """A packed map file decoded on the host, as the GPU decodes it: (rows float32[n, 12], (start_id, end_id), raw bool[n_blocks] --
+    the blocks stored verbatim).  ValueError for anything but a whole packed file."""
+    data = open(path, "rb").read()
+    if len(data) < 32:
+        raise ValueError(f"{path} is too short for a packed map file")
+    head = np.frombuffer(data, "<u4", 8)
+    n, nb, step = int(head[2]), int(head[6]), int(head[5:6].view(np.int32)[0])
+    if head[0] != PACK_MAGIC or head[1] != 1 or head[7] != 0 or nb != (n + 255) // 256 or not -14 <= step <= -6 or len(data) < 32 + 32 * nb:
+        raise ValueError(f"{path} is not a packed map file")
+    d = np.frombuffer(data, PACK_DIR, nb, 32)
+    raw = (d["flags"] & 1).astype(bool)
+    m = np.minimum(256, n - 256 * np.arange(nb))
+    size = np.where(raw, 48, 20) * m
+    at = np.concatenate([[0], np.cumsum(size)]).astype(np.int64)
+    if (d["flags"] > 1).any() or (d["offset"] != at[:-1].astype(np.uint64)).any() or len(data) != 32 + 32 * nb + int(at[-1]):
+        raise ValueError(f"{path}: the directory of the packed map file and its length disagree")
+    rows = np.zeros((n, 12), np.float32)
+    down = np.float32(2.0 ** step)
+    base = 32 + 32 * nb
+    for b in range(nb):
+        out = rows[256 * b:256 * b + m[b]]
+        if raw[b]:
+            out[:] = np.frombuffer(data, "<f4", 12 * int(m[b]), base + int(at[b])).reshape(-1, 12)
+            continue
+        w = np.frombuffer(data, "<u4", 5 * int(m[b]), base + int(at[b])).reshape(-1, 5)
+        q = np.stack([w[:, 0] & 0xFFFF, w[:, 0] >> 16, w[:, 1] & 0xFFFF], axis=1).astype(np.float32)
+        out[:, 0:3] = d["origin"][b] + q * down
+        out[:, 3] = (w[:, 3] >> 20).astype(np.float32) * np.float32(0.0625)
+        out.view(np.uint32)[:, 4] = w[:, 2]
+        out[:, 6] = d["init_base"][b] + (w[:, 4] >> 16).astype(np.float32)
+        out[:, 7] = d["time_base"][b] + (w[:, 4] & 0xFFFF).astype(np.float32)
+        # the normal: the fold in integers on the codes, then one fp32 normalisation
+        ui, vi = 2 * (w[:, 3] & 1023).astype(np.int64) - 1023, 2 * ((w[:, 3] >> 10) & 1023).astype(np.int64) - 1023
+        zi = 1023 - np.abs(ui) - np.abs(vi)
+        t = np.maximum(-zi, 0)
+        xi, yi = np.where(ui >= 0, ui - t, ui + t), np.where(vi >= 0, vi - t, vi + t)
+        ln = np.sqrt((xi * xi + yi * yi + zi * zi).astype(np.float32))
+        out[:, 8], out[:, 9], out[:, 10] = xi.astype(np.float32) / ln, yi.astype(np.float32) / ln, zi.astype(np.float32) / ln
+        out[:, 11] = (w[:, 1] >> 16).astype(np.float32) * np.float32(1.0 / 8192)
+    return rows, (int(head[3:4].view(np.int32)[0]), int(head[4:5].view(np.int32)[0])), raw
+
+
 def default_segment_params() -> SmSegmentParams:
     """sm_default_segment_params: voxel_mm 200, connectivity 26, by_class 1, every class, min_records 1, write_mask 1 (the records of
     numbered components), max_cells 1 << 24, origin (0, 0, 0)"""
@@ -1045,10 +1112,15 @@ def map_source(paths, include_model=True) -> SmMapSource:
 
 
 def _map_records(path) -> int:
-    """the records a well-formed map file of this length holds (12 bytes of header, 48 per record); 0 where there is no file --
-    the call that reads it reports that"""
+    """the records a well-formed map file of this length holds (12 bytes of header, 48 per record; a packed file: its header's
+    count); 0 where there is no file -- the call that reads it reports that"""
     try:
-        return max(0, (os.path.getsize(path) - 12) // 48)
+        size = os.path.getsize(path)
+        with open(path, "rb") as f:
+            head = np.frombuffer(f.read(12), "<u4")
+        if len(head) == 3 and head[0] == PACK_MAGIC and size != 12 + 48 * PACK_MAGIC:
+            return int(head[2])
+        return max(0, (size - 12) // 48)
     except OSError:
         return 0
 
@@ -2365,6 +2437,29 @@ class SurfelMap:
         """of the last tile_maps: records_in, placed, loose, tiles, largest_tile, files_written, readings, chunks, launches,
         sort_passes, device_ms, sort_ms, read_ms, write_ms, total_ms"""
         return self._stats(SmTileStats, "sm_tile_stats")
+
+    # -- packed map files (sm_pack_maps, sm_unpack_maps)
+    def pack_maps(self, paths, out_prefix, include_model=False, **params) -> list:
+        """The files `paths` -- then (include_model) the live model as one more -- written again in the packed format of 20 bytes
+        a record, file i as "<out_prefix>_%06u.smp" (sm_pack_maps; tests/pack_ref.py restates the format).  Every call that reads
+        a map set takes the packed files in place of the plain ones.  Sources and model stay as they are.  params: the fields of
+        pack_params().  Returns the files written, in order."""
+        p = pack_params(**params)
+        src = map_source(paths, include_model)
+        self._chk(self._L.sm_pack_maps(self._h, C.byref(src), C.byref(p), os.fsencode(out_prefix)), "sm_pack_maps")
+        return ["%s_%06d.smp" % (os.fspath(out_prefix), i) for i in range(len(paths) + (1 if include_model else 0))]
+
+    def unpack_maps(self, paths, out_prefix) -> list:
+        """The files `paths` as plain map files "<out_prefix>_%06u.bin": a packed one decoded, a plain one copied (sm_unpack_maps).
+        Returns the files written, in order."""
+        src = map_source(paths, include_model=False)
+        self._chk(self._L.sm_unpack_maps(self._h, C.byref(src), os.fsencode(out_prefix)), "sm_unpack_maps")
+        return ["%s_%06d.bin" % (os.fspath(out_prefix), i) for i in range(len(paths))]
+
+    def pack_stats(self) -> dict:
+        """of the last pack_maps or unpack_maps: records, bytes_in, bytes_out, files, blocks, raw_blocks, chunks, read_ms, copy_ms,
+        unpack_ms (of copy_ms: the decode of packed sources), device_ms, write_ms, total_ms"""
+        return self._stats(SmPackStats, "sm_pack_stats")
 
     # -- registration of one map set against another (sm_register_maps)
     def register_maps(self, source_paths, target_paths, guess=None, source_model=False, target_model=False, apply=False, **params):

@@ -315,6 +315,41 @@ public:
         return written;
     }
 
+    // The map files `mapFiles` -- then, with withModel, the live model as one more -- written again as packed files of 20 bytes a
+    // record, "<prefix>_%06u.smp" (sm_pack_maps; DESIGN.md "4aa. Packed map files"): every call that reads a map set takes them in
+    // place of the plain ones.  Sources and model stay as they are.  params null: the defaults.  Returns the files written, in
+    // order; none if the call was refused (the message is printed).
+    std::vector<std::string> packMaps(const std::vector<std::string> &mapFiles, const std::string &prefix, bool withModel = false,
+                                      const sm_pack_params *params = nullptr)
+    {
+        std::vector<const char *> paths;
+        for (const std::string &f : mapFiles) paths.push_back(f.c_str());
+        const sm_map_source src{paths.data(), (uint32_t)paths.size(), withModel ? 1 : 0};
+        sm_pack_params p;
+        sm_default_pack_params(&p);
+        if (params) p = *params;
+        (void)sm_sync(ctx_);                                             // (SM_FACADE_ASYNC: frames may still be in flight)
+        if (sm_pack_maps(ctx_, &src, &p, prefix.c_str()) != SM_OK) {
+            std::printf("packMaps: %s\n", sm_last_error());
+            return {};
+        }
+        return numberedFiles(prefix, ".smp", mapFiles.size() + (withModel ? 1 : 0));
+    }
+
+    // ... and back: "<prefix>_%06u.bin", a packed file decoded, a plain one copied (sm_unpack_maps)
+    std::vector<std::string> unpackMaps(const std::vector<std::string> &mapFiles, const std::string &prefix)
+    {
+        std::vector<const char *> paths;
+        for (const std::string &f : mapFiles) paths.push_back(f.c_str());
+        const sm_map_source src{paths.data(), (uint32_t)paths.size(), 0};
+        (void)sm_sync(ctx_);
+        if (sm_unpack_maps(ctx_, &src, prefix.c_str()) != SM_OK) {
+            std::printf("unpackMaps: %s\n", sm_last_error());
+            return {};
+        }
+        return numberedFiles(prefix, ".bin", mapFiles.size());
+    }
+
     // Which rigid transform takes the map set `sourceFiles` onto the set `targetFiles` (sm_register_maps; DESIGN.md "4q.
     // Registration"): two drives of one street, each in the world of its own first pose.  guess: source world -> target world, as
     // far as it is known (within about a cell of the coarsest level, 0.8 m by default); pose: the result, the guess unless the
@@ -819,6 +854,17 @@ public:
     Checker *checker;
 
 private:
+    // "<prefix>_%06u<ext>", 0 .. n - 1: the names sm_pack_maps and sm_unpack_maps give their outputs
+    static std::vector<std::string> numberedFiles(const std::string &prefix, const char *ext, size_t n)
+    {
+        std::vector<std::string> files;
+        for (size_t i = 0; i < n; ++i) {
+            char name[32];
+            std::snprintf(name, sizeof name, "_%06u", (unsigned)i);
+            files.push_back(prefix + name + ext);
+        }
+        return files;
+    }
     sm_ctx *ctx_ = nullptr;
     Eigen::Matrix4f currPose;
     IndexMap indexMap;

@@ -24,6 +24,7 @@
 //   sm_register.hip  registration (sm_register_*): the rigid transform from one map set to another, voxel-cell ICP, one pass over each set
 //   sm_compare.hip   change detection (sm_compare_*): every record of one map set labelled against the voxel tables of another, one pass over each set
 //   sm_voxel.hip     what those three share (sm_voxel.h): the grid, the slot count and the tally's verdict; the lookup table; the ranked output
+//   sm_pack.hip      packed map files (sm_pack_maps, sm_unpack_maps): the encoder, and the decoder the chunk stream runs on a packed file's chunks
 // and, beside it, for everything that touches a map file: sm_mapfile.h (the format: checked open, writer, chunk plan; host only),
 // sm_map_set.h (a listed set of files: the file index, the two openings, a rewrite's per-file record and temporary; host only) and
 // sm_map_stream.h (the double-buffered chunk stream of sm_render_maps.hip, sm_lidar.hip, sm_recall.hip, sm_warp.hip, sm_simplify.hip, sm_register.hip and sm_compare.hip).  The staging
@@ -186,6 +187,12 @@ struct MapStaging {
     Dev<float4> d_pos_conf, d_norm_rad, d_box;
     Dev<uint32_t> d_color;
     Dev<float> d_time;
+    // The packed pair, allocated whole by the first chunk of a packed file (maps_ensure_packed): the chunk's directory slice
+    // through h_dir into d_dir, its payload through h_rec into d_pk, and k_unpack (sm_k_pack.h) decodes it into d_rec on the
+    // context's stream before ev_k0, between ev_u0 and ev_u1 -- so no consumer of d_rec knows which format a file has.
+    Host<uint8_t> h_dir[2];            // pinned, 32 bytes per block of the chunk
+    Dev<uint8_t> d_dir[2], d_pk[2];    // (d_pk: a chunk of RAW blocks needs as much as d_rec)
+    Event ev_u0[2], ev_u1[2];          // (ev_u1[1] is set last: the pair is whole or absent)
 };
 
 // views of a map set (sm_render_maps.hip, sm_k_render_maps.h): the per-view block and the last call's tally
@@ -418,6 +425,14 @@ struct Tile {
     CallScratch<10> scratch;
     Dev<unsigned long long> d_bits;    // the OR and the AND of a batch's keys
     sm_tile_stats_t stats{};
+    bool stats_valid = false;
+};
+
+// packing (sm_pack.hip, sm_k_pack.h): the tallies and events that outlive a call, the last call's tally.  The output buffers live
+// for one call.
+struct Pack {
+    CallScratch<4> scratch;            // per buffer (two): the chunk's payload bytes | its RAW blocks; around the live model's chunks
+    sm_pack_stats_t stats{};
     bool stats_valid = false;
 };
 
@@ -735,6 +750,7 @@ struct sm_ctx {
     Compare cmp;
     RankScratch ranked;
     Tile tile;
+    Pack pack;
     Segment seg;
     Mesh mesh;
     Ground ground;
@@ -804,6 +820,11 @@ int maps_ensure_staging(sm_ctx *s);               // the staging's copy stream, 
 void maps_intake(sm_ctx *s, const float4 *d_rec, uint32_t n);
 // ... into planes and boxes of the caller's (the scenes' resident actors)
 void maps_intake_to(sm_ctx *s, const float4 *d_rec, uint32_t n, const MapsSoA &out, float4 *d_box);
+// ---- sm_pack.hip ----
+int maps_ensure_packed(sm_ctx *s);                // the staging's packed pair: whole or absent
+// k_unpack on the context's stream: the nblk blocks (n records) whose directory entries lie at d_dir and whose payload, beginning
+// at the first block's offset, at d_payload, decoded into n 48-byte records at d_rec
+void maps_unpack(sm_ctx *s, const uint8_t *d_dir, const uint8_t *d_payload, uint32_t n, int32_t pos_step_log2, float4 *d_rec);
 // ---- sm_scene.hip ----
 // The actors of a scene call as the host knows them once its arguments and every actor's header are checked (scene_check), and,
 // after scene_load, what the static sources' loops need to draw them.  The render path and the lidar's pass get it as a pointer,

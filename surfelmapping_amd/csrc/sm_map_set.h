@@ -55,7 +55,7 @@ private:
 };
 
 // ---- a set that is read whole: every header checked against its file's length, in list order; false with the first bad file's
-// message in `err`
+// message in `err`.  Plain and packed files may be mixed: a record's id is its position in the set either way.
 struct ReadSet {
     std::vector<Header> files;
     std::vector<Job> jobs;             // the chunk plan
@@ -66,7 +66,7 @@ inline bool open_read_set(const char *const *paths, uint32_t n, uint32_t chunk, 
 {
     set = ReadSet{std::vector<Header>(n), {}, std::vector<uint64_t>(n), 0};
     for (uint32_t i = 0; i < n; ++i) {
-        if (!sm_mapfile::open_checked(paths[i], who, set.files[i], err)) return false;
+        if (!sm_mapfile::open_checked(paths[i], who, set.files[i], err, false, sm_mapfile::PACKED_OK)) return false;
         set.id_base[i] = set.file_total;
         set.file_total += set.files[i].count;
     }
@@ -112,14 +112,16 @@ struct RewriteSet {
     std::vector<MapFile> files;        // by Job::file
     std::vector<Job> jobs;             // the chunk plan of the files that are read
     uint32_t listed = 0, skipped = 0, read = 0;
+    bool packed_refused = false;       // the opening failed at a packed file that the caller does not take (`err` names it)
 };
 
 // Every file is checked before anything changes: skipped on its stat() alone where skip(entry) says so of its valid index
 // entry (never asked while SM_RECALL_NO_INDEX=1, nor about `known_skip`, a file the caller knows it need not read, -1: none),
-// else its header against its length.  false with the first bad file's message in `err`.
+// else its header against its length.  false with the first bad file's message in `err`.  accept: PACKED_OK for a call that
+// only reads (a packed file is never rewritten); PLAIN_ONLY refuses a packed file by name and says so in set.packed_refused.
 template <typename Skip>
 bool open_rewrite_set(const char *const *paths, uint32_t n, uint32_t chunk, const FileIndex &index, int64_t known_skip, Skip skip, const char *who,
-                      RewriteSet &set, std::string &err)
+                      RewriteSet &set, std::string &err, sm_mapfile::Accept accept = sm_mapfile::PLAIN_ONLY)
 {
     const bool use_index = FileIndex::lookups_on();
     set.files = std::vector<MapFile>(n);
@@ -132,7 +134,13 @@ bool open_rewrite_set(const char *const *paths, uint32_t n, uint32_t chunk, cons
         if (!mf.skipped && use_index)
             if (const FileIndex::Entry *e = index.valid(mf.path, mf.h)) mf.skipped = skip(*e);
         if (mf.skipped) { set.skipped++; continue; }
-        if (!sm_mapfile::open_checked(mf.path, who, mf.h, err)) return false;
+        if (!sm_mapfile::open_checked(mf.path, who, mf.h, err, false, accept)) {
+            if (accept == sm_mapfile::PLAIN_ONLY && sm_mapfile::looks_packed(mf.path)) {
+                set.packed_refused = true;
+                err = sm_mapfile::said(who, mf.path, " is a packed map file, which is never rewritten; sm_unpack_maps makes a plain one");
+            }
+            return false;
+        }
         headers[i] = mf.h;
         set.read++;
     }

@@ -7,7 +7,9 @@
 // context's stream waits for the copy; the caller then launches its kernels on d_rec[q] and says done(q).  fold(q) waits for them
 // and adds the buffer's event times to the caller's tally.  The host reads chunk c while chunk c - 1 is on the device: next()
 // waits only for chunk c - 2, the last user of its buffer, and that one wait frees both sides (the copy out of h_rec[q] and the
-// kernels that read d_rec[q] precede the event).
+// kernels that read d_rec[q] precede the event).  A chunk of a PACKED file (sm_mapfile.h) takes the same way with fewer bytes: the
+// directory slice of its blocks and their payload are read (h_dir[q], h_rec[q]) and copied (d_dir[q], d_pk[q]), and the context's
+// stream decodes them into d_rec[q] before the start of the caller's kernels is marked; the decode's time counts as copy_ms.
 #pragma once
 
 #include "sm_ctx.h"
@@ -42,6 +44,8 @@ public:
     }
     // a pass over `jobs` begins (nothing of an earlier pass is in flight: it ended with fold() of both buffers)
     void begin(const std::vector<sm_mapfile::Job> &jobs) { jobs_ = &jobs; c_ = 0; in_.reset(); in_file_ = NO_FILE; }
+    // of the copy_ms folded so far: the decode of packed chunks
+    float unpack_ms() const { return unpack_ms_; }
     bool more() const { return c_ < jobs_->size(); }
 
     // the next chunk: read, on its way to the device, the context's stream waiting for it, the start of its kernels marked
@@ -51,20 +55,47 @@ public:
         const int q = (int)(c_ & 1u);
         if (int rc = fold(q)) return rc;                 // buffer q is free on both sides
         if (in_file_ != j.file) {
-            sm_mapfile::Header h;
-            in_ = sm_mapfile::open_checked(paths_[j.file], who_, h, g_err);
+            in_ = sm_mapfile::open_checked(paths_[j.file], who_, in_h_, g_err, false, sm_mapfile::PACKED_OK);
             in_file_ = j.file;
             if (!in_) return SM_E_ARG;
         }
+        const sm_mapfile::Header &h = in_h_;
+        // a packed file: the job's blocks (jobs begin at multiples of the chunk, so at a block) and their bytes in the payload
+        const size_t b0 = j.first / sm_mapfile::PACK_BLOCK, nblk = ((size_t)j.n + sm_mapfile::PACK_BLOCK - 1) / sm_mapfile::PACK_BLOCK;
+        uint64_t at = 0, bytes = 0;
+        if (h.packed) {
+            if ((uint64_t)j.first + j.n > h.count || j.first % sm_mapfile::PACK_BLOCK) { g_err = sm_mapfile::said(who_, paths_[j.file], " read err!! (changed while it was read)"); return SM_E_ARG; }
+            if (int rc = maps_ensure_packed(s_)) return rc;
+            const sm_mapfile::PackDir &last = h.dir[b0 + nblk - 1];
+            at = h.dir[b0].offset;
+            bytes = last.offset + sm_mapfile::pack_block_bytes(last.flags, j.n - (uint32_t)(nblk - 1) * sm_mapfile::PACK_BLOCK) - at;
+            if (bytes > (uint64_t)MapStaging::CHUNK * sm_mapfile::RECORD_BYTES) { g_err = sm_mapfile::said(who_, paths_[j.file], " read err!!"); return SM_E_ARG; }
+        }
         const double t0 = sm_mapfile::now_ms();
-        const bool got = sm_mapfile::read_rows(in_.get(), st_.h_rec[q].get(), j.n);
+        bool got;
+        if (h.packed) {
+            memcpy(st_.h_dir[q].get(), h.dir.data() + b0, nblk * sm_mapfile::PACK_DIR_BYTES);
+            got = fseeko(in_.get(), (off_t)(h.payload_at() + at), SEEK_SET) == 0 && (bytes == 0 || fread(st_.h_rec[q].get(), 1, bytes, in_.get()) == bytes);
+        } else
+            got = sm_mapfile::read_rows(in_.get(), st_.h_rec[q].get(), j.n);
         *t_.read_ms += (float)(sm_mapfile::now_ms() - t0);
         if (!got) { g_err = sm_mapfile::said(who_, paths_[j.file], " read err!!"); return SM_E_ARG; }
         in_flight_[q] = true;
+        packed_[q] = h.packed;
         HIPCK(hipEventRecord(st_.ev_copy0[q], st_.copy));
-        HIPCK(hipMemcpyAsync(st_.d_rec[q], st_.h_rec[q], (size_t)j.n * sm_mapfile::RECORD_BYTES, hipMemcpyHostToDevice, st_.copy));
+        if (h.packed) {
+            HIPCK(hipMemcpyAsync(st_.d_dir[q], st_.h_dir[q], nblk * sm_mapfile::PACK_DIR_BYTES, hipMemcpyHostToDevice, st_.copy));
+            HIPCK(hipMemcpyAsync(st_.d_pk[q], st_.h_rec[q], bytes, hipMemcpyHostToDevice, st_.copy));
+        } else
+            HIPCK(hipMemcpyAsync(st_.d_rec[q], st_.h_rec[q], (size_t)j.n * sm_mapfile::RECORD_BYTES, hipMemcpyHostToDevice, st_.copy));
         HIPCK(hipEventRecord(st_.ev_copied[q], st_.copy));
         HIPCK(hipStreamWaitEvent(s_->stream, st_.ev_copied[q], 0));
+        if (h.packed) {
+            HIPCK(hipEventRecord(st_.ev_u0[q], s_->stream));
+            maps_unpack(s_, st_.d_dir[q], st_.d_pk[q], j.n, h.pos_step_log2, st_.d_rec[q]);
+            HIPCK(hipGetLastError());
+            HIPCK(hipEventRecord(st_.ev_u1[q], s_->stream));
+        }
         HIPCK(hipEventRecord(st_.ev_k0[q], s_->stream));
         ck = {q, &j, st_.d_rec[q].get()};
         ++c_;
@@ -84,6 +115,11 @@ public:
         HIPCK(hipEventSynchronize(st_.ev_k1[q]));
         HIPCK(hipEventElapsedTime(&ms, st_.ev_copy0[q], st_.ev_copied[q]));
         *t_.copy_ms += ms;
+        if (packed_[q]) {
+            HIPCK(hipEventElapsedTime(&ms, st_.ev_u0[q], st_.ev_u1[q]));
+            *t_.copy_ms += ms;
+            unpack_ms_ += ms;
+        }
         HIPCK(hipEventElapsedTime(&ms, st_.ev_k0[q], st_.ev_k1[q]));
         *t_.device_ms += ms;
         in_flight_[q] = false;
@@ -100,6 +136,9 @@ private:
     const std::vector<sm_mapfile::Job> *jobs_ = nullptr;
     size_t c_ = 0;                     // chunks handed out in this pass
     sm_mapfile::File in_;              // the file being read
+    sm_mapfile::Header in_h_;          // ... and its header (a packed file's directory)
+    bool packed_[2] = {false, false};  // the chunk in the buffer came from a packed file
+    float unpack_ms_ = 0.0f;
     uint32_t in_file_ = NO_FILE;
     bool in_flight_[2] = {false, false};   // the buffer's events have been recorded and not yet folded
 };

@@ -109,8 +109,9 @@ int recall(sm_ctx *s, const sm_map_source *src, const float *pose16, const sm_re
     sm_mapset::RewriteSet set;
     std::vector<MapFile> &files = set.files;
     if (!sm_mapset::open_rewrite_set(src->paths, src->n_paths, CHUNK, s->index, known_far,
-                                     [&](const sm_mapset::FileIndex::Entry &en) { return box_out_of_reach(en, c3, ra.r2); }, who, set, g_err))
-        return SM_E_ARG;
+                                     [&](const sm_mapset::FileIndex::Entry &en) { return box_out_of_reach(en, c3, ra.r2); }, who, set, g_err,
+                                     mode == SM_RECALL_MOVE ? sm_mapfile::PLAIN_ONLY : sm_mapfile::PACKED_OK))
+        return set.packed_refused ? SM_E_UNSUPPORTED : SM_E_ARG;
     sm_recall_stats_t st{};
     st.files_listed = set.listed; st.files_skipped = set.skipped; st.files_read = set.read;
 

@@ -116,7 +116,8 @@ int sm_impl::scene_check(const sm_scene *scene, uint32_t n_views, const char *fn
         while (f < plan.files.size() && plan.files[f].path != path) ++f;
         if (f == plan.files.size()) {
             sm_mapfile::Header h;
-            if (!sm_mapfile::open_checked(path, fn, h, g_err)) return SM_E_ARG;
+            // (an actor file is resident as it lies in the file: a packed one is refused by name)
+            if (!sm_mapfile::open_checked(path, fn, h, g_err)) return sm_mapfile::looks_packed(path) ? SM_E_UNSUPPORTED : SM_E_ARG;
             plan.files.push_back({path, h.count, (uint32_t)plan.resident, (uint32_t)plan.rows});
             plan.resident += h.count;
             plan.rows += ((uint64_t)h.count + MAPS_BLOCK - 1) / MAPS_BLOCK * MAPS_BLOCK;

@@ -134,7 +134,7 @@ int warp(sm_ctx *s, const sm_map_source *src, int32_t t0, uint32_t n, const floa
     std::vector<MapFile> &files = set.files;
     if (!sm_mapset::open_rewrite_set(src->paths, src->n_paths, CHUNK, s->index, -1,
                                      [&](const sm_mapset::FileIndex::Entry &en) { return en.max_time < wa.t0; }, who, set, g_err))
-        return SM_E_ARG;
+        return set.packed_refused ? SM_E_UNSUPPORTED : SM_E_ARG;
     sm_warp_stats_t st{};
     st.files_listed = set.listed; st.files_skipped = set.skipped; st.files_read = set.read;
     w.stats = st;

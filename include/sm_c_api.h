@@ -2086,6 +2086,123 @@ int sm_pack_maps(sm_ctx *s, const sm_map_source *src, const sm_pack_params *p, c
 int sm_unpack_maps(sm_ctx *s, const sm_map_source *src, const char *out_prefix);
 int sm_pack_stats(sm_ctx *s, sm_pack_stats_t *out);
 
+/* ---- locating one map set in another without a guess (DESIGN.md "4ab. Locating") ----
+ * sm_register_maps needs a guess inside its basin (0.8 m, a few degrees).  sm_locate_maps finds that guess for two sets whose
+ * worlds share their up axis and differ by ANY yaw, by offsets of up to thousands of cells and by a height: the vertical structure
+ * of both sets is rasterised top-down (as sm_ground_maps rasterises), the SOURCE's occupied cells are correlated with the TARGET's
+ * occupancy over every yaw of a table and every offset of a range, and the ground heights give the fourth unknown.  The result is
+ * defined as an exact argmax of integer counts; tests/locate_ref.py restates every operation below and the GPU path is pinned to it
+ * bit for bit.  pose16_out (column-major, source world -> target world) is meant to be passed as guess16 to sm_register_maps.
+ *   Units and axes.  Q(mm) = (mm * 65536 + 500) / 1000 in integers, C = Q(cell_mm) (cell_mm 50..4000: C <= 2^18).  a = up >> 1 is the
+ *     up axis, sgn = up & 1 ? -1 : +1, ua < va are the two horizontal axes.
+ *   Record quantities.  sm_ground_maps' regular-record test, X[k] = floor(((double)p[k] - (double)o[k]) * 65536), ni[k], class c; cu =
+ *     floor_div(X[ua], C), cv = floor_div(X[va], C), H = sgn * X[a]; o = origin for the target set, source_origin for the source set.
+ *     A record that fails the test is LOOSE.  OUTSIDE: |H| >= 2^30; in the target cu outside [0, nu) or cv outside [0, nv); in the
+ *     source |cu| > 4095 or |cv| > 4095.
+ *   Kinds.  Structure-like: c has its bit in structure_mask and |ni[a]| <= max_up.  Ground-like: c has its bit in ground_mask and
+ *     normal_sign * sgn * ni[a] >= min_up.  A record may be both (it then takes part in both rasters) or neither.  It is counted
+ *     once: STRUCTURE if structure-like, else GROUND if ground-like, else OTHER.
+ *   Target raster, over the window of nu x nv cells (each 1..4096) whose low corner is origin: n_t[cell] = the cell's structure-like
+ *     records; occ0 = n_t >= min_records; occ = occ0 dilated by `dilate` cells (0..2, Chebyshev), clipped to the window; Zt[cell] =
+ *     the minimum H of the cell's ground-like records.
+ *   Source cells.  S = the cells with at least min_records structure-like records, in (cv, cu) order, n_s = |S|; more than
+ *     max_source_cells: SM_E_CAPACITY.  G = the cells with a ground-like record, each with Zs = the minimum H.
+ *   Rotation table.  n_fine = n_yaw * refine rows (n_yaw 1..1024, refine 1..16); row j = (c_j, s_j) = (llrint(cos(2 pi j / n_fine) *
+ *     2^30), llrint(sin(2 pi j / n_fine) * 2^30)), computed on the host in double.  sm_locate_rotations returns the 2 * n_fine
+ *     integers (c_0, s_0, c_1, ...).  Everything below uses the table's integers only.
+ *   Rotated cell.  x = cu * C + C / 2, y = cv * C + C / 2; xr = (c * x - s * y + 2^29) >> 30, yr = (s * x + c * y + 2^29) >> 30 in
+ *     int64 with arithmetic shifts (every product is below 2^61); ru = floor_div(xr, C), rv = floor_div(yr, C).
+ *   score(j, du, dv) = the number of cells of S with (ru + du, rv + dv) inside the window and occ set there.
+ *   Range.  R = (3 * max over S of max(|x|, |y|) / 2) / C + 2; du in [-R, nu - 1 + R], dv in [-R, nv - 1 + R].
+ *   Coarse winner (k*, du*, dv*).  Over the rows j = k * refine, k in 0 .. n_yaw - 1, and every offset of the range: the largest score,
+ *     of equal ones the smallest (k, dv, du).
+ *   Refinement.  Over dj in -(refine - 1) .. refine - 1 with j = (k* * refine + dj) mod n_fine, and the nine offsets within one cell
+ *     of (du*, dv*) (not cut to the range): the largest score, of equal ones the smallest (|dj|, dj, dv, du): (row, du, dv, score).
+ *   Runner-up.  The largest coarse score over the candidates with circular |k - k*| > sep_yaw or max(|du - du*|, |dv - dv*|) >
+ *     sep_cells; 0 without any.  sep_cells < 0: not searched, 0.
+ *   Height.  The pairs are the cells of G whose rotated cell (row `row`) plus (du, dv) is a window cell with a Zt; d = Zt - Zs per
+ *     pair, height_pairs = m = their number, dh = element (m - 1) / 2 of the sorted d; dh = 0 with m < min_ground.
+ *   Status, the first that applies: SM_LOCATE_NO_TARGET (no occ cell), SM_LOCATE_NO_SOURCE (n_s = 0) -- for these two nothing is
+ *     searched and every result field from `row` to `dh` is 0 --, SM_LOCATE_NONE (score * 256 < n_s * min_overlap_256),
+ *     SM_LOCATE_AMBIGUOUS (runner_up * 256 > coarse_score * ambiguity_256), SM_LOCATE_OK.
+ *   Pose.  For OK and AMBIGUOUS, in double, each entry rounded to float once: c = c_row * 2^-30, s = s_row * 2^-30, Cm = C * 2^-16,
+ *     O = (double)origin, So = (double)source_origin; M[ua][ua] = c, M[ua][va] = -s, M[va][ua] = s, M[va][va] = c, M[a][a] = 1,
+ *     M[ua][3] = (O[ua] + du * Cm) - (c * So[ua] - s * So[va]), M[va][3] = (O[va] + dv * Cm) - (s * So[ua] + c * So[va]), M[a][3] = (O[a] +
+ *     sgn * dh * 2^-16) - So[a]: a point p of the source world goes to O + Rot(p - So) + (du Cm, dv Cm, sgn dh 2^-16).  Otherwise
+ *     pose16_out is the identity; the call returns SM_OK for every status.
+ *   Worked example (tests/locate_ref.py EXAMPLE): cell_mm 1000, up 3, 6 x 4 cells at the origin, min_records 1, dilate 0, n_yaw 4,
+ *     refine 8, sep_yaw 0, sep_cells 1, min_ground 1.  Target occ at (1, 1), (2, 1), (4, 1), (5, 1); S = (0, 0), (1, 0).  k = 0 scores 2 at
+ *     (du, dv) = (1, 1) and (4, 1), k = 2 scores 2 at (3, 2) and (6, 2), k = 1, 3 score 1: the coarse winner is (0, 1, 1), the smallest
+ *     (k, dv, du).  dj = -1, 0, +1 all score 2 at (1, 1): dj = 0 stays, row 0.  The runner-up, (0, 1, 4), scores 2: 2 * 256 > 2 * 218,
+ *     AMBIGUOUS.  Ground at H -16384, -32768 under (1, 1), (2, 1) and -81920, -65536 under S: d = 65536, 32768, dh = 32768.
+ * The result is a function of the two multisets of (id, record) pairs alone: chunking, the split into files, plain or packed
+ *   files and the model's share change no bit.  The device finds the coarse winner and the runner-up by a branch and bound over a
+ *   max-pyramid of occ; SM_LOCATE_EXHAUSTIVE=1 (read per call) scores every coarse candidate instead -- the same result -- and is
+ *   refused with SM_E_ARG above 2^36 lookups (n_yaw * range * n_s).  max_nodes only limits the nodes scored per round.
+ * Side effects: none on files, model, tick, stored poses, keyframes or tracker state.  Synchronous.
+ * Errors.  SM_E_ARG: NULLs; a parameter out of its range; a non-finite origin or source_origin; the header and set checks of
+ *   sm_register_maps for both sets, a path that is in both; a call between sm_stage_conflict and sm_stage_cull; sm_locate_stats
+ *   before any call.  SM_E_CAPACITY: more than max_source_cells cells in S.  SM_E_UNSUPPORTED: a sharded or rig context. */
+enum { SM_LOCATE_OK = 0, SM_LOCATE_AMBIGUOUS = 1, SM_LOCATE_NONE = 2, SM_LOCATE_NO_TARGET = 3, SM_LOCATE_NO_SOURCE = 4 };
+enum { SM_LOCATE_STRUCTURE = 0, SM_LOCATE_GROUND = 1, SM_LOCATE_OTHER = 2, SM_LOCATE_OUTSIDE = 3, SM_LOCATE_LOOSE = 4 };
+typedef struct sm_locate_params {
+    int32_t  cell_mm;            /* 50..4000                                                         default 500 */
+    int32_t  up;                 /* 0..5: +x -x +y -y +z -z is up                                    default 3 */
+    float    origin[3];          /* the target window's low corner, height zero on the up axis       default 0 0 0 */
+    float    source_origin[3];   /* the point of the source world its cells are counted from         default 0 0 0 */
+    int32_t  nu, nv;             /* the window's cells, 1..4096 each                                 default 256 256 */
+    uint32_t structure_mask[8];  /* classes that may be structure                                    default all */
+    int32_t  max_up;             /* 0..16384: |ni[a]| of a structure-like record at most             default 8192 (30 degrees) */
+    uint32_t ground_mask[8];     /* classes that may be ground                                       default all */
+    int32_t  min_up;             /* 0..16384, as sm_ground_params'                                   default 11585 */
+    int32_t  normal_sign;        /* +1 / -1, as sm_ground_params'                                    default -1 */
+    uint32_t min_records;        /* >= 1: structure-like records that make a cell occupied           default 2 */
+    int32_t  dilate;             /* 0..2 cells                                                       default 1 */
+    int32_t  n_yaw;              /* 1..1024 coarse rows                                              default 360 */
+    int32_t  refine;             /* 1..16 fine rows per coarse row                                   default 8 */
+    int32_t  sep_yaw;            /* >= 0: coarse rows the runner-up keeps away                       default 10 */
+    int32_t  sep_cells;          /* cells the runner-up keeps away; < 0: no runner-up                default 8 */
+    int32_t  min_ground;         /* >= 0: pairs the height needs                                     default 16 */
+    int32_t  min_overlap_256;    /* 0..256                                                           default 128 */
+    int32_t  ambiguity_256;      /* 0..65536                                                         default 218 */
+    uint32_t max_source_cells;   /* 1..2^20                                                          default 2^18 */
+    uint32_t max_nodes;          /* 4..2^24: nodes scored per round of the search                    default 2^20 */
+} sm_locate_params;
+typedef struct sm_locate_info {
+    int32_t  status;             /* SM_LOCATE_* */
+    int32_t  row, du, dv;        /* the refined winner: fine row, offsets in cells */
+    uint32_t score;
+    int32_t  coarse_k, coarse_du, coarse_dv;
+    uint32_t coarse_score;
+    uint32_t runner_up;
+    uint32_t n_s;                /* cells of S */
+    uint32_t target_cells;       /* occ cells */
+    uint32_t height_pairs;
+    int32_t  dh;                 /* 2^-16 m */
+    uint64_t source_counts[5];   /* records by SM_LOCATE_STRUCTURE .. SM_LOCATE_LOOSE */
+    uint64_t target_counts[5];
+} sm_locate_info;
+typedef struct sm_locate_stats_t {
+    uint64_t source_records, target_records;
+    uint64_t nodes;              /* inner nodes whose bound was computed (both searches) */
+    uint64_t leaves;             /* coarse candidates scored (both searches) */
+    uint32_t chunks, launches;
+    uint32_t rounds;             /* rounds of the two searches */
+    uint32_t levels;             /* pyramid levels above occ */
+    uint32_t exhaustive;         /* 1: SM_LOCATE_EXHAUSTIVE=1 */
+    uint32_t range;              /* R */
+    float read_ms;               /* host: reading the files */
+    float raster_ms;             /* device: both sets' rasters, the compaction, the rotated lists */
+    float pyramid_ms;            /* device: occ, dilation, the pyramid */
+    float search_ms;             /* host clock: both searches, refinement and height */
+    float total_ms;
+} sm_locate_stats_t;
+int sm_default_locate_params(sm_locate_params *p);           /* pure, no context */
+int sm_locate_rotations(const sm_locate_params *p, int32_t *table);   /* pure: 2 * n_yaw * refine integers */
+int sm_locate_maps(sm_ctx *s, const sm_map_source *source, const sm_map_source *target, const sm_locate_params *p,
+                   float *pose16_out, sm_locate_info *info);
+int sm_locate_stats(sm_ctx *s, sm_locate_stats_t *out);      /* SM_E_ARG before the first call */
+
 /* ---- per-pass entry points (GlobalModel / IndexMap methods), synchronous ---- */
 /* Upload RGB / metric depth / semantic textures directly (bypasses p0). */
 int sm_set_frame(sm_ctx *s, const uint8_t *rgb, const float *depth_metric,

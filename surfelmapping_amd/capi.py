@@ -417,6 +417,31 @@ class SmGroundStats(C.Structure):
                 ("total_ms", C.c_float)]
 
 
+LOCATE_STATUS = ("OK", "AMBIGUOUS", "NONE", "NO_TARGET", "NO_SOURCE")         # SM_LOCATE_*: sm_locate_info.status
+LOCATE_KINDS = ("STRUCTURE", "GROUND", "OTHER", "OUTSIDE", "LOOSE")           # the entries of its source_counts / target_counts
+
+
+class SmLocateParams(C.Structure):
+    _fields_ = [("cell_mm", C.c_int32), ("up", C.c_int32), ("origin", C.c_float * 3), ("source_origin", C.c_float * 3), ("nu", C.c_int32),
+                ("nv", C.c_int32), ("structure_mask", C.c_uint32 * 8), ("max_up", C.c_int32), ("ground_mask", C.c_uint32 * 8), ("min_up", C.c_int32),
+                ("normal_sign", C.c_int32), ("min_records", C.c_uint32), ("dilate", C.c_int32), ("n_yaw", C.c_int32), ("refine", C.c_int32),
+                ("sep_yaw", C.c_int32), ("sep_cells", C.c_int32), ("min_ground", C.c_int32), ("min_overlap_256", C.c_int32),
+                ("ambiguity_256", C.c_int32), ("max_source_cells", C.c_uint32), ("max_nodes", C.c_uint32)]
+
+
+class SmLocateInfo(C.Structure):
+    _fields_ = [("status", C.c_int32), ("row", C.c_int32), ("du", C.c_int32), ("dv", C.c_int32), ("score", C.c_uint32), ("coarse_k", C.c_int32),
+                ("coarse_du", C.c_int32), ("coarse_dv", C.c_int32), ("coarse_score", C.c_uint32), ("runner_up", C.c_uint32), ("n_s", C.c_uint32),
+                ("target_cells", C.c_uint32), ("height_pairs", C.c_uint32), ("dh", C.c_int32), ("source_counts", C.c_uint64 * 5),
+                ("target_counts", C.c_uint64 * 5)]
+
+
+class SmLocateStats(C.Structure):
+    _fields_ = [("source_records", C.c_uint64), ("target_records", C.c_uint64), ("nodes", C.c_uint64), ("leaves", C.c_uint64), ("chunks", C.c_uint32),
+                ("launches", C.c_uint32), ("rounds", C.c_uint32), ("levels", C.c_uint32), ("exhaustive", C.c_uint32), ("range", C.c_uint32),
+                ("read_ms", C.c_float), ("raster_ms", C.c_float), ("pyramid_ms", C.c_float), ("search_ms", C.c_float), ("total_ms", C.c_float)]
+
+
 SM_REGISTER_OK, SM_REGISTER_LOST, SM_REGISTER_DEGENERATE, SM_REGISTER_NO_TARGET, SM_REGISTER_NO_SOURCE = 0, 1, 2, 3, 4
 REGISTER_STATUS = {SM_REGISTER_OK: "OK", SM_REGISTER_LOST: "LOST", SM_REGISTER_DEGENERATE: "DEGENERATE",
                    SM_REGISTER_NO_TARGET: "NO_TARGET", SM_REGISTER_NO_SOURCE: "NO_SOURCE"}
@@ -638,6 +663,10 @@ PROTOTYPES = {
     "sm_default_ground_params": (ci, [P(SmGroundParams)]),
     "sm_ground_maps": (ci, [vp, _SRC, P(SmGroundParams)] + [vp] * 6 + [P(SmGroundInfo)]),
     "sm_ground_stats": (ci, [vp, P(SmGroundStats)]),
+    "sm_default_locate_params": (ci, [P(SmLocateParams)]),
+    "sm_locate_rotations": (ci, [P(SmLocateParams), vp]),
+    "sm_locate_maps": (ci, [vp, _SRC, _SRC, P(SmLocateParams), vp, P(SmLocateInfo)]),
+    "sm_locate_stats": (ci, [vp, P(SmLocateStats)]),
     "sm_render_image_scene": (ci, [vp, _SRC, _SCENE, vp, u32] + _VIEW + [_FILL, vp, vp, vp]),
     "sm_lidar_sweep_scene": (ci, [vp, _SRC, _SCENE, _SENSOR, vp, u32, vp, vp, vp, vp]),
     "sm_scene_place_rows": (ci, [vp, vp, u32, vp]),
@@ -849,6 +878,8 @@ _SPECIAL = {
     SmSegmentParams: {"origin": _whole(float), "class_mask": _whole(int), "classes": _classes("class_mask")},
     SmMeshParams: {"origin": _whole(float), "class_mask": _whole(int), "classes": _classes("class_mask")},
     SmGroundParams: {"origin": _whole(float), "ground_mask": _whole(int), "classes": _classes("ground_mask")},
+    SmLocateParams: {"origin": _whole(float), "source_origin": _whole(float), "structure_mask": _whole(int), "ground_mask": _whole(int),
+                     "structure_classes": _classes("structure_mask"), "ground_classes": _classes("ground_mask")},
     # the fields of sm_loop_params by their own names; `loop` itself is no key
     SmAutoLoopParams: {**{n: _inner("loop") for n, _ in SmLoopParams._fields_}, "loop": _refused},
 }
@@ -1046,6 +1077,22 @@ def default_ground_params() -> SmGroundParams:
     band_mm 200, the body band 150..2000 mm, min_obstacle 2, fill_cells 3, step_mm 150, reach_cells 32, unknown_blocks 0, normal_sign -1
     (normals that point into the surface, as the fusion stores them)"""
     return ground_params()
+
+
+def locate_params(**over) -> SmLocateParams:
+    """sm_default_locate_params with fields overridden; origin and source_origin take a sequence of three, structure_mask and
+    ground_mask eight words (`structure_classes=` / `ground_classes=` take an iterable of classes instead)"""
+    return _params(SmLocateParams, "sm_default_locate_params", None, over)
+
+
+def locate_rotations(**over) -> np.ndarray:
+    """sm_locate_rotations: int32[n_yaw * refine, 2], row j = (c_j, s_j) in 2^-30 -- the table sm_locate_maps rotates cells with"""
+    p = locate_params(**over)
+    t = np.zeros((max(int(p.n_yaw), 0) * max(int(p.refine), 0), 2), np.int32)
+    rc = load().sm_locate_rotations(C.byref(p), _ptr(t))
+    if rc:
+        raise SurfelMapError("sm_locate_rotations", rc, load().sm_last_error().decode())
+    return t
 
 
 def ground_params(**over) -> SmGroundParams:
@@ -2561,6 +2608,30 @@ class SurfelMap:
     def mesh_stats(self) -> dict:
         """of the last mesh_maps: chunks, launches, read_ms, table_ms, field_ms, sort_ms, emit_ms, write_ms, total_ms"""
         return self._stats(SmMeshStats, "sm_mesh_stats")
+
+    # -- one map set located in another without a guess (sm_locate_maps)
+    def locate_maps(self, source_paths, target_paths, source_model=False, target_model=False, **params) -> dict:
+        """Where the map set `source_paths` (then, with source_model, the live model) lies in the world of the set `target_paths`
+        (target_model likewise), without a guess: any yaw about the shared up axis, offsets of thousands of cells, a height
+        (sm_locate_maps; tests/locate_ref.py restates it).  params: the fields of locate_params() -- the target window (origin, nu,
+        nv, cell_mm) should hold the target's structure, source_origin lie near the source's middle.  Nothing is changed.  Returns
+        dict(pose: 4x4 float32 source world -> target world, the identity unless status is "OK" or "AMBIGUOUS" -- pass it as `guess`
+        to register_maps --, info: status (name), status_code, row, yaw_deg, du, dv, score, coarse_k, coarse_du, coarse_dv,
+        coarse_score, runner_up, n_s, target_cells, height_pairs, dh, source_counts, target_counts (by LOCATE_KINDS))."""
+        p = locate_params(**params)
+        src, tgt = map_source(source_paths, include_model=source_model), map_source(target_paths, include_model=target_model)
+        out = np.zeros(16, np.float32)
+        info = SmLocateInfo()
+        self._chk(self._L.sm_locate_maps(self._h, C.byref(src), C.byref(tgt), C.byref(p), _ptr(out), C.byref(info)), "sm_locate_maps")
+        d = {n: int(getattr(info, n)) for n, _ in SmLocateInfo._fields_ if not n.endswith("_counts")}
+        d.update(status=LOCATE_STATUS[info.status], status_code=int(info.status), yaw_deg=360.0 * info.row / (p.n_yaw * p.refine),
+                 source_counts=[int(v) for v in info.source_counts], target_counts=[int(v) for v in info.target_counts])
+        return dict(pose=out.reshape(4, 4).T.copy(), info=d)
+
+    def locate_stats(self) -> dict:
+        """of the last locate_maps: source_records, target_records, nodes, leaves, chunks, launches, rounds, levels, exhaustive,
+        range, read_ms, raster_ms, pyramid_ms, search_ms, total_ms"""
+        return self._stats(SmLocateStats, "sm_locate_stats")
 
     # -- a map set as a planner's ground map (sm_ground_maps)
     def ground_maps(self, paths, include_model=False, planes=GROUND_PLANES, **params) -> dict:

@@ -376,6 +376,32 @@ public:
         if (info) *info = got;
         return got.status;
     }
+    // Where does the map set `sourceFiles` lie in the world of the set `targetFiles`, without a guess (sm_locate_maps; DESIGN.md
+    // "4ab. Locating"): any yaw about the shared up axis, offsets of thousands of cells, a height.  params (null: the defaults)
+    // should place the target window around the target's structure and source_origin near the source's middle.  pose: source
+    // world -> target world, to be given to registerMaps as its guess; the identity unless the status is SM_LOCATE_OK or
+    // SM_LOCATE_AMBIGUOUS.  Nothing is changed.  Returns the status (SM_LOCATE_*), or -1 with the error printed.
+    int locateMaps(const std::vector<std::string> &sourceFiles, const std::vector<std::string> &targetFiles, Eigen::Matrix4f &pose,
+                   const sm_locate_params *params = nullptr, sm_locate_info *info = nullptr)
+    {
+        std::vector<const char *> sp, tp;
+        for (const std::string &f : sourceFiles) sp.push_back(f.c_str());
+        for (const std::string &f : targetFiles) tp.push_back(f.c_str());
+        const sm_map_source src{sp.data(), (uint32_t)sp.size(), 0}, tgt{tp.data(), (uint32_t)tp.size(), 0};
+        sm_locate_params p;
+        sm_default_locate_params(&p);
+        if (params) p = *params;
+        sm_locate_info got;
+        float out[16];
+        (void)sm_sync(ctx_);                                             // (SM_FACADE_ASYNC: frames may still be in flight)
+        if (sm_locate_maps(ctx_, &src, &tgt, &p, out, &got) != SM_OK) {
+            std::printf("locateMaps: %s\n", sm_last_error());
+            return -1;
+        }
+        std::memcpy(pose.data(), out, 64);
+        if (info) *info = got;
+        return got.status;
+    }
     // registerMaps, and on SM_REGISTER_OK the source files moved into the target's world (sm_warp_by_time with t0 = 0 and one
     // row, the pose): the two sets can then be viewed, swept or simplified as one.  A file none of whose records moves is left
     // alone; the live model stays.  Returns as registerMaps; -1 as well if the warp fails (the error is printed).

@@ -23,7 +23,8 @@
 //   sm_simplify.hip  simplification (sm_simplify, sm_simplify_maps): the model or a map set merged per voxel cell, two passes over the records
 //   sm_register.hip  registration (sm_register_*): the rigid transform from one map set to another, voxel-cell ICP, one pass over each set
 //   sm_compare.hip   change detection (sm_compare_*): every record of one map set labelled against the voxel tables of another, one pass over each set
-//   sm_voxel.hip     what those three share (sm_voxel.h): the grid, the slot count and the tally's verdict; the lookup table; the ranked output
+//   sm_locate.hip    locating (sm_locate_*): where one map set lies in another without a guess, top-down occupancy correlated by branch and bound
+//   sm_voxel.hip     what simplification, registration and change detection share (sm_voxel.h): the grid, the slot count and the tally's verdict; the lookup table; the ranked output
 //   sm_pack.hip      packed map files (sm_pack_maps, sm_unpack_maps): the encoder, and the decoder the chunk stream runs on a packed file's chunks
 // and, beside it, for everything that touches a map file: sm_mapfile.h (the format: checked open, writer, chunk plan; host only),
 // sm_map_set.h (a listed set of files: the file index, the two openings, a rewrite's per-file record and temporary; host only) and
@@ -466,6 +467,17 @@ struct Ground {
     bool stats_valid = false;
 };
 
+// locating one map set in another (sm_locate.hip, sm_k_locate.h): the tally, its pinned mirror, the events and the last call's
+// stats, the pinned buffer of a round.  The rasters, the pyramid and the search's device buffers live for one call.
+struct Locate {
+    // the counts by record kind of both sets, the occupied cells.  Events around: the memsets, the target's model, the source's model
+    // and the compaction, occ and the pyramid
+    CallScratch<8> scratch;
+    Host<uint8_t> h_round;             // pinned: a round's nodes on their way in, its bounds or best candidates on their way out
+    sm_locate_stats_t stats{};
+    bool stats_valid = false;
+};
+
 // ray casts (sm_rays.hip, sm_k_rays.h): the last call's stats.  The index, the rays and the planes live for one call.
 struct Rays {
     sm_rays_stats_t stats{};
@@ -754,6 +766,7 @@ struct sm_ctx {
     Segment seg;
     Mesh mesh;
     Ground ground;
+    Locate locate;
     Rays rays;
     Scene scene;
     Points points;

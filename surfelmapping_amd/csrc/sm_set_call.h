@@ -1,5 +1,5 @@
 // sm_set_call.h -- private to sm_simplify.hip, sm_register.hip, sm_compare.hip, sm_tile.hip, sm_segment.hip, sm_mesh.hip,
-// sm_ground.hip, sm_rays.hip and sm_points.hip: the frame of a call that reads a whole map set and computes something from it (DESIGN.md "4w. The frame of a
+// sm_ground.hip, sm_locate.hip, sm_rays.hip and sm_points.hip: the frame of a call that reads a whole map set and computes something from it (DESIGN.md "4w. The frame of a
 // map-set call").  The opening of a call on one set (SetCall) and the live model's export; the scratch a call keeps on its context
 // (CallScratch, LabelPair: sm_ctx.h holds them, their members are defined here); the drain of device rows to the host in pieces;
 // the collect of a labelled pass; the stats getter.  What lies between a call's opening and its commit is the call's own.

@@ -1,8 +1,10 @@
-"""What the seven map-set analysis calls (sm_simplify_maps, sm_register_maps, sm_compare_maps, sm_tile_maps, sm_segment_maps,
-sm_mesh_maps, sm_ground_maps) do alike around their kernels ("The frame of a map-set call"): a context's scratch made
-whole by a first call that fails, the tally cleared per call, when the stats become valid, the output's own path, the live model in
-or out of the set.  What the calls compute is their own tests' business; here one call is held against another call of the same
-library, so the file passes unchanged on the library before the frame and on the one after it (SM_HIP_LIB selects a build)."""
+"""What the map-set analysis calls do alike around their kernels ("The frame of a map-set call"): a context's scratch
+made whole by a first call that fails, the tally cleared per call, when the stats become valid, the output's own path, the live model
+in or out of the set.  sm_set_call.h has ten users; seven are run here (sm_simplify_maps, sm_register_maps, sm_compare_maps,
+sm_tile_maps, sm_segment_maps, sm_mesh_maps, sm_ground_maps), each on a context of its own; sm_locate_maps, sm_cast_rays_maps and
+sm_query_points_maps stand with them in tests/test_call_order.py, which runs every call after every other.  What the calls compute is
+their own tests' business; here one call is held against another call of the same library, so the file passes unchanged on the
+library before the frame and on the one after it (SM_HIP_LIB selects a build).  _run and _counts live in tests/call_probes.py."""
 import os
 
 import numpy as np
@@ -10,6 +12,7 @@ import pytest
 
 import recall_ref as cr
 import test_simplify as ts
+from call_probes import counts as _counts, run_analysis as _run
 
 pytestmark = pytest.mark.gpu
 
@@ -64,49 +67,8 @@ class Sets:
         ts._no_tmp(self.folder)
 
 
-def _plain(v):
-    return v.tobytes() if isinstance(v, np.ndarray) else v
-
-
-def _run(m, call, sets, include_model=True, out=None, **over):
-    """One call; (what it gave, everything as bytes or plain values: outputs, info, files written), the records it says it read"""
-    out = out or sets.out()
-    if call == "simplify":
-        st = m.simplify_maps(sets.paths, out, include_model=include_model, voxel_mm=ts.BITE_MM, **over)
-        return dict(file=open(out, "rb").read(), **{k: st[k] for k in ts.STAT_KEYS}), st["records_in"]
-    if call == "tile":
-        files = m.tile_maps(sets.paths, out, include_model=include_model, cell_mm=200, tile_shift=1, max_file_records=256, **over)
-        st = m.tile_stats()
-        got = {k: st[k] for k in ("records_in", "placed", "loose", "tiles", "largest_tile", "files_written")}
-        return dict(files=[open(f, "rb").read() for f in files], **got), st["records_in"]
-    if call == "register":
-        pose, info = m.register_maps(sets.paths, sets.other, source_model=include_model, voxel_mm=200, levels=2, min_inliers=10,
-                                     pivot=(0.0, 0.0, 10.0), **over)
-        return dict(pose=pose.tobytes(), **info), m.register_stats()["source_records"]
-    if call == "compare":
-        lab, info = m.compare_maps(sets.paths, sets.other, query_model=include_model, out_path=out, write_mask=15, **over)
-        return dict(labels=lab.tobytes(), file=open(out, "rb").read(), **{k: v for k, v in info.items() if k != "counts"}), info["query_records"]
-    if call == "segment":
-        got = m.segment_maps(sets.paths, include_model=include_model, out_path=out, voxel_mm=200, **over)
-        info = {k: v for k, v in got["info"].items() if k != "counts"}
-        return dict(labels=got["labels"].tobytes(), components=got["components"].tobytes(), file=open(out, "rb").read(), info=info), info["records"]
-    if call == "mesh":
-        got = m.mesh_maps(sets.paths, include_model=include_model, ply_path=out, voxel_mm=200, **over)
-        info = {k: v for k, v in got["info"].items() if k != "counts"}
-        return dict(vertices=got["vertices"].tobytes(), faces=got["faces"].tobytes(), file=open(out, "rb").read(), info=info), info["records"]
-    assert call == "ground"
-    got = m.ground_maps(sets.paths, include_model=include_model, **{**dict(cell_mm=100, origin=(-12.8, 0.0, 0.0)), **over})
-    info = {k: v for k, v in got.pop("info").items() if k not in ("counts", "cells")}
-    return dict({k: _plain(v) for k, v in got.items()}, info=info), info["records"]
-
-
 def _stats(m, call):
     return getattr(m, call + "_stats")()
-
-
-def _counts(st):
-    """the stats without the times"""
-    return {k: v for k, v in st.items() if not k.endswith("_ms")}
 
 
 def _refused(m, call, sets, **kw):

@@ -139,7 +139,13 @@ void sm_destroy(sm_ctx *s);
 
 /* SurfelMapping::processFrame (src/SurfelMapping.h:31-34, src/SurfelMapping.cpp:115-251).
  * rgb H*W*3 u8 (R first), depth_mm H*W u16 (0 invalid), semantic H*W u8, pose = column-major
- * 4x4 camera->world (Eigen::Matrix4f storage).  Inputs are borrowed for the call only. */
+ * 4x4 camera->world (Eigen::Matrix4f storage).  Inputs are borrowed for the call only.
+ * depth_mm and semantic may each be null: "keep what is in the texture" (src/SurfelMapping.cpp:122-128).  The context has ONE
+ * current depth image and ONE current class image, as the reference has one DEPTH_RAW and one SEMANTIC texture: an image given
+ * to ANY entry point -- sm_process_frame, sm_process_frame_async, sm_process_frame_device, sm_clean_points*, sm_set_frame (class
+ * only), sm_shard_frame, sm_shard_frame_device -- becomes current, and a null in any of them reads the current one, whichever
+ * call gave it.  Before the first one is given the images are zeros (no depth anywhere); sm_reset, sm_upload_model, sm_load_map
+ * and the trackers leave them alone. */
 int sm_process_frame(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm,
                      const uint8_t *semantic, const float *pose16);
 /* Same, inputs already resident in device memory of this ctx's GPU; enqueue only.  Without the depth filter chain the
@@ -148,7 +154,10 @@ int sm_process_frame(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm,
  * effect is that a caller who never calls anything again must call sm_sync to have the last frame finished.
  * SM_DEFER_ASSOC=0 turns this off.  (One bounded exception to "enqueue only": when the model
  * is within one frame of MAX_VERTICES and the host has run ahead of the device, the call waits up to SM_CAPACITY_WAIT_US
- * (default 2000) microseconds for the device's slot count before deciding whether this frame's cull must compact.) */
+ * (default 2000) microseconds for the device's slot count before deciding whether this frame's cull must compact.)
+ * A depth or class image given here becomes the current one IN THE CALLER'S BUFFER (no copy is made): if a later call to any
+ * entry point passes null for it, the buffer must stay allocated and unchanged until another depth (or class) image has been
+ * given or the context is destroyed.  A caller who never passes null may reuse the buffer as soon as the frame has run. */
 int sm_process_frame_device(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_depth_mm,
                             const uint8_t *d_semantic, const float *pose16);
 /* The same for callers whose images live in HOST memory and who do not want to wait (SurfelMapping::processFrame uploads its
@@ -2281,7 +2290,8 @@ int sm_shard_rccl_nranks(sm_ctx *s);
  * takes device pointers and only enqueues (sm_sync to wait).  A frame is a sequence of collectives every rank must enter: an
  * error return from one rank (a failed launch or a failed RCCL call -- nothing a frame's data can cause) leaves the others inside
  * a collective and the communicator undefined; treat it as fatal for the stream and destroy the contexts on all ranks.  (The
- * rig's exchanges, which do run fallible local steps between collectives, carry a status word instead: sm_rig_consolidate.) */
+ * rig's exchanges, which do run fallible local steps between collectives, carry a status word instead: sm_rig_consolidate.)
+ * Null images and the lifetime of the _device form's buffers: as at sm_process_frame / sm_process_frame_device. */
 int sm_shard_frame_device(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_depth_mm, const uint8_t *d_semantic, const float *pose16);
 int sm_shard_frame(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, const uint8_t *semantic, const float *pose16);
 /* squeeze the dead slots out now (collective; frames do it every compact_period-th time by themselves) */

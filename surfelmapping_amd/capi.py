@@ -1531,6 +1531,10 @@ class SurfelMap:
                          "sm_process_frame", allow)
 
     def process_frame_device(self, d_rgb, d_depth, d_sem, pose):
+        """process_frame() of images in this context's device memory, enqueued and not waited for (sm_process_frame_device).
+        d_depth / d_sem None (or 0): the current image stays, whichever call gave it.  One given here becomes the current image
+        in the caller's buffer, without a copy: if a later call passes None for it, the buffer must stay allocated and unchanged
+        until another depth (or class) image has been given or the context is closed."""
         pose = np.ascontiguousarray(pose, np.float32)
         return self._chk(self._L.sm_process_frame_device(self._h, d_rgb, d_depth, d_sem, _ptr(pose)),
                          "sm_process_frame_device")
@@ -2124,8 +2128,10 @@ class SurfelMap:
 
     def process_frame_stereo(self, rgb_left, rgb_right, sem, pose):
         """process_frame() with the depth estimated from the pair: the images are uploaded, sm_stereo_depth_device and
-        sm_process_frame_device are enqueued one after the other, and the depth never leaves the device.  sem None: the previous
-        class image stays.  The four device images it stages in are allocated by the first call and live as long as the context."""
+        sm_process_frame_device are enqueued one after the other, and the depth never leaves the device.  sem None: the current
+        class image stays, whichever call gave it.  The four device images it stages in are allocated by the first call and live
+        as long as the context, so the depth and the class image given here stay readable as the current ones for later calls
+        that pass None (a later stereo frame rewrites them in place, on the context's stream: after every frame enqueued so far)."""
         rgb_left, rgb_right = self._stereo_pair(rgb_left, rgb_right)
         if getattr(self, "_stereo_dev", None) is None:
             P = self.P
@@ -2180,9 +2186,10 @@ class SurfelMap:
 
     def process_frame_lidar(self, rgb, points, T, sem, pose):
         """process_frame() with the depth made from the scan: the image and the points are uploaded, sm_lidar_depth_device and
-        sm_process_frame_device are enqueued one after the other, and the depth never leaves the device.  sem None: the previous
-        class image stays.  The device buffers it stages in are allocated by the first call and live as long as the context; the
-        scan's grows by at least half when a scan has more points than it holds, and the one it replaces is freed."""
+        sm_process_frame_device are enqueued one after the other, and the depth never leaves the device.  sem None: the current
+        class image stays, whichever call gave it.  The device buffers it stages in are allocated by the first call and live as
+        long as the context, so the depth and the class image given here stay readable as the current ones for later calls that
+        pass None; the scan's grows by at least half when a scan has more points than it holds, and the one it replaces is freed."""
         rgb = np.ascontiguousarray(rgb, np.uint8)
         assert rgb.shape == (self.H, self.W, 3), rgb.shape
         points, _ = self._scan(points, T)

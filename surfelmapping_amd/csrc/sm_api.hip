@@ -724,10 +724,17 @@ int begin_frame(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_raw, const ui
     return 1;
 }
 
+// the plain frame forms on a sharded context: refused (before a form that does not wait takes the caller's images as current)
+int refuse_sharded(const sm_ctx *s)
+{
+    if (s->ss_on) { g_err = "context is configured for sharding: use the sm_shard_* entry points"; return SM_E_ARG; }
+    return SM_OK;
+}
+
 // SurfelMapping::processFrame body (src/SurfelMapping.cpp:130-251); enqueue only.
 int enqueue_frame(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_raw, const uint8_t *d_sem, const float *pose)
 {
-    if (s->ss_on) { g_err = "context is configured for sharding: use the sm_shard_* entry points"; return SM_E_ARG; }
+    if (int rc = refuse_sharded(s)) return rc;
     FrameParams fp;
     // the cull's kind is decided first: a frame whose cull only marks the dead lets k_prep evaluate the tile skip flags for
     // the one-pass surfel kernel
@@ -778,6 +785,30 @@ int enqueue_frame(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_raw, const 
     return SM_OK;
 }
 
+// ---- the current depth and class image (sm_ctx::cur_depth / cur_sem): one owner for every entry point ----
+// "this image was given, here": a non-null image becomes current; `slot` is the async input set that holds it, -1 for
+// d_depth_raw / d_sem and for a buffer of the caller's (borrowed: see sm_process_frame_device in the header)
+void image_given(sm_ctx *s, const uint16_t *d_depth, const uint8_t *d_sem, int slot)
+{
+    if (d_depth) { s->cur_depth = d_depth; s->in_depth_slot = slot; }
+    if (d_sem) { s->cur_sem = d_sem; s->in_sem_slot = slot; }
+}
+
+// "which image is current": what a null image reads (the zeroed staging planes until one has been given)
+const uint16_t *current_depth(const sm_ctx *s) { return s->cur_depth ? s->cur_depth : s->d_depth_raw.get(); }
+const uint8_t *current_sem(const sm_ctx *s) { return s->cur_sem ? s->cur_sem : s->d_sem.get(); }
+
+// A frame that was enqueued without waiting read the current images: an input set that holds one of them (other than the
+// frame's own, `own`) is busy until that frame has prepared too -- sm_process_frame_async waits for ev_free before it refills a set
+int hold_current_sets(sm_ctx *s, int own)
+{
+    for (int o : {s->in_depth_slot, s->in_sem_slot})
+        if (o >= 0 && o != own) { HIPCK(hipEventRecord(s->in[o].ev_free, s->stream)); s->in[o].used = true; }
+    return SM_OK;
+}
+
+// host images of a form that waits: into the staging planes, on the context's stream (so a frame enqueued earlier that reads
+// them as the current images has its preparation launch ahead of the copy), and current from here on
 int upload_inputs(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth, const uint8_t *sem)
 {
     const size_t P = (size_t)s->P;
@@ -785,6 +816,7 @@ int upload_inputs(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth, const ui
     if (rgb) HIPCK(hipMemcpyAsync(s->d_rgb, rgb, P * 3, hipMemcpyHostToDevice, st));
     if (depth) HIPCK(hipMemcpyAsync(s->d_depth_raw, depth, P * 2, hipMemcpyHostToDevice, st));
     if (sem) HIPCK(hipMemcpyAsync(s->d_sem, sem, P, hipMemcpyHostToDevice, st));
+    image_given(s, depth ? s->d_depth_raw.get() : nullptr, sem ? s->d_sem.get() : nullptr, -1);
     return SM_OK;
 }
 
@@ -1247,8 +1279,13 @@ int sm_process_frame_device(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_d
 {
     if (!s || !d_rgb || !pose16) { g_err = "sm_process_frame_device: null argument"; return SM_E_ARG; }
     HIPCK(hipSetDevice(s->cfg.device));
-    // a null depth / semantic keeps the previous texture (src/SurfelMapping.cpp:124-128)
-    const int rc = enqueue_frame(s, d_rgb, d_depth_mm ? d_depth_mm : s->d_depth_raw, d_semantic ? d_semantic : s->d_sem, pose16);
+    if (int rc = refuse_sharded(s)) return rc;
+    // a null depth / semantic keeps the previous texture (src/SurfelMapping.cpp:124-128); one given is current from here on,
+    // in the caller's buffer
+    image_given(s, d_depth_mm, d_semantic, -1);
+    int rc = enqueue_frame(s, d_rgb, current_depth(s), current_sem(s), pose16);
+    const int rh = hold_current_sets(s, -1);
+    if (!rc) rc = rh;
     return rc ? rc : auto_retire_after_frame(s);
 }
 
@@ -1258,7 +1295,7 @@ int sm_process_frame(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, co
     HIPCK(hipSetDevice(s->cfg.device));
     int rc = upload_inputs(s, rgb, depth_mm, semantic);
     if (rc) return rc;
-    rc = enqueue_frame(s, s->d_rgb, s->d_depth_raw, s->d_sem, pose16);
+    rc = enqueue_frame(s, s->d_rgb, current_depth(s), current_sem(s), pose16);     // (an input set it reads is free again: the call waits)
     if (rc) return rc;
     rc = sm_sync(s);                     // (a sticky SM_E_CAPACITY of this frame is still reported when the policy retires after it)
     const int rr = auto_retire_after_frame(s);
@@ -1301,6 +1338,7 @@ int sm_process_frame_async(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_
 {
     if (!s || !rgb || !pose16) { g_err = "sm_process_frame_async: null argument (rgb and pose are required)"; return SM_E_ARG; }
     HIPCK(hipSetDevice(s->cfg.device));
+    if (int rc = refuse_sharded(s)) return rc;
     const size_t P = (size_t)s->P;
     if (!s->stream_in) {                  // the copy stream and the ring, built whole before the context takes them
         Stream st;
@@ -1353,16 +1391,15 @@ int sm_process_frame_async(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_
         if (semantic) HIPCK(hipMemcpyAsync(sl.sem, semantic, P, hipMemcpyHostToDevice, s->stream_in));
     }
     // a null depth / semantic keeps the previous texture (src/SurfelMapping.cpp:124-128)
-    if (depth_mm) { s->in_last_depth = sl.depth; s->in_depth_slot = slot; }
-    if (semantic) { s->in_last_sem = sl.sem; s->in_sem_slot = slot; }
+    image_given(s, depth_mm ? sl.depth : nullptr, semantic ? sl.sem : nullptr, slot);
     HIPCK(hipEventRecord(sl.ev_in, s->stream_in));
     HIPCK(hipStreamWaitEvent(s->stream, sl.ev_in, 0));
-    rc = enqueue_frame(s, sl.rgb, s->in_last_depth ? s->in_last_depth : s->d_depth_raw, s->in_last_sem ? s->in_last_sem : s->d_sem, pose16);
+    rc = enqueue_frame(s, sl.rgb, current_depth(s), current_sem(s), pose16);
     HIPCK(hipEventRecord(sl.ev_free, s->stream));
     sl.used = true;
-    // a frame without its own depth / semantic image read another set's: that set is busy until this frame has prepared too
-    for (int o : {s->in_depth_slot, s->in_sem_slot})
-        if (o >= 0 && o != slot) { HIPCK(hipEventRecord(s->in[o].ev_free, s->stream)); s->in[o].used = true; }
+    // a frame without its own depth / semantic image read another set's
+    const int rh = hold_current_sets(s, slot);
+    if (!rc) rc = rh;
     return rc ? rc : auto_retire_after_frame(s);
 }
 
@@ -1387,7 +1424,7 @@ int sm_clean_points_ex(sm_ctx *s, const uint16_t *depth_mm, const uint8_t *seman
     int rc = finalize_if_pending(s);             // (a held-back association still reads the staging buffers' frame planes)
     if (rc) return rc;
     if ((rc = upload_inputs(s, nullptr, depth_mm, semantic))) return rc;
-    return clean_points_device(s, s->d_depth_raw, s->d_sem, pose16, exempt_first);
+    return clean_points_device(s, current_depth(s), current_sem(s), pose16, exempt_first);
 }
 
 int sm_clean_points_cb(sm_ctx *s, const uint16_t *depth_mm, const uint8_t *semantic, const float *pose16, int exempt_first,
@@ -1399,9 +1436,9 @@ int sm_clean_points_cb(sm_ctx *s, const uint16_t *depth_mm, const uint8_t *seman
     int rc = finalize_if_pending(s);
     if (rc) return rc;
     if ((rc = upload_inputs(s, nullptr, depth_mm, semantic))) return rc;
-    if (!fn) return clean_points_device(s, s->d_depth_raw, s->d_sem, pose16, exempt_first);
+    if (!fn) return clean_points_device(s, current_depth(s), current_sem(s), pose16, exempt_first);
     const std::function<long long(uint32_t)> hook = [&](uint32_t local) { return fn(user, local); };
-    return clean_points_device(s, s->d_depth_raw, s->d_sem, pose16, exempt_first, &hook);
+    return clean_points_device(s, current_depth(s), current_sem(s), pose16, exempt_first, &hook);
 }
 
 int sm_reset(sm_ctx *s)
@@ -1449,7 +1486,7 @@ int sm_set_frame(sm_ctx *s, const uint8_t *rgb, const float *depth_metric, const
     memset(&tp, 0, sizeof tp);
     ShardSettle ss;
     memset(&ss, 0, sizeof ss);
-    hipLaunchKernelGGL(k_prep, dim3(tiles), dim3(1024), 0, s->stream, s->d_rgb, (const uint16_t *)nullptr, s->d_sem,
+    hipLaunchKernelGGL(k_prep, dim3(tiles), dim3(1024), 0, s->stream, s->d_rgb, (const uint16_t *)nullptr, current_sem(s),
                        depth_metric ? s->d_depth_f32 : nullptr, depth_metric ? s->cur().depthT : nullptr, s->cur().rgbsT,
                        (uint64_t *)nullptr, fp, s->cur().dcT, (uint32_t *)nullptr, tp, ss);
     HIPCK(hipGetLastError());
@@ -1789,7 +1826,9 @@ int sm_shard_frame_device(sm_ctx *s, const uint8_t *d_rgb, const uint16_t *d_dep
     }
     FrameParams fp;
     uint32_t n_prep = 0;
-    rc = begin_frame(s, d_rgb, d_depth_mm ? d_depth_mm : s->d_depth_raw, d_semantic ? d_semantic : s->d_sem, pose16, fusing, false, &fp, &n_prep);
+    image_given(s, d_depth_mm, d_semantic, -1);          // the caller's buffers, as in sm_process_frame_device
+    rc = begin_frame(s, d_rgb, current_depth(s), current_sem(s), pose16, fusing, false, &fp, &n_prep);
+    if (rc >= 0 && hold_current_sets(s, -1)) return SM_E_HIP;
     if (rc <= 0) return rc;
     fp.compact_now = 0u;
     fp.conflict_cap = 0xFFFFFFFFu;            // applied over all ranks below (k_shard_cap_pack / k_shard_cap_repair), not per shard
@@ -1846,7 +1885,7 @@ int sm_shard_frame(sm_ctx *s, const uint8_t *rgb, const uint16_t *depth_mm, cons
     HIPCK(hipSetDevice(s->cfg.device));
     int rc = upload_inputs(s, rgb, depth_mm, semantic);
     if (rc) return rc;
-    if ((rc = sm_shard_frame_device(s, s->d_rgb, s->d_depth_raw, s->d_sem, pose16))) return rc;
+    if ((rc = sm_shard_frame_device(s, s->d_rgb, nullptr, nullptr, pose16))) return rc;      // (given or not, the current images)
     return sm_sync(s);
 }
 

@@ -664,8 +664,11 @@ struct sm_ctx {
     InSlot in[IN_RING];
     size_t in_off_depth = 0, in_off_sem = 0, in_bytes = 0;   // a frame's images as ONE block: colour | depth | class, 16-byte aligned (sm_host_alloc_frame)
     uint32_t in_next = 0;
-    const uint16_t *in_last_depth = nullptr; const uint8_t *in_last_sem = nullptr;     // device copies of the last depth / semantic image given
-    int in_depth_slot = -1, in_sem_slot = -1;                                          // ... and the input sets that hold them
+    // The reference's ONE depth and ONE class texture (src/SurfelMapping.cpp:122-128): the last image given to ANY entry point
+    // is current, a null image reads it.  Host forms that wait give into d_depth_raw / d_sem, the async form into an input set,
+    // the device forms lend the caller's buffer.  Written by image_given(), read by current_depth() / current_sem() (sm_api.hip).
+    const uint16_t *cur_depth = nullptr; const uint8_t *cur_sem = nullptr;             // null until one is given: the zeroed d_depth_raw / d_sem
+    int in_depth_slot = -1, in_sem_slot = -1;                                          // the input sets that hold them, -1: none does
     // Pinned host buffers handed out by sm_host_alloc, with their sizes: the sources sm_process_frame_async copies from in
     // place.  Caller memory is never registered: hipHostRegister / hipHostUnregister of heap ranges left the runtime treating
     // later, unrelated host arrays at the same addresses as pinned -- a GPU memory fault in whatever copied to or from them next.

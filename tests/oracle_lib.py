@@ -156,8 +156,8 @@ class Oracle:
     # -- frame level
     def process_frame(self, rgb, depth, sem, pose, allow=(0,)):
         rgb = np.ascontiguousarray(rgb, np.uint8)
-        depth = np.ascontiguousarray(depth, np.uint16)
-        sem = np.ascontiguousarray(sem, np.uint8)
+        depth = None if depth is None else np.ascontiguousarray(depth, np.uint16)      # None: the image in the texture stays
+        sem = None if sem is None else np.ascontiguousarray(sem, np.uint8)
         pose = np.ascontiguousarray(pose, np.float32)
         rc = self._L.smo_process_frame(self._h, _ptr(rgb), _ptr(depth), _ptr(sem), _ptr(pose))
         if rc not in allow:

@@ -1825,6 +1825,95 @@ int sm_ground_maps(sm_ctx *s, const sm_map_source *src, const sm_ground_params *
                    uint32_t *clear2, sm_ground_info *info);   /* every plane may be NULL; info may not */
 int sm_ground_stats(sm_ctx *s, sm_ground_stats_t *out);      /* SM_E_ARG before the first call */
 
+/* ---- routes over the ground map: cost-to-go fields and paths (DESIGN.md "4ac. Routes") ----
+ * sm_route_ground takes the `state` and `clear2` planes sm_ground_maps returned and, for each of n_fields goal sets, computes over the
+ * same nu x nv window the least cost of an 8-connected path from every cell to any goal of the set (`cost`), the direction of the
+ * first step of such a path (`next`), and for a list of starts the cells of the path that follows `next`.  It reads nothing of the
+ * model and of no file and changes nothing in the context but its own stats; it runs on the context's stream, behind frames in
+ * flight, and works on any context.
+ *   Definition, in integers (restated by tests/route_ref.py):
+ *   Window.  nu, nv in 1..4096, nu * nv <= 2^22.  Planes are row-major, row = cell v, column = cell u, as sm_ground_maps writes them.
+ *   Passable.  A cell is passable when state == FREE, or state == UNKNOWN and unknown_passable is set; and clear2 >= body_cells^2.
+ *     body_cells is the vehicle's radius.  clear2 saturates at the ground map's reach_cells^2: the caller must have asked the ground
+ *     map for reach_cells >= body_cells (and >= soft_cells for the multiplier to see that far); this call cannot check it.
+ *   Multiplier.  S2 = soft_cells^2.  m = 1 when soft_cells == 0, otherwise m = 1 + (near_weight * (S2 - min(clear2, S2))) / S2 by
+ *     integer division: 1..15, cells near obstacles cost more.
+ *   Directions.  k = 0..7 is (du, dv) = (1,0) (1,1) (0,1) (-1,1) (-1,0) (-1,-1) (0,-1) (1,-1).  L_k = 12 for even k, 17 for odd k
+ *     (17 / 12 is within 0.2 % of sqrt 2).
+ *   Edges.  The edge p -> q = p + dir_k exists when p and q are both in the window and passable; for odd k the cells (pu + du, pv)
+ *     and (pu, pv + dv) must be passable too: no path cuts a corner.  Its cost is L_k * (m[p] + m[q]).  Edges are symmetric, so the
+ *     field from the goals is the cost to them.
+ *   Goals.  Field f's goals are the pairs (u, v) goals[2 i], goals[2 i + 1] for goal_first[f] <= i < goal_first[f + 1];
+ *     goal_first[0] = 0.  n_fields >= 1, n_fields * nu * nv <= 2^26.  A passable goal has cost 0; an impassable goal contributes
+ *     nothing and is counted in info.
+ *   cost.  uint32[n_fields][nv][nu]: the shortest-path distance in that graph, SM_ROUTE_NONE where there is no path: unique.  A
+ *     shortest path visits a cell at most once and an edge costs at most 17 * 30 = 510, so cost < 510 * 2^22 < 2^31: no overflow.
+ *   next.  uint8[n_fields][nv][nu].  The first rule that applies: 8 at a cell of cost 0; 255 at an impassable or unreachable cell;
+ *     otherwise the smallest k whose edge exists and has cost[q] + w == cost[p].  A pure function of cost.
+ *   Paths.  Start i is the triple (field, u, v) starts[3 i ..].  A start whose cost is NONE has path_len 0 and path_cost NONE.
+ *     Otherwise the path is the start, then `next` repeatedly until a cell with next == 8 (cost falls strictly along it: no cycle);
+ *     path_len = min(cells on it, max_steps + 1), path_cost = cost[start] whether truncated or not.  path is
+ *     uint32[n_starts][max_steps + 1] of cell numbers v * nu + u, padded with 0xFFFFFFFF.
+ *   Info, per field: goals used and dropped, reachable cells (the goals among them), the largest cost (0 with none reachable).
+ *   Output.  cost, next, path, path_len and path_cost may each be NULL: a caller who only wants paths copies nothing else back.  A
+ *     failing call writes none of them and not info.
+ *   Example 1.  nu = nv = 3, all FREE but the centre (OBSTACLE), body_cells = soft_cells = 0, one goal (0, 0).  cost by rows is
+ *     0 24 48 / 24 NONE 72 / 48 72 96: (2, 1) is 72 and not 24 + 34, the diagonal from (1, 0) would cut the corner of the centre.
+ *     next at (2, 2) is 4: directions 4 and 6 both reach 96, the smaller wins.
+ *   Example 2.  nu = 4, nv = 1, all FREE, clear2 = 4 1 2 4, soft_cells = 2, near_weight = 8, goal u = 3.  m = 1 7 5 1,
+ *     cost = 312 216 72 0.
+ *   Cost.  One launch writes a byte m and a byte of edge bits per cell, shared by all fields.  The relaxation is tiled: a workgroup
+ *     takes one (field, tile of 32 x 32 cells) whose flag is up, relaxes it in LDS until a sweep changes nothing, writes it back and
+ *     raises the flags of the neighbouring tiles whose facing border changed.  A round is a launch; the host reads one counter of
+ *     raised flags from pinned memory every rounds_per_check rounds and stops when it is 0.  No workgroup waits for another, and the
+ *     result does not depend on the order of anything.  SM_ROUTE_TILE=16|32|64 and SM_ROUTE_SWEEPS=n (the cap on the sweeps of one
+ *     visit, default half the tile's cells; 1 is the plain global relaxation), read per call, change the schedule and not a bit of the result.
+ *     Device memory: 4 bytes a cell and field for cost, 1 for next, 7 a cell shared, allocated per call and freed when it ends.
+ * sm_route_stats: of the context's last sm_route_ground that succeeded (a call that fails leaves them as they were).
+ * Errors.  SM_E_ARG: NULLs other than the outputs named above (goals with no goal and starts with no start may be NULL); a parameter
+ *   outside the ranges below; nu * nv > 2^22, n_fields * nu * nv > 2^26 or n_starts * (max_steps + 1) > 2^26 (all refused before
+ *   anything is allocated); goal_first that does not start at 0 or falls; a goal or a start outside the window, a start's field
+ *   outside 0..n_fields - 1; SM_ROUTE_TILE or SM_ROUTE_SWEEPS set to something else; sm_route_stats before any call has succeeded.
+ *   SM_E_STALL: flags still up after max_rounds rounds (termination is a theorem -- costs are integers that only fall -- the bound
+ *   is there for bugs). */
+#define SM_ROUTE_NONE 0xFFFFFFFFu     /* `cost` of a cell no path leaves towards a goal; `path_cost` of such a start */
+typedef struct sm_route_params {
+    int32_t nu, nv;             /* cells, 1..4096 each, nu * nv <= 2^22: the planes' window              default 256 each */
+    int32_t body_cells;         /* the vehicle's radius in cells, 0..255                                 default 0 */
+    int32_t soft_cells;         /* how far from an obstacle a cell costs more, 0..255; 0: nowhere        default 0 */
+    int32_t near_weight;        /* the multiplier beside an obstacle is 1 + near_weight, 0..14           default 0 */
+    int32_t unknown_passable;   /* 0 / 1: UNKNOWN cells may be driven on                                 default 0 */
+    int32_t max_steps;          /* a path holds at most max_steps + 1 cells, 0..2^22                     default 4096 */
+    int32_t rounds_per_check;   /* rounds enqueued between two looks at the counter, 1..64               default 4 */
+    int32_t max_rounds;         /* >= 1: SM_E_STALL beyond                                               default 65536 */
+} sm_route_params;
+typedef struct sm_route_info {
+    uint32_t goals_used;        /* passable goals of the field */
+    uint32_t goals_dropped;     /* impassable ones */
+    uint32_t reachable;         /* cells with a cost */
+    uint32_t max_cost;          /* the largest of them */
+} sm_route_info;
+typedef struct sm_route_stats_t {
+    uint32_t rounds;            /* relaxation launches that found a flag up */
+    uint32_t launches;          /* every kernel launch of the call, the rounds over lowered flags included */
+    uint64_t tile_visits;       /* (field, tile) pairs relaxed, over all rounds */
+    uint32_t tile;              /* the tile edge used */
+    uint32_t sweep_cap;         /* the cap on the sweeps of one visit used */
+    float prepare_ms;           /* device: the planes' way up, the multipliers and edges, the goals */
+    float relax_ms;             /* device and the host's looks at the counter: the rounds */
+    float next_ms;              /* device: next and the info */
+    float walk_ms;              /* device: the paths */
+    float copy_ms;              /* the outputs back to the caller */
+    float total_ms;
+} sm_route_stats_t;
+int sm_default_route_params(sm_route_params *p);              /* pure, no context */
+int sm_route_ground(sm_ctx *s, const sm_route_params *p, const uint8_t *state, const uint32_t *clear2,
+                    uint32_t n_fields, const uint32_t *goal_first, const int32_t *goals /* pairs u, v */,
+                    uint32_t n_starts, const int32_t *starts /* triples field, u, v */,
+                    uint32_t *cost, uint8_t *next, uint32_t *path, uint32_t *path_len, uint32_t *path_cost,
+                    sm_route_info *info /* [n_fields] */);
+int sm_route_stats(sm_ctx *s, sm_route_stats_t *out);         /* SM_E_ARG before the first call */
+
 /* ---- scenes: a map set with moving actors in it (DESIGN.md "4w. Scenes") ----
  * Everything above replays a static world.  A scene is a map set plus actors: an actor is a map file whose records are in the
  * actor's OWN frame, with one actor->world pose per view (or sweep).  The actor files are read once per call and stay on the

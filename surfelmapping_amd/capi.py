@@ -417,7 +417,28 @@ class SmGroundStats(C.Structure):
                 ("total_ms", C.c_float)]
 
 
-LOCATE_STATUS = ("OK", "AMBIGUOUS", "NONE", "NO_TARGET", "NO_SOURCE")         # SM_LOCATE_*: sm_locate_info.status
+ROUTE_NONE = 0xFFFFFFFF                                                  # SM_ROUTE_NONE: `cost` of a cell without a path to a goal
+ROUTE_DIRS = ((1, 0), (1, 1), (0, 1), (-1, 1), (-1, 0), (-1, -1), (0, -1), (1, -1))   # (du, dv) of `next` 0..7; 8: a goal, 255: none
+ROUTE_PLANES = ("cost", "next")
+SM_E_STALL = -6
+
+
+class SmRouteParams(C.Structure):
+    _fields_ = [("nu", C.c_int32), ("nv", C.c_int32), ("body_cells", C.c_int32), ("soft_cells", C.c_int32), ("near_weight", C.c_int32),
+                ("unknown_passable", C.c_int32), ("max_steps", C.c_int32), ("rounds_per_check", C.c_int32), ("max_rounds", C.c_int32)]
+
+
+class SmRouteInfo(C.Structure):
+    _fields_ = [("goals_used", C.c_uint32), ("goals_dropped", C.c_uint32), ("reachable", C.c_uint32), ("max_cost", C.c_uint32)]
+
+
+class SmRouteStats(C.Structure):
+    _fields_ = [("rounds", C.c_uint32), ("launches", C.c_uint32), ("tile_visits", C.c_uint64), ("tile", C.c_uint32), ("sweep_cap", C.c_uint32),
+                ("prepare_ms", C.c_float), ("relax_ms", C.c_float), ("next_ms", C.c_float), ("walk_ms", C.c_float), ("copy_ms", C.c_float),
+                ("total_ms", C.c_float)]
+
+
+LOCATE_STATUS =("OK", "AMBIGUOUS", "NONE", "NO_TARGET", "NO_SOURCE")         # SM_LOCATE_*: sm_locate_info.status
 LOCATE_KINDS = ("STRUCTURE", "GROUND", "OTHER", "OUTSIDE", "LOOSE")           # the entries of its source_counts / target_counts
 
 
@@ -663,6 +684,9 @@ PROTOTYPES = {
     "sm_default_ground_params": (ci, [P(SmGroundParams)]),
     "sm_ground_maps": (ci, [vp, _SRC, P(SmGroundParams)] + [vp] * 6 + [P(SmGroundInfo)]),
     "sm_ground_stats": (ci, [vp, P(SmGroundStats)]),
+    "sm_default_route_params": (ci, [P(SmRouteParams)]),
+    "sm_route_ground": (ci, [vp, P(SmRouteParams), vp, vp, u32, vp, vp, u32, vp] + [vp] * 5 + [P(SmRouteInfo)]),
+    "sm_route_stats": (ci, [vp, P(SmRouteStats)]),
     "sm_default_locate_params": (ci, [P(SmLocateParams)]),
     "sm_locate_rotations": (ci, [P(SmLocateParams), vp]),
     "sm_locate_maps": (ci, [vp, _SRC, _SRC, P(SmLocateParams), vp, P(SmLocateInfo)]),
@@ -1099,6 +1123,54 @@ def ground_params(**over) -> SmGroundParams:
     """default_ground_params() with fields overridden; origin takes a sequence of three, ground_mask eight words or an iterable of
     the classes that may be ground (`classes=` does the latter too)"""
     return _params(SmGroundParams, "sm_default_ground_params", None, over)
+
+
+def route_params(**over) -> SmRouteParams:
+    """sm_default_route_params (256 x 256 cells, body_cells 0, soft_cells 0, near_weight 0, unknown_passable 0, max_steps 4096,
+    rounds_per_check 4, max_rounds 65536) with fields overridden"""
+    return _params(SmRouteParams, "sm_default_route_params", None, over)
+
+
+def route_ground(m, ground, goals, starts=None, max_steps=4096, planes=ROUTE_PLANES, **params) -> dict:
+    """Cost-to-go fields and paths over a ground map (sm_route_ground; tests/route_ref.py restates it).  m: a SurfelMap, whose stream
+    the call runs on.  ground: the dict ground_maps returned, or any dict with `state` uint8[nv, nu] and `clear2` uint32[nv, nu].
+    goals: a list of goal sets, each a list of (u, v): one field per set.  starts: (field, u, v) triples whose paths are wanted.
+    params: the fields of route_params() (nu and nv are the planes').  planes: which of ROUTE_PLANES to copy back.
+    Returns dict(cost: uint32[G, nv, nu], ROUTE_NONE without a path; next: uint8[G, nv, nu], an index of ROUTE_DIRS, 8 at a goal, 255
+    without; a plane not asked for is None; info: per field dict(goals_used, goals_dropped, reachable, max_cost); with starts also
+    path: uint32[n, max_steps + 1] of cell numbers v * nu + u padded with ROUTE_NONE, path_len, path_cost: uint32[n])."""
+    unknown = set(planes) - set(ROUTE_PLANES)
+    if unknown:
+        raise KeyError(sorted(unknown)[0])
+    state = np.ascontiguousarray(ground["state"], np.uint8)
+    clear2 = np.ascontiguousarray(ground["clear2"], np.uint32)
+    if state.ndim != 2 or clear2.shape != state.shape:
+        raise ValueError("route_ground: state and clear2 are planes [nv, nu] of one shape")
+    nv, nu = state.shape
+    p = route_params(nu=nu, nv=nv, max_steps=max_steps, **params)
+    G = len(goals)
+    first = np.zeros(G + 1, np.uint32)
+    first[1:] = np.cumsum([len(g) for g in goals])
+    flat = np.ascontiguousarray([uv for g in goals for uv in g], np.int32).reshape(-1, 2)
+    st = np.ascontiguousarray([] if starts is None else starts, np.int32).reshape(-1, 3)
+    n = len(st)
+    ok = G >= 1 and 1 <= nu * nv and G * nu * nv <= 1 << 26 and 0 <= p.max_steps and n * (p.max_steps + 1) <= 1 << 26   # (else the call refuses)
+    out = dict(cost=np.zeros((G, nv, nu), np.uint32) if ok and "cost" in planes else None,
+               next=np.zeros((G, nv, nu), np.uint8) if ok and "next" in planes else None)
+    if n and ok:
+        out.update(path=np.zeros((n, p.max_steps + 1), np.uint32), path_len=np.zeros(n, np.uint32), path_cost=np.zeros(n, np.uint32))
+    info = (SmRouteInfo * max(G, 1))()
+    m._chk(m._L.sm_route_ground(m._h, C.byref(p), _ptr(state), _ptr(clear2), G, _ptr(first), _ptr(flat) if len(flat) else None, n,
+                                _ptr(st) if n else None, _ptr(out["cost"]), _ptr(out["next"]), _ptr(out.get("path")), _ptr(out.get("path_len")),
+                                _ptr(out.get("path_cost")), info), "sm_route_ground")
+    out["info"] = [_as_dict(info[f]) for f in range(G)]
+    return out
+
+
+def route_stats(m) -> dict:
+    """of m's last route_ground: rounds, launches, tile_visits, tile, sweep_cap, prepare_ms, relax_ms, next_ms, walk_ms, copy_ms,
+    total_ms (sm_route_stats)"""
+    return m._stats(SmRouteStats, "sm_route_stats")
 
 
 def default_register_params() -> SmRegisterParams:

@@ -40,6 +40,53 @@ struct GroundMap {
     }
 };
 
+// Not in the reference: the routes over a ground map (sm_route_ground; DESIGN.md "4ac. Routes"): per goal set a field of nu x nv
+// cells, row-major as the ground map's planes, field after field; per start a path.
+struct RouteGoal { int u, v; };
+struct RouteStart { int field, u, v; };
+struct RouteField {
+    int nu = 0, nv = 0, fields = 0;
+    std::vector<uint32_t> cost;        // SM_ROUTE_NONE without a path to a goal
+    std::vector<uint8_t> next;         // the direction 0..7 of the first step, 8 at a goal, 255 without
+    std::vector<std::vector<uint32_t>> paths;   // per start the cells v * nu + u of its path, the start first (truncated at max_steps + 1)
+    std::vector<uint32_t> pathCost;    // per start cost[start], SM_ROUTE_NONE without a path
+    std::vector<sm_route_info> info;   // per field
+    bool ok = false;                   // false: the call failed (the error is printed) and everything is empty
+
+    // the fields of the goal sets `goals` over the planes of `g`, the paths of `starts`
+    static RouteField of(sm_ctx *ctx, const GroundMap &g, const std::vector<std::vector<RouteGoal>> &goals, const std::vector<RouteStart> &starts,
+                         sm_route_params p, const char *who)
+    {
+        RouteField r;
+        p.nu = g.nu; p.nv = g.nv;
+        const size_t G = goals.size(), n = (size_t)g.nu * (size_t)g.nv;
+        const bool fits = G >= 1 && G * n <= ((size_t)1 << 26) && p.max_steps >= 0 &&
+                          starts.size() * ((size_t)p.max_steps + 1) <= ((size_t)1 << 26);             // (else refused below)
+        std::vector<uint32_t> first(G + 1, 0u), path, len(starts.size(), 0u);
+        std::vector<int32_t> flat, st;
+        for (size_t f = 0; f < G; ++f) {
+            for (const RouteGoal &q : goals[f]) { flat.push_back(q.u); flat.push_back(q.v); }
+            first[f + 1] = (uint32_t)(flat.size() / 2);
+        }
+        for (const RouteStart &s : starts) { st.push_back(s.field); st.push_back(s.u); st.push_back(s.v); }
+        const size_t row = fits ? (size_t)p.max_steps + 1 : 0;
+        if (fits) { r.cost.assign(G * n, 0u); r.next.assign(G * n, 0); path.assign(starts.size() * row, 0u); r.pathCost.assign(starts.size(), 0u); }
+        r.info.assign(G ? G : 1, sm_route_info{});
+        (void)sm_sync(ctx);                                              // (SM_FACADE_ASYNC: frames may still be in flight)
+        if (!g.ok || sm_route_ground(ctx, &p, g.state.data(), g.clear2.data(), (uint32_t)G, first.data(), flat.data(), (uint32_t)starts.size(), st.data(),
+                                     fits ? r.cost.data() : nullptr, fits ? r.next.data() : nullptr, fits ? path.data() : nullptr, len.data(),
+                                     fits ? r.pathCost.data() : nullptr, r.info.data()) != SM_OK) {
+            std::printf("%s: %s\n", who, g.ok ? sm_last_error() : "no ground map");
+            return RouteField{};
+        }
+        for (size_t i = 0; i < starts.size(); ++i) r.paths.emplace_back(path.begin() + i * row, path.begin() + i * row + len[i]);
+        r.info.resize(G);
+        r.nu = g.nu; r.nv = g.nv; r.fields = (int)G;
+        r.ok = true;
+        return r;
+    }
+};
+
 class GlobalModel {
 public:
     explicit GlobalModel(sm_ctx *ctx = nullptr)
@@ -196,6 +243,18 @@ public:
         sm_default_ground_params(&p);
         if (params) p = *params;
         return GroundMap::of(ctx_, sm_map_source{nullptr, 0u, 1}, p, "groundMap");
+    }
+
+    // Not in the reference: routes over a ground map (sm_route_ground; DESIGN.md "4ac. Routes"): per goal set the least cost of an
+    // 8-connected path from every cell to a goal and the direction of its first step, per start the path.  params: null = the
+    // defaults; nu and nv are the ground map's.  The model is neither read nor changed.
+    RouteField routeGround(const GroundMap &ground, const std::vector<std::vector<RouteGoal>> &goals, const std::vector<RouteStart> &starts = {},
+                           const sm_route_params *params = nullptr)
+    {
+        sm_route_params p;
+        sm_default_route_params(&p);
+        if (params) p = *params;
+        return RouteField::of(ctx_, ground, goals, starts, p, "routeGround");
     }
 
     // model read-back in the reference's AoS layout (12 floats / surfel, src/Config.cpp:17-32)

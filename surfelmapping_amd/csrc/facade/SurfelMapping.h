@@ -561,6 +561,19 @@ public:
         return GroundMap::of(ctx_, src, p, "groundMaps");
     }
 
+    // Routes over a ground map (sm_route_ground; DESIGN.md "4ac. Routes"): for each goal set of `goals` the cost-to-go field over the
+    // ground map's window -- the least cost of an 8-connected path that keeps body_cells away from blocking cells and pays more near
+    // them -- and the direction of the first step; for each start (field, u, v) the cells of its path.  params: null = the defaults;
+    // nu and nv are the ground map's.  Nothing is changed.  The result's `ok` is false, with the error printed, if the call failed.
+    RouteField routeGround(const GroundMap &ground, const std::vector<std::vector<RouteGoal>> &goals, const std::vector<RouteStart> &starts = {},
+                           const sm_route_params *params = nullptr)
+    {
+        sm_route_params p;
+        sm_default_route_params(&p);
+        if (params) p = *params;
+        return RouteField::of(ctx_, ground, goals, starts, p, "routeGround");
+    }
+
     // The second sensor's dump: what a lidar `sensor` (sm_lidar_sensor; sm_default_lidar_sensor) at each of `poses` (sensor->world,
     // the camera's axes) measures in the live model, written as <path>/velodyne/%06d.bin next to acquireImages' folders, in KITTI's
     // velodyne layout: per return four floats, (z, -x, -y) of t*d in the sensor frame -- x forward, y left, z up -- and the

@@ -467,6 +467,16 @@ struct Ground {
     bool stats_valid = false;
 };
 
+// routes over the ground map (sm_route.hip, sm_k_route.h): the events, the pinned mirror of the rounds' counters and the last call's
+// stats.  The planes, the flags and the paths live for one call.
+struct Route {
+    static constexpr int N_EV = 8;     // around: the planes' way up with prepare and seed, the rounds, next, the walk
+    Event ev[N_EV];
+    Host<uint32_t> h_counters;         // pinned (set last: it marks the block complete)
+    sm_route_stats_t stats{};
+    bool stats_valid = false;
+};
+
 // locating one map set in another (sm_locate.hip, sm_k_locate.h): the tally, its pinned mirror, the events and the last call's
 // stats, the pinned buffer of a round.  The rasters, the pyramid and the search's device buffers live for one call.
 struct Locate {
@@ -773,6 +783,7 @@ struct sm_ctx {
     Rays rays;
     Scene scene;
     Points points;
+    Route route;
 };
 
 namespace sm_impl __attribute__((visibility("hidden"))) {

@@ -1914,6 +1914,113 @@ int sm_route_ground(sm_ctx *s, const sm_route_params *p, const uint8_t *state, c
                     sm_route_info *info /* [n_fields] */);
 int sm_route_stats(sm_ctx *s, sm_route_stats_t *out);         /* SM_E_ARG before the first call */
 
+/* ---- routes a car can follow: cost-to-go over (cell, heading) with a turning radius (DESIGN.md "4ad. Routes for a car") ----
+ * sm_route_ground's path belongs to a point that turns on the spot.  sm_route_car searches over states (cell, heading) with moves a
+ * car can make -- a step ahead, a turn to either side that takes turn_cells cells ahead and as many along the new heading, and
+ * (if allowed) a step back -- over the same `state` and `clear2` planes, per goal set.  Like sm_route_ground it reads nothing of the
+ * model and of no file, changes nothing in the context but its own stats, runs on the context's stream and works on any context.
+ *   Definition, in integers (restated by tests/car_ref.py):
+ *   Cells.  The window and its limits, Passable, the Multiplier m, the Directions k = 0..7 with L_k, and the unit edge p -> p + dir_k
+ *     with its existence rule (corner rule included) and its cost e_k(p) = L_k * (m[p] + m[q]) are sm_route_ground's, above, word for
+ *     word; body_cells, soft_cells, near_weight, unknown_passable, max_steps, rounds_per_check and max_rounds mean what they mean there.
+ *   States.  (u, v, h): the cell and the heading h = 0..7, which is direction k = h.  Plane index (h * nv + v) * nu + u.
+ *   Parameters.  turn_cells = n in 1..16; turn_cost in 0..4095; reverse_weight in 0..15, 0: the car cannot reverse.
+ *   Moves out of (p, h), by code:
+ *     0 F  to (p + d_h, h); exists when the unit edge p -> p + d_h exists; weight e_h(p).
+ *     1 L (s = +1), 2 R (s = -1)  h' = (h + s) & 7; the cells c_0 = p, c_i = c_(i-1) + d_h for i = 1..n, c_(n+j) = c_(n+j-1) + d_h'
+ *          for j = 1..n; exists when all 2 n unit edges along that polyline exist; weight = the sum of their costs + turn_cost;
+ *          to (c_2n, h').
+ *     3 B  only with reverse_weight > 0: to (p - d_h, h); exists when the unit edge in direction (h + 4) & 7 exists; weight
+ *          reverse_weight * e_((h+4)&7)(p).
+ *     Every weight is at most 32 * 510 + 4095 = 20 415 < 2^15.
+ *   Turning radius.  The graph is directed.  Two turns to the same side are separated by a straight run of at least 2 n cells (a
+ *     turn ends with n cells along h', the next begins with n cells along h'), so a half turn -- four turns of 45 degrees -- is
+ *     6 n cells wide (Example 2) and the turning radius is about 3 * turn_cells cells.  Derived from the moves, not measured.
+ *   Goals.  Field f's goals are the triples (u, v, h) goals[3 i ..] for goal_first[f] <= i < goal_first[f + 1], goal_first as in
+ *     sm_route_ground; h = -1 means any heading and seeds all 8 states of the cell.  A goal in an impassable cell contributes
+ *     nothing and is counted in info.  n_fields >= 1, n_fields * nu * nv <= 2^23.
+ *   cost.  uint32[n_fields][8][nv][nu]: the least total weight of a sequence of moves from the state to a goal state of the field,
+ *     0 at goal states, SM_ROUTE_NONE where there is none (or none cheaper than 2^31, below).
+ *   Range.  A candidate cost[target] + w >= 2^31 is never stored.  The result is therefore the true least cost where that is
+ *     < 2^31 and SM_ROUTE_NONE otherwise: weights are >= 0, so every state on a least-cost sequence has a true cost no larger than
+ *     the start's, and a sequence through a state whose true cost is >= 2^31 costs >= 2^31 -- dropping such candidates removes no
+ *     sequence cheaper than 2^31 and keeps every one that is.  With cq < 2^31 and w < 2^15 the sum cq + w never wraps a uint32.
+ *   next.  uint8, the shape of cost: 8 at cost 0; 255 at SM_ROUTE_NONE; otherwise the smallest move code whose move exists with
+ *     cost[target] + w == cost[state].  A pure function of cost.
+ *   Paths.  Start i is the quadruple (field, u, v, h) starts[4 i ..].  path is uint32[n_starts][max_steps + 1] of words
+ *     cell | heading << 22 | reverse << 25 with cell = v * nu + u < 2^22.  The first word is the start state with reverse 0; then
+ *     EVERY unit cell passed, move after move along `next` until a state with next == 8: F one cell with heading h; L or R its 2 n
+ *     cells, the first n with heading h, the next n with h'; B one cell with heading h and reverse 1.  A start whose cost is NONE
+ *     has path_len 0 and path_cost NONE; otherwise path_len = min(words on it, max_steps + 1) (a turn may be cut in the middle),
+ *     path_cost = cost[start] whether truncated or not; padded with 0xFFFFFFFF.
+ *   Info, per field: goals used and dropped, reachable states, reachable cells (a cost at any heading), the largest cost.
+ *   Output.  cost, next, path, path_len and path_cost may each be NULL.  A failing call writes none of them and not info.
+ *   Example 1.  nu = 5, nv = 3, all FREE, m = 1, n = 1, turn_cost 0, no reverse, goal (4, 1, -1).  cost at (0, 1) for h = 0..7 is
+ *     96 116 NONE NONE NONE NONE NONE 116: 96 is four steps of 24; the 116 at h = 1 is R (to (1, 2) for 34, to (2, 2) for 24, now
+ *     h = 0), then R again (to (3, 2) for 24, to (4, 1) for 34).  With reverse_weight = 2: 96 116 290 464 192 464 290 116.  With the
+ *     goal (4, 1, 0) and turn_cost = 5 only h = 0 has a cost, 96.
+ *   Example 2.  nu = nv = 7, all FREE, n = 1, no reverse, goal (0, 6, 4).  From (3, 0, h 0) the cost is 304: four turns of 58 that
+ *     end at (3, 6, h 4), then three steps of 24; with turn_cost = 9 it is 340.  From (2, 0, h 0) it is 280; from (4, 0, h 0) NONE:
+ *     the half turn needs three cells to the side.
+ *   Example 3.  nu = 4, nv = 1, m = 1 7 5 1 (sm_route_ground's Example 2), goal (3, 0, -1), reverse_weight = 3.  cost at h = 0 is
+ *     312 216 72 0, at h = 4 it is 936 648 216 0.
+ *   Cost.  One launch writes m and the edge bits per cell as sm_route_ground does, a second the weights of the four moves of every
+ *     state (16 bits each, 0xFFFF: the move does not exist), shared by all fields.  The relaxation is sm_route_ground's in shape: a
+ *     workgroup per (field, tile of 32 x 32 cells x 8 headings) whose flag is up, the tile's 8192 costs in LDS; what the tile's
+ *     states reach outside it (a move's target lies up to 2 n cells away) is folded once per visit into one value per state, the
+ *     sweeps run over the targets inside.  Changed states go back, and the flags of the neighbouring tiles within 2 n cells of a
+ *     changed cell are raised.  Rounds are launches, the host reads one counter every rounds_per_check rounds.  SM_CAR_TILE=16|32
+ *     (16 refused with turn_cells > 8: a tile is at least 2 n cells wide) and SM_CAR_SWEEPS=n, read per call, change the schedule
+ *     and not a bit of the result.  Device memory: 32 bytes a cell and field for cost, 8 for next, 71 a cell shared.
+ * sm_route_car_stats: of the context's last sm_route_car that succeeded.
+ * Errors.  SM_E_ARG: as sm_route_ground's, with n_fields * nu * nv > 2^23 and n_starts * (max_steps + 1) > 2^26 refused before
+ *   anything is allocated; turn_cells, turn_cost or reverse_weight outside their ranges; a goal's heading outside -1..7, a start's
+ *   outside 0..7; SM_CAR_TILE or SM_CAR_SWEEPS set to something else.  SM_E_STALL: flags still up after max_rounds rounds. */
+#define SM_CAR_MOVE_F 0
+#define SM_CAR_MOVE_L 1
+#define SM_CAR_MOVE_R 2
+#define SM_CAR_MOVE_B 3
+typedef struct sm_route_car_params {
+    int32_t nu, nv;             /* as sm_route_params                                                    default 256 each */
+    int32_t body_cells;         /* as sm_route_params                                                    default 0 */
+    int32_t soft_cells;         /* as sm_route_params                                                    default 0 */
+    int32_t near_weight;        /* as sm_route_params                                                    default 0 */
+    int32_t unknown_passable;   /* as sm_route_params                                                    default 0 */
+    int32_t turn_cells;         /* n: a turn of 45 degrees runs n cells ahead and n along the new heading, 1..16   default 2 */
+    int32_t turn_cost;          /* added to a turn's weight, 0..4095                                     default 0 */
+    int32_t reverse_weight;     /* a step back costs this many times the edge, 0..15; 0: no reverse      default 0 */
+    int32_t max_steps;          /* a path holds at most max_steps + 1 words, 0..2^22                     default 4096 */
+    int32_t rounds_per_check;   /* as sm_route_params                                                    default 4 */
+    int32_t max_rounds;         /* as sm_route_params                                                    default 65536 */
+} sm_route_car_params;
+typedef struct sm_route_car_info {
+    uint32_t goals_used;        /* goals of the field in passable cells */
+    uint32_t goals_dropped;     /* those in impassable ones */
+    uint32_t reachable_states;  /* states with a cost */
+    uint32_t reachable_cells;   /* cells with a cost at any heading */
+    uint32_t max_cost;          /* the largest cost (0 with none) */
+} sm_route_car_info;
+typedef struct sm_route_car_stats_t {
+    uint32_t rounds;            /* relaxation launches that found a flag up */
+    uint32_t launches;          /* every kernel launch of the call */
+    uint64_t tile_visits;       /* (field, tile) pairs relaxed, over all rounds */
+    uint32_t tile;              /* the tile edge used */
+    uint32_t sweep_cap;         /* the cap on the sweeps of one visit used */
+    float prepare_ms;           /* device: the planes' way up, multipliers, edges, the moves' weights, the goals */
+    float relax_ms;             /* device and the host's looks at the counter: the rounds */
+    float next_ms;              /* device: next and the info */
+    float walk_ms;              /* device: the paths */
+    float copy_ms;              /* the outputs back to the caller */
+    float total_ms;
+} sm_route_car_stats_t;
+int sm_default_route_car_params(sm_route_car_params *p);      /* pure, no context */
+int sm_route_car(sm_ctx *s, const sm_route_car_params *p, const uint8_t *state, const uint32_t *clear2,
+                 uint32_t n_fields, const uint32_t *goal_first, const int32_t *goals /* triples u, v, h */,
+                 uint32_t n_starts, const int32_t *starts /* quadruples field, u, v, h */,
+                 uint32_t *cost, uint8_t *next, uint32_t *path, uint32_t *path_len, uint32_t *path_cost,
+                 sm_route_car_info *info /* [n_fields] */);
+int sm_route_car_stats(sm_ctx *s, sm_route_car_stats_t *out);  /* SM_E_ARG before the first call */
+
 /* ---- scenes: a map set with moving actors in it (DESIGN.md "4w. Scenes") ----
  * Everything above replays a static world.  A scene is a map set plus actors: an actor is a map file whose records are in the
  * actor's OWN frame, with one actor->world pose per view (or sweep).  The actor files are read once per call and stay on the

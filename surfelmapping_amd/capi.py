@@ -438,6 +438,26 @@ class SmRouteStats(C.Structure):
                 ("total_ms", C.c_float)]
 
 
+CAR_MOVES = ("F", "L", "R", "B")                                       # SM_CAR_MOVE_*: `next` 0..3 of route_car; 8: a goal, 255: none
+
+
+class SmRouteCarParams(C.Structure):
+    _fields_ = [("nu", C.c_int32), ("nv", C.c_int32), ("body_cells", C.c_int32), ("soft_cells", C.c_int32), ("near_weight", C.c_int32),
+                ("unknown_passable", C.c_int32), ("turn_cells", C.c_int32), ("turn_cost", C.c_int32), ("reverse_weight", C.c_int32),
+                ("max_steps", C.c_int32), ("rounds_per_check", C.c_int32), ("max_rounds", C.c_int32)]
+
+
+class SmRouteCarInfo(C.Structure):
+    _fields_ = [("goals_used", C.c_uint32), ("goals_dropped", C.c_uint32), ("reachable_states", C.c_uint32), ("reachable_cells", C.c_uint32),
+                ("max_cost", C.c_uint32)]
+
+
+class SmRouteCarStats(C.Structure):
+    _fields_ = [("rounds", C.c_uint32), ("launches", C.c_uint32), ("tile_visits", C.c_uint64), ("tile", C.c_uint32), ("sweep_cap", C.c_uint32),
+                ("prepare_ms", C.c_float), ("relax_ms", C.c_float), ("next_ms", C.c_float), ("walk_ms", C.c_float), ("copy_ms", C.c_float),
+                ("total_ms", C.c_float)]
+
+
 LOCATE_STATUS =("OK", "AMBIGUOUS", "NONE", "NO_TARGET", "NO_SOURCE")         # SM_LOCATE_*: sm_locate_info.status
 LOCATE_KINDS = ("STRUCTURE", "GROUND", "OTHER", "OUTSIDE", "LOOSE")           # the entries of its source_counts / target_counts
 
@@ -687,6 +707,9 @@ PROTOTYPES = {
     "sm_default_route_params": (ci, [P(SmRouteParams)]),
     "sm_route_ground": (ci, [vp, P(SmRouteParams), vp, vp, u32, vp, vp, u32, vp] + [vp] * 5 + [P(SmRouteInfo)]),
     "sm_route_stats": (ci, [vp, P(SmRouteStats)]),
+    "sm_default_route_car_params": (ci, [P(SmRouteCarParams)]),
+    "sm_route_car": (ci, [vp, P(SmRouteCarParams), vp, vp, u32, vp, vp, u32, vp] + [vp] * 5 + [P(SmRouteCarInfo)]),
+    "sm_route_car_stats": (ci, [vp, P(SmRouteCarStats)]),
     "sm_default_locate_params": (ci, [P(SmLocateParams)]),
     "sm_locate_rotations": (ci, [P(SmLocateParams), vp]),
     "sm_locate_maps": (ci, [vp, _SRC, _SRC, P(SmLocateParams), vp, P(SmLocateInfo)]),
@@ -1171,6 +1194,60 @@ def route_stats(m) -> dict:
     """of m's last route_ground: rounds, launches, tile_visits, tile, sweep_cap, prepare_ms, relax_ms, next_ms, walk_ms, copy_ms,
     total_ms (sm_route_stats)"""
     return m._stats(SmRouteStats, "sm_route_stats")
+
+
+def route_car_params(**over) -> SmRouteCarParams:
+    """sm_default_route_car_params (route_params()'s defaults, turn_cells 2, turn_cost 0, reverse_weight 0) with fields overridden"""
+    return _params(SmRouteCarParams, "sm_default_route_car_params", None, over)
+
+
+def route_car(m, ground, goals, starts=None, max_steps=4096, planes=ROUTE_PLANES, **params) -> dict:
+    """Cost-to-go over (cell, heading) and paths a car can follow (sm_route_car; tests/car_ref.py restates it).  m, ground, planes: as
+    route_ground's.  goals: a list of goal sets, each a list of (u, v, h), h = -1: any heading; one field per set.  starts:
+    (field, u, v, h) quadruples whose paths are wanted.  params: the fields of route_car_params() (nu and nv are the planes').
+    Returns dict(cost: uint32[G, 8, nv, nu] by heading, ROUTE_NONE without a way to a goal; next: uint8[G, 8, nv, nu], an index of
+    CAR_MOVES, 8 at a goal, 255 without; a plane not asked for is None; info: per field dict(goals_used, goals_dropped,
+    reachable_states, reachable_cells, max_cost); with starts also path: uint32[n, max_steps + 1] of words (car_path_cells splits
+    them) padded with ROUTE_NONE, path_len, path_cost: uint32[n])."""
+    unknown = set(planes) - set(ROUTE_PLANES)
+    if unknown:
+        raise KeyError(sorted(unknown)[0])
+    state = np.ascontiguousarray(ground["state"], np.uint8)
+    clear2 = np.ascontiguousarray(ground["clear2"], np.uint32)
+    if state.ndim != 2 or clear2.shape != state.shape:
+        raise ValueError("route_car: state and clear2 are planes [nv, nu] of one shape")
+    nv, nu = state.shape
+    p = route_car_params(nu=nu, nv=nv, max_steps=max_steps, **params)
+    G = len(goals)
+    first = np.zeros(G + 1, np.uint32)
+    first[1:] = np.cumsum([len(g) for g in goals])
+    flat = np.ascontiguousarray([uvh for g in goals for uvh in g], np.int32).reshape(-1, 3)
+    st = np.ascontiguousarray([] if starts is None else starts, np.int32).reshape(-1, 4)
+    n = len(st)
+    ok = G >= 1 and 1 <= nu * nv and G * nu * nv <= 1 << 23 and 0 <= p.max_steps and n * (p.max_steps + 1) <= 1 << 26   # (else the call refuses)
+    out = dict(cost=np.zeros((G, 8, nv, nu), np.uint32) if ok and "cost" in planes else None,
+               next=np.zeros((G, 8, nv, nu), np.uint8) if ok and "next" in planes else None)
+    if n and ok:
+        out.update(path=np.zeros((n, p.max_steps + 1), np.uint32), path_len=np.zeros(n, np.uint32), path_cost=np.zeros(n, np.uint32))
+    info = (SmRouteCarInfo * max(G, 1))()
+    m._chk(m._L.sm_route_car(m._h, C.byref(p), _ptr(state), _ptr(clear2), G, _ptr(first), _ptr(flat) if len(flat) else None, n,
+                             _ptr(st) if n else None, _ptr(out["cost"]), _ptr(out["next"]), _ptr(out.get("path")), _ptr(out.get("path_len")),
+                             _ptr(out.get("path_cost")), info), "sm_route_car")
+    out["info"] = [_as_dict(info[f]) for f in range(G)]
+    return out
+
+
+def route_car_stats(m) -> dict:
+    """of m's last route_car: rounds, launches, tile_visits, tile, sweep_cap, prepare_ms, relax_ms, next_ms, walk_ms, copy_ms,
+    total_ms (sm_route_car_stats)"""
+    return m._stats(SmRouteCarStats, "sm_route_car_stats")
+
+
+def car_path_cells(path_row):
+    """(cell, heading, reverse) of the words of one row of route_car's `path`, the padding dropped: cell = v * nu + u"""
+    w = np.asarray(path_row, np.uint32)
+    w = w[w != ROUTE_NONE]
+    return w & 0x3FFFFF, (w >> 22) & 7, (w >> 25) & 1
 
 
 def default_register_params() -> SmRegisterParams:

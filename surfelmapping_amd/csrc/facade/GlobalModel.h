@@ -87,6 +87,57 @@ struct RouteField {
     }
 };
 
+// Not in the reference: the routes a car can follow over a ground map (sm_route_car; DESIGN.md "4ad. Routes for a car"): per goal set
+// a field of 8 x nv x nu states, heading after heading, field after field; per start the path words.
+struct CarGoal { int u, v, h; };       // h = -1: any heading
+struct CarStart { int field, u, v, h; };
+struct CarField {
+    int nu = 0, nv = 0, fields = 0;
+    std::vector<uint32_t> cost;        // SM_ROUTE_NONE without a way to a goal
+    std::vector<uint8_t> next;         // the move SM_CAR_MOVE_* of the first step, 8 at a goal, 255 without
+    std::vector<std::vector<uint32_t>> paths;   // per start the words cell | heading << 22 | reverse << 25 of its path, the start first
+    std::vector<uint32_t> pathCost;    // per start cost[start], SM_ROUTE_NONE without a path
+    std::vector<sm_route_car_info> info;   // per field
+    bool ok = false;                   // false: the call failed (the error is printed) and everything is empty
+
+    static uint32_t cell(uint32_t word) { return word & 0x3FFFFFu; }
+    static int heading(uint32_t word) { return (int)(word >> 22 & 7u); }
+    static bool reverse(uint32_t word) { return (word >> 25 & 1u) != 0; }
+
+    // the fields of the goal sets `goals` over the planes of `g`, the paths of `starts`
+    static CarField of(sm_ctx *ctx, const GroundMap &g, const std::vector<std::vector<CarGoal>> &goals, const std::vector<CarStart> &starts,
+                       sm_route_car_params p, const char *who)
+    {
+        CarField r;
+        p.nu = g.nu; p.nv = g.nv;
+        const size_t G = goals.size(), n = (size_t)g.nu * (size_t)g.nv;
+        const bool fits = G >= 1 && G * n <= ((size_t)1 << 23) && p.max_steps >= 0 &&
+                          starts.size() * ((size_t)p.max_steps + 1) <= ((size_t)1 << 26);             // (else refused below)
+        std::vector<uint32_t> first(G + 1, 0u), path, len(starts.size(), 0u);
+        std::vector<int32_t> flat, st;
+        for (size_t f = 0; f < G; ++f) {
+            for (const CarGoal &q : goals[f]) { flat.push_back(q.u); flat.push_back(q.v); flat.push_back(q.h); }
+            first[f + 1] = (uint32_t)(flat.size() / 3);
+        }
+        for (const CarStart &s : starts) { st.push_back(s.field); st.push_back(s.u); st.push_back(s.v); st.push_back(s.h); }
+        const size_t row = fits ? (size_t)p.max_steps + 1 : 0;
+        if (fits) { r.cost.assign(G * 8 * n, 0u); r.next.assign(G * 8 * n, 0); path.assign(starts.size() * row, 0u); r.pathCost.assign(starts.size(), 0u); }
+        r.info.assign(G ? G : 1, sm_route_car_info{});
+        (void)sm_sync(ctx);                                              // (SM_FACADE_ASYNC: frames may still be in flight)
+        if (!g.ok || sm_route_car(ctx, &p, g.state.data(), g.clear2.data(), (uint32_t)G, first.data(), flat.data(), (uint32_t)starts.size(), st.data(),
+                                  fits ? r.cost.data() : nullptr, fits ? r.next.data() : nullptr, fits ? path.data() : nullptr, len.data(),
+                                  fits ? r.pathCost.data() : nullptr, r.info.data()) != SM_OK) {
+            std::printf("%s: %s\n", who, g.ok ? sm_last_error() : "no ground map");
+            return CarField{};
+        }
+        for (size_t i = 0; i < starts.size(); ++i) r.paths.emplace_back(path.begin() + i * row, path.begin() + i * row + len[i]);
+        r.info.resize(G);
+        r.nu = g.nu; r.nv = g.nv; r.fields = (int)G;
+        r.ok = true;
+        return r;
+    }
+};
+
 class GlobalModel {
 public:
     explicit GlobalModel(sm_ctx *ctx = nullptr)
@@ -255,6 +306,18 @@ public:
         sm_default_route_params(&p);
         if (params) p = *params;
         return RouteField::of(ctx_, ground, goals, starts, p, "routeGround");
+    }
+
+    // Not in the reference: routes a car can follow (sm_route_car; DESIGN.md "4ad. Routes for a car"): per goal set the least weight
+    // of a sequence of car moves from every (cell, heading) to a goal state and the first move, per start the path.  params: null =
+    // the defaults; nu and nv are the ground map's.  The model is neither read nor changed.
+    CarField routeCar(const GroundMap &ground, const std::vector<std::vector<CarGoal>> &goals, const std::vector<CarStart> &starts = {},
+                      const sm_route_car_params *params = nullptr)
+    {
+        sm_route_car_params p;
+        sm_default_route_car_params(&p);
+        if (params) p = *params;
+        return CarField::of(ctx_, ground, goals, starts, p, "routeCar");
     }
 
     // model read-back in the reference's AoS layout (12 floats / surfel, src/Config.cpp:17-32)

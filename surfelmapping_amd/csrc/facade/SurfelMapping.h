@@ -574,6 +574,20 @@ public:
         return RouteField::of(ctx_, ground, goals, starts, p, "routeGround");
     }
 
+    // Routes a car can follow over a ground map (sm_route_car; DESIGN.md "4ad. Routes for a car"): for each goal set of `goals` the
+    // cost-to-go over (cell, heading) -- the least weight of a sequence of steps ahead, turns of 45 degrees that take turn_cells
+    // cells before and after, and steps back where reverse_weight allows them -- and the first move; for each start (field, u, v, h)
+    // the words of its path, every unit cell passed.  params: null = the defaults; nu and nv are the ground map's.  Nothing is
+    // changed.  The result's `ok` is false, with the error printed, if the call failed.
+    CarField routeCar(const GroundMap &ground, const std::vector<std::vector<CarGoal>> &goals, const std::vector<CarStart> &starts = {},
+                      const sm_route_car_params *params = nullptr)
+    {
+        sm_route_car_params p;
+        sm_default_route_car_params(&p);
+        if (params) p = *params;
+        return CarField::of(ctx_, ground, goals, starts, p, "routeCar");
+    }
+
     // The second sensor's dump: what a lidar `sensor` (sm_lidar_sensor; sm_default_lidar_sensor) at each of `poses` (sensor->world,
     // the camera's axes) measures in the live model, written as <path>/velodyne/%06d.bin next to acquireImages' folders, in KITTI's
     // velodyne layout: per return four floats, (z, -x, -y) of t*d in the sensor frame -- x forward, y left, z up -- and the

@@ -477,6 +477,15 @@ struct Route {
     bool stats_valid = false;
 };
 
+// routes a car can follow (sm_car.hip, sm_k_car.h): as Route.  The moves' weights, the costs, the flags and the paths live for one call.
+struct Car {
+    static constexpr int N_EV = 8;     // around: the planes' way up with prepare and seed, the rounds, next, the walk
+    Event ev[N_EV];
+    Host<uint32_t> h_counters;         // pinned (set last: it marks the block complete)
+    sm_route_car_stats_t stats{};
+    bool stats_valid = false;
+};
+
 // locating one map set in another (sm_locate.hip, sm_k_locate.h): the tally, its pinned mirror, the events and the last call's
 // stats, the pinned buffer of a round.  The rasters, the pyramid and the search's device buffers live for one call.
 struct Locate {
@@ -784,6 +793,7 @@ struct sm_ctx {
     Scene scene;
     Points points;
     Route route;
+    Car car;
 };
 
 namespace sm_impl __attribute__((visibility("hidden"))) {

@@ -18,44 +18,14 @@
 // Every index is checked against the window before it is used.  Nothing is ever added to ROUTE_NONE.
 #pragma once
 
-#include "sm_device.h"
+#include "sm_d_route.h"
 
 namespace sm {
 
-constexpr uint32_t ROUTE_NONE = 0xFFFFFFFFu;             // SM_ROUTE_NONE
-constexpr int ROUTE_NEXT_GOAL = 8, ROUTE_NEXT_NONE = 255;
-constexpr int ROUTE_FREE = 1, ROUTE_UNKNOWN = 0;         // the ground map's states that may be passable
 // the info words of a field: goals used, goals dropped, reachable cells, largest cost
 enum { ROUTE_I_USED = 0, ROUTE_I_DROPPED, ROUTE_I_REACHED, ROUTE_I_MAX, ROUTE_INFO_WORDS };
 // the counter block: tile visits, then per round of a batch the flags it raised for the next
 enum { ROUTE_C_VISITS = 0, ROUTE_C_SEEDED = 1, ROUTE_C_ROUND0 = 2, ROUTE_MAX_BATCH = 64, ROUTE_COUNTER_WORDS = ROUTE_C_ROUND0 + ROUTE_MAX_BATCH };
-
-struct RouteArgs {
-    int nu, nv;
-    int body2;                         // body_cells^2
-    int S2, near_weight;               // soft_cells^2 (0: every multiplier is 1)
-    int unknown_passable;
-    int T, tu, tv;                     // the tile edge; tiles along u and v
-    int sweeps;                        // the cap on the sweeps of one visit
-};
-
-__device__ __forceinline__ int route_du(int k) { return (k == 0 || k == 1 || k == 7) ? 1 : (k >= 3 && k <= 5) ? -1 : 0; }
-__device__ __forceinline__ int route_dv(int k) { return (k >= 1 && k <= 3) ? 1 : (k >= 5) ? -1 : 0; }
-__device__ __forceinline__ uint32_t route_len(int k) { return (k & 1) ? 17u : 12u; }
-
-// the multiplier of a cell inside the window, 0 if it is impassable
-__device__ __forceinline__ uint32_t route_m(const RouteArgs &a, const uint8_t *state, const uint32_t *clear2, int u, int v)
-{
-    if (u < 0 || v < 0 || u >= a.nu || v >= a.nv) return 0u;
-    const size_t c = (size_t)v * a.nu + u;
-    const int st = state[c];
-    if (!(st == ROUTE_FREE || (st == ROUTE_UNKNOWN && a.unknown_passable))) return 0u;
-    const uint32_t c2 = clear2[c];
-    if (c2 < (uint32_t)a.body2) return 0u;
-    if (a.S2 == 0) return 1u;
-    const uint32_t lim = c2 < (uint32_t)a.S2 ? c2 : (uint32_t)a.S2;
-    return 1u + ((uint32_t)a.near_weight * ((uint32_t)a.S2 - lim)) / (uint32_t)a.S2;
-}
 
 __global__ void __launch_bounds__(256) k_route_prepare(RouteArgs a, const uint8_t *__restrict__ state, const uint32_t *__restrict__ clear2,
                                                        uint8_t *__restrict__ m, uint8_t *__restrict__ edge)
@@ -65,17 +35,7 @@ __global__ void __launch_bounds__(256) k_route_prepare(RouteArgs a, const uint8_
     if (c >= N) return;
     const int u = (int)(c % a.nu), v = (int)(c / a.nu);
     const uint32_t mp = route_m(a, state, clear2, u, v);
-    uint32_t e = 0;
-    if (mp) {
-        uint32_t pass = 0;             // bit k: the neighbour in direction k is in the window and passable
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-            if (route_m(a, state, clear2, u + route_du(k), v + route_dv(k))) pass |= 1u << k;
-        e = pass & 0x55u;
-#pragma unroll
-        for (int k = 1; k < 8; k += 2)                   // a diagonal needs both cells beside it: k - 1 and k + 1 are those
-            if ((pass >> k & 1u) && (pass >> (k - 1) & 1u) && (pass >> ((k + 1) & 7) & 1u)) e |= 1u << k;
-    }
+    const uint32_t e = route_edge_bits(a, state, clear2, u, v, mp);
     m[c] = (uint8_t)mp;
     edge[c] = (uint8_t)e;
 }
